@@ -321,8 +321,8 @@ def configs4_record(lnb, args):
 
 
 def _c_getenv(name):
-    """the process environment as the C runtime sees it (liblnb_hip.so sets a default GPU_MAX_HW_QUEUES=16 while it is loaded: os.environ is a
-    snapshot taken at interpreter start and does not show it)"""
+    """the process environment as the C runtime sees it (os.environ is a snapshot taken at interpreter start and misses what native code
+    changed since)"""
     import ctypes
     g = ctypes.CDLL(None).getenv
     g.restype = ctypes.c_char_p
@@ -636,7 +636,12 @@ def main():
                     help="exact (default, headline): the reference's k-ordered chains, token-identical to the CPU path; "
                          "fast: split-K / bf16-MFMA tolerance mode (opt-in, measured distance in NOTES.md 6.2)")
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)   # launcher check without a GPU: every rank reports its environment and exits
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed repeat returned to its caller (the K greedy token ids) as DIR/decode_tokens.npy "
+                         "(float64; the single-GPU path only)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("LNB_FORCE_PIPELINE") == "1"):
+        ap.error("--dump-outputs covers the single-GPU path only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)                        # `python bench.py --gpus N` as ONE plain command: this process becomes the launcher
@@ -720,6 +725,11 @@ def main():
         if reps[-1][2] != reps[0][2]:
             sys.stderr.write("PARITY FAILURE: repeat %d of the timed region produced different tokens\n" % rep)
             sys.exit(3)
+    if args.dump_outputs:
+        # what decode_greedy handed its caller in the last timed repeat: K token ids (exact in float64).  The model (fill_synthetic(1234)) and
+        # the prompt (synth_tokens(99, P)) are seeded, so the same arguments give the same inputs on every run and every build
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "decode_tokens.npy"), np.asarray(reps[-1][2], dtype=np.float64))
     # fused-RMSNorm rows of the decode steps so far (2 per block + 1 per token) whose sum left the branch-free item walk (same bits, slower walk)
     n_norm_rows = (W + K * len(reps)) * (2 * cfg["n_layers"] + 1)
     norm_walk = {"rows": n_norm_rows, "fallback_rows": ctx.norm_fallbacks(), "note": "rows summed by the record walk instead of the branch-free item list (more than 64 items or non-finite terms; round 6: a leaf too close to a binade edge is replayed as single-term items inside the list)"} if args.mode == "exact" else None

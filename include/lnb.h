@@ -50,19 +50,18 @@ int lnb_abi_version(void);
 const char* lnb_last_error(void);
 int lnb_device_count(int* out_count);
 /* Runtime facts a host needs before it trusts a run with SEVERAL contexts in flight (one InferenceContext per generation, one goroutine each:
- * src/inference/inference.go:163-174).  The HIP runtime spreads a process's streams over GPU_MAX_HW_QUEUES hardware queues (default 4) and
- * streams that share a queue serialise; while it is being loaded this library exports 16 unless the host set a value or LNB_KEEP_HW_QUEUES=1 --
- * but the runtime reads the variable at ITS initialisation, so a host that used HIP before loading the library keeps its 4 queues (two
- * contexts in flight then run slower than one).  hw_queues_measured (probe_queues != 0, 4-20 ms): streams that really ran concurrently.
+ * src/inference/inference.go:163-174).  The HIP runtime spreads a process's streams over a fixed number of hardware queues (its default: 4,
+ * read from the process environment when the runtime initialises) and streams that share a queue serialise; the library leaves that setting
+ * to the host.  hw_queues_measured (probe_queues != 0, 4-20 ms): streams that really ran concurrently.
  * A host warns when contexts in flight > min(hw_queues_expected, hw_queues_measured or expected) (bench.py, go/inferencecontext_hip.go do). */
 typedef struct lnb_runtime_info_t {
     int32_t abi_version;
     int32_t device, n_cus;
     int32_t shader_clock_khz, memory_clock_khz, wall_clock_khz;   /* hipDeviceAttributeClockRate / MemoryClockRate / WallClockRate */
     int32_t hw_queues_env;                 /* GPU_MAX_HW_QUEUES in the process environment now (0: unset = the runtime's default 4) */
-    int32_t hw_queues_set_by_library;      /* 1: the value is this library's load-time default */
-    int32_t hip_initialised_before_load;   /* 1: /dev/kfd was already open when the library was loaded: the runtime had read the variable before */
-    int32_t hw_queues_expected;            /* what the runtime will have honoured given the three fields above */
+    int32_t hw_queues_set_by_library;      /* always 0: the library sets no default (kept for the ABI) */
+    int32_t hip_initialised_before_load;   /* 1: /dev/kfd was already open when the library was loaded (HIP was in use before) */
+    int32_t hw_queues_expected;            /* what the runtime will have honoured: hw_queues_env, or 4 when unset */
     int32_t hw_queues_measured;            /* probe: 32 spinning one-wave kernels on 32 streams ran in 32 / this many rounds (0: not probed) */
     float   probe_ms;
     char    device_name[64];

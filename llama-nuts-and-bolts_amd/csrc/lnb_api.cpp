@@ -55,17 +55,12 @@ hipError_t lnbk_gemm_stream(const GemmParams* p, int epi, int num_cus, hipStream
 hipError_t lnbk_spin(int us, hipStream_t st);
 }
 
-// The HIP runtime spreads a process's streams over GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a queue run one after the
-// other.  This library gives every context its own stream precisely so that several generations overlap on one GPU (one InferenceContext per
-// generation, inference.go:174; 2N contexts per pipeline rank): with the default, two contexts can land on ONE queue (2 in flight: 218 instead of
-// 278 tokens/s) and eight share four (306 instead of 337 tokens/s; profiles/r05_hw_queues.log).  The runtime reads the variable when it initialises
-// -- at the first HIP call of the process -- so a default set while this library is being loaded is in time unless the host has used HIP before;
-// a value the host exported wins.
-// Round 6: the default is opt-out (LNB_KEEP_HW_QUEUES=1 leaves the environment alone), what happened is recorded, and
-// lnb_runtime_info() reports it -- including whether the HIP runtime had ALREADY been initialised when this library was loaded (a host that touched
-// HIP first silently keeps 4 queues: 2 contexts in flight then run SLOWER than one) and, on request, the number of streams that really run
-// concurrently (measured, not read from the environment).
-static int g_hwq_set_by_library = 0;      // 1: this library put "16" into the environment
+// The HIP runtime spreads a process's streams over a fixed number of hardware queues (its default: 4) and streams that share a queue run one
+// after the other.  This library gives every context its own stream so that several generations can overlap on one GPU (one InferenceContext
+// per generation, inference.go:174; 2N contexts per pipeline rank); how many really overlap is up to the process environment, which the library
+// leaves alone.  lnb_runtime_info() reports what the environment asks for, whether the HIP runtime had ALREADY been initialised when this library
+// was loaded and, on request, the number of streams that really run concurrently (measured, not read from the environment).
+static int g_hwq_set_by_library = 0;      // always 0: the library no longer sets a default (the ABI field stays)
 static int g_hip_live_at_load = 0;        // 1: /dev/kfd was already open when the library was loaded -> the runtime read the variable before us
 static bool kfd_is_open() {
     // the ROCm runtime (HSA) opens /dev/kfd when it initialises, never before: an open descriptor on it = HIP has been used in this process
@@ -84,11 +79,8 @@ static bool kfd_is_open() {
     closedir(d);
     return found;
 }
-__attribute__((constructor)) static void lnb_default_hw_queues() {
+__attribute__((constructor)) static void lnb_record_hip_state_at_load() {
     g_hip_live_at_load = kfd_is_open() ? 1 : 0;
-    const char* keep = getenv("LNB_KEEP_HW_QUEUES");
-    if (keep && *keep && atoi(keep) != 0) return;
-    if (!getenv("GPU_MAX_HW_QUEUES")) { setenv("GPU_MAX_HW_QUEUES", "16", 0); g_hwq_set_by_library = 1; }
 }
 
 static thread_local char g_err[1024] = "";
@@ -257,9 +249,8 @@ extern "C" int lnb_runtime_info(int device, int probe_queues, lnb_runtime_info_t
     out->hw_queues_env = q && *q ? atoi(q) : 0;
     out->hw_queues_set_by_library = g_hwq_set_by_library;
     out->hip_initialised_before_load = g_hip_live_at_load;
-    // what the runtime will have honoured: the environment's value unless HIP was live before this library could set it (then the runtime's default, 4,
-    // unless the HOST had exported a value -- which it read at its own initialisation)
-    out->hw_queues_expected = (g_hip_live_at_load && g_hwq_set_by_library) ? 4 : (out->hw_queues_env > 0 ? out->hw_queues_env : 4);
+    // what the runtime will have honoured: the environment's value, else the runtime's default, 4
+    out->hw_queues_expected = out->hw_queues_env > 0 ? out->hw_queues_env : 4;
     if (probe_queues) {
         constexpr int NSTREAM = 32, SPIN_US = 2000;      // (2 ms per spin: the ~0.3 ms it takes the host to launch on 32 streams must not count as a round)
         hipStream_t sts[NSTREAM] = {}; hipEvent_t e0 = nullptr, e1 = nullptr, ej[NSTREAM] = {};

@@ -131,11 +131,7 @@ func (ic *InferenceContext) attach(lt *LlamaTransformer) error {
 		var ri C.lnb_runtime_info_t
 		if C.lnb_runtime_info(0, 0, &ri) == 0 && nctx > int(ri.hw_queues_expected) && !queueWarned {
 			queueWarned = true
-			why := ""
-			if ri.hip_initialised_before_load != 0 && ri.hw_queues_set_by_library != 0 {
-				why = " (HIP was initialised before liblnb_hip.so was loaded: export GPU_MAX_HW_QUEUES=16 before the process starts)"
-			}
-			common.GLogger.ConsolePrintf("warning: %d inference contexts on %d hardware queues: their steps will serialise%s", nctx, int(ri.hw_queues_expected), why)
+			common.GLogger.ConsolePrintf("warning: %d inference contexts on %d hardware queues: their steps will serialise", nctx, int(ri.hw_queues_expected))
 		}
 	}
 	// Nothing pins the Go object: the reference creates one context per generation and never closes it (inference.go:174), so the

@@ -229,9 +229,7 @@ def queue_warning(contexts_in_flight, info):
     q = info.get("hw_queues_measured") or info.get("hw_queues_expected") or 4
     if contexts_in_flight <= q:
         return None
-    why = (" -- HIP had been initialised before liblnb_hip.so was loaded, so its GPU_MAX_HW_QUEUES=16 default came too late: export the variable "
-           "before the process starts" if info.get("hip_initialised_before_load") and info.get("hw_queues_set_by_library") else "")
-    return "%d contexts in flight on %d hardware queues: streams that share a queue run one after the other%s" % (contexts_in_flight, q, why)
+    return "%d contexts in flight on %d hardware queues: streams that share a queue run one after the other" % (contexts_in_flight, q)
 
 
 def can_access_peer(device, peer):

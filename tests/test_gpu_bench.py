@@ -56,6 +56,26 @@ def test_single_gpu_bench_prints_one_json_line_with_the_contract_keys(mode):
         assert "sequences_in_flight_batched" not in d
 
 
+def test_dump_outputs_writes_the_timed_steps_tokens_and_repeats(tmp_path):
+    """--dump-outputs DIR: the K token ids of the last timed repeat as float64, the same from run to run (seeded inputs)"""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--model", "tiny", "--steps", "10", "--warmup", "2", "--prompt-len", "16", "--cpu-steps", "0",
+           "--concurrent", "0", "--batch-sizes=", "--profile-iters", "2", "--no-traffic-probe"]
+    got = []
+    for run in range(2):
+        out = tmp_path / ("run%d" % run)
+        r = subprocess.run(cmd + ["--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+        assert d["steps"] == 10 and d["ms_per_step"] > 0
+        assert sorted(os.listdir(out)) == ["decode_tokens.npy"]
+        a = np.load(out / "decode_tokens.npy")
+        assert a.dtype == np.float64 and a.shape == (10,) and (a == np.round(a)).all() and (a >= 0).all() and (a < 1024).all()
+        assert [int(t) for t in a[-4:]] == d["last_tokens"]
+        got.append(a)
+    assert (got[0] == got[1]).all()
+
+
 def test_bench_gpus_2_as_a_plain_command_on_one_gpu_with_gloo():
     """the driver's N-GPU command line -- `python bench.py --gpus N --steps K --warmup W`, no launcher -- on a one-GPU box: the two ranks
     bench.py spawns share GPU 0 and exchange through gloo (LNB_PIPELINE_BACKEND=gloo; RCCL wants one GPU per rank)"""

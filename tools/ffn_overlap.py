@@ -50,7 +50,6 @@ runs = [("w2 as ONE quad_perm chain wave + 4 helpers (LNB_RW_W2=16 LNB_W2_QUAD=1
         ("throughput forms, no priority, w2 launched first", {"FFN_SCHED": "throughput", "FFN_DELAYS": "-1,-10"}),
         ("latency forms (production, 75 + 104 KB of LDS: cannot co-reside)", {"FFN_SCHED": "latency", "FFN_DELAYS": "0,25"}),
         ("throughput forms (75 + 57 KB: one workgroup of each fits a CU)", {"FFN_SCHED": "throughput", "FFN_PADS": "0,28672"}),
-        ("throughput forms, 4 hardware queues (the runtime's default)", {"FFN_SCHED": "throughput", "GPU_MAX_HW_QUEUES": "4", "FFN_DELAYS": "0,25"}),
         ("band order on one chain wave (LNB_RW_W13=28), throughput forms", {"FFN_SCHED": "throughput", "LNB_RW_W13": "28", "FFN_DELAYS": "0,25"})]
 for label, env in runs:
     r = subprocess.run([sys.executable, os.path.abspath(__file__), "child"], capture_output=True, text=True, env=dict(os.environ, **env), timeout=900)
