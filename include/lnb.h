@@ -194,6 +194,45 @@ int lnb_decode_greedy(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int
 int lnb_ctx_set_stop_ids(lnb_ctx* c, const int32_t* ids, int n);
 int lnb_decode_greedy_until(lnb_ctx* c, int32_t token, int start_pos, int max_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out);
 
+/* ---- token probabilities: how likely each generated (or given) token was, exactly as the reference's own Softmax gives it ----------
+ * For one logits row x[0..V) (bf16 values widened to f32: what lnb_forward returns -- the reference's Forward, llamatransformer.go:170-177):
+ *   Z       = sum_{j ascending} exp(f64(x_j)) in f64: ml.Softmax's serial rowExpSum (operations_impl.go:478-511);
+ *   prob(j) = float32(exp(f64(x_j)) / Z): BIT-IDENTICAL to the oracle's orc_softmax_f32 of that row with its default exp (the host C
+ *             library's; the device looks exp up in a 65536-entry table built on the host with it, once per model);
+ *   top-k   = candidates are the values ml.Argmax can select (operations_impl.go:529-541: strict '<' from -MaxFloat32): not NaN and strictly
+ *             greater than -MaxFloat32; value descending, lowest index first on ties.  Entry 0 is the ml.Argmax token -- the generated one.
+ *             Fewer than k candidates: the missing entries have id -1, logit NaN, prob NaN;
+ *   log_z   = ln Z in f64 from a sum in any order: |log_z - ln Z| <= (V + 8) 2^-52 (about 3e-11 at V = 128256).  logit - log_z is a
+ *             log-probability that stays usable where prob underflows f32.
+ * Non-finite rows give what orc_softmax_f32 gives: an x above 709.78 makes Z = +inf (other entries 0, the overflowing one NaN); a NaN
+ * anywhere makes Z and every prob NaN; top-k ids follow the candidate rule.  In the tolerance mode (lnb_ctx_set_mode) the same kernel runs
+ * on that mode's logits; bit-identity to the oracle is claimed for the exact mode only.  None of this changes which token is generated.
+ *
+ * lnb_ctx_set_token_probs: top_k 0..LNB_MAX_TOP_K (0, the default: nothing is recorded and the captured decode step is the plain one).
+ *   Whole-model contexts only; drops the context's captured decode graphs; refused while the context belongs to a live batch.  Every step
+ *   of lnb_decode_greedy[_until] / lnb_batch_decode[_until] then records its token's row: a device log of seq_len x top_k records beside the
+ *   token log (a batch needs all members at one top_k).  Pipeline ticks refuse such contexts.
+ * lnb_ctx_read_token_probs: records [first, first + n) of the last lnb_decode_greedy[_until] or lnb_batch_decode[_until] call that ran the
+ *   context (for a batch: read each member context).  ids / logits / probs: [n * k], log_z: [n], k = the top_k that call ran with;
+ *   ids[i * k] == out_tokens[i].  Fails if that call ran with top_k 0 or first + n exceeds the tokens it generated (n_generated of _until).
+ * lnb_ctx_token_prob_walks: rows (decode steps, scored rows) of this context that walked the serial sum (the certified estimate of Z could
+ *   not settle one of their reported probabilities; DESIGN.md "Token probabilities").
+ * lnb_forward_score: lnb_forward (same work, errors and KV effects, the same argmax_last_out) with the head on every row; instead of the
+ *   logits, for each row i with 0 <= targets[i] < V: target_logit[i], target_prob[i] = prob(targets[i]) of row i, and log_z[i].  A row with
+ *   targets[i] < 0 reports NaN logit and prob (log_z is still reported); targets[i] >= V is an error.  Scoring a text: targets = tokens[1:]
+ *   followed by the next token or -1.
+ * lnb_op_token_probs: the same kernel on host rows [rows][V] (a test aid, as lnb_op_argmax): ids / logits / probs [rows * top_k] (may be
+ *   NULL when top_k is 0), log_z [rows]; targets (optional) -> target_prob [rows]; force_serial: every row walks the serial sum (the fallback
+ *   gives the same bits); *serial_walks (optional) = rows that walked. */
+#define LNB_MAX_TOP_K 16
+int lnb_ctx_set_token_probs(lnb_ctx* c, int top_k);
+int lnb_ctx_read_token_probs(lnb_ctx* c, int first, int n, int32_t* ids, float* logits, float* probs, double* log_z);
+int lnb_ctx_token_prob_walks(lnb_ctx* c, int* out);
+int lnb_forward_score(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, const int32_t* targets,
+                      float* target_logit, float* target_prob, double* log_z, int32_t* argmax_last_out);
+int lnb_op_token_probs(int device, const uint16_t* logits_bf16, int rows, int V, int top_k, const int32_t* targets,
+                       int force_serial, int32_t* ids, float* logits, float* probs, float* target_prob, double* log_z, int* serial_walks);
+
 /* ---- batched exact decode: several generations per pass over the weights ----------------------------------
  * The reference runs one generation per InferenceContext (src/inference/inference.go:174) and shares the weight matrix across the rows of a
  * call (src/ml/operations_lineartransform.go:173-193).  A batch groups 1..128 contexts of ONE whole-model handle; per step, every

@@ -20,6 +20,7 @@
 #include "../../include/lnb.h"
 #include "lnb_device.h"
 #include "lnb_rccl.h"
+static_assert(LNB_MAX_TOP_K == LNB_TOKPROB_MAX_K, "lnb.h and lnb_device.h disagree on the largest top-k");
 
 extern "C" {
 hipError_t lnbk_gemv(const GemvParams* p, int rw, int nch, int epi, int norm, hipStream_t st);
@@ -53,6 +54,7 @@ hipError_t lnbk_batch_advance(const BatchTab* tab, hipStream_t st);
 hipError_t lnbk_batch_prepare(void);
 hipError_t lnbk_gemm_stream(const GemmParams* p, int epi, int num_cus, hipStream_t st);
 hipError_t lnbk_spin(int us, hipStream_t st);
+hipError_t lnbk_token_probs(const TokProbParams* p, hipStream_t st);
 }
 
 // The HIP runtime spreads a process's streams over a fixed number of hardware queues (its default: 4) and streams that share a queue run one
@@ -121,6 +123,7 @@ struct lnb_model {
     std::vector<LayerW> layers;           // indexed by absolute layer id - layer_begin
     std::map<std::string, TensorRef> tensors;
     float* cis = nullptr; int cis_rows = 0; float* silu = nullptr; double* exp_tab = nullptr;
+    double* prob_etab = nullptr;          // exp(double(bf16)) of the host C library for all 65536 patterns: the token probabilities (token_probs_kernel)
     std::vector<float> cis_host;
     hipStream_t stream = nullptr;
     bool finalized = false;
@@ -169,6 +172,13 @@ struct lnb_ctx {
     int call_T = 0;                        // start_pos + rows of the call being enqueued (0: not known to the host, e.g. inside a replayed graph)
     hipEvent_t ev_h2d = nullptr; bool h2d_pending = false;   // the last copy out of the pinned staging words h_io[2..] (enqueue-only paths)
     bool recv_unmatched = false;           // in-process transport: a receive into this context is posted and its sender has not arrived yet
+    // token probabilities of the greedy loop (lnb_ctx_set_token_probs): a record log of dout_cap x top_k beside the token log
+    int top_k = 0;
+    TokProbOut* tp_out = nullptr;          // device: this context's log (st = c->st: the record slot is the token's)
+    int32_t* tp_ids = nullptr; float* tp_logit = nullptr; float* tp_prob = nullptr; double* tp_logz = nullptr;
+    double* tp_zpart = nullptr; uint64_t* tp_kpart = nullptr; unsigned* tp_cnt = nullptr;   // one row's partials, arrival ticket
+    int tp_last_k = 0, tp_last_n = 0;      // what the last decode call that ran this context recorded (k 0: nothing)
+    void* sc_buf = nullptr; size_t sc_bytes = 0;   // lnb_forward_score's scratch, grown on demand
 };
 // Every path that rewrites the device-side StepState goes through here, so that the pipeline tick's "the graph left pos+1 behind, skip
 // the set_state launch" shortcut (dev_pos) can never act on a position some OTHER entry point has since overwritten (lnb_forward,
@@ -431,6 +441,7 @@ extern "C" int lnb_model_destroy(lnb_model* m) {
     if (m->cis) hipFree(m->cis);
     if (m->silu) hipFree(m->silu);
     if (m->exp_tab) hipFree(m->exp_tab);
+    if (m->prob_etab) hipFree(m->prob_etab);
     if (m->stream) hipStreamDestroy(m->stream);
     delete m;
     return 0;
@@ -544,6 +555,10 @@ static void build_rope_table(int head_dim, int rows, double theta, bool scaled, 
     }
 }
 
+static void prob_exp_table(std::vector<double>& et) {
+    et.resize(1 << 16);
+    for (int i = 0; i < (1 << 16); i++) et[i] = std::exp((double)bf_wide_h((uint16_t)i));
+}
 extern "C" int lnb_model_finalize(lnb_model* m, int rope_rows) {
     if (!m) return fail("null argument");
     HIPCHK(hipSetDevice(m->device));
@@ -557,6 +572,11 @@ extern "C" int lnb_model_finalize(lnb_model* m, int rope_rows) {
     for (int i = 0; i < (1 << 16); i++) { double x = (double)bf_wide_h((uint16_t)i); silu[i] = (float)(x / (1.0 + std::exp(-x))); }
     if (!m->silu) HIPCHK(hipMalloc((void**)&m->silu, silu.size() * 4));
     HIPCHK(hipMemcpy(m->silu, silu.data(), silu.size() * 4, hipMemcpyHostToDevice));
+    // token probabilities: exp(double(bf16)) with the host C library's exp, the oracle's (orc_softmax_f32) by construction
+    std::vector<double> et;
+    prob_exp_table(et);
+    if (!m->prob_etab) HIPCHK(hipMalloc((void**)&m->prob_etab, et.size() * 8));
+    HIPCHK(hipMemcpy(m->prob_etab, et.data(), et.size() * 8, hipMemcpyHostToDevice));
     if (!m->exp_tab) HIPCHK(hipMalloc((void**)&m->exp_tab, (size_t)(1 << 16) * 8));
     HIPCHK(lnbk_exp_table(m->exp_tab, bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim))), m->stream));   // (attn_mfma_kernel)
     HIPCHK(hipStreamSynchronize(m->stream));
@@ -632,6 +652,12 @@ static int ctx_alloc(lnb_ctx* c) {
     return 0;
 }
 
+static void tp_free(lnb_ctx* c) {
+    hipFree(c->tp_out); hipFree(c->tp_ids); hipFree(c->tp_logit); hipFree(c->tp_prob); hipFree(c->tp_logz);
+    hipFree(c->tp_zpart); hipFree(c->tp_kpart); hipFree(c->tp_cnt);
+    c->tp_out = nullptr; c->tp_ids = nullptr; c->tp_logit = nullptr; c->tp_prob = nullptr; c->tp_logz = nullptr;
+    c->tp_zpart = nullptr; c->tp_kpart = nullptr; c->tp_cnt = nullptr;
+}
 extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
     if (!c) return 0;
     // a batch bakes its members' device pointers (state words, token words, caches) into its tables and captured graphs: freeing a member
@@ -645,6 +671,7 @@ extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
     if (c->ev_sent) hipEventDestroy(c->ev_sent);
     if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
     hipFree(c->e_buf); hipFree(c->z_part); hipFree(c->zseq_count); hipFree(c->attn_cnt); if (c->score_idx) hipFree(c->score_idx);
+    tp_free(c); if (c->sc_buf) hipFree(c->sc_buf);
     for (auto p : c->ck) if (p) hipFree(p);
     for (auto p : c->cv) if (p) hipFree(p);
     hipFree(c->st); hipFree(c->dtok); hipFree(c->dnext); hipFree(c->derr); hipFree(c->dout);
@@ -978,7 +1005,23 @@ extern "C" int lnb_forward_stage_end(lnb_ctx* c, int32_t* argmax_last_out) {
     return 0;
 }
 
+// token_probs_kernel over `rows` logits rows (lnb_device.h: TokProbParams)
+static TokProbParams tp_params(const lnb_model* m, const uint16_t* logits, int rows, int k, double* zpart, uint64_t* kpart, unsigned* cnt,
+                               const TokProbOut* out, int per_row_out) {
+    TokProbParams p{};
+    p.logits = logits; p.V = m->a.vocab_size; p.rows = rows; p.k = k; p.G = lnb_tokprob_slices(rows); p.etab = m->prob_etab;
+    p.zpart = zpart; p.kpart = kpart; p.cnt = cnt; p.out = out; p.per_row_out = per_row_out;
+    return p;
+}
+
+// lnb_forward_score: per row, the target's logit and probability and the row's ln Z, on the device instead of the logits copy
+struct ScoreReq { const int32_t* targets; float* tlogit; float* tprob; double* log_z; };
+static int forward_stage_impl(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out, const ScoreReq* sc);
 extern "C" int lnb_forward_stage(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out) {
+    return forward_stage_impl(c, tokens, seq, start_pos, logits_out, argmax_last_out, nullptr);
+}
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+static int forward_stage_impl(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out, const ScoreReq* sc) {
     if (!c) return fail("null argument");
     lnb_model* m = c->m; const int V = m->a.vocab_size;
     HIPCHK(hipSetDevice(m->device));
@@ -995,8 +1038,9 @@ extern "C" int lnb_forward_stage(lnb_ctx* c, const int32_t* tokens, int seq, int
         HIPCHK(lnbk_embed(m->tok_embd, c->dtok, c->x, seq, m->a.dim, V, c->derr, st));       // Fwd_Get_Rows :118
     }
     if (enqueue_layers(c, seq, true)) return -1;
-    if (m->last() && (logits_out || argmax_last_out)) {
-        const int rows = logits_out ? seq : 1;
+    TokProbOut so{};                                         // (lives until the synchronise below: its copy to the device is asynchronous)
+    if (m->last() && (logits_out || argmax_last_out || sc)) {
+        const int rows = (logits_out || sc) ? seq : 1;
         if (rows > c->logits_rows) {
             HIPCHK(hipStreamSynchronize(st));
             // the captured decode graph has the old buffer baked into its head GEMV / argmax nodes: drop it with the buffer
@@ -1004,7 +1048,7 @@ extern "C" int lnb_forward_stage(lnb_ctx* c, const int32_t* tokens, int seq, int
             hipFree(c->logits); c->logits = nullptr; c->logits_rows = 0;
             HIPCHK(hipMalloc((void**)&c->logits, (size_t)rows * V * 2)); c->logits_rows = rows;
         }
-        if (enqueue_head(c, logits_out ? 0 : seq - 1, rows)) return -1;
+        if (enqueue_head(c, rows == seq ? 0 : seq - 1, rows)) return -1;
         HIPCHK(lnbk_argmax(c->logits + (size_t)(rows - 1) * V, V, c->dnext, c->st, c->dout, c->dout_cap, 0, st));   // inference.go:207-211
         if (logits_out) {
             std::vector<uint16_t> hb((size_t)rows * V);
@@ -1013,11 +1057,44 @@ extern "C" int lnb_forward_stage(lnb_ctx* c, const int32_t* tokens, int seq, int
             for (size_t i = 0; i < hb.size(); i++) logits_out[i] = bf_wide_h(hb[i]);              // output.ToFloat32() :175
         }
         if (argmax_last_out) HIPCHK(hipMemcpyAsync(argmax_last_out, c->dnext, 4, hipMemcpyDeviceToHost, st));
+        if (sc) {
+            // scratch: [out record][partial sums rows x G][tickets][targets][target logits][target probs][ln Z]
+            const size_t R = (size_t)rows;
+            const size_t o_z = align256(sizeof(TokProbOut)), o_cnt = o_z + align256(R * LNB_TOKPROB_MAX_G * 8), o_tg = o_cnt + align256(R * 4), o_tl = o_tg + align256(R * 4),
+                         o_tp = o_tl + align256(R * 4), o_lz = o_tp + align256(R * 4), need = o_lz + align256(R * 8);
+            if (need > c->sc_bytes) {
+                HIPCHK(hipStreamSynchronize(st));
+                if (c->sc_buf) { hipFree(c->sc_buf); c->sc_buf = nullptr; c->sc_bytes = 0; }
+                HIPCHK(hipMalloc(&c->sc_buf, need)); c->sc_bytes = need;
+            }
+            char* b = (char*)c->sc_buf;
+            so.log_z = (double*)(b + o_lz); so.walks = c->zseq_count + 2;
+            HIPCHK(hipMemcpyAsync(b, &so, sizeof so, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemsetAsync(b + o_cnt, 0, R * 4, st));
+            HIPCHK(hipMemcpyAsync(b + o_tg, sc->targets, R * 4, hipMemcpyHostToDevice, st));
+            TokProbParams p = tp_params(m, c->logits, rows, 0, (double*)(b + o_z), nullptr, (unsigned*)(b + o_cnt), (const TokProbOut*)b, 0);
+            p.targets = (const int32_t*)(b + o_tg); p.tlogit = (float*)(b + o_tl); p.tprob = (float*)(b + o_tp);
+            HIPCHK(lnbk_token_probs(&p, st));
+            HIPCHK(hipMemcpyAsync(sc->tlogit, b + o_tl, R * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(sc->tprob, b + o_tp, R * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(sc->log_z, b + o_lz, R * 8, hipMemcpyDeviceToHost, st));
+        }
     }
     if (tokens) HIPCHK(hipMemcpyAsync(c->h_io + 1, c->derr, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (tokens && c->h_io[1]) return fail("token id at index %d is outside the vocabulary", c->h_io[1] - 1);
     return 0;
+}
+
+// lnb_forward with the head on every row and, instead of the logits, each row's target logit / probability and ln Z (include/lnb.h)
+extern "C" int lnb_forward_score(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, const int32_t* targets,
+                                 float* target_logit, float* target_prob, double* log_z, int32_t* argmax_last_out) {
+    if (!c || !tokens || !targets || !target_logit || !target_prob || !log_z) return fail("null argument");
+    if (!c->m->first() || !c->m->last()) return fail("lnb_forward_score needs a whole-model handle");
+    for (int i = 0; i < seq; i++)
+        if (targets[i] >= c->m->a.vocab_size) return fail("target id %d at index %d is outside the vocabulary (a negative id: no target)", targets[i], i);
+    const ScoreReq sc{targets, target_logit, target_prob, log_z};
+    return forward_stage_impl(c, tokens, seq, start_pos, nullptr, argmax_last_out, &sc);
 }
 
 extern "C" int lnb_forward(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out) {
@@ -1026,7 +1103,7 @@ extern "C" int lnb_forward(lnb_ctx* c, const int32_t* tokens, int seq, int start
     return lnb_forward_stage(c, tokens, seq, start_pos, logits_out, argmax_last_out);
 }
 
-// one decode step = embed(token on device) -> layers -> head -> argmax that feeds the next step
+// one decode step = embed(token on device) -> layers -> head -> [token probabilities] -> argmax that feeds the next step
 static int enqueue_decode_step(lnb_ctx* c) {
     lnb_model* m = c->m;
     // LNB_MEASURE_SKIP_TOKEN_KERNELS=1 (timing only, the tokens are garbage): the step without its embedding gather and argmax launches =
@@ -1035,6 +1112,10 @@ static int enqueue_decode_step(lnb_ctx* c) {
     if (!skip) HIPCHK(lnbk_embed(m->tok_embd, c->dtok, c->x, 1, m->a.dim, m->a.vocab_size, c->derr, c->stream));
     if (enqueue_layers(c, 1, false)) return -1;
     if (enqueue_head(c, 0, 1)) return -1;
+    if (c->top_k > 0 && !skip) {                             // the record of the token the argmax below appends (it reads the slot before the argmax advances it)
+        TokProbParams p = tp_params(m, c->logits, 1, c->top_k, c->tp_zpart, c->tp_kpart, c->tp_cnt, c->tp_out, 0);
+        HIPCHK(lnbk_token_probs(&p, c->stream));
+    }
     if (!skip) HIPCHK(lnbk_argmax(c->logits, m->a.vocab_size, c->dtok, c->st, c->dout, c->dout_cap, 1, c->stream));
     return 0;
 }
@@ -1049,6 +1130,55 @@ extern "C" int lnb_ctx_set_stop_ids(lnb_ctx* c, const int32_t* ids, int n) {
     HIPCHK(lnbk_set_stop(c->st, ids, n, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->n_stop = n;
+    return 0;
+}
+// Token probabilities of the greedy loop (include/lnb.h): top_k records per generated token, kept on the device beside the token log.
+// 0 (default) enqueues nothing: the captured step is exactly the one without the feature.
+extern "C" int lnb_ctx_set_token_probs(lnb_ctx* c, int top_k) {
+    if (!c) return fail("null argument");
+    if (top_k < 0 || top_k > LNB_MAX_TOP_K) return fail("top_k must be 0..%d (got %d)", LNB_MAX_TOP_K, top_k);
+    if (!c->m->first() || !c->m->last()) return fail("token probabilities need a whole-model handle (pipeline stages are not supported)");
+    if (c->batch_users > 0) return fail("context is a member of %d live batch(es): its top-k is fixed until they are destroyed", c->batch_users);
+    HIPCHK(hipSetDevice(c->m->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    drop_graphs(c);
+    tp_free(c);
+    c->top_k = 0; c->tp_last_k = 0; c->tp_last_n = 0;
+    if (top_k == 0) return 0;
+    const size_t n = (size_t)c->dout_cap * top_k, G = LNB_TOKPROB_MAX_G;
+    HIPCHK(hipMalloc((void**)&c->tp_ids, n * 4)); HIPCHK(hipMalloc((void**)&c->tp_logit, n * 4)); HIPCHK(hipMalloc((void**)&c->tp_prob, n * 4));
+    HIPCHK(hipMalloc((void**)&c->tp_logz, (size_t)c->dout_cap * 8));
+    HIPCHK(hipMalloc((void**)&c->tp_zpart, G * 8)); HIPCHK(hipMalloc((void**)&c->tp_kpart, G * LNB_TOKPROB_MAX_K * 8));
+    HIPCHK(hipMalloc((void**)&c->tp_cnt, 16)); HIPCHK(hipMemsetAsync(c->tp_cnt, 0, 16, c->stream));
+    TokProbOut o{}; o.st = c->st; o.ids = c->tp_ids; o.logit = c->tp_logit; o.prob = c->tp_prob; o.log_z = c->tp_logz; o.walks = c->zseq_count + 2; o.cap = c->dout_cap;
+    HIPCHK(hipMalloc((void**)&c->tp_out, sizeof o));
+    HIPCHK(hipMemcpyAsync(c->tp_out, &o, sizeof o, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                 // (o is stack memory)
+    c->top_k = top_k;
+    return 0;
+}
+extern "C" int lnb_ctx_read_token_probs(lnb_ctx* c, int first, int n, int32_t* ids, float* logits, float* probs, double* log_z) {
+    if (!c || !ids || !logits || !probs || !log_z) return fail("null argument");
+    if (c->tp_last_k <= 0) return fail("the last decode call of this context recorded no token probabilities (lnb_ctx_set_token_probs)");
+    if (first < 0 || n < 0 || first + n > c->tp_last_n)
+        return fail("records [%d, %d) requested: the last decode call generated %d tokens", first, first + n, c->tp_last_n);
+    if (n == 0) return 0;
+    const size_t k = c->tp_last_k, off = (size_t)first * k, cnt = (size_t)n * k;
+    HIPCHK(hipSetDevice(c->m->device));
+    HIPCHK(hipMemcpyAsync(ids, c->tp_ids + off, cnt * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(logits, c->tp_logit + off, cnt * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(probs, c->tp_prob + off, cnt * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(log_z, c->tp_logz + first, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+// rows (decode steps, scored rows) of this context whose token probabilities walked the reference's serial sum
+extern "C" int lnb_ctx_token_prob_walks(lnb_ctx* c, int* out) {
+    if (!c || !out) return fail("null argument");
+    HIPCHK(hipSetDevice(c->m->device));
+    HIPCHK(hipMemcpyAsync(c->h_io, c->zseq_count + 2, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *out = c->h_io[0];
     return 0;
 }
 static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out);
@@ -1089,6 +1219,7 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     const bool any_short = !want_long_attention(c, 1, start_pos), any_long = want_long_attention(c, 1, start_pos + n_steps - 1);
     if (use_graph && any_short && capture(&c->graph, false)) return -1;
     if (use_graph && any_long && capture(&c->graph_long, true)) return -1;
+    c->tp_last_k = 0; c->tp_last_n = 0;
     HIPCHK(hipMemcpyAsync(c->dtok, &token, 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(c->derr, 0, 4, st));
     // (the argmax kernel advances the position on the device from here on.)  Stop ids are compared only on behalf of a caller that learns how far
@@ -1111,6 +1242,7 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     if (ms_out) HIPCHK(hipEventElapsedTime(ms_out, c->ev0, c->ev1));
     if (c->h_io[1]) return fail("generated token id is outside the vocabulary");
     if (n_generated) { *n_generated = hs.n_out; if (finished) *finished = hs.finished; c->dev_pos = -1; }     // (a stopped run leaves the device position short of start_pos + n_steps)
+    c->tp_last_k = c->top_k; c->tp_last_n = n_generated ? hs.n_out : n_steps;
     return 0;
 }
 
@@ -1319,6 +1451,8 @@ struct lnb_batch {
     // as a captured graph, events towards / from the exchange stream (as lnb_ctx has them for single-sequence ticks)
     int32_t* ring = nullptr; hipGraphExec_t stage_graph = nullptr;
     hipEvent_t ev_done = nullptr, ev_in = nullptr, ev_sent = nullptr; bool in_pending = false, sent_pending = false, recv_unmatched = false;
+    // token probabilities (the members' lnb_ctx_set_token_probs, one top_k for all): one row per sequence into its context's log
+    int top_k = 0; TokProbOut* tp_out = nullptr; double* tp_zpart = nullptr; uint64_t* tp_kpart = nullptr; unsigned* tp_cnt = nullptr;
 };
 static int m16_copy(lnb_model* m, const TiledDesc& t, int rows, uint16_t** out) {
     const size_t bytes = m16_elems(rows, t.k, t.nch) * 2;
@@ -1368,6 +1502,7 @@ extern "C" int lnb_batch_destroy(lnb_batch* b) {
     if (b->graph) hipGraphExecDestroy(b->graph);
     hipFree(b->tab); hipFree(b->kv); hipFree(b->x); hipFree(b->h); hipFree(b->xt); hipFree(b->q); hipFree(b->att_xt); hipFree(b->ffn_xt); hipFree(b->logits);
     hipFree(b->derr); hipFree(b->d_tokens); hipFree(b->d_pos); hipFree(b->ring);
+    hipFree(b->tp_out); hipFree(b->tp_zpart); hipFree(b->tp_kpart); hipFree(b->tp_cnt);
     if (b->stage_graph) hipGraphExecDestroy(b->stage_graph);
     if (b->ev_done) hipEventDestroy(b->ev_done);
     if (b->ev_in) hipEventDestroy(b->ev_in);
@@ -1403,6 +1538,19 @@ static int batch_alloc(lnb_batch* b) {
     HIPCHK(hipMalloc((void**)&b->derr, 16)); HIPCHK(hipMemsetAsync(b->derr, 0, 16, b->stream));
     HIPCHK(hipMalloc((void**)&b->d_tokens, LNB_BATCH_MAX * 4)); HIPCHK(hipMalloc((void**)&b->d_pos, LNB_BATCH_MAX * 4));
     HIPCHK(hipMalloc((void**)&b->ring, LNB_BATCH_MAX * 4)); HIPCHK(hipMemsetAsync(b->ring, 0, LNB_BATCH_MAX * 4, b->stream));
+    std::vector<TokProbOut> to(b->top_k > 0 ? n : 0);
+    if (b->top_k > 0) {
+        const size_t G = (size_t)lnb_tokprob_slices(n);
+        for (int s = 0; s < n; s++) {
+            const lnb_ctx* c = b->ctxs[s];
+            to[s].st = c->st; to[s].ids = c->tp_ids; to[s].logit = c->tp_logit; to[s].prob = c->tp_prob; to[s].log_z = c->tp_logz;
+            to[s].walks = c->zseq_count + 2; to[s].cap = c->dout_cap;
+        }
+        HIPCHK(hipMalloc((void**)&b->tp_out, n * sizeof(TokProbOut)));
+        HIPCHK(hipMemcpyAsync(b->tp_out, to.data(), n * sizeof(TokProbOut), hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipMalloc((void**)&b->tp_zpart, n * LNB_TOKPROB_MAX_G * 8)); HIPCHK(hipMalloc((void**)&b->tp_kpart, n * G * b->top_k * 8));
+        HIPCHK(hipMalloc((void**)&b->tp_cnt, n * 4)); HIPCHK(hipMemsetAsync(b->tp_cnt, 0, n * 4, b->stream));
+    }
     HIPCHK(hipStreamSynchronize(b->stream));
     return 0;
 }
@@ -1415,6 +1563,8 @@ extern "C" int lnb_batch_create(lnb_ctx* const* ctxs, int n, lnb_batch** out) {
         if (ctxs[s]->m != ctxs[0]->m) return fail("context %d belongs to another model handle", s);
         for (int r = 0; r < s; r++) if (ctxs[r] == ctxs[s]) return fail("context %d appears twice in the batch", s);
         if (ctxs[s]->mode != LNB_MODE_EXACT) return fail("context %d is in the tolerance mode: batched decode is exact-order only", s);
+        if (ctxs[s]->top_k != ctxs[0]->top_k)
+            return fail("context %d records top-%d token probabilities, context 0 top-%d: a batch needs one setting", s, ctxs[s]->top_k, ctxs[0]->top_k);
     }
     lnb_model* m = ctxs[0]->m;
     HIPCHK(hipSetDevice(m->device));
@@ -1428,7 +1578,7 @@ extern "C" int lnb_batch_create(lnb_ctx* const* ctxs, int n, lnb_batch** out) {
         HIPCHK(lnbk_batch_prepare());
     }
     lnb_batch* b = new lnb_batch();
-    b->m = m; b->n = n; b->ctxs.assign(ctxs, ctxs + n); b->rows_form = !m->batch_enabled;
+    b->m = m; b->n = n; b->ctxs.assign(ctxs, ctxs + n); b->rows_form = !m->batch_enabled; b->top_k = ctxs[0]->top_k;
     for (int s = 0; s < n; s++) {
         if (ctxs[s]->seq_len > ctxs[s]->attn_short_cap) {
             const int sl = ctxs[s]->seq_len, cap = ctxs[s]->attn_short_cap; delete b;
@@ -1581,6 +1731,10 @@ static int enqueue_batch_step(lnb_batch* b, bool ring_in = false) {
         for (int k = K_QKV; k <= K_W2; k++) if (enqueue_batch_kernel(b, l, k)) return -1;
     if (m->last()) {
         if (enqueue_batch_kernel(b, 0, K_HEAD)) return -1;
+        if (b->top_k > 0) {                                  // (ticks refuse such batches: only lnb_batch_decode[_until] gets here with it)
+            TokProbParams p = tp_params(m, b->logits, b->n, b->top_k, b->tp_zpart, b->tp_kpart, b->tp_cnt, b->tp_out, 1);
+            HIPCHK(lnbk_token_probs(&p, b->stream));
+        }
         HIPCHK(lnbk_batch_argmax(b->logits, m->a.vocab_size, b->tab, b->n, b->ring, b->stream));
     } else HIPCHK(lnbk_batch_advance(b->tab, b->stream));
     return 0;
@@ -1615,6 +1769,7 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
         HIPCHK(hipStreamSynchronize(c->stream));             // whatever the context's own stream still does to its caches comes first
         c->dev_pos = -1; c->call_T = 0;                      // the batch advances the context's device-side position by itself
     }
+    for (lnb_ctx* c : b->ctxs) { c->tp_last_k = 0; c->tp_last_n = 0; }
     hipStream_t st = b->stream;
     const bool use_graph = env_int("LNB_NO_GRAPH", 0) == 0;
     if (use_graph && !b->graph) {
@@ -1647,6 +1802,7 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     if (ms_out) HIPCHK(hipEventElapsedTime(ms_out, b->ev0, b->ev1));
     if (b->h_io[2 * LNB_BATCH_MAX]) return fail("sequence %d: generated token id is outside the vocabulary", b->h_io[2 * LNB_BATCH_MAX] - 1);
     for (int s = 0; s < (int)hs.size(); s++) { n_generated[s] = hs[s].n_out; if (finished) finished[s] = hs[s].finished; }
+    for (int s = 0; s < b->n; s++) { b->ctxs[s]->tp_last_k = b->top_k; b->ctxs[s]->tp_last_n = n_generated ? n_generated[s] : n_steps; }
     return 0;
 }
 // what a batched tick exchanges, for a host layer that moves it itself (lnb_pipeline_init_host)
@@ -1683,6 +1839,8 @@ extern "C" int lnb_batch_set_state(lnb_batch* b, const int32_t* tokens, const in
         if (tokens && (tokens[s] < 0 || tokens[s] >= b->m->a.vocab_size)) return fail("sequence %d: token id at index 0 is outside the vocabulary", s);
         // only the LAST stage's argmax sees a stop id: the other stages would go on advancing their positions, re-embedding the stale ring token
         // and appending KV rows behind the stop.  Stop ids in a multi-stage batched pipeline belong to the host: it reads the tokens.
+        if (c->top_k > 0 && !one_stage)
+            return fail("sequence %d: its context records token probabilities, which pipeline stages do not support (lnb_ctx_set_token_probs(ctx, 0))", s);
         if (c->n_stop > 0 && !one_stage)
             return fail("sequence %d: its context carries %d stop ids, which a batched tick of a multi-stage pipeline cannot honour (only the last stage sees the "
                         "token): clear them (lnb_ctx_set_stop_ids(ctx, NULL, 0)) and end the sequence on the host", s, c->n_stop);
@@ -1949,6 +2107,7 @@ extern "C" int lnb_pipeline_tick(lnb_pipe* p, lnb_ctx* run, int run_rows, int ru
     if (p->host && (send || recv)) return fail("this pipe has no transport (lnb_pipeline_init_host): the host layer moves lnb_ctx_hidden_ptr's buffers itself; send and recv must be NULL");
     if (token_slot_out) *token_slot_out = -1;
     if (run) {
+        if (run->top_k > 0) return fail("the context records token probabilities, which pipeline ticks do not support (lnb_ctx_set_token_probs(ctx, 0))");
         if (check_call(run, run_rows, run_pos)) return -1;
         if (run_tokens && !first) return fail("tokens given to a stage that does not own tok_embeddings");
         if (!run_tokens && first && run_rows != 1) return fail("the first stage needs host tokens for a multi-row step");
@@ -2036,6 +2195,7 @@ extern "C" int lnb_pipeline_tick_batch(lnb_pipe* p, lnb_batch* run, lnb_batch* s
     if (p->host && (send || recv)) return fail("this pipe has no transport (lnb_pipeline_init_host): the host layer moves lnb_batch_boundary_ptr's buffers itself; send and recv must be NULL");
     if (token_slot_out) *token_slot_out = -1;
     if (run) {
+        if (run->top_k > 0) return fail("the batch's contexts record token probabilities, which pipeline ticks do not support (lnb_ctx_set_token_probs(ctx, 0))");
         hipStream_t st = run->stream;
         if (run->recv_unmatched) return fail("in-process pipeline: this batch's input has been requested but the sending stage has not posted it yet "
                                              "(the mailbox transport needs the stages ticked in lock-step order from one thread)");
@@ -2224,6 +2384,50 @@ extern "C" int lnb_op_argmax(int device, const uint16_t* logits_bf16, int n, int
     if (e == hipSuccess) e = hipMemcpy(out, dn, 4, hipMemcpyDeviceToHost);
     hipFree(d); hipFree(dn); hipFree(st);
     HIPCHK(e);
+    return 0;
+}
+// token_probs_kernel on host rows (test aid): the records the greedy loop keeps, per row; targets (optional) as lnb_forward_score
+extern "C" int lnb_op_token_probs(int device, const uint16_t* logits_bf16, int rows, int V, int top_k, const int32_t* targets,
+                                  int force_serial, int32_t* ids, float* logits, float* probs, float* target_prob, double* log_z, int* serial_walks) {
+    if (!logits_bf16 || !log_z || (top_k > 0 && (!ids || !logits || !probs)) || (targets && !target_prob)) return fail("null argument");
+    if (rows <= 0 || V <= 0) return fail("empty operand");
+    if (top_k < 0 || top_k > LNB_MAX_TOP_K) return fail("top_k must be 0..%d (got %d)", LNB_MAX_TOP_K, top_k);
+    if (targets) for (int i = 0; i < rows; i++) if (targets[i] >= V) return fail("target id %d at index %d is outside the row of %d", targets[i], i, V);
+    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
+    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    const size_t R = rows, K = top_k, G = lnb_tokprob_slices(rows);
+    std::vector<double> et; prob_exp_table(et);
+    const size_t o_et = align256(sizeof(TokProbOut)), o_x = o_et + align256(65536 * 8), o_z = o_x + align256(R * V * 2 + 16), o_k = o_z + align256(R * LNB_TOKPROB_MAX_G * 8),
+                 o_cnt = o_k + align256(R * G * K * 8), o_ids = o_cnt + align256(R * 4), o_lg = o_ids + align256(R * K * 4), o_pr = o_lg + align256(R * K * 4),
+                 o_lz = o_pr + align256(R * K * 4), o_tg = o_lz + align256(R * 8), o_tl = o_tg + align256(R * 4), o_tp = o_tl + align256(R * 4),
+                 o_w = o_tp + align256(R * 4), need = o_w + 256;
+    char* b = nullptr;
+    HIPCHK(hipMalloc((void**)&b, need));
+    TokProbOut o{}; o.ids = (int32_t*)(b + o_ids); o.logit = (float*)(b + o_lg); o.prob = (float*)(b + o_pr); o.log_z = (double*)(b + o_lz); o.walks = (int*)(b + o_w); o.cap = rows;
+    TokProbParams p{};
+    p.logits = (const uint16_t*)(b + o_x); p.V = V; p.rows = rows; p.k = top_k; p.G = (int)G; p.etab = (const double*)(b + o_et);
+    p.zpart = (double*)(b + o_z); p.kpart = (uint64_t*)(b + o_k); p.cnt = (unsigned*)(b + o_cnt); p.out = (const TokProbOut*)b; p.per_row_out = 0;
+    if (targets) { p.targets = (const int32_t*)(b + o_tg); p.tlogit = (float*)(b + o_tl); p.tprob = (float*)(b + o_tp); }
+    p.force_serial = force_serial ? 1 : 0;
+    int walks = 0;
+    hipError_t e = hipMemcpy(b, &o, sizeof o, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(b + o_et, et.data(), 65536 * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(b + o_x, logits_bf16, R * V * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess && targets) e = hipMemcpy(b + o_tg, targets, R * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(b + o_cnt, 0, R * 4);
+    if (e == hipSuccess) e = hipMemset(b + o_w, 0, 4);
+    if (e == hipSuccess) e = lnbk_token_probs(&p, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess && K) e = hipMemcpy(ids, b + o_ids, R * K * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && K) e = hipMemcpy(logits, b + o_lg, R * K * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && K) e = hipMemcpy(probs, b + o_pr, R * K * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(log_z, b + o_lz, R * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && targets) e = hipMemcpy(target_prob, b + o_tp, R * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&walks, b + o_w, 4, hipMemcpyDeviceToHost);
+    hipFree(b);
+    HIPCHK(e);
+    if (serial_walks) *serial_walks = walks;
     return 0;
 }
 extern "C" int lnb_op_exp_table(int device, float divisor, double* out65536) {

@@ -215,3 +215,28 @@ LNB_HD int lnb_gemm_stream_ntw(int n_tiles, int ct, int nch, int num_cus) {
 }
 // Dispatch order: row groups fastest once there are more than 8 of them (NOTES.md 5.12, traffic)
 LNB_HD int lnb_gemm_stream_rows_fastest(int row_groups) { return row_groups > 8 ? 1 : 0; }
+
+// ---- token probabilities (token_probs_kernel; lnb_ctx_set_token_probs, lnb_forward_score, lnb_op_token_probs) -------------------------
+// One logits row -> Z = the reference's serial f64 sum of exp (Softmax, operations_impl.go:478-511), the top k entries in ml.Argmax's
+// order with their f32 probabilities, and ln Z.  The grid is G slices x rows; the last-arriving workgroup of a row merges the slices.
+constexpr int LNB_TOKPROB_MAX_K = 16;          // = LNB_MAX_TOP_K of lnb.h
+constexpr int LNB_TOKPROB_MAX_G = 64;          // slices per row (one wave merges them)
+struct TokProbOut {                            // where one row's record goes
+    StepState* st;                             // decode: record slot = st->n_out, nothing for a finished generation or past cap; nullptr: slot = row
+    int32_t* ids; float* logit; float* prob;   // [cap][k]
+    double* log_z;                             // [cap]
+    int* walks;                                // rows that walked the serial sum (diagnostics, tests)
+    int32_t cap, pad;
+};
+struct TokProbParams {
+    const uint16_t* logits;                    // [rows][V] bf16
+    int V, rows, k, G;
+    const double* etab;                        // [65536] exp(double(bf16 bits)) from the host C library (lnb_model_finalize)
+    double* zpart; uint64_t* kpart;            // [rows][LNB_TOKPROB_MAX_G] sub-slice sums, [rows][G][k] partial top-k keys
+    unsigned* cnt;                             // [rows] arrival tickets: zero between launches (the last workgroup of a row resets its own)
+    const TokProbOut* out; int per_row_out;    // out[row] (a batch: one context per row) or out[0] for every row
+    const int32_t* targets; float* tlogit; float* tprob;   // scoring: [rows] (targets nullptr: no target)
+    int force_serial;                          // every row walks the serial sum (tests)
+};
+// slices per row: a power of two (it divides LNB_TOKPROB_MAX_G, the sub-slices of the sum), about 2048 workgroups in all
+LNB_HD int lnb_tokprob_slices(int rows) { int g = LNB_TOKPROB_MAX_G; while (g > 1 && (long)g * rows > 2048) g >>= 1; return g; }

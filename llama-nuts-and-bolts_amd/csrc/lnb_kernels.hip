@@ -3737,6 +3737,218 @@ __global__ __launch_bounds__(1024) void batch_argmax_kernel(const uint16_t* logi
     }
 }
 
+// ---- token probabilities: what the reference's Softmax (operations_impl.go:478-511) gives for one logits row, and ml.Argmax's top k ----
+// prob(j) = f32(e_j / Z) with e_j = exp(f64(x_j)) and Z = sum_{j ascending} e_j in f64 -- the reference's serial order.  e comes from
+// a table of the host C library's exp for all 65536 bf16 patterns (p.etab), so the device evaluates no transcendental here.
+// Per workgroup (slice of a row): a partial f64 sum in any order + a top-k per lane in registers; the LAST workgroup of the row to arrive
+// (agent-scope ticket) merges them into the estimate Zt and the row's top k, and certifies each reported probability against the serial
+// Z: |Z - Zt| <= (4V + 8) 2^-53 Zt (cert_z, T = V), so a quotient that lies further than that from the one point of its f32 cell where
+// round-to-nearest changes (the midpoint: low 29 bits of the f64 mantissa = 2^28) is the reference's bits.  Anything else -- a quotient
+// in the band, an f32-denormal quotient whose ends disagree, a row with Zt zero, inf or NaN, or force_serial -- walks the serial sum on
+// one wave and recomputes every reported probability from the exact Z.
+// Top-k order = ml.Argmax's (operations_impl.go:529-541, strict '<' from -MaxFloat32): candidates are > -MaxFloat32 (never NaN), value
+// descending, lowest index first on ties.  As one 64-bit key: (order-preserving bits of the value, -0 folded into +0) << 32 | ~index;
+// 0 = no entry.
+DEVINL uint64_t tp_key(float v, int j) {
+    if (!(v > -3.40282346638528859811704183484516925440e+38f)) return 0;
+    const uint32_t u = __float_as_uint(v + 0.0f);            // (-0 + 0 = +0: ml.Argmax sees the two zeros as equal)
+    const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((uint64_t)o << 32) | (uint32_t)~(uint32_t)j;
+}
+DEVINL int tp_key_index(uint64_t key) { return (int)~(uint32_t)key; }
+template <int KT> DEVINL void tp_insert(uint64_t (&lk)[KT], uint64_t key) {     // lk sorted descending; key > lk[KT - 1]
+#pragma unroll
+    for (int r = KT - 1; r > 0; r--) lk[r] = key > lk[r - 1] ? lk[r - 1] : (key > lk[r] ? key : lk[r]);
+    lk[0] = key > lk[0] ? key : lk[0];
+}
+DEVINL uint64_t tp_wave_max(uint64_t v) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) { const uint64_t o = __shfl_xor(v, s, 64); v = o > v ? o : v; }
+    return v;
+}
+DEVINL double tp_wave_sum(double v) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+    return v;
+}
+// the wave's k largest keys (one sorted list per lane) in descending order: k rounds of a wave maximum, the winning lane pops its head
+template <int KT> DEVINL void tp_wave_topk(uint64_t (&lk)[KT], int k, uint64_t* dst) {
+    for (int r = 0; r < k; r++) {
+        const uint64_t m = tp_wave_max(lk[0]);
+        if ((threadIdx.x & 63) == 0) dst[r] = m;
+        if (m != 0 && lk[0] == m) {
+#pragma unroll
+            for (int q = 0; q < KT - 1; q++) lk[q] = lk[q + 1];
+            lk[KT - 1] = 0;
+        }
+    }
+}
+// f32-cell form of cert_p: p = f32(e / Z) (round to nearest) from the estimate; sets bad when Z's band may move it to another f32
+DEVINL float cert_p32(double e, const CertZ& c, int& bad) {
+    const double q = e * c.rzt;
+    const float pj = (float)q;
+    const unsigned qh = (unsigned)__double2hiint(q), ql = (unsigned)__double2loint(q);
+    const unsigned eq = (qh >> 20) & 0x7FFu;
+    if (eq - 897u <= 126u) {                                 // f32-normal quotient (2^-126 <= q < 2): distance from its cell's rounding midpoint
+        if ((ql & 0x1FFFFFFFu) - (0x10000000u - c.delta32) <= 2u * c.delta32) bad = 1;
+    } else if (q != 0.0) {                                   // f32 denormals (and anything out of range): both ends of the band
+        const float plo = (float)(e / c.zlo), phi = (float)(e / c.zhi);
+        if (__float_as_uint(plo) != __float_as_uint(phi) || __float_as_uint(pj) != __float_as_uint(plo)) bad = 1;
+    }
+    return pj;
+}
+DEVINL double tp_readlane(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+// the reference's serial sum over the row (impl:492-499: rowExpSum += exp, j ascending), walked by ONE wave: 256 table values per
+// round gathered by the lanes (the next round's in flight), then added in index order by every lane
+DEVINL double tp_zseq_wave(const uint16_t* x, int V, const double* etab) {
+    const int lane = threadIdx.x & 63;
+    auto gather = [&](int base, double (&e)[4]) {
+#pragma unroll
+        for (int u = 0; u < 4; u++) { const int j = base + u * 64 + lane; e[u] = j < V ? etab[x[j]] : 0.0; }     // (+0 added past the end: exact)
+    };
+    double z = 0.0, a[4], b[4];
+    gather(0, a);
+    for (int base = 0; base < V; base += 256) {
+        gather(base + 256, b);
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+#pragma unroll 16
+            for (int l = 0; l < 64; l++) z += tp_readlane(a[u], l);
+#pragma unroll
+        for (int u = 0; u < 4; u++) a[u] = b[u];
+    }
+    return z;
+}
+template <int KT> __global__ __launch_bounds__(256) void token_probs_kernel(TokProbParams p) {
+    constexpr int KA = KT > 0 ? KT : 1;                      // (KT = 0: scoring only, no top-k)
+    __shared__ uint64_t sk[4 * KA];
+    __shared__ double sz[4 * LNB_TOKPROB_MAX_G];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row = blockIdx.y, g = blockIdx.x, G = p.G, V = p.V, k = p.k;
+    const uint16_t* x = p.logits + (size_t)row * V;
+    const TokProbOut& o = p.out[p.per_row_out ? row : 0];
+    int slot = row;
+    if (o.st) {                                              // (the argmax that advances the state runs after this launch)
+        if (o.st->finished || o.st->n_out >= o.cap) return;  // a finished generation records nothing (every workgroup of the row agrees)
+        slot = o.st->n_out;
+    }
+    // this workgroup's slice: the unaligned head (workgroup 0), 16-byte chunks, the tail (workgroup G - 1)
+    int h = (int)((16 - (((uintptr_t)x) & 15)) & 15) >> 1;
+    if (h > V) h = V;
+    const int nb = (V - h) >> 3, tail0 = h + nb * 8;
+    const uint4* l4 = (const uint4*)(x + h);
+    uint64_t lk[KA];
+#pragma unroll
+    for (int r = 0; r < KA; r++) lk[r] = 0;
+    auto visit = [&](uint16_t b, int j) {
+        if constexpr (KT > 0) { const uint64_t key = tp_key(bf_wide(b), j); if (key > lk[KA - 1]) tp_insert<KA>(lk, key); }
+    };
+    // Zt is summed over LNB_TOKPROB_MAX_G fixed sub-slices of the row in a fixed order whatever G is (G divides it): a row's estimate, hence
+    // its ln Z and whether it walks, is the same in every launch shape (one sequence, a batch, scoring)
+    const int S = LNB_TOKPROB_MAX_G / G;
+    double mine = 0.0;                                       // lane l: the wave's sum of sub-slice l
+    for (int v = 0; v < S; v++) {
+        const int vs = g * S + v;
+        const int c0 = (int)((long)nb * vs / LNB_TOKPROB_MAX_G), c1 = (int)((long)nb * (vs + 1) / LNB_TOKPROB_MAX_G);
+        double zs = 0.0;
+        if (vs == 0 && tid < h) { zs += p.etab[x[tid]]; visit(x[tid], tid); }
+        if (vs == LNB_TOKPROB_MAX_G - 1 && tail0 + tid < V) { zs += p.etab[x[tail0 + tid]]; visit(x[tail0 + tid], tail0 + tid); }
+        for (int c = c0 + tid; c < c1; c += 512) {               // two chunks in flight: 16 table gathers before the first add
+            const bool two = c + 256 < c1;
+            const uint4 wa = l4[c], wb = l4[two ? c + 256 : c];
+            const uint32_t q[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+            double e[16];
+#pragma unroll
+            for (int t = 0; t < 16; t++) e[t] = p.etab[(t & 1) ? (q[t >> 1] >> 16) : (q[t >> 1] & 0xFFFFu)];
+#pragma unroll
+            for (int t = 0; t < 8; t++) zs += e[t];
+            if (two) {
+#pragma unroll
+                for (int t = 8; t < 16; t++) zs += e[t];
+            }
+            if constexpr (KT > 0) {
+#pragma unroll
+                for (int t = 0; t < 16; t++) {
+                    if (t >= 8 && !two) break;
+                    const int cc = t < 8 ? c : c + 256;
+                    visit((uint16_t)((t & 1) ? (q[t >> 1] >> 16) : (q[t >> 1] & 0xFFFFu)), h + cc * 8 + (t & 7));
+                }
+            }
+        }
+        zs = tp_wave_sum(zs);
+        if (lane == vs) mine = zs;
+    }
+    // the workgroup's sub-slice sums and top k -> this slice's partials
+    sz[wave * LNB_TOKPROB_MAX_G + lane] = mine;
+    if constexpr (KT > 0) tp_wave_topk<KA>(lk, k, sk + wave * KA);
+    __syncthreads();
+    if (wave == 0) {
+        uint64_t key = (KT > 0 && lane < 4 * KA && lane % KA < k) ? sk[lane] : 0;
+        for (int r = 0; r < k; r++) {                        // the four waves' lists: one key per lane, k rounds
+            const uint64_t m = tp_wave_max(key);
+            if (m != 0 && key == m) key = 0;
+            if (lane == 0) p.kpart[((size_t)row * G + g) * k + r] = m;
+        }
+        if (lane >= g * S && lane < (g + 1) * S) {
+            constexpr int M = LNB_TOKPROB_MAX_G;
+            p.zpart[(size_t)row * M + lane] = (sz[lane] + sz[M + lane]) + (sz[2 * M + lane] + sz[3 * M + lane]);
+        }
+        if (lane == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            const unsigned t = __hip_atomic_fetch_add(p.cnt + row, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+            s_last = t == (unsigned)G - 1;
+        }
+    }
+    __syncthreads();
+    if (!s_last || wave != 0) return;
+    // ---- the last workgroup of the row, one wave: merge the G slices, certify, walk if needed, report ----
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (lane == 0) p.cnt[row] = 0;                           // (ready for the next launch: stream order)
+    const double zt = tp_wave_sum(p.zpart[(size_t)row * LNB_TOKPROB_MAX_G + lane]);
+    uint64_t top = 0;                                        // lane r < k: the row's r-th entry
+    if constexpr (KT > 0) {
+        uint64_t mk[KA];
+#pragma unroll
+        for (int r = 0; r < KA; r++) mk[r] = (lane < G && r < k) ? p.kpart[((size_t)row * G + lane) * k + r] : 0;
+        for (int r = 0; r < k; r++) {
+            const uint64_t m = tp_wave_max(mk[0]);
+            if (lane == r) top = m;
+            if (m != 0 && mk[0] == m) {
+#pragma unroll
+                for (int q = 0; q < KA - 1; q++) mk[q] = mk[q + 1];
+                mk[KA - 1] = 0;
+            }
+        }
+    }
+    // lanes 0..k-1: the top entries; lane 32: the scoring target
+    int id = -1;
+    if (lane < k && top != 0) id = tp_key_index(top);
+    if (lane == 32 && p.targets) { const int t = p.targets[row]; if (t >= 0 && t < V) id = t; }
+    const uint16_t b = id >= 0 ? x[id] : (uint16_t)0;
+    const double e = id >= 0 ? p.etab[b] : 0.0;
+    const CertZ cz = cert_z(zt, V);
+    int bad = p.force_serial || !(zt > 0.0) || !(cz.zhi <= 1.7976931348623157e308);
+    float pr = 0.0f;
+    if (id >= 0) pr = cert_p32(e, cz, bad);
+    double z = zt;
+    if (__any(bad)) {
+        z = tp_zseq_wave(x, V, p.etab);
+        if (id >= 0) pr = (float)(e / z);
+        if (lane == 0 && o.walks) atomicAdd(o.walks, 1);
+    }
+    const float qnan = __uint_as_float(0x7FC00000u);
+    if (lane < k) {
+        const size_t at = (size_t)slot * k + lane;
+        o.ids[at] = id;
+        o.logit[at] = id >= 0 ? bf_wide(b) : qnan;
+        o.prob[at] = id >= 0 ? pr : qnan;
+    }
+    if (lane == 0 && o.log_z) o.log_z[slot] = log(z);
+    if (lane == 32 && p.targets) { p.tlogit[row] = id >= 0 ? bf_wide(b) : qnan; p.tprob[row] = id >= 0 ? pr : qnan; }
+}
+
 __global__ void set_state_kernel(StepState* st, int pos, int n_out, int honour_stop) { st->pos = pos; st->n_out = n_out; st->finished = 0; st->honour_stop = honour_stop; }
 struct StopIds { int32_t n; int32_t id[LNB_MAX_STOP_IDS]; };
 __global__ void set_stop_kernel(StepState* st, StopIds s) { st->n_stop = s.n; for (int k = 0; k < LNB_MAX_STOP_IDS; k++) st->stop[k] = k < s.n ? s.id[k] : -1; st->finished = 0; }
@@ -4228,6 +4440,17 @@ extern "C" hipError_t lnbk_batch_embed(const uint16_t* emb, const BatchTab* tab,
 }
 extern "C" hipError_t lnbk_batch_argmax(const uint16_t* logits, int V, const BatchTab* tab, int nseq, int32_t* ring, hipStream_t st) {
     hipLaunchKernelGGL(batch_argmax_kernel, dim3((unsigned)nseq), dim3(1024), 0, st, logits, V, tab, ring);
+    return hipGetLastError();
+}
+// one launch for `rows` rows of p->logits: grid G slices x rows, 256 threads (k picks the register top-k: 1 / 2 / 4 / 8 / 16, 0 = none)
+extern "C" hipError_t lnbk_token_probs(const TokProbParams* p, hipStream_t st) {
+    const dim3 grid((unsigned)p->G, (unsigned)p->rows), block(256);
+    if (p->k <= 0) hipLaunchKernelGGL(token_probs_kernel<0>, grid, block, 0, st, *p);
+    else if (p->k <= 1) hipLaunchKernelGGL(token_probs_kernel<1>, grid, block, 0, st, *p);
+    else if (p->k <= 2) hipLaunchKernelGGL(token_probs_kernel<2>, grid, block, 0, st, *p);
+    else if (p->k <= 4) hipLaunchKernelGGL(token_probs_kernel<4>, grid, block, 0, st, *p);
+    else if (p->k <= 8) hipLaunchKernelGGL(token_probs_kernel<8>, grid, block, 0, st, *p);
+    else hipLaunchKernelGGL(token_probs_kernel<16>, grid, block, 0, st, *p);
     return hipGetLastError();
 }
 extern "C" hipError_t lnbk_batch_set_state(const BatchTab* tab, const int32_t* tokens, const int32_t* pos, int32_t* ring, int honour_stop, hipStream_t st) {

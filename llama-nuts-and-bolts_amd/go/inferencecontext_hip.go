@@ -42,6 +42,7 @@ type InferenceContext struct {
 
 	handle *C.lnb_ctx
 	lt     *LlamaTransformer // keeps the transformer alive (and finalized after this context)
+	topK   int               // SetTokenProbs
 }
 
 // LayerProgress switches the per-layer "Transformer block layer %d / %d was run" message (llamatransformer.go:163) on or off for
@@ -210,6 +211,57 @@ func (ic *InferenceContext) DecodeGreedyUntil(lt *LlamaTransformer, token TokenI
 		return nil, false, err
 	}
 	return out[:int(n)], fin != 0, nil
+}
+
+// SetTokenProbs makes the greedy loops record, for every token they generate, the topK (0..LNB_MAX_TOP_K; 0 = off, the default) most likely
+// tokens of its logits row with their probabilities -- the bits of the reference's ml.Softmax on that row (include/lnb.h).
+func (ic *InferenceContext) SetTokenProbs(lt *LlamaTransformer, topK int) error {
+	if err := ic.attach(lt); err != nil {
+		return err
+	}
+	if err := lnbCall(func() C.int { return C.lnb_ctx_set_token_probs(ic.handle, C.int(topK)) }); err != nil {
+		return err
+	}
+	ic.topK = topK
+	return nil
+}
+
+// TokenProbs returns records [first, first+n) of the last greedy call: ids, logits and probs [n*k] (entry i*k is the generated token) and
+// ln Z [n] of each row.
+func (ic *InferenceContext) TokenProbs(first int, n int) (ids []TokenId, logits []float32, probs []float32, logZ []float64, err error) {
+	if ic.handle == nil {
+		return nil, nil, nil, nil, fmt.Errorf("inference context is closed")
+	}
+	k := ic.topK
+	ids, logits, probs, logZ = make([]TokenId, n*k+1), make([]float32, n*k+1), make([]float32, n*k+1), make([]float64, n+1)
+	if err = lnbCall(func() C.int {
+		return C.lnb_ctx_read_token_probs(ic.handle, C.int(first), C.int(n), (*C.int32_t)(unsafe.Pointer(&ids[0])), (*C.float)(unsafe.Pointer(&logits[0])),
+			(*C.float)(unsafe.Pointer(&probs[0])), (*C.double)(unsafe.Pointer(&logZ[0])))
+	}); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	return ids[:n*k], logits[:n*k], probs[:n*k], logZ[:n], nil
+}
+
+// Score runs Forward(tokens, startPos) and reports, per row, the logit and probability of targets[i] (a negative id: NaN) and ln Z,
+// instead of the logits (lnb_forward_score); argmaxLast is Forward's next token.
+func (ic *InferenceContext) Score(lt *LlamaTransformer, tokens []TokenId, startPos int, targets []TokenId) (targetLogit []float32, targetProb []float32, logZ []float64, argmaxLast TokenId, err error) {
+	if len(tokens) == 0 || len(targets) != len(tokens) {
+		return nil, nil, nil, -1, fmt.Errorf("Score: one target per token, at least one token")
+	}
+	if err = ic.attach(lt); err != nil {
+		return nil, nil, nil, -1, err
+	}
+	n := len(tokens)
+	targetLogit, targetProb, logZ = make([]float32, n), make([]float32, n), make([]float64, n)
+	var am C.int32_t
+	if err = lnbCall(func() C.int {
+		return C.lnb_forward_score(ic.handle, (*C.int32_t)(unsafe.Pointer(&tokens[0])), C.int(n), C.int(startPos), (*C.int32_t)(unsafe.Pointer(&targets[0])),
+			(*C.float)(unsafe.Pointer(&targetLogit[0])), (*C.float)(unsafe.Pointer(&targetProb[0])), (*C.double)(unsafe.Pointer(&logZ[0])), &am)
+	}); err != nil {
+		return nil, nil, nil, -1, err
+	}
+	return targetLogit, targetProb, logZ, TokenId(am), nil
 }
 
 // SetThroughputSchedule selects the co-residency-friendly forms of the one-token kernels (lnb_ctx_set_schedule): for hosts that keep several

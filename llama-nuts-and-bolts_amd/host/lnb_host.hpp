@@ -194,6 +194,25 @@ public:
     // hosts that keep several generations in flight on one GPU (one InferenceContext each, inference.go:174): the co-residency-friendly forms of
     // the one-token kernels (lnb_ctx_set_schedule); same tokens either way
     void SetThroughputSchedule(bool on) { check(lnb_ctx_set_schedule(h_, on ? LNB_SCHED_THROUGHPUT : LNB_SCHED_LATENCY)); }
+    // token probabilities (include/lnb.h): the greedy loops record the top k (0..LNB_MAX_TOP_K, 0 = off) of every token they generate
+    void SetTokenProbs(int topK) { check(lnb_ctx_set_token_probs(h_, topK)); topK_ = topK; }
+    struct TokenProbs { std::vector<int32_t> Ids; std::vector<float> Logits, Probs; std::vector<double> LogZ; int K = 0; };   // [n * K], [n]
+    TokenProbs ReadTokenProbs(int n, int first = 0) const {
+        TokenProbs r; r.K = topK_;
+        r.Ids.resize((size_t)n * topK_ + 1); r.Logits.resize(r.Ids.size()); r.Probs.resize(r.Ids.size()); r.LogZ.resize((size_t)n + 1);
+        check(lnb_ctx_read_token_probs(h_, first, n, r.Ids.data(), r.Logits.data(), r.Probs.data(), r.LogZ.data()));
+        r.Ids.resize((size_t)n * topK_); r.Logits.resize(r.Ids.size()); r.Probs.resize(r.Ids.size()); r.LogZ.resize(n);
+        return r;
+    }
+    // lnb_forward_score: Forward reporting each row's target logit / probability and ln Z instead of the logits (targets[i] < 0: NaN)
+    struct Score { std::vector<float> TargetLogit, TargetProb; std::vector<double> LogZ; TokenId ArgmaxLast = -1; };
+    Score ScoreTokens(const std::vector<TokenId>& tokens, int startPos, const std::vector<TokenId>& targets) {
+        if (targets.size() != tokens.size()) throw std::runtime_error("ScoreTokens: one target per token");
+        Score s; s.TargetLogit.resize(tokens.size() + 1); s.TargetProb.resize(tokens.size() + 1); s.LogZ.resize(tokens.size() + 1);
+        check(lnb_forward_score(h_, tokens.data(), (int)tokens.size(), startPos, targets.data(), s.TargetLogit.data(), s.TargetProb.data(), s.LogZ.data(), &s.ArgmaxLast));
+        s.TargetLogit.resize(tokens.size()); s.TargetProb.resize(tokens.size()); s.LogZ.resize(tokens.size());
+        return s;
+    }
 private:
     static void layer_cb(int layer, int n, double secs, void* user) {      // infContext.Logf(...), llamatransformer.go:163
         auto* self = (InferenceContext*)user;
@@ -206,7 +225,7 @@ private:
         check(lnb_ctx_read_kv(h_, layer, which, out.data()));
         return out;
     }
-    const LlamaTransformer& t_; LogFn logFn_; lnb_ctx* h_ = nullptr;
+    const LlamaTransformer& t_; LogFn logFn_; lnb_ctx* h_ = nullptr; int topK_ = 0;
 };
 
 // (*LlamaTransformer).Forward(infContext, inputTokens, startPos) -> logits [seq, vocab] f32 (llamatransformer.go:145-180)

@@ -63,7 +63,9 @@ EXPORTS = [
     "lnb_model_enable_batch", "lnb_model_batch_bytes", "lnb_batch_create", "lnb_batch_destroy", "lnb_batch_decode", "lnb_batch_decode_until", "lnb_ctx_set_stop_ids", "lnb_decode_greedy_until", "lnb_batch_profile_kernel", "lnb_batch_set_state", "lnb_batch_check_error", "lnb_pipeline_tick_batch",
     "lnb_pipeline_init_host", "lnb_batch_boundary_ptr",
     "lnb_abi_version", "lnb_runtime_info", "lnb_profile_ffn_pair",
+    "lnb_ctx_set_token_probs", "lnb_ctx_read_token_probs", "lnb_ctx_token_prob_walks", "lnb_forward_score", "lnb_op_token_probs",
 ]
+MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
 ABI_VERSION = 6          # LNB_ABI_VERSION of include/lnb.h this binding was written against (tests/test_cabi.py compares it with the header's)
 
 
@@ -162,6 +164,11 @@ def lib():
     L.lnb_op_linear_mode.argtypes = [C.c_int, vp, vp, C.c_float, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.lnb_op_argmax.argtypes = [C.c_int, vp, C.c_int, i32p]
     L.lnb_op_exp_table.argtypes = [C.c_int, C.c_float, vp]
+    L.lnb_ctx_set_token_probs.argtypes = [vp, C.c_int]
+    L.lnb_ctx_read_token_probs.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.lnb_ctx_token_prob_walks.argtypes = [vp, C.POINTER(C.c_int)]
+    L.lnb_forward_score.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, i32p]
+    L.lnb_op_token_probs.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.lnb_model_num_tensors.argtypes = [vp]
     L.lnb_model_tensor_info.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.lnb_checkpoint_open.argtypes = [C.c_char_p, C.POINTER(vp)]
@@ -528,6 +535,42 @@ class InferenceContext:
         _chk(self.L.lnb_decode_greedy_until(self.h, int(token), start_pos, max_steps, _p(out), C.byref(n), C.byref(fin), C.byref(ms)))
         return out[:n.value].copy(), bool(fin.value), ms.value
 
+    def set_token_probs(self, k):
+        """record the top k token probabilities (0..MAX_TOP_K; 0 = off, the default) of every token the greedy loops generate (include/lnb.h)"""
+        _chk(self.L.lnb_ctx_set_token_probs(self.h, int(k)))
+        self.top_k = int(k)
+        return self
+
+    def token_probs(self, n, first=0):
+        """records [first, first + n) of the last decode call: (ids int32 [n, k], logits f32 [n, k], probs f32 [n, k], log_z f64 [n]);
+        ids[:, 0] are the generated tokens.  k is the top_k that call ran with (the current setting: changing it drops the records)."""
+        k = getattr(self, "top_k", 0)
+        ids = np.empty((n, max(k, 1)), dtype=np.int32)
+        lg = np.empty((n, max(k, 1)), dtype=np.float32)
+        pr = np.empty((n, max(k, 1)), dtype=np.float32)
+        lz = np.empty(max(n, 1), dtype=np.float64)
+        _chk(self.L.lnb_ctx_read_token_probs(self.h, int(first), int(n), _p(ids), _p(lg), _p(pr), _p(lz)))
+        return ids[:, :k], lg[:, :k], pr[:, :k], lz[:n]
+
+    def token_prob_walks(self):
+        """rows of this context (decode steps, scored rows) whose probabilities walked the reference's serial sum"""
+        n = C.c_int(0)
+        _chk(self.L.lnb_ctx_token_prob_walks(self.h, C.byref(n)))
+        return n.value
+
+    def score(self, tokens, start_pos, targets):
+        """Forward(tokens, start_pos) reporting, per row, the target's logit and probability and ln Z instead of the logits (lnb_forward_score):
+        -> (target_logit f32 [S], target_prob f32 [S], log_z f64 [S], argmax of the last row).  targets[i] < 0: NaN for that row."""
+        tok = np.ascontiguousarray(tokens, dtype=np.int32)
+        tg = np.ascontiguousarray(targets, dtype=np.int32)
+        S = tok.size
+        if tg.size != S:
+            raise LnbError("score: %d targets for %d tokens" % (tg.size, S))
+        tl = np.empty(max(S, 1), dtype=np.float32); tp = np.empty(max(S, 1), dtype=np.float32); lz = np.empty(max(S, 1), dtype=np.float64)
+        am = C.c_int32(-2)
+        _chk(self.L.lnb_forward_score(self.h, _p(tok), S, start_pos, _p(tg), _p(tl), _p(tp), _p(lz), C.byref(am)))
+        return tl[:S], tp[:S], lz[:S], am.value
+
     def CacheK(self, layer):
         return self._kv(layer, 0)
 
@@ -733,6 +776,29 @@ def op_argmax(logits_u16, device=0):
     out = C.c_int32(-2)
     _chk(lib().lnb_op_argmax(device, _p(a), a.size, C.byref(out)))
     return out.value
+
+
+def op_token_probs(logits_u16, top_k, targets=None, force_serial=False, device=0):
+    """token_probs_kernel on rows of bf16 logits [rows, V] (lnb_op_token_probs) -> dict of ids / logits / probs [rows, k], log_z [rows],
+    target_prob [rows] (with targets), serial_walks"""
+    a = np.ascontiguousarray(logits_u16, dtype=np.uint16)
+    if a.ndim == 1:
+        a = a[None, :]
+    rows, V = a.shape
+    k = int(top_k)
+    ids = np.empty((rows, max(k, 1)), dtype=np.int32)
+    lg = np.empty((rows, max(k, 1)), dtype=np.float32)
+    pr = np.empty((rows, max(k, 1)), dtype=np.float32)
+    lz = np.empty(rows, dtype=np.float64)
+    tg = None if targets is None else np.ascontiguousarray(targets, dtype=np.int32)
+    tp = np.empty(rows, dtype=np.float32)
+    walks = C.c_int(0)
+    _chk(lib().lnb_op_token_probs(device, _p(a), rows, V, k, None if tg is None else _p(tg), 1 if force_serial else 0,
+                                  _p(ids), _p(lg), _p(pr), _p(tp) if tg is not None else None, _p(lz), C.byref(walks)))
+    out = dict(ids=ids[:, :k], logits=lg[:, :k], probs=pr[:, :k], log_z=lz, serial_walks=walks.value)
+    if tg is not None:
+        out["target_prob"] = tp
+    return out
 
 
 def op_exp_table(divisor=1.0, device=0):
