@@ -194,6 +194,36 @@ int lnb_decode_greedy(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int
 int lnb_ctx_set_stop_ids(lnb_ctx* c, const int32_t* ids, int n);
 int lnb_decode_greedy_until(lnb_ctx* c, int32_t token, int start_pos, int max_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out);
 
+/* ---- speculative greedy decoding with n-gram drafts: the same tokens, logits and KV rows as lnb_decode_greedy_until, fewer passes ----
+ * Each PASS guesses the next tokens by n-gram lookup (prompt lookup: no second model) and verifies them all in ONE batched pass over the
+ * weights whose w = draft_len + 1 columns alias this context: column i takes d_i (d_0 = the current token) at position pos + i with the
+ * context's caches, so it is exactly the one-token step at pos + i, bit for bit (DESIGN.md "Speculative decoding").  The argmax of columns
+ * 0 .. a is emitted, a = the longest prefix of columns whose argmax equals the next column's input, with the context's stop ids applied as
+ * the greedy loop applies them.  A pass without a draft replays the context's one-token step.  The host reads one pinned word per pass.
+ * Draft rule (ngram_draft_kernel; the running text R = history, token, the tokens generated so far; C = the corpus):
+ *   for n = ngram_max down to ngram_min, the first n with a match wins; a match is an earlier occurrence of R's last n tokens that is
+ *   followed by at least one token of its array (R's own final suffix is no match), searched in R before C, the latest start winning
+ *   within an array; the draft is up to max_draft tokens after the match, cut at the end of that array, at max_steps - generated - 1
+ *   and at seq_len - pos - 1.  No match: no draft.
+ * lnb_ctx_set_draft: max_draft 0..LNB_MAX_DRAFT (0 = off, the default: lnb_decode_speculative_until is then lnb_decode_greedy_until);
+ *   1 <= ngram_min <= ngram_max <= 16; the corpus (may be empty) is copied to the device.  Arguments are checked before the handle.
+ * lnb_decode_speculative_until: outputs as lnb_decode_greedy_until from `token` at start_pos (history: the n_history tokens before it,
+ *   e.g. the prompt); afterwards the cache rows [0, start_pos + *n_generated) hold that call's bits and lnb_decode_greedy / lnb_forward
+ *   continue the context.  Requires a whole-model handle, the exact mode, seq_len within the batched attention's reach (~7.8 K positions
+ *   at head_dim 128) and dim, n_heads*head_dim, FFN hidden size multiples of 128; refuses token probabilities, the tolerance mode and a
+ *   member of a live batch.  With or without lnb_model_enable_batch (its column forms, or rows of the streaming product; same bits).
+ *   stats (optional): passes, verify_passes (passes with a draft), drafted (draft tokens verified), accepted (draft tokens emitted:
+ *   *n_generated - passes).  ms_out (optional): HIP-event time of the whole loop.
+ * lnb_op_ngram_draft: the draft kernel on host arrays (a test aid): R = text, no decode limits; out[0 .. *n_out), out has max_draft entries. */
+#define LNB_MAX_DRAFT 15
+typedef struct lnb_spec_stats { int64_t passes, verify_passes, drafted, accepted; } lnb_spec_stats;
+int lnb_ctx_set_draft(lnb_ctx* c, int max_draft, int ngram_min, int ngram_max, const int32_t* corpus, int n_corpus);
+int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, int n_history, int32_t token, int start_pos,
+                                 int max_steps, int32_t* out_tokens, int* n_generated, int* finished,
+                                 lnb_spec_stats* stats, float* ms_out);
+int lnb_op_ngram_draft(int device, const int32_t* text, int n_text, const int32_t* corpus, int n_corpus,
+                       int ngram_min, int ngram_max, int max_draft, int32_t* out, int* n_out);
+
 /* ---- token probabilities: how likely each generated (or given) token was, exactly as the reference's own Softmax gives it ----------
  * For one logits row x[0..V) (bf16 values widened to f32: what lnb_forward returns -- the reference's Forward, llamatransformer.go:170-177):
  *   Z       = sum_{j ascending} exp(f64(x_j)) in f64: ml.Softmax's serial rowExpSum (operations_impl.go:478-511);

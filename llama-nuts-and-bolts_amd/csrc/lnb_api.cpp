@@ -21,6 +21,7 @@
 #include "lnb_device.h"
 #include "lnb_rccl.h"
 static_assert(LNB_MAX_TOP_K == LNB_TOKPROB_MAX_K, "lnb.h and lnb_device.h disagree on the largest top-k");
+static_assert(LNB_MAX_DRAFT == LNB_SPEC_MAX_DRAFT && LNB_MAX_DRAFT + 1 <= LNB_STREAM_COLS, "a verify pass is one column group of at most 16 columns");
 
 extern "C" {
 hipError_t lnbk_gemv(const GemvParams* p, int rw, int nch, int epi, int norm, hipStream_t st);
@@ -55,6 +56,9 @@ hipError_t lnbk_batch_prepare(void);
 hipError_t lnbk_gemm_stream(const GemmParams* p, int epi, int num_cus, hipStream_t st);
 hipError_t lnbk_spin(int us, hipStream_t st);
 hipError_t lnbk_token_probs(const TokProbParams* p, hipStream_t st);
+hipError_t lnbk_spec_argmax(const uint16_t* logits, int V, int w, int32_t* g, hipStream_t st);
+hipError_t lnbk_spec_commit(const int32_t* g, int w, const BatchTab* tab, hipStream_t st);
+hipError_t lnbk_ngram_draft(const DraftParams* p, hipStream_t st);
 }
 
 // The HIP runtime spreads a process's streams over a fixed number of hardware queues (its default: 4) and streams that share a queue run one
@@ -179,6 +183,15 @@ struct lnb_ctx {
     double* tp_zpart = nullptr; uint64_t* tp_kpart = nullptr; unsigned* tp_cnt = nullptr;   // one row's partials, arrival ticket
     int tp_last_k = 0, tp_last_n = 0;      // what the last decode call that ran this context recorded (k 0: nothing)
     void* sc_buf = nullptr; size_t sc_bytes = 0;   // lnb_forward_score's scratch, grown on demand
+    // speculative decoding (lnb_ctx_set_draft, lnb_decode_speculative_until): drafting settings, the corpus, the running text's head (history +
+    // token), the verify columns' states and token words (index 0 unused: column 0 is this context's own), their argmax, the draft kernel's
+    // scratch and the pinned word it reports to the host; one verify batch per width 2..16, built and captured on first use
+    int sp_max_draft = 0, sp_ngram_min = 1, sp_ngram_max = 1;
+    int32_t* sp_corpus = nullptr; int sp_n_corpus = 0;
+    int32_t* sp_text = nullptr; int sp_text_cap = 0;
+    StepState* sp_st = nullptr; int32_t* sp_tok = nullptr; int32_t* sp_g = nullptr; int* sp_best = nullptr; unsigned* sp_cnt = nullptr;
+    int32_t* sp_word = nullptr; int32_t* sp_word_dev = nullptr; hipEvent_t sp_ev = nullptr;
+    struct lnb_batch* sp_b[LNB_MAX_DRAFT + 2] = {};
 };
 // Every path that rewrites the device-side StepState goes through here, so that the pipeline tick's "the graph left pos+1 behind, skip
 // the set_state launch" shortcut (dev_pos) can never act on a position some OTHER entry point has since overwritten (lnb_forward,
@@ -658,6 +671,14 @@ static void tp_free(lnb_ctx* c) {
     c->tp_out = nullptr; c->tp_ids = nullptr; c->tp_logit = nullptr; c->tp_prob = nullptr; c->tp_logz = nullptr;
     c->tp_zpart = nullptr; c->tp_kpart = nullptr; c->tp_cnt = nullptr;
 }
+static void spec_free(lnb_ctx* c) {
+    for (auto& b : c->sp_b) { if (b) lnb_batch_destroy(b); b = nullptr; }
+    hipFree(c->sp_corpus); hipFree(c->sp_text); hipFree(c->sp_st); hipFree(c->sp_tok); hipFree(c->sp_g); hipFree(c->sp_best); hipFree(c->sp_cnt);
+    if (c->sp_word) hipHostFree(c->sp_word);
+    if (c->sp_ev) hipEventDestroy(c->sp_ev);
+    c->sp_corpus = nullptr; c->sp_text = nullptr; c->sp_st = nullptr; c->sp_tok = nullptr; c->sp_g = nullptr; c->sp_best = nullptr; c->sp_cnt = nullptr;
+    c->sp_word = nullptr; c->sp_word_dev = nullptr; c->sp_ev = nullptr; c->sp_text_cap = 0; c->sp_n_corpus = 0;
+}
 extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
     if (!c) return 0;
     // a batch bakes its members' device pointers (state words, token words, caches) into its tables and captured graphs: freeing a member
@@ -672,6 +693,7 @@ extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
     if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
     hipFree(c->e_buf); hipFree(c->z_part); hipFree(c->zseq_count); hipFree(c->attn_cnt); if (c->score_idx) hipFree(c->score_idx);
     tp_free(c); if (c->sc_buf) hipFree(c->sc_buf);
+    spec_free(c);
     for (auto p : c->ck) if (p) hipFree(p);
     for (auto p : c->cv) if (p) hipFree(p);
     hipFree(c->st); hipFree(c->dtok); hipFree(c->dnext); hipFree(c->derr); hipFree(c->dout);
@@ -1181,6 +1203,28 @@ extern "C" int lnb_ctx_token_prob_walks(lnb_ctx* c, int* out) {
     *out = c->h_io[0];
     return 0;
 }
+// one captured graph per attention form: the step at context T replays the long-context one when T exceeds the crossover.  Captures the
+// forms that steps at positions start_pos .. start_pos + n_steps - 1 need and the context does not hold yet.
+static int capture_decode_graphs(lnb_ctx* c, int start_pos, int n_steps) {
+    hipStream_t st = c->stream;
+    auto capture = [&](hipGraphExec_t* slot, bool longctx) -> int {
+        if (*slot) return 0;
+        hipGraph_t g = nullptr;
+        c->attn_long = longctx;
+        HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        int rc = enqueue_decode_step(c);
+        hipError_t e = hipStreamEndCapture(st, &g);
+        if (rc) { if (g) hipGraphDestroy(g); return -1; }
+        HIPCHK(e);
+        HIPCHK(hipGraphInstantiate(slot, g, nullptr, nullptr, 0));
+        HIPCHK(hipGraphDestroy(g));
+        return 0;
+    };
+    const bool any_short = !want_long_attention(c, 1, start_pos), any_long = want_long_attention(c, 1, start_pos + n_steps - 1);
+    if (any_short && capture(&c->graph, false)) return -1;
+    if (any_long && capture(&c->graph_long, true)) return -1;
+    return 0;
+}
 static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out);
 extern "C" int lnb_decode_greedy(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int32_t* out_tokens, float* ms_out) {
     return decode_greedy_impl(c, token, start_pos, n_steps, out_tokens, nullptr, nullptr, ms_out);
@@ -1202,23 +1246,7 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     if (token < 0 || token >= m->a.vocab_size) return fail("token id at index 0 is outside the vocabulary");
     hipStream_t st = c->stream;
     const bool use_graph = env_int("LNB_NO_GRAPH", 0) == 0;
-    // one captured graph per attention form: the step at context T replays the long-context one when T exceeds the crossover
-    auto capture = [&](hipGraphExec_t* slot, bool longctx) -> int {
-        if (*slot) return 0;
-        hipGraph_t g = nullptr;
-        c->attn_long = longctx;
-        HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        int rc = enqueue_decode_step(c);
-        hipError_t e = hipStreamEndCapture(st, &g);
-        if (rc) { if (g) hipGraphDestroy(g); return -1; }
-        HIPCHK(e);
-        HIPCHK(hipGraphInstantiate(slot, g, nullptr, nullptr, 0));
-        HIPCHK(hipGraphDestroy(g));
-        return 0;
-    };
-    const bool any_short = !want_long_attention(c, 1, start_pos), any_long = want_long_attention(c, 1, start_pos + n_steps - 1);
-    if (use_graph && any_short && capture(&c->graph, false)) return -1;
-    if (use_graph && any_long && capture(&c->graph_long, true)) return -1;
+    if (use_graph && capture_decode_graphs(c, start_pos, n_steps)) return -1;
     c->tp_last_k = 0; c->tp_last_n = 0;
     HIPCHK(hipMemcpyAsync(c->dtok, &token, 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(c->derr, 0, 4, st));
@@ -1453,6 +1481,9 @@ struct lnb_batch {
     hipEvent_t ev_done = nullptr, ev_in = nullptr, ev_sent = nullptr; bool in_pending = false, sent_pending = false, recv_unmatched = false;
     // token probabilities (the members' lnb_ctx_set_token_probs, one top_k for all): one row per sequence into its context's log
     int top_k = 0; TokProbOut* tp_out = nullptr; double* tp_zpart = nullptr; uint64_t* tp_kpart = nullptr; unsigned* tp_cnt = nullptr;
+    // speculative verify batch (lnb_decode_speculative_until): every column is ONE context (ctxs[s] = it, the same caches); columns s >= 1 take
+    // their state and token word from col_st + s / col_tok + s instead of the context's own
+    StepState* col_st = nullptr; int32_t* col_tok = nullptr;
 };
 static int m16_copy(lnb_model* m, const TiledDesc& t, int rows, uint16_t** out) {
     const size_t bytes = m16_elems(rows, t.k, t.nch) * 2;
@@ -1524,6 +1555,7 @@ static int batch_alloc(lnb_batch* b) {
     for (int s = 0; s < LNB_BATCH_MAX; s++) {
         lnb_ctx* c = b->ctxs[s < n ? s : 0];                // (unused columns point at sequence 0's words: never dereferenced, never null)
         t.st[s] = c->st; t.dtok[s] = c->dtok; t.dout[s] = c->dout; t.dout_cap[s] = c->dout_cap; t.seq_len[s] = c->seq_len;
+        if (b->col_st && s >= 1 && s < n) { t.st[s] = b->col_st + s; t.dtok[s] = b->col_tok + s; }
         for (size_t l = 0; l < m->layers.size(); l++) { kv[l].ck[s] = c->ck[l]; kv[l].cv[s] = c->cv[l]; }
     }
     HIPCHK(hipMalloc((void**)&b->tab, sizeof t)); HIPCHK(hipMemcpyAsync(b->tab, &t, sizeof t, hipMemcpyHostToDevice, b->stream));
@@ -1883,6 +1915,203 @@ extern "C" int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int it
     HIPCHK(hipStreamSynchronize(st));
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
     *avg_ms_out = ms / (float)iters;
+    return 0;
+}
+
+// ---- speculative greedy decoding: n-gram drafts verified by one batched pass over the weights (include/lnb.h) -------------------------
+// A verify pass of width w = draft_len + 1 is a batched decode step whose columns all alias THIS context: column i takes d_i (d_0 = the
+// current token) at position pos + i, every column has the context's caches, column 0 the context's own StepState and token word.  The
+// wq|wk|wv epilogue of a layer writes every column's K / V row before that layer's attention launch starts, so column i attends over
+// positions 0 .. pos + i: the one-token step at pos + i, the same bits (a batched column is bit-identical to its single-sequence run).
+// Rows a rejected column wrote beyond the accepted position are stale and are overwritten before anything reads them.
+static int spec_check_draft_args(int max_draft, int ngram_min, int ngram_max, int n_corpus) {
+    if (max_draft < 0 || max_draft > LNB_MAX_DRAFT) return fail("max_draft must be 0..%d (got %d)", LNB_MAX_DRAFT, max_draft);
+    if (ngram_min < 1 || ngram_min > ngram_max || ngram_max > LNB_SPEC_MAX_NGRAM)
+        return fail("n-gram lengths must satisfy 1 <= ngram_min <= ngram_max <= %d (got %d, %d)", LNB_SPEC_MAX_NGRAM, ngram_min, ngram_max);
+    if (n_corpus < 0) return fail("negative corpus length %d", n_corpus);
+    return 0;
+}
+extern "C" int lnb_ctx_set_draft(lnb_ctx* c, int max_draft, int ngram_min, int ngram_max, const int32_t* corpus, int n_corpus) {
+    if (max_draft < 0 || max_draft > LNB_MAX_DRAFT) return fail("max_draft must be 0..%d (got %d)", LNB_MAX_DRAFT, max_draft);
+    if (max_draft > 0 && spec_check_draft_args(max_draft, ngram_min, ngram_max, n_corpus)) return -1;
+    if (n_corpus < 0) return fail("negative corpus length %d", n_corpus);
+    if (!c || (n_corpus > 0 && !corpus)) return fail("null argument");
+    HIPCHK(hipSetDevice(c->m->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    hipFree(c->sp_corpus); c->sp_corpus = nullptr; c->sp_n_corpus = 0;
+    c->sp_max_draft = 0;
+    if (max_draft == 0) return 0;
+    HIPCHK(hipMalloc((void**)&c->sp_corpus, (size_t)std::max(n_corpus, 1) * 4));
+    if (n_corpus > 0) HIPCHK(hipMemcpy(c->sp_corpus, corpus, (size_t)n_corpus * 4, hipMemcpyHostToDevice));
+    c->sp_n_corpus = n_corpus; c->sp_max_draft = max_draft; c->sp_ngram_min = ngram_min; c->sp_ngram_max = ngram_max;
+    return 0;
+}
+// the per-context buffers of the drafting loop (the text head grows with the history)
+static int spec_alloc(lnb_ctx* c, int text_len) {
+    if (!c->sp_st) {
+        HIPCHK(hipMalloc((void**)&c->sp_st, (LNB_MAX_DRAFT + 1) * sizeof(StepState)));
+        HIPCHK(hipMemsetAsync(c->sp_st, 0, (LNB_MAX_DRAFT + 1) * sizeof(StepState), c->stream));
+        HIPCHK(hipMalloc((void**)&c->sp_tok, (LNB_MAX_DRAFT + 1) * 4)); HIPCHK(hipMemsetAsync(c->sp_tok, 0, (LNB_MAX_DRAFT + 1) * 4, c->stream));
+        HIPCHK(hipMalloc((void**)&c->sp_g, (LNB_MAX_DRAFT + 1) * 4));
+        HIPCHK(hipMalloc((void**)&c->sp_best, 2 * LNB_SPEC_MAX_NGRAM * 4));
+        HIPCHK(hipMalloc((void**)&c->sp_cnt, 16)); HIPCHK(hipMemsetAsync(c->sp_cnt, 0, 16, c->stream));
+        HIPCHK(hipHostMalloc((void**)&c->sp_word, 16, hipHostMallocMapped));
+        HIPCHK(hipHostGetDevicePointer((void**)&c->sp_word_dev, c->sp_word, 0));
+        HIPCHK(hipEventCreate(&c->sp_ev));
+    }
+    if (text_len > c->sp_text_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        hipFree(c->sp_text); c->sp_text = nullptr; c->sp_text_cap = 0;
+        HIPCHK(hipMalloc((void**)&c->sp_text, (size_t)text_len * 4));
+        c->sp_text_cap = text_len;
+    }
+    return 0;
+}
+// the verify batch of width w, its graph captured on first use: embedding gather of the w column tokens, the blocks, the head, the
+// columns' argmax, the commit.  With the matrix-core copy the products are its column forms, without it rows of gemm_stream_kernel.
+static int spec_verify_batch(lnb_ctx* c, int w, lnb_batch** out) {
+    if (c->sp_b[w]) { *out = c->sp_b[w]; return 0; }
+    lnb_model* m = c->m;
+    lnb_batch* b = new lnb_batch();
+    b->m = m; b->n = w; b->ctxs.assign(w, c); b->rows_form = !m->batch_enabled; b->lds_T = c->seq_len;
+    b->col_st = c->sp_st; b->col_tok = c->sp_tok;
+    if (batch_alloc(b)) { lnb_batch_destroy(b); return -1; }
+    hipGraph_t g = nullptr;
+    if (hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { lnb_batch_destroy(b); return fail("hipStreamBeginCapture failed"); }
+    int rc = 0;
+    if (lnbk_batch_embed(m->tok_embd, b->tab, b->x, w, m->a.dim, m->a.vocab_size, b->derr, b->stream) != hipSuccess) rc = fail("verify pass: embedding launch failed");
+    for (int l = m->layer_begin; l < m->layer_end && !rc; l++)
+        for (int k = K_QKV; k <= K_W2 && !rc; k++) rc = enqueue_batch_kernel(b, l, k);
+    if (!rc) rc = enqueue_batch_kernel(b, 0, K_HEAD);
+    if (!rc && lnbk_spec_argmax(b->logits, m->a.vocab_size, w, c->sp_g, b->stream) != hipSuccess) rc = fail("verify pass: argmax launch failed");
+    if (!rc && lnbk_spec_commit(c->sp_g, w, b->tab, b->stream) != hipSuccess) rc = fail("verify pass: commit launch failed");
+    hipError_t e = hipStreamEndCapture(b->stream, &g);
+    if (!rc && e == hipSuccess) e = hipGraphInstantiate(&b->graph, g, nullptr, nullptr, 0);
+    if (g) hipGraphDestroy(g);
+    if (rc || e != hipSuccess) { lnb_batch_destroy(b); return rc ? rc : fail("verify graph: %s", hipGetErrorString(e)); }
+    c->sp_b[w] = b; *out = b;
+    return 0;
+}
+static DraftParams spec_draft_params(lnb_ctx* c, int n_text, int max_steps) {
+    DraftParams p{}; p.text = c->sp_text; p.n_text = n_text; p.gen = c->dout; p.st = c->st;
+    p.corpus = c->sp_corpus; p.n_corpus = c->sp_n_corpus; p.ngram_min = c->sp_ngram_min; p.ngram_max = c->sp_ngram_max; p.max_draft = c->sp_max_draft;
+    p.max_steps = max_steps; p.seq_len = c->seq_len; p.out = c->sp_tok; p.col_st = c->sp_st; p.word = c->sp_word_dev; p.best = c->sp_best; p.cnt = c->sp_cnt;
+    return p;
+}
+extern "C" int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, int n_history, int32_t token, int start_pos, int max_steps,
+                                            int32_t* out_tokens, int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out) {
+    if (n_history < 0) return fail("negative history length %d", n_history);
+    if (max_steps <= 0) return fail("max_steps must be positive");
+    if (!c || !out_tokens || !n_generated || (n_history > 0 && !history)) return fail("null argument");
+    lnb_model* m = c->m;
+    if (!m->first() || !m->last()) return fail("speculative decoding needs a whole-model handle");
+    if (c->mode != LNB_MODE_EXACT) return fail("speculative decoding is exact-mode only: its verify pass is the batched exact step (the tolerance mode has none)");
+    if (c->top_k > 0) return fail("speculative decoding does not record token probabilities: lnb_ctx_set_token_probs(ctx, 0) first");
+    if (c->batch_users > 0) return fail("context is a member of %d live batch(es): speculative decoding runs it alone (lnb_batch_destroy first)", c->batch_users);
+    if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
+    if (stats) *stats = lnb_spec_stats{};
+    if (c->sp_max_draft == 0) {                              // drafting off: the greedy loop itself, one pass per token
+        if (decode_greedy_impl(c, token, start_pos, max_steps, out_tokens, n_generated, finished, ms_out)) return -1;
+        if (stats) stats->passes = *n_generated;
+        return 0;
+    }
+    HIPCHK(hipSetDevice(m->device));
+    if (max_steps > c->dout_cap) return fail("max_steps %d exceeds the context length %d", max_steps, c->dout_cap);
+    if (check_call(c, 1, start_pos) || check_call(c, 1, start_pos + max_steps - 1)) return -1;
+    if (token < 0 || token >= m->a.vocab_size) return fail("token id at index 0 is outside the vocabulary");
+    if (c->seq_len > c->attn_short_cap)
+        return fail("seq_len %d is beyond the %d positions the batched attention of a verify pass stages in the LDS", c->seq_len, c->attn_short_cap);
+    if (m->a.dim % 128 || m->q_dim % 128 || m->ffn_hidden % 128)
+        return fail("the verify pass streams the weights in 128-step chunks: dim (%d), n_heads*head_dim (%d) and the FFN hidden size (%d) must be multiples of 128", m->a.dim, m->q_dim, m->ffn_hidden);
+    if (!m->batch_enabled) HIPCHK(lnbk_batch_prepare());
+    const int n_text = n_history + 1;
+    if (spec_alloc(c, n_text) || capture_decode_graphs(c, start_pos, max_steps)) return -1;
+    hipStream_t st = c->stream;
+    c->tp_last_k = 0; c->tp_last_n = 0;
+    if (n_history > 0) HIPCHK(hipMemcpyAsync(c->sp_text, history, (size_t)n_history * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->sp_text + n_history, &token, 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->dtok, &token, 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(c->derr, 0, 4, st));
+    for (lnb_batch* b : c->sp_b) if (b) HIPCHK(hipMemsetAsync(b->derr, 0, 4, st));
+    HIPCHK(ctx_set_state(c, start_pos, 0, false, true));
+    c->call_T = 0;
+    const DraftParams dp = spec_draft_params(c, n_text, max_steps);
+    HIPCHK(hipEventRecord(c->ev0, st));
+    HIPCHK(lnbk_ngram_draft(&dp, st));
+    HIPCHK(hipEventRecord(c->sp_ev, st));
+    lnb_spec_stats s{};
+    int n_out = 0, fin = 0;
+    for (;;) {
+        // the one host round trip of a pass: the draft kernel's word {draft_len, n_out, finished}
+        HIPCHK(hipEventSynchronize(c->sp_ev));
+        const volatile int32_t* wd = c->sp_word;
+        const int k = wd[0]; n_out = wd[1]; fin = wd[2];
+        if (fin || n_out >= max_steps) break;
+        if (k < 0 || k > c->sp_max_draft) return fail("internal error: draft length %d", k);
+        s.passes++;
+        if (k == 0) HIPCHK(hipGraphLaunch(want_long_attention(c, 1, start_pos + n_out) ? c->graph_long : c->graph, st));
+        else {
+            lnb_batch* b = nullptr;
+            if (spec_verify_batch(c, k + 1, &b)) return -1;
+            HIPCHK(hipGraphLaunch(b->graph, st));
+            s.verify_passes++; s.drafted += k;
+        }
+        HIPCHK(lnbk_ngram_draft(&dp, st));
+        HIPCHK(hipEventRecord(c->sp_ev, st));
+    }
+    HIPCHK(hipEventRecord(c->ev1, st));
+    HIPCHK(hipMemcpyAsync(out_tokens, c->dout, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
+    int err = 0;
+    HIPCHK(hipMemcpyAsync(c->h_io + 1, c->derr, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    err |= c->h_io[1];
+    for (lnb_batch* b : c->sp_b) if (b) {
+        HIPCHK(hipMemcpyAsync(c->h_io + 1, b->derr, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        err |= c->h_io[1];
+    }
+    if (ms_out) HIPCHK(hipEventElapsedTime(ms_out, c->ev0, c->ev1));
+    c->dev_pos = -1;
+    if (err) return fail("generated token id is outside the vocabulary");
+    *n_generated = n_out;
+    if (finished) *finished = fin;
+    s.accepted = (int64_t)n_out - s.passes;                  // every pass emits its column 0 token plus the drafts it accepted
+    if (stats) *stats = s;
+    return 0;
+}
+// ngram_draft_kernel on host arrays (a test aid, as lnb_op_argmax): the draft that follows text, with no decode limits
+extern "C" int lnb_op_ngram_draft(int device, const int32_t* text, int n_text, const int32_t* corpus, int n_corpus,
+                                  int ngram_min, int ngram_max, int max_draft, int32_t* out, int* n_out) {
+    if (n_text < 0) return fail("negative text length %d", n_text);
+    if (spec_check_draft_args(max_draft, ngram_min, ngram_max, n_corpus)) return -1;
+    if ((n_text > 0 && !text) || (n_corpus > 0 && !corpus) || !out || !n_out) return fail("null argument");
+    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
+    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    int32_t *dt = nullptr, *dc = nullptr, *dout = nullptr, *dword = nullptr; int* best = nullptr; unsigned* cnt = nullptr;
+    hipError_t e = hipMalloc((void**)&dt, (size_t)std::max(n_text, 1) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&dc, (size_t)std::max(n_corpus, 1) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&dout, (LNB_MAX_DRAFT + 1) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&dword, 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&best, 2 * LNB_SPEC_MAX_NGRAM * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&cnt, 16);
+    if (e == hipSuccess) e = hipMemset(cnt, 0, 16);
+    if (e == hipSuccess && n_text > 0) e = hipMemcpy(dt, text, (size_t)n_text * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_corpus > 0) e = hipMemcpy(dc, corpus, (size_t)n_corpus * 4, hipMemcpyHostToDevice);
+    int32_t h[LNB_MAX_DRAFT + 1] = {}, word[4] = {};
+    if (e == hipSuccess) {
+        DraftParams p{}; p.text = dt; p.n_text = n_text; p.corpus = dc; p.n_corpus = n_corpus;
+        p.ngram_min = ngram_min; p.ngram_max = ngram_max; p.max_draft = max_draft; p.out = dout; p.word = dword; p.best = best; p.cnt = cnt;
+        e = lnbk_ngram_draft(&p, nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(word, dword, 12, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h, dout, sizeof h, hipMemcpyDeviceToHost);
+    hipFree(dt); hipFree(dc); hipFree(dout); hipFree(dword); hipFree(best); hipFree(cnt);
+    HIPCHK(e);
+    if (word[0] < 0 || word[0] > max_draft) return fail("internal error: draft length %d", word[0]);
+    for (int i = 0; i < word[0]; i++) out[i] = h[1 + i];
+    *n_out = word[0];
     return 0;
 }
 

@@ -240,3 +240,21 @@ struct TokProbParams {
 };
 // slices per row: a power of two (it divides LNB_TOKPROB_MAX_G, the sub-slices of the sum), about 2048 workgroups in all
 LNB_HD int lnb_tokprob_slices(int rows) { int g = LNB_TOKPROB_MAX_G; while (g > 1 && (long)g * rows > 2048) g >>= 1; return g; }
+
+// ---- speculative greedy decoding (lnb_decode_speculative_until; ngram_draft_kernel, spec_commit_kernel) ---------------------------------
+// A verify pass is a batched decode step of w = draft_len + 1 columns that all alias ONE context: column i takes d_i at position pos + i,
+// every column has the context's caches (BatchKV), column 0 its own StepState and token word, columns 1.. the context's column words.
+constexpr int LNB_SPEC_MAX_DRAFT = 15;         // = LNB_MAX_DRAFT of lnb.h: a verify pass has at most 16 columns (one matrix-core column group)
+constexpr int LNB_SPEC_MAX_NGRAM = 16;         // longest n-gram a draft is looked up with
+struct DraftParams {
+    const int32_t* text; int n_text;           // running text R = text[0, n_text) followed by the generated log gen[0, st->n_out)
+    const int32_t* gen; const StepState* st;   // st == nullptr: R = text alone and no decode limits (lnb_op_ngram_draft)
+    const int32_t* corpus; int n_corpus;       // the caller's corpus C (searched after R)
+    int ngram_min, ngram_max, max_draft;
+    int max_steps, seq_len;                    // decode: the draft is cut at max_steps - n_out - 1 and at seq_len - pos - 1
+    int32_t* out;                              // draft token i -> out[1 + i] (decode: the column token words, column 1 + i)
+    StepState* col_st;                         // decode: col_st[i].pos = pos + i for the draft's columns i = 1 .. draft_len; nullptr: none
+    int32_t* word;                             // [3] = {draft_len, n_out, finished} (decode: the host's pinned word)
+    int* best;                                 // [2 * LNB_SPEC_MAX_NGRAM]: per workgroup, the latest match start in R and in C (-1: none)
+    unsigned* cnt;                             // arrival ticket, zero between launches (the last workgroup resets it)
+};

@@ -3737,6 +3737,102 @@ __global__ __launch_bounds__(1024) void batch_argmax_kernel(const uint16_t* logi
     }
 }
 
+// ---- speculative greedy decoding (lnb_decode_speculative_until, include/lnb.h) ----------------------------------------------------------
+// A verify pass is a batched step whose w columns alias one context (DraftParams, lnb_device.h): column i's logits row is the one-token step
+// at pos + i, bit for bit.  spec_argmax_kernel: block i = ml.Argmax of column i's row (argmax_block, the greedy loop's rule).
+__global__ __launch_bounds__(1024) void spec_argmax_kernel(const uint16_t* logits, int V, int32_t* g) {
+    __shared__ float sv[1024];
+    __shared__ int si[1024];
+    const int i = blockIdx.x;
+    const int tok = argmax_block(logits + (size_t)i * V, V, sv, si);
+    if (threadIdx.x == 0) g[i] = tok;
+}
+// After the verify pass: a = the longest prefix of columns whose argmax equals the next column's input (the draft d_{i+1}); the argmax of
+// columns 0 .. a is emitted in order, exactly as a greedy step emits its token -- token log, position, the context's token word, and the stop
+// ids (the stop token is emitted and freezes the generation: nothing behind it).  Column 0 is the context's own state (tab->st[0]).
+__global__ void spec_commit_kernel(const int32_t* g, int w, const BatchTab* tab) {
+    if (threadIdx.x != 0) return;
+    StepState* st = tab->st[0];
+    if (st->finished) return;
+    int a = 0;
+    while (a < w - 1 && g[a] == *tab->dtok[a + 1]) a++;
+    for (int i = 0; i <= a; i++) {
+        const int tok = g[i];
+        const int n = st->n_out;
+        if (n < tab->dout_cap[0]) tab->dout[0][n] = tok;
+        st->n_out = n + 1;
+        st->pos = st->pos + 1;
+        *tab->dtok[0] = tok;
+        bool stop = false;
+        if (st->honour_stop) for (int k = 0; k < st->n_stop; k++) if (tok == st->stop[k]) stop = true;
+        if (stop) { st->finished = 1; break; }
+    }
+}
+DEVINL int32_t spec_text_at(const DraftParams& p, int j) { return j < p.n_text ? p.text[j] : p.gen[j - p.n_text]; }
+// N-gram (prompt lookup) draft of the next pass.  Workgroup b tries n = ngram_max - b: the latest start j in R = text ++ gen of an earlier
+// occurrence of R's last n tokens with at least one token after it (j <= L - n - 1: R's own final suffix is no match), and the same in the
+// corpus (j <= n_corpus - n - 1).  The last workgroup to arrive (agent-scope ticket) picks the longest n that matched, R before C, and takes
+// up to max_draft tokens after the match, cut at the end of its array and -- decoding -- at max_steps - n_out - 1 and seq_len - pos - 1.
+// It writes the draft into the column token words out[1 ..], the columns' positions pos + i, and {draft_len, n_out, finished}.
+__global__ __launch_bounds__(256) void ngram_draft_kernel(DraftParams p) {
+    __shared__ int32_t suf[LNB_SPEC_MAX_NGRAM];
+    __shared__ int sbest[2];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int n = p.ngram_max - b;
+    const int n_gen = p.st ? p.st->n_out : 0;
+    const int L = p.n_text + n_gen;
+    if (tid < 2) sbest[tid] = -1;
+    if (tid < n && n <= L) suf[tid] = spec_text_at(p, L - n + tid);
+    __syncthreads();
+    if (n < L) {                                             // descending per thread: its first hit is its latest
+        int mine = -1;
+        for (int j = L - n - 1 - tid; j >= 0; j -= (int)blockDim.x) {
+            bool ok = true;
+            for (int t = 0; t < n && ok; t++) ok = spec_text_at(p, j + t) == suf[t];
+            if (ok) { mine = j; break; }
+        }
+        if (mine >= 0) atomicMax(&sbest[0], mine);
+    }
+    if (n <= L && p.n_corpus > n) {
+        int mine = -1;
+        for (int j = p.n_corpus - n - 1 - tid; j >= 0; j -= (int)blockDim.x) {
+            bool ok = true;
+            for (int t = 0; t < n && ok; t++) ok = p.corpus[j + t] == suf[t];
+            if (ok) { mine = j; break; }
+        }
+        if (mine >= 0) atomicMax(&sbest[1], mine);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        p.best[2 * b] = sbest[0];
+        p.best[2 * b + 1] = sbest[1];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        const unsigned t = __hip_atomic_fetch_add(p.cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = t == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last || tid != 0) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    *p.cnt = 0;                                              // (ready for the next launch: stream order)
+    int src = -1, start = 0, avail = 0;
+    for (int q = 0; q < (int)gridDim.x && src < 0; q++) {
+        const int r = p.best[2 * q], c = p.best[2 * q + 1], nq = p.ngram_max - q;
+        if (r >= 0) { src = 0; start = r + nq; avail = L - start; }
+        else if (c >= 0) { src = 1; start = c + nq; avail = p.n_corpus - start; }
+    }
+    int k = src < 0 ? 0 : min(avail, p.max_draft);
+    int finished = 0, pos = 0;
+    if (p.st) {
+        finished = p.st->finished; pos = p.st->pos;
+        k = min(k, min(p.max_steps - n_gen - 1, p.seq_len - pos - 1));
+        if (finished || k < 0) k = 0;
+    }
+    for (int i = 0; i < k; i++) p.out[1 + i] = src == 0 ? spec_text_at(p, start + i) : p.corpus[start + i];
+    if (p.col_st) for (int i = 1; i <= k; i++) p.col_st[i].pos = pos + i;
+    p.word[0] = k; p.word[1] = n_gen; p.word[2] = finished;
+}
+
 // ---- token probabilities: what the reference's Softmax (operations_impl.go:478-511) gives for one logits row, and ml.Argmax's top k ----
 // prob(j) = f32(e_j / Z) with e_j = exp(f64(x_j)) and Z = sum_{j ascending} e_j in f64 -- the reference's serial order.  e comes from
 // a table of the host C library's exp for all 65536 bf16 patterns (p.etab), so the device evaluates no transcendental here.
@@ -4558,4 +4654,20 @@ extern "C" hipError_t lnbk_gemm_stream(const GemmParams* p, int epi, int num_cus
         case EPI_SILU_MUL: return (p && nch != 2) ? hipErrorInvalidValue : launch_gemm_stream<EPI_SILU_MUL, 2>(p, num_cus, st);
         default: return hipErrorInvalidValue;
     }
+}
+
+// speculative decoding: column argmax of a verify pass (w rows), the commit, the n-gram draft (one workgroup per n)
+extern "C" hipError_t lnbk_spec_argmax(const uint16_t* logits, int V, int w, int32_t* g, hipStream_t st) {
+    hipLaunchKernelGGL(spec_argmax_kernel, dim3((unsigned)w), dim3(1024), 0, st, logits, V, g);
+    return hipGetLastError();
+}
+extern "C" hipError_t lnbk_spec_commit(const int32_t* g, int w, const BatchTab* tab, hipStream_t st) {
+    hipLaunchKernelGGL(spec_commit_kernel, dim3(1), dim3(64), 0, st, g, w, tab);
+    return hipGetLastError();
+}
+extern "C" hipError_t lnbk_ngram_draft(const DraftParams* p, hipStream_t st) {
+    if (p->ngram_min < 1 || p->ngram_max < p->ngram_min || p->ngram_max > LNB_SPEC_MAX_NGRAM || p->max_draft < 0 || p->max_draft > LNB_SPEC_MAX_DRAFT)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ngram_draft_kernel, dim3((unsigned)(p->ngram_max - p->ngram_min + 1)), dim3(256), 0, st, *p);
+    return hipGetLastError();
 }

@@ -213,6 +213,48 @@ func (ic *InferenceContext) DecodeGreedyUntil(lt *LlamaTransformer, token TokenI
 	return out[:int(n)], fin != 0, nil
 }
 
+// SpecStats mirrors lnb_spec_stats: passes, passes that verified a draft, draft tokens verified, draft tokens emitted.
+type SpecStats struct{ Passes, VerifyPasses, Drafted, Accepted int64 }
+
+// SetDraft gives DecodeSpeculativeUntil its n-gram drafts: up to maxDraft (0..LNB_MAX_DRAFT; 0 = off, the default) tokens per pass, looked
+// up with n-grams of ngramMin..ngramMax tokens in the running text, then in corpus (copied to the device; may be empty).
+func (ic *InferenceContext) SetDraft(lt *LlamaTransformer, maxDraft int, ngramMin int, ngramMax int, corpus []TokenId) error {
+	if err := ic.attach(lt); err != nil {
+		return err
+	}
+	var p *C.int32_t
+	if len(corpus) > 0 {
+		p = (*C.int32_t)(unsafe.Pointer(&corpus[0]))
+	}
+	return lnbCall(func() C.int { return C.lnb_ctx_set_draft(ic.handle, C.int(maxDraft), C.int(ngramMin), C.int(ngramMax), p, C.int(len(corpus))) })
+}
+
+// DecodeSpeculativeUntil is DecodeGreedyUntil with drafts verified in batched passes over the weights: the same tokens, finished flag and
+// KV cache rows, fewer passes when the text repeats itself or the corpus.  history: the tokens before `token` (the prompt).
+func (ic *InferenceContext) DecodeSpeculativeUntil(lt *LlamaTransformer, history []TokenId, token TokenId, startPos int, maxSteps int) (tokens []TokenId, finished bool, stats SpecStats, err error) {
+	if maxSteps <= 0 {
+		return nil, false, stats, fmt.Errorf("max_steps must be positive")
+	}
+	if err = ic.attach(lt); err != nil {
+		return nil, false, stats, err
+	}
+	out := make([]TokenId, maxSteps)
+	var h *C.int32_t
+	if len(history) > 0 {
+		h = (*C.int32_t)(unsafe.Pointer(&history[0]))
+	}
+	var n, fin C.int
+	var st C.lnb_spec_stats
+	if err = lnbCall(func() C.int {
+		return C.lnb_decode_speculative_until(ic.handle, h, C.int(len(history)), C.int32_t(token), C.int(startPos), C.int(maxSteps),
+			(*C.int32_t)(unsafe.Pointer(&out[0])), &n, &fin, &st, nil)
+	}); err != nil {
+		return nil, false, stats, err
+	}
+	stats = SpecStats{int64(st.passes), int64(st.verify_passes), int64(st.drafted), int64(st.accepted)}
+	return out[:int(n)], fin != 0, stats, nil
+}
+
 // SetTokenProbs makes the greedy loops record, for every token they generate, the topK (0..LNB_MAX_TOP_K; 0 = off, the default) most likely
 // tokens of its logits row with their probabilities -- the bits of the reference's ml.Softmax on that row (include/lnb.h).
 func (ic *InferenceContext) SetTokenProbs(lt *LlamaTransformer, topK int) error {

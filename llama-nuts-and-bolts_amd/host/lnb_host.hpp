@@ -213,6 +213,20 @@ public:
         s.TargetLogit.resize(tokens.size()); s.TargetProb.resize(tokens.size()); s.LogZ.resize(tokens.size());
         return s;
     }
+    // speculative greedy decoding (include/lnb.h): n-gram drafts (maxDraft 0..LNB_MAX_DRAFT, 0 = off) verified in batched passes -- the tokens
+    // and KV rows of lnb_decode_greedy_until; history = the tokens before `token` (the prompt)
+    void SetDraft(int maxDraft, int ngramMin, int ngramMax, const std::vector<TokenId>& corpus = {}) {
+        check(lnb_ctx_set_draft(h_, maxDraft, ngramMin, ngramMax, corpus.empty() ? nullptr : corpus.data(), (int)corpus.size()));
+    }
+    struct Speculative { std::vector<TokenId> Tokens; bool Finished = false; lnb_spec_stats Stats{}; };
+    Speculative DecodeSpeculativeUntil(const std::vector<TokenId>& history, TokenId token, int startPos, int maxSteps) {
+        Speculative r; r.Tokens.resize(maxSteps > 0 ? maxSteps : 1);
+        int n = 0, fin = 0;
+        check(lnb_decode_speculative_until(h_, history.empty() ? nullptr : history.data(), (int)history.size(), token, startPos, maxSteps,
+                                           r.Tokens.data(), &n, &fin, &r.Stats, nullptr));
+        r.Tokens.resize(n); r.Finished = fin != 0;
+        return r;
+    }
 private:
     static void layer_cb(int layer, int n, double secs, void* user) {      // infContext.Logf(...), llamatransformer.go:163
         auto* self = (InferenceContext*)user;

@@ -64,9 +64,19 @@ EXPORTS = [
     "lnb_pipeline_init_host", "lnb_batch_boundary_ptr",
     "lnb_abi_version", "lnb_runtime_info", "lnb_profile_ffn_pair",
     "lnb_ctx_set_token_probs", "lnb_ctx_read_token_probs", "lnb_ctx_token_prob_walks", "lnb_forward_score", "lnb_op_token_probs",
+    "lnb_ctx_set_draft", "lnb_decode_speculative_until", "lnb_op_ngram_draft",
 ]
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
+MAX_DRAFT = 15           # LNB_MAX_DRAFT of include/lnb.h (tests/test_speculative_cpu.py compares them)
 ABI_VERSION = 6          # LNB_ABI_VERSION of include/lnb.h this binding was written against (tests/test_cabi.py compares it with the header's)
+
+
+class SpecStats(C.Structure):
+    """lnb_spec_stats (include/lnb.h)"""
+    _fields_ = [("passes", C.c_int64), ("verify_passes", C.c_int64), ("drafted", C.c_int64), ("accepted", C.c_int64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class RuntimeInfo(C.Structure):
@@ -169,6 +179,10 @@ def lib():
     L.lnb_ctx_token_prob_walks.argtypes = [vp, C.POINTER(C.c_int)]
     L.lnb_forward_score.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, i32p]
     L.lnb_op_token_probs.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
+    L.lnb_ctx_set_draft.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int]
+    L.lnb_decode_speculative_until.argtypes = [vp, vp, C.c_int, C.c_int32, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                               C.POINTER(SpecStats), f32p]
+    L.lnb_op_ngram_draft.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_int)]
     L.lnb_model_num_tensors.argtypes = [vp]
     L.lnb_model_tensor_info.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.lnb_checkpoint_open.argtypes = [C.c_char_p, C.POINTER(vp)]
@@ -552,6 +566,23 @@ class InferenceContext:
         _chk(self.L.lnb_ctx_read_token_probs(self.h, int(first), int(n), _p(ids), _p(lg), _p(pr), _p(lz)))
         return ids[:, :k], lg[:, :k], pr[:, :k], lz[:n]
 
+    def set_draft(self, max_draft, ngram_min=1, ngram_max=4, corpus=()):
+        """n-gram drafts for decode_speculative_until: up to max_draft (0..MAX_DRAFT; 0 = off, the default) tokens per pass, looked up with
+        n-grams of ngram_min..ngram_max tokens in the running text, then in corpus (copied to the device)"""
+        a = np.ascontiguousarray(corpus, dtype=np.int32)
+        _chk(self.L.lnb_ctx_set_draft(self.h, int(max_draft), int(ngram_min), int(ngram_max), _p(a) if a.size else None, int(a.size)))
+        return self
+
+    def decode_speculative_until(self, history, token, start_pos, max_steps):
+        """decode_greedy_until with drafts verified in batched passes (lnb_decode_speculative_until): the same tokens, logits and KV rows.
+        history: the tokens before `token` (e.g. the prompt) -> (tokens, finished flag, stats dict, device ms)"""
+        h = np.ascontiguousarray(history, dtype=np.int32)
+        out = np.empty(max_steps, dtype=np.int32)
+        ms, n, fin, st = C.c_float(0), C.c_int(0), C.c_int(0), SpecStats()
+        _chk(self.L.lnb_decode_speculative_until(self.h, _p(h) if h.size else None, int(h.size), int(token), start_pos, max_steps, _p(out),
+                                                 C.byref(n), C.byref(fin), C.byref(st), C.byref(ms)))
+        return out[:n.value].copy(), bool(fin.value), st.as_dict(), ms.value
+
     def token_prob_walks(self):
         """rows of this context (decode steps, scored rows) whose probabilities walked the reference's serial sum"""
         n = C.c_int(0)
@@ -799,6 +830,17 @@ def op_token_probs(logits_u16, top_k, targets=None, force_serial=False, device=0
     if tg is not None:
         out["target_prob"] = tp
     return out
+
+
+def op_ngram_draft(text, corpus=(), ngram_min=1, ngram_max=4, max_draft=MAX_DRAFT, device=0):
+    """ngram_draft_kernel on host arrays (lnb_op_ngram_draft): the draft that follows `text` -> int32 array"""
+    t = np.ascontiguousarray(text, dtype=np.int32)
+    c = np.ascontiguousarray(corpus, dtype=np.int32)
+    out = np.empty(max(int(max_draft), 1), dtype=np.int32)
+    n = C.c_int(0)
+    _chk(lib().lnb_op_ngram_draft(device, _p(t) if t.size else None, int(t.size), _p(c) if c.size else None, int(c.size),
+                                  int(ngram_min), int(ngram_max), int(max_draft), _p(out), C.byref(n)))
+    return out[:n.value].copy()
 
 
 def op_exp_table(divisor=1.0, device=0):
