@@ -13,7 +13,10 @@ N GPUs (torchrun, one rank per GPU): the 32 blocks are sharded by layer into N p
 RCCL point-to-point hidden-state hand-offs (llama-nuts-and-bolts_amd/pipeline.py); N independent
 sequences are kept in flight, so per-GPU bytes per step are constant ("weak" scaling).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  On one GPU a plain run (`--gpus 1 --steps K --warmup W`) does only what that line's headline needs: it
+builds the model, prefills, runs the W warm-up steps, times the K steps (`--repeats` times, the median repeat reported), writes
+`--dump-outputs` if asked and prints.  `--full` adds everything else on the same line: the oracle-golden and device self-checks, per-kernel
+times, the roofline and its measured model, the sequences in flight, configs[2], configs[4]'s shape, the runtime record and the CPU baseline.
 """
 import argparse
 import json
@@ -185,7 +188,7 @@ CFG2_P, CFG2_W, CFG2_K = 4096, 4, 64
 
 
 def configs2_record(lnb, model, cfg, args, a):
-    """BASELINE configs[2] inside the DEFAULT line, so that it is timed by whoever runs `python bench.py` (VERDICT r4 #1c): the 4096-token prompt
+    """BASELINE configs[2] inside the --full line, so that it is timed by whoever runs `python bench.py --full` (VERDICT r4 #1c): the 4096-token prompt
     in one Forward (exact chains on the f32 matrix cores), then 4 warm-up + 64 timed greedy steps at T = 4101 ... 4164 through the long-context
     attention kernels (three repeats of the same 64 steps, median), every token compared with the CPU oracle's continuation of the FULL 32-layer
     model (tests/golden/configs2_32layer_tokens.json, made once on the host by tests/golden/make_configs2_cut_tokens.py 32).  A mismatch in exact
@@ -258,7 +261,7 @@ CFG4_P, CFG4_W, CFG4_K = 16, 2, 16
 
 
 def configs4_record(lnb, args):
-    """BASELINE configs[4]'s shape (random-init Llama shape dim 8192 x 80 layers, "70B-like") on ONE GPU, inside the default line: 141 GB of synthetic
+    """BASELINE configs[4]'s shape (random-init Llama shape dim 8192 x 80 layers, "70B-like") on ONE GPU, inside the --full line: 141 GB of synthetic
     weights resident, a 16-token prompt (one Forward on the f32 matrix cores), 2 warm-up + 16 timed greedy steps (two repeats, the faster one).  The
     run's 19 tokens are compared with the CPU oracle's continuation of the FULL 80-layer model (tests/golden/configs4_80layer_tokens.json, made once on the
     GPU box's host: the oracle holds the 141 GB in memory); the 10-layer cut (one pipeline stage) is pinned too.  Next to it the device self-check: the same
@@ -438,7 +441,7 @@ def batched_sequences(lnb, model, cfg, args, a, single_run_tokens):
                                "kernel": "gemm_stream_kernel fed from the M16 copy", "first_token_same_as_headline_prefill": bool(single_run_tokens and int(tok_pf) == int(single_run_tokens[0]))}
     out["weight_bytes_resident_with_the_second_copy"] = model.weight_bytes() + model.batch_bytes()
     if args.model == "llama8b" and not args.no_configs2 and P < CFG2_P:
-        # configs[2]'s prompt again on the streaming feed (the default line's configs2.prefill ran before the copy existed)
+        # configs[2]'s prompt again on the streaming feed (the --full line's configs2.prefill ran before the copy existed)
         c2 = lnb.InferenceContext(model, CFG2_P + 8)
         p2 = lnb.synth_tokens(99, CFG2_P, cfg["vocab_size"])
         lnb._chk(lnb.lib().lnb_ctx_synchronize(c2.h))
@@ -620,15 +623,20 @@ def main():
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--prompt-len", type=int, default=128)
-    ap.add_argument("--cpu-steps", type=int, default=24, help="decode steps of the CPU baseline sample (0 = skip)")
-    ap.add_argument("--profile-iters", type=int, default=64)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the bench measures and checks on one GPU: the oracle-golden and device "
+                         "self-checks, the long run, warm / steady prefill, per-kernel times, roofline and measured model, the rocprofv3 traffic probe, "
+                         "sequences in flight (concurrent and batched), configs[2], configs[4]'s shape, runtime info and the CPU baseline. "
+                         "Without it a one-GPU run sets up, warms up, times the steps, dumps its outputs if asked and prints the headline line")
+    ap.add_argument("--cpu-steps", type=int, default=24, help="decode steps of the CPU baseline sample (0 = skip; --full only)")
+    ap.add_argument("--profile-iters", type=int, default=64, help="launches per kernel class of the per-kernel timings (--full only)")
     ap.add_argument("--repeats", type=int, default=3, help="repeats of the timed K steps; the median repeat is reported (SURVEY.md 8(d))")
-    ap.add_argument("--concurrent", type=int, default=8, help="also time this many independent prompts in flight on the one GPU (0/1 = skip)")
+    ap.add_argument("--concurrent", type=int, default=8, help="also time this many independent prompts in flight on the one GPU (0/1 = skip; --full only)")
     ap.add_argument("--batch-sizes", type=lambda v: [int(x) for x in v.split(",") if x], default=[2, 4, 8, 16, 32, 64, 128],
-                    help="also time BATCHED exact decode of this many prompts (comma list, each 1..128; empty = skip)")
-    ap.add_argument("--no-traffic-probe", action="store_true", help="do not run the rocprofv3 FETCH_SIZE pass of the dominant kernel")
-    ap.add_argument("--no-configs2", action="store_true", help="leave the configs[2] record (4096-token prompt + 64 steps, oracle-golden checked) out of the default line")
-    ap.add_argument("--no-configs4", action="store_true", help="leave the configs4_one_gpu record (the 70B-like shape, 141 GB, 16 timed steps) out of the default line")
+                    help="also time BATCHED exact decode of this many prompts (comma list, each 1..128; empty = skip; --full only)")
+    ap.add_argument("--no-traffic-probe", action="store_true", help="do not run the rocprofv3 FETCH_SIZE pass of the dominant kernel (--full only)")
+    ap.add_argument("--no-configs2", action="store_true", help="leave the configs[2] record (4096-token prompt + 64 steps, oracle-golden checked) out of the --full line")
+    ap.add_argument("--no-configs4", action="store_true", help="leave the configs4_one_gpu record (the 70B-like shape, 141 GB, 16 timed steps) out of the --full line")
     ap.add_argument("--traffic-child", default="", help=argparse.SUPPRESS)      # internal: kernel class(es) to loop under rocprofv3, comma separated
     ap.add_argument("--traffic-pos", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--model", default="llama8b", choices=["llama8b", "llama8b-2l", "llama8b-8l", "tiny", "llama70b-like"])
@@ -675,14 +683,16 @@ def main():
         return pipeline.bench_main(args, cfg, name)
 
     P, W, K = args.prompt_len, args.warmup, args.steps
-    # a short timed region (the driver passes --steps 20) is followed by a 256-step one, reported next to it (not under rocprofv3: its kernel
-    # trace has crashed inside the tool on runs of tens of thousands of graph-launched kernels)
+    # --full: a short timed region (the driver passes --steps 20) is followed by a 256-step one, reported next to it (not under rocprofv3: its
+    # kernel trace has crashed inside the tool on runs of tens of thousands of graph-launched kernels)
     K_LONG = 256 if (K < 64 and args.model in ("llama8b", "llama8b-2l", "llama8b-8l") and not os.environ.get("ROCP_TOOL_LIBRARIES")) else 0
     seq_len = P + W + K + K_LONG + 8
-    # the default line also carries configs[2] (4096-token prompt + 64 steps): one model serves both, its RoPE table long enough for either
+    # --full also carries configs[2] (4096-token prompt + 64 steps): one model serves both, its RoPE table long enough for either
     with_cfg2 = args.model == "llama8b" and P < CFG2_P and not args.no_configs2 and not os.environ.get("ROCP_TOOL_LIBRARIES")
     # ... and configs[4]'s shape on ONE GPU (141 GB resident, built after the 8B model has been released): VERDICT r5 #4b
     with_cfg4 = with_cfg2 and not args.no_configs4
+    # The context and the RoPE table are sized as above with or without --full, so that the timed steps run on the same model and context
+    # (the context's length picks the attention kernels' LDS staging) whether or not the sections after them run
     t_load = time.time()
     model = lnb.LlamaTransformer(device=0, **cfg).fill_synthetic(1234).finalize(rope_rows=max(seq_len, 2 * cfg["max_seq_len"], (CFG2_P + CFG2_W + CFG2_K + 8) if with_cfg2 else 0))
     ctx = lnb.InferenceContext(model, seq_len).set_mode(args.mode)
@@ -692,7 +702,7 @@ def main():
     _, tok = ctx.Forward(prompt, 0, want_logits=False)            # prefill (outside the timed region; reported separately)
     t_pf = time.perf_counter() - t_pf
     t_pf_warm = t_pf_steady = None
-    if P >= 16:                                                   # the same prompt again on a second context: warm prefill next to the cold first call
+    if args.full and P >= 16:                                     # the same prompt again on a second context: warm prefill next to the cold first call
         ctx_w = lnb.InferenceContext(model, P + 8).set_mode(args.mode)
         lnb._chk(lnb.lib().lnb_ctx_synchronize(ctx_w.h))
         tw = time.perf_counter()
@@ -730,12 +740,39 @@ def main():
         # the prompt (synth_tokens(99, P)) are seeded, so the same arguments give the same inputs on every run and every build
         os.makedirs(args.dump_outputs, exist_ok=True)
         np.save(os.path.join(args.dump_outputs, "decode_tokens.npy"), np.asarray(reps[-1][2], dtype=np.float64))
-    # fused-RMSNorm rows of the decode steps so far (2 per block + 1 per token) whose sum left the branch-free item walk (same bits, slower walk)
-    n_norm_rows = (W + K * len(reps)) * (2 * cfg["n_layers"] + 1)
-    norm_walk = {"rows": n_norm_rows, "fallback_rows": ctx.norm_fallbacks(), "note": "rows summed by the record walk instead of the branch-free item list (more than 64 items or non-finite terms; round 6: a leaf too close to a binade edge is replayed as single-term items inside the list)"} if args.mode == "exact" else None
     order = sorted(range(len(reps)), key=lambda i: reps[i][0])
     med = order[len(order) // 2]
     t0, t1, ev_ms, out = 0.0, reps[med][0], reps[med][1], np.array(reps[med][2], dtype=np.int32)
+    wall = t1 - t0
+    tps = K / wall
+    config = {"workload": "%s bf16, 1xMI355X, single-prompt greedy decode, seq_len=%d -> +%d tokens (%s)"
+                          % (name, P, K, ("configs[2] decode" if P >= 4096 else
+                                          "configs[1] proper: +256 tokens" if K == 256 else
+                                          "configs[1]'s prompt and kernels with the caller's --steps %d; with --full the same context's next %d steps -- configs[1]'s +256 -- are `long_run`" % (K, K_LONG) if K_LONG else
+                                          "configs[1]'s prompt, --steps %d" % K) if args.model == "llama8b" else "shape of configs[4] on one GPU" if args.model == "llama70b-like" else
+                             "configs[2] workload on the %d-layer cut the CPU oracle reaches" % cfg["n_layers"] if args.model in ("llama8b-2l", "llama8b-8l") else "test shape"),
+              "prompt_len": P, "sequences_in_flight": 1, "parallelism": "single GPU",
+              "mode": "exact-order (token-id identical to the CPU reference path)" if args.mode == "exact" else
+                      "fast (opt-in tolerance mode: split-K f32 sums, same bf16 truncation points; NOT token-identical, see NOTES.md 6.2)",
+              "hip_event_ms_per_step": round(ev_ms / K, 4),
+              "timed_region_repeats_ms_per_step": [round(1e3 * r[0] / K, 4) for r in reps], "reported_repeat": "median",
+              "weight_bytes_resident": model.weight_bytes(), "model_build_s": round(t_load, 1)}     # (+ sequences_in_flight_batched.weights_second_copy_bytes once that section has run)
+    res = {"metric": "decode tokens/s Llama-3.1-8B bf16 @1/2/4/8 MI355X; % HBM roofline", "value": round(tps, 2), "unit": "tokens/s",
+           "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": round(1000.0 * wall / K, 4), "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+           "schema": "lnb-bench/6 (without --full: the headline and its timed repeats only; --full adds roofline = the kernel symbol with the largest share of GPU time, "
+                     "configs2 = configs[2] in the same line, sequences_in_flight = throughput forms)",
+           "config": config}
+    if not args.full:
+        # the plain line: what the headline needs and nothing that takes a run of its own
+        res["last_tokens"] = [int(t) for t in out[-4:]]
+        res["prefill"] = {"rows": P, "ms": round(1e3 * t_pf, 2), "note": "the process's first call (cold); --full adds the warm and steady figures"}
+        ctx.close(); model.close()
+        print(json.dumps(res))
+        return 0
+    # fused-RMSNorm rows of the decode steps so far (2 per block + 1 per token) whose sum left the branch-free item walk (same bits, slower walk)
+    n_norm_rows = (W + K * len(reps)) * (2 * cfg["n_layers"] + 1)
+    norm_walk = {"rows": n_norm_rows, "fallback_rows": ctx.norm_fallbacks(), "note": "rows summed by the record walk instead of the branch-free item list (more than 64 items or non-finite terms; round 6: a leaf too close to a binade edge is replayed as single-term items inside the list)"} if args.mode == "exact" else None
     long_run = None
     if K_LONG:
         lnb._chk(lnb.lib().lnb_ctx_synchronize(ctx.h))
@@ -751,8 +788,6 @@ def main():
     self_check = None
     if golden_ok is None and args.model != "tiny":
         self_check = device_self_check(lnb, model, args, prompt, seq_len, [first_tok] + warm_toks + [int(t) for t in out])
-    wall = t1 - t0
-    tps = K / wall
     Tbar = pos + (K - 1) / 2.0 + 1.0
     a = {k: cfg[k] for k in ("dim", "n_layers", "n_heads", "n_kv_heads", "vocab_size")}
     B = algorithmic_bytes_per_token(a, model.ffn_hidden, Tbar)
@@ -803,23 +838,8 @@ def main():
                 "whole_step": {"achieved": round(tps * B / 1e9, 1), "frac": round(tps * B / 1e9 / PEAK_HBM_GBS, 4),
                                "algorithmic_bytes_per_token": int(B), "mean_context": Tbar,
                                "roofline_tokens_per_s": round(PEAK_HBM_GBS * 1e9 / B, 1)}}
-    res = {"metric": "decode tokens/s Llama-3.1-8B bf16 @1/2/4/8 MI355X; % HBM roofline", "value": round(tps, 2), "unit": "tokens/s",
-           "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": round(1000.0 * wall / K, 4), "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-           "schema": "lnb-bench/5 (roofline = the kernel symbol with the largest share of GPU time; configs2 = configs[2] in the same line; sequences_in_flight = throughput forms)",
-           "config": {"workload": "%s bf16, 1xMI355X, single-prompt greedy decode, seq_len=%d -> +%d tokens (%s)"
-                                  % (name, P, K, ("configs[2] decode" if P >= 4096 else
-                                                  "configs[1] proper: +256 tokens" if K == 256 else
-                                                  "configs[1]'s prompt and kernels with the caller's --steps %d; the same context's next %d steps -- configs[1]'s +256 -- are `long_run`" % (K, K_LONG) if K_LONG else
-                                                  "configs[1]'s prompt, --steps %d" % K) if args.model == "llama8b" else "shape of configs[4] on one GPU" if args.model == "llama70b-like" else
-                                     "configs[2] workload on the %d-layer cut the CPU oracle reaches" % cfg["n_layers"] if args.model in ("llama8b-2l", "llama8b-8l") else "test shape"),
-                      "prompt_len": P, "sequences_in_flight": 1, "parallelism": "single GPU",
-                      "mode": "exact-order (token-id identical to the CPU reference path)" if args.mode == "exact" else
-                              "fast (opt-in tolerance mode: split-K f32 sums, same bf16 truncation points; NOT token-identical, see NOTES.md 6.2)",
-                      "tokens_vs_oracle_golden": golden_ok, "device_self_check": self_check,
-                      "hip_event_ms_per_step": round(ev_ms / K, 4), "norm_item_walk": norm_walk,
-                      "timed_region_repeats_ms_per_step": [round(1e3 * r[0] / K, 4) for r in reps], "reported_repeat": "median",
-                      "weight_bytes_resident": model.weight_bytes(), "model_build_s": round(t_load, 1)},     # (+ sequences_in_flight_batched.weights_second_copy_bytes once that section has run)
+    config.update({"tokens_vs_oracle_golden": golden_ok, "device_self_check": self_check, "norm_item_walk": norm_walk})
+    res.update({
            "roofline": roofline, "kernels": kernels, "last_tokens": [int(t) for t in out[-4:]], "long_run": long_run,
            # prefill of the prompt: the same exact f32 chains on the matrix cores (v_mfma_f32_16x16x4_f32, bit-identical to the
            # k-ordered loop); FLOPs = 2 x rows x layer-matmul elements; peak = f32 MFMA (MI355X_MICROARCH.md: 157.3 TFLOP/s)
@@ -832,7 +852,7 @@ def main():
                        "frac_of_bf16_mfma_peak_2500": round(2.0 * P * 6979321856 / t_pf / 1e12 / 2500.0, 4) if name == "Llama-3.1-8B" else None,
                        "kernel": "gemm_stream_kernel fed from the resident weight layouts (round 5: no second copy; LNB_PREFILL_NATIVE=0 = the LDS-tiled gemm_mfma_kernel)" if args.mode == "exact" else "fast_gemm_kernel",
                        "bound": "mfma (f32, exact order: v_mfma_f32_16x16x4_f32 is the k-ordered chain; the bf16 instructions are not)" if args.mode == "exact"
-                                else "mfma (bf16, tolerance mode) / HBM at small row counts"}}
+                                else "mfma (bf16, tolerance mode) / HBM at small row counts"}})
     if args.concurrent > 1 and os.environ.get("ROCP_TOOL_LIBRARIES") and os.environ.get("LNB_BENCH_CONCURRENT_UNDER_PROFILER") != "1":
         # rocprofv3 --kernel-trace --stats of this section (8 streams x captured stage graphs) has crashed inside the tool on long runs;
         # a profile is of the headline path anyway

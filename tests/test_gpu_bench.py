@@ -1,5 +1,5 @@
-"""bench.py's contract on a real GPU (small shape, seconds): ONE JSON line on stdout with the driver's keys, the roofline and CPU-baseline
-objects, and the sequences-in-flight section."""
+"""bench.py's contract on a real GPU (small shape, seconds): ONE JSON line on stdout with the driver's keys; with --full also the roofline
+and CPU-baseline objects and the sequences-in-flight section, without it the headline alone."""
 import json
 import os
 import subprocess
@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("mode", ["exact", "fast"])
 def test_single_gpu_bench_prints_one_json_line_with_the_contract_keys(mode):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", "tiny", "--steps", "12", "--warmup", "3", "--prompt-len", "16",
-                        "--cpu-steps", "2", "--concurrent", "3", "--profile-iters", "4", "--mode", mode],
+                        "--cpu-steps", "2", "--concurrent", "3", "--profile-iters", "4", "--mode", mode, "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -54,6 +54,28 @@ def test_single_gpu_bench_prints_one_json_line_with_the_contract_keys(mode):
         assert set(sb["runs"][-1]["kernels_us"]) >= {"norm+wqkv+rope", "attention", "w2+residual", "norm+output"}
     else:
         assert "sequences_in_flight_batched" not in d
+
+
+def test_plain_single_gpu_run_prints_the_headline_and_nothing_that_needs_runs_of_its_own():
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: set up, warm up, time the K steps (three repeats, the median reported) and print
+    the line -- no checks, sections or baselines that --full adds"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "tiny", "--steps", "12", "--warmup", "3", "--prompt-len", "16"],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert key in d, key
+    assert d["unit"] == "tokens/s" and d["dtype"] == "bf16" and d["n_gpus"] == 1 and d["steps"] == 12 and d["warmup"] == 3 and d["higher_is_better"] is True
+    assert abs(d["value"] - 1000.0 / d["ms_per_step"]) / d["value"] < 0.02
+    rp = d["config"]["timed_region_repeats_ms_per_step"]
+    assert len(rp) == 3 and sorted(rp)[1] == pytest.approx(d["ms_per_step"], rel=1e-3)
+    assert len(d["last_tokens"]) == 4 and d["prefill"]["rows"] == 16 and d["prefill"]["ms"] > 0
+    for key in ("roofline", "kernels", "long_run", "cpu_baseline", "sequences_in_flight", "sequences_in_flight_batched", "configs2", "configs4_one_gpu", "runtime"):
+        assert key not in d, key
+    for key in ("tokens_vs_oracle_golden", "device_self_check", "norm_item_walk"):
+        assert key not in d["config"], key
 
 
 def test_dump_outputs_writes_the_timed_steps_tokens_and_repeats(tmp_path):
