@@ -116,7 +116,8 @@ int64_t lnb_model_weight_bytes(lnb_model* m);
 /* ---- context: replaces model.NewInferenceContext (src/model/inferencecontext.go:17-46) ---------------
  * device-resident, zero-filled CacheK/CacheV [seq_len, n_kv_heads, head_dim] bf16 per owned layer.
  * Context length: up to about 23000 positions (the long-context decode attention keeps 4 bytes per position in the LDS); head_dim 32, 64
- * or 128.  Calls of 2..15 rows use a kernel that stages 12 bytes per position and fail beyond ~7800 positions (head_dim 128; ~10800 at 64):
+ * or 128.  Calls of 2..15 rows use a kernel that stages 12 bytes per position and fail beyond ~7800 positions (head_dim 128; ~10800 at 64)
+ * (lnb_forward_append falls back to one-token steps there):
  * one-token calls and calls of 16 or more rows have no such limit. */
 int lnb_ctx_create(lnb_model* m, int seq_len, lnb_ctx** out);
 int lnb_ctx_destroy(lnb_ctx* c);
@@ -177,6 +178,30 @@ int lnb_ctx_set_layer_callback(lnb_ctx* c, lnb_layer_cb cb, void* user);
  * seq > 1 with (start_pos+seq) % seq != 0 "two tensor shapes cannot be broadcasted" (tensor.go:414-428).
  * Requires a whole-model handle (layer_begin == 0 && layer_end == n_layers). */
 int lnb_forward(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out);
+
+/* ---- causal multi-row append: extend a live context by seq tokens in ONE call, at any start position -------------------------------
+ * lnb_forward restates the reference's attention mask: the [seq, seq] upper triangle broadcast by modulo over the [seq, start_pos + seq]
+ * scores (tensoriterators.go:47-55).  At start_pos > 0 that is not a continuation of the cached text (and it is refused unless
+ * (start_pos + seq) % seq == 0); it is the correct behaviour for Forward and it stays.  lnb_forward_append is the other thing a caller wants:
+ * row i attends to every cached position 0 .. start_pos + i.
+ *   Contract: logits_out ([seq, vocab_size], may be NULL as for lnb_forward), the KV rows [start_pos, start_pos + seq) of every layer and
+ *   argmax_last_out are BIT-IDENTICAL to seq consecutive one-token lnb_forward calls at start_pos, start_pos + 1, ...; cache rows below
+ *   start_pos are read and never written.  Any seq >= 1 with start_pos + seq within the KV cache and the RoPE table is accepted: there is no
+ *   (start_pos + seq) % seq condition.  At start_pos == 0 the result equals lnb_forward of the same rows.
+ *   Why it is exact: the linear layers are per-row chains already; the reference's softmax subtracts no maximum, so a masked entry adds +0 to
+ *   the f64 sum and to the PV chain -- a row masked to j <= start_pos + i IS the shorter row of the one-token step.
+ *   Afterwards lnb_decode_greedy[_until], lnb_decode_speculative_until, lnb_batch_* and further appends continue the context.
+ *   Kernels: 16 or more rows at head_dim 64 / 128 run the matrix-core attention with the causal mask (tiles above the shifted diagonal are
+ *   skipped); 2..15 rows, and any row count at head_dim 32, the row-per-workgroup kernel.  Where that kernel cannot stage the context (see
+ *   lnb_ctx_create) the rows run as one-token steps on the long-context kernels inside the call instead of failing.
+ *   Refused, each with a message: a stage handle that is not the whole model; LNB_MODE_FAST (the tolerance mode is frozen and its flash
+ *   kernel keeps the modulo mask); NULL tokens, seq <= 0 or a negative start_pos (checked before the handle is touched); positions beyond the
+ *   KV cache or the RoPE table.
+ * lnb_forward_score_append: the same call with lnb_forward_score's outputs -- per row the target's logit and probability and ln Z, the bits
+ *   of seq one-row lnb_forward_score calls (targets[i] < 0: NaN logit and prob for that row; targets[i] >= V is an error). */
+int lnb_forward_append(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out);
+int lnb_forward_score_append(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, const int32_t* targets,
+                             float* target_logit, float* target_prob, double* log_z, int32_t* argmax_last_out);
 
 /* ---- greedy loop on the device: the decode half of InferenceEngine.generateTokensInternal
  * (src/inference/inference.go:194-252).  Starting from `token` at position start_pos (its KV is computed by

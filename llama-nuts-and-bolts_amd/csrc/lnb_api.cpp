@@ -173,6 +173,7 @@ struct lnb_ctx {
     hipEvent_t ev_done = nullptr, ev_in = nullptr, ev_sent = nullptr;
     bool in_pending = false, sent_pending = false;
     int dev_pos = -1;                      // position the device-side StepState will hold when the stream reaches this point (-1: unknown)
+    bool attn_causal = false;              // set by lnb_forward_append around its multi-row call: the attention launches take the true causal mask (AttnParams::causal)
     int call_T = 0;                        // start_pos + rows of the call being enqueued (0: not known to the host, e.g. inside a replayed graph)
     hipEvent_t ev_h2d = nullptr; bool h2d_pending = false;   // the last copy out of the pinned staging words h_io[2..] (enqueue-only paths)
     bool recv_unmatched = false;           // in-process transport: a receive into this context is posted and its sender has not arrived yet
@@ -868,6 +869,7 @@ static int enqueue_layer_kernel(lnb_ctx* c, int l, int S, int which, hipStream_t
         ap.host_T = c->call_T;
         ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));           // llamatransformer.go:464
         ap.mfma = use_mfma(S) ? 1 : 0; ap.exp_tab = m->exp_tab;
+        ap.causal = (c->attn_causal && S > 1) ? 1 : 0;
         ap.longctx = 0; ap.force_zseq = c->force_zseq & 1; ap.e_buf = c->e_buf; ap.z_part = c->z_part; ap.zseq_count = c->zseq_count; ap.cnt = c->attn_cnt;
         if (ap.mfma && c->sidx_jt > 0 && c->call_T > 0 && c->sidx_jt * 16 >= c->call_T) { ap.score_idx = c->score_idx; ap.sidx_jt = c->sidx_jt; }     // (round 6: scores once, attn_mfma3_kernel)
         if (S == 1 && c->attn_long) {
@@ -936,13 +938,13 @@ static int enqueue_head(lnb_ctx* c, int first, int rows) {
 static bool want_long_attention(const lnb_ctx* c, int seq, int start_pos) {
     return seq == 1 && (start_pos + 1 > c->attn_long_T || start_pos + 1 > c->attn_short_cap);
 }
-static int check_call(lnb_ctx* c, int seq, int start_pos) {
+static int check_call(lnb_ctx* c, int seq, int start_pos, bool causal = false) {
     if (seq == 0) return fail("empty token array");                                            // llamatransformer.go:146-148
     if (seq < 0 || start_pos < 0) return fail("negative sequence length or start position");
     const int T = start_pos + seq;
     if (T > c->m->cis_rows) return fail("incompatible locStart, locEnd values and tensor (position %d beyond the %d-row RoPE table)", T, c->m->cis_rows);
     if (T > c->seq_len) return fail("incompatible locStart, locEnd values and tensor (position %d beyond the KV cache of %d)", T, c->seq_len);
-    if (seq > 1 && T % seq != 0) return fail("two tensor shapes cannot be broadcasted: [%d %d %d] and [%d %d]", c->m->a.n_heads, seq, T, seq, seq);
+    if (seq > 1 && !causal && T % seq != 0) return fail("two tensor shapes cannot be broadcasted: [%d %d %d] and [%d %d]", c->m->a.n_heads, seq, T, seq, seq);
     // calls of 2.. rows that do NOT run on the matrix-core attention (fewer than 16 rows, or head_dim 32, which attn_mfma_kernel does not
     // take) go through the row-per-workgroup kernel, whose LDS arrays are sized for attn_short_cap positions
     const bool mfma_attn = use_mfma(seq) && (c->m->head_dim == 64 || c->m->head_dim == 128);
@@ -1038,16 +1040,19 @@ static TokProbParams tp_params(const lnb_model* m, const uint16_t* logits, int r
 
 // lnb_forward_score: per row, the target's logit and probability and the row's ln Z, on the device instead of the logits copy
 struct ScoreReq { const int32_t* targets; float* tlogit; float* tprob; double* log_z; };
-static int forward_stage_impl(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out, const ScoreReq* sc);
+static int forward_stage_impl(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out, const ScoreReq* sc, bool causal = false);
 extern "C" int lnb_forward_stage(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out) {
     return forward_stage_impl(c, tokens, seq, start_pos, logits_out, argmax_last_out, nullptr);
 }
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-static int forward_stage_impl(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out, const ScoreReq* sc) {
+// causal (lnb_forward_append): the multi-row attention takes the true causal mask with an offset instead of the reference's modulo broadcast
+static int forward_stage_impl(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out, const ScoreReq* sc, bool causal) {
     if (!c) return fail("null argument");
     lnb_model* m = c->m; const int V = m->a.vocab_size;
     HIPCHK(hipSetDevice(m->device));
-    if (check_call(c, seq, start_pos)) return -1;
+    if (check_call(c, seq, start_pos, causal)) return -1;
+    struct CausalScope { lnb_ctx* c; ~CausalScope() { c->attn_causal = false; } } causal_scope{c};       // (every return below leaves the context on the reference's mask)
+    c->attn_causal = causal;
     if (tokens && !m->first()) return fail("tokens given to a stage that does not own tok_embeddings");
     if (!tokens && m->first()) return fail("first stage needs tokens");
     if ((logits_out || argmax_last_out) && !m->last()) return fail("logits requested from a stage that does not own output.weight");
@@ -1123,6 +1128,46 @@ extern "C" int lnb_forward(lnb_ctx* c, const int32_t* tokens, int seq, int start
     if (!c || !tokens) return fail("null argument");
     if (!c->m->first() || !c->m->last()) return fail("lnb_forward needs a whole-model handle; use lnb_forward_stage for pipeline stages");
     return lnb_forward_stage(c, tokens, seq, start_pos, logits_out, argmax_last_out);
+}
+
+// lnb_forward_append / lnb_forward_score_append: `seq` rows at ANY start position under the true causal mask -- row i is the one-token step at
+// start_pos + i (include/lnb.h).  One multi-row call where the attention kernels take it; where they do not (2..15 rows, or any row count at head_dim 32,
+// with a context beyond what the row-per-workgroup kernel stages in the LDS) the rows run as the one-token steps they are defined by, on the long-context kernels.
+static int forward_append_impl(lnb_ctx* c, const char* name, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out, const ScoreReq* sc) {
+    if (!tokens) return fail("%s: null argument (tokens)", name);
+    if (seq <= 0) return fail("%s: seq must be positive (got %d)", name, seq);
+    if (start_pos < 0) return fail("%s: negative start position %d", name, start_pos);
+    if (!c) return fail("%s: null argument (context)", name);
+    lnb_model* m = c->m;
+    if (!m->first() || !m->last()) return fail("%s needs a whole-model handle: pipeline stages have no append", name);
+    if (c->mode != LNB_MODE_EXACT) return fail("%s is exact-mode only: the tolerance mode is frozen and its flash attention keeps the modulo mask", name);
+    if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
+    const int T = start_pos + seq, V = m->a.vocab_size;
+    if (T > m->cis_rows) return fail("%s: position %d is beyond the %d-row RoPE table", name, T, m->cis_rows);
+    if (T > c->seq_len) return fail("%s: position %d is beyond the KV cache of %d", name, T, c->seq_len);
+    const bool mfma_attn = use_mfma(seq) && (m->head_dim == 64 || m->head_dim == 128);
+    if (seq == 1 || (!mfma_attn && T > c->attn_short_cap)) {
+        for (int i = 0; i < seq; i++) {
+            ScoreReq s1{}; if (sc) s1 = ScoreReq{sc->targets + i, sc->tlogit + i, sc->tprob + i, sc->log_z + i};
+            if (forward_stage_impl(c, tokens + i, 1, start_pos + i, logits_out ? logits_out + (size_t)i * V : nullptr, i == seq - 1 ? argmax_last_out : nullptr, sc ? &s1 : nullptr)) return -1;
+        }
+        return 0;
+    }
+    return forward_stage_impl(c, tokens, seq, start_pos, logits_out, argmax_last_out, sc, true);
+}
+extern "C" int lnb_forward_append(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out) {
+    return forward_append_impl(c, "lnb_forward_append", tokens, seq, start_pos, logits_out, argmax_last_out, nullptr);
+}
+extern "C" int lnb_forward_score_append(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, const int32_t* targets,
+                                        float* target_logit, float* target_prob, double* log_z, int32_t* argmax_last_out) {
+    if (!tokens || !targets || !target_logit || !target_prob || !log_z) return fail("lnb_forward_score_append: null argument");
+    if (seq <= 0) return fail("lnb_forward_score_append: seq must be positive (got %d)", seq);
+    if (start_pos < 0) return fail("lnb_forward_score_append: negative start position %d", start_pos);
+    if (!c) return fail("lnb_forward_score_append: null argument (context)");
+    for (int i = 0; i < seq; i++)
+        if (targets[i] >= c->m->a.vocab_size) return fail("target id %d at index %d is outside the vocabulary (a negative id: no target)", targets[i], i);
+    const ScoreReq sc{targets, target_logit, target_prob, log_z};
+    return forward_append_impl(c, "lnb_forward_score_append", tokens, seq, start_pos, nullptr, argmax_last_out, &sc);
 }
 
 // one decode step = embed(token on device) -> layers -> head -> [token probabilities] -> argmax that feeds the next step

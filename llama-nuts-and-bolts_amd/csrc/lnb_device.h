@@ -152,6 +152,8 @@ struct AttnParams {
     uint64_t* score_idx;         // round 6, prefill (attn_mfma3_kernel): [H][ceil(S/16)][sidx_jt][64 lanes] x 8 bytes -- the sixteen-bit exp-table indices of pass 1, read back by pass 2; nullptr: attn_mfma_kernel (scores twice)
     int sidx_jt;                // position tiles per (head, query tile) strip of score_idx
     int touch;                  // round 6, long-context decode: 1 = the scores launch touches its layer's V rows for the PV launch that follows, from a workgroup on the XCD whose L2 the PV workgroups read
+    int causal;                 // multi-row call of lnb_forward_append: 1 = the TRUE causal mask with an offset (row i sees positions 0 .. st->pos + i, i.e. row i is the one-token
+                                // step at st->pos + i); 0 = the reference's [S,S] mask broadcast by modulo (lnb_forward).  Set by the entry point, never inferred from the position
     int head_major;             // batched dense grid: 1 = head-major dispatch order inside an XCD (the round-3 order), 0 = sequence-major (the heads of a KV head back to back)
 };
 

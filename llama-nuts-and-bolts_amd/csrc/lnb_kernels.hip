@@ -1862,6 +1862,10 @@ extern "C" hipError_t lnbk_exp_table(double* tab, float divisor, hipStream_t st)
 //           consecutive output dims n*HD/16.., so one 16 B load of a V row feeds its eight MFMAs).
 // Masked positions (j % S > i, the modulo-broadcast [S,S] mask) contribute e = 0 -> p = +0; acc + (+-0) == acc and acc is never -0,
 // so with the standard causal layout (pos0 == 0) the tiles above the diagonal are skipped like attn_exact_kernel does.
+// CAUSAL (lnb_forward_append, AttnParams::causal; a template parameter, so the modulo form's instantiation is the code it was): the mask is
+// j > pos0 + irow at ANY pos0.  The softmax subtracts no maximum and a masked entry adds +0 to the f64 sum and to the PV chain, so row i of the
+// call is the shorter row of the one-token step at pos0 + i, bit for bit; tiles wholly above the SHIFTED diagonal are skipped
+// (Tmax = min(pos0 + i0 + 16, T)), the longest rows are still handed out first.  attn_mfma3_kernel has the same parameter.
 // K cache layout [kv head][d/8][position][8]: a lane (j, kk) loads its position's 16 B units and picks elements kk and 4+kk
 // (k-groups 2c, 2c+1) with one v_perm_b32 each; the four kk-lanes of a position load the same unit (L1 traffic, not HBM).
 // grid (H, ceil(S/64)), block 256 = 4 independent waves (no workgroup barrier anywhere).
@@ -1889,7 +1893,7 @@ DEVINL void xcd_head_block_bmajor(int& h, int& b) {
     } else { h = (int)blockIdx.x; b = (int)blockIdx.y; }
 }
 constexpr int ATM_ET = 144, ATM_PT = 80, ATM_WLDS = 16 * ATM_ET + 16 * ATM_PT + 128;     // per-wave LDS patch: e tile | p tile | Z row
-template <int HD> __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(AttnParams p) {
+template <int HD, bool CAUSAL = false> __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(AttnParams p) {
     __shared__ __attribute__((aligned(16))) char sm[4 * ATM_WLDS];
     constexpr int NK = HD / 8, DPL = HD / 16;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1909,7 +1913,8 @@ template <int HD> __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(Att
     const uint16_t* vbase = p.cache_v + (size_t)kvh * HD + fi * DPL;
     const size_t vrow = (size_t)KVH * HD;
     const uint32_t sel = 0x0c0cu | ((uint32_t)(2 * fk) << 16) | ((uint32_t)(2 * fk + 1) << 24);   // element kk of a 4-element word pair
-    const int Tmax = (S > 1 && pos0 == 0) ? (i0 + 16 < T ? i0 + 16 : T) : T;
+    const int Tmax = CAUSAL ? (pos0 + i0 + 16 < T ? pos0 + i0 + 16 : T)      // the shifted diagonal: tiles wholly above it are skipped at every start position
+                            : (S > 1 && pos0 == 0) ? (i0 + 16 < T ? i0 + 16 : T) : T;
     const int NJ = (Tmax + 15) >> 4;
     const int irow = i0 + fi;                                // this lane's query row in the S^T tile (column i)
 
@@ -1943,7 +1948,8 @@ template <int HD> __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(Att
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int j = j0 + 4 * fk + r;
-            const bool dead = j >= T || ((S > 1) && ((pos0 == 0 ? j : j % S) > irow));   // triu(-inf,1) broadcast by modulo (tensoriterators.go:47-55);
+            const bool dead = CAUSAL ? j > pos0 + irow || j >= T                       // row irow is the one-token step at pos0 + irow: positions 0 .. pos0 + irow
+                                     : j >= T || ((S > 1) && ((pos0 == 0 ? j : j % S) > irow));   // triu(-inf,1) broadcast by modulo (tensoriterators.go:47-55);
                                                                                          // pos0 == 0: T == S, no wrap (uniform branch, saves the division)
             const double ev = p.exp_tab[bf_trunc(acc[r])];                       // / sqrt(hd) :464, (+ mask 0 :469-473), exp impl:498: tabulated
             e[r] = dead ? 0.0 : ev;                                              // exp(-inf) == 0
@@ -2056,7 +2062,7 @@ DEVINL const char* atm_uniform(const char* a) {             // a pointer that IS
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
     return (const char*)(((size_t)hi << 32) | lo);
 }
-template <int HD> __global__ __launch_bounds__(256, 2) void attn_mfma3_kernel(AttnParams p) {
+template <int HD, bool CAUSAL = false> __global__ __launch_bounds__(256, 2) void attn_mfma3_kernel(AttnParams p) {
     __shared__ __attribute__((aligned(16))) char sm[4 * ATM_WLDS];
     constexpr int NK = HD / 8, DPL = HD / 16;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -2073,7 +2079,8 @@ template <int HD> __global__ __launch_bounds__(256, 2) void attn_mfma3_kernel(At
     char* pt = et + 16 * ATM_ET;
     double* zrow = (double*)(pt + 16 * ATM_PT);
     const uint32_t sel = 0x0c0cu | ((uint32_t)(2 * fk) << 16) | ((uint32_t)(2 * fk + 1) << 24);   // element kk of a 4-element word pair
-    const int Tmax = (S > 1 && pos0 == 0) ? (i0 + 16 < T ? i0 + 16 : T) : T;
+    const int Tmax = CAUSAL ? (pos0 + i0 + 16 < T ? pos0 + i0 + 16 : T)      // the shifted diagonal: tiles wholly above it are skipped at every start position
+                            : (S > 1 && pos0 == 0) ? (i0 + 16 < T ? i0 + 16 : T) : T;
     const int NJ = (Tmax + 15) >> 4;
     const int irow = i0 + fi;                                // this lane's query row in the S^T tile (column i)
     const char* const kb = atm_uniform((const char*)p.cache_k + (size_t)kvh * NK * p.seq_len * 16);            // K runs of the KV head: [d / 8][position][8]
@@ -2158,7 +2165,8 @@ template <int HD> __global__ __launch_bounds__(256, 2) void attn_mfma3_kernel(At
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int j = j0 + 4 * fk + r;
-            const bool dead = j >= T || ((S > 1) && ((pos0 == 0 ? j : j % S) > irow));   // triu(-inf,1) broadcast by modulo (tensoriterators.go:47-55)
+            const bool dead = CAUSAL ? j > pos0 + irow || j >= T                       // row irow is the one-token step at pos0 + irow: positions 0 .. pos0 + irow
+                                     : j >= T || ((S > 1) && ((pos0 == 0 ? j : j % S) > irow));   // triu(-inf,1) broadcast by modulo (tensoriterators.go:47-55)
             ix[r] = dead ? 0xFF80u : (unsigned)bf_trunc(sc[r]);                          // -inf: exp == 0 (the mask's -inf added to the score, :469-473)
         }
         asm volatile("" : "+v"(ix[0]), "+v"(ix[1]), "+v"(ix[2]), "+v"(ix[3]));
@@ -2637,7 +2645,7 @@ DEVINL double attn_zseq_wave(const double* e, int T) {
 // DENSE = the batched decode's heads x sequences grids (thousands of workgroups): registers for TWO workgroups per CU (4 waves per SIMD, 128
 // VGPRs) instead of one -- the K rows of the next 512 positions are then NOT kept in flight during a pass's score chains (the ping-pong
 // buffer is 64 of the 178 VGPRs of the single stream's form, which launches 32 workgroups on 256 CUs and wants every register)
-template <int HD, bool DENSE = false> __global__ __launch_bounds__(ATT_NT, DENSE ? 4 : 2) void attn_exact_kernel(AttnParams p) {
+template <int HD, bool DENSE = false, bool CAUSAL = false> __global__ __launch_bounds__(ATT_NT, DENSE ? 4 : 2) void attn_exact_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NK = HD / 8;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -2649,9 +2657,10 @@ template <int HD, bool DENSE = false> __global__ __launch_bounds__(ATT_NT, DENSE
     if (DENSE && !p.head_major) xcd_head_block_bmajor(h, i); else xcd_head_block(h, i);
     // batched decode: query row i is the one new token of SEQUENCE i of the batch -- its own position, caches and cache length
     const BatchTab* const bt = p.btab;
-    const int S = bt ? 1 : p.S, KVH = p.KVH;
+    // CAUSAL (lnb_forward_append): query row i IS the one-token step at position st->pos + i -- the same program as a call of one row there
+    const int S = (bt || CAUSAL) ? 1 : p.S, KVH = p.KVH;
     const int seq_len = bt ? bt->seq_len[i] : p.seq_len;
-    const int pos0 = bt ? bt->st[i]->pos : p.st->pos, T = pos0 + S;
+    const int pos0 = bt ? bt->st[i]->pos : CAUSAL ? p.st->pos + i : p.st->pos, T = pos0 + S;
     const int kvh = h / (p.H / KVH);
     double* e = (double*)smem;
     float* pw = (float*)(smem + attn_off_pw(p.lds_T));
@@ -4316,6 +4325,9 @@ extern "C" hipError_t lnbk_init(void) {
     if ((e = hipFuncSetAttribute((const void*)attn_gqa_kernel<128, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)attn_exact_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)attn_exact_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)attn_exact_kernel<128, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)attn_exact_kernel<64, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)attn_exact_kernel<32, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)attn_long_pv_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)attn_long_pv_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)attn_long_pv_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
@@ -4382,17 +4394,25 @@ extern "C" hipError_t lnbk_attn(const AttnParams* p, hipStream_t st) {
     if (p->mfma && p->S >= 16 && (p->hd == 128 || p->hd == 64)) {       // prefill: 16 (attn_mfma_kernel) or 32 (attn_mfma2_kernel, round 6) query rows per wave on the matrix cores
         const char* e2 = getenv("LNB_ATTN_MFMA2");                        // 0: never the two-tile form; N > 0: from N rows on (default ATM2_MIN_S)
         const int min2 = (e2 && *e2) ? atoi(e2) : ATM2_MIN_S;              // (default 0 = off: measured slower, see attn_mfma2_kernel)
-        if (min2 > 0 && p->S >= min2) {
+        if (min2 > 0 && p->S >= min2 && !p->causal) {                      // (the opt-in two-tile form has no causal instantiation: an append never selects it)
             if (p->hd == 128) hipLaunchKernelGGL(attn_mfma2_kernel<128>, dim3(p->H, (p->S + 127) / 128), dim3(256), 0, st, *p);
             else hipLaunchKernelGGL(attn_mfma2_kernel<64>, dim3(p->H, (p->S + 127) / 128), dim3(256), 0, st, *p);
             return hipGetLastError();
         }
         if (p->score_idx && p->host_T > 0 && p->sidx_jt * 16 >= p->host_T) {              // round 6: scores once, indices kept (the caller sized the scratch for this call's context)
-            if (p->hd == 128) hipLaunchKernelGGL(attn_mfma3_kernel<128>, dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
+            if (p->causal) {                                                              // lnb_forward_append: the true causal mask with an offset (a template instantiation of
+                if (p->hd == 128) hipLaunchKernelGGL((attn_mfma3_kernel<128, true>), dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);      // its own: the modulo form's code is untouched)
+                else hipLaunchKernelGGL((attn_mfma3_kernel<64, true>), dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
+            }
+            else if (p->hd == 128) hipLaunchKernelGGL(attn_mfma3_kernel<128>, dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
             else hipLaunchKernelGGL(attn_mfma3_kernel<64>, dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
             return hipGetLastError();
         }
-        if (p->hd == 128) hipLaunchKernelGGL(attn_mfma_kernel<128>, dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
+        if (p->causal) {
+            if (p->hd == 128) hipLaunchKernelGGL((attn_mfma_kernel<128, true>), dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
+            else hipLaunchKernelGGL((attn_mfma_kernel<64, true>), dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
+        }
+        else if (p->hd == 128) hipLaunchKernelGGL(attn_mfma_kernel<128>, dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
         else hipLaunchKernelGGL(attn_mfma_kernel<64>, dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
         return hipGetLastError();
     }
@@ -4412,6 +4432,15 @@ extern "C" hipError_t lnbk_attn(const AttnParams* p, hipStream_t st) {
             hipLaunchKernelGGL((attn_gqa_kernel<128, 4>), dim3(p->KVH, p->S), dim3(512), gl, st, q);
             return hipGetLastError();
         }
+    }
+    if (p->causal && !p->btab && p->S > 1) {                    // lnb_forward_append, 2..15 rows (any row count at head_dim 32): workgroup (h, i) runs the one-token step at pos + i
+        switch (p->hd) {
+        case 128: hipLaunchKernelGGL((attn_exact_kernel<128, false, true>), dim3(p->H, p->S), dim3(ATT_NT), lds, st, *p); break;
+        case 64: hipLaunchKernelGGL((attn_exact_kernel<64, false, true>), dim3(p->H, p->S), dim3(ATT_NT), lds, st, *p); break;
+        case 32: hipLaunchKernelGGL((attn_exact_kernel<32, false, true>), dim3(p->H, p->S), dim3(ATT_NT), lds, st, *p); break;
+        default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
     }
     switch (p->hd) {
     case 128:

@@ -221,3 +221,36 @@ func (lt *LlamaTransformer) Forward(infContext *InferenceContext, inputTokens *m
 	runtime.KeepAlive(inputTokens)
 	return output, nil
 }
+
+// ForwardAppend extends a live context by inputTokens.Size[0] rows at ANY startPos under the true causal mask (lnb_forward_append): row i is the
+// one-token Forward at startPos+i, bit for bit (logits and KV rows), and there is no (startPos+seq) % seq condition.  Forward above keeps the
+// reference's modulo-broadcast mask (src/ml/tensoriterators.go:47-55) and is what the reference's callers get; this is an addition for
+// chunked prompts, later chat turns and shared prefixes.
+func (lt *LlamaTransformer) ForwardAppend(infContext *InferenceContext, inputTokens *ml.Tensor, startPos int) (*ml.Tensor, error) {
+	if inputTokens.Size[0] == 0 {
+		return nil, fmt.Errorf("empty token array")
+	}
+	if err := infContext.attach(lt); err != nil {
+		return nil, err
+	}
+	seq := inputTokens.Size[0]
+	output := ml.NewEmptyTensor([]int{seq, lt.args.VocabSize}, ml.DT_F32)
+	release, err := infContext.installLayerHook()
+	if err != nil {
+		return nil, err
+	}
+	defer release()
+	if err := lnbCall(func() C.int {
+		return C.lnb_forward_append(infContext.handle, (*C.int32_t)(unsafe.Pointer(&inputTokens.RawData[0])), C.int(seq), C.int(startPos),
+			(*C.float)(unsafe.Pointer(&output.RawData[0])), nil)
+	}); err != nil {
+		return nil, err
+	}
+	if infContext.MirrorCaches {
+		if err := infContext.SyncCachesFromDevice(); err != nil {
+			return nil, err
+		}
+	}
+	runtime.KeepAlive(inputTokens)
+	return output, nil
+}

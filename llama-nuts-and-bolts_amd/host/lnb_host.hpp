@@ -213,6 +213,14 @@ public:
         s.TargetLogit.resize(tokens.size()); s.TargetProb.resize(tokens.size()); s.LogZ.resize(tokens.size());
         return s;
     }
+    // lnb_forward_score_append: ScoreTokens of rows appended at ANY startPos under the true causal mask -- the bits of one-row ScoreTokens calls
+    Score ScoreAppend(const std::vector<TokenId>& tokens, int startPos, const std::vector<TokenId>& targets) {
+        if (targets.size() != tokens.size()) throw std::runtime_error("ScoreAppend: one target per token");
+        Score s; s.TargetLogit.resize(tokens.size() + 1); s.TargetProb.resize(tokens.size() + 1); s.LogZ.resize(tokens.size() + 1);
+        check(lnb_forward_score_append(h_, tokens.data(), (int)tokens.size(), startPos, targets.data(), s.TargetLogit.data(), s.TargetProb.data(), s.LogZ.data(), &s.ArgmaxLast));
+        s.TargetLogit.resize(tokens.size()); s.TargetProb.resize(tokens.size()); s.LogZ.resize(tokens.size());
+        return s;
+    }
     // speculative greedy decoding (include/lnb.h): n-gram drafts (maxDraft 0..LNB_MAX_DRAFT, 0 = off) verified in batched passes -- the tokens
     // and KV rows of lnb_decode_greedy_until; history = the tokens before `token` (the prompt)
     void SetDraft(int maxDraft, int ngramMin, int ngramMax, const std::vector<TokenId>& corpus = {}) {
@@ -246,6 +254,14 @@ private:
 inline std::vector<float> Forward(const LlamaTransformer& t, InferenceContext& ctx, const std::vector<TokenId>& inputTokens, int startPos) {
     std::vector<float> logits(inputTokens.size() * (size_t)t.Args().VocabSize);
     check(lnb_forward(ctx.handle(), inputTokens.data(), (int)inputTokens.size(), startPos, logits.data(), nullptr));
+    return logits;
+}
+
+// lnb_forward_append: extend a live context by inputTokens.size() rows at ANY startPos under the true causal mask -- row i is the one-token
+// Forward at startPos + i, bit for bit (logits, KV rows); no (startPos + seq) % seq condition.  Forward itself keeps the reference's mask.
+inline std::vector<float> ForwardAppend(const LlamaTransformer& t, InferenceContext& ctx, const std::vector<TokenId>& inputTokens, int startPos, TokenId* argmaxLast = nullptr) {
+    std::vector<float> logits(inputTokens.size() * (size_t)t.Args().VocabSize);
+    check(lnb_forward_append(ctx.handle(), inputTokens.data(), (int)inputTokens.size(), startPos, logits.data(), argmaxLast));
     return logits;
 }
 

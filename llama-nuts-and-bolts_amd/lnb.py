@@ -64,6 +64,7 @@ EXPORTS = [
     "lnb_pipeline_init_host", "lnb_batch_boundary_ptr",
     "lnb_abi_version", "lnb_runtime_info", "lnb_profile_ffn_pair",
     "lnb_ctx_set_token_probs", "lnb_ctx_read_token_probs", "lnb_ctx_token_prob_walks", "lnb_forward_score", "lnb_op_token_probs",
+    "lnb_forward_append", "lnb_forward_score_append",
     "lnb_ctx_set_draft", "lnb_decode_speculative_until", "lnb_op_ngram_draft",
 ]
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
@@ -178,6 +179,8 @@ def lib():
     L.lnb_ctx_read_token_probs.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.lnb_ctx_token_prob_walks.argtypes = [vp, C.POINTER(C.c_int)]
     L.lnb_forward_score.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, i32p]
+    L.lnb_forward_append.argtypes = [vp, vp, C.c_int, C.c_int, vp, i32p]
+    L.lnb_forward_score_append.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, i32p]
     L.lnb_op_token_probs.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.lnb_ctx_set_draft.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int]
     L.lnb_decode_speculative_until.argtypes = [vp, vp, C.c_int, C.c_int32, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -512,6 +515,16 @@ class InferenceContext:
         _chk(self.L.lnb_forward(self.h, _p(tok), S, start_pos, _p(logits) if want_logits else None, C.byref(am)))
         return logits, am.value
 
+    def ForwardAppend(self, tokens, start_pos, want_logits=True):
+        """Extend the context by len(tokens) rows at ANY start_pos under the true causal mask (lnb_forward_append): row i is the one-token
+        Forward at start_pos + i, bit for bit -> (logits f32 [S,V] | None, argmax of last row)."""
+        tok = np.ascontiguousarray(tokens, dtype=np.int32)
+        S, V = tok.size, self.t.args.vocab_size
+        logits = np.empty((S, V), dtype=np.float32) if want_logits else None
+        am = C.c_int32(-2)
+        _chk(self.L.lnb_forward_append(self.h, _p(tok) if S else None, S, start_pos, _p(logits) if want_logits and S else None, C.byref(am)))
+        return logits, am.value
+
     def decode_greedy(self, token, start_pos, n_steps):
         out = np.empty(n_steps, dtype=np.int32)
         ms = C.c_float(0)
@@ -600,6 +613,19 @@ class InferenceContext:
         tl = np.empty(max(S, 1), dtype=np.float32); tp = np.empty(max(S, 1), dtype=np.float32); lz = np.empty(max(S, 1), dtype=np.float64)
         am = C.c_int32(-2)
         _chk(self.L.lnb_forward_score(self.h, _p(tok), S, start_pos, _p(tg), _p(tl), _p(tp), _p(lz), C.byref(am)))
+        return tl[:S], tp[:S], lz[:S], am.value
+
+    def score_append(self, tokens, start_pos, targets):
+        """score() of rows appended at any start_pos under the true causal mask (lnb_forward_score_append): the bits of one-row score calls
+        -> (target_logit f32 [S], target_prob f32 [S], log_z f64 [S], argmax of the last row)"""
+        tok = np.ascontiguousarray(tokens, dtype=np.int32)
+        tg = np.ascontiguousarray(targets, dtype=np.int32)
+        S = tok.size
+        if tg.size != S:
+            raise LnbError("score_append: %d targets for %d tokens" % (tg.size, S))
+        tl = np.empty(max(S, 1), dtype=np.float32); tp = np.empty(max(S, 1), dtype=np.float32); lz = np.empty(max(S, 1), dtype=np.float64)
+        am = C.c_int32(-2)
+        _chk(self.L.lnb_forward_score_append(self.h, _p(tok) if S else None, S, start_pos, _p(tg), _p(tl), _p(tp), _p(lz), C.byref(am)))
         return tl[:S], tp[:S], lz[:S], am.value
 
     def CacheK(self, layer):
@@ -745,10 +771,14 @@ class Pipeline:
 
 class InferenceEngine:
     """Greedy generation loop of src/inference/inference.go:173-254 over the device path:
-    prefill(prompt) through Forward, then the decode steps as hipGraph replays on the device."""
+    prefill(prompt) through Forward, then the decode steps as hipGraph replays on the device.
+    prefill_chunk: 0 = the prompt goes in one Forward; n > 0 = it is ingested as ForwardAppend calls of at most n rows (the same tokens out:
+    every row is the same one-token step either way; the prefill attention's score scratch is then sized for n rows instead of the prompt)."""
 
-    def __init__(self, transformer, seq_len, stop_token_ids=()):
-        self.t, self.seq_len, self.stop = transformer, seq_len, set(stop_token_ids)
+    def __init__(self, transformer, seq_len, stop_token_ids=(), prefill_chunk=0):
+        if int(prefill_chunk) < 0:
+            raise LnbError("prefill_chunk must be 0 (one Forward) or a positive row count")
+        self.t, self.seq_len, self.stop, self.prefill_chunk = transformer, seq_len, set(stop_token_ids), int(prefill_chunk)
 
     def GenerateTokens(self, prompt_tokens, max_new=None):
         prompt = list(prompt_tokens)
@@ -757,7 +787,11 @@ class InferenceEngine:
         ctx = InferenceContext(self.t, self.seq_len)
         try:
             n_new = self.seq_len - len(prompt) if max_new is None else min(max_new, self.seq_len - len(prompt))
-            _, first = ctx.Forward(prompt, 0, want_logits=False)
+            if self.prefill_chunk > 0:
+                for p0 in range(0, len(prompt), self.prefill_chunk):
+                    _, first = ctx.ForwardAppend(prompt[p0:p0 + self.prefill_chunk], p0, want_logits=False)
+            else:
+                _, first = ctx.Forward(prompt, 0, want_logits=False)
             out = [first]
             if first not in self.stop and n_new > 1:
                 more, _ = ctx.decode_greedy(first, len(prompt), n_new - 1)
