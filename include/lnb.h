@@ -116,9 +116,10 @@ int64_t lnb_model_weight_bytes(lnb_model* m);
 /* ---- context: replaces model.NewInferenceContext (src/model/inferencecontext.go:17-46) ---------------
  * device-resident, zero-filled CacheK/CacheV [seq_len, n_kv_heads, head_dim] bf16 per owned layer.
  * Context length: up to about 23000 positions (the long-context decode attention keeps 4 bytes per position in the LDS); head_dim 32, 64
- * or 128.  Calls of 2..15 rows use a kernel that stages 12 bytes per position and fail beyond ~7800 positions (head_dim 128; ~10800 at 64)
- * (lnb_forward_append falls back to one-token steps there):
- * one-token calls and calls of 16 or more rows have no such limit. */
+ * or 128.  One-token calls, calls of 16 or more rows, batched decode (lnb_batch_*) and speculative decode reach that far: beyond what the
+ * one-workgroup-per-head attention stages in the LDS (12 bytes per position: ~7800 positions at head_dim 128, ~10800 at 64) they run the
+ * long-context kernels.  Calls of 2..15 rows use a kernel that stages 12 bytes per position and fail beyond ~7800 positions (head_dim 128; ~10800 at 64)
+ * (lnb_forward_append falls back to one-token steps there). */
 int lnb_ctx_create(lnb_model* m, int seq_len, lnb_ctx** out);
 int lnb_ctx_destroy(lnb_ctx* c);
 int lnb_ctx_reset(lnb_ctx* c);                                       /* zero the caches again */
@@ -234,8 +235,9 @@ int lnb_decode_greedy_until(lnb_ctx* c, int32_t token, int start_pos, int max_st
  *   1 <= ngram_min <= ngram_max <= 16; the corpus (may be empty) is copied to the device.  Arguments are checked before the handle.
  * lnb_decode_speculative_until: outputs as lnb_decode_greedy_until from `token` at start_pos (history: the n_history tokens before it,
  *   e.g. the prompt); afterwards the cache rows [0, start_pos + *n_generated) hold that call's bits and lnb_decode_greedy / lnb_forward
- *   continue the context.  Requires a whole-model handle, the exact mode, seq_len within the batched attention's reach (~7.8 K positions
- *   at head_dim 128) and dim, n_heads*head_dim, FFN hidden size multiples of 128; refuses token probabilities, the tolerance mode and a
+ *   continue the context.  Requires a whole-model handle, the exact mode and dim, n_heads*head_dim, FFN hidden size multiples of 128 (any
+ *   seq_len lnb_ctx_create accepts: a context beyond the one-workgroup attention's reach -- ~7.8 K positions at head_dim 128 -- verifies on
+ *   the long-context kernels, lnb_ctx_set_batched_attention); refuses token probabilities, the tolerance mode and a
  *   member of a live batch.  With or without lnb_model_enable_batch (its column forms, or rows of the streaming product; same bits).
  *   stats (optional): passes, verify_passes (passes with a draft), drafted (draft tokens verified), accepted (draft tokens emitted:
  *   *n_generated - passes).  ms_out (optional): HIP-event time of the whole loop.
@@ -302,8 +304,9 @@ int lnb_op_token_probs(int device, const uint16_t* logits_bf16, int rows, int V,
  *   more rows) stream the resident weight layouts, and lnb_batch_create on a model without the copy runs every product of the batch as rows of
  *   that streaming kernel, whatever the number of sequences (64..128 sequences: 3-8 % slower than with the copy; up to 32 the column forms,
  *   which read the copy, are the faster ones by more).  Same bits either way.
- * lnb_batch_create: the contexts keep their own KV caches and positions (prefill each with lnb_forward first); seq_len of each context at
- *   most ~7.8 K positions (head_dim 128).  A context must not be used by another call while a batch call that contains it runs.
+ * lnb_batch_create: the contexts keep their own KV caches and positions (prefill each with lnb_forward first); any seq_len lnb_ctx_create accepts,
+ *   the members' may differ (a batch with a member beyond the one-workgroup attention's reach, ~7.8 K positions at head_dim 128, runs the
+ *   long-context attention: lnb_batch_set_attention).  A context must not be used by another call while a batch call that contains it runs.
  * lnb_batch_decode: sequence s continues from tokens[s] at position start_pos[s] (different positions are fine); n_steps greedy steps for
  *   all of them as replays of one captured hipGraph; out_tokens[s * n_steps + i] = token i of sequence s.  Afterwards every context's
  *   cache holds its new rows: lnb_forward / lnb_decode_greedy / another batch may continue it.
@@ -325,6 +328,19 @@ int lnb_batch_decode_until(lnb_batch* b, const int32_t* tokens, const int32_t* s
 /* measurement aid: average HIP-event time of one kernel class of the batched step (which as lnb_profile_kernel; a norm launch counts
  * with the product it feeds), every sequence placed at `pos`; overwrites the caches' row `pos` */
 int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int iters, float* avg_ms_out);
+/* Attention form of a batch's steps (same bits either way): the one-workgroup-per-head kernels, or the long-context pair with the sequences as a
+ * grid dimension (its scratch -- n * n_heads * max seq_len * 8 bytes -- is allocated when a call first needs it; a call that cannot get it fails).
+ * The form is chosen per call (lnb_batch_decode[_until], lnb_batch_set_state for the ticks that follow, lnb_batch_profile_kernel): long when the
+ * largest start position + 1 exceeds long_threshold.  long_threshold < 0: keep; default: never, except that a batch with a member
+ * whose seq_len exceeds the short kernels' reach always runs the long form.  force_zseq bit 0: every (sequence, head) walks the serial sum
+ * (counted in lnb_ctx_zseq_count of the batch's first context).  Arguments are checked before the handle; refused while a
+ * lnb_forward_stage_begin of a member has not been ended. */
+int lnb_batch_set_attention(lnb_batch* b, int long_threshold, int force_zseq);
+/* the same for the verify passes of lnb_decode_speculative_until on this context (chosen per pass; one scratch for all widths) */
+int lnb_ctx_set_batched_attention(lnb_ctx* c, int long_threshold, int force_zseq);
+/* 0: the last batched call / verify pass ran the one-workgroup kernels, 1: the long-context pair (a test and a bench print it) */
+int lnb_batch_attention_form(const lnb_batch* b, int* out);
+int lnb_ctx_verify_attention_form(const lnb_ctx* c, int* out);
 
 /* ---- pipeline-stage form (layer-sharded multi-GPU) -------------------------------
  * hidden state buffers live on the device and are owned by the ctx: [seq_len, dim] bf16.

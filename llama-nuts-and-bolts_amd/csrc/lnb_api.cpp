@@ -193,6 +193,10 @@ struct lnb_ctx {
     StepState* sp_st = nullptr; int32_t* sp_tok = nullptr; int32_t* sp_g = nullptr; int* sp_best = nullptr; unsigned* sp_cnt = nullptr;
     int32_t* sp_word = nullptr; int32_t* sp_word_dev = nullptr; hipEvent_t sp_ev = nullptr;
     struct lnb_batch* sp_b[LNB_MAX_DRAFT + 2] = {};
+    // attention form of the verify passes (lnb_ctx_set_batched_attention): threshold (default: never), serial-sum switch, the ONE e_buf / z_part
+    // scratch all widths share (sized for 16 columns, allocated when a pass first needs the long form), the form of the last verify pass
+    int sp_attn_long_T = 0x7FFFFFFF, sp_force_zseq = 0, sp_last_form = 0;
+    double* sp_e_buf = nullptr; double* sp_z_part = nullptr;
 };
 // Every path that rewrites the device-side StepState goes through here, so that the pipeline tick's "the graph left pos+1 behind, skip
 // the set_state launch" shortcut (dev_pos) can never act on a position some OTHER entry point has since overwritten (lnb_forward,
@@ -675,6 +679,7 @@ static void tp_free(lnb_ctx* c) {
 static void spec_free(lnb_ctx* c) {
     for (auto& b : c->sp_b) { if (b) lnb_batch_destroy(b); b = nullptr; }
     hipFree(c->sp_corpus); hipFree(c->sp_text); hipFree(c->sp_st); hipFree(c->sp_tok); hipFree(c->sp_g); hipFree(c->sp_best); hipFree(c->sp_cnt);
+    hipFree(c->sp_e_buf); hipFree(c->sp_z_part); c->sp_e_buf = nullptr; c->sp_z_part = nullptr;
     if (c->sp_word) hipHostFree(c->sp_word);
     if (c->sp_ev) hipEventDestroy(c->sp_ev);
     c->sp_corpus = nullptr; c->sp_text = nullptr; c->sp_st = nullptr; c->sp_tok = nullptr; c->sp_g = nullptr; c->sp_best = nullptr; c->sp_cnt = nullptr;
@@ -1518,7 +1523,15 @@ struct lnb_batch {
     BatchTab* tab = nullptr; BatchKV* kv = nullptr;
     uint16_t *x = nullptr, *h = nullptr, *xt = nullptr, *q = nullptr, *att_xt = nullptr, *ffn_xt = nullptr, *logits = nullptr;
     int* derr = nullptr; int32_t *d_tokens = nullptr, *d_pos = nullptr; int32_t* h_io = nullptr;   // pinned: [0..MAX) tokens, [MAX..2 MAX) positions, [2 MAX] error word (MAX = LNB_BATCH_MAX)
-    hipGraphExec_t graph = nullptr; int lds_T = 0; bool counted = false;
+    hipGraphExec_t graph = nullptr; int lds_T = 0; bool counted = false;       // lds_T: what the one-workgroup kernels' LDS arrays are sized for = min(maxT, their cap)
+    // attention form (lnb_batch_set_attention).  maxT: the largest member seq_len; must_long: a member is beyond the one-workgroup kernels' reach;
+    // attn_long: the form the NEXT enqueue / capture takes (chosen on the host per call: a captured graph fixes the kernel), one graph per form;
+    // e_buf [n][H][maxT] / z_part [n][H][ceil(maxT/256)]: allocated when the long form is first needed, never inside a capture (a verify batch
+    // borrows its context's: scratch_owned false)
+    int maxT = 0; bool must_long = false, attn_long = false, tick_long = false, scratch_owned = true;
+    int attn_long_T = 0x7FFFFFFF, force_zseq = 0, last_form = 0;
+    double* e_buf = nullptr; double* z_part = nullptr;
+    hipGraphExec_t graph_long = nullptr, stage_graph_long = nullptr;
     bool rows_form = false;                // the model carries no matrix-core copy: every product runs as ROWS of gemm_stream_kernel on the resident layouts, whatever n
     // pipeline stage (lnb_pipeline_tick_batch): the contiguous token words exchanged between the last and the first stage, the stage step
     // as a captured graph, events towards / from the exchange stream (as lnb_ctx has them for single-sequence ticks)
@@ -1576,6 +1589,9 @@ extern "C" int lnb_batch_destroy(lnb_batch* b) {
     if (b->stream) hipStreamSynchronize(b->stream);
     if (b->counted) for (lnb_ctx* c : b->ctxs) c->batch_users--;
     if (b->graph) hipGraphExecDestroy(b->graph);
+    if (b->graph_long) hipGraphExecDestroy(b->graph_long);
+    if (b->stage_graph_long) hipGraphExecDestroy(b->stage_graph_long);
+    if (b->scratch_owned) { hipFree(b->e_buf); hipFree(b->z_part); }
     hipFree(b->tab); hipFree(b->kv); hipFree(b->x); hipFree(b->h); hipFree(b->xt); hipFree(b->q); hipFree(b->att_xt); hipFree(b->ffn_xt); hipFree(b->logits);
     hipFree(b->derr); hipFree(b->d_tokens); hipFree(b->d_pos); hipFree(b->ring);
     hipFree(b->tp_out); hipFree(b->tp_zpart); hipFree(b->tp_kpart); hipFree(b->tp_cnt);
@@ -1657,17 +1673,56 @@ extern "C" int lnb_batch_create(lnb_ctx* const* ctxs, int n, lnb_batch** out) {
     lnb_batch* b = new lnb_batch();
     b->m = m; b->n = n; b->ctxs.assign(ctxs, ctxs + n); b->rows_form = !m->batch_enabled; b->top_k = ctxs[0]->top_k;
     for (int s = 0; s < n; s++) {
-        if (ctxs[s]->seq_len > ctxs[s]->attn_short_cap) {
-            const int sl = ctxs[s]->seq_len, cap = ctxs[s]->attn_short_cap; delete b;
-            return fail("context %d: seq_len %d is beyond the %d positions the batched attention stages in the LDS", s, sl, cap);
+        if (lnbk_attn_long_lds(ctxs[s]->seq_len) > 160 * 1024) {       // (lnb_ctx_create refuses such a context: cannot happen)
+            const int sl = ctxs[s]->seq_len; delete b;
+            return fail("context %d: seq_len %d is beyond what the long-context attention keeps in the LDS", s, sl);
         }
-        b->lds_T = std::max(b->lds_T, ctxs[s]->seq_len);
+        b->maxT = std::max(b->maxT, ctxs[s]->seq_len);
+        if (ctxs[s]->seq_len > ctxs[s]->attn_short_cap) b->must_long = true;
     }
+    b->lds_T = std::min(b->maxT, ctxs[0]->attn_short_cap);
+    b->tick_long = b->must_long;
     if (batch_alloc(b)) { lnb_batch_destroy(b); return -1; }
     for (lnb_ctx* c : b->ctxs) c->batch_users++;
     b->counted = true;
     *out = b;
     return 0;
+}
+// ---- attention form of a batched step (same bits either way).  The one-workgroup kernels (attn_exact_kernel / attn_gqa_kernel) stage a whole
+// head in the LDS and stop at attn_short_cap positions; the long-context pair with a sequence dimension (lnb_kernels.hip, BATCH forms of
+// attn_long_scores_kernel / attn_long_pv[2]_kernel) reaches every context lnb_ctx_create accepts.  A call takes the long form when a member's
+// CAPACITY is beyond the cap (the short kernels cannot be launched for it) or when its largest position + 1 exceeds the batch's threshold
+// (default: never -- a batch that fits the short kernels runs exactly what it ran before the long form existed).
+static bool batch_want_long(const lnb_batch* b, int max_pos) { return b->must_long || max_pos + 1 > b->attn_long_T; }
+// the e_buf [n][H][maxT] / z_part [n][H][ceil(maxT/256)] scratch of the batched long form (a batch's own, or the one a context's verify batches share)
+static int attn_long_scratch(int n, int H, int maxT, double** e_buf, double** z_part, const char* whose) {
+    if (*e_buf && *z_part) return 0;
+    const size_t rows = (size_t)n * H, eb = rows * (size_t)maxT * 8, zb = rows * (size_t)((maxT + 255) / 256) * 8;
+    hipError_t e = hipMalloc((void**)e_buf, eb);
+    if (e == hipSuccess) e = hipMalloc((void**)z_part, zb);
+    if (e != hipSuccess) {
+        hipFree(*e_buf); hipFree(*z_part); *e_buf = nullptr; *z_part = nullptr; (void)hipGetLastError();
+        return fail("the long-context attention of %s needs %.1f MB of scratch (%d sequences x %d heads x %d positions): %s", whose, (double)(eb + zb) / 1e6,
+                    n, H, maxT, hipGetErrorString(e));
+    }
+    return 0;
+}
+static int batch_long_scratch(lnb_batch* b) {
+    if (b->e_buf && b->z_part) return 0;
+    if (!b->scratch_owned) return fail("internal error: verify batch without its context's attention scratch");
+    return attn_long_scratch(b->n, b->m->a.n_heads, b->maxT, &b->e_buf, &b->z_part, "this batch");
+}
+// selects the form of what is enqueued / captured next; allocates the scratch (host side of a call, outside any capture).  last_form (what
+// lnb_batch_attention_form reports) is set by the callers once their launches have been accepted.
+static int batch_select_form(lnb_batch* b, bool want_long) {
+    if (want_long && batch_long_scratch(b)) return -1;
+    b->attn_long = want_long;
+    return 0;
+}
+static void batch_attn_form(const lnb_batch* b, AttnParams& ap) {
+    ap.lds_T = b->lds_T; ap.seq_len = b->attn_long ? b->maxT : b->lds_T;
+    ap.longctx = b->attn_long ? 1 : 0; ap.force_zseq = b->attn_long ? (b->force_zseq & 1) : 0;
+    ap.e_buf = b->e_buf; ap.z_part = b->z_part;
 }
 static StreamParams stream_of(const lnb_batch* b, const uint16_t* w, const uint16_t* xt, int K, int n_rows, int nch) {
     StreamParams p{}; p.w = w; p.xt = xt; p.K = K; p.n_rows = n_rows; p.nch = nch; p.n_chains = ((n_rows + 15) / 16) * nch; p.nseq = b->n; p.dbg = g_dbg;
@@ -1708,9 +1763,10 @@ static int enqueue_batch_kernel_wide(lnb_batch* b, int l, int which) {
             HIPCHK(lnbk_stream(&p, EPI_QKV_ROPE, 0, g_num_cus, st)); return 0; }
         case K_ATTN: {
             AttnParams ap{}; ap.q = b->q; ap.out_xt = b->att_xt; ap.btab = b->tab; ap.bkv = b->kv + (l - m->layer_begin); ap.dbg = nullptr;
-            ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.seq_len = b->lds_T; ap.lds_T = b->lds_T; ap.host_T = 0;
+            ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
             ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
-            ap.force_zseq = 0; ap.zseq_count = b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;
+            ap.zseq_count = b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;
+            batch_attn_form(b, ap);
             HIPCHK(lnbk_attn(&ap, st)); return 0; }
         case K_WO: {
             StreamParams p = pair_of(L.m_wo, b->att_xt, m->q_dim, dim); p.out = b->h; p.res = b->x;
@@ -1740,9 +1796,10 @@ static int enqueue_batch_kernel_wide(lnb_batch* b, int l, int which) {
         HIPCHK(lnbk_gemm_stream(&g, EPI_QKV_ROPE, g_num_cus, st)); return 0; }
     case K_ATTN: {
         AttnParams ap{}; ap.q = b->q; ap.out = b->att_xt; ap.out_xt = nullptr; ap.btab = b->tab; ap.bkv = b->kv + (l - m->layer_begin); ap.dbg = nullptr;
-        ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.seq_len = b->lds_T; ap.lds_T = b->lds_T; ap.host_T = 0;
+        ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
         ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
-        ap.force_zseq = 0; ap.zseq_count = b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
+        ap.zseq_count = b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
+        batch_attn_form(b, ap);
         HIPCHK(lnbk_attn(&ap, st)); return 0; }
     case K_WO: {
         GemmParams g = wide_of(b, L.wo, L.m_wo, b->att_xt, m->q_dim, dim, 1); g.out = b->h; g.res = b->x;
@@ -1777,9 +1834,10 @@ static int enqueue_batch_kernel(lnb_batch* b, int l, int which) {
         HIPCHK(lnbk_stream(&p, EPI_QKV_ROPE, stream_acc2(p), g_num_cus, st)); return 0; }
     case K_ATTN: {
         AttnParams ap{}; ap.q = b->q; ap.out_xt = b->att_xt; ap.btab = b->tab; ap.bkv = b->kv + (l - m->layer_begin); ap.dbg = nullptr;
-        ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.seq_len = b->lds_T; ap.lds_T = b->lds_T; ap.host_T = 0;
+        ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
         ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
-        ap.force_zseq = 0; ap.zseq_count = b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
+        ap.zseq_count = b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
+        batch_attn_form(b, ap);
         HIPCHK(lnbk_attn(&ap, st)); return 0; }
     case K_WO: {
         StreamParams p = stream_of(b, L.m_wo, b->att_xt, m->q_dim, dim, 1); p.out = b->h; p.res = b->x;
@@ -1848,15 +1906,19 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     }
     for (lnb_ctx* c : b->ctxs) { c->tp_last_k = 0; c->tp_last_n = 0; }
     hipStream_t st = b->stream;
+    int max_pos = 0;
+    for (int s = 0; s < b->n; s++) max_pos = std::max(max_pos, start_pos[s]);         // (a frozen sequence does not move the form)
+    if (batch_select_form(b, batch_want_long(b, max_pos))) return -1;
     const bool use_graph = env_int("LNB_NO_GRAPH", 0) == 0;
-    if (use_graph && !b->graph) {
+    hipGraphExec_t* const gslot = b->attn_long ? &b->graph_long : &b->graph;       // one captured step per form
+    if (use_graph && !*gslot) {
         hipGraph_t g = nullptr;
         HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
         int rc = enqueue_batch_step(b);
         hipError_t e = hipStreamEndCapture(st, &g);
         if (rc) { if (g) hipGraphDestroy(g); return -1; }
         HIPCHK(e);
-        HIPCHK(hipGraphInstantiate(&b->graph, g, nullptr, nullptr, 0));
+        HIPCHK(hipGraphInstantiate(gslot, g, nullptr, nullptr, 0));
         HIPCHK(hipGraphDestroy(g));
     }
     memcpy(b->h_io, tokens, (size_t)b->n * 4); memcpy(b->h_io + LNB_BATCH_MAX, start_pos, (size_t)b->n * 4);
@@ -1866,10 +1928,11 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     HIPCHK(lnbk_batch_set_state(b->tab, b->d_tokens, b->d_pos, b->ring, n_generated ? 1 : 0, st));
     HIPCHK(hipEventRecord(b->ev0, st));
     for (int i = 0; i < n_steps; i++) {
-        if (use_graph) HIPCHK(hipGraphLaunch(b->graph, st));
+        if (use_graph) HIPCHK(hipGraphLaunch(*gslot, st));
         else if (enqueue_batch_step(b)) return -1;
     }
     HIPCHK(hipEventRecord(b->ev1, st));
+    b->last_form = b->attn_long ? 1 : 0;
     for (int s = 0; s < b->n; s++)
         HIPCHK(hipMemcpyAsync(out_tokens + (size_t)s * n_steps, b->ctxs[s]->dout, (size_t)n_steps * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(b->h_io + 2 * LNB_BATCH_MAX, b->derr, 4, hipMemcpyDeviceToHost, st));
@@ -1923,6 +1986,10 @@ extern "C" int lnb_batch_set_state(lnb_batch* b, const int32_t* tokens, const in
                         "token): clear them (lnb_ctx_set_stop_ids(ctx, NULL, 0)) and end the sequence on the host", s, c->n_stop);
         c->dev_pos = -1; c->call_T = 0;
     }
+    { int max_pos = 0;                                       // the ticks that follow run the form this start calls for (lnb_pipeline_tick_batch)
+      for (int s = 0; s < b->n; s++) max_pos = std::max(max_pos, start_pos[s]);
+      if (batch_select_form(b, batch_want_long(b, max_pos))) return -1;
+      b->tick_long = b->attn_long; }
     HIPCHK(hipDeviceSynchronize());                          // a setup call: whatever the contexts' streams and the pipe's exchange stream still do
                                                              // (the prefill's token hand-off into the contexts' token words) comes first
     if (tokens) memcpy(b->h_io, tokens, (size_t)b->n * 4);
@@ -1942,6 +2009,7 @@ extern "C" int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int it
     if (iters <= 0 || which < 0 || which > K_LAYER) return fail("bad arguments");
     if (which == K_HEAD && !m->last()) return fail("this stage does not own output.weight");
     for (int s = 0; s < b->n; s++) { if (check_call(b->ctxs[s], 1, pos)) return -1; b->h_io[s] = 0; b->h_io[LNB_BATCH_MAX + s] = pos; b->ctxs[s]->dev_pos = -1; }
+    if (batch_select_form(b, batch_want_long(b, pos))) return -1;
     hipStream_t st = b->stream;
     HIPCHK(hipMemcpyAsync(b->d_tokens, b->h_io, (size_t)b->n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(b->d_pos, b->h_io + LNB_BATCH_MAX, (size_t)b->n * 4, hipMemcpyHostToDevice, st));
@@ -1957,9 +2025,54 @@ extern "C" int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int it
     HIPCHK(hipEventRecord(b->ev0, st));
     for (int i = 0; i < iters; i++) if (run(i + 3)) return -1;
     HIPCHK(hipEventRecord(b->ev1, st));
+    b->last_form = b->attn_long ? 1 : 0;
     HIPCHK(hipStreamSynchronize(st));
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
     *avg_ms_out = ms / (float)iters;
+    return 0;
+}
+
+// lnb_batch_set_attention: long_threshold < 0 keeps the current value (default: never).  The threshold only picks between the two captured graphs;
+// force_zseq is baked into the long form's launches, so a change of it drops the long graphs (and nothing else).
+static int attention_args(int force_zseq) {
+    if (force_zseq & ~1) return fail("force_zseq must be 0 or 1 (got %d)", force_zseq);
+    return 0;
+}
+extern "C" int lnb_batch_set_attention(lnb_batch* b, int long_threshold, int force_zseq) {
+    if (attention_args(force_zseq)) return -1;
+    if (!b) return fail("null argument");
+    for (int s = 0; s < b->n; s++) if (b->ctxs[s]->pending) return fail("sequence %d: a lnb_forward_stage_begin has not been ended", s);
+    HIPCHK(hipSetDevice(b->m->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (long_threshold >= 0) b->attn_long_T = long_threshold;
+    if (force_zseq != b->force_zseq) {
+        if (b->graph_long) { hipGraphExecDestroy(b->graph_long); b->graph_long = nullptr; }
+        if (b->stage_graph_long) { hipGraphExecDestroy(b->stage_graph_long); b->stage_graph_long = nullptr; }
+        b->force_zseq = force_zseq;
+    }
+    return 0;
+}
+extern "C" int lnb_batch_attention_form(const lnb_batch* b, int* out) {
+    if (!b || !out) return fail("null argument");
+    *out = b->last_form;
+    return 0;
+}
+extern "C" int lnb_ctx_set_batched_attention(lnb_ctx* c, int long_threshold, int force_zseq) {
+    if (attention_args(force_zseq)) return -1;
+    if (!c) return fail("null argument");
+    if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
+    HIPCHK(hipSetDevice(c->m->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (long_threshold >= 0) c->sp_attn_long_T = long_threshold;
+    if (force_zseq != c->sp_force_zseq) {
+        for (lnb_batch* b : c->sp_b) if (b) { b->force_zseq = force_zseq; if (b->graph_long) { hipGraphExecDestroy(b->graph_long); b->graph_long = nullptr; } }
+        c->sp_force_zseq = force_zseq;
+    }
+    return 0;
+}
+extern "C" int lnb_ctx_verify_attention_form(const lnb_ctx* c, int* out) {
+    if (!c || !out) return fail("null argument");
+    *out = c->sp_last_form;
     return 0;
 }
 
@@ -2014,15 +2127,28 @@ static int spec_alloc(lnb_ctx* c, int text_len) {
 }
 // the verify batch of width w, its graph captured on first use: embedding gather of the w column tokens, the blocks, the head, the
 // columns' argmax, the commit.  With the matrix-core copy the products are its column forms, without it rows of gemm_stream_kernel.
-static int spec_verify_batch(lnb_ctx* c, int w, lnb_batch** out) {
-    if (c->sp_b[w]) { *out = c->sp_b[w]; return 0; }
+// long_form: the pass runs the long-context pair (one graph per form and width); its scratch is the context's, shared by all widths
+static int spec_verify_batch(lnb_ctx* c, int w, bool long_form, lnb_batch** out) {
     lnb_model* m = c->m;
-    lnb_batch* b = new lnb_batch();
-    b->m = m; b->n = w; b->ctxs.assign(w, c); b->rows_form = !m->batch_enabled; b->lds_T = c->seq_len;
-    b->col_st = c->sp_st; b->col_tok = c->sp_tok;
-    if (batch_alloc(b)) { lnb_batch_destroy(b); return -1; }
+    if (long_form && attn_long_scratch(LNB_MAX_DRAFT + 1, m->a.n_heads, c->seq_len, &c->sp_e_buf, &c->sp_z_part, "the verify passes")) return -1;   // (host side of the call, outside any capture)
+    lnb_batch* b = c->sp_b[w];
+    const bool fresh = !b;
+    if (fresh) {
+        b = new lnb_batch();
+        b->m = m; b->n = w; b->ctxs.assign(w, c); b->rows_form = !m->batch_enabled;
+        b->maxT = c->seq_len; b->lds_T = std::min(c->seq_len, c->attn_short_cap); b->must_long = c->seq_len > c->attn_short_cap;
+        b->scratch_owned = false; b->force_zseq = c->sp_force_zseq;
+        b->col_st = c->sp_st; b->col_tok = c->sp_tok;
+        if (batch_alloc(b)) { lnb_batch_destroy(b); return -1; }
+        c->sp_b[w] = b;
+    }
+    b->e_buf = c->sp_e_buf; b->z_part = c->sp_z_part;
+    b->attn_long = long_form;
+    hipGraphExec_t* const gslot = long_form ? &b->graph_long : &b->graph;
+    if (*gslot) { *out = b; return 0; }
+    auto drop = [&]() { if (fresh) { c->sp_b[w] = nullptr; lnb_batch_destroy(b); } };
     hipGraph_t g = nullptr;
-    if (hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { lnb_batch_destroy(b); return fail("hipStreamBeginCapture failed"); }
+    if (hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { drop(); return fail("hipStreamBeginCapture failed"); }
     int rc = 0;
     if (lnbk_batch_embed(m->tok_embd, b->tab, b->x, w, m->a.dim, m->a.vocab_size, b->derr, b->stream) != hipSuccess) rc = fail("verify pass: embedding launch failed");
     for (int l = m->layer_begin; l < m->layer_end && !rc; l++)
@@ -2031,10 +2157,10 @@ static int spec_verify_batch(lnb_ctx* c, int w, lnb_batch** out) {
     if (!rc && lnbk_spec_argmax(b->logits, m->a.vocab_size, w, c->sp_g, b->stream) != hipSuccess) rc = fail("verify pass: argmax launch failed");
     if (!rc && lnbk_spec_commit(c->sp_g, w, b->tab, b->stream) != hipSuccess) rc = fail("verify pass: commit launch failed");
     hipError_t e = hipStreamEndCapture(b->stream, &g);
-    if (!rc && e == hipSuccess) e = hipGraphInstantiate(&b->graph, g, nullptr, nullptr, 0);
+    if (!rc && e == hipSuccess) e = hipGraphInstantiate(gslot, g, nullptr, nullptr, 0);
     if (g) hipGraphDestroy(g);
-    if (rc || e != hipSuccess) { lnb_batch_destroy(b); return rc ? rc : fail("verify graph: %s", hipGetErrorString(e)); }
-    c->sp_b[w] = b; *out = b;
+    if (rc || e != hipSuccess) { drop(); return rc ? rc : fail("verify graph: %s", hipGetErrorString(e)); }
+    *out = b;
     return 0;
 }
 static DraftParams spec_draft_params(lnb_ctx* c, int n_text, int max_steps) {
@@ -2064,8 +2190,6 @@ extern "C" int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, 
     if (max_steps > c->dout_cap) return fail("max_steps %d exceeds the context length %d", max_steps, c->dout_cap);
     if (check_call(c, 1, start_pos) || check_call(c, 1, start_pos + max_steps - 1)) return -1;
     if (token < 0 || token >= m->a.vocab_size) return fail("token id at index 0 is outside the vocabulary");
-    if (c->seq_len > c->attn_short_cap)
-        return fail("seq_len %d is beyond the %d positions the batched attention of a verify pass stages in the LDS", c->seq_len, c->attn_short_cap);
     if (m->a.dim % 128 || m->q_dim % 128 || m->ffn_hidden % 128)
         return fail("the verify pass streams the weights in 128-step chunks: dim (%d), n_heads*head_dim (%d) and the FFN hidden size (%d) must be multiples of 128", m->a.dim, m->q_dim, m->ffn_hidden);
     if (!m->batch_enabled) HIPCHK(lnbk_batch_prepare());
@@ -2097,8 +2221,11 @@ extern "C" int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, 
         if (k == 0) HIPCHK(hipGraphLaunch(want_long_attention(c, 1, start_pos + n_out) ? c->graph_long : c->graph, st));
         else {
             lnb_batch* b = nullptr;
-            if (spec_verify_batch(c, k + 1, &b)) return -1;
-            HIPCHK(hipGraphLaunch(b->graph, st));
+            // the pass's last column sits at start_pos + n_out + k: the long form when the context is beyond the one-workgroup kernels' reach or past the threshold
+            const bool lf = c->seq_len > c->attn_short_cap || start_pos + n_out + k + 1 > c->sp_attn_long_T;
+            if (spec_verify_batch(c, k + 1, lf, &b)) return -1;
+            HIPCHK(hipGraphLaunch(lf ? b->graph_long : b->graph, st));
+            c->sp_last_form = lf ? 1 : 0; b->last_form = c->sp_last_form;
             s.verify_passes++; s.drafted += k;
         }
         HIPCHK(lnbk_ngram_draft(&dp, st));
@@ -2476,19 +2603,22 @@ extern "C" int lnb_pipeline_tick_batch(lnb_pipe* p, lnb_batch* run, lnb_batch* s
         if (run->in_pending) { HIPCHK(hipStreamWaitEvent(st, run->ev_in, 0)); run->in_pending = false; }
         if (run->sent_pending) { HIPCHK(hipStreamWaitEvent(st, run->ev_sent, 0)); run->sent_pending = false; }
         const bool ring_in = first && p->world > 1;
+        if (batch_select_form(run, run->tick_long)) return -1;       // the form lnb_batch_set_state chose for this run of ticks
         if (p->use_graph) {
-            if (!run->stage_graph) {
+            hipGraphExec_t* const gslot = run->attn_long ? &run->stage_graph_long : &run->stage_graph;
+            if (!*gslot) {
                 hipGraph_t g = nullptr;
                 HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
                 int rc = enqueue_batch_step(run, ring_in);
                 hipError_t e = hipStreamEndCapture(st, &g);
                 if (rc) { if (g) hipGraphDestroy(g); return -1; }
                 HIPCHK(e);
-                HIPCHK(hipGraphInstantiate(&run->stage_graph, g, nullptr, nullptr, 0));
+                HIPCHK(hipGraphInstantiate(gslot, g, nullptr, nullptr, 0));
                 HIPCHK(hipGraphDestroy(g));
             }
-            HIPCHK(hipGraphLaunch(run->stage_graph, st));
+            HIPCHK(hipGraphLaunch(*gslot, st));
         } else if (enqueue_batch_step(run, ring_in)) return -1;
+        run->last_form = run->attn_long ? 1 : 0;
         if (last) {
             if (p->tok_n > 0x7FFFFFFF - LNB_BATCH_MAX) return fail("pipeline token log: slot counter exhausted (2^31 tokens): create a new pipe");
             const int slot = p->tok_n, at = slot % p->tok_cap, fit = std::min(run->n, p->tok_cap - at);   // (the ring keeps the newest tok_cap tokens)

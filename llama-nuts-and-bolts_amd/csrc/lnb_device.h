@@ -144,6 +144,8 @@ struct AttnParams {
     int force_zseq;             // 1: always take the sequential-Z path of attn_long_pv_kernel (tests)
     double* e_buf;              // [H][seq_len] f64: exp of every score of the current token
     double* z_part;             // [H][ceil(seq_len / 256)] f64: per-block tree sums of e (only an ESTIMATE of Z, see the kernel)
+                                // batched long form (btab && longctx, the BATCH instantiations): S sequences in grid.z, seq_len = the LARGEST member's cache length,
+                                // e_buf [S][H][seq_len], z_part [S][H][ceil(seq_len / 256)]; every sequence's own length comes from btab->seq_len
     int* zseq_count;            // counts workgroups that had to fall back to the sequential Z chain (diagnostics)
     unsigned* cnt;              // attn_one_kernel (longctx >= 2): [H] arrival counters of the in-launch exchange (never reset: a launch's generation is old / slices) + [H] = polls that timed out
     // batched decode (attn_exact_kernel, S = 1 per sequence): query row i belongs to sequence i of the batch -- its own position, caches and

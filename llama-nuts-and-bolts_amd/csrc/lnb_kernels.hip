@@ -3062,21 +3062,50 @@ template <int NK> DEVINL double attn_score_value(const uint4 (&k)[NK], const flo
     s = bf_trunc(__fdiv_rn(bf_wide(s), divisor));           // DivToScalar :464
     return exp((double)bf_wide(s));                          // Softmax impl:498
 }
-template <int HD> __global__ __launch_bounds__(ALS_NT) void attn_long_scores_kernel(AttnParams p) {
+// BATCH (batched decode and the verify passes of the speculative loop, grid.z = the sequences): one more grid dimension over the same program.
+// Sequence s takes its position from its own StepState (btab), its caches from bkv and its OWN cache length (the K layout's stride, the
+// arrays' ends) from btab->seq_len[s] -- the members of a batch may differ in capacity; p.seq_len is then the LARGEST member's (maxT): the
+// stride of the e_buf [n][H][maxT] / z_part [n][H][ceil(maxT/256)] rows, the size of the scores grid and of the PV kernels' LDS arrays.
+// A sequence at a short position leaves most of its blocks at once (uniform return); a frozen one (stop id) recomputes its last step.
+// The position is clamped into the sequence's cache (a state word the batch never set cannot take a read past an array's end).
+// The XCD remap acts inside a z-slice and the V touch carries over unchanged (each sequence's group touches its own rows).
+struct AlSeq { int seq_len, T; const uint16_t* ck; const uint16_t* cv; size_t row; };       // row: (sequence, head) row of q / e_buf / z_part / out
+DEVINL AlSeq al_seq(const AttnParams& p, int h) {
+    AlSeq a;
+    const int s = blockIdx.z;
+    a.seq_len = p.btab->seq_len[s]; a.ck = p.bkv->ck[s]; a.cv = p.bkv->cv[s]; a.row = (size_t)s * p.H + h;
+    const int T = p.btab->st[s]->pos + 1;
+    a.T = T < 1 ? 1 : (T > a.seq_len ? a.seq_len : T);
+    return a;
+}
+// (accessors: the S == 1 instantiations read the launch parameters where they always did -- their code is unchanged by the BATCH forms)
+template <bool BATCH> DEVINL int al_len(const AttnParams& p, const AlSeq& a) { if constexpr (BATCH) return a.seq_len; else return p.seq_len; }
+template <bool BATCH> DEVINL int al_T(const AttnParams& p, const AlSeq& a) { if constexpr (BATCH) return a.T; else return p.st->pos + 1; }
+template <bool BATCH> DEVINL const uint16_t* al_ck(const AttnParams& p, const AlSeq& a) { if constexpr (BATCH) return a.ck; else return p.cache_k; }
+template <bool BATCH> DEVINL const uint16_t* al_cv(const AttnParams& p, const AlSeq& a) { if constexpr (BATCH) return a.cv; else return p.cache_v; }
+template <bool BATCH> DEVINL size_t al_row(const AlSeq& a, int h) { if constexpr (BATCH) return a.row; else return (size_t)h; }
+// the batched step's two destinations (the end of attn_exact_kernel): the B-operand layout of the wo product (column forms, 17..32 "groups") or rows
+DEVINL void al_store(const AttnParams& p, int h, int hd_, int d, float acc) {
+    const int s = blockIdx.z;
+    if (p.out_xt) p.out_xt[xt_group(s, p.H * hd_) + xt_index(s & 15, h * hd_ + d)] = bf_trunc(acc);
+    else p.out[((size_t)s * p.H + h) * hd_ + d] = bf_trunc(acc);
+}
+template <int HD, bool BATCH = false> __global__ __launch_bounds__(ALS_NT) void attn_long_scores_kernel(AttnParams p) {
     constexpr int NK = HD / 8;
     __shared__ __attribute__((aligned(16))) float qf[HD];
     __shared__ double wsum[ALS_NT / 64];
     const int tid = threadIdx.x;
     int h, blk; xcd_head_block(h, blk);
-    const int T = p.st->pos + 1, j0 = blk * ALS_NT;
+    [[maybe_unused]] AlSeq sq{}; if constexpr (BATCH) sq = al_seq(p, h);      // (BATCH: p.seq_len = the largest member's -- row strides, LDS layout; al_len = this sequence's array ends)
+    const int T = al_T<BATCH>(p, sq), j0 = blk * ALS_NT;
     if (j0 >= T) return;                                     // (uniform: the grid is sized for seq_len, the captured graph serves every T)
     const int kvh = h / (p.H / p.KVH);
-    const uint4* kbase = (const uint4*)p.cache_k + (size_t)kvh * NK * p.seq_len;
-    const uint16_t* q = p.q + (size_t)h * HD;
+    const uint4* kbase = (const uint4*)al_ck<BATCH>(p, sq) + (size_t)kvh * NK * al_len<BATCH>(p, sq);
+    const uint16_t* q = p.q + al_row<BATCH>(sq, h) * HD;
     const uint16_t q16 = q[tid < HD ? tid : 0];
     const int j = j0 + tid;
     uint4 k[NK];
-    attn_load_k<NK>(k, kbase, p.seq_len, j < T ? j : T - 1);
+    attn_load_k<NK>(k, kbase, al_len<BATCH>(p, sq), j < T ? j : T - 1);
     // round 6 (AttnParams.touch): the query heads of a GQA group touch the V rows of their block for the PV launch that follows -- these workgroups sit on the
     // XCD whose L2 the PV workgroups of the group will read (xcd_head_block), so the lines land where they are needed (a touch from another XCD lands in the wrong L2, and the
     // memory-side cache is barely faster than HBM: profiles/r06_kv_touch_ab.log).  Issued BEHIND the K rows.
@@ -3089,19 +3118,19 @@ template <int HD> __global__ __launch_bounds__(ALS_NT) void attn_long_scores_ker
         constexpr int LPR = HD / 64 > 0 ? HD / 64 : 1;       // 128-byte lines per (row, kv head)
         const int l = ((h % (p.H / p.KVH)) % LPR) * ALS_NT + tid;
         int jl = j0 + l / LPR; jl = jl < T ? jl : T - 1;
-        const char* va = (const char*)p.cache_v + ((size_t)jl * p.KVH + kvh) * HD * 2 + (l % LPR) * 128;
+        const char* va = (const char*)al_cv<BATCH>(p, sq) + ((size_t)jl * p.KVH + kvh) * HD * 2 + (l % LPR) * 128;
         va = p.touch ? va : (const char*)kbase;              // (off: a line this workgroup reads anyway)
         asm volatile("global_load_dword %0, %1, off ; RING_LOAD (never retired: tools/isa_audit.py flags any later use of the register)" : "=v"(vt) : "v"(va));
     }
     if (tid < HD) qf[tid] = bf_wide(q16);
     __syncthreads();
     double ev = 0.0;
-    if (j < T) { ev = attn_score_value<NK>(k, qf, p.divisor); p.e_buf[(size_t)h * p.seq_len + j] = ev; }
+    if (j < T) { ev = attn_score_value<NK>(k, qf, p.divisor); p.e_buf[al_row<BATCH>(sq, h) * p.seq_len + j] = ev; }
     // tree sum of the block (fixed shape: deterministic); only ever used as an estimate with a rigorous error bound
     ev = wave_sum_f64(ev);
     if ((tid & 63) == 0) wsum[tid >> 6] = ev;
     __syncthreads();
-    if (tid == 0) p.z_part[(size_t)h * ((p.seq_len + ALS_NT - 1) / ALS_NT) + blk] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    if (tid == 0) p.z_part[al_row<BATCH>(sq, h) * ((p.seq_len + ALS_NT - 1) / ALS_NT) + blk] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
     asm volatile("" :: "v"(vt));                              // the touch's destination stays allocated up to here
 }
 
@@ -3112,17 +3141,18 @@ constexpr int ALP_SLOT = ALP_DS * ALP_BATCH;                 // floats per ring 
 constexpr int ALP_EU = 12;                                   // e_j per thread and round
 __host__ __device__ inline size_t alp_lds_bytes(int seq_len) { return (size_t)((seq_len + ALP_BATCH - 1) / ALP_BATCH + 1) * ALP_BATCH * 4 + 2 * (size_t)ALP_SLOT * 4 + 64; }
 DEVINL float alp_p(double e, double z) { return bf_wide(bf_trunc((float)(e / z))); }     // impl:506 + ToBFloat16 :493
-template <int HD> DEVINL void alp_eager_body(const AttnParams& p) {
+template <int HD, bool BATCH = false> DEVINL void alp_eager_body(const AttnParams& p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int h, ds; xcd_head_block(h, ds);
-    const int T = p.st->pos + 1, nblk = (T + ALS_NT - 1) / ALS_NT, nbatch = (T + ALP_BATCH - 1) / ALP_BATCH;
+    [[maybe_unused]] AlSeq sq{}; if constexpr (BATCH) sq = al_seq(p, h);      // (BATCH: p.seq_len = the largest member's -- row strides, LDS layout; al_len = this sequence's array ends)
+    const int T = al_T<BATCH>(p, sq), nblk = (T + ALS_NT - 1) / ALS_NT, nbatch = (T + ALP_BATCH - 1) / ALP_BATCH;
     const int Tpad = (nbatch + 1) * ALP_BATCH;               // (+ one batch of zeros: the producers run ahead)
     float* pw = (float*)smem;                                // [Tpad] p_j (+0 beyond T)
     float* ring = (float*)(smem + (size_t)((p.seq_len + ALP_BATCH - 1) / ALP_BATCH + 1) * ALP_BATCH * 4);   // [2][ALP_SLOT] products
     double* zsh = (double*)(ring + 2 * ALP_SLOT);
-    const double* E = p.e_buf + (size_t)h * p.seq_len;
+    const double* E = p.e_buf + al_row<BATCH>(sq, h) * p.seq_len;
     const int kvh = h / (p.H / p.KVH);
 #define ALP_STAMP(n) do { if (p.dbg && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && (wave & 3) == 0) p.dbg[(wave >> 2) * 16 + (n)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
     ALP_STAMP(0);
@@ -3131,11 +3161,11 @@ template <int HD> DEVINL void alp_eager_body(const AttnParams& p) {
     // (clamped to the ARRAY ends, not to T: the addresses must not wait for the position word to arrive; what lies past T is not used)
     double ev[ALP_EU];
 #pragma unroll
-    for (int u = 0; u < ALP_EU; u++) { const int j = u * ALP_NT + tid; ev[u] = E[j < p.seq_len ? j : p.seq_len - 1]; }
+    for (int u = 0; u < ALP_EU; u++) { const int j = u * ALP_NT + tid; ev[u] = E[j < al_len<BATCH>(p, sq) ? j : al_len<BATCH>(p, sq) - 1]; }
     const int nblk_max = (p.seq_len + ALS_NT - 1) / ALS_NT;
-    const double* zp = p.z_part + (size_t)h * nblk_max;
+    const double* zp = p.z_part + al_row<BATCH>(sq, h) * nblk_max;
     double zmine = zp[lane < nblk_max ? lane : nblk_max - 1];
-    const uint16_t* vbase = p.cache_v + (size_t)kvh * HD + (size_t)ds * ALP_DS;
+    const uint16_t* vbase = al_cv<BATCH>(p, sq) + (size_t)kvh * HD + (size_t)ds * ALP_DS;
     const size_t vrow = (size_t)p.KVH * HD;
     const int pl = tid & 255, half8 = pl & 1, prow = pl >> 1;                // producers: 128 positions x two 8-dim halves per round, 4 rounds per batch
     auto load = [&](uint4 (&v)[4], int b) {
@@ -3247,7 +3277,7 @@ template <int HD> DEVINL void alp_eager_body(const AttnParams& p) {
             __syncthreads();
         }
         ALP_STAMP(5);
-        if (jj == 0) p.out[(size_t)h * HD + ds * ALP_DS + d] = bf_trunc(acc);
+        if (jj == 0) { if constexpr (BATCH) al_store(p, h, HD, ds * ALP_DS + d, acc); else p.out[(size_t)h * HD + ds * ALP_DS + d] = bf_trunc(acc); }
         ALP_STAMP(6);
     } else {
         auto produce = [&](const uint4 (&v)[4], int b) {
@@ -3273,7 +3303,7 @@ template <int HD> DEVINL void alp_eager_body(const AttnParams& p) {
     }
 }
 
-template <int HD> __global__ __launch_bounds__(ALP_NT) void attn_long_pv_kernel(AttnParams p) { alp_eager_body<HD>(p); }
+template <int HD, bool BATCH = false> __global__ __launch_bounds__(ALP_NT) void attn_long_pv_kernel(AttnParams p) { alp_eager_body<HD, BATCH>(p); }
 
 // ------------------------------------------------------------------------------------------------
 // attn_long_pv2_kernel (round 6): attn_long_pv_kernel with the p_j evaluated LAZILY, off the critical path.
@@ -3287,31 +3317,32 @@ template <int HD> __global__ __launch_bounds__(ALP_NT) void attn_long_pv_kernel(
 // equals the reference's bits whatever the serial sum is (monotone step function, attn_long_pv_kernel's header); an uncertified one is discarded.
 // Same grid, block and LDS as attn_long_pv_kernel (the p array is unused).  The kernel symbol attn_long_pv2_kernel picks between the two bodies (below).
 // ------------------------------------------------------------------------------------------------
-template <int HD> DEVINL void alp_lazy_body(const AttnParams& p) {
+template <int HD, bool BATCH = false> DEVINL void alp_lazy_body(const AttnParams& p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int h, ds; xcd_head_block(h, ds);
-    const int T = p.st->pos + 1, nblk = (T + ALS_NT - 1) / ALS_NT, nbatch = (T + ALP_BATCH - 1) / ALP_BATCH;
+    [[maybe_unused]] AlSeq sq{}; if constexpr (BATCH) sq = al_seq(p, h);      // (BATCH: p.seq_len = the largest member's -- row strides, LDS layout; al_len = this sequence's array ends)
+    const int T = al_T<BATCH>(p, sq), nblk = (T + ALS_NT - 1) / ALS_NT, nbatch = (T + ALP_BATCH - 1) / ALP_BATCH;
     float* ring = (float*)(smem + (size_t)((p.seq_len + ALP_BATCH - 1) / ALP_BATCH + 1) * ALP_BATCH * 4);   // [2][ALP_SLOT] products
     double* zsh = (double*)(ring + 2 * ALP_SLOT);
     int* const flag = (int*)(zsh + 1);
-    const double* E = p.e_buf + (size_t)h * p.seq_len;
+    const double* E = p.e_buf + al_row<BATCH>(sq, h) * p.seq_len;
     const int kvh = h / (p.H / p.KVH);
 #define ALQ_STAMP(n) do { if (p.dbg && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && (wave & 3) == 0) p.dbg[(wave >> 2) * 16 + (n)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
     ALQ_STAMP(0);
     // address-only loads first, oldest-needed first: the per-block partial sums, then the producers' first three batches of e_j and V rows
     const int nblk_max = (p.seq_len + ALS_NT - 1) / ALS_NT;
-    const double* zp = p.z_part + (size_t)h * nblk_max;
+    const double* zp = p.z_part + al_row<BATCH>(sq, h) * nblk_max;
     double zmine = zp[lane < nblk_max ? lane : nblk_max - 1];
-    const uint16_t* vbase = p.cache_v + (size_t)kvh * HD + (size_t)ds * ALP_DS;
+    const uint16_t* vbase = al_cv<BATCH>(p, sq) + (size_t)kvh * HD + (size_t)ds * ALP_DS;
     const size_t vrow = (size_t)p.KVH * HD;
     const int pl = tid & 255, half8 = pl & 1, prow = pl >> 1;                // producers: 128 positions x two 8-dim halves per round, 4 rounds per batch
     struct Rows { uint4 v[4]; double e[4]; };
     auto load = [&](Rows& r_, int b) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
-            int j = b * ALP_BATCH + r * 128 + prow; j = j < p.seq_len ? j : p.seq_len - 1;       // (clamped to the ARRAY end: no wait for the position word)
+            int j = b * ALP_BATCH + r * 128 + prow; j = j < al_len<BATCH>(p, sq) ? j : al_len<BATCH>(p, sq) - 1;       // (clamped to the ARRAY end: no wait for the position word)
             r_.e[r] = E[j];
             r_.v[r] = *(const uint4*)(vbase + (size_t)j * vrow + half8 * 8);
         }
@@ -3402,7 +3433,10 @@ template <int HD> DEVINL void alp_lazy_body(const AttnParams& p) {
         run_pv(true, zsh[0]);
     }
     ALQ_STAMP(5);
-    if (wave < 4 && (lane & 15) == 0) p.out[(size_t)h * HD + ds * ALP_DS + 4 * wave + (lane >> 4)] = bf_trunc(acc);
+    if (wave < 4 && (lane & 15) == 0) {
+        if constexpr (BATCH) al_store(p, h, HD, ds * ALP_DS + 4 * wave + (lane >> 4), acc);
+        else p.out[(size_t)h * HD + ds * ALP_DS + 4 * wave + (lane >> 4)] = bf_trunc(acc);
+    }
     ALQ_STAMP(6);
 #undef ALQ_STAMP
 }
@@ -3410,8 +3444,9 @@ template <int HD> DEVINL void alp_lazy_body(const AttnParams& p) {
 // up to two batches (T <= 1024) the eager form is the faster one (all 512 threads share the first batch's p_j: 11.2 against 11.5 us at T = 768,
 // 9.6 against 10.1 at 272); from three batches on the lazy one (T = 2048: 15.1 -> 14.5 us, 4101: 23.0 -> 21.8).  T lives on the device (one captured
 // graph serves every position), so the choice is made here, per launch, uniformly over the grid.
-template <int HD> __global__ __launch_bounds__(ALP_NT) void attn_long_pv2_kernel(AttnParams p) {
-    if (p.st->pos + 1 <= 2 * ALP_BATCH) alp_eager_body<HD>(p); else alp_lazy_body<HD>(p);
+template <int HD, bool BATCH = false> __global__ __launch_bounds__(ALP_NT) void attn_long_pv2_kernel(AttnParams p) {
+    if constexpr (BATCH) { if (p.btab->st[blockIdx.z]->pos + 1 <= 2 * ALP_BATCH) alp_eager_body<HD, true>(p); else alp_lazy_body<HD, true>(p); }     // (per sequence: uniform over its workgroups)
+    else if (p.st->pos + 1 <= 2 * ALP_BATCH) alp_eager_body<HD>(p); else alp_lazy_body<HD>(p);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4334,6 +4369,12 @@ extern "C" hipError_t lnbk_init(void) {
     if ((e = hipFuncSetAttribute((const void*)attn_long_pv2_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)attn_long_pv2_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)attn_long_pv2_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)attn_long_pv_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)attn_long_pv_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)attn_long_pv_kernel<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)attn_long_pv2_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)attn_long_pv2_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute((const void*)attn_long_pv2_kernel<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)attn_one_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)attn_one_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     if ((e = hipFuncSetAttribute((const void*)attn_one_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
@@ -4355,6 +4396,24 @@ static hipError_t launch_attn_long(const AttnParams* p, hipStream_t st) {
     case 128: hipLaunchKernelGGL(attn_long_scores_kernel<128>, gs, dim3(ALS_NT), 0, st, ps); LNB_PV(128); break;
     case 64: hipLaunchKernelGGL(attn_long_scores_kernel<64>, gs, dim3(ALS_NT), 0, st, ps); LNB_PV(64); break;
     case 32: hipLaunchKernelGGL(attn_long_scores_kernel<32>, gs, dim3(ALS_NT), 0, st, ps); LNB_PV(32); break;
+#undef LNB_PV
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+// the batched pair (p->btab): p->S sequences in grid.z, p->seq_len = the largest member's cache length (e_buf [S][H][seq_len], z_part [S][H][ceil(seq_len/256)])
+static hipError_t launch_attn_long_batch(const AttnParams* p, hipStream_t st) {
+    const size_t lds = alp_lds_bytes(p->seq_len);
+    if (lds > 160 * 1024 || p->hd % ALP_DS || !p->e_buf || !p->z_part || !p->bkv || p->S < 1 || p->S > LNB_BATCH_MAX || (!p->out && !p->out_xt)) return hipErrorInvalidValue;
+    const dim3 gs(p->H, (p->seq_len + ALS_NT - 1) / ALS_NT, p->S), gp(p->H, p->hd / ALP_DS, p->S);
+    const bool lazy = [] { const char* e = getenv("LNB_ATTN_LAZY"); return !(e && *e && atoi(e) == 0); }();
+    AttnParams ps = *p;
+    { const char* e = getenv("LNB_ATTN_TOUCH"); ps.touch = (e && *e) ? (atoi(e) != 0) : 1; }
+    switch (p->hd) {
+#define LNB_PV(HD_) do { if (lazy) hipLaunchKernelGGL((attn_long_pv2_kernel<HD_, true>), gp, dim3(ALP_NT), lds, st, ps); else hipLaunchKernelGGL((attn_long_pv_kernel<HD_, true>), gp, dim3(ALP_NT), lds, st, ps); } while (0)
+    case 128: hipLaunchKernelGGL((attn_long_scores_kernel<128, true>), gs, dim3(ALS_NT), 0, st, ps); LNB_PV(128); break;
+    case 64: hipLaunchKernelGGL((attn_long_scores_kernel<64, true>), gs, dim3(ALS_NT), 0, st, ps); LNB_PV(64); break;
+    case 32: hipLaunchKernelGGL((attn_long_scores_kernel<32, true>), gs, dim3(ALS_NT), 0, st, ps); LNB_PV(32); break;
 #undef LNB_PV
     default: return hipErrorInvalidValue;
     }
@@ -4389,6 +4448,7 @@ extern "C" void lnbk_attn_gqa_dbg_dump(void) {
 }
 static bool attn_batch_dense() { const char* e = getenv("LNB_ATTN_BATCH_DENSE"); return !(e && *e && atoi(e) == 0); }   // (read per launch: a test switches it inside one process)
 extern "C" hipError_t lnbk_attn(const AttnParams* p, hipStream_t st) {
+    if (p->btab && p->longctx) return launch_attn_long_batch(p, st);      // batched decode / verify pass in the long-context form (the caller chose it: lnb_api.cpp batch_want_long / batch_select_form)
     if (p->longctx >= 2 && p->S == 1) return launch_attn_one(p, st);
     if (p->longctx && p->S == 1) return launch_attn_long(p, st);
     if (p->mfma && p->S >= 16 && (p->hd == 128 || p->hd == 64)) {       // prefill: 16 (attn_mfma_kernel) or 32 (attn_mfma2_kernel, round 6) query rows per wave on the matrix cores

@@ -229,6 +229,26 @@ func (ic *InferenceContext) SetDraft(lt *LlamaTransformer, maxDraft int, ngramMi
 	return lnbCall(func() C.int { return C.lnb_ctx_set_draft(ic.handle, C.int(maxDraft), C.int(ngramMin), C.int(ngramMax), p, C.int(len(corpus))) })
 }
 
+// SetBatchedAttention picks the attention form of DecodeSpeculativeUntil's verify passes: past longThreshold positions (negative: keep;
+// default: never, unless the context is beyond the one-workgroup kernels' reach) the long-context kernels.  forceZseq 1: every column
+// walks the serial f64 sum.  The bits are the same either way.
+func (ic *InferenceContext) SetBatchedAttention(lt *LlamaTransformer, longThreshold int, forceZseq int) error {
+	if err := ic.attach(lt); err != nil {
+		return err
+	}
+	return lnbCall(func() C.int { return C.lnb_ctx_set_batched_attention(ic.handle, C.int(longThreshold), C.int(forceZseq)) })
+}
+
+// VerifyAttentionForm reports what the last verify pass ran: 0 the one-workgroup attention kernels, 1 the long-context pair.
+func (ic *InferenceContext) VerifyAttentionForm(lt *LlamaTransformer) (int, error) {
+	if err := ic.attach(lt); err != nil {
+		return 0, err
+	}
+	var f C.int
+	err := lnbCall(func() C.int { return C.lnb_ctx_verify_attention_form(ic.handle, &f) })
+	return int(f), err
+}
+
 // DecodeSpeculativeUntil is DecodeGreedyUntil with drafts verified in batched passes over the weights: the same tokens, finished flag and
 // KV cache rows, fewer passes when the text repeats itself or the corpus.  history: the tokens before `token` (the prompt).
 func (ic *InferenceContext) DecodeSpeculativeUntil(lt *LlamaTransformer, history []TokenId, token TokenId, startPos int, maxSteps int) (tokens []TokenId, finished bool, stats SpecStats, err error) {

@@ -226,6 +226,10 @@ public:
     void SetDraft(int maxDraft, int ngramMin, int ngramMax, const std::vector<TokenId>& corpus = {}) {
         check(lnb_ctx_set_draft(h_, maxDraft, ngramMin, ngramMax, corpus.empty() ? nullptr : corpus.data(), (int)corpus.size()));
     }
+    // attention form of DecodeSpeculativeUntil's verify passes: past longThreshold positions (default: never, unless the context is beyond the
+    // one-workgroup kernels' reach) the long-context kernels; forceZseq: always walk the serial f64 sum.  Same bits either way.
+    void SetBatchedAttention(int longThreshold = -1, int forceZseq = 0) { check(lnb_ctx_set_batched_attention(h_, longThreshold, forceZseq)); }
+    int VerifyAttentionForm() const { int f = 0; check(lnb_ctx_verify_attention_form(h_, &f)); return f; }      // 0: one-workgroup kernels, 1: the long-context pair
     struct Speculative { std::vector<TokenId> Tokens; bool Finished = false; lnb_spec_stats Stats{}; };
     Speculative DecodeSpeculativeUntil(const std::vector<TokenId>& history, TokenId token, int startPos, int maxSteps) {
         Speculative r; r.Tokens.resize(maxSteps > 0 ? maxSteps : 1);

@@ -66,6 +66,7 @@ EXPORTS = [
     "lnb_ctx_set_token_probs", "lnb_ctx_read_token_probs", "lnb_ctx_token_prob_walks", "lnb_forward_score", "lnb_op_token_probs",
     "lnb_forward_append", "lnb_forward_score_append",
     "lnb_ctx_set_draft", "lnb_decode_speculative_until", "lnb_op_ngram_draft",
+    "lnb_batch_set_attention", "lnb_ctx_set_batched_attention", "lnb_batch_attention_form", "lnb_ctx_verify_attention_form",
 ]
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
 MAX_DRAFT = 15           # LNB_MAX_DRAFT of include/lnb.h (tests/test_speculative_cpu.py compares them)
@@ -170,6 +171,10 @@ def lib():
     L.lnb_batch_profile_kernel.argtypes = [vp, C.c_int, C.c_int, C.c_int, f32p]
     L.lnb_batch_set_state.argtypes = [vp, i32p, i32p]
     L.lnb_batch_check_error.argtypes = [vp]
+    L.lnb_batch_set_attention.argtypes = [vp, C.c_int, C.c_int]
+    L.lnb_ctx_set_batched_attention.argtypes = [vp, C.c_int, C.c_int]
+    L.lnb_batch_attention_form.argtypes = [vp, C.POINTER(C.c_int)]
+    L.lnb_ctx_verify_attention_form.argtypes = [vp, C.POINTER(C.c_int)]
     L.lnb_pipeline_tick_batch.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.lnb_pipeline_read_tokens.argtypes = [vp, C.c_int, C.c_int, vp]
     L.lnb_op_linear_mode.argtypes = [C.c_int, vp, vp, C.c_float, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -586,6 +591,18 @@ class InferenceContext:
         _chk(self.L.lnb_ctx_set_draft(self.h, int(max_draft), int(ngram_min), int(ngram_max), _p(a) if a.size else None, int(a.size)))
         return self
 
+    def set_batched_attention(self, long_threshold=-1, force_zseq=0):
+        """attention form of decode_speculative_until's verify passes: past long_threshold positions (default: never, unless the context is
+        beyond the one-workgroup kernels' reach) the long-context kernels; force_zseq: always walk the serial f64 sum.  Same bits."""
+        _chk(self.L.lnb_ctx_set_batched_attention(self.h, int(long_threshold), int(force_zseq)))
+        return self
+
+    def verify_attention_form(self):
+        """0: the last verify pass ran the one-workgroup attention kernels, 1: the long-context pair"""
+        n = C.c_int(0)
+        _chk(self.L.lnb_ctx_verify_attention_form(self.h, C.byref(n)))
+        return n.value
+
     def decode_speculative_until(self, history, token, start_pos, max_steps):
         """decode_greedy_until with drafts verified in batched passes (lnb_decode_speculative_until): the same tokens, logits and KV rows.
         history: the tokens before `token` (e.g. the prompt) -> (tokens, finished flag, stats dict, device ms)"""
@@ -686,6 +703,18 @@ class Batch:
         ms = C.c_float(0)
         _chk(self.L.lnb_batch_profile_kernel(self.h, which, pos, iters, C.byref(ms)))
         return ms.value
+
+    def set_attention(self, long_threshold=-1, force_zseq=0):
+        """calls whose largest start position + 1 exceeds long_threshold run the long-context attention (default: never, unless a member is
+        beyond the one-workgroup kernels' reach); force_zseq: every (sequence, head) walks the serial f64 sum.  Same bits either way."""
+        _chk(self.L.lnb_batch_set_attention(self.h, int(long_threshold), int(force_zseq)))
+        return self
+
+    def attention_form(self):
+        """0: the last call of this batch ran the one-workgroup attention kernels, 1: the long-context pair"""
+        n = C.c_int(0)
+        _chk(self.L.lnb_batch_attention_form(self.h, C.byref(n)))
+        return n.value
 
     def set_state(self, tokens, start_pos):
         """positions (and optionally next input tokens) of the sequences before a run of Pipeline.tick_batch steps"""

@@ -7,7 +7,12 @@ Rows: plain greedy (the reference figure); drafting with no corpus (synthetic we
 pass); corpus = the golden continuation, max_draft 3 / 7 / 15 (the CEILING); the same corpus with every m-th token corrupted, m = 2 / 4 / 8
 (tokens/s against acceptance); one run per verify width w = max_draft + 1 with the golden corpus (device ms per pass: nearly every pass is
 a verify pass of width w).  Each row is the median of 3 repeats, interleaved with greedy runs in the same process; every run's tokens are
-checked against tests/golden/configs1_tokens.json."""
+checked against tests/golden/configs1_tokens.json.
+
+  python tools/spec_bench.py --prefix 4096 [--seq-len N] [--long-threshold N] [--steps 64]
+the verify passes at a long context: a prompt of --prefix tokens, the corpus = the context's own greedy continuation (checked against it),
+rows greedy and width 2 / 8 / 16 only.  --seq-len: the context's capacity (beyond ~7.8 K the passes run the long-context attention);
+--long-threshold N: lnb_ctx_set_batched_attention (0 = the long-context form in every verify pass)."""
 import argparse
 import json
 import os
@@ -24,12 +29,58 @@ import numpy as np  # noqa: E402
 import lnb  # noqa: E402
 
 
+def long_prefix(args):
+    """verify passes at a long context (no golden there: the context's own greedy run is the reference)"""
+    P, N, V = args.prefix, min(args.steps, 64), lnb.LLAMA_8B["vocab_size"]
+    cfg = dict(lnb.LLAMA_8B, n_layers=args.layers)
+    need = P + N + 1
+    model = lnb.LlamaTransformer(**cfg).fill_synthetic(1234).finalize(need if need > 2 * cfg["max_seq_len"] else 0)
+    prompt = lnb.synth_tokens(99, P, V)
+    result = {"workload": "Llama-3.1-8B shape (%d layers), synthetic weights seed 1234, prompt synth_tokens(99, %d), %d generated tokens, corpus = the greedy continuation"
+                          % (args.layers, P, N), "seq_len": args.seq_len or need, "long_threshold": args.long_threshold, "forms": {}}
+    for form in ("rows", "columns"):
+        if form == "columns":
+            model.enable_batch()
+        ctx = lnb.InferenceContext(model, args.seq_len or need)
+        if args.long_threshold is not None:
+            ctx.set_batched_attention(args.long_threshold, 0)
+        _, first = ctx.Forward(prompt, 0, want_logits=False)
+        want, _, _ = ctx.decode_greedy_until(first, P, N)
+        rows = {}
+        for md in (1, 7, 15):
+            ctx.set_draft(md, 1, 4, want)
+            runs = []
+            for rep in range(args.reps + 1):                 # (the first run captures the graphs)
+                out, _, st, ms = ctx.decode_speculative_until(prompt, first, P, N)
+                assert (out == want).all(), "speculative: tokens differ from the greedy run"
+                runs.append(ms)
+            ms = statistics.median(runs[1:])
+            rows["width%d" % (md + 1)] = dict(st, hip_event_ms=round(ms, 3), ms_per_pass=round(ms / st["passes"], 4),
+                                              verify_attention_form=ctx.verify_attention_form() if hasattr(ctx, "verify_attention_form") else 0)
+        g = [ctx.decode_greedy_until(first, P, N)[2] for _ in range(args.reps)]
+        rows["greedy"] = {"ms_per_token": round(statistics.median(g) / N, 4)}
+        result["forms"][form] = rows
+        ctx.close()
+    model.close()
+    print(json.dumps(result))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=287)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--prefix", type=int, default=None, help="prompt length (default: the 128 tokens of configs[1])")
+    ap.add_argument("--seq-len", type=int, default=None, help="capacity of the context (default: prompt + steps + 1)")
+    ap.add_argument("--long-threshold", type=int, default=None, help="lnb_ctx_set_batched_attention(N)")
+    ap.add_argument("--layers", type=int, default=32)
     args = ap.parse_args()
+    if args.prefix is not None:
+        return long_prefix(args)
     g = json.load(open(os.path.join(ROOT, "tests", "golden", "configs1_tokens.json")))
     gold = np.array(g["tokens"], dtype=np.int32)
     N, P = min(args.steps, gold.size - 1), 128
