@@ -19,6 +19,7 @@
 #include <vector>
 #include "../../include/lnb.h"
 #include "lnb_device.h"
+#include "lnb_knobs.h"
 #include "lnb_rccl.h"
 static_assert(LNB_MAX_TOP_K == LNB_TOKPROB_MAX_K, "lnb.h and lnb_device.h disagree on the largest top-k");
 static_assert(LNB_MAX_DRAFT == LNB_SPEC_MAX_DRAFT && LNB_MAX_DRAFT + 1 <= LNB_STREAM_COLS, "a verify pass is one column group of at most 16 columns");
@@ -223,9 +224,9 @@ static void drop_graphs(lnb_ctx* c) {
     if (c->graph_long) { hipGraphExecDestroy(c->graph_long); c->graph_long = nullptr; }
     for (int i = 0; i < 2; i++) if (c->stage_graph[i]) { hipGraphExecDestroy(c->stage_graph[i]); c->stage_graph[i] = nullptr; }
 }
-static int env_int(const char* name, int dflt) { const char* s = getenv(name); return s && *s ? atoi(s) : dflt; }
-static int auto_rw(int lane_rows, const char* env, int K = 0, bool plain = false) {
-    int v = env_int(env, 0);
+static int auto_rw(int lane_rows, Knob env, int K = 0, bool plain = false, int unforced = 0) {      // unforced: the caller's choice while the knob is 0 (0: by shape)
+    const int v = knob(env);
+    if (v == 0 && unforced) return unforced;
     if (v == 16 || v == 32 || v == 64 || (v == 4 && plain && K % 128 == 0 && K <= 16384) || ((v == 56 || v == 28) && lane_rows % v == 0) || (v == 24 && K > 0 && K % 256 == 0)) return v;
     // thin matrices without a fused norm / rope epilogue: the row-broadcast kernel (products stay in registers)
     if (plain && lane_rows <= 16 * 256 && K > 0 && K % 128 == 0 && K <= 16384) return 4;
@@ -404,16 +405,17 @@ static int model_alloc(lnb_model* m) {
         reg_linear(m, "tok_embeddings.weight", m->tok_embd, dim, 0, 0, a.vocab_size, 2);
     }
     m->layers.resize(layer_end - layer_begin);
+    // block heights of the resident layouts, each knob read once per model: 24-row wq|wk|wv blocks (gemv_quad_kernel) / 56-row gate|up blocks when that puts one block on every CU (the 8B shape)
+    const int qkv_rows = m->q_dim + 2 * m->kv_dim, rwo = auto_rw(dim, Knob::RW_WO, m->q_dim, true), rw2 = auto_rw(dim, Knob::RW_W2, F, true);
+    const int rwq = auto_rw(qkv_rows, Knob::RW_QKV, dim, false, qkv_rows == 24 * g_num_cus && dim % 256 == 0 ? 24 : 0);
+    const int rw13 = auto_rw(F, Knob::RW_W13, 0, false, F == 56 * g_num_cus ? 56 : 0);
     for (int l = layer_begin; l < layer_end; l++) {
         LayerW& L = m->layers[l - layer_begin];
         char nm[128]; uint32_t base = 16u * (uint32_t)(l + 1);
         if (m->has_attn(l)) {
             if (alloc_linear(&L.attn_norm, dim, wb)) return -1;
-            // wq|wk|wv: 24-row blocks (gemv_quad_kernel: quad-DPP chain waves, one block on every CU) when the rows divide that way -- the 8B shape
-            int rwq = auto_rw(m->q_dim + 2 * m->kv_dim, "LNB_RW_QKV", dim);
-            if (env_int("LNB_RW_QKV", 0) == 0 && m->q_dim + 2 * m->kv_dim == 24 * g_num_cus && dim % 256 == 0) rwq = 24;
             if (alloc_tiled(L.wqkv, m->q_dim + 2 * m->kv_dim, dim, rwq, 1, wb)) return -1;
-            if (alloc_tiled(L.wo, dim, m->q_dim, auto_rw(dim, "LNB_RW_WO", m->q_dim, true), 1, wb)) return -1;
+            if (alloc_tiled(L.wo, dim, m->q_dim, rwo, 1, wb)) return -1;
             snprintf(nm, sizeof nm, "layers.%d.attention_norm.weight", l); reg_linear(m, nm, L.attn_norm, dim, base + 0, 1);
             snprintf(nm, sizeof nm, "layers.%d.attention.wq.weight", l); reg_tiled(m, nm, &L.wqkv, m->q_dim, dim, 0, 0, base + 1);
             snprintf(nm, sizeof nm, "layers.%d.attention.wk.weight", l); reg_tiled(m, nm, &L.wqkv, m->kv_dim, dim, m->q_dim, 0, base + 2);
@@ -422,24 +424,20 @@ static int model_alloc(lnb_model* m) {
         }
         if (m->has_w13(l)) {
             if (alloc_linear(&L.ffn_norm, dim, wb)) return -1;
-            {   // two-chain gate|up matrix: when the rows split into exactly one 56-row block per CU, take it (all CUs stream)
-                int rw13 = auto_rw(F, "LNB_RW_W13");
-                if (env_int("LNB_RW_W13", 0) == 0 && F == 56 * g_num_cus) rw13 = 56;
-                if (alloc_tiled(L.w13, F, dim, rw13, 2, wb)) return -1;
-            }
+            if (alloc_tiled(L.w13, F, dim, rw13, 2, wb)) return -1;
             snprintf(nm, sizeof nm, "layers.%d.ffn_norm.weight", l); reg_linear(m, nm, L.ffn_norm, dim, base + 5, 1);
             snprintf(nm, sizeof nm, "layers.%d.feed_forward.w1.weight", l); reg_tiled(m, nm, &L.w13, F, dim, 0, 0, base + 6);
             snprintf(nm, sizeof nm, "layers.%d.feed_forward.w3.weight", l); reg_tiled(m, nm, &L.w13, F, dim, 0, 1, base + 8);
         }
         if (m->has_w2(l)) {
-            if (alloc_tiled(L.w2, dim, F, auto_rw(dim, "LNB_RW_W2", F, true), 1, wb)) return -1;
+            if (alloc_tiled(L.w2, dim, F, rw2, 1, wb)) return -1;
             snprintf(nm, sizeof nm, "layers.%d.feed_forward.w2.weight", l); reg_tiled(m, nm, &L.w2, dim, F, 0, 0, base + 7);
         }
     }
     if (m->last()) {
         if (alloc_linear(&m->norm, dim, wb)) return -1;
         reg_linear(m, "norm.weight", m->norm, dim, 1, 1);
-        if (alloc_tiled(m->output, a.vocab_size, dim, auto_rw(a.vocab_size, "LNB_RW_OUT"), 1, wb)) return -1;
+        if (alloc_tiled(m->output, a.vocab_size, dim, auto_rw(a.vocab_size, Knob::RW_OUT), 1, wb)) return -1;
         reg_tiled(m, "output.weight", &m->output, a.vocab_size, dim, 0, 0, 2);
     }
     return 0;
@@ -665,7 +663,7 @@ static int ctx_alloc(lnb_ctx* c) {
     HIPCHK(hipMalloc((void**)&c->attn_cnt, ((size_t)m->a.n_heads + 4) * 4)); HIPCHK(hipMemsetAsync(c->attn_cnt, 0, ((size_t)m->a.n_heads + 4) * 4, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     // crossover measured on MI355X (tools/att_timing.py): the one-workgroup-per-head kernel wins below a few hundred positions
-    c->attn_long_T = env_int("LNB_ATTN_LONG_T", 512);
+    c->attn_long_T = knob(Knob::ATTN_LONG_T);
     c->attn_short_cap = lnbk_attn_short_max_T(m->head_dim);
     return 0;
 }
@@ -813,7 +811,7 @@ extern "C" int lnb_ctx_synchronize(lnb_ctx* c) { if (!c) return fail("null argum
 enum { K_QKV = 0, K_ATTN = 1, K_WO = 2, K_W13 = 3, K_W2 = 4, K_HEAD = 5, K_LAYER = 6 };
 // Calls of 16 or more rows (prefill) run the same exact chains on the f32 matrix cores (gemm_mfma_kernel); LNB_PREFILL_MFMA=0
 // keeps them on the S = 1 kernels (one launch row per token row), which is what the parity tests compare the two with.
-static bool use_mfma(int S) { static const int on = env_int("LNB_PREFILL_MFMA", 1); return on && S >= 16; }
+static bool use_mfma(int S) { return knob(Knob::PREFILL_MFMA) && S >= 16; }
 static GemmParams gemm_of(const TiledDesc& t, const uint16_t* x, int K, int n_rows, int S, const StepState* st) {
     GemmParams g{}; g.w = t.w; g.rw = t.rw; g.nch = t.nch; g.x = x; g.K = K; g.n_rows = n_rows; g.S = S; g.st = st; g.w16 = t.w16; return g;
 }
@@ -827,14 +825,12 @@ static hipError_t gemm_dispatch(int mode, const GemmParams* g, int epi, hipStrea
     // below ~200 rows the bf16 GEMM's 256-row weight tiles leave most CUs without work (wq|wk|wv: 24 workgroups) and the exact
     // kernel with its 16-row tiles is the faster one (128 rows: 29.6 ms against 36.6 ms per Forward): the tolerance mode may always
     // use an exact kernel
-    static const int min_rows = env_int("LNB_FAST_GEMM_MIN_ROWS", 192);
-    if (mode == LNB_MODE_FAST && g->S >= min_rows) { hipError_t e = lnbk_fast_gemm(g, epi, st); if (e != hipErrorNotSupported) return e; }
+    if (mode == LNB_MODE_FAST && g->S >= knob(Knob::FAST_GEMM_MIN_ROWS)) { hipError_t e = lnbk_fast_gemm(g, epi, st); if (e != hipErrorNotSupported) return e; }
     // exact order with the matrix-core copy of the weights present (lnb_model_enable_batch): the streaming feed -- the same chains, the
     // same bits (tests/test_gpu_batch.py), the weights never staged through the LDS; LNB_PREFILL_STREAM=0 keeps the LDS-tiled kernel
     // Round 5: the same kernel also reads the RESIDENT layouts (no copy needed: the row-broadcast units are M16 units in another order, the chain
     // layouts' units are transposed inside the lane quads); LNB_PREFILL_NATIVE=0 keeps the LDS-tiled kernel for models without the copy
-    static const int stream_on = env_int("LNB_PREFILL_STREAM", 1), native_on = env_int("LNB_PREFILL_NATIVE", 1);
-    if (stream_on && (g->K & 127) == 0 && (g->w16 || (native_on && g->w && (g->rw == 4 ? g->nch == 1 && (epi == EPI_STORE || epi == EPI_RESID) : g->rw >= 16))))
+    if (knob(Knob::PREFILL_STREAM) && (g->K & 127) == 0 && (g->w16 || (knob(Knob::PREFILL_NATIVE) && g->w && (g->rw == 4 ? g->nch == 1 && (epi == EPI_STORE || epi == EPI_RESID) : g->rw >= 16))))
         return lnbk_gemm_stream(g, epi, g_num_cus, st);
     return lnbk_gemm(g, epi, st);
 }
@@ -884,8 +880,7 @@ static int enqueue_layer_kernel(lnb_ctx* c, int l, int S, int which, hipStream_t
             // in-launch exchange (write-through stores drained + arrive + poll: 6.6 k cycles) plus a second dependent round trip for e_j (6.3 k).
             // Opt-in: LNB_ATTN_ONE=1, or bit 3 (8) of lnb_ctx_set_attention's flags; only for a context whose stream owns the chip (latency schedule)
             // and whose (head, slice) grid fits the CUs.  Bit 1 (2) of the flags keeps the two launches whatever the environment says.
-            static const int one_env = env_int("LNB_ATTN_ONE", 0);
-            const bool one = (one_env || (c->force_zseq & 12)) && !(c->force_zseq & 2) && c->sched == LNB_SCHED_LATENCY && m->head_dim % 16 == 0 &&
+            const bool one = (knob(Knob::ATTN_ONE) || (c->force_zseq & 12)) && !(c->force_zseq & 2) && c->sched == LNB_SCHED_LATENCY && m->head_dim % 16 == 0 &&
                              a.n_heads * (m->head_dim / 16) <= g_num_cus && lnbk_attn_one_lds(c->seq_len, m->head_dim) <= (size_t)160 * 1024;
             ap.longctx = one ? ((c->force_zseq & 4) ? 3 : 2) : 1;
         }
@@ -902,7 +897,7 @@ static int enqueue_layer_kernel(lnb_ctx* c, int l, int S, int which, hipStream_t
         f.out = c->ffn; f.silu = m->silu; f.sched = c->sched;
         set_grid(f, L.w13); HIPCHK(gemv_dispatch(c, &f, L.w13.rw, 2, EPI_SILU_MUL, 1, st)); return 0; }
     case K_W2: {    // w2 + residual  (:619, :248)
-        GemvParams d{}; d.w = L.w2.w; d.x = c->ffn; d.K = m->ffn_hidden; d.n_rows = a.dim; d.S = S; d.st = c->st; d.out = c->x; d.res = hbuf; d.lds_pad = lds_pad; d.sched = c->sched; d.prio = env_int("LNB_W2_PRIO", 0);
+        GemvParams d{}; d.w = L.w2.w; d.x = c->ffn; d.K = m->ffn_hidden; d.n_rows = a.dim; d.S = S; d.st = c->st; d.out = c->x; d.res = hbuf; d.lds_pad = lds_pad; d.sched = c->sched; d.prio = knob(Knob::W2_PRIO);
         set_grid(d, L.w2); HIPCHK(gemv_dispatch(c, &d, L.w2.rw, 1, EPI_RESID, 0, st)); return 0; }
     }
     return fail("bad kernel id");
@@ -962,12 +957,12 @@ static int check_call(lnb_ctx* c, int seq, int start_pos, bool causal = false) {
     for (int l = c->m->layer_begin; l < c->m->layer_end && !stage_has_attn; l++) stage_has_attn = c->m->has_attn(l);
     // a one-token call on a context that still holds a LARGE scratch from its prompt (1.07 GB for 4096 rows of the 8B shape) gives it back: the decode steps never read it,
     // and a host that prefills many contexts would otherwise keep a gigabyte per context for their whole life.  Up to LNB_ATTN_SIDX_KEEP_MB (default 256) it stays for the next prompt.
-    if (seq == 1 && c->score_idx && c->score_idx_bytes > ((size_t)env_int("LNB_ATTN_SIDX_KEEP_MB", 256) << 20)) {
+    if (seq == 1 && c->score_idx && c->score_idx_bytes > ((size_t)knob(Knob::ATTN_SIDX_KEEP_MB) << 20)) {
         HIPCHK(hipStreamSynchronize(c->stream));
         hipFree(c->score_idx); c->score_idx = nullptr; c->score_idx_bytes = 0;
     }
     if (mfma_attn && stage_has_attn && c->mode != LNB_MODE_FAST) {
-        const int cap_mb = env_int("LNB_ATTN_SIDX_MB", 4096);                 // (read per call: a test switches it inside one process)
+        const int cap_mb = knob(Knob::ATTN_SIDX_MB);                 // (read per call: a test switches it inside one process)
         const size_t jt = (size_t)(T + 15) / 16, need = (size_t)c->m->a.n_heads * (size_t)((seq + 15) / 16) * jt * 512;
         if (cap_mb > 0 && need <= ((size_t)cap_mb << 20)) {
             if (need > c->score_idx_bytes) {
@@ -1180,7 +1175,7 @@ static int enqueue_decode_step(lnb_ctx* c) {
     lnb_model* m = c->m;
     // LNB_MEASURE_SKIP_TOKEN_KERNELS=1 (timing only, the tokens are garbage): the step without its embedding gather and argmax launches =
     // the most that fusing them into the neighbouring products could return (NOTES 5.8)
-    const bool skip = env_int("LNB_MEASURE_SKIP_TOKEN_KERNELS", 0) != 0;
+    const bool skip = knob(Knob::MEASURE_SKIP_TOKEN_KERNELS) != 0;
     if (!skip) HIPCHK(lnbk_embed(m->tok_embd, c->dtok, c->x, 1, m->a.dim, m->a.vocab_size, c->derr, c->stream));
     if (enqueue_layers(c, 1, false)) return -1;
     if (enqueue_head(c, 0, 1)) return -1;
@@ -1295,7 +1290,7 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     if (check_call(c, 1, start_pos) || check_call(c, 1, start_pos + n_steps - 1)) return -1;
     if (token < 0 || token >= m->a.vocab_size) return fail("token id at index 0 is outside the vocabulary");
     hipStream_t st = c->stream;
-    const bool use_graph = env_int("LNB_NO_GRAPH", 0) == 0;
+    const bool use_graph = knob(Knob::NO_GRAPH) == 0;
     if (use_graph && capture_decode_graphs(c, start_pos, n_steps)) return -1;
     c->tp_last_k = 0; c->tp_last_n = 0;
     HIPCHK(hipMemcpyAsync(c->dtok, &token, 4, hipMemcpyHostToDevice, st));
@@ -1441,7 +1436,7 @@ extern "C" int lnb_profile_kernel(lnb_ctx* c, int which, int pos, int iters, flo
         HIPCHK(hipEventCreateWithFlags(&ef, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ej, hipEventDisableTiming));
         c->attn_long = false;
         HIPCHK(ctx_set_state(c, pos, 0, true));
-        const int nl2 = m->layer_end - m->layer_begin, pad = env_int("LNB_W2_LDS_PAD", 28 * 1024);
+        const int nl2 = m->layer_end - m->layer_begin, pad = knob(Knob::W2_LDS_PAD);
         auto pair = [&](int i) -> int {
             const int l = m->layer_begin + i % nl2;
             HIPCHK(hipEventRecord(ef, st)); HIPCHK(hipStreamWaitEvent(st2, ef, 0));
@@ -1467,7 +1462,7 @@ extern "C" int lnb_profile_kernel(lnb_ctx* c, int which, int pos, int iters, flo
     // consecutive launches walk through the layers so that every launch streams its weights from HBM
     // (one layer's 235 MB gate/up matrix would otherwise sit in the 256 MiB Infinity Cache)
     auto run = [&](int i) -> int {
-        int l = m->layer_begin + (env_int("LNB_PROFILE_SAME_LAYER", 0) ? 0 : (i % nl));
+        int l = m->layer_begin + (knob(Knob::PROFILE_SAME_LAYER) ? 0 : (i % nl));
         if (which == K_HEAD) return enqueue_head(c, 0, 1);
         if (which == K_LAYER) { for (int k = K_QKV; k <= K_W2; k++) if (enqueue_layer_kernel(c, l, 1, k)) return -1; return 0; }
         return enqueue_layer_kernel(c, l, 1, which);
@@ -1479,7 +1474,8 @@ extern "C" int lnb_profile_kernel(lnb_ctx* c, int which, int pos, int iters, flo
     HIPCHK(hipStreamSynchronize(st));
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     *avg_ms_out = ms / (float)iters;
-    if (env_int("LNB_GEMV_TIMING", 0) && which == K_ATTN) {
+    const bool timing = knob(Knob::GEMV_TIMING) != 0;
+    if (timing && which == K_ATTN) {
         long long* dbuf = nullptr;
         HIPCHK(hipMalloc((void**)&dbuf, 64 * 8)); HIPCHK(hipMemsetAsync(dbuf, 0, 64 * 8, st));
         g_dbg = dbuf;
@@ -1497,7 +1493,7 @@ extern "C" int lnb_profile_kernel(lnb_ctx* c, int which, int pos, int iters, flo
             fprintf(stderr, "\n");
         }
     }
-    if (env_int("LNB_GEMV_TIMING", 0) && which != K_ATTN && which != K_LAYER) {
+    if (timing && which != K_ATTN && which != K_LAYER) {
         double v[8 * 16];
         if (gemv_stamps(c, which, v, 1)) return -1;
         fprintf(stderr, "[timing] kernel class %d: per-wave s_memtime ticks (avg over workgroups)\n", which);
@@ -1742,8 +1738,7 @@ static GemmParams wide_of(const lnb_batch* b, const TiledDesc& t, const uint16_t
 // wave, its operands unpacked by the same wave); the fat matrices stay rows.  The activations between them change layout at their producers:
 // norm -> xt groups (batch_rmsnorm_xt_kernel), attention -> out_xt groups, SiLU*up epilogue -> out_xt groups.
 static bool batch_groups(const lnb_batch* b) {
-    static const int on = env_int("LNB_BATCH_GROUPS", 1);
-    return on && !b->rows_form && b->n > LNB_STREAM_COLS && b->n <= 2 * LNB_STREAM_COLS;
+    return knob(Knob::BATCH_GROUPS) && !b->rows_form && b->n > LNB_STREAM_COLS && b->n <= 2 * LNB_STREAM_COLS;
 }
 static int enqueue_batch_kernel_wide(lnb_batch* b, int l, int which) {
     lnb_model* m = b->m; const lnb_model_args& a = m->a; hipStream_t st = b->stream;
@@ -1909,7 +1904,7 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     int max_pos = 0;
     for (int s = 0; s < b->n; s++) max_pos = std::max(max_pos, start_pos[s]);         // (a frozen sequence does not move the form)
     if (batch_select_form(b, batch_want_long(b, max_pos))) return -1;
-    const bool use_graph = env_int("LNB_NO_GRAPH", 0) == 0;
+    const bool use_graph = knob(Knob::NO_GRAPH) == 0;
     hipGraphExec_t* const gslot = b->attn_long ? &b->graph_long : &b->graph;       // one captured step per form
     if (use_graph && !*gslot) {
         hipGraph_t g = nullptr;
@@ -2315,7 +2310,8 @@ struct lnb_pipe {
     bool use_graph = true;
     bool host = false;                     // no transport: the host layer moves the boundary buffers (lnb_pipeline_init_host)
 };
-static int pipe_log_cap() { const int v = env_int("LNB_PIPELINE_LOG_CAP", 1 << 16); return v < 4 ? 4 : v; }   // (the env knob is for the wrap-around test)
+static bool pipe_use_graph() { return knob(Knob::PIPELINE_GRAPH) != 0; }
+static int pipe_log_cap() { const int v = knob(Knob::PIPELINE_LOG_CAP); return v < 4 ? 4 : v; }   // (the env knob is for the wrap-around test)
 #define NCCLCHK(p_, expr) do { int r_ = (expr); if (r_ != 0) return fail("%s failed: %s (%s:%d)", #expr, (p_)->api->GetErrorString(r_), __FILE__, __LINE__); } while (0)
 
 extern "C" int lnb_pipeline_unique_id(void* id128) {
@@ -2338,7 +2334,7 @@ extern "C" int lnb_pipeline_init(lnb_model* m, int rank, int world, const void* 
     if (world > 1 && !id128) return fail("null unique id");
     HIPCHK(hipSetDevice(m->device));
     lnb_pipe* p = new lnb_pipe();
-    p->m = m; p->rank = rank; p->world = world; p->use_graph = env_int("LNB_PIPELINE_GRAPH", 1) != 0;
+    p->m = m; p->rank = rank; p->world = world; p->use_graph = pipe_use_graph();
     if (world > 1) {
         p->api = lnb_rccl_load();
         if (!p->api) { delete p; return -1; }
@@ -2361,7 +2357,7 @@ extern "C" int lnb_pipeline_init_loopback(lnb_model* m, int rank, int world, con
     if ((rank == world - 1) != m->last()) return fail("pipeline rank %d of %d: only the last stage owns norm + output (this stage ends at block part %d)", rank, world, m->part_end);
     HIPCHK(hipSetDevice(m->device));
     lnb_pipe* p = new lnb_pipe();
-    p->m = m; p->rank = rank; p->world = world; p->use_graph = env_int("LNB_PIPELINE_GRAPH", 1) != 0;
+    p->m = m; p->rank = rank; p->world = world; p->use_graph = pipe_use_graph();
     hipError_t e = hipStreamCreateWithFlags(&p->xs, hipStreamNonBlocking);
     if (e == hipSuccess) { p->tok_cap = pipe_log_cap(); e = hipHostMalloc((void**)&p->h_tok, (size_t)p->tok_cap * 4, hipHostMallocDefault); }
     if (e != hipSuccess) { fail("pipeline init: %s", hipGetErrorString(e)); if (p->xs) hipStreamDestroy(p->xs); delete p; return -1; }
@@ -2393,7 +2389,7 @@ extern "C" int lnb_pipeline_init_host(lnb_model* m, int rank, int world, lnb_pip
     if ((rank == world - 1) != m->last()) return fail("pipeline rank %d of %d: only the last stage owns norm + output (this stage ends at block part %d)", rank, world, m->part_end);
     HIPCHK(hipSetDevice(m->device));
     lnb_pipe* p = new lnb_pipe();
-    p->m = m; p->rank = rank; p->world = world; p->host = true; p->use_graph = env_int("LNB_PIPELINE_GRAPH", 1) != 0;
+    p->m = m; p->rank = rank; p->world = world; p->host = true; p->use_graph = pipe_use_graph();
     hipError_t e = hipStreamCreateWithFlags(&p->xs, hipStreamNonBlocking);
     if (e == hipSuccess) { p->tok_cap = pipe_log_cap(); e = hipHostMalloc((void**)&p->h_tok, (size_t)p->tok_cap * 4, hipHostMallocDefault); }
     if (e != hipSuccess) { fail("pipeline init: %s", hipGetErrorString(e)); if (p->xs) hipStreamDestroy(p->xs); delete p; return -1; }
@@ -2734,7 +2730,7 @@ static int op_linear_impl(int device, const uint16_t* x, const uint16_t* norm_w,
     HIPCHK(lnbk_init());
     HIPCHK(lnbk_fast_init());
     if (mode != LNB_MODE_EXACT && mode != LNB_MODE_FAST) return fail("unknown mode %d", mode);
-    if (rw == 0) rw = auto_rw(n_out, "LNB_RW_OP", k_in, norm_w == nullptr);
+    if (rw == 0) rw = auto_rw(n_out, Knob::RW_OP, k_in, norm_w == nullptr);
     if (rw != 16 && rw != 32 && rw != 64 && !(rw == 4 && !norm_w && k_in % 128 == 0 && k_in <= 16384) && !(rw == 24 && k_in % 256 == 0))
         return fail("rw must be 16, 32 or 64 (or 4: row-broadcast layout, no fused norm, in_features a multiple of 128; or 24: quad layout, in_features a multiple of 256)");
     if ((size_t)k_in * 4 > 120 * 1024) return fail("in_features %d does not fit the LDS staging", k_in);
@@ -2748,7 +2744,7 @@ static int op_linear_impl(int device, const uint16_t* x, const uint16_t* norm_w,
     HIPCHK(hipMemcpy(dw, w, (size_t)n_out * k_in * 2, hipMemcpyHostToDevice));
     if (norm_w) { HIPCHK(hipMalloc((void**)&dn, (size_t)k_in * 2)); HIPCHK(hipMemcpy(dn, norm_w, (size_t)k_in * 2, hipMemcpyHostToDevice)); }
     HIPCHK(lnbk_tile(dw, t.w, n_out, k_in, 0, 0, rw, 1, 0, nullptr));
-    if (use_mfma(rows) && env_int("LNB_OP_STREAM", 0) && k_in % 128 == 0) {      // (tests: the same operator through gemm_stream_kernel)
+    if (use_mfma(rows) && knob(Knob::OP_STREAM) && k_in % 128 == 0) {      // (tests: the same operator through gemm_stream_kernel)
         HIPCHK(lnbk_batch_prepare());
         const size_t mb = m16_elems(n_out, k_in, 1) * 2;
         HIPCHK(hipMalloc((void**)&t.w16, mb)); HIPCHK(hipMemset(t.w16, 0, mb));

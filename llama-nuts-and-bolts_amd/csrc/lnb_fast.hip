@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "lnb_device.h"
+#include "lnb_knobs.h"
 
 #define DEVINL __device__ __forceinline__
 
@@ -472,7 +473,7 @@ template <int EPI, int NCH> hipError_t launch_gemm_fast(const GemmParams* p, int
     }
     // 128-row batch tiles with two workgroups per CU win while there are few tiles (512 rows: 35.6 against 42.5 ms per Forward of the 8B
     // shape), 256-row tiles with one workgroup per CU from ~1000 rows up (2048: 61.8 against 67.5 ms; 4096: 94.8 against 128.7)
-    static const int two = [] { const char* e = getenv("LNB_FAST_GEMM_2WG"); return e && *e ? atoi(e) : -1; }();   // -1: by row count
+    const int two = knob(Knob::FAST_GEMM_2WG);                // -1: by row count
     if (two == 1 || (two < 0 && p->S < 1024)) {              // 128 batch rows, two workgroups per CU
         if constexpr (NCH == 1) if (layb) return launch_gemm_fast_t<EPI, NCH, true, 4, 2>(p, st);
         return launch_gemm_fast_t<EPI, NCH, false, 4, 2>(p, st);
@@ -628,7 +629,7 @@ template <int HD> __global__ __launch_bounds__(256, 2) void fast_attn_prefill_ke
 }
 
 int fast_rg(int rw, int nch, int n_blocks) {
-    static const int force = [] { const char* e = getenv("LNB_FAST_RG"); return e && *e ? atoi(e) : 0; }();
+    const int force = knob(Knob::FAST_RG);
     if (force && rw % force == 0 && (force == 8 || force == 16 || force == 32 || force == 64)) return force;
     // measured on MI355X (8B shape, gpurun call A of round 2): LM head (2004 blocks of 64) 181 / 170 / 154 us with 8 / 16 / 32 rows per unit,
     // wq|wk|wv (192 blocks of 32) 14.1 / 13.0 / 17.0 us: the longer the contiguous run per wave load the better, as long as the
@@ -646,7 +647,7 @@ hipError_t launch_a_rg(const GemvParams* p, int rw, hipStream_t st) {
     const size_t lds = (size_t)p->K * 4 + 4 * NCH * 64 * 4 + 64;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const int units = p->n_blocks * (rw / RG);
-    static const int cap = [] { const char* e = getenv("LNB_FAST_GRID_CAP"); return e && *e ? atoi(e) : 2048; }();
+    const int cap = knob(Knob::FAST_GRID_CAP);
     hipLaunchKernelGGL(kfn, dim3((unsigned)(units < cap ? units : cap), (unsigned)p->S), dim3(256), lds, st, *p, rw);
     return hipGetLastError();
 }

@@ -4134,18 +4134,36 @@ __global__ void synth_fill_kernel(uint16_t* dst, int rows, int K, int row_off, i
 }
 
 #include "lnb_batch_kernels.h"
+#include "lnb_knobs.h"
 
 // ------------------------------------------------------------------------------------------------
 // host-side launchers (called from lnb_api.cpp)
 // ------------------------------------------------------------------------------------------------
+// Dynamic-LDS limits: a launcher called with NULL params ("prepare") raises the limit of every kernel it can pick and launches nothing: what is launched
+// and what is raised is one list.  Never inside a stream capture: prepare is reached from lnbk_init / lnbk_batch_prepare only.  Stops at the first error.
+template <class... K> static hipError_t raise_lds_to(int bytes, K... kernels) {
+    hipError_t e = hipSuccess;
+    ((e = e != hipSuccess ? e : hipFuncSetAttribute((const void*)kernels, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)), ...);
+    return e;
+}
+template <class... K> static hipError_t raise_lds(K... kernels) { return raise_lds_to(160 * 1024, kernels...); }
+// f(std::integral_constant<int, HD>) for p's head dimension (MIN_HD 64: the matrix-core forms have none for 32), hipErrorInvalidValue for one without
+// instantiations; NULL p (prepare): every head dimension in turn, up to the first error
+template <int MIN_HD = 32, class F> static hipError_t with_hd(const AttnParams* p, F&& f) {
+    hipError_t e = hipErrorInvalidValue;
+    if (!p || p->hd == 128) e = f(std::integral_constant<int, 128>{});
+    if (p ? p->hd == 64 : e == hipSuccess) e = f(std::integral_constant<int, 64>{});
+    if constexpr (MIN_HD <= 32) if (p ? p->hd == 32 : e == hipSuccess) e = f(std::integral_constant<int, 32>{});
+    return e;
+}
+
 // x staging: a whole number of stages (steps per stage = stage_bytes / (nch*rw*2)) + 64 floats of slack
 static size_t xs_bytes(int K, int steps_per_stage) { return ((size_t)((K + steps_per_stage - 1) / steps_per_stage) * steps_per_stage + 320) * 4 + 16; }
 
 template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC>
 static hipError_t launch_chain_x(const GemvParams* p, hipStream_t st) {
     auto kfn = gemv_chain_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>;
-    if (!p)   // prepare: raise the dynamic-LDS limit once, outside any stream capture
-        return hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (!p) return raise_lds(kfn);
     size_t lds = 4 * (size_t)SA + xs_bytes(p->K, SA / (NCH * RW * 2));
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (xs_bytes(p->K, SA / (NCH * RW * 2)) / 4 > (size_t)XC * (1 + NH) * 512) return hipErrorInvalidValue;   // x staging registers
@@ -4173,7 +4191,7 @@ static hipError_t launch_chain_t(const GemvParams* p, hipStream_t st) {
 template <int RW, int KS, int NH, int R, int EPI, bool NORM, int XC>
 static hipError_t launch_quad_x(const GemvParams* p, hipStream_t st) {
     auto kfn = gemv_quad_kernel<RW, KS, NH, R, EPI, NORM, XC>;
-    if (!p) return hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (!p) return raise_lds(kfn);
     constexpr int NW = gq_ncw(RW) + NH;
     constexpr size_t SB = (size_t)RW * KS * 4;
     if (p->K % KS) return hipErrorInvalidValue;                                  // whole stages only (auto_rw in lnb_api.cpp picks this layout accordingly)
@@ -4196,15 +4214,16 @@ static hipError_t launch_quad_t(const GemvParams* p, hipStream_t st) {
     return launch_quad_x<RW, KS, NH, R, EPI, NORM, XCh<NORM>::value>(p, st);
 }
 
-static bool env_tp_w13() { static const int on = [] { const char* e = getenv("LNB_TP_W13"); return e && *e ? atoi(e) : 1; }(); return on != 0; }   // (A/B switch of the throughput gate|up form)
 template <int EPI, bool NORM, int NCH>
 static hipError_t launch_gemv_rw(const GemvParams* p, int rw, hipStream_t st) {
+    // a choice between two forms that depends on the call: a launch takes one of them, prepare raises both
+    auto either = [&](bool first, auto a, auto b) { const hipError_t e = (p && !first) ? hipSuccess : a(p, st); return (p ? first : e != hipSuccess) ? e : b(p, st); };
     // RW 24 (one chain; the 8B wq|wk|wv: 6144 rows = 256 blocks of 24, one per CU): quad-DPP chain waves fed through the LDS, 256-step
     // stages, six helpers x 2 loads x 5 stages = 60 KiB in flight per CU
     // Throughput schedule (GemvParams.sched, lnb_ctx_set_schedule): the same kernel with 128-step stages -- 3 x 12 KiB of products + x = 55 KB of LDS
     // instead of 91 KB, so that a workgroup fits a CU beside the gate|up workgroup (75 KB) of another context's step; twice the stage barriers
     // (slower alone, which is why one stream keeps the 256-step form), ten stages of one load per helper in flight = the same 60 KiB per CU.
-    if constexpr (NCH == 1) if (rw == 24) return (p && p->sched) ? launch_quad_t<24, 128, 6, 10, EPI, NORM>(p, st) : launch_quad_t<24, 256, 6, LNB_QUAD_R, EPI, NORM>(p, st);
+    if constexpr (NCH == 1) if (rw == 24) return either(p && p->sched, launch_quad_t<24, 128, 6, 10, EPI, NORM>, launch_quad_t<24, 256, 6, LNB_QUAD_R, EPI, NORM>);
     // stage geometry (one workgroup per CU).  SA = bf16 bytes per stage, R = stages in flight per helper.
     //  RW 16/32 plain (thin; chain bound): 8 KiB stages, 2 helpers x 4 loads x 7 stages = 56 KiB in flight per CU.
     //  RW 32 with the fused RMSNorm (wq|wk|wv): six helpers so that the exact parallel norm sum has 384 folding lanes, and
@@ -4212,15 +4231,19 @@ static hipError_t launch_gemv_rw(const GemvParams* p, int rw, hipStream_t st) {
     //  chain at 10.2 cycles per step, 192-step ones at 8.7); 6 x 2 loads x 5 stages = 60 KiB in flight per CU.
     //  RW 64 (fat; HBM bound): 12 KiB stages, six helpers paired on three SIMDs (the chain wave owns the fourth),
     //  6 x 2 loads x 8 stages = 96 KiB in flight per CU (5 stages: 5.8 TB/s on the LM head, 8: 6.2, 14: worse again).
-    // very long rows (70B-like w2: K = 28672): x needs more staging registers than three stager waves hold -> four helpers
-    if (p && !NORM && NCH == 1 && (rw == 16 || rw == 32) && xs_bytes(p->K, 8192 / (rw * 2)) / 4 > (size_t)XCh<false>::value * 3 * 512)
-        return rw == 16 ? launch_chain_t<16, 1, 8192, 4, 7, EPI, false>(p, st) : launch_chain_t<32, 1, 8192, 4, 7, EPI, false>(p, st);
+    // very long rows (70B-like w2: K = 28672): x needs more staging registers than three stager waves hold -> four helpers (prepare: these, then on)
+    if (!NORM && NCH == 1 && (rw == 16 || rw == 32) && (!p || xs_bytes(p->K, 8192 / (rw * 2)) / 4 > (size_t)XCh<false>::value * 3 * 512)) {
+        const hipError_t e = rw == 16 ? launch_chain_t<16, 1, 8192, 4, 7, EPI, false>(p, st) : launch_chain_t<32, 1, 8192, 4, 7, EPI, false>(p, st);
+        if (p || e != hipSuccess) return e;
+    }
     // rung (a') of the FFN ladder (profiles/r06_ffn_stream.md; LNB_RW_W2=16 LNB_W2_QUAD=1, measurement only): the down projection's 16 rows per CU on ONE
     // quad_perm chain wave + four helpers -- the only w2 form that would leave a co-resident gate|up producer three SIMDs
     if constexpr (NCH == 1 && !NORM && (EPI == EPI_RESID || EPI == EPI_STORE)) {
-        const char* eq = getenv("LNB_W2_QUAD");              // (read per launch: a test switches it inside one process)
-        const int quad16 = (eq && *eq) ? atoi(eq) : 0;
-        if (rw == 16 && quad16 && (!p || p->K % 128 == 0)) return quad16 == 2 ? launch_quad_t<16, 256, 4, 7, EPI, false>(p, st) : launch_quad_t<16, 128, 4, 14, EPI, false>(p, st);
+        const int quad16 = p ? knob(Knob::W2_QUAD) : 0;
+        if (rw == 16 && (!p || (quad16 && p->K % 128 == 0))) {
+            const hipError_t e = either(quad16 == 2, launch_quad_t<16, 256, 4, 7, EPI, false>, launch_quad_t<16, 128, 4, 14, EPI, false>);
+            if (p || e != hipSuccess) return e;
+        }
     }
     if (rw == 16) return launch_chain_t<16, NCH, 8192, 2, 7, EPI, NORM>(p, st);
     if (rw == 32) return (NORM && NCH == 1) ? launch_chain_t<32, 1, 12288, 6, 5, EPI, NORM>(p, st) : launch_chain_t<32, NCH, 8192, 2, 7, EPI, NORM>(p, st);
@@ -4229,7 +4252,7 @@ static hipError_t launch_gemv_rw(const GemvParams* p, int rw, hipStream_t st) {
     // seven helpers (448 lanes = one (k-chunk, row) pair each), 64-step stages
     // (throughput schedule: six ring stages instead of eight -- 133 instead of 149 VGPRs, so that two of its waves and two of the 128-step
     // wq|wk|wv kernel's fit one SIMD's 512 registers: a gate|up workgroup of one context beside a wq|wk|wv workgroup of another)
-    if constexpr (NCH == 2) if (rw == 56) return (p && p->sched && env_tp_w13()) ? launch_chain_t<56, 2, 14336, 7, 6, EPI, NORM>(p, st) : launch_chain_t<56, 2, 14336, 7, 8, EPI, NORM>(p, st);
+    if constexpr (NCH == 2) if (rw == 56) return either(p && p->sched && knob(Knob::TP_W13), launch_chain_t<56, 2, 14336, 7, 6, EPI, NORM>, launch_chain_t<56, 2, 14336, 7, 8, EPI, NORM>);
     // RW 28 (two chains, LNB_RW_W13=28): the same stream cut into 512 half-height blocks, two per workgroup -- rows [0, F/2) are complete
     // after the first block of every workgroup: the row-band order a w1|w3 -> w2 pipeline needs (measurement, NOTES.md 6.1)
     if constexpr (NCH == 2) if (rw == 28) return launch_chain_t<28, 2, 14336, 7, 8, EPI, NORM>(p, st);
@@ -4239,16 +4262,12 @@ static hipError_t launch_gemv_rw(const GemvParams* p, int rw, hipStream_t st) {
 template <int EPI> static hipError_t launch_rowcast(const GemvParams* p, hipStream_t st) {
     auto kfn = rowcast_kernel<EPI>;
     auto kl = rowcast_lds_kernel<EPI>;
-    if (!p) {
-        hipError_t e = hipFuncSetAttribute((const void*)kl, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return e != hipSuccess ? e : hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
+    if (!p) return raise_lds(kl, kfn);
     if ((p->K & 127) || p->K > 16384) return hipErrorInvalidValue;              // x staging: 8 x 16 B per thread, K*4 bytes of LDS
     // helper-fed chain waves (rowcast_lds_kernel) whenever K is a whole number of its 512-step stages; LNB_ROWCAST_LDS=0: the self-feeding kernel
-    static const int use_lds = [] { const char* s = getenv("LNB_ROWCAST_LDS"); return s && *s ? atoi(s) : 1; }();
     // (throughput schedule: the self-feeding kernel -- four waves and K * 4 bytes of LDS instead of eight waves and 96 KB + K * 2: co-resident with
     // another context's gate|up workgroup, NOTES R5)
-    if (use_lds && !p->sched && p->K % (128 * RL_SC) == 0 && p->K >= 2 * 128 * RL_SC && rl_lds_bytes(p->K) + (size_t)(p->lds_pad > 0 ? p->lds_pad : 0) <= 160 * 1024) {
+    if (knob(Knob::ROWCAST_LDS) && !p->sched && p->K % (128 * RL_SC) == 0 && p->K >= 2 * 128 * RL_SC && rl_lds_bytes(p->K) + (size_t)(p->lds_pad > 0 ? p->lds_pad : 0) <= 160 * 1024) {
         hipLaunchKernelGGL(kl, dim3((unsigned)(p->S * p->n_wg)), dim3(512), rl_lds_bytes(p->K) + (size_t)(p->lds_pad > 0 ? p->lds_pad : 0), st, *p);
         return hipGetLastError();
     }
@@ -4276,45 +4295,39 @@ extern "C" hipError_t lnbk_gemv(const GemvParams* p, int rw, int nch, int epi, i
 }
 
 template <int EPI, int NCH> static hipError_t launch_gemm(const GemmParams* p, hipStream_t st) {
-    auto k4 = gemm_mfma_kernel<EPI, NCH, 4, 128>;
-    auto k2 = gemm_mfma_kernel<EPI, NCH, 4, 64>;
-    auto k1 = gemm_mfma_kernel<EPI, NCH, 1, 128>;
-    const size_t lds4 = gemm_lds_bytes(NCH, 4), lds2 = gemm_lds_bytes(NCH, 4, 64), lds1 = gemm_lds_bytes(NCH, 1);   // 53 / 73 KB (37 / 57, 39 / 44): >= two workgroups per CU
-    if (!p) {
-        hipError_t e = hipFuncSetAttribute((const void*)k4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-        return e != hipSuccess ? e : hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-    }
+    // the three tile forms, each with the LDS it asks for: 53 / 73 KB (37 / 57, 39 / 44): >= two workgroups per CU
+    const struct { void (*k)(GemmParams); size_t lds; } t128{gemm_mfma_kernel<EPI, NCH, 4, 128>, gemm_lds_bytes(NCH, 4)},
+        t64{gemm_mfma_kernel<EPI, NCH, 4, 64>, gemm_lds_bytes(NCH, 4, 64)}, t1{gemm_mfma_kernel<EPI, NCH, 1, 128>, gemm_lds_bytes(NCH, 1)};
+    hipError_t e = hipSuccess;
+    if (!p) { for (const auto& t : {t128, t64, t1}) if (e == hipSuccess) e = raise_lds_to((int)t.lds, t.k); return e; }
     const unsigned mb = (unsigned)((p->S + 127) / 128), nb4 = (unsigned)((p->n_rows + GM_NB - 1) / GM_NB);
-    static const int force = [] { const char* e = getenv("LNB_GEMM_TILE"); return e && *e ? atoi(e) : 0; }();       // 1 / 64 / 128: measurement aid
+    const int force = knob(Knob::GEMM_TILE);                 // 1 / 64 / 128: measurement aid
     // the two-chain w1|w3 kernel already runs 2x the MFMAs per staged byte: with more than four 64 x 128 tiles per CU it keeps them
     // (S = 2048: 3.90 ms against 4.11 ms with 64 x 64 tiles; the one-chain kernels gain 5 % from the smaller tile there;
     // S = 512, 896 tiles: the small tile still wins, 74 against 77 ms per Forward)
     const int tile = force ? force : (nb4 * mb <= 160 ? 1 : (NCH == 2 && nb4 * mb > 1024) ? 128 : nb4 * mb <= GM_MB64_UPTO ? 64 : 128);
     if (tile == 1)             // 64 x 128 tiles would leave most CUs idle: 16-row tiles, the four waves split the batch rows
                                // (tools/gemmbench.hip: 64 / 96 / 128 tiles: 1.4-2x faster; 256 tiles and up: 64-row tiles win)
-        hipLaunchKernelGGL(k1, dim3((unsigned)((p->n_rows + 15) / 16), mb), dim3(256), lds1, st, *p);
+        hipLaunchKernelGGL(t1.k, dim3((unsigned)((p->n_rows + 15) / 16), mb), dim3(256), t1.lds, st, *p);
     else if (tile == 64)       // about one 64 x 128 tile per CU: 64 x 64 tiles, two to three workgroups per CU overlap staging and MFMAs
-        hipLaunchKernelGGL(k2, dim3(nb4, (unsigned)((p->S + 63) / 64)), dim3(256), lds2, st, *p);
+        hipLaunchKernelGGL(t64.k, dim3(nb4, (unsigned)((p->S + 63) / 64)), dim3(256), t64.lds, st, *p);
     else
-        hipLaunchKernelGGL(k4, dim3(nb4, mb), dim3(256), lds4, st, *p);
+        hipLaunchKernelGGL(t128.k, dim3(nb4, mb), dim3(256), t128.lds, st, *p);
     return hipGetLastError();
 }
 
 extern "C" hipError_t lnbk_gemm(const GemmParams* p, int epi, hipStream_t st) {
-    const int nch = p ? p->nch : 0;
     switch (epi) {
         case EPI_STORE: return launch_gemm<EPI_STORE, 1>(p, st);
         case EPI_RESID: return launch_gemm<EPI_RESID, 1>(p, st);
         case EPI_QKV_ROPE: return launch_gemm<EPI_QKV_ROPE, 1>(p, st);
-        case EPI_SILU_MUL: return (p && nch != 2) ? hipErrorInvalidValue : launch_gemm<EPI_SILU_MUL, 2>(p, st);
+        case EPI_SILU_MUL: return (p && p->nch != 2) ? hipErrorInvalidValue : launch_gemm<EPI_SILU_MUL, 2>(p, st);
         default: return hipErrorInvalidValue;
     }
 }
 extern "C" hipError_t lnbk_rmsnorm_rows(const uint16_t* x, const uint16_t* w, uint16_t* out, int S, int K, float eps, hipStream_t st) {
-    static const int wide = getenv("LNB_NORM_ROWS_WIDE") ? atoi(getenv("LNB_NORM_ROWS_WIDE")) : 1;
     const size_t lds_w = bn_scratch() + ((size_t)bn_kpad(K) + 8) * 4;                  // one workgroup of seven waves per row: the exact parallel evaluation of the serial sum
-    if (wide && !(K & 127) && lds_w <= 64 * 1024 && (size_t)bn_kpad(K) <= (size_t)XCh<true>::value * (1 + BN_NH) * 512 && seq_leaf_size(K, rms_nf(BN_NH) * 64) <= 256) {
+    if (knob(Knob::NORM_ROWS_WIDE) && !(K & 127) && lds_w <= 64 * 1024 && (size_t)bn_kpad(K) <= (size_t)XCh<true>::value * (1 + BN_NH) * 512 && seq_leaf_size(K, rms_nf(BN_NH) * 64) <= 256) {
         hipLaunchKernelGGL(batch_rmsnorm_xt_kernel<false>, dim3((unsigned)S), dim3((1 + BN_NH) * 64), lds_w, st, x, w, eps, out, K);
         return hipGetLastError();
     }
@@ -4332,109 +4345,37 @@ extern "C" int lnbk_attn_short_max_T(int hd) {
     return lo;
 }
 static long long* g_gqa_dbg = nullptr;                       // LNB_ATTN_GQA_DBG: phase stamps of one attn_gqa_kernel workgroup
-extern "C" hipError_t lnbk_init(void) {
-    static bool done = false;
-    if (done) return hipSuccess;
-    { hipError_t eg; for (int ep = EPI_STORE; ep <= EPI_SILU_MUL; ep++) if ((eg = lnbk_gemm(nullptr, ep, nullptr)) != hipSuccess) return eg;
-      if ((eg = hipFuncSetAttribute((const void*)rmsnorm_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return eg; }
-    { hipError_t e4; if ((e4 = lnbk_gemv(nullptr, 4, 1, EPI_STORE, 0, nullptr)) != hipSuccess) return e4; if ((e4 = lnbk_gemv(nullptr, 4, 1, EPI_RESID, 0, nullptr)) != hipSuccess) return e4; }
-    { hipError_t e56; if ((e56 = lnbk_gemv(nullptr, 56, 2, EPI_SILU_MUL, 1, nullptr)) != hipSuccess) return e56;
-      if ((e56 = lnbk_gemv(nullptr, 28, 2, EPI_SILU_MUL, 1, nullptr)) != hipSuccess) return e56; }
-    { hipError_t el;
-      if ((el = launch_chain_t<16, 1, 8192, 4, 7, EPI_STORE, false>(nullptr, nullptr)) != hipSuccess) return el;
-      if ((el = launch_chain_t<32, 1, 8192, 4, 7, EPI_STORE, false>(nullptr, nullptr)) != hipSuccess) return el;
-      if ((el = launch_chain_t<16, 1, 8192, 4, 7, EPI_RESID, false>(nullptr, nullptr)) != hipSuccess) return el;
-      if ((el = launch_chain_t<32, 1, 8192, 4, 7, EPI_RESID, false>(nullptr, nullptr)) != hipSuccess) return el; }
-    const int rws[3] = {16, 32, 64};
-    for (int i = 0; i < 3; i++) {
-        hipError_t e;
-        if ((e = lnbk_gemv(nullptr, rws[i], 1, EPI_STORE, 1, nullptr)) != hipSuccess) return e;
-        if ((e = lnbk_gemv(nullptr, rws[i], 1, EPI_STORE, 0, nullptr)) != hipSuccess) return e;
-        if ((e = lnbk_gemv(nullptr, rws[i], 1, EPI_QKV_ROPE, 1, nullptr)) != hipSuccess) return e;
-        if ((e = lnbk_gemv(nullptr, rws[i], 1, EPI_RESID, 0, nullptr)) != hipSuccess) return e;
-        if ((e = lnbk_gemv(nullptr, rws[i], 2, EPI_SILU_MUL, 1, nullptr)) != hipSuccess) return e;
-    }
-    hipError_t e;
-    if ((e = hipFuncSetAttribute((const void*)attn_exact_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_exact_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_gqa_kernel<128, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_exact_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_exact_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_exact_kernel<128, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_exact_kernel<64, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_exact_kernel<32, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_long_pv_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_long_pv_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_long_pv_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_long_pv2_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_long_pv2_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_long_pv2_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_long_pv_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_long_pv_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_long_pv_kernel<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_long_pv2_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_long_pv2_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_long_pv2_kernel<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_one_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_one_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)attn_one_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if (getenv("LNB_ATTN_GQA_DBG") && !g_gqa_dbg) { if (hipMalloc(&g_gqa_dbg, 8 * 16 * 8) != hipSuccess) return hipErrorOutOfMemory; (void)hipMemset(g_gqa_dbg, 0, 8 * 16 * 8); }
-    done = true;
-    return hipSuccess;
-}
-
-static hipError_t launch_attn_long(const AttnParams* p, hipStream_t st) {
-    const size_t lds = alp_lds_bytes(p->seq_len);
-    if (lds > 160 * 1024 || p->hd % ALP_DS || !p->e_buf || !p->z_part) return hipErrorInvalidValue;
-    const dim3 gs(p->H, (p->seq_len + ALS_NT - 1) / ALS_NT), gp(p->H, p->hd / ALP_DS);
-    const bool lazy = [] { const char* e = getenv("LNB_ATTN_LAZY"); return !(e && *e && atoi(e) == 0); }();      // (read per launch: a test switches it inside one process)
-    AttnParams ps = *p;
-    { const char* e = getenv("LNB_ATTN_TOUCH"); ps.touch = (e && *e) ? (atoi(e) != 0) : 1; }      // (A/B switch; default on)
-    switch (p->hd) {
-    // PV: the lazily certified form (attn_long_pv2_kernel, round 6) unless LNB_ATTN_LAZY=0
-#define LNB_PV(HD_) do { if (lazy) hipLaunchKernelGGL(attn_long_pv2_kernel<HD_>, gp, dim3(ALP_NT), lds, st, ps); else hipLaunchKernelGGL(attn_long_pv_kernel<HD_>, gp, dim3(ALP_NT), lds, st, ps); } while (0)
-    case 128: hipLaunchKernelGGL(attn_long_scores_kernel<128>, gs, dim3(ALS_NT), 0, st, ps); LNB_PV(128); break;
-    case 64: hipLaunchKernelGGL(attn_long_scores_kernel<64>, gs, dim3(ALS_NT), 0, st, ps); LNB_PV(64); break;
-    case 32: hipLaunchKernelGGL(attn_long_scores_kernel<32>, gs, dim3(ALS_NT), 0, st, ps); LNB_PV(32); break;
-#undef LNB_PV
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-// the batched pair (p->btab): p->S sequences in grid.z, p->seq_len = the largest member's cache length (e_buf [S][H][seq_len], z_part [S][H][ceil(seq_len/256)])
-static hipError_t launch_attn_long_batch(const AttnParams* p, hipStream_t st) {
-    const size_t lds = alp_lds_bytes(p->seq_len);
-    if (lds > 160 * 1024 || p->hd % ALP_DS || !p->e_buf || !p->z_part || !p->bkv || p->S < 1 || p->S > LNB_BATCH_MAX || (!p->out && !p->out_xt)) return hipErrorInvalidValue;
-    const dim3 gs(p->H, (p->seq_len + ALS_NT - 1) / ALS_NT, p->S), gp(p->H, p->hd / ALP_DS, p->S);
-    const bool lazy = [] { const char* e = getenv("LNB_ATTN_LAZY"); return !(e && *e && atoi(e) == 0); }();
-    AttnParams ps = *p;
-    { const char* e = getenv("LNB_ATTN_TOUCH"); ps.touch = (e && *e) ? (atoi(e) != 0) : 1; }
-    switch (p->hd) {
-#define LNB_PV(HD_) do { if (lazy) hipLaunchKernelGGL((attn_long_pv2_kernel<HD_, true>), gp, dim3(ALP_NT), lds, st, ps); else hipLaunchKernelGGL((attn_long_pv_kernel<HD_, true>), gp, dim3(ALP_NT), lds, st, ps); } while (0)
-    case 128: hipLaunchKernelGGL((attn_long_scores_kernel<128, true>), gs, dim3(ALS_NT), 0, st, ps); LNB_PV(128); break;
-    case 64: hipLaunchKernelGGL((attn_long_scores_kernel<64, true>), gs, dim3(ALS_NT), 0, st, ps); LNB_PV(64); break;
-    case 32: hipLaunchKernelGGL((attn_long_scores_kernel<32, true>), gs, dim3(ALS_NT), 0, st, ps); LNB_PV(32); break;
-#undef LNB_PV
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+// long-context decode attention: scores, then PV -- the lazily certified form (attn_long_pv2_kernel, round 6) unless LNB_ATTN_LAZY=0.
+// BATCH (p->btab): p->S sequences in grid.z, p->seq_len = the largest member's cache length (e_buf [S][H][seq_len], z_part [S][H][ceil(seq_len/256)])
+template <bool BATCH> static hipError_t launch_attn_long(const AttnParams* p, hipStream_t st) {
+    return with_hd(p, [&](auto HD) {
+        const auto scores = attn_long_scores_kernel<HD, BATCH>, lazy = attn_long_pv2_kernel<HD, BATCH>, eager = attn_long_pv_kernel<HD, BATCH>;
+        if (!p) return raise_lds(lazy, eager);
+        const auto pv = knob(Knob::ATTN_LAZY) ? lazy : eager;
+        const size_t lds = alp_lds_bytes(p->seq_len);
+        if (lds > 160 * 1024 || p->hd % ALP_DS || !p->e_buf || !p->z_part) return hipErrorInvalidValue;
+        if (BATCH && (!p->bkv || p->S < 1 || p->S > LNB_BATCH_MAX || (!p->out && !p->out_xt))) return hipErrorInvalidValue;
+        const unsigned z = BATCH ? p->S : 1;
+        AttnParams ps = *p;
+        ps.touch = knob(Knob::ATTN_TOUCH) != 0;
+        hipLaunchKernelGGL(scores, dim3(p->H, (p->seq_len + ALS_NT - 1) / ALS_NT, z), dim3(ALS_NT), 0, st, ps);
+        hipLaunchKernelGGL(pv, dim3(p->H, p->hd / ALP_DS, z), dim3(ALP_NT), lds, st, ps);
+        return hipGetLastError();
+    });
 }
 // the one-launch form (attn_one_kernel): scores, softmax and PV per (head, 16-dim slice) workgroup with a bounded in-launch exchange
 static hipError_t launch_attn_one(const AttnParams* p, hipStream_t st) {
-    const size_t lds = att1_lds_bytes(p->seq_len, p->hd);
-    if (lds > 160 * 1024 || p->hd % ALP_DS || !p->e_buf || !p->z_part || !p->cnt) return hipErrorInvalidValue;
-    const dim3 g(p->H, p->hd / ALP_DS);
-    switch (p->hd) {
-    case 128: hipLaunchKernelGGL(attn_one_kernel<128>, g, dim3(ALP_NT), lds, st, *p); break;
-    case 64: hipLaunchKernelGGL(attn_one_kernel<64>, g, dim3(ALP_NT), lds, st, *p); break;
-    case 32: hipLaunchKernelGGL(attn_one_kernel<32>, g, dim3(ALP_NT), lds, st, *p); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_hd(p, [&](auto HD) {
+        const auto one = attn_one_kernel<HD>;
+        if (!p) return raise_lds(one);
+        const size_t lds = att1_lds_bytes(p->seq_len, p->hd);
+        if (lds > 160 * 1024 || p->hd % ALP_DS || !p->e_buf || !p->z_part || !p->cnt) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(one, dim3(p->H, p->hd / ALP_DS), dim3(ALP_NT), lds, st, *p);
+        return hipGetLastError();
+    });
 }
 extern "C" size_t lnbk_attn_one_lds(int seq_len, int hd) { return att1_lds_bytes(seq_len, hd); }
 extern "C" size_t lnbk_attn_long_lds(int seq_len) { return alp_lds_bytes(seq_len); }
-extern "C" size_t lnbk_attn_short_lds(int seq_len, int hd);
 
 extern "C" void lnbk_attn_gqa_dbg_dump(void) {
     if (!g_gqa_dbg) return;
@@ -4446,76 +4387,80 @@ extern "C" void lnbk_attn_gqa_dbg_dump(void) {
                 h[w * 16 + 1] - h[w * 16], h[w * 16 + 2] - h[w * 16 + 1], h[w * 16 + 3] - h[w * 16 + 2], h[w * 16 + 4] - h[w * 16 + 3], h[w * 16 + 5] - h[w * 16 + 4], h[w * 16 + 6] - h[w * 16 + 5], h[w * 16] - h[0]);
     }
 }
-static bool attn_batch_dense() { const char* e = getenv("LNB_ATTN_BATCH_DENSE"); return !(e && *e && atoi(e) == 0); }   // (read per launch: a test switches it inside one process)
+// prefill (head_dim 128 / 64): 16 (attn_mfma_kernel) or 32 (attn_mfma2_kernel, round 6) query rows per wave on the matrix cores; static LDS only.  The order of the conditions decides the form
+static hipError_t launch_attn_prefill(const AttnParams* p, hipStream_t st) {
+    const int min2 = knob(Knob::ATTN_MFMA2);                 // 0: never the two-tile form (the default: measured slower, see attn_mfma2_kernel); N > 0: from N rows on
+    static_assert(ATM2_MIN_S == 0, "LNB_ATTN_MFMA2's default in lnb_knobs.h is the kernel's");
+    const bool two = min2 > 0 && p->S >= min2 && !p->causal;                             // (the opt-in two-tile form has no causal instantiation: an append never selects it)
+    const bool kept = !two && p->score_idx && p->host_T > 0 && p->sidx_jt * 16 >= p->host_T;   // round 6: scores once, indices kept (the caller sized the scratch for this call's context)
+    return with_hd<64>(p, [&](auto HD) {
+        // causal (lnb_forward_append): the true causal mask with an offset -- template instantiations of their own, the modulo forms' code is untouched
+        void (*const k)(AttnParams) = two ? attn_mfma2_kernel<HD> : kept ? (p->causal ? attn_mfma3_kernel<HD, true> : attn_mfma3_kernel<HD>)
+                                                                         : (p->causal ? attn_mfma_kernel<HD, true> : attn_mfma_kernel<HD>);
+        hipLaunchKernelGGL(k, dim3(p->H, two ? (p->S + 127) / 128 : (p->S + 63) / 64), dim3(256), 0, st, *p);
+        return hipGetLastError();
+    });
+}
+// one workgroup per (head, row) and its batched forms
+static hipError_t launch_attn_short(const AttnParams* p, hipStream_t st) {
+    const auto gqa = attn_gqa_kernel<128, 4>;
+    const auto dense = attn_exact_kernel<128, true>;
+    const size_t lds = p ? attn_lds_bytes(p->lds_T, p->hd) : 0;
+    if (!p) { const hipError_t e = raise_lds(gqa, dense); if (e != hipSuccess) return e; }
+    else {
+        // (host_T: e[] / pw[] are sized for lds_T positions: never launch past them -- lnb_api.cpp check_call refuses first)
+        if (lds > 160 * 1024 || p->lds_T <= 0 || p->lds_T > p->seq_len || p->host_T > p->lds_T) return hipErrorInvalidValue;
+        if (p->btab && p->hd == 128 && p->H == 4 * p->KVH) {        // batched decode: one workgroup per (KV head, sequence) when that fills the chip
+            const int mode = knob(Knob::ATTN_GQA);                  // 0: never, 1: always, default: from LNB_ATTN_GQA_MIN_WG workgroups on
+            const size_t gl = gqa_lds_bytes(p->lds_T, 128, 4);
+            if (mode != 0 && p->exp_tab && gl <= 160 * 1024 && (mode == 1 || (long)p->KVH * p->S >= 256)) {
+                AttnParams q = *p;
+                if (knob(Knob::ATTN_GQA_FORCE_ZSEQ)) q.force_zseq = 1;      // (tests: every head walks the serial denominator)
+                if (knob(Knob::ATTN_GQA_DBG)) q.dbg = g_gqa_dbg;            // phase stamps of one workgroup (allocated by lnbk_init: no allocation inside a stream capture)
+                hipLaunchKernelGGL(gqa, dim3(p->KVH, p->S), dim3(512), gl, st, q);
+                return hipGetLastError();
+            }
+        }
+        if (p->btab && p->hd == 128 && (long)p->H * p->S > 256 && knob(Knob::ATTN_BATCH_DENSE)) {       // more workgroups than CUs (never an append: that has no btab)
+            AttnParams q = *p;
+            q.head_major = knob(Knob::ATTN_BATCH_HEADMAJOR) != 0;   // (A/B of the dispatch order)
+            hipLaunchKernelGGL(dense, dim3(p->H, p->S), dim3(ATT_NT), lds, st, q);
+            return hipGetLastError();
+        }
+    }
+    return with_hd(p, [&](auto HD) {
+        const auto plain = attn_exact_kernel<HD>, append = attn_exact_kernel<HD, false, true>;
+        if (!p) return raise_lds(plain, append);
+        // lnb_forward_append, 2..15 rows (any row count at head_dim 32): workgroup (h, i) runs the one-token step at pos + i
+        const auto k = p->causal && !p->btab && p->S > 1 ? append : plain;
+        hipLaunchKernelGGL(k, dim3(p->H, p->S), dim3(ATT_NT), lds, st, *p);
+        return hipGetLastError();
+    });
+}
 extern "C" hipError_t lnbk_attn(const AttnParams* p, hipStream_t st) {
-    if (p->btab && p->longctx) return launch_attn_long_batch(p, st);      // batched decode / verify pass in the long-context form (the caller chose it: lnb_api.cpp batch_want_long / batch_select_form)
+    if (p->btab && p->longctx) return launch_attn_long<true>(p, st);      // batched decode / verify pass in the long-context form (the caller chose it: lnb_api.cpp batch_want_long / batch_select_form)
     if (p->longctx >= 2 && p->S == 1) return launch_attn_one(p, st);
-    if (p->longctx && p->S == 1) return launch_attn_long(p, st);
-    if (p->mfma && p->S >= 16 && (p->hd == 128 || p->hd == 64)) {       // prefill: 16 (attn_mfma_kernel) or 32 (attn_mfma2_kernel, round 6) query rows per wave on the matrix cores
-        const char* e2 = getenv("LNB_ATTN_MFMA2");                        // 0: never the two-tile form; N > 0: from N rows on (default ATM2_MIN_S)
-        const int min2 = (e2 && *e2) ? atoi(e2) : ATM2_MIN_S;              // (default 0 = off: measured slower, see attn_mfma2_kernel)
-        if (min2 > 0 && p->S >= min2 && !p->causal) {                      // (the opt-in two-tile form has no causal instantiation: an append never selects it)
-            if (p->hd == 128) hipLaunchKernelGGL(attn_mfma2_kernel<128>, dim3(p->H, (p->S + 127) / 128), dim3(256), 0, st, *p);
-            else hipLaunchKernelGGL(attn_mfma2_kernel<64>, dim3(p->H, (p->S + 127) / 128), dim3(256), 0, st, *p);
-            return hipGetLastError();
-        }
-        if (p->score_idx && p->host_T > 0 && p->sidx_jt * 16 >= p->host_T) {              // round 6: scores once, indices kept (the caller sized the scratch for this call's context)
-            if (p->causal) {                                                              // lnb_forward_append: the true causal mask with an offset (a template instantiation of
-                if (p->hd == 128) hipLaunchKernelGGL((attn_mfma3_kernel<128, true>), dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);      // its own: the modulo form's code is untouched)
-                else hipLaunchKernelGGL((attn_mfma3_kernel<64, true>), dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
-            }
-            else if (p->hd == 128) hipLaunchKernelGGL(attn_mfma3_kernel<128>, dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
-            else hipLaunchKernelGGL(attn_mfma3_kernel<64>, dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
-            return hipGetLastError();
-        }
-        if (p->causal) {
-            if (p->hd == 128) hipLaunchKernelGGL((attn_mfma_kernel<128, true>), dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
-            else hipLaunchKernelGGL((attn_mfma_kernel<64, true>), dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
-        }
-        else if (p->hd == 128) hipLaunchKernelGGL(attn_mfma_kernel<128>, dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
-        else hipLaunchKernelGGL(attn_mfma_kernel<64>, dim3(p->H, (p->S + 63) / 64), dim3(256), 0, st, *p);
-        return hipGetLastError();
+    if (p->longctx && p->S == 1) return launch_attn_long<false>(p, st);
+    if (p->mfma && p->S >= 16 && (p->hd == 128 || p->hd == 64)) return launch_attn_prefill(p, st);
+    return launch_attn_short(p, st);
+}
+extern "C" hipError_t lnbk_init(void) {
+    static bool done = false;
+    if (done) return hipSuccess;
+    hipError_t e = raise_lds(rmsnorm_rows_kernel);           // (lnbk_rmsnorm_rows' other form stays within the 64 KiB every kernel gets)
+    for (int ep = EPI_STORE; ep <= EPI_SILU_MUL && e == hipSuccess; ep++) e = lnbk_gemm(nullptr, ep, nullptr);
+    // every (rows per block, chains, epilogue, norm) lnbk_gemv has kernels for
+    auto gemv = [&](int rw, int nch, int epi, int norm) { if (e == hipSuccess) e = lnbk_gemv(nullptr, rw, nch, epi, norm, nullptr); };
+    gemv(4, 1, EPI_STORE, 0); gemv(4, 1, EPI_RESID, 0); gemv(56, 2, EPI_SILU_MUL, 1); gemv(28, 2, EPI_SILU_MUL, 1);
+    for (int rw : {16, 24, 32, 64}) {
+        gemv(rw, 1, EPI_STORE, 1); gemv(rw, 1, EPI_STORE, 0); gemv(rw, 1, EPI_QKV_ROPE, 1); gemv(rw, 1, EPI_RESID, 0);
+        if (rw != 24) gemv(rw, 2, EPI_SILU_MUL, 1);
     }
-    size_t lds = attn_lds_bytes(p->lds_T, p->hd);
-    if (lds > 160 * 1024 || p->lds_T <= 0 || p->lds_T > p->seq_len) return hipErrorInvalidValue;
-    if (p->host_T > p->lds_T) return hipErrorInvalidValue;      // e[] / pw[] are sized for lds_T positions: never launch past them (lnb_api.cpp check_call refuses first)
-    if (p->btab && p->hd == 128 && p->H == 4 * p->KVH) {        // batched decode: one workgroup per (KV head, sequence) when that fills the chip
-        const char* e = getenv("LNB_ATTN_GQA");                 // 0: never, 1: always, default: from LNB_ATTN_GQA_MIN_WG workgroups on
-        const int mode = (e && *e) ? atoi(e) : -1;
-        const size_t gl = gqa_lds_bytes(p->lds_T, 128, 4);
-        if (mode != 0 && p->exp_tab && gl <= 160 * 1024 && (mode == 1 || (long)p->KVH * p->S >= 256)) {
-            AttnParams q = *p;
-            { const char* f = getenv("LNB_ATTN_GQA_FORCE_ZSEQ"); if (f && *f && atoi(f) != 0) q.force_zseq = 1; }      // (tests: every head walks the serial denominator)
-            if (getenv("LNB_ATTN_GQA_DBG")) {                   // phase stamps of one workgroup (lnbk_attn_gqa_dbg_dump prints them)
-                q.dbg = g_gqa_dbg;                              // (allocated by lnbk_init: no allocation inside a stream capture)
-            }
-            hipLaunchKernelGGL((attn_gqa_kernel<128, 4>), dim3(p->KVH, p->S), dim3(512), gl, st, q);
-            return hipGetLastError();
-        }
-    }
-    if (p->causal && !p->btab && p->S > 1) {                    // lnb_forward_append, 2..15 rows (any row count at head_dim 32): workgroup (h, i) runs the one-token step at pos + i
-        switch (p->hd) {
-        case 128: hipLaunchKernelGGL((attn_exact_kernel<128, false, true>), dim3(p->H, p->S), dim3(ATT_NT), lds, st, *p); break;
-        case 64: hipLaunchKernelGGL((attn_exact_kernel<64, false, true>), dim3(p->H, p->S), dim3(ATT_NT), lds, st, *p); break;
-        case 32: hipLaunchKernelGGL((attn_exact_kernel<32, false, true>), dim3(p->H, p->S), dim3(ATT_NT), lds, st, *p); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (p->hd) {
-    case 128:
-        if (p->btab && (long)p->H * p->S > 256 && attn_batch_dense()) { // more workgroups than CUs
-            AttnParams q = *p;
-            { const char* e = getenv("LNB_ATTN_BATCH_HEADMAJOR"); q.head_major = (e && *e && atoi(e) != 0) ? 1 : 0; }     // (A/B of the dispatch order)
-            hipLaunchKernelGGL((attn_exact_kernel<128, true>), dim3(p->H, p->S), dim3(ATT_NT), lds, st, q);
-        }
-        else hipLaunchKernelGGL(attn_exact_kernel<128>, dim3(p->H, p->S), dim3(ATT_NT), lds, st, *p);
-        break;
-    case 64: hipLaunchKernelGGL(attn_exact_kernel<64>, dim3(p->H, p->S), dim3(ATT_NT), lds, st, *p); break;
-    case 32: hipLaunchKernelGGL(attn_exact_kernel<32>, dim3(p->H, p->S), dim3(ATT_NT), lds, st, *p); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    for (auto prepare : {launch_attn_long<true>, launch_attn_long<false>, launch_attn_one, launch_attn_short}) if (e == hipSuccess) e = prepare(nullptr, nullptr);
+    if (e != hipSuccess) return e;
+    if (knob(Knob::ATTN_GQA_DBG) && !g_gqa_dbg) { if (hipMalloc(&g_gqa_dbg, 8 * 16 * 8) != hipSuccess) return hipErrorOutOfMemory; (void)hipMemset(g_gqa_dbg, 0, 8 * 16 * 8); }
+    done = true;
+    return hipSuccess;
 }
 
 extern "C" hipError_t lnbk_embed(const uint16_t* emb, const int32_t* tokens, uint16_t* x, int S, int dim, int vocab, int* err, hipStream_t st) {
@@ -4562,6 +4507,10 @@ extern "C" hipError_t lnbk_m16_from_tiled(const uint16_t* src, uint16_t* dst, in
     hipLaunchKernelGGL(m16_from_tiled_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, dst, rows, K, RW, NCH);
     return hipGetLastError();
 }
+// the epilogues mfma_pair_kernel exists for (nullptr: none)
+static auto pair_kernel(int epi) -> void (*)(StreamParams) {
+    return epi == EPI_STORE ? mfma_pair_kernel<EPI_STORE> : epi == EPI_RESID ? mfma_pair_kernel<EPI_RESID> : epi == EPI_QKV_ROPE ? mfma_pair_kernel<EPI_QKV_ROPE> : nullptr;
+}
 // acc2: two tile-chains per wave (fat matrices and the gate|up pairs); else one (thin matrices: every tile on its own SIMD)
 extern "C" hipError_t lnbk_stream(const StreamParams* p, int epi, int acc2, int num_cus, hipStream_t st) {
     const int G = p->n_groups > 1 ? p->n_groups : 1;
@@ -4570,26 +4519,19 @@ extern "C" hipError_t lnbk_stream(const StreamParams* p, int epi, int acc2, int 
     const int ACC = acc2 ? 2 : 1;
     q.n_jobs = (p->n_chains + ACC - 1) / ACC;
     unsigned grid = (unsigned)((q.n_jobs + 3) / 4); if (grid > (unsigned)num_cus) grid = (unsigned)num_cus;
-    {   // thin matrices: chain wave + helper wave per tile (mfma_pair_kernel); LNB_STREAM_PAIR=0: the one-wave form
-        const char* e = getenv("LNB_STREAM_PAIR");
-        if (!acc2 && (G > 1 || !(e && *e && atoi(e) == 0)) && (epi == EPI_STORE || epi == EPI_RESID || epi == EPI_QKV_ROPE)) {
-            const size_t lds = (size_t)2 * 2 * MP_BUF;
-            unsigned gp = (unsigned)((q.n_jobs * G + 1) / 2); if (gp > (unsigned)num_cus) gp = (unsigned)num_cus;
-            if (epi == EPI_STORE) hipLaunchKernelGGL((mfma_pair_kernel<EPI_STORE>), dim3(gp), dim3(256), lds, st, q);
-            else if (epi == EPI_RESID) hipLaunchKernelGGL((mfma_pair_kernel<EPI_RESID>), dim3(gp), dim3(256), lds, st, q);
-            else hipLaunchKernelGGL((mfma_pair_kernel<EPI_QKV_ROPE>), dim3(gp), dim3(256), lds, st, q);
-            return hipGetLastError();
-        }
+    // thin matrices: chain wave + helper wave per tile (mfma_pair_kernel); LNB_STREAM_PAIR=0: the one-wave form
+    if (const auto pair = pair_kernel(epi); pair && !acc2 && (G > 1 || knob(Knob::STREAM_PAIR))) {
+        const size_t lds = (size_t)2 * 2 * MP_BUF;
+        unsigned gp = (unsigned)((q.n_jobs * G + 1) / 2); if (gp > (unsigned)num_cus) gp = (unsigned)num_cus;
+        hipLaunchKernelGGL(pair, dim3(gp), dim3(256), lds, st, q);
+        return hipGetLastError();
     }
-#define LNB_STREAM(A, E) hipLaunchKernelGGL((mfma_stream_kernel<A, E>), dim3(grid), dim3(256), 0, st, q)
-    switch (epi) {
-    case EPI_STORE: if (acc2) LNB_STREAM(2, EPI_STORE); else LNB_STREAM(1, EPI_STORE); break;
-    case EPI_RESID: if (acc2) LNB_STREAM(2, EPI_RESID); else LNB_STREAM(1, EPI_RESID); break;
-    case EPI_QKV_ROPE: if (acc2) LNB_STREAM(2, EPI_QKV_ROPE); else LNB_STREAM(1, EPI_QKV_ROPE); break;
-    case EPI_SILU_MUL: if (!acc2 || p->nch != 2) return hipErrorInvalidValue; LNB_STREAM(2, EPI_SILU_MUL); break;
-    default: return hipErrorInvalidValue;
-    }
+#define LNB_STREAM(E) (acc2 ? mfma_stream_kernel<2, E> : mfma_stream_kernel<1, E>)
+    void (*const k)(StreamParams) = epi == EPI_STORE ? LNB_STREAM(EPI_STORE) : epi == EPI_RESID ? LNB_STREAM(EPI_RESID) : epi == EPI_QKV_ROPE ? LNB_STREAM(EPI_QKV_ROPE)
+                                    : (epi == EPI_SILU_MUL && acc2 && p->nch == 2) ? mfma_stream_kernel<2, EPI_SILU_MUL> : nullptr;
 #undef LNB_STREAM
+    if (!k) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, q);
     return hipGetLastError();
 }
 extern "C" hipError_t lnbk_gemm_stream(const GemmParams* p, int epi, int num_cus, hipStream_t st);
@@ -4605,11 +4547,11 @@ extern "C" hipError_t lnbk_spin(int us, hipStream_t st) {
 extern "C" hipError_t lnbk_batch_prepare(void) {             // raise the dynamic-LDS limits once, outside any stream capture
     static bool done = false;
     if (done) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute((const void*)batch_rmsnorm_xt_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)mfma_pair_kernel<EPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)mfma_pair_kernel<EPI_RESID>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)mfma_pair_kernel<EPI_QKV_ROPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    for (int ep = EPI_STORE; ep <= EPI_SILU_MUL && e == hipSuccess; ep++) e = lnbk_gemm_stream(nullptr, ep, 0, nullptr);
+    hipError_t e = raise_lds(batch_rmsnorm_xt_kernel<true>);
+    for (int ep = EPI_STORE; ep <= EPI_SILU_MUL && e == hipSuccess; ep++) {
+        if (pair_kernel(ep)) e = raise_lds(pair_kernel(ep));
+        if (e == hipSuccess) e = lnbk_gemm_stream(nullptr, ep, 0, nullptr);
+    }
     done = e == hipSuccess;
     return e;
 }
@@ -4630,12 +4572,9 @@ extern "C" hipError_t lnbk_batch_argmax(const uint16_t* logits, int V, const Bat
 // one launch for `rows` rows of p->logits: grid G slices x rows, 256 threads (k picks the register top-k: 1 / 2 / 4 / 8 / 16, 0 = none)
 extern "C" hipError_t lnbk_token_probs(const TokProbParams* p, hipStream_t st) {
     const dim3 grid((unsigned)p->G, (unsigned)p->rows), block(256);
-    if (p->k <= 0) hipLaunchKernelGGL(token_probs_kernel<0>, grid, block, 0, st, *p);
-    else if (p->k <= 1) hipLaunchKernelGGL(token_probs_kernel<1>, grid, block, 0, st, *p);
-    else if (p->k <= 2) hipLaunchKernelGGL(token_probs_kernel<2>, grid, block, 0, st, *p);
-    else if (p->k <= 4) hipLaunchKernelGGL(token_probs_kernel<4>, grid, block, 0, st, *p);
-    else if (p->k <= 8) hipLaunchKernelGGL(token_probs_kernel<8>, grid, block, 0, st, *p);
-    else hipLaunchKernelGGL(token_probs_kernel<16>, grid, block, 0, st, *p);
+    const auto k = p->k <= 0 ? token_probs_kernel<0> : p->k <= 1 ? token_probs_kernel<1> : p->k <= 2 ? token_probs_kernel<2> : p->k <= 4 ? token_probs_kernel<4>
+                 : p->k <= 8 ? token_probs_kernel<8> : token_probs_kernel<16>;
+    hipLaunchKernelGGL(k, grid, block, 0, st, *p);
     return hipGetLastError();
 }
 extern "C" hipError_t lnbk_batch_set_state(const BatchTab* tab, const int32_t* tokens, const int32_t* pos, int32_t* ring, int honour_stop, hipStream_t st) {
@@ -4653,20 +4592,23 @@ extern "C" hipError_t lnbk_batch_advance(const BatchTab* tab, hipStream_t st) {
 
 // prefill product on the streaming matrix-core feed (gemm_stream_kernel): one weight tile per wave and NTW batch tiles of 16 rows.
 // (batch tiles per wave and dispatch order: lnb_gemm_stream_ntw / lnb_gemm_stream_rows_fastest, lnb_device.h -- host logic, tests/test_layouts.py)
+// gemm_stream_kernel<EPI, NCH> for ntw batch tiles per wave (1 / 2, else 4), A-operand source src and tt (two weight tiles per wave); nullptr: no such instantiation
+// (source 1 and TT: one-chain EPI_STORE / EPI_RESID only).  Prepare walks this function: nothing it returns is launched unraised (up to 66,560 B of LDS)
+template <int EPI, int NCH, int SRC> static auto gs_ntw(int ntw) -> void (*)(GemmParams) {
+    return ntw == 1 ? gemm_stream_kernel<EPI, NCH, 1, SRC> : ntw == 2 ? gemm_stream_kernel<EPI, NCH, 2, SRC> : gemm_stream_kernel<EPI, NCH, 4, SRC>;
+}
+template <int EPI, int NCH> static auto gs_kernel(int ntw, int src, bool tt) -> void (*)(GemmParams) {
+    if constexpr (NCH == 1 && (EPI == EPI_STORE || EPI == EPI_RESID)) {
+        if (tt) return ntw != 4 ? nullptr : src == 0 ? gemm_stream_kernel<EPI, NCH, 4, 0, 1> : src == 1 ? gemm_stream_kernel<EPI, NCH, 4, 1, 1> : nullptr;
+        if (src == 1) return gs_ntw<EPI, NCH, 1>(ntw);
+    }
+    return tt ? nullptr : src == 0 ? gs_ntw<EPI, NCH, 0>(ntw) : src == 2 ? gs_ntw<EPI, NCH, 2>(ntw) : nullptr;
+}
 template <int EPI, int NCH> static hipError_t launch_gemm_stream(const GemmParams* p, int num_cus, hipStream_t st) {
     if (!p) {
         hipError_t e = hipSuccess;
-        // every instantiation the launch below can pick (the resident-layout sources SRC 1 / 2 request up to 66,560 B at four batch
-        // tiles per wave -- above the 64 KiB a kernel gets without this attribute)
-#define LNB_GS_PREP(N, SRC_) if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_stream_kernel<EPI, NCH, N, SRC_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-        LNB_GS_PREP(1, 0); LNB_GS_PREP(2, 0); LNB_GS_PREP(4, 0);
-        LNB_GS_PREP(1, 2); LNB_GS_PREP(2, 2); LNB_GS_PREP(4, 2);
-        if constexpr (NCH == 1 && (EPI == EPI_STORE || EPI == EPI_RESID)) { LNB_GS_PREP(1, 1); LNB_GS_PREP(2, 1); LNB_GS_PREP(4, 1); }
-        if constexpr (NCH == 1 && (EPI == EPI_STORE || EPI == EPI_RESID)) {        // two weight tiles per wave (TT)
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_stream_kernel<EPI, NCH, 4, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_stream_kernel<EPI, NCH, 4, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        }
-#undef LNB_GS_PREP
+        for (int ntw : {1, 2, 4}) for (int src = 0; src < 3; src++) for (int tt = 0; tt < 2; tt++)
+            if (const auto k = gs_kernel<EPI, NCH>(ntw, src, tt != 0); k && e == hipSuccess) e = raise_lds(k);
         return e;
     }
     // A operand: the M16 copy when the model carries one, else the RESIDENT layout (round 5: no second copy needed for a prompt) -- the row-broadcast
@@ -4676,9 +4618,9 @@ template <int EPI, int NCH> static hipError_t launch_gemm_stream(const GemmParam
     const int n_tiles = (p->n_rows + 15) / 16;
     const int ct = (p->S + 15) / 16;                         // batch tiles of 16 rows
     int ntw = lnb_gemm_stream_ntw(n_tiles, ct, NCH, num_cus);
-    const int force = getenv("LNB_GS_NTW") ? atoi(getenv("LNB_GS_NTW")) : 0;    // (tools / experiments / tests; read per launch)
+    const int force = knob(Knob::GS_NTW);                    // (tools / experiments / tests)
     if (force == 1 || force == 2 || force == 4) ntw = force;
-    static const int force_ct = getenv("LNB_GS_NTW_CHAIN") ? atoi(getenv("LNB_GS_NTW_CHAIN")) : 0;    // (experiments: the chain layouts only)
+    const int force_ct = knob(Knob::GS_NTW_CHAIN);           // (experiments: the chain layouts only)
     if (src == 2 && (force_ct == 1 || force_ct == 2 || force_ct == 4)) ntw = force_ct;
     GemmParams q = *p;
     // round 6: few batch rows on the chain layouts -- the one-k matrix instruction with FOUR WEIGHT blocks and the B operand broadcast by BLGP (gemm_blgp_kernel):
@@ -4686,24 +4628,19 @@ template <int EPI, int NCH> static hipError_t launch_gemm_stream(const GemmParam
     // of a 128-token prompt 125-130 us against 91, gate|up 346 against 301; whole Forward 16 / 128 rows 13.2 / 20.7 ms against 9.2 / 19.4) -- a wave carries FOUR weight
     // tiles as ONE dependent chain of 4 K one-k instructions with an unpack op in front of each (67 cycles per instruction instead of 32), and a quarter as many waves
     // to spread over the SIMDs (96 for wq|wk|wv at 16 rows).  LNB_GEMM_BLGP=1: where gemm_stream_kernel would run one or two batch tiles per wave; =2: every chain-layout product
-    {
-        const char* eb = getenv("LNB_GEMM_BLGP");            // (read per launch: a test switches it inside one process)
-        const int blgp = (eb && *eb) ? atoi(eb) : 0;
-        if (src == 2 && blgp && (ntw <= 2 || blgp == 2) && p->rw % 8 == 0) {
-            const int tpg = 4 / NCH, n_tg = (n_tiles + tpg - 1) / tpg;
-            const dim3 g((unsigned)((n_tg + 3) / 4), (unsigned)ct);
-            const size_t l = (size_t)2 * 16 * GS_PITCH * 4;
-            hipLaunchKernelGGL((gemm_blgp_kernel<EPI, NCH>), g, dim3(256), l, st, q);
-            return hipGetLastError();
-        }
+    if (const int blgp = knob(Knob::GEMM_BLGP); src == 2 && blgp && (ntw <= 2 || blgp == 2) && p->rw % 8 == 0) {
+        const int tpg = 4 / NCH, n_tg = (n_tiles + tpg - 1) / tpg;
+        const dim3 g((unsigned)((n_tg + 3) / 4), (unsigned)ct);
+        const size_t l = (size_t)2 * 16 * GS_PITCH * 4;             // (16 KiB + padding: within what every kernel gets)
+        hipLaunchKernelGGL((gemm_blgp_kernel<EPI, NCH>), g, dim3(256), l, st, q);
+        return hipGetLastError();
     }
     const int rows_wg = 16 * ntw;
     // round 6: wo / w2 with many rows -- two neighbouring weight tiles per wave (gemm_stream_kernel's TT form: the gate|up product's shape), as long as the tile PAIRS still
     // give every CU its two workgroups.  LNB_GS_TT=0: never, 1: whenever the form exists
     bool tt = false;
     if constexpr (NCH == 1 && (EPI == EPI_STORE || EPI == EPI_RESID)) {
-        const char* et = getenv("LNB_GS_TT");                // (read per launch: a test switches it inside one process)
-        const int ttm = (et && *et) ? atoi(et) : -1;
+        const int ttm = knob(Knob::GS_TT);
         const long wgs = (long)(((n_tiles + 1) / 2 + 3) / 4) * ((p->S + rows_wg - 1) / rows_wg);
         tt = ntw == 4 && (src == 0 || src == 1) && ttm != 0 && (ttm == 1 || wgs >= 2L * num_cus);
     }
@@ -4714,33 +4651,20 @@ template <int EPI, int NCH> static hipError_t launch_gemm_stream(const GemmParam
     // once; with many row groups the same tile group comes back once per row group (4096 rows: 15.6 GB of fabric reads per gate|up launch
     // for 235 MB of weights, rocprofv3 FETCH_SIZE).  Row groups fastest: the workgroups in flight cover ~8 tile groups x all row groups, a
     // weight tile is fetched once per XCD and shared through its L2 (4.8 GB; 1-4 % faster at 4096 rows, 2-3 % slower at 512).
-    static const int order = getenv("LNB_GS_ORDER") ? atoi(getenv("LNB_GS_ORDER")) : -1;
+    const int order = knob(Knob::GS_ORDER);
     q.rows_fastest = order >= 0 ? order : lnb_gemm_stream_rows_fastest((int)grid.y);
     const size_t lds = (size_t)2 * rows_wg * GS_PITCH * 4;
-#define LNB_GS_LAUNCH(SRC_) switch (ntw) { \
-    case 1: hipLaunchKernelGGL((gemm_stream_kernel<EPI, NCH, 1, SRC_>), grid, dim3(256), lds, st, q); break; \
-    case 2: hipLaunchKernelGGL((gemm_stream_kernel<EPI, NCH, 2, SRC_>), grid, dim3(256), lds, st, q); break; \
-    default: hipLaunchKernelGGL((gemm_stream_kernel<EPI, NCH, 4, SRC_>), grid, dim3(256), lds, st, q); break; }
-    if constexpr (NCH == 1 && (EPI == EPI_STORE || EPI == EPI_RESID)) {
-        if (tt) {
-            if (src == 0) hipLaunchKernelGGL((gemm_stream_kernel<EPI, NCH, 4, 0, 1>), grid, dim3(256), lds, st, q);
-            else hipLaunchKernelGGL((gemm_stream_kernel<EPI, NCH, 4, 1, 1>), grid, dim3(256), lds, st, q);
-            return hipGetLastError();
-        }
-    }
-    if (src == 0) { LNB_GS_LAUNCH(0) }
-    else if (src == 2) { LNB_GS_LAUNCH(2) }
-    else if constexpr (NCH == 1 && (EPI == EPI_STORE || EPI == EPI_RESID)) { LNB_GS_LAUNCH(1) }
-#undef LNB_GS_LAUNCH
+    const auto k = gs_kernel<EPI, NCH>(ntw, src, tt);
+    if (!k) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, grid, dim3(256), lds, st, q);
     return hipGetLastError();
 }
 extern "C" hipError_t lnbk_gemm_stream(const GemmParams* p, int epi, int num_cus, hipStream_t st) {
-    const int nch = p ? p->nch : 0;
     switch (epi) {
         case EPI_STORE: return launch_gemm_stream<EPI_STORE, 1>(p, num_cus, st);
         case EPI_RESID: return launch_gemm_stream<EPI_RESID, 1>(p, num_cus, st);
         case EPI_QKV_ROPE: return launch_gemm_stream<EPI_QKV_ROPE, 1>(p, num_cus, st);
-        case EPI_SILU_MUL: return (p && nch != 2) ? hipErrorInvalidValue : launch_gemm_stream<EPI_SILU_MUL, 2>(p, num_cus, st);
+        case EPI_SILU_MUL: return (p && p->nch != 2) ? hipErrorInvalidValue : launch_gemm_stream<EPI_SILU_MUL, 2>(p, num_cus, st);
         default: return hipErrorInvalidValue;
     }
 }

@@ -21,9 +21,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "llama-nuts-and-bolts_amd", "csrc", "lnb_kernels.hip")
 
 
-def compile_to_asm(workdir):
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
-           "-I" + os.path.dirname(SRC), "-c", SRC, "-save-temps=obj", "-o", os.path.join(workdir, "k.o")]
+def compile_to_asm(workdir, src=SRC):
+    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
+           "-I" + os.path.dirname(src), "-c", src, "-save-temps=obj", "-o", os.path.join(workdir, "k.o")]
     subprocess.check_call(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     for f in os.listdir(workdir):
         if f.endswith("gfx950.s"):
@@ -146,22 +146,26 @@ def audit_function(lines, execz_both=False):
     return viol
 
 
-def main(asm_path=None):
-    with tempfile.TemporaryDirectory() as wd:
-        asm = asm_path if asm_path else compile_to_asm(wd)
-        txt = open(asm).read().split("\n")
+def split_functions(txt, symbol=r"_Z\S+"):
+    """{symbol: [(line number, line)]} of a listing's functions whose symbol matches"""
     funcs, cur = {}, None
     for i, ln in enumerate(txt):
-        m = re.match(r"^(_Z\d\d(?:gemv_chain|gemv_quad|attn_exact|attn_gqa|attn_long_scores|attn_mfma3|rowcast|rowcast_lds|mfma_stream|mfma_pair|gemm_stream)_kernel\S*):", ln)
+        m = re.match(r"^(%s):" % symbol, ln)
         if m:
             cur = []; funcs[m.group(1)] = cur
             continue
         if cur is not None:
             cur.append((i + 1, ln))
-            if "s_endpgm" in ln and ln.strip().startswith("s_endpgm") and False:
-                pass
             if ln.startswith("\t.section") or ln.startswith(".Lfunc_end"):
                 cur = None
+    return funcs
+
+
+def main(asm_path=None):
+    with tempfile.TemporaryDirectory() as wd:
+        asm = asm_path if asm_path else compile_to_asm(wd)
+        txt = open(asm).read().split("\n")
+    funcs = split_functions(txt, r"_Z\d\d(?:gemv_chain|gemv_quad|attn_exact|attn_gqa|attn_long_scores|attn_mfma3|rowcast|rowcast_lds|mfma_stream|mfma_pair|gemm_stream)_kernel\S*")
     total = 0
     for name, lines in funcs.items():
         # gemv_chain_kernel: the ring lives in helper waves that always run with a full EXEC mask, so the structurizer's
