@@ -115,12 +115,28 @@ int64_t lnb_model_weight_bytes(lnb_model* m);
 
 /* ---- context: replaces model.NewInferenceContext (src/model/inferencecontext.go:17-46) ---------------
  * device-resident, zero-filled CacheK/CacheV [seq_len, n_kv_heads, head_dim] bf16 per owned layer.
- * Context length: up to about 23000 positions (the long-context decode attention keeps 4 bytes per position in the LDS); head_dim 32, 64
+ * Context length: up to about 23000 positions (23552: the long-context decode attention keeps 4 bytes per position in the LDS here); head_dim 32, 64
  * or 128.  One-token calls, calls of 16 or more rows, batched decode (lnb_batch_*) and speculative decode reach that far: beyond what the
  * one-workgroup-per-head attention stages in the LDS (12 bytes per position: ~7800 positions at head_dim 128, ~10800 at 64) they run the
  * long-context kernels.  Calls of 2..15 rows use a kernel that stages 12 bytes per position and fail beyond ~7800 positions (head_dim 128; ~10800 at 64)
- * (lnb_forward_append falls back to one-token steps there). */
+ * (lnb_forward_append falls back to one-token steps there).  A longer seq_len is refused ("... too long ..."): lnb_ctx_create_long goes further. */
 int lnb_ctx_create(lnb_model* m, int seq_len, lnb_ctx** out);
+/* A context of up to LNB_MAX_SEQ_LEN (131072) positions whose per-call activation buffers hold max_rows rows instead of seq_len.
+ * Capacity: seq_len 1..LNB_MAX_SEQ_LEN (<= 0: the model's max_seq_len); above, the call fails ("... too long ..."); the model's RoPE table must have at
+ * least seq_len rows (lnb_model_finalize's rope_rows), else the call fails and says so.  Beyond lnb_ctx_create's ~23000 positions the PV kernel of the
+ * long-context decode attention takes an LDS layout that does not grow with the context (72 KB: the p_j are evaluated where they are used); up to that
+ * capacity such a context launches exactly what lnb_ctx_create's does.  Everything reaches the whole context: one-token steps, lnb_decode_greedy[_until],
+ * calls of 16 or more rows, lnb_forward_append of any row count (2..15 rows beyond ~7800 positions run as one-token steps inside the call, as before),
+ * token probabilities, scoring, stop ids, lnb_batch_* and lnb_decode_speculative_until; every result is bit-identical to what a context of another
+ * capacity gives.  The attention forms that stage the whole context in the LDS (lnb_ctx_set_attention bits 2 / 3, LNB_ATTN_ONE, LNB_ATTN_LAZY=0) run the
+ * default pair beyond ~23000 positions of capacity.
+ * max_rows: the rows of x, h, xn, q, att, ffn (and of lnb_ctx_hidden_ptr's buffers); <= 0 or > seq_len: seq_len.  Every entry point that takes `seq` rows
+ * -- lnb_forward[_stage[_begin]], lnb_forward_append, lnb_forward_score[_append], the rows of a lnb_pipeline_tick -- refuses seq > max_rows up front, with
+ * both numbers in the message.  A 131072-position context of the 8B shape would otherwise carry ~9 GB of activation buffers beside its 17 GB of KV cache:
+ * feed a long prompt as lnb_forward_append calls of max_rows rows.  The KV caches, the token log and the attention scratch stay sized by seq_len. */
+#define LNB_MAX_SEQ_LEN 131072
+int lnb_ctx_create_long(lnb_model* m, int seq_len, int max_rows, lnb_ctx** out);
+int lnb_ctx_max_rows(const lnb_ctx* c, int* out);
 int lnb_ctx_destroy(lnb_ctx* c);
 int lnb_ctx_reset(lnb_ctx* c);                                       /* zero the caches again */
 /* InferenceContext.CacheK/CacheV[layer] (exported, poked by llamatransformer_simulated_test.go:527-538) */
@@ -151,6 +167,7 @@ int lnb_ctx_get_schedule(const lnb_ctx* c);
  * (head, slice) workgroups exchange the scores inside the launch behind a BOUNDED poll -- a workgroup whose peers are not resident computes their
  * share itself, so two contexts can never wait for each other; same bits; measured slower than the two launches, hence opt-in, also by
  * LNB_ATTN_ONE=1; latency schedule only); bit 2 (4) = one launch with every poll timing out; bit 1 (2) = two launches whatever the environment says.
+ * A context beyond lnb_ctx_create's capacity (lnb_ctx_create_long) cannot stage itself in the one-launch form's LDS: bits 2 / 3 run the two launches there.
  * lnb_ctx_zseq_count: rows that could not be certified and walked the serial sum. */
 int lnb_ctx_set_attention(lnb_ctx* c, int long_threshold, int force_zseq);
 int lnb_ctx_zseq_count(lnb_ctx* c, int* out);

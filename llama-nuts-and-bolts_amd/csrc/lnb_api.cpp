@@ -21,6 +21,7 @@
 #include "lnb_device.h"
 #include "lnb_knobs.h"
 #include "lnb_rccl.h"
+static_assert(LNB_MAX_SEQ_LEN == LNB_SEQ_MAX, "lnb.h and lnb_device.h disagree on the longest context");
 static_assert(LNB_MAX_TOP_K == LNB_TOKPROB_MAX_K, "lnb.h and lnb_device.h disagree on the largest top-k");
 static_assert(LNB_MAX_DRAFT == LNB_SPEC_MAX_DRAFT && LNB_MAX_DRAFT + 1 <= LNB_STREAM_COLS, "a verify pass is one column group of at most 16 columns");
 
@@ -29,6 +30,7 @@ hipError_t lnbk_gemv(const GemvParams* p, int rw, int nch, int epi, int norm, hi
 hipError_t lnbk_attn(const AttnParams* p, hipStream_t st);
 int lnbk_attn_short_max_T(int hd);
 size_t lnbk_attn_long_lds(int seq_len);
+size_t lnbk_attn_long_layout_lds(int seq_len);
 size_t lnbk_attn_one_lds(int seq_len, int hd);
 hipError_t lnbk_exp_table(double* tab, float divisor, hipStream_t st);
 hipError_t lnbk_gemm(const GemmParams* p, int epi, hipStream_t st);
@@ -144,12 +146,13 @@ struct lnb_model {
 };
 struct lnb_ctx {
     lnb_model* m = nullptr; int seq_len = 0;
+    int max_rows = 0;                      // rows per call the activation buffers (x, h, xn, q, att, ffn) hold: seq_len, or lnb_ctx_create_long's max_rows
     hipStream_t stream = nullptr;
     std::vector<uint16_t*> ck, cv;
     StepState* st = nullptr; int32_t* dtok = nullptr; int32_t* dnext = nullptr; int* derr = nullptr;
     int32_t* dout = nullptr; int dout_cap = 0;
     uint16_t *x = nullptr, *h = nullptr, *q = nullptr, *att = nullptr, *ffn = nullptr, *logits = nullptr;
-    uint16_t* xn = nullptr;                // [seq_len][dim] normalised rows for the matrix-core prefill path
+    uint16_t* xn = nullptr;                // [max_rows][dim] normalised rows for the matrix-core prefill path
     int logits_rows = 0;
     hipGraphExec_t graph = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -612,21 +615,47 @@ extern "C" int lnb_model_rope_table(lnb_model* m, float* out, int64_t nfloats, i
 
 // ---------------------------------------------------------------------------------------------------
 static int ctx_alloc(lnb_ctx* c);
+// the common path of lnb_ctx_create / lnb_ctx_create_long (seq_len already resolved and checked against the caller's cap)
+static int ctx_create_common(lnb_model* m, int seq_len, int max_rows, lnb_ctx** out) {
+    if (m->head_dim != 128 && m->head_dim != 64 && m->head_dim != 32) return fail("head_dim %d not one of 32/64/128", m->head_dim);
+    lnb_ctx* c = new lnb_ctx();
+    c->m = m; c->seq_len = seq_len; c->max_rows = max_rows > 0 && max_rows < seq_len ? max_rows : seq_len;
+    if (ctx_alloc(c)) { lnb_ctx_destroy(c); return -1; }
+    *out = c;
+    return 0;
+}
 extern "C" int lnb_ctx_create(lnb_model* m, int seq_len, lnb_ctx** out) {
     if (!m || !out) return fail("null argument");
     *out = nullptr;
     if (!m->finalized) return fail("model not finalized");
     HIPCHK(hipSetDevice(m->device));
-    lnb_ctx* c = new lnb_ctx();
-    c->m = m; c->seq_len = seq_len > 0 ? seq_len : m->a.max_seq_len;        // inferencecontext.go:22-26
+    const int sl = seq_len > 0 ? seq_len : m->a.max_seq_len;                 // inferencecontext.go:22-26
     // Context length: one-token calls above the attention crossover and calls of 16 or more rows run kernels without a per-position LDS
     // array that would not fit (the long-context PV kernel keeps 4 bytes per position: ~23 K positions); the one-workgroup-per-head kernel
-    // (12 bytes per position: ~7.8 K at head_dim 128) then only serves calls of 2..15 rows, which fail beyond its reach (lnb.h)
-    if (m->head_dim != 128 && m->head_dim != 64 && m->head_dim != 32) { delete c; return fail("head_dim %d not one of 32/64/128", m->head_dim); }
-    if (lnbk_attn_long_lds(c->seq_len) > 160 * 1024)
-        { const int sl = c->seq_len; delete c; return fail("seq_len %d too long for the LDS staging of the attention kernels (about 23000 positions)", sl); }
-    if (ctx_alloc(c)) { lnb_ctx_destroy(c); return -1; }
-    *out = c;
+    // (12 bytes per position: ~7.8 K at head_dim 128) then only serves calls of 2..15 rows, which fail beyond its reach (lnb.h).
+    // This entry point keeps that cap (and the per-position layout of the PV kernel below it); lnb_ctx_create_long goes beyond.
+    if (m->head_dim != 128 && m->head_dim != 64 && m->head_dim != 32) return fail("head_dim %d not one of 32/64/128", m->head_dim);
+    if (lnbk_attn_long_lds(sl) > 160 * 1024)
+        return fail("seq_len %d too long for the LDS staging of the attention kernels (about 23000 positions)", sl);
+    return ctx_create_common(m, sl, 0, out);
+}
+// Up to LNB_MAX_SEQ_LEN positions: beyond lnb_ctx_create's cap the long-context PV launch takes the layout whose LDS does not grow with the context
+// (lnb_kernels.hip: alp_pw_floats), chosen per launch from the capacity -- a long context below the cap launches exactly what lnb_ctx_create's would.
+// max_rows sizes the per-call activation buffers; the caches, the token words and log, e_buf and z_part stay sized by seq_len.
+extern "C" int lnb_ctx_create_long(lnb_model* m, int seq_len, int max_rows, lnb_ctx** out) {
+    if (!m || !out) return fail("null argument");
+    *out = nullptr;
+    if (!m->finalized) return fail("model not finalized");
+    HIPCHK(hipSetDevice(m->device));
+    const int sl = seq_len > 0 ? seq_len : m->a.max_seq_len;
+    if (sl > LNB_MAX_SEQ_LEN) return fail("seq_len %d too long: a long context holds at most %d positions", sl, LNB_MAX_SEQ_LEN);
+    if (sl > m->cis_rows)
+        return fail("seq_len %d is beyond the model's %d-row RoPE table: pass rope_rows >= %d to lnb_model_finalize", sl, m->cis_rows, sl);
+    return ctx_create_common(m, sl, max_rows, out);
+}
+extern "C" int lnb_ctx_max_rows(const lnb_ctx* c, int* out) {
+    if (!c || !out) return fail("null argument");
+    *out = c->max_rows;
     return 0;
 }
 static int ctx_alloc(lnb_ctx* c) {
@@ -651,14 +680,15 @@ static int ctx_alloc(lnb_ctx* c) {
     HIPCHK(hipMalloc((void**)&c->dtok, (size_t)c->seq_len * 4));
     HIPCHK(hipMalloc((void**)&c->dnext, 16)); HIPCHK(hipMalloc((void**)&c->derr, 16)); HIPCHK(hipMemsetAsync(c->derr, 0, 16, c->stream));
     c->dout_cap = c->seq_len; HIPCHK(hipMalloc((void**)&c->dout, (size_t)c->dout_cap * 4));
-    const size_t S = c->seq_len;
+    const size_t S = c->max_rows;                            // rows per call (lnb_ctx_create: seq_len)
     HIPCHK(hipMalloc((void**)&c->x, S * m->a.dim * 2)); HIPCHK(hipMalloc((void**)&c->h, S * m->a.dim * 2));
     HIPCHK(hipMalloc((void**)&c->xn, S * m->a.dim * 2));
     HIPCHK(hipMalloc((void**)&c->q, S * m->q_dim * 2)); HIPCHK(hipMalloc((void**)&c->att, S * m->q_dim * 2));
     HIPCHK(hipMalloc((void**)&c->ffn, S * m->ffn_hidden * 2));
     if (m->last()) { HIPCHK(hipMalloc((void**)&c->logits, (size_t)m->a.vocab_size * 2)); c->logits_rows = 1; }
-    HIPCHK(hipMalloc((void**)&c->e_buf, (size_t)m->a.n_heads * S * 8));
-    HIPCHK(hipMalloc((void**)&c->z_part, (size_t)m->a.n_heads * ((S + 63) / 64 + 8) * 8));     // (two-launch form: one partial per 256 positions; attn_one_kernel: one per 64)
+    const size_t SL = c->seq_len;
+    HIPCHK(hipMalloc((void**)&c->e_buf, (size_t)m->a.n_heads * SL * 8));
+    HIPCHK(hipMalloc((void**)&c->z_part, (size_t)m->a.n_heads * ((SL + 63) / 64 + 8) * 8));     // (two-launch form: one partial per 256 positions; attn_one_kernel: one per 64)
     HIPCHK(hipMalloc((void**)&c->zseq_count, 16)); HIPCHK(hipMemsetAsync(c->zseq_count, 0, 16, c->stream));
     HIPCHK(hipMalloc((void**)&c->attn_cnt, ((size_t)m->a.n_heads + 4) * 4)); HIPCHK(hipMemsetAsync(c->attn_cnt, 0, ((size_t)m->a.n_heads + 4) * 4, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -742,6 +772,8 @@ extern "C" int lnb_ctx_set_mode(lnb_ctx* c, int mode) {
     if (!c) return fail("null argument");
     if (mode != LNB_MODE_EXACT && mode != LNB_MODE_FAST) return fail("unknown mode %d (LNB_MODE_EXACT = 0, LNB_MODE_FAST = 1)", mode);
     if (mode == c->mode) return 0;
+    // (a long context, lnb_ctx_create_long, takes the tolerance mode too: none of lnb_fast.hip's kernels carries a per-position LDS array -- its GEMV / GEMM
+    // stage x, its flash attention two static V tiles -- and its one-token attention is the exact kernels' own)
     HIPCHK(hipSetDevice(c->m->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     drop_graphs(c);
@@ -769,6 +801,8 @@ extern "C" int lnb_ctx_get_schedule(const lnb_ctx* c) { return c ? c->sched : -1
 // Decode attention form: one-token calls at contexts above long_threshold run the chip-wide long-context kernels (bit-identical to the
 // one-workgroup-per-head kernel, tests/test_gpu_configs.py).  long_threshold < 0 keeps the current value; force_zseq = 1 makes the
 // long-context kernel always walk the reference's serial f64 sum instead of certifying the tree estimate (test hook).
+// On a context beyond lnb_ctx_create's cap (lnb_ctx_create_long) the forms that stage the whole context in the LDS -- the one-launch form (bits 2 / 3,
+// LNB_ATTN_ONE) and the eager-everywhere PV pass (LNB_ATTN_LAZY=0) -- cannot be launched: such a request runs the default scores + lazy-PV pair, same bits.
 extern "C" int lnb_ctx_set_attention(lnb_ctx* c, int long_threshold, int force_zseq) {
     if (!c) return fail("null argument");
     HIPCHK(hipSetDevice(c->m->device));
@@ -944,6 +978,7 @@ static int check_call(lnb_ctx* c, int seq, int start_pos, bool causal = false) {
     const int T = start_pos + seq;
     if (T > c->m->cis_rows) return fail("incompatible locStart, locEnd values and tensor (position %d beyond the %d-row RoPE table)", T, c->m->cis_rows);
     if (T > c->seq_len) return fail("incompatible locStart, locEnd values and tensor (position %d beyond the KV cache of %d)", T, c->seq_len);
+    if (seq > c->max_rows) return fail("a call of %d rows on a context whose activation buffers hold %d rows (lnb_ctx_create_long's max_rows)", seq, c->max_rows);
     if (seq > 1 && !causal && T % seq != 0) return fail("two tensor shapes cannot be broadcasted: [%d %d %d] and [%d %d]", c->m->a.n_heads, seq, T, seq, seq);
     // calls of 2.. rows that do NOT run on the matrix-core attention (fewer than 16 rows, or head_dim 32, which attn_mfma_kernel does not
     // take) go through the row-per-workgroup kernel, whose LDS arrays are sized for attn_short_cap positions
@@ -1145,6 +1180,7 @@ static int forward_append_impl(lnb_ctx* c, const char* name, const int32_t* toke
     const int T = start_pos + seq, V = m->a.vocab_size;
     if (T > m->cis_rows) return fail("%s: position %d is beyond the %d-row RoPE table", name, T, m->cis_rows);
     if (T > c->seq_len) return fail("%s: position %d is beyond the KV cache of %d", name, T, c->seq_len);
+    if (seq > c->max_rows) return fail("%s: a call of %d rows on a context whose activation buffers hold %d rows (lnb_ctx_create_long's max_rows)", name, seq, c->max_rows);
     const bool mfma_attn = use_mfma(seq) && (m->head_dim == 64 || m->head_dim == 128);
     if (seq == 1 || (!mfma_attn && T > c->attn_short_cap)) {
         for (int i = 0; i < seq; i++) {
@@ -1669,7 +1705,7 @@ extern "C" int lnb_batch_create(lnb_ctx* const* ctxs, int n, lnb_batch** out) {
     lnb_batch* b = new lnb_batch();
     b->m = m; b->n = n; b->ctxs.assign(ctxs, ctxs + n); b->rows_form = !m->batch_enabled; b->top_k = ctxs[0]->top_k;
     for (int s = 0; s < n; s++) {
-        if (lnbk_attn_long_lds(ctxs[s]->seq_len) > 160 * 1024) {       // (lnb_ctx_create refuses such a context: cannot happen)
+        if (lnbk_attn_long_layout_lds(ctxs[s]->seq_len) > 160 * 1024) {       // (neither lnb_ctx_create nor lnb_ctx_create_long makes such a context: cannot happen)
             const int sl = ctxs[s]->seq_len; delete b;
             return fail("context %d: seq_len %d is beyond what the long-context attention keeps in the LDS", s, sl);
         }
@@ -2503,6 +2539,8 @@ extern "C" int lnb_pipeline_tick(lnb_pipe* p, lnb_ctx* run, int run_rows, int ru
     for (lnb_ctx* c : {run, send, recv}) if (c) { if (c->m != m) return fail("context of another model stage"); if (pipe_events(c)) return -1; }
     if (p->host && (send || recv)) return fail("this pipe has no transport (lnb_pipeline_init_host): the host layer moves lnb_ctx_hidden_ptr's buffers itself; send and recv must be NULL");
     if (token_slot_out) *token_slot_out = -1;
+    if (send && send_rows > send->max_rows) return fail("a hand-off of %d rows from a context whose activation buffers hold %d rows (lnb_ctx_create_long's max_rows)", send_rows, send->max_rows);
+    if (recv && recv_rows > recv->max_rows) return fail("a hand-off of %d rows into a context whose activation buffers hold %d rows (lnb_ctx_create_long's max_rows)", recv_rows, recv->max_rows);
     if (run) {
         if (run->top_k > 0) return fail("the context records token probabilities, which pipeline ticks do not support (lnb_ctx_set_token_probs(ctx, 0))");
         if (check_call(run, run_rows, run_pos)) return -1;

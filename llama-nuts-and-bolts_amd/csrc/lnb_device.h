@@ -146,6 +146,8 @@ struct AttnParams {
     double* z_part;             // [H][ceil(seq_len / 256)] f64: per-block tree sums of e (only an ESTIMATE of Z, see the kernel)
                                 // batched long form (btab && longctx, the BATCH instantiations): S sequences in grid.z, seq_len = the LARGEST member's cache length,
                                 // e_buf [S][H][seq_len], z_part [S][H][ceil(seq_len / 256)]; every sequence's own length comes from btab->seq_len
+    int pw_floats;              // attn_long_pv[2]_kernel: floats of the p_j array in front of the product ring (alp_pw_floats(seq_len)): one per position up to what 160 KB
+                                // hold, a constant three batches beyond (only the eager body, T <= 1024, reads the array); set by the launcher
     int* zseq_count;            // counts workgroups that had to fall back to the sequential Z chain (diagnostics)
     unsigned* cnt;              // attn_one_kernel (longctx >= 2): [H] arrival counters of the in-launch exchange (never reset: a launch's generation is old / slices) + [H] = polls that timed out
     // batched decode (attn_exact_kernel, S = 1 per sequence): query row i belongs to sequence i of the batch -- its own position, caches and
@@ -169,6 +171,7 @@ struct AttnParams {
 // e = 0..7, its A operands of the k-groups g = 4e + m of the chunk (k = 128C + 4g + kk).  Activations of the batch ("xt"):
 //   [C][m][kk][s = sequence 0..15][e]   -- lane (s, kk) loads its B operands of the same k-groups with the same instruction shape.
 constexpr int LNB_BATCH_MAX = 128;          // sequences per batch
+constexpr int LNB_SEQ_MAX = 131072;         // positions of the longest context (lnb.h: LNB_MAX_SEQ_LEN, lnb_ctx_create_long)
 constexpr int LNB_STREAM_COLS = 16;         // ... of which mfma_stream_kernel carries up to 16 as the columns of ONE matrix instruction; larger batches are rows of gemm_stream_kernel
 LNB_HD size_t m16_index(int n, int k, int c, int K, int NCH) {
     const int t = n >> 4, i = n & 15, C = k >> 7, e = (k >> 4) & 7, m = (k >> 2) & 3, kk = k & 3;

@@ -2594,6 +2594,7 @@ template <int HD> DEVINL void attn_pv_add(int c, int nchunks, int r, const char*
 struct CertZ { double rzt, zlo, zhi; unsigned delta32; };
 DEVINL CertZ cert_z(double zt, int T) {
     const double epsr = (double)(4 * T + 8) * 1.1102230246251565e-16;
+    static_assert(LNB_SEQ_MAX < (1 << 20), "delta32 = 4T + 12 must stay far below the 2^28 between a cell's step point and its end");
     CertZ c; c.rzt = 1.0 / zt; c.zlo = zt * (1.0 - epsr); c.zhi = zt * (1.0 + epsr); c.delta32 = 4u * (unsigned)T + 12u;
     return c;
 }
@@ -3140,6 +3141,14 @@ constexpr int ALP_NT = 512;                                  // waves 0..3: adde
 constexpr int ALP_SLOT = ALP_DS * ALP_BATCH;                 // floats per ring slot: [dim][chunk][half][position % 16][4]
 constexpr int ALP_EU = 12;                                   // e_j per thread and round
 __host__ __device__ inline size_t alp_lds_bytes(int seq_len) { return (size_t)((seq_len + ALP_BATCH - 1) / ALP_BATCH + 1) * ALP_BATCH * 4 + 2 * (size_t)ALP_SLOT * 4 + 64; }
+// The p_j array in front of the ring: one float per cached position (+ a batch of zeros) while that fits the 160 KB of a CU's LDS -- contexts of up to 23552
+// positions, every context lnb_ctx_create accepts: the layout and the size they always had.  Beyond (lnb_ctx_create_long) the array is a CONSTANT three
+// batches: only the eager body reads it, attn_long_pv2_kernel runs that body for T <= 2 * ALP_BATCH (Tpad = 3 batches), and the lazy body evaluates p_j
+// where it multiplies the V row.  The launcher never pairs the constant layout with attn_long_pv_kernel (the eager body at every T).
+constexpr int ALP_PW_LONG = 3 * ALP_BATCH;
+__host__ __device__ inline bool alp_per_position(int seq_len) { return alp_lds_bytes(seq_len) <= (size_t)160 * 1024; }
+__host__ __device__ inline int alp_pw_floats(int seq_len) { return alp_per_position(seq_len) ? ((seq_len + ALP_BATCH - 1) / ALP_BATCH + 1) * ALP_BATCH : ALP_PW_LONG; }
+__host__ __device__ inline size_t alp_layout_bytes(int seq_len) { return (size_t)alp_pw_floats(seq_len) * 4 + 2 * (size_t)ALP_SLOT * 4 + 64; }
 DEVINL float alp_p(double e, double z) { return bf_wide(bf_trunc((float)(e / z))); }     // impl:506 + ToBFloat16 :493
 template <int HD, bool BATCH = false> DEVINL void alp_eager_body(const AttnParams& p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -3150,7 +3159,7 @@ template <int HD, bool BATCH = false> DEVINL void alp_eager_body(const AttnParam
     const int T = al_T<BATCH>(p, sq), nblk = (T + ALS_NT - 1) / ALS_NT, nbatch = (T + ALP_BATCH - 1) / ALP_BATCH;
     const int Tpad = (nbatch + 1) * ALP_BATCH;               // (+ one batch of zeros: the producers run ahead)
     float* pw = (float*)smem;                                // [Tpad] p_j (+0 beyond T)
-    float* ring = (float*)(smem + (size_t)((p.seq_len + ALP_BATCH - 1) / ALP_BATCH + 1) * ALP_BATCH * 4);   // [2][ALP_SLOT] products
+    float* ring = (float*)(smem + (size_t)p.pw_floats * 4);   // [2][ALP_SLOT] products, behind the p_j array (alp_pw_floats: the launcher's choice)
     double* zsh = (double*)(ring + 2 * ALP_SLOT);
     const double* E = p.e_buf + al_row<BATCH>(sq, h) * p.seq_len;
     const int kvh = h / (p.H / p.KVH);
@@ -3190,6 +3199,7 @@ template <int HD, bool BATCH = false> DEVINL void alp_eager_body(const AttnParam
     }
     // ---- p_j with the estimate, certified (header comment).  The quotient is formed as e * (1 / Zt): within 2 ulps of the correctly
     // rounded e / Zt, which the certification band absorbs (its half-width 4 T + 12 ulps instead of 4 T + 4)
+    static_assert(LNB_SEQ_MAX < (1 << 20), "the certification band 4T + 12 is sized for T < 2^20");
     const unsigned delta32 = 4u * (unsigned)T + 12u;         // (T < 2^20: far below the 2^28 between a cell's step point and its end)
     const double epsr = (double)(4 * T + 8) * 1.1102230246251565e-16;          // relative half-width of the interval that holds the reference's Z
     const double zlo = zt * (1.0 - epsr), zhi = zt * (1.0 + epsr), rzt = 1.0 / zt;
@@ -3324,7 +3334,7 @@ template <int HD, bool BATCH = false> DEVINL void alp_lazy_body(const AttnParams
     int h, ds; xcd_head_block(h, ds);
     [[maybe_unused]] AlSeq sq{}; if constexpr (BATCH) sq = al_seq(p, h);      // (BATCH: p.seq_len = the largest member's -- row strides, LDS layout; al_len = this sequence's array ends)
     const int T = al_T<BATCH>(p, sq), nblk = (T + ALS_NT - 1) / ALS_NT, nbatch = (T + ALP_BATCH - 1) / ALP_BATCH;
-    float* ring = (float*)(smem + (size_t)((p.seq_len + ALP_BATCH - 1) / ALP_BATCH + 1) * ALP_BATCH * 4);   // [2][ALP_SLOT] products
+    float* ring = (float*)(smem + (size_t)p.pw_floats * 4);   // [2][ALP_SLOT] products, behind the p_j array (alp_pw_floats: the launcher's choice)
     double* zsh = (double*)(ring + 2 * ALP_SLOT);
     int* const flag = (int*)(zsh + 1);
     const double* E = p.e_buf + al_row<BATCH>(sq, h) * p.seq_len;
@@ -4351,13 +4361,15 @@ template <bool BATCH> static hipError_t launch_attn_long(const AttnParams* p, hi
     return with_hd(p, [&](auto HD) {
         const auto scores = attn_long_scores_kernel<HD, BATCH>, lazy = attn_long_pv2_kernel<HD, BATCH>, eager = attn_long_pv_kernel<HD, BATCH>;
         if (!p) return raise_lds(lazy, eager);
-        const auto pv = knob(Knob::ATTN_LAZY) ? lazy : eager;
-        const size_t lds = alp_lds_bytes(p->seq_len);
-        if (lds > 160 * 1024 || p->hd % ALP_DS || !p->e_buf || !p->z_part) return hipErrorInvalidValue;
+        // (a context beyond the per-position layout cannot stage p_j for the eager-everywhere form: LNB_ATTN_LAZY=0 runs the default pair there)
+        const auto pv = knob(Knob::ATTN_LAZY) || !alp_per_position(p->seq_len) ? lazy : eager;
+        const size_t lds = alp_layout_bytes(p->seq_len);
+        if (lds > 160 * 1024 || p->seq_len > LNB_SEQ_MAX || p->hd % ALP_DS || !p->e_buf || !p->z_part) return hipErrorInvalidValue;
         if (BATCH && (!p->bkv || p->S < 1 || p->S > LNB_BATCH_MAX || (!p->out && !p->out_xt))) return hipErrorInvalidValue;
         const unsigned z = BATCH ? p->S : 1;
         AttnParams ps = *p;
         ps.touch = knob(Knob::ATTN_TOUCH) != 0;
+        ps.pw_floats = alp_pw_floats(p->seq_len);
         hipLaunchKernelGGL(scores, dim3(p->H, (p->seq_len + ALS_NT - 1) / ALS_NT, z), dim3(ALS_NT), 0, st, ps);
         hipLaunchKernelGGL(pv, dim3(p->H, p->hd / ALP_DS, z), dim3(ALP_NT), lds, st, ps);
         return hipGetLastError();
@@ -4376,6 +4388,8 @@ static hipError_t launch_attn_one(const AttnParams* p, hipStream_t st) {
 }
 extern "C" size_t lnbk_attn_one_lds(int seq_len, int hd) { return att1_lds_bytes(seq_len, hd); }
 extern "C" size_t lnbk_attn_long_lds(int seq_len) { return alp_lds_bytes(seq_len); }
+// what the PV launch of a context of seq_len positions really requests: lnbk_attn_long_lds up to 160 KB, a constant beyond (alp_pw_floats)
+extern "C" size_t lnbk_attn_long_layout_lds(int seq_len) { return alp_layout_bytes(seq_len); }
 
 extern "C" void lnbk_attn_gqa_dbg_dump(void) {
     if (!g_gqa_dbg) return;

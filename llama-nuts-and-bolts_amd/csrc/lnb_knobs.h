@@ -30,8 +30,8 @@
     X(OP_STREAM, 0, LIVE, "1: lnb_op_linear of 16+ rows through gemm_stream_kernel (tests)") \
     /* decode attention form */ \
     X(ATTN_LONG_T, 512, LIVE, "context length from which a new context decodes with the long-context attention kernels") \
-    X(ATTN_ONE, 0, ONCE, "1: long-context decode attention in one launch (attn_one_kernel; measured slower)") \
-    X(ATTN_LAZY, 1, LIVE, "0: the long-context PV pass without the lazy certificate (attn_long_pv_kernel)") \
+    X(ATTN_ONE, 0, ONCE, "1: long-context decode attention in one launch (attn_one_kernel; measured slower); a context beyond lnb_ctx_create's capacity keeps the two launches") \
+    X(ATTN_LAZY, 1, LIVE, "0: the long-context PV pass without the lazy certificate (attn_long_pv_kernel); a context beyond lnb_ctx_create's capacity keeps the lazy one") \
     X(ATTN_TOUCH, 1, LIVE, "0: the long-context scores pass does not touch V ahead of the PV pass (A/B)") \
     /* batched decode */ \
     X(BATCH_GROUPS, 1, ONCE, "0: 17..32 sequences decode as rows, not as two column groups") \

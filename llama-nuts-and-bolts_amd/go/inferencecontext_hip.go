@@ -43,6 +43,9 @@ type InferenceContext struct {
 	handle *C.lnb_ctx
 	lt     *LlamaTransformer // keeps the transformer alive (and finalized after this context)
 	topK   int               // SetTokenProbs
+
+	longContext bool // NewLongInferenceContext: created by lnb_ctx_create_long
+	maxRows     int  // ... with activation buffers of this many rows (0: SequenceLength)
 }
 
 // LayerProgress switches the per-layer "Transformer block layer %d / %d was run" message (llamatransformer.go:163) on or off for
@@ -68,6 +71,28 @@ func NewInferenceContext(model *Model, inferenceArgs common.InferenceArgs, logFn
 	}
 	common.GLogger.DebugPrintf("Inference Context created with SequenceLength: %d", context.SequenceLength)
 	return context
+}
+
+// NewLongInferenceContext: a context of up to 131072 positions (LNB_MAX_SEQ_LEN; lnb_ctx_create_long) whose per-call activation buffers hold
+// maxRows rows instead of SequenceLength (0: SequenceLength).  The transformer's RoPE table must have SequenceLength rows; a Forward of more
+// than maxRows rows is refused, so a long prompt goes in as chunks.  NewInferenceContext keeps the library's ~23000-position capacity.
+func NewLongInferenceContext(model *Model, inferenceArgs common.InferenceArgs, maxRows int, logFn func(format string, v ...any)) *InferenceContext {
+	context := NewInferenceContext(model, inferenceArgs, logFn)
+	context.longContext = true
+	context.maxRows = maxRows
+	return context
+}
+
+// MaxRows: the rows per call the device-side activation buffers hold (lnb_ctx_max_rows); 0 before the first Forward has attached the context.
+func (ic *InferenceContext) MaxRows() (int, error) {
+	if ic.handle == nil {
+		return 0, nil
+	}
+	var n C.int
+	if err := lnbCall(func() C.int { return C.lnb_ctx_max_rows(ic.handle, &n) }); err != nil {
+		return 0, err
+	}
+	return int(n), nil
 }
 
 func (ic *InferenceContext) Logf(format string, v ...any) {
@@ -118,7 +143,11 @@ func (ic *InferenceContext) attach(lt *LlamaTransformer) error {
 	if ic.handle != nil {
 		return nil
 	}
-	if err := lnbCall(func() C.int { return C.lnb_ctx_create(lt.handle, C.int(ic.SequenceLength), &ic.handle) }); err != nil {
+	create := func() C.int { return C.lnb_ctx_create(lt.handle, C.int(ic.SequenceLength), &ic.handle) }
+	if ic.longContext {
+		create = func() C.int { return C.lnb_ctx_create_long(lt.handle, C.int(ic.SequenceLength), C.int(ic.maxRows), &ic.handle) }
+	}
+	if err := lnbCall(create); err != nil {
 		return err
 	}
 	lt.mu.Lock()

@@ -186,8 +186,16 @@ public:
         check(lnb_ctx_create(t.handle(), SequenceLength, &h_));
         if (logFn_) check(lnb_ctx_set_layer_callback(h_, &InferenceContext::layer_cb, this));
     }
+    // a context of up to LNB_MAX_SEQ_LEN positions (lnb_ctx_create_long) whose per-call activation buffers hold maxRows rows (<= 0: SequenceLength): the
+    // transformer's RoPE table must have SequenceLength rows, and a Forward of more than maxRows rows is refused -- a long prompt goes in as chunks
+    InferenceContext(const LlamaTransformer& t, InferenceArgs ia, int maxRows, LogFn logFn) : t_(t), logFn_(std::move(logFn)) {
+        SequenceLength = ia.SequenceLength > 0 ? ia.SequenceLength : t.Args().MaxSequenceLength;
+        check(lnb_ctx_create_long(t.handle(), SequenceLength, maxRows, &h_));
+        if (logFn_) check(lnb_ctx_set_layer_callback(h_, &InferenceContext::layer_cb, this));
+    }
     ~InferenceContext() { if (h_) lnb_ctx_destroy(h_); }
     int SequenceLength = 0;
+    int MaxRows() const { int n = 0; check(lnb_ctx_max_rows(h_, &n)); return n; }
     std::vector<uint16_t> CacheK(int layer) const { return kv(layer, 0); }   // exported fields, poked by the reference's tests
     std::vector<uint16_t> CacheV(int layer) const { return kv(layer, 1); }
     lnb_ctx* handle() const { return h_; }

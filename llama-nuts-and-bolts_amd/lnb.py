@@ -67,9 +67,11 @@ EXPORTS = [
     "lnb_forward_append", "lnb_forward_score_append",
     "lnb_ctx_set_draft", "lnb_decode_speculative_until", "lnb_op_ngram_draft",
     "lnb_batch_set_attention", "lnb_ctx_set_batched_attention", "lnb_batch_attention_form", "lnb_ctx_verify_attention_form",
+    "lnb_ctx_create_long", "lnb_ctx_max_rows",
 ]
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
 MAX_DRAFT = 15           # LNB_MAX_DRAFT of include/lnb.h (tests/test_speculative_cpu.py compares them)
+MAX_SEQ_LEN = 131072     # LNB_MAX_SEQ_LEN of include/lnb.h (tests/test_long_context_cpu.py compares them)
 ABI_VERSION = 6          # LNB_ABI_VERSION of include/lnb.h this binding was written against (tests/test_cabi.py compares it with the header's)
 
 
@@ -122,6 +124,8 @@ def lib():
     L.lnb_model_weight_bytes.argtypes = [vp]
     L.lnb_model_weight_bytes.restype = C.c_int64
     L.lnb_ctx_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.lnb_ctx_create_long.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
+    L.lnb_ctx_max_rows.argtypes = [vp, C.POINTER(C.c_int)]
     L.lnb_ctx_destroy.argtypes = [vp]
     L.lnb_ctx_reset.argtypes = [vp]
     L.lnb_ctx_read_kv.argtypes = [vp, C.c_int, C.c_int, vp]
@@ -471,13 +475,24 @@ class LlamaTransformer:
 
 
 class InferenceContext:
-    """model.NewInferenceContext (inferencecontext.go:17-46): device KV cache for one generation."""
+    """model.NewInferenceContext (inferencecontext.go:17-46): device KV cache for one generation.
+    max_rows / long_context select lnb_ctx_create_long: up to MAX_SEQ_LEN positions (the transformer finalized with that many rope_rows), the per-call
+    activation buffers sized for max_rows rows (None: seq_len) -- calls of more rows are refused.  The two-argument form is lnb_ctx_create (~23 K positions)."""
 
-    def __init__(self, transformer, seq_len):
+    def __init__(self, transformer, seq_len, max_rows=None, long_context=False):
         self.t, self.L = transformer, transformer.L
         self.SequenceLength = seq_len
         self.h = C.c_void_p()
-        _chk(self.L.lnb_ctx_create(transformer.h, seq_len, C.byref(self.h)))
+        if long_context or max_rows is not None:
+            _chk(self.L.lnb_ctx_create_long(transformer.h, seq_len, int(max_rows or 0), C.byref(self.h)))
+        else:
+            _chk(self.L.lnb_ctx_create(transformer.h, seq_len, C.byref(self.h)))
+
+    def max_rows(self):
+        """rows per call the activation buffers hold (lnb_ctx_max_rows): seq_len unless the context was created with max_rows"""
+        n = C.c_int(0)
+        _chk(self.L.lnb_ctx_max_rows(self.h, C.byref(n)))
+        return n.value
 
     def set_mode(self, mode):
         """MODE_EXACT (default, bit-identical to the reference) or MODE_FAST (split-K / bf16-MFMA tolerance mode)"""
@@ -802,18 +817,24 @@ class InferenceEngine:
     """Greedy generation loop of src/inference/inference.go:173-254 over the device path:
     prefill(prompt) through Forward, then the decode steps as hipGraph replays on the device.
     prefill_chunk: 0 = the prompt goes in one Forward; n > 0 = it is ingested as ForwardAppend calls of at most n rows (the same tokens out:
-    every row is the same one-token step either way; the prefill attention's score scratch is then sized for n rows instead of the prompt)."""
+    every row is the same one-token step either way; the prefill attention's score scratch is then sized for n rows instead of the prompt).
+    long_context: the generation's context is a long one (lnb_ctx_create_long, up to MAX_SEQ_LEN positions) whose activation buffers hold
+    prefill_chunk rows, or the prompt when the chunk is 0."""
 
-    def __init__(self, transformer, seq_len, stop_token_ids=(), prefill_chunk=0):
+    def __init__(self, transformer, seq_len, stop_token_ids=(), prefill_chunk=0, long_context=False):
         if int(prefill_chunk) < 0:
             raise LnbError("prefill_chunk must be 0 (one Forward) or a positive row count")
         self.t, self.seq_len, self.stop, self.prefill_chunk = transformer, seq_len, set(stop_token_ids), int(prefill_chunk)
+        self.long_context = bool(long_context)
 
     def GenerateTokens(self, prompt_tokens, max_new=None):
         prompt = list(prompt_tokens)
         if len(prompt) >= self.seq_len:
             raise LnbError("context SequenceLength %d must be higher than prompt tokens length %d" % (self.seq_len, len(prompt)))
-        ctx = InferenceContext(self.t, self.seq_len)
+        if self.long_context:
+            ctx = InferenceContext(self.t, self.seq_len, max_rows=self.prefill_chunk or max(len(prompt), 1), long_context=True)
+        else:
+            ctx = InferenceContext(self.t, self.seq_len)
         try:
             n_new = self.seq_len - len(prompt) if max_new is None else min(max_new, self.seq_len - len(prompt))
             if self.prefill_chunk > 0:
