@@ -119,14 +119,14 @@ int64_t lnb_model_weight_bytes(lnb_model* m);
  * or 128.  One-token calls, calls of 16 or more rows, batched decode (lnb_batch_*) and speculative decode reach that far: beyond what the
  * one-workgroup-per-head attention stages in the LDS (12 bytes per position: ~7800 positions at head_dim 128, ~10800 at 64) they run the
  * long-context kernels.  Calls of 2..15 rows use a kernel that stages 12 bytes per position and fail beyond ~7800 positions (head_dim 128; ~10800 at 64)
- * (lnb_forward_append falls back to one-token steps there).  A longer seq_len is refused ("... too long ..."): lnb_ctx_create_long goes further. */
+ * (lnb_forward_append runs the multi-row long-context attention there: still one pass over the weights, lnb_ctx_set_rows_attention).  A longer seq_len is refused ("... too long ..."): lnb_ctx_create_long goes further. */
 int lnb_ctx_create(lnb_model* m, int seq_len, lnb_ctx** out);
 /* A context of up to LNB_MAX_SEQ_LEN (131072) positions whose per-call activation buffers hold max_rows rows instead of seq_len.
  * Capacity: seq_len 1..LNB_MAX_SEQ_LEN (<= 0: the model's max_seq_len); above, the call fails ("... too long ..."); the model's RoPE table must have at
  * least seq_len rows (lnb_model_finalize's rope_rows), else the call fails and says so.  Beyond lnb_ctx_create's ~23000 positions the PV kernel of the
  * long-context decode attention takes an LDS layout that does not grow with the context (72 KB: the p_j are evaluated where they are used); up to that
  * capacity such a context launches exactly what lnb_ctx_create's does.  Everything reaches the whole context: one-token steps, lnb_decode_greedy[_until],
- * calls of 16 or more rows, lnb_forward_append of any row count (2..15 rows beyond ~7800 positions run as one-token steps inside the call, as before),
+ * calls of 16 or more rows, lnb_forward_append of any row count (2..15 rows beyond ~7800 positions run the multi-row long-context attention, whose LDS does not grow with the context),
  * token probabilities, scoring, stop ids, lnb_batch_* and lnb_decode_speculative_until; every result is bit-identical to what a context of another
  * capacity gives.  The attention forms that stage the whole context in the LDS (lnb_ctx_set_attention bits 2 / 3, LNB_ATTN_ONE, LNB_ATTN_LAZY=0) run the
  * default pair beyond ~23000 positions of capacity.
@@ -211,7 +211,8 @@ int lnb_forward(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float
  *   Afterwards lnb_decode_greedy[_until], lnb_decode_speculative_until, lnb_batch_* and further appends continue the context.
  *   Kernels: 16 or more rows at head_dim 64 / 128 run the matrix-core attention with the causal mask (tiles above the shifted diagonal are
  *   skipped); 2..15 rows, and any row count at head_dim 32, the row-per-workgroup kernel.  Where that kernel cannot stage the context (see
- *   lnb_ctx_create) the rows run as one-token steps on the long-context kernels inside the call instead of failing.
+ *   lnb_ctx_create) the call runs the multi-row long-context attention (lnb_ctx_set_rows_attention below): one pass over the weights, K and V
+ *   read once for all rows; only if its scratch cannot be allocated do the rows run as one-token steps inside the call.
  *   Refused, each with a message: a stage handle that is not the whole model; LNB_MODE_FAST (the tolerance mode is frozen and its flash
  *   kernel keeps the modulo mask); NULL tokens, seq <= 0 or a negative start_pos (checked before the handle is touched); positions beyond the
  *   KV cache or the RoPE table.
@@ -220,6 +221,19 @@ int lnb_forward(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float
 int lnb_forward_append(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out);
 int lnb_forward_score_append(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, const int32_t* targets,
                              float* target_logit, float* target_prob, double* log_z, int32_t* argmax_last_out);
+/* Multi-row long-context attention: up to 16 consecutive rows of one context per launch pair, every K and V row read once for all of them; each
+ * row is the one-token step at its position, bit for bit (certified softmax per row, serial sum where certification fails).
+ * Appends of 2..15 rows (any row count at head_dim 32) whose start_pos + seq exceeds long_threshold run it; long_threshold < 0 keeps the current
+ * value; the default is what the row-per-workgroup kernel stages in the LDS (~7800 positions at head_dim 128), i.e. exactly the calls that kernel
+ * cannot take; 0 sends every such call there.  Calls beyond the row-per-workgroup kernel's reach run it whatever the threshold.  flags bit 0:
+ * every row walks the serial sum (counted per (row, head) in lnb_ctx_zseq_count).  flags bit 1: the verify passes of lnb_decode_speculative_until
+ * run it wherever they would run the long-context pair (off by default).  The scratch (16 * n_heads * seq_len * 8 bytes, shared with the verify
+ * passes) is allocated when a call first needs it.  Arguments are checked before the handle; refused while a lnb_forward_stage_begin is pending.
+ * Rows per PV workgroup: LNB_ATTN_ROWS_RPW. */
+int lnb_ctx_set_rows_attention(lnb_ctx* c, int long_threshold, int flags);
+/* the attention of the last lnb_forward_append / lnb_forward_score_append: 0 none yet or a one-row call, 1 the row-per-workgroup kernel,
+ * 2 the matrix-core kernel, 3 one-token steps inside the call, 4 the multi-row long-context pair */
+int lnb_ctx_append_attention_form(const lnb_ctx* c, int* out);
 
 /* ---- greedy loop on the device: the decode half of InferenceEngine.generateTokensInternal
  * (src/inference/inference.go:194-252).  Starting from `token` at position start_pos (its KV is computed by
@@ -355,7 +369,8 @@ int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int iters, float*
 int lnb_batch_set_attention(lnb_batch* b, int long_threshold, int force_zseq);
 /* the same for the verify passes of lnb_decode_speculative_until on this context (chosen per pass; one scratch for all widths) */
 int lnb_ctx_set_batched_attention(lnb_ctx* c, int long_threshold, int force_zseq);
-/* 0: the last batched call / verify pass ran the one-workgroup kernels, 1: the long-context pair (a test and a bench print it) */
+/* 0: the last batched call / verify pass ran the one-workgroup kernels, 1: the long-context pair (a test and a bench print it);
+ * lnb_ctx_verify_attention_form also 2: the multi-row long-context pair (lnb_ctx_set_rows_attention, flags bit 1) */
 int lnb_batch_attention_form(const lnb_batch* b, int* out);
 int lnb_ctx_verify_attention_form(const lnb_ctx* c, int* out);
 

@@ -28,6 +28,7 @@ static_assert(LNB_MAX_DRAFT == LNB_SPEC_MAX_DRAFT && LNB_MAX_DRAFT + 1 <= LNB_ST
 extern "C" {
 hipError_t lnbk_gemv(const GemvParams* p, int rw, int nch, int epi, int norm, hipStream_t st);
 hipError_t lnbk_attn(const AttnParams* p, hipStream_t st);
+hipError_t lnbk_attn_rows(const AttnParams* p, int pos0, hipStream_t st);
 int lnbk_attn_short_max_T(int hd);
 size_t lnbk_attn_long_lds(int seq_len);
 size_t lnbk_attn_long_layout_lds(int seq_len);
@@ -201,6 +202,12 @@ struct lnb_ctx {
     // scratch all widths share (sized for 16 columns, allocated when a pass first needs the long form), the form of the last verify pass
     int sp_attn_long_T = 0x7FFFFFFF, sp_force_zseq = 0, sp_last_form = 0;
     double* sp_e_buf = nullptr; double* sp_z_part = nullptr;
+    // multi-row long-context attention (attn_rows_*_kernel, lnb_ctx_set_rows_attention): appends of 2..15 rows (any row count at head_dim 32) whose
+    // start_pos + seq exceeds rows_T (default attn_short_cap: the calls the row-per-workgroup kernel cannot take) run it; rows_flags bit 0 = every row
+    // walks the serial sum, bit 1 = the verify passes run it wherever they would run the long form.  Its scratch is sp_e_buf / sp_z_part.
+    int rows_T = 0, rows_flags = 0, last_append_form = 0;
+    bool attn_rows = false;                // set by lnb_forward_append around a multi-row call that runs the pair
+    bool rows_no_scratch = false;          // an append could not allocate the pair's scratch: such calls run as one-token steps from then on
 };
 // Every path that rewrites the device-side StepState goes through here, so that the pipeline tick's "the graph left pos+1 behind, skip
 // the set_state launch" shortcut (dev_pos) can never act on a position some OTHER entry point has since overwritten (lnb_forward,
@@ -695,6 +702,7 @@ static int ctx_alloc(lnb_ctx* c) {
     // crossover measured on MI355X (tools/att_timing.py): the one-workgroup-per-head kernel wins below a few hundred positions
     c->attn_long_T = knob(Knob::ATTN_LONG_T);
     c->attn_short_cap = lnbk_attn_short_max_T(m->head_dim);
+    c->rows_T = c->attn_short_cap;
     return 0;
 }
 
@@ -918,6 +926,10 @@ static int enqueue_layer_kernel(lnb_ctx* c, int l, int S, int which, hipStream_t
                              a.n_heads * (m->head_dim / 16) <= g_num_cus && lnbk_attn_one_lds(c->seq_len, m->head_dim) <= (size_t)160 * 1024;
             ap.longctx = one ? ((c->force_zseq & 4) ? 3 : 2) : 1;
         }
+        if (c->attn_rows && ap.causal) {                     // lnb_forward_append beyond the row-per-workgroup kernel's reach: K and V read once for all rows
+            ap.e_buf = c->sp_e_buf; ap.z_part = c->sp_z_part; ap.force_zseq = c->rows_flags & 1;
+            HIPCHK(lnbk_attn_rows(&ap, c->call_T - S, st)); return 0;
+        }
         if (c->mode == LNB_MODE_FAST && ap.mfma) {           // tolerance mode prefill: flash form on the bf16 matrix cores
             hipError_t e = lnbk_fast_attn(&ap, st);
             if (e != hipErrorNotSupported) { HIPCHK(e); return 0; }
@@ -1010,7 +1022,7 @@ static int check_call(lnb_ctx* c, int seq, int start_pos, bool causal = false) {
         }
     }
     if (seq > 1) c->last_prefill_form = (!mfma_attn || !stage_has_attn || c->mode == LNB_MODE_FAST) ? 0 : c->sidx_jt > 0 ? 3 : 1;
-    if (seq > 1 && !mfma_attn && T > c->attn_short_cap)
+    if (seq > 1 && !mfma_attn && T > c->attn_short_cap && !(causal && c->attn_rows))
         return fail("a call of %d rows (2..15, or any multi-row call at head_dim 32) at context %d: the row-per-workgroup attention kernel stages "
                     "at most %d positions in the LDS; use one-token calls or 16 or more rows there", seq, T, c->attn_short_cap);
     return 0;
@@ -1166,8 +1178,11 @@ extern "C" int lnb_forward(lnb_ctx* c, const int32_t* tokens, int seq, int start
 }
 
 // lnb_forward_append / lnb_forward_score_append: `seq` rows at ANY start position under the true causal mask -- row i is the one-token step at
-// start_pos + i (include/lnb.h).  One multi-row call where the attention kernels take it; where they do not (2..15 rows, or any row count at head_dim 32,
-// with a context beyond what the row-per-workgroup kernel stages in the LDS) the rows run as the one-token steps they are defined by, on the long-context kernels.
+// start_pos + i (include/lnb.h).  Always one multi-row call: 16 or more rows on the matrix-core kernel, fewer (or head_dim 32) on the row-per-workgroup
+// kernel while the context fits its LDS, and beyond that -- or beyond lnb_ctx_set_rows_attention's threshold -- on the multi-row long-context pair
+// (attn_rows_*_kernel: K and V read once for all rows).  Only when that pair's scratch cannot be allocated do the rows run as the one-token steps they are defined by.
+static int attn_long_scratch(int n, int H, int maxT, double** e_buf, double** z_part, const char* whose, bool quiet = false);
+static bool rows_rpw_invalid() { const int v = knob(Knob::ATTN_ROWS_RPW); return v != 1 && v != 2 && v != 4; }     // (attn_rows_pv_kernel's instantiations)
 static int forward_append_impl(lnb_ctx* c, const char* name, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out, const ScoreReq* sc) {
     if (!tokens) return fail("%s: null argument (tokens)", name);
     if (seq <= 0) return fail("%s: seq must be positive (got %d)", name, seq);
@@ -1182,14 +1197,25 @@ static int forward_append_impl(lnb_ctx* c, const char* name, const int32_t* toke
     if (T > c->seq_len) return fail("%s: position %d is beyond the KV cache of %d", name, T, c->seq_len);
     if (seq > c->max_rows) return fail("%s: a call of %d rows on a context whose activation buffers hold %d rows (lnb_ctx_create_long's max_rows)", name, seq, c->max_rows);
     const bool mfma_attn = use_mfma(seq) && (m->head_dim == 64 || m->head_dim == 128);
-    if (seq == 1 || (!mfma_attn && T > c->attn_short_cap)) {
+    // the multi-row long-context pair: its 16-row scratch is the verify passes', allocated here on first need (host side, outside any capture)
+    // (no room for it: tried once per context, no error recorded -- the call succeeds on the one-token steps below)
+    c->last_append_form = 0;
+    bool rows = seq > 1 && !mfma_attn && T > std::min(c->rows_T, c->attn_short_cap) && !c->rows_no_scratch;
+    if (rows && rows_rpw_invalid()) return fail("%s: LNB_ATTN_ROWS_RPW=%d is not a form of the multi-row long-context attention (1, 2 or 4)", name, knob(Knob::ATTN_ROWS_RPW));
+    if (rows && attn_long_scratch(LNB_MAX_DRAFT + 1, m->a.n_heads, c->seq_len, &c->sp_e_buf, &c->sp_z_part, "a multi-row append", true)) { c->rows_no_scratch = true; rows = false; }
+    if (seq == 1 || (!rows && !mfma_attn && T > c->attn_short_cap)) {
         for (int i = 0; i < seq; i++) {
             ScoreReq s1{}; if (sc) s1 = ScoreReq{sc->targets + i, sc->tlogit + i, sc->tprob + i, sc->log_z + i};
             if (forward_stage_impl(c, tokens + i, 1, start_pos + i, logits_out ? logits_out + (size_t)i * V : nullptr, i == seq - 1 ? argmax_last_out : nullptr, sc ? &s1 : nullptr)) return -1;
         }
+        c->last_append_form = seq == 1 ? 0 : 3;
         return 0;
     }
-    return forward_stage_impl(c, tokens, seq, start_pos, logits_out, argmax_last_out, sc, true);
+    c->attn_rows = rows;
+    const int rc = forward_stage_impl(c, tokens, seq, start_pos, logits_out, argmax_last_out, sc, true);
+    c->attn_rows = false;
+    if (rc == 0) c->last_append_form = rows ? 4 : mfma_attn ? 2 : 1;
+    return rc;
 }
 extern "C" int lnb_forward_append(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out) {
     return forward_append_impl(c, "lnb_forward_append", tokens, seq, start_pos, logits_out, argmax_last_out, nullptr);
@@ -1564,6 +1590,8 @@ struct lnb_batch {
     int attn_long_T = 0x7FFFFFFF, force_zseq = 0, last_form = 0;
     double* e_buf = nullptr; double* z_part = nullptr;
     hipGraphExec_t graph_long = nullptr, stage_graph_long = nullptr;
+    // a verify batch whose columns run the multi-row long-context pair (lnb_ctx_set_rows_attention, flags bit 1): a captured graph of its own
+    bool attn_rows = false; int rows_zseq = 0; hipGraphExec_t graph_rows = nullptr;
     bool rows_form = false;                // the model carries no matrix-core copy: every product runs as ROWS of gemm_stream_kernel on the resident layouts, whatever n
     // pipeline stage (lnb_pipeline_tick_batch): the contiguous token words exchanged between the last and the first stage, the stage step
     // as a captured graph, events towards / from the exchange stream (as lnb_ctx has them for single-sequence ticks)
@@ -1622,6 +1650,7 @@ extern "C" int lnb_batch_destroy(lnb_batch* b) {
     if (b->counted) for (lnb_ctx* c : b->ctxs) c->batch_users--;
     if (b->graph) hipGraphExecDestroy(b->graph);
     if (b->graph_long) hipGraphExecDestroy(b->graph_long);
+    if (b->graph_rows) hipGraphExecDestroy(b->graph_rows);
     if (b->stage_graph_long) hipGraphExecDestroy(b->stage_graph_long);
     if (b->scratch_owned) { hipFree(b->e_buf); hipFree(b->z_part); }
     hipFree(b->tab); hipFree(b->kv); hipFree(b->x); hipFree(b->h); hipFree(b->xt); hipFree(b->q); hipFree(b->att_xt); hipFree(b->ffn_xt); hipFree(b->logits);
@@ -1727,13 +1756,14 @@ extern "C" int lnb_batch_create(lnb_ctx* const* ctxs, int n, lnb_batch** out) {
 // (default: never -- a batch that fits the short kernels runs exactly what it ran before the long form existed).
 static bool batch_want_long(const lnb_batch* b, int max_pos) { return b->must_long || max_pos + 1 > b->attn_long_T; }
 // the e_buf [n][H][maxT] / z_part [n][H][ceil(maxT/256)] scratch of the batched long form (a batch's own, or the one a context's verify batches share)
-static int attn_long_scratch(int n, int H, int maxT, double** e_buf, double** z_part, const char* whose) {
+static int attn_long_scratch(int n, int H, int maxT, double** e_buf, double** z_part, const char* whose, bool quiet) {
     if (*e_buf && *z_part) return 0;
     const size_t rows = (size_t)n * H, eb = rows * (size_t)maxT * 8, zb = rows * (size_t)((maxT + 255) / 256) * 8;
     hipError_t e = hipMalloc((void**)e_buf, eb);
     if (e == hipSuccess) e = hipMalloc((void**)z_part, zb);
     if (e != hipSuccess) {
         hipFree(*e_buf); hipFree(*z_part); *e_buf = nullptr; *z_part = nullptr; (void)hipGetLastError();
+        if (quiet) return -1;                                // (the caller has another way and records nothing)
         return fail("the long-context attention of %s needs %.1f MB of scratch (%d sequences x %d heads x %d positions): %s", whose, (double)(eb + zb) / 1e6,
                     n, H, maxT, hipGetErrorString(e));
     }
@@ -1755,6 +1785,13 @@ static void batch_attn_form(const lnb_batch* b, AttnParams& ap) {
     ap.lds_T = b->lds_T; ap.seq_len = b->attn_long ? b->maxT : b->lds_T;
     ap.longctx = b->attn_long ? 1 : 0; ap.force_zseq = b->attn_long ? (b->force_zseq & 1) : 0;
     ap.e_buf = b->e_buf; ap.z_part = b->z_part;
+}
+// the attention launch of a batched step: a verify batch in the rows form (its columns are consecutive rows of ONE context) runs the multi-row pair
+static hipError_t batch_attn_launch(const lnb_batch* b, AttnParams& ap, hipStream_t st) {
+    batch_attn_form(b, ap);
+    if (!b->attn_rows) return lnbk_attn(&ap, st);
+    ap.seq_len = b->maxT; ap.longctx = 1; ap.force_zseq = b->rows_zseq;
+    return lnbk_attn_rows(&ap, -1, st);
 }
 static StreamParams stream_of(const lnb_batch* b, const uint16_t* w, const uint16_t* xt, int K, int n_rows, int nch) {
     StreamParams p{}; p.w = w; p.xt = xt; p.K = K; p.n_rows = n_rows; p.nch = nch; p.n_chains = ((n_rows + 15) / 16) * nch; p.nseq = b->n; p.dbg = g_dbg;
@@ -1797,8 +1834,7 @@ static int enqueue_batch_kernel_wide(lnb_batch* b, int l, int which) {
             ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
             ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
             ap.zseq_count = b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;
-            batch_attn_form(b, ap);
-            HIPCHK(lnbk_attn(&ap, st)); return 0; }
+            HIPCHK(batch_attn_launch(b, ap, st)); return 0; }
         case K_WO: {
             StreamParams p = pair_of(L.m_wo, b->att_xt, m->q_dim, dim); p.out = b->h; p.res = b->x;
             HIPCHK(lnbk_stream(&p, EPI_RESID, 0, g_num_cus, st)); return 0; }
@@ -1830,8 +1866,7 @@ static int enqueue_batch_kernel_wide(lnb_batch* b, int l, int which) {
         ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
         ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
         ap.zseq_count = b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
-        batch_attn_form(b, ap);
-        HIPCHK(lnbk_attn(&ap, st)); return 0; }
+        HIPCHK(batch_attn_launch(b, ap, st)); return 0; }
     case K_WO: {
         GemmParams g = wide_of(b, L.wo, L.m_wo, b->att_xt, m->q_dim, dim, 1); g.out = b->h; g.res = b->x;
         HIPCHK(lnbk_gemm_stream(&g, EPI_RESID, g_num_cus, st)); return 0; }
@@ -1868,8 +1903,7 @@ static int enqueue_batch_kernel(lnb_batch* b, int l, int which) {
         ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
         ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
         ap.zseq_count = b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
-        batch_attn_form(b, ap);
-        HIPCHK(lnbk_attn(&ap, st)); return 0; }
+        HIPCHK(batch_attn_launch(b, ap, st)); return 0; }
     case K_WO: {
         StreamParams p = stream_of(b, L.m_wo, b->att_xt, m->q_dim, dim, 1); p.out = b->h; p.res = b->x;
         HIPCHK(lnbk_stream(&p, EPI_RESID, stream_acc2(p), g_num_cus, st)); return 0; }
@@ -2101,6 +2135,27 @@ extern "C" int lnb_ctx_set_batched_attention(lnb_ctx* c, int long_threshold, int
     }
     return 0;
 }
+// lnb_ctx_set_rows_attention: which appends run the multi-row long-context pair, and whether the verify passes do.  Bit 0 of flags is baked into the
+// verify passes' rows graphs, so a change of it drops those (and nothing else); the threshold and bit 1 only pick a form per call.
+extern "C" int lnb_ctx_set_rows_attention(lnb_ctx* c, int long_threshold, int flags) {
+    if (flags & ~3) return fail("flags must be a combination of bit 0 (walk the serial sum) and bit 1 (verify passes) (got %d)", flags);
+    if (!c) return fail("null argument");
+    if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
+    if ((flags & 2) && rows_rpw_invalid()) return fail("LNB_ATTN_ROWS_RPW=%d is not a form of the multi-row long-context attention (1, 2 or 4)", knob(Knob::ATTN_ROWS_RPW));
+    HIPCHK(hipSetDevice(c->m->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (long_threshold >= 0) c->rows_T = long_threshold;
+    if ((flags & 1) != (c->rows_flags & 1))
+        for (lnb_batch* b : c->sp_b) if (b && b->graph_rows) { hipGraphExecDestroy(b->graph_rows); b->graph_rows = nullptr; }
+    c->rows_flags = flags;
+    return 0;
+}
+// the attention of the last lnb_forward_append / lnb_forward_score_append: 0 none yet or one row, 1 row-per-workgroup, 2 matrix cores, 3 one-token steps, 4 the multi-row long-context pair
+extern "C" int lnb_ctx_append_attention_form(const lnb_ctx* c, int* out) {
+    if (!c || !out) return fail("null argument");
+    *out = c->last_append_form;
+    return 0;
+}
 extern "C" int lnb_ctx_verify_attention_form(const lnb_ctx* c, int* out) {
     if (!c || !out) return fail("null argument");
     *out = c->sp_last_form;
@@ -2158,9 +2213,10 @@ static int spec_alloc(lnb_ctx* c, int text_len) {
 }
 // the verify batch of width w, its graph captured on first use: embedding gather of the w column tokens, the blocks, the head, the
 // columns' argmax, the commit.  With the matrix-core copy the products are its column forms, without it rows of gemm_stream_kernel.
-// long_form: the pass runs the long-context pair (one graph per form and width); its scratch is the context's, shared by all widths
-static int spec_verify_batch(lnb_ctx* c, int w, bool long_form, lnb_batch** out) {
+// form 1: the pass runs the long-context pair, 2: the multi-row pair (one graph per form and width); their scratch is the context's, shared by all widths
+static int spec_verify_batch(lnb_ctx* c, int w, int form, lnb_batch** out) {
     lnb_model* m = c->m;
+    const bool long_form = form != 0;
     if (long_form && attn_long_scratch(LNB_MAX_DRAFT + 1, m->a.n_heads, c->seq_len, &c->sp_e_buf, &c->sp_z_part, "the verify passes")) return -1;   // (host side of the call, outside any capture)
     lnb_batch* b = c->sp_b[w];
     const bool fresh = !b;
@@ -2174,8 +2230,8 @@ static int spec_verify_batch(lnb_ctx* c, int w, bool long_form, lnb_batch** out)
         c->sp_b[w] = b;
     }
     b->e_buf = c->sp_e_buf; b->z_part = c->sp_z_part;
-    b->attn_long = long_form;
-    hipGraphExec_t* const gslot = long_form ? &b->graph_long : &b->graph;
+    b->attn_long = long_form; b->attn_rows = form == 2; b->rows_zseq = c->rows_flags & 1;
+    hipGraphExec_t* const gslot = form == 2 ? &b->graph_rows : long_form ? &b->graph_long : &b->graph;
     if (*gslot) { *out = b; return 0; }
     auto drop = [&]() { if (fresh) { c->sp_b[w] = nullptr; lnb_batch_destroy(b); } };
     hipGraph_t g = nullptr;
@@ -2254,9 +2310,10 @@ extern "C" int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, 
             lnb_batch* b = nullptr;
             // the pass's last column sits at start_pos + n_out + k: the long form when the context is beyond the one-workgroup kernels' reach or past the threshold
             const bool lf = c->seq_len > c->attn_short_cap || start_pos + n_out + k + 1 > c->sp_attn_long_T;
-            if (spec_verify_batch(c, k + 1, lf, &b)) return -1;
-            HIPCHK(hipGraphLaunch(lf ? b->graph_long : b->graph, st));
-            c->sp_last_form = lf ? 1 : 0; b->last_form = c->sp_last_form;
+            const int form = !lf ? 0 : (c->rows_flags & 2) ? 2 : 1;     // (2: lnb_ctx_set_rows_attention's opt-in -- K and V read once for all columns)
+            if (spec_verify_batch(c, k + 1, form, &b)) return -1;
+            HIPCHK(hipGraphLaunch(form == 2 ? b->graph_rows : lf ? b->graph_long : b->graph, st));
+            c->sp_last_form = form; b->last_form = lf ? 1 : 0;
             s.verify_passes++; s.drafted += k;
         }
         HIPCHK(lnbk_ngram_draft(&dp, st));

@@ -160,6 +160,19 @@ struct AttnParams {
                                 // step at st->pos + i); 0 = the reference's [S,S] mask broadcast by modulo (lnb_forward).  Set by the entry point, never inferred from the position
     int head_major;             // batched dense grid: 1 = head-major dispatch order inside an XCD (the round-3 order), 0 = sequence-major (the heads of a KV head back to back)
 };
+// long-context attention for W consecutive query rows of ONE context (attn_rows_scores_kernel + attn_rows_pv_kernel): row i of the launch is the
+// one-token step at position pos + i, its K / V row already written by the layer's wq|wk|wv launch.  a carries what the long pair takes (q, caches,
+// out / out_xt, H, KVH, hd, seq_len, divisor, force_zseq, zseq_count, touch, st or btab) with e_buf [16][H][seq_len] / z_part [16][H][ceil(seq_len / 256)]:
+// scratch row = the row's index IN THE LAUNCH, so one 16-row scratch serves every group of a longer call (the launches are stream-ordered).
+constexpr int LNB_ATTN_ROWS_MAX = 16;      // rows per launch
+struct AttnRowsParams {
+    AttnParams a;
+    int W;                      // rows of this launch, 1 .. LNB_ATTN_ROWS_MAX
+    int row0;                   // the launch's first row in the call: q / out row row0 + i (out_xt: column row0 + i)
+    int pos0;                   // position of the CALL's first row as the host knows it (lnb_forward_append); < 0: read on the device -- a.btab->st[0]->pos
+                                // (a verify pass: its columns alias one context, column 0 carries the context's own state) or a.st->pos -- so a captured graph serves every position
+    int pos_off;                // ... + pos_off = the position of this launch's first row
+};
 
 // ---- batched exact decode: up to 16 independent sequences per pass over the weights (lnb_batch_kernels.h) --------------------------
 // v_mfma_f32_16x16x4_f32 IS the reference's k-ordered chain (NOTES.md 5.6); its 16 batch columns carry 16 SEQUENCES' decode tokens,

@@ -3460,6 +3460,226 @@ template <int HD, bool BATCH = false> __global__ __launch_bounds__(ALP_NT) void 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Long-context attention for W <= 16 CONSECUTIVE query rows of one context (lnb_forward_append of 2..15 rows beyond the row-per-workgroup
+// kernel's reach; opt-in: the verify passes of the speculative loop).  Row i sits at position pos + i and attends to j <= pos + i: it is
+// the one-token step at that position, and its arithmetic is attn_long_scores_kernel + the lazily certified PV pass for T_i = pos + i + 1,
+// operation for operation.  What changes is who reads K and V: the batched long pair takes the rows as grid.z and reads every K and V row
+// once per query row; here
+//   attn_rows_scores_kernel  grid (H, blocks of 256 positions): a thread loads its K row ONCE and runs W chains against the W query
+//       vectors in the LDS (f32, W * HD * 4 bytes); e_buf[i][h][j] for j < T_i, one tree sum per (row, block) in attn_long_scores_kernel's
+//       fixed shape (positions >= T_i contribute +0); a block past the last row's T returns at once; the V touch once per block.
+//   attn_rows_pv_kernel<HD, RPW>  grid (H, hd / 16, ceil(W / RPW)): a workgroup serves RPW rows of one (head, 16-dim slice); a producer
+//       thread loads a V row once and turns it into RPW products (p_j of each row evaluated right there: alp_lazy_body's scheme, so the
+//       LDS holds product rings only and does not depend on the context length), the adder waves walk the RPW chains one after the
+//       other.  RPW 1: two ring slots of 512 positions (64 KB); RPW 2 / 4: slots of 256 positions (32 KB per row) -- the producers keep four
+//       batches of V rows and RPW e_j per row in registers, and at 512 positions two rows of them no longer fit the 256 VGPRs of a wave.
+// Certification per row with the band for ITS T_i (cert_z); if any element of any of the workgroup's rows fails (or force_zseq), the
+// workgroup walks every row's serial sum (wave r walks row r) and runs the pass again with the exact sums.  A certified p_j has the
+// reference's bits whether the one-token step formed it in its eager (T <= 1024) or its lazy body, so one body serves every T here.
+// Scratch row = the row's index in the launch (AttnRowsParams).
+// ------------------------------------------------------------------------------------------------
+DEVINL int ar_pos(const AttnRowsParams& rp) { return (rp.pos0 >= 0 ? rp.pos0 : rp.a.btab ? rp.a.btab->st[0]->pos : rp.a.st->pos) + rp.pos_off; }
+DEVINL int ar_T(const AttnRowsParams& rp, int pos, int i) { const int T = pos + i + 1; return T < 1 ? 1 : (T > rp.a.seq_len ? rp.a.seq_len : T); }      // (clamped into the cache, as al_seq does)
+// (a verify pass carries the context's caches of the layer in its batch table: every column has the same)
+DEVINL const uint16_t* ar_ck(const AttnParams& p) { return p.btab ? p.bkv->ck[0] : p.cache_k; }
+DEVINL const uint16_t* ar_cv(const AttnParams& p) { return p.btab ? p.bkv->cv[0] : p.cache_v; }
+DEVINL void ar_store(const AttnRowsParams& rp, int row, int h, int hd_, int d, float acc) {
+    const AttnParams& p = rp.a;
+    if (p.out_xt) p.out_xt[xt_group(row, p.H * hd_) + xt_index(row & 15, h * hd_ + d)] = bf_trunc(acc);
+    else p.out[((size_t)row * p.H + h) * hd_ + d] = bf_trunc(acc);
+}
+template <int HD> __global__ __launch_bounds__(ALS_NT) void attn_rows_scores_kernel(AttnRowsParams rp) {
+    constexpr int NK = HD / 8;
+    __shared__ __attribute__((aligned(16))) float qf[LNB_ATTN_ROWS_MAX * HD];
+    __shared__ double wsum[LNB_ATTN_ROWS_MAX][ALS_NT / 64];
+    const AttnParams& p = rp.a;
+    const int tid = threadIdx.x;
+    int h, blk; xcd_head_block(h, blk);
+    const int W = rp.W, pos = ar_pos(rp), j0 = blk * ALS_NT;
+    const int Tl = ar_T(rp, pos, W - 1);                     // the last row's T: the rows' lengths ascend
+    if (j0 >= Tl) return;                                    // (uniform)
+    const int kvh = h / (p.H / p.KVH);
+    const uint4* kbase = (const uint4*)ar_ck(p) + (size_t)kvh * NK * p.seq_len;
+    const int j = j0 + tid;
+    uint4 k[NK];
+    attn_load_k<NK>(k, kbase, p.seq_len, j < Tl ? j : Tl - 1);
+    unsigned vt;                                             // the V touch of attn_long_scores_kernel, once per block (for the longest row)
+    {
+        constexpr int LPR = HD / 64 > 0 ? HD / 64 : 1;
+        const int l = ((h % (p.H / p.KVH)) % LPR) * ALS_NT + tid;
+        int jl = j0 + l / LPR; jl = jl < Tl ? jl : Tl - 1;
+        const char* va = (const char*)ar_cv(p) + ((size_t)jl * p.KVH + kvh) * HD * 2 + (l % LPR) * 128;
+        va = p.touch ? va : (const char*)kbase;
+        asm volatile("global_load_dword %0, %1, off ; RING_LOAD (never retired: tools/isa_audit.py flags any later use of the register)" : "=v"(vt) : "v"(va));
+    }
+    for (int x = tid; x < W * HD; x += ALS_NT) qf[x] = bf_wide(p.q[((size_t)(rp.row0 + x / HD) * p.H + h) * HD + x % HD]);
+    __syncthreads();
+    const size_t nblk_max = (size_t)((p.seq_len + ALS_NT - 1) / ALS_NT);
+    for (int i = 0; i < W; i++) {
+        const int Ti = ar_T(rp, pos, i);
+        if (j0 >= Ti) continue;                              // (uniform: this row has no position in the block, the PV pass reads no partial sum of it)
+        double ev = 0.0;
+        if (j < Ti) { ev = attn_score_value<NK>(k, qf + i * HD, p.divisor); p.e_buf[((size_t)i * p.H + h) * p.seq_len + j] = ev; }
+        ev = wave_sum_f64(ev);                               // attn_long_scores_kernel's tree
+        if ((tid & 63) == 0) wsum[i][tid >> 6] = ev;
+    }
+    __syncthreads();
+    if (tid < W && j0 < ar_T(rp, pos, tid)) p.z_part[((size_t)tid * p.H + h) * nblk_max + blk] = (wsum[tid][0] + wsum[tid][1]) + (wsum[tid][2] + wsum[tid][3]);
+    asm volatile("" :: "v"(vt));
+}
+
+template <int RPW> struct ArCfg { static constexpr int B = RPW >= 2 ? 256 : 512, NR = B / 128, SLOT = ALP_DS * B; };      // positions per ring slot, 128-position rounds, floats per slot
+__host__ __device__ inline size_t ar_lds_bytes(int rpw) { return (size_t)rpw * 2 * ALP_DS * (rpw >= 2 ? 256 : 512) * 4 + 64; }
+template <int HD, int RPW> __global__ __launch_bounds__(ALP_NT) void attn_rows_pv_kernel(AttnRowsParams rp) {
+    constexpr int B = ArCfg<RPW>::B, NR = ArCfg<RPW>::NR, SLOT = ArCfg<RPW>::SLOT;
+    static_assert(RPW <= 4, "zsh holds four walked sums and the flag in 64 bytes; the serial walk is one wave per row of the adder waves");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const AttnParams& p = rp.a;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int h, ds; xcd_head_block(h, ds);
+    const int g0 = blockIdx.z * RPW;                         // first row of the launch this workgroup serves (g0 < W: the grid is ceil(W / RPW))
+    const int pos = ar_pos(rp);
+    float* ring = (float*)smem;                              // [RPW][2][SLOT] products: [dim][chunk][half][position % 16][4] per slot (alp_lazy_body's)
+    double* zsh = (double*)(ring + (size_t)RPW * 2 * SLOT);  // [RPW] walked serial sums
+    int* const flag = (int*)(zsh + RPW);
+    int T[RPW]; bool on[RPW]; const double* E[RPW];
+    int Tmax = 1;
+#pragma unroll
+    for (int r = 0; r < RPW; r++) {
+        on[r] = g0 + r < rp.W;
+        const int i = on[r] ? g0 + r : rp.W - 1;             // (a row past the launch's last: nothing of it is used; its addresses stay inside the scratch)
+        T[r] = on[r] ? ar_T(rp, pos, i) : 0;
+        if (on[r]) Tmax = T[r];
+        E[r] = p.e_buf + ((size_t)i * p.H + h) * p.seq_len;
+    }
+    const int nbatch = (Tmax + B - 1) / B;
+    const int kvh = h / (p.H / p.KVH);
+    // address-only loads first: the producers' first three batches of e_j and V rows
+    const uint16_t* vbase = ar_cv(p) + (size_t)kvh * HD + (size_t)ds * ALP_DS;
+    const size_t vrow = (size_t)p.KVH * HD;
+    const int pl = tid & 255, half8 = pl & 1, prow = pl >> 1; // producers: 128 positions x two 8-dim halves per round, NR rounds per batch
+    struct Rows { uint4 v[NR]; double e[RPW][NR]; };
+    auto load = [&](Rows& r_, int b) {
+#pragma unroll
+        for (int rr = 0; rr < NR; rr++) {
+            int j = b * B + rr * 128 + prow; j = j < p.seq_len ? j : p.seq_len - 1;        // (clamped to the ARRAY end)
+#pragma unroll
+            for (int r = 0; r < RPW; r++) r_.e[r][rr] = on[r] ? E[r][j] : 0.0;     // (uniform: a row past the launch's last costs no traffic)
+            r_.v[rr] = *(const uint4*)(vbase + (size_t)j * vrow + half8 * 8);
+        }
+    };
+    Rows v0, v1, v2, v3;
+    if (wave >= 4) { load(v0, 0); load(v1, 1); load(v2, 2); }
+    if (tid == 0) *flag = 0;
+    // ---- Z estimates: each row's per-block tree sums in block order (same value in every thread)
+    const size_t nblk_max = (size_t)((p.seq_len + ALS_NT - 1) / ALS_NT);
+    CertZ cz[RPW];
+#pragma unroll
+    for (int r = 0; r < RPW; r++) {
+        double zt = 1.0;
+        if (on[r]) {
+            const int nblk = (T[r] + ALS_NT - 1) / ALS_NT;
+            const double* zp = p.z_part + ((size_t)(g0 + r) * p.H + h) * nblk_max;
+            zt = 0.0;
+            for (int b0 = 0; b0 < nblk; b0 += 64) {
+                const double zmine = zp[b0 + lane < nblk ? b0 + lane : nblk - 1];
+                const int nb = nblk - b0 < 64 ? nblk - b0 : 64;
+                const long long zbits = __double_as_longlong(zmine);
+                for (int b = 0; b < nb; b++) {
+                    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)zbits, b), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(zbits >> 32), b);
+                    zt += __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+                }
+            }
+        }
+        cz[r] = cert_z(zt, T[r]);
+    }
+    __syncthreads();
+    float acc[RPW];
+    int bad = 0;
+    // one pass of PV over all batches for the workgroup's rows; exact == false: p_j = cert_p(e_j) (sets bad), else p_j = trunc(f32(e_j / z_r)) with the walked sums
+    auto run_pv = [&](bool exact) {
+#pragma unroll
+        for (int r = 0; r < RPW; r++) acc[r] = 0.0f;
+        if (wave < 4) {
+            const int d = 4 * wave + (lane >> 4), jj = lane & 15;
+            for (int it = 0; it <= nbatch; it++) {
+                if (it > 0) {
+#pragma unroll
+                    for (int r = 0; r < RPW; r++) {
+                        if (!on[r]) continue;                // (uniform)
+                        const float* src = ring + (size_t)(2 * r + ((it - 1) & 1)) * SLOT + (size_t)d * B + jj * 4;
+                        float4 a0 = *(const float4*)(src), a1 = *(const float4*)(src + 64);
+#pragma unroll
+                        for (int c = 0; c < NR; c++) {
+                            float pr[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+                            if (c < NR - 1) { a0 = *(const float4*)(src + (c + 1) * 128); a1 = *(const float4*)(src + (c + 1) * 128 + 64); }   // in flight behind the 128 adds
+                            asm volatile("" : "+v"(pr[0]), "+v"(pr[1]), "+v"(pr[2]), "+v"(pr[3]), "+v"(pr[4]), "+v"(pr[5]), "+v"(pr[6]), "+v"(pr[7]));
+                            __builtin_amdgcn_sched_barrier(0);
+                            chain128(acc[r], pr);            // j ascending: batches, chunks, then the chunk's 128 positions
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        } else {
+            auto produce = [&](const Rows& r_, int b) {
+                float* dst = ring + (size_t)(b & 1) * SLOT + (size_t)(half8 * 8) * B + ((prow >> 6) & 1) * 64 + (prow & 15) * 4 + ((prow >> 4) & 3);
+#pragma unroll
+                for (int rr = 0; rr < NR; rr++) {            // round rr = chunk rr of the batch; position prow of it
+                    const int j = b * B + rr * 128 + prow;
+                    const uint4 w = r_.v[rr];                // ONE V row, products for every row of the workgroup (exact: 8-bit x 8-bit significands)
+#pragma unroll
+                    for (int r = 0; r < RPW; r++) {
+                        if (!on[r]) continue;
+                        float pj = 0.0f;                     // +0 past the row's end: products +-0, acc is never -0
+                        if (j < T[r]) pj = exact ? alp_p(r_.e[r][rr], zsh[r]) : cert_p(r_.e[r][rr], cz[r], bad);       // impl:506 + ToBFloat16 :493
+                        float* q = dst + (size_t)(2 * r) * SLOT + rr * 128;
+                        q[0 * B] = pj * bf_lo(w.x); q[1 * B] = pj * bf_hi(w.x); q[2 * B] = pj * bf_lo(w.y); q[3 * B] = pj * bf_hi(w.y);
+                        q[4 * B] = pj * bf_lo(w.z); q[5 * B] = pj * bf_hi(w.z); q[6 * B] = pj * bf_lo(w.w); q[7 * B] = pj * bf_hi(w.w);
+                    }
+                }
+            };
+            auto step = [&](int it, const Rows& cur, Rows& nxt) {
+                if (it <= nbatch) {                          // (uniform; one barrier per iteration, like the adders)
+                    if (it < nbatch) { load(nxt, it + 3); produce(cur, it); }
+                    __syncthreads();
+                }
+            };
+            for (int it = 0; it <= nbatch; it += 4) { step(it, v0, v3); step(it + 1, v1, v0); step(it + 2, v2, v1); step(it + 3, v3, v2); }
+        }
+    };
+    if (!p.force_zseq) {
+        run_pv(false);
+        if (bad) *flag = 1;
+        __syncthreads();
+    }
+    if (p.force_zseq || *flag) {
+        // the reference's serial sums, j ascending, f64 (operations_impl.go:492-499): wave r walks row r, 16 values in flight ahead of the adds
+#pragma unroll
+        for (int r = 0; r < RPW; r++) {
+            if (wave != r || !on[r]) continue;
+            double z = 0.0;
+            for (int j0 = 0; j0 < T[r]; j0 += 16) {
+                double v[16];
+#pragma unroll
+                for (int u = 0; u < 16; u++) v[u] = E[r][j0 + u < T[r] ? j0 + u : T[r] - 1];
+#pragma unroll
+                for (int u = 0; u < 16; u++) z += (j0 + u < T[r]) ? v[u] : 0.0;
+            }
+            if (lane == 0) { zsh[r] = z; if (p.zseq_count && ds == 0) atomicAdd(p.zseq_count, 1); }      // once per (row, head)
+        }
+        if (wave >= 4) { load(v0, 0); load(v1, 1); load(v2, 2); }       // the producers' pipeline starts over
+        __syncthreads();
+        run_pv(true);
+    }
+    if (wave < 4 && (lane & 15) == 0) {
+#pragma unroll
+        for (int r = 0; r < RPW; r++) if (on[r]) ar_store(rp, rp.row0 + g0 + r, h, HD, ds * ALP_DS + 4 * wave + (lane >> 4), acc[r]);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // attn_one_kernel (round 6): the long-context decode attention in ONE launch.
 //
 // The two-launch form above pays, per layer at T = 4100: the scores launch (6.3 us), a kernel boundary, and ~8 k cycles at the head of
@@ -4390,6 +4610,35 @@ extern "C" size_t lnbk_attn_one_lds(int seq_len, int hd) { return att1_lds_bytes
 extern "C" size_t lnbk_attn_long_lds(int seq_len) { return alp_lds_bytes(seq_len); }
 // what the PV launch of a context of seq_len positions really requests: lnbk_attn_long_lds up to 160 KB, a constant beyond (alp_pw_floats)
 extern "C" size_t lnbk_attn_long_layout_lds(int seq_len) { return alp_layout_bytes(seq_len); }
+// long-context attention for p->S consecutive rows of one context (attn_rows_*_kernel), any row count: groups of up to 16 rows, launched one
+// after the other on the stream, so the 16-row scratch p->e_buf / p->z_part serves them all.  pos0: the first row's position when the host
+// knows it (the scores grid then ends at the group's last position), < 0: read from the device state (a captured graph: p->btab's column 0, else p->st).
+// Rows per PV workgroup: LNB_ATTN_ROWS_RPW (1 / 2 / 4).
+static int attn_rows_rpw() { const int v = knob(Knob::ATTN_ROWS_RPW); return v == 1 || v == 2 || v == 4 ? v : 0; }      // 0: no such form -- the launch is refused
+static hipError_t launch_attn_rows(const AttnParams* p, int pos0, hipStream_t st) {
+    return with_hd(p, [&](auto HD) {
+        const auto scores = attn_rows_scores_kernel<HD>;
+        const auto pv1 = attn_rows_pv_kernel<HD, 1>, pv2 = attn_rows_pv_kernel<HD, 2>, pv4 = attn_rows_pv_kernel<HD, 4>;
+        if (!p) return raise_lds(pv1, pv2, pv4);
+        const int rpw = attn_rows_rpw();
+        const size_t lds = ar_lds_bytes(rpw);
+        if (rpw == 0 || lds > 160 * 1024 || p->seq_len < 1 || p->seq_len > LNB_SEQ_MAX || p->hd % ALP_DS || !p->e_buf || !p->z_part) return hipErrorInvalidValue;
+        if (p->S < 1 || (!p->out && !p->out_xt) || (pos0 < 0 && !p->btab && !p->st) || pos0 > p->seq_len - p->S) return hipErrorInvalidValue;
+        if (p->btab ? (!p->bkv || p->S > LNB_ATTN_ROWS_MAX) : (!p->cache_k || !p->cache_v)) return hipErrorInvalidValue;       // (a verify pass: one column group)
+        if (!p->q || p->H < 1 || p->KVH < 1 || p->H % p->KVH) return hipErrorInvalidValue;
+        AttnRowsParams rp{};
+        rp.a = *p; rp.a.touch = knob(Knob::ATTN_TOUCH) != 0; rp.pos0 = pos0;
+        for (int row0 = 0; row0 < p->S; row0 += LNB_ATTN_ROWS_MAX) {
+            rp.W = p->S - row0 < LNB_ATTN_ROWS_MAX ? p->S - row0 : LNB_ATTN_ROWS_MAX; rp.row0 = row0; rp.pos_off = row0;
+            const int reach = pos0 >= 0 ? pos0 + row0 + rp.W : p->seq_len;     // positions the group can see
+            hipLaunchKernelGGL(scores, dim3(p->H, (reach + ALS_NT - 1) / ALS_NT), dim3(ALS_NT), 0, st, rp);
+            hipLaunchKernelGGL(rpw == 1 ? pv1 : rpw == 2 ? pv2 : pv4, dim3(p->H, p->hd / ALP_DS, (rp.W + rpw - 1) / rpw), dim3(ALP_NT), lds, st, rp);
+        }
+        return hipGetLastError();
+    });
+}
+extern "C" hipError_t lnbk_attn_rows(const AttnParams* p, int pos0, hipStream_t st) { return p ? launch_attn_rows(p, pos0, st) : hipErrorInvalidValue; }
+extern "C" size_t lnbk_attn_rows_lds(int hd, int rpw) { return (hd == 32 || hd == 64 || hd == 128) && (rpw == 1 || rpw == 2 || rpw == 4) ? ar_lds_bytes(rpw) : 0; }
 
 extern "C" void lnbk_attn_gqa_dbg_dump(void) {
     if (!g_gqa_dbg) return;
@@ -4471,6 +4720,7 @@ extern "C" hipError_t lnbk_init(void) {
         if (rw != 24) gemv(rw, 2, EPI_SILU_MUL, 1);
     }
     for (auto prepare : {launch_attn_long<true>, launch_attn_long<false>, launch_attn_one, launch_attn_short}) if (e == hipSuccess) e = prepare(nullptr, nullptr);
+    if (e == hipSuccess) e = launch_attn_rows(nullptr, -1, nullptr);
     if (e != hipSuccess) return e;
     if (knob(Knob::ATTN_GQA_DBG) && !g_gqa_dbg) { if (hipMalloc(&g_gqa_dbg, 8 * 16 * 8) != hipSuccess) return hipErrorOutOfMemory; (void)hipMemset(g_gqa_dbg, 0, 8 * 16 * 8); }
     done = true;

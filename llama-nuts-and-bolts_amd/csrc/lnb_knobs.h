@@ -33,6 +33,7 @@
     X(ATTN_ONE, 0, ONCE, "1: long-context decode attention in one launch (attn_one_kernel; measured slower); a context beyond lnb_ctx_create's capacity keeps the two launches") \
     X(ATTN_LAZY, 1, LIVE, "0: the long-context PV pass without the lazy certificate (attn_long_pv_kernel); a context beyond lnb_ctx_create's capacity keeps the lazy one") \
     X(ATTN_TOUCH, 1, LIVE, "0: the long-context scores pass does not touch V ahead of the PV pass (A/B)") \
+    X(ATTN_ROWS_RPW, 4, ONCE, "query rows per PV workgroup of the multi-row long-context attention (attn_rows_pv_kernel): 1, 2 or 4 -- any other value makes the calls that would run it fail with a message naming this knob") \
     /* batched decode */ \
     X(BATCH_GROUPS, 1, ONCE, "0: 17..32 sequences decode as rows, not as two column groups") \
     X(STREAM_PAIR, 1, LIVE, "0: thin batched products on the one-wave mfma_stream_kernel, not mfma_pair_kernel") \

@@ -268,7 +268,28 @@ func (ic *InferenceContext) SetBatchedAttention(lt *LlamaTransformer, longThresh
 	return lnbCall(func() C.int { return C.lnb_ctx_set_batched_attention(ic.handle, C.int(longThreshold), C.int(forceZseq)) })
 }
 
-// VerifyAttentionForm reports what the last verify pass ran: 0 the one-workgroup attention kernels, 1 the long-context pair.
+// SetRowsAttention picks which appends run the multi-row long-context attention (lnb_ctx_set_rows_attention): calls of 2..15 rows (any row
+// count at head_dim 32) past longThreshold positions (negative: keep; default: what the row-per-workgroup kernel cannot stage).  flags bit 0:
+// every row walks the serial f64 sum; bit 1: the verify passes of DecodeSpeculativeUntil run it wherever they would run the long form.
+func (ic *InferenceContext) SetRowsAttention(lt *LlamaTransformer, longThreshold int, flags int) error {
+	if err := ic.attach(lt); err != nil {
+		return err
+	}
+	return lnbCall(func() C.int { return C.lnb_ctx_set_rows_attention(ic.handle, C.int(longThreshold), C.int(flags)) })
+}
+
+// AppendAttentionForm reports the attention of the last append: 0 none yet or one row, 1 the row-per-workgroup kernel, 2 the matrix-core
+// kernel, 3 one-token steps inside the call, 4 the multi-row long-context pair.
+func (ic *InferenceContext) AppendAttentionForm(lt *LlamaTransformer) (int, error) {
+	if err := ic.attach(lt); err != nil {
+		return 0, err
+	}
+	var f C.int
+	err := lnbCall(func() C.int { return C.lnb_ctx_append_attention_form(ic.handle, &f) })
+	return int(f), err
+}
+
+// VerifyAttentionForm reports what the last verify pass ran: 0 the one-workgroup attention kernels, 1 the long-context pair, 2 the multi-row pair.
 func (ic *InferenceContext) VerifyAttentionForm(lt *LlamaTransformer) (int, error) {
 	if err := ic.attach(lt); err != nil {
 		return 0, err

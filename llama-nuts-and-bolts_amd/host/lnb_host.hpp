@@ -237,7 +237,10 @@ public:
     // attention form of DecodeSpeculativeUntil's verify passes: past longThreshold positions (default: never, unless the context is beyond the
     // one-workgroup kernels' reach) the long-context kernels; forceZseq: always walk the serial f64 sum.  Same bits either way.
     void SetBatchedAttention(int longThreshold = -1, int forceZseq = 0) { check(lnb_ctx_set_batched_attention(h_, longThreshold, forceZseq)); }
-    int VerifyAttentionForm() const { int f = 0; check(lnb_ctx_verify_attention_form(h_, &f)); return f; }      // 0: one-workgroup kernels, 1: the long-context pair
+    int VerifyAttentionForm() const { int f = 0; check(lnb_ctx_verify_attention_form(h_, &f)); return f; }      // 0: one-workgroup kernels, 1: the long-context pair, 2: the multi-row pair
+    // multi-row long-context attention of appends past longThreshold positions (flags bit 0: serial sums, bit 1: also the verify passes)
+    void SetRowsAttention(int longThreshold = -1, int flags = 0) { check(lnb_ctx_set_rows_attention(h_, longThreshold, flags)); }
+    int AppendAttentionForm() const { int f = 0; check(lnb_ctx_append_attention_form(h_, &f)); return f; }      // 0 none / one row, 1 row-per-workgroup, 2 matrix cores, 3 one-token steps, 4 the multi-row pair
     struct Speculative { std::vector<TokenId> Tokens; bool Finished = false; lnb_spec_stats Stats{}; };
     Speculative DecodeSpeculativeUntil(const std::vector<TokenId>& history, TokenId token, int startPos, int maxSteps) {
         Speculative r; r.Tokens.resize(maxSteps > 0 ? maxSteps : 1);

@@ -68,6 +68,7 @@ EXPORTS = [
     "lnb_ctx_set_draft", "lnb_decode_speculative_until", "lnb_op_ngram_draft",
     "lnb_batch_set_attention", "lnb_ctx_set_batched_attention", "lnb_batch_attention_form", "lnb_ctx_verify_attention_form",
     "lnb_ctx_create_long", "lnb_ctx_max_rows",
+    "lnb_ctx_set_rows_attention", "lnb_ctx_append_attention_form",
 ]
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
 MAX_DRAFT = 15           # LNB_MAX_DRAFT of include/lnb.h (tests/test_speculative_cpu.py compares them)
@@ -179,6 +180,8 @@ def lib():
     L.lnb_ctx_set_batched_attention.argtypes = [vp, C.c_int, C.c_int]
     L.lnb_batch_attention_form.argtypes = [vp, C.POINTER(C.c_int)]
     L.lnb_ctx_verify_attention_form.argtypes = [vp, C.POINTER(C.c_int)]
+    L.lnb_ctx_set_rows_attention.argtypes = [vp, C.c_int, C.c_int]
+    L.lnb_ctx_append_attention_form.argtypes = [vp, C.POINTER(C.c_int)]
     L.lnb_pipeline_tick_batch.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.lnb_pipeline_read_tokens.argtypes = [vp, C.c_int, C.c_int, vp]
     L.lnb_op_linear_mode.argtypes = [C.c_int, vp, vp, C.c_float, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -613,9 +616,23 @@ class InferenceContext:
         return self
 
     def verify_attention_form(self):
-        """0: the last verify pass ran the one-workgroup attention kernels, 1: the long-context pair"""
+        """0: the last verify pass ran the one-workgroup attention kernels, 1: the long-context pair, 2: the multi-row long-context pair"""
         n = C.c_int(0)
         _chk(self.L.lnb_ctx_verify_attention_form(self.h, C.byref(n)))
+        return n.value
+
+    def set_rows_attention(self, long_threshold=-1, flags=0):
+        """multi-row long-context attention (lnb_ctx_set_rows_attention): appends of 2..15 rows (any row count at head_dim 32) past long_threshold
+        positions run it (default: what the row-per-workgroup kernel cannot stage; 0: all of them).  flags bit 0: every row walks the serial
+        f64 sum; bit 1: the verify passes of decode_speculative_until run it wherever they would run the long form.  Same bits."""
+        _chk(self.L.lnb_ctx_set_rows_attention(self.h, int(long_threshold), int(flags)))
+        return self
+
+    def append_attention_form(self):
+        """the attention of the last forward_append / score_append: 0 none yet or one row, 1 row-per-workgroup kernel, 2 matrix-core kernel,
+        3 one-token steps inside the call, 4 the multi-row long-context pair"""
+        n = C.c_int(0)
+        _chk(self.L.lnb_ctx_append_attention_form(self.h, C.byref(n)))
         return n.value
 
     def decode_speculative_until(self, history, token, start_pos, max_steps):

@@ -12,7 +12,9 @@ checked against tests/golden/configs1_tokens.json.
   python tools/spec_bench.py --prefix 4096 [--seq-len N] [--long-threshold N] [--steps 64]
 the verify passes at a long context: a prompt of --prefix tokens, the corpus = the context's own greedy continuation (checked against it),
 rows greedy and width 2 / 8 / 16 only.  --seq-len: the context's capacity (beyond ~7.8 K the passes run the long-context attention);
---long-threshold N: lnb_ctx_set_batched_attention (0 = the long-context form in every verify pass)."""
+--long-threshold N: lnb_ctx_set_batched_attention (0 = the long-context form in every verify pass).
+--rows-attention: every width twice -- the long-context pair with the columns as grid.z (verify_attention_form 1) and the multi-row pair that reads K and V
+once for all columns (lnb_ctx_set_rows_attention flags bit 1, form 2) -- median ms per pass of --reps runs with min..max, next to the one-token step."""
 import argparse
 import json
 import os
@@ -47,16 +49,21 @@ def long_prefix(args):
         _, first = ctx.Forward(prompt, 0, want_logits=False)
         want, _, _ = ctx.decode_greedy_until(first, P, N)
         rows = {}
-        for md in (1, 7, 15):
+        for md, rows_flag in [(md, f) for md in (1, 7, 15) for f in ((0, 2) if args.rows_attention else (None,))]:
             ctx.set_draft(md, 1, 4, want)
+            if rows_flag is not None:
+                ctx.set_rows_attention(-1, rows_flag)
             runs = []
             for rep in range(args.reps + 1):                 # (the first run captures the graphs)
                 out, _, st, ms = ctx.decode_speculative_until(prompt, first, P, N)
                 assert (out == want).all(), "speculative: tokens differ from the greedy run"
                 runs.append(ms)
             ms = statistics.median(runs[1:])
-            rows["width%d" % (md + 1)] = dict(st, hip_event_ms=round(ms, 3), ms_per_pass=round(ms / st["passes"], 4),
-                                              verify_attention_form=ctx.verify_attention_form() if hasattr(ctx, "verify_attention_form") else 0)
+            name = "width%d" % (md + 1) + ("" if rows_flag is None else "_form%d" % (2 if rows_flag else 1))
+            rows[name] = dict(st, hip_event_ms=round(ms, 3), ms_per_pass=round(ms / st["passes"], 4),
+                              verify_attention_form=ctx.verify_attention_form() if hasattr(ctx, "verify_attention_form") else 0)
+            if rows_flag is not None:
+                rows[name].update(ms_per_pass_min=round(min(runs[1:]) / st["passes"], 4), ms_per_pass_max=round(max(runs[1:]) / st["passes"], 4))
         g = [ctx.decode_greedy_until(first, P, N)[2] for _ in range(args.reps)]
         rows["greedy"] = {"ms_per_token": round(statistics.median(g) / N, 4)}
         result["forms"][form] = rows
@@ -78,6 +85,7 @@ def main():
     ap.add_argument("--seq-len", type=int, default=None, help="capacity of the context (default: prompt + steps + 1)")
     ap.add_argument("--long-threshold", type=int, default=None, help="lnb_ctx_set_batched_attention(N)")
     ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--rows-attention", action="store_true", help="with --prefix: each width on the long pair (form 1) and on the multi-row pair (form 2)")
     args = ap.parse_args()
     if args.prefix is not None:
         return long_prefix(args)
