@@ -141,6 +141,38 @@ int lnb_ctx_destroy(lnb_ctx* c);
 int lnb_ctx_reset(lnb_ctx* c);                                       /* zero the caches again */
 /* InferenceContext.CacheK/CacheV[layer] (exported, poked by llamatransformer_simulated_test.go:527-538) */
 int lnb_ctx_read_kv(lnb_ctx* c, int layer, int which /*0=K 1=V*/, uint16_t* host_bf16);
+/* ---- a computed prefix shared between contexts ("a shared prefix followed by per-user text") -------------------------------------------
+ * A KV row depends on the tokens up to it and on nothing a context owns, so the rows one context computed for a text are, bit for bit, the rows
+ * any other context of the same model handle would compute for it: sharing a prefix is a copy, exact by construction.
+ * lnb_ctx_fork: when it returns, the KV rows [0, n_pos) of every layer the stage owns are, in each of the n_dst destinations, the source's bits;
+ *   rows at and beyond n_pos of a destination and the whole source are untouched.  ONE kernel launch (kv_fork_kernel: every source vector is
+ *   read once and stored to every destination); LNB_FORK_COPY=1 runs the same contract on the copy engine.  Nothing else is copied -- not the
+ *   token log, the device position, stop ids, draft settings or token-probability logs: every entry point re-establishes the position itself, so
+ *   lnb_forward_append, lnb_decode_greedy[_until], lnb_decode_speculative_until (history = the prefix's tokens) and lnb_batch_* continue a
+ *   destination at n_pos.  Capacities may differ in either direction (lnb_ctx_create_long's included); members of a live batch may be source and
+ *   destinations (a batch holds pointers, not contents); the arithmetic mode does not matter (both modes share the cache).  The call waits for
+ *   the streams of the source and of every destination, copies on the source's stream and returns when the copy has finished; no captured
+ *   graph is dropped.  n_pos == 0 succeeds and copies nothing.
+ *   Refused, each with a message, arguments before any handle is touched: NULL src, dsts or entry; n_dst outside 1..LNB_MAX_FORK; a negative
+ *   n_pos; a destination that is the source or appears twice; a destination of another lnb_model handle (a stage's contexts fork among
+ *   themselves); n_pos beyond the source's or a destination's capacity; a source or destination whose lnb_forward_stage_begin has not been
+ *   ended.  If the call's device table cannot be allocated it fails with every cache as it was.
+ * lnb_ctx_save_prefix / lnb_ctx_load_prefix: the same rows in host memory (a prefix cache in RAM or on disk), by strided copies, no kernel.
+ *   The blob is capacity-independent and deterministic (the same rows always give the same bytes):
+ *     bytes 0..63   header, little-endian: "LNBKV1" and two zero bytes; then 32-bit words: format version (1), n_pos, the stage's part_begin and
+ *                   part_end (lnb_model_create_parts), n_kv_heads, head_dim, the number of cached layers; 28 reserved zero bytes;
+ *     then per cached layer, in layer order: K as [kv head][head_dim/8][n_pos][8] bf16 (the device layout of a context of capacity n_pos),
+ *                   V as [n_pos][n_kv_heads * head_dim] bf16.
+ *   lnb_ctx_prefix_bytes: the blob's size for n_pos positions (64 + cached layers * 2 * n_pos * kv_dim * 2), < 0 on error.
+ *   lnb_ctx_save_prefix refuses a `cap` below that.  lnb_ctx_load_prefix writes rows [0, n_pos) and reports n_pos (n_pos_out may be NULL); it
+ *   refuses, before anything is written: a short or over-long blob, a wrong magic or version, a geometry or stage range that differs from the
+ *   context's model, n_pos beyond the context's capacity.
+ *   The blob carries NO model identity: loading rows that were computed with other weights is the caller's mistake and is not detected. */
+#define LNB_MAX_FORK 128
+int lnb_ctx_fork(lnb_ctx* src, int n_pos, lnb_ctx* const* dsts, int n_dst);
+int64_t lnb_ctx_prefix_bytes(const lnb_ctx* c, int n_pos);
+int lnb_ctx_save_prefix(lnb_ctx* c, int n_pos, void* host, int64_t cap);
+int lnb_ctx_load_prefix(lnb_ctx* c, const void* host, int64_t nbytes, int* n_pos_out);
 /* Arithmetic mode of a context.  LNB_MODE_EXACT (default): every matmul output is the reference's single k-ordered f32 chain
  * (src/ml/operations_lineartransform.go:46-65), every intermediate bit-identical to the Go CPU path.  LNB_MODE_FAST: the same
  * operators and bf16 truncation points with split-K f32 sums (decode) and bf16 matrix-core GEMMs (prefill): HBM / MFMA bound instead

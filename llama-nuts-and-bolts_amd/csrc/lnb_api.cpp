@@ -20,8 +20,10 @@
 #include "../../include/lnb.h"
 #include "lnb_device.h"
 #include "lnb_knobs.h"
+#include "lnb_kvcopy.h"
 #include "lnb_rccl.h"
 static_assert(LNB_MAX_SEQ_LEN == LNB_SEQ_MAX, "lnb.h and lnb_device.h disagree on the longest context");
+static_assert(LNB_MAX_FORK == KVC_MAX_DST, "lnb.h and lnb_kvcopy.h disagree on the destinations of a fork");
 static_assert(LNB_MAX_TOP_K == LNB_TOKPROB_MAX_K, "lnb.h and lnb_device.h disagree on the largest top-k");
 static_assert(LNB_MAX_DRAFT == LNB_SPEC_MAX_DRAFT && LNB_MAX_DRAFT + 1 <= LNB_STREAM_COLS, "a verify pass is one column group of at most 16 columns");
 
@@ -63,6 +65,7 @@ hipError_t lnbk_token_probs(const TokProbParams* p, hipStream_t st);
 hipError_t lnbk_spec_argmax(const uint16_t* logits, int V, int w, int32_t* g, hipStream_t st);
 hipError_t lnbk_spec_commit(const int32_t* g, int w, const BatchTab* tab, hipStream_t st);
 hipError_t lnbk_ngram_draft(const DraftParams* p, hipStream_t st);
+hipError_t lnbk_kv_fork(const KvForkTab* tab, int nt, int split, hipStream_t st);
 }
 
 // The HIP runtime spreads a process's streams over a fixed number of hardware queues (its default: 4) and streams that share a queue run one
@@ -208,6 +211,7 @@ struct lnb_ctx {
     int rows_T = 0, rows_flags = 0, last_append_form = 0;
     bool attn_rows = false;                // set by lnb_forward_append around a multi-row call that runs the pair
     bool rows_no_scratch = false;          // an append could not allocate the pair's scratch: such calls run as one-token steps from then on
+    void* fork_tab = nullptr; size_t fork_tab_bytes = 0;   // lnb_ctx_fork with this context as the source: the device table of the call, grown on demand
 };
 // Every path that rewrites the device-side StepState goes through here, so that the pipeline tick's "the graph left pos+1 behind, skip
 // the set_state launch" shortcut (dev_pos) can never act on a position some OTHER entry point has since overwritten (lnb_forward,
@@ -734,7 +738,7 @@ extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
     if (c->ev_sent) hipEventDestroy(c->ev_sent);
     if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
     hipFree(c->e_buf); hipFree(c->z_part); hipFree(c->zseq_count); hipFree(c->attn_cnt); if (c->score_idx) hipFree(c->score_idx);
-    tp_free(c); if (c->sc_buf) hipFree(c->sc_buf);
+    tp_free(c); if (c->sc_buf) hipFree(c->sc_buf); if (c->fork_tab) hipFree(c->fork_tab);
     spec_free(c);
     for (auto p : c->ck) if (p) hipFree(p);
     for (auto p : c->cv) if (p) hipFree(p);
@@ -772,6 +776,166 @@ extern "C" int lnb_ctx_read_kv(lnb_ctx* c, int layer, int which, uint16_t* host)
         for (int kh = 0; kh < KVH; kh++)
             for (int d = 0; d < hd; d++)
                 host[(size_t)j * c->m->kv_dim + kh * hd + d] = raw[(((size_t)kh * nk + (d >> 3)) * c->seq_len + j) * 8 + (d & 7)];
+    return 0;
+}
+
+// ---- a computed prefix shared between contexts: lnb_ctx_fork, lnb_ctx_save_prefix / lnb_ctx_load_prefix (include/lnb.h, lnb_kvcopy.h) ----------------
+// A KV row depends on the tokens up to it and on nothing a context owns, so the rows [0, n_pos) of one context ARE the rows any
+// other context of the same model would compute for that text: sharing them is a copy.  Nothing but cache rows moves -- every entry point
+// re-establishes the device position itself -- and no captured graph bakes in cache CONTENTS, so none is dropped.
+static int cached_layers(const lnb_ctx* c) { int n = 0; for (auto p : c->ck) n += p != nullptr; return n; }
+extern "C" int lnb_ctx_fork(lnb_ctx* src, int n_pos, lnb_ctx* const* dsts, int n_dst) {
+    if (!src || !dsts) return fail("null argument");
+    if (n_dst < 1 || n_dst > LNB_MAX_FORK) return fail("n_dst %d is outside 1..%d", n_dst, LNB_MAX_FORK);
+    if (n_pos < 0) return fail("negative n_pos %d", n_pos);
+    for (int d = 0; d < n_dst; d++) {
+        if (!dsts[d]) return fail("destination %d is NULL", d);
+        if (dsts[d] == src) return fail("destination %d is the source", d);
+        for (int e = 0; e < d; e++) if (dsts[e] == dsts[d]) return fail("destinations %d and %d are the same context", e, d);
+    }
+    if (n_pos > src->seq_len) return fail("n_pos %d is beyond the source's %d positions", n_pos, src->seq_len);
+    if (src->pending) return fail("source: a lnb_forward_stage_begin has not been ended");
+    for (int d = 0; d < n_dst; d++) {
+        if (dsts[d]->m != src->m) return fail("destination %d belongs to another lnb_model handle: a stage's contexts fork among themselves", d);
+        if (n_pos > dsts[d]->seq_len) return fail("n_pos %d is beyond the %d positions of destination %d", n_pos, dsts[d]->seq_len, d);
+        if (dsts[d]->pending) return fail("destination %d: a lnb_forward_stage_begin has not been ended", d);
+    }
+    const lnb_model* m = src->m;
+    const int n_arrays = 2 * cached_layers(src);
+    if (n_pos == 0 || n_arrays == 0) return 0;
+    HIPCHK(hipSetDevice(m->device));
+    const bool engine = knob(Knob::FORK_COPY) != 0;
+    const size_t ptr_bytes = (size_t)n_arrays * (size_t)(1 + n_dst) * sizeof(void*), tab_bytes = ptr_bytes + (size_t)n_dst * sizeof(int);
+    if (!engine && src->fork_tab_bytes < tab_bytes) {              // before any stream is touched: a failure here leaves everything as it was
+        void* t = nullptr;
+        if (hipMalloc(&t, tab_bytes) != hipSuccess) { (void)hipGetLastError(); return fail("no device memory for the fork table (%zu bytes)", tab_bytes); }
+        if (src->fork_tab) { hipStreamSynchronize(src->stream); (void)hipFree(src->fork_tab); }      // (the old table: nothing of a finished call reads it)
+        src->fork_tab = t; src->fork_tab_bytes = tab_bytes;
+    }
+    HIPCHK(hipStreamSynchronize(src->stream));
+    for (int d = 0; d < n_dst; d++) HIPCHK(hipStreamSynchronize(dsts[d]->stream));
+    if (engine) {
+        const size_t runs = kvc_runs(0, m->kv_dim), width = kvc_byte_offset(kvc_run_len(0, m->kv_dim, n_pos)), v_bytes = kvc_byte_offset(kvc_run_len(1, m->kv_dim, n_pos));
+        for (size_t l = 0; l < src->ck.size(); l++) {
+            if (!src->ck[l]) continue;
+            for (int d = 0; d < n_dst; d++) {
+                HIPCHK(hipMemcpy2DAsync(dsts[d]->ck[l], kvc_byte_offset(kvc_stride(0, dsts[d]->seq_len)), src->ck[l], kvc_byte_offset(kvc_stride(0, src->seq_len)),
+                                        width, runs, hipMemcpyDeviceToDevice, src->stream));
+                HIPCHK(hipMemcpyAsync(dsts[d]->cv[l], src->cv[l], v_bytes, hipMemcpyDeviceToDevice, src->stream));
+            }
+        }
+        HIPCHK(hipStreamSynchronize(src->stream));
+        return 0;
+    }
+    std::vector<char> host(tab_bytes);
+    const void** hp = (const void**)host.data();
+    int* hc = (int*)(host.data() + ptr_bytes);
+    size_t a = 0;
+    for (size_t l = 0; l < src->ck.size(); l++) {
+        if (!src->ck[l]) continue;
+        for (int which = 0; which < 2; which++, a++) {
+            const void** row = hp + a * (size_t)(1 + n_dst);
+            row[0] = which ? src->cv[l] : src->ck[l];
+            for (int d = 0; d < n_dst; d++) row[1 + d] = which ? dsts[d]->cv[l] : dsts[d]->ck[l];
+        }
+    }
+    for (int d = 0; d < n_dst; d++) hc[d] = dsts[d]->seq_len;
+    // (the upload reads `host`: every way out of this function from here on goes through a stream synchronise first)
+    const hipError_t up = hipMemcpyAsync(src->fork_tab, host.data(), tab_bytes, hipMemcpyHostToDevice, src->stream);
+    if (up != hipSuccess) { hipStreamSynchronize(src->stream); return fail("uploading the fork table failed: %s", hipGetErrorString(up)); }
+    KvForkTab tab;
+    tab.ptrs = (const void* const*)src->fork_tab; tab.cap_dst = (const int*)((const char*)src->fork_tab + ptr_bytes);
+    tab.n_arrays = n_arrays; tab.n_dst = n_dst; tab.kv_dim = m->kv_dim; tab.n_pos = n_pos; tab.cap_src = src->seq_len;
+    const hipError_t launched = lnbk_kv_fork(&tab, knob(Knob::FORK_NT), knob(Knob::FORK_SPLIT), src->stream);
+    HIPCHK(hipStreamSynchronize(src->stream));
+    if (launched != hipSuccess) return fail("kv_fork_kernel could not be launched: %s", hipGetErrorString(launched));
+    return 0;
+}
+
+// The saved prefix: a 64-byte little-endian header, then per cached layer K as [kv head][head_dim/8][n_pos][8] (the device layout of a context of
+// capacity n_pos) and V as [n_pos][kv_dim].  Header: bytes 0..7 "LNBKV1" + two zero bytes, then seven 32-bit words -- format version, n_pos, part_begin, part_end,
+// n_kv_heads, head_dim, cached layers -- and 28 reserved zero bytes.
+#define LNB_KV_BLOB_HEADER 64
+#define LNB_KV_BLOB_VERSION 1
+static const char LNB_KV_MAGIC[8] = {'L', 'N', 'B', 'K', 'V', '1', 0, 0};
+static void put_le32(unsigned char* p, uint32_t v) { p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); p[2] = (unsigned char)(v >> 16); p[3] = (unsigned char)(v >> 24); }
+static uint32_t get_le32(const unsigned char* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+static int64_t prefix_bytes(const lnb_ctx* c, int n_pos) { return LNB_KV_BLOB_HEADER + (int64_t)cached_layers(c) * (int64_t)kvc_layer_bytes(c->m->kv_dim, n_pos); }
+extern "C" int64_t lnb_ctx_prefix_bytes(const lnb_ctx* c, int n_pos) {
+    if (!c) return fail("null argument");
+    if (n_pos < 0 || n_pos > c->seq_len) return fail("n_pos %d is outside the context's 0..%d positions", n_pos, c->seq_len);
+    return prefix_bytes(c, n_pos);
+}
+// the strided copies of one cached layer between the device caches and the blob's arrays at p (to_host: device -> blob)
+static int prefix_copy_layer(lnb_ctx* c, size_t l, int n_pos, unsigned char* p, bool to_host) {
+    const int kv_dim = c->m->kv_dim;
+    const size_t runs = kvc_runs(0, kv_dim), width = kvc_byte_offset(kvc_run_len(0, kv_dim, n_pos)), pitch = kvc_byte_offset(kvc_stride(0, c->seq_len));
+    const size_t v_bytes = kvc_byte_offset(kvc_run_len(1, kv_dim, n_pos));
+    unsigned char* pv = p + runs * width;
+    if (to_host) {
+        HIPCHK(hipMemcpy2DAsync(p, width, c->ck[l], pitch, width, runs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(pv, c->cv[l], v_bytes, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        HIPCHK(hipMemcpy2DAsync(c->ck[l], pitch, p, width, width, runs, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->cv[l], pv, v_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    return 0;
+}
+extern "C" int lnb_ctx_save_prefix(lnb_ctx* c, int n_pos, void* host, int64_t cap) {
+    if (!c || !host) return fail("null argument");
+    if (n_pos < 0 || n_pos > c->seq_len) return fail("n_pos %d is outside the context's 0..%d positions", n_pos, c->seq_len);
+    if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
+    const int64_t need = prefix_bytes(c, n_pos);
+    if (cap < need) return fail("the buffer holds %lld bytes, %d positions take %lld (lnb_ctx_prefix_bytes)", (long long)cap, n_pos, (long long)need);
+    const lnb_model* m = c->m;
+    unsigned char* p = (unsigned char*)host;
+    memset(p, 0, LNB_KV_BLOB_HEADER);
+    memcpy(p, LNB_KV_MAGIC, 8);
+    const uint32_t words[7] = {LNB_KV_BLOB_VERSION, (uint32_t)n_pos, (uint32_t)m->part_begin, (uint32_t)m->part_end, (uint32_t)(m->kv_dim / m->head_dim), (uint32_t)m->head_dim, (uint32_t)cached_layers(c)};
+    for (int i = 0; i < 7; i++) put_le32(p + 8 + 4 * i, words[i]);
+    if (n_pos == 0) return 0;
+    HIPCHK(hipSetDevice(m->device));
+    p += LNB_KV_BLOB_HEADER;
+    for (size_t l = 0; l < c->ck.size(); l++) {
+        if (!c->ck[l]) continue;
+        if (prefix_copy_layer(c, l, n_pos, p, true)) { hipStreamSynchronize(c->stream); return -1; }
+        p += kvc_layer_bytes(m->kv_dim, n_pos);
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+extern "C" int lnb_ctx_load_prefix(lnb_ctx* c, const void* host, int64_t nbytes, int* n_pos_out) {
+    if (!c || !host) return fail("null argument");
+    if (nbytes < LNB_KV_BLOB_HEADER) return fail("a saved prefix has a %d-byte header, this blob has %lld bytes", LNB_KV_BLOB_HEADER, (long long)nbytes);
+    const unsigned char* p = (const unsigned char*)host;
+    if (memcmp(p, LNB_KV_MAGIC, 8)) return fail("not a saved prefix: the magic is not LNBKV1");
+    uint32_t w[7];
+    for (int i = 0; i < 7; i++) w[i] = get_le32(p + 8 + 4 * i);
+    if (w[0] != LNB_KV_BLOB_VERSION) return fail("saved prefix of format version %u, this library reads version %d", w[0], LNB_KV_BLOB_VERSION);
+    const lnb_model* m = c->m;
+    if (w[2] != (uint32_t)m->part_begin || w[3] != (uint32_t)m->part_end)
+        return fail("the saved prefix is of stage parts [%u, %u), the context's model of [%d, %d)", w[2], w[3], m->part_begin, m->part_end);
+    if (w[4] != (uint32_t)(m->kv_dim / m->head_dim) || w[5] != (uint32_t)m->head_dim || w[6] != (uint32_t)cached_layers(c))
+        return fail("the saved prefix has %u KV heads of head_dim %u in %u cached layers, the context's model %d of %d in %d", w[4], w[5], w[6],
+                    m->kv_dim / m->head_dim, m->head_dim, cached_layers(c));
+    if (w[1] > (uint32_t)LNB_MAX_SEQ_LEN) return fail("the saved prefix claims %u positions", w[1]);
+    const int n_pos = (int)w[1];
+    const int64_t need = prefix_bytes(c, n_pos);
+    if (nbytes != need) return fail("a saved prefix of %d positions takes %lld bytes, this blob has %lld", n_pos, (long long)need, (long long)nbytes);
+    if (n_pos > c->seq_len) return fail("the saved prefix holds %d positions, the context %d", n_pos, c->seq_len);
+    if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
+    if (n_pos > 0) {
+        HIPCHK(hipSetDevice(m->device));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        p += LNB_KV_BLOB_HEADER;
+        for (size_t l = 0; l < c->ck.size(); l++) {
+            if (!c->ck[l]) continue;
+            if (prefix_copy_layer(c, l, n_pos, (unsigned char*)p, false)) { hipStreamSynchronize(c->stream); return -1; }
+            p += kvc_layer_bytes(m->kv_dim, n_pos);
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    if (n_pos_out) *n_pos_out = n_pos;
     return 0;
 }
 

@@ -4948,3 +4948,19 @@ extern "C" hipError_t lnbk_ngram_draft(const DraftParams* p, hipStream_t st) {
     hipLaunchKernelGGL(ngram_draft_kernel, dim3((unsigned)(p->ngram_max - p->ngram_min + 1)), dim3(256), 0, st, *p);
     return hipGetLastError();
 }
+
+// lnb_ctx_fork: rows [0, n_pos) of every cached layer of one context into 1..KVC_MAX_DST others, one launch (lnb_kvcopy.h).  nt: non-temporal loads and
+// stores; split > 1: that many destination groups over grid.z.  The caller has checked n_pos against every capacity.
+#include "lnb_kvcopy.h"
+extern "C" hipError_t lnbk_kv_fork(const KvForkTab* tab, int nt, int split, hipStream_t st) {
+    if (!tab || tab->n_arrays < 1 || tab->n_arrays > 65535 || tab->n_dst < 1 || tab->n_dst > KVC_MAX_DST || tab->n_pos < 1 || (tab->kv_dim & 7)) return hipErrorInvalidValue;
+    const size_t tk = kvc_tiles(0, tab->kv_dim, tab->n_pos), tv = kvc_tiles(1, tab->kv_dim, tab->n_pos), tmax = tk > tv ? tk : tv;
+    size_t gx = KVC_GRID_CAP / (size_t)tab->n_arrays;
+    if (gx < 1) gx = 1;
+    if (gx > tmax) gx = tmax;
+    const int gz = split > 1 ? (split < tab->n_dst ? split : tab->n_dst) : 1;
+    const dim3 grid((unsigned)gx, (unsigned)tab->n_arrays, (unsigned)gz);
+    if (nt) hipLaunchKernelGGL(kv_fork_kernel<true>, grid, dim3(KVC_THREADS), 0, st, *tab);
+    else hipLaunchKernelGGL(kv_fork_kernel<false>, grid, dim3(KVC_THREADS), 0, st, *tab);
+    return hipGetLastError();
+}

@@ -278,6 +278,67 @@ func (ic *InferenceContext) SetRowsAttention(lt *LlamaTransformer, longThreshold
 	return lnbCall(func() C.int { return C.lnb_ctx_set_rows_attention(ic.handle, C.int(longThreshold), C.int(flags)) })
 }
 
+// ForkPrefix copies this context's KV rows [0, nPos) of every layer into up to 128 (LNB_MAX_FORK) other contexts of the same transformer in one
+// kernel launch (lnb_ctx_fork): a system prompt is prefilled once and shared.  Nothing but cache rows moves; continue each destination at nPos
+// (ForwardAppend, DecodeGreedyUntil, DecodeSpeculativeUntil with the prefix as its history, a batch).  Capacities may differ.
+func (ic *InferenceContext) ForkPrefix(lt *LlamaTransformer, dsts []*InferenceContext, nPos int) error {
+	if len(dsts) == 0 { // &hs[0] of an empty slice panics before the library can refuse the call
+		return fmt.Errorf("ForkPrefix: no destination")
+	}
+	if err := ic.attach(lt); err != nil {
+		return err
+	}
+	hs := make([]*C.lnb_ctx, len(dsts))
+	for i, d := range dsts {
+		if d == nil {
+			return fmt.Errorf("ForkPrefix: destination %d is nil", i)
+		}
+		if err := d.attach(lt); err != nil {
+			return err
+		}
+		hs[i] = d.handle
+	}
+	// (the handles are C memory: a Go slice of C pointers may be passed to C)
+	return lnbCall(func() C.int { return C.lnb_ctx_fork(ic.handle, C.int(nPos), (**C.lnb_ctx)(unsafe.Pointer(&hs[0])), C.int(len(hs))) })
+}
+
+// SavePrefix returns the KV rows [0, nPos) as a capacity-independent blob (lnb_ctx_save_prefix; layout in lnb.h): a prefix cache in host memory
+// or on disk.  The blob carries no model identity -- loading rows that other weights computed is the caller's mistake.
+func (ic *InferenceContext) SavePrefix(lt *LlamaTransformer, nPos int) ([]byte, error) {
+	if err := ic.attach(lt); err != nil {
+		return nil, err
+	}
+	var n C.int64_t
+	if err := lnbCall(func() C.int {
+		n = C.lnb_ctx_prefix_bytes(ic.handle, C.int(nPos))
+		if n < 0 {
+			return -1
+		}
+		return 0
+	}); err != nil {
+		return nil, err
+	}
+	blob := make([]byte, int(n))
+	if err := lnbCall(func() C.int { return C.lnb_ctx_save_prefix(ic.handle, C.int(nPos), unsafe.Pointer(&blob[0]), n) }); err != nil {
+		return nil, err
+	}
+	return blob, nil
+}
+
+// LoadPrefix writes a saved prefix into rows [0, nPos) of this context and returns nPos (lnb_ctx_load_prefix); a blob of another geometry or
+// stage range, a damaged one, or more positions than the context holds are refused before anything is written.
+func (ic *InferenceContext) LoadPrefix(lt *LlamaTransformer, blob []byte) (int, error) {
+	if len(blob) == 0 {
+		return 0, fmt.Errorf("LoadPrefix: empty blob")
+	}
+	if err := ic.attach(lt); err != nil {
+		return 0, err
+	}
+	var n C.int
+	err := lnbCall(func() C.int { return C.lnb_ctx_load_prefix(ic.handle, unsafe.Pointer(&blob[0]), C.int64_t(len(blob)), &n) })
+	return int(n), err
+}
+
 // AppendAttentionForm reports the attention of the last append: 0 none yet or one row, 1 the row-per-workgroup kernel, 2 the matrix-core
 // kernel, 3 one-token steps inside the call, 4 the multi-row long-context pair.
 func (ic *InferenceContext) AppendAttentionForm(lt *LlamaTransformer) (int, error) {

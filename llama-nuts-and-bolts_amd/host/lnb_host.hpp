@@ -241,6 +241,22 @@ public:
     // multi-row long-context attention of appends past longThreshold positions (flags bit 0: serial sums, bit 1: also the verify passes)
     void SetRowsAttention(int longThreshold = -1, int flags = 0) { check(lnb_ctx_set_rows_attention(h_, longThreshold, flags)); }
     int AppendAttentionForm() const { int f = 0; check(lnb_ctx_append_attention_form(h_, &f)); return f; }      // 0 none / one row, 1 row-per-workgroup, 2 matrix cores, 3 one-token steps, 4 the multi-row pair
+    // a computed prefix shared between contexts (include/lnb.h): ForkPrefix copies this context's KV rows [0, nPos) into up to LNB_MAX_FORK contexts of the
+    // same transformer in one launch (nothing else moves: continue each destination at nPos); SavePrefix / LoadPrefix give the rows a life in host memory
+    // (a capacity-independent blob without model identity: loading rows computed with other weights is the caller's mistake)
+    void ForkPrefix(const std::vector<InferenceContext*>& dsts, int nPos) {
+        std::vector<lnb_ctx*> hs;
+        for (auto* d : dsts) hs.push_back(d ? d->h_ : nullptr);
+        check(lnb_ctx_fork(h_, nPos, hs.data(), (int)hs.size()));
+    }
+    std::vector<uint8_t> SavePrefix(int nPos) {
+        const int64_t n = lnb_ctx_prefix_bytes(h_, nPos);
+        check(n < 0 ? -1 : 0);
+        std::vector<uint8_t> blob((size_t)n);
+        check(lnb_ctx_save_prefix(h_, nPos, blob.data(), n));
+        return blob;
+    }
+    int LoadPrefix(const std::vector<uint8_t>& blob) { int n = 0; check(lnb_ctx_load_prefix(h_, blob.data(), (int64_t)blob.size(), &n)); return n; }
     struct Speculative { std::vector<TokenId> Tokens; bool Finished = false; lnb_spec_stats Stats{}; };
     Speculative DecodeSpeculativeUntil(const std::vector<TokenId>& history, TokenId token, int startPos, int maxSteps) {
         Speculative r; r.Tokens.resize(maxSteps > 0 ? maxSteps : 1);

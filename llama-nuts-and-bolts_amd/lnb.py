@@ -69,10 +69,12 @@ EXPORTS = [
     "lnb_batch_set_attention", "lnb_ctx_set_batched_attention", "lnb_batch_attention_form", "lnb_ctx_verify_attention_form",
     "lnb_ctx_create_long", "lnb_ctx_max_rows",
     "lnb_ctx_set_rows_attention", "lnb_ctx_append_attention_form",
+    "lnb_ctx_fork", "lnb_ctx_prefix_bytes", "lnb_ctx_save_prefix", "lnb_ctx_load_prefix",
 ]
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
 MAX_DRAFT = 15           # LNB_MAX_DRAFT of include/lnb.h (tests/test_speculative_cpu.py compares them)
 MAX_SEQ_LEN = 131072     # LNB_MAX_SEQ_LEN of include/lnb.h (tests/test_long_context_cpu.py compares them)
+MAX_FORK = 128           # LNB_MAX_FORK of include/lnb.h (tests/test_prefix_fork_cpu.py compares them)
 ABI_VERSION = 6          # LNB_ABI_VERSION of include/lnb.h this binding was written against (tests/test_cabi.py compares it with the header's)
 
 
@@ -182,6 +184,11 @@ def lib():
     L.lnb_ctx_verify_attention_form.argtypes = [vp, C.POINTER(C.c_int)]
     L.lnb_ctx_set_rows_attention.argtypes = [vp, C.c_int, C.c_int]
     L.lnb_ctx_append_attention_form.argtypes = [vp, C.POINTER(C.c_int)]
+    L.lnb_ctx_fork.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_int]
+    L.lnb_ctx_prefix_bytes.argtypes = [vp, C.c_int]
+    L.lnb_ctx_prefix_bytes.restype = C.c_int64
+    L.lnb_ctx_save_prefix.argtypes = [vp, C.c_int, vp, C.c_int64]
+    L.lnb_ctx_load_prefix.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int)]
     L.lnb_pipeline_tick_batch.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.lnb_pipeline_read_tokens.argtypes = [vp, C.c_int, C.c_int, vp]
     L.lnb_op_linear_mode.argtypes = [C.c_int, vp, vp, C.c_float, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -676,6 +683,30 @@ class InferenceContext:
         am = C.c_int32(-2)
         _chk(self.L.lnb_forward_score_append(self.h, _p(tok) if S else None, S, start_pos, _p(tg), _p(tl), _p(tp), _p(lz), C.byref(am)))
         return tl[:S], tp[:S], lz[:S], am.value
+
+    def ForkPrefix(self, dsts, n_pos):
+        """copy this context's KV rows [0, n_pos) of every layer into the contexts `dsts` (1..MAX_FORK, same transformer, any capacities) in one
+        kernel launch (lnb_ctx_fork).  Nothing else moves: continue each destination at n_pos."""
+        dsts = list(dsts)
+        arr = (C.c_void_p * max(len(dsts), 1))(*[d.h for d in dsts])
+        _chk(self.L.lnb_ctx_fork(self.h, int(n_pos), arr, len(dsts)))
+        return self
+
+    def SavePrefix(self, n_pos):
+        """the KV rows [0, n_pos) as a capacity-independent blob (lnb_ctx_save_prefix; layout in lnb.h) -> numpy uint8 array"""
+        n = self.L.lnb_ctx_prefix_bytes(self.h, int(n_pos))
+        if n < 0:
+            _chk(-1)
+        blob = np.empty(n, dtype=np.uint8)
+        _chk(self.L.lnb_ctx_save_prefix(self.h, int(n_pos), _p(blob), n))
+        return blob
+
+    def LoadPrefix(self, blob):
+        """write a saved prefix into rows [0, n_pos) of this context (lnb_ctx_load_prefix) -> n_pos.  The blob carries no model identity."""
+        b = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, dtype=np.uint8)
+        n = C.c_int(-1)
+        _chk(self.L.lnb_ctx_load_prefix(self.h, _p(b) if b.size else None, int(b.size), C.byref(n)))
+        return n.value
 
     def CacheK(self, layer):
         return self._kv(layer, 0)
