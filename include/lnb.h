@@ -267,6 +267,41 @@ int lnb_ctx_set_rows_attention(lnb_ctx* c, int long_threshold, int flags);
  * 2 the matrix-core kernel, 3 one-token steps inside the call, 4 the multi-row long-context pair */
 int lnb_ctx_append_attention_form(const lnb_ctx* c, int* out);
 
+/* ---- ragged append to many contexts: n contexts extended by n_rows[s] tokens each, in passes of up to 128 rows over the weights -----------
+ * After lnb_ctx_fork has put a shared prefix into many contexts, each of them still needs its own text appended.  One lnb_forward_append per
+ * context walks the weights once per context (and, below 16 rows, once per row); this call packs the rows of ALL members, in member order, into
+ * batched steps of up to 128 columns -- the kernels of lnb_batch_decode, each column the one-token step of one row with its own position, token
+ * and KV caches -- so 256 rows cost two passes over the weights.
+ *   Member s is extended by n_rows[s] tokens at start_pos[s]; tokens is the concatenation of the members' rows in member order (sum(n_rows)
+ *   entries).
+ *   Contract: for every member, the KV rows [start_pos[s], start_pos[s] + n_rows[s]) of every layer, its rows of logits_out
+ *   ([sum(n_rows), vocab_size] f32 in the row order of tokens; may be NULL) and argmax_out[s] (ml.Argmax of its last row; the array may be NULL)
+ *   are BIT-IDENTICAL to lnb_forward_append(ctxs[s], its tokens, n_rows[s], start_pos[s], ...) on a context holding the same rows below
+ *   start_pos[s] -- hence to n_rows[s] one-token steps.  Cache rows below start_pos[s] are read and never written; rows at and beyond
+ *   start_pos[s] + n_rows[s] are untouched.  Nothing else of a member changes (token log, stop ids, draft settings, token-probability logs); its
+ *   cached device position is invalidated, as lnb_batch_decode does.  Afterwards lnb_decode_greedy[_until], lnb_decode_speculative_until,
+ *   lnb_batch_* and further appends continue a member.  Members may have any capacities (lnb_ctx_create_long's included) and may belong to a
+ *   live batch.  A member's max_rows does NOT limit n_rows[s]: the rows live in the call's own buffers (kept in the model handle, created on
+ *   first use, freed by lnb_model_destroy), not in the member's.
+ *   The call waits for every member's stream, runs on a stream of its own and returns when everything has finished.  Calls on one model handle
+ *   serialise on a mutex (two threads with disjoint contexts do not race); lnb_model_enable_batch must not run concurrently with a call.
+ *   How it runs: passes of at most W = LNB_APPEND_MANY_COLS (default 128) columns; a member's rows may straddle two passes, the later one reads
+ *   the KV rows the earlier one wrote.  A pass of up to 16 columns (17..32: two column groups) runs the column forms when lnb_model_enable_batch
+ *   was called, rows of the streaming product otherwise and above 32.  A pass runs the long-context attention pair when one of its members has a
+ *   capacity beyond the one-workgroup kernels' reach (~7800 positions at head_dim 128), else the one-workgroup kernels: same bits.
+ *   Refused, each with a message, arguments before any handle is dereferenced and everything before any cache is written: NULL ctxs, tokens,
+ *   n_rows, start_pos or entry of ctxs; n outside 1..128; an n_rows[s] < 1 or a negative start_pos[s]; a context that appears twice; a pass width
+ *   outside 1..128; members of different lnb_model handles; a handle that is not the whole model; a member in LNB_MODE_FAST; a member with a
+ *   pending lnb_forward_stage_begin; start_pos[s] + n_rows[s] beyond the member's KV cache or the RoPE table; a token id outside the vocabulary
+ *   (checked on the host, the message carries the row index); dim, n_heads*head_dim or the FFN hidden size not a multiple of 128; long-context
+ *   attention scratch that cannot be allocated (the message carries the size).
+ * lnb_model_append_many_info: of the last call on that model handle, the number of passes, the widest pass and the passes that ran the
+ *   long-context attention pair (any pointer may be NULL).
+ * Which calls belong here and which to lnb_forward_append: profiles/append_many.md. */
+int lnb_forward_append_many(lnb_ctx* const* ctxs, int n, const int32_t* tokens, const int32_t* n_rows, const int32_t* start_pos,
+                            float* logits_out, int32_t* argmax_out);
+int lnb_model_append_many_info(const lnb_model* m, int* passes, int* max_columns, int* long_passes);
+
 /* ---- greedy loop on the device: the decode half of InferenceEngine.generateTokensInternal
  * (src/inference/inference.go:194-252).  Starting from `token` at position start_pos (its KV is computed by
  * the first step), runs n_steps one-token Forward+Argmax steps as replays of one captured hipGraph without

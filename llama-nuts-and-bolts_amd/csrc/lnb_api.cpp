@@ -21,8 +21,10 @@
 #include "lnb_device.h"
 #include "lnb_knobs.h"
 #include "lnb_kvcopy.h"
+#include "lnb_rowpack.h"
 #include "lnb_rccl.h"
 static_assert(LNB_MAX_SEQ_LEN == LNB_SEQ_MAX, "lnb.h and lnb_device.h disagree on the longest context");
+static_assert(ROWPACK_MAX_W == LNB_BATCH_MAX, "lnb_rowpack.h and lnb_device.h disagree on the columns of a pass");
 static_assert(LNB_MAX_FORK == KVC_MAX_DST, "lnb.h and lnb_kvcopy.h disagree on the destinations of a fork");
 static_assert(LNB_MAX_TOP_K == LNB_TOKPROB_MAX_K, "lnb.h and lnb_device.h disagree on the largest top-k");
 static_assert(LNB_MAX_DRAFT == LNB_SPEC_MAX_DRAFT && LNB_MAX_DRAFT + 1 <= LNB_STREAM_COLS, "a verify pass is one column group of at most 16 columns");
@@ -66,6 +68,8 @@ hipError_t lnbk_spec_argmax(const uint16_t* logits, int V, int w, int32_t* g, hi
 hipError_t lnbk_spec_commit(const int32_t* g, int w, const BatchTab* tab, hipStream_t st);
 hipError_t lnbk_ngram_draft(const DraftParams* p, hipStream_t st);
 hipError_t lnbk_kv_fork(const KvForkTab* tab, int nt, int split, hipStream_t st);
+hipError_t lnbk_append_many_setup(const AmPass* p, hipStream_t st);
+hipError_t lnbk_append_many_finish(const uint16_t* logits, int V, const AmRow* rows, int width, int32_t* out, hipStream_t st);
 }
 
 // The HIP runtime spreads a process's streams over a fixed number of hardware queues (its default: 4) and streams that share a queue run one
@@ -140,6 +144,7 @@ struct lnb_model {
     bool finalized = false;
     int64_t weight_bytes = 0;
     bool batch_enabled = false; uint16_t* m_output = nullptr; int64_t batch_bytes = 0;
+    std::mutex am_mu; struct AppendMany* am = nullptr;     // lnb_forward_append_many: the call's buffers and tables, created on first use; the mutex is held for a whole call
     bool first() const { return part_begin == 0; }
     bool last() const { return part_end == 3 * a.n_layers; }
     bool has_part(int l, int q) const { return 3 * l + q >= part_begin && 3 * l + q < part_end; }
@@ -457,9 +462,11 @@ static int model_alloc(lnb_model* m) {
     return 0;
 }
 
+static void append_many_free(lnb_model* m);
 extern "C" int lnb_model_destroy(lnb_model* m) {
     if (!m) return 0;
     hipSetDevice(m->device);
+    append_many_free(m);
     if (m->tok_embd) hipFree(m->tok_embd);
     if (m->norm) hipFree(m->norm);
     if (m->output.w) hipFree(m->output.w);
@@ -1766,6 +1773,7 @@ struct lnb_batch {
     // speculative verify batch (lnb_decode_speculative_until): every column is ONE context (ctxs[s] = it, the same caches); columns s >= 1 take
     // their state and token word from col_st + s / col_tok + s instead of the context's own
     StepState* col_st = nullptr; int32_t* col_tok = nullptr;
+    int* zseq = nullptr;                   // lnb_forward_append_many's pass batch has no member contexts: the serial-sum counter the attention launches get instead of ctxs[0]'s
 };
 static int m16_copy(lnb_model* m, const TiledDesc& t, int rows, uint16_t** out) {
     const size_t bytes = m16_elems(rows, t.k, t.nch) * 2;
@@ -1997,7 +2005,7 @@ static int enqueue_batch_kernel_wide(lnb_batch* b, int l, int which) {
             AttnParams ap{}; ap.q = b->q; ap.out_xt = b->att_xt; ap.btab = b->tab; ap.bkv = b->kv + (l - m->layer_begin); ap.dbg = nullptr;
             ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
             ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
-            ap.zseq_count = b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;
+            ap.zseq_count = b->zseq ? b->zseq : b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;
             HIPCHK(batch_attn_launch(b, ap, st)); return 0; }
         case K_WO: {
             StreamParams p = pair_of(L.m_wo, b->att_xt, m->q_dim, dim); p.out = b->h; p.res = b->x;
@@ -2029,7 +2037,7 @@ static int enqueue_batch_kernel_wide(lnb_batch* b, int l, int which) {
         AttnParams ap{}; ap.q = b->q; ap.out = b->att_xt; ap.out_xt = nullptr; ap.btab = b->tab; ap.bkv = b->kv + (l - m->layer_begin); ap.dbg = nullptr;
         ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
         ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
-        ap.zseq_count = b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
+        ap.zseq_count = b->zseq ? b->zseq : b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
         HIPCHK(batch_attn_launch(b, ap, st)); return 0; }
     case K_WO: {
         GemmParams g = wide_of(b, L.wo, L.m_wo, b->att_xt, m->q_dim, dim, 1); g.out = b->h; g.res = b->x;
@@ -2066,7 +2074,7 @@ static int enqueue_batch_kernel(lnb_batch* b, int l, int which) {
         AttnParams ap{}; ap.q = b->q; ap.out_xt = b->att_xt; ap.btab = b->tab; ap.bkv = b->kv + (l - m->layer_begin); ap.dbg = nullptr;
         ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
         ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
-        ap.zseq_count = b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
+        ap.zseq_count = b->zseq ? b->zseq : b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
         HIPCHK(batch_attn_launch(b, ap, st)); return 0; }
     case K_WO: {
         StreamParams p = stream_of(b, L.m_wo, b->att_xt, m->q_dim, dim, 1); p.out = b->h; p.res = b->x;
@@ -2258,6 +2266,201 @@ extern "C" int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int it
     HIPCHK(hipStreamSynchronize(st));
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
     *avg_ms_out = ms / (float)iters;
+    return 0;
+}
+
+// ---- lnb_forward_append_many (include/lnb.h): n contexts extended by n_rows[s] rows each, in passes of up to LNB_APPEND_MANY_COLS rows over the weights.
+// A pass IS a batched step (enqueue_batch_kernel: the column forms, the column groups, rows of gemm_stream_kernel -- whatever its width selects) on a
+// lnb_batch that has no member contexts: its buffers hold 128 columns, its column states and token words are the call's own, and its BatchTab / BatchKV
+// are rewritten on the device at the start of every pass (append_many_setup_kernel) from the row and member tables the call uploaded once.  Two things
+// differ from a live batch (and are why this is not lnb_batch_decode on a temporary batch):
+//   * the width changes from pass to pass on ONE set of activation buffers, so "columns past n stay zero for ever" (batch_alloc) has to be re-established:
+//     the buffers are zeroed whenever a pass is narrower than the one before or changes layout (B-operand columns / column groups / rows);
+//   * nothing may advance a position or log a token: batch_argmax_kernel and spec_commit_kernel are never launched, the tab's token logs point at a
+//     dummy with capacity 0, and only append_many_finish_kernel reads the logits.
+struct AppendMany {
+    lnb_batch* b = nullptr;                 // stream, activation buffers and logits for LNB_BATCH_MAX columns, tab / kv filled per pass
+    StepState* st = nullptr; int32_t* tok = nullptr; int32_t* dummy_log = nullptr; int* zseq = nullptr;
+    AmRow* rows = nullptr; size_t rows_cap = 0;             // the call's row table (grown on demand)
+    char* members = nullptr;                // AmMembers + one BatchKV per layer, indexed by member
+    int32_t* d_arg = nullptr; int32_t* h_arg = nullptr;     // [LNB_BATCH_MAX] argmax per member: device, pinned host
+    uint16_t* pin[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr};     // logits of a pass on their way to the host, two passes in flight
+    int scratch_n = 0, scratch_T = 0;       // what b->e_buf / b->z_part hold: columns x positions of the long-context pair
+    int last_layout = -1, last_width = 0;   // what the activation buffers were last used as
+    int passes = 0, max_columns = 0, long_passes = 0;      // lnb_model_append_many_info
+};
+static void append_many_free(lnb_model* m) {
+    AppendMany* am = m->am;
+    if (!am) return;
+    if (am->b && am->b->stream) hipStreamSynchronize(am->b->stream);
+    hipFree(am->st); hipFree(am->tok); hipFree(am->dummy_log); hipFree(am->zseq); hipFree(am->rows); hipFree(am->members); hipFree(am->d_arg);
+    if (am->h_arg) hipHostFree(am->h_arg);
+    for (int i = 0; i < 2; i++) { if (am->pin[i]) hipHostFree(am->pin[i]); if (am->ev[i]) hipEventDestroy(am->ev[i]); }
+    if (am->b) lnb_batch_destroy(am->b);
+    delete am;
+    m->am = nullptr;
+}
+static int append_many_alloc(lnb_model* m) {
+    if (m->am) return 0;
+    AppendMany* am = new AppendMany();
+    m->am = am;                                              // (a failure below leaves a partial object: lnb_model_destroy frees it, the next call starts over)
+    auto bail = [&]() { append_many_free(m); return -1; };
+    lnb_batch* b = new lnb_batch();
+    am->b = b; b->m = m; b->n = 1; b->scratch_owned = true;
+    const size_t N = LNB_BATCH_MAX, dim = m->a.dim, L = m->layers.size();
+    auto dalloc = [&](void** p, size_t bytes) -> int { HIPCHK(hipMalloc(p, bytes)); HIPCHK(hipMemsetAsync(*p, 0, bytes, b->stream)); return 0; };
+    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) { fail("lnb_forward_append_many: no stream"); return bail(); }
+    if (dalloc((void**)&b->x, N * dim * 2) || dalloc((void**)&b->h, N * dim * 2) || dalloc((void**)&b->xt, N * dim * 2) || dalloc((void**)&b->q, N * m->q_dim * 2) ||
+        dalloc((void**)&b->att_xt, N * m->q_dim * 2) || dalloc((void**)&b->ffn_xt, N * m->ffn_hidden * 2) || dalloc((void**)&b->logits, N * (size_t)m->a.vocab_size * 2) ||
+        dalloc((void**)&b->derr, 16) || dalloc((void**)&b->tab, sizeof(BatchTab)) || dalloc((void**)&b->kv, L * sizeof(BatchKV)) ||
+        dalloc((void**)&am->st, N * sizeof(StepState)) || dalloc((void**)&am->tok, N * 4) || dalloc((void**)&am->dummy_log, 64) || dalloc((void**)&am->zseq, 16) ||
+        dalloc((void**)&am->members, sizeof(AmMembers) + L * sizeof(BatchKV)) || dalloc((void**)&am->d_arg, N * 4)) return bail();
+    b->zseq = am->zseq;
+    if (hipHostMalloc((void**)&am->h_arg, N * 4, hipHostMallocDefault) != hipSuccess) { fail("lnb_forward_append_many: no pinned host memory"); return bail(); }
+    for (int i = 0; i < 2; i++) if (hipEventCreateWithFlags(&am->ev[i], hipEventDisableTiming) != hipSuccess) { fail("lnb_forward_append_many: no event"); return bail(); }
+    BatchTab t{};                                            // the pointers of a column never change: its own state and token word, the dummy log (capacity 0: nothing is ever logged)
+    for (int c = 0; c < LNB_BATCH_MAX; c++) { t.st[c] = am->st + c; t.dtok[c] = am->tok + c; t.dout[c] = am->dummy_log; t.dout_cap[c] = 0; t.seq_len[c] = 0; }
+    if (hipMemcpyAsync(b->tab, &t, sizeof t, hipMemcpyHostToDevice, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess) {
+        fail("lnb_forward_append_many: uploading the column table failed"); return bail();
+    }
+    return 0;
+}
+// layout the activation buffers of a pass of `width` columns are used in: 0 = B-operand columns, 1 = column groups, 2 = rows
+static int append_many_layout(const lnb_batch* b) { return b->n <= LNB_STREAM_COLS && !b->rows_form ? 0 : batch_groups(b) ? 1 : 2; }
+extern "C" int lnb_model_append_many_info(const lnb_model* m, int* passes, int* max_columns, int* long_passes) {
+    if (!m) return fail("lnb_model_append_many_info: null argument (model)");
+    const AppendMany* am = m->am;
+    if (passes) *passes = am ? am->passes : 0;
+    if (max_columns) *max_columns = am ? am->max_columns : 0;
+    if (long_passes) *long_passes = am ? am->long_passes : 0;
+    return 0;
+}
+extern "C" int lnb_forward_append_many(lnb_ctx* const* ctxs, int n, const int32_t* tokens, const int32_t* n_rows, const int32_t* start_pos,
+                                       float* logits_out, int32_t* argmax_out) {
+    const char* const name = "lnb_forward_append_many";
+    // ---- the arguments alone: no handle is dereferenced
+    if (!ctxs || !tokens || !n_rows || !start_pos) return fail("%s: null argument (%s)", name, !ctxs ? "ctxs" : !tokens ? "tokens" : !n_rows ? "n_rows" : "start_pos");
+    if (n < 1 || n > LNB_BATCH_MAX) return fail("%s: a call takes 1..%d contexts (got %d)", name, LNB_BATCH_MAX, n);
+    for (int s = 0; s < n; s++) {
+        if (!ctxs[s]) return fail("%s: null context at index %d", name, s);
+        if (n_rows[s] < 1) return fail("%s: member %d: n_rows must be positive (got %d)", name, s, n_rows[s]);
+        if (start_pos[s] < 0) return fail("%s: member %d: negative start position %d", name, s, start_pos[s]);
+        for (int r = 0; r < s; r++) if (ctxs[r] == ctxs[s]) return fail("%s: context %d appears twice (also at index %d)", name, s, r);
+    }
+    const int W = knob(Knob::APPEND_MANY_COLS);
+    if (W < 1 || W > LNB_BATCH_MAX) return fail("%s: LNB_APPEND_MANY_COLS=%d is not a pass width (1..%d)", name, W, LNB_BATCH_MAX);
+    // ---- the handles: everything is checked before any cache is written
+    lnb_model* m = ctxs[0]->m;
+    for (int s = 0; s < n; s++) if (ctxs[s]->m != m) return fail("%s: context %d belongs to another lnb_model handle", name, s);
+    if (!m->first() || !m->last()) return fail("%s needs a whole-model handle: pipeline stages have no append", name);
+    if (m->a.dim % 128 || m->q_dim % 128 || m->ffn_hidden % 128)
+        return fail("%s streams the weights in 128-step chunks: dim (%d), n_heads*head_dim (%d) and the FFN hidden size (%d) must be multiples of 128", name, m->a.dim, m->q_dim, m->ffn_hidden);
+    const int V = m->a.vocab_size;
+    int64_t total = 0;
+    for (int s = 0; s < n; s++) {
+        const lnb_ctx* c = ctxs[s];
+        if (c->mode != LNB_MODE_EXACT) return fail("%s: context %d is in the tolerance mode: the call is exact-mode only", name, s);
+        if (c->pending) return fail("%s: context %d: a lnb_forward_stage_begin has not been ended", name, s);
+        const int64_t T = (int64_t)start_pos[s] + n_rows[s];
+        if (T > m->cis_rows) return fail("%s: member %d: position %lld is beyond the %d-row RoPE table", name, s, (long long)T, m->cis_rows);
+        if (T > c->seq_len) return fail("%s: member %d: position %lld is beyond the KV cache of %d", name, s, (long long)T, c->seq_len);
+        if (lnbk_attn_long_layout_lds(c->seq_len) > 160 * 1024) return fail("%s: member %d: seq_len %d is beyond what the long-context attention keeps in the LDS", name, s, c->seq_len);
+        total += n_rows[s];
+    }
+    for (int64_t i = 0; i < total; i++)
+        if (tokens[i] < 0 || tokens[i] >= V) return fail("%s: token id %d at row %lld is outside the vocabulary", name, tokens[i], (long long)i);
+    // ---- the call's tables on the host: one AmRow per row, the members' cache lengths and cache pointers; per pass its attention form
+    std::vector<AmRow> rows((size_t)total);
+    { size_t i = 0;
+      for (int s = 0; s < n; s++) for (int r = 0; r < n_rows[s]; r++, i++) rows[i] = AmRow{s, start_pos[s] + r, tokens[i], r == n_rows[s] - 1 ? 1 : 0}; }
+    const size_t L = m->layers.size();
+    std::vector<char> members(sizeof(AmMembers) + L * sizeof(BatchKV));
+    { AmMembers* hm = (AmMembers*)members.data(); BatchKV* hk = (BatchKV*)(members.data() + sizeof(AmMembers));
+      hm->n = n;
+      for (int s = 0; s < LNB_BATCH_MAX; s++) {
+          const lnb_ctx* c = ctxs[s < n ? s : 0];
+          hm->seq_len[s] = c->seq_len;
+          for (size_t l = 0; l < L; l++) { hk[l].ck[s] = c->ck[l]; hk[l].cv[s] = c->cv[l]; }
+      } }
+    RowPackWalk walk; RowSeg segs[ROWPACK_MAX_W]; int width = 0; int64_t row0 = 0;
+    int need_n = 0, need_T = 0;                              // the long-context pair's scratch over every pass that runs it
+    if (rowpack_begin(&walk, n, n_rows, W)) return fail("%s: internal error: the rows could not be packed", name);
+    while (int ns = rowpack_next(&walk, segs, &width, &row0)) {
+        bool lng = false; int maxT = 0;
+        for (int g = 0; g < ns; g++) { const lnb_ctx* c = ctxs[segs[g].member]; maxT = std::max(maxT, c->seq_len); lng = lng || c->seq_len > c->attn_short_cap; }
+        if (lng) { need_n = std::max(need_n, width); need_T = std::max(need_T, maxT); }
+    }
+    std::lock_guard<std::mutex> lock(m->am_mu);
+    HIPCHK(hipSetDevice(m->device));
+    HIPCHK(lnbk_batch_prepare());
+    if (append_many_alloc(m)) return -1;
+    AppendMany* am = m->am; lnb_batch* b = am->b; hipStream_t st = b->stream;
+    if (need_n > am->scratch_n || need_T > am->scratch_T) {
+        const int sn = std::max(need_n, am->scratch_n), sT = std::max(need_T, am->scratch_T);
+        hipFree(b->e_buf); hipFree(b->z_part); b->e_buf = nullptr; b->z_part = nullptr; am->scratch_n = am->scratch_T = 0;
+        if (attn_long_scratch(sn, m->a.n_heads, sT, &b->e_buf, &b->z_part, name)) return -1;
+        am->scratch_n = sn; am->scratch_T = sT;
+    }
+    if ((size_t)total > am->rows_cap) {
+        AmRow* t = nullptr;
+        if (hipMalloc((void**)&t, (size_t)total * sizeof(AmRow)) != hipSuccess) { (void)hipGetLastError(); return fail("%s: no device memory for the row table (%zu bytes)", name, (size_t)total * sizeof(AmRow)); }
+        hipFree(am->rows); am->rows = t; am->rows_cap = (size_t)total;
+    }
+    if (logits_out && !am->pin[0])
+        for (int i = 0; i < 2; i++)
+            if (hipHostMalloc((void**)&am->pin[i], (size_t)LNB_BATCH_MAX * V * 2, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError(); if (am->pin[0]) { hipHostFree(am->pin[0]); am->pin[0] = nullptr; }
+                return fail("%s: no pinned host memory for the logits of a pass (%zu bytes)", name, (size_t)LNB_BATCH_MAX * V * 2);
+            }
+    // ---- from here on the caches are written
+    for (int s = 0; s < n; s++) {
+        HIPCHK(hipStreamSynchronize(ctxs[s]->stream));       // whatever the member's own stream still does to its caches comes first
+        ctxs[s]->dev_pos = -1; ctxs[s]->call_T = 0;
+    }
+    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { hipStreamSynchronize(s); } } sync_on_exit{st};     // (the uploads below read `rows` and `members`: no way out before the stream has drained)
+    HIPCHK(hipMemcpyAsync(am->rows, rows.data(), (size_t)total * sizeof(AmRow), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(am->members, members.data(), members.size(), hipMemcpyHostToDevice, st));
+    b->rows_form = !m->batch_enabled; b->force_zseq = 0; b->attn_rows = false;
+    am->passes = am->max_columns = am->long_passes = 0;
+    auto fetch = [&](int slot, int64_t r0, int w) -> int {  // the logits of a pass, once its copy has landed: output.ToFloat32() :175
+        HIPCHK(hipEventSynchronize(am->ev[slot]));
+        const uint16_t* src = am->pin[slot]; float* dst = logits_out + (size_t)r0 * V;
+        for (size_t i = 0, e = (size_t)w * V; i < e; i++) dst[i] = bf_wide_h(src[i]);
+        return 0;
+    };
+    int pass = 0, prev_w = 0; int64_t prev_r0 = 0;
+    rowpack_begin(&walk, n, n_rows, W);
+    while (int ns = rowpack_next(&walk, segs, &width, &row0)) {
+        bool lng = false; int maxT = 0;
+        for (int g = 0; g < ns; g++) { const lnb_ctx* c = ctxs[segs[g].member]; maxT = std::max(maxT, c->seq_len); lng = lng || c->seq_len > c->attn_short_cap; }
+        b->n = width; b->maxT = maxT; b->lds_T = std::min(maxT, ctxs[0]->attn_short_cap); b->must_long = lng; b->attn_long = lng;
+        const int layout = append_many_layout(b);
+        if (am->last_layout >= 0 && (layout != am->last_layout || width < am->last_width)) {       // dead columns are zero again
+            const size_t N = LNB_BATCH_MAX, dim = m->a.dim;
+            HIPCHK(hipMemsetAsync(b->x, 0, N * dim * 2, st)); HIPCHK(hipMemsetAsync(b->h, 0, N * dim * 2, st)); HIPCHK(hipMemsetAsync(b->xt, 0, N * dim * 2, st));
+            HIPCHK(hipMemsetAsync(b->q, 0, N * m->q_dim * 2, st)); HIPCHK(hipMemsetAsync(b->att_xt, 0, N * m->q_dim * 2, st)); HIPCHK(hipMemsetAsync(b->ffn_xt, 0, N * m->ffn_hidden * 2, st));
+        }
+        am->last_layout = layout; am->last_width = width;
+        AmPass ap{}; ap.rows = am->rows + row0; ap.members = (const AmMembers*)am->members; ap.member_kv = (const BatchKV*)(am->members + sizeof(AmMembers));
+        ap.tab = b->tab; ap.kv = b->kv; ap.st = am->st; ap.tok = am->tok; ap.width = width; ap.n_layers = (int)L;
+        HIPCHK(lnbk_append_many_setup(&ap, st));
+        HIPCHK(lnbk_batch_embed(m->tok_embd, b->tab, b->x, width, m->a.dim, V, b->derr, st));
+        for (int l = m->layer_begin; l < m->layer_end; l++)
+            for (int k = K_QKV; k <= K_W2; k++) if (enqueue_batch_kernel(b, l, k)) return -1;
+        if (enqueue_batch_kernel(b, 0, K_HEAD)) return -1;
+        HIPCHK(lnbk_append_many_finish(b->logits, V, am->rows + row0, width, am->d_arg, st));
+        if (logits_out) {
+            HIPCHK(hipMemcpyAsync(am->pin[pass & 1], b->logits, (size_t)width * V * 2, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipEventRecord(am->ev[pass & 1], st));
+            if (pass > 0 && fetch((pass - 1) & 1, prev_r0, prev_w)) return -1;        // the pass before, while this one runs
+        }
+        prev_w = width; prev_r0 = row0; pass++;
+        am->passes = pass; am->max_columns = std::max(am->max_columns, width); am->long_passes += lng ? 1 : 0;
+    }
+    if (logits_out && fetch((pass - 1) & 1, prev_r0, prev_w)) return -1;
+    HIPCHK(hipMemcpyAsync(am->h_arg, am->d_arg, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (argmax_out) memcpy(argmax_out, am->h_arg, (size_t)n * 4);
     return 0;
 }
 

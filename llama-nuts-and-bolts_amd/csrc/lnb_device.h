@@ -207,6 +207,23 @@ struct BatchTab {                  // device-resident: the sequences of a batch 
 };
 struct BatchKV { uint16_t* ck[LNB_BATCH_MAX]; uint16_t* cv[LNB_BATCH_MAX]; };   // one per layer: every sequence's caches of that layer
 
+// ---- ragged append to many contexts (lnb_forward_append_many; lnb_append_many.h) ---------------------------------------------------------
+// A pass is a batched step whose columns are ROWS of the call: column c of the pass that starts at row0 is row row0 + c of the row table, the
+// one-token step of its member at its position.  Both tables are uploaded once per call; append_many_setup_kernel turns them, per pass, into the
+// BatchTab / BatchKV the batched kernels read.
+struct AmRow { int32_t member, pos, token, last; };        // last: 1 = the member's last row (the one whose argmax the call reports)
+struct AmMembers {                                         // followed in memory by one BatchKV per cached layer, indexed by MEMBER
+    int32_t seq_len[LNB_BATCH_MAX];
+    int32_t n, pad[3];
+};
+struct AmPass {                                            // one launch of append_many_setup_kernel / append_many_finish_kernel
+    const AmRow* rows;                                     // the pass's first row (row0 already added)
+    const AmMembers* members; const BatchKV* member_kv;    // [n_layers]
+    BatchTab* tab; BatchKV* kv;                            // what the pass's kernels read: filled here
+    StepState* st; int32_t* tok;                           // [LNB_BATCH_MAX] column states and token words (tab->st[c] = st + c, tab->dtok[c] = tok + c: set once by the host)
+    int32_t width, n_layers;
+};
+
 struct StreamParams {              // mfma_stream_kernel: Y[s][n] = trunc(sum_k x_s[k] W[n][k]) for the nseq sequences of a batch
     const uint16_t* w;             // M16 weights
     const uint16_t* xt;            // activations in the B-operand layout (already normalised where the GEMV would fuse the norm)

@@ -4964,3 +4964,16 @@ extern "C" hipError_t lnbk_kv_fork(const KvForkTab* tab, int nt, int split, hipS
     else hipLaunchKernelGGL(kv_fork_kernel<false>, grid, dim3(KVC_THREADS), 0, st, *tab);
     return hipGetLastError();
 }
+
+// lnb_forward_append_many: per pass, the columns' tables from the call's row and member tables, and the argmax of the members' last rows (lnb_append_many.h)
+#include "lnb_append_many.h"
+extern "C" hipError_t lnbk_append_many_setup(const AmPass* p, hipStream_t st) {
+    if (!p || !p->rows || !p->members || !p->member_kv || !p->tab || !p->kv || !p->st || !p->tok || p->width < 1 || p->width > LNB_BATCH_MAX || p->n_layers < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(append_many_setup_kernel, dim3((unsigned)(1 + p->n_layers)), dim3(LNB_BATCH_MAX), 0, st, *p);
+    return hipGetLastError();
+}
+extern "C" hipError_t lnbk_append_many_finish(const uint16_t* logits, int V, const AmRow* rows, int width, int32_t* out, hipStream_t st) {
+    if (!logits || !rows || !out || V < 1 || width < 1 || width > LNB_BATCH_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(append_many_finish_kernel, dim3((unsigned)width), dim3(1024), 0, st, logits, V, rows, out);
+    return hipGetLastError();
+}

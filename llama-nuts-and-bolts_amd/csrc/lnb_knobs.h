@@ -41,6 +41,7 @@
     X(ATTN_GQA_FORCE_ZSEQ, 0, LIVE, "1: every head of attn_gqa_kernel walks the serial denominator (tests)") \
     X(ATTN_BATCH_DENSE, 1, LIVE, "0: batched decode attention never takes the dense-dispatch attn_exact_kernel form") \
     X(ATTN_BATCH_HEADMAJOR, 0, LIVE, "1: that form dispatches head-major (A/B)") \
+    X(APPEND_MANY_COLS, 128, LIVE, "columns per pass of lnb_forward_append_many (1..128; any other value makes the call fail with a message naming this knob): tests reach every width form and the pass boundary with few rows, the bench sweeps it") \
     /* prefix sharing */ \
     X(FORK_COPY, 0, LIVE, "1: lnb_ctx_fork on the copy engine (hipMemcpy2DAsync per layer and destination, no kernel launch): the comparison kv_fork_kernel has to beat (2.5x slower at 4096 positions into 127 contexts, 7.6 - 52x at 128 positions, 1.4x at its best: no crossover), and a cross-check on its bits") \
     X(FORK_NT, 0, LIVE, "1: kv_fork_kernel with non-temporal loads and stores (measurement: from 3 % faster to 20 % slower than the plain form)") \

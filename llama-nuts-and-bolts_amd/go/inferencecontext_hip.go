@@ -302,6 +302,44 @@ func (ic *InferenceContext) ForkPrefix(lt *LlamaTransformer, dsts []*InferenceCo
 	return lnbCall(func() C.int { return C.lnb_ctx_fork(ic.handle, C.int(nPos), (**C.lnb_ctx)(unsafe.Pointer(&hs[0])), C.int(len(hs))) })
 }
 
+// ForwardAppendMany extends up to 128 contexts of one transformer in one call (lnb_forward_append_many): context s takes tokens[s] at startPos[s], the
+// rows of all of them packed into batched passes of up to 128 rows over the weights.  Every context's KV rows and its last row's argmax (the result,
+// one per context) are bit-identical to its own ForwardAppend.  The step after ForkPrefix: each user's own text behind the shared prompt.
+func ForwardAppendMany(lt *LlamaTransformer, ctxs []*InferenceContext, tokens [][]int32, startPos []int) ([]int32, error) {
+	if len(ctxs) == 0 || len(tokens) != len(ctxs) || len(startPos) != len(ctxs) {
+		return nil, fmt.Errorf("ForwardAppendMany: %d contexts, %d token lists, %d start positions", len(ctxs), len(tokens), len(startPos))
+	}
+	hs := make([]*C.lnb_ctx, len(ctxs))
+	nRows := make([]C.int32_t, len(ctxs))
+	pos := make([]C.int32_t, len(ctxs))
+	var flat []C.int32_t
+	for i, c := range ctxs {
+		if c == nil {
+			return nil, fmt.Errorf("ForwardAppendMany: context %d is nil", i)
+		}
+		if len(tokens[i]) == 0 {
+			return nil, fmt.Errorf("ForwardAppendMany: context %d has no tokens", i)
+		}
+		if err := c.attach(lt); err != nil {
+			return nil, err
+		}
+		hs[i] = c.handle
+		nRows[i] = C.int32_t(len(tokens[i]))
+		pos[i] = C.int32_t(startPos[i])
+		for _, t := range tokens[i] {
+			flat = append(flat, C.int32_t(t))
+		}
+	}
+	argmax := make([]int32, len(ctxs))
+	err := lnbCall(func() C.int {
+		return C.lnb_forward_append_many((**C.lnb_ctx)(unsafe.Pointer(&hs[0])), C.int(len(hs)), &flat[0], &nRows[0], &pos[0], nil, (*C.int32_t)(unsafe.Pointer(&argmax[0])))
+	})
+	if err != nil {
+		return nil, err
+	}
+	return argmax, nil
+}
+
 // SavePrefix returns the KV rows [0, nPos) as a capacity-independent blob (lnb_ctx_save_prefix; layout in lnb.h): a prefix cache in host memory
 // or on disk.  The blob carries no model identity -- loading rows that other weights computed is the caller's mistake.
 func (ic *InferenceContext) SavePrefix(lt *LlamaTransformer, nPos int) ([]byte, error) {

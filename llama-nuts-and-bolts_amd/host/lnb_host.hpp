@@ -295,8 +295,29 @@ inline std::vector<float> ForwardAppend(const LlamaTransformer& t, InferenceCont
     check(lnb_forward_append(ctx.handle(), inputTokens.data(), (int)inputTokens.size(), startPos, logits.data(), argmaxLast));
     return logits;
 }
+// lnb_forward_append_many: context s takes tokenLists[s] at startPos[s], the rows of all contexts (up to 128, one transformer) packed into batched
+// passes of up to 128 rows over the weights; every context's KV rows, logits and last-row argmax are the bits of its own ForwardAppend.
+// -> the argmax per context; logits (optional): [sum of rows][VocabSize] in the order of the lists
+inline std::vector<TokenId> ForwardAppendMany(const LlamaTransformer& t, const std::vector<InferenceContext*>& ctxs, const std::vector<std::vector<TokenId>>& tokenLists,
+                                              const std::vector<int>& startPos, std::vector<float>* logits = nullptr) {
+    std::vector<lnb_ctx*> hs;
+    std::vector<int32_t> flat, nRows, pos(startPos.begin(), startPos.end());
+    for (auto* c : ctxs) hs.push_back(c ? c->handle() : nullptr);
+    for (const auto& l : tokenLists) { nRows.push_back((int32_t)l.size()); flat.insert(flat.end(), l.begin(), l.end()); }
+    if (nRows.size() != hs.size() || pos.size() != hs.size()) { nRows.resize(hs.size(), 0); pos.resize(hs.size(), -1); }       // (the library refuses the call with a message)
+    if (logits) logits->assign(flat.size() * (size_t)t.Args().VocabSize, 0.f);
+    std::vector<TokenId> argmax(hs.size());
+    check(lnb_forward_append_many(hs.data(), (int)hs.size(), flat.data(), nRows.data(), pos.data(), logits ? logits->data() : nullptr, argmax.data()));
+    return argmax;
+}
+struct AppendManyInfo { int Passes = 0, MaxColumns = 0, LongPasses = 0; };
+inline AppendManyInfo GetAppendManyInfo(const LlamaTransformer& t) {       // of the last ForwardAppendMany on this transformer
+    AppendManyInfo i;
+    check(lnb_model_append_many_info(t.handle(), &i.Passes, &i.MaxColumns, &i.LongPasses));
+    return i;
+}
 
-enum GenerationState { GSInProgress = 1, GSFinishedByReachingEOS = 2, GSFinishedByReachingSeqLen = 3 };   // inference.go:13-17
+enum GenerationState{ GSInProgress = 1, GSFinishedByReachingEOS = 2, GSFinishedByReachingSeqLen = 3 };   // inference.go:13-17
 
 class InferenceEngine {                  // inference.go:40-56
 public:

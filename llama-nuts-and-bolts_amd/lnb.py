@@ -70,6 +70,7 @@ EXPORTS = [
     "lnb_ctx_create_long", "lnb_ctx_max_rows",
     "lnb_ctx_set_rows_attention", "lnb_ctx_append_attention_form",
     "lnb_ctx_fork", "lnb_ctx_prefix_bytes", "lnb_ctx_save_prefix", "lnb_ctx_load_prefix",
+    "lnb_forward_append_many", "lnb_model_append_many_info",
 ]
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
 MAX_DRAFT = 15           # LNB_MAX_DRAFT of include/lnb.h (tests/test_speculative_cpu.py compares them)
@@ -189,6 +190,8 @@ def lib():
     L.lnb_ctx_prefix_bytes.restype = C.c_int64
     L.lnb_ctx_save_prefix.argtypes = [vp, C.c_int, vp, C.c_int64]
     L.lnb_ctx_load_prefix.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int)]
+    L.lnb_forward_append_many.argtypes = [C.POINTER(vp), C.c_int, vp, vp, vp, vp, vp]
+    L.lnb_model_append_many_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lnb_pipeline_tick_batch.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.lnb_pipeline_read_tokens.argtypes = [vp, C.c_int, C.c_int, vp]
     L.lnb_op_linear_mode.argtypes = [C.c_int, vp, vp, C.c_float, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -478,6 +481,12 @@ class LlamaTransformer:
     def batch_bytes(self):
         return int(self.L.lnb_model_batch_bytes(self.h))
 
+    def append_many_info(self):
+        """of the last ForwardAppendMany on this transformer: {passes, max_columns, long_passes} (lnb_model_append_many_info)"""
+        p, w, g = C.c_int(0), C.c_int(0), C.c_int(0)
+        _chk(self.L.lnb_model_append_many_info(self.h, C.byref(p), C.byref(w), C.byref(g)))
+        return {"passes": p.value, "max_columns": w.value, "long_passes": g.value}
+
     def close(self):
         if self.h:
             self.L.lnb_model_destroy(self.h)
@@ -727,6 +736,28 @@ class InferenceContext:
         if self.h:
             _chk(self.L.lnb_ctx_destroy(self.h))             # refused while a live Batch holds the context: the handle (and the device memory) stays
             self.h = C.c_void_p()
+
+
+def ForwardAppendMany(ctxs, token_lists, start_pos, want_logits=True):
+    """Extend the contexts `ctxs` (1..128, one transformer, any capacities) in ONE call: context s takes token_lists[s] at start_pos[s], the rows of
+    all of them packed into batched passes of up to 128 rows over the weights (lnb_forward_append_many).  Every context's KV rows, logits and
+    last-row argmax are the bits of its own ForwardAppend -> (list of per-context logits f32 [rows_s, V] | None, int32 argmax [n])."""
+    ctxs = list(ctxs)
+    lists = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in token_lists]
+    if not ctxs or len(lists) != len(ctxs) or len(start_pos) != len(ctxs):
+        raise LnbError("ForwardAppendMany: %d contexts, %d token lists, %d start positions" % (len(ctxs), len(lists), len(start_pos)))
+    L, V = ctxs[0].L, ctxs[0].t.args.vocab_size
+    flat = np.ascontiguousarray(np.concatenate(lists), dtype=np.int32)
+    rows = np.array([t.size for t in lists], dtype=np.int32)
+    pos = np.ascontiguousarray(start_pos, dtype=np.int32)
+    arr = (C.c_void_p * len(ctxs))(*[c.h for c in ctxs])
+    logits = np.empty((max(flat.size, 1), V), dtype=np.float32) if want_logits else None
+    am = np.full(len(ctxs), -2, dtype=np.int32)
+    _chk(L.lnb_forward_append_many(arr, len(ctxs), _p(flat), _p(rows), _p(pos), _p(logits) if want_logits else None, _p(am)))
+    if not want_logits:
+        return None, am
+    ends = np.cumsum(rows)
+    return [logits[e - r:e] for e, r in zip(ends, rows)], am
 
 
 class Batch:
