@@ -4,6 +4,7 @@
 // and a hipGraph-replayed greedy decode loop whose position/token state lives on the device.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -22,9 +23,11 @@
 #include "lnb_knobs.h"
 #include "lnb_kvcopy.h"
 #include "lnb_rowpack.h"
+#include "lnb_batchplan.h"
 #include "lnb_rccl.h"
 static_assert(LNB_MAX_SEQ_LEN == LNB_SEQ_MAX, "lnb.h and lnb_device.h disagree on the longest context");
 static_assert(ROWPACK_MAX_W == LNB_BATCH_MAX, "lnb_rowpack.h and lnb_device.h disagree on the columns of a pass");
+static_assert(BATCHPLAN_COLS == LNB_STREAM_COLS, "lnb_batchplan.h and lnb_device.h disagree on the sequences of a column group");
 static_assert(LNB_MAX_FORK == KVC_MAX_DST, "lnb.h and lnb_kvcopy.h disagree on the destinations of a fork");
 static_assert(LNB_MAX_TOP_K == LNB_TOKPROB_MAX_K, "lnb.h and lnb_device.h disagree on the largest top-k");
 static_assert(LNB_MAX_DRAFT == LNB_SPEC_MAX_DRAFT && LNB_MAX_DRAFT + 1 <= LNB_STREAM_COLS, "a verify pass is one column group of at most 16 columns");
@@ -1481,23 +1484,24 @@ extern "C" int lnb_ctx_token_prob_walks(lnb_ctx* c, int* out) {
     *out = c->h_io[0];
     return 0;
 }
+// What `body` enqueues on `st`, captured into the graph slot -- once: a slot that holds a graph is left alone and the body does not run.
+// A body that fails has set the message; the capture is ended and its graph dropped.
+template <class Body> static int capture_once(hipGraphExec_t* slot, hipStream_t st, Body body) {
+    if (*slot) return 0;
+    hipGraph_t g = nullptr;
+    HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    int rc = body();
+    hipError_t e = hipStreamEndCapture(st, &g);
+    if (rc) { if (g) hipGraphDestroy(g); return -1; }
+    HIPCHK(e);
+    HIPCHK(hipGraphInstantiate(slot, g, nullptr, nullptr, 0));
+    HIPCHK(hipGraphDestroy(g));
+    return 0;
+}
 // one captured graph per attention form: the step at context T replays the long-context one when T exceeds the crossover.  Captures the
 // forms that steps at positions start_pos .. start_pos + n_steps - 1 need and the context does not hold yet.
 static int capture_decode_graphs(lnb_ctx* c, int start_pos, int n_steps) {
-    hipStream_t st = c->stream;
-    auto capture = [&](hipGraphExec_t* slot, bool longctx) -> int {
-        if (*slot) return 0;
-        hipGraph_t g = nullptr;
-        c->attn_long = longctx;
-        HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        int rc = enqueue_decode_step(c);
-        hipError_t e = hipStreamEndCapture(st, &g);
-        if (rc) { if (g) hipGraphDestroy(g); return -1; }
-        HIPCHK(e);
-        HIPCHK(hipGraphInstantiate(slot, g, nullptr, nullptr, 0));
-        HIPCHK(hipGraphDestroy(g));
-        return 0;
-    };
+    auto capture = [&](hipGraphExec_t* slot, bool longctx) { return capture_once(slot, c->stream, [&] { c->attn_long = longctx; return enqueue_decode_step(c); }); };
     const bool any_short = !want_long_attention(c, 1, start_pos), any_long = want_long_attention(c, 1, start_pos + n_steps - 1);
     if (any_short && capture(&c->graph, false)) return -1;
     if (any_long && capture(&c->graph_long, true)) return -1;
@@ -1775,6 +1779,13 @@ struct lnb_batch {
     StepState* col_st = nullptr; int32_t* col_tok = nullptr;
     int* zseq = nullptr;                   // lnb_forward_append_many's pass batch has no member contexts: the serial-sum counter the attention launches get instead of ctxs[0]'s
 };
+// What every batched step asks of the model stage it runs on (who: the caller, as its message names it).  A whole-model handle is a stage of whole blocks.
+static int batch_shape_check(const lnb_model* m, const char* who) {
+    if (m->part_begin % 3 || m->part_end % 3) return fail("batched decode needs a stage of whole blocks (this one is cut inside a block: parts [%d, %d))", m->part_begin, m->part_end);
+    if (m->a.dim % 128 || m->q_dim % 128 || m->ffn_hidden % 128)
+        return fail("%s streams the weights in 128-step chunks: dim (%d), n_heads*head_dim (%d) and the FFN hidden size (%d) must be multiples of 128", who, m->a.dim, m->q_dim, m->ffn_hidden);
+    return 0;
+}
 static int m16_copy(lnb_model* m, const TiledDesc& t, int rows, uint16_t** out) {
     const size_t bytes = m16_elems(rows, t.k, t.nch) * 2;
     HIPCHK(hipMalloc((void**)out, bytes));
@@ -1787,9 +1798,7 @@ extern "C" int lnb_model_enable_batch(lnb_model* m) {
     if (!m) return fail("null argument");
     if (!m->finalized) return fail("model not finalized");
     if (m->batch_enabled) return 0;
-    if (m->part_begin % 3 || m->part_end % 3) return fail("batched decode needs a stage of whole blocks (this one is cut inside a block: parts [%d, %d))", m->part_begin, m->part_end);
-    if (m->a.dim % 128 || m->q_dim % 128 || m->ffn_hidden % 128)
-        return fail("batched decode streams the weights in 128-step chunks: dim (%d), n_heads*head_dim (%d) and the FFN hidden size (%d) must be multiples of 128", m->a.dim, m->q_dim, m->ffn_hidden);
+    if (batch_shape_check(m, "batched decode")) return -1;
     HIPCHK(hipSetDevice(m->device));
     HIPCHK(lnbk_batch_prepare());
     int rc = 0;
@@ -1815,6 +1824,32 @@ extern "C" int lnb_model_enable_batch(lnb_model* m) {
 }
 extern "C" int64_t lnb_model_batch_bytes(lnb_model* m) { return m ? m->batch_bytes : 0; }
 
+// The activation buffers of a batched step, N columns each (N a multiple of 16: the column forms keep B-operand layouts per group of 16),
+// with the logits of a stage that owns the head and the error word.  All zero when allocated: the columns past n are never written by a
+// live batch, whose width is fixed; a caller whose width changes re-zeroes the six (not the logits: every pass writes the rows it reads).
+struct BatchBuf { uint16_t** p; size_t bytes; };
+static std::array<BatchBuf, 6> batch_bufs(lnb_batch* b, size_t N) {
+    const lnb_model* m = b->m; const size_t dim = m->a.dim;
+    return {{{&b->x, N * dim * 2}, {&b->h, N * dim * 2}, {&b->xt, N * dim * 2}, {&b->q, N * m->q_dim * 2}, {&b->att_xt, N * m->q_dim * 2}, {&b->ffn_xt, N * m->ffn_hidden * 2}}};
+}
+static int batch_bufs_zero(lnb_batch* b, size_t N) {
+    for (const BatchBuf& f : batch_bufs(b, N)) HIPCHK(hipMemsetAsync(*f.p, 0, f.bytes, b->stream));
+    return 0;
+}
+static int batch_bufs_alloc(lnb_batch* b, size_t N) {
+    for (const BatchBuf& f : batch_bufs(b, N)) HIPCHK(hipMalloc((void**)f.p, f.bytes));
+    if (batch_bufs_zero(b, N)) return -1;
+    if (b->m->last()) {
+        const size_t bytes = N * (size_t)b->m->a.vocab_size * 2;
+        HIPCHK(hipMalloc((void**)&b->logits, bytes)); HIPCHK(hipMemsetAsync(b->logits, 0, bytes, b->stream));
+    }
+    HIPCHK(hipMalloc((void**)&b->derr, 16)); HIPCHK(hipMemsetAsync(b->derr, 0, 16, b->stream));
+    return 0;
+}
+static void batch_bufs_free(lnb_batch* b) {
+    for (const BatchBuf& f : batch_bufs(b, 0)) hipFree(*f.p);
+    hipFree(b->logits); hipFree(b->derr);
+}
 extern "C" int lnb_batch_destroy(lnb_batch* b) {
     if (!b) return 0;
     hipSetDevice(b->m->device);
@@ -1825,8 +1860,8 @@ extern "C" int lnb_batch_destroy(lnb_batch* b) {
     if (b->graph_rows) hipGraphExecDestroy(b->graph_rows);
     if (b->stage_graph_long) hipGraphExecDestroy(b->stage_graph_long);
     if (b->scratch_owned) { hipFree(b->e_buf); hipFree(b->z_part); }
-    hipFree(b->tab); hipFree(b->kv); hipFree(b->x); hipFree(b->h); hipFree(b->xt); hipFree(b->q); hipFree(b->att_xt); hipFree(b->ffn_xt); hipFree(b->logits);
-    hipFree(b->derr); hipFree(b->d_tokens); hipFree(b->d_pos); hipFree(b->ring);
+    batch_bufs_free(b);
+    hipFree(b->tab); hipFree(b->kv); hipFree(b->d_tokens); hipFree(b->d_pos); hipFree(b->ring);
     hipFree(b->tp_out); hipFree(b->tp_zpart); hipFree(b->tp_kpart); hipFree(b->tp_cnt);
     if (b->stage_graph) hipGraphExecDestroy(b->stage_graph);
     if (b->ev_done) hipEventDestroy(b->ev_done);
@@ -1856,12 +1891,9 @@ static int batch_alloc(lnb_batch* b) {
     HIPCHK(hipMalloc((void**)&b->kv, kv.size() * sizeof(BatchKV)));
     HIPCHK(hipMemcpyAsync(b->kv, kv.data(), kv.size() * sizeof(BatchKV), hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));                 // (the host copies above are stack / vector memory)
-    const size_t N = (size_t)((std::max(n, LNB_STREAM_COLS) + 15) / 16) * 16, dim = m->a.dim;      // (whole column groups of 16: the 17..32-sequence form keeps B-operand layouts per group)
-    auto zalloc = [&](uint16_t** p, size_t elems) -> int { HIPCHK(hipMalloc((void**)p, elems * 2)); HIPCHK(hipMemsetAsync(*p, 0, elems * 2, b->stream)); return 0; };
     // 1..16 sequences: activations in the B-operand layout [K][16 sequences], the columns past n stay zero for ever; 17..128: plain rows [n][K]
-    if (zalloc(&b->x, N * dim) || zalloc(&b->h, N * dim) || zalloc(&b->xt, N * dim) || zalloc(&b->q, N * m->q_dim) || zalloc(&b->att_xt, N * m->q_dim) ||
-        zalloc(&b->ffn_xt, N * m->ffn_hidden) || (m->last() && zalloc(&b->logits, N * (size_t)m->a.vocab_size))) return -1;
-    HIPCHK(hipMalloc((void**)&b->derr, 16)); HIPCHK(hipMemsetAsync(b->derr, 0, 16, b->stream));
+    // (whole column groups of 16: the 17..32-sequence form keeps B-operand layouts per group)
+    if (batch_bufs_alloc(b, (size_t)((std::max(n, LNB_STREAM_COLS) + 15) / 16) * 16)) return -1;
     HIPCHK(hipMalloc((void**)&b->d_tokens, LNB_BATCH_MAX * 4)); HIPCHK(hipMalloc((void**)&b->d_pos, LNB_BATCH_MAX * 4));
     HIPCHK(hipMalloc((void**)&b->ring, LNB_BATCH_MAX * 4)); HIPCHK(hipMemsetAsync(b->ring, 0, LNB_BATCH_MAX * 4, b->stream));
     std::vector<TokProbOut> to(b->top_k > 0 ? n : 0);
@@ -1898,9 +1930,7 @@ extern "C" int lnb_batch_create(lnb_ctx* const* ctxs, int n, lnb_batch** out) {
         // Round 5: a batch on a model WITHOUT the matrix-core copy runs every product as rows of the streaming product, which reads the RESIDENT
         // weight layouts (gemm_stream_kernel, SRC 1 / 2) -- any number of sequences.  The copy (lnb_model_enable_batch) is a pure performance
         // option: the column forms of up to 32 sequences (mfma_stream_kernel / mfma_pair_kernel) read it and are faster there.
-        if (m->part_begin % 3 || m->part_end % 3) return fail("batched decode needs a stage of whole blocks (this one is cut inside a block: parts [%d, %d))", m->part_begin, m->part_end);
-        if (m->a.dim % 128 || m->q_dim % 128 || m->ffn_hidden % 128)
-            return fail("batched decode streams the weights in 128-step chunks: dim (%d), n_heads*head_dim (%d) and the FFN hidden size (%d) must be multiples of 128", m->a.dim, m->q_dim, m->ffn_hidden);
+        if (batch_shape_check(m, "batched decode")) return -1;
         HIPCHK(lnbk_batch_prepare());
     }
     lnb_batch* b = new lnb_batch();
@@ -1953,6 +1983,19 @@ static int batch_select_form(lnb_batch* b, bool want_long) {
     b->attn_long = want_long;
     return 0;
 }
+// ... for a run that starts at these positions: the largest decides (a frozen sequence's negative position does not move the form)
+static int batch_select_form_at(lnb_batch* b, const int32_t* start_pos) {
+    int max_pos = 0;
+    for (int s = 0; s < b->n; s++) max_pos = std::max(max_pos, start_pos[s]);
+    return batch_select_form(b, batch_want_long(b, max_pos));
+}
+// A call that writes a member's caches from another stream: whatever the context's own stream still does to them comes first, and the call
+// advances (or leaves behind) a device-side position the host no longer knows.
+static int member_drain(lnb_ctx* c) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->dev_pos = -1; c->call_T = 0;
+    return 0;
+}
 static void batch_attn_form(const lnb_batch* b, AttnParams& ap) {
     ap.lds_T = b->lds_T; ap.seq_len = b->attn_long ? b->maxT : b->lds_T;
     ap.longctx = b->attn_long ? 1 : 0; ap.force_zseq = b->attn_long ? (b->force_zseq & 1) : 0;
@@ -1965,144 +2008,108 @@ static hipError_t batch_attn_launch(const lnb_batch* b, AttnParams& ap, hipStrea
     ap.seq_len = b->maxT; ap.longctx = 1; ap.force_zseq = b->rows_zseq;
     return lnbk_attn_rows(&ap, -1, st);
 }
-static StreamParams stream_of(const lnb_batch* b, const uint16_t* w, const uint16_t* xt, int K, int n_rows, int nch) {
-    StreamParams p{}; p.w = w; p.xt = xt; p.K = K; p.n_rows = n_rows; p.nch = nch; p.n_chains = ((n_rows + 15) / 16) * nch; p.nseq = b->n; p.dbg = g_dbg;
-    return p;
-}
+static BatchPlan batch_plan_of(const lnb_batch* b) { return batch_plan(b->n, !b->rows_form, knob(Knob::BATCH_GROUPS)); }
 static bool stream_acc2(const StreamParams& p) { return p.nch == 2 || p.n_chains > 4 * g_num_cus; }   // thin matrices: one tile per wave, every tile on its own SIMD
-// More than 16 sequences: the batch's rows through the prefill's streaming product (gemm_stream_kernel: weights M16 -> A operand, 1 / 2 / 4
-// batch tiles of 16 sequences per wave), plain row-major activations.  Same chains per sequence; EPI_QKV_ROPE and the attention take each
-// row's position and caches from the batch tables.  (xt / att_xt / ffn_xt hold rows here, not the B-operand layout.)
-// (w16 == nullptr -- no matrix-core copy: the resident layout t feeds the same kernel, gemm_stream_kernel SRC 1 / 2)
-static GemmParams wide_of(const lnb_batch* b, const TiledDesc& t, const uint16_t* w16, const uint16_t* x, int K, int n_rows, int nch) {
-    GemmParams g{}; g.w16 = w16; g.w = t.w; g.rw = t.rw; g.nch = nch; g.x = x; g.K = K; g.n_rows = n_rows; g.S = b->n;
-    return g;
-}
-// 17 .. 32 sequences (LNB_BATCH_GROUPS=0: off): the thin matrices -- one k-ordered chain per 16-row tile and 16 columns -- as TWO column groups of
-// mfma_pair_kernel on disjoint CUs (256-384 tiles x 2 groups: every CU carries two chains) instead of rows of gemm_stream_kernel (one chain per
-// wave, its operands unpacked by the same wave); the fat matrices stay rows.  The activations between them change layout at their producers:
-// norm -> xt groups (batch_rmsnorm_xt_kernel), attention -> out_xt groups, SiLU*up epilogue -> out_xt groups.
-static bool batch_groups(const lnb_batch* b) {
-    return knob(Knob::BATCH_GROUPS) && !b->rows_form && b->n > LNB_STREAM_COLS && b->n <= 2 * LNB_STREAM_COLS;
-}
-static int enqueue_batch_kernel_wide(lnb_batch* b, int l, int which) {
-    lnb_model* m = b->m; const lnb_model_args& a = m->a; hipStream_t st = b->stream;
-    const int n = b->n, dim = a.dim, F = m->ffn_hidden;
-    if (batch_groups(b) && which != K_HEAD) {
-        LayerW& L = m->layers[l - m->layer_begin];
-        const int G = (n + LNB_STREAM_COLS - 1) / LNB_STREAM_COLS;
-        auto pair_of = [&](const uint16_t* w, const uint16_t* xt, int K, int n_rows) {
-            StreamParams p{}; p.w = w; p.xt = xt; p.K = K; p.n_rows = n_rows; p.nch = 1; p.n_chains = (n_rows + 15) / 16; p.nseq = n; p.n_groups = G; p.dbg = nullptr;
-            return p;
-        };
-        switch (which) {
-        case K_QKV: {
-            HIPCHK(lnbk_batch_rmsnorm(b->x, L.attn_norm, a.norm_eps, b->xt, dim, n, st));
-            StreamParams p = pair_of(L.m_wqkv, b->xt, dim, L.wqkv.n_rows);
-            p.cis = m->cis; p.q_out = b->q; p.tab = b->tab; p.kv = b->kv + (l - m->layer_begin); p.q_dim = m->q_dim; p.kv_dim = m->kv_dim; p.head_dim = m->head_dim;
-            HIPCHK(lnbk_stream(&p, EPI_QKV_ROPE, 0, g_num_cus, st)); return 0; }
-        case K_ATTN: {
-            AttnParams ap{}; ap.q = b->q; ap.out_xt = b->att_xt; ap.btab = b->tab; ap.bkv = b->kv + (l - m->layer_begin); ap.dbg = nullptr;
-            ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
-            ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
-            ap.zseq_count = b->zseq ? b->zseq : b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;
-            HIPCHK(batch_attn_launch(b, ap, st)); return 0; }
-        case K_WO: {
-            StreamParams p = pair_of(L.m_wo, b->att_xt, m->q_dim, dim); p.out = b->h; p.res = b->x;
-            HIPCHK(lnbk_stream(&p, EPI_RESID, 0, g_num_cus, st)); return 0; }
-        case K_W13: {
-            HIPCHK(lnbk_rmsnorm_rows(b->h, L.ffn_norm, b->xt, n, dim, a.norm_eps, st));
-            GemmParams g = wide_of(b, L.w13, L.m_w13, b->xt, dim, F, 2); g.out = nullptr; g.out_xt = b->ffn_xt; g.silu = m->silu;
-            HIPCHK(lnbk_gemm_stream(&g, EPI_SILU_MUL, g_num_cus, st)); return 0; }
-        case K_W2: {
-            StreamParams p = pair_of(L.m_w2, b->ffn_xt, F, dim); p.out = b->x; p.res = b->h;
-            HIPCHK(lnbk_stream(&p, EPI_RESID, 0, g_num_cus, st)); return 0; }
-        }
-        return fail("bad kernel id");
+// One product of a batched step: what is multiplied and where the result goes.  Through which feed is the plan's business (lnb_batchplan.h).
+// norm_w: the RMSNorm of `in` into b->xt runs in front and the product reads b->xt; nullptr: the product reads `in`.
+struct BatchProd {
+    BatchProduct id; const uint16_t* norm_w; const uint16_t* in;
+    const TiledDesc* t; const uint16_t* m16; int K, n_rows, nch, epi;
+    uint16_t* out = nullptr; uint16_t* out_xt = nullptr; const uint16_t* res = nullptr;
+    const BatchKV* kv = nullptr;           // EPI_QKV_ROPE: the layer's caches
+};
+// The norm launch and the product launch of one product, through the feed the plan gives it.
+// COLUMN with plan.groups (17 .. 32 sequences, LNB_BATCH_GROUPS=0: off): the thin matrices -- one k-ordered chain per 16-row tile and 16 columns -- as
+// TWO column groups of mfma_pair_kernel on disjoint CUs (256-384 tiles x 2 groups: every CU carries two chains) instead of rows of gemm_stream_kernel
+// (one chain per wave, its operands unpacked by the same wave); the fat matrices stay rows.  The activations between them change layout at their
+// producers: norm -> xt groups (batch_rmsnorm_xt_kernel), attention -> out_xt groups, SiLU*up epilogue -> out_xt groups.
+// ROW: the batch's rows through the prefill's streaming product (gemm_stream_kernel: weights M16 -> A operand, 1 / 2 / 4 batch tiles of 16 sequences
+// per wave), plain row-major activations.  Same chains per sequence; EPI_QKV_ROPE and the attention take each row's position and caches from the
+// batch tables.  (xt / att_xt / ffn_xt hold rows here, not the B-operand layout; m16 == nullptr -- no matrix-core copy: the resident layout t feeds
+// the same kernel, gemm_stream_kernel SRC 1 / 2.)
+static int enqueue_batch_product(lnb_batch* b, const BatchPlan& plan, const BatchProd& d) {
+    lnb_model* m = b->m; hipStream_t st = b->stream;
+    const bool column = plan.feed[d.id] == FEED_COLUMN;
+    const uint16_t* x = d.in;
+    if (d.norm_w) {
+        if (column) HIPCHK(lnbk_batch_rmsnorm(d.in, d.norm_w, m->a.norm_eps, b->xt, d.K, b->n, st));
+        else HIPCHK(lnbk_rmsnorm_rows(d.in, d.norm_w, b->xt, b->n, d.K, m->a.norm_eps, st));
+        x = b->xt;
     }
-    if (which == K_HEAD) {
-        HIPCHK(lnbk_rmsnorm_rows(b->x, m->norm, b->xt, n, dim, a.norm_eps, st));
-        GemmParams g = wide_of(b, m->output, m->m_output, b->xt, dim, a.vocab_size, 1); g.out = b->logits;
-        HIPCHK(lnbk_gemm_stream(&g, EPI_STORE, g_num_cus, st));
+    if (column) {
+        const int G = plan.groups;
+        StreamParams p{}; p.w = d.m16; p.xt = x; p.K = d.K; p.n_rows = d.n_rows; p.nch = G ? 1 : d.nch; p.n_chains = ((d.n_rows + 15) / 16) * p.nch;
+        p.nseq = b->n; p.n_groups = G; p.dbg = G ? nullptr : g_dbg;
+        p.out = d.out; p.out_xt = d.out_xt; p.res = d.res;
+        if (d.epi == EPI_SILU_MUL) p.silu = m->silu;
+        if (d.epi == EPI_QKV_ROPE) { p.cis = m->cis; p.q_out = b->q; p.tab = b->tab; p.kv = d.kv; p.q_dim = m->q_dim; p.kv_dim = m->kv_dim; p.head_dim = m->head_dim; }
+        HIPCHK(lnbk_stream(&p, d.epi, G ? 0 : stream_acc2(p), g_num_cus, st));
         return 0;
     }
-    LayerW& L = m->layers[l - m->layer_begin];
-    switch (which) {
-    case K_QKV: {
-        HIPCHK(lnbk_rmsnorm_rows(b->x, L.attn_norm, b->xt, n, dim, a.norm_eps, st));
-        GemmParams g = wide_of(b, L.wqkv, L.m_wqkv, b->xt, dim, L.wqkv.n_rows, 1);
-        g.cis = m->cis; g.q_out = b->q; g.btab = b->tab; g.bkv = b->kv + (l - m->layer_begin); g.q_dim = m->q_dim; g.kv_dim = m->kv_dim; g.head_dim = m->head_dim;
-        HIPCHK(lnbk_gemm_stream(&g, EPI_QKV_ROPE, g_num_cus, st)); return 0; }
-    case K_ATTN: {
-        AttnParams ap{}; ap.q = b->q; ap.out = b->att_xt; ap.out_xt = nullptr; ap.btab = b->tab; ap.bkv = b->kv + (l - m->layer_begin); ap.dbg = nullptr;
-        ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
-        ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
-        ap.zseq_count = b->zseq ? b->zseq : b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
-        HIPCHK(batch_attn_launch(b, ap, st)); return 0; }
-    case K_WO: {
-        GemmParams g = wide_of(b, L.wo, L.m_wo, b->att_xt, m->q_dim, dim, 1); g.out = b->h; g.res = b->x;
-        HIPCHK(lnbk_gemm_stream(&g, EPI_RESID, g_num_cus, st)); return 0; }
-    case K_W13: {
-        HIPCHK(lnbk_rmsnorm_rows(b->h, L.ffn_norm, b->xt, n, dim, a.norm_eps, st));
-        GemmParams g = wide_of(b, L.w13, L.m_w13, b->xt, dim, F, 2); g.out = b->ffn_xt; g.silu = m->silu;
-        HIPCHK(lnbk_gemm_stream(&g, EPI_SILU_MUL, g_num_cus, st)); return 0; }
-    case K_W2: {
-        GemmParams g = wide_of(b, L.w2, L.m_w2, b->ffn_xt, F, dim, 1); g.out = b->x; g.res = b->h;
-        HIPCHK(lnbk_gemm_stream(&g, EPI_RESID, g_num_cus, st)); return 0; }
-    }
-    return fail("bad kernel id");
+    GemmParams g{}; g.w16 = d.m16; g.w = d.t->w; g.rw = d.t->rw; g.nch = d.nch; g.x = x; g.K = d.K; g.n_rows = d.n_rows; g.S = b->n;
+    g.out = d.out; g.out_xt = d.out_xt; g.res = d.res;
+    if (d.epi == EPI_SILU_MUL) g.silu = m->silu;
+    if (d.epi == EPI_QKV_ROPE) { g.cis = m->cis; g.q_out = b->q; g.btab = b->tab; g.bkv = d.kv; g.q_dim = m->q_dim; g.kv_dim = m->kv_dim; g.head_dim = m->head_dim; }
+    HIPCHK(lnbk_gemm_stream(&g, d.epi, g_num_cus, st));
+    return 0;
 }
 // which: K_QKV (attention norm + wq|wk|wv + RoPE + KV append), K_ATTN, K_WO, K_W13 (ffn norm + w1|w3 + SiLU*up), K_W2, K_HEAD (norm + output)
+// A producer writes the layout its consumer's feed reads: the attention for wo, the SiLU*up epilogue of w1|w3 for w2.
 static int enqueue_batch_kernel(lnb_batch* b, int l, int which) {
-    if (b->n > LNB_STREAM_COLS || b->rows_form) return enqueue_batch_kernel_wide(b, l, which);
-    lnb_model* m = b->m; const lnb_model_args& a = m->a; hipStream_t st = b->stream;
-    const int n = b->n, dim = a.dim, F = m->ffn_hidden;
+    lnb_model* m = b->m; const lnb_model_args& a = m->a;
+    const int dim = a.dim, F = m->ffn_hidden;
+    const BatchPlan plan = batch_plan_of(b);
     if (which == K_HEAD) {
-        HIPCHK(lnbk_batch_rmsnorm(b->x, m->norm, a.norm_eps, b->xt, dim, n, st));
-        StreamParams p = stream_of(b, m->m_output, b->xt, dim, a.vocab_size, 1); p.out = b->logits;
-        HIPCHK(lnbk_stream(&p, EPI_STORE, stream_acc2(p), g_num_cus, st));
-        return 0;
+        BatchProd d{BP_HEAD, m->norm, b->x, &m->output, m->m_output, dim, a.vocab_size, 1, EPI_STORE}; d.out = b->logits;
+        return enqueue_batch_product(b, plan, d);
     }
     LayerW& L = m->layers[l - m->layer_begin];
+    const BatchKV* kv = b->kv + (l - m->layer_begin);
     switch (which) {
     case K_QKV: {
-        HIPCHK(lnbk_batch_rmsnorm(b->x, L.attn_norm, a.norm_eps, b->xt, dim, n, st));
-        StreamParams p = stream_of(b, L.m_wqkv, b->xt, dim, L.wqkv.n_rows, 1);
-        p.cis = m->cis; p.q_out = b->q; p.tab = b->tab; p.kv = b->kv + (l - m->layer_begin); p.q_dim = m->q_dim; p.kv_dim = m->kv_dim; p.head_dim = m->head_dim;
-        HIPCHK(lnbk_stream(&p, EPI_QKV_ROPE, stream_acc2(p), g_num_cus, st)); return 0; }
+        BatchProd d{BP_QKV, L.attn_norm, b->x, &L.wqkv, L.m_wqkv, dim, L.wqkv.n_rows, 1, EPI_QKV_ROPE}; d.kv = kv;
+        return enqueue_batch_product(b, plan, d); }
     case K_ATTN: {
-        AttnParams ap{}; ap.q = b->q; ap.out_xt = b->att_xt; ap.btab = b->tab; ap.bkv = b->kv + (l - m->layer_begin); ap.dbg = nullptr;
-        ap.S = n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
+        const bool wo_column = plan.feed[BP_WO] == FEED_COLUMN;
+        AttnParams ap{}; ap.q = b->q; ap.out = wo_column ? nullptr : b->att_xt; ap.out_xt = wo_column ? b->att_xt : nullptr; ap.btab = b->tab; ap.bkv = kv; ap.dbg = nullptr;
+        ap.S = b->n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
         ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
         ap.zseq_count = b->zseq ? b->zseq : b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
-        HIPCHK(batch_attn_launch(b, ap, st)); return 0; }
+        HIPCHK(batch_attn_launch(b, ap, b->stream)); return 0; }
     case K_WO: {
-        StreamParams p = stream_of(b, L.m_wo, b->att_xt, m->q_dim, dim, 1); p.out = b->h; p.res = b->x;
-        HIPCHK(lnbk_stream(&p, EPI_RESID, stream_acc2(p), g_num_cus, st)); return 0; }
+        BatchProd d{BP_WO, nullptr, b->att_xt, &L.wo, L.m_wo, m->q_dim, dim, 1, EPI_RESID}; d.out = b->h; d.res = b->x;
+        return enqueue_batch_product(b, plan, d); }
     case K_W13: {
-        HIPCHK(lnbk_batch_rmsnorm(b->h, L.ffn_norm, a.norm_eps, b->xt, dim, n, st));
-        StreamParams p = stream_of(b, L.m_w13, b->xt, dim, F, 2); p.out_xt = b->ffn_xt; p.silu = m->silu;
-        HIPCHK(lnbk_stream(&p, EPI_SILU_MUL, 1, g_num_cus, st)); return 0; }
+        BatchProd d{BP_W13, L.ffn_norm, b->h, &L.w13, L.m_w13, dim, F, 2, EPI_SILU_MUL};
+        if (plan.feed[BP_W2] == FEED_COLUMN) d.out_xt = b->ffn_xt; else d.out = b->ffn_xt;
+        return enqueue_batch_product(b, plan, d); }
     case K_W2: {
-        StreamParams p = stream_of(b, L.m_w2, b->ffn_xt, F, dim, 1); p.out = b->x; p.res = b->h;
-        HIPCHK(lnbk_stream(&p, EPI_RESID, stream_acc2(p), g_num_cus, st)); return 0; }
+        BatchProd d{BP_W2, nullptr, b->ffn_xt, &L.w2, L.m_w2, F, dim, 1, EPI_RESID}; d.out = b->x; d.res = b->h;
+        return enqueue_batch_product(b, plan, d); }
     }
     return fail("bad kernel id");
 }
-// One batched step of this model STAGE: the embedding gather on the first stage (otherwise the hidden states [n, dim] are already in b->x:
-// received from the stage before), the owned blocks, and on the last stage norm + output + argmax (which advances every sequence's
-// position); a stage without the head advances the positions itself.  ring_in: the first stage of a multi-stage pipeline takes the tokens
-// from the contiguous words the last stage sent (lnb_pipeline_tick_batch).
+// One batched pass over this model STAGE's weights: the embedding gather on the first stage (otherwise the hidden states [n, dim] are
+// already in b->x: received from the stage before), the owned blocks, and on the last stage norm + output.  What follows the logits
+// (token probabilities, argmax, commit, ...) is the caller's.
+static int enqueue_batch_blocks(lnb_batch* b, int l) {
+    for (int k = K_QKV; k <= K_W2; k++) if (enqueue_batch_kernel(b, l, k)) return -1;
+    return 0;
+}
+static int enqueue_batch_pass(lnb_batch* b) {
+    lnb_model* m = b->m;
+    if (m->first()) HIPCHK(lnbk_batch_embed(m->tok_embd, b->tab, b->x, b->n, m->a.dim, m->a.vocab_size, b->derr, b->stream));
+    for (int l = m->layer_begin; l < m->layer_end; l++) if (enqueue_batch_blocks(b, l)) return -1;
+    return m->last() ? enqueue_batch_kernel(b, 0, K_HEAD) : 0;
+}
+// One batched step of this model STAGE: the pass, and on the last stage the argmax (which advances every sequence's position); a stage
+// without the head advances the positions itself.  ring_in: the first stage of a multi-stage pipeline takes the tokens from the contiguous
+// words the last stage sent (lnb_pipeline_tick_batch).
 static int enqueue_batch_step(lnb_batch* b, bool ring_in = false) {
     lnb_model* m = b->m;
-    if (m->first()) {
-        if (ring_in) HIPCHK(lnbk_batch_scatter_ring(b->tab, b->ring, b->stream));
-        HIPCHK(lnbk_batch_embed(m->tok_embd, b->tab, b->x, b->n, m->a.dim, m->a.vocab_size, b->derr, b->stream));
-    }
-    for (int l = m->layer_begin; l < m->layer_end; l++)
-        for (int k = K_QKV; k <= K_W2; k++) if (enqueue_batch_kernel(b, l, k)) return -1;
+    if (ring_in && m->first()) HIPCHK(lnbk_batch_scatter_ring(b->tab, b->ring, b->stream));
+    if (enqueue_batch_pass(b)) return -1;
     if (m->last()) {
-        if (enqueue_batch_kernel(b, 0, K_HEAD)) return -1;
         if (b->top_k > 0) {                                  // (ticks refuse such batches: only lnb_batch_decode[_until] gets here with it)
             TokProbParams p = tp_params(m, b->logits, b->n, b->top_k, b->tp_zpart, b->tp_kpart, b->tp_cnt, b->tp_out, 1);
             HIPCHK(lnbk_token_probs(&p, b->stream));
@@ -2138,26 +2145,14 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
         if (!frozen && (check_call(c, 1, start_pos[s]) || check_call(c, 1, start_pos[s] + n_steps - 1))) return -1;
         if (!frozen && (tokens[s] < 0 || tokens[s] >= m->a.vocab_size)) return fail("sequence %d: token id at index 0 is outside the vocabulary", s);
         if (c->pending) return fail("sequence %d: a lnb_forward_stage_begin has not been ended", s);
-        HIPCHK(hipStreamSynchronize(c->stream));             // whatever the context's own stream still does to its caches comes first
-        c->dev_pos = -1; c->call_T = 0;                      // the batch advances the context's device-side position by itself
+        if (member_drain(c)) return -1;
     }
     for (lnb_ctx* c : b->ctxs) { c->tp_last_k = 0; c->tp_last_n = 0; }
     hipStream_t st = b->stream;
-    int max_pos = 0;
-    for (int s = 0; s < b->n; s++) max_pos = std::max(max_pos, start_pos[s]);         // (a frozen sequence does not move the form)
-    if (batch_select_form(b, batch_want_long(b, max_pos))) return -1;
+    if (batch_select_form_at(b, start_pos)) return -1;
     const bool use_graph = knob(Knob::NO_GRAPH) == 0;
     hipGraphExec_t* const gslot = b->attn_long ? &b->graph_long : &b->graph;       // one captured step per form
-    if (use_graph && !*gslot) {
-        hipGraph_t g = nullptr;
-        HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        int rc = enqueue_batch_step(b);
-        hipError_t e = hipStreamEndCapture(st, &g);
-        if (rc) { if (g) hipGraphDestroy(g); return -1; }
-        HIPCHK(e);
-        HIPCHK(hipGraphInstantiate(gslot, g, nullptr, nullptr, 0));
-        HIPCHK(hipGraphDestroy(g));
-    }
+    if (use_graph && capture_once(gslot, st, [&] { return enqueue_batch_step(b); })) return -1;
     memcpy(b->h_io, tokens, (size_t)b->n * 4); memcpy(b->h_io + LNB_BATCH_MAX, start_pos, (size_t)b->n * 4);
     HIPCHK(hipMemcpyAsync(b->d_tokens, b->h_io, (size_t)b->n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(b->d_pos, b->h_io + LNB_BATCH_MAX, (size_t)b->n * 4, hipMemcpyHostToDevice, st));
@@ -2223,10 +2218,8 @@ extern "C" int lnb_batch_set_state(lnb_batch* b, const int32_t* tokens, const in
                         "token): clear them (lnb_ctx_set_stop_ids(ctx, NULL, 0)) and end the sequence on the host", s, c->n_stop);
         c->dev_pos = -1; c->call_T = 0;
     }
-    { int max_pos = 0;                                       // the ticks that follow run the form this start calls for (lnb_pipeline_tick_batch)
-      for (int s = 0; s < b->n; s++) max_pos = std::max(max_pos, start_pos[s]);
-      if (batch_select_form(b, batch_want_long(b, max_pos))) return -1;
-      b->tick_long = b->attn_long; }
+    if (batch_select_form_at(b, start_pos)) return -1;
+    b->tick_long = b->attn_long;                             // the ticks that follow run the form this start calls for (lnb_pipeline_tick_batch)
     HIPCHK(hipDeviceSynchronize());                          // a setup call: whatever the contexts' streams and the pipe's exchange stream still do
                                                              // (the prefill's token hand-off into the contexts' token words) comes first
     if (tokens) memcpy(b->h_io, tokens, (size_t)b->n * 4);
@@ -2246,7 +2239,7 @@ extern "C" int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int it
     if (iters <= 0 || which < 0 || which > K_LAYER) return fail("bad arguments");
     if (which == K_HEAD && !m->last()) return fail("this stage does not own output.weight");
     for (int s = 0; s < b->n; s++) { if (check_call(b->ctxs[s], 1, pos)) return -1; b->h_io[s] = 0; b->h_io[LNB_BATCH_MAX + s] = pos; b->ctxs[s]->dev_pos = -1; }
-    if (batch_select_form(b, batch_want_long(b, pos))) return -1;
+    if (batch_select_form_at(b, b->h_io + LNB_BATCH_MAX)) return -1;
     hipStream_t st = b->stream;
     HIPCHK(hipMemcpyAsync(b->d_tokens, b->h_io, (size_t)b->n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(b->d_pos, b->h_io + LNB_BATCH_MAX, (size_t)b->n * 4, hipMemcpyHostToDevice, st));
@@ -2255,7 +2248,7 @@ extern "C" int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int it
     auto run = [&](int i) -> int {
         const int l = m->layer_begin + i % nl;
         if (which == K_HEAD) return enqueue_batch_kernel(b, 0, K_HEAD);
-        if (which == K_LAYER) { for (int k = K_QKV; k <= K_W2; k++) if (enqueue_batch_kernel(b, l, k)) return -1; return 0; }
+        if (which == K_LAYER) return enqueue_batch_blocks(b, l);
         return enqueue_batch_kernel(b, l, which);
     };
     for (int i = 0; i < 3; i++) if (run(i)) return -1;
@@ -2307,12 +2300,10 @@ static int append_many_alloc(lnb_model* m) {
     auto bail = [&]() { append_many_free(m); return -1; };
     lnb_batch* b = new lnb_batch();
     am->b = b; b->m = m; b->n = 1; b->scratch_owned = true;
-    const size_t N = LNB_BATCH_MAX, dim = m->a.dim, L = m->layers.size();
+    const size_t N = LNB_BATCH_MAX, L = m->layers.size();
     auto dalloc = [&](void** p, size_t bytes) -> int { HIPCHK(hipMalloc(p, bytes)); HIPCHK(hipMemsetAsync(*p, 0, bytes, b->stream)); return 0; };
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) { fail("lnb_forward_append_many: no stream"); return bail(); }
-    if (dalloc((void**)&b->x, N * dim * 2) || dalloc((void**)&b->h, N * dim * 2) || dalloc((void**)&b->xt, N * dim * 2) || dalloc((void**)&b->q, N * m->q_dim * 2) ||
-        dalloc((void**)&b->att_xt, N * m->q_dim * 2) || dalloc((void**)&b->ffn_xt, N * m->ffn_hidden * 2) || dalloc((void**)&b->logits, N * (size_t)m->a.vocab_size * 2) ||
-        dalloc((void**)&b->derr, 16) || dalloc((void**)&b->tab, sizeof(BatchTab)) || dalloc((void**)&b->kv, L * sizeof(BatchKV)) ||
+    if (batch_bufs_alloc(b, N) || dalloc((void**)&b->tab, sizeof(BatchTab)) || dalloc((void**)&b->kv, L * sizeof(BatchKV)) ||
         dalloc((void**)&am->st, N * sizeof(StepState)) || dalloc((void**)&am->tok, N * 4) || dalloc((void**)&am->dummy_log, 64) || dalloc((void**)&am->zseq, 16) ||
         dalloc((void**)&am->members, sizeof(AmMembers) + L * sizeof(BatchKV)) || dalloc((void**)&am->d_arg, N * 4)) return bail();
     b->zseq = am->zseq;
@@ -2325,8 +2316,6 @@ static int append_many_alloc(lnb_model* m) {
     }
     return 0;
 }
-// layout the activation buffers of a pass of `width` columns are used in: 0 = B-operand columns, 1 = column groups, 2 = rows
-static int append_many_layout(const lnb_batch* b) { return b->n <= LNB_STREAM_COLS && !b->rows_form ? 0 : batch_groups(b) ? 1 : 2; }
 extern "C" int lnb_model_append_many_info(const lnb_model* m, int* passes, int* max_columns, int* long_passes) {
     if (!m) return fail("lnb_model_append_many_info: null argument (model)");
     const AppendMany* am = m->am;
@@ -2353,8 +2342,7 @@ extern "C" int lnb_forward_append_many(lnb_ctx* const* ctxs, int n, const int32_
     lnb_model* m = ctxs[0]->m;
     for (int s = 0; s < n; s++) if (ctxs[s]->m != m) return fail("%s: context %d belongs to another lnb_model handle", name, s);
     if (!m->first() || !m->last()) return fail("%s needs a whole-model handle: pipeline stages have no append", name);
-    if (m->a.dim % 128 || m->q_dim % 128 || m->ffn_hidden % 128)
-        return fail("%s streams the weights in 128-step chunks: dim (%d), n_heads*head_dim (%d) and the FFN hidden size (%d) must be multiples of 128", name, m->a.dim, m->q_dim, m->ffn_hidden);
+    if (batch_shape_check(m, name)) return -1;
     const int V = m->a.vocab_size;
     int64_t total = 0;
     for (int s = 0; s < n; s++) {
@@ -2413,10 +2401,7 @@ extern "C" int lnb_forward_append_many(lnb_ctx* const* ctxs, int n, const int32_
                 return fail("%s: no pinned host memory for the logits of a pass (%zu bytes)", name, (size_t)LNB_BATCH_MAX * V * 2);
             }
     // ---- from here on the caches are written
-    for (int s = 0; s < n; s++) {
-        HIPCHK(hipStreamSynchronize(ctxs[s]->stream));       // whatever the member's own stream still does to its caches comes first
-        ctxs[s]->dev_pos = -1; ctxs[s]->call_T = 0;
-    }
+    for (int s = 0; s < n; s++) if (member_drain(ctxs[s])) return -1;
     struct SyncOnExit { hipStream_t s; ~SyncOnExit() { hipStreamSynchronize(s); } } sync_on_exit{st};     // (the uploads below read `rows` and `members`: no way out before the stream has drained)
     HIPCHK(hipMemcpyAsync(am->rows, rows.data(), (size_t)total * sizeof(AmRow), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(am->members, members.data(), members.size(), hipMemcpyHostToDevice, st));
@@ -2434,20 +2419,13 @@ extern "C" int lnb_forward_append_many(lnb_ctx* const* ctxs, int n, const int32_
         bool lng = false; int maxT = 0;
         for (int g = 0; g < ns; g++) { const lnb_ctx* c = ctxs[segs[g].member]; maxT = std::max(maxT, c->seq_len); lng = lng || c->seq_len > c->attn_short_cap; }
         b->n = width; b->maxT = maxT; b->lds_T = std::min(maxT, ctxs[0]->attn_short_cap); b->must_long = lng; b->attn_long = lng;
-        const int layout = append_many_layout(b);
-        if (am->last_layout >= 0 && (layout != am->last_layout || width < am->last_width)) {       // dead columns are zero again
-            const size_t N = LNB_BATCH_MAX, dim = m->a.dim;
-            HIPCHK(hipMemsetAsync(b->x, 0, N * dim * 2, st)); HIPCHK(hipMemsetAsync(b->h, 0, N * dim * 2, st)); HIPCHK(hipMemsetAsync(b->xt, 0, N * dim * 2, st));
-            HIPCHK(hipMemsetAsync(b->q, 0, N * m->q_dim * 2, st)); HIPCHK(hipMemsetAsync(b->att_xt, 0, N * m->q_dim * 2, st)); HIPCHK(hipMemsetAsync(b->ffn_xt, 0, N * m->ffn_hidden * 2, st));
-        }
+        const int layout = batch_plan_layout(batch_plan_of(b));      // what the activation buffers of this pass hold: B-operand columns, column groups or rows
+        if (am->last_layout >= 0 && (layout != am->last_layout || width < am->last_width) && batch_bufs_zero(b, LNB_BATCH_MAX)) return -1;       // dead columns are zero again
         am->last_layout = layout; am->last_width = width;
         AmPass ap{}; ap.rows = am->rows + row0; ap.members = (const AmMembers*)am->members; ap.member_kv = (const BatchKV*)(am->members + sizeof(AmMembers));
         ap.tab = b->tab; ap.kv = b->kv; ap.st = am->st; ap.tok = am->tok; ap.width = width; ap.n_layers = (int)L;
         HIPCHK(lnbk_append_many_setup(&ap, st));
-        HIPCHK(lnbk_batch_embed(m->tok_embd, b->tab, b->x, width, m->a.dim, V, b->derr, st));
-        for (int l = m->layer_begin; l < m->layer_end; l++)
-            for (int k = K_QKV; k <= K_W2; k++) if (enqueue_batch_kernel(b, l, k)) return -1;
-        if (enqueue_batch_kernel(b, 0, K_HEAD)) return -1;
+        if (enqueue_batch_pass(b)) return -1;
         HIPCHK(lnbk_append_many_finish(b->logits, V, am->rows + row0, width, am->d_arg, st));
         if (logits_out) {
             HIPCHK(hipMemcpyAsync(am->pin[pass & 1], b->logits, (size_t)width * V * 2, hipMemcpyDeviceToHost, st));
@@ -2599,21 +2577,16 @@ static int spec_verify_batch(lnb_ctx* c, int w, int form, lnb_batch** out) {
     b->e_buf = c->sp_e_buf; b->z_part = c->sp_z_part;
     b->attn_long = long_form; b->attn_rows = form == 2; b->rows_zseq = c->rows_flags & 1;
     hipGraphExec_t* const gslot = form == 2 ? &b->graph_rows : long_form ? &b->graph_long : &b->graph;
-    if (*gslot) { *out = b; return 0; }
-    auto drop = [&]() { if (fresh) { c->sp_b[w] = nullptr; lnb_batch_destroy(b); } };
-    hipGraph_t g = nullptr;
-    if (hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { drop(); return fail("hipStreamBeginCapture failed"); }
-    int rc = 0;
-    if (lnbk_batch_embed(m->tok_embd, b->tab, b->x, w, m->a.dim, m->a.vocab_size, b->derr, b->stream) != hipSuccess) rc = fail("verify pass: embedding launch failed");
-    for (int l = m->layer_begin; l < m->layer_end && !rc; l++)
-        for (int k = K_QKV; k <= K_W2 && !rc; k++) rc = enqueue_batch_kernel(b, l, k);
-    if (!rc) rc = enqueue_batch_kernel(b, 0, K_HEAD);
-    if (!rc && lnbk_spec_argmax(b->logits, m->a.vocab_size, w, c->sp_g, b->stream) != hipSuccess) rc = fail("verify pass: argmax launch failed");
-    if (!rc && lnbk_spec_commit(c->sp_g, w, b->tab, b->stream) != hipSuccess) rc = fail("verify pass: commit launch failed");
-    hipError_t e = hipStreamEndCapture(b->stream, &g);
-    if (!rc && e == hipSuccess) e = hipGraphInstantiate(gslot, g, nullptr, nullptr, 0);
-    if (g) hipGraphDestroy(g);
-    if (rc || e != hipSuccess) { drop(); return rc ? rc : fail("verify graph: %s", hipGetErrorString(e)); }
+    auto body = [&]() -> int {
+        if (enqueue_batch_pass(b)) return -1;
+        HIPCHK(lnbk_spec_argmax(b->logits, m->a.vocab_size, w, c->sp_g, b->stream));
+        HIPCHK(lnbk_spec_commit(c->sp_g, w, b->tab, b->stream));
+        return 0;
+    };
+    if (capture_once(gslot, b->stream, body)) {
+        if (fresh) { c->sp_b[w] = nullptr; lnb_batch_destroy(b); }      // (a batch without a graph is not kept)
+        return -1;
+    }
     *out = b;
     return 0;
 }
@@ -2644,8 +2617,7 @@ extern "C" int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, 
     if (max_steps > c->dout_cap) return fail("max_steps %d exceeds the context length %d", max_steps, c->dout_cap);
     if (check_call(c, 1, start_pos) || check_call(c, 1, start_pos + max_steps - 1)) return -1;
     if (token < 0 || token >= m->a.vocab_size) return fail("token id at index 0 is outside the vocabulary");
-    if (m->a.dim % 128 || m->q_dim % 128 || m->ffn_hidden % 128)
-        return fail("the verify pass streams the weights in 128-step chunks: dim (%d), n_heads*head_dim (%d) and the FFN hidden size (%d) must be multiples of 128", m->a.dim, m->q_dim, m->ffn_hidden);
+    if (batch_shape_check(m, "the verify pass")) return -1;
     if (!m->batch_enabled) HIPCHK(lnbk_batch_prepare());
     const int n_text = n_history + 1;
     if (spec_alloc(c, n_text) || capture_decode_graphs(c, start_pos, max_steps)) return -1;
@@ -2897,17 +2869,10 @@ static int enqueue_stage_step(lnb_pipe* p, lnb_ctx* c, const int32_t* tokens, in
     c->attn_long = longctx;
     if (rows == 1 && !tokens && p->use_graph) {
         hipGraphExec_t* slot = &c->stage_graph[longctx ? 1 : 0];
-        if (!*slot) {
-            hipGraph_t g = nullptr;
-            HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            int rc = body(false);
-            if (!rc && lnbk_advance_state(c->st, 1, st) != hipSuccess) rc = fail("advance_state launch failed");
-            hipError_t e = hipStreamEndCapture(st, &g);
-            if (rc) { if (g) hipGraphDestroy(g); return -1; }
-            HIPCHK(e);
-            HIPCHK(hipGraphInstantiate(slot, g, nullptr, nullptr, 0));
-            HIPCHK(hipGraphDestroy(g));
-        }
+        if (capture_once(slot, st, [&]() -> int {
+                if (body(false)) return -1;
+                return lnbk_advance_state(c->st, 1, st) != hipSuccess ? fail("advance_state launch failed") : 0;
+            })) return -1;
         if (c->dev_pos != pos) HIPCHK(ctx_set_state(c, pos, 0, true));
         c->call_T = 0;
         HIPCHK(hipGraphLaunch(*slot, st));
@@ -3064,16 +3029,7 @@ extern "C" int lnb_pipeline_tick_batch(lnb_pipe* p, lnb_batch* run, lnb_batch* s
         if (batch_select_form(run, run->tick_long)) return -1;       // the form lnb_batch_set_state chose for this run of ticks
         if (p->use_graph) {
             hipGraphExec_t* const gslot = run->attn_long ? &run->stage_graph_long : &run->stage_graph;
-            if (!*gslot) {
-                hipGraph_t g = nullptr;
-                HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-                int rc = enqueue_batch_step(run, ring_in);
-                hipError_t e = hipStreamEndCapture(st, &g);
-                if (rc) { if (g) hipGraphDestroy(g); return -1; }
-                HIPCHK(e);
-                HIPCHK(hipGraphInstantiate(gslot, g, nullptr, nullptr, 0));
-                HIPCHK(hipGraphDestroy(g));
-            }
+            if (capture_once(gslot, st, [&] { return enqueue_batch_step(run, ring_in); })) return -1;
             HIPCHK(hipGraphLaunch(*gslot, st));
         } else if (enqueue_batch_step(run, ring_in)) return -1;
         run->last_form = run->attn_long ? 1 : 0;

@@ -166,6 +166,49 @@ def test_column_group_batch_of_17_to_32_sequences_at_the_8b_shape(lnb):
     gm.close()
 
 
+def test_the_boundary_widths_of_the_feed_plan_equal_single_sequence_runs(lnb):
+    """csrc/lnb_batchplan.h: 16 | 17 and 32 | 33 sequences are where a batched step changes form with the matrix-core copy (B-operand columns, two
+    column groups, rows); without the copy every width runs rows.  One seed, two model handles (without / with lnb_model_enable_batch), widths
+    3, 16, 17, 32, 33, four steps from distinct short prompts: every member's tokens and K / V rows are bit for bit those of its own
+    single-sequence run (computed once, on the handle without the copy)."""
+    cfg = CFGS["tiny_hd64"]
+    steps, widths, V = 4, (3, 16, 17, 32, 33), cfg["vocab_size"]
+    plain = lnb.LlamaTransformer(**cfg).fill_synthetic(707).finalize()
+    copied = lnb.LlamaTransformer(**cfg).fill_synthetic(707).finalize().enable_batch()
+    assert plain.batch_bytes() == 0 and copied.batch_bytes() > 0
+    N = max(widths)
+    plens = [3 + (5 * s) % 11 for s in range(N)]                                   # 3..13 tokens: different positions per column
+    prompts = [lnb.synth_tokens(7000 + s, plens[s], V) for s in range(N)]
+    assert len({p.tobytes() for p in prompts}) == N
+    refs = []                                                                      # per sequence: first token, the four tokens, the K / V rows per layer
+    for s in range(N):
+        c = lnb.InferenceContext(plain, plens[s] + steps + 2)
+        _, f = c.Forward(prompts[s], 0, want_logits=False)
+        toks, _ = c.decode_greedy(f, plens[s], steps)
+        T = plens[s] + steps
+        refs.append((f, [int(t) for t in toks], [(c.CacheK(l)[:T].copy(), c.CacheV(l)[:T].copy()) for l in range(cfg["n_layers"])]))
+        c.close()
+    for gm in (plain, copied):
+        for n in widths:
+            ctxs = [lnb.InferenceContext(gm, plens[s] + steps + 2) for s in range(n)]
+            firsts = [ctxs[s].Forward(prompts[s], 0, want_logits=False)[1] for s in range(n)]
+            assert firsts == [refs[s][0] for s in range(n)]
+            b = lnb.Batch(ctxs)
+            got, _ = b.decode(firsts, plens[:n], steps)
+            for s in range(n):
+                tag = (gm is copied, n, s)
+                assert [int(t) for t in got[s]] == refs[s][1], tag
+                T = plens[s] + steps
+                for l in range(cfg["n_layers"]):
+                    k, v = ctxs[s].CacheK(l)[:T], ctxs[s].CacheV(l)[:T]
+                    assert k.dtype == refs[s][2][l][0].dtype and k.tobytes() == refs[s][2][l][0].tobytes(), tag + (l, "K")
+                    assert v.tobytes() == refs[s][2][l][1].tobytes(), tag + (l, "V")
+            b.close()
+            for c in ctxs:
+                c.close()
+    plain.close(); copied.close()
+
+
 def test_batch_argument_checks(lnb):
     cfg = dict(orc.TINY)
     gm = lnb.LlamaTransformer(**cfg).fill_synthetic(1).finalize()
