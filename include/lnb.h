@@ -349,6 +349,45 @@ int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, int n_histo
 int lnb_op_ngram_draft(int device, const int32_t* text, int n_text, const int32_t* corpus, int n_corpus,
                        int ngram_min, int ngram_max, int max_draft, int32_t* out, int* n_out);
 
+/* ---- speculative greedy decoding of MANY contexts: every member drafts for itself, one pass over the weights verifies them all --------------
+ * lnb_decode_speculative_until reads the weights once per pass of ONE context; lnb_batch_decode_until serves many contexts per pass, one column
+ * each.  This call joins them: a pass of up to col_budget columns whose columns are consecutive rows of several members -- a pass of
+ * lnb_forward_append_many, column i of a member the one-token step at pos + i, bit for bit -- with the n-gram draft, the packing and the commit
+ * done per member on the device (DESIGN.md "Speculative decoding of many contexts").
+ *   Contract: for every member s, out_tokens[s * max_steps .. + n_generated[s]), n_generated[s], finished[s] and the KV rows
+ *   [0, start_pos[s] + n_generated[s]) of every layer are BIT-IDENTICAL to lnb_decode_greedy_until(ctxs[s], tokens[s], start_pos[s], max_steps, ...)
+ *   run alone on a context holding the same rows below start_pos[s]; the member's stop ids are applied as that loop applies them.  Rows beyond
+ *   that range may hold rejected drafts (as after lnb_decode_speculative_until).  start_pos[s] < 0: member s is skipped -- nothing of it is
+ *   touched, n_generated[s] = 0, finished[s] = 1 (a member that finished in an earlier call of a chunked run, as in lnb_batch_decode_until).
+ *   Nothing else of a member changes; its cached device position is invalidated; afterwards every entry point continues it.
+ *   Drafts: each member's own lnb_ctx_set_draft settings (max_draft 0: it never drafts and takes one column per pass); its draft is exactly
+ *   ngram_draft_kernel's for it -- R = history[s], tokens[s], its generated tokens; the same match rule and cuts.
+ *   One pass: A = the members still running (not skipped, not finished, fewer than max_steps tokens), in member order; each gets one column for
+ *   its current token; the budget - |A| columns left are granted level by level -- for j = 1..15, for s in A in order: if member s's draft has at
+ *   least j tokens and a column is left, s gets one more.  Members occupy consecutive columns in member order at positions pos, pos + 1, ...
+ *   After the pass a_s = the longest prefix of member s's columns whose argmax equals the next column's input; the argmax of its columns 0 .. a_s
+ *   is emitted as the greedy loop emits (token log, position, token word; a stop token is emitted and freezes the member).  Finished members
+ *   contribute no columns: passes narrow as a run drains.  The call returns when A is empty.  The host reads one pinned block per pass.
+ *   col_budget: n..128, or 0 = the default 16 * ceil(n / 16) -- the products work in tiles of 16 columns (with n = 16 the default grants no drafts).
+ *   stats[s] (the array may be NULL): passes = passes in which s had a column, verify_passes = those in which it had a granted draft, drafted =
+ *   granted draft tokens, accepted = n_generated[s] - passes.  info (may be NULL): the passes of the call, those with any draft, the sum and the
+ *   maximum of their widths, the passes that ran the long-context attention pair (a running member's capacity beyond the one-workgroup kernels'
+ *   reach, as in lnb_forward_append_many).  ms_out (optional): HIP-event time of the whole loop.
+ *   The call waits for every member's stream, runs on the stream of lnb_forward_append_many's pass object and under its mutex, and returns when
+ *   everything has finished.
+ *   Refused, each with a message, arguments before any handle is dereferenced and everything before any cache is written: a NULL array or entry
+ *   (history[s] may be NULL when n_history[s] is 0; finished, stats, info, ms_out may be NULL); n outside 1..128; a context that appears twice; a
+ *   negative n_history[s]; max_steps <= 0 or beyond a member's token log; col_budget outside {0, n..128}; members of different lnb_model handles;
+ *   a handle that is not the whole model; a member in LNB_MODE_FAST, with token probabilities on, with a pending lnb_forward_stage_begin or in a
+ *   live batch; a token outside the vocabulary; start_pos[s] + max_steps beyond the member's KV cache or the RoPE table; dim, n_heads*head_dim or
+ *   the FFN hidden size not a multiple of 128; long-context attention scratch that cannot be allocated.
+ * Which callers belong here, which to lnb_batch_decode_until and which to lnb_decode_speculative_until: profiles/spec_many.md. */
+typedef struct lnb_spec_many_info { int64_t passes, verify_passes, columns, max_columns, long_passes; } lnb_spec_many_info;
+int lnb_decode_speculative_many(lnb_ctx* const* ctxs, int n, const int32_t* const* history, const int32_t* n_history,
+                                const int32_t* tokens, const int32_t* start_pos, int max_steps, int col_budget,
+                                int32_t* out_tokens, int32_t* n_generated, int32_t* finished,
+                                lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out);
+
 /* ---- token probabilities: how likely each generated (or given) token was, exactly as the reference's own Softmax gives it ----------
  * For one logits row x[0..V) (bf16 values widened to f32: what lnb_forward returns -- the reference's Forward, llamatransformer.go:170-177):
  *   Z       = sum_{j ascending} exp(f64(x_j)) in f64: ml.Softmax's serial rowExpSum (operations_impl.go:478-511);

@@ -73,6 +73,9 @@ hipError_t lnbk_ngram_draft(const DraftParams* p, hipStream_t st);
 hipError_t lnbk_kv_fork(const KvForkTab* tab, int nt, int split, hipStream_t st);
 hipError_t lnbk_append_many_setup(const AmPass* p, hipStream_t st);
 hipError_t lnbk_append_many_finish(const uint16_t* logits, int V, const AmRow* rows, int width, int32_t* out, hipStream_t st);
+hipError_t lnbk_spec_many_draft(const SmPass* p, hipStream_t st);
+hipError_t lnbk_spec_many_pack(const SmPass* p, hipStream_t st);
+hipError_t lnbk_spec_many_commit(const SmPass* p, hipStream_t st);
 }
 
 // The HIP runtime spreads a process's streams over a fixed number of hardware queues (its default: 4) and streams that share a queue run one
@@ -2271,6 +2274,13 @@ extern "C" int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int it
 //     the buffers are zeroed whenever a pass is narrower than the one before or changes layout (B-operand columns / column groups / rows);
 //   * nothing may advance a position or log a token: batch_argmax_kernel and spec_commit_kernel are never launched, the tab's token logs point at a
 //     dummy with capacity 0, and only append_many_finish_kernel reads the logits.
+// lnb_decode_speculative_many's own tables beside the pass object (created on its first call): SmPass's device arrays in one allocation, the
+// members' text heads (history ++ token, concatenated; grown on demand), the pinned block the pack kernel reports into, the events of the loop
+struct SpecMany {
+    char* dev = nullptr; SmPass p{};
+    int32_t* text = nullptr; size_t text_cap = 0;
+    int32_t* word = nullptr; hipEvent_t ev = nullptr, ev0 = nullptr, ev1 = nullptr;
+};
 struct AppendMany {
     lnb_batch* b = nullptr;                 // stream, activation buffers and logits for LNB_BATCH_MAX columns, tab / kv filled per pass
     StepState* st = nullptr; int32_t* tok = nullptr; int32_t* dummy_log = nullptr; int* zseq = nullptr;
@@ -2281,7 +2291,9 @@ struct AppendMany {
     int scratch_n = 0, scratch_T = 0;       // what b->e_buf / b->z_part hold: columns x positions of the long-context pair
     int last_layout = -1, last_width = 0;   // what the activation buffers were last used as
     int passes = 0, max_columns = 0, long_passes = 0;      // lnb_model_append_many_info
+    SpecMany* sm = nullptr;                 // lnb_decode_speculative_many runs its passes on this object
 };
+static void spec_many_free(SpecMany* sm);
 static void append_many_free(lnb_model* m) {
     AppendMany* am = m->am;
     if (!am) return;
@@ -2289,6 +2301,7 @@ static void append_many_free(lnb_model* m) {
     hipFree(am->st); hipFree(am->tok); hipFree(am->dummy_log); hipFree(am->zseq); hipFree(am->rows); hipFree(am->members); hipFree(am->d_arg);
     if (am->h_arg) hipHostFree(am->h_arg);
     for (int i = 0; i < 2; i++) { if (am->pin[i]) hipHostFree(am->pin[i]); if (am->ev[i]) hipEventDestroy(am->ev[i]); }
+    spec_many_free(am->sm);
     if (am->b) lnb_batch_destroy(am->b);
     delete am;
     m->am = nullptr;
@@ -2711,6 +2724,196 @@ extern "C" int lnb_op_ngram_draft(int device, const int32_t* text, int n_text, c
     if (word[0] < 0 || word[0] > max_draft) return fail("internal error: draft length %d", word[0]);
     for (int i = 0; i < word[0]; i++) out[i] = h[1 + i];
     *n_out = word[0];
+    return 0;
+}
+
+// ---- lnb_decode_speculative_many (include/lnb.h): speculative greedy decoding of n contexts together.  Every pass is a pass of lnb_forward_append_many on
+// the model handle's AppendMany object -- same buffers, stream, mutex and "dead columns are zero" duty -- whose row table the device writes itself:
+//   spec_many_draft_kernel (every member's n-gram draft) -> spec_many_pack_kernel (the grant rule of lnb_specpack.h, the AmRow table, the pinned block)
+//   -> [host: reads {width, any_draft, running, largest seq_len}, its one round trip per pass] -> append_many_setup_kernel -> the batched step
+//   -> spec_many_commit_kernel (argmax per column, acceptance and emission per member into the member's OWN state, token word and log).
+// The launches are eager, as lnb_forward_append_many's are (profiles/spec_many.md).
+static void spec_many_free(SpecMany* sm) {
+    if (!sm) return;
+    hipFree(sm->dev); hipFree(sm->text);
+    if (sm->word) hipHostFree(sm->word);
+    for (hipEvent_t e : {sm->ev, sm->ev0, sm->ev1}) if (e) hipEventDestroy(e);
+    delete sm;
+}
+static int spec_many_build(SpecMany* sm, hipStream_t st) {
+    const size_t N = LNB_BATCH_MAX;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_mem = carve(N * sizeof(SmMember)), o_want = carve(N * 4), o_run = carve(N * 4), o_draft = carve(N * LNB_SPEC_MAX_DRAFT * 4),
+                 o_best = carve(N * 2 * LNB_SPEC_MAX_NGRAM * 4), o_cnt = carve((N + 1) * 4), o_rows = carve(N * sizeof(AmRow)), o_seg = carve(N * sizeof(SmSeg)),
+                 o_stats = carve(N * sizeof(SmStats)), o_g = carve(N * 4);
+    HIPCHK(hipMalloc((void**)&sm->dev, off));
+    HIPCHK(hipMemsetAsync(sm->dev, 0, off, st));
+    HIPCHK(hipHostMalloc((void**)&sm->word, 16, hipHostMallocMapped));
+    int32_t* word_dev = nullptr;
+    HIPCHK(hipHostGetDevicePointer((void**)&word_dev, sm->word, 0));
+    HIPCHK(hipEventCreate(&sm->ev));
+    HIPCHK(hipEventCreate(&sm->ev0)); HIPCHK(hipEventCreate(&sm->ev1));
+    HIPCHK(hipStreamSynchronize(st));
+    SmPass& p = sm->p; char* d = sm->dev;
+    p.members = (const SmMember*)(d + o_mem); p.want = (int32_t*)(d + o_want); p.running = (int32_t*)(d + o_run); p.draft = (int32_t*)(d + o_draft);
+    p.best = (int*)(d + o_best); p.cnt = (unsigned*)(d + o_cnt); p.rows = (AmRow*)(d + o_rows); p.seg = (SmSeg*)(d + o_seg);
+    p.stats = (SmStats*)(d + o_stats); p.g = (int32_t*)(d + o_g); p.word = word_dev;
+    return 0;
+}
+// the object is published only when all of it exists: a failed allocation leaves the handle as it was, and the next call starts over
+static int spec_many_alloc(AppendMany* am) {
+    if (am->sm) return 0;
+    SpecMany* sm = new SpecMany();
+    if (spec_many_build(sm, am->b->stream)) { (void)hipGetLastError(); spec_many_free(sm); return -1; }
+    am->sm = sm;
+    return 0;
+}
+extern "C" int lnb_decode_speculative_many(lnb_ctx* const* ctxs, int n, const int32_t* const* history, const int32_t* n_history,
+                                           const int32_t* tokens, const int32_t* start_pos, int max_steps, int col_budget,
+                                           int32_t* out_tokens, int32_t* n_generated, int32_t* finished,
+                                           lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out) {
+    const char* const name = "lnb_decode_speculative_many";
+    // ---- the arguments alone: no handle is dereferenced
+    if (!ctxs || !history || !n_history || !tokens || !start_pos || !out_tokens || !n_generated)
+        return fail("%s: null argument (%s)", name, !ctxs ? "ctxs" : !history ? "history" : !n_history ? "n_history" : !tokens ? "tokens" : !start_pos ? "start_pos" :
+                    !out_tokens ? "out_tokens" : "n_generated");
+    if (n < 1 || n > LNB_BATCH_MAX) return fail("%s: a call takes 1..%d contexts (got %d)", name, LNB_BATCH_MAX, n);
+    if (max_steps <= 0) return fail("%s: max_steps must be positive (got %d)", name, max_steps);
+    if (col_budget != 0 && (col_budget < n || col_budget > LNB_BATCH_MAX))
+        return fail("%s: col_budget must be 0 (the default) or %d..%d, one column per member at least (got %d)", name, n, LNB_BATCH_MAX, col_budget);
+    for (int s = 0; s < n; s++) {
+        if (!ctxs[s]) return fail("%s: null context at index %d", name, s);
+        if (n_history[s] < 0) return fail("%s: member %d: negative history length %d", name, s, n_history[s]);
+        if (n_history[s] > 0 && !history[s]) return fail("%s: member %d: null history of %d tokens", name, s, n_history[s]);
+        for (int r = 0; r < s; r++) if (ctxs[r] == ctxs[s]) return fail("%s: context %d appears twice (also at index %d)", name, s, r);
+    }
+    // ---- the handles: everything is checked before any cache is written
+    lnb_model* m = ctxs[0]->m;
+    for (int s = 0; s < n; s++) if (ctxs[s]->m != m) return fail("%s: context %d belongs to another lnb_model handle", name, s);
+    if (!m->first() || !m->last()) return fail("%s needs a whole-model handle: pipeline stages have no speculative decoding", name);
+    if (batch_shape_check(m, name)) return -1;
+    const int V = m->a.vocab_size, cap = ctxs[0]->attn_short_cap;
+    const int budget = col_budget ? col_budget : LNB_STREAM_COLS * ((n + LNB_STREAM_COLS - 1) / LNB_STREAM_COLS);
+    int n_levels = 1, need_T = 0; bool any_long = false; size_t text_total = 0;
+    for (int s = 0; s < n; s++) {
+        const lnb_ctx* c = ctxs[s];
+        if (c->mode != LNB_MODE_EXACT) return fail("%s: context %d is in the tolerance mode: the call is exact-mode only", name, s);
+        if (c->top_k > 0) return fail("%s: context %d records token probabilities, which the call does not: lnb_ctx_set_token_probs(ctx, 0) first", name, s);
+        if (c->pending) return fail("%s: context %d: a lnb_forward_stage_begin has not been ended", name, s);
+        if (c->batch_users > 0) return fail("%s: context %d is a member of %d live batch(es): lnb_batch_destroy first", name, s, c->batch_users);
+        if (max_steps > c->dout_cap) return fail("%s: member %d: max_steps %d exceeds its token log of %d", name, s, max_steps, c->dout_cap);
+        if (start_pos[s] < 0) continue;                      // skipped: a member that finished in an earlier call of a chunked run
+        if (tokens[s] < 0 || tokens[s] >= V) return fail("%s: member %d: token id %d is outside the vocabulary", name, s, tokens[s]);
+        const int64_t T = (int64_t)start_pos[s] + max_steps;
+        if (T > m->cis_rows) return fail("%s: member %d: position %lld is beyond the %d-row RoPE table", name, s, (long long)T, m->cis_rows);
+        if (T > c->seq_len) return fail("%s: member %d: position %lld is beyond the KV cache of %d", name, s, (long long)T, c->seq_len);
+        if (lnbk_attn_long_layout_lds(c->seq_len) > 160 * 1024) return fail("%s: member %d: seq_len %d is beyond what the long-context attention keeps in the LDS", name, s, c->seq_len);
+        if (c->sp_max_draft > 0) n_levels = std::max(n_levels, c->sp_ngram_max - c->sp_ngram_min + 1);
+        need_T = std::max(need_T, c->seq_len); any_long = any_long || c->seq_len > c->attn_short_cap;
+        text_total += (size_t)n_history[s] + 1;
+    }
+    std::lock_guard<std::mutex> lock(m->am_mu);
+    HIPCHK(hipSetDevice(m->device));
+    HIPCHK(lnbk_batch_prepare());
+    if (append_many_alloc(m)) return -1;
+    AppendMany* am = m->am; lnb_batch* b = am->b; hipStream_t st = b->stream;
+    if (spec_many_alloc(am)) return -1;
+    SpecMany* sm = am->sm;
+    if (any_long && (budget > am->scratch_n || need_T > am->scratch_T)) {
+        const int sn = std::max(budget, am->scratch_n), sT = std::max(need_T, am->scratch_T);
+        hipFree(b->e_buf); hipFree(b->z_part); b->e_buf = nullptr; b->z_part = nullptr; am->scratch_n = am->scratch_T = 0;
+        if (attn_long_scratch(sn, m->a.n_heads, sT, &b->e_buf, &b->z_part, name)) return -1;
+        am->scratch_n = sn; am->scratch_T = sT;
+    }
+    if (text_total > sm->text_cap) {
+        int32_t* t = nullptr;
+        if (hipMalloc((void**)&t, text_total * 4) != hipSuccess) { (void)hipGetLastError(); return fail("%s: no device memory for the members' histories (%zu bytes)", name, text_total * 4); }
+        hipFree(sm->text); sm->text = t; sm->text_cap = text_total;
+    }
+    // ---- the call's tables on the host: the members' cache lengths and pointers (as lnb_forward_append_many's), their SmMember, their text heads
+    const size_t L = m->layers.size();
+    std::vector<char> members(sizeof(AmMembers) + L * sizeof(BatchKV));
+    std::vector<SmMember> smm(LNB_BATCH_MAX, SmMember{});
+    std::vector<int32_t> text(std::max<size_t>(text_total, 1));
+    { AmMembers* hm = (AmMembers*)members.data(); BatchKV* hk = (BatchKV*)(members.data() + sizeof(AmMembers));
+      hm->n = n;
+      size_t t0 = 0;
+      for (int s = 0; s < LNB_BATCH_MAX; s++) {
+          const lnb_ctx* c = ctxs[s < n ? s : 0];
+          hm->seq_len[s] = c->seq_len;
+          for (size_t l = 0; l < L; l++) { hk[l].ck[s] = c->ck[l]; hk[l].cv[s] = c->cv[l]; }
+          if (s >= n || start_pos[s] < 0) continue;
+          SmMember& e = smm[s];
+          e.st = c->st; e.tok = c->dtok; e.log = c->dout; e.log_cap = c->dout_cap; e.seq_len = c->seq_len; e.active = 1;
+          e.text = sm->text + t0; e.n_text = n_history[s] + 1;
+          if (n_history[s] > 0) memcpy(text.data() + t0, history[s], (size_t)n_history[s] * 4);
+          text[t0 + n_history[s]] = tokens[s];
+          t0 += (size_t)e.n_text;
+          e.max_draft = c->sp_max_draft; e.ngram_min = c->sp_ngram_min; e.ngram_max = c->sp_ngram_max; e.corpus = c->sp_corpus; e.n_corpus = c->sp_n_corpus;
+          if (e.max_draft == 0) { e.ngram_min = e.ngram_max = 1; e.corpus = nullptr; e.n_corpus = 0; }
+      } }
+    // ---- from here on the members' states and caches are written
+    for (int s = 0; s < n; s++) if (start_pos[s] >= 0) { if (member_drain(ctxs[s])) return -1; ctxs[s]->tp_last_k = 0; ctxs[s]->tp_last_n = 0; }
+    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { hipStreamSynchronize(s); } } sync_on_exit{st};     // (the uploads below read host vectors: no way out before the stream has drained)
+    HIPCHK(hipMemcpyAsync(am->members, members.data(), members.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync((void*)sm->p.members, smm.data(), smm.size() * sizeof(SmMember), hipMemcpyHostToDevice, st));
+    if (text_total) HIPCHK(hipMemcpyAsync(sm->text, text.data(), text_total * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(sm->p.stats, 0, LNB_BATCH_MAX * sizeof(SmStats), st));
+    HIPCHK(hipMemsetAsync(b->derr, 0, 4, st));
+    for (int s = 0; s < n; s++) if (start_pos[s] >= 0) {
+        HIPCHK(hipMemcpyAsync(ctxs[s]->dtok, tokens + s, 4, hipMemcpyHostToDevice, st));
+        HIPCHK(lnbk_set_state(ctxs[s]->st, start_pos[s], 0, 1, st));
+    }
+    b->rows_form = !m->batch_enabled; b->force_zseq = 0; b->attn_rows = false;
+    SmPass sp = sm->p; sp.n = n; sp.max_steps = max_steps; sp.budget = budget; sp.n_levels = n_levels; sp.logits = b->logits; sp.V = V;
+    lnb_spec_many_info inf{};
+    HIPCHK(hipEventRecord(sm->ev0, st));
+    HIPCHK(lnbk_spec_many_draft(&sp, st));
+    HIPCHK(lnbk_spec_many_pack(&sp, st));
+    HIPCHK(hipEventRecord(sm->ev, st));
+    for (;;) {
+        // the one host round trip of a pass: the pack kernel's block {width, any_draft, running members, largest seq_len of a running member}
+        HIPCHK(hipEventSynchronize(sm->ev));
+        const volatile int32_t* wd = sm->word;
+        const int width = wd[0], any = wd[1], running = wd[2], maxT = wd[3];
+        if (width < 0 || running < 0 || running > n || width < running || width > budget || (running > 0 && inf.passes >= max_steps)) return fail("%s: internal error: a pass of %d columns for %d running members", name, width, running);
+        if (running == 0) break;
+        const bool lng = maxT > cap;
+        b->n = width; b->maxT = maxT; b->lds_T = std::min(maxT, cap); b->must_long = lng; b->attn_long = lng;
+        const int layout = batch_plan_layout(batch_plan_of(b));
+        if (am->last_layout >= 0 && (layout != am->last_layout || width < am->last_width) && batch_bufs_zero(b, LNB_BATCH_MAX)) return -1;       // dead columns are zero again
+        am->last_layout = layout; am->last_width = width;
+        AmPass ap{}; ap.rows = sp.rows; ap.members = (const AmMembers*)am->members; ap.member_kv = (const BatchKV*)(am->members + sizeof(AmMembers));
+        ap.tab = b->tab; ap.kv = b->kv; ap.st = am->st; ap.tok = am->tok; ap.width = width; ap.n_layers = (int)L;
+        HIPCHK(lnbk_append_many_setup(&ap, st));
+        if (enqueue_batch_pass(b)) return -1;
+        sp.width = width;
+        HIPCHK(lnbk_spec_many_commit(&sp, st));
+        HIPCHK(lnbk_spec_many_draft(&sp, st));
+        HIPCHK(lnbk_spec_many_pack(&sp, st));
+        HIPCHK(hipEventRecord(sm->ev, st));
+        inf.passes++; inf.verify_passes += any ? 1 : 0; inf.columns += width; inf.max_columns = std::max<int64_t>(inf.max_columns, width); inf.long_passes += lng ? 1 : 0;
+    }
+    HIPCHK(hipEventRecord(sm->ev1, st));
+    std::vector<StepState> hs(n); std::vector<SmStats> hst(n);
+    for (int s = 0; s < n; s++) if (start_pos[s] >= 0) {
+        HIPCHK(hipMemcpyAsync(out_tokens + (size_t)s * max_steps, ctxs[s]->dout, (size_t)max_steps * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&hs[s], ctxs[s]->st, sizeof(StepState), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipMemcpyAsync(hst.data(), sm->p.stats, (size_t)n * sizeof(SmStats), hipMemcpyDeviceToHost, st));
+    int32_t err = 0;
+    HIPCHK(hipMemcpyAsync(&err, b->derr, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ms_out) HIPCHK(hipEventElapsedTime(ms_out, sm->ev0, sm->ev1));
+    if (err) return fail("%s: a generated token id is outside the vocabulary", name);
+    for (int s = 0; s < n; s++) {
+        const bool skipped = start_pos[s] < 0;
+        n_generated[s] = skipped ? 0 : hs[s].n_out;
+        if (finished) finished[s] = skipped ? 1 : hs[s].finished;
+        if (stats) stats[s] = skipped ? lnb_spec_stats{} : lnb_spec_stats{hst[s].passes, hst[s].verify_passes, hst[s].drafted, (int64_t)hs[s].n_out - hst[s].passes};
+    }
+    if (info) *info = inf;
     return 0;
 }
 

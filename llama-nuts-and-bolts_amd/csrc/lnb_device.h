@@ -295,3 +295,27 @@ struct DraftParams {
     int* best;                                 // [2 * LNB_SPEC_MAX_NGRAM]: per workgroup, the latest match start in R and in C (-1: none)
     unsigned* cnt;                             // arrival ticket, zero between launches (the last workgroup resets it)
 };
+
+// ---- speculative decoding of many contexts (lnb_decode_speculative_many; lnb_spec_many.h, lnb_specpack.h) ------------------------------------
+// A pass is a pass of lnb_forward_append_many whose row table is written ON THE DEVICE: per member, column 0 = its current token at its position
+// and columns 1.. = the draft tokens the grant rule gave it.  One SmMember per member, uploaded once per call; everything else is per pass.
+struct SmMember {
+    StepState* st; int32_t* tok; int32_t* log;             // the member's OWN state, token word and token log (what its greedy loop advances)
+    const int32_t* text; const int32_t* corpus;            // its running text's head (history ++ token) and its corpus (lnb_ctx_set_draft)
+    int32_t log_cap, n_text, n_corpus, ngram_min, ngram_max, max_draft, seq_len;
+    int32_t active;                                        // 0: skipped by the caller (start_pos < 0): nothing of it is read or written
+};
+struct SmSeg { int32_t first, cols; };                     // a member's columns of the pass: [first, first + cols); cols 0 = it has none
+struct SmStats { int32_t passes, verify_passes, drafted, pad; };
+struct SmPass {                                            // the launches around one pass: spec_many_draft / _pack / _commit kernels
+    const SmMember* members; int32_t n, max_steps, budget, n_levels;   // n_levels: the draft kernel's grid.x = the most n-gram lengths a member tries
+    int32_t* want;                                         // [LNB_BATCH_MAX] draft length per member
+    int32_t* running;                                      // [LNB_BATCH_MAX] 1 = in A: active, not finished, n_out < max_steps
+    int32_t* draft;                                        // [LNB_BATCH_MAX][LNB_SPEC_MAX_DRAFT]
+    int* best; unsigned* cnt;                              // [LNB_BATCH_MAX][2 * LNB_SPEC_MAX_NGRAM] / [LNB_BATCH_MAX + 1] arrival tickets, zero between launches ([LNB_BATCH_MAX]: the commit's)
+    AmRow* rows; SmSeg* seg;                               // [LNB_BATCH_MAX] the pass's row table and the members' columns
+    SmStats* stats;                                        // [LNB_BATCH_MAX]
+    int32_t* word;                                         // the host's pinned block {width, any_draft, running members, largest seq_len of a running member}
+    int32_t* g;                                            // [LNB_BATCH_MAX] argmax per column
+    const uint16_t* logits; int32_t V, width;              // commit: the pass's logits and width as the host launched it
+};

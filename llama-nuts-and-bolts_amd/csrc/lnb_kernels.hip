@@ -4048,14 +4048,12 @@ DEVINL int32_t spec_text_at(const DraftParams& p, int j) { return j < p.n_text ?
 // corpus (j <= n_corpus - n - 1).  The last workgroup to arrive (agent-scope ticket) picks the longest n that matched, R before C, and takes
 // up to max_draft tokens after the match, cut at the end of its array and -- decoding -- at max_steps - n_out - 1 and seq_len - pos - 1.
 // It writes the draft into the column token words out[1 ..], the columns' positions pos + i, and {draft_len, n_out, finished}.
-__global__ __launch_bounds__(256) void ngram_draft_kernel(DraftParams p) {
-    __shared__ int32_t suf[LNB_SPEC_MAX_NGRAM];
-    __shared__ int sbest[2];
-    __shared__ int s_last;
-    const int tid = threadIdx.x, b = blockIdx.x;
-    const int n = p.ngram_max - b;
-    const int n_gen = p.st ? p.st->n_out : 0;
-    const int L = p.n_text + n_gen;
+// ngram_search_block: the search of ONE n by one workgroup (all its threads call it; suf [LNB_SPEC_MAX_NGRAM] and sbest [2] are its LDS) -> after
+// the call sbest = {latest match start in R, in C} (-1: none).  ngram_pick: what the last workgroup makes of the `count` results in p.best
+// (result q belongs to n = ngram_max - q) -> the draft length after every cut, *src = 0 R / 1 C, *start = the draft's first token in that array.
+// Shared by ngram_draft_kernel and spec_many_draft_kernel (lnb_spec_many.h): one rule, one body.
+DEVINL void ngram_search_block(const DraftParams& p, int n, int L, int32_t* suf, int* sbest) {
+    const int tid = threadIdx.x;
     if (tid < 2) sbest[tid] = -1;
     if (tid < n && n <= L) suf[tid] = spec_text_at(p, L - n + tid);
     __syncthreads();
@@ -4078,6 +4076,31 @@ __global__ __launch_bounds__(256) void ngram_draft_kernel(DraftParams p) {
         if (mine >= 0) atomicMax(&sbest[1], mine);
     }
     __syncthreads();
+}
+DEVINL int ngram_pick(const DraftParams& p, int count, int L, int n_gen, int* src_out, int* start_out) {
+    int src = -1, start = 0, avail = 0;
+    for (int q = 0; q < count && src < 0; q++) {
+        const int r = p.best[2 * q], c = p.best[2 * q + 1], nq = p.ngram_max - q;
+        if (r >= 0) { src = 0; start = r + nq; avail = L - start; }
+        else if (c >= 0) { src = 1; start = c + nq; avail = p.n_corpus - start; }
+    }
+    int k = src < 0 ? 0 : min(avail, p.max_draft);
+    if (p.st) {
+        k = min(k, min(p.max_steps - n_gen - 1, p.seq_len - p.st->pos - 1));
+        if (p.st->finished || k < 0) k = 0;
+    }
+    *src_out = src; *start_out = start;
+    return k;
+}
+__global__ __launch_bounds__(256) void ngram_draft_kernel(DraftParams p) {
+    __shared__ int32_t suf[LNB_SPEC_MAX_NGRAM];
+    __shared__ int sbest[2];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int n = p.ngram_max - b;
+    const int n_gen = p.st ? p.st->n_out : 0;
+    const int L = p.n_text + n_gen;
+    ngram_search_block(p, n, L, suf, sbest);
     if (tid == 0) {
         p.best[2 * b] = sbest[0];
         p.best[2 * b + 1] = sbest[1];
@@ -4089,19 +4112,9 @@ __global__ __launch_bounds__(256) void ngram_draft_kernel(DraftParams p) {
     if (!s_last || tid != 0) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     *p.cnt = 0;                                              // (ready for the next launch: stream order)
-    int src = -1, start = 0, avail = 0;
-    for (int q = 0; q < (int)gridDim.x && src < 0; q++) {
-        const int r = p.best[2 * q], c = p.best[2 * q + 1], nq = p.ngram_max - q;
-        if (r >= 0) { src = 0; start = r + nq; avail = L - start; }
-        else if (c >= 0) { src = 1; start = c + nq; avail = p.n_corpus - start; }
-    }
-    int k = src < 0 ? 0 : min(avail, p.max_draft);
-    int finished = 0, pos = 0;
-    if (p.st) {
-        finished = p.st->finished; pos = p.st->pos;
-        k = min(k, min(p.max_steps - n_gen - 1, p.seq_len - pos - 1));
-        if (finished || k < 0) k = 0;
-    }
+    int src = -1, start = 0;
+    const int k = ngram_pick(p, (int)gridDim.x, L, n_gen, &src, &start);
+    const int finished = p.st ? p.st->finished : 0, pos = p.st ? p.st->pos : 0;
     for (int i = 0; i < k; i++) p.out[1 + i] = src == 0 ? spec_text_at(p, start + i) : p.corpus[start + i];
     if (p.col_st) for (int i = 1; i <= k; i++) p.col_st[i].pos = pos + i;
     p.word[0] = k; p.word[1] = n_gen; p.word[2] = finished;
@@ -4975,5 +4988,27 @@ extern "C" hipError_t lnbk_append_many_setup(const AmPass* p, hipStream_t st) {
 extern "C" hipError_t lnbk_append_many_finish(const uint16_t* logits, int V, const AmRow* rows, int width, int32_t* out, hipStream_t st) {
     if (!logits || !rows || !out || V < 1 || width < 1 || width > LNB_BATCH_MAX) return hipErrorInvalidValue;
     hipLaunchKernelGGL(append_many_finish_kernel, dim3((unsigned)width), dim3(1024), 0, st, logits, V, rows, out);
+    return hipGetLastError();
+}
+
+// lnb_decode_speculative_many: per pass, every member's draft, the pass's row table from the grant rule, and the per-member commit (lnb_spec_many.h)
+#include "lnb_spec_many.h"
+static bool spec_many_tables_ok(const SmPass* p) {
+    return p && p->members && p->want && p->running && p->draft && p->best && p->cnt && p->rows && p->seg && p->stats && p->word && p->g &&
+           p->n >= 1 && p->n <= LNB_BATCH_MAX && p->budget >= p->n && p->budget <= LNB_BATCH_MAX && p->max_steps >= 1;
+}
+extern "C" hipError_t lnbk_spec_many_draft(const SmPass* p, hipStream_t st) {
+    if (!spec_many_tables_ok(p) || p->n_levels < 1 || p->n_levels > LNB_SPEC_MAX_NGRAM) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_many_draft_kernel, dim3((unsigned)p->n_levels, (unsigned)p->n), dim3(256), 0, st, *p);
+    return hipGetLastError();
+}
+extern "C" hipError_t lnbk_spec_many_pack(const SmPass* p, hipStream_t st) {
+    if (!spec_many_tables_ok(p)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_many_pack_kernel, dim3(1), dim3(LNB_BATCH_MAX), 0, st, *p);
+    return hipGetLastError();
+}
+extern "C" hipError_t lnbk_spec_many_commit(const SmPass* p, hipStream_t st) {
+    if (!spec_many_tables_ok(p) || !p->logits || p->V < 1 || p->width < 1 || p->width > LNB_BATCH_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(spec_many_commit_kernel, dim3((unsigned)p->width), dim3(1024), 0, st, *p);
     return hipGetLastError();
 }

@@ -15,6 +15,7 @@ package model
 
 /*
 #include <stdint.h>
+#include <stdlib.h>
 #include "lnb.h"
 extern void lnbGoLayerCallback(int layer, int nLayers, double secs, void* user);
 */
@@ -338,6 +339,75 @@ func ForwardAppendMany(lt *LlamaTransformer, ctxs []*InferenceContext, tokens []
 		return nil, err
 	}
 	return argmax, nil
+}
+
+// SpecManyInfo is lnb_spec_many_info: the passes of one DecodeSpeculativeMany call, those with any draft, the sum and the maximum of their widths,
+// the passes that ran the long-context attention pair.
+type SpecManyInfo struct{ Passes, VerifyPasses, Columns, MaxColumns, LongPasses int64 }
+
+// DecodeSpeculativeMany decodes up to 128 contexts of one transformer together (lnb_decode_speculative_many): every context drafts for itself with its
+// own SetDraft settings and ONE batched pass over the weights verifies all of them.  Context s continues from tokens[s] at startPos[s] (histories[s]:
+// the tokens before it; startPos[s] < 0: skipped, as a finished member of a chunked run).  colBudget: columns per pass, 0 = 16 * ceil(n / 16).  Every
+// context's tokens, finished flag and KV cache rows are bit-identical to its own DecodeGreedyUntil.
+func DecodeSpeculativeMany(lt *LlamaTransformer, ctxs []*InferenceContext, histories [][]TokenId, tokens []TokenId, startPos []int, maxSteps int, colBudget int) (out [][]TokenId, finished []bool, stats []SpecStats, info SpecManyInfo, err error) {
+	n := len(ctxs)
+	if n == 0 || len(histories) != n || len(tokens) != n || len(startPos) != n {
+		return nil, nil, nil, info, fmt.Errorf("DecodeSpeculativeMany: %d contexts, %d histories, %d tokens, %d start positions", n, len(histories), len(tokens), len(startPos))
+	}
+	if maxSteps <= 0 {
+		return nil, nil, nil, info, fmt.Errorf("max_steps must be positive")
+	}
+	hs := make([]*C.lnb_ctx, n)
+	hn := make([]C.int32_t, n)
+	pos := make([]C.int32_t, n)
+	tok := make([]C.int32_t, n)
+	total := 0
+	for i, c := range ctxs {
+		if c == nil {
+			return nil, nil, nil, info, fmt.Errorf("DecodeSpeculativeMany: context %d is nil", i)
+		}
+		if err = c.attach(lt); err != nil {
+			return nil, nil, nil, info, err
+		}
+		hs[i], hn[i], pos[i], tok[i] = c.handle, C.int32_t(len(histories[i])), C.int32_t(startPos[i]), C.int32_t(tokens[i])
+		total += len(histories[i])
+	}
+	// the histories and the array of pointers to them live in C memory: a Go slice of Go pointers must not be passed to C
+	flat := (*C.int32_t)(C.malloc(C.size_t(4 * (total + 1))))
+	hp := (**C.int32_t)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(uintptr(0)))))
+	defer C.free(unsafe.Pointer(flat))
+	defer C.free(unsafe.Pointer(hp))
+	flatS := unsafe.Slice(flat, total+1)
+	hpS := unsafe.Slice(hp, n)
+	at := 0
+	for i, h := range histories {
+		hpS[i] = nil
+		if len(h) > 0 {
+			hpS[i] = &flatS[at]
+		}
+		for _, t := range h {
+			flatS[at] = C.int32_t(t)
+			at++
+		}
+	}
+	buf := make([]TokenId, n*maxSteps)
+	ng := make([]C.int32_t, n)
+	fin := make([]C.int32_t, n)
+	st := make([]C.lnb_spec_stats, n)
+	var ci C.lnb_spec_many_info
+	if err = lnbCall(func() C.int {
+		return C.lnb_decode_speculative_many((**C.lnb_ctx)(unsafe.Pointer(&hs[0])), C.int(n), hp, &hn[0], &tok[0], &pos[0], C.int(maxSteps), C.int(colBudget),
+			(*C.int32_t)(unsafe.Pointer(&buf[0])), &ng[0], &fin[0], &st[0], &ci, nil)
+	}); err != nil {
+		return nil, nil, nil, info, err
+	}
+	for i := 0; i < n; i++ {
+		out = append(out, buf[i*maxSteps:i*maxSteps+int(ng[i])])
+		finished = append(finished, fin[i] != 0)
+		stats = append(stats, SpecStats{int64(st[i].passes), int64(st[i].verify_passes), int64(st[i].drafted), int64(st[i].accepted)})
+	}
+	info = SpecManyInfo{int64(ci.passes), int64(ci.verify_passes), int64(ci.columns), int64(ci.max_columns), int64(ci.long_passes)}
+	return out, finished, stats, info, nil
 }
 
 // SavePrefix returns the KV rows [0, nPos) as a capacity-independent blob (lnb_ctx_save_prefix; layout in lnb.h): a prefix cache in host memory

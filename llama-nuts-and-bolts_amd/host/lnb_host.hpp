@@ -317,6 +317,27 @@ inline AppendManyInfo GetAppendManyInfo(const LlamaTransformer& t) {       // of
     return i;
 }
 
+// lnb_decode_speculative_many: the contexts (up to 128, one transformer) decoded together, each drafting with its own SetDraft settings, one batched
+// pass over the weights verifying all of them.  Context s continues from tokens[s] at startPos[s] (histories[s]: the tokens before it; startPos[s] < 0:
+// skipped).  colBudget: columns per pass, 0 = 16 * ceil(n / 16).  Every context's tokens, finished flag and KV rows are its own DecodeGreedyUntil's.
+struct SpeculativeMany {
+    std::vector<std::vector<TokenId>> Tokens; std::vector<bool> Finished; std::vector<lnb_spec_stats> Stats; lnb_spec_many_info Info{}; float Ms = 0.f;
+};
+inline SpeculativeMany DecodeSpeculativeMany(const std::vector<InferenceContext*>& ctxs, const std::vector<std::vector<TokenId>>& histories,
+                                             const std::vector<TokenId>& tokens, const std::vector<int>& startPos, int maxSteps, int colBudget = 0) {
+    const size_t n = ctxs.size(), steps = maxSteps > 0 ? (size_t)maxSteps : 1;
+    if (n == 0 || histories.size() != n || tokens.size() != n || startPos.size() != n) throw std::runtime_error("DecodeSpeculativeMany: the arrays differ in length");
+    std::vector<lnb_ctx*> hs;
+    std::vector<const int32_t*> hp; std::vector<int32_t> hn, pos(startPos.begin(), startPos.end()), out(n * steps), ng(n), fin(n);
+    for (auto* c : ctxs) hs.push_back(c ? c->handle() : nullptr);
+    for (const auto& h : histories) { hp.push_back(h.empty() ? nullptr : h.data()); hn.push_back((int32_t)h.size()); }
+    SpeculativeMany r; r.Stats.resize(n);
+    check(lnb_decode_speculative_many(hs.data(), (int)n, hp.data(), hn.data(), tokens.data(), pos.data(), maxSteps, colBudget, out.data(), ng.data(), fin.data(),
+                                      r.Stats.data(), &r.Info, &r.Ms));
+    for (size_t s = 0; s < n; s++) { r.Tokens.emplace_back(out.begin() + s * steps, out.begin() + s * steps + ng[s]); r.Finished.push_back(fin[s] != 0); }
+    return r;
+}
+
 enum GenerationState{ GSInProgress = 1, GSFinishedByReachingEOS = 2, GSFinishedByReachingSeqLen = 3 };   // inference.go:13-17
 
 class InferenceEngine {                  // inference.go:40-56

@@ -71,6 +71,7 @@ EXPORTS = [
     "lnb_ctx_set_rows_attention", "lnb_ctx_append_attention_form",
     "lnb_ctx_fork", "lnb_ctx_prefix_bytes", "lnb_ctx_save_prefix", "lnb_ctx_load_prefix",
     "lnb_forward_append_many", "lnb_model_append_many_info",
+    "lnb_decode_speculative_many",
 ]
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
 MAX_DRAFT = 15           # LNB_MAX_DRAFT of include/lnb.h (tests/test_speculative_cpu.py compares them)
@@ -82,6 +83,14 @@ ABI_VERSION = 6          # LNB_ABI_VERSION of include/lnb.h this binding was wri
 class SpecStats(C.Structure):
     """lnb_spec_stats (include/lnb.h)"""
     _fields_ = [("passes", C.c_int64), ("verify_passes", C.c_int64), ("drafted", C.c_int64), ("accepted", C.c_int64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class SpecManyInfo(C.Structure):
+    """lnb_spec_many_info (include/lnb.h)"""
+    _fields_ = [("passes", C.c_int64), ("verify_passes", C.c_int64), ("columns", C.c_int64), ("max_columns", C.c_int64), ("long_passes", C.c_int64)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -192,6 +201,8 @@ def lib():
     L.lnb_ctx_load_prefix.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int)]
     L.lnb_forward_append_many.argtypes = [C.POINTER(vp), C.c_int, vp, vp, vp, vp, vp]
     L.lnb_model_append_many_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.lnb_decode_speculative_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, vp, vp, vp,
+                                              C.POINTER(SpecStats), C.POINTER(SpecManyInfo), f32p]
     L.lnb_pipeline_tick_batch.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.lnb_pipeline_read_tokens.argtypes = [vp, C.c_int, C.c_int, vp]
     L.lnb_op_linear_mode.argtypes = [C.c_int, vp, vp, C.c_float, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -758,6 +769,31 @@ def ForwardAppendMany(ctxs, token_lists, start_pos, want_logits=True):
         return None, am
     ends = np.cumsum(rows)
     return [logits[e - r:e] for e, r in zip(ends, rows)], am
+
+
+def DecodeSpeculativeMany(ctxs, histories, tokens, start_pos, max_steps, col_budget=0):
+    """decode_greedy_until of the contexts `ctxs` (1..128, one transformer) together, every context drafting for itself with its own set_draft
+    settings and ONE batched pass over the weights verifying all of them (lnb_decode_speculative_many).  Context s continues from tokens[s] at
+    start_pos[s] (histories[s]: the tokens before it; start_pos[s] < 0: skipped); col_budget: columns per pass, 0 = 16 * ceil(n / 16).  Every
+    context's tokens, finished flag and KV rows are the bits of its own decode_greedy_until
+    -> (list of int32 token arrays, list of finished flags, list of stats dicts, info dict, device ms)"""
+    ctxs = list(ctxs)
+    n = len(ctxs)
+    hist = [np.ascontiguousarray(h, dtype=np.int32).reshape(-1) for h in histories]
+    if not ctxs or len(hist) != n or len(tokens) != n or len(start_pos) != n:
+        raise LnbError("DecodeSpeculativeMany: %d contexts, %d histories, %d tokens, %d start positions" % (n, len(hist), len(tokens), len(start_pos)))
+    L = ctxs[0].L
+    arr = (C.c_void_p * n)(*[c.h for c in ctxs])
+    harr = (C.c_void_p * n)(*[h.ctypes.data if h.size else None for h in hist])
+    nh = np.array([h.size for h in hist], dtype=np.int32)
+    tok = np.ascontiguousarray(tokens, dtype=np.int32)
+    pos = np.ascontiguousarray(start_pos, dtype=np.int32)
+    out = np.zeros((n, max(int(max_steps), 1)), dtype=np.int32)
+    ng = np.zeros(n, dtype=np.int32); fin = np.zeros(n, dtype=np.int32)
+    st = (SpecStats * n)(); info = SpecManyInfo(); ms = C.c_float(0)
+    _chk(L.lnb_decode_speculative_many(arr, n, harr, _p(nh), _p(tok), _p(pos), int(max_steps), int(col_budget), _p(out), _p(ng), _p(fin),
+                                       st, C.byref(info), C.byref(ms)))
+    return ([out[s, :ng[s]].copy() for s in range(n)], [bool(f) for f in fin], [st[s].as_dict() for s in range(n)], info.as_dict(), ms.value)
 
 
 class Batch:
