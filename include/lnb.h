@@ -452,6 +452,17 @@ int lnb_op_token_probs(int device, const uint16_t* logits_bf16, int rows, int V,
 typedef struct lnb_batch lnb_batch;
 int lnb_model_enable_batch(lnb_model* m);
 int64_t lnb_model_batch_bytes(lnb_model* m);
+/* One-token decode streams the gate|up matrices from a lossless 13-bit planar copy (csrc/lnb_wpack.h: low byte raw, a 4-bit exponent code in a per-matrix
+ * window of 30 binades, the sign), built on the device by lnb_model_finalize unless LNB_W13_PACKED=0.  Every weight decodes to its own 16 bits, so every
+ * product and every chain is what the raw kernel computes.  The raw layouts stay resident: prefill, batches, appends, the throughput schedule and the
+ * tolerance mode read them.  A matrix that cannot be packed -- it holds a subnormal or an exponent of 1, an Inf / NaN, or non-zero weights more than 30
+ * binades apart -- or whose copy cannot be allocated keeps the raw kernel, and says so here:
+ *   lnb_model_wpack_bytes   device bytes of the copies (13/16 of the matrices they cover)
+ *   lnb_model_wpack_info    counts6[0] = matrices decoding from their copy; [1] refused for a subnormal / exponent 1, [2] Inf / NaN, [3] out of window,
+ *                           [4] no memory; [5] never tried (knob off at finalize, or not the 56-row layout the packed kernel reads)
+ * Bind every tensor before lnb_model_finalize: a gate|up tensor bound afterwards is re-packed in place if it fits the copy's window, else the call fails. */
+int64_t lnb_model_wpack_bytes(lnb_model* m);
+int lnb_model_wpack_info(lnb_model* m, int32_t* counts6);
 int lnb_batch_create(lnb_ctx* const* ctxs, int n, lnb_batch** out);
 int lnb_batch_destroy(lnb_batch* b);
 int lnb_batch_decode(lnb_batch* b, const int32_t* tokens, const int32_t* start_pos, int n_steps, int32_t* out_tokens, float* ms_out);
@@ -581,6 +592,11 @@ int lnb_op_linear(int device, const uint16_t* x, const uint16_t* w, uint16_t* y,
 /* RMSNorm.Forward (llamatransformer.go:633-639) followed by a linear layer, as the fused kernel computes it */
 int lnb_op_rmsnorm_linear(int device, const uint16_t* x, const uint16_t* norm_w, float eps, const uint16_t* w,
                           uint16_t* y, int rows, int n_out, int k_in, int rw);
+/* the fused ffn_norm + w1|w3 + SiLU(gate)*up launch of a one-token step on one row x[k_in] -> y[n_out] (llamatransformer.go:601-617), 56-row layout.
+ * packed 0: the raw kernel; 1: from the 13-bit copy when the w1|w3 matrix is packable.  *status (may be NULL): 0 packable, 1 subnormal / exponent 1,
+ * 2 Inf / NaN, 3 out of window -- a refused matrix runs the raw kernel */
+int lnb_op_rmsnorm_gate_up(int device, const uint16_t* x, const uint16_t* norm_w, float eps, const uint16_t* w1, const uint16_t* w3, uint16_t* y,
+                           int n_out, int k_in, int packed, int* status);
 
 /* either operator in a given arithmetic mode (norm_w == NULL: plain linear); LNB_MODE_FAST runs the split-K kernels */
 int lnb_op_linear_mode(int device, const uint16_t* x, const uint16_t* norm_w, float eps, const uint16_t* w, uint16_t* y,

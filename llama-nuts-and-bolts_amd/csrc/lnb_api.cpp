@@ -23,6 +23,7 @@
 #include "lnb_knobs.h"
 #include "lnb_kvcopy.h"
 #include "lnb_rowpack.h"
+#include "lnb_wpack.h"
 #include "lnb_batchplan.h"
 #include "lnb_rccl.h"
 static_assert(LNB_MAX_SEQ_LEN == LNB_SEQ_MAX, "lnb.h and lnb_device.h disagree on the longest context");
@@ -51,6 +52,11 @@ hipError_t lnbk_advance_state(StepState* state, int rows, hipStream_t st);
 hipError_t lnbk_tile(const uint16_t* src, uint16_t* dst, int rows, int K, int row_off, int chain, int RW, int NCH, int gather, hipStream_t st);
 hipError_t lnbk_synth_fill(uint16_t* dst, int rows, int K, int row_off, int chain, int RW, int NCH, uint64_t seed, uint32_t tensor_id, int kind, float sigma, hipStream_t st);
 hipError_t lnbk_init(void);
+int lnbk_w13p_supported(int rw, int K);
+hipError_t lnbk_gemv_w13p(const GemvParams* p, hipStream_t st);
+size_t lnbk_wpack_w13_bytes(int n_blocks, int K);
+hipError_t lnbk_wpack_stats(const uint16_t* w, size_t elems, unsigned* d_stats, hipStream_t st);
+hipError_t lnbk_wpack_w13(const uint16_t* w, void* out, int K, int n_blocks, unsigned base, hipStream_t st);
 hipError_t lnbk_fast_gemv(const GemvParams* p, int rw, int nch, int epi, int norm, hipStream_t st);
 hipError_t lnbk_fast_gemm(const GemmParams* p, int epi, hipStream_t st);
 hipError_t lnbk_fast_attn(const AttnParams* p, hipStream_t st);
@@ -134,6 +140,9 @@ struct LayerW {
     TiledDesc wqkv{}, wo{}, w13{}, w2{};
     // batched decode (lnb_model_enable_batch): the same matrices in the 16-row matrix-core layout (M16, lnb_device.h)
     uint16_t *m_wqkv = nullptr, *m_wo = nullptr, *m_w13 = nullptr, *m_w2 = nullptr;
+    // one-token decode (lnb_model_finalize, LNB_W13_PACKED): the 13-bit planar copy of w13 (lnb_wpack.h) the latency form streams instead of the raw bf16
+    void* p_w13 = nullptr; unsigned p_base = 0; bool p_ok = false;     // p_ok: the copy holds what w13 holds
+    int p_status = -1;                                                  // WPACK_* of the last attempt (-1: none -- knob off or a layout the packed kernel has no form for)
 };
 struct lnb_model {
     lnb_model_args a{};
@@ -150,6 +159,7 @@ struct lnb_model {
     bool finalized = false;
     int64_t weight_bytes = 0;
     bool batch_enabled = false; uint16_t* m_output = nullptr; int64_t batch_bytes = 0;
+    int64_t wpack_bytes = 0;              // the 13-bit planar copies of the gate|up matrices (lnb_model_wpack_bytes)
     std::mutex am_mu; struct AppendMany* am = nullptr;     // lnb_forward_append_many: the call's buffers and tables, created on first use; the mutex is held for a whole call
     bool first() const { return part_begin == 0; }
     bool last() const { return part_end == 3 * a.n_layers; }
@@ -419,6 +429,7 @@ extern "C" int lnb_model_create_parts(const lnb_model_args* args, int device, in
     *out = m;
     return 0;
 }
+static int wpack_refresh(lnb_model* m, const TiledDesc* t);
 static int model_alloc(lnb_model* m) {
     const lnb_model_args& a = m->a;
     const int layer_begin = m->layer_begin, layer_end = m->layer_end;
@@ -478,7 +489,7 @@ extern "C" int lnb_model_destroy(lnb_model* m) {
     if (m->output.w) hipFree(m->output.w);
     for (auto& L : m->layers) {
         hipFree(L.attn_norm); hipFree(L.ffn_norm); hipFree(L.wqkv.w); hipFree(L.wo.w); hipFree(L.w13.w); hipFree(L.w2.w);
-        hipFree(L.m_wqkv); hipFree(L.m_wo); hipFree(L.m_w13); hipFree(L.m_w2);
+        hipFree(L.m_wqkv); hipFree(L.m_wo); hipFree(L.m_w13); hipFree(L.m_w2); hipFree(L.p_w13);
     }
     hipFree(m->m_output);
     if (m->cis) hipFree(m->cis);
@@ -491,6 +502,84 @@ extern "C" int lnb_model_destroy(lnb_model* m) {
 }
 
 extern "C" int64_t lnb_model_weight_bytes(lnb_model* m) { return m ? m->weight_bytes : 0; }
+
+// ---- the 13-bit planar copy of the gate|up matrices (lnb_wpack.h) ----------------------------------
+// Window of a resident matrix, on the device (no pass over the weights on the host): WPACK_* and *base
+static int wpack_matrix_window(lnb_model* m, const TiledDesc& t, unsigned* d_stats, unsigned* base) {
+    HIPCHK(lnbk_wpack_stats(t.w, tiled_elems(t.n_rows, t.k, t.rw, t.nch), d_stats, m->stream));
+    WpackStats s;
+    HIPCHK(hipMemcpyAsync(&s, d_stats, sizeof s, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return wpack_window(&s, base);
+}
+// lnb_model_finalize: every gate|up matrix in the 56-row layout that has no valid copy yet gets one, if it is packable and the memory is there;
+// a matrix that is refused keeps the raw kernel and says why (lnb_model_wpack_info)
+static int wpack_build(lnb_model* m) {
+    unsigned* d_stats = nullptr;
+    for (int l = m->layer_begin; l < m->layer_end; l++) {
+        LayerW& L = m->layers[l - m->layer_begin];
+        if (!m->has_w13(l) || L.p_ok || L.w13.nch != 2 || !lnbk_w13p_supported(L.w13.rw, L.w13.k)) continue;
+        if (!d_stats) HIPCHK(hipMalloc((void**)&d_stats, sizeof(WpackStats)));
+        unsigned base = 0;
+        const int why = wpack_matrix_window(m, L.w13, d_stats, &base);
+        if (why < 0) { hipFree(d_stats); return -1; }
+        L.p_status = why;
+        if (why != WPACK_OK) continue;
+        const size_t n = lnbk_wpack_w13_bytes(L.w13.n_blocks, L.w13.k);
+        if (!L.p_w13) {
+            if (hipMalloc(&L.p_w13, n) != hipSuccess) { (void)hipGetLastError(); L.p_w13 = nullptr; L.p_status = WPACK_NOMEM; continue; }     // the model runs raw and reports it
+            m->wpack_bytes += (int64_t)n;
+        }
+        hipError_t e = lnbk_wpack_w13(L.w13.w, L.p_w13, L.w13.k, L.w13.n_blocks, base, m->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+        if (e != hipSuccess) { hipFree(d_stats); return fail("packing the gate|up matrix of layer %d failed: %s", l, hipGetErrorString(e)); }
+        L.p_base = base; L.p_ok = true;
+    }
+    hipFree(d_stats);
+    return 0;
+}
+// A gate|up matrix was rewritten after its copy was built (t: that matrix; nullptr: all of them).  A captured decode step may hold the copy's address and
+// window, so the copy is rebuilt IN PLACE when the new weights still fit its window; otherwise the layer returns to the raw kernel and the call fails, saying so.
+static int wpack_refresh(lnb_model* m, const TiledDesc* t) {
+    unsigned* d_stats = nullptr; int rc = 0;
+    for (int l = m->layer_begin; l < m->layer_end && !rc; l++) {
+        LayerW& L = m->layers[l - m->layer_begin];
+        if (!L.p_ok || (t && t != &L.w13)) continue;
+        if (!d_stats && hipMalloc((void**)&d_stats, sizeof(WpackStats)) != hipSuccess) { (void)hipGetLastError(); L.p_ok = false; rc = fail("out of memory"); break; }
+        L.p_ok = false;
+        HIPCHK(lnbk_wpack_stats(L.w13.w, tiled_elems(L.w13.n_rows, L.w13.k, L.w13.rw, L.w13.nch), d_stats, m->stream));
+        WpackStats s;
+        HIPCHK(hipMemcpyAsync(&s, d_stats, sizeof s, hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream));
+        unsigned base = 0;
+        const int why = wpack_window(&s, &base);
+        const bool fits = why == WPACK_OK && (s.max_e2 == 0 || (s.min_e2 > L.p_base && s.max_e2 <= L.p_base + 15));
+        if (!fits) {
+            L.p_status = why != WPACK_OK ? why : WPACK_WINDOW;
+            rc = fail("layer %d: the gate|up weights bound after lnb_model_finalize do not fit the window of the matrix's 13-bit copy; the layer decodes from the raw "
+                      "weights from now on (a decode step captured before keeps the old copy: bind every tensor before lnb_model_finalize)", l);
+            break;
+        }
+        HIPCHK(lnbk_wpack_w13(L.w13.w, L.p_w13, L.w13.k, L.w13.n_blocks, L.p_base, m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream));
+        L.p_ok = true; L.p_status = WPACK_OK;
+    }
+    hipFree(d_stats);
+    return rc;
+}
+extern "C" int64_t lnb_model_wpack_bytes(lnb_model* m) { return m ? m->wpack_bytes : 0; }
+// counts[0] = gate|up matrices decoding from their 13-bit copy, counts[WPACK_SUBNORMAL / WPACK_INFNAN / WPACK_WINDOW / WPACK_NOMEM] = matrices refused for that
+// reason, counts[5] = matrices never tried (LNB_W13_PACKED=0 at lnb_model_finalize, or a layout the packed kernel has no form for)
+extern "C" int lnb_model_wpack_info(lnb_model* m, int32_t* counts6) {
+    if (!m || !counts6) return fail("null argument");
+    for (int i = 0; i < 6; i++) counts6[i] = 0;
+    for (int l = m->layer_begin; l < m->layer_end; l++) {
+        const LayerW& L = m->layers[l - m->layer_begin];
+        if (!m->has_w13(l)) continue;
+        counts6[L.p_ok ? 0 : (L.p_status > 0 && L.p_status <= WPACK_NOMEM) ? L.p_status : 5]++;
+    }
+    return 0;
+}
 
 extern "C" int lnb_model_set_tensor(lnb_model* m, const char* name, const uint16_t* host, const int64_t* shape, int rank) {
     if (!m || !name || !host || !shape) return fail("null argument");
@@ -511,6 +600,7 @@ extern "C" int lnb_model_set_tensor(lnb_model* m, const char* name, const uint16
     if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
     hipFree(stage);
     HIPCHK(e);
+    if (wpack_refresh(m, r.td)) return -1;
     return 0;
 }
 
@@ -555,6 +645,7 @@ extern "C" int lnb_model_fill_synthetic(lnb_model* m, uint64_t seed) {
         else HIPCHK(lnbk_synth_fill(r.linear, r.rows, r.cols, 0, 0, 0, 1, seed, r.synth_id, r.synth_kind, 0.02f, m->stream));
     }
     HIPCHK(hipStreamSynchronize(m->stream));
+    if (wpack_refresh(m, nullptr)) return -1;
     return 0;
 }
 
@@ -623,6 +714,7 @@ extern "C" int lnb_model_finalize(lnb_model* m, int rope_rows) {
     if (!m->exp_tab) HIPCHK(hipMalloc((void**)&m->exp_tab, (size_t)(1 << 16) * 8));
     HIPCHK(lnbk_exp_table(m->exp_tab, bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim))), m->stream));   // (attn_mfma_kernel)
     HIPCHK(hipStreamSynchronize(m->stream));
+    if (knob(Knob::W13_PACKED) && wpack_build(m)) return -1;
     m->finalized = true;
     return 0;
 }
@@ -1118,7 +1210,10 @@ static int enqueue_layer_kernel(lnb_ctx* c, int l, int S, int which, hipStream_t
     case K_W13: {   // ffn_norm + w1|w3 + SiLU*up  (:237, :601-617)
         GemvParams f{}; f.w = L.w13.w; f.x = hbuf; f.norm_w = L.ffn_norm; f.norm_fb = c->zseq_count + 1; f.eps = a.norm_eps; f.K = a.dim; f.n_rows = m->ffn_hidden; f.S = S; f.st = c->st;
         f.out = c->ffn; f.silu = m->silu; f.sched = c->sched;
-        set_grid(f, L.w13); HIPCHK(gemv_dispatch(c, &f, L.w13.rw, 2, EPI_SILU_MUL, 1, st)); return 0; }
+        set_grid(f, L.w13);
+        // one token, latency schedule, exact mode, and the layer has its 13-bit copy: the same chains fed from 13/16 of the bytes
+        if (S == 1 && L.p_ok && c->mode == LNB_MODE_EXACT && c->sched == LNB_SCHED_LATENCY) { f.wp = L.p_w13; f.wp_base4 = L.p_base * 0x01010101u; HIPCHK(lnbk_gemv_w13p(&f, st)); return 0; }
+        HIPCHK(gemv_dispatch(c, &f, L.w13.rw, 2, EPI_SILU_MUL, 1, st)); return 0; }
     case K_W2: {    // w2 + residual  (:619, :248)
         GemvParams d{}; d.w = L.w2.w; d.x = c->ffn; d.K = m->ffn_hidden; d.n_rows = a.dim; d.S = S; d.st = c->st; d.out = c->x; d.res = hbuf; d.lds_pad = lds_pad; d.sched = c->sched; d.prio = knob(Knob::W2_PRIO);
         set_grid(d, L.w2); HIPCHK(gemv_dispatch(c, &d, L.w2.rw, 1, EPI_RESID, 0, st)); return 0; }
@@ -3387,6 +3482,50 @@ static int op_linear_impl(int device, const uint16_t* x, const uint16_t* norm_w,
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(y, dy, (size_t)rows * n_out * 2, hipMemcpyDeviceToHost));
     hipFree(dx); hipFree(dw); hipFree(dy); hipFree(st); hipFree(t.w); if (dn) hipFree(dn); if (t.w16) hipFree(t.w16);
+    return 0;
+}
+// The fused ffn_norm + w1|w3 + SiLU*up launch of a one-token step on its own: y[n_out] from one row x.  packed = 0: the raw 56-row kernel; 1: from the
+// 13-bit copy when the w1|w3 matrix is packable.  *status = WPACK_* of the matrix (WPACK_OK: the packed kernel ran when asked for).
+extern "C" int lnb_op_rmsnorm_gate_up(int device, const uint16_t* x, const uint16_t* norm_w, float eps, const uint16_t* w1, const uint16_t* w3, uint16_t* y,
+                                      int n_out, int k_in, int packed, int* status) {
+    if (!x || !norm_w || !w1 || !w3 || !y) return fail("null argument");
+    if (n_out <= 0 || k_in <= 0) return fail("empty operand");
+    if (k_in % 8) return fail("in_features must be a multiple of 8");
+    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
+    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(lnbk_init());
+    if (!lnbk_w13p_supported(56, k_in)) return fail("in_features %d does not fit the LDS staging of the 56-row gate|up kernel", k_in);
+    TiledDesc t{}; int64_t bytes = 0;
+    if (alloc_tiled(t, n_out, k_in, 56, 2, bytes)) return -1;
+    const size_t wn = (size_t)n_out * k_in * 2;
+    uint16_t *dx = nullptr, *dw = nullptr, *dy = nullptr, *dn = nullptr; StepState* st = nullptr; float* dsilu = nullptr; unsigned* dstats = nullptr; void* wp = nullptr;
+    HIPCHK(hipMalloc((void**)&dx, (size_t)k_in * 2)); HIPCHK(hipMalloc((void**)&dw, wn)); HIPCHK(hipMalloc((void**)&dn, (size_t)k_in * 2));
+    HIPCHK(hipMalloc((void**)&dy, (size_t)n_out * 2)); HIPCHK(hipMalloc((void**)&st, sizeof(StepState))); HIPCHK(hipMalloc((void**)&dsilu, (size_t)65536 * 4));
+    HIPCHK(hipMalloc((void**)&dstats, sizeof(WpackStats)));
+    HIPCHK(hipMemset(st, 0, sizeof(StepState)));
+    std::vector<float> silu(1 << 16);
+    for (int i = 0; i < (1 << 16); i++) { double v = (double)bf_wide_h((uint16_t)i); silu[i] = (float)(v / (1.0 + std::exp(-v))); }
+    HIPCHK(hipMemcpy(dsilu, silu.data(), silu.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dx, x, (size_t)k_in * 2, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dn, norm_w, (size_t)k_in * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dw, w1, wn, hipMemcpyHostToDevice)); HIPCHK(lnbk_tile(dw, t.w, n_out, k_in, 0, 0, 56, 2, 0, nullptr)); HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(dw, w3, wn, hipMemcpyHostToDevice)); HIPCHK(lnbk_tile(dw, t.w, n_out, k_in, 0, 1, 56, 2, 0, nullptr)); HIPCHK(hipDeviceSynchronize());
+    HIPCHK(lnbk_wpack_stats(t.w, tiled_elems(n_out, k_in, 56, 2), dstats, nullptr));
+    WpackStats ws; HIPCHK(hipMemcpy(&ws, dstats, sizeof ws, hipMemcpyDeviceToHost));
+    unsigned base = 0;
+    const int why = wpack_window(&ws, &base);
+    if (status) *status = why;
+    GemvParams g{}; g.w = t.w; g.x = dx; g.norm_w = dn; g.eps = eps; g.K = k_in; g.n_rows = n_out; g.S = 1; g.st = st; g.out = dy; g.silu = dsilu;
+    set_grid(g, t);
+    if (packed && why == WPACK_OK) {
+        HIPCHK(hipMalloc(&wp, lnbk_wpack_w13_bytes(t.n_blocks, k_in)));
+        HIPCHK(lnbk_wpack_w13(t.w, wp, k_in, t.n_blocks, base, nullptr));
+        g.wp = wp; g.wp_base4 = base * 0x01010101u;
+        HIPCHK(lnbk_gemv_w13p(&g, nullptr));
+    } else HIPCHK(lnbk_gemv(&g, 56, 2, EPI_SILU_MUL, 1, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(y, dy, (size_t)n_out * 2, hipMemcpyDeviceToHost));
+    hipFree(dx); hipFree(dw); hipFree(dy); hipFree(dn); hipFree(st); hipFree(dsilu); hipFree(dstats); hipFree(t.w); if (wp) hipFree(wp);
     return 0;
 }
 // ml.Argmax (operations_impl.go:513-548) of one row of bf16 logits through argmax_kernel, the kernel of the greedy loop

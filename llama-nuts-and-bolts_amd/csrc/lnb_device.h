@@ -105,6 +105,8 @@ struct GemvParams {
     int sched;                  // host side only: 0 = latency forms (one stream owns the chip: every CU, eight or nine waves, up to 124 KB of LDS per
                                 // workgroup), 1 = throughput forms of the same arithmetic (lnb_ctx_set_schedule: at most 57 KB of LDS per workgroup, so
                                 // that a chain-bound launch of one context shares a CU with the HBM-bound gate|up launch of another)
+    const void* wp;             // gemv_chain_pk_kernel: the 13-bit planar copy of w (lnb_wpack.h), wp_base4 = its window base in every byte
+    unsigned wp_base4;
 };
 
 // exact-order prefill GEMM on the f32 matrix cores (gemm_mfma_kernel): Y[m][n] for S >= 16 rows per call

@@ -24,6 +24,7 @@
 #include <type_traits>
 #include "lnb_device.h"
 #include "lnb_seqsum.h"
+#include "lnb_wpack.h"
 
 #define DEVINL __device__ __forceinline__
 
@@ -596,6 +597,11 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 DEVINL void ld_nt_asm(u32x4& dst, unsigned voff, const char* sbase) { asm volatile("global_load_dwordx4 %0, %1, %2 nt ; RING_LOAD" : "=&v"(dst) : "v"(voff), "s"(sbase) : "memory"); }
 // the "; RING_RETIRE ..." comment names the registers this wait retires: tools/isa_audit.py checks on the compiled
 // code that hipcc touches no ring register between its asm load and the wait that retires it
+DEVINL void ld_nt_asm4(unsigned& dst, unsigned voff, const char* sbase) { asm volatile("global_load_dword %0, %1, %2 nt ; RING_LOAD" : "=&v"(dst) : "v"(voff), "s"(sbase) : "memory"); }
+// packed source (PK): a stage is three 16-byte loads and one dword per lane
+template <int N> DEVINL void wait_ring_pk(u32x4 (&b)[4], unsigned& s) {
+    asm volatile("s_waitcnt vmcnt(%4) ; RING_RETIRE %0 %1 %2 %3" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(s) : "n"(N) : "memory");
+}
 template <int N, int NP> DEVINL void wait_ring(u32x4 (&b)[NP]) {
     static_assert(NP == 1 || NP == 2 || NP == 4 || NP == 8, "loads per stage per helper");
     if constexpr (NP == 1) asm volatile("s_waitcnt vmcnt(%1) ; RING_RETIRE %0" : "+v"(b[0]) : "n"(N) : "memory");
@@ -604,8 +610,10 @@ template <int N, int NP> DEVINL void wait_ring(u32x4 (&b)[NP]) {
     if constexpr (NP == 8) asm volatile("s_waitcnt vmcnt(%8) ; RING_RETIRE %0 %1 %2 %3 %4 %5 %6 %7" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]) : "n"(N) : "memory");
 }
 
-template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value>
-__global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_kernel(GemvParams p) {
+// PK (two chains only): the helpers stream the 13-bit planar copy of the block (lnb_wpack.h) instead of the raw bf16 -- per lane and stage two 16-byte
+// loads of low bytes, one of exponent codes and one dword of signs for 32 weights -- and rebuild the same f32 weights; everything behind the unpack is the raw form's
+template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC, bool PK>
+DEVINL void gemv_chain_body(const GemvParams& p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     long long t_begin = p.dbg ? clock64() : 0, t_wait = 0, t_x = 0, t_aux = 0;
     const long long t_wall0 = p.dbg ? (long long)wall_clock64() : 0;
@@ -617,6 +625,7 @@ __global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_kernel(GemvParams p)
     static_assert(KC >= 2 && (KC & 1) == 0, "bad stage geometry");
     static_assert(UNITS % (64 * NH) == 0 && R * NP <= 60, "vmcnt is a 6-bit counter");
     static_assert(NH >= 2, "x staging is sized for >= 3 stager waves");
+    static_assert(!PK || (NCH == 2 && NP == 4 && 2 * NH * 64 == KC * RW), "packed source: one 32-weight group (two (chunk, row) pairs x two chains) per helper lane and stage");
     char* ringB = smem;
     float* xs = (float*)(smem + 2 * SB);
 
@@ -640,6 +649,7 @@ __global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_kernel(GemvParams p)
         // ================================ helper waves ============================================
         const int hw = wave < CW ? wave : wave - 1;
         u32x4 buf[R][NP];
+        unsigned sgn[PK ? R : 1];                                      // PK: buf[j][0..1] low plane, buf[j][2] codes, sgn[j] signs
         {
             uint4 xv[XC], nv[XC];
             x_issue<NORM, NS>(p, xrow, 1 + hw, lane, xv, nv);
@@ -660,7 +670,16 @@ __global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_kernel(GemvParams p)
             loff[i] = NCH == 2 ? (unsigned)((((pq / RW) * 2 + (i & 1)) * RW + (pq % RW)) * 16) : (unsigned)(((i * NH + hw) * 64 + lane) * 16);
         }
         int ib = wg, is = 0, issued = 0;
-        auto issue_next = [&](u32x4 (&dst)[NP]) {
+        const unsigned pk_l16 = (unsigned)((hw * 64 + lane) * 16), pk_l4 = (unsigned)(NH * 64 * 48 + (hw * 64 + lane) * 4);
+        auto issue_next = [&](u32x4 (&dst)[NP], unsigned& sg) {
+            if constexpr (PK) {
+                // whole stages only (the copy pads a block's last stage with zeros): no clamp
+                const char* sb = (const char*)p.wp + ((size_t)ib * nstages + is) * wpack_stage_bytes(NH * 64);     // wave-uniform
+                ld_nt_asm(dst[0], pk_l16, sb); ld_nt_asm(dst[1], pk_l16 + NH * 64 * 16, sb); ld_nt_asm(dst[2], pk_l16 + NH * 64 * 32, sb);
+                ld_nt_asm4(sg, pk_l4, sb);
+                if (issued + 1 < T) { issued++; if (++is == nstages) { is = 0; ib += p.n_wg; } }
+                return;
+            }
             const size_t soff = (size_t)is * SA;
             const char* sb = (const char*)p.w + (size_t)ib * stream_bytes + soff;     // wave-uniform
             // branch-free clamp (only the last, partial stage of a block ever clamps): one v_min_u32 per load
@@ -676,7 +695,7 @@ __global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_kernel(GemvParams p)
             constexpr int EARLY_ = NCH == 2 ? LNB_EARLY_W13 : LNB_EARLY_HEAD;
             constexpr int EARLY = late ? (EARLY_ < R ? EARLY_ : R) : R;      // stages issued in front of the fold
 #pragma unroll
-            for (int j = 0; j < EARLY; j++) issue_next(buf[j]);
+            for (int j = 0; j < EARLY; j++) issue_next(buf[j], sgn[PK ? j : 0]);
             x_store<NORM, NS>(p, xs, kpad, 1 + hw, lane, xv);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             TIMED_BARRIER();                                           // B1: xs (or the squares) are in LDS
@@ -685,7 +704,7 @@ __global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_kernel(GemvParams p)
                 rms_fold<rms_nf(NH)>(p, xs, ringB, hw - (NH - rms_nf(NH)), lane, t_aux);      // X1, X2 inside; the LAST four helpers fold (waves 4..7 of 8: four SIMDs)
                 {                                                      // the walker walks now: the issue stall costs nothing here
 #pragma unroll
-                    for (int j = EARLY; j < R; j++) issue_next(buf[j]);
+                    for (int j = EARLY; j < R; j++) issue_next(buf[j], sgn[PK ? j : 0]);
                 }
                 TIMED_BARRIER();                                       // B2: r published
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -702,11 +721,33 @@ __global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_kernel(GemvParams p)
                 if (t <= T) {
                     if (t < T) {
                         const long long tb_ = p.dbg_full ? clock64() : 0;
-                        wait_ring<(R - 1) * NP, NP>(buf[j]);           // stage t landed; R-1 younger stages stay in flight
+                        if constexpr (PK) wait_ring_pk<(R - 1) * 4>(buf[j], sgn[j]);
+                        else wait_ring<(R - 1) * NP, NP>(buf[j]);           // stage t landed; R-1 younger stages stay in flight
                         if (p.dbg_full) t_x += clock64() - tb_;
                         char* dst = ringB + (t & 1) * SB;
                         const float* xst = xs + (size_t)st * (KC * 8);
-                        if constexpr (NCH == 2) {
+                        if constexpr (PK) {
+                            // the raw form's two (chunk, row) pairs, their weights rebuilt from the planes: quads 4 pi .. 4 pi + 3 = gate 0-3, gate 4-7, up 0-3, up 4-7
+                            const unsigned base4 = p.wp_base4, sg = sgn[j];
+#pragma unroll
+                            for (int pi = 0; pi < 2; pi++) {
+                                const int pq = (pi * NH + hw) * 64 + lane, kc = pq / RW, r = pq % RW;
+                                const float4 xa = *(const float4*)(xst + kc * 8), xb = *(const float4*)(xst + kc * 8 + 4);
+                                const u32x4 lo = buf[j][pi];
+                                const unsigned cg = pi ? buf[j][2].z : buf[j][2].x, cu = pi ? buf[j][2].w : buf[j][2].y;
+                                const unsigned hg0 = wpack_hi4(wpack_spread(cg, 0), sg, 4 * pi + 0, base4), hg1 = wpack_hi4(wpack_spread(cg, 1), sg, 4 * pi + 1, base4);
+                                const unsigned hu0 = wpack_hi4(wpack_spread(cu, 0), sg, 4 * pi + 2, base4), hu1 = wpack_hi4(wpack_spread(cu, 1), sg, 4 * pi + 3, base4);
+#define LNB_WIDE4(h, l) __uint_as_float(wpack_wide<0>(h, l)), __uint_as_float(wpack_wide<1>(h, l)), __uint_as_float(wpack_wide<2>(h, l)), __uint_as_float(wpack_wide<3>(h, l))
+                                const float4 ga = mul4(xa, LNB_WIDE4(hg0, lo.x)), gb = mul4(xb, LNB_WIDE4(hg1, lo.y));
+                                const float4 ua = mul4(xa, LNB_WIDE4(hu0, lo.z)), ub = mul4(xb, LNB_WIDE4(hu1, lo.w));
+#undef LNB_WIDE4
+                                char* d = dst + r * 16;
+                                *(float4*)(d + ((4 * kc + 0) * RW) * 16) = make_float4(ga.x, ua.x, ga.y, ua.y);
+                                *(float4*)(d + ((4 * kc + 1) * RW) * 16) = make_float4(ga.z, ua.z, ga.w, ua.w);
+                                *(float4*)(d + ((4 * kc + 2) * RW) * 16) = make_float4(gb.x, ub.x, gb.y, ub.y);
+                                *(float4*)(d + ((4 * kc + 3) * RW) * 16) = make_float4(gb.z, ub.z, gb.w, ub.w);
+                            }
+                        } else if constexpr (NCH == 2) {
                             // both chains of (kc, r): products written pair-interleaved, [k4][half][r] x (gate_s, up_s, gate_s+1, up_s+1)
 #pragma unroll
                             for (int pi = 0; pi < NP / 2; pi++) {
@@ -741,7 +782,7 @@ __global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_kernel(GemvParams p)
                         }
                         if (++st == nstages) st = 0;
                         __builtin_amdgcn_sched_barrier(0);             // refill AFTER the slot has been consumed (no register copies)
-                        issue_next(buf[j]);                            // refill this register slot with stage t+R
+                        issue_next(buf[j], sgn[PK ? j : 0]);           // refill this register slot with stage t+R
                     }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");     // ds_writes complete before the barrier
                     TIMED_BARRIER();
@@ -838,6 +879,10 @@ __global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_kernel(GemvParams p)
     }
     DBG_EXIT();
 }
+template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value>
+__global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_kernel(GemvParams p) { gemv_chain_body<RW, NCH, SA, NH, R, EPI, NORM, XC, false>(p); }
+template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value>
+__global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_pk_kernel(GemvParams p) { gemv_chain_body<RW, NCH, SA, NH, R, EPI, NORM, XC, true>(p); }
 
 // ------------------------------------------------------------------------------------------------
 // gemv_quad_kernel (round 4): the norm-fused thin product wq|wk|wv on ALL CUs, its chains fed through the LDS AND by DPP.
@@ -4376,6 +4421,44 @@ __global__ void synth_fill_kernel(uint16_t* dst, int rows, int K, int row_off, i
     dst[o] = bf_trunc(v);
 }
 
+// ---- the 13-bit planar copy of a gate|up matrix (lnb_wpack.h), built once on the device from the resident chain layout ----------------
+// stats[4] = {min_e2, max_e2, subnormal, infnan} (WpackStats), preset to {0xFF, 0, 0, 0} by the caller
+__global__ void wpack_stats_kernel(const uint16_t* w, size_t n_units, unsigned* stats) {
+    __shared__ unsigned sh[4];
+    if (threadIdx.x == 0) { sh[0] = 0xFFu; sh[1] = sh[2] = sh[3] = 0; }
+    __syncthreads();
+    WpackStats s; wpack_stats_init(&s);
+    for (size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x; u < n_units; u += (size_t)gridDim.x * blockDim.x) {
+        const uint4 v = *(const uint4*)(w + u * 8);
+        const uint16_t* e = (const uint16_t*)&v;
+#pragma unroll
+        for (int i = 0; i < 8; i++) wpack_stats_add(&s, e[i]);
+    }
+    atomicMin(&sh[0], s.min_e2); atomicMax(&sh[1], s.max_e2); if (s.subnormal) atomicOr(&sh[2], 1u); if (s.infnan) atomicOr(&sh[3], 1u);
+    __syncthreads();
+    if (threadIdx.x == 0) { atomicMin(&stats[0], sh[0]); atomicMax(&stats[1], sh[1]); if (sh[2]) atomicOr(&stats[2], 1u); if (sh[3]) atomicOr(&stats[3], 1u); }
+}
+// one thread per (block, stage, helper lane): the lane's four units out of the chain layout [N/RW][K/8][2][RW][8], its group into the stage's planes
+__global__ void wpack_pack_kernel(const uint16_t* w, char* out, int K, int rw, int lanes, int n_blocks, unsigned base) {
+    const int nst = wpack_stages(K, lanes, rw), kcs = 2 * lanes / rw;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)n_blocks * nst * lanes) return;
+    const int L = (int)(idx % lanes), st = (int)((idx / lanes) % nst), b = (int)(idx / ((size_t)lanes * nst));
+    uint4 g[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const int pq = (u >> 1) * lanes + L, kcg = st * kcs + pq / rw, r = pq % rw;
+        g[u] = kcg < (K >> 3) ? *(const uint4*)(w + ((((size_t)b * (K >> 3) + kcg) * 2 + (u & 1)) * rw + r) * 8) : make_uint4(0, 0, 0, 0);
+    }
+    uint32_t low8[8], code4[4], sg;
+    wpack_pack_group((const uint16_t*)g, base, low8, code4, &sg);
+    char* o = out + ((size_t)b * nst + st) * wpack_stage_bytes(lanes);
+    *(uint4*)(o + (size_t)L * 16) = make_uint4(low8[0], low8[1], low8[2], low8[3]);
+    *(uint4*)(o + (size_t)lanes * 16 + (size_t)L * 16) = make_uint4(low8[4], low8[5], low8[6], low8[7]);
+    *(uint4*)(o + (size_t)lanes * 32 + (size_t)L * 16) = make_uint4(code4[0], code4[1], code4[2], code4[3]);
+    *(uint32_t*)(o + (size_t)lanes * 48 + (size_t)L * 4) = sg;
+}
+
 #include "lnb_batch_kernels.h"
 #include "lnb_knobs.h"
 
@@ -4403,9 +4486,10 @@ template <int MIN_HD = 32, class F> static hipError_t with_hd(const AttnParams* 
 // x staging: a whole number of stages (steps per stage = stage_bytes / (nch*rw*2)) + 64 floats of slack
 static size_t xs_bytes(int K, int steps_per_stage) { return ((size_t)((K + steps_per_stage - 1) / steps_per_stage) * steps_per_stage + 320) * 4 + 16; }
 
-template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC>
+template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC, bool PK = false>
 static hipError_t launch_chain_x(const GemvParams* p, hipStream_t st) {
-    auto kfn = gemv_chain_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>;
+    void (*kfn)(GemvParams);
+    if constexpr (PK) kfn = gemv_chain_pk_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; else kfn = gemv_chain_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>;
     if (!p) return raise_lds(kfn);
     size_t lds = 4 * (size_t)SA + xs_bytes(p->K, SA / (NCH * RW * 2));
     if (lds > 160 * 1024) return hipErrorInvalidValue;
@@ -4416,19 +4500,19 @@ static hipError_t launch_chain_x(const GemvParams* p, hipStream_t st) {
 }
 // x staging chunks per stager wave: the norm-fused kernels are instantiated for 2, 3 and 6 chunks of 512 elements per wave (K up to ~4 K, ~6 K / 12 K with
 // the 70B-like shape's 8192 in the middle one, 24 K) and the smallest that holds the padded row is launched; the plain kernels keep their 12
-template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM>
+template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, bool PK = false>
 static hipError_t launch_chain_t(const GemvParams* p, hipStream_t st) {
     if constexpr (NORM) {
         if (!p) {
-            hipError_t e = launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 2>(p, st);
-            if (e == hipSuccess) e = launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 3>(p, st);
-            return e != hipSuccess ? e : launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, XCh<NORM>::value>(p, st);
+            hipError_t e = launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 2, PK>(p, st);
+            if (e == hipSuccess) e = launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 3, PK>(p, st);
+            return e != hipSuccess ? e : launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, XCh<NORM>::value, PK>(p, st);
         }
         const size_t need = xs_bytes(p->K, SA / (NCH * RW * 2)) / 4, per = (size_t)(1 + NH) * 512;
-        if (need <= 2 * per) return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 2>(p, st);
-        if (need <= 3 * per) return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 3>(p, st);
+        if (need <= 2 * per) return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 2, PK>(p, st);
+        if (need <= 3 * per) return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 3, PK>(p, st);
     }
-    return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, XCh<NORM>::value>(p, st);
+    return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, XCh<NORM>::value, PK>(p, st);
 }
 
 template <int RW, int KS, int NH, int R, int EPI, bool NORM, int XC>
@@ -4500,6 +4584,34 @@ static hipError_t launch_gemv_rw(const GemvParams* p, int rw, hipStream_t st) {
     // after the first block of every workgroup: the row-band order a w1|w3 -> w2 pipeline needs (measurement, NOTES.md 6.1)
     if constexpr (NCH == 2) if (rw == 28) return launch_chain_t<28, 2, 14336, 7, 8, EPI, NORM>(p, st);
     return hipErrorInvalidValue;
+}
+
+// The one-token gate|up product of 56-row blocks from the 13-bit planar copy (GemvParams.wp, lnb_wpack.h): 128-step stages -- one 32-weight group per helper
+// lane -- so 2 x 56 KB of products + x = 132 KB of LDS; LNB_W13P_R stages of 52 bytes per lane in flight (5: the raw form's 114 KB per CU)
+#ifndef LNB_W13P_R
+#define LNB_W13P_R 5
+#endif
+#define WPACK_LANES_W13 (7 * 64)
+extern "C" int lnbk_w13p_supported(int rw, int K) {
+    return rw == 56 && K > 0 && K % 8 == 0 && 4 * (size_t)28672 + xs_bytes(K, 128) <= 160 * 1024 && xs_bytes(K, 128) / 4 <= (size_t)XCh<true>::value * 8 * 512 && seq_leaf_size(K, rms_nf(7) * 64) <= 256;
+}
+extern "C" hipError_t lnbk_gemv_w13p(const GemvParams* p, hipStream_t st) {
+    if (p && (!p->wp || !lnbk_w13p_supported(56, p->K))) return hipErrorInvalidValue;
+    return launch_chain_t<56, 2, 28672, 7, LNB_W13P_R, EPI_SILU_MUL, true, true>(p, st);
+}
+extern "C" size_t lnbk_wpack_w13_bytes(int n_blocks, int K) { return wpack_bytes(n_blocks, K, WPACK_LANES_W13, 56); }
+// d_stats: four words on the device; on return (after the stream has run) the matrix's WpackStats
+extern "C" hipError_t lnbk_wpack_stats(const uint16_t* w, size_t elems, unsigned* d_stats, hipStream_t st) {
+    static const unsigned init[4] = {0xFFu, 0, 0, 0};
+    hipError_t e = hipMemcpyAsync(d_stats, init, sizeof init, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wpack_stats_kernel, dim3(1024), dim3(256), 0, st, w, elems / 8, d_stats);
+    return hipGetLastError();
+}
+extern "C" hipError_t lnbk_wpack_w13(const uint16_t* w, void* out, int K, int n_blocks, unsigned base, hipStream_t st) {
+    const size_t n = (size_t)n_blocks * wpack_stages(K, WPACK_LANES_W13, 56) * WPACK_LANES_W13;
+    hipLaunchKernelGGL(wpack_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, (char*)out, K, 56, WPACK_LANES_W13, n_blocks, base);
+    return hipGetLastError();
 }
 
 template <int EPI> static hipError_t launch_rowcast(const GemvParams* p, hipStream_t st) {
@@ -4732,6 +4844,7 @@ extern "C" hipError_t lnbk_init(void) {
         gemv(rw, 1, EPI_STORE, 1); gemv(rw, 1, EPI_STORE, 0); gemv(rw, 1, EPI_QKV_ROPE, 1); gemv(rw, 1, EPI_RESID, 0);
         if (rw != 24) gemv(rw, 2, EPI_SILU_MUL, 1);
     }
+    if (e == hipSuccess) e = lnbk_gemv_w13p(nullptr, nullptr);
     for (auto prepare : {launch_attn_long<true>, launch_attn_long<false>, launch_attn_one, launch_attn_short}) if (e == hipSuccess) e = prepare(nullptr, nullptr);
     if (e == hipSuccess) e = launch_attn_rows(nullptr, -1, nullptr);
     if (e != hipSuccess) return e;

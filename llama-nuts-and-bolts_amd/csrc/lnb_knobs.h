@@ -13,6 +13,8 @@
     X(RW_W2, 0, LIVE, "rows per block of the resident w2 layout (16 with W2_QUAD: measurement; 0: by shape)") \
     X(RW_OUT, 0, LIVE, "rows per block of the resident LM-head layout (0: by shape)") \
     X(RW_OP, 0, LIVE, "rows per block of a stand-alone lnb_op_linear operand (0: by shape)") \
+    /* one-token decode */ \
+    X(W13_PACKED, 1, LIVE, "0: lnb_model_finalize builds no 13-bit planar copy of the gate|up matrices; the one-token step streams the raw bf16 (lnb_model_wpack_info)") \
     /* prefill form */ \
     X(PREFILL_MFMA, 1, ONCE, "0: calls of 16+ rows stay on the one-row kernels (what the parity tests compare the matrix-core forms with)") \
     X(PREFILL_STREAM, 1, ONCE, "0: prefill products on the LDS-tiled gemm_mfma_kernel, never the streaming feed") \

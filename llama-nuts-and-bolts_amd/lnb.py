@@ -63,6 +63,7 @@ EXPORTS = [
     "lnb_model_enable_batch", "lnb_model_batch_bytes", "lnb_batch_create", "lnb_batch_destroy", "lnb_batch_decode", "lnb_batch_decode_until", "lnb_ctx_set_stop_ids", "lnb_decode_greedy_until", "lnb_batch_profile_kernel", "lnb_batch_set_state", "lnb_batch_check_error", "lnb_pipeline_tick_batch",
     "lnb_pipeline_init_host", "lnb_batch_boundary_ptr",
     "lnb_abi_version", "lnb_runtime_info", "lnb_profile_ffn_pair",
+    "lnb_model_wpack_bytes", "lnb_model_wpack_info", "lnb_op_rmsnorm_gate_up",
     "lnb_ctx_set_token_probs", "lnb_ctx_read_token_probs", "lnb_ctx_token_prob_walks", "lnb_forward_score", "lnb_op_token_probs",
     "lnb_forward_append", "lnb_forward_score_append",
     "lnb_ctx_set_draft", "lnb_decode_speculative_until", "lnb_op_ngram_draft",
@@ -179,6 +180,10 @@ def lib():
     L.lnb_model_enable_batch.argtypes = [vp]
     L.lnb_model_batch_bytes.argtypes = [vp]
     L.lnb_model_batch_bytes.restype = C.c_int64
+    L.lnb_model_wpack_bytes.argtypes = [vp]
+    L.lnb_model_wpack_bytes.restype = C.c_int64
+    L.lnb_model_wpack_info.argtypes = [vp, i32p]
+    L.lnb_op_rmsnorm_gate_up.argtypes = [C.c_int, vp, vp, C.c_float, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.lnb_batch_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp)]
     L.lnb_batch_destroy.argtypes = [vp]
     L.lnb_batch_decode.argtypes = [vp, i32p, i32p, C.c_int, vp, f32p]
@@ -491,6 +496,16 @@ class LlamaTransformer:
 
     def batch_bytes(self):
         return int(self.L.lnb_model_batch_bytes(self.h))
+
+    def wpack_bytes(self):
+        """device bytes of the 13-bit planar copies of the gate|up matrices (lnb_model_wpack_bytes)"""
+        return int(self.L.lnb_model_wpack_bytes(self.h))
+
+    def wpack_info(self):
+        """gate|up matrices by what the one-token step streams them from (lnb_model_wpack_info)"""
+        c = np.zeros(6, dtype=np.int32)
+        _chk(self.L.lnb_model_wpack_info(self.h, c.ctypes.data_as(C.POINTER(C.c_int32))))
+        return dict(zip(("packed", "subnormal", "infnan", "window", "no_memory", "not_tried"), (int(v) for v in c)))
 
     def append_many_info(self):
         """of the last ForwardAppendMany on this transformer: {passes, max_columns, long_passes} (lnb_model_append_many_info)"""
@@ -1062,3 +1077,17 @@ def _splitmix64(z):
 def synth_tokens(seed, n, vocab):
     """Synthetic prompt of DESIGN.md ("Synthetic weights"): tok[i] = splitmix64(seed ^ i*golden) mod vocab."""
     return np.array([_splitmix64(seed ^ ((i * 0x9E3779B97F4A7C15) & _M64)) % vocab for i in range(n)], dtype=np.int32)
+
+
+def op_rmsnorm_gate_up(x_u16, norm_w_u16, eps, w1_u16, w3_u16, packed=1, device=0):
+    """ffn_norm + w1|w3 + SiLU(gate)*up of one row, as the one-token step launches it -> (y uint16 [n_out], WPACK status of the matrix)"""
+    x = np.ascontiguousarray(x_u16, dtype=np.uint16).reshape(-1)
+    nw = np.ascontiguousarray(norm_w_u16, dtype=np.uint16)
+    w1 = np.ascontiguousarray(w1_u16, dtype=np.uint16)
+    w3 = np.ascontiguousarray(w3_u16, dtype=np.uint16)
+    n, k = w1.shape
+    assert w3.shape == (n, k) and x.shape == (k,) and nw.shape == (k,)
+    y = np.empty(n, dtype=np.uint16)
+    st = C.c_int(0)
+    _chk(lib().lnb_op_rmsnorm_gate_up(device, _p(x), _p(nw), np.float32(eps), _p(w1), _p(w3), _p(y), n, k, int(packed), C.byref(st)))
+    return y, st.value

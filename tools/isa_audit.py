@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Static audit of the hand-counted register rings in gemv_chain_kernel, rowcast_kernel, attn_exact_kernel and mfma_stream_kernel
+"""Static audit of the hand-counted register rings in gemv_chain_kernel (and its packed-source form gemv_chain_pk_kernel), rowcast_kernel, attn_exact_kernel and mfma_stream_kernel
 (llama-nuts-and-bolts_amd/csrc/lnb_kernels.hip, lnb_batch_kernels.h).
 
 The helper waves issue `global_load_dwordx4 ... nt` from inline asm (invisible to hipcc's s_waitcnt bookkeeping) and
@@ -165,12 +165,12 @@ def main(asm_path=None):
     with tempfile.TemporaryDirectory() as wd:
         asm = asm_path if asm_path else compile_to_asm(wd)
         txt = open(asm).read().split("\n")
-    funcs = split_functions(txt, r"_Z\d\d(?:gemv_chain|gemv_quad|attn_exact|attn_gqa|attn_long_scores|attn_mfma3|rowcast|rowcast_lds|mfma_stream|mfma_pair|gemm_stream)_kernel\S*")
+    funcs = split_functions(txt, r"_Z\d\d(?:gemv_chain|gemv_chain_pk|gemv_quad|attn_exact|attn_gqa|attn_long_scores|attn_mfma3|rowcast|rowcast_lds|mfma_stream|mfma_pair|gemm_stream)_kernel\S*")
     total = 0
     for name, lines in funcs.items():
         # gemv_chain_kernel: the ring lives in helper waves that always run with a full EXEC mask, so the structurizer's
         # execz skip-edges are dead there; the other kernels are analysed with both edges
-        v = audit_function(lines, execz_both=not (name.startswith("_Z17gemv_chain") or name.startswith("_Z16gemv_quad")))
+        v = audit_function(lines, execz_both=not name.startswith(("_Z17gemv_chain", "_Z20gemv_chain_pk", "_Z16gemv_quad")))
         reach = sum(1 for _, l in lines if "RING_RETIRE" in l)
         body = "\n".join(l for _, l in lines)
         n_loads = body.count("RING_LOAD")
