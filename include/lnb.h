@@ -226,7 +226,16 @@ int lnb_ctx_set_layer_callback(lnb_ctx* c, lnb_layer_cb cb, void* user);
  * start_pos+seq beyond the RoPE table or the KV cache (tensor.go:275-279; the reference silently drops the
  * SetSlice error at llamatransformer.go:402-403 and then fails in Slice :409 -- here it fails up front);
  * seq > 1 with (start_pos+seq) % seq != 0 "two tensor shapes cannot be broadcasted" (tensor.go:414-428).
- * Requires a whole-model handle (layer_begin == 0 && layer_end == n_layers). */
+ * Requires a whole-model handle (layer_begin == 0 && layer_end == n_layers).
+ * Non-finite rows: the multi-row attention kernels rest on finite K / V rows (a masked entry is e = 0 without its score, positions beyond the
+ *   diagonal are skipped).  The reference ADDS the mask (NaN + -inf = NaN) and multiplies p = +0 by every V row of the call, so one NaN row makes
+ *   every row of a modulo-mask call NaN.  A multi-row call therefore scans the K / V rows each layer writes (as lnb_ctx_load_prefix scans the rows
+ *   it loads; lnb_ctx_fork hands the source's flag on; lnb_ctx_reset clears it), and a context that holds an inf or a NaN recomputes the attention
+ *   of its multi-row calls the reference's way, row by row (slow; the same bits as the reference, tests/test_gpu_attention_crafted.py).  Calls on
+ *   finite rows launch one scan and one early-returning kernel per layer beyond what they launched before.
+ *   Stated limit: rows written by ONE-TOKEN calls, batched and speculative decode are not scanned, and a +inf SCORE of finite rows (|k| ~ 1e38) at
+ *   a masked position is not seen by the scan; a later modulo-mask call at start_pos > 0 over such rows may keep rows finite that the reference
+ *   makes NaN.  lnb_forward_append is not affected: every earlier row is unmasked for every row of an append. */
 int lnb_forward(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out);
 
 /* ---- causal multi-row append: extend a live context by seq tokens in ONE call, at any start position -------------------------------
@@ -240,6 +249,8 @@ int lnb_forward(lnb_ctx* c, const int32_t* tokens, int seq, int start_pos, float
  *   (start_pos + seq) % seq condition.  At start_pos == 0 the result equals lnb_forward of the same rows.
  *   Why it is exact: the linear layers are per-row chains already; the reference's softmax subtracts no maximum, so a masked entry adds +0 to
  *   the f64 sum and to the PV chain -- a row masked to j <= start_pos + i IS the shorter row of the one-token step.
+ *   That argument holds for finite V rows; +0 x NaN is NaN.  A call whose own rows hold an inf or a NaN (scanned as they are written, see
+ *   lnb_forward) is recomputed row by row with each row's own T, so the contract holds there too: the rows before a NaN row stay finite.
  *   Afterwards lnb_decode_greedy[_until], lnb_decode_speculative_until, lnb_batch_* and further appends continue the context.
  *   Kernels: 16 or more rows at head_dim 64 / 128 run the matrix-core attention with the causal mask (tiles above the shifted diagonal are
  *   skipped); 2..15 rows, and any row count at head_dim 32, the row-per-workgroup kernel.  Where that kernel cannot stage the context (see

@@ -37,6 +37,9 @@ extern "C" {
 hipError_t lnbk_gemv(const GemvParams* p, int rw, int nch, int epi, int norm, hipStream_t st);
 hipError_t lnbk_attn(const AttnParams* p, hipStream_t st);
 hipError_t lnbk_attn_rows(const AttnParams* p, int pos0, hipStream_t st);
+hipError_t lnbk_kv_scan_nonfinite(const uint16_t* ck, const uint16_t* cv, int seq_len, int kv_dim, int hd, const StepState* st, int pos0, int rows, int* word, hipStream_t s);
+hipError_t lnbk_nonfinite_or(int* dst, const int* src, hipStream_t s);
+hipError_t lnbk_attn_plain(const AttnParams* p, const int* word, hipStream_t st);
 int lnbk_attn_short_max_T(int hd);
 size_t lnbk_attn_long_lds(int seq_len);
 size_t lnbk_attn_long_layout_lds(int seq_len);
@@ -805,7 +808,7 @@ static int ctx_alloc(lnb_ctx* c) {
     const size_t SL = c->seq_len;
     HIPCHK(hipMalloc((void**)&c->e_buf, (size_t)m->a.n_heads * SL * 8));
     HIPCHK(hipMalloc((void**)&c->z_part, (size_t)m->a.n_heads * ((SL + 63) / 64 + 8) * 8));     // (two-launch form: one partial per 256 positions; attn_one_kernel: one per 64)
-    HIPCHK(hipMalloc((void**)&c->zseq_count, 16)); HIPCHK(hipMemsetAsync(c->zseq_count, 0, 16, c->stream));
+    HIPCHK(hipMalloc((void**)&c->zseq_count, 16)); HIPCHK(hipMemsetAsync(c->zseq_count, 0, 16, c->stream));      // [0] serial-sum walks, [1] norm fallbacks, [2] token-probability walks, [3] sticky: a cached row holds an inf or a NaN
     HIPCHK(hipMalloc((void**)&c->attn_cnt, ((size_t)m->a.n_heads + 4) * 4)); HIPCHK(hipMemsetAsync(c->attn_cnt, 0, ((size_t)m->a.n_heads + 4) * 4, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     // crossover measured on MI355X (tools/att_timing.py): the one-workgroup-per-head kernel wins below a few hundred positions
@@ -862,6 +865,7 @@ extern "C" int lnb_ctx_reset(lnb_ctx* c) {
     HIPCHK(hipSetDevice(c->m->device));
     const size_t kvn = (size_t)c->seq_len * c->m->kv_dim;
     for (size_t l = 0; l < c->ck.size(); l++) if (c->ck[l]) { HIPCHK(hipMemsetAsync(c->ck[l], 0, kvn * 2, c->stream)); HIPCHK(hipMemsetAsync(c->cv[l], 0, kvn * 2, c->stream)); }
+    HIPCHK(hipMemsetAsync(c->zseq_count + 3, 0, 4, c->stream));      // no cached row holds an inf or a NaN any more
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -929,6 +933,7 @@ extern "C" int lnb_ctx_fork(lnb_ctx* src, int n_pos, lnb_ctx* const* dsts, int n
                 HIPCHK(hipMemcpyAsync(dsts[d]->cv[l], src->cv[l], v_bytes, hipMemcpyDeviceToDevice, src->stream));
             }
         }
+        for (int d = 0; d < n_dst; d++) HIPCHK(lnbk_nonfinite_or(dsts[d]->zseq_count + 3, src->zseq_count + 3, src->stream));
         HIPCHK(hipStreamSynchronize(src->stream));
         return 0;
     }
@@ -952,6 +957,7 @@ extern "C" int lnb_ctx_fork(lnb_ctx* src, int n_pos, lnb_ctx* const* dsts, int n
     tab.ptrs = (const void* const*)src->fork_tab; tab.cap_dst = (const int*)((const char*)src->fork_tab + ptr_bytes);
     tab.n_arrays = n_arrays; tab.n_dst = n_dst; tab.kv_dim = m->kv_dim; tab.n_pos = n_pos; tab.cap_src = src->seq_len;
     const hipError_t launched = lnbk_kv_fork(&tab, knob(Knob::FORK_NT), knob(Knob::FORK_SPLIT), src->stream);
+    for (int d = 0; d < n_dst; d++) (void)lnbk_nonfinite_or(dsts[d]->zseq_count + 3, src->zseq_count + 3, src->stream);      // the word travels with the rows
     HIPCHK(hipStreamSynchronize(src->stream));
     if (launched != hipSuccess) return fail("kv_fork_kernel could not be launched: %s", hipGetErrorString(launched));
     return 0;
@@ -1037,6 +1043,9 @@ extern "C" int lnb_ctx_load_prefix(lnb_ctx* c, const void* host, int64_t nbytes,
             if (!c->ck[l]) continue;
             if (prefix_copy_layer(c, l, n_pos, (unsigned char*)p, false)) { hipStreamSynchronize(c->stream); return -1; }
             p += kvc_layer_bytes(m->kv_dim, n_pos);
+            // (the blob's rows are the caller's: an inf or a NaN among them raises the context's word, see enqueue_layer_kernel's K_ATTN)
+            const hipError_t scanned = lnbk_kv_scan_nonfinite(c->ck[l], c->cv[l], c->seq_len, m->kv_dim, m->head_dim, nullptr, 0, n_pos, c->zseq_count + 3, c->stream);
+            if (scanned != hipSuccess) { hipStreamSynchronize(c->stream); return fail("kv_nonfinite_scan_kernel could not be launched: %s", hipGetErrorString(scanned)); }
         }
         HIPCHK(hipStreamSynchronize(c->stream));
     }
@@ -1195,15 +1204,22 @@ static int enqueue_layer_kernel(lnb_ctx* c, int l, int S, int which, hipStream_t
                              a.n_heads * (m->head_dim / 16) <= g_num_cus && lnbk_attn_one_lds(c->seq_len, m->head_dim) <= (size_t)160 * 1024;
             ap.longctx = one ? ((c->force_zseq & 4) ? 3 : 2) : 1;
         }
+        // a multi-row call: the context's sticky word "a cached row holds an inf or a NaN" (zseq_count[3]) takes the rows this layer just wrote
+        const bool multi = S > 1 && c->mode == LNB_MODE_EXACT;
+        if (multi) HIPCHK(lnbk_kv_scan_nonfinite(ck, cv, c->seq_len, m->kv_dim, m->head_dim, c->st, 0, S, c->zseq_count + 3, st));
         if (c->attn_rows && ap.causal) {                     // lnb_forward_append beyond the row-per-workgroup kernel's reach: K and V read once for all rows
             ap.e_buf = c->sp_e_buf; ap.z_part = c->sp_z_part; ap.force_zseq = c->rows_flags & 1;
-            HIPCHK(lnbk_attn_rows(&ap, c->call_T - S, st)); return 0;
+            HIPCHK(lnbk_attn_rows(&ap, c->call_T - S, st)); return 0;       // (every row of the pair ends at its own T: nothing to recompute)
         }
         if (c->mode == LNB_MODE_FAST && ap.mfma) {           // tolerance mode prefill: flash form on the bf16 matrix cores
             hipError_t e = lnbk_fast_attn(&ap, st);
             if (e != hipErrorNotSupported) { HIPCHK(e); return 0; }
         }
-        HIPCHK(lnbk_attn(&ap, st)); return 0; }
+        HIPCHK(lnbk_attn(&ap, st));
+        // the multi-row kernels rest on finite rows (lnb_kernels.hip, attn_mfma_kernel's header): with the word set the rows are computed again the
+        // reference's way -- the launch returns at once otherwise, and a call of one row launches nothing new
+        if (multi) HIPCHK(lnbk_attn_plain(&ap, c->zseq_count + 3, st));
+        return 0; }
     case K_WO: {    // wo + residual  (:522, :232)
         GemvParams o{}; o.w = L.wo.w; o.x = c->att; o.K = m->q_dim; o.n_rows = a.dim; o.S = S; o.st = c->st; o.out = hbuf; o.res = c->x; o.sched = c->sched;
         set_grid(o, L.wo); HIPCHK(gemv_dispatch(c, &o, L.wo.rw, 1, EPI_RESID, 0, st)); return 0; }

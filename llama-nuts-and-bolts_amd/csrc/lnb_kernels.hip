@@ -1905,8 +1905,11 @@ extern "C" hipError_t lnbk_exp_table(double* tab, float divisor, hipStream_t st)
 //   pass 2  the scores again (cheaper than keeping S x T doubles), p = trunc(f32(e / Z_i)), transposed through the LDS into the A
 //           operand layout, and out[i][d] += p[i][j] v[j][d] with j ascending inside and across the MFMAs (lane n owns the HD/16
 //           consecutive output dims n*HD/16.., so one 16 B load of a V row feeds its eight MFMAs).
-// Masked positions (j % S > i, the modulo-broadcast [S,S] mask) contribute e = 0 -> p = +0; acc + (+-0) == acc and acc is never -0,
-// so with the standard causal layout (pos0 == 0) the tiles above the diagonal are skipped like attn_exact_kernel does.
+// Masked positions (j % S > i, the modulo-broadcast [S,S] mask) contribute e = 0 -> p = +0.  With FINITE K and V rows the masked score adds
+// to -inf and the product p * v is +-0, acc + (+-0) == acc and acc is never -0, so with the standard causal layout (pos0 == 0) the tiles above
+// the diagonal are skipped like attn_exact_kernel does.  With a NaN or inf in a row this is NOT the reference (NaN + -inf = NaN, +0 x NaN = NaN,
+// and a tile's 16 positions are the B operand of all 16 query rows): the entry point scans the rows a multi-row call writes
+// (kv_nonfinite_scan_kernel) and attn_plain_kernel, launched behind this kernel, recomputes the call's rows when the context holds such a row.
 // CAUSAL (lnb_forward_append, AttnParams::causal; a template parameter, so the modulo form's instantiation is the code it was): the mask is
 // j > pos0 + irow at ANY pos0.  The softmax subtracts no maximum and a masked entry adds +0 to the f64 sum and to the PV chain, so row i of the
 // call is the shorter row of the one-token step at pos0 + i, bit for bit; tiles wholly above the SHIFTED diagonal are skipped
@@ -2619,7 +2622,8 @@ template <int HD, int D = 3> DEVINL void attn_pv_produce(int c, int nchunks, int
 template <int HD> DEVINL void attn_pv_add(int c, int nchunks, int r, const char* ring, float& acc) {      // r: the lane's ring ROW (its dim: attn_row_dim)
     constexpr int SLOT = ATT_RP * HD * 4;
     if (c > 0 && c <= nchunks && r < HD) {
-        // positions past the end of the row carry p == +0: their products are +-0 and acc is never -0, so whole chunks are added
+        // positions past the end of the row carry p == +0 and a V row clamped to T - 1, the call's own last row: for finite V their products are
+        // +-0 and acc is never -0, so whole chunks are added (a multi-row call whose rows hold an inf or a NaN is recomputed by attn_plain_kernel)
         const float* src = (const float*)(ring + ((c - 1) & 1) * SLOT) + r * ATT_RP;
         float4 a[ATT_JC / 4];
 #pragma unroll
@@ -3673,12 +3677,16 @@ template <int HD, int RPW> __global__ __launch_bounds__(ALP_NT) void attn_rows_p
 #pragma unroll
                 for (int rr = 0; rr < NR; rr++) {            // round rr = chunk rr of the batch; position prow of it
                     const int j = b * B + rr * 128 + prow;
-                    const uint4 w = r_.v[rr];                // ONE V row, products for every row of the workgroup (exact: 8-bit x 8-bit significands)
+                    const uint4 wv = r_.v[rr];               // ONE V row, products for every row of the workgroup (exact: 8-bit x 8-bit significands)
 #pragma unroll
                     for (int r = 0; r < RPW; r++) {
                         if (!on[r]) continue;
-                        float pj = 0.0f;                     // +0 past the row's end: products +-0, acc is never -0
-                        if (j < T[r]) pj = exact ? alp_p(r_.e[r][rr], zsh[r]) : cert_p(r_.e[r][rr], cz[r], bad);       // impl:506 + ToBFloat16 :493
+                        // past the row's end: p = +0 AND V = +0, products +0 (acc is never -0).  The V row there is a later row of the call, a stale row of
+                        // an earlier generation or the array's end: it may hold anything, a NaN or an inf included, and +0 x NaN would reach the chain
+                        const bool live = j < T[r];
+                        const uint4 w = live ? wv : make_uint4(0u, 0u, 0u, 0u);
+                        float pj = 0.0f;
+                        if (live) pj = exact ? alp_p(r_.e[r][rr], zsh[r]) : cert_p(r_.e[r][rr], cz[r], bad);       // impl:506 + ToBFloat16 :493
                         float* q = dst + (size_t)(2 * r) * SLOT + rr * 128;
                         q[0 * B] = pj * bf_lo(w.x); q[1 * B] = pj * bf_hi(w.x); q[2 * B] = pj * bf_lo(w.y); q[3 * B] = pj * bf_hi(w.y);
                         q[4 * B] = pj * bf_lo(w.z); q[5 * B] = pj * bf_hi(w.z); q[6 * B] = pj * bf_lo(w.w); q[7 * B] = pj * bf_hi(w.w);
@@ -3722,6 +3730,88 @@ template <int HD, int RPW> __global__ __launch_bounds__(ALP_NT) void attn_rows_p
 #pragma unroll
         for (int r = 0; r < RPW; r++) if (on[r]) ar_store(rp, rp.row0 + g0 + r, h, HD, ds * ALP_DS + 4 * wave + (lane >> 4), acc[r]);
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Non-finite K / V rows in a multi-row call (lnb_forward, lnb_forward_append): the matrix-core kernels and the multi-row forms of
+// attn_exact_kernel rest on FINITE rows -- a masked entry is e = 0 without its score, tiles and chunks beyond the diagonal are skipped, and
+// the 16 positions of a tile are the B operand of all 16 query rows.  The reference adds the mask to the score (NaN + -inf = NaN: the whole
+// row NaN) and multiplies p = +0 by every V row of the call (+0 x NaN = NaN); the one-token step at an earlier position never sees a later row.
+//   kv_nonfinite_scan_kernel  raises the context's sticky word when one of the rows [pos, pos + rows) of a layer's K or V holds an inf or a NaN;
+//   attn_plain_kernel<HD>     launched behind the attention of such a call: returns at once while the word is clear; otherwise workgroup
+//       (head, row) computes the row again as the reference's attention does (llamatransformer.go:409-514) -- every position's score, the mask ADDED (modulo form)
+//       or the row's own T (causal form), the serial f64 sum, PV over every position, j ascending -- and overwrites the row's output.
+// Slow and obvious on purpose: 256 positions scored per round, one thread adds them in order, head_dim threads own one output dim each.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void kv_nonfinite_scan_kernel(const uint16_t* ck, const uint16_t* cv, int seq_len, int kv_dim, int hd, const StepState* st, int pos0,
+                                                                int rows, int* word) {
+    const int pos = st ? st->pos : pos0;
+    const size_t n = (size_t)rows * kv_dim;
+    bool hit = false;
+    for (size_t x = (size_t)blockIdx.x * 256 + threadIdx.x; x < n; x += (size_t)gridDim.x * 256) {
+        const int j = pos + (int)(x / kv_dim), c = (int)(x % kv_dim), kh = c / hd, d = c % hd;
+        if (j >= seq_len) break;
+        const uint16_t k = ck[(((size_t)kh * (hd >> 3) + (d >> 3)) * seq_len + j) * 8 + (d & 7)], v = cv[(size_t)j * kv_dim + c];
+        hit |= (k & 0x7F80) == 0x7F80 || (v & 0x7F80) == 0x7F80;
+    }
+    if (hit) atomicOr(word, 1);
+}
+__global__ void nonfinite_or_kernel(int* dst, const int* src) { if (*src) atomicOr(dst, 1); }
+template <int HD> __global__ __launch_bounds__(256) void attn_plain_kernel(AttnParams p, const int* nonfinite) {
+    if (*nonfinite == 0) return;                             // (uniform) every row the call can see is finite: the fast kernel's result stands
+    constexpr int NK = HD / 8, NT = 256;
+    __shared__ __attribute__((aligned(16))) float qf[HD];
+    __shared__ double eb[NT];
+    __shared__ float pb[NT];
+    __shared__ double zs;
+    const int tid = threadIdx.x, h = blockIdx.x, i = blockIdx.y;
+    const int S = p.S, pos0 = p.st->pos;
+    int T = p.causal ? pos0 + i + 1 : pos0 + S;              // causal: row i IS the one-token step at pos0 + i
+    T = T > p.seq_len ? p.seq_len : T;
+    const bool add_mask = !p.causal && S > 1;                // Add(scores, mask), the [S,S] mask broadcast by modulo (llamatransformer.go:469-473)
+    const int kvh = h / (p.H / p.KVH);
+    const uint4* kbase = (const uint4*)p.cache_k + (size_t)kvh * NK * p.seq_len;
+    const uint16_t* vbase = p.cache_v + (size_t)kvh * HD;
+    const size_t vrow = (size_t)p.KVH * HD;
+    if (tid < HD) qf[tid] = bf_wide(p.q[((size_t)i * p.H + h) * HD + tid]);
+    __syncthreads();
+    auto e_of = [&](int j) -> double {
+        uint4 k[NK];
+        attn_load_k<NK>(k, kbase, p.seq_len, j);
+        float acc = 0.0f;
+#pragma unroll
+        for (int c = 0; c < NK; c++) {                       // MatMul q.k, d ascending (operations_matmul.go:37-55)
+            const float4 xa = *(const float4*)(qf + c * 8), xb = *(const float4*)(qf + c * 8 + 4);
+            acc = mac8(acc, xa, xb, k[c]);
+        }
+        uint16_t s = bf_trunc(acc);
+        s = bf_trunc(__fdiv_rn(bf_wide(s), p.divisor));     // DivToScalar :464
+        if (add_mask) s = bf_trunc(bf_wide(s) + ((j % S) > i ? -INFINITY : 0.0f));
+        return exp((double)bf_wide(s));
+    };
+    double z = 0.0;                                          // rowExpSum += exp(...), j ascending, f64 (impl:492-499): thread 0
+    for (int j0 = 0; j0 < T; j0 += NT) {
+        const int j = j0 + tid;
+        eb[tid] = j < T ? e_of(j) : 0.0;
+        __syncthreads();
+        if (tid == 0) { const int n = T - j0 < NT ? T - j0 : NT; for (int u = 0; u < n; u++) z += eb[u]; }
+        __syncthreads();
+    }
+    if (tid == 0) zs = z;
+    __syncthreads();
+    z = zs;
+    float acc = 0.0f;
+    for (int j0 = 0; j0 < T; j0 += NT) {
+        const int j = j0 + tid;
+        if (j < T) pb[tid] = bf_wide(bf_trunc((float)(e_of(j) / z)));       // impl:506 + ToBFloat16 :493
+        __syncthreads();
+        if (tid < HD) {
+            const int n = T - j0 < NT ? T - j0 : NT;
+            for (int u = 0; u < n; u++) acc += pb[u] * bf_wide(vbase[(size_t)(j0 + u) * vrow + tid]);      // MatMul(scores, values) :504, every position
+        }
+        __syncthreads();
+    }
+    if (tid < HD) p.out[((size_t)i * p.H + h) * HD + tid] = bf_trunc(acc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4831,6 +4921,26 @@ extern "C" hipError_t lnbk_attn(const AttnParams* p, hipStream_t st) {
     if (p->longctx && p->S == 1) return launch_attn_long<false>(p, st);
     if (p->mfma && p->S >= 16 && (p->hd == 128 || p->hd == 64)) return launch_attn_prefill(p, st);
     return launch_attn_short(p, st);
+}
+// rows [pos, pos + rows) of one layer's caches (st: the position is the device state's; nullptr: pos0): raises *word on an inf or a NaN
+extern "C" hipError_t lnbk_kv_scan_nonfinite(const uint16_t* ck, const uint16_t* cv, int seq_len, int kv_dim, int hd, const StepState* st, int pos0, int rows, int* word, hipStream_t s) {
+    if (!ck || !cv || !word || rows < 1 || kv_dim < 1 || hd < 8 || kv_dim % hd || (!st && (pos0 < 0 || pos0 > seq_len - rows))) return hipErrorInvalidValue;
+    const size_t n = (size_t)rows * kv_dim;
+    const unsigned blocks = (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
+    hipLaunchKernelGGL(kv_nonfinite_scan_kernel, dim3(blocks), dim3(256), 0, s, ck, cv, seq_len, kv_dim, hd, st, pos0, rows, word);
+    return hipGetLastError();
+}
+extern "C" hipError_t lnbk_nonfinite_or(int* dst, const int* src, hipStream_t s) {
+    hipLaunchKernelGGL(nonfinite_or_kernel, dim3(1), dim3(1), 0, s, dst, src);
+    return hipGetLastError();
+}
+// behind the attention launch of a multi-row call of one context: the rows again, the reference's way, if the context's word is set
+extern "C" hipError_t lnbk_attn_plain(const AttnParams* p, const int* word, hipStream_t st) {
+    if (!p || !word || p->btab || !p->st || !p->q || !p->out || !p->cache_k || !p->cache_v || p->S < 1 || p->H < 1 || p->KVH < 1 || p->H % p->KVH) return hipErrorInvalidValue;
+    return with_hd(p, [&](auto HD) {
+        hipLaunchKernelGGL(attn_plain_kernel<HD>, dim3(p->H, p->S), dim3(256), 0, st, *p, word);
+        return hipGetLastError();
+    });
 }
 extern "C" hipError_t lnbk_init(void) {
     static bool done = false;
