@@ -212,6 +212,16 @@ int lnb_ctx_norm_fallbacks(lnb_ctx* c, int* out);
  * a bench prints it so that a silently refused scratch shows.  The scratch is 512 bytes per (head, 16 query rows, 16 positions) -- 1.07 GB for a 4096-row prompt of the
  * 8B shape --, one per context, grown on demand; a context's first one-token call after the prompt frees it when it is larger than LNB_ATTN_SIDX_KEEP_MB (default 256). */
 int lnb_ctx_prefill_attention_form(const lnb_ctx* c, int* out);
+/* The launch tally: which kernel FORM the launch layer picked (csrc/lnb_forms.h lists the forms: one row per arm of a launch function's choice by shape or by
+ * LNB_* knob -- "gemm_mfma.t64", "gemm_stream.chain.ntw2", "rmsnorm_rows.wave" ...).  Process-wide counters, incremented on the host where the kernel is chosen; a
+ * launch recorded during a graph capture counts once, at capture, and replays do not count.  What it is for: a test (or a bench) that sets a knob asserts that the
+ * form it meant really ran -- a ONCE knob set after its first use is silently without effect.
+ *   lnb_form_count: launches of `form` since the last reset with epilogue `epi` (0 store, 1 RoPE + KV append, 2 residual, 3 SiLU*up; forms that are no product count
+ *   under 0), epi = -1: the sum.  An unknown name is an error whose message names it.
+ *   lnb_form_name: the name of row `index` (0 .. until it fails): enumeration. */
+int lnb_form_count(const char* form, int epi, int64_t* out);
+int lnb_form_count_reset(void);
+int lnb_form_name(int index, const char** name);
 /* optional per-layer progress hook = infContext.Logf("Transformer block layer %d / %d was run, took %.4f sec(s)")
  * (llamatransformer.go:157-163); forces a per-layer stream sync, so it is off by default */
 typedef void (*lnb_layer_cb)(int layer_1based, int n_layers, double secs, void* user);

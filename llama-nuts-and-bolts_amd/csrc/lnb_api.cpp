@@ -21,6 +21,7 @@
 #include "../../include/lnb.h"
 #include "lnb_device.h"
 #include "lnb_knobs.h"
+#include "lnb_forms.h"
 #include "lnb_kvcopy.h"
 #include "lnb_rowpack.h"
 #include "lnb_wpack.h"
@@ -293,6 +294,22 @@ static int alloc_linear(uint16_t** p, size_t elems, int64_t& bytes) {
 
 extern "C" int lnb_device_count(int* out) { int n = 0; HIPCHK(hipGetDeviceCount(&n)); *out = n; return 0; }
 extern "C" int lnb_abi_version(void) { return LNB_ABI_VERSION; }
+// the launch tally (lnb_forms.h): which kernel forms the launch functions of this process have picked since the last reset
+extern "C" int lnb_form_count(const char* form, int epi, int64_t* out) {
+    if (!form || !out) return fail("null argument");
+    const int i = form_index(form);
+    if (i < 0) return fail("unknown form '%s' (lnb_form_name enumerates the table of csrc/lnb_forms.h)", form);
+    if (epi < -1 || epi >= LNB_FORM_EPIS) return fail("epilogue %d: -1 (the sum) or 0..%d", epi, LNB_FORM_EPIS - 1);
+    *out = form_count(i, epi);
+    return 0;
+}
+extern "C" int lnb_form_count_reset(void) { form_count_reset(); return 0; }
+extern "C" int lnb_form_name(int index, const char** name) {
+    if (!name) return fail("null argument");
+    if (index < 0 || index >= (int)Form::COUNT) return fail("form index %d: the table has %d rows", index, (int)Form::COUNT);
+    *name = LNB_FORM_TABLE[index].name;
+    return 0;
+}
 // What the host should know before it trusts a multi-context run: the hardware queues the HIP runtime was told to use, who told it,
 // whether that was in time, and -- probe_queues != 0 -- how many streams REALLY run concurrently: 32 one-wave kernels that each hold their stream for
 // 2 ms of wall clock, one per stream; with Q queues they finish in ceil(32 / Q) rounds (4-20 ms including the stream set-up).
@@ -924,6 +941,7 @@ extern "C" int lnb_ctx_fork(lnb_ctx* src, int n_pos, lnb_ctx* const* dsts, int n
     HIPCHK(hipStreamSynchronize(src->stream));
     for (int d = 0; d < n_dst; d++) HIPCHK(hipStreamSynchronize(dsts[d]->stream));
     if (engine) {
+        form_ran(Form::KV_FORK_COPY);
         const size_t runs = kvc_runs(0, m->kv_dim), width = kvc_byte_offset(kvc_run_len(0, m->kv_dim, n_pos)), v_bytes = kvc_byte_offset(kvc_run_len(1, m->kv_dim, n_pos));
         for (size_t l = 0; l < src->ck.size(); l++) {
             if (!src->ck[l]) continue;
@@ -3189,11 +3207,13 @@ static int enqueue_stage_step(lnb_pipe* p, lnb_ctx* c, const int32_t* tokens, in
             })) return -1;
         if (c->dev_pos != pos) HIPCHK(ctx_set_state(c, pos, 0, true));
         c->call_T = 0;
+        form_ran(Form::PIPELINE_REPLAY);
         HIPCHK(hipGraphLaunch(*slot, st));
         c->dev_pos = pos + 1;                                // (the graph ends with advance_state)
         return 0;
     }
     HIPCHK(ctx_set_state(c, pos, 0, true));
+    if (rows == 1 && !tokens) form_ran(Form::PIPELINE_EAGER);
     return body(tokens != nullptr);
 }
 // What crosses the boundary behind this stage (towards rank+1) / in front of it: the [rows, dim] hidden state, plus the [rows, ffn_hidden]
@@ -3344,8 +3364,9 @@ extern "C" int lnb_pipeline_tick_batch(lnb_pipe* p, lnb_batch* run, lnb_batch* s
         if (p->use_graph) {
             hipGraphExec_t* const gslot = run->attn_long ? &run->stage_graph_long : &run->stage_graph;
             if (capture_once(gslot, st, [&] { return enqueue_batch_step(run, ring_in); })) return -1;
+            form_ran(Form::PIPELINE_REPLAY);
             HIPCHK(hipGraphLaunch(*gslot, st));
-        } else if (enqueue_batch_step(run, ring_in)) return -1;
+        } else { form_ran(Form::PIPELINE_EAGER); if (enqueue_batch_step(run, ring_in)) return -1; }
         run->last_form = run->attn_long ? 1 : 0;
         if (last) {
             if (p->tok_n > 0x7FFFFFFF - LNB_BATCH_MAX) return fail("pipeline token log: slot counter exhausted (2^31 tokens): create a new pipe");

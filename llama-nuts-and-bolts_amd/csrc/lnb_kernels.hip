@@ -4551,6 +4551,7 @@ __global__ void wpack_pack_kernel(const uint16_t* w, char* out, int K, int rw, i
 
 #include "lnb_batch_kernels.h"
 #include "lnb_knobs.h"
+#include "lnb_forms.h"
 
 // ------------------------------------------------------------------------------------------------
 // host-side launchers (called from lnb_api.cpp)
@@ -4585,6 +4586,7 @@ static hipError_t launch_chain_x(const GemvParams* p, hipStream_t st) {
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (xs_bytes(p->K, SA / (NCH * RW * 2)) / 4 > (size_t)XC * (1 + NH) * 512) return hipErrorInvalidValue;   // x staging registers
     if (NORM && (rms_scratch_bytes(rms_nf(NH)) > 4 * (size_t)SA || seq_leaf_size(p->K, rms_nf(NH) * 64) > 256)) return hipErrorInvalidValue;   // records live in the idle ring; leaf over-read stays inside the x padding
+    form_ran(PK ? Form::GEMV_CHAIN_PK : RW == 16 ? Form::GEMV_CHAIN_16 : RW == 28 ? Form::GEMV_CHAIN_28 : RW == 32 ? Form::GEMV_CHAIN_32 : RW == 56 ? (R == 6 ? Form::GEMV_CHAIN_56_TP : Form::GEMV_CHAIN_56) : Form::GEMV_CHAIN_64, EPI);
     hipLaunchKernelGGL(kfn, dim3((unsigned)(p->S * p->n_wg)), dim3((1 + NH) * 64), lds, st, *p);
     return hipGetLastError();
 }
@@ -4616,6 +4618,7 @@ static hipError_t launch_quad_x(const GemvParams* p, hipStream_t st) {
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (xs_bytes(p->K, KS) / 4 > (size_t)XC * NW * 512) return hipErrorInvalidValue;     // x staging registers
     if (NORM && (rms_scratch_bytes(rms_nf(NH)) > GQ_SLOTS * SB || seq_leaf_size(p->K, rms_nf(NH) * 64) > 256)) return hipErrorInvalidValue;
+    form_ran(Form::GEMV_QUAD, EPI);
     hipLaunchKernelGGL(kfn, dim3((unsigned)(p->S * p->n_wg)), dim3(NW * 64), lds, st, *p);
     return hipGetLastError();
 }
@@ -4713,9 +4716,11 @@ template <int EPI> static hipError_t launch_rowcast(const GemvParams* p, hipStre
     // (throughput schedule: the self-feeding kernel -- four waves and K * 4 bytes of LDS instead of eight waves and 96 KB + K * 2: co-resident with
     // another context's gate|up workgroup, NOTES R5)
     if (knob(Knob::ROWCAST_LDS) && !p->sched && p->K % (128 * RL_SC) == 0 && p->K >= 2 * 128 * RL_SC && rl_lds_bytes(p->K) + (size_t)(p->lds_pad > 0 ? p->lds_pad : 0) <= 160 * 1024) {
+        form_ran(Form::ROWCAST_LDS, EPI);
         hipLaunchKernelGGL(kl, dim3((unsigned)(p->S * p->n_wg)), dim3(512), rl_lds_bytes(p->K) + (size_t)(p->lds_pad > 0 ? p->lds_pad : 0), st, *p);
         return hipGetLastError();
     }
+    form_ran(Form::ROWCAST, EPI);
     hipLaunchKernelGGL(kfn, dim3((unsigned)(p->S * p->n_wg)), dim3(256), (size_t)p->K * 4 + (size_t)(p->lds_pad > 0 ? p->lds_pad : 0), st, *p);
     return hipGetLastError();
 }
@@ -4751,6 +4756,7 @@ template <int EPI, int NCH> static hipError_t launch_gemm(const GemmParams* p, h
     // (S = 2048: 3.90 ms against 4.11 ms with 64 x 64 tiles; the one-chain kernels gain 5 % from the smaller tile there;
     // S = 512, 896 tiles: the small tile still wins, 74 against 77 ms per Forward)
     const int tile = force ? force : (nb4 * mb <= 160 ? 1 : (NCH == 2 && nb4 * mb > 1024) ? 128 : nb4 * mb <= GM_MB64_UPTO ? 64 : 128);
+    form_ran(tile == 1 ? Form::GEMM_MFMA_T16 : tile == 64 ? Form::GEMM_MFMA_T64 : Form::GEMM_MFMA_T128, EPI);
     if (tile == 1)             // 64 x 128 tiles would leave most CUs idle: 16-row tiles, the four waves split the batch rows
                                // (tools/gemmbench.hip: 64 / 96 / 128 tiles: 1.4-2x faster; 256 tiles and up: 64-row tiles win)
         hipLaunchKernelGGL(t1.k, dim3((unsigned)((p->n_rows + 15) / 16), mb), dim3(256), t1.lds, st, *p);
@@ -4773,10 +4779,12 @@ extern "C" hipError_t lnbk_gemm(const GemmParams* p, int epi, hipStream_t st) {
 extern "C" hipError_t lnbk_rmsnorm_rows(const uint16_t* x, const uint16_t* w, uint16_t* out, int S, int K, float eps, hipStream_t st) {
     const size_t lds_w = bn_scratch() + ((size_t)bn_kpad(K) + 8) * 4;                  // one workgroup of seven waves per row: the exact parallel evaluation of the serial sum
     if (knob(Knob::NORM_ROWS_WIDE) && !(K & 127) && lds_w <= 64 * 1024 && (size_t)bn_kpad(K) <= (size_t)XCh<true>::value * (1 + BN_NH) * 512 && seq_leaf_size(K, rms_nf(BN_NH) * 64) <= 256) {
+        form_ran(Form::RMSNORM_ROWS_WIDE);
         hipLaunchKernelGGL(batch_rmsnorm_xt_kernel<false>, dim3((unsigned)S), dim3((1 + BN_NH) * 64), lds_w, st, x, w, eps, out, K);
         return hipGetLastError();
     }
     if (((size_t)K + 64) * 4 > 150 * 1024) return hipErrorInvalidValue;
+    form_ran(Form::RMSNORM_ROWS_WAVE);
     hipLaunchKernelGGL(rmsnorm_rows_kernel, dim3((unsigned)S), dim3(64), ((size_t)K + 64) * 4, st, x, w, out, S, K, eps);
     return hipGetLastError();
 }
@@ -4895,6 +4903,7 @@ static hipError_t launch_attn_short(const AttnParams* p, hipStream_t st) {
                 AttnParams q = *p;
                 if (knob(Knob::ATTN_GQA_FORCE_ZSEQ)) q.force_zseq = 1;      // (tests: every head walks the serial denominator)
                 if (knob(Knob::ATTN_GQA_DBG)) q.dbg = g_gqa_dbg;            // phase stamps of one workgroup (allocated by lnbk_init: no allocation inside a stream capture)
+                form_ran(Form::ATTN_BATCH_GQA);
                 hipLaunchKernelGGL(gqa, dim3(p->KVH, p->S), dim3(512), gl, st, q);
                 return hipGetLastError();
             }
@@ -4902,6 +4911,7 @@ static hipError_t launch_attn_short(const AttnParams* p, hipStream_t st) {
         if (p->btab && p->hd == 128 && (long)p->H * p->S > 256 && knob(Knob::ATTN_BATCH_DENSE)) {       // more workgroups than CUs (never an append: that has no btab)
             AttnParams q = *p;
             q.head_major = knob(Knob::ATTN_BATCH_HEADMAJOR) != 0;   // (A/B of the dispatch order)
+            form_ran(q.head_major ? Form::ATTN_BATCH_DENSE_HM : Form::ATTN_BATCH_DENSE);
             hipLaunchKernelGGL(dense, dim3(p->H, p->S), dim3(ATT_NT), lds, st, q);
             return hipGetLastError();
         }
@@ -4911,6 +4921,7 @@ static hipError_t launch_attn_short(const AttnParams* p, hipStream_t st) {
         if (!p) return raise_lds(plain, append);
         // lnb_forward_append, 2..15 rows (any row count at head_dim 32): workgroup (h, i) runs the one-token step at pos + i
         const auto k = p->causal && !p->btab && p->S > 1 ? append : plain;
+        if (p->btab) form_ran(Form::ATTN_BATCH_PLAIN);
         hipLaunchKernelGGL(k, dim3(p->H, p->S), dim3(ATT_NT), lds, st, *p);
         return hipGetLastError();
     });
@@ -5023,6 +5034,7 @@ extern "C" hipError_t lnbk_stream(const StreamParams* p, int epi, int acc2, int 
     if (const auto pair = pair_kernel(epi); pair && !acc2 && (G > 1 || knob(Knob::STREAM_PAIR))) {
         const size_t lds = (size_t)2 * 2 * MP_BUF;
         unsigned gp = (unsigned)((q.n_jobs * G + 1) / 2); if (gp > (unsigned)num_cus) gp = (unsigned)num_cus;
+        form_ran(Form::MFMA_PAIR, epi);
         hipLaunchKernelGGL(pair, dim3(gp), dim3(256), lds, st, q);
         return hipGetLastError();
     }
@@ -5031,6 +5043,7 @@ extern "C" hipError_t lnbk_stream(const StreamParams* p, int epi, int acc2, int 
                                     : (epi == EPI_SILU_MUL && acc2 && p->nch == 2) ? mfma_stream_kernel<2, EPI_SILU_MUL> : nullptr;
 #undef LNB_STREAM
     if (!k) return hipErrorInvalidValue;
+    form_ran(acc2 ? Form::MFMA_STREAM_C2 : Form::MFMA_STREAM_C1, epi);
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, q);
     return hipGetLastError();
 }
@@ -5058,6 +5071,7 @@ extern "C" hipError_t lnbk_batch_prepare(void) {             // raise the dynami
 extern "C" hipError_t lnbk_batch_rmsnorm(const uint16_t* x, const uint16_t* norm_w, float eps, uint16_t* xt, int K, int nseq, hipStream_t st) {
     const size_t lds = bn_scratch() + ((size_t)bn_kpad(K) + 8) * 4;
     if ((K & 127) || lds > 160 * 1024 || (size_t)bn_kpad(K) > (size_t)XCh<true>::value * (1 + BN_NH) * 512 || seq_leaf_size(K, rms_nf(BN_NH) * 64) > 256) return hipErrorInvalidValue;
+    form_ran(Form::BATCH_RMSNORM);
     hipLaunchKernelGGL(batch_rmsnorm_xt_kernel<true>, dim3((unsigned)nseq), dim3((1 + BN_NH) * 64), lds, st, x, norm_w, eps, xt, K);
     return hipGetLastError();
 }
@@ -5132,6 +5146,7 @@ template <int EPI, int NCH> static hipError_t launch_gemm_stream(const GemmParam
         const int tpg = 4 / NCH, n_tg = (n_tiles + tpg - 1) / tpg;
         const dim3 g((unsigned)((n_tg + 3) / 4), (unsigned)ct);
         const size_t l = (size_t)2 * 16 * GS_PITCH * 4;             // (16 KiB + padding: within what every kernel gets)
+        form_ran(Form::GEMM_BLGP, EPI);
         hipLaunchKernelGGL((gemm_blgp_kernel<EPI, NCH>), g, dim3(256), l, st, q);
         return hipGetLastError();
     }
@@ -5156,6 +5171,9 @@ template <int EPI, int NCH> static hipError_t launch_gemm_stream(const GemmParam
     const size_t lds = (size_t)2 * rows_wg * GS_PITCH * 4;
     const auto k = gs_kernel<EPI, NCH>(ntw, src, tt);
     if (!k) return hipErrorInvalidValue;
+    // (the table's rows run source-major: copy 1 / 2 / 4 / 4.tt, row-broadcast the same four, chain 1 / 2 / 4)
+    form_ran((Form)((int)Form::GS_COPY_1 + 4 * src + (ntw == 1 ? 0 : ntw == 2 ? 1 : tt ? 3 : 2)), EPI);
+    form_ran(q.rows_fastest ? Form::GS_ORDER_ROWS : Form::GS_ORDER_TILES, EPI);
     hipLaunchKernelGGL(k, grid, dim3(256), lds, st, q);
     return hipGetLastError();
 }
@@ -5196,6 +5214,8 @@ extern "C" hipError_t lnbk_kv_fork(const KvForkTab* tab, int nt, int split, hipS
     if (gx > tmax) gx = tmax;
     const int gz = split > 1 ? (split < tab->n_dst ? split : tab->n_dst) : 1;
     const dim3 grid((unsigned)gx, (unsigned)tab->n_arrays, (unsigned)gz);
+    form_ran(nt ? Form::KV_FORK_NT : Form::KV_FORK_PLAIN);
+    if (gz > 1) form_ran(Form::KV_FORK_SPLIT);
     if (nt) hipLaunchKernelGGL(kv_fork_kernel<true>, grid, dim3(KVC_THREADS), 0, st, *tab);
     else hipLaunchKernelGGL(kv_fork_kernel<false>, grid, dim3(KVC_THREADS), 0, st, *tab);
     return hipGetLastError();

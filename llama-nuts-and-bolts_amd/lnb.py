@@ -73,7 +73,9 @@ EXPORTS = [
     "lnb_ctx_fork", "lnb_ctx_prefix_bytes", "lnb_ctx_save_prefix", "lnb_ctx_load_prefix",
     "lnb_forward_append_many", "lnb_model_append_many_info",
     "lnb_decode_speculative_many",
+    "lnb_form_count", "lnb_form_count_reset", "lnb_form_name",
 ]
+EPILOGUES = {"store": 0, "qkv_rope": 1, "resid": 2, "silu_mul": 3}      # EPI_* of csrc/lnb_device.h: the second index of the launch tally
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
 MAX_DRAFT = 15           # LNB_MAX_DRAFT of include/lnb.h (tests/test_speculative_cpu.py compares them)
 MAX_SEQ_LEN = 131072     # LNB_MAX_SEQ_LEN of include/lnb.h (tests/test_long_context_cpu.py compares them)
@@ -249,6 +251,9 @@ def lib():
     L.lnb_tokenizer_stream_free.restype = None
     L.lnb_tokenizer_decode_stream.argtypes = [vp, C.c_int32, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     L.lnb_tokenizer_stream_pending.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+    L.lnb_form_count.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int64)]
+    L.lnb_form_count_reset.argtypes = []
+    L.lnb_form_name.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     _lib = L
     return L
 
@@ -260,6 +265,25 @@ def _chk(rc):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def form_names():
+    """the names of the launch tally's rows (csrc/lnb_forms.h), in table order"""
+    L, out, name = lib(), [], C.c_char_p()
+    while L.lnb_form_name(len(out), C.byref(name)) == 0:
+        out.append(name.value.decode())
+    return out
+
+
+def form_count(form, epi=None):
+    """launches of the kernel form `form` since the last form_count_reset(); epi: one of EPILOGUES (a name or its number), None = the sum"""
+    n = C.c_int64(0)
+    _chk(lib().lnb_form_count(form.encode(), -1 if epi is None else EPILOGUES.get(epi, epi), C.byref(n)))
+    return n.value
+
+
+def form_count_reset():
+    _chk(lib().lnb_form_count_reset())
 
 
 def device_count():

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from form_tally import ran
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -30,14 +31,45 @@ CFGS = {
 }
 
 
+# what a step of a given width launches (lnb_batchplan.h): up to 16 members every product a column product -- the thin ones on mfma_pair_kernel, gate|up on
+# mfma_stream_kernel<2> --, 17..32 the thin ones as two column groups and gate|up and the head as rows of gemm_stream_kernel, more: rows only
+BATCH_FORMS = {
+    "column": {"mfma_pair": ("qkv_rope", "resid", "store"), "mfma_stream.c2": "silu_mul", "batch_rmsnorm": None},
+    "column_nopair": {"mfma_stream.c1": ("qkv_rope", "resid", "store"), "mfma_stream.c2": "silu_mul", "batch_rmsnorm": None},
+    "groups": {"mfma_pair": ("qkv_rope", "resid"), "gemm_stream.copy": ("silu_mul", "store"), "batch_rmsnorm": None, "rmsnorm_rows.wide": None},
+    "rows": {"gemm_stream.copy": ("qkv_rope", "resid", "silu_mul", "store"), "rmsnorm_rows.wide": None},
+}
+BATCH_NOT = {"column": ("mfma_stream.c1", "gemm_stream"), "column_nopair": ("mfma_pair", "gemm_stream"), "groups": ("mfma_stream",),
+             "rows": ("mfma_pair", "mfma_stream", "batch_rmsnorm")}
+# the short-context attention of the step (launch_attn_short): head_dim 64 keeps the one-token kernel; head_dim 128 with more than 256 (head, sequence) pairs
+# -- h8kv2_hd128 at 40 members -- takes the dense dispatch (four query heads per KV head, but 2 x 40 workgroups are too few for attn_gqa_kernel)
+ATTN_FORMS = {False: "attn_batch.plain", True: "attn_batch.dense"}
+
+
+def batch_plan_kind(n, pair=True):
+    return ("column" if pair else "column_nopair") if n <= 16 else "groups" if n <= 32 else "rows"
+
+
 @pytest.mark.parametrize("name", sorted(CFGS))
 def test_every_sequence_of_a_batch_equals_its_own_oracle_run(lnb, name):
+    every_sequence_equals_its_own_oracle_run(lnb, name, (1, 2, 5, 16, 17, 40))     # up to 16: columns of one matrix instruction; more: rows of the streaming product
+
+
+@pytest.mark.parametrize("name", sorted(CFGS))
+def test_every_sequence_of_a_batch_on_the_one_wave_stream_kernel(lnb, monkeypatch, name):
+    """LNB_STREAM_PAIR=0 (LIVE): the thin products of a batch of up to 16 on mfma_stream_kernel<1, STORE | RESID | QKV_ROPE> -- reachable only this way -- instead
+    of mfma_pair_kernel; a partial and a full column group"""
+    monkeypatch.setenv("LNB_STREAM_PAIR", "0")
+    every_sequence_equals_its_own_oracle_run(lnb, name, (5, 16), pair=False)
+
+
+def every_sequence_equals_its_own_oracle_run(lnb, name, widths, pair=True):
     cfg = CFGS[name]
     om = orc.Model(**cfg).fill_synthetic(606).finalize()
     gm = lnb.LlamaTransformer(**cfg).fill_synthetic(606).finalize().enable_batch()
     assert gm.batch_bytes() > 0
     steps = 11
-    for n in (1, 2, 5, 16, 17, 40):                                                # up to 16: columns of one matrix instruction; more: rows of the streaming product
+    for n in widths:
         plens = [4 + 3 * s + (17 if s % 4 == 1 else 0) for s in range(n)]           # different prompt lengths: different positions per column
         prompts = [orc.synth_tokens(100 * n + s, plens[s], cfg["vocab_size"]) for s in range(n)]
         refs, ocs = [], []
@@ -52,7 +84,10 @@ def test_every_sequence_of_a_batch_equals_its_own_oracle_run(lnb, name):
             firsts.append(t)
         assert firsts == [r[0] for r in refs]
         b = lnb.Batch(ctxs)
-        got, ms = b.decode(firsts, plens, steps)
+        kind = batch_plan_kind(n, pair)
+        dense = cfg["dim"] // cfg["n_heads"] == 128 and cfg["n_heads"] * n > 256
+        with ran(lnb, dict(BATCH_FORMS[kind], **{ATTN_FORMS[dense]: None}), not_ran=BATCH_NOT[kind] + ("gemm_mfma", ATTN_FORMS[not dense], "attn_batch.gqa")):
+            got, ms = b.decode(firsts, plens, steps)
         assert ms > 0
         for s in range(n):
             assert [int(t) for t in got[s]] == refs[s][1:1 + steps], (name, n, s)
@@ -330,7 +365,10 @@ def test_dense_batch_attention_beyond_one_pass_of_512_positions(lnb, monkeypatch
     """attn_exact_kernel<HD, DENSE> (chosen for a batch when heads x sequences > 256) reloads its K rows per 512-position pass; the
     other batch tests stop at ~150 positions.  Here: 70 sequences x 4 heads on the tiny shape with prompts of 480..1100 positions -- some
     cross 512 and 1024 INSIDE the decode window -- against each sequence's own single-sequence run (lnb_decode_greedy: the oracle-checked
-    path), against the oracle itself for three of them, and against the non-DENSE form (LNB_ATTN_BATCH_DENSE=0)."""
+    path), against the oracle itself for three of them, and against the non-DENSE form (LNB_ATTN_BATCH_DENSE=0).
+    What runs here today: the DENSE kernel exists for head_dim 128 only and this shape has 64, and a batch with a member beyond 512 positions decodes with the batched
+    long-context kernels -- so this is a test of those against single-sequence runs.  The dense dispatch itself, tile-major and head-major, is
+    tests/test_gpu_forms.py::test_dense_batch_attention_tile_major_head_major_and_off, where the launch tally shows it."""
     cfg = dict(orc.TINY)
     n, steps = 70, 10
     plens = [480 + (s * 97) % 620 for s in range(n)]
@@ -397,7 +435,8 @@ def test_gqa_aware_batch_attention_equals_the_oracle_per_sequence(lnb, monkeypat
         ctxs = [lnb.InferenceContext(gm, seqmax) for _ in range(n)]
         firsts = [ctxs[s].Forward(prompts[s], 0, want_logits=False)[1] for s in range(n)]
         b = lnb.Batch(ctxs)
-        got, _ = b.decode(firsts, plens, steps)
+        with ran(lnb, "attn_batch.gqa", not_ran=("attn_batch.dense", "attn_batch.plain")):
+            got, _ = b.decode(firsts, plens, steps)
         for s in range(n):
             oc = orc.Context(om, seqmax)
             r, _ = oc.generate(prompts[s], steps + 1)

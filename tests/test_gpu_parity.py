@@ -12,6 +12,8 @@ import os
 import numpy as np
 import pytest
 
+from form_tally import ran
+from linear_cases import check_linear_special_values, check_rmsnorm_adversarial
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -77,13 +79,15 @@ def test_linear_bit_exact(lnb, rows, n, k, rw):
     (64, 300, 8, 64), (200, 96, 14336, 4),
 ])
 def test_prefill_gemm_on_the_matrix_cores_is_bit_exact(lnb, rows, n, k, rw):
-    """16 or more rows go through gemm_mfma_kernel: v_mfma_f32_16x16x4_f32 is the same k-ordered f32 chain (tools/mfma_exact.hip),
-    so the outputs must still be bit-identical to the oracle -- for every weight layout, ragged M / N, K not a multiple of the
-    128-step slab."""
+    """16 or more rows go through the f32 matrix cores: v_mfma_f32_16x16x4_f32 is the same k-ordered f32 chain (tools/mfma_exact.hip),
+    so the outputs must still be bit-identical to the oracle -- for every weight layout, ragged M / N.  Which kernel: since the streaming feed
+    reads the resident layouts, gemm_stream_kernel wherever K is a multiple of 128 and gemm_mfma_kernel (16-row tile) only at K = 8 -- the launch
+    tally says so; gemm_mfma_kernel's other tiles and epilogues are tests/test_gpu_forms.py's."""
     rng = np.random.default_rng(rows * 7 + n + k + rw)
     x = bf(rng.standard_normal((rows, k)) * 10 ** rng.uniform(-2, 2))
     w = bf(rng.standard_normal((n, k)) * 0.05)
-    y = lnb.op_linear(x, w, rw=rw)
+    with ran(lnb, "gemm_stream" if k % 128 == 0 else "gemm_mfma.t16", epi="store", not_ran=("gemm_mfma" if k % 128 == 0 else "gemm_stream",)):
+        y = lnb.op_linear(x, w, rw=rw)
     assert (y == orc_linear(x, w)).all()
 
 
@@ -108,51 +112,9 @@ def _same_bits_or_both_nan(a, b):
 
 @pytest.mark.parametrize("rows,rw", [(1, 16), (1, 64), (1, 4), (3, 32), (20, 16), (20, 4), (130, 64), (1, 24), (2, 24)])
 def test_linear_special_values(lnb, rows, rw):
-    """Values outside the comfortable range, through every exact kernel family (chain GEMV, row-broadcast GEMV, f32 matrix-core GEMM):
-    signed zeros (the chain starts at +0, so a sum of -0 products is +0), +-inf and NaN in weights and activations (inf - inf, 0 * inf),
-    products that overflow f32, products and partial sums in the f32-subnormal range (bf16 shares f32's exponent range: two tiny
-    operands give a subnormal, inexactly rounded product -- operations_lineartransform.go:60 multiplies in float32), and sums that
-    cancel to exactly zero.  Bits must match the oracle; for NaN results only the NaN-ness.
-    The GEMVs multiply, then add, like the reference, and match everywhere.  The f32 matrix-core instruction of the prefill GEMM
-    (16 or more rows) FUSES the multiply: same bits whenever every single product is a normal f32 (NOTES.md section 2) -- its rows
-    here keep sums that overflow and subnormal partial sums, but no single product outside [2^-126, 2^128)."""
-    k, n = 512, 96
-    rng = np.random.default_rng(rows * 131 + rw)
-    x = bf(rng.standard_normal((rows, k)))
-    w = bf(rng.standard_normal((n, k)) * 0.05)
-    xf, wf = orc.bf16_to_f32(x).copy(), orc.bf16_to_f32(w).copy()
-    wf[0, :] = -0.0                                              # all products -0 (or +0): result +0
-    wf[1, :] = 0.0; wf[1, 7] = np.inf                            # one inf product
-    wf[2, 3] = np.inf; wf[2, 200] = -np.inf                      # inf - inf -> NaN
-    wf[3, 11] = np.nan
-    gemm = rows >= 16
-    wf[4, :] = 3.0e38                                            # single products overflow (GEMV rows) ...
-    if gemm:
-        wf[4, :] = 0.0; wf[4, :64] = 1.0e37                      # ... or only the running SUM does (x[:, :64] = 2 below: 64 x 2e37)
-    wf[5, :] = 1e-30 * rng.standard_normal(k)                    # products ~1e-30 x 1: tiny but normal
-    wf[6, :] = 1e-38 * rng.standard_normal(k)                    # bf16 values at the edge of / inside the subnormal range
-    wf[7, :] = np.float32(2.0 ** -100) * rng.integers(1, 128, k)      # with the tiny activations below: subnormal products
-    wf[8, 0::2] = 1.0; wf[8, 1::2] = -1.0                        # exact cancellation on duplicated activations
-    wf[9, :] = 0.0; wf[9, 100] = np.inf                          # inf * 0 -> NaN (activation 100 is zeroed below)
-    wf[10, :] = -wf[5, :]
-    xf[:, 100] = 0.0
-    xf[:, 1::2] = xf[:, 0::2]
-    if gemm:
-        xf[:, :64] = 2.0
-    if rows > 1:
-        # tiny activations: with weight row 7 (2^-100 x small integers) the products are 2^-140 x integers -- exact subnormals in both
-        # arithmetics, partial sums subnormal; with weight row 6 (1e-38) single products underflow inexactly: GEMV rows only
-        xf[1, :] = np.float32(2.0 ** -40) * rng.integers(-127, 128, k)
-        if gemm:
-            wf[6, :] = 1e-20 * rng.standard_normal(k)
-    if rows > 2:
-        xf[2, 17] = np.nan; xf[2, 18] = -np.inf
-    x, w = bf(xf), bf(wf)
-    y = lnb.op_linear(x, w, rw=rw)
-    ref = orc_linear(x, w)
-    bad = np.argwhere(~((y == ref) | (np.isnan(orc.bf16_to_f32(y)) & np.isnan(orc.bf16_to_f32(ref)))))
-    assert bad.size == 0, "first differences (row, col): %s  got %s  oracle %s" % (bad[:6].tolist(), [hex(int(y[i, j])) for i, j in bad[:6]], [hex(int(ref[i, j])) for i, j in bad[:6]])
-    assert y[0, 0] == 0x0000                                     # +0, not -0
+    """The special-values product of tests/linear_cases.py (signed zeros, inf, NaN, overflowing sums, subnormal products, exact cancellation) through every
+    exact kernel family: chain GEMV, row-broadcast GEMV, and from 16 rows on the prefill product the launch layer picks by default."""
+    check_linear_special_values(lnb, rows, rw)
 
 
 def test_linear_lm_head_shape(lnb):
@@ -188,31 +150,18 @@ def test_rmsnorm_linear_bit_exact(lnb, rows, n, k, rw):
 
 @pytest.mark.parametrize("k,rw", [(4096, 16), (4096, 64), (8192, 32), (512, 16), (3072, 64), (64, 16), (4096, 24), (512, 24)])
 def test_rmsnorm_exact_parallel_sum_adversarial(lnb, k, rw):
-    """The RMSNorm sum of squares is evaluated by the exact parity-map tree (rms_scale_wide); inputs chosen to stress it:
-    huge dynamic range, ties everywhere (powers of two), sparse rows, subnormal squares, outliers, leading zeros."""
-    rng = np.random.default_rng(k + rw)
-    rows = []
-    for kind in range(12):
-        if kind == 0: x = rng.standard_normal(k)
-        elif kind == 1: x = rng.standard_normal(k) * 1e-15
-        elif kind == 2: x = 2.0 ** rng.integers(-12, 4, k)
-        elif kind == 3: x = rng.standard_normal(k) * (rng.random(k) < 0.05)
-        elif kind == 4: x = np.exp(rng.uniform(-40, 5, k))
-        elif kind == 5: x = np.full(k, 2.0 ** rng.integers(-8, 8))
-        elif kind == 6: x = np.abs(rng.standard_normal(k)) * np.where(rng.random(k) < 0.01, 1e4, 1.0)
-        elif kind == 7: x = np.where(np.arange(k) < k // 3, 0.0, rng.standard_normal(k))
-        elif kind == 8: x = np.zeros(k)
-        elif kind == 9: x = rng.standard_normal(k) * 1e12
-        elif kind == 10: x = np.where(np.arange(k) == k - 1, 3e4, 1e-3 * rng.standard_normal(k))
-        else: x = rng.standard_normal(k) * np.exp(rng.uniform(-20, 8, k))
-        rows.append(x)
-    x = bf(np.stack(rows))
-    nw = bf(1 + 0.1 * rng.standard_normal(k))
-    w = bf(rng.standard_normal((64, k)) * 0.05)
-    y = lnb.op_rmsnorm_linear(x, nw, 1e-5, w, rw=rw)
-    xn = np.zeros_like(x)
-    orc.lib().orc_rmsnorm_bf16(orc._p(x), orc._p(nw), orc._p(xn), x.shape[0], k, np.float32(1e-5), None)
-    assert (y == orc_linear(xn, w)).all()
+    """the twelve adversarial row families of tests/linear_cases.py, 12 rows: the RMSNorm fused into the GEMV's prologue"""
+    check_rmsnorm_adversarial(lnb, k, rw)
+
+
+@pytest.mark.parametrize("k,form", [(4096, "rmsnorm_rows.wide"), (512, "rmsnorm_rows.wide"), (1000, "rmsnorm_rows.wave"), (200, "rmsnorm_rows.wave")])
+def test_rmsnorm_exact_parallel_sum_adversarial_on_the_prefill_norm_kernels(lnb, k, form):
+    """the same families twice over = 24 rows, so the row norm kernels of the prefill: batch_rmsnorm_xt_kernel<false> (seven waves per row) where K is a multiple
+    of 128, the one-wave rmsnorm_rows_kernel where it is not -- and the product behind them on the feed that K allows"""
+    wide = form == "rmsnorm_rows.wide"
+    with ran(lnb, {form: None, ("gemm_stream.chain" if wide else "gemm_mfma.t16"): "store"},
+             not_ran=("rmsnorm_rows.wave" if wide else "rmsnorm_rows.wide", "gemm_mfma" if wide else "gemm_stream", "gemv_chain")):
+        check_rmsnorm_adversarial(lnb, k, 16, reps=2)
 
 
 @pytest.mark.parametrize("k,rw", [(4096, 24), (4096, 16), (2048, 32)])
@@ -235,12 +184,14 @@ def test_rmsnorm_item_list_walk_many_rows(lnb, k, rw):
         assert (y == orc_linear(xn, w)).all(), chunk
 
 
-@pytest.mark.parametrize("k,rw,reps", [(4096, 32, 1), (512, 16, 1), (4096, 64, 1), (4096, 32, 2), (4096, 24, 1), (1024, 24, 2)])
+@pytest.mark.parametrize("k,rw,reps", [(4096, 32, 1), (512, 16, 1), (4096, 64, 1), (4096, 32, 2), (4096, 24, 1), (1024, 24, 2),
+                                       (1000, 32, 2), (200, 16, 2)])          # K no multiple of 128, 20 rows: the one-wave rmsnorm_rows_kernel
 def test_rmsnorm_rows_with_non_finite_and_overflowing_squares(lnb, k, rw, reps):
     """Rows the parity-map evaluation of the norm sum was not designed around: inf / NaN activations, squares that overflow f32
     (|x| > 1.8e19), a running sum that overflows after a few terms, squares that underflow to zero.  The reference just keeps adding
     (sum = inf -> mean = inf -> 1/sqrt = 0 -> x * 0, or NaN): the device must land on the same bits (NaN-ness for NaNs).
-    reps = 2: 20 rows, i.e. the prefill form (rmsnorm_rows_kernel + matrix-core GEMM)."""
+    reps = 2: 20 rows, i.e. the prefill form: batch_rmsnorm_xt_kernel<false> + gemm_stream_kernel where K is a multiple of 128, rmsnorm_rows_kernel +
+    gemm_mfma_kernel where it is not (the launch tally says which)."""
     rng = np.random.default_rng(k + rw + reps)
     base = rng.standard_normal(k).astype(np.float32)
     rows = []
@@ -260,7 +211,14 @@ def test_rmsnorm_rows_with_non_finite_and_overflowing_squares(lnb, k, rw, reps):
     x = bf(np.stack(rows * reps))
     nw = bf(1 + 0.1 * rng.standard_normal(k))
     w = bf(rng.standard_normal((48, k)) * 0.05)
-    y = lnb.op_rmsnorm_linear(x, nw, 1e-5, w, rw=rw)
+    if x.shape[0] < 16:                                       # the norm fused into the GEMV: no row norm kernel, no matrix-core product
+        want, never = {("gemv_quad" if rw == 24 else "gemv_chain"): "store"}, ("rmsnorm_rows", "gemm_mfma", "gemm_stream")
+    elif k % 128 == 0:
+        want, never = {"rmsnorm_rows.wide": None, "gemm_stream.chain": "store"}, ("rmsnorm_rows.wave", "gemm_mfma")
+    else:
+        want, never = {"rmsnorm_rows.wave": None, "gemm_mfma.t16": "store"}, ("rmsnorm_rows.wide", "gemm_stream")
+    with ran(lnb, want, not_ran=never):
+        y = lnb.op_rmsnorm_linear(x, nw, 1e-5, w, rw=rw)
     xn = np.zeros_like(x)
     orc.lib().orc_rmsnorm_bf16(orc._p(x), orc._p(nw), orc._p(xn), x.shape[0], k, np.float32(1e-5), None)
     ref = orc_linear(xn, w)
@@ -554,15 +512,16 @@ def test_tiny_device_greedy_loop_matches_oracle(lnb, tiny_pair):
 
 
 def test_tiny_long_prefill_through_the_matrix_cores_bit_exact(lnb, tiny_pair):
-    """A 48-token prompt (>= 16 rows: rmsnorm_rows + gemm_mfma with the RoPE/KV, residual and SiLU*up epilogues, the K cache in
-    its position-contiguous layout) and a chunked continuation of 48 more rows at start_pos 48: logits, KV caches and the
-    following greedy steps must equal the oracle's bit for bit."""
+    """A 48-token prompt (>= 16 rows: the wide row norm + gemm_stream_kernel with the RoPE/KV, residual and SiLU*up epilogues -- every K of this model
+    is a multiple of 128, so nothing here is gemm_mfma_kernel's: the launch tally says so --, the K cache in its position-contiguous layout) and a
+    chunked continuation of 48 more rows at start_pos 48: logits, KV caches and the following greedy steps must equal the oracle's bit for bit."""
     om, gm = tiny_pair
     oc, gc = orc.Context(om, 128), lnb.InferenceContext(gm, 128)
     toks = orc.synth_tokens(77, 96, TINY["vocab_size"])
     for lo_, hi_ in ((0, 48), (48, 96)):                      # second call: T = 96, S = 48 (T % S == 0, modulo-broadcast mask)
         lo, ao = oc.forward(toks[lo_:hi_], lo_)
-        lg, ag = gc.Forward(toks[lo_:hi_], lo_)
+        with ran(lnb, {"gemm_stream": ("qkv_rope", "resid", "silu_mul", "store"), "rmsnorm_rows.wide": None}, not_ran=("gemm_mfma", "rmsnorm_rows.wave")):
+            lg, ag = gc.Forward(toks[lo_:hi_], lo_)
         assert (lo.view(np.uint32) == lg.view(np.uint32)).all() and ao == ag
     for layer in range(TINY["n_layers"]):
         assert (oc.cache(layer, 0)[:96] == gc.CacheK(layer)[:96]).all() and (oc.cache(layer, 1)[:96] == gc.CacheV(layer)[:96]).all()
@@ -609,7 +568,8 @@ def test_rw24_quad_chain_blocks_bit_exact(lnb, tiny_pair, monkeypatch):
     oc, gc = orc.Context(om, 48), lnb.InferenceContext(gm, 48)
     toks = orc.synth_tokens(5, 7, TINY["vocab_size"])
     lo, ao = oc.forward(toks, 0)
-    lg, ag = gc.Forward(toks, 0)
+    with ran(lnb, "gemv_quad", epi="qkv_rope"):
+        lg, ag = gc.Forward(toks, 0)
     assert (lo.view(np.uint32) == lg.view(np.uint32)).all() and ao == ag
     tok = ag
     for i in range(8):
@@ -639,14 +599,17 @@ def test_rw56_two_chain_blocks_bit_exact(lnb, tiny_pair, monkeypatch):
     oc, gc = orc.Context(om, 48), lnb.InferenceContext(gm, 48)
     toks = orc.synth_tokens(5, 7, TINY["vocab_size"])
     lo, ao = oc.forward(toks, 0)
-    lg, ag = gc.Forward(toks, 0)
+    with ran(lnb, "gemv_chain.rw56", epi="silu_mul", not_ran=("gemv_chain_pk",)):      # seven rows: seven launch rows of the raw kernel
+        lg, ag = gc.Forward(toks, 0)
     assert (lo.view(np.uint32) == lg.view(np.uint32)).all() and ao == ag
     tok = ag
-    for i in range(8):
-        lo, to = oc.forward([tok], 7 + i)
-        lg, tg = gc.Forward(np.array([tok], dtype=np.int32), 7 + i)
-        assert (lo.view(np.uint32) == lg.view(np.uint32)).all() and to == tg
-        tok = to
+    packed = gm.wpack_info()["packed"] == TINY["n_layers"]    # one row: from the 13-bit copy the model built for this layout (where the weights allow one)
+    with ran(lnb, "gemv_chain_pk" if packed else "gemv_chain.rw56", epi="silu_mul", not_ran=("gemv_chain.rw56" if packed else "gemv_chain_pk",)):
+        for i in range(8):
+            lo, to = oc.forward([tok], 7 + i)
+            lg, tg = gc.Forward(np.array([tok], dtype=np.int32), 7 + i)
+            assert (lo.view(np.uint32) == lg.view(np.uint32)).all() and to == tg
+            tok = to
     gc.close(); oc.close(); gm.close()
 
 

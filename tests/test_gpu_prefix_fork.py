@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from form_tally import ran
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -110,14 +111,24 @@ def check_continuation(R, ctx, cap, tag):
         assert np.array_equal(k[:end], R["okv"][l][0][:end]) and np.array_equal(v[:end], R["okv"][l][1][:end]), (tag, l)
 
 
-@pytest.mark.parametrize("engine", [0, 1], ids=["kernel", "copy-engine"])
+# how lnb_ctx_fork copies: (LNB_FORK_COPY, LNB_FORK_NT, LNB_FORK_SPLIT) and the forms the launch tally must show (and, of the kv_fork forms, no other)
+FORK_KNOBS = {0: (0, 0, 0), 1: (1, 0, 0), "nt": (0, 1, 0), "split2": (0, 0, 2), "split4": (0, 1, 4)}        # (split4: four destinations, one group each)
+FORK_FORMS = {0: ("kv_fork.plain",), 1: ("kv_fork.copy",), "nt": ("kv_fork.nt",), "split2": ("kv_fork.plain", "kv_fork.split"), "split4": ("kv_fork.nt", "kv_fork.split")}
+
+
+@pytest.mark.parametrize("engine", [0, 1, "nt", "split2", "split4"], ids=["kernel", "copy-engine", "nt", "split2", "split4"])
 @pytest.mark.parametrize("hd", sorted(CFGS))
 def test_fork_bits_and_continuation(lnb, hd, engine, monkeypatch):
     R = reference(lnb, hd)
-    monkeypatch.setenv("LNB_FORK_COPY", str(engine))           # LIVE: read by every call
+    (copy, nt, split), forms = FORK_KNOBS[engine], FORK_FORMS[engine]
+    others = tuple(f for f in ("kv_fork.plain", "kv_fork.nt", "kv_fork.split", "kv_fork.copy") if f not in forms)
+    monkeypatch.setenv("LNB_FORK_COPY", str(copy))             # LIVE, all three: read by every call
+    monkeypatch.setenv("LNB_FORK_NT", str(nt))
+    monkeypatch.setenv("LNB_FORK_SPLIT", str(split))
     dsts = [stale_context(lnb, R, cap, k) for k, cap in enumerate(DST_CAPS)]
     before = [caches(d, R["nl"]) for d in dsts]
-    assert R["src"].ForkPrefix(dsts, NPOS) is R["src"]
+    with ran(lnb, FORK_FORMS[engine], not_ran=others):
+        assert R["src"].ForkPrefix(dsts, NPOS) is R["src"]
     for d, b, cap in zip(dsts, before, DST_CAPS):
         check_forked(R, d, b, (hd, engine, cap))
     assert same_caches(caches(R["src"], R["nl"]), R["skv"])    # the source over its whole capacity

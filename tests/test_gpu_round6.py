@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+from form_tally import count, ran
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -471,7 +472,8 @@ def test_blgp_matrix_core_feed_from_the_chain_layouts_is_bit_exact(lnb, monkeypa
     lo, ao = oc.forward(toks, 0)
     monkeypatch.setenv("LNB_GEMM_BLGP", "2")
     gc = lnb.InferenceContext(gm, rows + 8)
-    lg, ag = gc.Forward(toks, 0)
+    with ran(lnb, "gemm_blgp", epi=("qkv_rope", "silu_mul", "store"), not_ran=("gemm_stream.chain", "gemm_mfma")):
+        lg, ag = gc.Forward(toks, 0)
     assert (lo.view(np.uint32) == lg.view(np.uint32)).all() and ao == ag
     tok = ag
     for i in range(3):
@@ -480,6 +482,10 @@ def test_blgp_matrix_core_feed_from_the_chain_layouts_is_bit_exact(lnb, monkeypa
         assert (lo1.view(np.uint32) == lg1.view(np.uint32)).all() and to == tg
         tok = to
     gc.close(); oc.close(); gm.close(); om.close()
+
+
+TT_FORMS = {False: ("gemm_stream.rowcast.ntw4_tt",), True: ("gemm_stream.copy.ntw4_tt",)}       # wo and w2 with two weight tiles per wave, by source ...
+TT_OFF_FORMS = {False: ("gemm_stream.rowcast.ntw4",), True: ("gemm_stream.copy.ntw4",)}        # ... and with one
 
 
 @pytest.mark.parametrize("rows,copy", [(64, False), (100, False), (200, True), (130, True)])
@@ -499,7 +505,10 @@ def test_two_weight_tiles_per_wave_in_the_prefill_products_is_bit_exact(lnb, mon
     for tt in ("1", "0"):
         monkeypatch.setenv("LNB_GS_TT", tt)
         gc = lnb.InferenceContext(gm, rows + 8)
-        lg, ag = gc.Forward(toks, 0)
+        with ran(lnb, (TT_FORMS if tt == "1" else TT_OFF_FORMS)[copy], epi="resid"):
+            lg, ag = gc.Forward(toks, 0)
+        # wo and w2 (the residual epilogue) on the other form: never (from the copy, wq|wk|wv and gate|up keep one weight tile per wave either way)
+        assert count(lnb, (TT_OFF_FORMS if tt == "1" else TT_FORMS)[copy][0], "resid") == 0
         assert (lo.view(np.uint32) == lg.view(np.uint32)).all() and ao == ag, tt
         gc.close()
     oc.close(); gm.close(); om.close()
@@ -518,7 +527,8 @@ def test_down_projection_on_one_quad_chain_wave_is_bit_exact(lnb, monkeypatch, q
     toks = orc.synth_tokens(9, 9, cfg["vocab_size"])
     oc, gc = orc.Context(om, 40), lnb.InferenceContext(gm, 40)
     lo, ao = oc.forward(toks, 0)
-    lg, ag = gc.Forward(toks, 0)
+    with ran(lnb, "gemv_quad", epi="resid"):                 # (nine launch rows of w2 per layer)
+        lg, ag = gc.Forward(toks, 0)
     assert (lo.view(np.uint32) == lg.view(np.uint32)).all() and ao == ag
     tok = ag
     for i in range(4):

@@ -5,6 +5,8 @@ window, and a matrix the format must refuse -- which has to say so and still com
 import numpy as np
 import pytest
 
+from form_tally import ran
+
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -75,8 +77,11 @@ def test_packed_gate_up_is_the_raw_kernel_and_the_oracle_bit_for_bit(lnb, n, k, 
     x = bf(rng.standard_normal(k) * 2.0)
     nw = bf(1 + 0.1 * rng.standard_normal(k))
     w1, w3, want = weights(kind, n, k, rng)
-    y_raw, st_raw = lnb.op_rmsnorm_gate_up(x, nw, EPS, w1, w3, packed=0)
-    y_pk, st_pk = lnb.op_rmsnorm_gate_up(x, nw, EPS, w1, w3, packed=1)
+    with ran(lnb, "gemv_chain.rw56", epi="silu_mul", not_ran=("gemv_chain_pk",)):
+        y_raw, st_raw = lnb.op_rmsnorm_gate_up(x, nw, EPS, w1, w3, packed=0)
+    # a packable matrix runs the packed kernel when asked; a refused one keeps the raw kernel
+    with ran(lnb, "gemv_chain_pk" if want == 0 else "gemv_chain.rw56", epi="silu_mul", not_ran=("gemv_chain.rw56" if want == 0 else "gemv_chain_pk",)):
+        y_pk, st_pk = lnb.op_rmsnorm_gate_up(x, nw, EPS, w1, w3, packed=1)
     ref = oracle_gate_up(x, nw, w1, w3)
     assert st_pk == want == st_raw                          # a refused matrix is reported, with its reason
     assert (y_raw == ref).all()
