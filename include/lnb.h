@@ -497,6 +497,57 @@ int lnb_batch_decode_until(lnb_batch* b, const int32_t* tokens, const int32_t* s
 /* measurement aid: average HIP-event time of one kernel class of the batched step (which as lnb_profile_kernel; a norm launch counts
  * with the product it feeds), every sequence placed at `pos`; overwrites the caches' row `pos` */
 int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int iters, float* avg_ms_out);
+
+/* ---- seeded temperature / top-k / top-p sampling in the device loops ----------------------------------------
+ * The reference generates with ml.Argmax alone (inference.go:207-226).  A sampler {temperature, top_k, top_p, seed} replaces that argmax in the
+ * device-resident loop and in the batched loop; the sampled token is a pure function of the step's bf16 logits row x[0..V), the sampler and
+ * the position pos of the step's input token (csrc/lnb_sample.h holds the definition in plain C++; tests/sampler_ref.py restates it):
+ *   1. y_j = trunc_bf16(f32(x_j) / temperature) -- ml.DivToScalar (operations_impl.go:273-289); temperature 1 leaves the row as it is
+ *   2. candidates are ml.Argmax's: y_j not NaN and > -MaxFloat32.  No candidate: token -1, which the loops treat as an all-NaN row
+ *   3. e_j = exp(f64(y_j)) of the host C library (the 65536-entry table of the token probabilities); a = ml.Argmax(y), e_max = e_a; a
+ *      DEGENERATE row -- e_max +inf or below 2^-1022 -- gives token a
+ *   4. w_j = floor(e_j * 2^(45 - E)) as unsigned 64-bit integers, E = floor(log2(e_max)); S = {j: w_j >= 1}.  V <= 131072 keeps every sum below 2^63
+ *   5. S is ordered by y descending, the lowest index first among equal values (the order of the token-probability top-k)
+ *   6. top_k > 0 keeps the first min(top_k, |S|) entries, top_k == 0 all of S; W1 = their weight sum
+ *   7. top_p < 1 keeps the shortest prefix of those whose weight sum is >= P = uint64(floor(f64(top_p) * f64(W1))), at least one; top_p == 1 is off
+ *   8. W_K = the kept weight sum, u = splitmix64(splitmix64(seed) ^ (uint64(pos) * 0x9E3779B97F4A7C15)), r = (u * W_K) >> 64 (128-bit product);
+ *      the token is the first kept index, walking the kept set in INDEX order, at which the running weight sum exceeds r
+ * Everything behind the table lookup is integer arithmetic -- associative -- so the parallel kernel, the serial walk and the Python restatement
+ * agree bit for bit: no tolerance, no statistics.  temperature == 0 means greedy: the token is ml.Argmax(x), the other fields are ignored.
+ * The draw depends on (seed, pos) only: a run gives the same tokens whatever its chunking, a batch member the tokens of its own single-context
+ * run; two members with the same seed, positions and logits draw alike (seeds are the caller's business).
+ * The sampler is an ARGUMENT of the call, not context state: the greedy, speculative, append and pipeline entry points know nothing of it.
+ * The FIRST token of a generation is the prompt's: lnb_forward reports its argmax only.  A caller that wants it sampled too takes the prompt's last
+ *   logits row (lnb_forward / lnb_forward_append with logits) through lnb_op_sample at the position of the last prompt token, as the Python
+ *   InferenceEngine(..., sampler=) does; the loops below sample every token after it.
+ * lnb_decode_sample_until: lnb_decode_greedy_until with step 8's token in place of the argmax -- same arguments, stop ids, finished flag,
+ *   token log, error latch and n_generated.  The sampling step has captured graphs of its own (the greedy ones are neither dropped nor
+ *   recaptured); the graph holds a pointer to the sampler, so another sampler replays the same graph.
+ * lnb_batch_decode_sample_until: lnb_batch_decode_until with one sampler per member (samplers[n]); a temperature-0 member is greedy;
+ *   start_pos[s] < 0 freezes a finished member.
+ * lnb_op_sample: the kernel on host rows [rows][V] (a test aid, as lnb_op_token_probs).  draws (optional): u of step 8 given per row instead
+ *   of derived from (seed, pos).  info (optional), per row: w_all = the weight sum over S, n_candidates = |S|, w_topk = W1, w_kept = W_K,
+ *   n_kept, degenerate (a degenerate, greedy or candidate-less row reports zeros elsewhere).
+ * Refused, each with a message, before any handle is dereferenced or any device touched: NULL pointers; temperature negative, NaN or infinite;
+ *   top_k < 0; top_p NaN, <= 0 or > 1; reserved != 0; V > 131072 or V < 1.  (lnb_batch_decode_sample_until: the NULL checks come before the
+ *   handle is used; how many samplers there are is the batch's own n, so they are checked right after it is read and before anything else.)  Then: a stage handle that is not the whole model; a context or a
+ *   member that records token probabilities (the record promises ids[i * k] == out_tokens[i], which a sampled token does not keep: switch it
+ *   off with lnb_ctx_set_token_probs(ctx, 0)); a pending lnb_forward_stage_begin; max_steps beyond the token log, the KV cache or the RoPE table.
+ * Out of scope: sampling in the speculative loops (it needs rejection sampling, a different contract), pipeline ticks, recording the sampled
+ *   token's probability, min-p, repetition penalties, logit bias. */
+#define LNB_SAMPLE_MAX_VOCAB 131072
+typedef struct lnb_sampler { float temperature; float top_p; int32_t top_k; int32_t reserved; uint64_t seed; } lnb_sampler;
+typedef struct lnb_sample_info { uint64_t w_all, w_topk, w_kept; int32_t n_candidates, n_kept, degenerate, pad; } lnb_sample_info;
+int lnb_decode_sample_until(lnb_ctx* c, const lnb_sampler* sampler, int32_t token, int start_pos, int max_steps,
+                            int32_t* out_tokens, int* n_generated, int* finished, float* ms_out);
+int lnb_batch_decode_sample_until(lnb_batch* b, const lnb_sampler* samplers, const int32_t* tokens, const int32_t* start_pos, int max_steps,
+                                  int32_t* out_tokens, int32_t* n_generated, int32_t* finished, float* ms_out);
+int lnb_op_sample(int device, const uint16_t* logits_bf16, int rows, int V, const lnb_sampler* samplers, const int32_t* pos,
+                  const uint64_t* draws, int32_t* tokens_out, lnb_sample_info* info);
+/* measurement aid: average HIP-event time of a decode step's token launch alone -- sample_kernel with this sampler, or argmax_kernel (sampler
+ * NULL) -- on the logits row the context's last step left; the launches advance the context's device state from `pos` as steps do.  Whole-model
+ * contexts with no lnb_forward_stage_begin pending; a bad sampler is refused as above. */
+int lnb_profile_sample(lnb_ctx* c, const lnb_sampler* sampler, int pos, int iters, float* avg_ms_out);
 /* Attention form of a batch's steps (same bits either way): the one-workgroup-per-head kernels, or the long-context pair with the sequences as a
  * grid dimension (its scratch -- n * n_heads * max seq_len * 8 bytes -- is allocated when a call first needs it; a call that cannot get it fails).
  * The form is chosen per call (lnb_batch_decode[_until], lnb_batch_set_state for the ticks that follow, lnb_batch_profile_kernel): long when the

@@ -27,11 +27,14 @@
 #include "lnb_wpack.h"
 #include "lnb_batchplan.h"
 #include "lnb_rccl.h"
+#include "lnb_sample.h"
 static_assert(LNB_MAX_SEQ_LEN == LNB_SEQ_MAX, "lnb.h and lnb_device.h disagree on the longest context");
 static_assert(ROWPACK_MAX_W == LNB_BATCH_MAX, "lnb_rowpack.h and lnb_device.h disagree on the columns of a pass");
 static_assert(BATCHPLAN_COLS == LNB_STREAM_COLS, "lnb_batchplan.h and lnb_device.h disagree on the sequences of a column group");
 static_assert(LNB_MAX_FORK == KVC_MAX_DST, "lnb.h and lnb_kvcopy.h disagree on the destinations of a fork");
 static_assert(LNB_MAX_TOP_K == LNB_TOKPROB_MAX_K, "lnb.h and lnb_device.h disagree on the largest top-k");
+static_assert(sizeof(lnb_sampler) == sizeof(LnbSampler) && sizeof(lnb_sampler) == 24 && sizeof(lnb_sample_info) == sizeof(LnbSampleInfo) && sizeof(lnb_sample_info) == 40 &&
+              LNB_SAMPLE_MAX_VOCAB == LNB_SAMPLE_MAX_V, "lnb.h and lnb_sample.h disagree on the sampler");
 static_assert(LNB_MAX_DRAFT == LNB_SPEC_MAX_DRAFT && LNB_MAX_DRAFT + 1 <= LNB_STREAM_COLS, "a verify pass is one column group of at most 16 columns");
 
 extern "C" {
@@ -50,6 +53,9 @@ hipError_t lnbk_gemm(const GemmParams* p, int epi, hipStream_t st);
 hipError_t lnbk_rmsnorm_rows(const uint16_t* x, const uint16_t* w, uint16_t* out, int S, int K, float eps, hipStream_t st);
 hipError_t lnbk_embed(const uint16_t* emb, const int32_t* tokens, uint16_t* x, int S, int dim, int vocab, int* err, hipStream_t st);
 hipError_t lnbk_argmax(const uint16_t* logits, int V, int32_t* next_token, StepState* state, int32_t* out_tokens, int out_cap, int advance, hipStream_t st);
+hipError_t lnbk_sample(const uint16_t* logits, int V, int rows, const double* etab, const LnbSampler* smp, int32_t* next_token, StepState* state, int32_t* out_tokens,
+                       int out_cap, int advance, const int32_t* pos, const unsigned long long* draws, LnbSampleInfo* info, hipStream_t st);
+hipError_t lnbk_batch_sample(const uint16_t* logits, int V, const double* etab, const LnbSampler* smp, const BatchTab* tab, int nseq, hipStream_t st);
 hipError_t lnbk_set_state(StepState* state, int pos, int n_out, int honour_stop, hipStream_t st);
 hipError_t lnbk_set_stop(StepState* state, const int32_t* ids, int n, hipStream_t st);
 hipError_t lnbk_advance_state(StepState* state, int rows, hipStream_t st);
@@ -201,6 +207,10 @@ struct lnb_ctx {
     int attn_short_cap = 0;                // longest context the one-workgroup-per-head kernel can stage in the LDS
     bool attn_long = false;                // selection for the launches being enqueued (set per call / per captured graph)
     hipGraphExec_t graph_long = nullptr;   // the decode step captured with the long-context attention
+    // the sampling step (lnb_decode_sample_until): graphs of its own beside graph / graph_long, one per attention form; they hold the POINTER d_smp, the
+    // call copies its sampler there before the replays
+    hipGraphExec_t sgraph = nullptr, sgraph_long = nullptr;
+    LnbSampler* d_smp = nullptr;
     // pipeline stage (lnb_pipeline_tick): one-token stage step as a captured graph per attention form, events towards / from the exchange stream
     hipGraphExec_t stage_graph[2] = {nullptr, nullptr};
     hipEvent_t ev_done = nullptr, ev_in = nullptr, ev_sent = nullptr;
@@ -261,6 +271,8 @@ static int staging_release(lnb_ctx* c) {
 static void drop_graphs(lnb_ctx* c) {
     if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; }
     if (c->graph_long) { hipGraphExecDestroy(c->graph_long); c->graph_long = nullptr; }
+    if (c->sgraph) { hipGraphExecDestroy(c->sgraph); c->sgraph = nullptr; }
+    if (c->sgraph_long) { hipGraphExecDestroy(c->sgraph_long); c->sgraph_long = nullptr; }
     for (int i = 0; i < 2; i++) if (c->stage_graph[i]) { hipGraphExecDestroy(c->stage_graph[i]); c->stage_graph[i] = nullptr; }
 }
 static int auto_rw(int lane_rows, Knob env, int K = 0, bool plain = false, int unforced = 0) {      // unforced: the caller's choice while the knob is 0 (0: by shape)
@@ -867,7 +879,7 @@ extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
     spec_free(c);
     for (auto p : c->ck) if (p) hipFree(p);
     for (auto p : c->cv) if (p) hipFree(p);
-    hipFree(c->st); hipFree(c->dtok); hipFree(c->dnext); hipFree(c->derr); hipFree(c->dout);
+    hipFree(c->st); hipFree(c->dtok); hipFree(c->dnext); hipFree(c->derr); hipFree(c->dout); hipFree(c->d_smp);
     if (c->h_io) hipHostFree(c->h_io);
     hipFree(c->x); hipFree(c->h); hipFree(c->xn); hipFree(c->q); hipFree(c->att); hipFree(c->ffn); if (c->logits) hipFree(c->logits);
     if (c->ev0) hipEventDestroy(c->ev0);
@@ -1538,8 +1550,9 @@ extern "C" int lnb_forward_score_append(lnb_ctx* c, const int32_t* tokens, int s
     return forward_append_impl(c, "lnb_forward_score_append", tokens, seq, start_pos, nullptr, argmax_last_out, &sc);
 }
 
-// one decode step = embed(token on device) -> layers -> head -> [token probabilities] -> argmax that feeds the next step
-static int enqueue_decode_step(lnb_ctx* c) {
+// one decode step = embed(token on device) -> layers -> head -> [token probabilities] -> argmax that feeds the next step; sample: the sampler's token
+// (the context's device sampler, lnb_decode_sample_until) in place of the argmax
+static int enqueue_decode_step(lnb_ctx* c, bool sample = false) {
     lnb_model* m = c->m;
     // LNB_MEASURE_SKIP_TOKEN_KERNELS=1 (timing only, the tokens are garbage): the step without its embedding gather and argmax launches =
     // the most that fusing them into the neighbouring products could return (NOTES 5.8)
@@ -1551,7 +1564,8 @@ static int enqueue_decode_step(lnb_ctx* c) {
         TokProbParams p = tp_params(m, c->logits, 1, c->top_k, c->tp_zpart, c->tp_kpart, c->tp_cnt, c->tp_out, 0);
         HIPCHK(lnbk_token_probs(&p, c->stream));
     }
-    if (!skip) HIPCHK(lnbk_argmax(c->logits, m->a.vocab_size, c->dtok, c->st, c->dout, c->dout_cap, 1, c->stream));
+    if (sample) HIPCHK(lnbk_sample(c->logits, m->a.vocab_size, 1, m->prob_etab, c->d_smp, c->dtok, c->st, c->dout, c->dout_cap, 1, nullptr, nullptr, nullptr, c->stream));
+    else if (!skip) HIPCHK(lnbk_argmax(c->logits, m->a.vocab_size, c->dtok, c->st, c->dout, c->dout_cap, 1, c->stream));
     return 0;
 }
 
@@ -1632,14 +1646,28 @@ template <class Body> static int capture_once(hipGraphExec_t* slot, hipStream_t 
 }
 // one captured graph per attention form: the step at context T replays the long-context one when T exceeds the crossover.  Captures the
 // forms that steps at positions start_pos .. start_pos + n_steps - 1 need and the context does not hold yet.
-static int capture_decode_graphs(lnb_ctx* c, int start_pos, int n_steps) {
-    auto capture = [&](hipGraphExec_t* slot, bool longctx) { return capture_once(slot, c->stream, [&] { c->attn_long = longctx; return enqueue_decode_step(c); }); };
+static int capture_decode_graphs(lnb_ctx* c, int start_pos, int n_steps, bool sample = false) {
+    auto capture = [&](hipGraphExec_t* slot, bool longctx) { return capture_once(slot, c->stream, [&] { c->attn_long = longctx; return enqueue_decode_step(c, sample); }); };
     const bool any_short = !want_long_attention(c, 1, start_pos), any_long = want_long_attention(c, 1, start_pos + n_steps - 1);
-    if (any_short && capture(&c->graph, false)) return -1;
-    if (any_long && capture(&c->graph_long, true)) return -1;
+    if (any_short && capture(sample ? &c->sgraph : &c->graph, false)) return -1;
+    if (any_long && capture(sample ? &c->sgraph_long : &c->graph_long, true)) return -1;
     return 0;
 }
-static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out);
+// what every sampling entry point asks of a sampler (who: "" or "sequence 3: "), before anything else is looked at
+static int sampler_check(const lnb_sampler* s, const char* who) {
+    if (!(s->temperature >= 0.0f) || std::isinf(s->temperature)) return fail("%ssampler: temperature must be finite and >= 0 (got %g; 0 = greedy)", who, (double)s->temperature);
+    if (s->top_k < 0) return fail("%ssampler: top_k must be >= 0 (got %d; 0 = off)", who, s->top_k);
+    if (!(s->top_p > 0.0f && s->top_p <= 1.0f)) return fail("%ssampler: top_p must be in (0, 1] (got %g; 1 = off)", who, (double)s->top_p);
+    if (s->reserved != 0) return fail("%ssampler: reserved must be 0 (got %d)", who, s->reserved);
+    return 0;
+}
+static int sample_vocab_check(int V) {
+    if (V < 1 || V > LNB_SAMPLE_MAX_VOCAB) return fail("sampling takes rows of 1..%d entries (got %d): the integer weight sums of a longer row could pass 2^63", LNB_SAMPLE_MAX_VOCAB, V);
+    return 0;
+}
+static const char* const k_sample_probs_advice = "records token probabilities, whose records promise ids[i * k] == out_tokens[i] -- a sampled token does not keep that: "
+                                                 "switch them off (lnb_ctx_set_token_probs(ctx, 0)) for a sampling call";
+static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out, const lnb_sampler* smp = nullptr);
 extern "C" int lnb_decode_greedy(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int32_t* out_tokens, float* ms_out) {
     return decode_greedy_impl(c, token, start_pos, n_steps, out_tokens, nullptr, nullptr, ms_out);
 }
@@ -1649,10 +1677,51 @@ extern "C" int lnb_decode_greedy_until(lnb_ctx* c, int32_t token, int start_pos,
     if (!n_generated) return fail("null argument");
     return decode_greedy_impl(c, token, start_pos, max_steps, out_tokens, n_generated, finished, ms_out);
 }
-static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out) {
+// lnb_decode_greedy_until with the sampler's token in place of the argmax (include/lnb.h): the same loop over sampling steps, which have captured
+// graphs of their own; the sampler is copied to the device struct those graphs point at
+extern "C" int lnb_decode_sample_until(lnb_ctx* c, const lnb_sampler* sampler, int32_t token, int start_pos, int max_steps, int32_t* out_tokens, int* n_generated,
+                                       int* finished, float* ms_out) {
+    if (!c || !sampler || !out_tokens || !n_generated) return fail("null argument");
+    if (sampler_check(sampler, "")) return -1;
+    return decode_greedy_impl(c, token, start_pos, max_steps, out_tokens, n_generated, finished, ms_out, sampler);
+}
+// measurement aid (tools/sample_bench.py): average HIP-event time of the token launch of a decode step ALONE, on the logits row the context's last step
+// left -- sample_kernel with this sampler, or argmax_kernel (sampler NULL).  Every launch advances the context's device state from `pos` as a step does.
+extern "C" int lnb_profile_sample(lnb_ctx* c, const lnb_sampler* sampler, int pos, int iters, float* avg_ms_out) {
+    if (!c || !avg_ms_out) return fail("null argument");
+    if (sampler && sampler_check(sampler, "")) return -1;
+    lnb_model* m = c->m;
+    if (!m->first() || !m->last()) return fail("lnb_profile_sample needs a whole-model handle");
+    if (sampler && sample_vocab_check(m->a.vocab_size)) return -1;
+    if (iters <= 0 || pos < 0) return fail("bad arguments");
+    if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
+    HIPCHK(hipSetDevice(m->device));
+    hipStream_t st = c->stream;
+    if (sampler && !c->d_smp) HIPCHK(hipMalloc((void**)&c->d_smp, sizeof(LnbSampler)));
+    if (sampler) HIPCHK(hipMemcpyAsync(c->d_smp, sampler, sizeof(LnbSampler), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx_set_state(c, pos, 0, false, false));
+    auto launch = [&]() {
+        return sampler ? lnbk_sample(c->logits, m->a.vocab_size, 1, m->prob_etab, c->d_smp, c->dtok, c->st, c->dout, c->dout_cap, 1, nullptr, nullptr, nullptr, st)
+                       : lnbk_argmax(c->logits, m->a.vocab_size, c->dtok, c->st, c->dout, c->dout_cap, 1, st);
+    };
+    for (int i = 0; i < 3; i++) HIPCHK(launch());
+    HIPCHK(hipEventRecord(c->ev0, st));
+    for (int i = 0; i < iters; i++) HIPCHK(launch());
+    HIPCHK(hipEventRecord(c->ev1, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *avg_ms_out = ms / (float)iters;
+    return 0;
+}
+static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out, const lnb_sampler* smp) {
     if (!c || !out_tokens) return fail("null argument");
     lnb_model* m = c->m;
-    if (!m->first() || !m->last()) return fail("lnb_decode_greedy needs a whole-model handle");
+    if (!m->first() || !m->last()) return fail("%s needs a whole-model handle", smp ? "lnb_decode_sample_until" : "lnb_decode_greedy");
+    if (smp) {
+        if (sample_vocab_check(m->a.vocab_size)) return -1;
+        if (c->top_k > 0) return fail("the context %s", k_sample_probs_advice);
+        if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
+    }
     HIPCHK(hipSetDevice(m->device));
     if (n_steps <= 0) return fail("n_steps must be positive");
     if (n_steps > c->dout_cap) return fail("n_steps %d exceeds the context length %d", n_steps, c->dout_cap);
@@ -1660,8 +1729,10 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     if (token < 0 || token >= m->a.vocab_size) return fail("token id at index 0 is outside the vocabulary");
     hipStream_t st = c->stream;
     const bool use_graph = knob(Knob::NO_GRAPH) == 0;
-    if (use_graph && capture_decode_graphs(c, start_pos, n_steps)) return -1;
+    if (smp && !c->d_smp) HIPCHK(hipMalloc((void**)&c->d_smp, sizeof(LnbSampler)));
+    if (use_graph && capture_decode_graphs(c, start_pos, n_steps, smp != nullptr)) return -1;
     c->tp_last_k = 0; c->tp_last_n = 0;
+    if (smp) HIPCHK(hipMemcpyAsync(c->d_smp, smp, sizeof(LnbSampler), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(c->dtok, &token, 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(c->derr, 0, 4, st));
     // (the argmax kernel advances the position on the device from here on.)  Stop ids are compared only on behalf of a caller that learns how far
@@ -1672,8 +1743,8 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     HIPCHK(hipEventRecord(c->ev0, st));
     for (int i = 0; i < n_steps; i++) {
         const bool longctx = want_long_attention(c, 1, start_pos + i);
-        if (use_graph) HIPCHK(hipGraphLaunch(longctx ? c->graph_long : c->graph, st));
-        else { c->attn_long = longctx; if (enqueue_decode_step(c)) return -1; }
+        if (use_graph) HIPCHK(hipGraphLaunch(smp ? (longctx ? c->sgraph_long : c->sgraph) : (longctx ? c->graph_long : c->graph), st));
+        else { c->attn_long = longctx; if (enqueue_decode_step(c, smp != nullptr)) return -1; }
     }
     HIPCHK(hipEventRecord(c->ev1, st));
     HIPCHK(hipMemcpyAsync(out_tokens, c->dout, (size_t)n_steps * 4, hipMemcpyDeviceToHost, st));
@@ -1897,6 +1968,8 @@ struct lnb_batch {
     int attn_long_T = 0x7FFFFFFF, force_zseq = 0, last_form = 0;
     double* e_buf = nullptr; double* z_part = nullptr;
     hipGraphExec_t graph_long = nullptr, stage_graph_long = nullptr;
+    // the sampling step (lnb_batch_decode_sample_until): graph slots of its own, one per attention form, and the device array of n samplers they point at
+    hipGraphExec_t sgraph = nullptr, sgraph_long = nullptr; LnbSampler* d_smp = nullptr;
     // a verify batch whose columns run the multi-row long-context pair (lnb_ctx_set_rows_attention, flags bit 1): a captured graph of its own
     bool attn_rows = false; int rows_zseq = 0; hipGraphExec_t graph_rows = nullptr;
     bool rows_form = false;                // the model carries no matrix-core copy: every product runs as ROWS of gemm_stream_kernel on the resident layouts, whatever n
@@ -1989,6 +2062,9 @@ extern "C" int lnb_batch_destroy(lnb_batch* b) {
     if (b->counted) for (lnb_ctx* c : b->ctxs) c->batch_users--;
     if (b->graph) hipGraphExecDestroy(b->graph);
     if (b->graph_long) hipGraphExecDestroy(b->graph_long);
+    if (b->sgraph) hipGraphExecDestroy(b->sgraph);
+    if (b->sgraph_long) hipGraphExecDestroy(b->sgraph_long);
+    hipFree(b->d_smp);
     if (b->graph_rows) hipGraphExecDestroy(b->graph_rows);
     if (b->stage_graph_long) hipGraphExecDestroy(b->stage_graph_long);
     if (b->scratch_owned) { hipFree(b->e_buf); hipFree(b->z_part); }
@@ -2237,11 +2313,13 @@ static int enqueue_batch_pass(lnb_batch* b) {
 // One batched step of this model STAGE: the pass, and on the last stage the argmax (which advances every sequence's position); a stage
 // without the head advances the positions itself.  ring_in: the first stage of a multi-stage pipeline takes the tokens from the contiguous
 // words the last stage sent (lnb_pipeline_tick_batch).
-static int enqueue_batch_step(lnb_batch* b, bool ring_in = false) {
+static int enqueue_batch_step(lnb_batch* b, bool ring_in = false, bool sample = false) {
     lnb_model* m = b->m;
     if (ring_in && m->first()) HIPCHK(lnbk_batch_scatter_ring(b->tab, b->ring, b->stream));
     if (enqueue_batch_pass(b)) return -1;
-    if (m->last()) {
+    if (m->last() && sample) {                               // every member's own sampler (lnb_batch_decode_sample_until: a whole model, no token probabilities)
+        HIPCHK(lnbk_batch_sample(b->logits, m->a.vocab_size, m->prob_etab, b->d_smp, b->tab, b->n, b->stream));
+    } else if (m->last()) {
         if (b->top_k > 0) {                                  // (ticks refuse such batches: only lnb_batch_decode[_until] gets here with it)
             TokProbParams p = tp_params(m, b->logits, b->n, b->top_k, b->tp_zpart, b->tp_kpart, b->tp_cnt, b->tp_out, 1);
             HIPCHK(lnbk_token_probs(&p, b->stream));
@@ -2250,7 +2328,8 @@ static int enqueue_batch_step(lnb_batch* b, bool ring_in = false) {
     } else HIPCHK(lnbk_batch_advance(b->tab, b->stream));
     return 0;
 }
-static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t* start_pos, int n_steps, int32_t* out_tokens, int32_t* n_generated, int32_t* finished, float* ms_out);
+static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t* start_pos, int n_steps, int32_t* out_tokens, int32_t* n_generated, int32_t* finished, float* ms_out,
+                             const lnb_sampler* smp = nullptr);
 extern "C" int lnb_batch_decode(lnb_batch* b, const int32_t* tokens, const int32_t* start_pos, int n_steps, int32_t* out_tokens, float* ms_out) {
     return batch_decode_impl(b, tokens, start_pos, n_steps, out_tokens, nullptr, nullptr, ms_out);     // n_steps tokens per sequence: stop ids are not compared
 }
@@ -2263,10 +2342,26 @@ extern "C" int lnb_batch_decode_until(lnb_batch* b, const int32_t* tokens, const
     if (!n_generated) return fail("null argument");
     return batch_decode_impl(b, tokens, start_pos, max_steps, out_tokens, n_generated, finished, ms_out);
 }
-static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t* start_pos, int n_steps, int32_t* out_tokens, int32_t* n_generated, int32_t* finished, float* ms_out) {
+// lnb_batch_decode_until with one sampler per member (include/lnb.h).  The samplers are checked as far as the caller's n reaches: the batch's own n is
+// behind the handle, so the loop over them runs after the NULL checks and before anything else of the batch is used.
+extern "C" int lnb_batch_decode_sample_until(lnb_batch* b, const lnb_sampler* samplers, const int32_t* tokens, const int32_t* start_pos, int max_steps, int32_t* out_tokens,
+                                             int32_t* n_generated, int32_t* finished, float* ms_out) {
+    if (!b || !samplers || !tokens || !start_pos || !out_tokens || !n_generated) return fail("null argument");
+    return batch_decode_impl(b, tokens, start_pos, max_steps, out_tokens, n_generated, finished, ms_out, samplers);
+}
+static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t* start_pos, int n_steps, int32_t* out_tokens, int32_t* n_generated, int32_t* finished, float* ms_out,
+                             const lnb_sampler* smp) {
     if (!b || !tokens || !start_pos || !out_tokens) return fail("null argument");
     lnb_model* m = b->m;
-    if (!m->first() || !m->last()) return fail("lnb_batch_decode needs a whole-model handle; pipeline stages run their batches through lnb_pipeline_tick_batch");
+    if (smp) {
+        char who[32];
+        for (int s = 0; s < b->n; s++) { snprintf(who, sizeof who, "sequence %d: ", s); if (sampler_check(smp + s, who)) return -1; }
+    }
+    if (!m->first() || !m->last()) return fail("%s needs a whole-model handle; pipeline stages run their batches through lnb_pipeline_tick_batch", smp ? "lnb_batch_decode_sample_until" : "lnb_batch_decode");
+    if (smp) {
+        if (sample_vocab_check(m->a.vocab_size)) return -1;
+        for (int s = 0; s < b->n; s++) if (b->ctxs[s]->top_k > 0) return fail("sequence %d: its context %s", s, k_sample_probs_advice);
+    }
     HIPCHK(hipSetDevice(m->device));
     if (n_steps <= 0) return fail("n_steps must be positive");
     for (int s = 0; s < b->n; s++) {
@@ -2283,8 +2378,10 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     hipStream_t st = b->stream;
     if (batch_select_form_at(b, start_pos)) return -1;
     const bool use_graph = knob(Knob::NO_GRAPH) == 0;
-    hipGraphExec_t* const gslot = b->attn_long ? &b->graph_long : &b->graph;       // one captured step per form
-    if (use_graph && capture_once(gslot, st, [&] { return enqueue_batch_step(b); })) return -1;
+    hipGraphExec_t* const gslot = smp ? (b->attn_long ? &b->sgraph_long : &b->sgraph) : (b->attn_long ? &b->graph_long : &b->graph);       // one captured step per form
+    if (smp && !b->d_smp) HIPCHK(hipMalloc((void**)&b->d_smp, (size_t)LNB_BATCH_MAX * sizeof(LnbSampler)));
+    if (use_graph && capture_once(gslot, st, [&] { return enqueue_batch_step(b, false, smp != nullptr); })) return -1;
+    if (smp) HIPCHK(hipMemcpyAsync(b->d_smp, smp, (size_t)b->n * sizeof(LnbSampler), hipMemcpyHostToDevice, st));
     memcpy(b->h_io, tokens, (size_t)b->n * 4); memcpy(b->h_io + LNB_BATCH_MAX, start_pos, (size_t)b->n * 4);
     HIPCHK(hipMemcpyAsync(b->d_tokens, b->h_io, (size_t)b->n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(b->d_pos, b->h_io + LNB_BATCH_MAX, (size_t)b->n * 4, hipMemcpyHostToDevice, st));
@@ -2293,7 +2390,7 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     HIPCHK(hipEventRecord(b->ev0, st));
     for (int i = 0; i < n_steps; i++) {
         if (use_graph) HIPCHK(hipGraphLaunch(*gslot, st));
-        else if (enqueue_batch_step(b)) return -1;
+        else if (enqueue_batch_step(b, false, smp != nullptr)) return -1;
     }
     HIPCHK(hipEventRecord(b->ev1, st));
     b->last_form = b->attn_long ? 1 : 0;
@@ -2599,6 +2696,7 @@ extern "C" int lnb_batch_set_attention(lnb_batch* b, int long_threshold, int for
     if (long_threshold >= 0) b->attn_long_T = long_threshold;
     if (force_zseq != b->force_zseq) {
         if (b->graph_long) { hipGraphExecDestroy(b->graph_long); b->graph_long = nullptr; }
+        if (b->sgraph_long) { hipGraphExecDestroy(b->sgraph_long); b->sgraph_long = nullptr; }
         if (b->stage_graph_long) { hipGraphExecDestroy(b->stage_graph_long); b->stage_graph_long = nullptr; }
         b->force_zseq = force_zseq;
     }
@@ -3625,6 +3723,37 @@ extern "C" int lnb_op_token_probs(int device, const uint16_t* logits_bf16, int r
     hipFree(b);
     HIPCHK(e);
     if (serial_walks) *serial_walks = walks;
+    return 0;
+}
+// sample_kernel on host rows (test aid): row i with samplers[i] at pos[i] (or with u = draws[i]); info optional
+extern "C" int lnb_op_sample(int device, const uint16_t* logits_bf16, int rows, int V, const lnb_sampler* samplers, const int32_t* pos, const uint64_t* draws,
+                             int32_t* tokens_out, lnb_sample_info* info) {
+    if (!logits_bf16 || !samplers || !pos || !tokens_out) return fail("null argument");
+    if (rows <= 0) return fail("empty operand");
+    if (sample_vocab_check(V)) return -1;
+    char who[32];
+    for (int i = 0; i < rows; i++) { snprintf(who, sizeof who, "row %d: ", i); if (sampler_check(samplers + i, who)) return -1; }
+    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
+    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    const size_t R = rows;
+    std::vector<double> et; prob_exp_table(et);
+    const size_t o_x = align256(65536 * 8), o_s = o_x + align256(R * V * 2 + 16), o_p = o_s + align256(R * sizeof(LnbSampler)), o_u = o_p + align256(R * 4),
+                 o_t = o_u + align256(R * 8), o_i = o_t + align256(R * 4), need = o_i + align256(R * sizeof(LnbSampleInfo));
+    char* b = nullptr;
+    HIPCHK(hipMalloc((void**)&b, need));
+    hipError_t e = hipMemcpy(b, et.data(), 65536 * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(b + o_x, logits_bf16, R * V * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(b + o_s, samplers, R * sizeof(LnbSampler), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(b + o_p, pos, R * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && draws) e = hipMemcpy(b + o_u, draws, R * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = lnbk_sample((const uint16_t*)(b + o_x), V, rows, (const double*)b, (const LnbSampler*)(b + o_s), (int32_t*)(b + o_t), nullptr, nullptr, 0, 0,
+                                         (const int32_t*)(b + o_p), draws ? (const unsigned long long*)(b + o_u) : nullptr, info ? (LnbSampleInfo*)(b + o_i) : nullptr, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(tokens_out, b + o_t, R * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && info) e = hipMemcpy(info, b + o_i, R * sizeof(LnbSampleInfo), hipMemcpyDeviceToHost);
+    hipFree(b);
+    HIPCHK(e);
     return 0;
 }
 extern "C" int lnb_op_exp_table(int device, float divisor, double* out65536) {

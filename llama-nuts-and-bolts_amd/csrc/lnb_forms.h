@@ -60,6 +60,9 @@
     X(KV_FORK_NT, "kv_fork.nt", "kv_fork_kernel<true>: non-temporal loads and stores (LNB_FORK_NT)") \
     X(KV_FORK_SPLIT, "kv_fork.split", "kv_fork_kernel with the destinations dealt over several workgroup groups (LNB_FORK_SPLIT; counted beside plain / nt)") \
     X(KV_FORK_COPY, "kv_fork.copy", "the copy engine, no kernel (LNB_FORK_COPY)") \
+    /* the token of a sampling decode step (lnb_decode_sample_until; greedy steps launch argmax_kernel and count nothing) */ \
+    X(SAMPLE_ROW, "sample.row", "sample_kernel: one workgroup per logits row -- the one-token sampling step, rows of lnb_op_sample") \
+    X(SAMPLE_BATCH, "sample.batch", "batch_sample_kernel: one workgroup per member of a batched sampling step, each with its own sampler") \
     /* pipeline stage step */ \
     X(PIPELINE_REPLAY, "pipeline.replay", "a one-token or batched pipeline stage step replayed from its captured graph (counted per step)") \
     X(PIPELINE_EAGER, "pipeline.eager", "such a step launched eagerly (LNB_PIPELINE_GRAPH=0; counted per step)")

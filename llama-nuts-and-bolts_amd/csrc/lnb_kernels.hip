@@ -27,6 +27,10 @@
 #include "lnb_wpack.h"
 
 #define DEVINL __device__ __forceinline__
+#define LNB_SAMPLE_FN DEVINL
+#define LNB_SAMPLE_FDIV(a, b) __fdiv_rn(a, b)
+#define LNB_SAMPLE_NO_SERIAL                 // (the serial whole-row walk is the host's: tests/native/sample_test.cpp)
+#include "lnb_sample.h"
 
 DEVINL float bf_lo(uint32_t u) { return __uint_as_float(u << 16); }
 DEVINL float bf_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
@@ -4109,6 +4113,18 @@ DEVINL int argmax_block(const uint16_t* logits, int V, float* sv, int* si) {    
     }
     return si[0];
 }
+// What a step's token does to its generation (inference.go:211-226): the token word the next step embeds, the token log, the position, the stop ids --
+// and nothing at all for a finished generation (see StepState).  The stop token itself is emitted (GSFinishedByReachingEOS).
+DEVINL void step_advance(StepState* st, int tok, int32_t* token_word, int32_t* ring_word, int32_t* out_tokens, int out_cap) {
+    if (st->finished) return;
+    *token_word = tok;
+    if (ring_word) *ring_word = tok;
+    const int n = st->n_out;
+    if (n < out_cap) out_tokens[n] = tok;
+    st->n_out = n + 1;
+    st->pos = st->pos + 1;
+    if (st->honour_stop) for (int k = 0; k < st->n_stop; k++) if (tok == st->stop[k]) st->finished = 1;
+}
 __global__ __launch_bounds__(1024) void argmax_kernel(const uint16_t* logits, int V, int32_t* next_token, StepState* st,
                                                       int32_t* out_tokens, int out_cap, int advance) {
     __shared__ float sv[1024];
@@ -4116,14 +4132,7 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const uint16_t* logits, in
     const int tok = argmax_block(logits, V, sv, si);
     if (threadIdx.x == 0) {
         if (!advance) next_token[0] = tok;
-        else if (!st->finished) {                            // (a finished generation: nothing moves any more, see StepState)
-            next_token[0] = tok;
-            int n = st->n_out;
-            if (n < out_cap) out_tokens[n] = tok;
-            st->n_out = n + 1;
-            st->pos = st->pos + 1;
-            if (st->honour_stop) for (int k = 0; k < st->n_stop; k++) if (tok == st->stop[k]) st->finished = 1;     // the stop token itself is emitted (GSFinishedByReachingEOS)
-        }
+        else step_advance(st, tok, next_token, nullptr, out_tokens, out_cap);
     }
 }
 // the same for the batch: block s = sequence s's logits row; its context's token word, token log and position advance (inference.go:211-226)
@@ -4133,17 +4142,306 @@ __global__ __launch_bounds__(1024) void batch_argmax_kernel(const uint16_t* logi
     const int s = blockIdx.x;
     const int tok = argmax_block(logits + (size_t)s * V, V, sv, si);
     if (threadIdx.x == 0) {
-        StepState* st = tab->st[s];
-        if (!st->finished) {                                 // a finished sequence keeps its token word, log and position (its column goes on computing the same step)
-            *tab->dtok[s] = tok;
-            if (ring) ring[s] = tok;                         // (pipeline: the contiguous words the last stage sends to the first)
-            const int n = st->n_out;
-            if (n < tab->dout_cap[s]) tab->dout[s][n] = tok;
-            st->n_out = n + 1;
-            st->pos = st->pos + 1;
-            if (st->honour_stop) for (int k = 0; k < st->n_stop; k++) if (tok == st->stop[k]) st->finished = 1;
+        // a finished sequence keeps its token word, log and position (its column goes on computing the same step); ring (pipeline): the contiguous
+        // words the last stage sends to the first
+        step_advance(tab->st[s], tok, tab->dtok[s], ring ? ring + s : nullptr, tab->dout[s], tab->dout_cap[s]);
+    }
+}
+
+// ---- seeded temperature / top-k / top-p sampling (lnb_decode_sample_until, include/lnb.h; the rule: lnb_sample.h) -------------------------
+// One workgroup of 1024 lanes per logits row.  The row is read ONCE: lane l keeps the keys (lnb_sample_key of the scaled entry, 16 bits, 0 = no
+// candidate) of the `per` consecutive entries [l * per, (l + 1) * per), per = ceil(V / 1024) rounded up to 8, packed two to a register -- at most
+// 64 registers for V <= 131072.  So the layout is index order: lane-major, then the element inside the lane, and the two index-order prefix sums
+// (ties at the threshold, kept weights) are a per-lane sum, one workgroup scan and a walk inside one lane.  Everything else is a register pass
+// plus a workgroup reduction of integers (any order gives the same bits): the thresholds come from bisection on the key -- counts for top-k,
+// weights for the nucleus -- and a weight is one lookup of the model's exp table by the key's bf16 pattern.
+struct SampleSh {
+    unsigned long long w[2][16];
+    unsigned c[2][16];
+    uint32_t keys[64];                                       // the lane that holds the draw hands its keys to the workgroup
+    unsigned long long ex;
+    unsigned tie0;
+    int owner, tok;
+    LnbSampleInfo z;                                         // filled as the sums become known (thread 0), copied out at the end
+};
+// (a reduction's result is the same in every lane: saying so keeps everything the thresholds are computed from in scalar registers)
+DEVINL unsigned sample_uniform(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
+DEVINL unsigned long long sample_uniform(unsigned long long v) {
+    return ((unsigned long long)sample_uniform((unsigned)(v >> 32)) << 32) | sample_uniform((unsigned)v);
+}
+DEVINL void sample_wg_sum(SampleSh& sh, int& par, unsigned& c, unsigned long long& w) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { c += __shfl_xor(c, o); w += __shfl_xor(w, o); }
+    if ((threadIdx.x & 63) == 0) { sh.c[par][threadIdx.x >> 6] = c; sh.w[par][threadIdx.x >> 6] = w; }
+    __syncthreads();                                         // (two slots: the next reduction writes the other one, the one after comes behind its barrier)
+    c = 0; w = 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) { c += sh.c[par][i]; w += sh.w[par][i]; }
+    c = sample_uniform(c); w = sample_uniform(w);
+    par ^= 1;
+}
+DEVINL unsigned sample_wg_min(SampleSh& sh, int& par, unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned t = __shfl_xor(v, o); v = t < v ? t : v; }
+    if ((threadIdx.x & 63) == 0) sh.c[par][threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = sh.c[par][0];
+#pragma unroll
+    for (int i = 1; i < 16; i++) v = sh.c[par][i] < v ? sh.c[par][i] : v;
+    par ^= 1;
+    return sample_uniform(v);
+}
+// exclusive prefix of v in lane order; total = the workgroup's sum
+DEVINL unsigned long long sample_wg_scan(SampleSh& sh, int& par, unsigned long long v, unsigned long long& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const unsigned long long t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+    if (lane == 63) sh.w[par][wave] = inc;
+    __syncthreads();
+    unsigned long long base = 0; total = 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) { const unsigned long long t = sh.w[par][i]; if (i < wave) base += t; total += t; }
+    total = sample_uniform(total);
+    par ^= 1;
+    return base + inc - v;
+}
+// f(key) for the lane's keys in index order (per is a multiple of 8: the groups in use are the first per / 8)
+template <class F> DEVINL void sample_each(const uint32_t (&kr)[64], int per, F f) {
+#pragma unroll
+    for (int q = 0; q < 16; q++) {
+        if (q * 8 < per) {
+#pragma unroll
+            for (int t = 0; t < 4; t++) { f(kr[q * 4 + t] & 0xffffu); f(kr[q * 4 + t] >> 16); }
         }
     }
+}
+// g(eight keys) group by group; the fence keeps one group's table lookups in flight at a time (their registers are the keys').  The empty asm
+// statements make `per` and the packed keys opaque per pass: otherwise the sixteen group conditions, the 128 unpacked keys and their table offsets are
+// hoisted out of the bisection loop -- into spilled scalar registers and into scratch.  They emit no instruction; like the fences they steer THIS compiler's
+// schedule and register allocation, so "no scratch" is a property of the build, not of the source: tools/isa_audit.py (tests/test_isa_audit.py) checks the
+// compiled kernels' scratch size and VGPR spill count on every build, and a compiler that spills here anyway fails that test instead of running slowly.
+template <class G> DEVINL void sample_groups(uint32_t (&kr)[64], int per, G g) {
+    asm volatile("" : "+s"(per));
+#pragma unroll
+    for (int q = 0; q < 16; q++) {
+        if (q * 8 < per) {
+#pragma unroll
+            for (int t = 0; t < 4; t++) asm volatile("" : "+v"(kr[q * 4 + t]));
+            const unsigned k8[8] = {kr[q * 4] & 0xffffu, kr[q * 4] >> 16, kr[q * 4 + 1] & 0xffffu, kr[q * 4 + 1] >> 16,
+                                    kr[q * 4 + 2] & 0xffffu, kr[q * 4 + 2] >> 16, kr[q * 4 + 3] & 0xffffu, kr[q * 4 + 3] >> 16};
+            g(k8);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+DEVINL unsigned long long sample_key_weight(const double* etab, unsigned key, int E) {
+    return lnb_sample_weight((unsigned long long)__double_as_longlong(etab[lnb_sample_key_bits(key)]), E);
+}
+// -> the token, valid in thread 0, and sh.z = the row's info.  has_u: pos_or_u is u of step 8 itself.
+DEVINL int sample_block(const uint16_t* x, int V, const double* etab, const LnbSampler& s, bool has_u, unsigned long long pos_or_u, SampleSh& sh) {
+    const int tid = threadIdx.x;
+    int par = 0;
+    if (tid == 0) { const LnbSampleInfo z0 = {0, 0, 0, 0, 0, 0, 0}; sh.z = z0; }      // (read back by thread 0 only)
+    const float T = s.temperature;
+    const int per = (((V + 1023) >> 10) + 7) & ~7;
+    // the row, once: scaled (step 1), keyed (steps 2 and 5), packed
+    uint32_t kr[64];
+    const bool al = (((uintptr_t)x) & 15) == 0;
+    auto key_of = [&](uint16_t b) -> uint32_t { return lnb_sample_key(T == 1.0f ? b : lnb_sample_scale(b, T)); };
+#pragma unroll
+    for (int q = 0; q < 16; q++) {
+        if (q * 8 < per) {
+            const int j0 = tid * per + q * 8;
+            if (al && j0 + 8 <= V) {
+                const uint4 v = *(const uint4*)(x + j0);
+                const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int t = 0; t < 4; t++) kr[q * 4 + t] = key_of((uint16_t)(wd[t] & 0xffffu)) | (key_of((uint16_t)(wd[t] >> 16)) << 16);
+            } else {
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+                    const int j = j0 + 2 * t;
+                    const uint32_t lo = j < V ? key_of(x[j]) : 0u, hi = j + 1 < V ? key_of(x[j + 1]) : 0u;
+                    kr[q * 4 + t] = lo | (hi << 16);
+                }
+            }
+            if (q & 1) __builtin_amdgcn_sched_barrier(0);    // (two 16 B loads in flight: with all sixteen hoisted, the raw words and the keys would not fit)
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; t++) kr[q * 4 + t] = 0;
+        }
+    }
+    // step 3: the largest key and its first index
+    unsigned kmax_l = 0;
+    sample_each(kr, per, [&](unsigned k) { kmax_l = k > kmax_l ? k : kmax_l; });
+    const unsigned kmax = ~sample_wg_min(sh, par, ~kmax_l);
+    if (kmax == 0) return -1;                                            // no candidate
+    unsigned a_l = 0xffffffffu, e_l = 0;
+    sample_each(kr, per, [&](unsigned k) { if (k == kmax && a_l == 0xffffffffu) a_l = (unsigned)(tid * per) + e_l; e_l++; });
+    const int a = (int)sample_wg_min(sh, par, a_l);
+    const unsigned long long emax = (unsigned long long)__double_as_longlong(etab[lnb_sample_key_bits(kmax)]);
+    if (lnb_sample_degenerate(emax)) { if (tid == 0) sh.z.degenerate = 1; return a; }
+    const int E = lnb_sample_exponent(emax);
+    // step 4: S = the keys >= kmin, kmin = the smallest key of weight >= 1 (the weight grows with the key).  Two rounds of 1024 probes.
+    unsigned kmin;
+    {
+        const unsigned lo0 = 0x80u, step = (kmax - lo0 + 1023u) >> 10;           // probes lo0 + (i + 1) * step, the last ones clamped to kmax (weight >= 2^45)
+        unsigned k = lo0 + ((unsigned)tid + 1u) * step; k = k > kmax ? kmax : k;
+        const unsigned k1 = sample_wg_min(sh, par, sample_key_weight(etab, k, E) >= 1 ? k : 0xffffffffu);
+        const unsigned lo1 = k1 > lo0 + step ? k1 - step : lo0;                  // weight(lo1) == 0 (a probe that failed) or lo1 is no candidate's key
+        unsigned k2 = lo1 + 1u + (unsigned)tid; k2 = k2 > k1 ? k1 : k2;          // step <= 64: the probes lo1 + 1 .. k1
+        kmin = sample_wg_min(sh, par, sample_key_weight(etab, k2, E) >= 1 ? k2 : 0xffffffffu);
+    }
+    // Steps 6 and 7 as ONE loop around one tally -- (count, weight) of the entries whose key is >= t, t >= kmin: the weight of all of S, then the
+    // bisection for top-k on counts, the weight above its threshold, the bisection for the nucleus on weights, and last the weight above the final
+    // threshold t2, whose per-lane part feeds the index-order prefix sum.  (t, m) = a threshold key and the ties kept at it, lowest indices first;
+    // t = kmin - 1, m = 0 keeps all of S.
+    enum { PH_ALL, PH_TOPK, PH_TOPK_W, PH_TOPP, PH_LAST, PH_DONE };
+    const bool do_p = s.top_p < 1.0f;
+    unsigned t1 = kmin - 1, m1 = 0, n1 = 0, t2 = 0, m2 = 0, nk = 0, kk = 0;
+    unsigned long long w1 = 0, P = 0;
+    unsigned lo = 0, hi = 0, c_hi = 0; unsigned long long w_hi = 0;
+    unsigned t = kmin, lane_t = 0; bool want_w = true; int ph = PH_ALL;
+    unsigned long long lane_w = 0;                                               // this lane's part of the last weight tally, which was for t = lane_t
+    auto begin_last = [&]() {
+        if (lane_t == t2 + 1) ph = PH_DONE; else { t = t2 + 1; want_w = true; ph = PH_LAST; }
+    };
+    auto next_topp = [&]() {
+        if (hi - lo > 1) { t = lo + ((hi - lo) >> 1); want_w = true; ph = PH_TOPP; return; }
+        const unsigned long long wt = sample_key_weight(etab, lo, E);           // kept weight(>= lo) >= P > weight(>= hi), hi = lo + 1
+        unsigned long long need = P > w_hi ? (P - w_hi + wt - 1) / wt : 0;
+        if (need < 1) need = 1;                                                  // at least one entry
+        if (lo == t1 && need > m1) need = m1;
+        t2 = lo; m2 = (unsigned)need; nk = c_hi + m2;
+        begin_last();
+    };
+    auto start_topp = [&]() {
+        if (!do_p) { if (tid == 0) sh.z.w_topk = w1; t2 = t1; m2 = m1; nk = n1; begin_last(); return; }
+        if (tid == 0) sh.z.w_topk = w1;
+        P = lnb_sample_p(s.top_p, w1);
+        lo = P == 0 ? kmax : t1; hi = kmax + 1; c_hi = 0; w_hi = 0;              // above t1 the kept weight is the plain one; P == 0 keeps the first entry
+        next_topp();
+    };
+    auto next_topk = [&]() {
+        if (hi - lo > 1) { t = lo + ((hi - lo) >> 1); want_w = false; ph = PH_TOPK; }
+        else { t = lo + 1; want_w = true; ph = PH_TOPK_W; }                      // count(>= lo) >= kk > count(>= hi) = c_hi
+    };
+    while (ph != PH_DONE) {
+        unsigned c = 0; unsigned long long w = 0;
+        if (!want_w) sample_each(kr, per, [&](unsigned k) { c += 1u + (unsigned)((int)(k - t) >> 31); });      // (keys are 16 bits: the sign of k - t)
+        else {
+            // Branch-free and select-free (eight entries side by side would otherwise hold eight compare masks in scalar registers): every lane looks
+            // up max(key, t) -- a valid pattern, t >= kmin -- eight lookups in flight; an entry below t then adds weight(t), taken off again at the end
+            unsigned seen = 0;
+            sample_groups(kr, per, [&](const unsigned (&k8)[8]) {
+                unsigned gm = k8[0];
+#pragma unroll
+                for (int i = 1; i < 8; i++) gm = k8[i] > gm ? k8[i] : gm;
+                if (!__any(gm >= t)) return;                                     // (wave-uniform: near the top of the row most groups hold nothing)
+                unsigned long long e8[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++) e8[i] = (unsigned long long)__double_as_longlong(etab[lnb_sample_key_bits(k8[i] > t ? k8[i] : t)]);
+#pragma unroll
+                for (int i = 0; i < 8; i++) { c += 1u + (unsigned)((int)(k8[i] - t) >> 31); w += lnb_sample_weight(e8[i], E); }
+                seen += 8;
+            });
+            w -= (unsigned long long)(seen - c) * sample_key_weight(etab, t, E);
+        }
+        if (want_w) { lane_w = w; lane_t = t; }
+        sample_wg_sum(sh, par, c, w);
+        if (ph == PH_ALL) {
+            n1 = c; w1 = w;
+            if (tid == 0) { sh.z.n_candidates = (int)c; sh.z.w_all = w; }
+            if (s.top_k > 0 && (unsigned)s.top_k < c) { kk = (unsigned)s.top_k; lo = kmin; hi = kmax + 1; c_hi = 0; next_topk(); }
+            else start_topp();
+        } else if (ph == PH_TOPK) {
+            if (c >= kk) lo = t; else { hi = t; c_hi = c; }
+            next_topk();
+        } else if (ph == PH_TOPK_W) {
+            t1 = lo; m1 = kk - c_hi; n1 = kk;
+            w1 = w + (unsigned long long)m1 * sample_key_weight(etab, t1, E);
+            start_topp();
+        } else if (ph == PH_TOPP) {
+            if (w >= P) lo = t; else { hi = t; c_hi = c; w_hi = w; }
+            next_topp();
+        } else ph = PH_DONE;                                                     // PH_LAST
+    }
+    // the ties at t2 in index order: this lane's first tie has rank tie0; the lane's kept weight = what it holds above t2 + its kept ties
+    unsigned long long ties_l = 0, ties_all;
+    sample_each(kr, per, [&](unsigned k) { if (k == t2) ties_l++; });
+    const unsigned long long tie0 = sample_wg_scan(sh, par, ties_l, ties_all);
+    if (m2 > ties_all) m2 = (unsigned)ties_all;                                  // (t2 = kmin - 1: no tie is kept, none is wanted)
+    const unsigned long long ties_in = tie0 >= m2 ? 0 : (m2 - tie0 < ties_l ? m2 - tie0 : ties_l);
+    const unsigned long long wl = lane_w + (ties_in ? ties_in * sample_key_weight(etab, t2, E) : 0);
+    // step 8: the kept weights in index order -- the lane whose span holds r, then the entry inside it
+    unsigned long long wk;
+    const unsigned long long ex = sample_wg_scan(sh, par, wl, wk);
+    const unsigned long long u = has_u ? pos_or_u : lnb_sample_draw(s.seed, (int)pos_or_u);
+    const unsigned long long r = lnb_sample_mulhi(u, wk);
+    if (tid == 0) { sh.tok = -1; sh.z.w_kept = wk; sh.z.n_kept = (int)nk; }
+    if (wl > 0 && ex <= r && r < ex + wl) {                                      // exactly one lane
+#pragma unroll
+        for (int i = 0; i < 64; i++) sh.keys[i] = kr[i];
+        sh.owner = tid; sh.ex = ex; sh.tie0 = (unsigned)tie0;
+    }
+    __syncthreads();
+    {
+        const unsigned k = tid < per ? (sh.keys[tid >> 1] >> ((tid & 1) * 16)) & 0xffffu : 0u;
+        unsigned long long tt;
+        const unsigned long long rank = sh.tie0 + sample_wg_scan(sh, par, k == t2 && tid < per ? 1ull : 0ull, tt);
+        const bool member = tid < per && (k > t2 || (k == t2 && rank < m2));
+        const unsigned long long wv = member ? sample_key_weight(etab, k, E) : 0;
+        const unsigned long long exv = sh.ex + sample_wg_scan(sh, par, wv, tt);
+        if (member && exv <= r && r < exv + wv) sh.tok = sh.owner * per + tid;
+    }
+    __syncthreads();
+    return sh.tok;
+}
+// What thread 0 needs AFTER the row is sampled -- where the token goes -- waits in the LDS meanwhile instead of in scalar registers across the bisection
+// loop, which uses nearly all of them (a dozen scalars are still parked in the lanes of one vector register around it: no memory, tools/isa_audit.py).
+struct SampleEnd { StepState* st; int32_t* token_word; int32_t* out_tokens; LnbSampleInfo* info; int out_cap, advance; };
+// sample_kernel: argmax_kernel with the sampler's token (advance: the decode loop's step; its position is the state's).  advance == 0: block i = row i
+// of lnb_op_sample -- its own sampler, position, optional u and info.  temperature 0 = argmax_block on the raw row.
+__global__ __launch_bounds__(1024) void sample_kernel(const uint16_t* logits, int V, const double* etab, const LnbSampler* smp, int32_t* next_token,
+                                                      StepState* st, int32_t* out_tokens, int out_cap, int advance, const int32_t* op_pos,
+                                                      const unsigned long long* op_draws, LnbSampleInfo* op_info) {
+    __shared__ float sv[1024];
+    __shared__ int si[1024];
+    __shared__ SampleSh sh;
+    __shared__ SampleEnd end;
+    const int row = advance ? 0 : blockIdx.x;
+    const LnbSampler s = smp[row];
+    const uint16_t* x = logits + (size_t)row * V;
+    const bool has_u = !advance && op_draws != nullptr;
+    const unsigned long long pos_or_u = advance ? (unsigned long long)(long long)st->pos : has_u ? op_draws[row] : (unsigned long long)(long long)op_pos[row];
+    if (threadIdx.x == 0) {
+        end.st = st; end.token_word = next_token + row; end.out_tokens = out_tokens; end.out_cap = out_cap; end.advance = advance;
+        end.info = !advance && op_info ? op_info + row : nullptr;
+        const LnbSampleInfo z0 = {0, 0, 0, 0, 0, 0, 0}; sh.z = z0;             // (what a greedy row reports)
+    }
+    int tok;
+    if (s.temperature == 0.0f) tok = argmax_block(x, V, sv, si);
+    else tok = sample_block(x, V, etab, s, has_u, pos_or_u, sh);
+    if (threadIdx.x == 0) {
+        if (end.info) *end.info = sh.z;
+        if (!end.advance) *end.token_word = tok;
+        else step_advance(end.st, tok, end.token_word, nullptr, end.out_tokens, end.out_cap);
+    }
+}
+// the same for the batch: block s = sequence s's logits row, sampler s, its context's position
+__global__ __launch_bounds__(1024) void batch_sample_kernel(const uint16_t* logits, int V, const double* etab, const LnbSampler* smp, const BatchTab* tab) {
+    __shared__ float sv[1024];
+    __shared__ int si[1024];
+    __shared__ SampleSh sh;
+    __shared__ SampleEnd end;
+    const int q = blockIdx.x;
+    const LnbSampler s = smp[q];
+    const uint16_t* x = logits + (size_t)q * V;
+    const unsigned long long pos = (unsigned long long)(long long)tab->st[q]->pos;
+    if (threadIdx.x == 0) { end.st = tab->st[q]; end.token_word = tab->dtok[q]; end.out_tokens = tab->dout[q]; end.out_cap = tab->dout_cap[q]; }
+    const int tok = s.temperature == 0.0f ? argmax_block(x, V, sv, si) : sample_block(x, V, etab, s, false, pos, sh);
+    if (threadIdx.x == 0) step_advance(end.st, tok, end.token_word, nullptr, end.out_tokens, end.out_cap);
 }
 
 // ---- speculative greedy decoding (lnb_decode_speculative_until, include/lnb.h) ----------------------------------------------------------
@@ -4981,6 +5279,20 @@ extern "C" hipError_t lnbk_embed(const uint16_t* emb, const int32_t* tokens, uin
 extern "C" hipError_t lnbk_argmax(const uint16_t* logits, int V, int32_t* next_token, StepState* state, int32_t* out_tokens,
                                   int out_cap, int advance, hipStream_t st) {
     hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(1024), 0, st, logits, V, next_token, state, out_tokens, out_cap, advance);
+    return hipGetLastError();
+}
+// the decode step's sampler launch (advance = 1, one row, smp[0]) or rows of lnb_op_sample (advance = 0: next_token[rows], pos[rows], draws / info optional)
+extern "C" hipError_t lnbk_sample(const uint16_t* logits, int V, int rows, const double* etab, const LnbSampler* smp, int32_t* next_token, StepState* state,
+                                  int32_t* out_tokens, int out_cap, int advance, const int32_t* pos, const unsigned long long* draws, LnbSampleInfo* info, hipStream_t st) {
+    if (V < 1 || V > LNB_SAMPLE_MAX_V || rows < 1 || (advance && rows != 1)) return hipErrorInvalidValue;
+    form_ran(Form::SAMPLE_ROW);
+    hipLaunchKernelGGL(sample_kernel, dim3(rows), dim3(1024), 0, st, logits, V, etab, smp, next_token, state, out_tokens, out_cap, advance, pos, draws, info);
+    return hipGetLastError();
+}
+extern "C" hipError_t lnbk_batch_sample(const uint16_t* logits, int V, const double* etab, const LnbSampler* smp, const BatchTab* tab, int nseq, hipStream_t st) {
+    if (V < 1 || V > LNB_SAMPLE_MAX_V) return hipErrorInvalidValue;
+    form_ran(Form::SAMPLE_BATCH);
+    hipLaunchKernelGGL(batch_sample_kernel, dim3(nseq), dim3(1024), 0, st, logits, V, etab, smp, tab);
     return hipGetLastError();
 }
 extern "C" hipError_t lnbk_set_state(StepState* state, int pos, int n_out, int honour_stop, hipStream_t st) {

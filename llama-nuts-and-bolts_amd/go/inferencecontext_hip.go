@@ -243,6 +243,35 @@ func (ic *InferenceContext) DecodeGreedyUntil(lt *LlamaTransformer, token TokenI
 	return out[:int(n)], fin != 0, nil
 }
 
+// Sampler mirrors lnb_sampler (include/lnb.h): Temperature 0 = greedy, TopK 0 = off, TopP 1 = off.  The sampled token is a function of the
+// step's logits row, these four numbers and the position alone.
+type Sampler struct {
+	Temperature float32
+	TopK        int
+	TopP        float32
+	Seed        uint64
+}
+
+// DecodeSampleUntil is DecodeGreedyUntil with the sampler's token in place of the argmax: the same stop ids, finished flag and chunking
+// independence; the tokens are those of the rule in include/lnb.h, bit for bit the CPU restatement's.
+func (ic *InferenceContext) DecodeSampleUntil(lt *LlamaTransformer, s Sampler, token TokenId, startPos int, maxSteps int) (tokens []TokenId, finished bool, err error) {
+	if maxSteps <= 0 { // &out[0] of an empty slice panics before the library can refuse the call
+		return nil, false, fmt.Errorf("n_steps must be positive")
+	}
+	if err = ic.attach(lt); err != nil {
+		return nil, false, err
+	}
+	out := make([]TokenId, maxSteps)
+	var n, fin C.int
+	cs := C.lnb_sampler{temperature: C.float(s.Temperature), top_p: C.float(s.TopP), top_k: C.int32_t(s.TopK), reserved: 0, seed: C.uint64_t(s.Seed)}
+	if err = lnbCall(func() C.int {
+		return C.lnb_decode_sample_until(ic.handle, &cs, C.int32_t(token), C.int(startPos), C.int(maxSteps), (*C.int32_t)(unsafe.Pointer(&out[0])), &n, &fin, nil)
+	}); err != nil {
+		return nil, false, err
+	}
+	return out[:int(n)], fin != 0, nil
+}
+
 // SpecStats mirrors lnb_spec_stats: passes, passes that verified a draft, draft tokens verified, draft tokens emitted.
 type SpecStats struct{ Passes, VerifyPasses, Drafted, Accepted int64 }
 

@@ -229,6 +229,16 @@ public:
         s.TargetLogit.resize(tokens.size()); s.TargetProb.resize(tokens.size()); s.LogZ.resize(tokens.size());
         return s;
     }
+    // lnb_decode_sample_until: lnb_decode_greedy_until with the sampler's token (temperature / top-k / top-p / seed; include/lnb.h) in place of the argmax
+    // -> the tokens generated; *finished (optional) = a stop id ended the run
+    std::vector<TokenId> DecodeSampleUntil(const lnb_sampler& sampler, TokenId token, int startPos, int maxSteps, bool* finished = nullptr) {
+        std::vector<TokenId> out((size_t)(maxSteps > 0 ? maxSteps : 0));
+        int n = 0, fin = 0;
+        check(lnb_decode_sample_until(h_, &sampler, token, startPos, maxSteps, out.data(), &n, &fin, nullptr));
+        out.resize((size_t)n);
+        if (finished) *finished = fin != 0;
+        return out;
+    }
     // speculative greedy decoding (include/lnb.h): n-gram drafts (maxDraft 0..LNB_MAX_DRAFT, 0 = off) verified in batched passes -- the tokens
     // and KV rows of lnb_decode_greedy_until; history = the tokens before `token` (the prompt)
     void SetDraft(int maxDraft, int ngramMin, int ngramMax, const std::vector<TokenId>& corpus = {}) {

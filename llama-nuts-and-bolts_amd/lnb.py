@@ -65,6 +65,7 @@ EXPORTS = [
     "lnb_abi_version", "lnb_runtime_info", "lnb_profile_ffn_pair",
     "lnb_model_wpack_bytes", "lnb_model_wpack_info", "lnb_op_rmsnorm_gate_up",
     "lnb_ctx_set_token_probs", "lnb_ctx_read_token_probs", "lnb_ctx_token_prob_walks", "lnb_forward_score", "lnb_op_token_probs",
+    "lnb_decode_sample_until", "lnb_batch_decode_sample_until", "lnb_op_sample", "lnb_profile_sample",
     "lnb_forward_append", "lnb_forward_score_append",
     "lnb_ctx_set_draft", "lnb_decode_speculative_until", "lnb_op_ngram_draft",
     "lnb_batch_set_attention", "lnb_ctx_set_batched_attention", "lnb_batch_attention_form", "lnb_ctx_verify_attention_form",
@@ -97,6 +98,35 @@ class SpecManyInfo(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class Sampler(C.Structure):
+    """lnb_sampler (include/lnb.h): temperature 0 = greedy, top_k 0 = off, top_p 1 = off; the token is a function of the logits row, these four numbers and the position"""
+    _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+    def __init__(self, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+        super().__init__(float(temperature), float(top_p), int(top_k), 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+class SampleInfo(C.Structure):
+    """lnb_sample_info (include/lnb.h)"""
+    _fields_ = [("w_all", C.c_uint64), ("w_topk", C.c_uint64), ("w_kept", C.c_uint64), ("n_candidates", C.c_int32), ("n_kept", C.c_int32), ("degenerate", C.c_int32),
+                ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "pad"}
+
+
+def _samplers(samplers, n):
+    """n lnb_sampler structs from Sampler objects or (temperature, top_k, top_p, seed) tuples"""
+    ss = list(samplers)
+    if len(ss) != n:
+        raise LnbError("%d samplers for %d rows" % (len(ss), n))
+    arr = (Sampler * n)()
+    for i, s in enumerate(ss):
+        s = s if isinstance(s, Sampler) else Sampler(*s)
+        arr[i] = s
+    return arr
 
 
 class RuntimeInfo(C.Structure):
@@ -221,6 +251,10 @@ def lib():
     L.lnb_forward_score.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, i32p]
     L.lnb_forward_append.argtypes = [vp, vp, C.c_int, C.c_int, vp, i32p]
     L.lnb_forward_score_append.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, i32p]
+    L.lnb_decode_sample_until.argtypes = [vp, C.POINTER(Sampler), C.c_int32, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), f32p]
+    L.lnb_batch_decode_sample_until.argtypes = [vp, C.POINTER(Sampler), i32p, i32p, C.c_int, vp, vp, vp, f32p]
+    L.lnb_op_sample.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), vp, vp, vp, C.POINTER(SampleInfo)]
+    L.lnb_profile_sample.argtypes = [vp, C.POINTER(Sampler), C.c_int, C.c_int, f32p]
     L.lnb_op_token_probs.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.lnb_ctx_set_draft.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int]
     L.lnb_decode_speculative_until.argtypes = [vp, vp, C.c_int, C.c_int32, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -462,6 +496,7 @@ class LlamaTransformer:
         self.args = ModelArgs(**d)
         self.L = lib()
         self.h = C.c_void_p()
+        self.device = int(device)
         if part_begin is None and part_end is None:
             part_begin, part_end = 3 * layer_begin, 3 * (self.args.n_layers if layer_end is None else layer_end)
         self.part_begin, self.part_end = int(part_begin), int(part_end)
@@ -650,6 +685,21 @@ class InferenceContext:
         ms, n, fin = C.c_float(0), C.c_int(0), C.c_int(0)
         _chk(self.L.lnb_decode_greedy_until(self.h, int(token), start_pos, max_steps, _p(out), C.byref(n), C.byref(fin), C.byref(ms)))
         return out[:n.value].copy(), bool(fin.value), ms.value
+
+    def decode_sample_until(self, sampler, token, start_pos, max_steps):
+        """decode_greedy_until with the sampler's token in place of the argmax (lnb_decode_sample_until): sampler = a Sampler or (temperature, top_k, top_p, seed)
+        -> (tokens generated, finished flag, device ms)"""
+        s = _samplers([sampler], 1)
+        out = np.empty(max(int(max_steps), 0), dtype=np.int32)
+        ms, n, fin = C.c_float(0), C.c_int(0), C.c_int(0)
+        _chk(self.L.lnb_decode_sample_until(self.h, s, int(token), start_pos, max_steps, _p(out), C.byref(n), C.byref(fin), C.byref(ms)))
+        return out[:n.value].copy(), bool(fin.value), ms.value
+
+    def profile_sample(self, sampler, pos, iters):
+        """average device ms of the step's token launch alone: sample_kernel with this sampler, argmax_kernel with None (lnb_profile_sample)"""
+        ms = C.c_float(0)
+        _chk(self.L.lnb_profile_sample(self.h, None if sampler is None else _samplers([sampler], 1), pos, iters, C.byref(ms)))
+        return ms.value
 
     def set_token_probs(self, k):
         """record the top k token probabilities (0..MAX_TOP_K; 0 = off, the default) of every token the greedy loops generate (include/lnb.h)"""
@@ -868,6 +918,20 @@ class Batch:
         self.finished = [bool(f) for f in fin]               # per sequence: a stop id ended it (start_pos[s] < 0 keeps an ended sequence frozen in the next chunk)
         return [out[s, :cnt[s]].copy() for s in range(n)], ms.value
 
+    def decode_sample_until(self, samplers, tokens, start_pos, max_steps):
+        """decode_until with one sampler per member (lnb_batch_decode_sample_until; a temperature-0 member is greedy): -> (per-sequence token arrays, device ms)"""
+        n = len(self.ctxs)
+        ss = _samplers(samplers, n)
+        tok = np.ascontiguousarray(tokens, dtype=np.int32); pos = np.ascontiguousarray(start_pos, dtype=np.int32)
+        assert tok.size == n and pos.size == n
+        out = np.empty((n, max(int(max_steps), 0)), dtype=np.int32)
+        cnt = np.zeros(n, dtype=np.int32); fin = np.zeros(n, dtype=np.int32)
+        ms = C.c_float(0)
+        _chk(self.L.lnb_batch_decode_sample_until(self.h, ss, tok.ctypes.data_as(C.POINTER(C.c_int32)), pos.ctypes.data_as(C.POINTER(C.c_int32)), max_steps, _p(out), _p(cnt),
+                                                  _p(fin), C.byref(ms)))
+        self.finished = [bool(f) for f in fin]
+        return [out[s, :cnt[s]].copy() for s in range(n)], ms.value
+
     def profile_kernel(self, which, pos, iters):
         ms = C.c_float(0)
         _chk(self.L.lnb_batch_profile_kernel(self.h, which, pos, iters, C.byref(ms)))
@@ -975,11 +1039,12 @@ class InferenceEngine:
     long_context: the generation's context is a long one (lnb_ctx_create_long, up to MAX_SEQ_LEN positions) whose activation buffers hold
     prefill_chunk rows, or the prompt when the chunk is 0."""
 
-    def __init__(self, transformer, seq_len, stop_token_ids=(), prefill_chunk=0, long_context=False):
+    def __init__(self, transformer, seq_len, stop_token_ids=(), prefill_chunk=0, long_context=False, sampler=None):
         if int(prefill_chunk) < 0:
             raise LnbError("prefill_chunk must be 0 (one Forward) or a positive row count")
         self.t, self.seq_len, self.stop, self.prefill_chunk = transformer, seq_len, set(stop_token_ids), int(prefill_chunk)
         self.long_context = bool(long_context)
+        self.sampler = sampler                               # None: greedy.  A Sampler (or its tuple): EVERY generated token is sampled, the prompt's own next token included
 
     def GenerateTokens(self, prompt_tokens, max_new=None):
         prompt = list(prompt_tokens)
@@ -996,9 +1061,20 @@ class InferenceEngine:
                     _, first = ctx.ForwardAppend(prompt[p0:p0 + self.prefill_chunk], p0, want_logits=False)
             else:
                 _, first = ctx.Forward(prompt, 0, want_logits=False)
+            if self.sampler is not None:
+                # the prompt's next token by the same rule, at the position of the row's input token: the last prompt row once more as a one-token step
+                # (the same bits into the same KV row) for its logits, then sample_kernel on that row
+                row, _ = ctx.ForwardAppend(prompt[-1:], len(prompt) - 1, want_logits=True)
+                row16 = (np.ascontiguousarray(row[0], dtype=np.float32).view(np.uint32) >> 16).astype(np.uint16)
+                first = int(op_sample(row16, [self.sampler], [len(prompt) - 1], want_info=False, device=self.t.device)[0][0])
+                if first < 0:
+                    raise LnbError("the prompt's last logits row has no candidate to sample (all NaN or -inf)")
             out = [first]
             if first not in self.stop and n_new > 1:
-                more, _ = ctx.decode_greedy(first, len(prompt), n_new - 1)
+                if self.sampler is None:
+                    more, _ = ctx.decode_greedy(first, len(prompt), n_new - 1)
+                else:
+                    more, _, _ = ctx.decode_sample_until(self.sampler, first, len(prompt), n_new - 1)
                 for t in more:
                     out.append(int(t))
                     if int(t) in self.stop:
@@ -1045,6 +1121,24 @@ def op_argmax(logits_u16, device=0):
     out = C.c_int32(-2)
     _chk(lib().lnb_op_argmax(device, _p(a), a.size, C.byref(out)))
     return out.value
+
+
+def op_sample(logits_u16, samplers, pos, draws=None, want_info=True, device=0):
+    """sample_kernel on rows of bf16 logits [rows, V] (lnb_op_sample): row i with samplers[i] at position pos[i], or with u = draws[i] given instead of derived
+    -> (tokens int32 [rows], list of info dicts or None)"""
+    a = np.ascontiguousarray(logits_u16, dtype=np.uint16)
+    if a.ndim == 1:
+        a = a[None, :]
+    rows, V = a.shape
+    ss = _samplers(samplers, rows)
+    p = np.ascontiguousarray(pos, dtype=np.int32)
+    u = None if draws is None else np.array([int(d) & 0xFFFFFFFFFFFFFFFF for d in draws], dtype=np.uint64)
+    if p.size != rows or (u is not None and u.size != rows):
+        raise LnbError("%d rows, %d positions%s" % (rows, p.size, "" if u is None else ", %d draws" % u.size))
+    tok = np.full(rows, -2, dtype=np.int32)
+    info = (SampleInfo * rows)() if want_info else None
+    _chk(lib().lnb_op_sample(device, _p(a), rows, V, ss, _p(p), None if u is None else _p(u), _p(tok), info))
+    return tok, ([i.as_dict() for i in info] if want_info else None)
 
 
 def op_token_probs(logits_u16, top_k, targets=None, force_serial=False, device=0):

@@ -183,7 +183,9 @@ def main(asm_path=None):
     # scratch memory and VGPR spills: never.  SGPR spills into VGPR lanes (v_writelane, no memory): tolerated for the kernels listed here only --
     # attn_gqa_kernel inlines the f64 exp (two dozen SGPRs of polynomial constants) and saves 18 scalars in one VGPR around it
     # (round 6: attn_one_kernel inlines the same exp beside its in-launch exchange: 30 scalars parked in VGPR lanes; it is the opt-in one-launch form)
-    SGPR_SPILL_OK = ("attn_gqa_kernel", "attn_one_kernel")
+    # (sample_kernel / batch_sample_kernel: the bisection loop's eight-wide weight arithmetic fills the scalar file; 18 / 11 loop-invariant scalars wait in the lanes
+    # of one VGPR around it.  Their scratch size is 0 and their vgpr_spill_count is 0, which the line above still requires.)
+    SGPR_SPILL_OK = ("attn_gqa_kernel", "attn_one_kernel", "_Z13sample_kernelP", "_Z19batch_sample_kernelP")      # (the last two: these two kernels and no other *sample_kernel)
     spills, cur = [], ""
     for l in txt:
         mname = re.search(r"\.name:\s+(\S+)", l)
