@@ -2548,8 +2548,11 @@ constexpr int ATT_VU = ATT_JC / 4 / ATT_NPROD;              // 4-row units per p
 // than a load round trip, so three chunks are kept in flight; hipcc drains vmcnt(0) around loop-carried register prefetch,
 // hence the same hand-counted asm ring as the GEMV (RING_LOAD / RING_RETIRE, checked by tools/isa_audit.py).
 // Always issued (rows clamped to T-1, whose p is +0 beyond the row) so that the count is the same on every path.
-DEVINL void attn_load_v(u32x4 (&v)[ATT_VU], const uint16_t* vbase, uint32_t row_bytes, int c, int pwv, int lane, int T) {
-    const uint32_t dq = (uint32_t)(lane & 15) * 16u;                      // byte offset of this lane's 8 dims
+template <int HD> DEVINL void attn_load_v(u32x4 (&v)[ATT_VU], const uint16_t* vbase, uint32_t row_bytes, int c, int pwv, int lane, int T) {
+    // byte offset of this lane's 8 dims.  With heads of 64 or 32 dims the lanes past the head (their loads are never used) stay INSIDE it: 16 bytes per lane
+    // over sixteen lanes are 256 bytes, and from the last KV head of row seq_len - 1 that ran up to 192 bytes past the end of the V cache -- a fault when the
+    // cache ends on a page boundary (tests/test_gpu_op_crafted.py: one row at position 127 of a 128-position context, two KV heads of 64)
+    const uint32_t dq = (HD >= 128 || (lane & 15) * 8 < HD) ? (uint32_t)(lane & 15) * 16u : 0u;
 #pragma unroll
     for (int u = 0; u < ATT_VU; u++) {
         int j = c * ATT_JC + (pwv * 4 + (lane >> 4)) * 4 + u;
@@ -2602,7 +2605,7 @@ template <int HD> DEVINL int attn_row_dim(int r) { return (r % (HD / 8)) * 8 + r
 template <int HD, int D = 3> DEVINL void attn_pv_produce(int c, int nchunks, int pwv, int lane, int T, const uint16_t* vbase, uint32_t row_bytes,
                                               const float* pw, char* ring, u32x4 (&vc)[ATT_VU], u32x4 (&vn)[ATT_VU]) {
     constexpr int SLOT = ATT_RP * HD * 4;
-    attn_load_v(vn, vbase, row_bytes, c + D, pwv, lane, T);
+    attn_load_v<HD>(vn, vbase, row_bytes, c + D, pwv, lane, T);
     attn_retire_v<D * ATT_VU>(vc);                           // chunks c+1 .. c+D stay in flight
     if (c < nchunks && (lane & 15) * 8 < HD) {
         const int pg = pwv * 4 + (lane >> 4);                // positions 4 pg .. 4 pg + 3 of the chunk
@@ -2772,12 +2775,12 @@ template <int HD, bool DENSE = false, bool CAUSAL = false> __global__ __launch_b
     constexpr int VD = DENSE ? 3 : 7;
     u32x4 v0[ATT_VU], v1[ATT_VU], v2[ATT_VU], v3[ATT_VU], v4[ATT_VU], v5[ATT_VU], v6[ATT_VU], v7[ATT_VU];
     if (producer) {
-        attn_load_v(v0, vbase, row_bytes, 0, pwv, lane, T);
-        attn_load_v(v1, vbase, row_bytes, 1, pwv, lane, T);
-        attn_load_v(v2, vbase, row_bytes, 2, pwv, lane, T);
+        attn_load_v<HD>(v0, vbase, row_bytes, 0, pwv, lane, T);
+        attn_load_v<HD>(v1, vbase, row_bytes, 1, pwv, lane, T);
+        attn_load_v<HD>(v2, vbase, row_bytes, 2, pwv, lane, T);
         if constexpr (VD == 7) {
-            attn_load_v(v3, vbase, row_bytes, 3, pwv, lane, T); attn_load_v(v4, vbase, row_bytes, 4, pwv, lane, T);
-            attn_load_v(v5, vbase, row_bytes, 5, pwv, lane, T); attn_load_v(v6, vbase, row_bytes, 6, pwv, lane, T);
+            attn_load_v<HD>(v3, vbase, row_bytes, 3, pwv, lane, T); attn_load_v<HD>(v4, vbase, row_bytes, 4, pwv, lane, T);
+            attn_load_v<HD>(v5, vbase, row_bytes, 5, pwv, lane, T); attn_load_v<HD>(v6, vbase, row_bytes, 6, pwv, lane, T);
         }
     }
     ATT_STAMP(2);
