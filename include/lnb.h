@@ -484,6 +484,15 @@ int64_t lnb_model_batch_bytes(lnb_model* m);
  * Bind every tensor before lnb_model_finalize: a gate|up tensor bound afterwards is re-packed in place if it fits the copy's window, else the call fails. */
 int64_t lnb_model_wpack_bytes(lnb_model* m);
 int lnb_model_wpack_info(lnb_model* m, int32_t* counts6);
+/* The LM head has a copy of the same format (unless LNB_HEAD_PACKED=0), cut into 128-row blocks that the one-token head walks as two chains per lane.  It is
+ * built when the head's resident layout is the 64-row one, a row fits the kernel's 128-step stages (dim 8192 does not) and the vocabulary gives every CU a
+ * 128-row block.  The two queries above count gate|up matrices only; the head reports here:
+ *   lnb_model_wpack_head_bytes    device bytes of the head's copy (13/16 of the matrix for whole blocks and stages; 0: none)
+ *   lnb_model_wpack_head_status   0 the one-token head streams its copy; 1 subnormal / exponent 1, 2 Inf / NaN, 3 out of window, 4 no memory; 5 never tried
+ *                                 (knob off at finalize, a stage without output.weight, a shape without a packed form); -1 null argument
+ * output.weight bound after lnb_model_finalize is re-packed in place if it fits the copy's window, else the call fails and the head streams the raw weights. */
+int64_t lnb_model_wpack_head_bytes(lnb_model* m);
+int lnb_model_wpack_head_status(lnb_model* m);
 int lnb_batch_create(lnb_ctx* const* ctxs, int n, lnb_batch** out);
 int lnb_batch_destroy(lnb_batch* b);
 int lnb_batch_decode(lnb_batch* b, const int32_t* tokens, const int32_t* start_pos, int n_steps, int32_t* out_tokens, float* ms_out);
@@ -669,6 +678,11 @@ int lnb_op_rmsnorm_linear(int device, const uint16_t* x, const uint16_t* norm_w,
  * 2 Inf / NaN, 3 out of window -- a refused matrix runs the raw kernel */
 int lnb_op_rmsnorm_gate_up(int device, const uint16_t* x, const uint16_t* norm_w, float eps, const uint16_t* w1, const uint16_t* w3, uint16_t* y,
                            int n_out, int k_in, int packed, int* status);
+/* the fused final norm + output projection launch of a one-token step on one row x[k_in] -> y[n_out] (llamatransformer.go:166-170), w = [n_out][k_in].
+ * packed 0: the raw 64-row kernel; 1: from the 13-bit copy in 128-row blocks when the matrix is packable.  n_wg > 0 caps the workgroups, so that a small
+ * matrix still walks several blocks per workgroup (0: no cap).  *status as above */
+int lnb_op_rmsnorm_head(int device, const uint16_t* x, const uint16_t* norm_w, float eps, const uint16_t* w, uint16_t* y,
+                        int n_out, int k_in, int packed, int n_wg, int* status);
 
 /* either operator in a given arithmetic mode (norm_w == NULL: plain linear); LNB_MODE_FAST runs the split-K kernels */
 int lnb_op_linear_mode(int device, const uint16_t* x, const uint16_t* norm_w, float eps, const uint16_t* w, uint16_t* y,

@@ -67,6 +67,10 @@ hipError_t lnbk_gemv_w13p(const GemvParams* p, hipStream_t st);
 size_t lnbk_wpack_w13_bytes(int n_blocks, int K);
 hipError_t lnbk_wpack_stats(const uint16_t* w, size_t elems, unsigned* d_stats, hipStream_t st);
 hipError_t lnbk_wpack_w13(const uint16_t* w, void* out, int K, int n_blocks, unsigned base, hipStream_t st);
+int lnbk_headp_supported(int K);
+hipError_t lnbk_gemv_headp(const GemvParams* p, hipStream_t st);
+size_t lnbk_wpack_head_bytes(int N, int K);
+hipError_t lnbk_wpack_head(const uint16_t* w, void* out, int N, int K, unsigned base, hipStream_t st);
 hipError_t lnbk_fast_gemv(const GemvParams* p, int rw, int nch, int epi, int norm, hipStream_t st);
 hipError_t lnbk_fast_gemm(const GemmParams* p, int epi, hipStream_t st);
 hipError_t lnbk_fast_attn(const AttnParams* p, hipStream_t st);
@@ -170,6 +174,8 @@ struct lnb_model {
     int64_t weight_bytes = 0;
     bool batch_enabled = false; uint16_t* m_output = nullptr; int64_t batch_bytes = 0;
     int64_t wpack_bytes = 0;              // the 13-bit planar copies of the gate|up matrices (lnb_model_wpack_bytes)
+    // the LM head's 13-bit copy (lnb_model_finalize, LNB_HEAD_PACKED; 128-row two-chain blocks: lnb_wpack.h), as LayerW's p_* fields are for gate|up
+    void* p_out = nullptr; unsigned p_out_base = 0; bool p_out_ok = false; int p_out_status = -1; int64_t wpack_head_bytes = 0;
     std::mutex am_mu; struct AppendMany* am = nullptr;     // lnb_forward_append_many: the call's buffers and tables, created on first use; the mutex is held for a whole call
     bool first() const { return part_begin == 0; }
     bool last() const { return part_end == 3 * a.n_layers; }
@@ -523,7 +529,7 @@ extern "C" int lnb_model_destroy(lnb_model* m) {
         hipFree(L.attn_norm); hipFree(L.ffn_norm); hipFree(L.wqkv.w); hipFree(L.wo.w); hipFree(L.w13.w); hipFree(L.w2.w);
         hipFree(L.m_wqkv); hipFree(L.m_wo); hipFree(L.m_w13); hipFree(L.m_w2); hipFree(L.p_w13);
     }
-    hipFree(m->m_output);
+    hipFree(m->m_output); hipFree(m->p_out);
     if (m->cis) hipFree(m->cis);
     if (m->silu) hipFree(m->silu);
     if (m->exp_tab) hipFree(m->exp_tab);
@@ -599,6 +605,67 @@ static int wpack_refresh(lnb_model* m, const TiledDesc* t) {
     hipFree(d_stats);
     return rc;
 }
+// ---- the LM head's copy: the same format cut into 128-row two-chain blocks (lnb_wpack.h; lnbk_gemv_headp) ----
+// The head has a packed form when its resident layout is the 64-row one, the row fits the 128-step stages (K = 8192 does not) and the vocabulary gives every
+// CU at least one 128-row block: below that the launch is a few microseconds and the copy buys nothing.
+static bool head_pack_applies(const lnb_model* m) {
+    return m->last() && m->output.w && m->output.rw == 64 && m->output.nch == 1 && lnbk_headp_supported(m->output.k) && m->output.n_rows >= 128 * g_num_cus;
+}
+// lnb_model_finalize: build the copy if the head has none that is valid; a refusal keeps the raw kernel and records why (lnb_model_wpack_head_status)
+static int wpack_head_build(lnb_model* m) {
+    if (m->p_out_ok || !head_pack_applies(m)) return 0;
+    const TiledDesc& t = m->output;
+    unsigned* d_stats = nullptr; unsigned base = 0;
+    HIPCHK(hipMalloc((void**)&d_stats, sizeof(WpackStats)));
+    const int why = wpack_matrix_window(m, t, d_stats, &base);
+    hipFree(d_stats);
+    if (why < 0) return -1;
+    m->p_out_status = why;
+    if (why != WPACK_OK) return 0;
+    const size_t n = lnbk_wpack_head_bytes(t.n_rows, t.k);
+    if (!m->p_out) {
+        if (hipMalloc(&m->p_out, n) != hipSuccess) { (void)hipGetLastError(); m->p_out = nullptr; m->p_out_status = WPACK_NOMEM; return 0; }      // the head runs raw and reports it
+        m->wpack_head_bytes = (int64_t)n;
+    }
+    hipError_t e = lnbk_wpack_head(t.w, m->p_out, t.n_rows, t.k, base, m->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+    if (e != hipSuccess) return fail("packing the LM head failed: %s", hipGetErrorString(e));
+    m->p_out_base = base; m->p_out_ok = true;
+    return 0;
+}
+// output.weight was rewritten after its copy was built: as wpack_refresh -- rebuilt in place inside the copy's window, or back to the raw kernel and an error
+static int wpack_head_refresh(lnb_model* m) {
+    if (!m->p_out_ok) return 0;
+    m->p_out_ok = false;
+    unsigned* d_stats = nullptr;
+    if (hipMalloc((void**)&d_stats, sizeof(WpackStats)) != hipSuccess) { (void)hipGetLastError(); return fail("out of memory"); }
+    const TiledDesc& t = m->output;
+    WpackStats s;
+    hipError_t e = lnbk_wpack_stats(t.w, tiled_elems(t.n_rows, t.k, t.rw, t.nch), d_stats, m->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&s, d_stats, sizeof s, hipMemcpyDeviceToHost, m->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+    hipFree(d_stats);
+    HIPCHK(e);
+    unsigned base = 0;
+    const int why = wpack_window(&s, &base);
+    const bool fits = why == WPACK_OK && (s.max_e2 == 0 || (s.min_e2 > m->p_out_base && s.max_e2 <= m->p_out_base + 15));
+    if (!fits) {
+        m->p_out_status = why != WPACK_OK ? why : WPACK_WINDOW;
+        return fail("the output.weight bound after lnb_model_finalize does not fit the window of the LM head's 13-bit copy; the head decodes from the raw weights "
+                    "from now on (a decode step captured before keeps the old copy: bind every tensor before lnb_model_finalize)");
+    }
+    HIPCHK(lnbk_wpack_head(t.w, m->p_out, t.n_rows, t.k, m->p_out_base, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    m->p_out_ok = true; m->p_out_status = WPACK_OK;
+    return 0;
+}
+extern "C" int64_t lnb_model_wpack_head_bytes(lnb_model* m) { return m ? m->wpack_head_bytes : 0; }
+// 0: the one-token head streams its 13-bit copy; WPACK_SUBNORMAL .. WPACK_NOMEM (1..4): refused for that reason; 5: never tried (LNB_HEAD_PACKED=0 at
+// lnb_model_finalize, a stage without output.weight, or a shape the packed head has no form for); -1: null argument
+extern "C" int lnb_model_wpack_head_status(lnb_model* m) {
+    if (!m) return fail("null argument");
+    return m->p_out_ok ? 0 : (m->p_out_status > 0 && m->p_out_status <= WPACK_NOMEM) ? m->p_out_status : 5;
+}
 extern "C" int64_t lnb_model_wpack_bytes(lnb_model* m) { return m ? m->wpack_bytes : 0; }
 // counts[0] = gate|up matrices decoding from their 13-bit copy, counts[WPACK_SUBNORMAL / WPACK_INFNAN / WPACK_WINDOW / WPACK_NOMEM] = matrices refused for that
 // reason, counts[5] = matrices never tried (LNB_W13_PACKED=0 at lnb_model_finalize, or a layout the packed kernel has no form for)
@@ -633,6 +700,7 @@ extern "C" int lnb_model_set_tensor(lnb_model* m, const char* name, const uint16
     hipFree(stage);
     HIPCHK(e);
     if (wpack_refresh(m, r.td)) return -1;
+    if (r.td == &m->output && wpack_head_refresh(m)) return -1;
     return 0;
 }
 
@@ -678,6 +746,7 @@ extern "C" int lnb_model_fill_synthetic(lnb_model* m, uint64_t seed) {
     }
     HIPCHK(hipStreamSynchronize(m->stream));
     if (wpack_refresh(m, nullptr)) return -1;
+    if (wpack_head_refresh(m)) return -1;
     return 0;
 }
 
@@ -747,6 +816,7 @@ extern "C" int lnb_model_finalize(lnb_model* m, int rope_rows) {
     HIPCHK(lnbk_exp_table(m->exp_tab, bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim))), m->stream));   // (attn_mfma_kernel)
     HIPCHK(hipStreamSynchronize(m->stream));
     if (knob(Knob::W13_PACKED) && wpack_build(m)) return -1;
+    if (knob(Knob::HEAD_PACKED) && wpack_head_build(m)) return -1;
     m->finalized = true;
     return 0;
 }
@@ -1294,6 +1364,14 @@ static int enqueue_head(lnb_ctx* c, int first, int rows) {
     GemvParams g{}; g.w = m->output.w; g.x = c->x + (size_t)first * m->a.dim; g.norm_w = m->norm; g.norm_fb = c->zseq_count + 1; g.eps = m->a.norm_eps; g.K = m->a.dim;
     g.n_rows = m->a.vocab_size; g.S = rows; g.st = c->st; g.out = c->logits;
     set_grid(g, m->output);
+    // one token, latency schedule, exact mode, and the head has its 13-bit copy (head_pack_applies: 64-row resident layout, K fits, a 128-row block per CU):
+    // the same chains, two per lane, fed from 13/16 of the bytes
+    if (rows == 1 && m->p_out_ok && c->mode == LNB_MODE_EXACT && c->sched == LNB_SCHED_LATENCY) {
+        g.wp = m->p_out; g.wp_base4 = m->p_out_base * 0x01010101u;
+        g.n_blocks = (m->a.vocab_size + 127) / 128; g.n_wg = g.n_blocks < g_num_cus ? g.n_blocks : g_num_cus;
+        HIPCHK(lnbk_gemv_headp(&g, c->stream));
+        return 0;
+    }
     HIPCHK(gemv_dispatch(c, &g, m->output.rw, 1, EPI_STORE, 1, c->stream));
     return 0;
 }
@@ -3661,6 +3739,52 @@ extern "C" int lnb_op_rmsnorm_gate_up(int device, const uint16_t* x, const uint1
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(y, dy, (size_t)n_out * 2, hipMemcpyDeviceToHost));
     hipFree(dx); hipFree(dw); hipFree(dy); hipFree(dn); hipFree(st); hipFree(dsilu); hipFree(dstats); hipFree(t.w); if (wp) hipFree(wp);
+    return 0;
+}
+// The fused final norm + output projection launch of a one-token step on its own: y[n_out] from one row x, w = [n_out][k_in] row-major.  packed = 0: the raw
+// 64-row kernel; 1: from the 13-bit copy in 128-row blocks when the matrix is packable.  n_wg > 0 caps the workgroups (a small matrix then still walks several
+// blocks per workgroup); 0: one per block up to the CU count.  *status = WPACK_* of the matrix (WPACK_OK: the packed kernel ran when asked for).
+extern "C" int lnb_op_rmsnorm_head(int device, const uint16_t* x, const uint16_t* norm_w, float eps, const uint16_t* w, uint16_t* y,
+                                   int n_out, int k_in, int packed, int n_wg, int* status) {
+    if (!x || !norm_w || !w || !y) return fail("null argument");
+    if (n_out <= 0 || k_in <= 0) return fail("empty operand");
+    if (k_in % 8) return fail("in_features must be a multiple of 8");
+    if (n_wg < 0) return fail("n_wg must not be negative");
+    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
+    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(lnbk_init());
+    if (!lnbk_headp_supported(k_in)) return fail("in_features %d does not fit the LDS staging of the packed LM-head kernel", k_in);
+    TiledDesc t{}; int64_t bytes = 0;
+    if (alloc_tiled(t, n_out, k_in, 64, 1, bytes)) return -1;
+    const size_t wn = (size_t)n_out * k_in * 2;
+    uint16_t *dx = nullptr, *dw = nullptr, *dy = nullptr, *dn = nullptr; StepState* st = nullptr; unsigned* dstats = nullptr; void* wp = nullptr;
+    HIPCHK(hipMalloc((void**)&dx, (size_t)k_in * 2)); HIPCHK(hipMalloc((void**)&dw, wn)); HIPCHK(hipMalloc((void**)&dn, (size_t)k_in * 2));
+    HIPCHK(hipMalloc((void**)&dy, (size_t)n_out * 2)); HIPCHK(hipMalloc((void**)&st, sizeof(StepState))); HIPCHK(hipMalloc((void**)&dstats, sizeof(WpackStats)));
+    HIPCHK(hipMemset(st, 0, sizeof(StepState))); HIPCHK(hipMemset(dy, 0xFF, (size_t)n_out * 2));        // (a row the kernel does not write reads back as a NaN pattern)
+    HIPCHK(hipMemcpy(dx, x, (size_t)k_in * 2, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dn, norm_w, (size_t)k_in * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dw, w, wn, hipMemcpyHostToDevice)); HIPCHK(lnbk_tile(dw, t.w, n_out, k_in, 0, 0, 64, 1, 0, nullptr)); HIPCHK(hipDeviceSynchronize());
+    HIPCHK(lnbk_wpack_stats(t.w, tiled_elems(n_out, k_in, 64, 1), dstats, nullptr));
+    WpackStats ws; HIPCHK(hipMemcpy(&ws, dstats, sizeof ws, hipMemcpyDeviceToHost));
+    unsigned base = 0;
+    const int why = wpack_window(&ws, &base);
+    if (status) *status = why;
+    GemvParams g{}; g.w = t.w; g.x = dx; g.norm_w = dn; g.eps = eps; g.K = k_in; g.n_rows = n_out; g.S = 1; g.st = st; g.out = dy;
+    set_grid(g, t);
+    if (packed && why == WPACK_OK) {
+        HIPCHK(hipMalloc(&wp, lnbk_wpack_head_bytes(n_out, k_in)));
+        HIPCHK(lnbk_wpack_head(t.w, wp, n_out, k_in, base, nullptr));
+        g.wp = wp; g.wp_base4 = base * 0x01010101u;
+        g.n_blocks = (n_out + 127) / 128; g.n_wg = g.n_blocks < g_num_cus ? g.n_blocks : g_num_cus;
+        if (n_wg > 0 && n_wg < g.n_wg) g.n_wg = n_wg;
+        HIPCHK(lnbk_gemv_headp(&g, nullptr));
+    } else {
+        if (n_wg > 0 && n_wg < g.n_wg) g.n_wg = n_wg;
+        HIPCHK(lnbk_gemv(&g, 64, 1, EPI_STORE, 1, nullptr));
+    }
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(y, dy, (size_t)n_out * 2, hipMemcpyDeviceToHost));
+    hipFree(dx); hipFree(dw); hipFree(dy); hipFree(dn); hipFree(st); hipFree(dstats); hipFree(t.w); if (wp) hipFree(wp);
     return 0;
 }
 // ml.Argmax (operations_impl.go:513-548) of one row of bf16 logits through argmax_kernel, the kernel of the greedy loop

@@ -72,7 +72,8 @@ struct StepState {
                         // one-stage pipe) and the stop ids are compared; 0 = lnb_decode_greedy / lnb_batch_decode, which promise n_steps tokens: the ids are ignored
 };
 
-enum { EPI_STORE = 0, EPI_QKV_ROPE = 1, EPI_RESID = 2, EPI_SILU_MUL = 3 };
+enum { EPI_STORE = 0, EPI_QKV_ROPE = 1, EPI_RESID = 2, EPI_SILU_MUL = 3,
+       EPI_STORE2 = 4 };       // kernel-internal: EPI_STORE of a two-chain block of 2 RW rows (the packed LM head); the form tally counts it as EPI_STORE
 
 struct GemvParams {
     const uint16_t* w;          // tiled weights

@@ -50,6 +50,7 @@
     X(GEMV_CHAIN_56_TP, "gemv_chain.rw56_tp", "the same with six ring stages: the throughput schedule's gate|up kernel (LNB_TP_W13=0: the eight-stage one)") \
     X(GEMV_CHAIN_64, "gemv_chain.rw64", "gemv_chain_kernel, 64 rows per block") \
     X(GEMV_CHAIN_PK, "gemv_chain_pk", "gemv_chain_pk_kernel: gate|up from the 13-bit planar copy") \
+    X(GEMV_HEAD_PK, "gemv_head_pk", "gemv_chain_pk_kernel, 128-row blocks as two chains of 64: the LM head from its 13-bit planar copy (LNB_HEAD_PACKED)") \
     /* short-context attention of a batched step (launch_attn_short with a batch table) */ \
     X(ATTN_BATCH_PLAIN, "attn_batch.plain", "attn_exact_kernel<HD>: one workgroup per (head, sequence), the one-token kernel (head_dim 64 / 32, few workgroups, LNB_ATTN_BATCH_DENSE=0)") \
     X(ATTN_BATCH_DENSE, "attn_batch.dense", "attn_exact_kernel<128, DENSE>: head_dim 128 and more than 256 (head, sequence) workgroups, dispatched tile-major") \

@@ -158,6 +158,13 @@ __host__ __device__ inline size_t rms_scratch_bytes(int NH) { return (size_t)NH 
 #ifndef LNB_EARLY_HEAD
 #define LNB_EARLY_HEAD 0
 #endif
+// the packed-source forms have macros of their own (a packed stage is 52 bytes per lane, not 32 per load: what suits the raw form need not suit them)
+#ifndef LNB_EARLY_W13P
+#define LNB_EARLY_W13P 2                                    // gate|up from the 13-bit copy: 2 / 3 / 4 -> block 119.4 / 119.8 / 120.5 us, headline +1.0 % at 2 (profiles/head_packed.md, section 5)
+#endif
+#ifndef LNB_EARLY_HEADP
+#define LNB_EARLY_HEADP 2                                   // the LM head from the 13-bit copy: 0 / 2 -> launch 151.6 / 150.1 us and 149.9 / 148.3 us on two boxes (same section)
+#endif
 #ifndef LNB_RMS_NF_MAX
 #define LNB_RMS_NF_MAX 8
 #endif
@@ -589,11 +596,12 @@ DEVINL void gemv_epilogue(const GemvParams& p, const float (&acc)[NCH], int m, i
 // optional per-wave timing (GemvParams.dbg != nullptr): [wg][wave][4] = {total, barrier wait, x staging / vm wait, -} in s_memtime ticks
 #define TIMED_BARRIER() do { if (p.dbg_full) { long long tb_ = clock64(); __builtin_amdgcn_s_barrier(); t_wait += clock64() - tb_; } else __builtin_amdgcn_s_barrier(); } while (0)
 // phase stamp i (0..7) of this wave, cycles since the kernel started: a second region behind the [4096][8][4] totals (lnb_api.cpp prints the averages)
-#define LNB_STAMP(i) do { if (p.dbg && lane == 0) p.dbg[(size_t)4096 * 8 * 4 + ((size_t)blockIdx.x * 8 + wave) * 8 + (i)] = clock64() - t_begin; } while (0)
+// (the buffer has eight wave slots per workgroup: a ninth wave -- the packed LM head's -- records nothing instead of writing into the next workgroup's slots)
+#define LNB_STAMP(i) do { if (p.dbg && lane == 0 && wave < 8) p.dbg[(size_t)4096 * 8 * 4 + ((size_t)blockIdx.x * 8 + wave) * 8 + (i)] = clock64() - t_begin; } while (0)
 // ... and stamp 7 = the same interval on the constant-rate wall clock (s_memrealtime; hipDeviceAttributeWallClockRate): the shader clock of THIS launch
 // under ITS load = total / wall, which is what turns the cycle counts into microseconds (bench.py: roofline.measured_model)
-#define LNB_WALL_EXIT() do { if (p.dbg && lane == 0) p.dbg[(size_t)4096 * 8 * 4 + ((size_t)blockIdx.x * 8 + wave) * 8 + 7] = (long long)wall_clock64() - t_wall0; } while (0)
-#define DBG_EXIT() do { if (p.dbg && lane == 0) { long long* d_ = p.dbg + ((size_t)blockIdx.x * 8 + wave) * 4; d_[0] = clock64() - t_begin; d_[1] = t_wait; d_[2] = t_x; d_[3] = t_aux; } LNB_WALL_EXIT(); } while (0)
+#define LNB_WALL_EXIT() do { if (p.dbg && lane == 0 && wave < 8) p.dbg[(size_t)4096 * 8 * 4 + ((size_t)blockIdx.x * 8 + wave) * 8 + 7] = (long long)wall_clock64() - t_wall0; } while (0)
+#define DBG_EXIT() do { if (p.dbg && lane == 0 && wave < 8) { long long* d_ = p.dbg + ((size_t)blockIdx.x * 8 + wave) * 4; d_[0] = clock64() - t_begin; d_[1] = t_wait; d_[2] = t_x; d_[3] = t_aux; } LNB_WALL_EXIT(); } while (0)
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // asm loads are invisible to hipcc's s_waitcnt bookkeeping: the ring below is waited for by hand (wait_ring)
@@ -615,7 +623,9 @@ template <int N, int NP> DEVINL void wait_ring(u32x4 (&b)[NP]) {
 }
 
 // PK (two chains only): the helpers stream the 13-bit planar copy of the block (lnb_wpack.h) instead of the raw bf16 -- per lane and stage two 16-byte
-// loads of low bytes, one of exponent codes and one dword of signs for 32 weights -- and rebuild the same f32 weights; everything behind the unpack is the raw form's
+// loads of low bytes, one of exponent codes and one dword of signs for 32 weights -- and rebuild the same f32 weights; everything behind the unpack is the raw form's.
+// Two instances: gate|up (RW 56, seven helpers, EPI_SILU_MUL: the chains are gate and up of one row) and the LM head (RW 64, eight helpers, EPI_STORE2: the
+// chains are rows r and 64 + r of a 128-row block)
 template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC, bool PK>
 DEVINL void gemv_chain_body(const GemvParams& p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -674,7 +684,7 @@ DEVINL void gemv_chain_body(const GemvParams& p) {
             loff[i] = NCH == 2 ? (unsigned)((((pq / RW) * 2 + (i & 1)) * RW + (pq % RW)) * 16) : (unsigned)(((i * NH + hw) * 64 + lane) * 16);
         }
         int ib = wg, is = 0, issued = 0;
-        const unsigned pk_l16 = (unsigned)((hw * 64 + lane) * 16), pk_l4 = (unsigned)(NH * 64 * 48 + (hw * 64 + lane) * 4);
+        const unsigned pk_l16 = (unsigned)wpack_plane_off(NH * 64, 0, hw * 64 + lane), pk_l4 = (unsigned)wpack_plane_off(NH * 64, 3, hw * 64 + lane);
         auto issue_next = [&](u32x4 (&dst)[NP], unsigned& sg) {
             if constexpr (PK) {
                 // whole stages only (the copy pads a block's last stage with zeros): no clamp
@@ -696,7 +706,7 @@ DEVINL void gemv_chain_body(const GemvParams& p) {
             // pipeline stalls the issuing waves ~3 k cycles -- the waves that fold; behind the fold they only wait for the walker anyway
             // (measured: wq|wk|wv -1.0 us, w1|w3 -2.3 us, output -1 us)
             constexpr bool late = NORM;
-            constexpr int EARLY_ = NCH == 2 ? LNB_EARLY_W13 : LNB_EARLY_HEAD;
+            constexpr int EARLY_ = PK ? (EPI == EPI_STORE2 ? LNB_EARLY_HEADP : LNB_EARLY_W13P) : NCH == 2 ? LNB_EARLY_W13 : LNB_EARLY_HEAD;
             constexpr int EARLY = late ? (EARLY_ < R ? EARLY_ : R) : R;      // stages issued in front of the fold
 #pragma unroll
             for (int j = 0; j < EARLY; j++) issue_next(buf[j], sgn[PK ? j : 0]);
@@ -872,6 +882,15 @@ DEVINL void gemv_chain_body(const GemvParams& p) {
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (++st == nstages) {                                     // end of a row block: write it out, start the next
+                if constexpr (EPI == EPI_STORE2) {
+                    // the packed LM head: a block is 2 RW rows, chain c of lane r is row blk * 2 RW + c * RW + r
+                    static_assert(EPI != EPI_STORE2 || NCH == 2, "the two-row store epilogue needs two chains");
+#pragma unroll
+                    for (int c = 0; c < NCH; c++) {
+                        const int n = blk * (2 * RW) + c * RW + lane;
+                        if (lane < RW && n < p.n_rows) p.out[(size_t)m * p.n_rows + n] = bf_trunc(acc[c]);
+                    }
+                } else
                 gemv_epilogue<NCH, EPI>(p, acc, m, blk * RW + lane, (lane < RW) && (blk * RW + lane < p.n_rows));
 #pragma unroll
                 for (int c = 0; c < NCH; c++) acc[c] = 0.0f;
@@ -4849,6 +4868,27 @@ __global__ void wpack_pack_kernel(const uint16_t* w, char* out, int K, int rw, i
     *(uint4*)(o + (size_t)lanes * 32 + (size_t)L * 16) = make_uint4(code4[0], code4[1], code4[2], code4[3]);
     *(uint32_t*)(o + (size_t)lanes * 48 + (size_t)L * 4) = sg;
 }
+// the LM head's copy: one thread per (128-row block, stage, helper lane); the lane's four units out of the resident [N/64][K/8][1][64][8] layout
+// (wpack_head_src_unit: chain 0 from resident block 2 b, chain 1 from 2 b + 1, zeros past N and past K)
+__global__ void wpack_pack_head_kernel(const uint16_t* w, char* out, int N, int K, unsigned base) {
+    const int nst = wpack_head_stages(K), lanes = WPACK_HEAD_LANES;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)wpack_head_blocks(N) * nst * lanes) return;
+    const int L = (int)(idx % lanes), st = (int)((idx / lanes) % nst), b = (int)(idx / ((size_t)lanes * nst));
+    uint4 g[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const long long su = wpack_head_src_unit(N, K, b, st, L, u);
+        g[u] = su >= 0 ? *(const uint4*)(w + (size_t)su * 8) : make_uint4(0, 0, 0, 0);
+    }
+    uint32_t low8[8], code4[4], sg;
+    wpack_pack_group((const uint16_t*)g, base, low8, code4, &sg);
+    char* o = out + wpack_head_stage_off(K, b, st);
+    *(uint4*)(o + wpack_plane_off(lanes, 0, L)) = make_uint4(low8[0], low8[1], low8[2], low8[3]);
+    *(uint4*)(o + wpack_plane_off(lanes, 1, L)) = make_uint4(low8[4], low8[5], low8[6], low8[7]);
+    *(uint4*)(o + wpack_plane_off(lanes, 2, L)) = make_uint4(code4[0], code4[1], code4[2], code4[3]);
+    *(uint32_t*)(o + wpack_plane_off(lanes, 3, L)) = sg;
+}
 
 #include "lnb_batch_kernels.h"
 #include "lnb_knobs.h"
@@ -4887,7 +4927,7 @@ static hipError_t launch_chain_x(const GemvParams* p, hipStream_t st) {
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (xs_bytes(p->K, SA / (NCH * RW * 2)) / 4 > (size_t)XC * (1 + NH) * 512) return hipErrorInvalidValue;   // x staging registers
     if (NORM && (rms_scratch_bytes(rms_nf(NH)) > 4 * (size_t)SA || seq_leaf_size(p->K, rms_nf(NH) * 64) > 256)) return hipErrorInvalidValue;   // records live in the idle ring; leaf over-read stays inside the x padding
-    form_ran(PK ? Form::GEMV_CHAIN_PK : RW == 16 ? Form::GEMV_CHAIN_16 : RW == 28 ? Form::GEMV_CHAIN_28 : RW == 32 ? Form::GEMV_CHAIN_32 : RW == 56 ? (R == 6 ? Form::GEMV_CHAIN_56_TP : Form::GEMV_CHAIN_56) : Form::GEMV_CHAIN_64, EPI);
+    form_ran(PK ? (EPI == EPI_STORE2 ? Form::GEMV_HEAD_PK : Form::GEMV_CHAIN_PK) : RW == 16 ? Form::GEMV_CHAIN_16 : RW == 28 ? Form::GEMV_CHAIN_28 : RW == 32 ? Form::GEMV_CHAIN_32 : RW == 56 ? (R == 6 ? Form::GEMV_CHAIN_56_TP : Form::GEMV_CHAIN_56) : Form::GEMV_CHAIN_64, EPI == EPI_STORE2 ? EPI_STORE : EPI);
     hipLaunchKernelGGL(kfn, dim3((unsigned)(p->S * p->n_wg)), dim3((1 + NH) * 64), lds, st, *p);
     return hipGetLastError();
 }
@@ -5005,6 +5045,29 @@ extern "C" hipError_t lnbk_wpack_stats(const uint16_t* w, size_t elems, unsigned
 extern "C" hipError_t lnbk_wpack_w13(const uint16_t* w, void* out, int K, int n_blocks, unsigned base, hipStream_t st) {
     const size_t n = (size_t)n_blocks * wpack_stages(K, WPACK_LANES_W13, 56) * WPACK_LANES_W13;
     hipLaunchKernelGGL(wpack_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, (char*)out, K, 56, WPACK_LANES_W13, n_blocks, base);
+    return hipGetLastError();
+}
+
+// The one-token LM head from ITS 13-bit copy (blocks of 128 rows as two chains per lane; lnb_wpack.h): the one-chain 64-row form walks 8.7 - 9.0 cycles per step,
+// which at 13/16 of the bytes would be the bound (7.83 blocks x 4096 steps = 123 us); two chains through one v_pk_add_f32 walk half the blocks at 6.0.
+// Eight helpers (512 lanes, one 32-weight group each), 128-step stages: 2 x 64 KB of products + x = 149 KB of LDS; nine waves = three on one SIMD, so the
+// instance has 168 VGPRs at most; LNB_HEADP_R stages of 52 bytes per lane in flight (5: 133 KB per CU).
+#ifndef LNB_HEADP_R
+#define LNB_HEADP_R 5
+#endif
+extern "C" int lnbk_headp_supported(int K) {
+    return K > 0 && K % 8 == 0 && 4 * (size_t)32768 + xs_bytes(K, 128) <= 160 * 1024 && xs_bytes(K, 128) / 4 <= (size_t)XCh<true>::value * 9 * 512 && seq_leaf_size(K, rms_nf(8) * 64) <= 256;
+}
+// p->w: unused; p->n_blocks / p->n_wg count 128-row blocks
+extern "C" hipError_t lnbk_gemv_headp(const GemvParams* p, hipStream_t st) {
+    if (p && (!p->wp || p->S != 1 || !lnbk_headp_supported(p->K) || p->n_blocks != wpack_head_blocks(p->n_rows))) return hipErrorInvalidValue;
+    return launch_chain_t<WPACK_HEAD_RW, 2, 32768, WPACK_HEAD_LANES / 64, LNB_HEADP_R, EPI_STORE2, true, true>(p, st);
+}
+extern "C" size_t lnbk_wpack_head_bytes(int N, int K) { return wpack_head_bytes(N, K); }
+// w: the resident 64-row one-chain layout of the [N][K] matrix
+extern "C" hipError_t lnbk_wpack_head(const uint16_t* w, void* out, int N, int K, unsigned base, hipStream_t st) {
+    const size_t n = (size_t)wpack_head_blocks(N) * wpack_head_stages(K) * WPACK_HEAD_LANES;
+    hipLaunchKernelGGL(wpack_pack_head_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, (char*)out, N, K, base);
     return hipGetLastError();
 }
 
@@ -5267,6 +5330,7 @@ extern "C" hipError_t lnbk_init(void) {
         if (rw != 24) gemv(rw, 2, EPI_SILU_MUL, 1);
     }
     if (e == hipSuccess) e = lnbk_gemv_w13p(nullptr, nullptr);
+    if (e == hipSuccess) e = lnbk_gemv_headp(nullptr, nullptr);
     for (auto prepare : {launch_attn_long<true>, launch_attn_long<false>, launch_attn_one, launch_attn_short}) if (e == hipSuccess) e = prepare(nullptr, nullptr);
     if (e == hipSuccess) e = launch_attn_rows(nullptr, -1, nullptr);
     if (e != hipSuccess) return e;

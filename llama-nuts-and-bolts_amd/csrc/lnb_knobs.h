@@ -15,6 +15,7 @@
     X(RW_OP, 0, LIVE, "rows per block of a stand-alone lnb_op_linear operand (0: by shape)") \
     /* one-token decode */ \
     X(W13_PACKED, 1, LIVE, "0: lnb_model_finalize builds no 13-bit planar copy of the gate|up matrices; the one-token step streams the raw bf16 (lnb_model_wpack_info)") \
+    X(HEAD_PACKED, 1, LIVE, "0: lnb_model_finalize builds no 13-bit planar copy of the LM head; the one-token step streams the raw bf16 (lnb_model_wpack_head_status)") \
     /* prefill form */ \
     X(PREFILL_MFMA, 1, ONCE, "0: calls of 16+ rows stay on the one-row kernels (what the parity tests compare the matrix-core forms with)") \
     X(PREFILL_STREAM, 1, ONCE, "0: prefill products on the LDS-tiled gemm_mfma_kernel, never the streaming feed") \

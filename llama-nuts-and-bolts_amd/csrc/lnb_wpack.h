@@ -1,5 +1,5 @@
-// lnb_wpack.h -- the lossless 13-bit planar copy of a bf16 weight matrix that the one-token gate|up kernel streams instead of the raw bf16
-// (gemv_chain_kernel's packed source form).  Plain C++ shared by host and device: tests/native/wpack_test.cpp includes exactly this file.
+// lnb_wpack.h -- the lossless 13-bit planar copy of a bf16 weight matrix that the one-token gate|up kernel and the one-token LM head stream instead of
+// the raw bf16 (gemv_chain_kernel's packed source form).  Plain C++ shared by host and device: tests/native/wpack_test.cpp and wpack_head_test.cpp include exactly this file.
 //
 // bf16 = sign | 8 exponent bits | 7 mantissa bits.  The LOW byte (exponent bit 0 + mantissa) is kept raw.  The HIGH byte is sign | exponent >> 1,
 // and the non-zero weights of a matrix live in a few dozen binades, so exponent >> 1 is stored as a 4-bit code relative to a per-matrix window:
@@ -105,3 +105,25 @@ template <int J> LNB_WP_HD uint32_t wpack_wide(uint32_t hi4, uint32_t lo4) {
 LNB_WP_HD size_t wpack_stage_bytes(int lanes) { return (size_t)lanes * WPACK_GROUP_BYTES; }
 LNB_WP_HD int wpack_stages(int K, int lanes, int rw) { const int kcs = 2 * lanes / rw; return ((K >> 3) + kcs - 1) / kcs; }
 LNB_WP_HD size_t wpack_bytes(int n_blocks, int K, int lanes, int rw) { return (size_t)n_blocks * (size_t)wpack_stages(K, lanes, rw) * wpack_stage_bytes(lanes); }
+// where lane L's planes of a stage lie behind the stage's first byte: plane 0 low bytes of quads 0..3, 1 low bytes of quads 4..7, 2 codes (16 bytes each), 3 signs (4 bytes)
+LNB_WP_HD size_t wpack_plane_off(int lanes, int plane, int L) { return (size_t)lanes * 16 * plane + (size_t)L * (plane == 3 ? 4 : 16); }
+
+// ---- the LM head's stream ------------------------------------------------------------------------
+// The head keeps its resident layout [N/64][K/8][1][64][8] (one chain per lane: prefill, batches, every other path).  Its packed copy is cut for a TWO-chain
+// kernel instead: a block is 128 vocabulary rows, chain 0 = row 128 b + r, chain 1 = row 128 b + 64 + r (r = 0..63) -- the resident blocks 2 b and 2 b + 1 --
+// streamed by 512 helper lanes in stages of 16 chunks (128 k steps).  Stage, plane and pair arithmetic are the gate|up stream's with RW = 64; only the source
+// of a unit differs.  Rows at or beyond N and chunks at or beyond K / 8 are zeros (code 0).
+#define WPACK_HEAD_LANES 512
+#define WPACK_HEAD_RW 64                  // rows per chain of a block
+LNB_WP_HD int wpack_head_blocks(int N) { return (N + 2 * WPACK_HEAD_RW - 1) / (2 * WPACK_HEAD_RW); }
+LNB_WP_HD int wpack_head_stages(int K) { return wpack_stages(K, WPACK_HEAD_LANES, WPACK_HEAD_RW); }
+LNB_WP_HD size_t wpack_head_bytes(int N, int K) { return wpack_bytes(wpack_head_blocks(N), K, WPACK_HEAD_LANES, WPACK_HEAD_RW); }
+// first byte of (block b, stage st) in the copy
+LNB_WP_HD size_t wpack_head_stage_off(int K, int b, int st) { return ((size_t)b * (size_t)wpack_head_stages(K) + (size_t)st) * wpack_stage_bytes(WPACK_HEAD_LANES); }
+// unit u = 0..3 of the group of (block b, stage st, lane L): the 16-byte unit of the resident layout it holds (an index in units), or -1: zeros
+LNB_WP_HD long long wpack_head_src_unit(int N, int K, int b, int st, int L, int u) {
+    const int kcs = 2 * WPACK_HEAD_LANES / WPACK_HEAD_RW;                  // chunks per stage
+    const int pq = (u >> 1) * WPACK_HEAD_LANES + L, kc = st * kcs + pq / WPACK_HEAD_RW, r = pq % WPACK_HEAD_RW, rb = 2 * b + (u & 1);
+    if (kc >= (K >> 3) || rb * WPACK_HEAD_RW + r >= N) return -1;
+    return ((long long)rb * (K >> 3) + kc) * WPACK_HEAD_RW + r;
+}

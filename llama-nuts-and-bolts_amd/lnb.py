@@ -64,6 +64,7 @@ EXPORTS = [
     "lnb_pipeline_init_host", "lnb_batch_boundary_ptr",
     "lnb_abi_version", "lnb_runtime_info", "lnb_profile_ffn_pair",
     "lnb_model_wpack_bytes", "lnb_model_wpack_info", "lnb_op_rmsnorm_gate_up",
+    "lnb_model_wpack_head_bytes", "lnb_model_wpack_head_status", "lnb_op_rmsnorm_head",
     "lnb_ctx_set_token_probs", "lnb_ctx_read_token_probs", "lnb_ctx_token_prob_walks", "lnb_forward_score", "lnb_op_token_probs",
     "lnb_decode_sample_until", "lnb_batch_decode_sample_until", "lnb_op_sample", "lnb_profile_sample",
     "lnb_forward_append", "lnb_forward_score_append",
@@ -216,6 +217,10 @@ def lib():
     L.lnb_model_wpack_bytes.restype = C.c_int64
     L.lnb_model_wpack_info.argtypes = [vp, i32p]
     L.lnb_op_rmsnorm_gate_up.argtypes = [C.c_int, vp, vp, C.c_float, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.lnb_model_wpack_head_bytes.argtypes = [vp]
+    L.lnb_model_wpack_head_bytes.restype = C.c_int64
+    L.lnb_model_wpack_head_status.argtypes = [vp]
+    L.lnb_op_rmsnorm_head.argtypes = [C.c_int, vp, vp, C.c_float, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.lnb_batch_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp)]
     L.lnb_batch_destroy.argtypes = [vp]
     L.lnb_batch_decode.argtypes = [vp, i32p, i32p, C.c_int, vp, f32p]
@@ -565,6 +570,17 @@ class LlamaTransformer:
         c = np.zeros(6, dtype=np.int32)
         _chk(self.L.lnb_model_wpack_info(self.h, c.ctypes.data_as(C.POINTER(C.c_int32))))
         return dict(zip(("packed", "subnormal", "infnan", "window", "no_memory", "not_tried"), (int(v) for v in c)))
+
+    def wpack_head_bytes(self):
+        """device bytes of the LM head's 13-bit planar copy, 0 without one (lnb_model_wpack_head_bytes)"""
+        return int(self.L.lnb_model_wpack_head_bytes(self.h))
+
+    def wpack_head_status(self):
+        """what the one-token LM head streams (lnb_model_wpack_head_status): "packed", the reason its copy was refused, or "not_tried" """
+        s = int(self.L.lnb_model_wpack_head_status(self.h))
+        if s < 0:
+            _chk(s)
+        return ("packed", "subnormal", "infnan", "window", "no_memory", "not_tried")[s]
 
     def append_many_info(self):
         """of the last ForwardAppendMany on this transformer: {passes, max_columns, long_passes} (lnb_model_append_many_info)"""
@@ -1195,6 +1211,19 @@ def _splitmix64(z):
 def synth_tokens(seed, n, vocab):
     """Synthetic prompt of DESIGN.md ("Synthetic weights"): tok[i] = splitmix64(seed ^ i*golden) mod vocab."""
     return np.array([_splitmix64(seed ^ ((i * 0x9E3779B97F4A7C15) & _M64)) % vocab for i in range(n)], dtype=np.int32)
+
+
+def op_rmsnorm_head(x_u16, norm_w_u16, eps, w_u16, packed=1, n_wg=0, device=0):
+    """final norm + output projection of one row, as the one-token step launches it -> (y uint16 [n_out], WPACK status of the matrix); n_wg > 0 caps the workgroups"""
+    x = np.ascontiguousarray(x_u16, dtype=np.uint16).reshape(-1)
+    nw = np.ascontiguousarray(norm_w_u16, dtype=np.uint16)
+    w = np.ascontiguousarray(w_u16, dtype=np.uint16)
+    n, k = w.shape
+    assert x.shape == (k,) and nw.shape == (k,)
+    y = np.empty(n, dtype=np.uint16)
+    st = C.c_int(0)
+    _chk(lib().lnb_op_rmsnorm_head(device, _p(x), _p(nw), np.float32(eps), _p(w), _p(y), n, k, int(packed), int(n_wg), C.byref(st)))
+    return y, st.value
 
 
 def op_rmsnorm_gate_up(x_u16, norm_w_u16, eps, w1_u16, w3_u16, packed=1, device=0):
