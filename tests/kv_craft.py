@@ -190,6 +190,46 @@ def case_minus_masked_tail(rng, cfg, q, own, T):
     return gaussian_rows(rng, cfg, T - 1)
 
 
+# ---- the PV chain on columns that reveal a wrong order of its adds (tests/order_craft.py) ------------------------------------------------------------------
+PV_E_TOP, PV_WINDOWS = 118, 40              # a ladder's first opener 2^118, its last (window 39) 2^40 with v = 1.5 * 2^14: beside p ~ 2^-10 still far above the call's own term
+PV_ZS = (20, 60)                            # the zero-sum columns' binades
+
+
+def pv_windows(n, hd):
+    """windows per ladder: PV_WINDOWS, more when the columns of a head would not hold the ladders of n positions (three offsets each) beside a head column and eight zero-sum ones"""
+    per = max((hd - 9) // 3, 1)
+    return max(PV_WINDOWS, -(-(n // 3) // per))
+
+
+def pv_kinds(n, hd):
+    """the construction of every V column of a KV head over n cached positions: ("ladder", offset, ladder), ("head",), then zero-sum columns"""
+    w = pv_windows(n, hd)
+    kinds = [("ladder", o, l) for l in range(-(-(n // 3) // w)) for o in range(3)] if n >= 3 else []
+    kinds += [("head",)] if n >= 8 else []
+    assert len(kinds) <= hd - 8
+    return kinds + ["zero_sum"] * (hd - len(kinds))
+
+
+def case_v_order(rng, cfg, q, own, T):
+    """K rows of +0: every cached position has the score 0, e = 1 and the same p, whatever the head; the V columns are ladders, a head column and zero-sum columns
+    over the cached positions (tests/order_craft.py), so p * V -- a product of two bf16 values, exact -- keeps each construction: a ladder column sums to exactly
+    +0 and the output is the call's own term alone, any other order of the adds leaves residue far above it.  QK^T itself is not covered: the query cannot be
+    injected and its dot runs over 64 or 128 terms."""
+    import order_craft as od
+    n, kvh, hd = T - 1, cfg["n_kv_heads"], head_dim(cfg)
+    K = np.zeros((n, kvh, hd), dtype=np.uint16)
+    V = np.zeros((n, kvh, hd), dtype=np.float32)
+    kinds, w = pv_kinds(n, hd), pv_windows(n, hd)
+    for k in range(kvh):
+        for d in rng.permutation(hd):
+            kd = kinds[d]
+            V[:, k, d] = (od.zero_sum_products(rng, n, *PV_ZS) if kd == "zero_sum" else od.head_products(rng, n, PV_E_TOP) if kd == ("head",)
+                          else od.ladder_products(rng, n, kd[1], kd[2], PV_E_TOP, w))
+    Vb = bf(V)
+    assert np.array_equal(wide(Vb), V)
+    return K, Vb
+
+
 CASES = {
     "spread": case_spread,
     "denormal_visible": case_denormal_visible,
@@ -198,6 +238,7 @@ CASES = {
     "ties": case_ties,
     "signed_zero_v": case_signed_zero_v,
     "minus_masked_tail": case_minus_masked_tail,
+    "v_order": case_v_order,                # (sorts last: the other cases keep their seeds)
 }
 POISON_BEYOND = {"minus_masked_tail"}
 
@@ -206,6 +247,7 @@ POISON_BEYOND = {"minus_masked_tail"}
 LEFT_OUT = {
     ("spread", 1), ("denormal_visible", 1), ("huge_finite", 1), ("one_inf", 1), ("ties", 1),
     ("spread", 2), ("ties", 2),
+    ("v_order", 1), ("v_order", 2),           # no window of three fits
 }
 MAX_LEFT_OUT_FRACTION = 1.0 / 8.0
 

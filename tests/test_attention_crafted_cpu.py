@@ -141,6 +141,11 @@ def check_condition(case, geometry, T):
         for row in p16:
             assert np.unique(row, return_counts=True)[1].max() >= 8, tag
         assert not np.isnan(r["logits"]).any(), tag
+    elif case == "v_order":                                    # (what the columns show: tests/test_order_crafted_cpu.py)
+        assert not d[("scores", 0)][:, 0, :T - 1].any() and not np.isnan(r["logits"]).any(), tag
+        ladder = [c for c, kd in enumerate(kc.pv_kinds(T - 1, kc.head_dim(cfg))) if kd != "zero_sum"]
+        own = kc.bf(kc.wide(d[("softmax", 0)])[:, 0, T - 1, None] * kc.wide(r["kv"][0][1])[T - 1][np.arange(cfg["n_heads"]) // (cfg["n_heads"] // cfg["n_kv_heads"])])
+        assert np.array_equal(d[("attn_pre_wo", 0)].reshape(cfg["n_heads"], -1)[:, ladder], own[:, ladder]), tag      # exactly +0 from the cached rows
     else:                                                      # signed_zero_v, minus_masked_tail: equality with the device is the whole test
         assert not np.isnan(r["logits"]).any(), tag
 
@@ -151,7 +156,7 @@ def test_the_grid_leaves_out_at_most_one_case_in_eight():
     assert len(kc.LEFT_OUT) <= full * kc.MAX_LEFT_OUT_FRACTION and kc.MAX_LEFT_OUT_FRACTION == 1.0 / 8.0
     assert len(kc.grid()) == full - len(kc.LEFT_OUT)
     assert set(kc.TS) >= {1, 2, 15, 16, 17, 63, 64, 65, 255, 256, 257, 511, 512, 513} and kc.CAPACITY >= max(kc.TS) + kc.TAIL
-    assert set(kc.CASES) == {"spread", "denormal_visible", "huge_finite", "one_inf", "ties", "signed_zero_v", "minus_masked_tail"}
+    assert set(kc.CASES) == {"spread", "denormal_visible", "huge_finite", "one_inf", "ties", "signed_zero_v", "minus_masked_tail", "v_order"}
 
 
 def test_the_blob_is_the_documented_layout():

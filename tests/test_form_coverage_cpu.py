@@ -125,3 +125,27 @@ def test_every_knob_is_set_by_a_gpu_test_or_exempt_with_a_reason():
     missing = [k for k in knobs if k not in used and k not in KNOB_EXEMPT]
     assert not missing, "knobs no GPU test sets (set them in a test that asserts the form they pick, or exempt them with a reason): %s" % missing
     assert all(len(r) > 20 for r in KNOB_EXEMPT.values())
+
+
+PRODUCT_FAMILIES = ("gemm_mfma", "gemm_stream", "gemm_stream_order", "gemm_blgp", "mfma_pair", "mfma_stream", "rowcast", "rowcast_lds", "gemv_quad", "gemv_chain",
+                    "gemv_chain_pk", "gemv_head_pk")
+
+
+def test_every_product_form_runs_on_the_order_revealing_rows_or_is_exempt_there():
+    """every form that evaluates a dot product is named by a ran(...) of tests/test_gpu_order_crafted.py -- the rows on which a wrong order of the adds changes a
+    bf16 output -- or stands in that file's docstring under "Exempt, one line each:" as `  name: reason`"""
+    forms = form_names()
+    product = [f for f in forms if f.split(".")[0] in PRODUCT_FAMILIES]
+    assert len(product) >= 30 and {f.split(".")[0] for f in product} == set(PRODUCT_FAMILIES)
+    src = gpu_test_sources()["test_gpu_order_crafted.py"]
+    found = named_in(src, set())
+    doc = ast.get_docstring(ast.parse(src))
+    assert "Exempt, one line each:" in doc
+    exempt = dict(re.findall(r"^\s*([a-z0-9_.]+): (.+)$", doc.split("Exempt, one line each:")[1], re.M))
+    stale = sorted(set(exempt) - set(forms))
+    assert not stale, "exempt forms the table does not have: %s" % stale
+    both = sorted(f for f in exempt if f in found)
+    assert not both, "exempt AND named by a ran(...): %s" % both
+    missing = [f for f in product if f not in found and f not in exempt]
+    assert not missing, "product forms that never meet the order-revealing rows: %s" % missing
+    assert all(len(r) > 20 for r in exempt.values())

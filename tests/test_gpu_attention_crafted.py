@@ -169,7 +169,7 @@ def members_at(Ts):
 @pytest.mark.parametrize("geometry", sorted(kc.GEOMETRIES))
 def test_batched_decode_gives_each_member_its_own_oracle_run(lnb, geometry):
     batch_step(lnb, geometry, [("one_inf", 17), ("denormal_visible", 17)])          # two members
-    batch_step(lnb, geometry, members_at((65,)))                                    # all seven cases at one T
+    batch_step(lnb, geometry, members_at((65,)))                                    # every case at one T
     batch_step(lnb, geometry, members_at((2, 15, 16, 63, 64, 255, 256, 257, 511, 512)))
     batch_step(lnb, geometry, [(c, 64) for c in sorted(kc.CASES) if c != "one_inf"])          # no NaN member: the call succeeds, form and tokens asserted
 
@@ -183,7 +183,7 @@ def test_batched_decode_on_the_dense_dispatch(lnb):
 
 @pytest.mark.parametrize("force_z", ["0", "1"])
 def test_batched_decode_per_kv_head_kernel(lnb, monkeypatch, force_z):
-    """attn_gqa_kernel (head_dim 128, four query heads per KV head), forced on at seven members"""
+    """attn_gqa_kernel (head_dim 128, four query heads per KV head), forced on at one member per case"""
     monkeypatch.setenv("LNB_ATTN_GQA", "1")
     monkeypatch.setenv("LNB_ATTN_GQA_FORCE_ZSEQ", force_z)
     batch_step(lnb, "h8kv2_hd128", members_at((65,)))
@@ -335,7 +335,7 @@ def test_modulo_mask_forward_on_the_row_kernel_in_a_fresh_process(lnb):
 
 
 # ---- speculative verify passes after crafted rows --------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", ["spread", "denormal_visible", "huge_finite", "ties", "signed_zero_v", "minus_masked_tail"])
+@pytest.mark.parametrize("case", ["spread", "denormal_visible", "huge_finite", "ties", "signed_zero_v", "minus_masked_tail", "v_order"])
 @pytest.mark.parametrize("geometry", ["hd128", "h8kv2_hd128"])
 def test_speculative_decode_after_crafted_rows_equals_greedy(lnb, geometry, case):
     gm = gpu_model(lnb, geometry)

@@ -126,13 +126,22 @@ def test_linear_lm_head_shape(lnb):
 
 
 def test_linear_order_sensitivity_guard(lnb):
-    # a vector whose sequential f32 sum differs from any pairwise/blocked sum: catches split-K kernels
+    # The old vector: 1.0 followed by 4095 terms of 2^-12.  It shows that the chain is complete (4096 terms, none twice), and nothing about its order: the sum
+    # has 13 significant bits, so it is exact in f32 and every order -- sequential, reversed, split, pairwise -- gives 1.9997559
+    # (tests/test_order_crafted_cpu.py::test_the_old_inputs_reveal_almost_nothing).
     k = 4096
     x = bf(np.ones((1, k)))
     wrow = np.full(k, 2.0 ** -12, dtype=np.float32); wrow[0] = 1.0
     w = bf(np.tile(wrow, (64, 1)))
     y = lnb.op_linear(x, w, rw=16)
     assert (y == orc_linear(x, w)).all()
+    # What does show the order: the zero-sum, ladder and head rows of tests/order_craft.py, whose f32 sum is rounding residue or exactly +0 -- every wrong order
+    # on that module's list changes a bf16 output (the CPU test proves it per set); every form, with its launch tally: tests/test_gpu_order_crafted.py
+    import order_craft as od
+    for rw, sets in ((16, od.GEMV_SETS), (32, od.GEMV_SETS), (64, od.GEMV_SETS), (4, od.ROWCAST_SETS + od.ROWCAST_LDS_SETS), (24, od.QUAD_SETS)):
+        for key in sets:
+            s = od.get_set(*key)
+            assert (lnb.op_linear(s["x"], s["w"], rw=rw) == s["ref"]).all(), (rw, key)
 
 
 @pytest.mark.parametrize("rows,n,k,rw", [(1, 256, 256, 16), (4, 96, 512, 32), (1, 6144, 4096, 16), (2, 1024, 4096, 64),
