@@ -683,6 +683,26 @@ int lnb_op_rmsnorm_gate_up(int device, const uint16_t* x, const uint16_t* norm_w
  * matrix still walks several blocks per workgroup (0: no cap).  *status as above */
 int lnb_op_rmsnorm_head(int device, const uint16_t* x, const uint16_t* norm_w, float eps, const uint16_t* w, uint16_t* y,
                         int n_out, int k_in, int packed, int n_wg, int* status);
+/* What the RMSNorm of a kernel form computed, per row of x[rows][k_in] (Mean of llamatransformer.go:641-660, operations_impl.go:236-251): the raw f32 bits of
+ * the serial sum of squares as the kernel holds it in front of the division by k_in, the raw bits of r = f32(1 / sqrt(f64(sum / k_in + eps))), and the
+ * walker's path word.  form picks the launch function and the kernel: the production template arguments in an instantiation of their own that has the
+ * report compiled in (the production instantiations carry none of it).  A fused form runs with a zero weight matrix of one row block (the packed forms: its
+ * 13-bit copy) and its product is discarded; the fused forms take up to 15 rows per launch (the packed ones a single row), more rows are looped over here.
+ * Path word (csrc/lnb_seqsum.h, RMS_PATH_*): no bit of 0x70000000 set -- the branch-free item list was walked to its end: items << 16 | split leaves << 8 |
+ * single-term items (a split leaf is two items; it is counted by its second one, the only kind that carries both a term and a binade).  Otherwise the row
+ * took the record walk: 0x10000000 a folding wave flagged its segment (0x80000 its items do not fit the 128-entry segment, 0x40000 a leaf no item
+ * covers: a non-finite tree sum, 0x20000 a failed scan composition), 0x20000000 more than 64 items, 0x40000000 an item's check failed; bits 20..27 the
+ * flagging waves, bits 8..15 the item total & 0xFF, bits 0..7 the leaves replayed by the record walk (at most 255).
+ * LNB_NORM_ROWS_WAVE has no item list: its path word is -1.
+ * Returns 0; 1 when the form's launch function refuses k_in (nothing is written); -1 on an error. */
+enum { LNB_NORM_CHAIN16 = 0, LNB_NORM_CHAIN32 = 1, LNB_NORM_CHAIN64 = 2,      /* gemv_chain_kernel<16 / 32 / 64, 1, ...>: 2 / 6 / 6 folding waves */
+       LNB_NORM_QUAD24 = 3, LNB_NORM_QUAD24_SCHED = 4,                        /* gemv_quad_kernel<24, 256, 6, ...> / <24, 128, 6, 10, ...>: 6 */
+       LNB_NORM_GATE_UP56 = 5, LNB_NORM_GATE_UP28 = 6,                        /* gemv_chain_kernel<56 / 28, 2, 14336, 7, 8, SILU_MUL>: 7 */
+       LNB_NORM_GATE_UP56_PACKED = 7, LNB_NORM_HEAD_PACKED = 8,               /* gemv_chain_pk_kernel, gate|up: 7; the LM head: 8 */
+       LNB_NORM_ROWS_WIDE = 9, LNB_NORM_BATCH_XT = 10,                        /* batch_rmsnorm_xt_kernel<false> / <true>: 6 */
+       LNB_NORM_ROWS_WAVE = 11, LNB_NORM_FORMS = 12 };                        /* rmsnorm_rows_kernel: the plain serial loop */
+int lnb_op_rmsnorm_sum(int device, const uint16_t* x, int rows, int k_in, float eps, int form,
+                       uint32_t* sum_bits, uint32_t* scale_bits, int32_t* walk);
 
 /* either operator in a given arithmetic mode (norm_w == NULL: plain linear); LNB_MODE_FAST runs the split-K kernels */
 int lnb_op_linear_mode(int device, const uint16_t* x, const uint16_t* norm_w, float eps, const uint16_t* w, uint16_t* y,

@@ -51,6 +51,8 @@ size_t lnbk_attn_one_lds(int seq_len, int hd);
 hipError_t lnbk_exp_table(double* tab, float divisor, hipStream_t st);
 hipError_t lnbk_gemm(const GemmParams* p, int epi, hipStream_t st);
 hipError_t lnbk_rmsnorm_rows(const uint16_t* x, const uint16_t* w, uint16_t* out, int S, int K, float eps, hipStream_t st);
+hipError_t lnbk_rmsnorm_rows_form(const uint16_t* x, const uint16_t* w, uint16_t* out, int S, int K, float eps, int form, uint32_t* norm_out, hipStream_t st);
+hipError_t lnbk_gemv_norm_report(const GemvParams* p, int form, hipStream_t st);
 hipError_t lnbk_embed(const uint16_t* emb, const int32_t* tokens, uint16_t* x, int S, int dim, int vocab, int* err, hipStream_t st);
 hipError_t lnbk_argmax(const uint16_t* logits, int V, int32_t* next_token, StepState* state, int32_t* out_tokens, int out_cap, int advance, hipStream_t st);
 hipError_t lnbk_sample(const uint16_t* logits, int V, int rows, const double* etab, const LnbSampler* smp, int32_t* next_token, StepState* state, int32_t* out_tokens,
@@ -78,6 +80,7 @@ hipError_t lnbk_fast_init(void);
 hipError_t lnbk_m16_from_tiled(const uint16_t* src, uint16_t* dst, int rows, int K, int RW, int NCH, hipStream_t st);
 hipError_t lnbk_stream(const StreamParams* p, int epi, int acc2, int num_cus, hipStream_t st);
 hipError_t lnbk_batch_rmsnorm(const uint16_t* x, const uint16_t* norm_w, float eps, uint16_t* xt, int K, int nseq, hipStream_t st);
+hipError_t lnbk_batch_rmsnorm_out(const uint16_t* x, const uint16_t* norm_w, float eps, uint16_t* xt, int K, int nseq, uint32_t* norm_out, hipStream_t st);
 hipError_t lnbk_batch_embed(const uint16_t* emb, const BatchTab* tab, uint16_t* x, int nseq, int dim, int vocab, int* err, hipStream_t st);
 hipError_t lnbk_batch_argmax(const uint16_t* logits, int V, const BatchTab* tab, int nseq, int32_t* ring, hipStream_t st);
 hipError_t lnbk_batch_set_state(const BatchTab* tab, const int32_t* tokens, const int32_t* pos, int32_t* ring, int honour_stop, hipStream_t st);
@@ -3894,6 +3897,72 @@ extern "C" int lnb_op_exp_table(int device, float divisor, double* out65536) {
     hipFree(d);
     HIPCHK(e);
     return 0;
+}
+// What the norm of a kernel form computed (include/lnb.h): each form through its own launch function, in the kernel's REPORT instantiation -- the production
+// template arguments with the walker's report compiled in.  The fused forms get a zero weight matrix of one row block; the product is discarded.
+extern "C" int lnb_op_rmsnorm_sum(int device, const uint16_t* x, int rows, int k_in, float eps, int form, uint32_t* sum_bits, uint32_t* scale_bits, int32_t* walk) {
+    if (!x || !sum_bits || !scale_bits || !walk) return fail("null argument");
+    if (rows <= 0 || k_in <= 0) return fail("empty operand");
+    if (k_in % 8) return fail("in_features must be a multiple of 8");
+    if (form < 0 || form >= LNB_NORM_FORMS) return fail("unknown norm form %d", form);
+    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
+    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(lnbk_init());
+    if (form == LNB_NORM_BATCH_XT) HIPCHK(lnbk_batch_prepare());
+    const bool alone = form == LNB_NORM_ROWS_WIDE || form == LNB_NORM_BATCH_XT || form == LNB_NORM_ROWS_WAVE;
+    const bool packed = form == LNB_NORM_GATE_UP56_PACKED || form == LNB_NORM_HEAD_PACKED;
+    // the smallest matrix the form takes: one row block (the packed head: one block of 128 rows)
+    const int rw = form == LNB_NORM_CHAIN16 ? 16 : form == LNB_NORM_CHAIN32 ? 32 : (form == LNB_NORM_CHAIN64 || form == LNB_NORM_HEAD_PACKED) ? 64 :
+                   (form == LNB_NORM_QUAD24 || form == LNB_NORM_QUAD24_SCHED) ? 24 : form == LNB_NORM_GATE_UP28 ? 28 : 56;
+    const int nch = (form == LNB_NORM_GATE_UP56 || form == LNB_NORM_GATE_UP28 || form == LNB_NORM_GATE_UP56_PACKED) ? 2 : 1;
+    const int n_out = form == LNB_NORM_HEAD_PACKED ? 128 : rw;
+    if (form == LNB_NORM_GATE_UP56_PACKED && !lnbk_w13p_supported(56, k_in)) return 1;
+    if (form == LNB_NORM_HEAD_PACKED && !lnbk_headp_supported(k_in)) return 1;
+    const size_t out_rows = alone ? (size_t)((rows + 15) & ~15) : 15;      // (batch_rmsnorm_xt_kernel<true> writes whole groups of 16 columns)
+    uint16_t *dx = nullptr, *dn = nullptr, *dy = nullptr; uint32_t* dno = nullptr; StepState* st = nullptr; float* dsilu = nullptr; void* wp = nullptr;
+    TiledDesc t{}; int64_t bytes = 0;
+    std::vector<uint16_t> ones((size_t)k_in, (uint16_t)0x3F80);
+    std::vector<uint32_t> got((size_t)rows * 3);
+    hipError_t e = hipSuccess;
+    int rc = -1;
+    do {
+        if ((e = hipMalloc((void**)&dx, (size_t)rows * k_in * 2)) != hipSuccess || (e = hipMalloc((void**)&dn, (size_t)k_in * 2)) != hipSuccess ||
+            (e = hipMalloc((void**)&dy, out_rows * (size_t)(alone ? k_in : n_out) * 2)) != hipSuccess || (e = hipMalloc((void**)&dno, got.size() * 4)) != hipSuccess ||
+            (e = hipMalloc((void**)&st, sizeof(StepState))) != hipSuccess) break;
+        if ((e = hipMemset(st, 0, sizeof(StepState))) != hipSuccess || (e = hipMemset(dno, 0, got.size() * 4)) != hipSuccess ||      // (the walker ADDS its path word)
+            (e = hipMemcpy(dx, x, (size_t)rows * k_in * 2, hipMemcpyHostToDevice)) != hipSuccess ||
+            (e = hipMemcpy(dn, ones.data(), (size_t)k_in * 2, hipMemcpyHostToDevice)) != hipSuccess) break;
+        if (alone) {
+            e = form == LNB_NORM_BATCH_XT ? lnbk_batch_rmsnorm_out(dx, dn, eps, dy, k_in, rows, dno, nullptr)
+                                          : lnbk_rmsnorm_rows_form(dx, dn, dy, rows, k_in, eps, form == LNB_NORM_ROWS_WIDE ? 1 : 2, dno, nullptr);
+        } else {
+            if (alloc_tiled(t, n_out, k_in, rw, nch, bytes)) { e = hipErrorOutOfMemory; break; }
+            if (nch == 2) { if ((e = hipMalloc((void**)&dsilu, (size_t)65536 * 4)) != hipSuccess || (e = hipMemset(dsilu, 0, (size_t)65536 * 4)) != hipSuccess) break; }
+            GemvParams g{}; g.w = t.w; g.norm_w = dn; g.eps = eps; g.K = k_in; g.n_rows = n_out; g.st = st; g.out = dy; g.silu = dsilu;
+            g.n_blocks = 1; g.n_wg = 1; g.sched = form == LNB_NORM_QUAD24_SCHED ? 1 : 0;
+            if (packed) {                                                 // the 13-bit copy of the zero matrix (window base 0)
+                const size_t n = form == LNB_NORM_HEAD_PACKED ? lnbk_wpack_head_bytes(n_out, k_in) : lnbk_wpack_w13_bytes(1, k_in);
+                if ((e = hipMalloc(&wp, n)) != hipSuccess) break;
+                e = form == LNB_NORM_HEAD_PACKED ? lnbk_wpack_head(t.w, wp, n_out, k_in, 0, nullptr) : lnbk_wpack_w13(t.w, wp, k_in, 1, 0, nullptr);
+                if (e != hipSuccess) break;
+                g.wp = wp; g.wp_base4 = 0;
+            }
+            const int per = packed ? 1 : 15;                              // rows per launch, as production launches them
+            for (int r0 = 0; r0 < rows && e == hipSuccess; r0 += per) {
+                g.S = rows - r0 < per ? rows - r0 : per; g.x = dx + (size_t)r0 * k_in; g.norm_out = dno + (size_t)r0 * 3;
+                e = lnbk_gemv_norm_report(&g, form, nullptr);
+            }
+        }
+        if (e == hipErrorInvalidValue) { rc = 1; e = hipSuccess; break; }  // the launch function refuses this K
+        if (e != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) break;
+        if ((e = hipMemcpy(got.data(), dno, got.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess) break;
+        for (int r = 0; r < rows; r++) { sum_bits[r] = got[(size_t)r * 3]; scale_bits[r] = got[(size_t)r * 3 + 1]; walk[r] = (int32_t)got[(size_t)r * 3 + 2]; }
+        rc = 0;
+    } while (0);
+    hipFree(dx); hipFree(dn); hipFree(dy); hipFree(dno); hipFree(st); if (dsilu) hipFree(dsilu); if (wp) hipFree(wp); if (t.w) hipFree(t.w);
+    if (e != hipSuccess) return fail("lnb_op_rmsnorm_sum: %s", hipGetErrorString(e));
+    return rc;
 }
 extern "C" int lnb_op_linear(int device, const uint16_t* x, const uint16_t* w, uint16_t* y, int rows, int n_out, int k_in, int rw) {
     return op_linear_impl(device, x, nullptr, 0.0f, w, y, rows, n_out, k_in, rw);

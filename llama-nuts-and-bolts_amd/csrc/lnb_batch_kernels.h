@@ -292,12 +292,14 @@ __global__ __launch_bounds__(256) void mfma_pair_kernel(StreamParams p) {
 // written out in the B-operand layout of the following product.  grid = nseq, block = (1 + NH) * 64, dynamic LDS = scratch + (kpad + 8) f32.
 // ------------------------------------------------------------------------------------------------
 constexpr int BN_NH = 6;
+static_assert(rms_norm_helpers_has(BN_NH), "the stand-alone norms' helper count: add it to LNB_RMS_NORM_HELPERS (lnb_seqsum.h)");
 __host__ __device__ inline int bn_kpad(int K) { return ((K + 7) & ~7) + 320; }
 __host__ __device__ inline size_t bn_scratch() { return (rms_scratch_bytes(BN_NH) + 255) & ~(size_t)255; }
 // XT false: the same norm with plain row-major bf16 output [row][K] -- the prefill's rows (rmsnorm_rows_kernel walks the serial sum with
 // one wave per row, 24 us per launch at K = 4096 whatever the row count; this evaluation takes 9).
-template <bool XT>
-__global__ __launch_bounds__((1 + BN_NH) * 64) void batch_rmsnorm_xt_kernel(const uint16_t* x, const uint16_t* norm_w, float eps, uint16_t* xt, int K) {
+// REPORT: the instantiation lnb_op_rmsnorm_sum launches (norm_out: [rows][3] words: sum bits, r bits, path word); production launches <XT, false> with null
+template <bool XT, bool REPORT>
+__global__ __launch_bounds__((1 + BN_NH) * 64) void batch_rmsnorm_xt_kernel(const uint16_t* x, const uint16_t* norm_w, float eps, uint16_t* xt, int K, uint32_t* norm_out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NH = BN_NH, NS = 1 + NH, CW = 3;
     char* scratch = smem;
@@ -316,7 +318,7 @@ __global__ __launch_bounds__((1 + BN_NH) * 64) void batch_rmsnorm_xt_kernel(cons
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_s_barrier();                        // B1: the squares are in LDS
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        rms_fold<rms_nf(NH)>(p, xs, scratch, hw < rms_nf(NH) ? hw : -1, lane, t_aux);       // X1, X2 inside
+        rms_fold<rms_nf(NH), REPORT>(p, xs, scratch, hw < rms_nf(NH) ? hw : -1, lane, t_aux);       // X1, X2 inside
         __builtin_amdgcn_s_barrier();                        // B2: r published
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         x_normalize<NS>(p, xs, kpad, xs[kpad], 1 + hw, lane, xv, nv);
@@ -326,7 +328,7 @@ __global__ __launch_bounds__((1 + BN_NH) * 64) void batch_rmsnorm_xt_kernel(cons
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_s_barrier();                        // B1
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        const float r = rms_scale_wide<rms_nf(NH)>(p, xs, scratch, lane, t_aux);     // X1, X2 inside
+        const float r = rms_scale_wide<rms_nf(NH), REPORT ? 1 : 0>(p, xs, scratch, lane, t_aux, (REPORT && norm_out) ? norm_out + (size_t)s * 3 : nullptr);     // X1, X2 inside
         if (lane == 0) xs[kpad] = r;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_s_barrier();                        // B2

@@ -108,6 +108,8 @@ struct GemvParams {
                                 // that a chain-bound launch of one context shares a CU with the HBM-bound gate|up launch of another)
     const void* wp;             // gemv_chain_pk_kernel: the 13-bit planar copy of w (lnb_wpack.h), wp_base4 = its window base in every byte
     unsigned wp_base4;
+    uint32_t* norm_out;         // read by the REPORT instantiations only (lnb_op_rmsnorm_sum; nullptr in production): [S][3] words per row from workgroup 0's walker --
+                                // the f32 bits of the sum of squares in front of the division by K, the bits of r, the walker's path word (RMS_PATH_*, lnb_seqsum.h)
 };
 
 // exact-order prefill GEMM on the f32 matrix cores (gemm_mfma_kernel): Y[m][n] for S >= 16 rows per call

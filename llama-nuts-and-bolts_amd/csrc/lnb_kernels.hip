@@ -25,6 +25,7 @@
 #include "lnb_device.h"
 #include "lnb_seqsum.h"
 #include "lnb_wpack.h"
+#include "../../include/lnb.h"                                // (LNB_NORM_*: the forms of lnbk_gemv_norm_report)
 
 #define DEVINL __device__ __forceinline__
 #define LNB_SAMPLE_FN DEVINL
@@ -141,7 +142,8 @@ DEVINL void x_store(const GemvParams& p, float* xs, int kpad, int sidx, int lane
 constexpr int RMS_HEAD = 256;
 __host__ __device__ inline size_t rms_scratch_bytes(int NH) { return (size_t)NH * (512 + 8 + 4 + 4 + 2048 + 8) + 64; }
 // LDS scratch (the idle product ring): SeqNode rec[NH][64] | uint64 items[NH] | float wtot[NH] | uint32 scan_failed[NH] |
-//                                      SeqItem list[NH][128] (each wave's items of the branch-free walk, in leaf order) | uint32 {count, uncovered}[NH]
+//                                      SeqItem list[NH][128] (each wave's items of the branch-free walk, in leaf order) | uint32 {count, uncovered}[NH] |
+//                                      64 spare bytes, of which the REPORT instantiations use the first 8: the walker's report address (rms_report_park)
 // Folding waves: every helper (-DLNB_RMS_NF_MAX=4 restricts the fold to four waves on four different SIMDs -- waves w and w+4 of a workgroup
 // share one: HW_ID read per wave, round 4 -- with leaves of 16 terms instead of 12: measured SLOWER, wq|wk|wv 21.2 vs 20.1 us; the fold's time
 // follows its instruction count per wave, not the number of waves on a SIMD).  Helpers past the limit only pass the fold's two barriers.
@@ -165,13 +167,10 @@ __host__ __device__ inline size_t rms_scratch_bytes(int NH) { return (size_t)NH 
 #ifndef LNB_EARLY_HEADP
 #define LNB_EARLY_HEADP 2                                   // the LM head from the 13-bit copy: 0 / 2 -> launch 151.6 / 150.1 us and 149.9 / 148.3 us on two boxes (same section)
 #endif
-#ifndef LNB_RMS_NF_MAX
-#define LNB_RMS_NF_MAX 8
-#endif
 #ifndef LNB_QUAD_R
 #define LNB_QUAD_R 5                                        // ring stages in flight per helper of gemv_quad_kernel<24, 256, ...> (A/B builds: 4, 6)
 #endif
-__host__ __device__ constexpr int rms_nf(int NH) { return NH > LNB_RMS_NF_MAX ? LNB_RMS_NF_MAX : NH; }
+// (LNB_RMS_NF_MAX, rms_nf: lnb_seqsum.h -- the host emulation folds on the same wave counts)
 __host__ __device__ inline size_t rms_list_off(int NH) { return (size_t)NH * 528; }
 __host__ __device__ inline size_t rms_meta_off(int NH) { return (size_t)NH * (528 + 2048); }
 
@@ -215,7 +214,8 @@ DEVINL void rms_load16(float (&tv)[16], const float* q, int c, int LEAF) {
 DEVINL float rms_tree16(const float (&tv)[16]) {
     return (((tv[0] + tv[1]) + (tv[2] + tv[3])) + ((tv[4] + tv[5]) + (tv[6] + tv[7]))) + (((tv[8] + tv[9]) + (tv[10] + tv[11])) + ((tv[12] + tv[13]) + (tv[14] + tv[15])));
 }
-template <int NH> DEVINL void rms_fold(const GemvParams& p, const float* xs, char* scratch, int hw, int lane, long long& t_dbg) {
+// REPORT (the instantiations lnb_op_rmsnorm_sum launches, never production's): the wave's flag word says WHY the row takes the record walk
+template <int NH, bool REPORT = false> DEVINL void rms_fold(const GemvParams& p, const float* xs, char* scratch, int hw, int lane, long long& t_dbg) {
     if (hw < 0) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); return; }      // a helper that does not fold: X1, X2
     const long long tf0_ = p.dbg ? clock64() : 0;
     const int LEAF = seq_leaf_size(p.K, NH * 64), nleaf = (p.K + LEAF - 1) / LEAF;
@@ -298,7 +298,7 @@ template <int NH> DEVINL void rms_fold(const GemvParams& p, const float* xs, cha
         const unsigned long long m1 = __ballot(pick && (valid || split_ok)), m2 = __ballot(pick && !valid && split_ok), m3 = __ballot(single);
         const unsigned cntw = (unsigned)(__builtin_popcountll(m1) + __builtin_popcountll(m2)) + (unsigned)LEAF * (unsigned)__builtin_popcountll(m3);
         const bool fits = cntw <= 128u;                                  // (the wave's list segment; the walker takes at most 64 items per row anyway)
-        const unsigned long long mu = __ballot(pick && !valid && !split_ok && !single) | (fits ? 0ull : 1ull);
+        const unsigned long long mu = __ballot(pick && !valid && !split_ok && !single) | ((REPORT || fits) ? 0ull : 1ull);
         const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m1, 0u)) +
                               __builtin_amdgcn_mbcnt_hi((unsigned)(m2 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m2, 0u)) +
                               (unsigned)LEAF * __builtin_amdgcn_mbcnt_hi((unsigned)(m3 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m3, 0u));
@@ -314,7 +314,7 @@ template <int NH> DEVINL void rms_fold(const GemvParams& p, const float* xs, cha
         if (lane == 0) {
             uint32_t* meta = (uint32_t*)(scratch + rms_meta_off(NH)) + hw * 2;
             meta[0] = fits ? cntw : 0u;
-            meta[1] = mu ? 1u : 0u;
+            meta[1] = (mu ? 1u : 0u) | ((REPORT && !fits) ? 2u : 0u);    // != 0: the row takes the record walk (REPORT: 1 a leaf nothing covers, 2 the segment is too short)
         }
     }
     n.b |= (uint32_t)start << 24;                                        // c1 < 2^24: the run's first leaf rides in the top byte
@@ -404,7 +404,13 @@ DEVINL uint32_t rms_walk_fast(uint32_t sb, const SeqNode& rc, unsigned long long
     return sb;
 }
 
-template <int NH> DEVINL float rms_scale_wide(const GemvParams& p, const float* xs, const char* scratch, int lane, long long& t_dbg) {
+// REPORT: the instantiations that lnb_op_rmsnorm_sum launches (production launches the REPORT = 0 ones, whose code is what it was): this row's three words
+// -- sum bits, r bits, path word (RMS_PATH_*, lnb_seqsum.h) -- go to `o` (1: the stand-alone norm kernels) or to the address rms_report_park left in the
+// spare bytes behind the LDS scratch (2: the norm-fused kernels, which have no scalar registers to carry it across the x staging and the walk)
+template <int NH> DEVINL void rms_report_park(const GemvParams& p, char* scratch, int row, int lane) {
+    if (lane == 0) *(uint32_t* volatile*)(scratch + rms_scratch_bytes(NH) - 64) = (p.norm_out && row >= 0) ? p.norm_out + (size_t)row * 3 : nullptr;
+}
+template <int NH, int REPORT = 0> DEVINL float rms_scale_wide(const GemvParams& p, const float* xs, const char* scratch, int lane, long long& t_dbg, uint32_t* o = nullptr) {
     const int K = p.K, LEAF = seq_leaf_size(K, NH * 64), nleaf = (K + LEAF - 1) / LEAF;
     const SeqNode* rec = (const SeqNode*)scratch;
     const unsigned long long* items = (const unsigned long long*)(scratch + (size_t)NH * 512);
@@ -497,11 +503,32 @@ template <int NH> DEVINL float rms_scale_wide(const GemvParams& p, const float* 
         }
     }
     if (p.dbg) t_dbg = clock64() - tw0_;                                 // walk time
+    if constexpr (REPORT == 2) o = *(uint32_t* volatile*)(scratch + rms_scratch_bytes(NH) - 64);
+    // (one scalar branch and selects behind it: every lane mask held across this block is a pair of scalar registers)
+    if (REPORT && (__builtin_amdgcn_readfirstlane((int)(uintptr_t)o) | __builtin_amdgcn_readfirstlane((int)((uintptr_t)o >> 32))) != 0) {
+        // the path word (RMS_PATH_*, lnb_seqsum.h; the host zeroes it): what the folding waves left in the LDS, read again here; lane g adds what it counts
+        uint32_t val = 0u, fl = 0u;
+#pragma unroll 1
+        for (int w = 0; w < NH; w++) {
+            const uint2 mw = ((const uint2*)(scratch + rms_meta_off(NH)))[w];                  // (every lane reads the same words)
+            const uint32_t fv = ((const uint32_t*)(scratch + (size_t)NH * 524))[w];
+            fl |= ((mw.y & 2u) ? RMS_PATH_NOFIT : 0u) | ((mw.y & 1u) ? RMS_PATH_UNCOVERED : 0u) | (fv ? RMS_PATH_SCANFAIL : 0u);
+            const bool mine = (uint32_t)lane < mw.x;                     // done: at most 64 items, so a wave's segment holds at most 64
+            const uint4 it = ((const uint4*)(scratch + rms_list_off(NH)))[w * 128 + (mine ? lane : 0)];
+            val += !mine ? 0u : it.w == SEQ_ANY_BINADE ? 1u : it.x != 0u ? 256u : 0u;          // single-term items | split leaves << 8
+        }
+        const int rp = (cnt & 0xFFFF) - 1;                               // leaves replayed by rms_walk_fast
+        const uint32_t own = done ? (uint32_t)cnt : ((uint32_t)why | fl | (uint32_t)(rp > 255 ? 255 : rp));
+        val = (done ? val : 0u) + (lane == 0 ? own : 0u);
+        atomicAdd(o + 2, val);
+    }
     if (!done) cnt = why;
     if (p.dbg && lane == 0) p.dbg[(size_t)4096 * 8 * 4 + ((size_t)blockIdx.x * 8 + 0) * 8 + 7] = cnt;   // stamp slot 7 of the walker: items << 16 | (old walk: 1 + ...)
     float mean = __fdiv_rn(__uint_as_float(sb), (float)K);
     mean = mean + p.eps;
-    return (float)(1.0 / sqrt((double)mean));
+    const float r = (float)(1.0 / sqrt((double)mean));
+    if (REPORT && o && lane == 0) { o[0] = sb; o[1] = __float_as_uint(r); }
+    return r;
 }
 // trunc(x*r) then trunc(.*w): two truncations (llamatransformer.go:656,638), from the registers loaded by x_issue
 template <int NS, int X_CH>
@@ -626,7 +653,7 @@ template <int N, int NP> DEVINL void wait_ring(u32x4 (&b)[NP]) {
 // loads of low bytes, one of exponent codes and one dword of signs for 32 weights -- and rebuild the same f32 weights; everything behind the unpack is the raw form's.
 // Two instances: gate|up (RW 56, seven helpers, EPI_SILU_MUL: the chains are gate and up of one row) and the LM head (RW 64, eight helpers, EPI_STORE2: the
 // chains are rows r and 64 + r of a 128-row block)
-template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC, bool PK>
+template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC, bool PK, bool REPORT = false>
 DEVINL void gemv_chain_body(const GemvParams& p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     long long t_begin = p.dbg ? clock64() : 0, t_wait = 0, t_x = 0, t_aux = 0;
@@ -715,7 +742,7 @@ DEVINL void gemv_chain_body(const GemvParams& p) {
             TIMED_BARRIER();                                           // B1: xs (or the squares) are in LDS
             if (NORM) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                rms_fold<rms_nf(NH)>(p, xs, ringB, hw - (NH - rms_nf(NH)), lane, t_aux);      // X1, X2 inside; the LAST four helpers fold (waves 4..7 of 8: four SIMDs)
+                rms_fold<rms_nf(NH), REPORT>(p, xs, ringB, hw - (NH - rms_nf(NH)), lane, t_aux);      // X1, X2 inside; the LAST four helpers fold (waves 4..7 of 8: four SIMDs)
                 {                                                      // the walker walks now: the issue stall costs nothing here
 #pragma unroll
                     for (int j = EARLY; j < R; j++) issue_next(buf[j], sgn[PK ? j : 0]);
@@ -810,6 +837,7 @@ DEVINL void gemv_chain_body(const GemvParams& p) {
     }
     // ==================================== chain wave ==================================================
     {
+        if constexpr (NORM && REPORT) rms_report_park<rms_nf(NH)>(p, ringB, wg == 0 ? m : -1, lane);
         uint4 xv[XC], nv[XC];
         x_issue<NORM, NS>(p, xrow, 0, lane, xv, nv);
         x_store<NORM, NS>(p, xs, kpad, 0, lane, xv);
@@ -817,7 +845,7 @@ DEVINL void gemv_chain_body(const GemvParams& p) {
         TIMED_BARRIER();                                               // B1
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         if (NORM) {
-            const float r = rms_scale_wide<rms_nf(NH)>(p, xs, ringB, lane, t_aux);     // X1, X2 inside
+            const float r = rms_scale_wide<rms_nf(NH), REPORT ? 2 : 0>(p, xs, ringB, lane, t_aux);     // X1, X2 inside
             if (lane == 0) xs[kpad] = r;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             TIMED_BARRIER();                                           // B2
@@ -906,6 +934,11 @@ template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC = X
 __global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_kernel(GemvParams p) { gemv_chain_body<RW, NCH, SA, NH, R, EPI, NORM, XC, false>(p); }
 template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value>
 __global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_pk_kernel(GemvParams p) { gemv_chain_body<RW, NCH, SA, NH, R, EPI, NORM, XC, true>(p); }
+// the same two kernels with the norm's report compiled in (GemvParams.norm_out): launched by lnb_op_rmsnorm_sum only
+template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value>
+__global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_report_kernel(GemvParams p) { gemv_chain_body<RW, NCH, SA, NH, R, EPI, NORM, XC, false, true>(p); }
+template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value>
+__global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_pk_report_kernel(GemvParams p) { gemv_chain_body<RW, NCH, SA, NH, R, EPI, NORM, XC, true, true>(p); }
 
 // ------------------------------------------------------------------------------------------------
 // gemv_quad_kernel (round 4): the norm-fused thin product wq|wk|wv on ALL CUs, its chains fed through the LDS AND by DPP.
@@ -938,184 +971,16 @@ constexpr int GQ_SLOTS = 3;
 __host__ __device__ constexpr int gq_ncw(int RW) { return (RW + 15) / 16; }
 template <int RW, int KS, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value>
 __global__ __launch_bounds__((gq_ncw(RW) + NH) * 64) void gemv_quad_kernel(GemvParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    long long t_begin = p.dbg ? clock64() : 0, t_wait = 0, t_x = 0, t_aux = 0;
-    const long long t_wall0 = p.dbg ? (long long)wall_clock64() : 0;
-    constexpr int NCW = gq_ncw(RW), NW = NCW + NH;
-    constexpr int KC = KS / 8;                            // 8-wide k chunks per stage
-    constexpr int GS = KS / 16;                           // 16-step groups per stage
-    constexpr int SA = RW * KS * 2;                       // bf16 bytes per stage
-    constexpr int SB = 2 * SA;                            // f32 product bytes per stage
-    constexpr int UNITS = RW * KC;                        // 16-byte weight units per stage
-    constexpr int NP = UNITS / (64 * NH);                 // loads per lane per stage per helper
-    static_assert(RW % 8 == 0 && KS % 16 == 0, "rows in eights (conflict-free product writes), whole 16-step groups");
-    static_assert(UNITS % (64 * NH) == 0 && R * NP <= 60, "vmcnt is a 6-bit counter");
-    static_assert(NH >= 2 && GS >= 4 && GS % 4 == 0, "stage geometry");
-    char* ringB = smem;
-    float* xs = (float*)(smem + GQ_SLOTS * SB);
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int K = p.K, S = p.S;
-    const int m = (S == 1) ? 0 : (int)(blockIdx.x % (unsigned)S);
-    const int wg = (S == 1) ? (int)blockIdx.x : (int)(blockIdx.x / (unsigned)S);
-    const size_t stream_bytes = (size_t)K * RW * 2;
-    const int nstages = (int)((stream_bytes + SA - 1) / SA);
-    const int nb_mine = (p.n_blocks - wg + p.n_wg - 1) / p.n_wg;       // row blocks wg, wg+n_wg, ...
-    const int T = nb_mine * nstages;                                   // stages of this workgroup
-    constexpr int NS = NW;                                             // every wave stages x
-    const int kpad = nstages * KS + 320;                               // launcher guarantees kpad <= X_CH*NS*512
-    const uint16_t* xrow = p.x + (size_t)m * K;
-
-    if (wave >= NCW) {
-        // ================================ helper waves ============================================
-        const int hw = wave - NCW;
-        u32x4 buf[R][NP];
-        uint4 xv[XC], nv[XC];
-        x_issue<NORM, NS>(p, xrow, wave, lane, xv, nv);
-        __builtin_amdgcn_s_waitcnt(0x0F70);                            // vmcnt(0): x (and the norm weights) have landed (see gemv_chain_kernel)
-        const size_t last16 = stream_bytes - 16;
-        unsigned loff[NP];
-#pragma unroll
-        for (int i = 0; i < NP; i++) loff[i] = (unsigned)(((i * NH + hw) * 64 + lane) * 16);
-        int ib = wg, is = 0, issued = 0;
-        auto issue_next = [&](u32x4 (&dst)[NP]) {
-            const size_t soff = (size_t)is * SA;
-            const char* sb = (const char*)p.w + (size_t)ib * stream_bytes + soff;     // wave-uniform
-            const unsigned lim = (soff + SA <= stream_bytes) ? 0xFFFFFFFFu : (unsigned)(last16 - soff);
-#pragma unroll
-            for (int i = 0; i < NP; i++) ld_nt_asm(dst[i], loff[i] < lim ? loff[i] : lim, sb);
-            if (issued + 1 < T) { issued++; if (++is == nstages) { is = 0; ib += p.n_wg; } }
-        };
-        constexpr bool late = NORM;                                    // the weight stream starts behind the norm's fold (see gemv_chain_kernel)
-        constexpr int EARLY = late ? (LNB_EARLY_QUAD < R ? LNB_EARLY_QUAD : R) : R;
-#pragma unroll
-        for (int j = 0; j < EARLY; j++) issue_next(buf[j]);
-        x_store<NORM, NS>(p, xs, kpad, wave, lane, xv);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        TIMED_BARRIER();                                               // B1: xs (or the squares) are in LDS
-        if (NORM) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            rms_fold<rms_nf(NH)>(p, xs, ringB, hw < rms_nf(NH) ? hw : -1, lane, t_aux);      // X1, X2 inside; the first four helpers fold (four consecutive waves: four SIMDs)
-            {                                                          // the walker walks now: the issue stall costs nothing here
-#pragma unroll
-                for (int j = EARLY; j < R; j++) issue_next(buf[j]);
-            }
-            TIMED_BARRIER();                                           // B2: r published
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            if constexpr (NORM) x_normalize<NS>(p, xs, kpad, xs[kpad], wave, lane, xv, nv);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            TIMED_BARRIER();                                           // B3: xs normalised
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        // unit of load i: q = kc*RW + r (stage-local k-chunk kc, row r); its eight products are the slots j0, j0+1 of group kc/2
-        unsigned doff[NP]; int xoff[NP];
-#pragma unroll
-        for (int i = 0; i < NP; i++) {
-            const int q = (i * NH + hw) * 64 + lane, kc = q / RW, r = q % RW;
-            const int j0 = (kc & 1) * 2, sw = (r >> 1) & 3;
-            doff[i] = (unsigned)((((kc >> 1) * RW + r) * 4 + (j0 ^ sw)) * 16);      // slot j0+1 sits at doff ^ 16 (j0 is even)
-            xoff[i] = kc * 8;
-        }
-        int st = 0;                                        // stage-in-block of the stage being converted
-        for (int it0 = 0; it0 <= T + 1; it0 += R) {
-#pragma unroll
-            for (int j = 0; j < R; j++) {
-                const int t = it0 + j;
-                if (t <= T + 1) {
-                    if (t < T) {
-                        const long long tb_ = p.dbg_full ? clock64() : 0;
-                        wait_ring<(R - 1) * NP, NP>(buf[j]);           // stage t landed; R-1 younger stages stay in flight
-                        if (p.dbg_full) t_x += clock64() - tb_;
-                        char* dst = ringB + (size_t)(t % GQ_SLOTS) * SB;
-                        const float* xst = xs + (size_t)st * KS;
-                        float4 xa[NP], xb[NP];
-#pragma unroll
-                        for (int i = 0; i < NP; i++) { xa[i] = *(const float4*)(xst + xoff[i]); xb[i] = *(const float4*)(xst + xoff[i] + 4); }
-#pragma unroll
-                        for (int i = 0; i < NP; i++) {
-                            const u32x4 v = buf[j][i];
-                            // exact products (8-bit x 8-bit significands): val1F32 * val2F32, operations_lineartransform.go:60
-                            *(float4*)(dst + doff[i]) = mul4(xa[i], bf_lo(v.x), bf_hi(v.x), bf_lo(v.y), bf_hi(v.y));
-                            *(float4*)(dst + (doff[i] ^ 16u)) = mul4(xb[i], bf_lo(v.z), bf_hi(v.z), bf_lo(v.w), bf_hi(v.w));
-                        }
-                        if (++st == nstages) st = 0;
-                        __builtin_amdgcn_sched_barrier(0);             // refill AFTER the slot has been consumed (no register copies)
-                        issue_next(buf[j]);
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");     // ds_writes complete before the barrier
-                    TIMED_BARRIER();
-                }
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0) ; RING_RETIRE_ALL" ::: "memory");
-        DBG_EXIT();
-        return;
-    }
-    // ==================================== chain waves ==================================================
-    {
-        uint4 xv[XC], nv[XC];
-        x_issue<NORM, NS>(p, xrow, wave, lane, xv, nv);
-        LNB_STAMP(0);
-        x_store<NORM, NS>(p, xs, kpad, wave, lane, xv);
-        LNB_STAMP(1);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        TIMED_BARRIER();                                               // B1
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        LNB_STAMP(2);
-        if (NORM) {
-            float r;
-            if (wave == 0) {
-                r = rms_scale_wide<rms_nf(NH)>(p, xs, ringB, lane, t_aux);     // X1, X2 inside
-                LNB_STAMP(3);
-                if (lane == 0) xs[kpad] = r;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                TIMED_BARRIER();                                       // B2
-                LNB_STAMP(4);
-            } else {
-                __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier();     // X1, X2
-                TIMED_BARRIER();                                       // B2
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                r = xs[kpad];
-            }
-            if constexpr (NORM) x_normalize<NS>(p, xs, kpad, r, wave, lane, xv, nv);
-            LNB_STAMP(5);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            TIMED_BARRIER();                                           // B3
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            LNB_STAMP(6);
-        }
-    }
-    if (p.dbg) { t_x = clock64() - t_begin; t_wait = 0; }              // (chain waves report the barrier wait of the main loop only)
-    __builtin_amdgcn_s_setprio(3);
-    constexpr int last_rows = RW - 16 * (NCW - 1);                     // rows of the last chain wave
-    const int rows_here = wave == NCW - 1 ? last_rows : 16;
-    const int rq = (lane >> 2) % rows_here, row = wave * 16 + rq, jq = lane & 3;
-    const char* const src0 = ringB + (size_t)((row * 4 + (jq ^ ((row >> 1) & 3))) * 16);
-    float acc[1] = {0.0f};
-    float4 pq[4];
-    int st = 0, blk = wg;
-    for (int it = 0; it <= T + 1; it++) {
-        if (it >= 2) {
-            const char* cur = src0 + (size_t)((it - 2) % GQ_SLOTS) * SB;
-            const char* nxt = src0 + (size_t)((it - 1) % GQ_SLOTS) * SB;       // complete since the last barrier (past the end: stale bytes, never added)
-            if (it == 2) { pq[0] = *(const float4*)cur; pq[1] = *(const float4*)(cur + RW * 64); pq[2] = *(const float4*)(cur + 2 * RW * 64); }
-#pragma unroll
-            for (int g = 0; g < GS; g++) {
-                pq[(g + 3) & 3] = g + 3 < GS ? *(const float4*)(cur + (g + 3) * (RW * 64)) : *(const float4*)(nxt + (g + 3 - GS) * (RW * 64));
-                __builtin_amdgcn_sched_barrier(0);                     // the read is issued HERE, three groups ahead of its adds
-                chain16q(acc[0], pq[g & 3]);                           // valDstF32 += p, k ascending (operations_lineartransform.go:63)
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (++st == nstages) {                                     // end of a row block: write it out, start the next
-                gemv_epilogue<1, EPI, 4>(p, acc, m, blk * RW + row, jq == 0 && lane < rows_here * 4 && blk * RW + row < p.n_rows);
-                acc[0] = 0.0f; st = 0; blk += p.n_wg;
-            }
-        }
-        TIMED_BARRIER();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
-    DBG_EXIT();
+#define LNB_QUAD_REPORT false
+#include "lnb_gemv_quad_body.h"
+#undef LNB_QUAD_REPORT
+}
+// the same kernel with the norm's report compiled in (GemvParams.norm_out): launched by lnb_op_rmsnorm_sum only
+template <int RW, int KS, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value>
+__global__ __launch_bounds__((gq_ncw(RW) + NH) * 64) void gemv_quad_report_kernel(GemvParams p) {
+#define LNB_QUAD_REPORT true
+#include "lnb_gemv_quad_body.h"
+#undef LNB_QUAD_REPORT
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1590,7 +1455,8 @@ __global__ __launch_bounds__(512) void rowcast_lds_kernel(GemvParams p) {
 // Weights are gathered 16 B at a time from whichever tiled layout the matrix was stored in (tiled_index).
 // grid = (ceil(n_rows/64), ceil(S/128)); dynamic LDS = (NCH*128*80 + 128*144) * 4 bytes.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void rmsnorm_rows_kernel(const uint16_t* x, const uint16_t* w, uint16_t* out, int S, int K, float eps) {
+template <bool REPORT>                                    // REPORT: lnb_op_rmsnorm_sum's instantiation (norm_out: [S][3] words); production launches <false> with null
+__global__ __launch_bounds__(64) void rmsnorm_rows_kernel(const uint16_t* x, const uint16_t* w, uint16_t* out, int S, int K, float eps, uint32_t* norm_out) {
     // one wave per row: the row's squares go to the LDS with coalesced loads, every lane then walks the SAME sequential sum
     // (broadcast float4 reads, the next 16 values in flight behind 16 adds), and the lanes share the normalisation
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1623,6 +1489,7 @@ __global__ __launch_bounds__(64) void rmsnorm_rows_kernel(const uint16_t* x, con
     float mean = __fdiv_rn(sum, (float)K);
     mean = mean + eps;
     const float r = (float)(1.0 / sqrt((double)mean));
+    if (REPORT && norm_out && lane == 0) { uint32_t* no = norm_out + (size_t)m * 3; no[0] = __float_as_uint(sum); no[1] = __float_as_uint(r); no[2] = RMS_PATH_SERIAL; }   // (lnb_op_rmsnorm_sum; nullptr in production)
     uint16_t* o = out + (size_t)m * K;
     for (int k = lane * 8; k < K; k += 512) {                // trunc(trunc(x*r)*w) (llamatransformer.go:656,638)
         const uint4 v = *(const uint4*)(xr + k), g = *(const uint4*)(w + k);
@@ -4918,10 +4785,12 @@ template <int MIN_HD = 32, class F> static hipError_t with_hd(const AttnParams* 
 // x staging: a whole number of stages (steps per stage = stage_bytes / (nch*rw*2)) + 64 floats of slack
 static size_t xs_bytes(int K, int steps_per_stage) { return ((size_t)((K + steps_per_stage - 1) / steps_per_stage) * steps_per_stage + 320) * 4 + 16; }
 
-template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC, bool PK = false>
+template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC, bool PK = false, bool REPORT = false>
 static hipError_t launch_chain_x(const GemvParams* p, hipStream_t st) {
+    static_assert(!NORM || rms_norm_helpers_has(NH), "a norm on this many helper waves: add it to LNB_RMS_NORM_HELPERS (lnb_seqsum.h)");
     void (*kfn)(GemvParams);
-    if constexpr (PK) kfn = gemv_chain_pk_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; else kfn = gemv_chain_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>;
+    if constexpr (REPORT) { if constexpr (PK) kfn = gemv_chain_pk_report_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; else kfn = gemv_chain_report_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; }
+    else if constexpr (PK) kfn = gemv_chain_pk_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; else kfn = gemv_chain_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>;
     if (!p) return raise_lds(kfn);
     size_t lds = 4 * (size_t)SA + xs_bytes(p->K, SA / (NCH * RW * 2));
     if (lds > 160 * 1024) return hipErrorInvalidValue;
@@ -4933,24 +4802,26 @@ static hipError_t launch_chain_x(const GemvParams* p, hipStream_t st) {
 }
 // x staging chunks per stager wave: the norm-fused kernels are instantiated for 2, 3 and 6 chunks of 512 elements per wave (K up to ~4 K, ~6 K / 12 K with
 // the 70B-like shape's 8192 in the middle one, 24 K) and the smallest that holds the padded row is launched; the plain kernels keep their 12
-template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, bool PK = false>
+template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, bool PK = false, bool REPORT = false>
 static hipError_t launch_chain_t(const GemvParams* p, hipStream_t st) {
     if constexpr (NORM) {
         if (!p) {
-            hipError_t e = launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 2, PK>(p, st);
-            if (e == hipSuccess) e = launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 3, PK>(p, st);
-            return e != hipSuccess ? e : launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, XCh<NORM>::value, PK>(p, st);
+            hipError_t e = launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 2, PK, REPORT>(p, st);
+            if (e == hipSuccess) e = launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 3, PK, REPORT>(p, st);
+            return e != hipSuccess ? e : launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, XCh<NORM>::value, PK, REPORT>(p, st);
         }
         const size_t need = xs_bytes(p->K, SA / (NCH * RW * 2)) / 4, per = (size_t)(1 + NH) * 512;
-        if (need <= 2 * per) return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 2, PK>(p, st);
-        if (need <= 3 * per) return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 3, PK>(p, st);
+        if (need <= 2 * per) return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 2, PK, REPORT>(p, st);
+        if (need <= 3 * per) return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 3, PK, REPORT>(p, st);
     }
-    return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, XCh<NORM>::value, PK>(p, st);
+    return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, XCh<NORM>::value, PK, REPORT>(p, st);
 }
 
-template <int RW, int KS, int NH, int R, int EPI, bool NORM, int XC>
+template <int RW, int KS, int NH, int R, int EPI, bool NORM, int XC, bool REPORT = false>
 static hipError_t launch_quad_x(const GemvParams* p, hipStream_t st) {
-    auto kfn = gemv_quad_kernel<RW, KS, NH, R, EPI, NORM, XC>;
+    static_assert(!NORM || rms_norm_helpers_has(NH), "a norm on this many helper waves: add it to LNB_RMS_NORM_HELPERS (lnb_seqsum.h)");
+    void (*kfn)(GemvParams);
+    if constexpr (REPORT) kfn = gemv_quad_report_kernel<RW, KS, NH, R, EPI, NORM, XC>; else kfn = gemv_quad_kernel<RW, KS, NH, R, EPI, NORM, XC>;
     if (!p) return raise_lds(kfn);
     constexpr int NW = gq_ncw(RW) + NH;
     constexpr size_t SB = (size_t)RW * KS * 4;
@@ -4963,16 +4834,16 @@ static hipError_t launch_quad_x(const GemvParams* p, hipStream_t st) {
     hipLaunchKernelGGL(kfn, dim3((unsigned)(p->S * p->n_wg)), dim3(NW * 64), lds, st, *p);
     return hipGetLastError();
 }
-template <int RW, int KS, int NH, int R, int EPI, bool NORM>
+template <int RW, int KS, int NH, int R, int EPI, bool NORM, bool REPORT = false>
 static hipError_t launch_quad_t(const GemvParams* p, hipStream_t st) {
     if constexpr (NORM) {
         if (!p) {
-            hipError_t e = launch_quad_x<RW, KS, NH, R, EPI, NORM, 2>(p, st);
-            return e != hipSuccess ? e : launch_quad_x<RW, KS, NH, R, EPI, NORM, XCh<NORM>::value>(p, st);
+            hipError_t e = launch_quad_x<RW, KS, NH, R, EPI, NORM, 2, REPORT>(p, st);
+            return e != hipSuccess ? e : launch_quad_x<RW, KS, NH, R, EPI, NORM, XCh<NORM>::value, REPORT>(p, st);
         }
-        if (xs_bytes(p->K, KS) / 4 <= (size_t)2 * (gq_ncw(RW) + NH) * 512) return launch_quad_x<RW, KS, NH, R, EPI, NORM, 2>(p, st);
+        if (xs_bytes(p->K, KS) / 4 <= (size_t)2 * (gq_ncw(RW) + NH) * 512) return launch_quad_x<RW, KS, NH, R, EPI, NORM, 2, REPORT>(p, st);
     }
-    return launch_quad_x<RW, KS, NH, R, EPI, NORM, XCh<NORM>::value>(p, st);
+    return launch_quad_x<RW, KS, NH, R, EPI, NORM, XCh<NORM>::value, REPORT>(p, st);
 }
 
 template <int EPI, bool NORM, int NCH>
@@ -5064,6 +4935,27 @@ extern "C" hipError_t lnbk_gemv_headp(const GemvParams* p, hipStream_t st) {
     return launch_chain_t<WPACK_HEAD_RW, 2, 32768, WPACK_HEAD_LANES / 64, LNB_HEADP_R, EPI_STORE2, true, true>(p, st);
 }
 extern "C" size_t lnbk_wpack_head_bytes(int N, int K) { return wpack_head_bytes(N, K); }
+// lnb_op_rmsnorm_sum: the norm-fused kernel of `form` (LNB_NORM_CHAIN16 .. LNB_NORM_HEAD_PACKED of include/lnb.h) in its REPORT instantiation -- the same template arguments, launch
+// function, checks and tally row as the production launch, with the norm's report (p->norm_out) compiled in.  Never inside a stream capture (it raises the
+// instantiation's dynamic-LDS limit first).
+template <class F> static hipError_t report_launch(F f, const GemvParams* p, hipStream_t st) { const hipError_t e = f(nullptr, st); return e != hipSuccess ? e : f(p, st); }
+extern "C" hipError_t lnbk_gemv_norm_report(const GemvParams* p, int form, hipStream_t st) {
+    if (!p || !p->norm_w || !p->norm_out) return hipErrorInvalidValue;
+    switch (form) {
+        case LNB_NORM_CHAIN16: return report_launch(launch_chain_t<16, 1, 8192, 2, 7, EPI_STORE, true, false, true>, p, st);
+        case LNB_NORM_CHAIN32: return report_launch(launch_chain_t<32, 1, 12288, 6, 5, EPI_STORE, true, false, true>, p, st);
+        case LNB_NORM_CHAIN64: return report_launch(launch_chain_t<64, 1, 12288, 6, 8, EPI_STORE, true, false, true>, p, st);
+        case LNB_NORM_QUAD24: return report_launch(launch_quad_t<24, 256, 6, LNB_QUAD_R, EPI_STORE, true, true>, p, st);
+        case LNB_NORM_QUAD24_SCHED: return report_launch(launch_quad_t<24, 128, 6, 10, EPI_STORE, true, true>, p, st);
+        case LNB_NORM_GATE_UP56: return report_launch(launch_chain_t<56, 2, 14336, 7, 8, EPI_SILU_MUL, true, false, true>, p, st);
+        case LNB_NORM_GATE_UP28: return report_launch(launch_chain_t<28, 2, 14336, 7, 8, EPI_SILU_MUL, true, false, true>, p, st);
+        case LNB_NORM_GATE_UP56_PACKED: if (!p->wp || !lnbk_w13p_supported(56, p->K)) return hipErrorInvalidValue;
+                return report_launch(launch_chain_t<56, 2, 28672, 7, LNB_W13P_R, EPI_SILU_MUL, true, true, true>, p, st);
+        case LNB_NORM_HEAD_PACKED: if (!p->wp || p->S != 1 || !lnbk_headp_supported(p->K) || p->n_blocks != wpack_head_blocks(p->n_rows)) return hipErrorInvalidValue;
+                return report_launch(launch_chain_t<WPACK_HEAD_RW, 2, 32768, WPACK_HEAD_LANES / 64, LNB_HEADP_R, EPI_STORE2, true, true, true>, p, st);
+        default: return hipErrorInvalidValue;
+    }
+}
 // w: the resident 64-row one-chain layout of the [N][K] matrix
 extern "C" hipError_t lnbk_wpack_head(const uint16_t* w, void* out, int N, int K, unsigned base, hipStream_t st) {
     const size_t n = (size_t)wpack_head_blocks(N) * wpack_head_stages(K) * WPACK_HEAD_LANES;
@@ -5140,17 +5032,23 @@ extern "C" hipError_t lnbk_gemm(const GemmParams* p, int epi, hipStream_t st) {
         default: return hipErrorInvalidValue;
     }
 }
-extern "C" hipError_t lnbk_rmsnorm_rows(const uint16_t* x, const uint16_t* w, uint16_t* out, int S, int K, float eps, hipStream_t st) {
+// form 0: by knob and shape (production); 1 / 2: the wide / the one-wave kernel or an error, whatever the knob says (lnb_op_rmsnorm_sum).  norm_out: the kernels' report argument, [S][3] words or null
+extern "C" hipError_t lnbk_rmsnorm_rows_form(const uint16_t* x, const uint16_t* w, uint16_t* out, int S, int K, float eps, int form, uint32_t* norm_out, hipStream_t st) {
     const size_t lds_w = bn_scratch() + ((size_t)bn_kpad(K) + 8) * 4;                  // one workgroup of seven waves per row: the exact parallel evaluation of the serial sum
-    if (knob(Knob::NORM_ROWS_WIDE) && !(K & 127) && lds_w <= 64 * 1024 && (size_t)bn_kpad(K) <= (size_t)XCh<true>::value * (1 + BN_NH) * 512 && seq_leaf_size(K, rms_nf(BN_NH) * 64) <= 256) {
+    if ((form ? form == 1 : knob(Knob::NORM_ROWS_WIDE) != 0) && !(K & 127) && lds_w <= 64 * 1024 && (size_t)bn_kpad(K) <= (size_t)XCh<true>::value * (1 + BN_NH) * 512 && seq_leaf_size(K, rms_nf(BN_NH) * 64) <= 256) {
         form_ran(Form::RMSNORM_ROWS_WIDE);
-        hipLaunchKernelGGL(batch_rmsnorm_xt_kernel<false>, dim3((unsigned)S), dim3((1 + BN_NH) * 64), lds_w, st, x, w, eps, out, K);
+        if (norm_out) hipLaunchKernelGGL((batch_rmsnorm_xt_kernel<false, true>), dim3((unsigned)S), dim3((1 + BN_NH) * 64), lds_w, st, x, w, eps, out, K, norm_out);
+        else hipLaunchKernelGGL((batch_rmsnorm_xt_kernel<false, false>), dim3((unsigned)S), dim3((1 + BN_NH) * 64), lds_w, st, x, w, eps, out, K, norm_out);
         return hipGetLastError();
     }
-    if (((size_t)K + 64) * 4 > 150 * 1024) return hipErrorInvalidValue;
+    if (form == 1 || ((size_t)K + 64) * 4 > 150 * 1024) return hipErrorInvalidValue;
     form_ran(Form::RMSNORM_ROWS_WAVE);
-    hipLaunchKernelGGL(rmsnorm_rows_kernel, dim3((unsigned)S), dim3(64), ((size_t)K + 64) * 4, st, x, w, out, S, K, eps);
+    if (norm_out) hipLaunchKernelGGL(rmsnorm_rows_kernel<true>, dim3((unsigned)S), dim3(64), ((size_t)K + 64) * 4, st, x, w, out, S, K, eps, norm_out);
+    else hipLaunchKernelGGL(rmsnorm_rows_kernel<false>, dim3((unsigned)S), dim3(64), ((size_t)K + 64) * 4, st, x, w, out, S, K, eps, norm_out);
     return hipGetLastError();
+}
+extern "C" hipError_t lnbk_rmsnorm_rows(const uint16_t* x, const uint16_t* w, uint16_t* out, int S, int K, float eps, hipStream_t st) {
+    return lnbk_rmsnorm_rows_form(x, w, out, S, K, eps, 0, nullptr, st);
 }
 
 static size_t attn_lds_bytes(int seq_len, int hd) { return attn_off_ring(seq_len, hd) + 2 * (size_t)ATT_RP * hd * 4; }
@@ -5320,7 +5218,7 @@ extern "C" hipError_t lnbk_attn_plain(const AttnParams* p, const int* word, hipS
 extern "C" hipError_t lnbk_init(void) {
     static bool done = false;
     if (done) return hipSuccess;
-    hipError_t e = raise_lds(rmsnorm_rows_kernel);           // (lnbk_rmsnorm_rows' other form stays within the 64 KiB every kernel gets)
+    hipError_t e = raise_lds(rmsnorm_rows_kernel<false>, rmsnorm_rows_kernel<true>);           // (lnbk_rmsnorm_rows' other form stays within the 64 KiB every kernel gets)
     for (int ep = EPI_STORE; ep <= EPI_SILU_MUL && e == hipSuccess; ep++) e = lnbk_gemm(nullptr, ep, nullptr);
     // every (rows per block, chains, epilogue, norm) lnbk_gemv has kernels for
     auto gemv = [&](int rw, int nch, int epi, int norm) { if (e == hipSuccess) e = lnbk_gemv(nullptr, rw, nch, epi, norm, nullptr); };
@@ -5439,7 +5337,7 @@ extern "C" hipError_t lnbk_spin(int us, hipStream_t st) {
 extern "C" hipError_t lnbk_batch_prepare(void) {             // raise the dynamic-LDS limits once, outside any stream capture
     static bool done = false;
     if (done) return hipSuccess;
-    hipError_t e = raise_lds(batch_rmsnorm_xt_kernel<true>);
+    hipError_t e = raise_lds(batch_rmsnorm_xt_kernel<true, false>, batch_rmsnorm_xt_kernel<true, true>);
     for (int ep = EPI_STORE; ep <= EPI_SILU_MUL && e == hipSuccess; ep++) {
         if (pair_kernel(ep)) e = raise_lds(pair_kernel(ep));
         if (e == hipSuccess) e = lnbk_gemm_stream(nullptr, ep, 0, nullptr);
@@ -5447,12 +5345,16 @@ extern "C" hipError_t lnbk_batch_prepare(void) {             // raise the dynami
     done = e == hipSuccess;
     return e;
 }
-extern "C" hipError_t lnbk_batch_rmsnorm(const uint16_t* x, const uint16_t* norm_w, float eps, uint16_t* xt, int K, int nseq, hipStream_t st) {
+extern "C" hipError_t lnbk_batch_rmsnorm_out(const uint16_t* x, const uint16_t* norm_w, float eps, uint16_t* xt, int K, int nseq, uint32_t* norm_out, hipStream_t st) {
     const size_t lds = bn_scratch() + ((size_t)bn_kpad(K) + 8) * 4;
     if ((K & 127) || lds > 160 * 1024 || (size_t)bn_kpad(K) > (size_t)XCh<true>::value * (1 + BN_NH) * 512 || seq_leaf_size(K, rms_nf(BN_NH) * 64) > 256) return hipErrorInvalidValue;
     form_ran(Form::BATCH_RMSNORM);
-    hipLaunchKernelGGL(batch_rmsnorm_xt_kernel<true>, dim3((unsigned)nseq), dim3((1 + BN_NH) * 64), lds, st, x, norm_w, eps, xt, K);
+    if (norm_out) hipLaunchKernelGGL((batch_rmsnorm_xt_kernel<true, true>), dim3((unsigned)nseq), dim3((1 + BN_NH) * 64), lds, st, x, norm_w, eps, xt, K, norm_out);
+    else hipLaunchKernelGGL((batch_rmsnorm_xt_kernel<true, false>), dim3((unsigned)nseq), dim3((1 + BN_NH) * 64), lds, st, x, norm_w, eps, xt, K, norm_out);
     return hipGetLastError();
+}
+extern "C" hipError_t lnbk_batch_rmsnorm(const uint16_t* x, const uint16_t* norm_w, float eps, uint16_t* xt, int K, int nseq, hipStream_t st) {
+    return lnbk_batch_rmsnorm_out(x, norm_w, eps, xt, K, nseq, nullptr, st);
 }
 extern "C" hipError_t lnbk_batch_embed(const uint16_t* emb, const BatchTab* tab, uint16_t* x, int nseq, int dim, int vocab, int* err, hipStream_t st) {
     hipLaunchKernelGGL(batch_embed_kernel, dim3((unsigned)nseq), dim3(256), 0, st, emb, tab, x, dim, vocab, err);

@@ -217,6 +217,32 @@ SEQ_HD SeqSplit seq_split_leaf(const float* p, int n, float lo, float hi) {
     return r;
 }
 
+// ---- folding waves of the RMSNorm prologue: every helper wave of a norm-carrying kernel, LNB_RMS_NF_MAX at most ------------------------------------------
+#ifndef LNB_RMS_NF_MAX
+#define LNB_RMS_NF_MAX 8
+#endif
+SEQ_HD constexpr int rms_nf(int NH) { return NH > LNB_RMS_NF_MAX ? LNB_RMS_NF_MAX : NH; }
+// helper waves of the kernels that carry a norm (their NH template arguments in lnb_kernels.hip / BN_NH of lnb_batch_kernels.h): 16-row chain; 32- / 64-row
+// chain, 24-row quad and the two stand-alone norm kernels; gate|up (raw and packed); the packed LM head
+#define LNB_RMS_NORM_HELPERS {2, 6, 7, 8}
+// every launch function of a norm-carrying kernel asserts this of its NH (lnb_kernels.hip: launch_chain_x, launch_quad_x, BN_NH): a new helper count cannot
+// ship without entering the list the host emulation is fuzzed on (tests/test_seqsum.py reads it through seqsum_folding_waves)
+SEQ_HD constexpr bool rms_norm_helpers_has(int nh) { constexpr int l[] = LNB_RMS_NORM_HELPERS; for (int v : l) if (v == nh) return true; return false; }
+
+// ---- the walker's path word (lnb_op_rmsnorm_sum; tests/native/seqsum_host.cpp returns the same encoding) ------------------------
+// The item list was walked to its end (no RMS_PATH_LEFT bit):  items << 16 | split leaves << 8 | single-term items.
+// (A split leaf is two items; it is counted by its second one -- the crossing term and the map behind it -- the only kind with a term AND a binade.)
+// The list was left for the record walk: why (FLAGGED: a folding wave flagged its segment -- NOFIT, UNCOVERED or SCANFAIL say how; OVER64: more than 64 items;
+// CHECK: an item's check failed), bits 20..27 = the flagging waves, bits 8..15 = the item total & 0xFF, bits 0..7 = the leaf replays of the record walk (<= 255).
+#define RMS_PATH_FLAGGED (1u << 28)
+#define RMS_PATH_OVER64 (2u << 28)
+#define RMS_PATH_CHECK (4u << 28)
+#define RMS_PATH_LEFT (7u << 28)
+#define RMS_PATH_NOFIT (1u << 19)        // a wave's items do not fit its 128-entry list segment
+#define RMS_PATH_UNCOVERED (1u << 18)    // a leaf that no item covers: a non-finite (or overflowing) tree sum
+#define RMS_PATH_SCANFAIL (1u << 17)     // a composition of the segmented scan failed: that wave's records are walked by rms_walk_heap
+#define RMS_PATH_SERIAL 0xFFFFFFFFu      // rmsnorm_rows_kernel: no item list, the plain serial loop
+
 // ---- segmented inclusive scan of leaf maps (one wave = 64 leaves) -------------------------------------------------
 // a leaf starts a new run when it or its left neighbour is invalid, when the binade changes, or when forced
 SEQ_HD int seq_is_start(int lane, const SeqNode& me, const SeqNode& left, int forced) {

@@ -76,6 +76,7 @@ EXPORTS = [
     "lnb_forward_append_many", "lnb_model_append_many_info",
     "lnb_decode_speculative_many",
     "lnb_form_count", "lnb_form_count_reset", "lnb_form_name",
+    "lnb_op_rmsnorm_sum",
 ]
 EPILOGUES = {"store": 0, "qkv_rope": 1, "resid": 2, "silu_mul": 3}      # EPI_* of csrc/lnb_device.h: the second index of the launch tally
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
@@ -220,6 +221,7 @@ def lib():
     L.lnb_model_wpack_head_bytes.argtypes = [vp]
     L.lnb_model_wpack_head_bytes.restype = C.c_int64
     L.lnb_model_wpack_head_status.argtypes = [vp]
+    L.lnb_op_rmsnorm_sum.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]
     L.lnb_op_rmsnorm_head.argtypes = [C.c_int, vp, vp, C.c_float, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.lnb_batch_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp)]
     L.lnb_batch_destroy.argtypes = [vp]
@@ -1211,6 +1213,30 @@ def _splitmix64(z):
 def synth_tokens(seed, n, vocab):
     """Synthetic prompt of DESIGN.md ("Synthetic weights"): tok[i] = splitmix64(seed ^ i*golden) mod vocab."""
     return np.array([_splitmix64(seed ^ ((i * 0x9E3779B97F4A7C15) & _M64)) % vocab for i in range(n)], dtype=np.int32)
+
+
+# LNB_NORM_* of include/lnb.h: name -> (form, the launch tally's row, its epilogue, folding waves; None: the plain serial loop)
+NORM_FORMS = {
+    "chain16": (0, "gemv_chain.rw16", "store", 2), "chain32": (1, "gemv_chain.rw32", "store", 6), "chain64": (2, "gemv_chain.rw64", "store", 6),
+    "quad24": (3, "gemv_quad", "store", 6), "quad24_sched": (4, "gemv_quad", "store", 6),
+    "gate_up56": (5, "gemv_chain.rw56", "silu_mul", 7), "gate_up28": (6, "gemv_chain.rw28", "silu_mul", 7),
+    "gate_up56_packed": (7, "gemv_chain_pk", "silu_mul", 7), "head_packed": (8, "gemv_head_pk", "store", 8),
+    "rows_wide": (9, "rmsnorm_rows.wide", "store", 6), "batch_xt": (10, "batch_rmsnorm", "store", 6),
+    "rows_wave": (11, "rmsnorm_rows.wave", "store", None),
+}
+
+
+def op_rmsnorm_sum(x_u16, eps, form, device=0):
+    """what the norm of the kernel form `form` (a key of NORM_FORMS) computed for every row of x [rows][K] -> (sum_bits uint32 [rows],
+    scale_bits uint32 [rows], walk int32 [rows]: the path words of include/lnb.h), or None when the form's launch function refuses this K"""
+    x = np.ascontiguousarray(x_u16, dtype=np.uint16)
+    rows, k = x.shape
+    sb, rb, wk = np.empty(rows, dtype=np.uint32), np.empty(rows, dtype=np.uint32), np.empty(rows, dtype=np.int32)
+    rc = lib().lnb_op_rmsnorm_sum(device, _p(x), rows, k, np.float32(eps), NORM_FORMS[form][0], _p(sb), _p(rb), _p(wk))
+    if rc == 1:
+        return None
+    _chk(rc)
+    return sb, rb, wk
 
 
 def op_rmsnorm_head(x_u16, norm_w_u16, eps, w_u16, packed=1, n_wg=0, device=0):

@@ -237,7 +237,8 @@ const float* orc_silu_table(void) {   /* activations.go:15-25 */
 /* ---------------------------------------------------------------- RMSNorm */
 /* llamatransformer.go:633-660 -> Pow(x,2) impl:197-217; Mean impl:236-251; AddScalar :262-267;
    RSqrt :298-301; MultiplyElementwise(x,h) -> bf16 (trunc); MultiplyElementwise(h, weights) -> bf16 */
-void orc_rmsnorm_bf16(const uint16_t* x, const uint16_t* w, uint16_t* y, int rows, int dim, float eps, uint16_t* pre) {
+/* per row: the serial f32 sum of squares and rs = f32(1 / sqrt(f64(sum / dim + eps))) -- the one statement of the reference's loop (either output may be NULL) */
+void orc_rmsnorm_stats(const uint16_t* x, int rows, int dim, float eps, float* sum_out, float* rs_out) {
     for (int r = 0; r < rows; r++) {
         const uint16_t* xr = x + (size_t)r * dim;
         float sum = 0.0f;
@@ -245,6 +246,15 @@ void orc_rmsnorm_bf16(const uint16_t* x, const uint16_t* w, uint16_t* y, int row
         float mean = sum / (float)dim;
         mean = mean + eps;
         float rs = (float)(1.0 / sqrt((double)mean));
+        if (sum_out) sum_out[r] = sum;
+        if (rs_out) rs_out[r] = rs;
+    }
+}
+void orc_rmsnorm_bf16(const uint16_t* x, const uint16_t* w, uint16_t* y, int rows, int dim, float eps, uint16_t* pre) {
+    for (int r = 0; r < rows; r++) {
+        const uint16_t* xr = x + (size_t)r * dim;
+        float rs;
+        orc_rmsnorm_stats(xr, 1, dim, eps, NULL, &rs);
         for (int k = 0; k < dim; k++) {
             uint16_t h = trunc16(wide(xr[k]) * rs);
             if (pre) pre[(size_t)r * dim + k] = h;

@@ -67,6 +67,7 @@ int32_t orc_argmax_f32(const float* in, int n);
 /* activations.go:10-25 */
 const float* orc_silu_table(void);
 /* llamatransformer.go:633-660 : full RMSNorm on [rows,dim] bf16 */
+void orc_rmsnorm_stats(const uint16_t* x, int rows, int dim, float eps, float* sum_out, float* rs_out);   /* the sum and the scale orc_rmsnorm_bf16 uses */
 void orc_rmsnorm_bf16(const uint16_t* x, const uint16_t* w, uint16_t* y, int rows, int dim, float eps, uint16_t* pre_weight_opt);
 /* llamatransformer.go:662-751 : freqs (after optional scaling, bf16) and the cis table [rows][dim/2][2] f32 */
 void orc_rope_freqs(int head_dim, double theta, int use_scaled, uint16_t* freqs_out);

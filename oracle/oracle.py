@@ -56,6 +56,7 @@ def lib():
         "orc_argmax_f32": (C.c_int32, [vp, C.c_int]),
         "orc_silu_table": (f32p, []),
         "orc_rmsnorm_bf16": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_float, vp]),
+        "orc_rmsnorm_stats": (None, [vp, C.c_int, C.c_int, C.c_float, vp, vp]),
         "orc_rope_freqs": (None, [C.c_int, C.c_double, C.c_int, vp]),
         "orc_rope_table": (None, [C.c_int, C.c_int, C.c_double, C.c_int, vp, vp]),
         "orc_rope_apply": (None, [vp, C.c_int, C.c_int, C.c_int, vp]),

@@ -25,7 +25,17 @@ def lib():
     L.seqsum_items.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.seqsum_tree.restype = C.c_float
     L.seqsum_tree.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.seqsum_device.restype = C.c_float
+    L.seqsum_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+    L.seqsum_folding_waves.argtypes = [C.POINTER(C.c_int), C.c_int]
     return L
+
+
+def shipped_folding_waves(L):
+    """rms_nf of the helper counts of every kernel that carries a norm (csrc/lnb_seqsum.h): the wave counts the device folds on"""
+    out = (C.c_int * 16)()
+    n = L.seqsum_folding_waves(out, 16)
+    return sorted(set(out[:n]))
 
 
 def bf16(a):
@@ -126,3 +136,27 @@ def test_item_list_walk_is_bit_identical_and_rarely_falls_back(lib):
         fast_out.append(fast.value)
     print("rows with outlier channels: list sufficient for %.1f %%" % (100 * np.mean(fast_out)))
     assert np.mean(fast_out) > 0.9
+
+
+def test_the_fuzz_runs_the_folding_wave_counts_that_ship(lib):
+    """The device folds on 2, 6, 7 and 8 waves (LNB_RMS_NF_MAX = 8), so at K = 4096 its leaves are 32, 12, 12 and 8 terms: the item-list walk (the
+    device's own order of every approximate sum, its per-wave list segments, its single-term criterion) and the record walk at exactly those counts."""
+    waves = shipped_folding_waves(lib)
+    assert waves == [2, 6, 7, 8]
+    rng = np.random.default_rng(41)
+    done, gauss = {nh: 0 for nh in waves}, {nh: 0 for nh in waves}
+    for trial in range(3200):
+        K = [4096, 4096, 8192, 256, 512, 1024, 64, 3072, 5120, 8][trial % 10] if trial >= 1600 else 4096
+        NH = waves[(trial // 8) % len(waves)]
+        p = _cases(rng, K, trial)
+        path, ni = C.c_uint32(0), C.c_int(0)
+        r = lib.seqsum_ref(p.ctypes.data, K)
+        s = lib.seqsum_device(p.ctypes.data, K, NH, 256, C.byref(path), C.byref(ni))
+        assert np.float32(r).view(np.uint32) == np.float32(s).view(np.uint32), (trial, K, NH, hex(path.value))
+        t = lib.seqsum_tree(p.ctypes.data, K, NH, 256, None, None)
+        assert np.float32(r).view(np.uint32) == np.float32(t).view(np.uint32), (trial, K, NH)
+        if K == 4096 and trial % 8 == 0 and NH != 2:
+            gauss[NH] += 1
+            done[NH] += not (path.value & 0x70000000)
+    for nh in waves[1:]:                              # gaussian rows at K = 4096: the list suffices for nearly every one
+        assert gauss[nh] >= 40 and done[nh] > 0.9 * gauss[nh], (nh, done[nh], gauss[nh])
