@@ -26,6 +26,7 @@
 #include "lnb_rowpack.h"
 #include "lnb_wpack.h"
 #include "lnb_batchplan.h"
+#include "lnb_handoff.h"
 #include "lnb_rccl.h"
 #include "lnb_sample.h"
 static_assert(LNB_MAX_SEQ_LEN == LNB_SEQ_MAX, "lnb.h and lnb_device.h disagree on the longest context");
@@ -188,6 +189,26 @@ struct lnb_model {
     bool has_w2(int l) const { return has_part(l, 2); }
     bool whole(int l) const { return has_attn(l) && has_w13(l) && has_w2(l); }
 };
+// What a unit that moves through the pipeline's stages -- a context (lnb_pipeline_tick) or a batch (lnb_pipeline_tick_batch) -- needs to be
+// handed across a stage boundary: three events between its own stream and the pipe's exchange stream, and whether one is outstanding.
+struct PipeLink {
+    hipEvent_t ev_done = nullptr, ev_in = nullptr, ev_sent = nullptr;   // its stage step has run / its input has arrived / its output has left
+    bool in_pending = false, sent_pending = false;
+    bool recv_unmatched = false;           // in-process transport: a receive into this unit is posted and its sender has not arrived yet
+    int ensure() {                         // (created on the unit's first tick)
+        if (!ev_done) for (hipEvent_t* e : {&ev_done, &ev_in, &ev_sent}) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        return 0;
+    }
+    void destroy() { for (hipEvent_t e : {ev_done, ev_in, ev_sent}) if (e) hipEventDestroy(e); }
+    // before the unit's stage step on its stream st: its input has arrived and its previous output has left
+    int await(hipStream_t st, const char* unit) {
+        if (recv_unmatched) return fail("in-process pipeline: this %s's input has been requested but the sending stage has not posted it yet "
+                                        "(the mailbox transport needs the stages ticked in lock-step order from one thread)", unit);
+        if (in_pending) { HIPCHK(hipStreamWaitEvent(st, ev_in, 0)); in_pending = false; }
+        if (sent_pending) { HIPCHK(hipStreamWaitEvent(st, ev_sent, 0)); sent_pending = false; }
+        return 0;
+    }
+};
 struct lnb_ctx {
     lnb_model* m = nullptr; int seq_len = 0;
     int max_rows = 0;                      // rows per call the activation buffers (x, h, xn, q, att, ffn) hold: seq_len, or lnb_ctx_create_long's max_rows
@@ -222,13 +243,11 @@ struct lnb_ctx {
     LnbSampler* d_smp = nullptr;
     // pipeline stage (lnb_pipeline_tick): one-token stage step as a captured graph per attention form, events towards / from the exchange stream
     hipGraphExec_t stage_graph[2] = {nullptr, nullptr};
-    hipEvent_t ev_done = nullptr, ev_in = nullptr, ev_sent = nullptr;
-    bool in_pending = false, sent_pending = false;
+    PipeLink link;
     int dev_pos = -1;                      // position the device-side StepState will hold when the stream reaches this point (-1: unknown)
     bool attn_causal = false;              // set by lnb_forward_append around its multi-row call: the attention launches take the true causal mask (AttnParams::causal)
     int call_T = 0;                        // start_pos + rows of the call being enqueued (0: not known to the host, e.g. inside a replayed graph)
     hipEvent_t ev_h2d = nullptr; bool h2d_pending = false;   // the last copy out of the pinned staging words h_io[2..] (enqueue-only paths)
-    bool recv_unmatched = false;           // in-process transport: a receive into this context is posted and its sender has not arrived yet
     // token probabilities of the greedy loop (lnb_ctx_set_token_probs): a record log of dout_cap x top_k beside the token log
     int top_k = 0;
     TokProbOut* tp_out = nullptr;          // device: this context's log (st = c->st: the record slot is the token's)
@@ -943,9 +962,7 @@ extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
     hipSetDevice(c->m->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     drop_graphs(c);
-    if (c->ev_done) hipEventDestroy(c->ev_done);
-    if (c->ev_in) hipEventDestroy(c->ev_in);
-    if (c->ev_sent) hipEventDestroy(c->ev_sent);
+    c->link.destroy();
     if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
     hipFree(c->e_buf); hipFree(c->z_part); hipFree(c->zseq_count); hipFree(c->attn_cnt); if (c->score_idx) hipFree(c->score_idx);
     tp_free(c); if (c->sc_buf) hipFree(c->sc_buf); if (c->fork_tab) hipFree(c->fork_tab);
@@ -2057,7 +2074,7 @@ struct lnb_batch {
     // pipeline stage (lnb_pipeline_tick_batch): the contiguous token words exchanged between the last and the first stage, the stage step
     // as a captured graph, events towards / from the exchange stream (as lnb_ctx has them for single-sequence ticks)
     int32_t* ring = nullptr; hipGraphExec_t stage_graph = nullptr;
-    hipEvent_t ev_done = nullptr, ev_in = nullptr, ev_sent = nullptr; bool in_pending = false, sent_pending = false, recv_unmatched = false;
+    PipeLink link;
     // token probabilities (the members' lnb_ctx_set_token_probs, one top_k for all): one row per sequence into its context's log
     int top_k = 0; TokProbOut* tp_out = nullptr; double* tp_zpart = nullptr; uint64_t* tp_kpart = nullptr; unsigned* tp_cnt = nullptr;
     // speculative verify batch (lnb_decode_speculative_until): every column is ONE context (ctxs[s] = it, the same caches); columns s >= 1 take
@@ -2153,9 +2170,7 @@ extern "C" int lnb_batch_destroy(lnb_batch* b) {
     hipFree(b->tab); hipFree(b->kv); hipFree(b->d_tokens); hipFree(b->d_pos); hipFree(b->ring);
     hipFree(b->tp_out); hipFree(b->tp_zpart); hipFree(b->tp_kpart); hipFree(b->tp_cnt);
     if (b->stage_graph) hipGraphExecDestroy(b->stage_graph);
-    if (b->ev_done) hipEventDestroy(b->ev_done);
-    if (b->ev_in) hipEventDestroy(b->ev_in);
-    if (b->ev_sent) hipEventDestroy(b->ev_sent);
+    b->link.destroy();
     if (b->h_io) hipHostFree(b->h_io);
     if (b->ev0) hipEventDestroy(b->ev0);
     if (b->ev1) hipEventDestroy(b->ev1);
@@ -3239,8 +3254,9 @@ extern "C" int lnb_decode_speculative_many(lnb_ctx* const* ctxs, int n, const in
 // "send" meets its "receive" in a mailbox; whichever side is posted second enqueues the device copy.  Same tick code, same events, same
 // graphs as the RCCL transport -- what it replaces is only ncclSend / ncclRecv.  Used to test host schedules where RCCL cannot run
 // (two ranks need two GPUs) and by single-process multi-GPU hosts.
-struct LoopMsg { lnb_ctx* ctx; int rows; lnb_batch* bat = nullptr; };   // a single-sequence hand-off (ctx) or a batch's (bat)
-struct LoopGroup { std::map<std::pair<int, int>, std::deque<LoopMsg>> sends, recvs; int users = 0; int device = -1; };
+// What crosses a boundary (the hidden state, the gate*up activations behind a gate/up part, the token word between the last and the first
+// stage) and when a send fits a receive is decided in lnb_handoff.h; pipe_exchange below enqueues what it says, for either transport.
+struct LoopGroup { HandoffBox box; int users = 0; int device = -1; };   // (a posted hand-off's owner is its unit's PipeLink)
 static std::map<std::string, LoopGroup> g_loops;
 static std::mutex g_loops_mu;
 
@@ -3267,32 +3283,9 @@ extern "C" int lnb_pipeline_unique_id(void* id128) {
     memcpy(id128, &id, sizeof id);
     return 0;
 }
-extern "C" int lnb_pipeline_init(lnb_model* m, int rank, int world, const void* id128, lnb_pipe** out) {
+// What the three kinds of pipe share: the argument checks, the exchange stream and the pinned token log.  *out holds the pipe on success.
+static int pipe_new(lnb_model* m, int rank, int world, lnb_pipe** out) {
     if (!m || !out) return fail("null argument");
-    *out = nullptr;
-    if (world < 1 || rank < 0 || rank >= world) return fail("rank %d out of range for %d pipeline stages", rank, world);
-    if (!m->finalized) return fail("model not finalized");
-    if ((rank == 0) != m->first()) return fail("pipeline rank %d: only the first stage owns tok_embeddings (this stage starts at block part %d)", rank, m->part_begin);
-    if ((rank == world - 1) != m->last()) return fail("pipeline rank %d of %d: only the last stage owns norm + output (this stage ends at block part %d)", rank, world, m->part_end);
-    if (world > 1 && !id128) return fail("null unique id");
-    HIPCHK(hipSetDevice(m->device));
-    lnb_pipe* p = new lnb_pipe();
-    p->m = m; p->rank = rank; p->world = world; p->use_graph = pipe_use_graph();
-    if (world > 1) {
-        p->api = lnb_rccl_load();
-        if (!p->api) { delete p; return -1; }
-        lnb_nccl_id id; memcpy(&id, id128, sizeof id);
-        int r = p->api->CommInitRank(&p->comm, world, id, rank);
-        if (r != 0) { fail("ncclCommInitRank failed: %s", p->api->GetErrorString(r)); delete p; return -1; }
-    }
-    hipError_t e = hipStreamCreateWithFlags(&p->xs, hipStreamNonBlocking);
-    if (e == hipSuccess) { p->tok_cap = pipe_log_cap(); e = hipHostMalloc((void**)&p->h_tok, (size_t)p->tok_cap * 4, hipHostMallocDefault); }
-    if (e != hipSuccess) { fail("pipeline init: %s", hipGetErrorString(e)); if (p->comm) p->api->CommDestroy(p->comm); if (p->xs) hipStreamDestroy(p->xs); delete p; return -1; }
-    *out = p;
-    return 0;
-}
-extern "C" int lnb_pipeline_init_loopback(lnb_model* m, int rank, int world, const char* group, lnb_pipe** out) {
-    if (!m || !out || !group) return fail("null argument");
     *out = nullptr;
     if (world < 1 || rank < 0 || rank >= world) return fail("rank %d out of range for %d pipeline stages", rank, world);
     if (!m->finalized) return fail("model not finalized");
@@ -3304,39 +3297,48 @@ extern "C" int lnb_pipeline_init_loopback(lnb_model* m, int rank, int world, con
     hipError_t e = hipStreamCreateWithFlags(&p->xs, hipStreamNonBlocking);
     if (e == hipSuccess) { p->tok_cap = pipe_log_cap(); e = hipHostMalloc((void**)&p->h_tok, (size_t)p->tok_cap * 4, hipHostMallocDefault); }
     if (e != hipSuccess) { fail("pipeline init: %s", hipGetErrorString(e)); if (p->xs) hipStreamDestroy(p->xs); delete p; return -1; }
+    *out = p;
+    return 0;
+}
+// an entry point whose own part failed (the error is set; no communicator, no group joined): what pipe_new made goes, nothing enqueued yet
+static int pipe_abandon(lnb_pipe** out) { hipStreamDestroy((*out)->xs); hipHostFree((*out)->h_tok); delete *out; *out = nullptr; return -1; }
+extern "C" int lnb_pipeline_init(lnb_model* m, int rank, int world, const void* id128, lnb_pipe** out) {
+    if (pipe_new(m, rank, world, out)) return -1;
+    lnb_pipe* p = *out;
     if (world > 1) {
-        // The mailbox transport records a context's events on whichever pipe's exchange stream posts second, and a context's flags are
+        if (!id128) { fail("null unique id"); return pipe_abandon(out); }
+        p->api = lnb_rccl_load();
+        if (!p->api) return pipe_abandon(out);
+        lnb_nccl_id id; memcpy(&id, id128, sizeof id);
+        int r = p->api->CommInitRank(&p->comm, world, id, rank);
+        if (r != 0) { fail("ncclCommInitRank failed: %s", p->api->GetErrorString(r)); p->comm = nullptr; return pipe_abandon(out); }
+    }
+    return 0;
+}
+extern "C" int lnb_pipeline_init_loopback(lnb_model* m, int rank, int world, const char* group, lnb_pipe** out) {
+    if (!group) return fail("null argument");
+    if (pipe_new(m, rank, world, out)) return -1;
+    lnb_pipe* p = *out;
+    if (world > 1) {
+        // The mailbox transport records a unit's events on whichever pipe's exchange stream posts second, and a unit's flags are
         // plain fields: every stage of a group must live on ONE device and be ticked from ONE host thread in lock-step order (what the
         // tests and single-process hosts do).  One stage per GPU is the RCCL transport's job (lnb_pipeline_init).
         std::lock_guard<std::mutex> lock(g_loops_mu);
         LoopGroup& g = g_loops[group];
         if (g.users > 0 && g.device != m->device) {
-            const int have = g.device;
-            hipStreamDestroy(p->xs); hipHostFree(p->h_tok); delete p;
-            return fail("in-process pipeline group \"%s\" lives on device %d: a stage on device %d cannot join it (use lnb_pipeline_init for one stage per GPU)", group, have, m->device);
+            fail("in-process pipeline group \"%s\" lives on device %d: a stage on device %d cannot join it (use lnb_pipeline_init for one stage per GPU)", group, g.device, m->device);
+            return pipe_abandon(out);                        // (it has not joined the group)
         }
         g.device = m->device;
         p->loop_tag = group; p->loop = &g; p->loop->users++;
     }
-    *out = p;
     return 0;
 }
 // The pipe WITHOUT a transport: stage steps, graphs, positions and the token log as in the other two, but what crosses the stage boundary is
 // moved by the host layer (pipeline.py's torch.distributed fallback: staging tensors + batch_isend_irecv) between lnb_pipeline_sync calls.
 extern "C" int lnb_pipeline_init_host(lnb_model* m, int rank, int world, lnb_pipe** out) {
-    if (!m || !out) return fail("null argument");
-    *out = nullptr;
-    if (world < 1 || rank < 0 || rank >= world) return fail("rank %d out of range for %d pipeline stages", rank, world);
-    if (!m->finalized) return fail("model not finalized");
-    if ((rank == 0) != m->first()) return fail("pipeline rank %d: only the first stage owns tok_embeddings (this stage starts at block part %d)", rank, m->part_begin);
-    if ((rank == world - 1) != m->last()) return fail("pipeline rank %d of %d: only the last stage owns norm + output (this stage ends at block part %d)", rank, world, m->part_end);
-    HIPCHK(hipSetDevice(m->device));
-    lnb_pipe* p = new lnb_pipe();
-    p->m = m; p->rank = rank; p->world = world; p->host = true; p->use_graph = pipe_use_graph();
-    hipError_t e = hipStreamCreateWithFlags(&p->xs, hipStreamNonBlocking);
-    if (e == hipSuccess) { p->tok_cap = pipe_log_cap(); e = hipHostMalloc((void**)&p->h_tok, (size_t)p->tok_cap * 4, hipHostMallocDefault); }
-    if (e != hipSuccess) { fail("pipeline init: %s", hipGetErrorString(e)); if (p->xs) hipStreamDestroy(p->xs); delete p; return -1; }
-    *out = p;
+    if (pipe_new(m, rank, world, out)) return -1;
+    (*out)->host = true;
     return 0;
 }
 extern "C" int lnb_pipeline_destroy(lnb_pipe* p) {
@@ -3348,11 +3350,6 @@ extern "C" int lnb_pipeline_destroy(lnb_pipe* p) {
     if (p->xs) hipStreamDestroy(p->xs);
     if (p->h_tok) hipHostFree(p->h_tok);
     delete p;
-    return 0;
-}
-static int pipe_events(lnb_ctx* c) {
-    if (!c->ev_done) { HIPCHK(hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
-                       HIPCHK(hipEventCreateWithFlags(&c->ev_sent, hipEventDisableTiming)); }
     return 0;
 }
 // one stage step on the context's stream; tokens != NULL: host tokens (prefill on rank 0); NULL on rank 0: the token already sits in
@@ -3395,42 +3392,70 @@ static int enqueue_stage_step(lnb_pipe* p, lnb_ctx* c, const int32_t* tokens, in
     if (rows == 1 && !tokens) form_ran(Form::PIPELINE_EAGER);
     return body(tokens != nullptr);
 }
-// What crosses the boundary behind this stage (towards rank+1) / in front of it: the [rows, dim] hidden state, plus the [rows, ffn_hidden]
-// gate*up activations when the cut lies between a block's gate/up and down parts.
-static int pipe_xfer(lnb_pipe* p, lnb_ctx* c, int rows, bool sending) {
-    lnb_model* m = c->m;
-    const int edge = sending ? m->part_end : m->part_begin, peer = sending ? p->rank + 1 : p->rank - 1;
-    const size_t nx = (size_t)rows * m->a.dim * 2, nf = (size_t)rows * m->ffn_hidden * 2;
-    if (sending) { NCCLCHK(p, p->api->Send(c->x, nx, LNB_NCCL_INT8, peer, p->comm, p->xs)); if (edge % 3 == 2) NCCLCHK(p, p->api->Send(c->ffn, nf, LNB_NCCL_INT8, peer, p->comm, p->xs)); }
-    else { NCCLCHK(p, p->api->Recv(c->x, nx, LNB_NCCL_INT8, peer, p->comm, p->xs)); if (edge % 3 == 2) NCCLCHK(p, p->api->Recv(c->ffn, nf, LNB_NCCL_INT8, peer, p->comm, p->xs)); }
+// n tokens of the last stage, device words at src, appended to the pinned ring on stream st (the ring keeps the newest tok_cap tokens)
+static int pipe_log_tokens(lnb_pipe* p, const int32_t* src, int n, hipStream_t st, int* slot_out) {
+    const int slot = p->tok_n, at = slot % p->tok_cap, fit = std::min(n, p->tok_cap - at);
+    HIPCHK(hipMemcpyAsync(p->h_tok + at, src, (size_t)fit * 4, hipMemcpyDeviceToHost, st));
+    if (fit < n) HIPCHK(hipMemcpyAsync(p->h_tok, src + fit, (size_t)(n - fit) * 4, hipMemcpyDeviceToHost, st));
+    if (slot_out) *slot_out = slot;
+    p->tok_n += n;
     return 0;
 }
-// mailbox transport: `mine` is posted now; if its counterpart is already waiting, enqueue the copy on this pipe's exchange stream
-static int loop_copy(lnb_pipe* p, const LoopMsg& s, const LoopMsg& r, bool token) {
-    HIPCHK(hipStreamWaitEvent(p->xs, s.ctx->ev_done, 0));   // the result has been computed
-    HIPCHK(hipStreamWaitEvent(p->xs, r.ctx->ev_done, 0));   // nothing still reads the buffer being overwritten
-    if (token) HIPCHK(hipMemcpyAsync(r.ctx->dtok, s.ctx->dnext, 4, hipMemcpyDeviceToDevice, p->xs));
-    else {
-        if (s.rows != r.rows) return fail("loopback exchange: %d rows sent, %d rows expected", s.rows, r.rows);
-        lnb_model* sm = s.ctx->m;
-        HIPCHK(hipMemcpyAsync(r.ctx->x, s.ctx->x, (size_t)s.rows * sm->a.dim * 2, hipMemcpyDeviceToDevice, p->xs));
-        if (sm->part_end % 3 == 2) HIPCHK(hipMemcpyAsync(r.ctx->ffn, s.ctx->ffn, (size_t)s.rows * sm->ffn_hidden * 2, hipMemcpyDeviceToDevice, p->xs));
+// One side of a tick's exchange: the unit's link and stream, what lnb_handoff.h says crosses the boundary, and where those segments live.
+struct PipeSide { PipeLink* link; hipStream_t stream; HandoffPlan plan; void* ptr[2]; };
+static void* ctx_buf(lnb_ctx* c, HandoffBuf which) { return which == HB_HIDDEN ? (void*)c->x : which == HB_ACTS ? (void*)c->ffn : which == HB_TOKEN_OUT ? (void*)c->dnext : (void*)c->dtok; }
+static PipeSide pipe_side(lnb_pipe* p, lnb_ctx* c, int rows, bool sending) {
+    const lnb_model* m = p->m;
+    PipeSide s{&c->link, c->stream, handoff_plan(p->rank, p->world, m->part_begin, m->part_end, sending, HU_SEQUENCE, rows, m->a.dim, m->ffn_hidden), {nullptr, nullptr}};
+    for (int i = 0; i < s.plan.nseg; i++) s.ptr[i] = ctx_buf(c, s.plan.seg[i].buf);
+    return s;
+}
+static PipeSide pipe_side(lnb_pipe* p, lnb_batch* b, bool sending) {
+    const lnb_model* m = p->m;
+    PipeSide s{&b->link, b->stream, handoff_plan(p->rank, p->world, m->part_begin, m->part_end, sending, HU_BATCH, b->n, m->a.dim, m->ffn_hidden), {nullptr, nullptr}};
+    for (int i = 0; i < s.plan.nseg; i++) s.ptr[i] = s.plan.seg[i].buf == HB_RING ? (void*)b->ring : (void*)b->x;
+    return s;
+}
+// The exchange of a tick, after its run part: send and / or recv (NULL: none) on the pipe's exchange stream.
+static int pipe_exchange(lnb_pipe* p, const PipeSide* send, const PipeSide* recv) {
+    if (p->world < 2 || (!send && !recv)) return 0;
+    if (p->loop) {                                           // in-process transport: whichever side is posted second enqueues the copy
+        if (recv) HIPCHK(hipEventRecord(recv->link->ev_done, recv->stream));
+        for (const PipeSide* mine : {send, recv}) if (mine) {
+            std::lock_guard<std::mutex> lock(g_loops_mu);
+            const HandoffMsg msg{mine->link, mine->plan, {mine->ptr[0], mine->ptr[1]}};
+            HandoffMsg other; char why[320];
+            const HandoffBox::Result res = p->loop->box.post(p->rank, msg, &other, why, sizeof why);
+            if (res == HandoffBox::QUEUED) { if (mine == recv) mine->link->recv_unmatched = true; continue; }
+            const HandoffMsg &s = mine == send ? msg : other, &r = mine == send ? other : msg;
+            PipeLink *sl = (PipeLink*)s.owner, *rl = (PipeLink*)r.owner;
+            rl->recv_unmatched = false;                      // (its message has left the mailbox, matched or refused)
+            if (res == HandoffBox::REFUSED) return fail("%s", why);
+            HIPCHK(hipStreamWaitEvent(p->xs, sl->ev_done, 0));   // the result has been computed
+            HIPCHK(hipStreamWaitEvent(p->xs, rl->ev_done, 0));   // nothing still reads the buffers being overwritten
+            for (int i = 0; i < s.plan.nseg; i++) HIPCHK(hipMemcpyAsync(r.ptr[i], s.ptr[i], s.plan.seg[i].bytes, hipMemcpyDeviceToDevice, p->xs));
+            HIPCHK(hipEventRecord(sl->ev_sent, p->xs)); sl->sent_pending = true;
+            HIPCHK(hipEventRecord(rl->ev_in, p->xs)); rl->in_pending = true;
+        }
+        return 0;
     }
-    HIPCHK(hipEventRecord(s.ctx->ev_sent, p->xs)); s.ctx->sent_pending = true;
-    HIPCHK(hipEventRecord(r.ctx->ev_in, p->xs)); r.ctx->in_pending = true;
+    // RCCL: ONE group with every segment of the send and of the receive; GroupEnd is called whenever GroupStart succeeded
+    if (send) HIPCHK(hipStreamWaitEvent(p->xs, send->link->ev_done, 0));
+    if (recv) { HIPCHK(hipEventRecord(recv->link->ev_done, recv->stream)); HIPCHK(hipStreamWaitEvent(p->xs, recv->link->ev_done, 0)); }
+    NCCLCHK(p, p->api->GroupStart());
+    int bad = 0; const PipeSide* failed = nullptr;
+    for (const PipeSide* side : {send, recv}) if (side)
+        for (int i = 0; i < side->plan.nseg && !bad; i++) {
+            bad = side == send ? p->api->Send(side->ptr[i], side->plan.seg[i].bytes, LNB_NCCL_INT8, side->plan.peer, p->comm, p->xs)
+                               : p->api->Recv(side->ptr[i], side->plan.seg[i].bytes, LNB_NCCL_INT8, side->plan.peer, p->comm, p->xs);
+            if (bad) failed = side;
+        }
+    const int end = p->api->GroupEnd();
+    if (bad) return fail("RCCL exchange failed: %s rank %d: %s", failed == send ? "send to" : "receive from", failed->plan.peer, p->api->GetErrorString(bad));
+    if (end) return fail("RCCL exchange failed: ncclGroupEnd: %s", p->api->GetErrorString(end));
+    if (send) { HIPCHK(hipEventRecord(send->link->ev_sent, p->xs)); send->link->sent_pending = true; }
+    if (recv) { HIPCHK(hipEventRecord(recv->link->ev_in, p->xs)); recv->link->in_pending = true; }
     return 0;
-}
-static int loop_post(lnb_pipe* p, bool sending, lnb_ctx* c, int rows, int peer, bool token) {
-    std::lock_guard<std::mutex> lock(g_loops_mu);
-    const std::pair<int, int> key = sending ? std::make_pair(p->rank, peer) : std::make_pair(peer, p->rank);   // (source rank, destination rank)
-    auto& mine = sending ? p->loop->sends[key] : p->loop->recvs[key];
-    auto& theirs = sending ? p->loop->recvs[key] : p->loop->sends[key];
-    const LoopMsg msg{c, rows};
-    if (theirs.empty()) { mine.push_back(msg); if (!sending) c->recv_unmatched = true; return 0; }
-    const LoopMsg other = theirs.front(); theirs.pop_front();
-    if (other.bat) return fail("in-process pipeline: a single-sequence hand-off met a batch hand-off (the stages must post the same ticks in the same order)");
-    (sending ? other.ctx : c)->recv_unmatched = false;
-    return sending ? loop_copy(p, msg, other, token) : loop_copy(p, other, msg, token);
 }
 extern "C" int lnb_pipeline_tick(lnb_pipe* p, lnb_ctx* run, int run_rows, int run_pos, const int32_t* run_tokens,
                                  lnb_ctx* send, int send_rows, lnb_ctx* recv, int recv_rows, int* token_slot_out) {
@@ -3438,7 +3463,7 @@ extern "C" int lnb_pipeline_tick(lnb_pipe* p, lnb_ctx* run, int run_rows, int ru
     lnb_model* m = p->m;
     HIPCHK(hipSetDevice(m->device));
     const bool first = p->rank == 0, last = p->rank == p->world - 1;
-    for (lnb_ctx* c : {run, send, recv}) if (c) { if (c->m != m) return fail("context of another model stage"); if (pipe_events(c)) return -1; }
+    for (lnb_ctx* c : {run, send, recv}) if (c) { if (c->m != m) return fail("context of another model stage"); if (c->link.ensure()) return -1; }
     if (p->host && (send || recv)) return fail("this pipe has no transport (lnb_pipeline_init_host): the host layer moves lnb_ctx_hidden_ptr's buffers itself; send and recv must be NULL");
     if (token_slot_out) *token_slot_out = -1;
     if (send && send_rows > send->max_rows) return fail("a hand-off of %d rows from a context whose activation buffers hold %d rows (lnb_ctx_create_long's max_rows)", send_rows, send->max_rows);
@@ -3448,46 +3473,19 @@ extern "C" int lnb_pipeline_tick(lnb_pipe* p, lnb_ctx* run, int run_rows, int ru
         if (check_call(run, run_rows, run_pos)) return -1;
         if (run_tokens && !first) return fail("tokens given to a stage that does not own tok_embeddings");
         if (!run_tokens && first && run_rows != 1) return fail("the first stage needs host tokens for a multi-row step");
-        if (run->recv_unmatched) return fail("in-process pipeline: this sequence's input has been requested but the sending stage has not posted it yet "
-                                             "(the mailbox transport needs the stages ticked in lock-step order from one thread)");
-        if (run->in_pending) { HIPCHK(hipStreamWaitEvent(run->stream, run->ev_in, 0)); run->in_pending = false; }      // its input has arrived
-        if (run->sent_pending) { HIPCHK(hipStreamWaitEvent(run->stream, run->ev_sent, 0)); run->sent_pending = false; }  // its previous output has left
+        if (run->link.await(run->stream, "sequence")) return -1;
         if (enqueue_stage_step(p, run, run_tokens, run_rows, run_pos)) return -1;
         if (last) {
             if (p->tok_n == 0x7FFFFFFF) return fail("pipeline token log: slot counter exhausted (2^31 tokens): create a new pipe");
-            HIPCHK(hipMemcpyAsync(p->h_tok + p->tok_n % p->tok_cap, run->dnext, 4, hipMemcpyDeviceToHost, run->stream));   // (the ring keeps the newest tok_cap tokens)
-            if (token_slot_out) *token_slot_out = p->tok_n;
-            p->tok_n++;
+            if (pipe_log_tokens(p, run->dnext, 1, run->stream, token_slot_out)) return -1;
             if (p->world == 1) HIPCHK(hipMemcpyAsync(run->dtok, run->dnext, 4, hipMemcpyDeviceToDevice, run->stream));    // the ring of a one-stage pipe
         }
-        HIPCHK(hipEventRecord(run->ev_done, run->stream));
+        HIPCHK(hipEventRecord(run->link.ev_done, run->stream));
     }
-    if (p->world > 1 && p->loop && (send || recv)) {         // in-process transport
-        if (recv) HIPCHK(hipEventRecord(recv->ev_done, recv->stream));
-        if (send && loop_post(p, true, send, send_rows, last ? 0 : p->rank + 1, last)) return -1;
-        if (recv && loop_post(p, false, recv, recv_rows, first ? p->world - 1 : p->rank - 1, first)) return -1;
-        return 0;
-    }
-    if (p->world > 1 && (send || recv)) {
-        if (send) HIPCHK(hipStreamWaitEvent(p->xs, send->ev_done, 0));                 // the result being sent has been computed
-        if (recv) { HIPCHK(hipEventRecord(recv->ev_done, recv->stream)); HIPCHK(hipStreamWaitEvent(p->xs, recv->ev_done, 0)); }   // nothing still reads the buffer being overwritten
-        NCCLCHK(p, p->api->GroupStart());
-        int rc = 0;
-        if (send) {
-            if (last) { int r_ = p->api->Send(send->dnext, 4, LNB_NCCL_INT8, 0, p->comm, p->xs); if (r_) rc = fail("ncclSend failed: %s", p->api->GetErrorString(r_)); }
-            else rc = pipe_xfer(p, send, send_rows, true);
-        }
-        if (!rc && recv) {
-            if (first) { int r_ = p->api->Recv(recv->dtok, 4, LNB_NCCL_INT8, p->world - 1, p->comm, p->xs); if (r_) rc = fail("ncclRecv failed: %s", p->api->GetErrorString(r_)); }
-            else rc = pipe_xfer(p, recv, recv_rows, false);
-        }
-        int re = p->api->GroupEnd();
-        if (rc) return -1;
-        if (re != 0) return fail("ncclGroupEnd failed: %s", p->api->GetErrorString(re));
-        if (send) { HIPCHK(hipEventRecord(send->ev_sent, p->xs)); send->sent_pending = true; }
-        if (recv) { HIPCHK(hipEventRecord(recv->ev_in, p->xs)); recv->in_pending = true; }
-    }
-    return 0;
+    PipeSide ss{}, rs{};
+    if (send) ss = pipe_side(p, send, send_rows, true);
+    if (recv) rs = pipe_side(p, recv, recv_rows, false);
+    return pipe_exchange(p, send ? &ss : nullptr, recv ? &rs : nullptr);
 }
 
 // ---- the pipeline with BATCHES as the unit that moves through the stages ---------------------------------------------------------------
@@ -3496,48 +3494,18 @@ extern "C" int lnb_pipeline_tick(lnb_pipe* p, lnb_ctx* run, int run_rows, int ru
 //   run : one decode step of the group on this stage -- ONE pass over the stage's weights for all its sequences (captured graph); the
 //         positions advance on the device; on the last rank the n tokens are appended to the pinned log (*token_slot_out = first slot);
 //   send: the group's hidden states [n, dim] to rank + 1 (the last rank: its n token words to rank 0);   recv: the mirror image.
-static int batch_events(lnb_batch* b) {
-    if (!b->ev_done) { HIPCHK(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&b->ev_in, hipEventDisableTiming));
-                       HIPCHK(hipEventCreateWithFlags(&b->ev_sent, hipEventDisableTiming)); }
-    return 0;
-}
-static int loop_copy_batch(lnb_pipe* p, lnb_batch* sb, lnb_batch* rb, bool token) {
-    if (sb->n != rb->n) return fail("loopback exchange: a batch of %d sequences sent, %d expected", sb->n, rb->n);
-    HIPCHK(hipStreamWaitEvent(p->xs, sb->ev_done, 0));
-    HIPCHK(hipStreamWaitEvent(p->xs, rb->ev_done, 0));
-    if (token) HIPCHK(hipMemcpyAsync(rb->ring, sb->ring, (size_t)sb->n * 4, hipMemcpyDeviceToDevice, p->xs));
-    else HIPCHK(hipMemcpyAsync(rb->x, sb->x, (size_t)sb->n * sb->m->a.dim * 2, hipMemcpyDeviceToDevice, p->xs));
-    HIPCHK(hipEventRecord(sb->ev_sent, p->xs)); sb->sent_pending = true;
-    HIPCHK(hipEventRecord(rb->ev_in, p->xs)); rb->in_pending = true;
-    return 0;
-}
-static int loop_post_batch(lnb_pipe* p, bool sending, lnb_batch* b, int peer, bool token) {
-    std::lock_guard<std::mutex> lock(g_loops_mu);
-    const std::pair<int, int> key = sending ? std::make_pair(p->rank, peer) : std::make_pair(peer, p->rank);
-    auto& mine = sending ? p->loop->sends[key] : p->loop->recvs[key];
-    auto& theirs = sending ? p->loop->recvs[key] : p->loop->sends[key];
-    LoopMsg msg{nullptr, b->n}; msg.bat = b;
-    if (theirs.empty()) { mine.push_back(msg); if (!sending) b->recv_unmatched = true; return 0; }
-    const LoopMsg other = theirs.front(); theirs.pop_front();
-    if (!other.bat) return fail("in-process pipeline: a batch hand-off met a single-sequence hand-off (the stages must post the same ticks in the same order)");
-    (sending ? other.bat : b)->recv_unmatched = false;
-    return sending ? loop_copy_batch(p, b, other.bat, token) : loop_copy_batch(p, other.bat, b, token);
-}
 extern "C" int lnb_pipeline_tick_batch(lnb_pipe* p, lnb_batch* run, lnb_batch* send, lnb_batch* recv, int* token_slot_out) {
     if (!p) return fail("null argument");
     lnb_model* m = p->m;
     HIPCHK(hipSetDevice(m->device));
     const bool first = p->rank == 0, last = p->rank == p->world - 1;
-    for (lnb_batch* b : {run, send, recv}) if (b) { if (b->m != m) return fail("batch of another model stage"); if (batch_events(b)) return -1; }
+    for (lnb_batch* b : {run, send, recv}) if (b) { if (b->m != m) return fail("batch of another model stage"); if (b->link.ensure()) return -1; }
     if (p->host && (send || recv)) return fail("this pipe has no transport (lnb_pipeline_init_host): the host layer moves lnb_batch_boundary_ptr's buffers itself; send and recv must be NULL");
     if (token_slot_out) *token_slot_out = -1;
     if (run) {
         if (run->top_k > 0) return fail("the batch's contexts record token probabilities, which pipeline ticks do not support (lnb_ctx_set_token_probs(ctx, 0))");
         hipStream_t st = run->stream;
-        if (run->recv_unmatched) return fail("in-process pipeline: this batch's input has been requested but the sending stage has not posted it yet "
-                                             "(the mailbox transport needs the stages ticked in lock-step order from one thread)");
-        if (run->in_pending) { HIPCHK(hipStreamWaitEvent(st, run->ev_in, 0)); run->in_pending = false; }
-        if (run->sent_pending) { HIPCHK(hipStreamWaitEvent(st, run->ev_sent, 0)); run->sent_pending = false; }
+        if (run->link.await(st, "batch")) return -1;
         const bool ring_in = first && p->world > 1;
         if (batch_select_form(run, run->tick_long)) return -1;       // the form lnb_batch_set_state chose for this run of ticks
         if (p->use_graph) {
@@ -3549,35 +3517,14 @@ extern "C" int lnb_pipeline_tick_batch(lnb_pipe* p, lnb_batch* run, lnb_batch* s
         run->last_form = run->attn_long ? 1 : 0;
         if (last) {
             if (p->tok_n > 0x7FFFFFFF - LNB_BATCH_MAX) return fail("pipeline token log: slot counter exhausted (2^31 tokens): create a new pipe");
-            const int slot = p->tok_n, at = slot % p->tok_cap, fit = std::min(run->n, p->tok_cap - at);   // (the ring keeps the newest tok_cap tokens)
-            HIPCHK(hipMemcpyAsync(p->h_tok + at, run->ring, (size_t)fit * 4, hipMemcpyDeviceToHost, st));
-            if (fit < run->n) HIPCHK(hipMemcpyAsync(p->h_tok, run->ring + fit, (size_t)(run->n - fit) * 4, hipMemcpyDeviceToHost, st));
-            if (token_slot_out) *token_slot_out = slot;
-            p->tok_n += run->n;
+            if (pipe_log_tokens(p, run->ring, run->n, st, token_slot_out)) return -1;
         }
-        HIPCHK(hipEventRecord(run->ev_done, st));
+        HIPCHK(hipEventRecord(run->link.ev_done, st));
     }
-    if (p->world > 1 && p->loop && (send || recv)) {         // in-process transport
-        if (recv) HIPCHK(hipEventRecord(recv->ev_done, recv->stream));
-        if (send && loop_post_batch(p, true, send, last ? 0 : p->rank + 1, last)) return -1;
-        if (recv && loop_post_batch(p, false, recv, first ? p->world - 1 : p->rank - 1, first)) return -1;
-        return 0;
-    }
-    if (p->world > 1 && (send || recv)) {
-        if (send) HIPCHK(hipStreamWaitEvent(p->xs, send->ev_done, 0));
-        if (recv) { HIPCHK(hipEventRecord(recv->ev_done, recv->stream)); HIPCHK(hipStreamWaitEvent(p->xs, recv->ev_done, 0)); }
-        NCCLCHK(p, p->api->GroupStart());
-        int r1 = 0, r2 = 0;
-        if (send) r1 = last ? p->api->Send(send->ring, (size_t)send->n * 4, LNB_NCCL_INT8, 0, p->comm, p->xs)
-                            : p->api->Send(send->x, (size_t)send->n * m->a.dim * 2, LNB_NCCL_INT8, p->rank + 1, p->comm, p->xs);
-        if (recv) r2 = first ? p->api->Recv(recv->ring, (size_t)recv->n * 4, LNB_NCCL_INT8, p->world - 1, p->comm, p->xs)
-                             : p->api->Recv(recv->x, (size_t)recv->n * m->a.dim * 2, LNB_NCCL_INT8, p->rank - 1, p->comm, p->xs);
-        const int re = p->api->GroupEnd();
-        if (r1 || r2 || re) return fail("RCCL batch exchange failed: %s", p->api->GetErrorString(r1 ? r1 : r2 ? r2 : re));
-        if (send) { HIPCHK(hipEventRecord(send->ev_sent, p->xs)); send->sent_pending = true; }
-        if (recv) { HIPCHK(hipEventRecord(recv->ev_in, p->xs)); recv->in_pending = true; }
-    }
-    return 0;
+    PipeSide ss{}, rs{};
+    if (send) ss = pipe_side(p, send, true);
+    if (recv) rs = pipe_side(p, recv, false);
+    return pipe_exchange(p, send ? &ss : nullptr, recv ? &rs : nullptr);
 }
 // The RCCL binding on real hardware without a second GPU: a one-rank communicator and the pipeline's own grouped exchange -- one
 // ncclSend + one ncclRecv, here both to rank 0 (itself) -- on a non-blocking stream, device buffer to device buffer, then a byte

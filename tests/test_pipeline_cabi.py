@@ -270,6 +270,46 @@ def test_multi_stage_pipeline_ticks_through_the_in_process_transport(lnb, cuts):
 
 
 @pytest.mark.gpu
+def test_in_process_transport_refuses_hand_offs_that_do_not_fit(lnb):
+    """The mailbox of the in-process transport (csrc/lnb_handoff.h) through the ABI, on a two-stage pipe cut (0, 3, 6): a send that does not fit
+    the receive it meets is refused on the host before any copy is enqueued -- another unit kind, another row count, another batch width, and a
+    sender cut at (0, 2) whose receiver was built as (3, 6): the sender hands over hidden state + activations, the receiver expects the hidden
+    state alone.  Either posting order.  A refusal leaves the mailbox empty: the fitting hand-off at the end goes through."""
+    from oracle import oracle as orc
+    cfg = dict(orc.TINY)
+    stage = lambda a, b: lnb.LlamaTransformer(part_begin=a, part_end=b, **cfg).fill_synthetic(1234).finalize()
+    g0, g1, g0_cut = stage(0, 3), stage(3, 6), stage(0, 2)
+    p0, p1 = [lnb.Pipeline(g, r, 2, loopback_group="misfit") for r, g in enumerate((g0, g1))]
+    q0, q1 = [lnb.Pipeline(g, r, 2, loopback_group="misfit_cut") for r, g in enumerate((g0_cut, g1))]
+    c0, c1 = [[lnb.InferenceContext(g, 16) for _ in range(4)] for g in (g0, g1)]
+    c0_cut = lnb.InferenceContext(g0_cut, 16)
+    b0, b1 = lnb.Batch(c0[:2]), lnb.Batch(c1[:3])
+    s0, s1 = c0[3], c1[3]
+
+    p0.tick(send=s0, send_rows=1)
+    with pytest.raises(lnb.LnbError, match="a batch hand-off met a single-sequence hand-off"):
+        p1.tick_batch(recv=b1)
+    p0.tick_batch(send=b0)
+    with pytest.raises(lnb.LnbError, match="a single-sequence hand-off met a batch hand-off"):
+        p1.tick(recv=s1, recv_rows=1)
+    p0.tick(send=s0, send_rows=2)
+    with pytest.raises(lnb.LnbError, match="2 rows sent, 3 rows expected"):
+        p1.tick(recv=s1, recv_rows=3)
+    p1.tick_batch(recv=b1)                                    # (the receive posted first)
+    with pytest.raises(lnb.LnbError, match="a batch of 2 sequences sent, 3 expected"):
+        p0.tick_batch(send=b0)
+    q0.tick(send=c0_cut, send_rows=2)
+    with pytest.raises(lnb.LnbError, match="sending stage ends at block part 2 .* receiving stage begins at part 3"):
+        q1.tick(recv=s1, recv_rows=2)
+    p0.tick(send=s0, send_rows=2)                            # nothing is left waiting: a send meets the receive posted after it
+    p1.tick(recv=s1, recv_rows=2)
+    for p_ in (p0, p1, q0, q1):
+        p_.sync()
+    for x in [b0, b1, p0, p1, q0, q1, c0_cut] + c0 + c1 + [g0, g1, g0_cut]:
+        x.close()
+
+
+@pytest.mark.gpu
 def test_bench_force_pipeline_on_one_gpu_runs_the_native_tick_path(lnb):
     import json
     import subprocess

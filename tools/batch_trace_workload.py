@@ -2,7 +2,8 @@
 """Every host path of the batched step once, on the tiny config, to be run under a kernel trace (rocprofv3 --kernel-trace -- python tools/batch_trace_workload.py;
 LNB_SO=<other build> for the build to compare with; tools/compare_kernel_traces.py compares two such traces).  Sections, in this order: lnb_batch_decode at
 3 / 17 / 33 sequences with the matrix-core copy, 3 without it, a speculative run with verify passes, lnb_forward_append_many calls whose passes change
-width and layout (B-operand columns, column groups, rows), batched ticks of a two-stage in-process pipeline.  A section starts with a marker: two exp-table
+width and layout (B-operand columns, column groups, rows), batched ticks of a two-stage in-process pipeline, single-sequence ticks of a two-stage
+pipeline cut behind a gate/up part (two segments per hand-off).  A section starts with a marker: two exp-table
 launches back to back, which nothing else issues."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -81,6 +82,20 @@ for t in range(n_decode * G + 2 * (world - 1)):
     for r in range(world):
         state[r] = pipeline.run_ticks_native_batched(r, world, pipes[r], batches[r], n_decode, t, t + 1, state[r])
 for p_ in pipes:
+    p_.sync()
+
+mark("pipeline_single_gate_up_cut")
+cuts, P, n_decode = (0, 2, 6), 5, 4                          # the cut lies behind a gate/up part: hidden state + gate*up activations cross it
+sstages = [lnb.LlamaTransformer(part_begin=a, part_end=b, **pcfg).fill_synthetic(1234).finalize() for a, b in zip(cuts[:-1], cuts[1:])]
+n_seq = 2 * world
+sctx = [[lnb.InferenceContext(st_, P + n_decode + 2) for _ in range(n_seq)] for st_ in sstages]
+spipes = [lnb.Pipeline(sstages[r], r, world, loopback_group="trace_single") for r in range(world)]
+sprompts = [lnb.synth_tokens(70 + s, P, V) for s in range(n_seq)]
+state = [None] * world
+for t in range((1 + n_decode) * n_seq + 2 * (world - 1)):
+    for r in range(world):
+        state[r] = pipeline.run_ticks_native(r, world, spipes[r], sctx[r], sprompts, n_decode, t, t + 1, state[r])
+for p_ in spipes:
     p_.sync()
 mark("end")
 print("trace workload done", flush=True)

@@ -33,7 +33,7 @@ b, _ = load(sys.argv[2])
 print("columns:", cols)
 print("kernels:", len(a), len(b))
 sa, sb = sections(a), sections(b)
-names = ["setup", "batch_copy_n3", "batch_copy_n17", "batch_copy_n33", "batch_nocopy_n3", "speculative", "append_many", "pipeline_two_stage", "end"]
+names = ["setup", "batch_copy_n3", "batch_copy_n17", "batch_copy_n33", "batch_nocopy_n3", "speculative", "append_many", "pipeline_two_stage", "pipeline_single_gate_up_cut", "end"]
 print("sections:", len(sa), len(sb))
 same = True
 for i, (x, y) in enumerate(zip(sa, sb)):
