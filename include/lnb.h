@@ -542,8 +542,12 @@ int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int iters, float*
  *   handle is used; how many samplers there are is the batch's own n, so they are checked right after it is read and before anything else.)  Then: a stage handle that is not the whole model; a context or a
  *   member that records token probabilities (the record promises ids[i * k] == out_tokens[i], which a sampled token does not keep: switch it
  *   off with lnb_ctx_set_token_probs(ctx, 0)); a pending lnb_forward_stage_begin; max_steps beyond the token log, the KV cache or the RoPE table.
- * Out of scope: sampling in the speculative loops (it needs rejection sampling, a different contract), pipeline ticks, recording the sampled
- *   token's probability, min-p, repetition penalties, logit bias. */
+ * Sampling in the speculative loops (lnb_decode_speculative_sample_until / _many, below) needs NO rejection sampling: the draw is u(seed, pos), so the
+ *   token lnb_decode_sample_until emits at position p is sample(row_p, sampler, p) and depends on nothing else; column i of a verify pass has
+ *   row_{pos + i} exactly, so the greedy acceptance rule holds with "the sampler's token of column i at position pos + i" in place of the argmax.
+ *   No distribution is compared and there is no tolerance: the output is the sampling loop's token sequence, the same bits, in fewer passes.
+ * Out of scope: rejection sampling against a draft MODEL, pipeline ticks, recording the sampled token's probability, min-p, repetition penalties,
+ *   logit bias. */
 #define LNB_SAMPLE_MAX_VOCAB 131072
 typedef struct lnb_sampler { float temperature; float top_p; int32_t top_k; int32_t reserved; uint64_t seed; } lnb_sampler;
 typedef struct lnb_sample_info { uint64_t w_all, w_topk, w_kept; int32_t n_candidates, n_kept, degenerate, pad; } lnb_sample_info;
@@ -553,6 +557,32 @@ int lnb_batch_decode_sample_until(lnb_batch* b, const lnb_sampler* samplers, con
                                   int32_t* out_tokens, int32_t* n_generated, int32_t* finished, float* ms_out);
 int lnb_op_sample(int device, const uint16_t* logits_bf16, int rows, int V, const lnb_sampler* samplers, const int32_t* pos,
                   const uint64_t* draws, int32_t* tokens_out, lnb_sample_info* info);
+/* ---- sampling in the speculative loops ----
+ * lnb_decode_speculative_sample_until: out_tokens[0 .. *n_generated), *n_generated, *finished and the KV rows [0, start_pos + *n_generated) of every
+ *   layer are bit-identical to lnb_decode_sample_until(c, sampler, token, start_pos, max_steps, ...) on a context holding the same rows below
+ *   start_pos; stop ids apply as there.  The result does not depend on the draft settings or on chunking.  Rows beyond that range may hold rejected
+ *   drafts, as after the greedy form.  Draft rule, draft cuts and stats are lnb_decode_speculative_until's (accepted = *n_generated - passes);
+ *   temperature 0 gives that call's tokens and stats; max_draft 0 (lnb_ctx_set_draft) runs lnb_decode_sample_until itself.  A verify pass samples
+ *   every column in ONE launch (column i at position pos + i; the last workgroup to arrive accepts and emits); it has captured graphs of its own per
+ *   (width, attention form) beside the greedy ones, which a sampling call neither drops nor recaptures (and vice versa), and which hold a pointer
+ *   to the sampler: another sampler replays them.  A pass without a draft replays the context's sampling one-token graph.
+ * lnb_decode_speculative_sample_many: the contract of lnb_decode_speculative_many with lnb_decode_sample_until(ctxs[s], &samplers[s], ...) as member
+ *   s's reference; grant rule, col_budget, the start_pos[s] < 0 skip, stats and info are unchanged; a temperature-0 member is greedy.
+ * lnb_op_spec_sample_accept (a test aid, as lnb_op_sample / lnb_op_ngram_draft): the accept-and-emit rule on host rows -- column i of a pass of w
+ *   columns has logits row i, took col_tokens[i] (col_tokens[0] = the current token) and sits at pos0 + i -> the tokens the pass emits.
+ * Refused, each with a message, argument checks before any handle is dereferenced and everything before any cache is written: whatever the greedy
+ *   speculative form refuses and whatever lnb_decode_sample_until refuses (a NULL sampler; temperature negative, NaN or infinite; top_k < 0; top_p
+ *   NaN, <= 0 or > 1; reserved != 0; V > LNB_SAMPLE_MAX_VOCAB; a context that records token probabilities).  The many form checks its samplers right
+ *   after n is known to be valid. */
+int lnb_decode_speculative_sample_until(lnb_ctx* c, const lnb_sampler* sampler, const int32_t* history, int n_history, int32_t token, int start_pos,
+                                        int max_steps, int32_t* out_tokens, int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out);
+int lnb_decode_speculative_sample_many(lnb_ctx* const* ctxs, int n, const lnb_sampler* samplers /* [n] */, const int32_t* const* history,
+                                       const int32_t* n_history, const int32_t* tokens, const int32_t* start_pos, int max_steps, int col_budget,
+                                       int32_t* out_tokens, int32_t* n_generated, int32_t* finished, lnb_spec_stats* stats, lnb_spec_many_info* info,
+                                       float* ms_out);
+int lnb_op_spec_sample_accept(int device, const uint16_t* logits_bf16 /* [w][V] */, int w, int V, const lnb_sampler* sampler, int pos0,
+                              const int32_t* col_tokens /* [w] */, const int32_t* stop_ids, int n_stop, int32_t* emitted /* [w] */, int* n_emitted,
+                              int* finished);
 /* measurement aid: average HIP-event time of a decode step's token launch alone -- sample_kernel with this sampler, or argmax_kernel (sampler
  * NULL) -- on the logits row the context's last step left; the launches advance the context's device state from `pos` as steps do.  Whole-model
  * contexts with no lnb_forward_stage_begin pending; a bad sampler is refused as above. */

@@ -93,6 +93,7 @@ hipError_t lnbk_spin(int us, hipStream_t st);
 hipError_t lnbk_token_probs(const TokProbParams* p, hipStream_t st);
 hipError_t lnbk_spec_argmax(const uint16_t* logits, int V, int w, int32_t* g, hipStream_t st);
 hipError_t lnbk_spec_commit(const int32_t* g, int w, const BatchTab* tab, hipStream_t st);
+hipError_t lnbk_spec_sample_commit(const uint16_t* logits, int V, int w, const double* etab, const LnbSampler* smp, int32_t* g, const BatchTab* tab, unsigned* cnt, hipStream_t st);
 hipError_t lnbk_ngram_draft(const DraftParams* p, hipStream_t st);
 hipError_t lnbk_kv_fork(const KvForkTab* tab, int nt, int split, hipStream_t st);
 hipError_t lnbk_append_many_setup(const AmPass* p, hipStream_t st);
@@ -100,6 +101,7 @@ hipError_t lnbk_append_many_finish(const uint16_t* logits, int V, const AmRow* r
 hipError_t lnbk_spec_many_draft(const SmPass* p, hipStream_t st);
 hipError_t lnbk_spec_many_pack(const SmPass* p, hipStream_t st);
 hipError_t lnbk_spec_many_commit(const SmPass* p, hipStream_t st);
+hipError_t lnbk_spec_many_sample_commit(const SmPass* p, hipStream_t st);
 }
 
 // The HIP runtime spreads a process's streams over a fixed number of hardware queues (its default: 4) and streams that share a queue run one
@@ -2070,6 +2072,8 @@ struct lnb_batch {
     hipGraphExec_t sgraph = nullptr, sgraph_long = nullptr; LnbSampler* d_smp = nullptr;
     // a verify batch whose columns run the multi-row long-context pair (lnb_ctx_set_rows_attention, flags bit 1): a captured graph of its own
     bool attn_rows = false; int rows_zseq = 0; hipGraphExec_t graph_rows = nullptr;
+    // ... and its sampling twin (lnb_decode_speculative_sample_until: a verify batch keeps its sampling passes in sgraph / sgraph_long / sgraph_rows)
+    hipGraphExec_t sgraph_rows = nullptr;
     bool rows_form = false;                // the model carries no matrix-core copy: every product runs as ROWS of gemm_stream_kernel on the resident layouts, whatever n
     // pipeline stage (lnb_pipeline_tick_batch): the contiguous token words exchanged between the last and the first stage, the stage step
     // as a captured graph, events towards / from the exchange stream (as lnb_ctx has them for single-sequence ticks)
@@ -2164,6 +2168,7 @@ extern "C" int lnb_batch_destroy(lnb_batch* b) {
     if (b->sgraph_long) hipGraphExecDestroy(b->sgraph_long);
     hipFree(b->d_smp);
     if (b->graph_rows) hipGraphExecDestroy(b->graph_rows);
+    if (b->sgraph_rows) hipGraphExecDestroy(b->sgraph_rows);
     if (b->stage_graph_long) hipGraphExecDestroy(b->stage_graph_long);
     if (b->scratch_owned) { hipFree(b->e_buf); hipFree(b->z_part); }
     batch_bufs_free(b);
@@ -2811,7 +2816,10 @@ extern "C" int lnb_ctx_set_batched_attention(lnb_ctx* c, int long_threshold, int
     HIPCHK(hipStreamSynchronize(c->stream));
     if (long_threshold >= 0) c->sp_attn_long_T = long_threshold;
     if (force_zseq != c->sp_force_zseq) {
-        for (lnb_batch* b : c->sp_b) if (b) { b->force_zseq = force_zseq; if (b->graph_long) { hipGraphExecDestroy(b->graph_long); b->graph_long = nullptr; } }
+        for (lnb_batch* b : c->sp_b) if (b) {
+            b->force_zseq = force_zseq;
+            for (hipGraphExec_t* g : {&b->graph_long, &b->sgraph_long}) if (*g) { hipGraphExecDestroy(*g); *g = nullptr; }      // (the greedy pass and its sampling twin)
+        }
         c->sp_force_zseq = force_zseq;
     }
     return 0;
@@ -2827,7 +2835,7 @@ extern "C" int lnb_ctx_set_rows_attention(lnb_ctx* c, int long_threshold, int fl
     HIPCHK(hipStreamSynchronize(c->stream));
     if (long_threshold >= 0) c->rows_T = long_threshold;
     if ((flags & 1) != (c->rows_flags & 1))
-        for (lnb_batch* b : c->sp_b) if (b && b->graph_rows) { hipGraphExecDestroy(b->graph_rows); b->graph_rows = nullptr; }
+        for (lnb_batch* b : c->sp_b) if (b) for (hipGraphExec_t* g : {&b->graph_rows, &b->sgraph_rows}) if (*g) { hipGraphExecDestroy(*g); *g = nullptr; }
     c->rows_flags = flags;
     return 0;
 }
@@ -2895,7 +2903,7 @@ static int spec_alloc(lnb_ctx* c, int text_len) {
 // the verify batch of width w, its graph captured on first use: embedding gather of the w column tokens, the blocks, the head, the
 // columns' argmax, the commit.  With the matrix-core copy the products are its column forms, without it rows of gemm_stream_kernel.
 // form 1: the pass runs the long-context pair, 2: the multi-row pair (one graph per form and width); their scratch is the context's, shared by all widths
-static int spec_verify_batch(lnb_ctx* c, int w, int form, lnb_batch** out) {
+static int spec_verify_batch(lnb_ctx* c, int w, int form, bool sample, lnb_batch** out, hipGraphExec_t* graph_out) {
     lnb_model* m = c->m;
     const bool long_form = form != 0;
     if (long_form && attn_long_scratch(LNB_MAX_DRAFT + 1, m->a.n_heads, c->seq_len, &c->sp_e_buf, &c->sp_z_part, "the verify passes")) return -1;   // (host side of the call, outside any capture)
@@ -2912,9 +2920,13 @@ static int spec_verify_batch(lnb_ctx* c, int w, int form, lnb_batch** out) {
     }
     b->e_buf = c->sp_e_buf; b->z_part = c->sp_z_part;
     b->attn_long = long_form; b->attn_rows = form == 2; b->rows_zseq = c->rows_flags & 1;
-    hipGraphExec_t* const gslot = form == 2 ? &b->graph_rows : long_form ? &b->graph_long : &b->graph;
+    hipGraphExec_t* const gslot = sample ? (form == 2 ? &b->sgraph_rows : long_form ? &b->sgraph_long : &b->sgraph) : (form == 2 ? &b->graph_rows : long_form ? &b->graph_long : &b->graph);
     auto body = [&]() -> int {
         if (enqueue_batch_pass(b)) return -1;
+        if (sample) {                                        // the token launch is the one difference: every column's sampled token at its own position, then the same acceptance
+            HIPCHK(lnbk_spec_sample_commit(b->logits, m->a.vocab_size, w, m->prob_etab, c->d_smp, c->sp_g, b->tab, c->sp_cnt + 1, b->stream));
+            return 0;
+        }
         HIPCHK(lnbk_spec_argmax(b->logits, m->a.vocab_size, w, c->sp_g, b->stream));
         HIPCHK(lnbk_spec_commit(c->sp_g, w, b->tab, b->stream));
         return 0;
@@ -2923,7 +2935,7 @@ static int spec_verify_batch(lnb_ctx* c, int w, int form, lnb_batch** out) {
         if (fresh) { c->sp_b[w] = nullptr; lnb_batch_destroy(b); }      // (a batch without a graph is not kept)
         return -1;
     }
-    *out = b;
+    *out = b; *graph_out = *gslot;
     return 0;
 }
 static DraftParams spec_draft_params(lnb_ctx* c, int n_text, int max_steps) {
@@ -2932,8 +2944,10 @@ static DraftParams spec_draft_params(lnb_ctx* c, int n_text, int max_steps) {
     p.max_steps = max_steps; p.seq_len = c->seq_len; p.out = c->sp_tok; p.col_st = c->sp_st; p.word = c->sp_word_dev; p.best = c->sp_best; p.cnt = c->sp_cnt;
     return p;
 }
-extern "C" int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, int n_history, int32_t token, int start_pos, int max_steps,
-                                            int32_t* out_tokens, int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out) {
+// lnb_decode_speculative_until (smp null) and lnb_decode_speculative_sample_until: one loop; the sampler picks the token launch of a pass -- the sampling
+// one-token graph or the verify batch's sampling graph -- and nothing else
+static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* history, int n_history, int32_t token, int start_pos, int max_steps,
+                            int32_t* out_tokens, int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out) {
     if (n_history < 0) return fail("negative history length %d", n_history);
     if (max_steps <= 0) return fail("max_steps must be positive");
     if (!c || !out_tokens || !n_generated || (n_history > 0 && !history)) return fail("null argument");
@@ -2943,9 +2957,10 @@ extern "C" int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, 
     if (c->top_k > 0) return fail("speculative decoding does not record token probabilities: lnb_ctx_set_token_probs(ctx, 0) first");
     if (c->batch_users > 0) return fail("context is a member of %d live batch(es): speculative decoding runs it alone (lnb_batch_destroy first)", c->batch_users);
     if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
+    if (smp && sample_vocab_check(m->a.vocab_size)) return -1;
     if (stats) *stats = lnb_spec_stats{};
-    if (c->sp_max_draft == 0) {                              // drafting off: the greedy loop itself, one pass per token
-        if (decode_greedy_impl(c, token, start_pos, max_steps, out_tokens, n_generated, finished, ms_out)) return -1;
+    if (c->sp_max_draft == 0) {                              // drafting off: the greedy (the sampling) loop itself, one pass per token
+        if (decode_greedy_impl(c, token, start_pos, max_steps, out_tokens, n_generated, finished, ms_out, smp)) return -1;
         if (stats) stats->passes = *n_generated;
         return 0;
     }
@@ -2956,9 +2971,11 @@ extern "C" int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, 
     if (batch_shape_check(m, "the verify pass")) return -1;
     if (!m->batch_enabled) HIPCHK(lnbk_batch_prepare());
     const int n_text = n_history + 1;
-    if (spec_alloc(c, n_text) || capture_decode_graphs(c, start_pos, max_steps)) return -1;
+    if (smp && !c->d_smp) HIPCHK(hipMalloc((void**)&c->d_smp, sizeof(LnbSampler)));
+    if (spec_alloc(c, n_text) || capture_decode_graphs(c, start_pos, max_steps, smp != nullptr)) return -1;
     hipStream_t st = c->stream;
     c->tp_last_k = 0; c->tp_last_n = 0;
+    if (smp) HIPCHK(hipMemcpyAsync(c->d_smp, smp, sizeof(LnbSampler), hipMemcpyHostToDevice, st));       // (the captured graphs hold the pointer: another sampler replays them)
     if (n_history > 0) HIPCHK(hipMemcpyAsync(c->sp_text, history, (size_t)n_history * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(c->sp_text + n_history, &token, 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(c->dtok, &token, 4, hipMemcpyHostToDevice, st));
@@ -2980,14 +2997,16 @@ extern "C" int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, 
         if (fin || n_out >= max_steps) break;
         if (k < 0 || k > c->sp_max_draft) return fail("internal error: draft length %d", k);
         s.passes++;
-        if (k == 0) HIPCHK(hipGraphLaunch(want_long_attention(c, 1, start_pos + n_out) ? c->graph_long : c->graph, st));
-        else {
-            lnb_batch* b = nullptr;
+        if (k == 0) {
+            const bool lg = want_long_attention(c, 1, start_pos + n_out);
+            HIPCHK(hipGraphLaunch(smp ? (lg ? c->sgraph_long : c->sgraph) : (lg ? c->graph_long : c->graph), st));
+        } else {
+            lnb_batch* b = nullptr; hipGraphExec_t pass = nullptr;
             // the pass's last column sits at start_pos + n_out + k: the long form when the context is beyond the one-workgroup kernels' reach or past the threshold
             const bool lf = c->seq_len > c->attn_short_cap || start_pos + n_out + k + 1 > c->sp_attn_long_T;
             const int form = !lf ? 0 : (c->rows_flags & 2) ? 2 : 1;     // (2: lnb_ctx_set_rows_attention's opt-in -- K and V read once for all columns)
-            if (spec_verify_batch(c, k + 1, form, &b)) return -1;
-            HIPCHK(hipGraphLaunch(form == 2 ? b->graph_rows : lf ? b->graph_long : b->graph, st));
+            if (spec_verify_batch(c, k + 1, form, smp != nullptr, &b, &pass)) return -1;
+            HIPCHK(hipGraphLaunch(pass, st));
             c->sp_last_form = form; b->last_form = lf ? 1 : 0;
             s.verify_passes++; s.drafted += k;
         }
@@ -3013,6 +3032,17 @@ extern "C" int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, 
     s.accepted = (int64_t)n_out - s.passes;                  // every pass emits its column 0 token plus the drafts it accepted
     if (stats) *stats = s;
     return 0;
+}
+extern "C" int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, int n_history, int32_t token, int start_pos, int max_steps,
+                                            int32_t* out_tokens, int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out) {
+    return spec_decode_impl(c, nullptr, history, n_history, token, start_pos, max_steps, out_tokens, n_generated, finished, stats, ms_out);
+}
+// the same loop with the sampler's token per column (include/lnb.h): the tokens of lnb_decode_sample_until, because its draw is u(seed, pos) alone
+extern "C" int lnb_decode_speculative_sample_until(lnb_ctx* c, const lnb_sampler* sampler, const int32_t* history, int n_history, int32_t token, int start_pos,
+                                                   int max_steps, int32_t* out_tokens, int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out) {
+    if (!sampler) return fail("null argument (sampler)");
+    if (sampler_check(sampler, "")) return -1;
+    return spec_decode_impl(c, sampler, history, n_history, token, start_pos, max_steps, out_tokens, n_generated, finished, stats, ms_out);
 }
 // ngram_draft_kernel on host arrays (a test aid, as lnb_op_argmax): the draft that follows text, with no decode limits
 extern "C" int lnb_op_ngram_draft(int device, const int32_t* text, int n_text, const int32_t* corpus, int n_corpus,
@@ -3069,7 +3099,7 @@ static int spec_many_build(SpecMany* sm, hipStream_t st) {
     auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_mem = carve(N * sizeof(SmMember)), o_want = carve(N * 4), o_run = carve(N * 4), o_draft = carve(N * LNB_SPEC_MAX_DRAFT * 4),
                  o_best = carve(N * 2 * LNB_SPEC_MAX_NGRAM * 4), o_cnt = carve((N + 1) * 4), o_rows = carve(N * sizeof(AmRow)), o_seg = carve(N * sizeof(SmSeg)),
-                 o_stats = carve(N * sizeof(SmStats)), o_g = carve(N * 4);
+                 o_stats = carve(N * sizeof(SmStats)), o_g = carve(N * 4), o_smp = carve(N * sizeof(LnbSampler));
     HIPCHK(hipMalloc((void**)&sm->dev, off));
     HIPCHK(hipMemsetAsync(sm->dev, 0, off, st));
     HIPCHK(hipHostMalloc((void**)&sm->word, 16, hipHostMallocMapped));
@@ -3081,7 +3111,7 @@ static int spec_many_build(SpecMany* sm, hipStream_t st) {
     SmPass& p = sm->p; char* d = sm->dev;
     p.members = (const SmMember*)(d + o_mem); p.want = (int32_t*)(d + o_want); p.running = (int32_t*)(d + o_run); p.draft = (int32_t*)(d + o_draft);
     p.best = (int*)(d + o_best); p.cnt = (unsigned*)(d + o_cnt); p.rows = (AmRow*)(d + o_rows); p.seg = (SmSeg*)(d + o_seg);
-    p.stats = (SmStats*)(d + o_stats); p.g = (int32_t*)(d + o_g); p.word = word_dev;
+    p.stats = (SmStats*)(d + o_stats); p.g = (int32_t*)(d + o_g); p.word = word_dev; p.smp = (const LnbSampler*)(d + o_smp);
     return 0;
 }
 // the object is published only when all of it exists: a failed allocation leaves the handle as it was, and the next call starts over
@@ -3092,16 +3122,22 @@ static int spec_many_alloc(AppendMany* am) {
     am->sm = sm;
     return 0;
 }
-extern "C" int lnb_decode_speculative_many(lnb_ctx* const* ctxs, int n, const int32_t* const* history, const int32_t* n_history,
-                                           const int32_t* tokens, const int32_t* start_pos, int max_steps, int col_budget,
-                                           int32_t* out_tokens, int32_t* n_generated, int32_t* finished,
-                                           lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out) {
-    const char* const name = "lnb_decode_speculative_many";
+// lnb_decode_speculative_many (sampling false) and lnb_decode_speculative_sample_many: one loop; the commit launch of a pass is the one difference
+static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_sampler* samplers, const int32_t* const* history, const int32_t* n_history,
+                          const int32_t* tokens, const int32_t* start_pos, int max_steps, int col_budget,
+                          int32_t* out_tokens, int32_t* n_generated, int32_t* finished,
+                          lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out) {
+    const char* const name = sampling ? "lnb_decode_speculative_sample_many" : "lnb_decode_speculative_many";
+    if (sampling && !samplers) return fail("%s: null argument (samplers)", name);
     // ---- the arguments alone: no handle is dereferenced
     if (!ctxs || !history || !n_history || !tokens || !start_pos || !out_tokens || !n_generated)
         return fail("%s: null argument (%s)", name, !ctxs ? "ctxs" : !history ? "history" : !n_history ? "n_history" : !tokens ? "tokens" : !start_pos ? "start_pos" :
                     !out_tokens ? "out_tokens" : "n_generated");
     if (n < 1 || n > LNB_BATCH_MAX) return fail("%s: a call takes 1..%d contexts (got %d)", name, LNB_BATCH_MAX, n);
+    if (sampling) {
+        char who[96];
+        for (int s = 0; s < n; s++) { snprintf(who, sizeof who, "%s: member %d: ", name, s); if (sampler_check(samplers + s, who)) return -1; }
+    }
     if (max_steps <= 0) return fail("%s: max_steps must be positive (got %d)", name, max_steps);
     if (col_budget != 0 && (col_budget < n || col_budget > LNB_BATCH_MAX))
         return fail("%s: col_budget must be 0 (the default) or %d..%d, one column per member at least (got %d)", name, n, LNB_BATCH_MAX, col_budget);
@@ -3116,6 +3152,7 @@ extern "C" int lnb_decode_speculative_many(lnb_ctx* const* ctxs, int n, const in
     for (int s = 0; s < n; s++) if (ctxs[s]->m != m) return fail("%s: context %d belongs to another lnb_model handle", name, s);
     if (!m->first() || !m->last()) return fail("%s needs a whole-model handle: pipeline stages have no speculative decoding", name);
     if (batch_shape_check(m, name)) return -1;
+    if (sampling && sample_vocab_check(m->a.vocab_size)) return -1;
     const int V = m->a.vocab_size, cap = ctxs[0]->attn_short_cap;
     const int budget = col_budget ? col_budget : LNB_STREAM_COLS * ((n + LNB_STREAM_COLS - 1) / LNB_STREAM_COLS);
     int n_levels = 1, need_T = 0; bool any_long = false; size_t text_total = 0;
@@ -3183,6 +3220,7 @@ extern "C" int lnb_decode_speculative_many(lnb_ctx* const* ctxs, int n, const in
     HIPCHK(hipMemcpyAsync((void*)sm->p.members, smm.data(), smm.size() * sizeof(SmMember), hipMemcpyHostToDevice, st));
     if (text_total) HIPCHK(hipMemcpyAsync(sm->text, text.data(), text_total * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(sm->p.stats, 0, LNB_BATCH_MAX * sizeof(SmStats), st));
+    if (sampling) HIPCHK(hipMemcpyAsync((void*)sm->p.smp, samplers, (size_t)n * sizeof(LnbSampler), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(b->derr, 0, 4, st));
     for (int s = 0; s < n; s++) if (start_pos[s] >= 0) {
         HIPCHK(hipMemcpyAsync(ctxs[s]->dtok, tokens + s, 4, hipMemcpyHostToDevice, st));
@@ -3190,6 +3228,7 @@ extern "C" int lnb_decode_speculative_many(lnb_ctx* const* ctxs, int n, const in
     }
     b->rows_form = !m->batch_enabled; b->force_zseq = 0; b->attn_rows = false;
     SmPass sp = sm->p; sp.n = n; sp.max_steps = max_steps; sp.budget = budget; sp.n_levels = n_levels; sp.logits = b->logits; sp.V = V;
+    if (sampling) sp.etab = m->prob_etab; else sp.smp = nullptr;
     lnb_spec_many_info inf{};
     HIPCHK(hipEventRecord(sm->ev0, st));
     HIPCHK(lnbk_spec_many_draft(&sp, st));
@@ -3212,7 +3251,7 @@ extern "C" int lnb_decode_speculative_many(lnb_ctx* const* ctxs, int n, const in
         HIPCHK(lnbk_append_many_setup(&ap, st));
         if (enqueue_batch_pass(b)) return -1;
         sp.width = width;
-        HIPCHK(lnbk_spec_many_commit(&sp, st));
+        HIPCHK(sampling ? lnbk_spec_many_sample_commit(&sp, st) : lnbk_spec_many_commit(&sp, st));
         HIPCHK(lnbk_spec_many_draft(&sp, st));
         HIPCHK(lnbk_spec_many_pack(&sp, st));
         HIPCHK(hipEventRecord(sm->ev, st));
@@ -3238,6 +3277,19 @@ extern "C" int lnb_decode_speculative_many(lnb_ctx* const* ctxs, int n, const in
     }
     if (info) *info = inf;
     return 0;
+}
+extern "C" int lnb_decode_speculative_many(lnb_ctx* const* ctxs, int n, const int32_t* const* history, const int32_t* n_history,
+                                           const int32_t* tokens, const int32_t* start_pos, int max_steps, int col_budget,
+                                           int32_t* out_tokens, int32_t* n_generated, int32_t* finished,
+                                           lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out) {
+    return spec_many_impl(false, ctxs, n, nullptr, history, n_history, tokens, start_pos, max_steps, col_budget, out_tokens, n_generated, finished, stats, info, ms_out);
+}
+// the same call with one sampler per member (include/lnb.h): every member's tokens are those of its own lnb_decode_sample_until
+extern "C" int lnb_decode_speculative_sample_many(lnb_ctx* const* ctxs, int n, const lnb_sampler* samplers, const int32_t* const* history, const int32_t* n_history,
+                                                  const int32_t* tokens, const int32_t* start_pos, int max_steps, int col_budget,
+                                                  int32_t* out_tokens, int32_t* n_generated, int32_t* finished,
+                                                  lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out) {
+    return spec_many_impl(true, ctxs, n, samplers, history, n_history, tokens, start_pos, max_steps, col_budget, out_tokens, n_generated, finished, stats, info, ms_out);
 }
 
 // ---- layer-sharded pipeline: the exchange behind the C ABI ---------------------------------------------------------------------
@@ -3828,6 +3880,50 @@ extern "C" int lnb_op_sample(int device, const uint16_t* logits_bf16, int rows, 
     if (e == hipSuccess && info) e = hipMemcpy(info, b + o_i, R * sizeof(LnbSampleInfo), hipMemcpyDeviceToHost);
     hipFree(b);
     HIPCHK(e);
+    return 0;
+}
+// spec_sample_commit_kernel on host rows (test aid): the w columns of a verify pass whose column i holds logits row i, takes col_tokens[i] and sits at
+// pos0 + i, with a generation state that honours stop_ids -> what the pass emits
+extern "C" int lnb_op_spec_sample_accept(int device, const uint16_t* logits_bf16, int w, int V, const lnb_sampler* sampler, int pos0, const int32_t* col_tokens,
+                                         const int32_t* stop_ids, int n_stop, int32_t* emitted, int* n_emitted, int* finished) {
+    if (!logits_bf16 || !sampler || !col_tokens || !emitted || !n_emitted || (n_stop > 0 && !stop_ids)) return fail("null argument");
+    if (w < 1 || w > LNB_MAX_DRAFT + 1) return fail("a verify pass has 1..%d columns (got %d)", LNB_MAX_DRAFT + 1, w);
+    if (sample_vocab_check(V)) return -1;
+    if (sampler_check(sampler, "")) return -1;
+    if (pos0 < 0 || n_stop < 0 || n_stop > LNB_MAX_STOP_IDS) return fail("bad arguments: pos0 %d, %d stop ids (at most %d)", pos0, n_stop, LNB_MAX_STOP_IDS);
+    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
+    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    const size_t W = w;
+    std::vector<double> et; prob_exp_table(et);
+    const size_t o_x = align256(65536 * 8), o_s = o_x + align256(W * V * 2 + 16), o_st = o_s + align256(sizeof(LnbSampler)), o_tok = o_st + align256(W * sizeof(StepState)),
+                 o_g = o_tok + align256(W * 4), o_log = o_g + align256(W * 4), o_tab = o_log + align256(W * 4), o_cnt = o_tab + align256(sizeof(BatchTab)), need = o_cnt + 256;
+    char* b = nullptr;
+    HIPCHK(hipMalloc((void**)&b, need));
+    std::vector<StepState> hst(W, StepState{});
+    for (int i = 0; i < w; i++) hst[i].pos = pos0 + i;
+    hst[0].n_stop = n_stop; hst[0].honour_stop = 1;
+    for (int k = 0; k < n_stop; k++) hst[0].stop[k] = stop_ids[k];
+    std::vector<BatchTab> tab(1, BatchTab{});
+    for (int i = 0; i < w; i++) { tab[0].st[i] = (StepState*)(b + o_st) + i; tab[0].dtok[i] = (int32_t*)(b + o_tok) + i; }
+    tab[0].dout[0] = (int32_t*)(b + o_log); tab[0].dout_cap[0] = w; tab[0].n = w;
+    hipError_t e = hipMemset(b + o_g, 0, need - o_g);
+    if (e == hipSuccess) e = hipMemcpy(b, et.data(), 65536 * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(b + o_x, logits_bf16, W * V * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(b + o_s, sampler, sizeof(LnbSampler), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(b + o_st, hst.data(), W * sizeof(StepState), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(b + o_tok, col_tokens, W * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(b + o_tab, tab.data(), sizeof(BatchTab), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = lnbk_spec_sample_commit((const uint16_t*)(b + o_x), V, w, (const double*)b, (const LnbSampler*)(b + o_s), (int32_t*)(b + o_g),
+                                                     (const BatchTab*)(b + o_tab), (unsigned*)(b + o_cnt), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(hst.data(), b + o_st, sizeof(StepState), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(emitted, b + o_log, W * 4, hipMemcpyDeviceToHost);
+    hipFree(b);
+    HIPCHK(e);
+    if (hst[0].n_out < 1 || hst[0].n_out > w) return fail("internal error: a pass of %d columns emitted %d tokens", w, hst[0].n_out);
+    *n_emitted = hst[0].n_out;
+    if (finished) *finished = hst[0].finished;
     return 0;
 }
 extern "C" int lnb_op_exp_table(int device, float divisor, double* out65536) {

@@ -323,4 +323,5 @@ struct SmPass {                                            // the launches aroun
     int32_t* word;                                         // the host's pinned block {width, any_draft, running members, largest seq_len of a running member}
     int32_t* g;                                            // [LNB_BATCH_MAX] argmax per column
     const uint16_t* logits; int32_t V, width;              // commit: the pass's logits and width as the host launched it
+    const struct LnbSampler* smp; const double* etab;      // spec_many_sample_commit_kernel: [LNB_BATCH_MAX] the members' samplers, the model's exp table (the greedy call: both null)
 };

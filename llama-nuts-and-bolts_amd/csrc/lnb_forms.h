@@ -64,6 +64,8 @@
     /* the token of a sampling decode step (lnb_decode_sample_until; greedy steps launch argmax_kernel and count nothing) */ \
     X(SAMPLE_ROW, "sample.row", "sample_kernel: one workgroup per logits row -- the one-token sampling step, rows of lnb_op_sample") \
     X(SAMPLE_BATCH, "sample.batch", "batch_sample_kernel: one workgroup per member of a batched sampling step, each with its own sampler") \
+    X(SAMPLE_SPEC, "sample.spec", "spec_sample_commit_kernel: one workgroup per column of a verify pass, each at its own position; the last one accepts and emits") \
+    X(SAMPLE_SPEC_MANY, "sample.spec_many", "spec_many_sample_commit_kernel: the same per column of a many-context pass, each member with its own sampler") \
     /* pipeline stage step */ \
     X(PIPELINE_REPLAY, "pipeline.replay", "a one-token or batched pipeline stage step replayed from its captured graph (counted per step)") \
     X(PIPELINE_EAGER, "pipeline.eager", "such a step launched eagerly (LNB_PIPELINE_GRAPH=0; counted per step)")

@@ -4346,8 +4346,8 @@ __global__ __launch_bounds__(1024) void spec_argmax_kernel(const uint16_t* logit
 // After the verify pass: a = the longest prefix of columns whose argmax equals the next column's input (the draft d_{i+1}); the argmax of
 // columns 0 .. a is emitted in order, exactly as a greedy step emits its token -- token log, position, the context's token word, and the stop
 // ids (the stop token is emitted and freezes the generation: nothing behind it).  Column 0 is the context's own state (tab->st[0]).
-__global__ void spec_commit_kernel(const int32_t* g, int w, const BatchTab* tab) {
-    if (threadIdx.x != 0) return;
+// (spec_accept_emit: one thread; shared with spec_sample_commit_kernel, whose g holds the sampler's tokens -- the same loop for both)
+DEVINL void spec_accept_emit(const int32_t* g, int w, const BatchTab* tab) {
     StepState* st = tab->st[0];
     if (st->finished) return;
     int a = 0;
@@ -4363,6 +4363,38 @@ __global__ void spec_commit_kernel(const int32_t* g, int w, const BatchTab* tab)
         if (st->honour_stop) for (int k = 0; k < st->n_stop; k++) if (tok == st->stop[k]) stop = true;
         if (stop) { st->finished = 1; break; }
     }
+}
+__global__ void spec_commit_kernel(const int32_t* g, int w, const BatchTab* tab) {
+    if (threadIdx.x != 0) return;
+    spec_accept_emit(g, w, tab);
+}
+// ---- sampling in the speculative loop (lnb_decode_speculative_sample_until) --------------------------------------------------------------
+// The sampler's draw is u(seed, pos) and nothing else, so the token the sampling loop emits at position p is sample(row_p, sampler, p): column i of a
+// verify pass has row_{pos + i} exactly, and the greedy acceptance rule holds with "the sampler's token of column i AT POSITION pos + i" in place of
+// the argmax.  spec_sample_commit_kernel: workgroup i samples column i's row at tab->st[i]->pos (column 0: the context's own state; columns 1..: what
+// ngram_draft_kernel wrote, pos + i) -> g[i]; the last workgroup to arrive (agent-scope ticket, as ngram_draft_kernel's) runs spec_accept_emit.  One
+// launch in place of spec_argmax_kernel + spec_commit_kernel.  What the epilogue needs waits in the LDS across sample_block (see SampleEnd).
+struct SpecSampleEnd { int32_t* g; unsigned* cnt; const BatchTab* tab; int w, last; };
+__global__ __launch_bounds__(1024) void spec_sample_commit_kernel(const uint16_t* logits, int V, const double* etab, const LnbSampler* smp, int32_t* g,
+                                                                  const BatchTab* tab, unsigned* cnt) {
+    __shared__ float sv[1024];
+    __shared__ int si[1024];
+    __shared__ SampleSh sh;
+    __shared__ SpecSampleEnd end;
+    const int i = blockIdx.x;
+    const LnbSampler s = smp[0];
+    const uint16_t* x = logits + (size_t)i * V;
+    const unsigned long long pos = (unsigned long long)(long long)tab->st[i]->pos;
+    if (threadIdx.x == 0) { end.g = g; end.cnt = cnt; end.tab = tab; end.w = (int)gridDim.x; end.last = 0; }
+    const int tok = s.temperature == 0.0f ? argmax_block(x, V, sv, si) : sample_block(x, V, etab, s, false, pos, sh);
+    if (threadIdx.x != 0) return;
+    end.g[i] = tok;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    const unsigned t = __hip_atomic_fetch_add(end.cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (t != (unsigned)end.w - 1u) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    *end.cnt = 0;                                            // (ready for the next launch: stream order)
+    spec_accept_emit(end.g, end.w, end.tab);
 }
 DEVINL int32_t spec_text_at(const DraftParams& p, int j) { return j < p.n_text ? p.text[j] : p.gen[j - p.n_text]; }
 // N-gram (prompt lookup) draft of the next pass.  Workgroup b tries n = ngram_max - b: the latest start j in R = text ++ gen of an earlier
@@ -5260,6 +5292,14 @@ extern "C" hipError_t lnbk_batch_sample(const uint16_t* logits, int V, const dou
     hipLaunchKernelGGL(batch_sample_kernel, dim3(nseq), dim3(1024), 0, st, logits, V, etab, smp, tab);
     return hipGetLastError();
 }
+// the verify pass's token launch of the sampling speculative loop: w columns of one context, smp[0], cnt = the launch's arrival ticket (zero between launches)
+extern "C" hipError_t lnbk_spec_sample_commit(const uint16_t* logits, int V, int w, const double* etab, const LnbSampler* smp, int32_t* g, const BatchTab* tab,
+                                              unsigned* cnt, hipStream_t st) {
+    if (V < 1 || V > LNB_SAMPLE_MAX_V || w < 1 || w > LNB_SPEC_MAX_DRAFT + 1 || !logits || !etab || !smp || !g || !tab || !cnt) return hipErrorInvalidValue;
+    form_ran(Form::SAMPLE_SPEC);
+    hipLaunchKernelGGL(spec_sample_commit_kernel, dim3((unsigned)w), dim3(1024), 0, st, logits, V, etab, smp, g, tab, cnt);
+    return hipGetLastError();
+}
 extern "C" hipError_t lnbk_set_state(StepState* state, int pos, int n_out, int honour_stop, hipStream_t st) {
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, state, pos, n_out, honour_stop);
     return hipGetLastError();
@@ -5534,5 +5574,11 @@ extern "C" hipError_t lnbk_spec_many_pack(const SmPass* p, hipStream_t st) {
 extern "C" hipError_t lnbk_spec_many_commit(const SmPass* p, hipStream_t st) {
     if (!spec_many_tables_ok(p) || !p->logits || p->V < 1 || p->width < 1 || p->width > LNB_BATCH_MAX) return hipErrorInvalidValue;
     hipLaunchKernelGGL(spec_many_commit_kernel, dim3((unsigned)p->width), dim3(1024), 0, st, *p);
+    return hipGetLastError();
+}
+extern "C" hipError_t lnbk_spec_many_sample_commit(const SmPass* p, hipStream_t st) {
+    if (!spec_many_tables_ok(p) || !p->logits || p->V < 1 || p->V > LNB_SAMPLE_MAX_V || p->width < 1 || p->width > LNB_BATCH_MAX || !p->smp || !p->etab) return hipErrorInvalidValue;
+    form_ran(Form::SAMPLE_SPEC_MANY);
+    hipLaunchKernelGGL(spec_many_sample_commit_kernel, dim3((unsigned)p->width), dim3(1024), 0, st, *p);
     return hipGetLastError();
 }

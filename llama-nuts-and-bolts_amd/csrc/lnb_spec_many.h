@@ -13,6 +13,8 @@
 //   spec_many_commit_kernel   one workgroup per column: ml.Argmax of the column (argmax_block); the last workgroup to arrive (ticket) lets thread s
 //                             accept for member s -- a_s = the longest prefix of its columns whose argmax equals the next column's input -- and
 //                             emit the argmax of its columns 0 .. a_s into the member's OWN state, token word and log, as spec_commit_kernel does.
+//   spec_many_sample_commit_kernel   the same with every member's own sampler (lnb_decode_speculative_sample_many): column c's token is the sampler's of
+//                             its member at the column's own position; acceptance and emission are the same function (spec_many_accept_emit).
 // Plain C++ and vector stores; no waits; every index is bounded by the tables' own sizes (members < p.n <= LNB_BATCH_MAX, columns < LNB_BATCH_MAX,
 // draft tokens < LNB_SPEC_MAX_DRAFT, n-gram results < LNB_SPEC_MAX_NGRAM).
 #pragma once
@@ -96,23 +98,9 @@ __global__ __launch_bounds__(LNB_BATCH_MAX) void spec_many_pack_kernel(SmPass p)
     t.passes += 1; t.verify_passes += k > 1 ? 1 : 0; t.drafted += k - 1;
 }
 
-__global__ __launch_bounds__(1024) void spec_many_commit_kernel(SmPass p) {
-    __shared__ float sv[1024];
-    __shared__ int si[1024];
-    __shared__ int s_last;
-    const int c = (int)blockIdx.x;
-    const int tok = argmax_block(p.logits + (size_t)c * p.V, p.V, sv, si);
-    if (threadIdx.x == 0) {
-        p.g[c] = tok;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        const unsigned t = __hip_atomic_fetch_add(p.cnt + LNB_BATCH_MAX, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = t == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (threadIdx.x == 0) p.cnt[LNB_BATCH_MAX] = 0;          // (ready for the next launch: stream order)
-    const int s = (int)threadIdx.x;
+// what the last workgroup's thread s does for member s (shared by spec_many_commit_kernel and spec_many_sample_commit_kernel: p.g holds the columns'
+// argmax or the samplers' tokens, the loop is the same)
+DEVINL void spec_many_accept_emit(const SmPass& p, int s) {
     if (s >= p.n || s >= LNB_BATCH_MAX) return;
     const SmSeg sg = p.seg[s];
     if (sg.cols <= 0 || sg.first < 0 || sg.first + sg.cols > p.width || p.width > LNB_BATCH_MAX) return;
@@ -132,4 +120,55 @@ __global__ __launch_bounds__(1024) void spec_many_commit_kernel(SmPass p) {
         if (st->honour_stop) for (int q = 0; q < st->n_stop; q++) if (t == st->stop[q]) stop = true;
         if (stop) { st->finished = 1; break; }
     }
+}
+
+__global__ __launch_bounds__(1024) void spec_many_commit_kernel(SmPass p) {
+    __shared__ float sv[1024];
+    __shared__ int si[1024];
+    __shared__ int s_last;
+    const int c = (int)blockIdx.x;
+    const int tok = argmax_block(p.logits + (size_t)c * p.V, p.V, sv, si);
+    if (threadIdx.x == 0) {
+        p.g[c] = tok;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        const unsigned t = __hip_atomic_fetch_add(p.cnt + LNB_BATCH_MAX, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = t == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (threadIdx.x == 0) p.cnt[LNB_BATCH_MAX] = 0;          // (ready for the next launch: stream order)
+    spec_many_accept_emit(p, (int)threadIdx.x);
+}
+
+// spec_many_commit_kernel with every member's own sampler (lnb_decode_speculative_sample_many): column c is the one-token step of member rows[c].member at
+// rows[c].pos, so its token is that member's sampler's at THAT position (a temperature-0 member: argmax_block).  The pass's tables wait in the LDS across
+// sample_block, which leaves no scalar registers to hold them (SampleEnd, lnb_kernels.hip).
+__global__ __launch_bounds__(1024) void spec_many_sample_commit_kernel(SmPass p) {
+    __shared__ float sv[1024];
+    __shared__ int si[1024];
+    __shared__ SampleSh sh;
+    __shared__ SmPass end;
+    __shared__ int s_last;
+    const int c = (int)blockIdx.x;
+    const AmRow row = p.rows[c];
+    const int mem = row.member >= 0 && row.member < LNB_BATCH_MAX ? row.member : 0;
+    const LnbSampler s = p.smp[mem];
+    const uint16_t* x = p.logits + (size_t)c * p.V;
+    const double* etab = p.etab;
+    const int V = p.V;
+    const unsigned long long pos = (unsigned long long)(long long)row.pos;
+    if (threadIdx.x == 0) { end = p; s_last = 0; }
+    const int tok = s.temperature == 0.0f ? argmax_block(x, V, sv, si) : sample_block(x, V, etab, s, false, pos, sh);
+    if (threadIdx.x == 0) {
+        end.g[c] = tok;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        const unsigned t = __hip_atomic_fetch_add(end.cnt + LNB_BATCH_MAX, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = t == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (threadIdx.x == 0) end.cnt[LNB_BATCH_MAX] = 0;        // (ready for the next launch: stream order)
+    spec_many_accept_emit(end, (int)threadIdx.x);
 }

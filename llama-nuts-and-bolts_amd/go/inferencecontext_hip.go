@@ -379,6 +379,21 @@ type SpecManyInfo struct{ Passes, VerifyPasses, Columns, MaxColumns, LongPasses 
 // the tokens before it; startPos[s] < 0: skipped, as a finished member of a chunked run).  colBudget: columns per pass, 0 = 16 * ceil(n / 16).  Every
 // context's tokens, finished flag and KV cache rows are bit-identical to its own DecodeGreedyUntil.
 func DecodeSpeculativeMany(lt *LlamaTransformer, ctxs []*InferenceContext, histories [][]TokenId, tokens []TokenId, startPos []int, maxSteps int, colBudget int) (out [][]TokenId, finished []bool, stats []SpecStats, info SpecManyInfo, err error) {
+	return decodeSpeculativeMany(lt, ctxs, nil, histories, tokens, startPos, maxSteps, colBudget)
+}
+
+// DecodeSpeculativeSampleMany is DecodeSpeculativeMany with one sampler per context (lnb_decode_speculative_sample_many): every context's tokens,
+// finished flag and KV cache rows are bit-identical to its own DecodeSampleUntil -- the sampler's draw depends on (seed, position) only, so the
+// drafts are accepted by plain comparison and no rejection sampling is involved.  A Temperature-0 member is greedy.
+func DecodeSpeculativeSampleMany(lt *LlamaTransformer, ctxs []*InferenceContext, samplers []Sampler, histories [][]TokenId, tokens []TokenId, startPos []int, maxSteps int, colBudget int) (out [][]TokenId, finished []bool, stats []SpecStats, info SpecManyInfo, err error) {
+	if len(samplers) != len(ctxs) || len(samplers) == 0 {
+		return nil, nil, nil, info, fmt.Errorf("DecodeSpeculativeSampleMany: %d samplers for %d contexts", len(samplers), len(ctxs))
+	}
+	return decodeSpeculativeMany(lt, ctxs, samplers, histories, tokens, startPos, maxSteps, colBudget)
+}
+
+// samplers nil: the greedy call
+func decodeSpeculativeMany(lt *LlamaTransformer, ctxs []*InferenceContext, samplers []Sampler, histories [][]TokenId, tokens []TokenId, startPos []int, maxSteps int, colBudget int) (out [][]TokenId, finished []bool, stats []SpecStats, info SpecManyInfo, err error) {
 	n := len(ctxs)
 	if n == 0 || len(histories) != n || len(tokens) != n || len(startPos) != n {
 		return nil, nil, nil, info, fmt.Errorf("DecodeSpeculativeMany: %d contexts, %d histories, %d tokens, %d start positions", n, len(histories), len(tokens), len(startPos))
@@ -424,7 +439,15 @@ func DecodeSpeculativeMany(lt *LlamaTransformer, ctxs []*InferenceContext, histo
 	fin := make([]C.int32_t, n)
 	st := make([]C.lnb_spec_stats, n)
 	var ci C.lnb_spec_many_info
+	cs := make([]C.lnb_sampler, len(samplers))
+	for i, s := range samplers {
+		cs[i] = C.lnb_sampler{temperature: C.float(s.Temperature), top_p: C.float(s.TopP), top_k: C.int32_t(s.TopK), reserved: 0, seed: C.uint64_t(s.Seed)}
+	}
 	if err = lnbCall(func() C.int {
+		if samplers != nil {
+			return C.lnb_decode_speculative_sample_many((**C.lnb_ctx)(unsafe.Pointer(&hs[0])), C.int(n), &cs[0], hp, &hn[0], &tok[0], &pos[0], C.int(maxSteps), C.int(colBudget),
+				(*C.int32_t)(unsafe.Pointer(&buf[0])), &ng[0], &fin[0], &st[0], &ci, nil)
+		}
 		return C.lnb_decode_speculative_many((**C.lnb_ctx)(unsafe.Pointer(&hs[0])), C.int(n), hp, &hn[0], &tok[0], &pos[0], C.int(maxSteps), C.int(colBudget),
 			(*C.int32_t)(unsafe.Pointer(&buf[0])), &ng[0], &fin[0], &st[0], &ci, nil)
 	}); err != nil {
@@ -500,6 +523,17 @@ func (ic *InferenceContext) VerifyAttentionForm(lt *LlamaTransformer) (int, erro
 // DecodeSpeculativeUntil is DecodeGreedyUntil with drafts verified in batched passes over the weights: the same tokens, finished flag and
 // KV cache rows, fewer passes when the text repeats itself or the corpus.  history: the tokens before `token` (the prompt).
 func (ic *InferenceContext) DecodeSpeculativeUntil(lt *LlamaTransformer, history []TokenId, token TokenId, startPos int, maxSteps int) (tokens []TokenId, finished bool, stats SpecStats, err error) {
+	return ic.decodeSpeculative(lt, nil, history, token, startPos, maxSteps)
+}
+
+// DecodeSpeculativeSampleUntil is DecodeSampleUntil with drafts verified in batched passes (lnb_decode_speculative_sample_until): the same tokens,
+// finished flag and KV cache rows whatever the draft settings, because the sampler's draw depends on (seed, position) only.
+func (ic *InferenceContext) DecodeSpeculativeSampleUntil(lt *LlamaTransformer, s Sampler, history []TokenId, token TokenId, startPos int, maxSteps int) (tokens []TokenId, finished bool, stats SpecStats, err error) {
+	return ic.decodeSpeculative(lt, &s, history, token, startPos, maxSteps)
+}
+
+// s nil: the greedy loop
+func (ic *InferenceContext) decodeSpeculative(lt *LlamaTransformer, s *Sampler, history []TokenId, token TokenId, startPos int, maxSteps int) (tokens []TokenId, finished bool, stats SpecStats, err error) {
 	if maxSteps <= 0 {
 		return nil, false, stats, fmt.Errorf("max_steps must be positive")
 	}
@@ -514,6 +548,11 @@ func (ic *InferenceContext) DecodeSpeculativeUntil(lt *LlamaTransformer, history
 	var n, fin C.int
 	var st C.lnb_spec_stats
 	if err = lnbCall(func() C.int {
+		if s != nil {
+			cs := C.lnb_sampler{temperature: C.float(s.Temperature), top_p: C.float(s.TopP), top_k: C.int32_t(s.TopK), reserved: 0, seed: C.uint64_t(s.Seed)}
+			return C.lnb_decode_speculative_sample_until(ic.handle, &cs, h, C.int(len(history)), C.int32_t(token), C.int(startPos), C.int(maxSteps),
+				(*C.int32_t)(unsafe.Pointer(&out[0])), &n, &fin, &st, nil)
+		}
 		return C.lnb_decode_speculative_until(ic.handle, h, C.int(len(history)), C.int32_t(token), C.int(startPos), C.int(maxSteps),
 			(*C.int32_t)(unsafe.Pointer(&out[0])), &n, &fin, &st, nil)
 	}); err != nil {

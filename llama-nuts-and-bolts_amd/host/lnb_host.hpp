@@ -276,6 +276,16 @@ public:
         r.Tokens.resize(n); r.Finished = fin != 0;
         return r;
     }
+    // lnb_decode_speculative_sample_until: DecodeSampleUntil with drafts verified in batched passes -- the same tokens and KV rows (the draw depends on
+    // (seed, position) only, so no rejection sampling is involved)
+    Speculative DecodeSpeculativeSampleUntil(const lnb_sampler& sampler, const std::vector<TokenId>& history, TokenId token, int startPos, int maxSteps) {
+        Speculative r; r.Tokens.resize(maxSteps > 0 ? maxSteps : 1);
+        int n = 0, fin = 0;
+        check(lnb_decode_speculative_sample_until(h_, &sampler, history.empty() ? nullptr : history.data(), (int)history.size(), token, startPos, maxSteps,
+                                                  r.Tokens.data(), &n, &fin, &r.Stats, nullptr));
+        r.Tokens.resize(n); r.Finished = fin != 0;
+        return r;
+    }
 private:
     static void layer_cb(int layer, int n, double secs, void* user) {      // infContext.Logf(...), llamatransformer.go:163
         auto* self = (InferenceContext*)user;
@@ -333,8 +343,9 @@ inline AppendManyInfo GetAppendManyInfo(const LlamaTransformer& t) {       // of
 struct SpeculativeMany {
     std::vector<std::vector<TokenId>> Tokens; std::vector<bool> Finished; std::vector<lnb_spec_stats> Stats; lnb_spec_many_info Info{}; float Ms = 0.f;
 };
-inline SpeculativeMany DecodeSpeculativeMany(const std::vector<InferenceContext*>& ctxs, const std::vector<std::vector<TokenId>>& histories,
-                                             const std::vector<TokenId>& tokens, const std::vector<int>& startPos, int maxSteps, int colBudget = 0) {
+// samplers: nullptr = lnb_decode_speculative_many (greedy), else lnb_decode_speculative_sample_many with samplers[n]
+inline SpeculativeMany decodeSpeculativeMany(const lnb_sampler* samplers, const std::vector<InferenceContext*>& ctxs, const std::vector<std::vector<TokenId>>& histories,
+                                             const std::vector<TokenId>& tokens, const std::vector<int>& startPos, int maxSteps, int colBudget) {
     const size_t n = ctxs.size(), steps = maxSteps > 0 ? (size_t)maxSteps : 1;
     if (n == 0 || histories.size() != n || tokens.size() != n || startPos.size() != n) throw std::runtime_error("DecodeSpeculativeMany: the arrays differ in length");
     std::vector<lnb_ctx*> hs;
@@ -342,10 +353,26 @@ inline SpeculativeMany DecodeSpeculativeMany(const std::vector<InferenceContext*
     for (auto* c : ctxs) hs.push_back(c ? c->handle() : nullptr);
     for (const auto& h : histories) { hp.push_back(h.empty() ? nullptr : h.data()); hn.push_back((int32_t)h.size()); }
     SpeculativeMany r; r.Stats.resize(n);
-    check(lnb_decode_speculative_many(hs.data(), (int)n, hp.data(), hn.data(), tokens.data(), pos.data(), maxSteps, colBudget, out.data(), ng.data(), fin.data(),
-                                      r.Stats.data(), &r.Info, &r.Ms));
+    if (samplers)
+        check(lnb_decode_speculative_sample_many(hs.data(), (int)n, samplers, hp.data(), hn.data(), tokens.data(), pos.data(), maxSteps, colBudget, out.data(), ng.data(),
+                                                 fin.data(), r.Stats.data(), &r.Info, &r.Ms));
+    else
+        check(lnb_decode_speculative_many(hs.data(), (int)n, hp.data(), hn.data(), tokens.data(), pos.data(), maxSteps, colBudget, out.data(), ng.data(), fin.data(),
+                                          r.Stats.data(), &r.Info, &r.Ms));
     for (size_t s = 0; s < n; s++) { r.Tokens.emplace_back(out.begin() + s * steps, out.begin() + s * steps + ng[s]); r.Finished.push_back(fin[s] != 0); }
     return r;
+}
+inline SpeculativeMany DecodeSpeculativeMany(const std::vector<InferenceContext*>& ctxs, const std::vector<std::vector<TokenId>>& histories,
+                                             const std::vector<TokenId>& tokens, const std::vector<int>& startPos, int maxSteps, int colBudget = 0) {
+    return decodeSpeculativeMany(nullptr, ctxs, histories, tokens, startPos, maxSteps, colBudget);
+}
+// lnb_decode_speculative_sample_many: the same with one sampler per context (a temperature-0 member is greedy); every context's tokens, finished flag and
+// KV rows are its own DecodeSampleUntil's
+inline SpeculativeMany DecodeSpeculativeSampleMany(const std::vector<InferenceContext*>& ctxs, const std::vector<lnb_sampler>& samplers,
+                                                   const std::vector<std::vector<TokenId>>& histories, const std::vector<TokenId>& tokens,
+                                                   const std::vector<int>& startPos, int maxSteps, int colBudget = 0) {
+    if (samplers.size() != ctxs.size() || samplers.empty()) throw std::runtime_error("DecodeSpeculativeSampleMany: one sampler per context");
+    return decodeSpeculativeMany(samplers.data(), ctxs, histories, tokens, startPos, maxSteps, colBudget);
 }
 
 enum GenerationState{ GSInProgress = 1, GSFinishedByReachingEOS = 2, GSFinishedByReachingSeqLen = 3 };   // inference.go:13-17

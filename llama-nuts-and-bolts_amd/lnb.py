@@ -75,6 +75,7 @@ EXPORTS = [
     "lnb_ctx_fork", "lnb_ctx_prefix_bytes", "lnb_ctx_save_prefix", "lnb_ctx_load_prefix",
     "lnb_forward_append_many", "lnb_model_append_many_info",
     "lnb_decode_speculative_many",
+    "lnb_decode_speculative_sample_until", "lnb_decode_speculative_sample_many", "lnb_op_spec_sample_accept",
     "lnb_form_count", "lnb_form_count_reset", "lnb_form_name",
     "lnb_op_rmsnorm_sum",
 ]
@@ -267,6 +268,11 @@ def lib():
     L.lnb_decode_speculative_until.argtypes = [vp, vp, C.c_int, C.c_int32, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                C.POINTER(SpecStats), f32p]
     L.lnb_op_ngram_draft.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_int)]
+    L.lnb_decode_speculative_sample_until.argtypes = [vp, C.POINTER(Sampler), vp, C.c_int, C.c_int32, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                      C.POINTER(SpecStats), f32p]
+    L.lnb_decode_speculative_sample_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Sampler), C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, vp, vp, vp,
+                                                     C.POINTER(SpecStats), C.POINTER(SpecManyInfo), f32p]
+    L.lnb_op_spec_sample_accept.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.c_int, vp, vp, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lnb_model_num_tensors.argtypes = [vp]
     L.lnb_model_tensor_info.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.lnb_checkpoint_open.argtypes = [C.c_char_p, C.POINTER(vp)]
@@ -779,6 +785,18 @@ class InferenceContext:
                                                  C.byref(n), C.byref(fin), C.byref(st), C.byref(ms)))
         return out[:n.value].copy(), bool(fin.value), st.as_dict(), ms.value
 
+    def decode_speculative_sample_until(self, sampler, history, token, start_pos, max_steps):
+        """decode_sample_until with drafts verified in batched passes (lnb_decode_speculative_sample_until): the same tokens and KV rows, because the
+        sampler's draw depends on (seed, position) only.  sampler = a Sampler or (temperature, top_k, top_p, seed); None reaches the library as NULL
+        -> (tokens, finished flag, stats dict, device ms)"""
+        s = None if sampler is None else _samplers([sampler], 1)
+        h = np.ascontiguousarray(history, dtype=np.int32)
+        out = np.empty(max(int(max_steps), 0), dtype=np.int32)
+        ms, n, fin, st = C.c_float(0), C.c_int(0), C.c_int(0), SpecStats()
+        _chk(self.L.lnb_decode_speculative_sample_until(self.h, s, _p(h) if h.size else None, int(h.size), int(token), start_pos, max_steps, _p(out),
+                                                        C.byref(n), C.byref(fin), C.byref(st), C.byref(ms)))
+        return out[:n.value].copy(), bool(fin.value), st.as_dict(), ms.value
+
     def token_prob_walks(self):
         """rows of this context (decode steps, scored rows) whose probabilities walked the reference's serial sum"""
         n = C.c_int(0)
@@ -878,12 +896,24 @@ def ForwardAppendMany(ctxs, token_lists, start_pos, want_logits=True):
     return [logits[e - r:e] for e, r in zip(ends, rows)], am
 
 
+def DecodeSpeculativeSampleMany(ctxs, samplers, histories, tokens, start_pos, max_steps, col_budget=0):
+    """DecodeSpeculativeMany with one sampler per context (lnb_decode_speculative_sample_many): every context's tokens, finished flag and KV rows are the
+    bits of its own decode_sample_until; a temperature-0 member is greedy -> the same tuple"""
+    ctxs = list(ctxs)
+    ss = None if samplers is None else _samplers(samplers, len(ctxs))
+    return _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, True, ss)
+
+
 def DecodeSpeculativeMany(ctxs, histories, tokens, start_pos, max_steps, col_budget=0):
     """decode_greedy_until of the contexts `ctxs` (1..128, one transformer) together, every context drafting for itself with its own set_draft
     settings and ONE batched pass over the weights verifying all of them (lnb_decode_speculative_many).  Context s continues from tokens[s] at
     start_pos[s] (histories[s]: the tokens before it; start_pos[s] < 0: skipped); col_budget: columns per pass, 0 = 16 * ceil(n / 16).  Every
     context's tokens, finished flag and KV rows are the bits of its own decode_greedy_until
     -> (list of int32 token arrays, list of finished flags, list of stats dicts, info dict, device ms)"""
+    return _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, False, None)
+
+
+def _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, sample, ss):
     ctxs = list(ctxs)
     n = len(ctxs)
     hist = [np.ascontiguousarray(h, dtype=np.int32).reshape(-1) for h in histories]
@@ -898,8 +928,12 @@ def DecodeSpeculativeMany(ctxs, histories, tokens, start_pos, max_steps, col_bud
     out = np.zeros((n, max(int(max_steps), 1)), dtype=np.int32)
     ng = np.zeros(n, dtype=np.int32); fin = np.zeros(n, dtype=np.int32)
     st = (SpecStats * n)(); info = SpecManyInfo(); ms = C.c_float(0)
-    _chk(L.lnb_decode_speculative_many(arr, n, harr, _p(nh), _p(tok), _p(pos), int(max_steps), int(col_budget), _p(out), _p(ng), _p(fin),
-                                       st, C.byref(info), C.byref(ms)))
+    if sample:
+        _chk(L.lnb_decode_speculative_sample_many(arr, n, ss, harr, _p(nh), _p(tok), _p(pos), int(max_steps), int(col_budget), _p(out), _p(ng), _p(fin),
+                                                  st, C.byref(info), C.byref(ms)))
+    else:
+        _chk(L.lnb_decode_speculative_many(arr, n, harr, _p(nh), _p(tok), _p(pos), int(max_steps), int(col_budget), _p(out), _p(ng), _p(fin),
+                                           st, C.byref(info), C.byref(ms)))
     return ([out[s, :ng[s]].copy() for s in range(n)], [bool(f) for f in fin], [st[s].as_dict() for s in range(n)], info.as_dict(), ms.value)
 
 
@@ -1057,12 +1091,15 @@ class InferenceEngine:
     long_context: the generation's context is a long one (lnb_ctx_create_long, up to MAX_SEQ_LEN positions) whose activation buffers hold
     prefill_chunk rows, or the prompt when the chunk is 0."""
 
-    def __init__(self, transformer, seq_len, stop_token_ids=(), prefill_chunk=0, long_context=False, sampler=None):
+    def __init__(self, transformer, seq_len, stop_token_ids=(), prefill_chunk=0, long_context=False, sampler=None, draft=None):
         if int(prefill_chunk) < 0:
             raise LnbError("prefill_chunk must be 0 (one Forward) or a positive row count")
         self.t, self.seq_len, self.stop, self.prefill_chunk = transformer, seq_len, set(stop_token_ids), int(prefill_chunk)
         self.long_context = bool(long_context)
         self.sampler = sampler                               # None: greedy.  A Sampler (or its tuple): EVERY generated token is sampled, the prompt's own next token included
+        if draft is not None and len(tuple(draft)) != 3:
+            raise LnbError("draft must be None or (max_draft, ngram_min, ngram_max)")
+        self.draft = None if draft is None else tuple(int(v) for v in draft)      # None: one pass per token.  Else the speculative loop drafts from the running text: the same tokens
 
     def GenerateTokens(self, prompt_tokens, max_new=None):
         prompt = list(prompt_tokens)
@@ -1089,7 +1126,13 @@ class InferenceEngine:
                     raise LnbError("the prompt's last logits row has no candidate to sample (all NaN or -inf)")
             out = [first]
             if first not in self.stop and n_new > 1:
-                if self.sampler is None:
+                if self.draft is not None:
+                    ctx.set_draft(*self.draft)
+                    if self.sampler is None:
+                        more, _, _, _ = ctx.decode_speculative_until(prompt, first, len(prompt), n_new - 1)
+                    else:
+                        more, _, _, _ = ctx.decode_speculative_sample_until(self.sampler, prompt, first, len(prompt), n_new - 1)
+                elif self.sampler is None:
                     more, _ = ctx.decode_greedy(first, len(prompt), n_new - 1)
                 else:
                     more, _, _ = ctx.decode_sample_until(self.sampler, first, len(prompt), n_new - 1)
@@ -1191,6 +1234,22 @@ def op_ngram_draft(text, corpus=(), ngram_min=1, ngram_max=4, max_draft=MAX_DRAF
     _chk(lib().lnb_op_ngram_draft(device, _p(t) if t.size else None, int(t.size), _p(c) if c.size else None, int(c.size),
                                   int(ngram_min), int(ngram_max), int(max_draft), _p(out), C.byref(n)))
     return out[:n.value].copy()
+
+
+def op_spec_sample_accept(logits_u16, sampler, pos0, col_tokens, stop_ids=(), device=0):
+    """spec_sample_commit_kernel on host rows (lnb_op_spec_sample_accept): column i of a verify pass has logits row i, took col_tokens[i] and sits at pos0 + i
+    -> (the tokens the pass emits as an int32 array, finished flag)"""
+    a = np.ascontiguousarray(logits_u16, dtype=np.uint16)
+    w, V = a.shape
+    ct = np.ascontiguousarray(col_tokens, dtype=np.int32)
+    if ct.size != w:
+        raise LnbError("%d column tokens for %d rows" % (ct.size, w))
+    stop = np.ascontiguousarray(stop_ids, dtype=np.int32)
+    out = np.zeros(w, dtype=np.int32)
+    n, fin = C.c_int(0), C.c_int(0)
+    _chk(lib().lnb_op_spec_sample_accept(device, _p(a), w, V, _samplers([sampler], 1), int(pos0), _p(ct), _p(stop) if stop.size else None, int(stop.size),
+                                         _p(out), C.byref(n), C.byref(fin)))
+    return out[:n.value].copy(), bool(fin.value)
 
 
 def op_exp_table(divisor=1.0, device=0):

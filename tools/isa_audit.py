@@ -185,7 +185,9 @@ def main(asm_path=None):
     # (round 6: attn_one_kernel inlines the same exp beside its in-launch exchange: 30 scalars parked in VGPR lanes; it is the opt-in one-launch form)
     # (sample_kernel / batch_sample_kernel: the bisection loop's eight-wide weight arithmetic fills the scalar file; 18 / 11 loop-invariant scalars wait in the lanes
     # of one VGPR around it.  Their scratch size is 0 and their vgpr_spill_count is 0, which the line above still requires.)
-    SGPR_SPILL_OK = ("attn_gqa_kernel", "attn_one_kernel", "_Z13sample_kernelP", "_Z19batch_sample_kernelP")      # (the last two: these two kernels and no other *sample_kernel)
+    # (spec_sample_commit_kernel / spec_many_sample_commit_kernel: the same sample_block inlined, 17 / 15 scalars in VGPR lanes; what their epilogues need waits in the LDS)
+    SGPR_SPILL_OK = ("attn_gqa_kernel", "attn_one_kernel", "_Z13sample_kernelP", "_Z19batch_sample_kernelP",      # (these two kernels and no other *sample_kernel)
+                     "_Z25spec_sample_commit_kernelP", "_Z30spec_many_sample_commit_kernel6SmPass")
     spills, cur = [], ""
     for l in txt:
         mname = re.search(r"\.name:\s+(\S+)", l)
