@@ -27,6 +27,7 @@
 #include "lnb_wpack.h"
 #include "lnb_batchplan.h"
 #include "lnb_handoff.h"
+#include "lnb_own.h"
 #include "lnb_rccl.h"
 #include "lnb_sample.h"
 static_assert(LNB_MAX_SEQ_LEN == LNB_SEQ_MAX, "lnb.h and lnb_device.h disagree on the longest context");
@@ -142,6 +143,25 @@ extern "C" const char* lnb_last_error(void) { return g_err; }
 extern "C" __attribute__((visibility("hidden"))) void lnb_set_error(const char* msg) { snprintf(g_err, sizeof g_err, "%s", msg); }
 #define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
+// Who releases what (lnb_own.h): a device resource is an owning member or a local owner, released when its scope ends -- no free list to keep.
+// Members are destroyed in reverse order of declaration: a handle struct declares its stream FIRST, so that it goes after everything enqueued on it.
+template <class T> using Dev = Owned<T*, hipFree>;                    // device memory
+template <class T> using Pinned = Owned<T*, hipHostFree>;             // pinned host memory
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using GraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
+template <class T> using DevGrown = Grown<T*, hipFree>;
+using DevArena = Arena<hipError_t, hipMalloc, hipFree>;
+template <class T> static hipError_t dev_alloc(Dev<T>& p, size_t bytes) { return p.fill([&](T** q) { return hipMalloc((void**)q, bytes); }); }
+template <class T> static hipError_t dev_reserve(DevGrown<T>& p, size_t bytes) { return p.reserve(bytes, [](T** q, size_t n) { return hipMalloc((void**)q, n); }); }
+template <class T> static hipError_t pinned_alloc(Pinned<T>& p, size_t bytes, unsigned flags) { return p.fill([&](T** q) { return hipHostMalloc((void**)q, bytes, flags); }); }
+static hipError_t event_create(Event& e, unsigned flags = hipEventDefault) { return e.fill([&](hipEvent_t* q) { return hipEventCreateWithFlags(q, flags); }); }
+static hipError_t stream_create(Stream& s, unsigned flags) { return s.fill([&](hipStream_t* q) { return hipStreamCreateWithFlags(q, flags); }); }
+// which captured step: the token launch that ends it, and the attention form its launches bake in
+enum GraphLaunch { GL_GREEDY = 0, GL_SAMPLE, GL_STAGE, GL_COUNT };
+enum GraphForm { GF_SHORT = 0, GF_LONG, GF_ROWS, GF_COUNT };         // (0, 1, 2: also what lnb_ctx_verify_attention_form reports)
+using Graphs = GraphTable<hipGraphExec_t, hipGraphExecDestroy, GL_COUNT, GF_COUNT>;
+
 static inline float bf_wide_h(uint16_t b) { uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; }
 static inline uint16_t bf_trunc_h(float f) { uint32_t u; memcpy(&u, &f, 4); return (uint16_t)(u >> 16); }
 
@@ -149,19 +169,20 @@ static inline uint16_t bf_trunc_h(float f) { uint32_t u; memcpy(&u, &f, 4); retu
 struct TensorRef {
     int rows = 0, cols = 0;        // logical shape in the reference layout (1-D tensors: rows = 1)
     bool tiled = false;
-    uint16_t* linear = nullptr;    // when !tiled
+    uint16_t* linear = nullptr;    // when !tiled (the model's `weights` arena owns it)
     TiledDesc* td = nullptr;       // when tiled
     int row_off = 0, chain = 0;
     uint32_t synth_id = 0; int synth_kind = 0;
     int rank = 2;
 };
 struct LayerW {
+    // (raw pointers, these and TiledDesc::w / w16 -- the launch layer shares the descriptor: the model's `weights` arena owns them, its `m16` arena the M16 copies)
     uint16_t* attn_norm = nullptr; uint16_t* ffn_norm = nullptr;
     TiledDesc wqkv{}, wo{}, w13{}, w2{};
     // batched decode (lnb_model_enable_batch): the same matrices in the 16-row matrix-core layout (M16, lnb_device.h)
     uint16_t *m_wqkv = nullptr, *m_wo = nullptr, *m_w13 = nullptr, *m_w2 = nullptr;
     // one-token decode (lnb_model_finalize, LNB_W13_PACKED): the 13-bit planar copy of w13 (lnb_wpack.h) the latency form streams instead of the raw bf16
-    void* p_w13 = nullptr; unsigned p_base = 0; bool p_ok = false;     // p_ok: the copy holds what w13 holds
+    Dev<void> p_w13; unsigned p_base = 0; bool p_ok = false;           // p_ok: the copy holds what w13 holds
     int p_status = -1;                                                  // WPACK_* of the last attempt (-1: none -- knob off or a layout the packed kernel has no form for)
 };
 struct lnb_model {
@@ -169,19 +190,20 @@ struct lnb_model {
     int device = 0, layer_begin = 0, layer_end = 0;      // layers this handle touches
     int part_begin = 0, part_end = 0;                     // ... in thirds of a block: 3l = attention part of layer l, 3l+1 = gate/up, 3l+2 = down
     int head_dim = 0, n_rep = 0, ffn_hidden = 0, q_dim = 0, kv_dim = 0;
+    Stream stream;
+    DevArena weights, m16;                // what alloc_tiled / alloc_linear and m16_copy hand out: tok_embd, norm, output, m_output and the LayerW pointers
     uint16_t* tok_embd = nullptr; uint16_t* norm = nullptr; TiledDesc output{};
     std::vector<LayerW> layers;           // indexed by absolute layer id - layer_begin
     std::map<std::string, TensorRef> tensors;
-    float* cis = nullptr; int cis_rows = 0; float* silu = nullptr; double* exp_tab = nullptr;
-    double* prob_etab = nullptr;          // exp(double(bf16)) of the host C library for all 65536 patterns: the token probabilities (token_probs_kernel)
+    Dev<float> cis; int cis_rows = 0; Dev<float> silu; Dev<double> exp_tab;
+    Dev<double> prob_etab;                // exp(double(bf16)) of the host C library for all 65536 patterns: the token probabilities (token_probs_kernel)
     std::vector<float> cis_host;
-    hipStream_t stream = nullptr;
     bool finalized = false;
     int64_t weight_bytes = 0;
     bool batch_enabled = false; uint16_t* m_output = nullptr; int64_t batch_bytes = 0;
     int64_t wpack_bytes = 0;              // the 13-bit planar copies of the gate|up matrices (lnb_model_wpack_bytes)
     // the LM head's 13-bit copy (lnb_model_finalize, LNB_HEAD_PACKED; 128-row two-chain blocks: lnb_wpack.h), as LayerW's p_* fields are for gate|up
-    void* p_out = nullptr; unsigned p_out_base = 0; bool p_out_ok = false; int p_out_status = -1; int64_t wpack_head_bytes = 0;
+    Dev<void> p_out; unsigned p_out_base = 0; bool p_out_ok = false; int p_out_status = -1; int64_t wpack_head_bytes = 0;
     std::mutex am_mu; struct AppendMany* am = nullptr;     // lnb_forward_append_many: the call's buffers and tables, created on first use; the mutex is held for a whole call
     bool first() const { return part_begin == 0; }
     bool last() const { return part_end == 3 * a.n_layers; }
@@ -194,14 +216,13 @@ struct lnb_model {
 // What a unit that moves through the pipeline's stages -- a context (lnb_pipeline_tick) or a batch (lnb_pipeline_tick_batch) -- needs to be
 // handed across a stage boundary: three events between its own stream and the pipe's exchange stream, and whether one is outstanding.
 struct PipeLink {
-    hipEvent_t ev_done = nullptr, ev_in = nullptr, ev_sent = nullptr;   // its stage step has run / its input has arrived / its output has left
+    Event ev_done, ev_in, ev_sent;         // its stage step has run / its input has arrived / its output has left
     bool in_pending = false, sent_pending = false;
     bool recv_unmatched = false;           // in-process transport: a receive into this unit is posted and its sender has not arrived yet
     int ensure() {                         // (created on the unit's first tick)
-        if (!ev_done) for (hipEvent_t* e : {&ev_done, &ev_in, &ev_sent}) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        if (!ev_sent) for (Event* e : {&ev_done, &ev_in, &ev_sent}) HIPCHK(event_create(*e, hipEventDisableTiming));
         return 0;
     }
-    void destroy() { for (hipEvent_t e : {ev_done, ev_in, ev_sent}) if (e) hipEventDestroy(e); }
     // before the unit's stage step on its stream st: its input has arrived and its previous output has left
     int await(hipStream_t st, const char* unit) {
         if (recv_unmatched) return fail("in-process pipeline: this %s's input has been requested but the sending stage has not posted it yet "
@@ -214,69 +235,70 @@ struct PipeLink {
 struct lnb_ctx {
     lnb_model* m = nullptr; int seq_len = 0;
     int max_rows = 0;                      // rows per call the activation buffers (x, h, xn, q, att, ffn) hold: seq_len, or lnb_ctx_create_long's max_rows
-    hipStream_t stream = nullptr;
-    std::vector<uint16_t*> ck, cv;
-    StepState* st = nullptr; int32_t* dtok = nullptr; int32_t* dnext = nullptr; int* derr = nullptr;
-    int32_t* dout = nullptr; int dout_cap = 0;
-    uint16_t *x = nullptr, *h = nullptr, *q = nullptr, *att = nullptr, *ffn = nullptr, *logits = nullptr;
-    uint16_t* xn = nullptr;                // [max_rows][dim] normalised rows for the matrix-core prefill path
+    Stream stream;                         // (declared before everything enqueued on it: released last)
+    std::vector<Dev<uint16_t>> ck, cv;     // per layer of the stage; empty where the stage holds no attention part of the block
+    Dev<StepState> st; Dev<int32_t> dtok, dnext; Dev<int> derr;
+    Dev<int32_t> dout; int dout_cap = 0;
+    Dev<uint16_t> x, h, q, att, ffn, logits;
+    Dev<uint16_t> xn;                      // [max_rows][dim] normalised rows for the matrix-core prefill path
     int logits_rows = 0;
-    hipGraphExec_t graph = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // the captured steps: greedy / sampling (lnb_decode_sample_until: they hold the POINTER d_smp, the call copies its sampler there before the replays) /
+    // pipeline stage (lnb_pipeline_tick), each per attention form (short, long).  Every one bakes in the context's buffers, its arithmetic mode and its
+    // attention form: whatever changes one of those drops them all (graphs.drop_all())
+    Graphs graphs;
+    Event ev0, ev1;
     lnb_layer_cb cb = nullptr; void* cb_user = nullptr;
-    int32_t* h_io = nullptr;               // pinned host words of lnb_forward_stage_begin/_end: [0] argmax, [1] token error, [2..] tokens
+    Pinned<int32_t> h_io;                  // pinned host words of lnb_forward_stage_begin/_end: [0] argmax, [1] token error, [2..] tokens
     bool pending = false, pending_tokens = false, pending_argmax = false;
     int mode = LNB_MODE_EXACT;             // LNB_MODE_FAST: split-K kernels of lnb_fast.hip (tolerance mode, opt-in)
     int sched = LNB_SCHED_LATENCY;         // LNB_SCHED_THROUGHPUT: the co-residency-friendly forms of the one-token kernels (lnb_ctx_set_schedule)
     int n_stop = 0;                        // host copy of StepState.n_stop (lnb_ctx_set_stop_ids): entry points that cannot honour stop ids refuse such a context
     int batch_users = 0;                   // live lnb_batch handles this context is a member of: their device tables and captured graphs hold its raw pointers
     // long-context decode attention (attn_long_*_kernel): used for one-token calls whose context exceeds attn_long_T
-    double* e_buf = nullptr; double* z_part = nullptr; int* zseq_count = nullptr;
+    Dev<double> e_buf, z_part; Dev<int> zseq_count;
     int last_prefill_form = 0;         // lnb_ctx_prefill_attention_form
-    uint64_t* score_idx = nullptr; size_t score_idx_bytes = 0; int sidx_jt = 0;      // attn_mfma3_kernel's scratch (the exp-table indices of pass 1), grown on demand by check_call; sidx_jt = 0: this call runs attn_mfma_kernel
-    unsigned* attn_cnt = nullptr;          // attn_one_kernel: [n_heads] arrival counters of its in-launch exchange + [n_heads] = polls that ran out
+    DevGrown<uint64_t> score_idx; int sidx_jt = 0;      // attn_mfma3_kernel's scratch (the exp-table indices of pass 1), grown on demand by check_call; sidx_jt = 0: this call runs attn_mfma_kernel
+    Dev<unsigned> attn_cnt;                // attn_one_kernel: [n_heads] arrival counters of its in-launch exchange + [n_heads] = polls that ran out
     int attn_long_T = 0; int force_zseq = 0;   // force_zseq: bit 0 = walk the serial softmax denominator, bit 1 = keep the two-launch long-context form, bit 2 = one launch with every poll timing out (tests), bit 3 = one launch
     int attn_short_cap = 0;                // longest context the one-workgroup-per-head kernel can stage in the LDS
     bool attn_long = false;                // selection for the launches being enqueued (set per call / per captured graph)
-    hipGraphExec_t graph_long = nullptr;   // the decode step captured with the long-context attention
-    // the sampling step (lnb_decode_sample_until): graphs of its own beside graph / graph_long, one per attention form; they hold the POINTER d_smp, the
-    // call copies its sampler there before the replays
-    hipGraphExec_t sgraph = nullptr, sgraph_long = nullptr;
-    LnbSampler* d_smp = nullptr;
-    // pipeline stage (lnb_pipeline_tick): one-token stage step as a captured graph per attention form, events towards / from the exchange stream
-    hipGraphExec_t stage_graph[2] = {nullptr, nullptr};
-    PipeLink link;
+    Dev<LnbSampler> d_smp;                 // the sampling step's sampler
+    PipeLink link;                         // pipeline stage (lnb_pipeline_tick): events towards / from the exchange stream
     int dev_pos = -1;                      // position the device-side StepState will hold when the stream reaches this point (-1: unknown)
     bool attn_causal = false;              // set by lnb_forward_append around its multi-row call: the attention launches take the true causal mask (AttnParams::causal)
     int call_T = 0;                        // start_pos + rows of the call being enqueued (0: not known to the host, e.g. inside a replayed graph)
-    hipEvent_t ev_h2d = nullptr; bool h2d_pending = false;   // the last copy out of the pinned staging words h_io[2..] (enqueue-only paths)
+    Event ev_h2d; bool h2d_pending = false;   // the last copy out of the pinned staging words h_io[2..] (enqueue-only paths)
     // token probabilities of the greedy loop (lnb_ctx_set_token_probs): a record log of dout_cap x top_k beside the token log
     int top_k = 0;
-    TokProbOut* tp_out = nullptr;          // device: this context's log (st = c->st: the record slot is the token's)
-    int32_t* tp_ids = nullptr; float* tp_logit = nullptr; float* tp_prob = nullptr; double* tp_logz = nullptr;
-    double* tp_zpart = nullptr; uint64_t* tp_kpart = nullptr; unsigned* tp_cnt = nullptr;   // one row's partials, arrival ticket
+    // (one struct, so that switching the feature off is `tp = {}`; the members of the TokProbOut on the device alias ids .. logz, st and zseq_count of this context)
+    struct TokProbLog {
+        Dev<TokProbOut> out;               // device: this context's log (st = c->st: the record slot is the token's)
+        Dev<int32_t> ids; Dev<float> logit, prob; Dev<double> logz;
+        Dev<double> zpart; Dev<uint64_t> kpart; Dev<unsigned> cnt;   // one row's partials, arrival ticket
+    } tp;
     int tp_last_k = 0, tp_last_n = 0;      // what the last decode call that ran this context recorded (k 0: nothing)
-    void* sc_buf = nullptr; size_t sc_bytes = 0;   // lnb_forward_score's scratch, grown on demand
+    DevGrown<char> sc_buf;                 // lnb_forward_score's scratch, grown on demand
     // speculative decoding (lnb_ctx_set_draft, lnb_decode_speculative_until): drafting settings, the corpus, the running text's head (history +
     // token), the verify columns' states and token words (index 0 unused: column 0 is this context's own), their argmax, the draft kernel's
     // scratch and the pinned word it reports to the host; one verify batch per width 2..16, built and captured on first use
     int sp_max_draft = 0, sp_ngram_min = 1, sp_ngram_max = 1;
-    int32_t* sp_corpus = nullptr; int sp_n_corpus = 0;
-    int32_t* sp_text = nullptr; int sp_text_cap = 0;
-    StepState* sp_st = nullptr; int32_t* sp_tok = nullptr; int32_t* sp_g = nullptr; int* sp_best = nullptr; unsigned* sp_cnt = nullptr;
-    int32_t* sp_word = nullptr; int32_t* sp_word_dev = nullptr; hipEvent_t sp_ev = nullptr;
-    struct lnb_batch* sp_b[LNB_MAX_DRAFT + 2] = {};
+    Dev<int32_t> sp_corpus; int sp_n_corpus = 0;
+    DevGrown<int32_t> sp_text;
+    Dev<StepState> sp_st; Dev<int32_t> sp_tok, sp_g; Dev<int> sp_best; Dev<unsigned> sp_cnt;
+    Pinned<int32_t> sp_word; Event sp_ev;
+    int32_t* sp_word_dev = nullptr;        // the device address of sp_word (mapped pinned memory: sp_word owns it)
+    struct lnb_batch* sp_b[LNB_MAX_DRAFT + 2] = {};      // (their scratch is this context's: destroyed before it, in lnb_ctx_destroy)
     // attention form of the verify passes (lnb_ctx_set_batched_attention): threshold (default: never), serial-sum switch, the ONE e_buf / z_part
     // scratch all widths share (sized for 16 columns, allocated when a pass first needs the long form), the form of the last verify pass
     int sp_attn_long_T = 0x7FFFFFFF, sp_force_zseq = 0, sp_last_form = 0;
-    double* sp_e_buf = nullptr; double* sp_z_part = nullptr;
+    Dev<double> sp_e_buf, sp_z_part;
     // multi-row long-context attention (attn_rows_*_kernel, lnb_ctx_set_rows_attention): appends of 2..15 rows (any row count at head_dim 32) whose
     // start_pos + seq exceeds rows_T (default attn_short_cap: the calls the row-per-workgroup kernel cannot take) run it; rows_flags bit 0 = every row
     // walks the serial sum, bit 1 = the verify passes run it wherever they would run the long form.  Its scratch is sp_e_buf / sp_z_part.
     int rows_T = 0, rows_flags = 0, last_append_form = 0;
     bool attn_rows = false;                // set by lnb_forward_append around a multi-row call that runs the pair
     bool rows_no_scratch = false;          // an append could not allocate the pair's scratch: such calls run as one-token steps from then on
-    void* fork_tab = nullptr; size_t fork_tab_bytes = 0;   // lnb_ctx_fork with this context as the source: the device table of the call, grown on demand
+    DevGrown<char> fork_tab;               // lnb_ctx_fork with this context as the source: the device table of the call, grown on demand
 };
 // Every path that rewrites the device-side StepState goes through here, so that the pipeline tick's "the graph left pos+1 behind, skip
 // the set_state launch" shortcut (dev_pos) can never act on a position some OTHER entry point has since overwritten (lnb_forward,
@@ -292,19 +314,11 @@ static int staging_acquire(lnb_ctx* c) {
     return 0;
 }
 static int staging_release(lnb_ctx* c) {
-    if (!c->ev_h2d) HIPCHK(hipEventCreateWithFlags(&c->ev_h2d, hipEventDisableTiming));
+    if (!c->ev_h2d) HIPCHK(event_create(c->ev_h2d, hipEventDisableTiming));
     HIPCHK(hipEventRecord(c->ev_h2d, c->stream)); c->h2d_pending = true;
     return 0;
 }
 
-// every captured graph of a context bakes in its buffers, its arithmetic mode and its attention form: whatever changes one of those drops them all
-static void drop_graphs(lnb_ctx* c) {
-    if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; }
-    if (c->graph_long) { hipGraphExecDestroy(c->graph_long); c->graph_long = nullptr; }
-    if (c->sgraph) { hipGraphExecDestroy(c->sgraph); c->sgraph = nullptr; }
-    if (c->sgraph_long) { hipGraphExecDestroy(c->sgraph_long); c->sgraph_long = nullptr; }
-    for (int i = 0; i < 2; i++) if (c->stage_graph[i]) { hipGraphExecDestroy(c->stage_graph[i]); c->stage_graph[i] = nullptr; }
-}
 static int auto_rw(int lane_rows, Knob env, int K = 0, bool plain = false, int unforced = 0) {      // unforced: the caller's choice while the knob is 0 (0: by shape)
     const int v = knob(env);
     if (v == 0 && unforced) return unforced;
@@ -322,18 +336,32 @@ static thread_local long long* g_dbg = nullptr;   // (thread-local: arming the s
 static thread_local int g_dbg_full = 0;           // ... with every barrier and ring wait timed (perturbs the launch); 0: phase stamps and the exit record only
 // one resident workgroup per CU: a matrix with more row blocks than CUs is walked persistently
 static void set_grid(GemvParams& g, const TiledDesc& t) { g.dbg = g_dbg; g.dbg_full = g_dbg ? g_dbg_full : 0; g.n_blocks = t.n_blocks; g.n_wg = t.n_blocks < g_num_cus ? t.n_blocks : g_num_cus; }
-static int alloc_tiled(TiledDesc& t, int n_rows, int K, int rw, int nch, int64_t& bytes) {
+// `bytes` of device memory out of an arena (the caller's scope owns them); a null pointer: the arena's latched error, in HIPCHK's words
+template <class T> static int arena_alloc(DevArena& a, T** p, size_t bytes) {
+    *p = (T*)a.alloc<char>(bytes);
+    if (!*p) HIPCHK(a.error());
+    return 0;
+}
+static int alloc_tiled(DevArena& a, TiledDesc& t, int n_rows, int K, int rw, int nch, int64_t& bytes) {
     t.n_rows = n_rows; t.k = K; t.rw = rw; t.nch = nch; t.n_blocks = rw == 4 ? (n_rows + 15) / 16 : (n_rows + rw - 1) / rw;   // rw 4: 16-row workgroups
     size_t n = tiled_elems(n_rows, K, rw, nch) * 2;
-    HIPCHK(hipMalloc((void**)&t.w, n));
+    if (arena_alloc(a, &t.w, n)) return -1;
     HIPCHK(hipMemset(t.w, 0, n));
     bytes += (int64_t)n;
     return 0;
 }
-static int alloc_linear(uint16_t** p, size_t elems, int64_t& bytes) {
-    HIPCHK(hipMalloc((void**)p, elems * 2)); HIPCHK(hipMemset(*p, 0, elems * 2)); bytes += (int64_t)elems * 2; return 0;
+static int alloc_linear(DevArena& a, uint16_t** p, size_t elems, int64_t& bytes) {
+    if (arena_alloc(a, p, elems * 2)) return -1;
+    HIPCHK(hipMemset(*p, 0, elems * 2)); bytes += (int64_t)elems * 2; return 0;
 }
 
+// what every entry point that takes a device index instead of a handle does first (the lnb_op_* test aids, lnb_pipeline_selftest)
+static int op_device(int device) {
+    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
+    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    return 0;
+}
 extern "C" int lnb_device_count(int* out) { int n = 0; HIPCHK(hipGetDeviceCount(&n)); *out = n; return 0; }
 extern "C" int lnb_abi_version(void) { return LNB_ABI_VERSION; }
 // the launch tally (lnb_forms.h): which kernel forms the launch functions of this process have picked since the last reset
@@ -379,25 +407,19 @@ extern "C" int lnb_runtime_info(int device, int probe_queues, lnb_runtime_info_t
     out->hw_queues_expected = out->hw_queues_env > 0 ? out->hw_queues_env : 4;
     if (probe_queues) {
         constexpr int NSTREAM = 32, SPIN_US = 2000;      // (2 ms per spin: the ~0.3 ms it takes the host to launch on 32 streams must not count as a round)
-        hipStream_t sts[NSTREAM] = {}; hipEvent_t e0 = nullptr, e1 = nullptr, ej[NSTREAM] = {};
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < NSTREAM && e == hipSuccess; i++) { e = hipStreamCreateWithFlags(&sts[i], hipStreamNonBlocking); if (e == hipSuccess) e = hipEventCreateWithFlags(&ej[i], hipEventDisableTiming); }
-        if (e == hipSuccess) e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
+        Stream sts[NSTREAM]; Event e0, e1, ej[NSTREAM];
+        for (int i = 0; i < NSTREAM; i++) { HIPCHK(stream_create(sts[i], hipStreamNonBlocking)); HIPCHK(event_create(ej[i], hipEventDisableTiming)); }
+        HIPCHK(event_create(e0)); HIPCHK(event_create(e1));
         float ms = 0;
-        for (int rep = 0; rep < 2 && e == hipSuccess; rep++) {      // (the first round warms the streams up)
-            e = hipEventRecord(e0, sts[0]);
-            for (int i = 1; i < NSTREAM && e == hipSuccess; i++) e = hipStreamWaitEvent(sts[i], e0, 0);
-            for (int i = 0; i < NSTREAM && e == hipSuccess; i++) e = lnbk_spin(SPIN_US, sts[i]);
-            for (int i = 1; i < NSTREAM && e == hipSuccess; i++) { e = hipEventRecord(ej[i], sts[i]); if (e == hipSuccess) e = hipStreamWaitEvent(sts[0], ej[i], 0); }
-            if (e == hipSuccess) e = hipEventRecord(e1, sts[0]);
-            if (e == hipSuccess) e = hipEventSynchronize(e1);
-            if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        for (int rep = 0; rep < 2; rep++) {                          // (the first round warms the streams up)
+            HIPCHK(hipEventRecord(e0, sts[0]));
+            for (int i = 1; i < NSTREAM; i++) HIPCHK(hipStreamWaitEvent(sts[i], e0, 0));
+            for (int i = 0; i < NSTREAM; i++) HIPCHK(lnbk_spin(SPIN_US, sts[i]));
+            for (int i = 1; i < NSTREAM; i++) { HIPCHK(hipEventRecord(ej[i], sts[i])); HIPCHK(hipStreamWaitEvent(sts[0], ej[i], 0)); }
+            HIPCHK(hipEventRecord(e1, sts[0]));
+            HIPCHK(hipEventSynchronize(e1));
+            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
         }
-        for (int i = 0; i < NSTREAM; i++) { if (sts[i]) hipStreamDestroy(sts[i]); if (ej[i]) hipEventDestroy(ej[i]); }
-        if (e0) hipEventDestroy(e0);
-        if (e1) hipEventDestroy(e1);
-        HIPCHK(e);
         const double rounds = (double)ms * 1000.0 / SPIN_US;     // 32 / Q, plus launch overhead
         int qm = rounds > 0.5 ? (int)((double)NSTREAM / rounds + 0.5) : NSTREAM;
         out->hw_queues_measured = qm < 1 ? 1 : (qm > NSTREAM ? NSTREAM : qm);
@@ -495,11 +517,11 @@ static int wpack_refresh(lnb_model* m, const TiledDesc* t);
 static int model_alloc(lnb_model* m) {
     const lnb_model_args& a = m->a;
     const int layer_begin = m->layer_begin, layer_end = m->layer_end;
-    HIPCHK(hipStreamCreate(&m->stream));
-    int64_t& wb = m->weight_bytes;
+    HIPCHK(stream_create(m->stream, hipStreamDefault));
+    int64_t& wb = m->weight_bytes; DevArena& A = m->weights;
     const int dim = a.dim, F = m->ffn_hidden;
     if (m->first()) {
-        if (alloc_linear(&m->tok_embd, (size_t)a.vocab_size * dim, wb)) return -1;
+        if (alloc_linear(A, &m->tok_embd, (size_t)a.vocab_size * dim, wb)) return -1;
         reg_linear(m, "tok_embeddings.weight", m->tok_embd, dim, 0, 0, a.vocab_size, 2);
     }
     m->layers.resize(layer_end - layer_begin);
@@ -511,9 +533,9 @@ static int model_alloc(lnb_model* m) {
         LayerW& L = m->layers[l - layer_begin];
         char nm[128]; uint32_t base = 16u * (uint32_t)(l + 1);
         if (m->has_attn(l)) {
-            if (alloc_linear(&L.attn_norm, dim, wb)) return -1;
-            if (alloc_tiled(L.wqkv, m->q_dim + 2 * m->kv_dim, dim, rwq, 1, wb)) return -1;
-            if (alloc_tiled(L.wo, dim, m->q_dim, rwo, 1, wb)) return -1;
+            if (alloc_linear(A, &L.attn_norm, dim, wb)) return -1;
+            if (alloc_tiled(A, L.wqkv, m->q_dim + 2 * m->kv_dim, dim, rwq, 1, wb)) return -1;
+            if (alloc_tiled(A, L.wo, dim, m->q_dim, rwo, 1, wb)) return -1;
             snprintf(nm, sizeof nm, "layers.%d.attention_norm.weight", l); reg_linear(m, nm, L.attn_norm, dim, base + 0, 1);
             snprintf(nm, sizeof nm, "layers.%d.attention.wq.weight", l); reg_tiled(m, nm, &L.wqkv, m->q_dim, dim, 0, 0, base + 1);
             snprintf(nm, sizeof nm, "layers.%d.attention.wk.weight", l); reg_tiled(m, nm, &L.wqkv, m->kv_dim, dim, m->q_dim, 0, base + 2);
@@ -521,21 +543,21 @@ static int model_alloc(lnb_model* m) {
             snprintf(nm, sizeof nm, "layers.%d.attention.wo.weight", l); reg_tiled(m, nm, &L.wo, dim, m->q_dim, 0, 0, base + 4);
         }
         if (m->has_w13(l)) {
-            if (alloc_linear(&L.ffn_norm, dim, wb)) return -1;
-            if (alloc_tiled(L.w13, F, dim, rw13, 2, wb)) return -1;
+            if (alloc_linear(A, &L.ffn_norm, dim, wb)) return -1;
+            if (alloc_tiled(A, L.w13, F, dim, rw13, 2, wb)) return -1;
             snprintf(nm, sizeof nm, "layers.%d.ffn_norm.weight", l); reg_linear(m, nm, L.ffn_norm, dim, base + 5, 1);
             snprintf(nm, sizeof nm, "layers.%d.feed_forward.w1.weight", l); reg_tiled(m, nm, &L.w13, F, dim, 0, 0, base + 6);
             snprintf(nm, sizeof nm, "layers.%d.feed_forward.w3.weight", l); reg_tiled(m, nm, &L.w13, F, dim, 0, 1, base + 8);
         }
         if (m->has_w2(l)) {
-            if (alloc_tiled(L.w2, dim, F, rw2, 1, wb)) return -1;
+            if (alloc_tiled(A, L.w2, dim, F, rw2, 1, wb)) return -1;
             snprintf(nm, sizeof nm, "layers.%d.feed_forward.w2.weight", l); reg_tiled(m, nm, &L.w2, dim, F, 0, 0, base + 7);
         }
     }
     if (m->last()) {
-        if (alloc_linear(&m->norm, dim, wb)) return -1;
+        if (alloc_linear(A, &m->norm, dim, wb)) return -1;
         reg_linear(m, "norm.weight", m->norm, dim, 1, 1);
-        if (alloc_tiled(m->output, a.vocab_size, dim, auto_rw(a.vocab_size, Knob::RW_OUT), 1, wb)) return -1;
+        if (alloc_tiled(A, m->output, a.vocab_size, dim, auto_rw(a.vocab_size, Knob::RW_OUT), 1, wb)) return -1;
         reg_tiled(m, "output.weight", &m->output, a.vocab_size, dim, 0, 0, 2);
     }
     return 0;
@@ -546,19 +568,6 @@ extern "C" int lnb_model_destroy(lnb_model* m) {
     if (!m) return 0;
     hipSetDevice(m->device);
     append_many_free(m);
-    if (m->tok_embd) hipFree(m->tok_embd);
-    if (m->norm) hipFree(m->norm);
-    if (m->output.w) hipFree(m->output.w);
-    for (auto& L : m->layers) {
-        hipFree(L.attn_norm); hipFree(L.ffn_norm); hipFree(L.wqkv.w); hipFree(L.wo.w); hipFree(L.w13.w); hipFree(L.w2.w);
-        hipFree(L.m_wqkv); hipFree(L.m_wo); hipFree(L.m_w13); hipFree(L.m_w2); hipFree(L.p_w13);
-    }
-    hipFree(m->m_output); hipFree(m->p_out);
-    if (m->cis) hipFree(m->cis);
-    if (m->silu) hipFree(m->silu);
-    if (m->exp_tab) hipFree(m->exp_tab);
-    if (m->prob_etab) hipFree(m->prob_etab);
-    if (m->stream) hipStreamDestroy(m->stream);
     delete m;
     return 0;
 }
@@ -577,37 +586,36 @@ static int wpack_matrix_window(lnb_model* m, const TiledDesc& t, unsigned* d_sta
 // lnb_model_finalize: every gate|up matrix in the 56-row layout that has no valid copy yet gets one, if it is packable and the memory is there;
 // a matrix that is refused keeps the raw kernel and says why (lnb_model_wpack_info)
 static int wpack_build(lnb_model* m) {
-    unsigned* d_stats = nullptr;
+    Dev<unsigned> d_stats;
     for (int l = m->layer_begin; l < m->layer_end; l++) {
         LayerW& L = m->layers[l - m->layer_begin];
         if (!m->has_w13(l) || L.p_ok || L.w13.nch != 2 || !lnbk_w13p_supported(L.w13.rw, L.w13.k)) continue;
-        if (!d_stats) HIPCHK(hipMalloc((void**)&d_stats, sizeof(WpackStats)));
+        if (!d_stats) HIPCHK(dev_alloc(d_stats, sizeof(WpackStats)));
         unsigned base = 0;
         const int why = wpack_matrix_window(m, L.w13, d_stats, &base);
-        if (why < 0) { hipFree(d_stats); return -1; }
+        if (why < 0) return -1;
         L.p_status = why;
         if (why != WPACK_OK) continue;
         const size_t n = lnbk_wpack_w13_bytes(L.w13.n_blocks, L.w13.k);
         if (!L.p_w13) {
-            if (hipMalloc(&L.p_w13, n) != hipSuccess) { (void)hipGetLastError(); L.p_w13 = nullptr; L.p_status = WPACK_NOMEM; continue; }     // the model runs raw and reports it
+            if (dev_alloc(L.p_w13, n) != hipSuccess) { (void)hipGetLastError(); L.p_status = WPACK_NOMEM; continue; }     // the model runs raw and reports it
             m->wpack_bytes += (int64_t)n;
         }
         hipError_t e = lnbk_wpack_w13(L.w13.w, L.p_w13, L.w13.k, L.w13.n_blocks, base, m->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-        if (e != hipSuccess) { hipFree(d_stats); return fail("packing the gate|up matrix of layer %d failed: %s", l, hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail("packing the gate|up matrix of layer %d failed: %s", l, hipGetErrorString(e));
         L.p_base = base; L.p_ok = true;
     }
-    hipFree(d_stats);
     return 0;
 }
 // A gate|up matrix was rewritten after its copy was built (t: that matrix; nullptr: all of them).  A captured decode step may hold the copy's address and
 // window, so the copy is rebuilt IN PLACE when the new weights still fit its window; otherwise the layer returns to the raw kernel and the call fails, saying so.
 static int wpack_refresh(lnb_model* m, const TiledDesc* t) {
-    unsigned* d_stats = nullptr; int rc = 0;
+    Dev<unsigned> d_stats; int rc = 0;
     for (int l = m->layer_begin; l < m->layer_end && !rc; l++) {
         LayerW& L = m->layers[l - m->layer_begin];
         if (!L.p_ok || (t && t != &L.w13)) continue;
-        if (!d_stats && hipMalloc((void**)&d_stats, sizeof(WpackStats)) != hipSuccess) { (void)hipGetLastError(); L.p_ok = false; rc = fail("out of memory"); break; }
+        if (!d_stats && dev_alloc(d_stats, sizeof(WpackStats)) != hipSuccess) { (void)hipGetLastError(); L.p_ok = false; rc = fail("out of memory"); break; }
         L.p_ok = false;
         HIPCHK(lnbk_wpack_stats(L.w13.w, tiled_elems(L.w13.n_rows, L.w13.k, L.w13.rw, L.w13.nch), d_stats, m->stream));
         WpackStats s;
@@ -626,7 +634,6 @@ static int wpack_refresh(lnb_model* m, const TiledDesc* t) {
         HIPCHK(hipStreamSynchronize(m->stream));
         L.p_ok = true; L.p_status = WPACK_OK;
     }
-    hipFree(d_stats);
     return rc;
 }
 // ---- the LM head's copy: the same format cut into 128-row two-chain blocks (lnb_wpack.h; lnbk_gemv_headp) ----
@@ -639,16 +646,16 @@ static bool head_pack_applies(const lnb_model* m) {
 static int wpack_head_build(lnb_model* m) {
     if (m->p_out_ok || !head_pack_applies(m)) return 0;
     const TiledDesc& t = m->output;
-    unsigned* d_stats = nullptr; unsigned base = 0;
-    HIPCHK(hipMalloc((void**)&d_stats, sizeof(WpackStats)));
+    Dev<unsigned> d_stats; unsigned base = 0;
+    HIPCHK(dev_alloc(d_stats, sizeof(WpackStats)));
     const int why = wpack_matrix_window(m, t, d_stats, &base);
-    hipFree(d_stats);
+    d_stats.reset();
     if (why < 0) return -1;
     m->p_out_status = why;
     if (why != WPACK_OK) return 0;
     const size_t n = lnbk_wpack_head_bytes(t.n_rows, t.k);
     if (!m->p_out) {
-        if (hipMalloc(&m->p_out, n) != hipSuccess) { (void)hipGetLastError(); m->p_out = nullptr; m->p_out_status = WPACK_NOMEM; return 0; }      // the head runs raw and reports it
+        if (dev_alloc(m->p_out, n) != hipSuccess) { (void)hipGetLastError(); m->p_out_status = WPACK_NOMEM; return 0; }      // the head runs raw and reports it
         m->wpack_head_bytes = (int64_t)n;
     }
     hipError_t e = lnbk_wpack_head(t.w, m->p_out, t.n_rows, t.k, base, m->stream);
@@ -661,15 +668,14 @@ static int wpack_head_build(lnb_model* m) {
 static int wpack_head_refresh(lnb_model* m) {
     if (!m->p_out_ok) return 0;
     m->p_out_ok = false;
-    unsigned* d_stats = nullptr;
-    if (hipMalloc((void**)&d_stats, sizeof(WpackStats)) != hipSuccess) { (void)hipGetLastError(); return fail("out of memory"); }
+    Dev<unsigned> d_stats;
+    if (dev_alloc(d_stats, sizeof(WpackStats)) != hipSuccess) { (void)hipGetLastError(); return fail("out of memory"); }
     const TiledDesc& t = m->output;
     WpackStats s;
-    hipError_t e = lnbk_wpack_stats(t.w, tiled_elems(t.n_rows, t.k, t.rw, t.nch), d_stats, m->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&s, d_stats, sizeof s, hipMemcpyDeviceToHost, m->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    hipFree(d_stats);
-    HIPCHK(e);
+    HIPCHK(lnbk_wpack_stats(t.w, tiled_elems(t.n_rows, t.k, t.rw, t.nch), d_stats, m->stream));
+    HIPCHK(hipMemcpyAsync(&s, d_stats, sizeof s, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    d_stats.reset();
     unsigned base = 0;
     const int why = wpack_window(&s, &base);
     const bool fits = why == WPACK_OK && (s.max_e2 == 0 || (s.min_e2 > m->p_out_base && s.max_e2 <= m->p_out_base + 15));
@@ -716,13 +722,12 @@ extern "C" int lnb_model_set_tensor(lnb_model* m, const char* name, const uint16
         return fail("tensor \"%s\": shape mismatch, expected [%d%s%d]", name, r.rank == 1 ? r.cols : r.rows, r.rank == 1 ? "" : " ", r.rank == 1 ? 0 : r.cols);
     size_t n = (size_t)r.rows * r.cols;
     if (!r.tiled) { HIPCHK(hipMemcpy(r.linear, host, n * 2, hipMemcpyHostToDevice)); return 0; }
-    uint16_t* stage = nullptr;
-    HIPCHK(hipMalloc((void**)&stage, n * 2));
+    Dev<uint16_t> stage;
+    HIPCHK(dev_alloc(stage, n * 2));
     HIPCHK(hipMemcpy(stage, host, n * 2, hipMemcpyHostToDevice));
-    hipError_t e = lnbk_tile(stage, r.td->w, r.rows, r.cols, r.row_off, r.chain, r.td->rw, r.td->nch, 0, m->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    hipFree(stage);
-    HIPCHK(e);
+    HIPCHK(lnbk_tile(stage, r.td->w, r.rows, r.cols, r.row_off, r.chain, r.td->rw, r.td->nch, 0, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    stage.reset();
     if (wpack_refresh(m, r.td)) return -1;
     if (r.td == &m->output && wpack_head_refresh(m)) return -1;
     return 0;
@@ -749,13 +754,11 @@ extern "C" int lnb_model_get_tensor(lnb_model* m, const char* name, uint16_t* ho
     size_t n = (size_t)r.rows * r.cols;
     if ((int64_t)n != nelem) return fail("tensor \"%s\": expected %zu elements", name, n);
     if (!r.tiled) { HIPCHK(hipMemcpy(host, r.linear, n * 2, hipMemcpyDeviceToHost)); return 0; }
-    uint16_t* stage = nullptr;
-    HIPCHK(hipMalloc((void**)&stage, n * 2));
-    hipError_t e = lnbk_tile(r.td->w, stage, r.rows, r.cols, r.row_off, r.chain, r.td->rw, r.td->nch, 1, m->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    if (e == hipSuccess) e = hipMemcpy(host, stage, n * 2, hipMemcpyDeviceToHost);
-    hipFree(stage);
-    HIPCHK(e);
+    Dev<uint16_t> stage;
+    HIPCHK(dev_alloc(stage, n * 2));
+    HIPCHK(lnbk_tile(r.td->w, stage, r.rows, r.cols, r.row_off, r.chain, r.td->rw, r.td->nch, 1, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    HIPCHK(hipMemcpy(host, stage, n * 2, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -823,20 +826,19 @@ extern "C" int lnb_model_finalize(lnb_model* m, int rope_rows) {
     HIPCHK(hipSetDevice(m->device));
     m->cis_rows = rope_rows > 0 ? rope_rows : m->a.max_seq_len * 2;           // llamatransformer.go:109
     build_rope_table(m->head_dim, m->cis_rows, m->a.rope_theta, m->a.use_scaled_rope != 0, m->cis_host);
-    if (m->cis) hipFree(m->cis);
-    HIPCHK(hipMalloc((void**)&m->cis, m->cis_host.size() * 4));
+    HIPCHK(dev_alloc(m->cis, m->cis_host.size() * 4));             // (a second call: the old table goes first)
     HIPCHK(hipMemcpy(m->cis, m->cis_host.data(), m->cis_host.size() * 4, hipMemcpyHostToDevice));
     // TABLE_SILU (activations.go:15-25): f32(x / (1 + exp(-x))) in f64 for every bf16 bit pattern
     std::vector<float> silu(1 << 16);
     for (int i = 0; i < (1 << 16); i++) { double x = (double)bf_wide_h((uint16_t)i); silu[i] = (float)(x / (1.0 + std::exp(-x))); }
-    if (!m->silu) HIPCHK(hipMalloc((void**)&m->silu, silu.size() * 4));
+    if (!m->silu) HIPCHK(dev_alloc(m->silu, silu.size() * 4));
     HIPCHK(hipMemcpy(m->silu, silu.data(), silu.size() * 4, hipMemcpyHostToDevice));
     // token probabilities: exp(double(bf16)) with the host C library's exp, the oracle's (orc_softmax_f32) by construction
     std::vector<double> et;
     prob_exp_table(et);
-    if (!m->prob_etab) HIPCHK(hipMalloc((void**)&m->prob_etab, et.size() * 8));
+    if (!m->prob_etab) HIPCHK(dev_alloc(m->prob_etab, et.size() * 8));
     HIPCHK(hipMemcpy(m->prob_etab, et.data(), et.size() * 8, hipMemcpyHostToDevice));
-    if (!m->exp_tab) HIPCHK(hipMalloc((void**)&m->exp_tab, (size_t)(1 << 16) * 8));
+    if (!m->exp_tab) HIPCHK(dev_alloc(m->exp_tab, (size_t)(1 << 16) * 8));
     HIPCHK(lnbk_exp_table(m->exp_tab, bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim))), m->stream));   // (attn_mfma_kernel)
     HIPCHK(hipStreamSynchronize(m->stream));
     if (knob(Knob::W13_PACKED) && wpack_build(m)) return -1;
@@ -906,33 +908,31 @@ static int ctx_alloc(lnb_ctx* c) {
     // once (one per generation); with a blocking stream, one thread's graph capture made any other thread's null-stream call
     // (hipMemcpy, hipMemset) fail with "would make the legacy stream depend on a capturing blocking stream".  Everything a context
     // does is therefore ordered on ITS stream: asynchronous copies and memsets + a stream synchronise, never the null stream.
-    HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&c->ev0)); HIPCHK(hipEventCreate(&c->ev1));
-    HIPCHK(hipHostMalloc((void**)&c->h_io, ((size_t)c->seq_len + 2) * 4, hipHostMallocDefault));
+    HIPCHK(stream_create(c->stream, hipStreamNonBlocking));
+    HIPCHK(event_create(c->ev0)); HIPCHK(event_create(c->ev1));
+    HIPCHK(pinned_alloc(c->h_io, ((size_t)c->seq_len + 2) * 4, hipHostMallocDefault));
     const size_t kvn = (size_t)c->seq_len * m->kv_dim;
+    c->ck.resize(m->layers.size()); c->cv.resize(m->layers.size());
     for (size_t l = 0; l < m->layers.size(); l++) {
-        uint16_t *k = nullptr, *v = nullptr;
-        if (m->has_attn(m->layer_begin + (int)l)) {                         // a stage that holds only FFN parts of a block keeps no cache for it
-            HIPCHK(hipMalloc((void**)&k, kvn * 2)); c->ck.push_back(k); c->cv.push_back(nullptr);
-            HIPCHK(hipMalloc((void**)&v, kvn * 2)); c->cv.back() = v;
-            HIPCHK(hipMemsetAsync(k, 0, kvn * 2, c->stream)); HIPCHK(hipMemsetAsync(v, 0, kvn * 2, c->stream));     // ml.Zeros, inferencecontext.go:32-42
-        } else { c->ck.push_back(nullptr); c->cv.push_back(nullptr); }
+        if (!m->has_attn(m->layer_begin + (int)l)) continue;               // a stage that holds only FFN parts of a block keeps no cache for it
+        HIPCHK(dev_alloc(c->ck[l], kvn * 2)); HIPCHK(dev_alloc(c->cv[l], kvn * 2));
+        HIPCHK(hipMemsetAsync(c->ck[l], 0, kvn * 2, c->stream)); HIPCHK(hipMemsetAsync(c->cv[l], 0, kvn * 2, c->stream));     // ml.Zeros, inferencecontext.go:32-42
     }
-    HIPCHK(hipMalloc((void**)&c->st, sizeof(StepState))); HIPCHK(hipMemsetAsync(c->st, 0, sizeof(StepState), c->stream));
-    HIPCHK(hipMalloc((void**)&c->dtok, (size_t)c->seq_len * 4));
-    HIPCHK(hipMalloc((void**)&c->dnext, 16)); HIPCHK(hipMalloc((void**)&c->derr, 16)); HIPCHK(hipMemsetAsync(c->derr, 0, 16, c->stream));
-    c->dout_cap = c->seq_len; HIPCHK(hipMalloc((void**)&c->dout, (size_t)c->dout_cap * 4));
+    HIPCHK(dev_alloc(c->st, sizeof(StepState))); HIPCHK(hipMemsetAsync(c->st, 0, sizeof(StepState), c->stream));
+    HIPCHK(dev_alloc(c->dtok, (size_t)c->seq_len * 4));
+    HIPCHK(dev_alloc(c->dnext, 16)); HIPCHK(dev_alloc(c->derr, 16)); HIPCHK(hipMemsetAsync(c->derr, 0, 16, c->stream));
+    c->dout_cap = c->seq_len; HIPCHK(dev_alloc(c->dout, (size_t)c->dout_cap * 4));
     const size_t S = c->max_rows;                            // rows per call (lnb_ctx_create: seq_len)
-    HIPCHK(hipMalloc((void**)&c->x, S * m->a.dim * 2)); HIPCHK(hipMalloc((void**)&c->h, S * m->a.dim * 2));
-    HIPCHK(hipMalloc((void**)&c->xn, S * m->a.dim * 2));
-    HIPCHK(hipMalloc((void**)&c->q, S * m->q_dim * 2)); HIPCHK(hipMalloc((void**)&c->att, S * m->q_dim * 2));
-    HIPCHK(hipMalloc((void**)&c->ffn, S * m->ffn_hidden * 2));
-    if (m->last()) { HIPCHK(hipMalloc((void**)&c->logits, (size_t)m->a.vocab_size * 2)); c->logits_rows = 1; }
+    HIPCHK(dev_alloc(c->x, S * m->a.dim * 2)); HIPCHK(dev_alloc(c->h, S * m->a.dim * 2));
+    HIPCHK(dev_alloc(c->xn, S * m->a.dim * 2));
+    HIPCHK(dev_alloc(c->q, S * m->q_dim * 2)); HIPCHK(dev_alloc(c->att, S * m->q_dim * 2));
+    HIPCHK(dev_alloc(c->ffn, S * m->ffn_hidden * 2));
+    if (m->last()) { HIPCHK(dev_alloc(c->logits, (size_t)m->a.vocab_size * 2)); c->logits_rows = 1; }
     const size_t SL = c->seq_len;
-    HIPCHK(hipMalloc((void**)&c->e_buf, (size_t)m->a.n_heads * SL * 8));
-    HIPCHK(hipMalloc((void**)&c->z_part, (size_t)m->a.n_heads * ((SL + 63) / 64 + 8) * 8));     // (two-launch form: one partial per 256 positions; attn_one_kernel: one per 64)
-    HIPCHK(hipMalloc((void**)&c->zseq_count, 16)); HIPCHK(hipMemsetAsync(c->zseq_count, 0, 16, c->stream));      // [0] serial-sum walks, [1] norm fallbacks, [2] token-probability walks, [3] sticky: a cached row holds an inf or a NaN
-    HIPCHK(hipMalloc((void**)&c->attn_cnt, ((size_t)m->a.n_heads + 4) * 4)); HIPCHK(hipMemsetAsync(c->attn_cnt, 0, ((size_t)m->a.n_heads + 4) * 4, c->stream));
+    HIPCHK(dev_alloc(c->e_buf, (size_t)m->a.n_heads * SL * 8));
+    HIPCHK(dev_alloc(c->z_part, (size_t)m->a.n_heads * ((SL + 63) / 64 + 8) * 8));     // (two-launch form: one partial per 256 positions; attn_one_kernel: one per 64)
+    HIPCHK(dev_alloc(c->zseq_count, 16)); HIPCHK(hipMemsetAsync(c->zseq_count, 0, 16, c->stream));      // [0] serial-sum walks, [1] norm fallbacks, [2] token-probability walks, [3] sticky: a cached row holds an inf or a NaN
+    HIPCHK(dev_alloc(c->attn_cnt, ((size_t)m->a.n_heads + 4) * 4)); HIPCHK(hipMemsetAsync(c->attn_cnt, 0, ((size_t)m->a.n_heads + 4) * 4, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     // crossover measured on MI355X (tools/att_timing.py): the one-workgroup-per-head kernel wins below a few hundred positions
     c->attn_long_T = knob(Knob::ATTN_LONG_T);
@@ -941,21 +941,6 @@ static int ctx_alloc(lnb_ctx* c) {
     return 0;
 }
 
-static void tp_free(lnb_ctx* c) {
-    hipFree(c->tp_out); hipFree(c->tp_ids); hipFree(c->tp_logit); hipFree(c->tp_prob); hipFree(c->tp_logz);
-    hipFree(c->tp_zpart); hipFree(c->tp_kpart); hipFree(c->tp_cnt);
-    c->tp_out = nullptr; c->tp_ids = nullptr; c->tp_logit = nullptr; c->tp_prob = nullptr; c->tp_logz = nullptr;
-    c->tp_zpart = nullptr; c->tp_kpart = nullptr; c->tp_cnt = nullptr;
-}
-static void spec_free(lnb_ctx* c) {
-    for (auto& b : c->sp_b) { if (b) lnb_batch_destroy(b); b = nullptr; }
-    hipFree(c->sp_corpus); hipFree(c->sp_text); hipFree(c->sp_st); hipFree(c->sp_tok); hipFree(c->sp_g); hipFree(c->sp_best); hipFree(c->sp_cnt);
-    hipFree(c->sp_e_buf); hipFree(c->sp_z_part); c->sp_e_buf = nullptr; c->sp_z_part = nullptr;
-    if (c->sp_word) hipHostFree(c->sp_word);
-    if (c->sp_ev) hipEventDestroy(c->sp_ev);
-    c->sp_corpus = nullptr; c->sp_text = nullptr; c->sp_st = nullptr; c->sp_tok = nullptr; c->sp_g = nullptr; c->sp_best = nullptr; c->sp_cnt = nullptr;
-    c->sp_word = nullptr; c->sp_word_dev = nullptr; c->sp_ev = nullptr; c->sp_text_cap = 0; c->sp_n_corpus = 0;
-}
 extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
     if (!c) return 0;
     // a batch bakes its members' device pointers (state words, token words, caches) into its tables and captured graphs: freeing a member
@@ -963,20 +948,7 @@ extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
     if (c->batch_users > 0) return fail("context is a member of %d live batch(es): lnb_batch_destroy them first", c->batch_users);
     hipSetDevice(c->m->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    drop_graphs(c);
-    c->link.destroy();
-    if (c->ev_h2d) hipEventDestroy(c->ev_h2d);
-    hipFree(c->e_buf); hipFree(c->z_part); hipFree(c->zseq_count); hipFree(c->attn_cnt); if (c->score_idx) hipFree(c->score_idx);
-    tp_free(c); if (c->sc_buf) hipFree(c->sc_buf); if (c->fork_tab) hipFree(c->fork_tab);
-    spec_free(c);
-    for (auto p : c->ck) if (p) hipFree(p);
-    for (auto p : c->cv) if (p) hipFree(p);
-    hipFree(c->st); hipFree(c->dtok); hipFree(c->dnext); hipFree(c->derr); hipFree(c->dout); hipFree(c->d_smp);
-    if (c->h_io) hipHostFree(c->h_io);
-    hipFree(c->x); hipFree(c->h); hipFree(c->xn); hipFree(c->q); hipFree(c->att); hipFree(c->ffn); if (c->logits) hipFree(c->logits);
-    if (c->ev0) hipEventDestroy(c->ev0);
-    if (c->ev1) hipEventDestroy(c->ev1);
-    if (c->stream) hipStreamDestroy(c->stream);
+    for (lnb_batch* b : c->sp_b) if (b) lnb_batch_destroy(b);      // the verify batches: their tables hold this context's pointers
     delete c;
     return 0;
 }
@@ -1013,7 +985,7 @@ extern "C" int lnb_ctx_read_kv(lnb_ctx* c, int layer, int which, uint16_t* host)
 // A KV row depends on the tokens up to it and on nothing a context owns, so the rows [0, n_pos) of one context ARE the rows any
 // other context of the same model would compute for that text: sharing them is a copy.  Nothing but cache rows moves -- every entry point
 // re-establishes the device position itself -- and no captured graph bakes in cache CONTENTS, so none is dropped.
-static int cached_layers(const lnb_ctx* c) { int n = 0; for (auto p : c->ck) n += p != nullptr; return n; }
+static int cached_layers(const lnb_ctx* c) { int n = 0; for (const auto& p : c->ck) n += p.get() != nullptr; return n; }
 extern "C" int lnb_ctx_fork(lnb_ctx* src, int n_pos, lnb_ctx* const* dsts, int n_dst) {
     if (!src || !dsts) return fail("null argument");
     if (n_dst < 1 || n_dst > LNB_MAX_FORK) return fail("n_dst %d is outside 1..%d", n_dst, LNB_MAX_FORK);
@@ -1036,11 +1008,9 @@ extern "C" int lnb_ctx_fork(lnb_ctx* src, int n_pos, lnb_ctx* const* dsts, int n
     HIPCHK(hipSetDevice(m->device));
     const bool engine = knob(Knob::FORK_COPY) != 0;
     const size_t ptr_bytes = (size_t)n_arrays * (size_t)(1 + n_dst) * sizeof(void*), tab_bytes = ptr_bytes + (size_t)n_dst * sizeof(int);
-    if (!engine && src->fork_tab_bytes < tab_bytes) {              // before any stream is touched: a failure here leaves everything as it was
-        void* t = nullptr;
-        if (hipMalloc(&t, tab_bytes) != hipSuccess) { (void)hipGetLastError(); return fail("no device memory for the fork table (%zu bytes)", tab_bytes); }
-        if (src->fork_tab) { hipStreamSynchronize(src->stream); (void)hipFree(src->fork_tab); }      // (the old table: nothing of a finished call reads it)
-        src->fork_tab = t; src->fork_tab_bytes = tab_bytes;
+    if (!engine && !src->fork_tab.fits(tab_bytes)) {               // before any copy is enqueued: a failure here leaves the caches as they were
+        if (src->fork_tab) hipStreamSynchronize(src->stream);      // (the old table: nothing of a finished call reads it)
+        if (dev_reserve(src->fork_tab, tab_bytes) != hipSuccess) { (void)hipGetLastError(); return fail("no device memory for the fork table (%zu bytes)", tab_bytes); }
     }
     HIPCHK(hipStreamSynchronize(src->stream));
     for (int d = 0; d < n_dst; d++) HIPCHK(hipStreamSynchronize(dsts[d]->stream));
@@ -1076,7 +1046,7 @@ extern "C" int lnb_ctx_fork(lnb_ctx* src, int n_pos, lnb_ctx* const* dsts, int n
     const hipError_t up = hipMemcpyAsync(src->fork_tab, host.data(), tab_bytes, hipMemcpyHostToDevice, src->stream);
     if (up != hipSuccess) { hipStreamSynchronize(src->stream); return fail("uploading the fork table failed: %s", hipGetErrorString(up)); }
     KvForkTab tab;
-    tab.ptrs = (const void* const*)src->fork_tab; tab.cap_dst = (const int*)((const char*)src->fork_tab + ptr_bytes);
+    tab.ptrs = (const void* const*)src->fork_tab.get(); tab.cap_dst = (const int*)(src->fork_tab.get() + ptr_bytes);
     tab.n_arrays = n_arrays; tab.n_dst = n_dst; tab.kv_dim = m->kv_dim; tab.n_pos = n_pos; tab.cap_src = src->seq_len;
     const hipError_t launched = lnbk_kv_fork(&tab, knob(Knob::FORK_NT), knob(Knob::FORK_SPLIT), src->stream);
     for (int d = 0; d < n_dst; d++) (void)lnbk_nonfinite_or(dsts[d]->zseq_count + 3, src->zseq_count + 3, src->stream);      // the word travels with the rows
@@ -1184,7 +1154,7 @@ extern "C" int lnb_ctx_set_mode(lnb_ctx* c, int mode) {
     // stage x, its flash attention two static V tiles -- and its one-token attention is the exact kernels' own)
     HIPCHK(hipSetDevice(c->m->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    drop_graphs(c);
+    c->graphs.drop_all();
     c->mode = mode;
     return 0;
 }
@@ -1201,7 +1171,7 @@ extern "C" int lnb_ctx_set_schedule(lnb_ctx* c, int sched) {
     if (sched == c->sched) return 0;
     HIPCHK(hipSetDevice(c->m->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    drop_graphs(c);
+    c->graphs.drop_all();
     c->sched = sched;
     return 0;
 }
@@ -1215,7 +1185,7 @@ extern "C" int lnb_ctx_set_attention(lnb_ctx* c, int long_threshold, int force_z
     if (!c) return fail("null argument");
     HIPCHK(hipSetDevice(c->m->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    drop_graphs(c);
+    c->graphs.drop_all();
     if (long_threshold >= 0) c->attn_long_T = long_threshold;
     c->force_zseq = force_zseq & 15;                         // bit 0: serial denominator; bit 1: two-launch long-context form; bit 2: one launch, every poll times out (tests); bit 3: one launch
     return 0;
@@ -1422,19 +1392,17 @@ static int check_call(lnb_ctx* c, int seq, int start_pos, bool causal = false) {
     for (int l = c->m->layer_begin; l < c->m->layer_end && !stage_has_attn; l++) stage_has_attn = c->m->has_attn(l);
     // a one-token call on a context that still holds a LARGE scratch from its prompt (1.07 GB for 4096 rows of the 8B shape) gives it back: the decode steps never read it,
     // and a host that prefills many contexts would otherwise keep a gigabyte per context for their whole life.  Up to LNB_ATTN_SIDX_KEEP_MB (default 256) it stays for the next prompt.
-    if (seq == 1 && c->score_idx && c->score_idx_bytes > ((size_t)knob(Knob::ATTN_SIDX_KEEP_MB) << 20)) {
+    if (seq == 1 && c->score_idx && c->score_idx.capacity() > ((size_t)knob(Knob::ATTN_SIDX_KEEP_MB) << 20)) {
         HIPCHK(hipStreamSynchronize(c->stream));
-        hipFree(c->score_idx); c->score_idx = nullptr; c->score_idx_bytes = 0;
+        c->score_idx.reset();
     }
     if (mfma_attn && stage_has_attn && c->mode != LNB_MODE_FAST) {
         const int cap_mb = knob(Knob::ATTN_SIDX_MB);                 // (read per call: a test switches it inside one process)
         const size_t jt = (size_t)(T + 15) / 16, need = (size_t)c->m->a.n_heads * (size_t)((seq + 15) / 16) * jt * 512;
         if (cap_mb > 0 && need <= ((size_t)cap_mb << 20)) {
-            if (need > c->score_idx_bytes) {
+            if (!c->score_idx.fits(need)) {
                 HIPCHK(hipStreamSynchronize(c->stream));
-                if (c->score_idx) { hipFree(c->score_idx); c->score_idx = nullptr; c->score_idx_bytes = 0; }
-                if (hipMalloc((void**)&c->score_idx, need) == hipSuccess) c->score_idx_bytes = need;
-                else { (void)hipGetLastError(); c->score_idx = nullptr; }             // (no room: the two-pass kernel needs none)
+                if (dev_reserve(c->score_idx, need) != hipSuccess) (void)hipGetLastError();      // (no room: the two-pass kernel needs none)
             }
             if (c->score_idx) c->sidx_jt = (int)jt;
         }
@@ -1472,7 +1440,7 @@ extern "C" int lnb_forward_stage_begin(lnb_ctx* c, const int32_t* tokens, int se
     }
     if (enqueue_layers(c, seq, false)) return -1;
     if (want_argmax) {
-        if (c->logits_rows < 1) { HIPCHK(hipMalloc((void**)&c->logits, (size_t)V * 2)); c->logits_rows = 1; }
+        if (c->logits_rows < 1) { HIPCHK(dev_alloc(c->logits, (size_t)V * 2)); c->logits_rows = 1; }
         if (enqueue_head(c, seq - 1, 1)) return -1;
         HIPCHK(lnbk_argmax(c->logits, V, c->dnext, c->st, c->dout, c->dout_cap, 0, st));        // inference.go:207-211
         HIPCHK(hipMemcpyAsync(c->h_io, c->dnext, 4, hipMemcpyDeviceToHost, st));
@@ -1536,9 +1504,9 @@ static int forward_stage_impl(lnb_ctx* c, const int32_t* tokens, int seq, int st
         if (rows > c->logits_rows) {
             HIPCHK(hipStreamSynchronize(st));
             // the captured decode graph has the old buffer baked into its head GEMV / argmax nodes: drop it with the buffer
-            drop_graphs(c);
-            hipFree(c->logits); c->logits = nullptr; c->logits_rows = 0;
-            HIPCHK(hipMalloc((void**)&c->logits, (size_t)rows * V * 2)); c->logits_rows = rows;
+            c->graphs.drop_all();
+            c->logits_rows = 0;
+            HIPCHK(dev_alloc(c->logits, (size_t)rows * V * 2)); c->logits_rows = rows;
         }
         if (enqueue_head(c, rows == seq ? 0 : seq - 1, rows)) return -1;
         HIPCHK(lnbk_argmax(c->logits + (size_t)(rows - 1) * V, V, c->dnext, c->st, c->dout, c->dout_cap, 0, st));   // inference.go:207-211
@@ -1554,12 +1522,11 @@ static int forward_stage_impl(lnb_ctx* c, const int32_t* tokens, int seq, int st
             const size_t R = (size_t)rows;
             const size_t o_z = align256(sizeof(TokProbOut)), o_cnt = o_z + align256(R * LNB_TOKPROB_MAX_G * 8), o_tg = o_cnt + align256(R * 4), o_tl = o_tg + align256(R * 4),
                          o_tp = o_tl + align256(R * 4), o_lz = o_tp + align256(R * 4), need = o_lz + align256(R * 8);
-            if (need > c->sc_bytes) {
+            if (!c->sc_buf.fits(need)) {
                 HIPCHK(hipStreamSynchronize(st));
-                if (c->sc_buf) { hipFree(c->sc_buf); c->sc_buf = nullptr; c->sc_bytes = 0; }
-                HIPCHK(hipMalloc(&c->sc_buf, need)); c->sc_bytes = need;
+                HIPCHK(dev_reserve(c->sc_buf, need));
             }
-            char* b = (char*)c->sc_buf;
+            char* b = c->sc_buf;
             so.log_z = (double*)(b + o_lz); so.walks = c->zseq_count + 2;
             HIPCHK(hipMemcpyAsync(b, &so, sizeof so, hipMemcpyHostToDevice, st));
             HIPCHK(hipMemsetAsync(b + o_cnt, 0, R * 4, st));
@@ -1599,7 +1566,7 @@ extern "C" int lnb_forward(lnb_ctx* c, const int32_t* tokens, int seq, int start
 // start_pos + i (include/lnb.h).  Always one multi-row call: 16 or more rows on the matrix-core kernel, fewer (or head_dim 32) on the row-per-workgroup
 // kernel while the context fits its LDS, and beyond that -- or beyond lnb_ctx_set_rows_attention's threshold -- on the multi-row long-context pair
 // (attn_rows_*_kernel: K and V read once for all rows).  Only when that pair's scratch cannot be allocated do the rows run as the one-token steps they are defined by.
-static int attn_long_scratch(int n, int H, int maxT, double** e_buf, double** z_part, const char* whose, bool quiet = false);
+static int attn_long_scratch(int n, int H, int maxT, Dev<double>& e_buf, Dev<double>& z_part, const char* whose, bool quiet = false);
 static bool rows_rpw_invalid() { const int v = knob(Knob::ATTN_ROWS_RPW); return v != 1 && v != 2 && v != 4; }     // (attn_rows_pv_kernel's instantiations)
 static int forward_append_impl(lnb_ctx* c, const char* name, const int32_t* tokens, int seq, int start_pos, float* logits_out, int32_t* argmax_last_out, const ScoreReq* sc) {
     if (!tokens) return fail("%s: null argument (tokens)", name);
@@ -1620,7 +1587,7 @@ static int forward_append_impl(lnb_ctx* c, const char* name, const int32_t* toke
     c->last_append_form = 0;
     bool rows = seq > 1 && !mfma_attn && T > std::min(c->rows_T, c->attn_short_cap) && !c->rows_no_scratch;
     if (rows && rows_rpw_invalid()) return fail("%s: LNB_ATTN_ROWS_RPW=%d is not a form of the multi-row long-context attention (1, 2 or 4)", name, knob(Knob::ATTN_ROWS_RPW));
-    if (rows && attn_long_scratch(LNB_MAX_DRAFT + 1, m->a.n_heads, c->seq_len, &c->sp_e_buf, &c->sp_z_part, "a multi-row append", true)) { c->rows_no_scratch = true; rows = false; }
+    if (rows && attn_long_scratch(LNB_MAX_DRAFT + 1, m->a.n_heads, c->seq_len, c->sp_e_buf, c->sp_z_part, "a multi-row append", true)) { c->rows_no_scratch = true; rows = false; }
     if (seq == 1 || (!rows && !mfma_attn && T > c->attn_short_cap)) {
         for (int i = 0; i < seq; i++) {
             ScoreReq s1{}; if (sc) s1 = ScoreReq{sc->targets + i, sc->tlogit + i, sc->tprob + i, sc->log_z + i};
@@ -1661,7 +1628,7 @@ static int enqueue_decode_step(lnb_ctx* c, bool sample = false) {
     if (enqueue_layers(c, 1, false)) return -1;
     if (enqueue_head(c, 0, 1)) return -1;
     if (c->top_k > 0 && !skip) {                             // the record of the token the argmax below appends (it reads the slot before the argmax advances it)
-        TokProbParams p = tp_params(m, c->logits, 1, c->top_k, c->tp_zpart, c->tp_kpart, c->tp_cnt, c->tp_out, 0);
+        TokProbParams p = tp_params(m, c->logits, 1, c->top_k, c->tp.zpart, c->tp.kpart, c->tp.cnt, c->tp.out, 0);
         HIPCHK(lnbk_token_probs(&p, c->stream));
     }
     if (sample) HIPCHK(lnbk_sample(c->logits, m->a.vocab_size, 1, m->prob_etab, c->d_smp, c->dtok, c->st, c->dout, c->dout_cap, 1, nullptr, nullptr, nullptr, c->stream));
@@ -1690,18 +1657,18 @@ extern "C" int lnb_ctx_set_token_probs(lnb_ctx* c, int top_k) {
     if (c->batch_users > 0) return fail("context is a member of %d live batch(es): its top-k is fixed until they are destroyed", c->batch_users);
     HIPCHK(hipSetDevice(c->m->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    drop_graphs(c);
-    tp_free(c);
+    c->graphs.drop_all();
+    c->tp = {};
     c->top_k = 0; c->tp_last_k = 0; c->tp_last_n = 0;
     if (top_k == 0) return 0;
     const size_t n = (size_t)c->dout_cap * top_k, G = LNB_TOKPROB_MAX_G;
-    HIPCHK(hipMalloc((void**)&c->tp_ids, n * 4)); HIPCHK(hipMalloc((void**)&c->tp_logit, n * 4)); HIPCHK(hipMalloc((void**)&c->tp_prob, n * 4));
-    HIPCHK(hipMalloc((void**)&c->tp_logz, (size_t)c->dout_cap * 8));
-    HIPCHK(hipMalloc((void**)&c->tp_zpart, G * 8)); HIPCHK(hipMalloc((void**)&c->tp_kpart, G * LNB_TOKPROB_MAX_K * 8));
-    HIPCHK(hipMalloc((void**)&c->tp_cnt, 16)); HIPCHK(hipMemsetAsync(c->tp_cnt, 0, 16, c->stream));
-    TokProbOut o{}; o.st = c->st; o.ids = c->tp_ids; o.logit = c->tp_logit; o.prob = c->tp_prob; o.log_z = c->tp_logz; o.walks = c->zseq_count + 2; o.cap = c->dout_cap;
-    HIPCHK(hipMalloc((void**)&c->tp_out, sizeof o));
-    HIPCHK(hipMemcpyAsync(c->tp_out, &o, sizeof o, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(dev_alloc(c->tp.ids, n * 4)); HIPCHK(dev_alloc(c->tp.logit, n * 4)); HIPCHK(dev_alloc(c->tp.prob, n * 4));
+    HIPCHK(dev_alloc(c->tp.logz, (size_t)c->dout_cap * 8));
+    HIPCHK(dev_alloc(c->tp.zpart, G * 8)); HIPCHK(dev_alloc(c->tp.kpart, G * LNB_TOKPROB_MAX_K * 8));
+    HIPCHK(dev_alloc(c->tp.cnt, 16)); HIPCHK(hipMemsetAsync(c->tp.cnt, 0, 16, c->stream));
+    TokProbOut o{}; o.st = c->st; o.ids = c->tp.ids; o.logit = c->tp.logit; o.prob = c->tp.prob; o.log_z = c->tp.logz; o.walks = c->zseq_count + 2; o.cap = c->dout_cap;
+    HIPCHK(dev_alloc(c->tp.out, sizeof o));
+    HIPCHK(hipMemcpyAsync(c->tp.out, &o, sizeof o, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));                 // (o is stack memory)
     c->top_k = top_k;
     return 0;
@@ -1714,10 +1681,10 @@ extern "C" int lnb_ctx_read_token_probs(lnb_ctx* c, int first, int n, int32_t* i
     if (n == 0) return 0;
     const size_t k = c->tp_last_k, off = (size_t)first * k, cnt = (size_t)n * k;
     HIPCHK(hipSetDevice(c->m->device));
-    HIPCHK(hipMemcpyAsync(ids, c->tp_ids + off, cnt * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(logits, c->tp_logit + off, cnt * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(probs, c->tp_prob + off, cnt * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(log_z, c->tp_logz + first, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(ids, c->tp.ids + off, cnt * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(logits, c->tp.logit + off, cnt * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(probs, c->tp.prob + off, cnt * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(log_z, c->tp.logz + first, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1732,25 +1699,27 @@ extern "C" int lnb_ctx_token_prob_walks(lnb_ctx* c, int* out) {
 }
 // What `body` enqueues on `st`, captured into the graph slot -- once: a slot that holds a graph is left alone and the body does not run.
 // A body that fails has set the message; the capture is ended and its graph dropped.
-template <class Body> static int capture_once(hipGraphExec_t* slot, hipStream_t st, Body body) {
-    if (*slot) return 0;
-    hipGraph_t g = nullptr;
+template <class Body> static int capture_once(GraphExec& slot, hipStream_t st, Body body) {
+    if (slot) return 0;
+    Owned<hipGraph_t, hipGraphDestroy> g;                    // the transient graph: gone on every way out
     HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     int rc = body();
-    hipError_t e = hipStreamEndCapture(st, &g);
-    if (rc) { if (g) hipGraphDestroy(g); return -1; }
+    hipError_t e = g.fill([&](hipGraph_t* q) { return hipStreamEndCapture(st, q); });
+    if (rc) return -1;
     HIPCHK(e);
-    HIPCHK(hipGraphInstantiate(slot, g, nullptr, nullptr, 0));
-    HIPCHK(hipGraphDestroy(g));
+    HIPCHK(slot.fill([&](hipGraphExec_t* q) { return hipGraphInstantiate(q, g, nullptr, nullptr, 0); }));
     return 0;
 }
 // one captured graph per attention form: the step at context T replays the long-context one when T exceeds the crossover.  Captures the
 // forms that steps at positions start_pos .. start_pos + n_steps - 1 need and the context does not hold yet.
 static int capture_decode_graphs(lnb_ctx* c, int start_pos, int n_steps, bool sample = false) {
-    auto capture = [&](hipGraphExec_t* slot, bool longctx) { return capture_once(slot, c->stream, [&] { c->attn_long = longctx; return enqueue_decode_step(c, sample); }); };
+    const GraphLaunch launch = sample ? GL_SAMPLE : GL_GREEDY;
+    auto capture = [&](bool longctx) {
+        return capture_once(c->graphs.slot(launch, longctx ? GF_LONG : GF_SHORT), c->stream, [&] { c->attn_long = longctx; return enqueue_decode_step(c, sample); });
+    };
     const bool any_short = !want_long_attention(c, 1, start_pos), any_long = want_long_attention(c, 1, start_pos + n_steps - 1);
-    if (any_short && capture(sample ? &c->sgraph : &c->graph, false)) return -1;
-    if (any_long && capture(sample ? &c->sgraph_long : &c->graph_long, true)) return -1;
+    if (any_short && capture(false)) return -1;
+    if (any_long && capture(true)) return -1;
     return 0;
 }
 // what every sampling entry point asks of a sampler (who: "" or "sequence 3: "), before anything else is looked at
@@ -1797,7 +1766,7 @@ extern "C" int lnb_profile_sample(lnb_ctx* c, const lnb_sampler* sampler, int po
     if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
     HIPCHK(hipSetDevice(m->device));
     hipStream_t st = c->stream;
-    if (sampler && !c->d_smp) HIPCHK(hipMalloc((void**)&c->d_smp, sizeof(LnbSampler)));
+    if (sampler && !c->d_smp) HIPCHK(dev_alloc(c->d_smp, sizeof(LnbSampler)));
     if (sampler) HIPCHK(hipMemcpyAsync(c->d_smp, sampler, sizeof(LnbSampler), hipMemcpyHostToDevice, st));
     HIPCHK(ctx_set_state(c, pos, 0, false, false));
     auto launch = [&]() {
@@ -1829,7 +1798,7 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     if (token < 0 || token >= m->a.vocab_size) return fail("token id at index 0 is outside the vocabulary");
     hipStream_t st = c->stream;
     const bool use_graph = knob(Knob::NO_GRAPH) == 0;
-    if (smp && !c->d_smp) HIPCHK(hipMalloc((void**)&c->d_smp, sizeof(LnbSampler)));
+    if (smp && !c->d_smp) HIPCHK(dev_alloc(c->d_smp, sizeof(LnbSampler)));
     if (use_graph && capture_decode_graphs(c, start_pos, n_steps, smp != nullptr)) return -1;
     c->tp_last_k = 0; c->tp_last_n = 0;
     if (smp) HIPCHK(hipMemcpyAsync(c->d_smp, smp, sizeof(LnbSampler), hipMemcpyHostToDevice, st));
@@ -1843,7 +1812,7 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     HIPCHK(hipEventRecord(c->ev0, st));
     for (int i = 0; i < n_steps; i++) {
         const bool longctx = want_long_attention(c, 1, start_pos + i);
-        if (use_graph) HIPCHK(hipGraphLaunch(smp ? (longctx ? c->sgraph_long : c->sgraph) : (longctx ? c->graph_long : c->graph), st));
+        if (use_graph) HIPCHK(hipGraphLaunch(c->graphs.slot(smp ? GL_SAMPLE : GL_GREEDY, longctx ? GF_LONG : GF_SHORT), st));
         else { c->attn_long = longctx; if (enqueue_decode_step(c, smp != nullptr)) return -1; }
     }
     HIPCHK(hipEventRecord(c->ev1, st));
@@ -1865,11 +1834,11 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
 static int gemv_stamps(lnb_ctx* c, int which, double* out, int full) {
     lnb_model* m = c->m; hipStream_t st = c->stream;
     const size_t n = (size_t)4096 * 8 * 4, n2 = (size_t)4096 * 8 * 8;       // + 8 phase stamps per wave behind the four totals (LNB_STAMP in lnb_kernels.hip)
-    long long* dbuf = nullptr;
-    HIPCHK(hipMalloc((void**)&dbuf, (n + n2) * 8));
-    { hipError_t e = hipMemsetAsync(dbuf, 0, (n + n2) * 8, st); if (e != hipSuccess) { hipFree(dbuf); HIPCHK(e); } }
+    Dev<long long> dbuf;
+    HIPCHK(dev_alloc(dbuf, (n + n2) * 8));
+    HIPCHK(hipMemsetAsync(dbuf, 0, (n + n2) * 8, st));
     const int nl = m->layer_end - m->layer_begin;
-    if (nl <= 0 && which != K_HEAD) { hipFree(dbuf); return fail("this stage holds no transformer block: only kernel class %d (norm + output) can be stamped", K_HEAD); }   // (i % nl below)
+    if (nl <= 0 && which != K_HEAD) return fail("this stage holds no transformer block: only kernel class %d (norm + output) can be stamped", K_HEAD);   // (i % nl below)
     // three plain launches of the class on other layers first, back to back with the stamped one: it then runs as a launch inside a decode step does
     // (instruction cache, clocks and memory pipeline warm) instead of as the first launch after an idle gap
     int rc = 0;
@@ -1877,14 +1846,10 @@ static int gemv_stamps(lnb_ctx* c, int which, double* out, int full) {
     g_dbg = dbuf; g_dbg_full = full;
     if (!rc) rc = which == K_HEAD ? enqueue_head(c, 0, 1) : enqueue_layer_kernel(c, m->layer_begin + 7 % nl, 1, which);
     g_dbg = nullptr; g_dbg_full = 0;
-    if (rc) { hipFree(dbuf); return -1; }
+    if (rc) { hipStreamSynchronize(st); return -1; }          // (the launches that were accepted still write the buffer)
     std::vector<long long> h(n + n2);
-    {   // (no early return between here and the free: ADVICE r5)
-        hipError_t e = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = hipMemcpy(h.data(), dbuf, (n + n2) * 8, hipMemcpyDeviceToHost);
-        hipFree(dbuf);
-        HIPCHK(e);
-    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(h.data(), dbuf, (n + n2) * 8, hipMemcpyDeviceToHost));
     for (int w = 0; w < 8; w++) {
         double* o = out + w * 16; for (int k = 0; k < 16; k++) o[k] = 0;
         int cnt = 0;
@@ -1919,6 +1884,16 @@ extern "C" int lnb_profile_kernel_stamps(lnb_ctx* c, int which, int pos, double*
 // spin kernel in front of it holds its stream): delay 0 = plain co-residency, delay ~ "the first row band is complete" = the timeline of a band
 // pipeline, with no dependency stall at all (w2 reads STALE activations -- the results are meaningless, only the time is).  w2_lds_pad pads w2's
 // LDS request (r3's way of forcing exactly one workgroup of each kernel per CU).  Both kernels take the forms of the context's schedule.
+// the second stream of a two-stream measurement with its fork and join events; on every way out the device is idle before they are released
+struct PairStreams {
+    Stream st2; Event ef, ej;
+    int create() {
+        HIPCHK(stream_create(st2, hipStreamNonBlocking));
+        HIPCHK(event_create(ef, hipEventDisableTiming)); HIPCHK(event_create(ej, hipEventDisableTiming));
+        return 0;
+    }
+    ~PairStreams() { hipDeviceSynchronize(); }
+};
 extern "C" int lnb_profile_ffn_pair(lnb_ctx* c, int pos, int iters, int w2_delay_us, int w2_lds_pad, float* avg_ms_out) {
     if (!c || !avg_ms_out) return fail("null argument");
     lnb_model* m = c->m;
@@ -1927,9 +1902,9 @@ extern "C" int lnb_profile_ffn_pair(lnb_ctx* c, int pos, int iters, int w2_delay
     if (check_call(c, 1, pos)) return -1;
     const int nl2 = m->layer_end - m->layer_begin;
     if (nl2 <= 0) return fail("this stage holds no transformer block");
-    hipStream_t st = c->stream, st2 = nullptr; hipEvent_t ef = nullptr, ej = nullptr;
-    HIPCHK(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&ef, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ej, hipEventDisableTiming));
+    PairStreams ps;
+    if (ps.create()) return -1;
+    hipStream_t st = c->stream, st2 = ps.st2; hipEvent_t ef = ps.ef, ej = ps.ej;
     c->attn_long = false;
     HIPCHK(ctx_set_state(c, pos, 0, true));
     auto pair = [&](int i) -> int {
@@ -1950,11 +1925,9 @@ extern "C" int lnb_profile_ffn_pair(lnb_ctx* c, int pos, int iters, int w2_delay
     int rc = 0;
     for (int i = 0; i < 3 && !rc; i++) rc = pair(i);
     if (!rc) { HIPCHK(hipEventRecord(c->ev0, st)); for (int i = 0; i < iters && !rc; i++) rc = pair(i + 3); HIPCHK(hipEventRecord(c->ev1, st)); }
-    hipError_t e = hipDeviceSynchronize();
-    float ms2 = 0; if (!rc && e == hipSuccess) e = hipEventElapsedTime(&ms2, c->ev0, c->ev1);
-    hipEventDestroy(ef); hipEventDestroy(ej); hipStreamDestroy(st2);
     if (rc) return -1;
-    HIPCHK(e);
+    HIPCHK(hipDeviceSynchronize());
+    float ms2 = 0; HIPCHK(hipEventElapsedTime(&ms2, c->ev0, c->ev1));
     *avg_ms_out = ms2 / (float)iters;
     return 0;
 }
@@ -1971,9 +1944,9 @@ extern "C" int lnb_profile_kernel(lnb_ctx* c, int which, int pos, int iters, flo
     if (which == K_HEAD && !m->last()) return fail("this stage does not own output.weight");
     hipStream_t st = c->stream;
     if (which > K_LAYER) {
-        hipStream_t st2 = nullptr; hipEvent_t ef = nullptr, ej = nullptr;
-        HIPCHK(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&ef, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ej, hipEventDisableTiming));
+        PairStreams ps;
+        if (ps.create()) return -1;
+        hipStream_t st2 = ps.st2; hipEvent_t ef = ps.ef, ej = ps.ej;
         c->attn_long = false;
         HIPCHK(ctx_set_state(c, pos, 0, true));
         const int nl2 = m->layer_end - m->layer_begin, pad = knob(Knob::W2_LDS_PAD);
@@ -1988,11 +1961,9 @@ extern "C" int lnb_profile_kernel(lnb_ctx* c, int which, int pos, int iters, flo
         int rc = 0;
         for (int i = 0; i < 3 && !rc; i++) rc = pair(i);
         if (!rc) { HIPCHK(hipEventRecord(c->ev0, st)); for (int i = 0; i < iters && !rc; i++) rc = pair(i + 3); HIPCHK(hipEventRecord(c->ev1, st)); }
-        hipError_t e = hipDeviceSynchronize();
-        float ms2 = 0; if (!rc && e == hipSuccess) e = hipEventElapsedTime(&ms2, c->ev0, c->ev1);
-        hipEventDestroy(ef); hipEventDestroy(ej); hipStreamDestroy(st2);
         if (rc) return -1;
-        HIPCHK(e);
+        HIPCHK(hipDeviceSynchronize());
+        float ms2 = 0; HIPCHK(hipEventElapsedTime(&ms2, c->ev0, c->ev1));
         *avg_ms_out = ms2 / (float)iters;
         return 0;
     }
@@ -2016,16 +1987,15 @@ extern "C" int lnb_profile_kernel(lnb_ctx* c, int which, int pos, int iters, flo
     *avg_ms_out = ms / (float)iters;
     const bool timing = knob(Knob::GEMV_TIMING) != 0;
     if (timing && which == K_ATTN) {
-        long long* dbuf = nullptr;
-        HIPCHK(hipMalloc((void**)&dbuf, 64 * 8)); HIPCHK(hipMemsetAsync(dbuf, 0, 64 * 8, st));
+        Dev<long long> dbuf;
+        HIPCHK(dev_alloc(dbuf, 64 * 8)); HIPCHK(hipMemsetAsync(dbuf, 0, 64 * 8, st));
         g_dbg = dbuf;
         int rc = run(7);
         g_dbg = nullptr;
-        if (rc) { hipFree(dbuf); return -1; }
+        if (rc) return -1;
         HIPCHK(hipStreamSynchronize(st));
         long long h[64] = {0};
         HIPCHK(hipMemcpy(h, dbuf, sizeof h, hipMemcpyDeviceToHost));
-        hipFree(dbuf);
         for (int w = 0; w < 4; w++) {
             fprintf(stderr, "[timing] attention pos %d wave %d phases (s_memtime ticks):", pos, w);
             for (int k = 1; k < 7; k++) fprintf(stderr, " %lld", h[w * 16 + k] - h[w * 16 + k - 1]);
@@ -2055,36 +2025,36 @@ extern "C" int lnb_profile_kernel(lnb_ctx* c, int which, int pos, int iters, flo
 // row, KV append and attention.  Every sequence's tokens and caches are bit-identical to its single-sequence run.
 struct lnb_batch {
     lnb_model* m = nullptr; int n = 0; std::vector<lnb_ctx*> ctxs;
-    hipStream_t stream = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    BatchTab* tab = nullptr; BatchKV* kv = nullptr;
-    uint16_t *x = nullptr, *h = nullptr, *xt = nullptr, *q = nullptr, *att_xt = nullptr, *ffn_xt = nullptr, *logits = nullptr;
-    int* derr = nullptr; int32_t *d_tokens = nullptr, *d_pos = nullptr; int32_t* h_io = nullptr;   // pinned: [0..MAX) tokens, [MAX..2 MAX) positions, [2 MAX] error word (MAX = LNB_BATCH_MAX)
-    hipGraphExec_t graph = nullptr; int lds_T = 0; bool counted = false;       // lds_T: what the one-workgroup kernels' LDS arrays are sized for = min(maxT, their cap)
+    Stream stream; Event ev0, ev1;         // (the stream is declared before everything enqueued on it: released last)
+    Dev<BatchTab> tab; Dev<BatchKV> kv;    // (everything INSIDE the two tables aliases the members' state words, token words, logs and caches)
+    Dev<uint16_t> x, h, xt, q, att_xt, ffn_xt, logits;
+    Dev<int> derr; Dev<int32_t> d_tokens, d_pos; Pinned<int32_t> h_io;   // pinned: [0..MAX) tokens, [MAX..2 MAX) positions, [2 MAX] error word (MAX = LNB_BATCH_MAX)
+    // the captured steps: greedy (a verify batch: the verify pass) / sampling (lnb_batch_decode_sample_until; a verify batch: lnb_decode_speculative_sample_until) /
+    // pipeline stage (lnb_pipeline_tick_batch), each per attention form; the rows form is a verify batch's whose columns run the multi-row long-context pair
+    Graphs graphs;
+    int lds_T = 0; bool counted = false;   // lds_T: what the one-workgroup kernels' LDS arrays are sized for = min(maxT, their cap)
     // attention form (lnb_batch_set_attention).  maxT: the largest member seq_len; must_long: a member is beyond the one-workgroup kernels' reach;
     // attn_long: the form the NEXT enqueue / capture takes (chosen on the host per call: a captured graph fixes the kernel), one graph per form;
     // e_buf [n][H][maxT] / z_part [n][H][ceil(maxT/256)]: allocated when the long form is first needed, never inside a capture (a verify batch
     // borrows its context's: scratch_owned false)
     int maxT = 0; bool must_long = false, attn_long = false, tick_long = false, scratch_owned = true;
     int attn_long_T = 0x7FFFFFFF, force_zseq = 0, last_form = 0;
-    double* e_buf = nullptr; double* z_part = nullptr;
-    hipGraphExec_t graph_long = nullptr, stage_graph_long = nullptr;
-    // the sampling step (lnb_batch_decode_sample_until): graph slots of its own, one per attention form, and the device array of n samplers they point at
-    hipGraphExec_t sgraph = nullptr, sgraph_long = nullptr; LnbSampler* d_smp = nullptr;
-    // a verify batch whose columns run the multi-row long-context pair (lnb_ctx_set_rows_attention, flags bit 1): a captured graph of its own
-    bool attn_rows = false; int rows_zseq = 0; hipGraphExec_t graph_rows = nullptr;
-    // ... and its sampling twin (lnb_decode_speculative_sample_until: a verify batch keeps its sampling passes in sgraph / sgraph_long / sgraph_rows)
-    hipGraphExec_t sgraph_rows = nullptr;
+    Dev<double> e_own, z_own;              // the batch's own scratch (scratch_owned)
+    double* e_buf = nullptr; double* z_part = nullptr;     // what the launches take: e_own / z_own, or (a verify batch) its context's sp_e_buf / sp_z_part
+    Dev<LnbSampler> d_smp;                 // the device array of n samplers the sampling steps point at
+    // a verify batch whose columns run the multi-row long-context pair (lnb_ctx_set_rows_attention, flags bit 1)
+    bool attn_rows = false; int rows_zseq = 0;
     bool rows_form = false;                // the model carries no matrix-core copy: every product runs as ROWS of gemm_stream_kernel on the resident layouts, whatever n
     // pipeline stage (lnb_pipeline_tick_batch): the contiguous token words exchanged between the last and the first stage, the stage step
     // as a captured graph, events towards / from the exchange stream (as lnb_ctx has them for single-sequence ticks)
-    int32_t* ring = nullptr; hipGraphExec_t stage_graph = nullptr;
+    Dev<int32_t> ring;
     PipeLink link;
-    // token probabilities (the members' lnb_ctx_set_token_probs, one top_k for all): one row per sequence into its context's log
-    int top_k = 0; TokProbOut* tp_out = nullptr; double* tp_zpart = nullptr; uint64_t* tp_kpart = nullptr; unsigned* tp_cnt = nullptr;
+    // token probabilities (the members' lnb_ctx_set_token_probs, one top_k for all): one row per sequence into its context's log (the records' members alias the contexts' logs)
+    int top_k = 0; Dev<TokProbOut> tp_out; Dev<double> tp_zpart; Dev<uint64_t> tp_kpart; Dev<unsigned> tp_cnt;
     // speculative verify batch (lnb_decode_speculative_until): every column is ONE context (ctxs[s] = it, the same caches); columns s >= 1 take
-    // their state and token word from col_st + s / col_tok + s instead of the context's own
+    // their state and token word from col_st + s / col_tok + s instead of the context's own (the context's sp_st / sp_tok: it owns them)
     StepState* col_st = nullptr; int32_t* col_tok = nullptr;
-    int* zseq = nullptr;                   // lnb_forward_append_many's pass batch has no member contexts: the serial-sum counter the attention launches get instead of ctxs[0]'s
+    int* zseq = nullptr;                   // lnb_forward_append_many's pass batch has no member contexts: the serial-sum counter the attention launches get instead of ctxs[0]'s (AppendMany::zseq owns it)
 };
 // What every batched step asks of the model stage it runs on (who: the caller, as its message names it).  A whole-model handle is a stage of whole blocks.
 static int batch_shape_check(const lnb_model* m, const char* who) {
@@ -2095,7 +2065,7 @@ static int batch_shape_check(const lnb_model* m, const char* who) {
 }
 static int m16_copy(lnb_model* m, const TiledDesc& t, int rows, uint16_t** out) {
     const size_t bytes = m16_elems(rows, t.k, t.nch) * 2;
-    HIPCHK(hipMalloc((void**)out, bytes));
+    if (arena_alloc(m->m16, out, bytes)) return -1;
     HIPCHK(hipMemsetAsync(*out, 0, bytes, m->stream));
     HIPCHK(lnbk_m16_from_tiled(t.w, *out, rows, t.k, t.rw, t.nch, m->stream));
     m->batch_bytes += (int64_t)bytes;
@@ -2120,8 +2090,9 @@ extern "C" int lnb_model_enable_batch(lnb_model* m) {
         m->output.w16 = m->m_output;
     }
     if (rc || e != hipSuccess) {                             // (out of memory on a model that fills the HBM: the single-sequence paths stay usable)
-        for (auto& L : m->layers) { hipFree(L.m_wqkv); hipFree(L.m_wo); hipFree(L.m_w13); hipFree(L.m_w2); L.m_wqkv = L.m_wo = L.m_w13 = L.m_w2 = nullptr; }
-        hipFree(m->m_output); m->m_output = nullptr; m->batch_bytes = 0;
+        m->m16.reset();
+        for (auto& L : m->layers) L.m_wqkv = L.m_wo = L.m_w13 = L.m_w2 = nullptr;
+        m->m_output = nullptr; m->batch_bytes = 0;
         (void)hipGetLastError();                             // the failed hipMalloc leaves the thread's last-error set: every launcher ends with hipGetLastError()
         if (!rc) return fail("lnb_model_enable_batch: %s", hipGetErrorString(e));
         return -1;
@@ -2134,60 +2105,38 @@ extern "C" int64_t lnb_model_batch_bytes(lnb_model* m) { return m ? m->batch_byt
 // The activation buffers of a batched step, N columns each (N a multiple of 16: the column forms keep B-operand layouts per group of 16),
 // with the logits of a stage that owns the head and the error word.  All zero when allocated: the columns past n are never written by a
 // live batch, whose width is fixed; a caller whose width changes re-zeroes the six (not the logits: every pass writes the rows it reads).
-struct BatchBuf { uint16_t** p; size_t bytes; };
+struct BatchBuf { Dev<uint16_t>* p; size_t bytes; };
 static std::array<BatchBuf, 6> batch_bufs(lnb_batch* b, size_t N) {
     const lnb_model* m = b->m; const size_t dim = m->a.dim;
     return {{{&b->x, N * dim * 2}, {&b->h, N * dim * 2}, {&b->xt, N * dim * 2}, {&b->q, N * m->q_dim * 2}, {&b->att_xt, N * m->q_dim * 2}, {&b->ffn_xt, N * m->ffn_hidden * 2}}};
 }
 static int batch_bufs_zero(lnb_batch* b, size_t N) {
-    for (const BatchBuf& f : batch_bufs(b, N)) HIPCHK(hipMemsetAsync(*f.p, 0, f.bytes, b->stream));
+    for (const BatchBuf& f : batch_bufs(b, N)) HIPCHK(hipMemsetAsync(f.p->get(), 0, f.bytes, b->stream));
     return 0;
 }
 static int batch_bufs_alloc(lnb_batch* b, size_t N) {
-    for (const BatchBuf& f : batch_bufs(b, N)) HIPCHK(hipMalloc((void**)f.p, f.bytes));
+    for (const BatchBuf& f : batch_bufs(b, N)) HIPCHK(dev_alloc(*f.p, f.bytes));
     if (batch_bufs_zero(b, N)) return -1;
     if (b->m->last()) {
         const size_t bytes = N * (size_t)b->m->a.vocab_size * 2;
-        HIPCHK(hipMalloc((void**)&b->logits, bytes)); HIPCHK(hipMemsetAsync(b->logits, 0, bytes, b->stream));
+        HIPCHK(dev_alloc(b->logits, bytes)); HIPCHK(hipMemsetAsync(b->logits, 0, bytes, b->stream));
     }
-    HIPCHK(hipMalloc((void**)&b->derr, 16)); HIPCHK(hipMemsetAsync(b->derr, 0, 16, b->stream));
+    HIPCHK(dev_alloc(b->derr, 16)); HIPCHK(hipMemsetAsync(b->derr, 0, 16, b->stream));
     return 0;
-}
-static void batch_bufs_free(lnb_batch* b) {
-    for (const BatchBuf& f : batch_bufs(b, 0)) hipFree(*f.p);
-    hipFree(b->logits); hipFree(b->derr);
 }
 extern "C" int lnb_batch_destroy(lnb_batch* b) {
     if (!b) return 0;
     hipSetDevice(b->m->device);
     if (b->stream) hipStreamSynchronize(b->stream);
     if (b->counted) for (lnb_ctx* c : b->ctxs) c->batch_users--;
-    if (b->graph) hipGraphExecDestroy(b->graph);
-    if (b->graph_long) hipGraphExecDestroy(b->graph_long);
-    if (b->sgraph) hipGraphExecDestroy(b->sgraph);
-    if (b->sgraph_long) hipGraphExecDestroy(b->sgraph_long);
-    hipFree(b->d_smp);
-    if (b->graph_rows) hipGraphExecDestroy(b->graph_rows);
-    if (b->sgraph_rows) hipGraphExecDestroy(b->sgraph_rows);
-    if (b->stage_graph_long) hipGraphExecDestroy(b->stage_graph_long);
-    if (b->scratch_owned) { hipFree(b->e_buf); hipFree(b->z_part); }
-    batch_bufs_free(b);
-    hipFree(b->tab); hipFree(b->kv); hipFree(b->d_tokens); hipFree(b->d_pos); hipFree(b->ring);
-    hipFree(b->tp_out); hipFree(b->tp_zpart); hipFree(b->tp_kpart); hipFree(b->tp_cnt);
-    if (b->stage_graph) hipGraphExecDestroy(b->stage_graph);
-    b->link.destroy();
-    if (b->h_io) hipHostFree(b->h_io);
-    if (b->ev0) hipEventDestroy(b->ev0);
-    if (b->ev1) hipEventDestroy(b->ev1);
-    if (b->stream) hipStreamDestroy(b->stream);
     delete b;
     return 0;
 }
 static int batch_alloc(lnb_batch* b) {
     lnb_model* m = b->m; const int n = b->n;
-    HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&b->ev0)); HIPCHK(hipEventCreate(&b->ev1));
-    HIPCHK(hipHostMalloc((void**)&b->h_io, (2 * LNB_BATCH_MAX + 8) * 4, hipHostMallocDefault));
+    HIPCHK(stream_create(b->stream, hipStreamNonBlocking));
+    HIPCHK(event_create(b->ev0)); HIPCHK(event_create(b->ev1));
+    HIPCHK(pinned_alloc(b->h_io, (2 * LNB_BATCH_MAX + 8) * 4, hipHostMallocDefault));
     BatchTab t{}; t.n = n;
     std::vector<BatchKV> kv(m->layers.size());
     for (int s = 0; s < LNB_BATCH_MAX; s++) {
@@ -2196,27 +2145,27 @@ static int batch_alloc(lnb_batch* b) {
         if (b->col_st && s >= 1 && s < n) { t.st[s] = b->col_st + s; t.dtok[s] = b->col_tok + s; }
         for (size_t l = 0; l < m->layers.size(); l++) { kv[l].ck[s] = c->ck[l]; kv[l].cv[s] = c->cv[l]; }
     }
-    HIPCHK(hipMalloc((void**)&b->tab, sizeof t)); HIPCHK(hipMemcpyAsync(b->tab, &t, sizeof t, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipMalloc((void**)&b->kv, kv.size() * sizeof(BatchKV)));
+    HIPCHK(dev_alloc(b->tab, sizeof t)); HIPCHK(hipMemcpyAsync(b->tab, &t, sizeof t, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(dev_alloc(b->kv, kv.size() * sizeof(BatchKV)));
     HIPCHK(hipMemcpyAsync(b->kv, kv.data(), kv.size() * sizeof(BatchKV), hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));                 // (the host copies above are stack / vector memory)
     // 1..16 sequences: activations in the B-operand layout [K][16 sequences], the columns past n stay zero for ever; 17..128: plain rows [n][K]
     // (whole column groups of 16: the 17..32-sequence form keeps B-operand layouts per group)
     if (batch_bufs_alloc(b, (size_t)((std::max(n, LNB_STREAM_COLS) + 15) / 16) * 16)) return -1;
-    HIPCHK(hipMalloc((void**)&b->d_tokens, LNB_BATCH_MAX * 4)); HIPCHK(hipMalloc((void**)&b->d_pos, LNB_BATCH_MAX * 4));
-    HIPCHK(hipMalloc((void**)&b->ring, LNB_BATCH_MAX * 4)); HIPCHK(hipMemsetAsync(b->ring, 0, LNB_BATCH_MAX * 4, b->stream));
+    HIPCHK(dev_alloc(b->d_tokens, LNB_BATCH_MAX * 4)); HIPCHK(dev_alloc(b->d_pos, LNB_BATCH_MAX * 4));
+    HIPCHK(dev_alloc(b->ring, LNB_BATCH_MAX * 4)); HIPCHK(hipMemsetAsync(b->ring, 0, LNB_BATCH_MAX * 4, b->stream));
     std::vector<TokProbOut> to(b->top_k > 0 ? n : 0);
     if (b->top_k > 0) {
         const size_t G = (size_t)lnb_tokprob_slices(n);
         for (int s = 0; s < n; s++) {
             const lnb_ctx* c = b->ctxs[s];
-            to[s].st = c->st; to[s].ids = c->tp_ids; to[s].logit = c->tp_logit; to[s].prob = c->tp_prob; to[s].log_z = c->tp_logz;
+            to[s].st = c->st; to[s].ids = c->tp.ids; to[s].logit = c->tp.logit; to[s].prob = c->tp.prob; to[s].log_z = c->tp.logz;
             to[s].walks = c->zseq_count + 2; to[s].cap = c->dout_cap;
         }
-        HIPCHK(hipMalloc((void**)&b->tp_out, n * sizeof(TokProbOut)));
+        HIPCHK(dev_alloc(b->tp_out, n * sizeof(TokProbOut)));
         HIPCHK(hipMemcpyAsync(b->tp_out, to.data(), n * sizeof(TokProbOut), hipMemcpyHostToDevice, b->stream));
-        HIPCHK(hipMalloc((void**)&b->tp_zpart, n * LNB_TOKPROB_MAX_G * 8)); HIPCHK(hipMalloc((void**)&b->tp_kpart, n * G * b->top_k * 8));
-        HIPCHK(hipMalloc((void**)&b->tp_cnt, n * 4)); HIPCHK(hipMemsetAsync(b->tp_cnt, 0, n * 4, b->stream));
+        HIPCHK(dev_alloc(b->tp_zpart, n * LNB_TOKPROB_MAX_G * 8)); HIPCHK(dev_alloc(b->tp_kpart, n * G * b->top_k * 8));
+        HIPCHK(dev_alloc(b->tp_cnt, n * 4)); HIPCHK(hipMemsetAsync(b->tp_cnt, 0, n * 4, b->stream));
     }
     HIPCHK(hipStreamSynchronize(b->stream));
     return 0;
@@ -2267,23 +2216,30 @@ extern "C" int lnb_batch_create(lnb_ctx* const* ctxs, int n, lnb_batch** out) {
 // (default: never -- a batch that fits the short kernels runs exactly what it ran before the long form existed).
 static bool batch_want_long(const lnb_batch* b, int max_pos) { return b->must_long || max_pos + 1 > b->attn_long_T; }
 // the e_buf [n][H][maxT] / z_part [n][H][ceil(maxT/256)] scratch of the batched long form (a batch's own, or the one a context's verify batches share)
-static int attn_long_scratch(int n, int H, int maxT, double** e_buf, double** z_part, const char* whose, bool quiet) {
-    if (*e_buf && *z_part) return 0;
+static int attn_long_scratch(int n, int H, int maxT, Dev<double>& e_buf, Dev<double>& z_part, const char* whose, bool quiet) {
+    if (e_buf && z_part) return 0;
     const size_t rows = (size_t)n * H, eb = rows * (size_t)maxT * 8, zb = rows * (size_t)((maxT + 255) / 256) * 8;
-    hipError_t e = hipMalloc((void**)e_buf, eb);
-    if (e == hipSuccess) e = hipMalloc((void**)z_part, zb);
+    hipError_t e = dev_alloc(e_buf, eb);
+    if (e == hipSuccess) e = dev_alloc(z_part, zb);
     if (e != hipSuccess) {
-        hipFree(*e_buf); hipFree(*z_part); *e_buf = nullptr; *z_part = nullptr; (void)hipGetLastError();
+        e_buf.reset(); z_part.reset(); (void)hipGetLastError();
         if (quiet) return -1;                                // (the caller has another way and records nothing)
         return fail("the long-context attention of %s needs %.1f MB of scratch (%d sequences x %d heads x %d positions): %s", whose, (double)(eb + zb) / 1e6,
                     n, H, maxT, hipGetErrorString(e));
     }
     return 0;
 }
+// a batch's OWN scratch for n columns of maxT positions (what it held before goes first), and the pointers its launches take
+static int batch_own_scratch(lnb_batch* b, int n, int maxT, const char* whose) {
+    b->e_own.reset(); b->z_own.reset(); b->e_buf = nullptr; b->z_part = nullptr;
+    if (attn_long_scratch(n, b->m->a.n_heads, maxT, b->e_own, b->z_own, whose)) return -1;
+    b->e_buf = b->e_own; b->z_part = b->z_own;
+    return 0;
+}
 static int batch_long_scratch(lnb_batch* b) {
     if (b->e_buf && b->z_part) return 0;
     if (!b->scratch_owned) return fail("internal error: verify batch without its context's attention scratch");
-    return attn_long_scratch(b->n, b->m->a.n_heads, b->maxT, &b->e_buf, &b->z_part, "this batch");
+    return batch_own_scratch(b, b->n, b->maxT, "this batch");
 }
 // selects the form of what is enqueued / captured next; allocates the scratch (host side of a call, outside any capture).  last_form (what
 // lnb_batch_attention_form reports) is set by the callers once their launches have been accepted.
@@ -2479,8 +2435,8 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     hipStream_t st = b->stream;
     if (batch_select_form_at(b, start_pos)) return -1;
     const bool use_graph = knob(Knob::NO_GRAPH) == 0;
-    hipGraphExec_t* const gslot = smp ? (b->attn_long ? &b->sgraph_long : &b->sgraph) : (b->attn_long ? &b->graph_long : &b->graph);       // one captured step per form
-    if (smp && !b->d_smp) HIPCHK(hipMalloc((void**)&b->d_smp, (size_t)LNB_BATCH_MAX * sizeof(LnbSampler)));
+    GraphExec& gslot = b->graphs.slot(smp ? GL_SAMPLE : GL_GREEDY, b->attn_long ? GF_LONG : GF_SHORT);       // one captured step per form
+    if (smp && !b->d_smp) HIPCHK(dev_alloc(b->d_smp, (size_t)LNB_BATCH_MAX * sizeof(LnbSampler)));
     if (use_graph && capture_once(gslot, st, [&] { return enqueue_batch_step(b, false, smp != nullptr); })) return -1;
     if (smp) HIPCHK(hipMemcpyAsync(b->d_smp, smp, (size_t)b->n * sizeof(LnbSampler), hipMemcpyHostToDevice, st));
     memcpy(b->h_io, tokens, (size_t)b->n * 4); memcpy(b->h_io + LNB_BATCH_MAX, start_pos, (size_t)b->n * 4);
@@ -2490,7 +2446,7 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     HIPCHK(lnbk_batch_set_state(b->tab, b->d_tokens, b->d_pos, b->ring, n_generated ? 1 : 0, st));
     HIPCHK(hipEventRecord(b->ev0, st));
     for (int i = 0; i < n_steps; i++) {
-        if (use_graph) HIPCHK(hipGraphLaunch(*gslot, st));
+        if (use_graph) HIPCHK(hipGraphLaunch(gslot, st));
         else if (enqueue_batch_step(b, false, smp != nullptr)) return -1;
     }
     HIPCHK(hipEventRecord(b->ev1, st));
@@ -2604,33 +2560,31 @@ extern "C" int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int it
 // lnb_decode_speculative_many's own tables beside the pass object (created on its first call): SmPass's device arrays in one allocation, the
 // members' text heads (history ++ token, concatenated; grown on demand), the pinned block the pack kernel reports into, the events of the loop
 struct SpecMany {
-    char* dev = nullptr; SmPass p{};
-    int32_t* text = nullptr; size_t text_cap = 0;
-    int32_t* word = nullptr; hipEvent_t ev = nullptr, ev0 = nullptr, ev1 = nullptr;
+    Dev<char> dev; SmPass p{};              // (p's device arrays are carved out of dev; p.word is the device address of `word`)
+    DevGrown<int32_t> text;
+    Pinned<int32_t> word; Event ev, ev0, ev1;
 };
 struct AppendMany {
-    lnb_batch* b = nullptr;                 // stream, activation buffers and logits for LNB_BATCH_MAX columns, tab / kv filled per pass
-    StepState* st = nullptr; int32_t* tok = nullptr; int32_t* dummy_log = nullptr; int* zseq = nullptr;
-    AmRow* rows = nullptr; size_t rows_cap = 0;             // the call's row table (grown on demand)
-    char* members = nullptr;                // AmMembers + one BatchKV per layer, indexed by member
-    int32_t* d_arg = nullptr; int32_t* h_arg = nullptr;     // [LNB_BATCH_MAX] argmax per member: device, pinned host
-    uint16_t* pin[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr};     // logits of a pass on their way to the host, two passes in flight
-    int scratch_n = 0, scratch_T = 0;       // what b->e_buf / b->z_part hold: columns x positions of the long-context pair
+    lnb_batch* b = nullptr;                 // stream, activation buffers and logits for LNB_BATCH_MAX columns, tab / kv filled per pass (append_many_free destroys it)
+    Dev<StepState> st; Dev<int32_t> tok, dummy_log; Dev<int> zseq;
+    DevGrown<AmRow> rows;                   // the call's row table (grown on demand)
+    Dev<char> members;                      // AmMembers + one BatchKV per layer, indexed by member
+    Dev<int32_t> d_arg; Pinned<int32_t> h_arg;              // [LNB_BATCH_MAX] argmax per member: device, pinned host
+    Pinned<uint16_t> pin[2]; Event ev[2];   // logits of a pass on their way to the host, two passes in flight
+    int scratch_n = 0, scratch_T = 0;       // what b->e_own / b->z_own hold: columns x positions of the long-context pair
     int last_layout = -1, last_width = 0;   // what the activation buffers were last used as
     int passes = 0, max_columns = 0, long_passes = 0;      // lnb_model_append_many_info
-    SpecMany* sm = nullptr;                 // lnb_decode_speculative_many runs its passes on this object
+    SpecMany* sm = nullptr;                 // lnb_decode_speculative_many runs its passes on this object (append_many_free deletes it)
 };
-static void spec_many_free(SpecMany* sm);
+// everything the object holds was enqueued on its batch's stream: that drains first, the batch (and its stream) goes last
 static void append_many_free(lnb_model* m) {
     AppendMany* am = m->am;
     if (!am) return;
     if (am->b && am->b->stream) hipStreamSynchronize(am->b->stream);
-    hipFree(am->st); hipFree(am->tok); hipFree(am->dummy_log); hipFree(am->zseq); hipFree(am->rows); hipFree(am->members); hipFree(am->d_arg);
-    if (am->h_arg) hipHostFree(am->h_arg);
-    for (int i = 0; i < 2; i++) { if (am->pin[i]) hipHostFree(am->pin[i]); if (am->ev[i]) hipEventDestroy(am->ev[i]); }
-    spec_many_free(am->sm);
-    if (am->b) lnb_batch_destroy(am->b);
+    delete am->sm;
+    lnb_batch* b = am->b;
     delete am;
+    if (b) lnb_batch_destroy(b);
     m->am = nullptr;
 }
 static int append_many_alloc(lnb_model* m) {
@@ -2641,14 +2595,14 @@ static int append_many_alloc(lnb_model* m) {
     lnb_batch* b = new lnb_batch();
     am->b = b; b->m = m; b->n = 1; b->scratch_owned = true;
     const size_t N = LNB_BATCH_MAX, L = m->layers.size();
-    auto dalloc = [&](void** p, size_t bytes) -> int { HIPCHK(hipMalloc(p, bytes)); HIPCHK(hipMemsetAsync(*p, 0, bytes, b->stream)); return 0; };
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) { fail("lnb_forward_append_many: no stream"); return bail(); }
-    if (batch_bufs_alloc(b, N) || dalloc((void**)&b->tab, sizeof(BatchTab)) || dalloc((void**)&b->kv, L * sizeof(BatchKV)) ||
-        dalloc((void**)&am->st, N * sizeof(StepState)) || dalloc((void**)&am->tok, N * 4) || dalloc((void**)&am->dummy_log, 64) || dalloc((void**)&am->zseq, 16) ||
-        dalloc((void**)&am->members, sizeof(AmMembers) + L * sizeof(BatchKV)) || dalloc((void**)&am->d_arg, N * 4)) return bail();
+    auto dalloc = [&](auto& p, size_t bytes) -> int { HIPCHK(dev_alloc(p, bytes)); HIPCHK(hipMemsetAsync(p.get(), 0, bytes, b->stream)); return 0; };
+    if (stream_create(b->stream, hipStreamNonBlocking) != hipSuccess) { fail("lnb_forward_append_many: no stream"); return bail(); }
+    if (batch_bufs_alloc(b, N) || dalloc(b->tab, sizeof(BatchTab)) || dalloc(b->kv, L * sizeof(BatchKV)) ||
+        dalloc(am->st, N * sizeof(StepState)) || dalloc(am->tok, N * 4) || dalloc(am->dummy_log, 64) || dalloc(am->zseq, 16) ||
+        dalloc(am->members, sizeof(AmMembers) + L * sizeof(BatchKV)) || dalloc(am->d_arg, N * 4)) return bail();
     b->zseq = am->zseq;
-    if (hipHostMalloc((void**)&am->h_arg, N * 4, hipHostMallocDefault) != hipSuccess) { fail("lnb_forward_append_many: no pinned host memory"); return bail(); }
-    for (int i = 0; i < 2; i++) if (hipEventCreateWithFlags(&am->ev[i], hipEventDisableTiming) != hipSuccess) { fail("lnb_forward_append_many: no event"); return bail(); }
+    if (pinned_alloc(am->h_arg, N * 4, hipHostMallocDefault) != hipSuccess) { fail("lnb_forward_append_many: no pinned host memory"); return bail(); }
+    for (int i = 0; i < 2; i++) if (event_create(am->ev[i], hipEventDisableTiming) != hipSuccess) { fail("lnb_forward_append_many: no event"); return bail(); }
     BatchTab t{};                                            // the pointers of a column never change: its own state and token word, the dummy log (capacity 0: nothing is ever logged)
     for (int c = 0; c < LNB_BATCH_MAX; c++) { t.st[c] = am->st + c; t.dtok[c] = am->tok + c; t.dout[c] = am->dummy_log; t.dout_cap[c] = 0; t.seq_len[c] = 0; }
     if (hipMemcpyAsync(b->tab, &t, sizeof t, hipMemcpyHostToDevice, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess) {
@@ -2725,19 +2679,16 @@ extern "C" int lnb_forward_append_many(lnb_ctx* const* ctxs, int n, const int32_
     AppendMany* am = m->am; lnb_batch* b = am->b; hipStream_t st = b->stream;
     if (need_n > am->scratch_n || need_T > am->scratch_T) {
         const int sn = std::max(need_n, am->scratch_n), sT = std::max(need_T, am->scratch_T);
-        hipFree(b->e_buf); hipFree(b->z_part); b->e_buf = nullptr; b->z_part = nullptr; am->scratch_n = am->scratch_T = 0;
-        if (attn_long_scratch(sn, m->a.n_heads, sT, &b->e_buf, &b->z_part, name)) return -1;
+        am->scratch_n = am->scratch_T = 0;
+        if (batch_own_scratch(b, sn, sT, name)) return -1;
         am->scratch_n = sn; am->scratch_T = sT;
     }
-    if ((size_t)total > am->rows_cap) {
-        AmRow* t = nullptr;
-        if (hipMalloc((void**)&t, (size_t)total * sizeof(AmRow)) != hipSuccess) { (void)hipGetLastError(); return fail("%s: no device memory for the row table (%zu bytes)", name, (size_t)total * sizeof(AmRow)); }
-        hipFree(am->rows); am->rows = t; am->rows_cap = (size_t)total;
-    }
+    // (every call ends with the stream drained: nothing reads the old row table)
+    if (dev_reserve(am->rows, (size_t)total * sizeof(AmRow)) != hipSuccess) { (void)hipGetLastError(); return fail("%s: no device memory for the row table (%zu bytes)", name, (size_t)total * sizeof(AmRow)); }
     if (logits_out && !am->pin[0])
         for (int i = 0; i < 2; i++)
-            if (hipHostMalloc((void**)&am->pin[i], (size_t)LNB_BATCH_MAX * V * 2, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError(); if (am->pin[0]) { hipHostFree(am->pin[0]); am->pin[0] = nullptr; }
+            if (pinned_alloc(am->pin[i], (size_t)LNB_BATCH_MAX * V * 2, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError(); am->pin[0].reset();
                 return fail("%s: no pinned host memory for the logits of a pass (%zu bytes)", name, (size_t)LNB_BATCH_MAX * V * 2);
             }
     // ---- from here on the caches are written
@@ -2762,7 +2713,7 @@ extern "C" int lnb_forward_append_many(lnb_ctx* const* ctxs, int n, const int32_
         const int layout = batch_plan_layout(batch_plan_of(b));      // what the activation buffers of this pass hold: B-operand columns, column groups or rows
         if (am->last_layout >= 0 && (layout != am->last_layout || width < am->last_width) && batch_bufs_zero(b, LNB_BATCH_MAX)) return -1;       // dead columns are zero again
         am->last_layout = layout; am->last_width = width;
-        AmPass ap{}; ap.rows = am->rows + row0; ap.members = (const AmMembers*)am->members; ap.member_kv = (const BatchKV*)(am->members + sizeof(AmMembers));
+        AmPass ap{}; ap.rows = am->rows + row0; ap.members = (const AmMembers*)am->members.get(); ap.member_kv = (const BatchKV*)(am->members + sizeof(AmMembers));
         ap.tab = b->tab; ap.kv = b->kv; ap.st = am->st; ap.tok = am->tok; ap.width = width; ap.n_layers = (int)L;
         HIPCHK(lnbk_append_many_setup(&ap, st));
         if (enqueue_batch_pass(b)) return -1;
@@ -2796,9 +2747,7 @@ extern "C" int lnb_batch_set_attention(lnb_batch* b, int long_threshold, int for
     HIPCHK(hipStreamSynchronize(b->stream));
     if (long_threshold >= 0) b->attn_long_T = long_threshold;
     if (force_zseq != b->force_zseq) {
-        if (b->graph_long) { hipGraphExecDestroy(b->graph_long); b->graph_long = nullptr; }
-        if (b->sgraph_long) { hipGraphExecDestroy(b->sgraph_long); b->sgraph_long = nullptr; }
-        if (b->stage_graph_long) { hipGraphExecDestroy(b->stage_graph_long); b->stage_graph_long = nullptr; }
+        b->graphs.drop(GF_LONG);
         b->force_zseq = force_zseq;
     }
     return 0;
@@ -2816,10 +2765,7 @@ extern "C" int lnb_ctx_set_batched_attention(lnb_ctx* c, int long_threshold, int
     HIPCHK(hipStreamSynchronize(c->stream));
     if (long_threshold >= 0) c->sp_attn_long_T = long_threshold;
     if (force_zseq != c->sp_force_zseq) {
-        for (lnb_batch* b : c->sp_b) if (b) {
-            b->force_zseq = force_zseq;
-            for (hipGraphExec_t* g : {&b->graph_long, &b->sgraph_long}) if (*g) { hipGraphExecDestroy(*g); *g = nullptr; }      // (the greedy pass and its sampling twin)
-        }
+        for (lnb_batch* b : c->sp_b) if (b) { b->force_zseq = force_zseq; b->graphs.drop(GF_LONG); }      // (the greedy pass and its sampling twin; a verify batch has no stage step)
         c->sp_force_zseq = force_zseq;
     }
     return 0;
@@ -2835,7 +2781,7 @@ extern "C" int lnb_ctx_set_rows_attention(lnb_ctx* c, int long_threshold, int fl
     HIPCHK(hipStreamSynchronize(c->stream));
     if (long_threshold >= 0) c->rows_T = long_threshold;
     if ((flags & 1) != (c->rows_flags & 1))
-        for (lnb_batch* b : c->sp_b) if (b) for (hipGraphExec_t* g : {&b->graph_rows, &b->sgraph_rows}) if (*g) { hipGraphExecDestroy(*g); *g = nullptr; }
+        for (lnb_batch* b : c->sp_b) if (b) b->graphs.drop(GF_ROWS);
     c->rows_flags = flags;
     return 0;
 }
@@ -2871,10 +2817,10 @@ extern "C" int lnb_ctx_set_draft(lnb_ctx* c, int max_draft, int ngram_min, int n
     if (!c || (n_corpus > 0 && !corpus)) return fail("null argument");
     HIPCHK(hipSetDevice(c->m->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    hipFree(c->sp_corpus); c->sp_corpus = nullptr; c->sp_n_corpus = 0;
+    c->sp_corpus.reset(); c->sp_n_corpus = 0;
     c->sp_max_draft = 0;
     if (max_draft == 0) return 0;
-    HIPCHK(hipMalloc((void**)&c->sp_corpus, (size_t)std::max(n_corpus, 1) * 4));
+    HIPCHK(dev_alloc(c->sp_corpus, (size_t)std::max(n_corpus, 1) * 4));
     if (n_corpus > 0) HIPCHK(hipMemcpy(c->sp_corpus, corpus, (size_t)n_corpus * 4, hipMemcpyHostToDevice));
     c->sp_n_corpus = n_corpus; c->sp_max_draft = max_draft; c->sp_ngram_min = ngram_min; c->sp_ngram_max = ngram_max;
     return 0;
@@ -2882,31 +2828,29 @@ extern "C" int lnb_ctx_set_draft(lnb_ctx* c, int max_draft, int ngram_min, int n
 // the per-context buffers of the drafting loop (the text head grows with the history)
 static int spec_alloc(lnb_ctx* c, int text_len) {
     if (!c->sp_st) {
-        HIPCHK(hipMalloc((void**)&c->sp_st, (LNB_MAX_DRAFT + 1) * sizeof(StepState)));
+        HIPCHK(dev_alloc(c->sp_st, (LNB_MAX_DRAFT + 1) * sizeof(StepState)));
         HIPCHK(hipMemsetAsync(c->sp_st, 0, (LNB_MAX_DRAFT + 1) * sizeof(StepState), c->stream));
-        HIPCHK(hipMalloc((void**)&c->sp_tok, (LNB_MAX_DRAFT + 1) * 4)); HIPCHK(hipMemsetAsync(c->sp_tok, 0, (LNB_MAX_DRAFT + 1) * 4, c->stream));
-        HIPCHK(hipMalloc((void**)&c->sp_g, (LNB_MAX_DRAFT + 1) * 4));
-        HIPCHK(hipMalloc((void**)&c->sp_best, 2 * LNB_SPEC_MAX_NGRAM * 4));
-        HIPCHK(hipMalloc((void**)&c->sp_cnt, 16)); HIPCHK(hipMemsetAsync(c->sp_cnt, 0, 16, c->stream));
-        HIPCHK(hipHostMalloc((void**)&c->sp_word, 16, hipHostMallocMapped));
+        HIPCHK(dev_alloc(c->sp_tok, (LNB_MAX_DRAFT + 1) * 4)); HIPCHK(hipMemsetAsync(c->sp_tok, 0, (LNB_MAX_DRAFT + 1) * 4, c->stream));
+        HIPCHK(dev_alloc(c->sp_g, (LNB_MAX_DRAFT + 1) * 4));
+        HIPCHK(dev_alloc(c->sp_best, 2 * LNB_SPEC_MAX_NGRAM * 4));
+        HIPCHK(dev_alloc(c->sp_cnt, 16)); HIPCHK(hipMemsetAsync(c->sp_cnt, 0, 16, c->stream));
+        HIPCHK(pinned_alloc(c->sp_word, 16, hipHostMallocMapped));
         HIPCHK(hipHostGetDevicePointer((void**)&c->sp_word_dev, c->sp_word, 0));
-        HIPCHK(hipEventCreate(&c->sp_ev));
+        HIPCHK(event_create(c->sp_ev));
     }
-    if (text_len > c->sp_text_cap) {
+    if (!c->sp_text.fits((size_t)text_len * 4)) {
         HIPCHK(hipStreamSynchronize(c->stream));
-        hipFree(c->sp_text); c->sp_text = nullptr; c->sp_text_cap = 0;
-        HIPCHK(hipMalloc((void**)&c->sp_text, (size_t)text_len * 4));
-        c->sp_text_cap = text_len;
+        HIPCHK(dev_reserve(c->sp_text, (size_t)text_len * 4));
     }
     return 0;
 }
 // the verify batch of width w, its graph captured on first use: embedding gather of the w column tokens, the blocks, the head, the
 // columns' argmax, the commit.  With the matrix-core copy the products are its column forms, without it rows of gemm_stream_kernel.
 // form 1: the pass runs the long-context pair, 2: the multi-row pair (one graph per form and width); their scratch is the context's, shared by all widths
-static int spec_verify_batch(lnb_ctx* c, int w, int form, bool sample, lnb_batch** out, hipGraphExec_t* graph_out) {
+static int spec_verify_batch(lnb_ctx* c, int w, GraphForm form, bool sample, lnb_batch** out, hipGraphExec_t* graph_out) {
     lnb_model* m = c->m;
-    const bool long_form = form != 0;
-    if (long_form && attn_long_scratch(LNB_MAX_DRAFT + 1, m->a.n_heads, c->seq_len, &c->sp_e_buf, &c->sp_z_part, "the verify passes")) return -1;   // (host side of the call, outside any capture)
+    const bool long_form = form != GF_SHORT;
+    if (long_form && attn_long_scratch(LNB_MAX_DRAFT + 1, m->a.n_heads, c->seq_len, c->sp_e_buf, c->sp_z_part, "the verify passes")) return -1;   // (host side of the call, outside any capture)
     lnb_batch* b = c->sp_b[w];
     const bool fresh = !b;
     if (fresh) {
@@ -2919,8 +2863,8 @@ static int spec_verify_batch(lnb_ctx* c, int w, int form, bool sample, lnb_batch
         c->sp_b[w] = b;
     }
     b->e_buf = c->sp_e_buf; b->z_part = c->sp_z_part;
-    b->attn_long = long_form; b->attn_rows = form == 2; b->rows_zseq = c->rows_flags & 1;
-    hipGraphExec_t* const gslot = sample ? (form == 2 ? &b->sgraph_rows : long_form ? &b->sgraph_long : &b->sgraph) : (form == 2 ? &b->graph_rows : long_form ? &b->graph_long : &b->graph);
+    b->attn_long = long_form; b->attn_rows = form == GF_ROWS; b->rows_zseq = c->rows_flags & 1;
+    GraphExec& gslot = b->graphs.slot(sample ? GL_SAMPLE : GL_GREEDY, form);
     auto body = [&]() -> int {
         if (enqueue_batch_pass(b)) return -1;
         if (sample) {                                        // the token launch is the one difference: every column's sampled token at its own position, then the same acceptance
@@ -2935,7 +2879,7 @@ static int spec_verify_batch(lnb_ctx* c, int w, int form, bool sample, lnb_batch
         if (fresh) { c->sp_b[w] = nullptr; lnb_batch_destroy(b); }      // (a batch without a graph is not kept)
         return -1;
     }
-    *out = b; *graph_out = *gslot;
+    *out = b; *graph_out = gslot;
     return 0;
 }
 static DraftParams spec_draft_params(lnb_ctx* c, int n_text, int max_steps) {
@@ -2971,7 +2915,7 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
     if (batch_shape_check(m, "the verify pass")) return -1;
     if (!m->batch_enabled) HIPCHK(lnbk_batch_prepare());
     const int n_text = n_history + 1;
-    if (smp && !c->d_smp) HIPCHK(hipMalloc((void**)&c->d_smp, sizeof(LnbSampler)));
+    if (smp && !c->d_smp) HIPCHK(dev_alloc(c->d_smp, sizeof(LnbSampler)));
     if (spec_alloc(c, n_text) || capture_decode_graphs(c, start_pos, max_steps, smp != nullptr)) return -1;
     hipStream_t st = c->stream;
     c->tp_last_k = 0; c->tp_last_n = 0;
@@ -2999,12 +2943,12 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
         s.passes++;
         if (k == 0) {
             const bool lg = want_long_attention(c, 1, start_pos + n_out);
-            HIPCHK(hipGraphLaunch(smp ? (lg ? c->sgraph_long : c->sgraph) : (lg ? c->graph_long : c->graph), st));
+            HIPCHK(hipGraphLaunch(c->graphs.slot(smp ? GL_SAMPLE : GL_GREEDY, lg ? GF_LONG : GF_SHORT), st));
         } else {
             lnb_batch* b = nullptr; hipGraphExec_t pass = nullptr;
             // the pass's last column sits at start_pos + n_out + k: the long form when the context is beyond the one-workgroup kernels' reach or past the threshold
             const bool lf = c->seq_len > c->attn_short_cap || start_pos + n_out + k + 1 > c->sp_attn_long_T;
-            const int form = !lf ? 0 : (c->rows_flags & 2) ? 2 : 1;     // (2: lnb_ctx_set_rows_attention's opt-in -- K and V read once for all columns)
+            const GraphForm form = !lf ? GF_SHORT : (c->rows_flags & 2) ? GF_ROWS : GF_LONG;     // (rows: lnb_ctx_set_rows_attention's opt-in -- K and V read once for all columns)
             if (spec_verify_batch(c, k + 1, form, smp != nullptr, &b, &pass)) return -1;
             HIPCHK(hipGraphLaunch(pass, st));
             c->sp_last_form = form; b->last_form = lf ? 1 : 0;
@@ -3050,30 +2994,22 @@ extern "C" int lnb_op_ngram_draft(int device, const int32_t* text, int n_text, c
     if (n_text < 0) return fail("negative text length %d", n_text);
     if (spec_check_draft_args(max_draft, ngram_min, ngram_max, n_corpus)) return -1;
     if ((n_text > 0 && !text) || (n_corpus > 0 && !corpus) || !out || !n_out) return fail("null argument");
-    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
-    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
-    int32_t *dt = nullptr, *dc = nullptr, *dout = nullptr, *dword = nullptr; int* best = nullptr; unsigned* cnt = nullptr;
-    hipError_t e = hipMalloc((void**)&dt, (size_t)std::max(n_text, 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&dc, (size_t)std::max(n_corpus, 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&dout, (LNB_MAX_DRAFT + 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&dword, 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&best, 2 * LNB_SPEC_MAX_NGRAM * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&cnt, 16);
-    if (e == hipSuccess) e = hipMemset(cnt, 0, 16);
-    if (e == hipSuccess && n_text > 0) e = hipMemcpy(dt, text, (size_t)n_text * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_corpus > 0) e = hipMemcpy(dc, corpus, (size_t)n_corpus * 4, hipMemcpyHostToDevice);
+    if (op_device(device)) return -1;
+    DevArena a;
+    int32_t* dt = a.alloc<int32_t>((size_t)std::max(n_text, 1)); int32_t* dc = a.alloc<int32_t>((size_t)std::max(n_corpus, 1));
+    int32_t* dout = a.alloc<int32_t>(LNB_MAX_DRAFT + 1); int32_t* dword = a.alloc<int32_t>(4);
+    int* best = a.alloc<int>(2 * LNB_SPEC_MAX_NGRAM); unsigned* cnt = a.alloc<unsigned>(4);
+    HIPCHK(a.error());
+    HIPCHK(hipMemset(cnt, 0, 16));
+    if (n_text > 0) HIPCHK(hipMemcpy(dt, text, (size_t)n_text * 4, hipMemcpyHostToDevice));
+    if (n_corpus > 0) HIPCHK(hipMemcpy(dc, corpus, (size_t)n_corpus * 4, hipMemcpyHostToDevice));
     int32_t h[LNB_MAX_DRAFT + 1] = {}, word[4] = {};
-    if (e == hipSuccess) {
-        DraftParams p{}; p.text = dt; p.n_text = n_text; p.corpus = dc; p.n_corpus = n_corpus;
-        p.ngram_min = ngram_min; p.ngram_max = ngram_max; p.max_draft = max_draft; p.out = dout; p.word = dword; p.best = best; p.cnt = cnt;
-        e = lnbk_ngram_draft(&p, nullptr);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(word, dword, 12, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(h, dout, sizeof h, hipMemcpyDeviceToHost);
-    hipFree(dt); hipFree(dc); hipFree(dout); hipFree(dword); hipFree(best); hipFree(cnt);
-    HIPCHK(e);
+    DraftParams p{}; p.text = dt; p.n_text = n_text; p.corpus = dc; p.n_corpus = n_corpus;
+    p.ngram_min = ngram_min; p.ngram_max = ngram_max; p.max_draft = max_draft; p.out = dout; p.word = dword; p.best = best; p.cnt = cnt;
+    HIPCHK(lnbk_ngram_draft(&p, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(word, dword, 12, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h, dout, sizeof h, hipMemcpyDeviceToHost));
     if (word[0] < 0 || word[0] > max_draft) return fail("internal error: draft length %d", word[0]);
     for (int i = 0; i < word[0]; i++) out[i] = h[1 + i];
     *n_out = word[0];
@@ -3086,13 +3022,6 @@ extern "C" int lnb_op_ngram_draft(int device, const int32_t* text, int n_text, c
 //   -> [host: reads {width, any_draft, running, largest seq_len}, its one round trip per pass] -> append_many_setup_kernel -> the batched step
 //   -> spec_many_commit_kernel (argmax per column, acceptance and emission per member into the member's OWN state, token word and log).
 // The launches are eager, as lnb_forward_append_many's are (profiles/spec_many.md).
-static void spec_many_free(SpecMany* sm) {
-    if (!sm) return;
-    hipFree(sm->dev); hipFree(sm->text);
-    if (sm->word) hipHostFree(sm->word);
-    for (hipEvent_t e : {sm->ev, sm->ev0, sm->ev1}) if (e) hipEventDestroy(e);
-    delete sm;
-}
 static int spec_many_build(SpecMany* sm, hipStream_t st) {
     const size_t N = LNB_BATCH_MAX;
     size_t off = 0;
@@ -3100,13 +3029,13 @@ static int spec_many_build(SpecMany* sm, hipStream_t st) {
     const size_t o_mem = carve(N * sizeof(SmMember)), o_want = carve(N * 4), o_run = carve(N * 4), o_draft = carve(N * LNB_SPEC_MAX_DRAFT * 4),
                  o_best = carve(N * 2 * LNB_SPEC_MAX_NGRAM * 4), o_cnt = carve((N + 1) * 4), o_rows = carve(N * sizeof(AmRow)), o_seg = carve(N * sizeof(SmSeg)),
                  o_stats = carve(N * sizeof(SmStats)), o_g = carve(N * 4), o_smp = carve(N * sizeof(LnbSampler));
-    HIPCHK(hipMalloc((void**)&sm->dev, off));
+    HIPCHK(dev_alloc(sm->dev, off));
     HIPCHK(hipMemsetAsync(sm->dev, 0, off, st));
-    HIPCHK(hipHostMalloc((void**)&sm->word, 16, hipHostMallocMapped));
+    HIPCHK(pinned_alloc(sm->word, 16, hipHostMallocMapped));
     int32_t* word_dev = nullptr;
     HIPCHK(hipHostGetDevicePointer((void**)&word_dev, sm->word, 0));
-    HIPCHK(hipEventCreate(&sm->ev));
-    HIPCHK(hipEventCreate(&sm->ev0)); HIPCHK(hipEventCreate(&sm->ev1));
+    HIPCHK(event_create(sm->ev));
+    HIPCHK(event_create(sm->ev0)); HIPCHK(event_create(sm->ev1));
     HIPCHK(hipStreamSynchronize(st));
     SmPass& p = sm->p; char* d = sm->dev;
     p.members = (const SmMember*)(d + o_mem); p.want = (int32_t*)(d + o_want); p.running = (int32_t*)(d + o_run); p.draft = (int32_t*)(d + o_draft);
@@ -3118,7 +3047,7 @@ static int spec_many_build(SpecMany* sm, hipStream_t st) {
 static int spec_many_alloc(AppendMany* am) {
     if (am->sm) return 0;
     SpecMany* sm = new SpecMany();
-    if (spec_many_build(sm, am->b->stream)) { (void)hipGetLastError(); spec_many_free(sm); return -1; }
+    if (spec_many_build(sm, am->b->stream)) { (void)hipGetLastError(); delete sm; return -1; }
     am->sm = sm;
     return 0;
 }
@@ -3182,15 +3111,11 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
     SpecMany* sm = am->sm;
     if (any_long && (budget > am->scratch_n || need_T > am->scratch_T)) {
         const int sn = std::max(budget, am->scratch_n), sT = std::max(need_T, am->scratch_T);
-        hipFree(b->e_buf); hipFree(b->z_part); b->e_buf = nullptr; b->z_part = nullptr; am->scratch_n = am->scratch_T = 0;
-        if (attn_long_scratch(sn, m->a.n_heads, sT, &b->e_buf, &b->z_part, name)) return -1;
+        am->scratch_n = am->scratch_T = 0;
+        if (batch_own_scratch(b, sn, sT, name)) return -1;
         am->scratch_n = sn; am->scratch_T = sT;
     }
-    if (text_total > sm->text_cap) {
-        int32_t* t = nullptr;
-        if (hipMalloc((void**)&t, text_total * 4) != hipSuccess) { (void)hipGetLastError(); return fail("%s: no device memory for the members' histories (%zu bytes)", name, text_total * 4); }
-        hipFree(sm->text); sm->text = t; sm->text_cap = text_total;
-    }
+    if (dev_reserve(sm->text, text_total * 4) != hipSuccess) { (void)hipGetLastError(); return fail("%s: no device memory for the members' histories (%zu bytes)", name, text_total * 4); }
     // ---- the call's tables on the host: the members' cache lengths and pointers (as lnb_forward_append_many's), their SmMember, their text heads
     const size_t L = m->layers.size();
     std::vector<char> members(sizeof(AmMembers) + L * sizeof(BatchKV));
@@ -3246,7 +3171,7 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
         const int layout = batch_plan_layout(batch_plan_of(b));
         if (am->last_layout >= 0 && (layout != am->last_layout || width < am->last_width) && batch_bufs_zero(b, LNB_BATCH_MAX)) return -1;       // dead columns are zero again
         am->last_layout = layout; am->last_width = width;
-        AmPass ap{}; ap.rows = sp.rows; ap.members = (const AmMembers*)am->members; ap.member_kv = (const BatchKV*)(am->members + sizeof(AmMembers));
+        AmPass ap{}; ap.rows = sp.rows; ap.members = (const AmMembers*)am->members.get(); ap.member_kv = (const BatchKV*)(am->members + sizeof(AmMembers));
         ap.tab = b->tab; ap.kv = b->kv; ap.st = am->st; ap.tok = am->tok; ap.width = width; ap.n_layers = (int)L;
         HIPCHK(lnbk_append_many_setup(&ap, st));
         if (enqueue_batch_pass(b)) return -1;
@@ -3316,8 +3241,8 @@ struct lnb_pipe {
     lnb_model* m = nullptr; int rank = 0, world = 1;
     LoopGroup* loop = nullptr; std::string loop_tag;
     void* comm = nullptr; const lnb_rccl_api* api = nullptr;
-    hipStream_t xs = nullptr;              // exchange stream
-    int32_t* h_tok = nullptr; int tok_cap = 0, tok_n = 0;   // pinned RING of the tokens the last stage produced, in tick order: slot s lives at s % tok_cap
+    Stream xs;                             // exchange stream
+    Pinned<int32_t> h_tok; int tok_cap = 0, tok_n = 0;   // pinned RING of the tokens the last stage produced, in tick order: slot s lives at s % tok_cap
     bool use_graph = true;
     bool host = false;                     // no transport: the host layer moves the boundary buffers (lnb_pipeline_init_host)
 };
@@ -3346,14 +3271,14 @@ static int pipe_new(lnb_model* m, int rank, int world, lnb_pipe** out) {
     HIPCHK(hipSetDevice(m->device));
     lnb_pipe* p = new lnb_pipe();
     p->m = m; p->rank = rank; p->world = world; p->use_graph = pipe_use_graph();
-    hipError_t e = hipStreamCreateWithFlags(&p->xs, hipStreamNonBlocking);
-    if (e == hipSuccess) { p->tok_cap = pipe_log_cap(); e = hipHostMalloc((void**)&p->h_tok, (size_t)p->tok_cap * 4, hipHostMallocDefault); }
-    if (e != hipSuccess) { fail("pipeline init: %s", hipGetErrorString(e)); if (p->xs) hipStreamDestroy(p->xs); delete p; return -1; }
+    hipError_t e = stream_create(p->xs, hipStreamNonBlocking);
+    if (e == hipSuccess) { p->tok_cap = pipe_log_cap(); e = pinned_alloc(p->h_tok, (size_t)p->tok_cap * 4, hipHostMallocDefault); }
+    if (e != hipSuccess) { fail("pipeline init: %s", hipGetErrorString(e)); delete p; return -1; }
     *out = p;
     return 0;
 }
 // an entry point whose own part failed (the error is set; no communicator, no group joined): what pipe_new made goes, nothing enqueued yet
-static int pipe_abandon(lnb_pipe** out) { hipStreamDestroy((*out)->xs); hipHostFree((*out)->h_tok); delete *out; *out = nullptr; return -1; }
+static int pipe_abandon(lnb_pipe** out) { delete *out; *out = nullptr; return -1; }
 extern "C" int lnb_pipeline_init(lnb_model* m, int rank, int world, const void* id128, lnb_pipe** out) {
     if (pipe_new(m, rank, world, out)) return -1;
     lnb_pipe* p = *out;
@@ -3399,8 +3324,6 @@ extern "C" int lnb_pipeline_destroy(lnb_pipe* p) {
     hipDeviceSynchronize();
     if (p->loop) { std::lock_guard<std::mutex> lock(g_loops_mu); if (--p->loop->users == 0) g_loops.erase(p->loop_tag); }
     if (p->comm) p->api->CommDestroy(p->comm);
-    if (p->xs) hipStreamDestroy(p->xs);
-    if (p->h_tok) hipHostFree(p->h_tok);
     delete p;
     return 0;
 }
@@ -3428,7 +3351,7 @@ static int enqueue_stage_step(lnb_pipe* p, lnb_ctx* c, const int32_t* tokens, in
     };
     c->attn_long = longctx;
     if (rows == 1 && !tokens && p->use_graph) {
-        hipGraphExec_t* slot = &c->stage_graph[longctx ? 1 : 0];
+        GraphExec& slot = c->graphs.slot(GL_STAGE, longctx ? GF_LONG : GF_SHORT);
         if (capture_once(slot, st, [&]() -> int {
                 if (body(false)) return -1;
                 return lnbk_advance_state(c->st, 1, st) != hipSuccess ? fail("advance_state launch failed") : 0;
@@ -3436,7 +3359,7 @@ static int enqueue_stage_step(lnb_pipe* p, lnb_ctx* c, const int32_t* tokens, in
         if (c->dev_pos != pos) HIPCHK(ctx_set_state(c, pos, 0, true));
         c->call_T = 0;
         form_ran(Form::PIPELINE_REPLAY);
-        HIPCHK(hipGraphLaunch(*slot, st));
+        HIPCHK(hipGraphLaunch(slot, st));
         c->dev_pos = pos + 1;                                // (the graph ends with advance_state)
         return 0;
     }
@@ -3561,10 +3484,10 @@ extern "C" int lnb_pipeline_tick_batch(lnb_pipe* p, lnb_batch* run, lnb_batch* s
         const bool ring_in = first && p->world > 1;
         if (batch_select_form(run, run->tick_long)) return -1;       // the form lnb_batch_set_state chose for this run of ticks
         if (p->use_graph) {
-            hipGraphExec_t* const gslot = run->attn_long ? &run->stage_graph_long : &run->stage_graph;
+            GraphExec& gslot = run->graphs.slot(GL_STAGE, run->attn_long ? GF_LONG : GF_SHORT);
             if (capture_once(gslot, st, [&] { return enqueue_batch_step(run, ring_in); })) return -1;
             form_ran(Form::PIPELINE_REPLAY);
-            HIPCHK(hipGraphLaunch(*gslot, st));
+            HIPCHK(hipGraphLaunch(gslot, st));
         } else { form_ran(Form::PIPELINE_EAGER); if (enqueue_batch_step(run, ring_in)) return -1; }
         run->last_form = run->attn_long ? 1 : 0;
         if (last) {
@@ -3583,9 +3506,7 @@ extern "C" int lnb_pipeline_tick_batch(lnb_pipe* p, lnb_batch* run, lnb_batch* s
 // compare.  Exercises dlopen, the by-value unique id, the group calls and a RCCL kernel launch from a process that never loaded torch.
 extern "C" int lnb_pipeline_selftest(int device, int n_bytes) {
     if (n_bytes <= 0 || n_bytes > (1 << 26)) return fail("n_bytes out of range");
-    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
-    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
+    if (op_device(device)) return -1;
     const lnb_rccl_api* api = lnb_rccl_load();
     if (!api) return -1;
     lnb_nccl_id id; memset(&id, 0, sizeof id);
@@ -3596,11 +3517,11 @@ extern "C" int lnb_pipeline_selftest(int device, int n_bytes) {
     if (r != 0) return fail("ncclCommInitRank failed: %s", api->GetErrorString(r));
     std::vector<unsigned char> h((size_t)n_bytes), back((size_t)n_bytes);
     for (int i = 0; i < n_bytes; i++) h[i] = (unsigned char)((i * 131 + 7) >> 3);
-    unsigned char *src = nullptr, *dst = nullptr; hipStream_t xs = nullptr;
+    Stream xs; Dev<unsigned char> src, dst;
     int rc = 0;
-    hipError_t e = hipMalloc((void**)&src, (size_t)n_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&dst, (size_t)n_bytes);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&xs, hipStreamNonBlocking);
+    hipError_t e = dev_alloc(src, (size_t)n_bytes);
+    if (e == hipSuccess) e = dev_alloc(dst, (size_t)n_bytes);
+    if (e == hipSuccess) e = stream_create(xs, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMemcpy(src, h.data(), (size_t)n_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(dst, 0, (size_t)n_bytes);
     if (e != hipSuccess) rc = fail("selftest setup: %s", hipGetErrorString(e));
@@ -3613,9 +3534,6 @@ extern "C" int lnb_pipeline_selftest(int device, int n_bytes) {
     if (!rc && (e = hipMemcpy(back.data(), dst, (size_t)n_bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = fail("selftest readback: %s", hipGetErrorString(e));
     if (!rc && memcmp(back.data(), h.data(), (size_t)n_bytes) != 0) rc = fail("RCCL self exchange delivered different bytes");
     api->CommDestroy(comm);
-    if (xs) hipStreamDestroy(xs);
-    if (src) hipFree(src);
-    if (dst) hipFree(dst);
     return rc;
 }
 // how many ranks the exchange spans, asked of the transport itself: ncclCommCount of the RCCL communicator (world > 1), the number of pipes
@@ -3655,9 +3573,7 @@ static int op_linear_impl(int device, const uint16_t* x, const uint16_t* norm_w,
     if (!x || !w || !y) return fail("null argument");
     if (rows <= 0 || n_out <= 0 || k_in <= 0) return fail("empty operand");
     if (k_in % 8) return fail("in_features must be a multiple of 8");
-    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
-    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
+    if (op_device(device)) return -1;
     HIPCHK(lnbk_init());
     HIPCHK(lnbk_fast_init());
     if (mode != LNB_MODE_EXACT && mode != LNB_MODE_FAST) return fail("unknown mode %d", mode);
@@ -3665,29 +3581,31 @@ static int op_linear_impl(int device, const uint16_t* x, const uint16_t* norm_w,
     if (rw != 16 && rw != 32 && rw != 64 && !(rw == 4 && !norm_w && k_in % 128 == 0 && k_in <= 16384) && !(rw == 24 && k_in % 256 == 0))
         return fail("rw must be 16, 32 or 64 (or 4: row-broadcast layout, no fused norm, in_features a multiple of 128; or 24: quad layout, in_features a multiple of 256)");
     if ((size_t)k_in * 4 > 120 * 1024) return fail("in_features %d does not fit the LDS staging", k_in);
+    DevArena a;                                             // every buffer of the call: released on every way out
     TiledDesc t{}; int64_t bytes = 0;
-    if (alloc_tiled(t, n_out, k_in, rw, 1, bytes)) return -1;
-    uint16_t *dx = nullptr, *dw = nullptr, *dy = nullptr, *dn = nullptr; StepState* st = nullptr;
-    HIPCHK(hipMalloc((void**)&dx, (size_t)rows * k_in * 2)); HIPCHK(hipMalloc((void**)&dw, (size_t)n_out * k_in * 2));
-    HIPCHK(hipMalloc((void**)&dy, (size_t)rows * n_out * 2)); HIPCHK(hipMalloc((void**)&st, sizeof(StepState)));
+    if (alloc_tiled(a, t, n_out, k_in, rw, 1, bytes)) return -1;
+    uint16_t* dx = a.alloc<uint16_t>((size_t)rows * k_in); uint16_t* dw = a.alloc<uint16_t>((size_t)n_out * k_in);
+    uint16_t* dy = a.alloc<uint16_t>((size_t)rows * n_out); StepState* st = a.alloc<StepState>(1);
+    uint16_t* dn = nullptr;
+    HIPCHK(a.error());
     HIPCHK(hipMemset(st, 0, sizeof(StepState)));
     HIPCHK(hipMemcpy(dx, x, (size_t)rows * k_in * 2, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dw, w, (size_t)n_out * k_in * 2, hipMemcpyHostToDevice));
-    if (norm_w) { HIPCHK(hipMalloc((void**)&dn, (size_t)k_in * 2)); HIPCHK(hipMemcpy(dn, norm_w, (size_t)k_in * 2, hipMemcpyHostToDevice)); }
+    if (norm_w) { if (arena_alloc(a, &dn, (size_t)k_in * 2)) return -1; HIPCHK(hipMemcpy(dn, norm_w, (size_t)k_in * 2, hipMemcpyHostToDevice)); }
     HIPCHK(lnbk_tile(dw, t.w, n_out, k_in, 0, 0, rw, 1, 0, nullptr));
     if (use_mfma(rows) && knob(Knob::OP_STREAM) && k_in % 128 == 0) {      // (tests: the same operator through gemm_stream_kernel)
         HIPCHK(lnbk_batch_prepare());
         const size_t mb = m16_elems(n_out, k_in, 1) * 2;
-        HIPCHK(hipMalloc((void**)&t.w16, mb)); HIPCHK(hipMemset(t.w16, 0, mb));
+        if (arena_alloc(a, &t.w16, mb)) return -1;
+        HIPCHK(hipMemset(t.w16, 0, mb));
         HIPCHK(lnbk_m16_from_tiled(t.w, t.w16, n_out, k_in, rw, 1, nullptr));
     }
     if (use_mfma(rows)) {                                   // 16 or more rows: the matrix-core path of the prefill
         uint16_t* dxn = nullptr;
-        if (norm_w) { HIPCHK(hipMalloc((void**)&dxn, (size_t)rows * k_in * 2)); HIPCHK(lnbk_rmsnorm_rows(dx, dn, dxn, rows, k_in, eps, nullptr)); }
+        if (norm_w) { if (arena_alloc(a, &dxn, (size_t)rows * k_in * 2)) return -1; HIPCHK(lnbk_rmsnorm_rows(dx, dn, dxn, rows, k_in, eps, nullptr)); }
         GemmParams gm = gemm_of(t, norm_w ? dxn : dx, k_in, n_out, rows, st); gm.out = dy;
         HIPCHK(gemm_dispatch(mode, &gm, EPI_STORE, nullptr));
         HIPCHK(hipDeviceSynchronize());
-        if (dxn) hipFree(dxn);
     } else {
     GemvParams g{}; g.w = t.w; g.x = dx; g.norm_w = dn; g.eps = eps; g.K = k_in; g.n_rows = n_out; g.S = rows; g.st = st; g.out = dy;
     set_grid(g, t);
@@ -3696,7 +3614,6 @@ static int op_linear_impl(int device, const uint16_t* x, const uint16_t* norm_w,
     }
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(y, dy, (size_t)rows * n_out * 2, hipMemcpyDeviceToHost));
-    hipFree(dx); hipFree(dw); hipFree(dy); hipFree(st); hipFree(t.w); if (dn) hipFree(dn); if (t.w16) hipFree(t.w16);
     return 0;
 }
 // The fused ffn_norm + w1|w3 + SiLU*up launch of a one-token step on its own: y[n_out] from one row x.  packed = 0: the raw 56-row kernel; 1: from the
@@ -3706,18 +3623,17 @@ extern "C" int lnb_op_rmsnorm_gate_up(int device, const uint16_t* x, const uint1
     if (!x || !norm_w || !w1 || !w3 || !y) return fail("null argument");
     if (n_out <= 0 || k_in <= 0) return fail("empty operand");
     if (k_in % 8) return fail("in_features must be a multiple of 8");
-    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
-    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
+    if (op_device(device)) return -1;
     HIPCHK(lnbk_init());
     if (!lnbk_w13p_supported(56, k_in)) return fail("in_features %d does not fit the LDS staging of the 56-row gate|up kernel", k_in);
+    DevArena a;
     TiledDesc t{}; int64_t bytes = 0;
-    if (alloc_tiled(t, n_out, k_in, 56, 2, bytes)) return -1;
+    if (alloc_tiled(a, t, n_out, k_in, 56, 2, bytes)) return -1;
     const size_t wn = (size_t)n_out * k_in * 2;
-    uint16_t *dx = nullptr, *dw = nullptr, *dy = nullptr, *dn = nullptr; StepState* st = nullptr; float* dsilu = nullptr; unsigned* dstats = nullptr; void* wp = nullptr;
-    HIPCHK(hipMalloc((void**)&dx, (size_t)k_in * 2)); HIPCHK(hipMalloc((void**)&dw, wn)); HIPCHK(hipMalloc((void**)&dn, (size_t)k_in * 2));
-    HIPCHK(hipMalloc((void**)&dy, (size_t)n_out * 2)); HIPCHK(hipMalloc((void**)&st, sizeof(StepState))); HIPCHK(hipMalloc((void**)&dsilu, (size_t)65536 * 4));
-    HIPCHK(hipMalloc((void**)&dstats, sizeof(WpackStats)));
+    uint16_t* dx = a.alloc<uint16_t>((size_t)k_in); uint16_t* dw = a.alloc<uint16_t>(wn / 2); uint16_t* dn = a.alloc<uint16_t>((size_t)k_in);
+    uint16_t* dy = a.alloc<uint16_t>((size_t)n_out); StepState* st = a.alloc<StepState>(1); float* dsilu = a.alloc<float>(65536);
+    unsigned* dstats = (unsigned*)a.alloc<WpackStats>(1); void* wp = nullptr;
+    HIPCHK(a.error());
     HIPCHK(hipMemset(st, 0, sizeof(StepState)));
     std::vector<float> silu(1 << 16);
     for (int i = 0; i < (1 << 16); i++) { double v = (double)bf_wide_h((uint16_t)i); silu[i] = (float)(v / (1.0 + std::exp(-v))); }
@@ -3733,14 +3649,13 @@ extern "C" int lnb_op_rmsnorm_gate_up(int device, const uint16_t* x, const uint1
     GemvParams g{}; g.w = t.w; g.x = dx; g.norm_w = dn; g.eps = eps; g.K = k_in; g.n_rows = n_out; g.S = 1; g.st = st; g.out = dy; g.silu = dsilu;
     set_grid(g, t);
     if (packed && why == WPACK_OK) {
-        HIPCHK(hipMalloc(&wp, lnbk_wpack_w13_bytes(t.n_blocks, k_in)));
+        if (arena_alloc(a, &wp, lnbk_wpack_w13_bytes(t.n_blocks, k_in))) return -1;
         HIPCHK(lnbk_wpack_w13(t.w, wp, k_in, t.n_blocks, base, nullptr));
         g.wp = wp; g.wp_base4 = base * 0x01010101u;
         HIPCHK(lnbk_gemv_w13p(&g, nullptr));
     } else HIPCHK(lnbk_gemv(&g, 56, 2, EPI_SILU_MUL, 1, nullptr));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(y, dy, (size_t)n_out * 2, hipMemcpyDeviceToHost));
-    hipFree(dx); hipFree(dw); hipFree(dy); hipFree(dn); hipFree(st); hipFree(dsilu); hipFree(dstats); hipFree(t.w); if (wp) hipFree(wp);
     return 0;
 }
 // The fused final norm + output projection launch of a one-token step on its own: y[n_out] from one row x, w = [n_out][k_in] row-major.  packed = 0: the raw
@@ -3752,17 +3667,16 @@ extern "C" int lnb_op_rmsnorm_head(int device, const uint16_t* x, const uint16_t
     if (n_out <= 0 || k_in <= 0) return fail("empty operand");
     if (k_in % 8) return fail("in_features must be a multiple of 8");
     if (n_wg < 0) return fail("n_wg must not be negative");
-    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
-    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
+    if (op_device(device)) return -1;
     HIPCHK(lnbk_init());
     if (!lnbk_headp_supported(k_in)) return fail("in_features %d does not fit the LDS staging of the packed LM-head kernel", k_in);
+    DevArena a;
     TiledDesc t{}; int64_t bytes = 0;
-    if (alloc_tiled(t, n_out, k_in, 64, 1, bytes)) return -1;
+    if (alloc_tiled(a, t, n_out, k_in, 64, 1, bytes)) return -1;
     const size_t wn = (size_t)n_out * k_in * 2;
-    uint16_t *dx = nullptr, *dw = nullptr, *dy = nullptr, *dn = nullptr; StepState* st = nullptr; unsigned* dstats = nullptr; void* wp = nullptr;
-    HIPCHK(hipMalloc((void**)&dx, (size_t)k_in * 2)); HIPCHK(hipMalloc((void**)&dw, wn)); HIPCHK(hipMalloc((void**)&dn, (size_t)k_in * 2));
-    HIPCHK(hipMalloc((void**)&dy, (size_t)n_out * 2)); HIPCHK(hipMalloc((void**)&st, sizeof(StepState))); HIPCHK(hipMalloc((void**)&dstats, sizeof(WpackStats)));
+    uint16_t* dx = a.alloc<uint16_t>((size_t)k_in); uint16_t* dw = a.alloc<uint16_t>(wn / 2); uint16_t* dn = a.alloc<uint16_t>((size_t)k_in);
+    uint16_t* dy = a.alloc<uint16_t>((size_t)n_out); StepState* st = a.alloc<StepState>(1); unsigned* dstats = (unsigned*)a.alloc<WpackStats>(1); void* wp = nullptr;
+    HIPCHK(a.error());
     HIPCHK(hipMemset(st, 0, sizeof(StepState))); HIPCHK(hipMemset(dy, 0xFF, (size_t)n_out * 2));        // (a row the kernel does not write reads back as a NaN pattern)
     HIPCHK(hipMemcpy(dx, x, (size_t)k_in * 2, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dn, norm_w, (size_t)k_in * 2, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dw, w, wn, hipMemcpyHostToDevice)); HIPCHK(lnbk_tile(dw, t.w, n_out, k_in, 0, 0, 64, 1, 0, nullptr)); HIPCHK(hipDeviceSynchronize());
@@ -3774,7 +3688,7 @@ extern "C" int lnb_op_rmsnorm_head(int device, const uint16_t* x, const uint16_t
     GemvParams g{}; g.w = t.w; g.x = dx; g.norm_w = dn; g.eps = eps; g.K = k_in; g.n_rows = n_out; g.S = 1; g.st = st; g.out = dy;
     set_grid(g, t);
     if (packed && why == WPACK_OK) {
-        HIPCHK(hipMalloc(&wp, lnbk_wpack_head_bytes(n_out, k_in)));
+        if (arena_alloc(a, &wp, lnbk_wpack_head_bytes(n_out, k_in))) return -1;
         HIPCHK(lnbk_wpack_head(t.w, wp, n_out, k_in, base, nullptr));
         g.wp = wp; g.wp_base4 = base * 0x01010101u;
         g.n_blocks = (n_out + 127) / 128; g.n_wg = g.n_blocks < g_num_cus ? g.n_blocks : g_num_cus;
@@ -3786,25 +3700,21 @@ extern "C" int lnb_op_rmsnorm_head(int device, const uint16_t* x, const uint16_t
     }
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(y, dy, (size_t)n_out * 2, hipMemcpyDeviceToHost));
-    hipFree(dx); hipFree(dw); hipFree(dy); hipFree(dn); hipFree(st); hipFree(dstats); hipFree(t.w); if (wp) hipFree(wp);
     return 0;
 }
 // ml.Argmax (operations_impl.go:513-548) of one row of bf16 logits through argmax_kernel, the kernel of the greedy loop
 extern "C" int lnb_op_argmax(int device, const uint16_t* logits_bf16, int n, int32_t* out) {
     if (!logits_bf16 || !out) return fail("null argument");
     if (n <= 0) return fail("empty operand");
-    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
-    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
-    uint16_t* d = nullptr; int32_t* dn = nullptr; StepState* st = nullptr;
-    HIPCHK(hipMalloc((void**)&d, (size_t)n * 2 + 16)); HIPCHK(hipMalloc((void**)&dn, 16)); HIPCHK(hipMalloc((void**)&st, sizeof(StepState)));
+    if (op_device(device)) return -1;
+    DevArena a;
+    uint16_t* d = a.alloc<uint16_t>((size_t)n + 8); int32_t* dn = a.alloc<int32_t>(4); StepState* st = a.alloc<StepState>(1);
+    HIPCHK(a.error());
     HIPCHK(hipMemset(st, 0, sizeof(StepState)));
     HIPCHK(hipMemcpy(d, logits_bf16, (size_t)n * 2, hipMemcpyHostToDevice));
-    hipError_t e = lnbk_argmax(d, n, dn, st, nullptr, 0, 0, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out, dn, 4, hipMemcpyDeviceToHost);
-    hipFree(d); hipFree(dn); hipFree(st);
-    HIPCHK(e);
+    HIPCHK(lnbk_argmax(d, n, dn, st, nullptr, 0, 0, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, dn, 4, hipMemcpyDeviceToHost));
     return 0;
 }
 // token_probs_kernel on host rows (test aid): the records the greedy loop keeps, per row; targets (optional) as lnb_forward_score
@@ -3814,17 +3724,16 @@ extern "C" int lnb_op_token_probs(int device, const uint16_t* logits_bf16, int r
     if (rows <= 0 || V <= 0) return fail("empty operand");
     if (top_k < 0 || top_k > LNB_MAX_TOP_K) return fail("top_k must be 0..%d (got %d)", LNB_MAX_TOP_K, top_k);
     if (targets) for (int i = 0; i < rows; i++) if (targets[i] >= V) return fail("target id %d at index %d is outside the row of %d", targets[i], i, V);
-    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
-    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
+    if (op_device(device)) return -1;
     const size_t R = rows, K = top_k, G = lnb_tokprob_slices(rows);
     std::vector<double> et; prob_exp_table(et);
     const size_t o_et = align256(sizeof(TokProbOut)), o_x = o_et + align256(65536 * 8), o_z = o_x + align256(R * V * 2 + 16), o_k = o_z + align256(R * LNB_TOKPROB_MAX_G * 8),
                  o_cnt = o_k + align256(R * G * K * 8), o_ids = o_cnt + align256(R * 4), o_lg = o_ids + align256(R * K * 4), o_pr = o_lg + align256(R * K * 4),
                  o_lz = o_pr + align256(R * K * 4), o_tg = o_lz + align256(R * 8), o_tl = o_tg + align256(R * 4), o_tp = o_tl + align256(R * 4),
                  o_w = o_tp + align256(R * 4), need = o_w + 256;
-    char* b = nullptr;
-    HIPCHK(hipMalloc((void**)&b, need));
+    Dev<char> buf;
+    HIPCHK(dev_alloc(buf, need));
+    char* const b = buf;
     TokProbOut o{}; o.ids = (int32_t*)(b + o_ids); o.logit = (float*)(b + o_lg); o.prob = (float*)(b + o_pr); o.log_z = (double*)(b + o_lz); o.walks = (int*)(b + o_w); o.cap = rows;
     TokProbParams p{};
     p.logits = (const uint16_t*)(b + o_x); p.V = V; p.rows = rows; p.k = top_k; p.G = (int)G; p.etab = (const double*)(b + o_et);
@@ -3832,22 +3741,20 @@ extern "C" int lnb_op_token_probs(int device, const uint16_t* logits_bf16, int r
     if (targets) { p.targets = (const int32_t*)(b + o_tg); p.tlogit = (float*)(b + o_tl); p.tprob = (float*)(b + o_tp); }
     p.force_serial = force_serial ? 1 : 0;
     int walks = 0;
-    hipError_t e = hipMemcpy(b, &o, sizeof o, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b + o_et, et.data(), 65536 * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b + o_x, logits_bf16, R * V * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess && targets) e = hipMemcpy(b + o_tg, targets, R * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(b + o_cnt, 0, R * 4);
-    if (e == hipSuccess) e = hipMemset(b + o_w, 0, 4);
-    if (e == hipSuccess) e = lnbk_token_probs(&p, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && K) e = hipMemcpy(ids, b + o_ids, R * K * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && K) e = hipMemcpy(logits, b + o_lg, R * K * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && K) e = hipMemcpy(probs, b + o_pr, R * K * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(log_z, b + o_lz, R * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && targets) e = hipMemcpy(target_prob, b + o_tp, R * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(&walks, b + o_w, 4, hipMemcpyDeviceToHost);
-    hipFree(b);
-    HIPCHK(e);
+    HIPCHK(hipMemcpy(b, &o, sizeof o, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_et, et.data(), 65536 * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_x, logits_bf16, R * V * 2, hipMemcpyHostToDevice));
+    if (targets) HIPCHK(hipMemcpy(b + o_tg, targets, R * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(b + o_cnt, 0, R * 4));
+    HIPCHK(hipMemset(b + o_w, 0, 4));
+    HIPCHK(lnbk_token_probs(&p, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (K) HIPCHK(hipMemcpy(ids, b + o_ids, R * K * 4, hipMemcpyDeviceToHost));
+    if (K) HIPCHK(hipMemcpy(logits, b + o_lg, R * K * 4, hipMemcpyDeviceToHost));
+    if (K) HIPCHK(hipMemcpy(probs, b + o_pr, R * K * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(log_z, b + o_lz, R * 8, hipMemcpyDeviceToHost));
+    if (targets) HIPCHK(hipMemcpy(target_prob, b + o_tp, R * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&walks, b + o_w, 4, hipMemcpyDeviceToHost));
     if (serial_walks) *serial_walks = walks;
     return 0;
 }
@@ -3859,27 +3766,24 @@ extern "C" int lnb_op_sample(int device, const uint16_t* logits_bf16, int rows, 
     if (sample_vocab_check(V)) return -1;
     char who[32];
     for (int i = 0; i < rows; i++) { snprintf(who, sizeof who, "row %d: ", i); if (sampler_check(samplers + i, who)) return -1; }
-    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
-    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
+    if (op_device(device)) return -1;
     const size_t R = rows;
     std::vector<double> et; prob_exp_table(et);
     const size_t o_x = align256(65536 * 8), o_s = o_x + align256(R * V * 2 + 16), o_p = o_s + align256(R * sizeof(LnbSampler)), o_u = o_p + align256(R * 4),
                  o_t = o_u + align256(R * 8), o_i = o_t + align256(R * 4), need = o_i + align256(R * sizeof(LnbSampleInfo));
-    char* b = nullptr;
-    HIPCHK(hipMalloc((void**)&b, need));
-    hipError_t e = hipMemcpy(b, et.data(), 65536 * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b + o_x, logits_bf16, R * V * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b + o_s, samplers, R * sizeof(LnbSampler), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b + o_p, pos, R * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && draws) e = hipMemcpy(b + o_u, draws, R * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = lnbk_sample((const uint16_t*)(b + o_x), V, rows, (const double*)b, (const LnbSampler*)(b + o_s), (int32_t*)(b + o_t), nullptr, nullptr, 0, 0,
-                                         (const int32_t*)(b + o_p), draws ? (const unsigned long long*)(b + o_u) : nullptr, info ? (LnbSampleInfo*)(b + o_i) : nullptr, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(tokens_out, b + o_t, R * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && info) e = hipMemcpy(info, b + o_i, R * sizeof(LnbSampleInfo), hipMemcpyDeviceToHost);
-    hipFree(b);
-    HIPCHK(e);
+    Dev<char> buf;
+    HIPCHK(dev_alloc(buf, need));
+    char* const b = buf;
+    HIPCHK(hipMemcpy(b, et.data(), 65536 * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_x, logits_bf16, R * V * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_s, samplers, R * sizeof(LnbSampler), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_p, pos, R * 4, hipMemcpyHostToDevice));
+    if (draws) HIPCHK(hipMemcpy(b + o_u, draws, R * 8, hipMemcpyHostToDevice));
+    HIPCHK(lnbk_sample((const uint16_t*)(b + o_x), V, rows, (const double*)b, (const LnbSampler*)(b + o_s), (int32_t*)(b + o_t), nullptr, nullptr, 0, 0,
+                       (const int32_t*)(b + o_p), draws ? (const unsigned long long*)(b + o_u) : nullptr, info ? (LnbSampleInfo*)(b + o_i) : nullptr, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(tokens_out, b + o_t, R * 4, hipMemcpyDeviceToHost));
+    if (info) HIPCHK(hipMemcpy(info, b + o_i, R * sizeof(LnbSampleInfo), hipMemcpyDeviceToHost));
     return 0;
 }
 // spec_sample_commit_kernel on host rows (test aid): the w columns of a verify pass whose column i holds logits row i, takes col_tokens[i] and sits at
@@ -3891,15 +3795,14 @@ extern "C" int lnb_op_spec_sample_accept(int device, const uint16_t* logits_bf16
     if (sample_vocab_check(V)) return -1;
     if (sampler_check(sampler, "")) return -1;
     if (pos0 < 0 || n_stop < 0 || n_stop > LNB_MAX_STOP_IDS) return fail("bad arguments: pos0 %d, %d stop ids (at most %d)", pos0, n_stop, LNB_MAX_STOP_IDS);
-    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
-    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
+    if (op_device(device)) return -1;
     const size_t W = w;
     std::vector<double> et; prob_exp_table(et);
     const size_t o_x = align256(65536 * 8), o_s = o_x + align256(W * V * 2 + 16), o_st = o_s + align256(sizeof(LnbSampler)), o_tok = o_st + align256(W * sizeof(StepState)),
                  o_g = o_tok + align256(W * 4), o_log = o_g + align256(W * 4), o_tab = o_log + align256(W * 4), o_cnt = o_tab + align256(sizeof(BatchTab)), need = o_cnt + 256;
-    char* b = nullptr;
-    HIPCHK(hipMalloc((void**)&b, need));
+    Dev<char> buf;
+    HIPCHK(dev_alloc(buf, need));
+    char* const b = buf;
     std::vector<StepState> hst(W, StepState{});
     for (int i = 0; i < w; i++) hst[i].pos = pos0 + i;
     hst[0].n_stop = n_stop; hst[0].honour_stop = 1;
@@ -3907,20 +3810,18 @@ extern "C" int lnb_op_spec_sample_accept(int device, const uint16_t* logits_bf16
     std::vector<BatchTab> tab(1, BatchTab{});
     for (int i = 0; i < w; i++) { tab[0].st[i] = (StepState*)(b + o_st) + i; tab[0].dtok[i] = (int32_t*)(b + o_tok) + i; }
     tab[0].dout[0] = (int32_t*)(b + o_log); tab[0].dout_cap[0] = w; tab[0].n = w;
-    hipError_t e = hipMemset(b + o_g, 0, need - o_g);
-    if (e == hipSuccess) e = hipMemcpy(b, et.data(), 65536 * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b + o_x, logits_bf16, W * V * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b + o_s, sampler, sizeof(LnbSampler), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b + o_st, hst.data(), W * sizeof(StepState), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b + o_tok, col_tokens, W * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b + o_tab, tab.data(), sizeof(BatchTab), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = lnbk_spec_sample_commit((const uint16_t*)(b + o_x), V, w, (const double*)b, (const LnbSampler*)(b + o_s), (int32_t*)(b + o_g),
-                                                     (const BatchTab*)(b + o_tab), (unsigned*)(b + o_cnt), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(hst.data(), b + o_st, sizeof(StepState), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(emitted, b + o_log, W * 4, hipMemcpyDeviceToHost);
-    hipFree(b);
-    HIPCHK(e);
+    HIPCHK(hipMemset(b + o_g, 0, need - o_g));
+    HIPCHK(hipMemcpy(b, et.data(), 65536 * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_x, logits_bf16, W * V * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_s, sampler, sizeof(LnbSampler), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_st, hst.data(), W * sizeof(StepState), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_tok, col_tokens, W * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_tab, tab.data(), sizeof(BatchTab), hipMemcpyHostToDevice));
+    HIPCHK(lnbk_spec_sample_commit((const uint16_t*)(b + o_x), V, w, (const double*)b, (const LnbSampler*)(b + o_s), (int32_t*)(b + o_g),
+                                   (const BatchTab*)(b + o_tab), (unsigned*)(b + o_cnt), nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(hst.data(), b + o_st, sizeof(StepState), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(emitted, b + o_log, W * 4, hipMemcpyDeviceToHost));
     if (hst[0].n_out < 1 || hst[0].n_out > w) return fail("internal error: a pass of %d columns emitted %d tokens", w, hst[0].n_out);
     *n_emitted = hst[0].n_out;
     if (finished) *finished = hst[0].finished;
@@ -3929,16 +3830,12 @@ extern "C" int lnb_op_spec_sample_accept(int device, const uint16_t* logits_bf16
 extern "C" int lnb_op_exp_table(int device, float divisor, double* out65536) {
     if (!out65536) return fail("null argument");
     if (!(divisor > 0.0f)) return fail("divisor must be positive");
-    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
-    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
-    double* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, (size_t)65536 * 8));
-    hipError_t e = lnbk_exp_table(d, divisor, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out65536, d, (size_t)65536 * 8, hipMemcpyDeviceToHost);
-    hipFree(d);
-    HIPCHK(e);
+    if (op_device(device)) return -1;
+    Dev<double> d;
+    HIPCHK(dev_alloc(d, (size_t)65536 * 8));
+    HIPCHK(lnbk_exp_table(d, divisor, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out65536, d, (size_t)65536 * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 // What the norm of a kernel form computed (include/lnb.h): each form through its own launch function, in the kernel's REPORT instantiation -- the production
@@ -3948,9 +3845,7 @@ extern "C" int lnb_op_rmsnorm_sum(int device, const uint16_t* x, int rows, int k
     if (rows <= 0 || k_in <= 0) return fail("empty operand");
     if (k_in % 8) return fail("in_features must be a multiple of 8");
     if (form < 0 || form >= LNB_NORM_FORMS) return fail("unknown norm form %d", form);
-    int ndev = 0; HIPCHK(hipGetDeviceCount(&ndev));
-    if (ndev == 0) return fail("no HIP device: liblnb_hip.so has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
+    if (op_device(device)) return -1;
     HIPCHK(lnbk_init());
     if (form == LNB_NORM_BATCH_XT) HIPCHK(lnbk_batch_prepare());
     const bool alone = form == LNB_NORM_ROWS_WIDE || form == LNB_NORM_BATCH_XT || form == LNB_NORM_ROWS_WAVE;
@@ -3963,32 +3858,38 @@ extern "C" int lnb_op_rmsnorm_sum(int device, const uint16_t* x, int rows, int k
     if (form == LNB_NORM_GATE_UP56_PACKED && !lnbk_w13p_supported(56, k_in)) return 1;
     if (form == LNB_NORM_HEAD_PACKED && !lnbk_headp_supported(k_in)) return 1;
     const size_t out_rows = alone ? (size_t)((rows + 15) & ~15) : 15;      // (batch_rmsnorm_xt_kernel<true> writes whole groups of 16 columns)
-    uint16_t *dx = nullptr, *dn = nullptr, *dy = nullptr; uint32_t* dno = nullptr; StepState* st = nullptr; float* dsilu = nullptr; void* wp = nullptr;
-    TiledDesc t{}; int64_t bytes = 0;
     std::vector<uint16_t> ones((size_t)k_in, (uint16_t)0x3F80);
     std::vector<uint32_t> got((size_t)rows * 3);
-    hipError_t e = hipSuccess;
-    int rc = -1;
-    do {
-        if ((e = hipMalloc((void**)&dx, (size_t)rows * k_in * 2)) != hipSuccess || (e = hipMalloc((void**)&dn, (size_t)k_in * 2)) != hipSuccess ||
-            (e = hipMalloc((void**)&dy, out_rows * (size_t)(alone ? k_in : n_out) * 2)) != hipSuccess || (e = hipMalloc((void**)&dno, got.size() * 4)) != hipSuccess ||
-            (e = hipMalloc((void**)&st, sizeof(StepState))) != hipSuccess) break;
-        if ((e = hipMemset(st, 0, sizeof(StepState))) != hipSuccess || (e = hipMemset(dno, 0, got.size() * 4)) != hipSuccess ||      // (the walker ADDS its path word)
-            (e = hipMemcpy(dx, x, (size_t)rows * k_in * 2, hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy(dn, ones.data(), (size_t)k_in * 2, hipMemcpyHostToDevice)) != hipSuccess) break;
+    DevArena a;
+    // the launches; a runtime error comes back as its code (refused: the launch function does not take this K)
+    bool refused = false;
+    auto run = [&]() -> hipError_t {
+        uint16_t* dx = a.alloc<uint16_t>((size_t)rows * k_in); uint16_t* dn = a.alloc<uint16_t>((size_t)k_in);
+        uint16_t* dy = a.alloc<uint16_t>(out_rows * (size_t)(alone ? k_in : n_out)); uint32_t* dno = a.alloc<uint32_t>(got.size());
+        StepState* st = a.alloc<StepState>(1);
+        hipError_t e = a.error();
+        if (e == hipSuccess) e = hipMemset(st, 0, sizeof(StepState));
+        if (e == hipSuccess) e = hipMemset(dno, 0, got.size() * 4);                     // (the walker ADDS its path word)
+        if (e == hipSuccess) e = hipMemcpy(dx, x, (size_t)rows * k_in * 2, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dn, ones.data(), (size_t)k_in * 2, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return e;
         if (alone) {
             e = form == LNB_NORM_BATCH_XT ? lnbk_batch_rmsnorm_out(dx, dn, eps, dy, k_in, rows, dno, nullptr)
                                           : lnbk_rmsnorm_rows_form(dx, dn, dy, rows, k_in, eps, form == LNB_NORM_ROWS_WIDE ? 1 : 2, dno, nullptr);
         } else {
-            if (alloc_tiled(t, n_out, k_in, rw, nch, bytes)) { e = hipErrorOutOfMemory; break; }
-            if (nch == 2) { if ((e = hipMalloc((void**)&dsilu, (size_t)65536 * 4)) != hipSuccess || (e = hipMemset(dsilu, 0, (size_t)65536 * 4)) != hipSuccess) break; }
+            TiledDesc t{}; int64_t bytes = 0; float* dsilu = nullptr;
+            if (alloc_tiled(a, t, n_out, k_in, rw, nch, bytes)) return hipErrorOutOfMemory;
+            if (nch == 2) {
+                if (!(dsilu = a.alloc<float>(65536))) return a.error();
+                if ((e = hipMemset(dsilu, 0, (size_t)65536 * 4)) != hipSuccess) return e;
+            }
             GemvParams g{}; g.w = t.w; g.norm_w = dn; g.eps = eps; g.K = k_in; g.n_rows = n_out; g.st = st; g.out = dy; g.silu = dsilu;
             g.n_blocks = 1; g.n_wg = 1; g.sched = form == LNB_NORM_QUAD24_SCHED ? 1 : 0;
             if (packed) {                                                 // the 13-bit copy of the zero matrix (window base 0)
-                const size_t n = form == LNB_NORM_HEAD_PACKED ? lnbk_wpack_head_bytes(n_out, k_in) : lnbk_wpack_w13_bytes(1, k_in);
-                if ((e = hipMalloc(&wp, n)) != hipSuccess) break;
+                void* wp = a.alloc<char>(form == LNB_NORM_HEAD_PACKED ? lnbk_wpack_head_bytes(n_out, k_in) : lnbk_wpack_w13_bytes(1, k_in));
+                if (!wp) return a.error();
                 e = form == LNB_NORM_HEAD_PACKED ? lnbk_wpack_head(t.w, wp, n_out, k_in, 0, nullptr) : lnbk_wpack_w13(t.w, wp, k_in, 1, 0, nullptr);
-                if (e != hipSuccess) break;
+                if (e != hipSuccess) return e;
                 g.wp = wp; g.wp_base4 = 0;
             }
             const int per = packed ? 1 : 15;                              // rows per launch, as production launches them
@@ -3997,15 +3898,16 @@ extern "C" int lnb_op_rmsnorm_sum(int device, const uint16_t* x, int rows, int k
                 e = lnbk_gemv_norm_report(&g, form, nullptr);
             }
         }
-        if (e == hipErrorInvalidValue) { rc = 1; e = hipSuccess; break; }  // the launch function refuses this K
-        if (e != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) break;
-        if ((e = hipMemcpy(got.data(), dno, got.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess) break;
-        for (int r = 0; r < rows; r++) { sum_bits[r] = got[(size_t)r * 3]; scale_bits[r] = got[(size_t)r * 3 + 1]; walk[r] = (int32_t)got[(size_t)r * 3 + 2]; }
-        rc = 0;
-    } while (0);
-    hipFree(dx); hipFree(dn); hipFree(dy); hipFree(dno); hipFree(st); if (dsilu) hipFree(dsilu); if (wp) hipFree(wp); if (t.w) hipFree(t.w);
+        if (e == hipErrorInvalidValue) { refused = true; return hipSuccess; }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(got.data(), dno, got.size() * 4, hipMemcpyDeviceToHost);
+        return e;
+    };
+    const hipError_t e = run();
     if (e != hipSuccess) return fail("lnb_op_rmsnorm_sum: %s", hipGetErrorString(e));
-    return rc;
+    if (refused) return 1;
+    for (int r = 0; r < rows; r++) { sum_bits[r] = got[(size_t)r * 3]; scale_bits[r] = got[(size_t)r * 3 + 1]; walk[r] = (int32_t)got[(size_t)r * 3 + 2]; }
+    return 0;
 }
 extern "C" int lnb_op_linear(int device, const uint16_t* x, const uint16_t* w, uint16_t* y, int rows, int n_out, int k_in, int rw) {
     return op_linear_impl(device, x, nullptr, 0.0f, w, y, rows, n_out, k_in, rw);

@@ -504,6 +504,114 @@ def test_lifecycle_contexts_models_and_pipes_give_their_device_memory_back(lnb, 
         (before - mid) / 1048576.0, (mid - after) / 1048576.0)
 
 
+def test_lifecycle_batches_speculation_appends_and_single_ops_give_their_device_memory_back(lnb, tiny_pair):
+    """The object kinds the test above does not create: a Batch with token probabilities in both attention forms, the verify batches of a
+    speculating context (two widths, the greedy and the sampling graph family, long graphs dropped by a changed force_zseq and captured again), the
+    model-owned tables of ForwardAppendMany / DecodeSpeculativeMany, the fork table, a saved prefix, the score scratch, and every single-op entry point
+    with its per-call buffers.  Every round computes what round 1 computed; 25 rounds, then 8 models, may each cost at most 4 MiB of device memory."""
+    om, gm = tiny_pair
+    V, P = TINY["vocab_size"], 10
+    prompt = orc.synth_tokens(31, P, V)
+    ref, _ = orc.Context(om, 64).generate(prompt, 13)
+    ref = [int(v) for v in ref]
+    text = [int(t) for t in prompt] + ref                                  # the corpus of the drafts: the greedy continuation itself
+    rng = np.random.default_rng(11)
+    K = 256
+    x1, x16, nw = bf(rng.standard_normal((1, K))), bf(rng.standard_normal((16, K))), bf(1 + 0.1 * rng.standard_normal(K))
+    w48, w112a, w112b, w128 = (bf(rng.standard_normal((n, K)) * 0.05) for n in (48, 112, 112, 128))
+    rows2 = bf(rng.standard_normal((2, V)))
+    smp = (0.8, 0, 1.0, 5)
+
+    def at_prompt(seq_len=64):
+        c = lnb.InferenceContext(gm, seq_len)
+        _, first = c.Forward(prompt, 0, want_logits=False)
+        assert first == ref[0]
+        return c
+
+    def one_round():
+        out = []
+        # a batch of three with token probabilities, short form then long form
+        cs = [at_prompt().set_token_probs(2) for _ in range(3)]
+        b = lnb.Batch(cs)
+        t1, _ = b.decode_until([ref[0]] * 3, [P] * 3, 4)
+        b.set_attention(0, 0)
+        t2, _ = b.decode_until([ref[4]] * 3, [P + 4] * 3, 4)
+        assert b.attention_form() == 1
+        for s in range(3):
+            assert [int(t) for t in t1[s]] + [int(t) for t in t2[s]] == ref[1:9], s
+        out.append([a.tolist() for a in cs[1].token_probs(4)])
+        b.close()
+        for c in cs:
+            c.close()
+        # a speculating context: verify batches of two widths, greedy and sampling, short and long form, long graphs dropped and captured again
+        sc = at_prompt()
+        for draft in (3, 2):
+            sc.set_draft(draft, 1, 2, corpus=text)
+            g, _, st, _ = sc.decode_speculative_until(prompt, ref[0], P, 8)
+            assert [int(t) for t in g] == ref[1:9] and st["verify_passes"] > 0 and st["accepted"] > 0, (draft, st)
+            # a pass drafts at most `draft` tokens: more than (draft - 1) per pass on average means a pass of width draft + 1 ran -- widths 4 and 3
+            assert (draft - 1) * st["verify_passes"] < st["drafted"] <= draft * st["verify_passes"], (draft, st)
+            s, _, st, _ = sc.decode_speculative_sample_until(smp, prompt, ref[0], P, 8)
+            assert st["verify_passes"] > 0, (draft, st)
+            out.append(s.tolist())
+        for force in (0, 1):                                               # (0: the threshold alone picks the long form; 1: its graphs go and come back)
+            sc.set_batched_attention(0, force)
+            g, _, st, _ = sc.decode_speculative_until(prompt, ref[0], P, 8)
+            assert [int(t) for t in g] == ref[1:9] and st["verify_passes"] > 0 and sc.verify_attention_form() == 1, (force, st)
+            s, _, _, _ = sc.decode_speculative_sample_until(smp, prompt, ref[0], P, 8)
+            out.append(s.tolist())
+        sc.close()
+        # the model-owned tables of the many-context calls, the fork table, a saved prefix, the score scratch
+        a, c7 = lnb.InferenceContext(gm, 64), lnb.InferenceContext(gm, 64)
+        lg, am = lnb.ForwardAppendMany([a, c7], [prompt, prompt[:7]], [0, 0], want_logits=True)
+        assert int(am[0]) == ref[0]
+        a.set_draft(3, 1, 2, corpus=text)
+        toks, _, _, info, _ = lnb.DecodeSpeculativeMany([a, c7], [prompt, prompt[:7]], [int(am[0]), int(am[1])], [P, 7], 5)
+        assert [int(t) for t in toks[0]] == ref[1:6] and info["passes"] > 0
+        out += [lg[1][-1].tolist(), toks[1].tolist()]
+        d, e = lnb.InferenceContext(gm, 48), lnb.InferenceContext(gm, 64)
+        a.ForkPrefix([d], P)
+        assert e.LoadPrefix(a.SavePrefix(P)) == P
+        for c in (d, e):
+            got, _ = c.decode_greedy(ref[0], P, 3)
+            assert [int(t) for t in got] == ref[1:4]
+        tl, tp, lz, last = e.score(prompt, 0, np.roll(prompt, -1))
+        assert last == ref[0]
+        out += [tl.tolist(), tp.tolist(), lz.tolist()]
+        for c in (a, c7, d, e):
+            c.close()
+        # the single-op entry points: every buffer of a call goes with the call
+        out += [lnb.op_linear(x1, w48).tolist(), lnb.op_linear(x16, w48).tolist(), lnb.op_rmsnorm_linear(x1, nw, 1e-5, w48).tolist(),
+                lnb.op_rmsnorm_gate_up(x1[0], nw, 1e-5, w112a, w112b)[0].tolist(), lnb.op_rmsnorm_head(x1[0], nw, 1e-5, w128)[0].tolist()]
+        for x, form in ((x1, "chain16"), (x16, "rows_wide")):              # one fused form, one row form
+            sums = lnb.op_rmsnorm_sum(x, 1e-5, form)
+            assert sums is not None
+            out.append([v.tolist() for v in sums])
+        pr = lnb.op_token_probs(rows2, 2)
+        out += [lnb.op_argmax(rows2[0]), lnb.op_sample(rows2, [smp, smp], [3, 4])[0].tolist(), pr["ids"].tolist(), pr["log_z"].tolist(),
+                lnb.op_spec_sample_accept(rows2, smp, 3, [7, 9])[0].tolist(), lnb.op_exp_table(1.0)[:4096:97].tolist()]
+        return out
+
+    first_round = one_round()                                              # warm-up: code objects, allocator pools, the model's AppendMany / SpecMany
+    assert one_round() == first_round
+    before = _device_free_bytes()
+    for i in range(25):
+        assert one_round() == first_round, i
+    mid = _device_free_bytes()
+    for _ in range(8):
+        m2 = lnb.LlamaTransformer(**TINY).fill_synthetic(7).finalize()
+        m2.enable_batch()
+        c2 = lnb.InferenceContext(m2, 32)
+        c2.set_draft(2, 1, 2, corpus=text)
+        _, am = lnb.ForwardAppendMany([c2], [prompt], [0], want_logits=False)
+        lnb.DecodeSpeculativeMany([c2], [prompt], [int(am[0])], [P], 3)     # (the model-owned SpecMany exists too)
+        c2.close(); m2.close()
+    after = _device_free_bytes()
+    print("device memory lost: %.1f MB over 25 rounds, %.1f MB over 8 models" % ((before - mid) / 1048576.0, (mid - after) / 1048576.0))
+    assert before - mid <= 4 << 20 and mid - after <= 4 << 20, "device memory not returned: %.1f MB over 25 rounds, %.1f MB over 8 models" % (
+        (before - mid) / 1048576.0, (mid - after) / 1048576.0)
+
+
 def test_tiny_device_greedy_loop_matches_oracle(lnb, tiny_pair):
     om, gm = tiny_pair
     prompt = orc.synth_tokens(5, 9, TINY["vocab_size"])
