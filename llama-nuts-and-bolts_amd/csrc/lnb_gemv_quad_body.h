@@ -1,9 +1,10 @@
-// The body of gemv_quad_kernel (lnb_kernels.hip), included once per kernel: LNB_QUAD_REPORT false in the production kernel, true in gemv_quad_report_kernel
+// The body of gemv_quad_kernel (lnb_kernels.hip), included once per kernel: LNB_QUAD_REPORT false in the production kernel, true in gemv_quad_report_kernel.
+// TIMING (a constant of the including kernel): true in the instantiation launched when GemvParams.dbg is set -- the stamps and timed barriers exist only there
 // (the norm's report compiled in, lnb_op_rmsnorm_sum).  Text, not a function: routed through an inlined body function hipcc allocated the production
 // kernels' registers differently, and their code is to stay what it was.  No include guard: it is meant to be included twice.
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    long long t_begin = p.dbg ? clock64() : 0, t_wait = 0, t_x = 0, t_aux = 0;
-    const long long t_wall0 = p.dbg ? (long long)wall_clock64() : 0;
+    long long t_begin = LNB_DBG ? clock64() : 0, t_wait = 0, t_x = 0, t_aux = 0;
+    const long long t_wall0 = LNB_DBG ? (long long)wall_clock64() : 0;
     constexpr int NCW = gq_ncw(RW), NW = NCW + NH;
     constexpr int KC = KS / 8;                            // 8-wide k chunks per stage
     constexpr int GS = KS / 16;                           // 16-step groups per stage
@@ -59,7 +60,7 @@
         TIMED_BARRIER();                                               // B1: xs (or the squares) are in LDS
         if (NORM) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            rms_fold<rms_nf(NH), LNB_QUAD_REPORT>(p, xs, ringB, hw < rms_nf(NH) ? hw : -1, lane, t_aux);      // X1, X2 inside; the first four helpers fold (four consecutive waves: four SIMDs)
+            rms_fold<rms_nf(NH), LNB_QUAD_REPORT, TIMING>(p, xs, ringB, hw < rms_nf(NH) ? hw : -1, lane, t_aux);      // X1, X2 inside; the first four helpers fold (four consecutive waves: four SIMDs)
             {                                                          // the walker walks now: the issue stall costs nothing here
 #pragma unroll
                 for (int j = EARLY; j < R; j++) issue_next(buf[j]);
@@ -87,9 +88,9 @@
                 const int t = it0 + j;
                 if (t <= T + 1) {
                     if (t < T) {
-                        const long long tb_ = p.dbg_full ? clock64() : 0;
+                        const long long tb_ = LNB_DBG_FULL ? clock64() : 0;
                         wait_ring<(R - 1) * NP, NP>(buf[j]);           // stage t landed; R-1 younger stages stay in flight
-                        if (p.dbg_full) t_x += clock64() - tb_;
+                        if (LNB_DBG_FULL) t_x += clock64() - tb_;
                         char* dst = ringB + (size_t)(t % GQ_SLOTS) * SB;
                         const float* xst = xs + (size_t)st * KS;
                         float4 xa[NP], xb[NP];
@@ -129,8 +130,38 @@
         LNB_STAMP(2);
         if (NORM) {
             float r;
+#ifdef LNB_PROBE_WARM_XNORM
+            // measurement only (tools/build_variant.sh warm -DLNB_PROBE_WARM_XNORM, profiles/prologue_fetch.md): the chain waves that idle until the walker is done run
+            // the ONE copy of the x_normalize code below twice -- first with r = 1 into the third product slot (unused until B3), so that the real pass behind B2
+            // finds its instructions fetched.  `warm` is opaque to the compiler: a peeled first pass would be a second copy of the code and warm nothing.
+            int warm = __builtin_amdgcn_readfirstlane((wave != 0 && kpad * 4 <= SB) ? 1 : 0), warmed = 0;
+            asm volatile("" : "+s"(warm));
+            float* xdst = xs;
+            for (;;) {
+                if (warm) {
+                    __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier();     // X1, X2
+                    r = 1.0f; xdst = (float*)(ringB + 2 * SB); warmed = 1;
+                } else if (wave == 0) {
+                    r = rms_scale_wide<rms_nf(NH), LNB_QUAD_REPORT ? 2 : 0, TIMING>(p, xs, ringB, lane, t_aux);     // X1, X2 inside
+                    LNB_STAMP(3);
+                    if (lane == 0) xs[kpad] = r;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    TIMED_BARRIER();                                   // B2
+                    LNB_STAMP(4);
+                } else {
+                    if (!warmed) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); }     // X1, X2
+                    TIMED_BARRIER();                                   // B2
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                    r = xs[kpad]; xdst = xs;
+                    LNB_STAMP(4);
+                }
+                x_normalize<NS>(p, xdst, kpad, r, wave, lane, xv, nv);
+                if (!warm) break;
+                warm = 0;
+            }
+#else
             if (wave == 0) {
-                r = rms_scale_wide<rms_nf(NH), LNB_QUAD_REPORT ? 2 : 0>(p, xs, ringB, lane, t_aux);     // X1, X2 inside
+                r = rms_scale_wide<rms_nf(NH), LNB_QUAD_REPORT ? 2 : 0, TIMING>(p, xs, ringB, lane, t_aux);     // X1, X2 inside
                 LNB_STAMP(3);
                 if (lane == 0) xs[kpad] = r;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -143,6 +174,7 @@
                 r = xs[kpad];
             }
             if constexpr (NORM) x_normalize<NS>(p, xs, kpad, r, wave, lane, xv, nv);
+#endif
             LNB_STAMP(5);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             TIMED_BARRIER();                                           // B3
@@ -150,7 +182,7 @@
             LNB_STAMP(6);
         }
     }
-    if (p.dbg) { t_x = clock64() - t_begin; t_wait = 0; }              // (chain waves report the barrier wait of the main loop only)
+    if (LNB_DBG) { t_x = clock64() - t_begin; t_wait = 0; }              // (chain waves report the barrier wait of the main loop only)
     __builtin_amdgcn_s_setprio(3);
     constexpr int last_rows = RW - 16 * (NCW - 1);                     // rows of the last chain wave
     const int rows_here = wave == NCW - 1 ? last_rows : 16;

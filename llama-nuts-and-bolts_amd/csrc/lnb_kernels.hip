@@ -215,9 +215,10 @@ DEVINL float rms_tree16(const float (&tv)[16]) {
     return (((tv[0] + tv[1]) + (tv[2] + tv[3])) + ((tv[4] + tv[5]) + (tv[6] + tv[7]))) + (((tv[8] + tv[9]) + (tv[10] + tv[11])) + ((tv[12] + tv[13]) + (tv[14] + tv[15])));
 }
 // REPORT (the instantiations lnb_op_rmsnorm_sum launches, never production's): the wave's flag word says WHY the row takes the record walk
-template <int NH, bool REPORT = false> DEVINL void rms_fold(const GemvParams& p, const float* xs, char* scratch, int hw, int lane, long long& t_dbg) {
+// TIMING (the instantiations launched with GemvParams.dbg set, never production's): the fold / walk time goes to t_dbg; false: no clock read, no dbg branch
+template <int NH, bool REPORT = false, bool TIMING = false> DEVINL void rms_fold(const GemvParams& p, const float* xs, char* scratch, int hw, int lane, long long& t_dbg) {
     if (hw < 0) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); return; }      // a helper that does not fold: X1, X2
-    const long long tf0_ = p.dbg ? clock64() : 0;
+    const long long tf0_ = (TIMING && p.dbg) ? clock64() : 0;
     const int LEAF = seq_leaf_size(p.K, NH * 64), nleaf = (p.K + LEAF - 1) / LEAF;
     SeqNode* rec = (SeqNode*)scratch;
     unsigned long long* items = (unsigned long long*)(scratch + (size_t)NH * 512);
@@ -321,7 +322,7 @@ template <int NH, bool REPORT = false> DEVINL void rms_fold(const GemvParams& p,
     rec[hw * 64 + lane] = n;
     { const unsigned long long fm = __ballot(failed != 0); if (lane == 0) ((uint32_t*)(scratch + (size_t)NH * 524))[hw] = fm ? 1u : 0u; }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (p.dbg) t_dbg = clock64() - tf0_;                                 // fold time incl. the X1 wait
+    if (TIMING && p.dbg) t_dbg = clock64() - tf0_;                       // fold time incl. the X1 wait
     __builtin_amdgcn_s_barrier();                                        // X2: records published
 }
 
@@ -410,7 +411,7 @@ DEVINL uint32_t rms_walk_fast(uint32_t sb, const SeqNode& rc, unsigned long long
 template <int NH> DEVINL void rms_report_park(const GemvParams& p, char* scratch, int row, int lane) {
     if (lane == 0) *(uint32_t* volatile*)(scratch + rms_scratch_bytes(NH) - 64) = (p.norm_out && row >= 0) ? p.norm_out + (size_t)row * 3 : nullptr;
 }
-template <int NH, int REPORT = 0> DEVINL float rms_scale_wide(const GemvParams& p, const float* xs, const char* scratch, int lane, long long& t_dbg, uint32_t* o = nullptr) {
+template <int NH, int REPORT = 0, bool TIMING = false> DEVINL float rms_scale_wide(const GemvParams& p, const float* xs, const char* scratch, int lane, long long& t_dbg, uint32_t* o = nullptr) {
     const int K = p.K, LEAF = seq_leaf_size(K, NH * 64), nleaf = (K + LEAF - 1) / LEAF;
     const SeqNode* rec = (const SeqNode*)scratch;
     const unsigned long long* items = (const unsigned long long*)(scratch + (size_t)NH * 512);
@@ -422,7 +423,7 @@ template <int NH, int REPORT = 0> DEVINL float rms_scale_wide(const GemvParams& 
     __builtin_amdgcn_s_barrier();                                        // X2 (the records)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     uint32_t sb = (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(sum));
-    const long long tw0_ = p.dbg ? clock64() : 0;
+    const long long tw0_ = (TIMING && p.dbg) ? clock64() : 0;
     int cnt = 0;
     // ---- the row's item list (rms_fold), walked WITHOUT a branch per item -------------------------------------------------------
     // lane w < NH: wave w's item count and "something uncovered" flag; lane g: global item g, fetched from its wave's list segment
@@ -502,7 +503,7 @@ template <int NH, int REPORT = 0> DEVINL float rms_scale_wide(const GemvParams& 
             else sb = rms_walk_fast(sb, rc[w], ((unsigned long long)hi32 << 32) | lo32, pos, nloc, xs + (size_t)w * 64 * LEAF, LEAF, cnt);
         }
     }
-    if (p.dbg) t_dbg = clock64() - tw0_;                                 // walk time
+    if (TIMING && p.dbg) t_dbg = clock64() - tw0_;                       // walk time
     if constexpr (REPORT == 2) o = *(uint32_t* volatile*)(scratch + rms_scratch_bytes(NH) - 64);
     // (one scalar branch and selects behind it: every lane mask held across this block is a pair of scalar registers)
     if (REPORT && (__builtin_amdgcn_readfirstlane((int)(uintptr_t)o) | __builtin_amdgcn_readfirstlane((int)((uintptr_t)o >> 32))) != 0) {
@@ -523,7 +524,7 @@ template <int NH, int REPORT = 0> DEVINL float rms_scale_wide(const GemvParams& 
         atomicAdd(o + 2, val);
     }
     if (!done) cnt = why;
-    if (p.dbg && lane == 0) p.dbg[(size_t)4096 * 8 * 4 + ((size_t)blockIdx.x * 8 + 0) * 8 + 7] = cnt;   // stamp slot 7 of the walker: items << 16 | (old walk: 1 + ...)
+    if (TIMING && p.dbg && lane == 0) p.dbg[(size_t)4096 * 8 * 4 + ((size_t)blockIdx.x * 8 + 0) * 8 + 7] = cnt;   // stamp slot 7 of the walker: items << 16 | (old walk: 1 + ...)
     float mean = __fdiv_rn(__uint_as_float(sb), (float)K);
     mean = mean + p.eps;
     const float r = (float)(1.0 / sqrt((double)mean));
@@ -621,14 +622,19 @@ DEVINL void gemv_epilogue(const GemvParams& p, const float (&acc)[NCH], int m, i
 // dynamic LDS: [2 * 2*SA product ring][kpad f32 x + 16 B]
 // ------------------------------------------------------------------------------------------------
 // optional per-wave timing (GemvParams.dbg != nullptr): [wg][wave][4] = {total, barrier wait, x staging / vm wait, -} in s_memtime ticks
-#define TIMED_BARRIER() do { if (p.dbg_full) { long long tb_ = clock64(); __builtin_amdgcn_s_barrier(); t_wait += clock64() - tb_; } else __builtin_amdgcn_s_barrier(); } while (0)
+// TIMING (a compile-time constant in scope wherever these macros are used): true in the instantiations the launch functions pick when GemvParams.dbg is set
+// (lnb_profile_kernel_stamps, LNB_GEMV_TIMING), false in production's -- there no clock is read, no stamp is stored, nothing branches on dbg / dbg_full and a
+// barrier is one s_barrier: the measurement code is neither executed nor fetched (profiles/prologue_fetch.md)
+#define LNB_DBG (TIMING && p.dbg)
+#define LNB_DBG_FULL (TIMING && p.dbg_full)
+#define TIMED_BARRIER() do { if (LNB_DBG_FULL) { long long tb_ = clock64(); __builtin_amdgcn_s_barrier(); t_wait += clock64() - tb_; } else __builtin_amdgcn_s_barrier(); } while (0)
 // phase stamp i (0..7) of this wave, cycles since the kernel started: a second region behind the [4096][8][4] totals (lnb_api.cpp prints the averages)
 // (the buffer has eight wave slots per workgroup: a ninth wave -- the packed LM head's -- records nothing instead of writing into the next workgroup's slots)
-#define LNB_STAMP(i) do { if (p.dbg && lane == 0 && wave < 8) p.dbg[(size_t)4096 * 8 * 4 + ((size_t)blockIdx.x * 8 + wave) * 8 + (i)] = clock64() - t_begin; } while (0)
+#define LNB_STAMP(i) do { if (LNB_DBG && lane == 0 && wave < 8) p.dbg[(size_t)4096 * 8 * 4 + ((size_t)blockIdx.x * 8 + wave) * 8 + (i)] = clock64() - t_begin; } while (0)
 // ... and stamp 7 = the same interval on the constant-rate wall clock (s_memrealtime; hipDeviceAttributeWallClockRate): the shader clock of THIS launch
 // under ITS load = total / wall, which is what turns the cycle counts into microseconds (bench.py: roofline.measured_model)
-#define LNB_WALL_EXIT() do { if (p.dbg && lane == 0 && wave < 8) p.dbg[(size_t)4096 * 8 * 4 + ((size_t)blockIdx.x * 8 + wave) * 8 + 7] = (long long)wall_clock64() - t_wall0; } while (0)
-#define DBG_EXIT() do { if (p.dbg && lane == 0 && wave < 8) { long long* d_ = p.dbg + ((size_t)blockIdx.x * 8 + wave) * 4; d_[0] = clock64() - t_begin; d_[1] = t_wait; d_[2] = t_x; d_[3] = t_aux; } LNB_WALL_EXIT(); } while (0)
+#define LNB_WALL_EXIT() do { if (LNB_DBG && lane == 0 && wave < 8) p.dbg[(size_t)4096 * 8 * 4 + ((size_t)blockIdx.x * 8 + wave) * 8 + 7] = (long long)wall_clock64() - t_wall0; } while (0)
+#define DBG_EXIT() do { if (LNB_DBG && lane == 0 && wave < 8) { long long* d_ = p.dbg + ((size_t)blockIdx.x * 8 + wave) * 4; d_[0] = clock64() - t_begin; d_[1] = t_wait; d_[2] = t_x; d_[3] = t_aux; } LNB_WALL_EXIT(); } while (0)
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // asm loads are invisible to hipcc's s_waitcnt bookkeeping: the ring below is waited for by hand (wait_ring)
@@ -653,11 +659,11 @@ template <int N, int NP> DEVINL void wait_ring(u32x4 (&b)[NP]) {
 // loads of low bytes, one of exponent codes and one dword of signs for 32 weights -- and rebuild the same f32 weights; everything behind the unpack is the raw form's.
 // Two instances: gate|up (RW 56, seven helpers, EPI_SILU_MUL: the chains are gate and up of one row) and the LM head (RW 64, eight helpers, EPI_STORE2: the
 // chains are rows r and 64 + r of a 128-row block)
-template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC, bool PK, bool REPORT = false>
+template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC, bool PK, bool REPORT = false, bool TIMING = false>
 DEVINL void gemv_chain_body(const GemvParams& p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    long long t_begin = p.dbg ? clock64() : 0, t_wait = 0, t_x = 0, t_aux = 0;
-    const long long t_wall0 = p.dbg ? (long long)wall_clock64() : 0;
+    long long t_begin = LNB_DBG ? clock64() : 0, t_wait = 0, t_x = 0, t_aux = 0;
+    const long long t_wall0 = LNB_DBG ? (long long)wall_clock64() : 0;
     constexpr int KC = SA / (NCH * RW * 16);              // 8-wide k chunks per stage
     constexpr int GS = KC / 2;                            // 16-step groups per stage
     constexpr int SB = 2 * SA;                            // f32 product stage
@@ -742,7 +748,7 @@ DEVINL void gemv_chain_body(const GemvParams& p) {
             TIMED_BARRIER();                                           // B1: xs (or the squares) are in LDS
             if (NORM) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                rms_fold<rms_nf(NH), REPORT>(p, xs, ringB, hw - (NH - rms_nf(NH)), lane, t_aux);      // X1, X2 inside; the LAST four helpers fold (waves 4..7 of 8: four SIMDs)
+                rms_fold<rms_nf(NH), REPORT, TIMING>(p, xs, ringB, hw - (NH - rms_nf(NH)), lane, t_aux);      // X1, X2 inside; the LAST four helpers fold (waves 4..7 of 8: four SIMDs)
                 {                                                      // the walker walks now: the issue stall costs nothing here
 #pragma unroll
                     for (int j = EARLY; j < R; j++) issue_next(buf[j], sgn[PK ? j : 0]);
@@ -761,10 +767,10 @@ DEVINL void gemv_chain_body(const GemvParams& p) {
                 const int t = it0 + j;
                 if (t <= T) {
                     if (t < T) {
-                        const long long tb_ = p.dbg_full ? clock64() : 0;
+                        const long long tb_ = LNB_DBG_FULL ? clock64() : 0;
                         if constexpr (PK) wait_ring_pk<(R - 1) * 4>(buf[j], sgn[j]);
                         else wait_ring<(R - 1) * NP, NP>(buf[j]);           // stage t landed; R-1 younger stages stay in flight
-                        if (p.dbg_full) t_x += clock64() - tb_;
+                        if (LNB_DBG_FULL) t_x += clock64() - tb_;
                         char* dst = ringB + (t & 1) * SB;
                         const float* xst = xs + (size_t)st * (KC * 8);
                         if constexpr (PK) {
@@ -845,7 +851,7 @@ DEVINL void gemv_chain_body(const GemvParams& p) {
         TIMED_BARRIER();                                               // B1
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         if (NORM) {
-            const float r = rms_scale_wide<rms_nf(NH), REPORT ? 2 : 0>(p, xs, ringB, lane, t_aux);     // X1, X2 inside
+            const float r = rms_scale_wide<rms_nf(NH), REPORT ? 2 : 0, TIMING>(p, xs, ringB, lane, t_aux);     // X1, X2 inside
             if (lane == 0) xs[kpad] = r;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             TIMED_BARRIER();                                           // B2
@@ -855,7 +861,7 @@ DEVINL void gemv_chain_body(const GemvParams& p) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         }
     }
-    if (p.dbg) t_x = clock64() - t_begin;
+    if (LNB_DBG) t_x = clock64() - t_begin;
     LNB_STAMP(6);                                                      // (stamp 6 marks a chain wave: the cycle its main loop starts)
     float acc[NCH];
 #pragma unroll
@@ -930,10 +936,11 @@ DEVINL void gemv_chain_body(const GemvParams& p) {
     }
     DBG_EXIT();
 }
-template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value>
-__global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_kernel(GemvParams p) { gemv_chain_body<RW, NCH, SA, NH, R, EPI, NORM, XC, false>(p); }
-template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value>
-__global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_pk_kernel(GemvParams p) { gemv_chain_body<RW, NCH, SA, NH, R, EPI, NORM, XC, true>(p); }
+// TIMING: the instantiation with the measurement code (stamps, timed barriers and ring waits), launched exactly when GemvParams.dbg is set
+template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value, bool TIMING = false>
+__global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_kernel(GemvParams p) { gemv_chain_body<RW, NCH, SA, NH, R, EPI, NORM, XC, false, false, TIMING>(p); }
+template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value, bool TIMING = false>
+__global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_pk_kernel(GemvParams p) { gemv_chain_body<RW, NCH, SA, NH, R, EPI, NORM, XC, true, false, TIMING>(p); }
 // the same two kernels with the norm's report compiled in (GemvParams.norm_out): launched by lnb_op_rmsnorm_sum only
 template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value>
 __global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_report_kernel(GemvParams p) { gemv_chain_body<RW, NCH, SA, NH, R, EPI, NORM, XC, false, true>(p); }
@@ -969,7 +976,7 @@ DEVINL void chain16q(float& acc, const float4& q) {
 }
 constexpr int GQ_SLOTS = 3;
 __host__ __device__ constexpr int gq_ncw(int RW) { return (RW + 15) / 16; }
-template <int RW, int KS, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value>
+template <int RW, int KS, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value, bool TIMING = false>
 __global__ __launch_bounds__((gq_ncw(RW) + NH) * 64) void gemv_quad_kernel(GemvParams p) {
 #define LNB_QUAD_REPORT false
 #include "lnb_gemv_quad_body.h"
@@ -978,6 +985,7 @@ __global__ __launch_bounds__((gq_ncw(RW) + NH) * 64) void gemv_quad_kernel(GemvP
 // the same kernel with the norm's report compiled in (GemvParams.norm_out): launched by lnb_op_rmsnorm_sum only
 template <int RW, int KS, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value>
 __global__ __launch_bounds__((gq_ncw(RW) + NH) * 64) void gemv_quad_report_kernel(GemvParams p) {
+    constexpr bool TIMING = false;
 #define LNB_QUAD_REPORT true
 #include "lnb_gemv_quad_body.h"
 #undef LNB_QUAD_REPORT
@@ -1137,12 +1145,12 @@ DEVINL void chain128(float& acc, const float (&pr)[8]) {
                  "v_add_f32_dpp %0, %8, %0 row_newbcast:15 row_mask:0xf bank_mask:0xf\n\t"
                  : "+v"(acc) : "v"(pr[0]), "v"(pr[1]), "v"(pr[2]), "v"(pr[3]), "v"(pr[4]), "v"(pr[5]), "v"(pr[6]), "v"(pr[7]));
 }
-template <int EPI>
+template <int EPI, bool TIMING = false>
 __global__ __launch_bounds__(256) void rowcast_kernel(GemvParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* xT = (float*)smem;                                // x[128c + 16i + j] at xT[(c*16 + j)*8 + i]
-    const long long t_begin = p.dbg ? clock64() : 0;         // LNB_GEMV_TIMING: [wg][wave] = {total, -, prologue, -}
-    const long long t_wall0 = p.dbg ? (long long)wall_clock64() : 0;
+    const long long t_begin = LNB_DBG ? clock64() : 0;       // LNB_GEMV_TIMING: [wg][wave] = {total, -, prologue, -}
+    const long long t_wall0 = LNB_DBG ? (long long)wall_clock64() : 0;
     long long t_x = 0;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1189,7 +1197,7 @@ __global__ __launch_bounds__(256) void rowcast_kernel(GemvParams p) {
         }
     }
     __syncthreads();
-    if (p.dbg) t_x = clock64() - t_begin;
+    if (LNB_DBG) t_x = clock64() - t_begin;
     LNB_STAMP(6);
     if (p.prio) __builtin_amdgcn_s_setprio(3);               // (rung (a) of the FFN ladder: what a prioritised w2 chain keeps beside a co-resident gate|up workgroup)
     const float* xl = xT + (size_t)(lane & 15) * 8;
@@ -1233,7 +1241,7 @@ __global__ __launch_bounds__(256) void rowcast_kernel(GemvParams p) {
         }
     }
     asm volatile("s_waitcnt vmcnt(0) ; RING_RETIRE_ALL" ::: "memory");
-    if (p.dbg && lane == 0) { long long* d_ = p.dbg + ((size_t)blockIdx.x * 8 + wave) * 4; d_[0] = clock64() - t_begin; d_[1] = 0; d_[2] = t_x; d_[3] = t_x; }
+    if (LNB_DBG && lane == 0) { long long* d_ = p.dbg + ((size_t)blockIdx.x * 8 + wave) * 4; d_[0] = clock64() - t_begin; d_[1] = 0; d_[2] = t_x; d_[3] = t_x; }
     LNB_WALL_EXIT();
 }
 
@@ -1263,14 +1271,14 @@ constexpr int RL_SLOTS = 3;
 constexpr int RL_R = 12;                                    // 1 KiB weight chunks in flight per helper wave (a multiple of RL_SC * RL_SLOTS' unroll)
 constexpr int RL_STAGE = 4 * RL_SC * 2048;                  // bytes of products per stage: 4 pairs x RL_SC chunks x 2 KiB
 __host__ __device__ constexpr size_t rl_lds_bytes(int K) { return (size_t)RL_SLOTS * RL_STAGE + (size_t)K * 2; }
-template <int EPI>
+template <int EPI, bool TIMING = false>
 __global__ __launch_bounds__(512) void rowcast_lds_kernel(GemvParams p) {
     static_assert(RL_R == RL_SC * RL_SLOTS, "the helper's ring index and the product slot are static inside a three-stage unroll");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ring = smem;
     uint16_t* xb = (uint16_t*)(smem + RL_SLOTS * RL_STAGE);  // x[128c + 16i + j] at xb[(c*16 + j)*8 + i]
-    const long long t_begin = p.dbg ? clock64() : 0;         // LNB_GEMV_TIMING: [wg][wave] = {total, barrier wait, x staged, chain start (chain waves)}
-    const long long t_wall0 = p.dbg ? (long long)wall_clock64() : 0;
+    const long long t_begin = LNB_DBG ? clock64() : 0;       // LNB_GEMV_TIMING: [wg][wave] = {total, barrier wait, x staged, chain start (chain waves)}
+    const long long t_wall0 = LNB_DBG ? (long long)wall_clock64() : 0;
     long long t_x = 0, t_wait = 0, t_chain = 0;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), pair = wave & 3;
@@ -1309,9 +1317,9 @@ __global__ __launch_bounds__(512) void rowcast_lds_kernel(GemvParams p) {
             }
         }
         __syncthreads();
-        if (p.dbg) t_x = clock64() - t_begin;
+        if (LNB_DBG) t_x = clock64() - t_begin;
     };
-#define RL_BARRIER() do { if (p.dbg_full) { const long long tb_ = clock64(); __builtin_amdgcn_s_barrier(); t_wait += clock64() - tb_; } else __builtin_amdgcn_s_barrier(); } while (0)
+#define RL_BARRIER() do { if (LNB_DBG_FULL) { const long long tb_ = clock64(); __builtin_amdgcn_s_barrier(); t_wait += clock64() - tb_; } else __builtin_amdgcn_s_barrier(); } while (0)
     // Schedule (iterations it = 0 .. NS, one s_barrier each).  Iteration 0 fills the ring from BOTH sides: the helper makes stage 0, the
     // chain wave -- idle until there is something to add -- makes stage 1 from four weight loads of its own (otherwise it sits through
     // two helper stages, ~4 k cycles per launch measured).  From then on: iteration it, the helper writes stage it+1 (slot (it+1) % 3),
@@ -1393,7 +1401,7 @@ __global__ __launch_bounds__(512) void rowcast_lds_kernel(GemvParams p) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         }
         __builtin_amdgcn_s_setprio(3);
-        if (p.dbg) { t_chain = clock64() - t_begin; t_wait = 0; }         // (chain waves report the barrier wait of the main loop only)
+        if (LNB_DBG) { t_chain = clock64() - t_begin; t_wait = 0; }         // (chain waves report the barrier wait of the main loop only)
         LNB_STAMP(6);
         float acc = 0.0f;
         float4 ba[2], bb[2];                                 // products of the chunk being added / of the next one
@@ -1433,7 +1441,7 @@ __global__ __launch_bounds__(512) void rowcast_lds_kernel(GemvParams p) {
         }
     }
 #undef RL_BARRIER
-    if (p.dbg && lane == 0) { long long* d_ = p.dbg + ((size_t)blockIdx.x * 8 + wave) * 4; d_[0] = clock64() - t_begin; d_[1] = t_wait; d_[2] = t_x; d_[3] = t_chain; }
+    if (LNB_DBG && lane == 0) { long long* d_ = p.dbg + ((size_t)blockIdx.x * 8 + wave) * 4; d_[0] = clock64() - t_begin; d_[1] = t_wait; d_[2] = t_x; d_[3] = t_chain; }
     LNB_WALL_EXIT();
 }
 
@@ -2588,7 +2596,8 @@ DEVINL double attn_zseq_wave(const double* e, int T) {
 // DENSE = the batched decode's heads x sequences grids (thousands of workgroups): registers for TWO workgroups per CU (4 waves per SIMD, 128
 // VGPRs) instead of one -- the K rows of the next 512 positions are then NOT kept in flight during a pass's score chains (the ping-pong
 // buffer is 64 of the 178 VGPRs of the single stream's form, which launches 32 workgroups on 256 CUs and wants every register)
-template <int HD, bool DENSE = false, bool CAUSAL = false> __global__ __launch_bounds__(ATT_NT, DENSE ? 4 : 2) void attn_exact_kernel(AttnParams p) {
+// TIMING: the instantiation with the phase stamps (AttnParams.dbg, LNB_GEMV_TIMING): launched exactly when dbg is set; production reads no clock
+template <int HD, bool DENSE = false, bool CAUSAL = false, bool TIMING = false> __global__ __launch_bounds__(ATT_NT, DENSE ? 4 : 2) void attn_exact_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NK = HD / 8;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -2616,7 +2625,7 @@ template <int HD, bool DENSE = false, bool CAUSAL = false> __global__ __launch_b
     const uint16_t* vbase = (bt ? p.bkv->cv[i] : p.cache_v) + (size_t)kvh * HD;
     const int Tend = (S > 1 && pos0 == 0) ? (i + 1) : T;    // see PV below
     const int nchunks = (Tend + ATT_JC - 1) / ATT_JC;
-#define ATT_STAMP(n) do { if (p.dbg && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0) p.dbg[wave * 16 + (n)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
+#define ATT_STAMP(n) do { if (LNB_DBG && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0) p.dbg[wave * 16 + (n)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
     ATT_STAMP(0);
 
     // q first (everything waits on it), then what does not depend on q: this thread's K row and chunk 0 of V (producers)
@@ -3092,7 +3101,7 @@ __host__ __device__ inline bool alp_per_position(int seq_len) { return alp_lds_b
 __host__ __device__ inline int alp_pw_floats(int seq_len) { return alp_per_position(seq_len) ? ((seq_len + ALP_BATCH - 1) / ALP_BATCH + 1) * ALP_BATCH : ALP_PW_LONG; }
 __host__ __device__ inline size_t alp_layout_bytes(int seq_len) { return (size_t)alp_pw_floats(seq_len) * 4 + 2 * (size_t)ALP_SLOT * 4 + 64; }
 DEVINL float alp_p(double e, double z) { return bf_wide(bf_trunc((float)(e / z))); }     // impl:506 + ToBFloat16 :493
-template <int HD, bool BATCH = false> DEVINL void alp_eager_body(const AttnParams& p) {
+template <int HD, bool BATCH = false, bool TIMING = false> DEVINL void alp_eager_body(const AttnParams& p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -3105,7 +3114,7 @@ template <int HD, bool BATCH = false> DEVINL void alp_eager_body(const AttnParam
     double* zsh = (double*)(ring + 2 * ALP_SLOT);
     const double* E = p.e_buf + al_row<BATCH>(sq, h) * p.seq_len;
     const int kvh = h / (p.H / p.KVH);
-#define ALP_STAMP(n) do { if (p.dbg && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && (wave & 3) == 0) p.dbg[(wave >> 2) * 16 + (n)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
+#define ALP_STAMP(n) do { if (LNB_DBG && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && (wave & 3) == 0) p.dbg[(wave >> 2) * 16 + (n)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
     ALP_STAMP(0);
     // ---- everything that depends only on addresses goes in flight first, oldest-needed first (waits retire in issue order): the first
     // round of e_j, the per-block partial sums, then the producers' first three batches of V rows (HBM: the slowest, needed last)
@@ -3255,7 +3264,8 @@ template <int HD, bool BATCH = false> DEVINL void alp_eager_body(const AttnParam
     }
 }
 
-template <int HD, bool BATCH = false> __global__ __launch_bounds__(ALP_NT) void attn_long_pv_kernel(AttnParams p) { alp_eager_body<HD, BATCH>(p); }
+// TIMING: the instantiations with the phase stamps (AttnParams.dbg), launched exactly when dbg is set
+template <int HD, bool BATCH = false, bool TIMING = false> __global__ __launch_bounds__(ALP_NT) void attn_long_pv_kernel(AttnParams p) { alp_eager_body<HD, BATCH, TIMING>(p); }
 
 // ------------------------------------------------------------------------------------------------
 // attn_long_pv2_kernel (round 6): attn_long_pv_kernel with the p_j evaluated LAZILY, off the critical path.
@@ -3269,7 +3279,7 @@ template <int HD, bool BATCH = false> __global__ __launch_bounds__(ALP_NT) void 
 // equals the reference's bits whatever the serial sum is (monotone step function, attn_long_pv_kernel's header); an uncertified one is discarded.
 // Same grid, block and LDS as attn_long_pv_kernel (the p array is unused).  The kernel symbol attn_long_pv2_kernel picks between the two bodies (below).
 // ------------------------------------------------------------------------------------------------
-template <int HD, bool BATCH = false> DEVINL void alp_lazy_body(const AttnParams& p) {
+template <int HD, bool BATCH = false, bool TIMING = false> DEVINL void alp_lazy_body(const AttnParams& p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -3281,7 +3291,7 @@ template <int HD, bool BATCH = false> DEVINL void alp_lazy_body(const AttnParams
     int* const flag = (int*)(zsh + 1);
     const double* E = p.e_buf + al_row<BATCH>(sq, h) * p.seq_len;
     const int kvh = h / (p.H / p.KVH);
-#define ALQ_STAMP(n) do { if (p.dbg && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && (wave & 3) == 0) p.dbg[(wave >> 2) * 16 + (n)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
+#define ALQ_STAMP(n) do { if (LNB_DBG && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && (wave & 3) == 0) p.dbg[(wave >> 2) * 16 + (n)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
     ALQ_STAMP(0);
     // address-only loads first, oldest-needed first: the per-block partial sums, then the producers' first three batches of e_j and V rows
     const int nblk_max = (p.seq_len + ALS_NT - 1) / ALS_NT;
@@ -3396,9 +3406,9 @@ template <int HD, bool BATCH = false> DEVINL void alp_lazy_body(const AttnParams
 // up to two batches (T <= 1024) the eager form is the faster one (all 512 threads share the first batch's p_j: 11.2 against 11.5 us at T = 768,
 // 9.6 against 10.1 at 272); from three batches on the lazy one (T = 2048: 15.1 -> 14.5 us, 4101: 23.0 -> 21.8).  T lives on the device (one captured
 // graph serves every position), so the choice is made here, per launch, uniformly over the grid.
-template <int HD, bool BATCH = false> __global__ __launch_bounds__(ALP_NT) void attn_long_pv2_kernel(AttnParams p) {
-    if constexpr (BATCH) { if (p.btab->st[blockIdx.z]->pos + 1 <= 2 * ALP_BATCH) alp_eager_body<HD, true>(p); else alp_lazy_body<HD, true>(p); }     // (per sequence: uniform over its workgroups)
-    else if (p.st->pos + 1 <= 2 * ALP_BATCH) alp_eager_body<HD>(p); else alp_lazy_body<HD>(p);
+template <int HD, bool BATCH = false, bool TIMING = false> __global__ __launch_bounds__(ALP_NT) void attn_long_pv2_kernel(AttnParams p) {
+    if constexpr (BATCH) { if (p.btab->st[blockIdx.z]->pos + 1 <= 2 * ALP_BATCH) alp_eager_body<HD, true, TIMING>(p); else alp_lazy_body<HD, true, TIMING>(p); }     // (per sequence: uniform over its workgroups)
+    else if (p.st->pos + 1 <= 2 * ALP_BATCH) alp_eager_body<HD, false, TIMING>(p); else alp_lazy_body<HD, false, TIMING>(p);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4820,16 +4830,18 @@ static size_t xs_bytes(int K, int steps_per_stage) { return ((size_t)((K + steps
 template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC, bool PK = false, bool REPORT = false>
 static hipError_t launch_chain_x(const GemvParams* p, hipStream_t st) {
     static_assert(!NORM || rms_norm_helpers_has(NH), "a norm on this many helper waves: add it to LNB_RMS_NORM_HELPERS (lnb_seqsum.h)");
-    void (*kfn)(GemvParams);
-    if constexpr (REPORT) { if constexpr (PK) kfn = gemv_chain_pk_report_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; else kfn = gemv_chain_report_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; }
-    else if constexpr (PK) kfn = gemv_chain_pk_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; else kfn = gemv_chain_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>;
-    if (!p) return raise_lds(kfn);
+    // kfn: production's instantiation; ktm: the one with the measurement code compiled in, launched exactly when p->dbg is set (the report kernels have none)
+    void (*kfn)(GemvParams), (*ktm)(GemvParams);
+    if constexpr (REPORT) { if constexpr (PK) kfn = gemv_chain_pk_report_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; else kfn = gemv_chain_report_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; ktm = kfn; }
+    else if constexpr (PK) { kfn = gemv_chain_pk_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; ktm = gemv_chain_pk_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC, true>; }
+    else { kfn = gemv_chain_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; ktm = gemv_chain_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC, true>; }
+    if (!p) return raise_lds(kfn, ktm);
     size_t lds = 4 * (size_t)SA + xs_bytes(p->K, SA / (NCH * RW * 2));
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (xs_bytes(p->K, SA / (NCH * RW * 2)) / 4 > (size_t)XC * (1 + NH) * 512) return hipErrorInvalidValue;   // x staging registers
     if (NORM && (rms_scratch_bytes(rms_nf(NH)) > 4 * (size_t)SA || seq_leaf_size(p->K, rms_nf(NH) * 64) > 256)) return hipErrorInvalidValue;   // records live in the idle ring; leaf over-read stays inside the x padding
     form_ran(PK ? (EPI == EPI_STORE2 ? Form::GEMV_HEAD_PK : Form::GEMV_CHAIN_PK) : RW == 16 ? Form::GEMV_CHAIN_16 : RW == 28 ? Form::GEMV_CHAIN_28 : RW == 32 ? Form::GEMV_CHAIN_32 : RW == 56 ? (R == 6 ? Form::GEMV_CHAIN_56_TP : Form::GEMV_CHAIN_56) : Form::GEMV_CHAIN_64, EPI == EPI_STORE2 ? EPI_STORE : EPI);
-    hipLaunchKernelGGL(kfn, dim3((unsigned)(p->S * p->n_wg)), dim3((1 + NH) * 64), lds, st, *p);
+    hipLaunchKernelGGL(p->dbg ? ktm : kfn, dim3((unsigned)(p->S * p->n_wg)), dim3((1 + NH) * 64), lds, st, *p);
     return hipGetLastError();
 }
 // x staging chunks per stager wave: the norm-fused kernels are instantiated for 2, 3 and 6 chunks of 512 elements per wave (K up to ~4 K, ~6 K / 12 K with
@@ -4852,9 +4864,10 @@ static hipError_t launch_chain_t(const GemvParams* p, hipStream_t st) {
 template <int RW, int KS, int NH, int R, int EPI, bool NORM, int XC, bool REPORT = false>
 static hipError_t launch_quad_x(const GemvParams* p, hipStream_t st) {
     static_assert(!NORM || rms_norm_helpers_has(NH), "a norm on this many helper waves: add it to LNB_RMS_NORM_HELPERS (lnb_seqsum.h)");
-    void (*kfn)(GemvParams);
-    if constexpr (REPORT) kfn = gemv_quad_report_kernel<RW, KS, NH, R, EPI, NORM, XC>; else kfn = gemv_quad_kernel<RW, KS, NH, R, EPI, NORM, XC>;
-    if (!p) return raise_lds(kfn);
+    void (*kfn)(GemvParams), (*ktm)(GemvParams);                                 // (ktm: as in launch_chain_x)
+    if constexpr (REPORT) { kfn = gemv_quad_report_kernel<RW, KS, NH, R, EPI, NORM, XC>; ktm = kfn; }
+    else { kfn = gemv_quad_kernel<RW, KS, NH, R, EPI, NORM, XC>; ktm = gemv_quad_kernel<RW, KS, NH, R, EPI, NORM, XC, true>; }
+    if (!p) return raise_lds(kfn, ktm);
     constexpr int NW = gq_ncw(RW) + NH;
     constexpr size_t SB = (size_t)RW * KS * 4;
     if (p->K % KS) return hipErrorInvalidValue;                                  // whole stages only (auto_rw in lnb_api.cpp picks this layout accordingly)
@@ -4863,7 +4876,7 @@ static hipError_t launch_quad_x(const GemvParams* p, hipStream_t st) {
     if (xs_bytes(p->K, KS) / 4 > (size_t)XC * NW * 512) return hipErrorInvalidValue;     // x staging registers
     if (NORM && (rms_scratch_bytes(rms_nf(NH)) > GQ_SLOTS * SB || seq_leaf_size(p->K, rms_nf(NH) * 64) > 256)) return hipErrorInvalidValue;
     form_ran(Form::GEMV_QUAD, EPI);
-    hipLaunchKernelGGL(kfn, dim3((unsigned)(p->S * p->n_wg)), dim3(NW * 64), lds, st, *p);
+    hipLaunchKernelGGL(p->dbg ? ktm : kfn, dim3((unsigned)(p->S * p->n_wg)), dim3(NW * 64), lds, st, *p);
     return hipGetLastError();
 }
 template <int RW, int KS, int NH, int R, int EPI, bool NORM, bool REPORT = false>
@@ -4996,9 +5009,10 @@ extern "C" hipError_t lnbk_wpack_head(const uint16_t* w, void* out, int N, int K
 }
 
 template <int EPI> static hipError_t launch_rowcast(const GemvParams* p, hipStream_t st) {
-    auto kfn = rowcast_kernel<EPI>;
-    auto kl = rowcast_lds_kernel<EPI>;
-    if (!p) return raise_lds(kl, kfn);
+    // (the <EPI, true> instantiations carry the measurement code: launched exactly when p->dbg is set)
+    const auto kfn = (p && p->dbg) ? rowcast_kernel<EPI, true> : rowcast_kernel<EPI>;
+    const auto kl = (p && p->dbg) ? rowcast_lds_kernel<EPI, true> : rowcast_lds_kernel<EPI>;
+    if (!p) return raise_lds(kl, kfn, rowcast_lds_kernel<EPI, true>, rowcast_kernel<EPI, true>);
     if ((p->K & 127) || p->K > 16384) return hipErrorInvalidValue;              // x staging: 8 x 16 B per thread, K*4 bytes of LDS
     // helper-fed chain waves (rowcast_lds_kernel) whenever K is a whole number of its 512-step stages; LNB_ROWCAST_LDS=0: the self-feeding kernel
     // (throughput schedule: the self-feeding kernel -- four waves and K * 4 bytes of LDS instead of eight waves and 96 KB + K * 2: co-resident with
@@ -5096,8 +5110,10 @@ static long long* g_gqa_dbg = nullptr;                       // LNB_ATTN_GQA_DBG
 // BATCH (p->btab): p->S sequences in grid.z, p->seq_len = the largest member's cache length (e_buf [S][H][seq_len], z_part [S][H][ceil(seq_len/256)])
 template <bool BATCH> static hipError_t launch_attn_long(const AttnParams* p, hipStream_t st) {
     return with_hd(p, [&](auto HD) {
-        const auto scores = attn_long_scores_kernel<HD, BATCH>, lazy = attn_long_pv2_kernel<HD, BATCH>, eager = attn_long_pv_kernel<HD, BATCH>;
-        if (!p) return raise_lds(lazy, eager);
+        const bool tm = p && p->dbg;                                 // the PV pair's instantiations with the phase stamps
+        const auto scores = attn_long_scores_kernel<HD, BATCH>, lazy = tm ? attn_long_pv2_kernel<HD, BATCH, true> : attn_long_pv2_kernel<HD, BATCH>,
+                   eager = tm ? attn_long_pv_kernel<HD, BATCH, true> : attn_long_pv_kernel<HD, BATCH>;
+        if (!p) return raise_lds(lazy, eager, attn_long_pv2_kernel<HD, BATCH, true>, attn_long_pv_kernel<HD, BATCH, true>);
         // (a context beyond the per-position layout cannot stage p_j for the eager-everywhere form: LNB_ATTN_LAZY=0 runs the default pair there)
         const auto pv = knob(Knob::ATTN_LAZY) || !alp_per_position(p->seq_len) ? lazy : eager;
         const size_t lds = alp_layout_bytes(p->seq_len);
@@ -5211,8 +5227,9 @@ static hipError_t launch_attn_short(const AttnParams* p, hipStream_t st) {
         }
     }
     return with_hd(p, [&](auto HD) {
-        const auto plain = attn_exact_kernel<HD>, append = attn_exact_kernel<HD, false, true>;
-        if (!p) return raise_lds(plain, append);
+        const bool tm = p && p->dbg;                                 // the instantiations with the phase stamps
+        const auto plain = tm ? attn_exact_kernel<HD, false, false, true> : attn_exact_kernel<HD>, append = tm ? attn_exact_kernel<HD, false, true, true> : attn_exact_kernel<HD, false, true>;
+        if (!p) return raise_lds(plain, append, attn_exact_kernel<HD, false, false, true>, attn_exact_kernel<HD, false, true, true>);
         // lnb_forward_append, 2..15 rows (any row count at head_dim 32): workgroup (h, i) runs the one-token step at pos + i
         const auto k = p->causal && !p->btab && p->S > 1 ? append : plain;
         if (p->btab) form_ran(Form::ATTN_BATCH_PLAIN);

@@ -34,7 +34,8 @@ CLASSES = [
 
 # wo and w2 run through ONE kernel symbol with the same grid (rocprofv3 reports only static LDS, which is 0 for both): their launches are
 # told apart by size -- durations in the trace pass, bytes in the PMC pass -- at the geometric mean of the extremes (K = 4096 against 14336)
-SPLIT = {"rowcast_kernel<2>": ("wo+residual GEMV", "w2+residual GEMV"), "rowcast_lds_kernel<2>": ("wo+residual GEMV", "w2+residual GEMV"), "fast_gemv_b<2>": ("wo+residual GEMV", "w2+residual GEMV"),
+# (substrings: the rowcast kernels' names go on with their TIMING argument, "<2, false>" in a production launch)
+SPLIT = {"rowcast_kernel<2": ("wo+residual GEMV", "w2+residual GEMV"), "rowcast_lds_kernel<2": ("wo+residual GEMV", "w2+residual GEMV"), "fast_gemv_b<2>": ("wo+residual GEMV", "w2+residual GEMV"),
          "mfma_stream_kernel<1, 2>": ("batch: wo+residual stream", "batch: w2+residual stream")}
 
 
