@@ -607,6 +607,12 @@ int lnb_ctx_verify_attention_form(const lnb_ctx* c, int* out);
  * which: 0 = stage input, 1 = stage output, 2 = the [seq_len, ffn_hidden] gate*up activations, part of the hand-off when the
  * stage boundary lies between a block's gate/up and down parts.  RCCL send/recv (done by the host layer) targets these pointers. */
 void* lnb_ctx_hidden_ptr(lnb_ctx* c, int which);
+/* A test aid: the attention launch of `layer` on the caller's query rows.  Copies q_bf16 [seq][n_heads][head_dim] into the context's query buffer, sets the
+ * device position and enqueues what a Forward of `seq` rows at start_pos enqueues for the attention of that block (the same function: the context's mode,
+ * the one-row / row-per-workgroup / matrix-core / long-context dispatch and the non-finite rescan apply), then copies the [seq][n_heads][head_dim] result to
+ * out_bf16.  The K / V rows [0, start_pos + seq) are what the context holds (lnb_ctx_load_prefix).  A Forward's checks apply (the reference's broadcast rule:
+ * seq divides start_pos + seq); only a call that reaches the tolerance mode's flash kernel, whose mask is defined at any length, may break that rule. */
+int lnb_ctx_attention(lnb_ctx* c, int layer, const uint16_t* q_bf16, int seq, int start_pos, uint16_t* out_bf16);
 /* Runs this stage's layers.  tokens != NULL only on the first stage (embedding gather); otherwise the input
  * hidden state must already be in hidden_ptr(0).  On the last stage logits_out/argmax_last_out behave as in
  * lnb_forward; on other stages they must be NULL and the result is left in hidden_ptr(1). */

@@ -1562,6 +1562,28 @@ extern "C" int lnb_forward(lnb_ctx* c, const int32_t* tokens, int seq, int start
     return lnb_forward_stage(c, tokens, seq, start_pos, logits_out, argmax_last_out);
 }
 
+// lnb_ctx_attention (a test aid, include/lnb.h): the K_ATTN launch of `layer` as a Forward of `seq` rows at start_pos enqueues it, on a caller's query rows
+extern "C" int lnb_ctx_attention(lnb_ctx* c, int layer, const uint16_t* q, int seq, int start_pos, uint16_t* out) {
+    if (!c || !q || !out) return fail("null argument");
+    lnb_model* m = c->m;
+    HIPCHK(hipSetDevice(m->device));
+    if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
+    if (layer < m->layer_begin || layer >= m->layer_end || !m->has_attn(layer)) return fail("layer %d: this handle holds no attention of that block", layer);
+    // the reference cannot broadcast its [seq, seq] mask over T positions unless seq divides T, and every exact kernel rests on that; the flash kernel of the
+    // tolerance mode evaluates (j mod seq) > i at any T, and is reached with any T here (the same 16-row and head_dim conditions as enqueue_layer_kernel's)
+    const bool flash = c->mode == LNB_MODE_FAST && use_mfma(seq) && (m->head_dim == 64 || m->head_dim == 128);
+    if (check_call(c, seq, start_pos, flash)) return -1;
+    hipStream_t st = c->stream;
+    const size_t n = (size_t)seq * m->q_dim;
+    c->attn_long = want_long_attention(c, seq, start_pos);
+    HIPCHK(ctx_set_state(c, start_pos, 0, true));
+    HIPCHK(hipMemcpyAsync(c->q, q, n * 2, hipMemcpyHostToDevice, st));
+    if (enqueue_layer_kernel(c, layer, seq, K_ATTN)) return -1;
+    HIPCHK(hipMemcpyAsync(out, c->att, n * 2, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
 // lnb_forward_append / lnb_forward_score_append: `seq` rows at ANY start position under the true causal mask -- row i is the one-token step at
 // start_pos + i (include/lnb.h).  Always one multi-row call: 16 or more rows on the matrix-core kernel, fewer (or head_dim 32) on the row-per-workgroup
 // kernel while the context fits its LDS, and beyond that -- or beyond lnb_ctx_set_rows_attention's threshold -- on the multi-row long-context pair

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include "lnb_device.h"
 #include "lnb_knobs.h"
+#include "lnb_forms.h"
 
 #define DEVINL __device__ __forceinline__
 
@@ -458,6 +459,8 @@ template <int EPI, int NCH, bool LAYB, int MT, int WB = 3> hipError_t launch_gem
     const int nwg = NCH == 2 ? 128 : 256;
     const unsigned gx = (unsigned)((p->S + 32 * MT - 1) / (32 * MT)), ny = (unsigned)((p->n_rows + nwg - 1) / nwg);
     const dim3 grid(((ny + 7) / 8) * 8 * gx);                // (padded to whole groups of 8 weight tiles: see the tile order in the kernel)
+    form_ran(MT == 8 ? (LAYB ? Form::FAST_GEMM_B_MT8_WB3 : Form::FAST_GEMM_A_MT8_WB3) : WB == 3 ? (LAYB ? Form::FAST_GEMM_B_MT4_WB3 : Form::FAST_GEMM_A_MT4_WB3)
+                     : (LAYB ? Form::FAST_GEMM_B_MT4_WB2 : Form::FAST_GEMM_A_MT4_WB2), EPI);
     hipLaunchKernelGGL(kfn, grid, dim3(256), lds, st, *p);
     return hipGetLastError();
 }
@@ -648,6 +651,7 @@ hipError_t launch_a_rg(const GemvParams* p, int rw, hipStream_t st) {
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const int units = p->n_blocks * (rw / RG);
     const int cap = knob(Knob::FAST_GRID_CAP);
+    form_ran(RG == 64 ? Form::FAST_GEMV_A_RG64 : RG == 32 ? Form::FAST_GEMV_A_RG32 : RG == 16 ? Form::FAST_GEMV_A_RG16 : Form::FAST_GEMV_A_RG8, EPI);
     hipLaunchKernelGGL(kfn, dim3((unsigned)(units < cap ? units : cap), (unsigned)p->S), dim3(256), lds, st, *p, rw);
     return hipGetLastError();
 }
@@ -674,6 +678,7 @@ template <int EPI> hipError_t launch_b(const GemvParams* p, hipStream_t st) {
     if (p->K & 127) return hipErrorInvalidValue;
     const size_t lds = (size_t)p->K * 2 + 64;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
+    form_ran(Form::FAST_GEMV_B, EPI);
     hipLaunchKernelGGL(kfn, dim3((unsigned)(p->n_blocks * 4), (unsigned)p->S), dim3(256), lds, st, *p);
     return hipGetLastError();
 }
@@ -714,8 +719,8 @@ extern "C" hipError_t lnbk_fast_gemm(const GemmParams* p, int epi, hipStream_t s
 extern "C" hipError_t lnbk_fast_attn(const AttnParams* p, hipStream_t st) {
     if (!p || p->S < 16) return hipErrorInvalidValue;
     const dim3 grid((unsigned)p->H, (unsigned)((p->S + 127) / 128));
-    if (p->hd == 128) hipLaunchKernelGGL(fast_attn_prefill_kernel<128>, grid, dim3(256), 0, st, *p);
-    else if (p->hd == 64) hipLaunchKernelGGL(fast_attn_prefill_kernel<64>, grid, dim3(256), 0, st, *p);
+    if (p->hd == 128) { form_ran(Form::FAST_ATTN_HD128); hipLaunchKernelGGL(fast_attn_prefill_kernel<128>, grid, dim3(256), 0, st, *p); }
+    else if (p->hd == 64) { form_ran(Form::FAST_ATTN_HD64); hipLaunchKernelGGL(fast_attn_prefill_kernel<64>, grid, dim3(256), 0, st, *p); }
     else return hipErrorNotSupported;
     return hipGetLastError();
 }

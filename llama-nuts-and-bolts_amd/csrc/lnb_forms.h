@@ -66,6 +66,20 @@
     X(SAMPLE_BATCH, "sample.batch", "batch_sample_kernel: one workgroup per member of a batched sampling step, each with its own sampler") \
     X(SAMPLE_SPEC, "sample.spec", "spec_sample_commit_kernel: one workgroup per column of a verify pass, each at its own position; the last one accepts and emits") \
     X(SAMPLE_SPEC_MANY, "sample.spec_many", "spec_many_sample_commit_kernel: the same per column of a many-context pass, each member with its own sampler") \
+    /* the tolerance mode (lnb_fast.hip: launch_a, launch_b, launch_gemm_fast, lnbk_fast_attn) */ \
+    X(FAST_GEMV_A_RG8, "fast_gemv_a.rg8", "fast_gemv_a<*, *, *, 8>: split-K GEMV over a chain layout, 8 rows per work unit (few units, LNB_FAST_RG=8)") \
+    X(FAST_GEMV_A_RG16, "fast_gemv_a.rg16", "the same, 16 rows per work unit") \
+    X(FAST_GEMV_A_RG32, "fast_gemv_a.rg32", "the same, 32 rows per work unit") \
+    X(FAST_GEMV_A_RG64, "fast_gemv_a.rg64", "the same, 64 rows per work unit (1024 and more 64-row blocks: the LM head)") \
+    X(FAST_GEMV_B, "fast_gemv_b", "fast_gemv_b: split-K GEMV over the row-broadcast layout") \
+    X(FAST_GEMM_A_MT4_WB2, "fast_gemm.a.mt4_wb2", "fast_gemm_kernel<*, *, false, 4, 2>: bf16 matrix-core GEMM from a chain layout, 128 batch rows, two workgroups per CU") \
+    X(FAST_GEMM_A_MT4_WB3, "fast_gemm.a.mt4_wb3", "fast_gemm_kernel<*, *, false, 4, 3>: 128 batch rows, one workgroup per CU (LNB_FAST_GEMM_2WG=0, up to 128 rows)") \
+    X(FAST_GEMM_A_MT8_WB3, "fast_gemm.a.mt8_wb3", "fast_gemm_kernel<*, *, false, 8, 3>: 256 batch rows, one workgroup per CU (1024 rows and more)") \
+    X(FAST_GEMM_B_MT4_WB2, "fast_gemm.b.mt4_wb2", "fast_gemm_kernel<*, 1, true, 4, 2>: the same three from the row-broadcast layout") \
+    X(FAST_GEMM_B_MT4_WB3, "fast_gemm.b.mt4_wb3", "fast_gemm_kernel<*, 1, true, 4, 3>") \
+    X(FAST_GEMM_B_MT8_WB3, "fast_gemm.b.mt8_wb3", "fast_gemm_kernel<*, 1, true, 8, 3>") \
+    X(FAST_ATTN_HD64, "fast_attn.hd64", "fast_attn_prefill_kernel<64>: flash attention on the bf16 matrix cores") \
+    X(FAST_ATTN_HD128, "fast_attn.hd128", "fast_attn_prefill_kernel<128>") \
     /* pipeline stage step */ \
     X(PIPELINE_REPLAY, "pipeline.replay", "a one-token or batched pipeline stage step replayed from its captured graph (counted per step)") \
     X(PIPELINE_EAGER, "pipeline.eager", "such a step launched eagerly (LNB_PIPELINE_GRAPH=0; counted per step)")

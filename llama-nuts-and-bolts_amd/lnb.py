@@ -78,6 +78,7 @@ EXPORTS = [
     "lnb_decode_speculative_sample_until", "lnb_decode_speculative_sample_many", "lnb_op_spec_sample_accept",
     "lnb_form_count", "lnb_form_count_reset", "lnb_form_name",
     "lnb_op_rmsnorm_sum",
+    "lnb_ctx_attention",
 ]
 EPILOGUES = {"store": 0, "qkv_rope": 1, "resid": 2, "silu_mul": 3}      # EPI_* of csrc/lnb_device.h: the second index of the launch tally
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
@@ -183,6 +184,7 @@ def lib():
     L.lnb_decode_greedy.argtypes = [vp, C.c_int32, C.c_int, C.c_int, vp, f32p]
     L.lnb_ctx_hidden_ptr.argtypes = [vp, C.c_int]
     L.lnb_ctx_hidden_ptr.restype = vp
+    L.lnb_ctx_attention.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp]
     L.lnb_forward_stage.argtypes = [vp, vp, C.c_int, C.c_int, vp, i32p]
     L.lnb_forward_stage_begin.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.lnb_forward_stage_end.argtypes = [vp, i32p]
@@ -653,6 +655,14 @@ class InferenceContext:
         n = C.c_int(0)
         _chk(self.L.lnb_ctx_prefill_attention_form(self.h, C.byref(n)))
         return n.value
+
+    def attention(self, layer, q_u16, start_pos):
+        """lnb_ctx_attention (a test aid): the attention launch of `layer` on q_u16 [S, n_heads, head_dim] over the context's K / V rows -> uint16 [S, n_heads, head_dim]"""
+        q = np.ascontiguousarray(q_u16, dtype=np.uint16)
+        assert q.ndim == 3
+        out = np.empty_like(q)
+        _chk(self.L.lnb_ctx_attention(self.h, layer, q.ctypes.data, q.shape[0], start_pos, out.ctypes.data))
+        return out
 
     def Forward(self, tokens, start_pos, want_logits=True):
         """(*LlamaTransformer).Forward (llamatransformer.go:145-180) -> (logits f32 [S,V] | None, argmax of last row)."""

@@ -25,9 +25,6 @@ KNOB_EXEMPT = {
     "LNB_GEMV_TIMING": "timing only, produces no result", "LNB_PROFILE_SAME_LAYER": "timing only, produces no result",
     "LNB_MEASURE_SKIP_TOKEN_KERNELS": "timing only: the tokens are garbage by design", "LNB_W2_PRIO": "a wave priority: timing only, produces no result",
     "LNB_W2_LDS_PAD": "LDS padding of the profiled pair: timing only, produces no result", "LNB_ATTN_GQA_DBG": "prints phase stamps, produces no result",
-    # tolerance mode: not bit-exact by contract, its forms are chosen by row count and checked against a tolerance in tests/test_gpu_fast.py
-    "LNB_FAST_GEMM_2WG": "tolerance mode, a batch-tile choice by row count: tests/test_gpu_fast.py runs both sides of the default",
-    "LNB_FAST_RG": "tolerance mode, measurement aid of the split-K GEMV", "LNB_FAST_GRID_CAP": "tolerance mode, measurement aid of the split-K GEMV",
     # covered elsewhere, or an aid that picks nothing of its own
     "LNB_PIPELINE_LOG_CAP": "set by the wrap-around test of tests/test_pipeline_cabi.py (GPU-marked, outside the test_gpu_* files): a log size, no kernel form",
     "LNB_ATTN_LONG_T": "only the initial value of a per-context threshold: the tests set that threshold itself, through lnb_ctx_set_attention / lnb_batch_set_attention "
