@@ -22,6 +22,7 @@
 #include "lnb_device.h"
 #include "lnb_knobs.h"
 #include "lnb_forms.h"
+#include "lnb_gemv_geom.h"
 #include "lnb_kvcopy.h"
 #include "lnb_rowpack.h"
 #include "lnb_wpack.h"
@@ -322,9 +323,9 @@ static int staging_release(lnb_ctx* c) {
 static int auto_rw(int lane_rows, Knob env, int K = 0, bool plain = false, int unforced = 0) {      // unforced: the caller's choice while the knob is 0 (0: by shape)
     const int v = knob(env);
     if (v == 0 && unforced) return unforced;
-    if (v == 16 || v == 32 || v == 64 || (v == 4 && plain && K % 128 == 0 && K <= 16384) || ((v == 56 || v == 28) && lane_rows % v == 0) || (v == 24 && K > 0 && K % 256 == 0)) return v;
+    if (v == 16 || v == 32 || v == 64 || (v == 4 && plain && gemv_layout_takes(4, K)) || ((v == 56 || v == 28) && lane_rows % v == 0) || (v == 24 && K > 0 && gemv_layout_takes(24, K))) return v;
     // thin matrices without a fused norm / rope epilogue: the row-broadcast kernel (products stay in registers)
-    if (plain && lane_rows <= 16 * 256 && K > 0 && K % 128 == 0 && K <= 16384) return 4;
+    if (plain && lane_rows <= 16 * 256 && K > 0 && gemv_layout_takes(4, K)) return 4;
     // thin matrices: one workgroup (16 or 32 rows) per CU, all resident at once on the 256 CUs -- a second round of
     // workgroups would double the serial chain time
     if (lane_rows <= 16 * 256) return 16;
@@ -527,7 +528,7 @@ static int model_alloc(lnb_model* m) {
     m->layers.resize(layer_end - layer_begin);
     // block heights of the resident layouts, each knob read once per model: 24-row wq|wk|wv blocks (gemv_quad_kernel) / 56-row gate|up blocks when that puts one block on every CU (the 8B shape)
     const int qkv_rows = m->q_dim + 2 * m->kv_dim, rwo = auto_rw(dim, Knob::RW_WO, m->q_dim, true), rw2 = auto_rw(dim, Knob::RW_W2, F, true);
-    const int rwq = auto_rw(qkv_rows, Knob::RW_QKV, dim, false, qkv_rows == 24 * g_num_cus && dim % 256 == 0 ? 24 : 0);
+    const int rwq = auto_rw(qkv_rows, Knob::RW_QKV, dim, false, qkv_rows == 24 * g_num_cus && gemv_layout_takes(24, dim) ? 24 : 0);
     const int rw13 = auto_rw(F, Knob::RW_W13, 0, false, F == 56 * g_num_cus ? 56 : 0);
     for (int l = layer_begin; l < layer_end; l++) {
         LayerW& L = m->layers[l - layer_begin];
@@ -3600,7 +3601,7 @@ static int op_linear_impl(int device, const uint16_t* x, const uint16_t* norm_w,
     HIPCHK(lnbk_fast_init());
     if (mode != LNB_MODE_EXACT && mode != LNB_MODE_FAST) return fail("unknown mode %d", mode);
     if (rw == 0) rw = auto_rw(n_out, Knob::RW_OP, k_in, norm_w == nullptr);
-    if (rw != 16 && rw != 32 && rw != 64 && !(rw == 4 && !norm_w && k_in % 128 == 0 && k_in <= 16384) && !(rw == 24 && k_in % 256 == 0))
+    if (rw != 16 && rw != 32 && rw != 64 && !(rw == 4 && !norm_w && gemv_layout_takes(4, k_in)) && !(rw == 24 && gemv_layout_takes(24, k_in)))
         return fail("rw must be 16, 32 or 64 (or 4: row-broadcast layout, no fused norm, in_features a multiple of 128; or 24: quad layout, in_features a multiple of 256)");
     if ((size_t)k_in * 4 > 120 * 1024) return fail("in_features %d does not fit the LDS staging", k_in);
     DevArena a;                                             // every buffer of the call: released on every way out
@@ -3871,12 +3872,10 @@ extern "C" int lnb_op_rmsnorm_sum(int device, const uint16_t* x, int rows, int k
     HIPCHK(lnbk_init());
     if (form == LNB_NORM_BATCH_XT) HIPCHK(lnbk_batch_prepare());
     const bool alone = form == LNB_NORM_ROWS_WIDE || form == LNB_NORM_BATCH_XT || form == LNB_NORM_ROWS_WAVE;
-    const bool packed = form == LNB_NORM_GATE_UP56_PACKED || form == LNB_NORM_HEAD_PACKED;
-    // the smallest matrix the form takes: one row block (the packed head: one block of 128 rows)
-    const int rw = form == LNB_NORM_CHAIN16 ? 16 : form == LNB_NORM_CHAIN32 ? 32 : (form == LNB_NORM_CHAIN64 || form == LNB_NORM_HEAD_PACKED) ? 64 :
-                   (form == LNB_NORM_QUAD24 || form == LNB_NORM_QUAD24_SCHED) ? 24 : form == LNB_NORM_GATE_UP28 ? 28 : 56;
-    const int nch = (form == LNB_NORM_GATE_UP56 || form == LNB_NORM_GATE_UP28 || form == LNB_NORM_GATE_UP56_PACKED) ? 2 : 1;
-    const int n_out = form == LNB_NORM_HEAD_PACKED ? 128 : rw;
+    // the smallest matrix the form takes: one row block of its row in lnb_gemv_geom.h, in the resident layout that row reads (the packed head: one block of 128 rows)
+    const GemvGeom geom = alone ? GemvGeom{} : gemv_geom(gemv_report_geom(form));
+    const bool packed = geom.packed;
+    const int rw = geom.rw, nch = geom.resident_nch(), n_out = alone ? 0 : geom.block_rows();
     if (form == LNB_NORM_GATE_UP56_PACKED && !lnbk_w13p_supported(56, k_in)) return 1;
     if (form == LNB_NORM_HEAD_PACKED && !lnbk_headp_supported(k_in)) return 1;
     const size_t out_rows = alone ? (size_t)((rows + 15) & ~15) : 15;      // (batch_rmsnorm_xt_kernel<true> writes whole groups of 16 columns)

@@ -24,6 +24,7 @@
 #include <type_traits>
 #include "lnb_device.h"
 #include "lnb_seqsum.h"
+#include "lnb_gemv_geom.h"                                       // (XCh, rms_scratch_bytes, gq_ncw, GQ_SLOTS: what the launch checks share with the kernels)
 #include "lnb_wpack.h"
 #include "../../include/lnb.h"                                // (LNB_NORM_*: the forms of lnbk_gemv_norm_report)
 
@@ -85,8 +86,7 @@ DEVINL float4 mul4(const float4& x, float w0, float w1, float w2, float w3) {   
 // The global loads of x are ISSUED BEFORE the loaders start their LDS-DMA burst (barrier B0) -- otherwise the
 // 8 KB of x queue behind ~56 KiB of weight prefetch per CU (measured: +4 us per launch).
 // 512-element chunks per stager wave held in registers: 12 for the plain kernels (K up to 18k with 3 stagers), 6 for the
-// RMSNorm kernels (K = dim <= 8192; they also hold the norm weights and must stay clear of the 256-VGPR budget)
-template <bool NORM> struct XCh { static constexpr int value = NORM ? 6 : 12; };
+// RMSNorm kernels (K = dim <= 8192; they also hold the norm weights and must stay clear of the 256-VGPR budget): XCh<NORM> of lnb_gemv_geom.h
 // X_CH (deduced from the register arrays) is a compile-time property of the kernel instance: the launchers pick the smallest count that covers the
 // row (2 for K = 4096 -- round 5: the norm-fused kernels used to carry 6 chunks' worth of clamped loads, lane-varying compares and registers
 // through x_issue / x_store / x_normalize; of the 2 k cycles x_normalize took, ~1.7 k were control flow around five empty rounds)
@@ -140,8 +140,7 @@ DEVINL void x_store(const GemvParams& p, float* xs, int kpad, int sidx, int lane
 // lane; on the GPU: tests/test_gpu_parity.py through lnb_op_rmsnorm_linear); ~17 items + ~5 replayed leaves for gaussian x.
 // A leaf is seq_leaf_size(K, NH*64) terms (one leaf per folding lane; the last one may run into the zero padding).
 constexpr int RMS_HEAD = 256;
-__host__ __device__ inline size_t rms_scratch_bytes(int NH) { return (size_t)NH * (512 + 8 + 4 + 4 + 2048 + 8) + 64; }
-// LDS scratch (the idle product ring): SeqNode rec[NH][64] | uint64 items[NH] | float wtot[NH] | uint32 scan_failed[NH] |
+// LDS scratch (the idle product ring; rms_scratch_bytes of lnb_gemv_geom.h): SeqNode rec[NH][64] | uint64 items[NH] | float wtot[NH] | uint32 scan_failed[NH] |
 //                                      SeqItem list[NH][128] (each wave's items of the branch-free walk, in leaf order) | uint32 {count, uncovered}[NH] |
 //                                      64 spare bytes, of which the REPORT instantiations use the first 8: the walker's report address (rms_report_park)
 // Folding waves: every helper (-DLNB_RMS_NF_MAX=4 restricts the fold to four waves on four different SIMDs -- waves w and w+4 of a workgroup
@@ -166,9 +165,6 @@ __host__ __device__ inline size_t rms_scratch_bytes(int NH) { return (size_t)NH 
 #endif
 #ifndef LNB_EARLY_HEADP
 #define LNB_EARLY_HEADP 2                                   // the LM head from the 13-bit copy: 0 / 2 -> launch 151.6 / 150.1 us and 149.9 / 148.3 us on two boxes (same section)
-#endif
-#ifndef LNB_QUAD_R
-#define LNB_QUAD_R 5                                        // ring stages in flight per helper of gemv_quad_kernel<24, 256, ...> (A/B builds: 4, 6)
 #endif
 // (LNB_RMS_NF_MAX, rms_nf: lnb_seqsum.h -- the host emulation folds on the same wave counts)
 __host__ __device__ inline size_t rms_list_off(int NH) { return (size_t)NH * 528; }
@@ -974,8 +970,6 @@ __global__ __launch_bounds__((1 + NH) * 64) void gemv_chain_pk_report_kernel(Gem
 DEVINL void chain16q(float& acc, const float4& q) {
     asm volatile("s_nop 1\n\t" LNB_QADD4(0) LNB_QADD4(1) LNB_QADD4(2) LNB_QADD4(3) : "+v"(acc) : "v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w));
 }
-constexpr int GQ_SLOTS = 3;
-__host__ __device__ constexpr int gq_ncw(int RW) { return (RW + 15) / 16; }
 template <int RW, int KS, int NH, int R, int EPI, bool NORM, int XC = XCh<NORM>::value, bool TIMING = false>
 __global__ __launch_bounds__((gq_ncw(RW) + NH) * 64) void gemv_quad_kernel(GemvParams p) {
 #define LNB_QUAD_REPORT false
@@ -4824,71 +4818,61 @@ template <int MIN_HD = 32, class F> static hipError_t with_hd(const AttnParams* 
     return e;
 }
 
-// x staging: a whole number of stages (steps per stage = stage_bytes / (nch*rw*2)) + 64 floats of slack
-static size_t xs_bytes(int K, int steps_per_stage) { return ((size_t)((K + steps_per_stage - 1) / steps_per_stage) * steps_per_stage + 320) * 4 + 16; }
-
-template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, int XC, bool PK = false, bool REPORT = false>
-static hipError_t launch_chain_x(const GemvParams* p, hipStream_t st) {
-    static_assert(!NORM || rms_norm_helpers_has(NH), "a norm on this many helper waves: add it to LNB_RMS_NORM_HELPERS (lnb_seqsum.h)");
-    // kfn: production's instantiation; ktm: the one with the measurement code compiled in, launched exactly when p->dbg is set (the report kernels have none)
-    void (*kfn)(GemvParams), (*ktm)(GemvParams);
-    if constexpr (REPORT) { if constexpr (PK) kfn = gemv_chain_pk_report_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; else kfn = gemv_chain_report_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; ktm = kfn; }
-    else if constexpr (PK) { kfn = gemv_chain_pk_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; ktm = gemv_chain_pk_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC, true>; }
-    else { kfn = gemv_chain_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; ktm = gemv_chain_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC, true>; }
+// The launch functions of the one-token chain and quad kernels take a row of lnb_gemv_geom.h: the template arguments, the LDS, the checks and the tally row
+// are all the row's.
+#define X(name) static_assert((int)GEMV_REPORT_##name == LNB_NORM_##name, "lnb_gemv_geom.h and include/lnb.h number the report forms differently");
+LNB_GEMV_REPORTS(X)
+#undef X
+static_assert(gemv_geom(Geom::HEAD_PACKED).rw == WPACK_HEAD_RW && gemv_geom(Geom::HEAD_PACKED).nh * 64 == WPACK_HEAD_LANES, "lnb_wpack.h cuts the LM head for another geometry");
+// kfn: production's instantiation; ktm: the one with the measurement code compiled in, launched exactly when p->dbg is set (the report kernels have none)
+static hipError_t launch_row(const GemvGeom& g, void (*kfn)(GemvParams), void (*ktm)(GemvParams), const GemvParams* p, int epi, bool norm, int xc, hipStream_t st) {
     if (!p) return raise_lds(kfn, ktm);
-    size_t lds = 4 * (size_t)SA + xs_bytes(p->K, SA / (NCH * RW * 2));
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (xs_bytes(p->K, SA / (NCH * RW * 2)) / 4 > (size_t)XC * (1 + NH) * 512) return hipErrorInvalidValue;   // x staging registers
-    if (NORM && (rms_scratch_bytes(rms_nf(NH)) > 4 * (size_t)SA || seq_leaf_size(p->K, rms_nf(NH) * 64) > 256)) return hipErrorInvalidValue;   // records live in the idle ring; leaf over-read stays inside the x padding
-    form_ran(PK ? (EPI == EPI_STORE2 ? Form::GEMV_HEAD_PK : Form::GEMV_CHAIN_PK) : RW == 16 ? Form::GEMV_CHAIN_16 : RW == 28 ? Form::GEMV_CHAIN_28 : RW == 32 ? Form::GEMV_CHAIN_32 : RW == 56 ? (R == 6 ? Form::GEMV_CHAIN_56_TP : Form::GEMV_CHAIN_56) : Form::GEMV_CHAIN_64, EPI == EPI_STORE2 ? EPI_STORE : EPI);
-    hipLaunchKernelGGL(p->dbg ? ktm : kfn, dim3((unsigned)(p->S * p->n_wg)), dim3((1 + NH) * 64), lds, st, *p);
+    if (!gemv_geom_fits(g, p->K, norm, xc)) return hipErrorInvalidValue;
+    form_ran(g.form, epi == EPI_STORE2 ? EPI_STORE : epi);
+    hipLaunchKernelGGL(p->dbg ? ktm : kfn, dim3((unsigned)(p->S * p->n_wg)), dim3(g.waves() * 64), g.ring_bytes() + xs_bytes(p->K, g.steps()), st, *p);
     return hipGetLastError();
 }
-// x staging chunks per stager wave: the norm-fused kernels are instantiated for 2, 3 and 6 chunks of 512 elements per wave (K up to ~4 K, ~6 K / 12 K with
-// the 70B-like shape's 8192 in the middle one, 24 K) and the smallest that holds the padded row is launched; the plain kernels keep their 12
-template <int RW, int NCH, int SA, int NH, int R, int EPI, bool NORM, bool PK = false, bool REPORT = false>
+template <Geom ID, int EPI, bool NORM, int XC, bool REPORT = false>
+static hipError_t launch_chain_x(const GemvParams* p, hipStream_t st) {
+    constexpr GemvGeom G = gemv_geom(ID);
+    constexpr int RW = G.rw, NCH = G.nch, SA = G.stage, NH = G.nh, R = G.r;
+    static_assert(!NORM || rms_norm_helpers_has(NH), "a norm on this many helper waves: add it to LNB_RMS_NORM_HELPERS (lnb_seqsum.h)");
+    void (*kfn)(GemvParams), (*ktm)(GemvParams);
+    if constexpr (REPORT) { if constexpr (G.packed) kfn = gemv_chain_pk_report_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; else kfn = gemv_chain_report_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; ktm = kfn; }
+    else if constexpr (G.packed) { kfn = gemv_chain_pk_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; ktm = gemv_chain_pk_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC, true>; }
+    else { kfn = gemv_chain_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC>; ktm = gemv_chain_kernel<RW, NCH, SA, NH, R, EPI, NORM, XC, true>; }
+    return launch_row(gemv_geom(ID), kfn, ktm, p, EPI, NORM, XC, st);
+}
+// the smallest x staging chunk count that holds the padded row (gemv_geom_chunks); prepare: every one the kernels are instantiated for
+template <Geom ID, int EPI, bool NORM, bool REPORT = false>
 static hipError_t launch_chain_t(const GemvParams* p, hipStream_t st) {
     if constexpr (NORM) {
-        if (!p) {
-            hipError_t e = launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 2, PK, REPORT>(p, st);
-            if (e == hipSuccess) e = launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 3, PK, REPORT>(p, st);
-            return e != hipSuccess ? e : launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, XCh<NORM>::value, PK, REPORT>(p, st);
-        }
-        const size_t need = xs_bytes(p->K, SA / (NCH * RW * 2)) / 4, per = (size_t)(1 + NH) * 512;
-        if (need <= 2 * per) return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 2, PK, REPORT>(p, st);
-        if (need <= 3 * per) return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, 3, PK, REPORT>(p, st);
+        const int xc = p ? gemv_geom_chunks(gemv_geom(ID), p->K, NORM) : 0;
+        hipError_t e = hipSuccess;
+        if (!p || xc == 2) e = launch_chain_x<ID, EPI, NORM, 2, REPORT>(p, st);
+        if (p ? xc == 3 : e == hipSuccess) e = launch_chain_x<ID, EPI, NORM, 3, REPORT>(p, st);
+        if (p ? xc == 2 || xc == 3 : e != hipSuccess) return e;
     }
-    return launch_chain_x<RW, NCH, SA, NH, R, EPI, NORM, XCh<NORM>::value, PK, REPORT>(p, st);
+    return launch_chain_x<ID, EPI, NORM, XCh<NORM>::value, REPORT>(p, st);
 }
 
-template <int RW, int KS, int NH, int R, int EPI, bool NORM, int XC, bool REPORT = false>
+template <Geom ID, int EPI, bool NORM, int XC, bool REPORT = false>
 static hipError_t launch_quad_x(const GemvParams* p, hipStream_t st) {
+    constexpr GemvGeom G = gemv_geom(ID);
+    constexpr int RW = G.rw, KS = G.stage, NH = G.nh, R = G.r;
     static_assert(!NORM || rms_norm_helpers_has(NH), "a norm on this many helper waves: add it to LNB_RMS_NORM_HELPERS (lnb_seqsum.h)");
-    void (*kfn)(GemvParams), (*ktm)(GemvParams);                                 // (ktm: as in launch_chain_x)
+    void (*kfn)(GemvParams), (*ktm)(GemvParams);
     if constexpr (REPORT) { kfn = gemv_quad_report_kernel<RW, KS, NH, R, EPI, NORM, XC>; ktm = kfn; }
     else { kfn = gemv_quad_kernel<RW, KS, NH, R, EPI, NORM, XC>; ktm = gemv_quad_kernel<RW, KS, NH, R, EPI, NORM, XC, true>; }
-    if (!p) return raise_lds(kfn, ktm);
-    constexpr int NW = gq_ncw(RW) + NH;
-    constexpr size_t SB = (size_t)RW * KS * 4;
-    if (p->K % KS) return hipErrorInvalidValue;                                  // whole stages only (auto_rw in lnb_api.cpp picks this layout accordingly)
-    const size_t lds = GQ_SLOTS * SB + xs_bytes(p->K, KS);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (xs_bytes(p->K, KS) / 4 > (size_t)XC * NW * 512) return hipErrorInvalidValue;     // x staging registers
-    if (NORM && (rms_scratch_bytes(rms_nf(NH)) > GQ_SLOTS * SB || seq_leaf_size(p->K, rms_nf(NH) * 64) > 256)) return hipErrorInvalidValue;
-    form_ran(Form::GEMV_QUAD, EPI);
-    hipLaunchKernelGGL(p->dbg ? ktm : kfn, dim3((unsigned)(p->S * p->n_wg)), dim3(NW * 64), lds, st, *p);
-    return hipGetLastError();
+    return launch_row(gemv_geom(ID), kfn, ktm, p, EPI, NORM, XC, st);
 }
-template <int RW, int KS, int NH, int R, int EPI, bool NORM, bool REPORT = false>
+template <Geom ID, int EPI, bool NORM, bool REPORT = false>
 static hipError_t launch_quad_t(const GemvParams* p, hipStream_t st) {
     if constexpr (NORM) {
-        if (!p) {
-            hipError_t e = launch_quad_x<RW, KS, NH, R, EPI, NORM, 2, REPORT>(p, st);
-            return e != hipSuccess ? e : launch_quad_x<RW, KS, NH, R, EPI, NORM, XCh<NORM>::value, REPORT>(p, st);
-        }
-        if (xs_bytes(p->K, KS) / 4 <= (size_t)2 * (gq_ncw(RW) + NH) * 512) return launch_quad_x<RW, KS, NH, R, EPI, NORM, 2, REPORT>(p, st);
+        const bool two = p && gemv_geom_chunks(gemv_geom(ID), p->K, NORM) == 2;
+        if (!p || two) { const hipError_t e = launch_quad_x<ID, EPI, NORM, 2, REPORT>(p, st); if (two || e != hipSuccess) return e; }
     }
-    return launch_quad_x<RW, KS, NH, R, EPI, NORM, XCh<NORM>::value, REPORT>(p, st);
+    return launch_quad_x<ID, EPI, NORM, XCh<NORM>::value, REPORT>(p, st);
 }
 
 template <int EPI, bool NORM, int NCH>
@@ -4900,7 +4884,7 @@ static hipError_t launch_gemv_rw(const GemvParams* p, int rw, hipStream_t st) {
     // Throughput schedule (GemvParams.sched, lnb_ctx_set_schedule): the same kernel with 128-step stages -- 3 x 12 KiB of products + x = 55 KB of LDS
     // instead of 91 KB, so that a workgroup fits a CU beside the gate|up workgroup (75 KB) of another context's step; twice the stage barriers
     // (slower alone, which is why one stream keeps the 256-step form), ten stages of one load per helper in flight = the same 60 KiB per CU.
-    if constexpr (NCH == 1) if (rw == 24) return either(p && p->sched, launch_quad_t<24, 128, 6, 10, EPI, NORM>, launch_quad_t<24, 256, 6, LNB_QUAD_R, EPI, NORM>);
+    if constexpr (NCH == 1) if (rw == 24) return either(p && p->sched, launch_quad_t<Geom::QUAD24_SCHED, EPI, NORM>, launch_quad_t<Geom::QUAD24, EPI, NORM>);
     // stage geometry (one workgroup per CU).  SA = bf16 bytes per stage, R = stages in flight per helper.
     //  RW 16/32 plain (thin; chain bound): 8 KiB stages, 2 helpers x 4 loads x 7 stages = 56 KiB in flight per CU.
     //  RW 32 with the fused RMSNorm (wq|wk|wv): six helpers so that the exact parallel norm sum has 384 folding lanes, and
@@ -4909,8 +4893,8 @@ static hipError_t launch_gemv_rw(const GemvParams* p, int rw, hipStream_t st) {
     //  RW 64 (fat; HBM bound): 12 KiB stages, six helpers paired on three SIMDs (the chain wave owns the fourth),
     //  6 x 2 loads x 8 stages = 96 KiB in flight per CU (5 stages: 5.8 TB/s on the LM head, 8: 6.2, 14: worse again).
     // very long rows (70B-like w2: K = 28672): x needs more staging registers than three stager waves hold -> four helpers (prepare: these, then on)
-    if (!NORM && NCH == 1 && (rw == 16 || rw == 32) && (!p || xs_bytes(p->K, 8192 / (rw * 2)) / 4 > (size_t)XCh<false>::value * 3 * 512)) {
-        const hipError_t e = rw == 16 ? launch_chain_t<16, 1, 8192, 4, 7, EPI, false>(p, st) : launch_chain_t<32, 1, 8192, 4, 7, EPI, false>(p, st);
+    if (!NORM && NCH == 1 && (rw == 16 || rw == 32) && (!p || !gemv_geom_fits(gemv_geom(rw == 16 ? Geom::CHAIN16 : Geom::CHAIN32), p->K, false, XCh<false>::value))) {
+        const hipError_t e = rw == 16 ? launch_chain_t<Geom::CHAIN16_LONG, EPI, false>(p, st) : launch_chain_t<Geom::CHAIN32_LONG, EPI, false>(p, st);
         if (p || e != hipSuccess) return e;
     }
     // rung (a') of the FFN ladder (profiles/r06_ffn_stream.md; LNB_RW_W2=16 LNB_W2_QUAD=1, measurement only): the down projection's 16 rows per CU on ONE
@@ -4918,37 +4902,35 @@ static hipError_t launch_gemv_rw(const GemvParams* p, int rw, hipStream_t st) {
     if constexpr (NCH == 1 && !NORM && (EPI == EPI_RESID || EPI == EPI_STORE)) {
         const int quad16 = p ? knob(Knob::W2_QUAD) : 0;
         if (rw == 16 && (!p || (quad16 && p->K % 128 == 0))) {
-            const hipError_t e = either(quad16 == 2, launch_quad_t<16, 256, 4, 7, EPI, false>, launch_quad_t<16, 128, 4, 14, EPI, false>);
+            const hipError_t e = either(quad16 == 2, launch_quad_t<Geom::QUAD16_256, EPI, false>, launch_quad_t<Geom::QUAD16_128, EPI, false>);
             if (p || e != hipSuccess) return e;
         }
     }
-    if (rw == 16) return launch_chain_t<16, NCH, 8192, 2, 7, EPI, NORM>(p, st);
-    if (rw == 32) return (NORM && NCH == 1) ? launch_chain_t<32, 1, 12288, 6, 5, EPI, NORM>(p, st) : launch_chain_t<32, NCH, 8192, 2, 7, EPI, NORM>(p, st);
-    if (rw == 64) return launch_chain_t<64, NCH, 12288, 6, 8, EPI, NORM>(p, st);
+    if (rw == 16) return launch_chain_t<NCH == 2 ? Geom::CHAIN16_X2 : Geom::CHAIN16, EPI, NORM>(p, st);
+    if (rw == 32) return (NORM && NCH == 1) ? launch_chain_t<Geom::CHAIN32_NORM, EPI, NORM>(p, st) : launch_chain_t<NCH == 2 ? Geom::CHAIN32_X2 : Geom::CHAIN32, EPI, NORM>(p, st);
+    if (rw == 64) return launch_chain_t<NCH == 2 ? Geom::CHAIN64_X2 : Geom::CHAIN64, EPI, NORM>(p, st);
     // RW 56 (two chains only): 28672 gate/up rows = 256 blocks of 56 x 2 -- one block per CU on ALL 256 CUs instead of 224 of them;
     // seven helpers (448 lanes = one (k-chunk, row) pair each), 64-step stages
     // (throughput schedule: six ring stages instead of eight -- 133 instead of 149 VGPRs, so that two of its waves and two of the 128-step
     // wq|wk|wv kernel's fit one SIMD's 512 registers: a gate|up workgroup of one context beside a wq|wk|wv workgroup of another)
-    if constexpr (NCH == 2) if (rw == 56) return either(p && p->sched && knob(Knob::TP_W13), launch_chain_t<56, 2, 14336, 7, 6, EPI, NORM>, launch_chain_t<56, 2, 14336, 7, 8, EPI, NORM>);
+    if constexpr (NCH == 2) if (rw == 56) return either(p && p->sched && knob(Knob::TP_W13), launch_chain_t<Geom::CHAIN56_TP, EPI, NORM>, launch_chain_t<Geom::CHAIN56, EPI, NORM>);
     // RW 28 (two chains, LNB_RW_W13=28): the same stream cut into 512 half-height blocks, two per workgroup -- rows [0, F/2) are complete
     // after the first block of every workgroup: the row-band order a w1|w3 -> w2 pipeline needs (measurement, NOTES.md 6.1)
-    if constexpr (NCH == 2) if (rw == 28) return launch_chain_t<28, 2, 14336, 7, 8, EPI, NORM>(p, st);
+    if constexpr (NCH == 2) if (rw == 28) return launch_chain_t<Geom::CHAIN28, EPI, NORM>(p, st);
     return hipErrorInvalidValue;
 }
 
 // The one-token gate|up product of 56-row blocks from the 13-bit planar copy (GemvParams.wp, lnb_wpack.h): 128-step stages -- one 32-weight group per helper
 // lane -- so 2 x 56 KB of products + x = 132 KB of LDS; LNB_W13P_R stages of 52 bytes per lane in flight (5: the raw form's 114 KB per CU)
-#ifndef LNB_W13P_R
-#define LNB_W13P_R 5
-#endif
-#define WPACK_LANES_W13 (7 * 64)
-extern "C" int lnbk_w13p_supported(int rw, int K) {
-    return rw == 56 && K > 0 && K % 8 == 0 && 4 * (size_t)28672 + xs_bytes(K, 128) <= 160 * 1024 && xs_bytes(K, 128) / 4 <= (size_t)XCh<true>::value * 8 * 512 && seq_leaf_size(K, rms_nf(7) * 64) <= 256;
+#define WPACK_LANES_W13 (gemv_geom(Geom::W13_PACKED).nh * 64)
+// a packed row's launch (always norm-fused): gate|up, or the LM head's blocks of two chains stored side by side
+template <Geom ID, bool REPORT = false> static hipError_t launch_packed(const GemvParams* p, hipStream_t st) {
+    constexpr bool HEAD = gemv_geom(ID).form == Form::GEMV_HEAD_PK;
+    if (p && (!p->wp || !gemv_packed_takes(gemv_geom(ID), p->K) || (HEAD && (p->S != 1 || p->n_blocks != wpack_head_blocks(p->n_rows))))) return hipErrorInvalidValue;
+    return launch_chain_t<ID, HEAD ? EPI_STORE2 : EPI_SILU_MUL, true, REPORT>(p, st);
 }
-extern "C" hipError_t lnbk_gemv_w13p(const GemvParams* p, hipStream_t st) {
-    if (p && (!p->wp || !lnbk_w13p_supported(56, p->K))) return hipErrorInvalidValue;
-    return launch_chain_t<56, 2, 28672, 7, LNB_W13P_R, EPI_SILU_MUL, true, true>(p, st);
-}
+extern "C" int lnbk_w13p_supported(int rw, int K) { return rw == gemv_geom(Geom::W13_PACKED).rw && gemv_packed_takes(gemv_geom(Geom::W13_PACKED), K); }
+extern "C" hipError_t lnbk_gemv_w13p(const GemvParams* p, hipStream_t st) { return launch_packed<Geom::W13_PACKED>(p, st); }
 extern "C" size_t lnbk_wpack_w13_bytes(int n_blocks, int K) { return wpack_bytes(n_blocks, K, WPACK_LANES_W13, 56); }
 // d_stats: four words on the device; on return (after the stream has run) the matrix's WpackStats
 extern "C" hipError_t lnbk_wpack_stats(const uint16_t* w, size_t elems, unsigned* d_stats, hipStream_t st) {
@@ -4968,36 +4950,29 @@ extern "C" hipError_t lnbk_wpack_w13(const uint16_t* w, void* out, int K, int n_
 // which at 13/16 of the bytes would be the bound (7.83 blocks x 4096 steps = 123 us); two chains through one v_pk_add_f32 walk half the blocks at 6.0.
 // Eight helpers (512 lanes, one 32-weight group each), 128-step stages: 2 x 64 KB of products + x = 149 KB of LDS; nine waves = three on one SIMD, so the
 // instance has 168 VGPRs at most; LNB_HEADP_R stages of 52 bytes per lane in flight (5: 133 KB per CU).
-#ifndef LNB_HEADP_R
-#define LNB_HEADP_R 5
-#endif
-extern "C" int lnbk_headp_supported(int K) {
-    return K > 0 && K % 8 == 0 && 4 * (size_t)32768 + xs_bytes(K, 128) <= 160 * 1024 && xs_bytes(K, 128) / 4 <= (size_t)XCh<true>::value * 9 * 512 && seq_leaf_size(K, rms_nf(8) * 64) <= 256;
-}
+extern "C" int lnbk_headp_supported(int K) { return gemv_packed_takes(gemv_geom(Geom::HEAD_PACKED), K); }
 // p->w: unused; p->n_blocks / p->n_wg count 128-row blocks
-extern "C" hipError_t lnbk_gemv_headp(const GemvParams* p, hipStream_t st) {
-    if (p && (!p->wp || p->S != 1 || !lnbk_headp_supported(p->K) || p->n_blocks != wpack_head_blocks(p->n_rows))) return hipErrorInvalidValue;
-    return launch_chain_t<WPACK_HEAD_RW, 2, 32768, WPACK_HEAD_LANES / 64, LNB_HEADP_R, EPI_STORE2, true, true>(p, st);
-}
+extern "C" hipError_t lnbk_gemv_headp(const GemvParams* p, hipStream_t st) { return launch_packed<Geom::HEAD_PACKED>(p, st); }
 extern "C" size_t lnbk_wpack_head_bytes(int N, int K) { return wpack_head_bytes(N, K); }
-// lnb_op_rmsnorm_sum: the norm-fused kernel of `form` (LNB_NORM_CHAIN16 .. LNB_NORM_HEAD_PACKED of include/lnb.h) in its REPORT instantiation -- the same template arguments, launch
-// function, checks and tally row as the production launch, with the norm's report (p->norm_out) compiled in.  Never inside a stream capture (it raises the
-// instantiation's dynamic-LDS limit first).
-template <class F> static hipError_t report_launch(F f, const GemvParams* p, hipStream_t st) { const hipError_t e = f(nullptr, st); return e != hipSuccess ? e : f(p, st); }
+// lnb_op_rmsnorm_sum: the norm-fused kernel of `form` (LNB_NORM_CHAIN16 .. LNB_NORM_HEAD_PACKED of include/lnb.h) in its REPORT instantiation -- the table row that
+// serves the form, through the launch function, checks and tally row of the production launch, with the norm's report (p->norm_out) compiled in and the
+// epilogue its matrix has in production.  Never inside a stream capture (it raises the instantiation's dynamic-LDS limit first).
+template <Geom ID> static hipError_t report_launch(const GemvParams* p, hipStream_t st) {
+    static_assert(ID != Geom::COUNT, "a fused kernel's report form without a row in lnb_gemv_geom.h");
+    constexpr GemvGeom G = gemv_geom(ID);
+    hipError_t (*f)(const GemvParams*, hipStream_t);
+    if constexpr (G.packed) f = launch_packed<ID, true>;
+    else if constexpr (G.quad) f = launch_quad_t<ID, EPI_STORE, true, true>;
+    else f = launch_chain_t<ID, G.nch == 2 ? EPI_SILU_MUL : EPI_STORE, true, true>;
+    const hipError_t e = f(nullptr, st);
+    return e != hipSuccess ? e : f(p, st);
+}
 extern "C" hipError_t lnbk_gemv_norm_report(const GemvParams* p, int form, hipStream_t st) {
     if (!p || !p->norm_w || !p->norm_out) return hipErrorInvalidValue;
     switch (form) {
-        case LNB_NORM_CHAIN16: return report_launch(launch_chain_t<16, 1, 8192, 2, 7, EPI_STORE, true, false, true>, p, st);
-        case LNB_NORM_CHAIN32: return report_launch(launch_chain_t<32, 1, 12288, 6, 5, EPI_STORE, true, false, true>, p, st);
-        case LNB_NORM_CHAIN64: return report_launch(launch_chain_t<64, 1, 12288, 6, 8, EPI_STORE, true, false, true>, p, st);
-        case LNB_NORM_QUAD24: return report_launch(launch_quad_t<24, 256, 6, LNB_QUAD_R, EPI_STORE, true, true>, p, st);
-        case LNB_NORM_QUAD24_SCHED: return report_launch(launch_quad_t<24, 128, 6, 10, EPI_STORE, true, true>, p, st);
-        case LNB_NORM_GATE_UP56: return report_launch(launch_chain_t<56, 2, 14336, 7, 8, EPI_SILU_MUL, true, false, true>, p, st);
-        case LNB_NORM_GATE_UP28: return report_launch(launch_chain_t<28, 2, 14336, 7, 8, EPI_SILU_MUL, true, false, true>, p, st);
-        case LNB_NORM_GATE_UP56_PACKED: if (!p->wp || !lnbk_w13p_supported(56, p->K)) return hipErrorInvalidValue;
-                return report_launch(launch_chain_t<56, 2, 28672, 7, LNB_W13P_R, EPI_SILU_MUL, true, true, true>, p, st);
-        case LNB_NORM_HEAD_PACKED: if (!p->wp || p->S != 1 || !lnbk_headp_supported(p->K) || p->n_blocks != wpack_head_blocks(p->n_rows)) return hipErrorInvalidValue;
-                return report_launch(launch_chain_t<WPACK_HEAD_RW, 2, 32768, WPACK_HEAD_LANES / 64, LNB_HEADP_R, EPI_STORE2, true, true, true>, p, st);
+#define X(name) case LNB_NORM_##name: return report_launch<gemv_report_geom(LNB_NORM_##name)>(p, st);
+        LNB_GEMV_REPORTS(X)
+#undef X
         default: return hipErrorInvalidValue;
     }
 }
@@ -5013,7 +4988,7 @@ template <int EPI> static hipError_t launch_rowcast(const GemvParams* p, hipStre
     const auto kfn = (p && p->dbg) ? rowcast_kernel<EPI, true> : rowcast_kernel<EPI>;
     const auto kl = (p && p->dbg) ? rowcast_lds_kernel<EPI, true> : rowcast_lds_kernel<EPI>;
     if (!p) return raise_lds(kl, kfn, rowcast_lds_kernel<EPI, true>, rowcast_kernel<EPI, true>);
-    if ((p->K & 127) || p->K > 16384) return hipErrorInvalidValue;              // x staging: 8 x 16 B per thread, K*4 bytes of LDS
+    if (!gemv_layout_takes(4, p->K)) return hipErrorInvalidValue;                // x staging: 8 x 16 B per thread, K*4 bytes of LDS
     // helper-fed chain waves (rowcast_lds_kernel) whenever K is a whole number of its 512-step stages; LNB_ROWCAST_LDS=0: the self-feeding kernel
     // (throughput schedule: the self-feeding kernel -- four waves and K * 4 bytes of LDS instead of eight waves and 96 KB + K * 2: co-resident with
     // another context's gate|up workgroup, NOTES R5)
@@ -5027,23 +5002,18 @@ template <int EPI> static hipError_t launch_rowcast(const GemvParams* p, hipStre
     return hipGetLastError();
 }
 
+// the (chains, epilogue, norm) combinations lnbk_gemv has kernels for; the row-broadcast layout (thin matrices): one chain, no norm
+constexpr bool gemv_dispatches(int rw, int nch, int epi, bool norm) {
+    if (rw == 4 && (nch != 1 || norm)) return false;
+    return nch == 2 ? epi == EPI_SILU_MUL && norm : epi == EPI_STORE || (epi == EPI_QKV_ROPE && norm) || (epi == EPI_RESID && !norm);
+}
 extern "C" hipError_t lnbk_gemv(const GemvParams* p, int rw, int nch, int epi, int norm, hipStream_t st) {
-    if (rw == 4) {                                           // row-broadcast layout (thin matrices)
-        if (nch != 1 || norm) return hipErrorInvalidValue;
-        if (epi == EPI_STORE) return launch_rowcast<EPI_STORE>(p, st);
-        if (epi == EPI_RESID) return launch_rowcast<EPI_RESID>(p, st);
-        return hipErrorInvalidValue;
-    }
-    if (nch == 2) {
-        if (epi == EPI_SILU_MUL && norm) return launch_gemv_rw<EPI_SILU_MUL, true, 2>(p, rw, st);
-        return hipErrorInvalidValue;
-    }
-    switch (epi) {
-        case EPI_STORE: return norm ? launch_gemv_rw<EPI_STORE, true, 1>(p, rw, st) : launch_gemv_rw<EPI_STORE, false, 1>(p, rw, st);
-        case EPI_QKV_ROPE: return norm ? launch_gemv_rw<EPI_QKV_ROPE, true, 1>(p, rw, st) : hipErrorInvalidValue;
-        case EPI_RESID: return norm ? hipErrorInvalidValue : launch_gemv_rw<EPI_RESID, false, 1>(p, rw, st);
-        default: return hipErrorInvalidValue;
-    }
+    if (!gemv_dispatches(rw, nch, epi, norm != 0)) return hipErrorInvalidValue;
+    if (rw == 4) return epi == EPI_STORE ? launch_rowcast<EPI_STORE>(p, st) : launch_rowcast<EPI_RESID>(p, st);
+    if (nch == 2) return launch_gemv_rw<EPI_SILU_MUL, true, 2>(p, rw, st);
+    if (epi == EPI_QKV_ROPE) return launch_gemv_rw<EPI_QKV_ROPE, true, 1>(p, rw, st);
+    if (epi == EPI_RESID) return launch_gemv_rw<EPI_RESID, false, 1>(p, rw, st);
+    return norm ? launch_gemv_rw<EPI_STORE, true, 1>(p, rw, st) : launch_gemv_rw<EPI_STORE, false, 1>(p, rw, st);
 }
 
 template <int EPI, int NCH> static hipError_t launch_gemm(const GemmParams* p, hipStream_t st) {
@@ -5269,13 +5239,14 @@ extern "C" hipError_t lnbk_init(void) {
     if (done) return hipSuccess;
     hipError_t e = raise_lds(rmsnorm_rows_kernel<false>, rmsnorm_rows_kernel<true>);           // (lnbk_rmsnorm_rows' other form stays within the 64 KiB every kernel gets)
     for (int ep = EPI_STORE; ep <= EPI_SILU_MUL && e == hipSuccess; ep++) e = lnbk_gemm(nullptr, ep, nullptr);
-    // every (rows per block, chains, epilogue, norm) lnbk_gemv has kernels for
-    auto gemv = [&](int rw, int nch, int epi, int norm) { if (e == hipSuccess) e = lnbk_gemv(nullptr, rw, nch, epi, norm, nullptr); };
-    gemv(4, 1, EPI_STORE, 0); gemv(4, 1, EPI_RESID, 0); gemv(56, 2, EPI_SILU_MUL, 1); gemv(28, 2, EPI_SILU_MUL, 1);
-    for (int rw : {16, 24, 32, 64}) {
-        gemv(rw, 1, EPI_STORE, 1); gemv(rw, 1, EPI_STORE, 0); gemv(rw, 1, EPI_QKV_ROPE, 1); gemv(rw, 1, EPI_RESID, 0);
-        if (rw != 24) gemv(rw, 2, EPI_SILU_MUL, 1);
-    }
+    // the row-broadcast layout and every raw row of lnb_gemv_geom.h, each under every (epilogue, norm) lnbk_gemv dispatches its (rows per block, chains) to;
+    // the two packed rows
+    auto gemv = [&](int rw, int nch) {
+        for (int epi = EPI_STORE; epi <= EPI_SILU_MUL; epi++)
+            for (int norm = 0; norm <= 1; norm++) if (e == hipSuccess && gemv_dispatches(rw, nch, epi, norm != 0)) e = lnbk_gemv(nullptr, rw, nch, epi, norm, nullptr);
+    };
+    gemv(4, 1);
+    for (const GemvGeom& g : LNB_GEMV_GEOM_TABLE) if (!g.packed) gemv(g.rw, g.nch);
     if (e == hipSuccess) e = lnbk_gemv_w13p(nullptr, nullptr);
     if (e == hipSuccess) e = lnbk_gemv_headp(nullptr, nullptr);
     for (auto prepare : {launch_attn_long<true>, launch_attn_long<false>, launch_attn_one, launch_attn_short}) if (e == hipSuccess) e = prepare(nullptr, nullptr);

@@ -222,7 +222,7 @@ SEQ_HD SeqSplit seq_split_leaf(const float* p, int n, float lo, float hi) {
 #define LNB_RMS_NF_MAX 8
 #endif
 SEQ_HD constexpr int rms_nf(int NH) { return NH > LNB_RMS_NF_MAX ? LNB_RMS_NF_MAX : NH; }
-// helper waves of the kernels that carry a norm (their NH template arguments in lnb_kernels.hip / BN_NH of lnb_batch_kernels.h): 16-row chain; 32- / 64-row
+// helper waves of the kernels that carry a norm (the helper-wave column of lnb_gemv_geom.h / BN_NH of lnb_batch_kernels.h): 16-row chain; 32- / 64-row
 // chain, 24-row quad and the two stand-alone norm kernels; gate|up (raw and packed); the packed LM head
 #define LNB_RMS_NORM_HELPERS {2, 6, 7, 8}
 // every launch function of a norm-carrying kernel asserts this of its NH (lnb_kernels.hip: launch_chain_x, launch_quad_x, BN_NH): a new helper count cannot
