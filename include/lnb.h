@@ -546,8 +546,9 @@ int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int iters, float*
  *   token lnb_decode_sample_until emits at position p is sample(row_p, sampler, p) and depends on nothing else; column i of a verify pass has
  *   row_{pos + i} exactly, so the greedy acceptance rule holds with "the sampler's token of column i at position pos + i" in place of the argmax.
  *   No distribution is compared and there is no tolerance: the output is the sampling loop's token sequence, the same bits, in fewer passes.
- * Out of scope: rejection sampling against a draft MODEL, pipeline ticks, recording the sampled token's probability, min-p, repetition penalties,
- *   logit bias. */
+ * Out of scope: rejection sampling against a draft MODEL, pipeline ticks, recording the sampled token's probability.  Logit bias, repetition
+ *   penalties and min-p: the rules calls below; under rules the speculative loops, pipeline ticks and token-probability records are out of scope
+ *   (the acceptance argument survives rules, but a verify pass would need per-column count deltas). */
 #define LNB_SAMPLE_MAX_VOCAB 131072
 typedef struct lnb_sampler { float temperature; float top_p; int32_t top_k; int32_t reserved; uint64_t seed; } lnb_sampler;
 typedef struct lnb_sample_info { uint64_t w_all, w_topk, w_kept; int32_t n_candidates, n_kept, degenerate, pad; } lnb_sample_info;
@@ -557,6 +558,50 @@ int lnb_batch_decode_sample_until(lnb_batch* b, const lnb_sampler* samplers, con
                                   int32_t* out_tokens, int32_t* n_generated, int32_t* finished, float* ms_out);
 int lnb_op_sample(int device, const uint16_t* logits_bf16, int rows, int V, const lnb_sampler* samplers, const int32_t* pos,
                   const uint64_t* draws, int32_t* tokens_out, lnb_sample_info* info);
+/* ---- logit rules in the sampling loops: logit bias, repetition / presence / frequency penalties, min-p ----
+ * A step 0 in front of step 1 and a step 4b behind step 4 of the rule above (csrc/lnb_sample.h; tests/logit_rules_ref.py restates them).  c_j = the
+ * number of occurrences of token j in the COUNTED TEXT: the caller's counted[0 .. n_counted), then the call's `token`, then every token the call has
+ * emitted before this step -- exact 32-bit counts.  Per entry, from f = f32(x_j); every operation is ONE IEEE f32 operation, never an fma, and every
+ * sub-step's result is truncated to bf16:
+ *   0a. c_j > 0 and repetition_penalty != 1:  f = trunc_bf16(f > 0 ? f / rp : f * rp)
+ *   0b. c_j > 0 and (presence != 0 or frequency != 0):  t = frequency * f32(c_j); t = presence + t; f = trunc_bf16(f - t)
+ *   0c. n_bias > 0:  f = trunc_bf16(f + f32(bias_j)) for EVERY j; bias_j = the listed value truncated to bf16, +0 for an unlisted id; -inf bans a token
+ *   4b. M = uint64(f64(min_p) * f64(w_a)), w_a = the weight of the maximum; S = {j: w_j >= max(M, 1)}; n_candidates and w_all describe this S
+ * Steps 1-8 run on the adjusted row.  temperature == 0 is ml.Argmax of the ADJUSTED row.  The token is a pure function of (logits row, sampler, rules,
+ * counted text, pos): a run gives the same tokens whatever its chunking if the caller hands the earlier chunks' tokens back in `counted`, a batch
+ * member gives the tokens of its own single run, and rules that are all off give lnb_decode_sample_until's tokens bit for bit.
+ * lnb_decode_sample_rules_until: lnb_decode_sample_until under the rules; stop ids, finished flag, token log and error latch unchanged (a stop id
+ *   freezes the counts with everything else).  Captured graphs of its own beside the greedy and plain-sampling ones (none is dropped or recaptured
+ *   for another); they hold pointers to the device copies of the sampler, the rules and the context's two tables (uint32 counts[V], bf16 bias[V],
+ *   allocated on first use, rebuilt by every call before its first step), so another rule set replays the same graph.
+ * lnb_batch_decode_sample_rules_until: one sampler, one rule set and one counted text per member (rules[n], counted[n] pointers, n_counted[n]);
+ *   start_pos[s] < 0 freezes a member, whose rules and counted text are then not looked at beyond the checks.
+ * lnb_op_sample_rules: the kernel on host rows, as lnb_op_sample; counts [rows][V] uint32 (NULL: all zero) are the c_j themselves.
+ * Refused, each with a message, before any handle is dereferenced: NULL rules; a penalty that is NaN or infinite; repetition_penalty <= 0; min_p NaN,
+ *   < 0 or > 1; reserved != 0; n_bias outside 0..LNB_MAX_LOGIT_BIAS; NULL bias arrays with n_bias > 0; a bias value that is NaN or +inf; a bias id
+ *   given twice or negative; negative n_counted; NULL counted with n_counted > 0; a negative counted id; and whatever lnb_decode_sample_until refuses.
+ *   Ids are compared with the vocabulary as soon as V is known (the op: at once; the loops: right after the model's V is read). */
+#define LNB_MAX_LOGIT_BIAS 1024
+typedef struct lnb_logit_rules {
+    float repetition_penalty;   /* 1 = off */
+    float presence_penalty;     /* 0 = off */
+    float frequency_penalty;    /* 0 = off */
+    float min_p;                /* 0 = off */
+    int32_t n_bias, reserved;
+    const int32_t* bias_ids;    /* n_bias distinct ids in [0, V) */
+    const float*   bias_values; /* truncated to bf16; -inf bans a token */
+} lnb_logit_rules;
+int lnb_decode_sample_rules_until(lnb_ctx* c, const lnb_sampler* sampler, const lnb_logit_rules* rules, const int32_t* counted, int n_counted,
+                                  int32_t token, int start_pos, int max_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out);
+int lnb_batch_decode_sample_rules_until(lnb_batch* b, const lnb_sampler* samplers, const lnb_logit_rules* rules /* [n] */,
+                                        const int32_t* const* counted /* [n] */, const int32_t* n_counted /* [n] */, const int32_t* tokens,
+                                        const int32_t* start_pos, int max_steps, int32_t* out_tokens, int32_t* n_generated, int32_t* finished,
+                                        float* ms_out);
+int lnb_op_sample_rules(int device, const uint16_t* logits_bf16, int rows, int V, const lnb_sampler* samplers, const lnb_logit_rules* rules /* [rows] */,
+                        const uint32_t* counts /* [rows][V] or NULL */, const int32_t* pos, const uint64_t* draws, int32_t* tokens_out,
+                        lnb_sample_info* info);
+/* lnb_profile_sample with the rules launch (sample_rules_kernel on the context's tables as the last rules call left them; rules NULL: all off) */
+int lnb_profile_sample_rules(lnb_ctx* c, const lnb_sampler* sampler, const lnb_logit_rules* rules, int pos, int iters, float* avg_ms_out);
 /* ---- sampling in the speculative loops ----
  * lnb_decode_speculative_sample_until: out_tokens[0 .. *n_generated), *n_generated, *finished and the KV rows [0, start_pos + *n_generated) of every
  *   layer are bit-identical to lnb_decode_sample_until(c, sampler, token, start_pos, max_steps, ...) on a context holding the same rows below

@@ -38,6 +38,7 @@ static_assert(LNB_MAX_FORK == KVC_MAX_DST, "lnb.h and lnb_kvcopy.h disagree on t
 static_assert(LNB_MAX_TOP_K == LNB_TOKPROB_MAX_K, "lnb.h and lnb_device.h disagree on the largest top-k");
 static_assert(sizeof(lnb_sampler) == sizeof(LnbSampler) && sizeof(lnb_sampler) == 24 && sizeof(lnb_sample_info) == sizeof(LnbSampleInfo) && sizeof(lnb_sample_info) == 40 &&
               LNB_SAMPLE_MAX_VOCAB == LNB_SAMPLE_MAX_V, "lnb.h and lnb_sample.h disagree on the sampler");
+static_assert(sizeof(lnb_logit_rules) == 40 && offsetof(lnb_logit_rules, bias_ids) == 24 && sizeof(LnbRulesDev) == 32, "the layout of the logit rules");
 static_assert(LNB_MAX_DRAFT == LNB_SPEC_MAX_DRAFT && LNB_MAX_DRAFT + 1 <= LNB_STREAM_COLS, "a verify pass is one column group of at most 16 columns");
 
 extern "C" {
@@ -61,6 +62,13 @@ hipError_t lnbk_argmax(const uint16_t* logits, int V, int32_t* next_token, StepS
 hipError_t lnbk_sample(const uint16_t* logits, int V, int rows, const double* etab, const LnbSampler* smp, int32_t* next_token, StepState* state, int32_t* out_tokens,
                        int out_cap, int advance, const int32_t* pos, const unsigned long long* draws, LnbSampleInfo* info, hipStream_t st);
 hipError_t lnbk_batch_sample(const uint16_t* logits, int V, const double* etab, const LnbSampler* smp, const BatchTab* tab, int nseq, hipStream_t st);
+hipError_t lnbk_sample_rules(const uint16_t* logits, int V, int rows, const double* etab, const LnbSampler* smp, const LnbRulesDev* rules, int32_t* next_token,
+                             StepState* state, int32_t* out_tokens, int out_cap, int advance, const int32_t* pos, const unsigned long long* draws, LnbSampleInfo* info,
+                             hipStream_t st);
+hipError_t lnbk_batch_sample_rules(const uint16_t* logits, int V, const double* etab, const LnbSampler* smp, const LnbRulesDev* rules, const BatchTab* tab, int nseq,
+                                   hipStream_t st);
+hipError_t lnbk_rules_tables(uint32_t* counts, int V, const int32_t* counted, int n_counted, int32_t token, uint16_t* bias, const int32_t* ids, const float* values,
+                             int n_bias, hipStream_t st);
 hipError_t lnbk_set_state(StepState* state, int pos, int n_out, int honour_stop, hipStream_t st);
 hipError_t lnbk_set_stop(StepState* state, const int32_t* ids, int n, hipStream_t st);
 hipError_t lnbk_advance_state(StepState* state, int rows, hipStream_t st);
@@ -159,7 +167,7 @@ template <class T> static hipError_t pinned_alloc(Pinned<T>& p, size_t bytes, un
 static hipError_t event_create(Event& e, unsigned flags = hipEventDefault) { return e.fill([&](hipEvent_t* q) { return hipEventCreateWithFlags(q, flags); }); }
 static hipError_t stream_create(Stream& s, unsigned flags) { return s.fill([&](hipStream_t* q) { return hipStreamCreateWithFlags(q, flags); }); }
 // which captured step: the token launch that ends it, and the attention form its launches bake in
-enum GraphLaunch { GL_GREEDY = 0, GL_SAMPLE, GL_STAGE, GL_COUNT };
+enum GraphLaunch { GL_GREEDY = 0, GL_SAMPLE, GL_STAGE, GL_SAMPLE_RULES, GL_COUNT };
 enum GraphForm { GF_SHORT = 0, GF_LONG, GF_ROWS, GF_COUNT };         // (0, 1, 2: also what lnb_ctx_verify_attention_form reports)
 using Graphs = GraphTable<hipGraphExec_t, hipGraphExecDestroy, GL_COUNT, GF_COUNT>;
 
@@ -264,6 +272,12 @@ struct lnb_ctx {
     int attn_short_cap = 0;                // longest context the one-workgroup-per-head kernel can stage in the LDS
     bool attn_long = false;                // selection for the launches being enqueued (set per call / per captured graph)
     Dev<LnbSampler> d_smp;                 // the sampling step's sampler
+    // logit rules (lnb_decode_sample_rules_until): the context's occurrence table and bias table [V], rebuilt by every rules call before its first step
+    // (the staging buffer holds the call's counted text and bias list for that), and the device struct the rules graphs point at; allocated on first use
+    struct RulesTabs {
+        Dev<uint32_t> counts; Dev<uint16_t> bias; DevGrown<char> stage; Dev<LnbRulesDev> d_rules;
+        LnbRulesDev h_rules{};             // what the last call copied to d_rules (it must outlive the copy)
+    } rl;
     PipeLink link;                         // pipeline stage (lnb_pipeline_tick): events towards / from the exchange stream
     int dev_pos = -1;                      // position the device-side StepState will hold when the stream reaches this point (-1: unknown)
     bool attn_causal = false;              // set by lnb_forward_append around its multi-row call: the attention launches take the true causal mask (AttnParams::causal)
@@ -1642,7 +1656,7 @@ extern "C" int lnb_forward_score_append(lnb_ctx* c, const int32_t* tokens, int s
 
 // one decode step = embed(token on device) -> layers -> head -> [token probabilities] -> argmax that feeds the next step; sample: the sampler's token
 // (the context's device sampler, lnb_decode_sample_until) in place of the argmax
-static int enqueue_decode_step(lnb_ctx* c, bool sample = false) {
+static int enqueue_decode_step(lnb_ctx* c, GraphLaunch launch = GL_GREEDY) {
     lnb_model* m = c->m;
     // LNB_MEASURE_SKIP_TOKEN_KERNELS=1 (timing only, the tokens are garbage): the step without its embedding gather and argmax launches =
     // the most that fusing them into the neighbouring products could return (NOTES 5.8)
@@ -1654,7 +1668,9 @@ static int enqueue_decode_step(lnb_ctx* c, bool sample = false) {
         TokProbParams p = tp_params(m, c->logits, 1, c->top_k, c->tp.zpart, c->tp.kpart, c->tp.cnt, c->tp.out, 0);
         HIPCHK(lnbk_token_probs(&p, c->stream));
     }
-    if (sample) HIPCHK(lnbk_sample(c->logits, m->a.vocab_size, 1, m->prob_etab, c->d_smp, c->dtok, c->st, c->dout, c->dout_cap, 1, nullptr, nullptr, nullptr, c->stream));
+    if (launch == GL_SAMPLE_RULES)
+        HIPCHK(lnbk_sample_rules(c->logits, m->a.vocab_size, 1, m->prob_etab, c->d_smp, c->rl.d_rules, c->dtok, c->st, c->dout, c->dout_cap, 1, nullptr, nullptr, nullptr, c->stream));
+    else if (launch == GL_SAMPLE) HIPCHK(lnbk_sample(c->logits, m->a.vocab_size, 1, m->prob_etab, c->d_smp, c->dtok, c->st, c->dout, c->dout_cap, 1, nullptr, nullptr, nullptr, c->stream));
     else if (!skip) HIPCHK(lnbk_argmax(c->logits, m->a.vocab_size, c->dtok, c->st, c->dout, c->dout_cap, 1, c->stream));
     return 0;
 }
@@ -1735,10 +1751,9 @@ template <class Body> static int capture_once(GraphExec& slot, hipStream_t st, B
 }
 // one captured graph per attention form: the step at context T replays the long-context one when T exceeds the crossover.  Captures the
 // forms that steps at positions start_pos .. start_pos + n_steps - 1 need and the context does not hold yet.
-static int capture_decode_graphs(lnb_ctx* c, int start_pos, int n_steps, bool sample = false) {
-    const GraphLaunch launch = sample ? GL_SAMPLE : GL_GREEDY;
+static int capture_decode_graphs(lnb_ctx* c, int start_pos, int n_steps, GraphLaunch launch = GL_GREEDY) {
     auto capture = [&](bool longctx) {
-        return capture_once(c->graphs.slot(launch, longctx ? GF_LONG : GF_SHORT), c->stream, [&] { c->attn_long = longctx; return enqueue_decode_step(c, sample); });
+        return capture_once(c->graphs.slot(launch, longctx ? GF_LONG : GF_SHORT), c->stream, [&] { c->attn_long = longctx; return enqueue_decode_step(c, launch); });
     };
     const bool any_short = !want_long_attention(c, 1, start_pos), any_long = want_long_attention(c, 1, start_pos + n_steps - 1);
     if (any_short && capture(false)) return -1;
@@ -1757,9 +1772,53 @@ static int sample_vocab_check(int V) {
     if (V < 1 || V > LNB_SAMPLE_MAX_VOCAB) return fail("sampling takes rows of 1..%d entries (got %d): the integer weight sums of a longer row could pass 2^63", LNB_SAMPLE_MAX_VOCAB, V);
     return 0;
 }
-static const char* const k_sample_probs_advice = "records token probabilities, whose records promise ids[i * k] == out_tokens[i] -- a sampled token does not keep that: "
+// what every rules entry point asks of a rule set and its counted text, before anything else is looked at.  V <= 0: the vocabulary is not known yet
+// (it sits behind a handle) -- ids are then only refused when negative, and the caller comes back with V once it has read it.
+static int rules_check(const lnb_logit_rules* r, const int32_t* counted, int n_counted, int V, const char* who) {
+    if (!r) return fail("%snull argument (rules)", who);
+    for (const auto& pn : {std::make_pair(r->repetition_penalty, "repetition_penalty"), std::make_pair(r->presence_penalty, "presence_penalty"),
+                           std::make_pair(r->frequency_penalty, "frequency_penalty")})
+        if (std::isnan(pn.first) || std::isinf(pn.first)) return fail("%srules: %s must be finite (got %g)", who, pn.second, (double)pn.first);
+    if (!(r->repetition_penalty > 0.0f)) return fail("%srules: repetition_penalty must be > 0 (got %g; 1 = off)", who, (double)r->repetition_penalty);
+    if (!(r->min_p >= 0.0f && r->min_p <= 1.0f)) return fail("%srules: min_p must be in [0, 1] (got %g; 0 = off)", who, (double)r->min_p);
+    if (r->reserved != 0) return fail("%srules: reserved must be 0 (got %d)", who, r->reserved);
+    if (r->n_bias < 0 || r->n_bias > LNB_MAX_LOGIT_BIAS) return fail("%srules: n_bias must be 0..%d (got %d)", who, LNB_MAX_LOGIT_BIAS, r->n_bias);
+    if (r->n_bias > 0 && (!r->bias_ids || !r->bias_values)) return fail("%srules: null bias arrays with n_bias = %d", who, r->n_bias);
+    const int top = V > 0 ? V : 0x7FFFFFFF;
+    std::vector<int32_t> ids(r->bias_ids, r->bias_ids + r->n_bias);
+    std::sort(ids.begin(), ids.end());
+    for (int i = 0; i < r->n_bias; i++) {
+        const float v = r->bias_values[i];
+        if (std::isnan(v) || (std::isinf(v) && v > 0)) return fail("%srules: bias value %d must not be NaN or +inf (got %g; -inf bans a token)", who, i, (double)v);
+        if (ids[i] < 0 || ids[i] >= top) return fail("%srules: bias id %d is outside the vocabulary [0, %d)", who, ids[i], top);
+        if (i > 0 && ids[i] == ids[i - 1]) return fail("%srules: bias id %d is given twice", who, ids[i]);
+    }
+    if (n_counted < 0) return fail("%sn_counted must be >= 0 (got %d)", who, n_counted);
+    if (n_counted > 0 && !counted) return fail("%snull argument (counted) with n_counted = %d", who, n_counted);
+    for (int i = 0; i < n_counted; i++)
+        if (counted[i] < 0 || counted[i] >= top) return fail("%scounted id %d at index %d is outside the vocabulary [0, %d)", who, counted[i], i, top);
+    return 0;
+}
+// The tables of one context for a rules call, enqueued on st (the caller's arrays are read before this returns or stay the caller's until the call
+// ends): counts = the histogram of counted ++ [token], bias = the scattered list -> *out = what the token launch reads (bias NULL: no list).
+static int rules_tables(lnb_ctx* c, const lnb_logit_rules* r, const int32_t* counted, int n_counted, int32_t token, hipStream_t st, LnbRulesDev* out) {
+    const int V = c->m->a.vocab_size;
+    if (!c->rl.counts) HIPCHK(dev_alloc(c->rl.counts, (size_t)V * 4));
+    if (r->n_bias > 0 && !c->rl.bias) HIPCHK(dev_alloc(c->rl.bias, (size_t)V * 2));
+    const size_t nc = (size_t)n_counted * 4, nb = (size_t)r->n_bias * 4;
+    HIPCHK(dev_reserve(c->rl.stage, nc + 2 * nb + 16));
+    char* const s = c->rl.stage;
+    if (nc) HIPCHK(hipMemcpyAsync(s, counted, nc, hipMemcpyHostToDevice, st));
+    if (nb) { HIPCHK(hipMemcpyAsync(s + nc, r->bias_ids, nb, hipMemcpyHostToDevice, st)); HIPCHK(hipMemcpyAsync(s + nc + nb, r->bias_values, nb, hipMemcpyHostToDevice, st)); }
+    HIPCHK(lnbk_rules_tables(c->rl.counts, V, nc ? (const int32_t*)s : nullptr, n_counted, token, c->rl.bias, (const int32_t*)(s + nc), (const float*)(s + nc + nb), r->n_bias, st));
+    *out = LnbRulesDev{r->repetition_penalty, r->presence_penalty, r->frequency_penalty, r->min_p, c->rl.counts, r->n_bias > 0 ? (const lnbs_u16*)c->rl.bias.get() : nullptr};
+    return 0;
+}
+struct RulesCall { const lnb_logit_rules* rules; const int32_t* counted; int n_counted; };      // one generation's rules and counted text
+static const char* const k_sample_probs_advice ="records token probabilities, whose records promise ids[i * k] == out_tokens[i] -- a sampled token does not keep that: "
                                                  "switch them off (lnb_ctx_set_token_probs(ctx, 0)) for a sampling call";
-static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out, const lnb_sampler* smp = nullptr);
+static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out, const lnb_sampler* smp = nullptr,
+                              const RulesCall* rc = nullptr);
 extern "C" int lnb_decode_greedy(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int32_t* out_tokens, float* ms_out) {
     return decode_greedy_impl(c, token, start_pos, n_steps, out_tokens, nullptr, nullptr, ms_out);
 }
@@ -1776,6 +1835,15 @@ extern "C" int lnb_decode_sample_until(lnb_ctx* c, const lnb_sampler* sampler, i
     if (!c || !sampler || !out_tokens || !n_generated) return fail("null argument");
     if (sampler_check(sampler, "")) return -1;
     return decode_greedy_impl(c, token, start_pos, max_steps, out_tokens, n_generated, finished, ms_out, sampler);
+}
+// lnb_decode_sample_until under logit rules (include/lnb.h): the rules steps have captured graphs of their own, which point at the context's device
+// sampler, device rules and the two tables; the call rebuilds the tables from its counted text before the first step
+extern "C" int lnb_decode_sample_rules_until(lnb_ctx* c, const lnb_sampler* sampler, const lnb_logit_rules* rules, const int32_t* counted, int n_counted, int32_t token,
+                                             int start_pos, int max_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out) {
+    if (!c || !sampler || !out_tokens || !n_generated) return fail("null argument");
+    if (sampler_check(sampler, "") || rules_check(rules, counted, n_counted, 0, "")) return -1;
+    const RulesCall rc{rules, counted, n_counted};
+    return decode_greedy_impl(c, token, start_pos, max_steps, out_tokens, n_generated, finished, ms_out, sampler, &rc);
 }
 // measurement aid (tools/sample_bench.py): average HIP-event time of the token launch of a decode step ALONE, on the logits row the context's last step
 // left -- sample_kernel with this sampler, or argmax_kernel (sampler NULL).  Every launch advances the context's device state from `pos` as a step does.
@@ -1805,10 +1873,46 @@ extern "C" int lnb_profile_sample(lnb_ctx* c, const lnb_sampler* sampler, int po
     *avg_ms_out = ms / (float)iters;
     return 0;
 }
-static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out, const lnb_sampler* smp) {
+// the same for the rules launch: sample_rules_kernel with this sampler and these penalties / min-p (NULL: all off) on the context's tables as they are --
+// what the last rules call left, or zeroed ones; a bias list in `rules` is taken only if that call left a bias table.  The launches count their tokens.
+extern "C" int lnb_profile_sample_rules(lnb_ctx* c, const lnb_sampler* sampler, const lnb_logit_rules* rules, int pos, int iters, float* avg_ms_out) {
+    if (!c || !sampler || !avg_ms_out) return fail("null argument");
+    const lnb_logit_rules off = {1.0f, 0.0f, 0.0f, 0.0f, 0, 0, nullptr, nullptr};
+    if (!rules) rules = &off;
+    if (sampler_check(sampler, "") || rules_check(rules, nullptr, 0, 0, "")) return -1;
+    lnb_model* m = c->m;
+    if (!m->first() || !m->last()) return fail("lnb_profile_sample_rules needs a whole-model handle");
+    if (sample_vocab_check(m->a.vocab_size)) return -1;
+    if (iters <= 0 || pos < 0) return fail("bad arguments");
+    if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
+    HIPCHK(hipSetDevice(m->device));
+    hipStream_t st = c->stream;
+    if (!c->d_smp) HIPCHK(dev_alloc(c->d_smp, sizeof(LnbSampler)));
+    if (!c->rl.d_rules) HIPCHK(dev_alloc(c->rl.d_rules, sizeof(LnbRulesDev)));
+    if (!c->rl.counts) { HIPCHK(dev_alloc(c->rl.counts, (size_t)m->a.vocab_size * 4)); HIPCHK(hipMemsetAsync(c->rl.counts, 0, (size_t)m->a.vocab_size * 4, st)); }
+    c->rl.h_rules = LnbRulesDev{rules->repetition_penalty, rules->presence_penalty, rules->frequency_penalty, rules->min_p, c->rl.counts,
+                                rules->n_bias > 0 ? (const lnbs_u16*)c->rl.bias.get() : nullptr};
+    HIPCHK(hipMemcpyAsync(c->d_smp, sampler, sizeof(LnbSampler), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->rl.d_rules, &c->rl.h_rules, sizeof(LnbRulesDev), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx_set_state(c, pos, 0, false, false));
+    auto launch = [&]() {
+        return lnbk_sample_rules(c->logits, m->a.vocab_size, 1, m->prob_etab, c->d_smp, c->rl.d_rules, c->dtok, c->st, c->dout, c->dout_cap, 1, nullptr, nullptr, nullptr, st);
+    };
+    for (int i = 0; i < 3; i++) HIPCHK(launch());
+    HIPCHK(hipEventRecord(c->ev0, st));
+    for (int i = 0; i < iters; i++) HIPCHK(launch());
+    HIPCHK(hipEventRecord(c->ev1, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *avg_ms_out = ms / (float)iters;
+    return 0;
+}
+static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_steps, int32_t* out_tokens, int* n_generated, int* finished, float* ms_out, const lnb_sampler* smp,
+                              const RulesCall* rc) {
     if (!c || !out_tokens) return fail("null argument");
     lnb_model* m = c->m;
-    if (!m->first() || !m->last()) return fail("%s needs a whole-model handle", smp ? "lnb_decode_sample_until" : "lnb_decode_greedy");
+    if (rc && rules_check(rc->rules, rc->counted, rc->n_counted, m->a.vocab_size, "")) return -1;         // (the ids against the vocabulary, now that it is known)
+    if (!m->first() || !m->last()) return fail("%s needs a whole-model handle", rc ? "lnb_decode_sample_rules_until" : smp ? "lnb_decode_sample_until" : "lnb_decode_greedy");
     if (smp) {
         if (sample_vocab_check(m->a.vocab_size)) return -1;
         if (c->top_k > 0) return fail("the context %s", k_sample_probs_advice);
@@ -1822,9 +1926,15 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     hipStream_t st = c->stream;
     const bool use_graph = knob(Knob::NO_GRAPH) == 0;
     if (smp && !c->d_smp) HIPCHK(dev_alloc(c->d_smp, sizeof(LnbSampler)));
-    if (use_graph && capture_decode_graphs(c, start_pos, n_steps, smp != nullptr)) return -1;
+    if (rc && !c->rl.d_rules) HIPCHK(dev_alloc(c->rl.d_rules, sizeof(LnbRulesDev)));
+    const GraphLaunch launch = rc ? GL_SAMPLE_RULES : smp ? GL_SAMPLE : GL_GREEDY;
+    if (use_graph && capture_decode_graphs(c, start_pos, n_steps, launch)) return -1;
     c->tp_last_k = 0; c->tp_last_n = 0;
     if (smp) HIPCHK(hipMemcpyAsync(c->d_smp, smp, sizeof(LnbSampler), hipMemcpyHostToDevice, st));
+    if (rc) {
+        if (rules_tables(c, rc->rules, rc->counted, rc->n_counted, token, st, &c->rl.h_rules)) return -1;
+        HIPCHK(hipMemcpyAsync(c->rl.d_rules, &c->rl.h_rules, sizeof(LnbRulesDev), hipMemcpyHostToDevice, st));
+    }
     HIPCHK(hipMemcpyAsync(c->dtok, &token, 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(c->derr, 0, 4, st));
     // (the argmax kernel advances the position on the device from here on.)  Stop ids are compared only on behalf of a caller that learns how far
@@ -1835,8 +1945,8 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     HIPCHK(hipEventRecord(c->ev0, st));
     for (int i = 0; i < n_steps; i++) {
         const bool longctx = want_long_attention(c, 1, start_pos + i);
-        if (use_graph) HIPCHK(hipGraphLaunch(c->graphs.slot(smp ? GL_SAMPLE : GL_GREEDY, longctx ? GF_LONG : GF_SHORT), st));
-        else { c->attn_long = longctx; if (enqueue_decode_step(c, smp != nullptr)) return -1; }
+        if (use_graph) HIPCHK(hipGraphLaunch(c->graphs.slot(launch, longctx ? GF_LONG : GF_SHORT), st));
+        else { c->attn_long = longctx; if (enqueue_decode_step(c, launch)) return -1; }
     }
     HIPCHK(hipEventRecord(c->ev1, st));
     HIPCHK(hipMemcpyAsync(out_tokens, c->dout, (size_t)n_steps * 4, hipMemcpyDeviceToHost, st));
@@ -2065,6 +2175,7 @@ struct lnb_batch {
     Dev<double> e_own, z_own;              // the batch's own scratch (scratch_owned)
     double* e_buf = nullptr; double* z_part = nullptr;     // what the launches take: e_own / z_own, or (a verify batch) its context's sp_e_buf / sp_z_part
     Dev<LnbSampler> d_smp;                 // the device array of n samplers the sampling steps point at
+    Dev<LnbRulesDev> d_rules; std::vector<LnbRulesDev> h_rules;      // the same for the rules steps: every member's rules and ITS CONTEXT's tables (BatchTab stays as it is)
     // a verify batch whose columns run the multi-row long-context pair (lnb_ctx_set_rows_attention, flags bit 1)
     bool attn_rows = false; int rows_zseq = 0;
     bool rows_form = false;                // the model carries no matrix-core copy: every product runs as ROWS of gemm_stream_kernel on the resident layouts, whatever n
@@ -2393,11 +2504,13 @@ static int enqueue_batch_pass(lnb_batch* b) {
 // One batched step of this model STAGE: the pass, and on the last stage the argmax (which advances every sequence's position); a stage
 // without the head advances the positions itself.  ring_in: the first stage of a multi-stage pipeline takes the tokens from the contiguous
 // words the last stage sent (lnb_pipeline_tick_batch).
-static int enqueue_batch_step(lnb_batch* b, bool ring_in = false, bool sample = false) {
+static int enqueue_batch_step(lnb_batch* b, bool ring_in = false, bool sample = false, bool rules = false) {
     lnb_model* m = b->m;
     if (ring_in && m->first()) HIPCHK(lnbk_batch_scatter_ring(b->tab, b->ring, b->stream));
     if (enqueue_batch_pass(b)) return -1;
-    if (m->last() && sample) {                               // every member's own sampler (lnb_batch_decode_sample_until: a whole model, no token probabilities)
+    if (m->last() && rules) {                                // every member's own sampler, rules and tables (lnb_batch_decode_sample_rules_until)
+        HIPCHK(lnbk_batch_sample_rules(b->logits, m->a.vocab_size, m->prob_etab, b->d_smp, b->d_rules, b->tab, b->n, b->stream));
+    } else if (m->last() && sample) {                               // every member's own sampler (lnb_batch_decode_sample_until: a whole model, no token probabilities)
         HIPCHK(lnbk_batch_sample(b->logits, m->a.vocab_size, m->prob_etab, b->d_smp, b->tab, b->n, b->stream));
     } else if (m->last()) {
         if (b->top_k > 0) {                                  // (ticks refuse such batches: only lnb_batch_decode[_until] gets here with it)
@@ -2409,7 +2522,7 @@ static int enqueue_batch_step(lnb_batch* b, bool ring_in = false, bool sample = 
     return 0;
 }
 static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t* start_pos, int n_steps, int32_t* out_tokens, int32_t* n_generated, int32_t* finished, float* ms_out,
-                             const lnb_sampler* smp = nullptr);
+                             const lnb_sampler* smp = nullptr, const lnb_logit_rules* rules = nullptr, const int32_t* const* counted = nullptr, const int32_t* n_counted = nullptr);
 extern "C" int lnb_batch_decode(lnb_batch* b, const int32_t* tokens, const int32_t* start_pos, int n_steps, int32_t* out_tokens, float* ms_out) {
     return batch_decode_impl(b, tokens, start_pos, n_steps, out_tokens, nullptr, nullptr, ms_out);     // n_steps tokens per sequence: stop ids are not compared
 }
@@ -2429,15 +2542,27 @@ extern "C" int lnb_batch_decode_sample_until(lnb_batch* b, const lnb_sampler* sa
     if (!b || !samplers || !tokens || !start_pos || !out_tokens || !n_generated) return fail("null argument");
     return batch_decode_impl(b, tokens, start_pos, max_steps, out_tokens, n_generated, finished, ms_out, samplers);
 }
+// lnb_batch_decode_sample_until with one rule set and one counted text per member (include/lnb.h); checked like the samplers, right after the batch's n is read
+extern "C" int lnb_batch_decode_sample_rules_until(lnb_batch* b, const lnb_sampler* samplers, const lnb_logit_rules* rules, const int32_t* const* counted,
+                                                   const int32_t* n_counted, const int32_t* tokens, const int32_t* start_pos, int max_steps, int32_t* out_tokens,
+                                                   int32_t* n_generated, int32_t* finished, float* ms_out) {
+    if (!b || !samplers || !rules || !counted || !n_counted || !tokens || !start_pos || !out_tokens || !n_generated) return fail("null argument");
+    return batch_decode_impl(b, tokens, start_pos, max_steps, out_tokens, n_generated, finished, ms_out, samplers, rules, counted, n_counted);
+}
 static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t* start_pos, int n_steps, int32_t* out_tokens, int32_t* n_generated, int32_t* finished, float* ms_out,
-                             const lnb_sampler* smp) {
+                             const lnb_sampler* smp, const lnb_logit_rules* rules, const int32_t* const* counted, const int32_t* n_counted) {
     if (!b || !tokens || !start_pos || !out_tokens) return fail("null argument");
     lnb_model* m = b->m;
     if (smp) {
         char who[32];
-        for (int s = 0; s < b->n; s++) { snprintf(who, sizeof who, "sequence %d: ", s); if (sampler_check(smp + s, who)) return -1; }
+        for (int s = 0; s < b->n; s++) {
+            snprintf(who, sizeof who, "sequence %d: ", s);
+            if (sampler_check(smp + s, who) || (rules && rules_check(rules + s, counted[s], n_counted[s], m->a.vocab_size, who))) return -1;
+        }
     }
-    if (!m->first() || !m->last()) return fail("%s needs a whole-model handle; pipeline stages run their batches through lnb_pipeline_tick_batch", smp ? "lnb_batch_decode_sample_until" : "lnb_batch_decode");
+    if (!m->first() || !m->last())
+        return fail("%s needs a whole-model handle; pipeline stages run their batches through lnb_pipeline_tick_batch",
+                    rules ? "lnb_batch_decode_sample_rules_until" : smp ? "lnb_batch_decode_sample_until" : "lnb_batch_decode");
     if (smp) {
         if (sample_vocab_check(m->a.vocab_size)) return -1;
         for (int s = 0; s < b->n; s++) if (b->ctxs[s]->top_k > 0) return fail("sequence %d: its context %s", s, k_sample_probs_advice);
@@ -2458,10 +2583,22 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     hipStream_t st = b->stream;
     if (batch_select_form_at(b, start_pos)) return -1;
     const bool use_graph = knob(Knob::NO_GRAPH) == 0;
-    GraphExec& gslot = b->graphs.slot(smp ? GL_SAMPLE : GL_GREEDY, b->attn_long ? GF_LONG : GF_SHORT);       // one captured step per form
+    GraphExec& gslot = b->graphs.slot(rules ? GL_SAMPLE_RULES : smp ? GL_SAMPLE : GL_GREEDY, b->attn_long ? GF_LONG : GF_SHORT);       // one captured step per form
     if (smp && !b->d_smp) HIPCHK(dev_alloc(b->d_smp, (size_t)LNB_BATCH_MAX * sizeof(LnbSampler)));
-    if (use_graph && capture_once(gslot, st, [&] { return enqueue_batch_step(b, false, smp != nullptr); })) return -1;
+    if (rules && !b->d_rules) { HIPCHK(dev_alloc(b->d_rules, (size_t)LNB_BATCH_MAX * sizeof(LnbRulesDev))); b->h_rules.assign(LNB_BATCH_MAX, LnbRulesDev{}); }
+    if (use_graph && capture_once(gslot, st, [&] { return enqueue_batch_step(b, false, smp != nullptr, rules != nullptr); })) return -1;
     if (smp) HIPCHK(hipMemcpyAsync(b->d_smp, smp, (size_t)b->n * sizeof(LnbSampler), hipMemcpyHostToDevice, st));
+    if (rules) {                                             // every running member's tables, on the batch's stream (member_drain above: its own stream is idle)
+        for (int s = 0; s < b->n; s++) {
+            lnb_ctx* c = b->ctxs[s];
+            if (start_pos[s] >= 0) { if (rules_tables(c, rules + s, counted[s], n_counted[s], tokens[s], st, &b->h_rules[s])) return -1; }
+            else {                                           // frozen: its launch reads the tables and changes nothing -- they only have to exist
+                if (!c->rl.counts) { HIPCHK(dev_alloc(c->rl.counts, (size_t)m->a.vocab_size * 4)); HIPCHK(hipMemsetAsync(c->rl.counts, 0, (size_t)m->a.vocab_size * 4, st)); }
+                b->h_rules[s] = LnbRulesDev{1.0f, 0.0f, 0.0f, 0.0f, c->rl.counts, nullptr};
+            }
+        }
+        HIPCHK(hipMemcpyAsync(b->d_rules, b->h_rules.data(), (size_t)b->n * sizeof(LnbRulesDev), hipMemcpyHostToDevice, st));
+    }
     memcpy(b->h_io, tokens, (size_t)b->n * 4); memcpy(b->h_io + LNB_BATCH_MAX, start_pos, (size_t)b->n * 4);
     HIPCHK(hipMemcpyAsync(b->d_tokens, b->h_io, (size_t)b->n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(b->d_pos, b->h_io + LNB_BATCH_MAX, (size_t)b->n * 4, hipMemcpyHostToDevice, st));
@@ -2470,7 +2607,7 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     HIPCHK(hipEventRecord(b->ev0, st));
     for (int i = 0; i < n_steps; i++) {
         if (use_graph) HIPCHK(hipGraphLaunch(gslot, st));
-        else if (enqueue_batch_step(b, false, smp != nullptr)) return -1;
+        else if (enqueue_batch_step(b, false, smp != nullptr, rules != nullptr)) return -1;
     }
     HIPCHK(hipEventRecord(b->ev1, st));
     b->last_form = b->attn_long ? 1 : 0;
@@ -2939,7 +3076,7 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
     if (!m->batch_enabled) HIPCHK(lnbk_batch_prepare());
     const int n_text = n_history + 1;
     if (smp && !c->d_smp) HIPCHK(dev_alloc(c->d_smp, sizeof(LnbSampler)));
-    if (spec_alloc(c, n_text) || capture_decode_graphs(c, start_pos, max_steps, smp != nullptr)) return -1;
+    if (spec_alloc(c, n_text) || capture_decode_graphs(c, start_pos, max_steps, smp ? GL_SAMPLE : GL_GREEDY)) return -1;
     hipStream_t st = c->stream;
     c->tp_last_k = 0; c->tp_last_n = 0;
     if (smp) HIPCHK(hipMemcpyAsync(c->d_smp, smp, sizeof(LnbSampler), hipMemcpyHostToDevice, st));       // (the captured graphs hold the pointer: another sampler replays them)
@@ -3804,6 +3941,53 @@ extern "C" int lnb_op_sample(int device, const uint16_t* logits_bf16, int rows, 
     if (draws) HIPCHK(hipMemcpy(b + o_u, draws, R * 8, hipMemcpyHostToDevice));
     HIPCHK(lnbk_sample((const uint16_t*)(b + o_x), V, rows, (const double*)b, (const LnbSampler*)(b + o_s), (int32_t*)(b + o_t), nullptr, nullptr, 0, 0,
                        (const int32_t*)(b + o_p), draws ? (const unsigned long long*)(b + o_u) : nullptr, info ? (LnbSampleInfo*)(b + o_i) : nullptr, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(tokens_out, b + o_t, R * 4, hipMemcpyDeviceToHost));
+    if (info) HIPCHK(hipMemcpy(info, b + o_i, R * sizeof(LnbSampleInfo), hipMemcpyDeviceToHost));
+    return 0;
+}
+// sample_rules_kernel on host rows (test aid): lnb_op_sample with rules[i] and the counts row i (NULL: all zero) -- row i of every array starts i * V
+// elements in, so the three arrays of a row are aligned each in its own way
+extern "C" int lnb_op_sample_rules(int device, const uint16_t* logits_bf16, int rows, int V, const lnb_sampler* samplers, const lnb_logit_rules* rules,
+                                   const uint32_t* counts, const int32_t* pos, const uint64_t* draws, int32_t* tokens_out, lnb_sample_info* info) {
+    if (!logits_bf16 || !samplers || !rules || !pos || !tokens_out) return fail("null argument");
+    if (rows <= 0) return fail("empty operand");
+    if (sample_vocab_check(V)) return -1;
+    char who[32];
+    bool any_bias = false;
+    for (int i = 0; i < rows; i++) {
+        snprintf(who, sizeof who, "row %d: ", i);
+        if (sampler_check(samplers + i, who) || rules_check(rules + i, nullptr, 0, V, who)) return -1;
+        any_bias = any_bias || rules[i].n_bias > 0;
+    }
+    if (op_device(device)) return -1;
+    const size_t R = rows;
+    std::vector<double> et; prob_exp_table(et);
+    const size_t o_x = align256(65536 * 8), o_s = o_x + align256(R * V * 2 + 16), o_p = o_s + align256(R * sizeof(LnbSampler)), o_u = o_p + align256(R * 4),
+                 o_t = o_u + align256(R * 8), o_i = o_t + align256(R * 4), o_r = o_i + align256(R * sizeof(LnbSampleInfo)), o_c = o_r + align256(R * sizeof(LnbRulesDev)),
+                 o_b = o_c + align256(R * V * 4), need = o_b + (any_bias ? align256(R * V * 2) : 0);
+    Dev<char> buf;
+    HIPCHK(dev_alloc(buf, need));
+    char* const b = buf;
+    std::vector<LnbRulesDev> hr(R);
+    std::vector<uint16_t> hb(any_bias ? R * V : 0, (uint16_t)0);
+    for (size_t i = 0; i < R; i++) {
+        const lnb_logit_rules& r = rules[i];
+        for (int k = 0; k < r.n_bias; k++) hb[i * V + r.bias_ids[k]] = bf_trunc_h(r.bias_values[k]);
+        hr[i] = LnbRulesDev{r.repetition_penalty, r.presence_penalty, r.frequency_penalty, r.min_p, (lnbs_u32*)(b + o_c) + i * V,
+                            r.n_bias > 0 ? (const lnbs_u16*)(b + o_b) + i * V : nullptr};
+    }
+    HIPCHK(hipMemcpy(b, et.data(), 65536 * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_x, logits_bf16, R * V * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_s, samplers, R * sizeof(LnbSampler), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_p, pos, R * 4, hipMemcpyHostToDevice));
+    if (draws) HIPCHK(hipMemcpy(b + o_u, draws, R * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_r, hr.data(), R * sizeof(LnbRulesDev), hipMemcpyHostToDevice));
+    if (counts) HIPCHK(hipMemcpy(b + o_c, counts, R * V * 4, hipMemcpyHostToDevice)); else HIPCHK(hipMemset(b + o_c, 0, R * V * 4));
+    if (any_bias) HIPCHK(hipMemcpy(b + o_b, hb.data(), R * V * 2, hipMemcpyHostToDevice));
+    HIPCHK(lnbk_sample_rules((const uint16_t*)(b + o_x), V, rows, (const double*)b, (const LnbSampler*)(b + o_s), (const LnbRulesDev*)(b + o_r), (int32_t*)(b + o_t), nullptr,
+                             nullptr, 0, 0, (const int32_t*)(b + o_p), draws ? (const unsigned long long*)(b + o_u) : nullptr, info ? (LnbSampleInfo*)(b + o_i) : nullptr,
+                             nullptr));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(tokens_out, b + o_t, R * 4, hipMemcpyDeviceToHost));
     if (info) HIPCHK(hipMemcpy(info, b + o_i, R * sizeof(LnbSampleInfo), hipMemcpyDeviceToHost));

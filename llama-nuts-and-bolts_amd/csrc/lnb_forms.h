@@ -66,6 +66,9 @@
     X(SAMPLE_BATCH, "sample.batch", "batch_sample_kernel: one workgroup per member of a batched sampling step, each with its own sampler") \
     X(SAMPLE_SPEC, "sample.spec", "spec_sample_commit_kernel: one workgroup per column of a verify pass, each at its own position; the last one accepts and emits") \
     X(SAMPLE_SPEC_MANY, "sample.spec_many", "spec_many_sample_commit_kernel: the same per column of a many-context pass, each member with its own sampler") \
+    /* the same token launches under logit rules (lnb_decode_sample_rules_until: step 0 in the row load, step 4b in the probe) */ \
+    X(SAMPLE_RULES_ROW, "sample.rules_row", "sample_rules_kernel: one workgroup per logits row with its counts and bias tables -- the one-token rules step, rows of lnb_op_sample_rules") \
+    X(SAMPLE_RULES_BATCH, "sample.rules_batch", "batch_sample_rules_kernel: one workgroup per member of a batched rules step, each with its own sampler, rules and tables") \
     /* the tolerance mode (lnb_fast.hip: launch_a, launch_b, launch_gemm_fast, lnbk_fast_attn) */ \
     X(FAST_GEMV_A_RG8, "fast_gemv_a.rg8", "fast_gemv_a<*, *, *, 8>: split-K GEMV over a chain layout, 8 rows per work unit (few units, LNB_FAST_RG=8)") \
     X(FAST_GEMV_A_RG16, "fast_gemv_a.rg16", "the same, 16 rows per work unit") \

@@ -31,6 +31,7 @@
 #define DEVINL __device__ __forceinline__
 #define LNB_SAMPLE_FN DEVINL
 #define LNB_SAMPLE_FDIV(a, b) __fdiv_rn(a, b)
+#define LNB_SAMPLE_FMUL(a, b) __fmul_rn(a, b)                    // (never contracted with the addition behind it)
 #define LNB_SAMPLE_NO_SERIAL                 // (the serial whole-row walk is the host's: tests/native/sample_test.cpp)
 #include "lnb_sample.h"
 
@@ -4131,22 +4132,79 @@ template <class G> DEVINL void sample_groups(uint32_t (&kr)[64], int per, G g) {
 DEVINL unsigned long long sample_key_weight(const double* etab, unsigned key, int E) {
     return lnb_sample_weight((unsigned long long)__double_as_longlong(etab[lnb_sample_key_bits(key)]), E);
 }
-// -> the token, valid in thread 0, and sh.z = the row's info.  has_u: pos_or_u is u of step 8 itself.
-DEVINL int sample_block(const uint16_t* x, int V, const double* etab, const LnbSampler& s, bool has_u, unsigned long long pos_or_u, SampleSh& sh) {
+// ---- the logit rules' step 0 in the row load (lnb_sample.h; lnb_decode_sample_rules_until) ------------------------------------------------
+// The lane's group of eight logits at j0 (one 16 B load) is joined by its eight counts (two 16 B loads of the context's occurrence table) and, when a
+// bias table is present, its eight bf16 biases (one 16 B load); step 0 then runs in registers and the group is keyed and packed as a plain row's.  Each
+// array takes the 16 B path by its OWN alignment (row r of lnb_op_sample_rules starts r * V elements into each: 2, 4 and 2 bytes apiece) and otherwise,
+// or in the group that crosses V, element by element with the entries beyond V read as zero -- the caller gives those key 0.
+DEVINL void sample_rules_load8(const uint16_t* p, bool vec, int j0, int V, uint32_t (&w)[4]) {
+    if (vec) { const uint4 v = *(const uint4*)(p + j0); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; return; }
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const int j = j0 + 2 * t;
+        w[t] = (j < V ? (uint32_t)p[j] : 0u) | ((j + 1 < V ? (uint32_t)p[j + 1] : 0u) << 16);
+    }
+}
+DEVINL void sample_rules_group(const uint16_t* x, const LnbRulesDev& ru, bool alx, bool alc, bool alb, int j0, int V, uint32_t (&wd)[4]) {
+    const bool full = j0 + 8 <= V;
+    uint32_t cw[8];
+    sample_rules_load8(x, full && alx, j0, V, wd);
+    if (full && alc) {
+        const uint4 c0 = *(const uint4*)(ru.counts + j0), c1 = *(const uint4*)(ru.counts + j0 + 4);
+        cw[0] = c0.x; cw[1] = c0.y; cw[2] = c0.z; cw[3] = c0.w; cw[4] = c1.x; cw[5] = c1.y; cw[6] = c1.z; cw[7] = c1.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++) cw[i] = j0 + i < V ? ru.counts[j0 + i] : 0u;
+    }
+    if ((cw[0] | cw[1] | cw[2] | cw[3] | cw[4] | cw[5] | cw[6] | cw[7]) != 0u &&      // (a counted token is rare: most groups skip 0a and 0b whole)
+        (ru.repetition_penalty != 1.0f || ru.presence_penalty != 0.0f || ru.frequency_penalty != 0.0f)) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            if (cw[i] == 0u) continue;
+            const int sft = (i & 1) * 16;
+            const uint32_t y = lnb_sample_penalise((uint16_t)(wd[i >> 1] >> sft), cw[i], ru.repetition_penalty, ru.presence_penalty, ru.frequency_penalty);
+            wd[i >> 1] = (wd[i >> 1] & ~(0xffffu << sft)) | (y << sft);
+        }
+    }
+    if (ru.bias) {                                           // 0c: every entry, +0 where no id is listed
+        uint32_t bw[4];
+        sample_rules_load8(ru.bias, full && alb, j0, V, bw);
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+            wd[t] = (uint32_t)lnb_sample_add_bias((uint16_t)(wd[t] & 0xffffu), (uint16_t)(bw[t] & 0xffffu)) |
+                    ((uint32_t)lnb_sample_add_bias((uint16_t)(wd[t] >> 16), (uint16_t)(bw[t] >> 16)) << 16);
+    }
+}
+// -> the token, valid in thread 0, and sh.z = the row's info.  has_u: pos_or_u is u of step 8 itself.  RULES: the row is adjusted by ru's step 0 as it
+// is loaded, S is step 4b's, and temperature 0 = the first maximum of the adjusted row (steps 1-3); without it the code is the plain sampler's, token for token.
+template <bool RULES = false>
+DEVINL int sample_block(const uint16_t* x, int V, const double* etab, const LnbSampler& s, bool has_u, unsigned long long pos_or_u, SampleSh& sh,
+                        const LnbRulesDev* rules = nullptr) {
     const int tid = threadIdx.x;
     int par = 0;
     if (tid == 0) { const LnbSampleInfo z0 = {0, 0, 0, 0, 0, 0, 0}; sh.z = z0; }      // (read back by thread 0 only)
-    const float T = s.temperature;
+    const float T = RULES && s.temperature == 0.0f ? 1.0f : s.temperature;
     const int per = (((V + 1023) >> 10) + 7) & ~7;
     // the row, once: scaled (step 1), keyed (steps 2 and 5), packed
     uint32_t kr[64];
     const bool al = (((uintptr_t)x) & 15) == 0;
     auto key_of = [&](uint16_t b) -> uint32_t { return lnb_sample_key(T == 1.0f ? b : lnb_sample_scale(b, T)); };
+    LnbRulesDev ru = {1.0f, 0.0f, 0.0f, 0.0f, nullptr, nullptr};
+    if constexpr (RULES) ru = *rules;
 #pragma unroll
     for (int q = 0; q < 16; q++) {
         if (q * 8 < per) {
             const int j0 = tid * per + q * 8;
-            if (al && j0 + 8 <= V) {
+            if constexpr (RULES) {
+                uint32_t wd[4];
+                sample_rules_group(x, ru, al, (((uintptr_t)ru.counts) & 15) == 0, (((uintptr_t)ru.bias) & 15) == 0, j0, V, wd);
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+                    const int j = j0 + 2 * t;
+                    const uint32_t lo = j < V ? key_of((uint16_t)(wd[t] & 0xffffu)) : 0u, hi = j + 1 < V ? key_of((uint16_t)(wd[t] >> 16)) : 0u;
+                    kr[q * 4 + t] = lo | (hi << 16);
+                }
+            } else if (al && j0 + 8 <= V) {
                 const uint4 v = *(const uint4*)(x + j0);
                 const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -4173,18 +4231,22 @@ DEVINL int sample_block(const uint16_t* x, int V, const double* etab, const LnbS
     unsigned a_l = 0xffffffffu, e_l = 0;
     sample_each(kr, per, [&](unsigned k) { if (k == kmax && a_l == 0xffffffffu) a_l = (unsigned)(tid * per) + e_l; e_l++; });
     const int a = (int)sample_wg_min(sh, par, a_l);
+    if constexpr (RULES) { if (s.temperature == 0.0f) return a; }               // greedy with rules: ml.Argmax of the adjusted row
     const unsigned long long emax = (unsigned long long)__double_as_longlong(etab[lnb_sample_key_bits(kmax)]);
     if (lnb_sample_degenerate(emax)) { if (tid == 0) sh.z.degenerate = 1; return a; }
     const int E = lnb_sample_exponent(emax);
     // step 4: S = the keys >= kmin, kmin = the smallest key of weight >= 1 (the weight grows with the key).  Two rounds of 1024 probes.
+    // (RULES, step 4b: of weight >= wmin = max(M, 1) <= the maximum's own weight, min_p being <= 1 -- the same probes, the last of which still succeeds)
+    unsigned long long wmin = 1;
+    if constexpr (RULES) wmin = lnb_sample_min_weight(ru.min_p, lnb_sample_weight(emax, E));
     unsigned kmin;
     {
         const unsigned lo0 = 0x80u, step = (kmax - lo0 + 1023u) >> 10;           // probes lo0 + (i + 1) * step, the last ones clamped to kmax (weight >= 2^45)
         unsigned k = lo0 + ((unsigned)tid + 1u) * step; k = k > kmax ? kmax : k;
-        const unsigned k1 = sample_wg_min(sh, par, sample_key_weight(etab, k, E) >= 1 ? k : 0xffffffffu);
+        const unsigned k1 = sample_wg_min(sh, par, sample_key_weight(etab, k, E) >= wmin ? k : 0xffffffffu);
         const unsigned lo1 = k1 > lo0 + step ? k1 - step : lo0;                  // weight(lo1) == 0 (a probe that failed) or lo1 is no candidate's key
         unsigned k2 = lo1 + 1u + (unsigned)tid; k2 = k2 > k1 ? k1 : k2;          // step <= 64: the probes lo1 + 1 .. k1
-        kmin = sample_wg_min(sh, par, sample_key_weight(etab, k2, E) >= 1 ? k2 : 0xffffffffu);
+        kmin = sample_wg_min(sh, par, sample_key_weight(etab, k2, E) >= wmin ? k2 : 0xffffffffu);
     }
     // Steps 6 and 7 as ONE loop around one tally -- (count, weight) of the entries whose key is >= t, t >= kmin: the weight of all of S, then the
     // bisection for top-k on counts, the weight above its threshold, the bisection for the nucleus on weights, and last the weight above the final
@@ -4335,6 +4397,68 @@ __global__ __launch_bounds__(1024) void batch_sample_kernel(const uint16_t* logi
     if (threadIdx.x == 0) { end.st = tab->st[q]; end.token_word = tab->dtok[q]; end.out_tokens = tab->dout[q]; end.out_cap = tab->dout_cap[q]; }
     const int tok = s.temperature == 0.0f ? argmax_block(x, V, sv, si) : sample_block(x, V, etab, s, false, pos, sh);
     if (threadIdx.x == 0) step_advance(end.st, tok, end.token_word, nullptr, end.out_tokens, end.out_cap);
+}
+// ---- the same two launches under logit rules (lnb_decode_sample_rules_until / lnb_batch_decode_sample_rules_until; the rule: lnb_sample.h) --------
+// rules[i] = row i's penalties, min-p and the two device tables of its context.  A step that advances a generation counts the token it emits
+// (counts[tok] += 1, thread 0, inside the not-finished path: a frozen generation changes nothing) -- the next step is a later launch on the same
+// stream, so a plain store suffices.  Temperature 0 runs the same sample_block (steps 1-3 on the adjusted row), so these kernels hold no argmax LDS.
+// Step 0 is eight f32 operations side by side: the packed f32 instructions are switched off for these two kernels (one IEEE operation per entry).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LNB_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define LNB_NO_PK_F32                                        // (the host pass knows no such feature)
+#endif
+struct SampleRulesEnd { SampleEnd e; uint32_t* counts; };
+DEVINL void sample_rules_advance(const SampleRulesEnd& end, int tok) {
+    if (!end.e.st->finished && tok >= 0) end.counts[tok] += 1u;                  // (tok < V: an index of the row)
+    step_advance(end.e.st, tok, end.e.token_word, nullptr, end.e.out_tokens, end.e.out_cap);
+}
+LNB_NO_PK_F32 __global__ __launch_bounds__(1024) void sample_rules_kernel(const uint16_t* logits, int V, const double* etab, const LnbSampler* smp,
+                                                                          const LnbRulesDev* rules, int32_t* next_token, StepState* st, int32_t* out_tokens,
+                                                                          int out_cap, int advance, const int32_t* op_pos, const unsigned long long* op_draws,
+                                                                          LnbSampleInfo* op_info) {
+    __shared__ SampleSh sh;
+    __shared__ SampleRulesEnd end;
+    const int row = advance ? 0 : blockIdx.x;
+    const LnbSampler s = smp[row];
+    const uint16_t* x = logits + (size_t)row * V;
+    const bool has_u = !advance && op_draws != nullptr;
+    const unsigned long long pos_or_u = advance ? (unsigned long long)(long long)st->pos : has_u ? op_draws[row] : (unsigned long long)(long long)op_pos[row];
+    if (threadIdx.x == 0) {
+        end.e.st = st; end.e.token_word = next_token + row; end.e.out_tokens = out_tokens; end.e.out_cap = out_cap; end.e.advance = advance;
+        end.e.info = !advance && op_info ? op_info + row : nullptr;
+        end.counts = rules[row].counts;
+    }
+    const int tok = sample_block<true>(x, V, etab, s, has_u, pos_or_u, sh, rules + row);
+    if (threadIdx.x == 0) {
+        if (end.e.info) *end.e.info = sh.z;
+        if (!end.e.advance) *end.e.token_word = tok;
+        else sample_rules_advance(end, tok);
+    }
+}
+LNB_NO_PK_F32 __global__ __launch_bounds__(1024) void batch_sample_rules_kernel(const uint16_t* logits, int V, const double* etab, const LnbSampler* smp,
+                                                                                const LnbRulesDev* rules, const BatchTab* tab) {
+    __shared__ SampleSh sh;
+    __shared__ SampleRulesEnd end;
+    const int q = blockIdx.x;
+    const LnbSampler s = smp[q];
+    const uint16_t* x = logits + (size_t)q * V;
+    const unsigned long long pos = (unsigned long long)(long long)tab->st[q]->pos;
+    if (threadIdx.x == 0) {
+        end.e.st = tab->st[q]; end.e.token_word = tab->dtok[q]; end.e.out_tokens = tab->dout[q]; end.e.out_cap = tab->dout_cap[q];
+        end.counts = rules[q].counts;
+    }
+    const int tok = sample_block<true>(x, V, etab, s, false, pos, sh, rules + q);
+    if (threadIdx.x == 0) sample_rules_advance(end, tok);
+}
+// The two tables of a call, before its first step (the context's stream, outside the captured graph): counts = the histogram of the counted text --
+// the caller's `counted`, then the call's token -- over a zeroed table; bias = the truncated values scattered over a zeroed table (distinct ids).
+__global__ void rules_tables_kernel(uint32_t* counts, const int32_t* counted, int n_counted, int32_t token, uint16_t* bias, const int32_t* ids,
+                                    const float* values, int n_bias) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_counted) atomicAdd(counts + counted[i], 1u);
+    else if (i == n_counted) atomicAdd(counts + token, 1u);
+    if (i < n_bias) bias[ids[i]] = bf_trunc(values[i]);
 }
 
 // ---- speculative greedy decoding (lnb_decode_speculative_until, include/lnb.h) ----------------------------------------------------------
@@ -5278,6 +5402,35 @@ extern "C" hipError_t lnbk_batch_sample(const uint16_t* logits, int V, const dou
     if (V < 1 || V > LNB_SAMPLE_MAX_V) return hipErrorInvalidValue;
     form_ran(Form::SAMPLE_BATCH);
     hipLaunchKernelGGL(batch_sample_kernel, dim3(nseq), dim3(1024), 0, st, logits, V, etab, smp, tab);
+    return hipGetLastError();
+}
+// the same two launches under logit rules: rules[rows] / rules[nseq] on the device, each with its context's tables
+extern "C" hipError_t lnbk_sample_rules(const uint16_t* logits, int V, int rows, const double* etab, const LnbSampler* smp, const LnbRulesDev* rules,
+                                        int32_t* next_token, StepState* state, int32_t* out_tokens, int out_cap, int advance, const int32_t* pos,
+                                        const unsigned long long* draws, LnbSampleInfo* info, hipStream_t st) {
+    if (V < 1 || V > LNB_SAMPLE_MAX_V || rows < 1 || (advance && rows != 1) || !rules) return hipErrorInvalidValue;
+    form_ran(Form::SAMPLE_RULES_ROW);
+    hipLaunchKernelGGL(sample_rules_kernel, dim3(rows), dim3(1024), 0, st, logits, V, etab, smp, rules, next_token, state, out_tokens, out_cap, advance, pos, draws, info);
+    return hipGetLastError();
+}
+extern "C" hipError_t lnbk_batch_sample_rules(const uint16_t* logits, int V, const double* etab, const LnbSampler* smp, const LnbRulesDev* rules,
+                                              const BatchTab* tab, int nseq, hipStream_t st) {
+    if (V < 1 || V > LNB_SAMPLE_MAX_V || !rules) return hipErrorInvalidValue;
+    form_ran(Form::SAMPLE_RULES_BATCH);
+    hipLaunchKernelGGL(batch_sample_rules_kernel, dim3(nseq), dim3(1024), 0, st, logits, V, etab, smp, rules, tab);
+    return hipGetLastError();
+}
+// a call's tables (ids in [0, V), distinct bias ids, token in [0, V): the caller has checked them).  bias is written only when n_bias > 0.
+// (hipMemsetAsync: these launches are never captured)
+extern "C" hipError_t lnbk_rules_tables(uint32_t* counts, int V, const int32_t* counted, int n_counted, int32_t token, uint16_t* bias, const int32_t* ids,
+                                        const float* values, int n_bias, hipStream_t st) {
+    if (V < 1 || !counts || n_counted < 0 || (n_counted > 0 && !counted) || token < 0 || token >= V || n_bias < 0 || (n_bias > 0 && (!bias || !ids || !values)))
+        return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)V * 4, st);
+    if (e == hipSuccess && n_bias > 0) e = hipMemsetAsync(bias, 0, (size_t)V * 2, st);
+    if (e != hipSuccess) return e;
+    const int n = n_counted + 1 > n_bias ? n_counted + 1 : n_bias;
+    hipLaunchKernelGGL(rules_tables_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, counts, counted, n_counted, token, bias, ids, values, n_bias);
     return hipGetLastError();
 }
 // the verify pass's token launch of the sampling speculative loop: w columns of one context, smp[0], cnt = the launch's arrival ticket (zero between launches)

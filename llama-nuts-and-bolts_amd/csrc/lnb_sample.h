@@ -13,6 +13,15 @@
 //   8. W_K = the kept weight; u = splitmix64(splitmix64(seed) ^ (uint64(pos) * 0x9E3779B97F4A7C15)); r = (u * W_K) >> 64; the token is the first
 //      kept index, in INDEX order, at which the running kept weight exceeds r
 // Everything behind the table lookup is integer arithmetic, so a parallel kernel, this serial walk and a Python restatement give the same token.
+//
+// Logit rules (include/lnb.h: lnb_logit_rules; lnb_decode_sample_rules_until) put a step 0 in front and a step 4b behind step 4.  c_j = how often token j
+// occurs in the counted text (an exact 32-bit number), bias_j = the bf16 bias of a listed id, +0 for every other.  Every operation is ONE IEEE f32
+// operation, never contracted into an fma, and each sub-step's result is truncated to bf16:
+//   0a. c_j > 0 and repetition_penalty != 1:  f = trunc_bf16(f > 0 ? f / rp : f * rp)         (f = f32(x_j) to begin with)
+//   0b. c_j > 0 and (presence != 0 or frequency != 0):  t = frequency * f32(c_j); t = presence + t; f = trunc_bf16(f - t)
+//   0c. a bias table is present:  f = trunc_bf16(f + f32(bias_j)), for EVERY j
+//   4b. min-p: M = uint64(f64(min_p) * f64(w_a)), w_a = the weight of the maximum; S = {j: w_j >= max(M, 1)} (the weight grows with the key: only kmin moves)
+// Steps 1-8 run on the adjusted row; temperature 0 is ml.Argmax of the ADJUSTED row (steps 1-3 at temperature 1).
 // Steps 6 and 7 each come down to a pair (threshold key t, number m of entries kept among those whose key equals t, the lowest indices first).
 #pragma once
 
@@ -23,6 +32,12 @@
 #define LNB_SAMPLE_FDIV(a, b) ((a) / (b))   // one IEEE f32 division (the device build names its correctly rounded one)
 #endif
 
+#ifndef LNB_SAMPLE_FMUL
+// one IEEE f32 product that no later addition can absorb into an fma: it is rounded into memory first (the device build names its own)
+LNB_SAMPLE_FN float lnb_sample_fmul_host(float a, float b) { volatile float r = a * b; return r; }
+#define LNB_SAMPLE_FMUL(a, b) lnb_sample_fmul_host(a, b)
+#endif
+
 #define LNB_SAMPLE_MAX_V 131072          // every weight sum stays below 2^63: 131072 weights below 2^46
 
 typedef unsigned long long lnbs_u64;
@@ -30,6 +45,9 @@ typedef unsigned int lnbs_u32;
 typedef unsigned short lnbs_u16;
 
 struct LnbSampler { float temperature, top_p; int top_k, reserved; lnbs_u64 seed; };                           // = lnb_sampler of lnb.h
+// the rules as the kernels take them: counts[V] (the occurrence table; the token launch of a decode step adds the token it emits) and bias[V] (bf16,
+// NULL: no bias) are the context's device tables
+struct LnbRulesDev { float repetition_penalty, presence_penalty, frequency_penalty, min_p; lnbs_u32* counts; const lnbs_u16* bias; };
 struct LnbSampleInfo { lnbs_u64 w_all, w_topk, w_kept; int n_candidates, n_kept, degenerate, pad; };           // = lnb_sample_info of lnb.h
 
 LNB_SAMPLE_FN lnbs_u64 lnb_sample_splitmix64(lnbs_u64 z) {
@@ -57,6 +75,32 @@ LNB_SAMPLE_FN lnbs_u16 lnb_sample_scale(lnbs_u16 x16, float temperature) {
     q = LNB_SAMPLE_FDIV(f, temperature);
     __builtin_memcpy(&b, &q, 4);
     return (lnbs_u16)(b >> 16);
+}
+LNB_SAMPLE_FN float lnb_sample_wide(lnbs_u16 b16) { lnbs_u32 b = (lnbs_u32)b16 << 16; float f; __builtin_memcpy(&f, &b, 4); return f; }
+LNB_SAMPLE_FN lnbs_u16 lnb_sample_trunc(float f) { lnbs_u32 b; __builtin_memcpy(&b, &f, 4); return (lnbs_u16)(b >> 16); }
+// step 0a + 0b on one entry that occurs c > 0 times
+LNB_SAMPLE_FN lnbs_u16 lnb_sample_penalise(lnbs_u16 x16, lnbs_u32 c, float rp, float presence, float frequency) {
+    float f = lnb_sample_wide(x16);
+    if (rp != 1.0f) f = lnb_sample_wide(lnb_sample_trunc(f > 0.0f ? LNB_SAMPLE_FDIV(f, rp) : LNB_SAMPLE_FMUL(f, rp)));
+    if (presence != 0.0f || frequency != 0.0f) {
+        float t = LNB_SAMPLE_FMUL(frequency, (float)c);
+        t = presence + t;
+        f = lnb_sample_wide(lnb_sample_trunc(f - t));
+    }
+    return lnb_sample_trunc(f);
+}
+// step 0c on one entry
+LNB_SAMPLE_FN lnbs_u16 lnb_sample_add_bias(lnbs_u16 x16, lnbs_u16 bias16) { return lnb_sample_trunc(lnb_sample_wide(x16) + lnb_sample_wide(bias16)); }
+// step 0 on one entry (bias: NULL = no table)
+LNB_SAMPLE_FN lnbs_u16 lnb_sample_adjust(lnbs_u16 x16, lnbs_u32 c, const lnbs_u16* bias16, float rp, float presence, float frequency) {
+    if (c > 0) x16 = lnb_sample_penalise(x16, c, rp, presence, frequency);
+    return bias16 ? lnb_sample_add_bias(x16, *bias16) : x16;
+}
+// step 4b: the smallest weight of S
+LNB_SAMPLE_FN lnbs_u64 lnb_sample_min_weight(float min_p, lnbs_u64 w_a) {
+    const double p = (double)min_p * (double)w_a;
+    const lnbs_u64 M = (lnbs_u64)p;
+    return M > 1 ? M : 1;
 }
 // y -> a key that orders as step 5 does: larger y = larger key, +0 and -0 share one, 0 = no candidate (NaN, -inf).  Candidates have keys >= 0x81.
 LNB_SAMPLE_FN lnbs_u32 lnb_sample_key(lnbs_u16 y16) {
@@ -96,8 +140,15 @@ LNB_SAMPLE_FN lnbs_u64 lnb_sample_p(float top_p, lnbs_u64 w1) {
 #ifndef LNB_SAMPLE_NO_SERIAL
 // The whole rule on one row, serially, as written above.  has_u: pos_or_u is u itself (a test puts r on a boundary), otherwise the position.
 // etab = the 65536 exp values.  -> the token (-1: no candidate); info (optional) as lnb_sample_info.  temperature 0 = ml.Argmax(x), info all zero.
+// ru (optional): the logit rules -- the row is x adjusted by step 0 with counts ru->counts[V] (NULL: all zero) and bias ru->bias[V], S is step 4b's.
 LNB_SAMPLE_FN int lnb_sample_row_serial(const lnbs_u16* x16, int V, const double* etab, const LnbSampler* s, int has_u, lnbs_u64 pos_or_u,
-                                        LnbSampleInfo* info) {
+                                        LnbSampleInfo* info, const LnbRulesDev* ru = nullptr, lnbs_u16* adjusted = nullptr) {
+    if (ru) {                                                // step 0 into the caller's scratch row, then the walk below on it
+        for (int j = 0; j < V; j++)
+            adjusted[j] = lnb_sample_adjust(x16[j], ru->counts ? ru->counts[j] : 0u, ru->bias ? ru->bias + j : nullptr, ru->repetition_penalty,
+                                            ru->presence_penalty, ru->frequency_penalty);
+        x16 = adjusted;
+    }
     LnbSampleInfo z = {0, 0, 0, 0, 0, 0, 0};
     if (info) *info = z;
     const int greedy = s->temperature == 0.0f;
@@ -112,6 +163,7 @@ LNB_SAMPLE_FN int lnb_sample_row_serial(const lnbs_u16* x16, int V, const double
     const lnbs_u64 emax = lnb_sample_f64_bits(etab[lnb_sample_key_bits(kmax)]);
     if (lnb_sample_degenerate(emax)) { z.degenerate = 1; if (info) *info = z; return a; }
     const int E = lnb_sample_exponent(emax);
+    const lnbs_u64 wmin = ru ? lnb_sample_min_weight(ru->min_p, lnb_sample_weight(emax, E)) : 1;
     // step 4: S as entries per key (equal keys = equal weights)
     static_assert(sizeof(lnbs_u32) == 4 && sizeof(lnbs_u64) == 8, "integer widths");
     lnbs_u32 cnt[65536];
@@ -120,7 +172,7 @@ LNB_SAMPLE_FN int lnb_sample_row_serial(const lnbs_u16* x16, int V, const double
         const lnbs_u32 k = lnb_sample_key(lnb_sample_scale(x16[j], T));
         if (!k) continue;
         const lnbs_u64 w = lnb_sample_weight(lnb_sample_f64_bits(etab[lnb_sample_key_bits(k)]), E);
-        if (w >= 1) { cnt[k]++; z.n_candidates++; z.w_all += w; }
+        if (w >= wmin) { cnt[k]++; z.n_candidates++; z.w_all += w; }
     }
     // steps 5-6: walk the keys downwards = the order, group by group
     const lnbs_u64 kk = s->top_k > 0 && s->top_k < z.n_candidates ? (lnbs_u64)s->top_k : (lnbs_u64)z.n_candidates;

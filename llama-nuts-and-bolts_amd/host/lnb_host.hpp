@@ -239,6 +239,18 @@ public:
         if (finished) *finished = fin != 0;
         return out;
     }
+    // lnb_decode_sample_rules_until: the same under logit rules (bias, repetition / presence / frequency penalties, min-p; include/lnb.h); counted = the
+    // text the penalties count before `token` (the prompt, and the earlier chunks' tokens of a chunked run)
+    std::vector<TokenId> DecodeSampleRulesUntil(const lnb_sampler& sampler, const lnb_logit_rules& rules, const std::vector<TokenId>& counted, TokenId token,
+                                                int startPos, int maxSteps, bool* finished = nullptr) {
+        std::vector<TokenId> out((size_t)(maxSteps > 0 ? maxSteps : 0));
+        int n = 0, fin = 0;
+        check(lnb_decode_sample_rules_until(h_, &sampler, &rules, counted.empty() ? nullptr : counted.data(), (int)counted.size(), token, startPos, maxSteps, out.data(),
+                                            &n, &fin, nullptr));
+        out.resize((size_t)n);
+        if (finished) *finished = fin != 0;
+        return out;
+    }
     // speculative greedy decoding (include/lnb.h): n-gram drafts (maxDraft 0..LNB_MAX_DRAFT, 0 = off) verified in batched passes -- the tokens
     // and KV rows of lnb_decode_greedy_until; history = the tokens before `token` (the prompt)
     void SetDraft(int maxDraft, int ngramMin, int ngramMax, const std::vector<TokenId>& corpus = {}) {

@@ -67,6 +67,7 @@ EXPORTS = [
     "lnb_model_wpack_head_bytes", "lnb_model_wpack_head_status", "lnb_op_rmsnorm_head",
     "lnb_ctx_set_token_probs", "lnb_ctx_read_token_probs", "lnb_ctx_token_prob_walks", "lnb_forward_score", "lnb_op_token_probs",
     "lnb_decode_sample_until", "lnb_batch_decode_sample_until", "lnb_op_sample", "lnb_profile_sample",
+    "lnb_decode_sample_rules_until", "lnb_batch_decode_sample_rules_until", "lnb_op_sample_rules", "lnb_profile_sample_rules",
     "lnb_forward_append", "lnb_forward_score_append",
     "lnb_ctx_set_draft", "lnb_decode_speculative_until", "lnb_op_ngram_draft",
     "lnb_batch_set_attention", "lnb_ctx_set_batched_attention", "lnb_batch_attention_form", "lnb_ctx_verify_attention_form",
@@ -131,6 +132,34 @@ def _samplers(samplers, n):
         s = s if isinstance(s, Sampler) else Sampler(*s)
         arr[i] = s
     return arr
+
+
+MAX_LOGIT_BIAS = 1024    # LNB_MAX_LOGIT_BIAS of include/lnb.h
+
+
+class LogitRules(C.Structure):
+    """lnb_logit_rules (include/lnb.h): repetition_penalty 1, presence_penalty 0, frequency_penalty 0, min_p 0 and an empty bias are each "off"; bias = {token id:
+    value} (or pairs), the values truncated to bf16, -inf bans a token.  The struct keeps the two arrays it points at alive."""
+    _fields_ = [("repetition_penalty", C.c_float), ("presence_penalty", C.c_float), ("frequency_penalty", C.c_float), ("min_p", C.c_float),
+                ("n_bias", C.c_int32), ("reserved", C.c_int32), ("bias_ids", C.POINTER(C.c_int32)), ("bias_values", C.POINTER(C.c_float))]
+
+    def __init__(self, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, bias=None):
+        pairs = list(bias.items()) if isinstance(bias, dict) else list(bias or ())
+        self._ids = np.array([p[0] for p in pairs], dtype=np.int32)
+        self._values = np.array([p[1] for p in pairs], dtype=np.float32)
+        super().__init__(float(repetition_penalty), float(presence_penalty), float(frequency_penalty), float(min_p), len(pairs), 0,
+                         self._ids.ctypes.data_as(C.POINTER(C.c_int32)) if pairs else None, self._values.ctypes.data_as(C.POINTER(C.c_float)) if pairs else None)
+
+
+def _rules(rules, n):
+    """n lnb_logit_rules structs from LogitRules objects, their argument tuples or None (all off) -> (the array, the objects that own its bias arrays)"""
+    rr = [r if isinstance(r, LogitRules) else LogitRules(*(r or ())) for r in rules]
+    if len(rr) != n:
+        raise LnbError("%d rule sets for %d rows" % (len(rr), n))
+    arr = (LogitRules * n)()
+    for i, r in enumerate(rr):
+        C.memmove(C.byref(arr, i * C.sizeof(LogitRules)), C.byref(r), C.sizeof(LogitRules))
+    return arr, rr
 
 
 class RuntimeInfo(C.Structure):
@@ -265,6 +294,11 @@ def lib():
     L.lnb_batch_decode_sample_until.argtypes = [vp, C.POINTER(Sampler), i32p, i32p, C.c_int, vp, vp, vp, f32p]
     L.lnb_op_sample.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), vp, vp, vp, C.POINTER(SampleInfo)]
     L.lnb_profile_sample.argtypes = [vp, C.POINTER(Sampler), C.c_int, C.c_int, f32p]
+    L.lnb_decode_sample_rules_until.argtypes = [vp, C.POINTER(Sampler), C.POINTER(LogitRules), vp, C.c_int, C.c_int32, C.c_int, C.c_int, vp, C.POINTER(C.c_int),
+                                                C.POINTER(C.c_int), f32p]
+    L.lnb_batch_decode_sample_rules_until.argtypes = [vp, C.POINTER(Sampler), C.POINTER(LogitRules), vp, vp, i32p, i32p, C.c_int, vp, vp, vp, f32p]
+    L.lnb_op_sample_rules.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.POINTER(LogitRules), vp, vp, vp, vp, C.POINTER(SampleInfo)]
+    L.lnb_profile_sample_rules.argtypes = [vp, C.POINTER(Sampler), C.POINTER(LogitRules), C.c_int, C.c_int, f32p]
     L.lnb_op_token_probs.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.lnb_ctx_set_draft.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int]
     L.lnb_decode_speculative_until.argtypes = [vp, vp, C.c_int, C.c_int32, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -720,19 +754,31 @@ class InferenceContext:
         _chk(self.L.lnb_decode_greedy_until(self.h, int(token), start_pos, max_steps, _p(out), C.byref(n), C.byref(fin), C.byref(ms)))
         return out[:n.value].copy(), bool(fin.value), ms.value
 
-    def decode_sample_until(self, sampler, token, start_pos, max_steps):
+    def decode_sample_until(self, sampler, token, start_pos, max_steps, rules=None, counted=None):
         """decode_greedy_until with the sampler's token in place of the argmax (lnb_decode_sample_until): sampler = a Sampler or (temperature, top_k, top_p, seed)
-        -> (tokens generated, finished flag, device ms)"""
+        -> (tokens generated, finished flag, device ms).  rules (a LogitRules or its argument tuple) or counted given: lnb_decode_sample_rules_until -- logit bias,
+        penalties over the counted text `counted` ++ [token] ++ what the call emits, min-p; a later chunk passes the earlier chunks' tokens back in `counted`"""
         s = _samplers([sampler], 1)
         out = np.empty(max(int(max_steps), 0), dtype=np.int32)
         ms, n, fin = C.c_float(0), C.c_int(0), C.c_int(0)
-        _chk(self.L.lnb_decode_sample_until(self.h, s, int(token), start_pos, max_steps, _p(out), C.byref(n), C.byref(fin), C.byref(ms)))
+        if rules is None and counted is None:
+            _chk(self.L.lnb_decode_sample_until(self.h, s, int(token), start_pos, max_steps, _p(out), C.byref(n), C.byref(fin), C.byref(ms)))
+        else:
+            rr, _keep = _rules([rules], 1)
+            cn = np.ascontiguousarray(counted if counted is not None else [], dtype=np.int32)
+            _chk(self.L.lnb_decode_sample_rules_until(self.h, s, rr, _p(cn) if cn.size else None, int(cn.size), int(token), start_pos, max_steps, _p(out), C.byref(n),
+                                                      C.byref(fin), C.byref(ms)))
         return out[:n.value].copy(), bool(fin.value), ms.value
 
-    def profile_sample(self, sampler, pos, iters):
-        """average device ms of the step's token launch alone: sample_kernel with this sampler, argmax_kernel with None (lnb_profile_sample)"""
+    def profile_sample(self, sampler, pos, iters, rules=None):
+        """average device ms of the step's token launch alone: sample_kernel with this sampler, argmax_kernel with None (lnb_profile_sample); rules (a LogitRules
+        or its argument tuple; () = all off): sample_rules_kernel on the context's tables as its last rules call left them (lnb_profile_sample_rules)"""
         ms = C.c_float(0)
-        _chk(self.L.lnb_profile_sample(self.h, None if sampler is None else _samplers([sampler], 1), pos, iters, C.byref(ms)))
+        if rules is not None:
+            rr, _keep = _rules([rules], 1)
+            _chk(self.L.lnb_profile_sample_rules(self.h, _samplers([sampler], 1), rr, pos, iters, C.byref(ms)))
+        else:
+            _chk(self.L.lnb_profile_sample(self.h, None if sampler is None else _samplers([sampler], 1), pos, iters, C.byref(ms)))
         return ms.value
 
     def set_token_probs(self, k):
@@ -980,8 +1026,9 @@ class Batch:
         self.finished = [bool(f) for f in fin]               # per sequence: a stop id ended it (start_pos[s] < 0 keeps an ended sequence frozen in the next chunk)
         return [out[s, :cnt[s]].copy() for s in range(n)], ms.value
 
-    def decode_sample_until(self, samplers, tokens, start_pos, max_steps):
-        """decode_until with one sampler per member (lnb_batch_decode_sample_until; a temperature-0 member is greedy): -> (per-sequence token arrays, device ms)"""
+    def decode_sample_until(self, samplers, tokens, start_pos, max_steps, rules=None, counted=None):
+        """decode_until with one sampler per member (lnb_batch_decode_sample_until; a temperature-0 member is greedy): -> (per-sequence token arrays, device ms).
+        rules (one LogitRules, argument tuple or None per member) or counted (one id list per member) given: lnb_batch_decode_sample_rules_until"""
         n = len(self.ctxs)
         ss = _samplers(samplers, n)
         tok = np.ascontiguousarray(tokens, dtype=np.int32); pos = np.ascontiguousarray(start_pos, dtype=np.int32)
@@ -989,8 +1036,17 @@ class Batch:
         out = np.empty((n, max(int(max_steps), 0)), dtype=np.int32)
         cnt = np.zeros(n, dtype=np.int32); fin = np.zeros(n, dtype=np.int32)
         ms = C.c_float(0)
-        _chk(self.L.lnb_batch_decode_sample_until(self.h, ss, tok.ctypes.data_as(C.POINTER(C.c_int32)), pos.ctypes.data_as(C.POINTER(C.c_int32)), max_steps, _p(out), _p(cnt),
-                                                  _p(fin), C.byref(ms)))
+        i32p = C.POINTER(C.c_int32)
+        if rules is None and counted is None:
+            _chk(self.L.lnb_batch_decode_sample_until(self.h, ss, tok.ctypes.data_as(i32p), pos.ctypes.data_as(i32p), max_steps, _p(out), _p(cnt), _p(fin), C.byref(ms)))
+        else:
+            rr, _keep = _rules(rules if rules is not None else [None] * n, n)
+            texts = [np.ascontiguousarray(t if t is not None else [], dtype=np.int32) for t in (counted if counted is not None else [None] * n)]
+            assert len(texts) == n
+            ptrs = (C.c_void_p * n)(*[t.ctypes.data if t.size else None for t in texts])
+            nc = np.array([t.size for t in texts], dtype=np.int32)
+            _chk(self.L.lnb_batch_decode_sample_rules_until(self.h, ss, rr, ptrs, _p(nc), tok.ctypes.data_as(i32p), pos.ctypes.data_as(i32p), max_steps, _p(out), _p(cnt),
+                                                            _p(fin), C.byref(ms)))
         self.finished = [bool(f) for f in fin]
         return [out[s, :cnt[s]].copy() for s in range(n)], ms.value
 
@@ -1101,12 +1157,19 @@ class InferenceEngine:
     long_context: the generation's context is a long one (lnb_ctx_create_long, up to MAX_SEQ_LEN positions) whose activation buffers hold
     prefill_chunk rows, or the prompt when the chunk is 0."""
 
-    def __init__(self, transformer, seq_len, stop_token_ids=(), prefill_chunk=0, long_context=False, sampler=None, draft=None):
+    def __init__(self, transformer, seq_len, stop_token_ids=(), prefill_chunk=0, long_context=False, sampler=None, draft=None, rules=None):
         if int(prefill_chunk) < 0:
             raise LnbError("prefill_chunk must be 0 (one Forward) or a positive row count")
         self.t, self.seq_len, self.stop, self.prefill_chunk = transformer, seq_len, set(stop_token_ids), int(prefill_chunk)
         self.long_context = bool(long_context)
         self.sampler = sampler                               # None: greedy.  A Sampler (or its tuple): EVERY generated token is sampled, the prompt's own next token included
+        # rules (a LogitRules or its argument tuple): logit bias, penalties and min-p on every generated token; the counted text is the prompt plus what has
+        # been generated.  Without a sampler the rules run greedy (temperature 0 = the argmax of the adjusted row).
+        self.rules = rules
+        if rules is not None and self.sampler is None:
+            self.sampler = Sampler(0.0)
+        if rules is not None and draft is not None:
+            raise LnbError("logit rules in the speculative loops are out of scope (include/lnb.h): pass draft=None with rules")
         if draft is not None and len(tuple(draft)) != 3:
             raise LnbError("draft must be None or (max_draft, ngram_min, ngram_max)")
         self.draft = None if draft is None else tuple(int(v) for v in draft)      # None: one pass per token.  Else the speculative loop drafts from the running text: the same tokens
@@ -1131,7 +1194,11 @@ class InferenceEngine:
                 # (the same bits into the same KV row) for its logits, then sample_kernel on that row
                 row, _ = ctx.ForwardAppend(prompt[-1:], len(prompt) - 1, want_logits=True)
                 row16 = (np.ascontiguousarray(row[0], dtype=np.float32).view(np.uint32) >> 16).astype(np.uint16)
-                first = int(op_sample(row16, [self.sampler], [len(prompt) - 1], want_info=False, device=self.t.device)[0][0])
+                if self.rules is None:
+                    first = int(op_sample(row16, [self.sampler], [len(prompt) - 1], want_info=False, device=self.t.device)[0][0])
+                else:                                        # the counted text of that step is the prompt
+                    counts = np.bincount(np.asarray(prompt, dtype=np.int64), minlength=row16.size).astype(np.uint32)
+                    first = int(op_sample_rules(row16, [self.sampler], [self.rules], counts, [len(prompt) - 1], want_info=False, device=self.t.device)[0][0])
                 if first < 0:
                     raise LnbError("the prompt's last logits row has no candidate to sample (all NaN or -inf)")
             out = [first]
@@ -1145,7 +1212,7 @@ class InferenceEngine:
                 elif self.sampler is None:
                     more, _ = ctx.decode_greedy(first, len(prompt), n_new - 1)
                 else:
-                    more, _, _ = ctx.decode_sample_until(self.sampler, first, len(prompt), n_new - 1)
+                    more, _, _ = ctx.decode_sample_until(self.sampler, first, len(prompt), n_new - 1, rules=self.rules, counted=None if self.rules is None else prompt)
                 for t in more:
                     out.append(int(t))
                     if int(t) in self.stop:
@@ -1209,6 +1276,26 @@ def op_sample(logits_u16, samplers, pos, draws=None, want_info=True, device=0):
     tok = np.full(rows, -2, dtype=np.int32)
     info = (SampleInfo * rows)() if want_info else None
     _chk(lib().lnb_op_sample(device, _p(a), rows, V, ss, _p(p), None if u is None else _p(u), _p(tok), info))
+    return tok, ([i.as_dict() for i in info] if want_info else None)
+
+
+def op_sample_rules(logits_u16, samplers, rules, counts, pos, draws=None, want_info=True, device=0):
+    """sample_rules_kernel on rows of bf16 logits [rows, V] (lnb_op_sample_rules): op_sample with rules[i] (a LogitRules, its argument tuple or None) and the
+    occurrence counts row i of counts (uint32 [rows, V]; None: all zero) -> (tokens int32 [rows], list of info dicts or None)"""
+    a = np.ascontiguousarray(logits_u16, dtype=np.uint16)
+    if a.ndim == 1:
+        a = a[None, :]
+    rows, V = a.shape
+    ss = _samplers(samplers, rows)
+    rr, _keep = _rules(rules, rows)
+    c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32).reshape(rows, V)
+    p = np.ascontiguousarray(pos, dtype=np.int32)
+    u = None if draws is None else np.array([int(d) & 0xFFFFFFFFFFFFFFFF for d in draws], dtype=np.uint64)
+    if p.size != rows or (u is not None and u.size != rows):
+        raise LnbError("%d rows, %d positions%s" % (rows, p.size, "" if u is None else ", %d draws" % u.size))
+    tok = np.full(rows, -2, dtype=np.int32)
+    info = (SampleInfo * rows)() if want_info else None
+    _chk(lib().lnb_op_sample_rules(device, _p(a), rows, V, ss, rr, None if c is None else _p(c), _p(p), None if u is None else _p(u), _p(tok), info))
     return tok, ([i.as_dict() for i in info] if want_info else None)
 
 

@@ -6,6 +6,9 @@
 The variants are alternated, --repeats runs each (at least five), and median / min / max are reported.  --parent-pkg DIR (a build of the parent commit's
 package directory): its greedy figures are taken in child processes before and after this commit's, the comparator for "sampling costs x".
 --phases: the token launch alone for samplers that switch the rule's parts on one by one.
+--rules: what the logit rules cost (lnb_decode_sample_rules_until) -- one context, sample(0.7, 40, 0.9) under three rule sets (all off, penalties only, all four) next
+to plain sampling and greedy, tokens/s and the token launch alone (lnb_profile_sample_rules); with --parent-pkg the parent's greedy AND plain sampling figures
+(--plain-only children) before and after.  Its report goes to profiles/logit_rules.md.
 Writes a markdown report (--out) and prints one JSON line."""
 import argparse
 import json
@@ -23,15 +26,24 @@ ap.add_argument("--pkg", default=os.path.join(ROOT, "llama-nuts-and-bolts_amd"),
 ap.add_argument("--greedy-only", action="store_true", help="only the greedy figures (what a parent build can run)")
 ap.add_argument("--parent-pkg", default="", help="package directory of a build of the parent commit")
 ap.add_argument("--phases", action="store_true", help="only the token launch alone, for samplers that switch the kernel's phases on one by one (one JSON line)")
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sampling.md"))
+ap.add_argument("--rules", action="store_true", help="one context under logit rules next to plain sampling and greedy -> profiles/logit_rules.md")
+ap.add_argument("--plain-only", action="store_true", help="only greedy and plain sampling on one context (what a parent build without the rules can run)")
+ap.add_argument("--out", default="")
 a = ap.parse_args()
+a.out = a.out or os.path.join(ROOT, "profiles", "logit_rules.md" if a.rules else "sampling.md")
+if a.rules or a.plain_only:
+    a.batches = ""
 assert a.repeats >= 5, "at least five runs per variant"
 sys.path[:0] = [ROOT, a.pkg]
 import lnb  # noqa: E402
 
 V, P = 128256, 128
 SAMPLERS = {"sample(1, 0, 1)": (1.0, 0, 1.0, 1234), "sample(0.7, 40, 0.9)": (0.7, 40, 0.9, 1234)}
-VARIANTS = ["greedy"] + ([] if a.greedy_only else list(SAMPLERS))
+BIAS = tuple((7 * i + 3, (-1.0) ** i * (0.5 + 0.01 * i)) for i in range(64)) + ((11, float("-inf")),)
+RULE_SETS = {"rules off": (1.0, 0.0, 0.0, 0.0, ()), "rules: penalties": (1.2, 0.4, 0.1, 0.0, ()), "rules: all four": (1.2, 0.4, 0.1, 0.05, BIAS)} if a.rules else {}
+if a.rules or a.plain_only:
+    SAMPLERS = {"sample(0.7, 40, 0.9)": SAMPLERS["sample(0.7, 40, 0.9)"]}
+VARIANTS = ["greedy"] + ([] if a.greedy_only else list(SAMPLERS)) + list(RULE_SETS)
 
 
 def spread(v):
@@ -44,11 +56,14 @@ def measure():
     res = {}
     # ---- one context ----
     c = lnb.InferenceContext(m, P + a.steps + 8)
-    _, first = c.Forward(lnb.synth_tokens(99, P, V), 0, want_logits=False)
+    prompt = lnb.synth_tokens(99, P, V)
+    _, first = c.Forward(prompt, 0, want_logits=False)
 
     def run(name):
         if name == "greedy":
             _, _, ms = c.decode_greedy_until(first, P, a.steps)
+        elif name in RULE_SETS:                              # the prompt is the counted text: 128 ids to histogram before the first step
+            _, _, ms = c.decode_sample_until(SAMPLERS["sample(0.7, 40, 0.9)"], first, P, a.steps, rules=RULE_SETS[name], counted=prompt)
         else:
             _, _, ms = c.decode_sample_until(SAMPLERS[name], first, P, a.steps)
         return 1e3 * a.steps / ms
@@ -63,7 +78,11 @@ def measure():
         us = {n: [] for n in VARIANTS}
         for _ in range(a.repeats):
             for name in VARIANTS:
-                us[name].append(1e3 * c.profile_sample(None if name == "greedy" else SAMPLERS[name], P, 200))
+                if name in RULE_SETS:
+                    run(name)                                # (leaves this rule set's tables and a logits row behind)
+                    us[name].append(1e3 * c.profile_sample(SAMPLERS["sample(0.7, 40, 0.9)"], P, 200, rules=RULE_SETS[name]))
+                else:
+                    us[name].append(1e3 * c.profile_sample(None if name == "greedy" else SAMPLERS[name], P, 200))
         res["token_launch_us"] = {("argmax" if n == "greedy" else n): spread(v) for n, v in us.items()}
     c.close()
     # ---- batches ----
@@ -95,7 +114,7 @@ def measure():
 
 
 def parent_run():
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--greedy-only", "--pkg", a.parent_pkg, "--steps", str(a.steps), "--repeats", str(a.repeats),
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--plain-only" if a.rules else "--greedy-only", "--pkg", a.parent_pkg, "--steps", str(a.steps), "--repeats", str(a.repeats),
                         "--batches", a.batches], capture_output=True, text=True, timeout=1500)
     if r.returncode != 0:
         raise SystemExit("parent run failed:\n" + r.stdout[-2000:] + r.stderr[-3000:])
@@ -126,7 +145,7 @@ if a.phases:
     lnb.build()
     print(json.dumps(phases()))
     sys.exit(0)
-if a.greedy_only:
+if a.greedy_only or a.plain_only:
     print(json.dumps(measure()))
     sys.exit(0)
 out = {"what": "sampling on configs[1] (8B shape, synthetic weights 1234, %d-token prompts, %d steps)" % (P, a.steps)}
@@ -135,7 +154,7 @@ if a.parent_pkg:
 out["this"] = measure()
 if a.parent_pkg:
     out["parent_after"] = parent_run()
-lines = ["# Sampling in the device loop: measured", "",
+lines = ["# Logit rules in the device loop: measured" if a.rules else "# Sampling in the device loop: measured", "",
          "`tools/sample_bench.py`: the 8B shape (configs[1], synthetic weights 1234), %d-token prompts, %d steps per run, the variants alternated, median (min .. max)" % (P, a.steps),
          "of %d runs each.  Tokens/s from the device events around the replays; the token launch alone from `lnb_profile_sample`." % a.repeats, ""]
 keys = ["single_tokens_per_s"] + ["batch%s_tokens_per_s" % n for n in a.batches.split(",") if n]
@@ -143,8 +162,8 @@ lines += ["| workload | variant | tokens/s | against greedy |", "|---|---|---|--
 for k in keys:
     g = out["this"][k]["greedy"]["median"]
     for side in ("parent_before", "parent_after"):
-        if side in out:
-            lines.append("| %s | greedy, parent commit (%s) | %s | |" % (k.replace("_tokens_per_s", ""), side.split("_")[1], fmt(out[side][k]["greedy"])))
+        for name, s in (out[side][k].items() if side in out else ()):
+            lines.append("| %s | %s, parent commit (%s) | %s | |" % (k.replace("_tokens_per_s", ""), name, side.split("_")[1], fmt(s)))
     for name, s in out["this"][k].items():
         lines.append("| %s | %s | %s | %+.2f %% |" % (k.replace("_tokens_per_s", ""), name, fmt(s), 100.0 * (s["median"] / g - 1.0)))
 lines += ["", "| token launch alone | microseconds |", "|---|---|"]
