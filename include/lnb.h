@@ -547,8 +547,8 @@ int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int iters, float*
  *   row_{pos + i} exactly, so the greedy acceptance rule holds with "the sampler's token of column i at position pos + i" in place of the argmax.
  *   No distribution is compared and there is no tolerance: the output is the sampling loop's token sequence, the same bits, in fewer passes.
  * Out of scope: rejection sampling against a draft MODEL, pipeline ticks, recording the sampled token's probability.  Logit bias, repetition
- *   penalties and min-p: the rules calls below; under rules the speculative loops, pipeline ticks and token-probability records are out of scope
- *   (the acceptance argument survives rules, but a verify pass would need per-column count deltas). */
+ *   penalties and min-p: the rules calls below, the speculative loops included (lnb_decode_speculative_sample_rules_until / _many); under rules
+ *   pipeline ticks, token-probability records and a draft model are out of scope. */
 #define LNB_SAMPLE_MAX_VOCAB 131072
 typedef struct lnb_sampler { float temperature; float top_p; int32_t top_k; int32_t reserved; uint64_t seed; } lnb_sampler;
 typedef struct lnb_sample_info { uint64_t w_all, w_topk, w_kept; int32_t n_candidates, n_kept, degenerate, pad; } lnb_sample_info;
@@ -628,6 +628,46 @@ int lnb_decode_speculative_sample_many(lnb_ctx* const* ctxs, int n, const lnb_sa
 int lnb_op_spec_sample_accept(int device, const uint16_t* logits_bf16 /* [w][V] */, int w, int V, const lnb_sampler* sampler, int pos0,
                               const int32_t* col_tokens /* [w] */, const int32_t* stop_ids, int n_stop, int32_t* emitted /* [w] */, int* n_emitted,
                               int* finished);
+/* ---- logit rules in the speculative sampling loops ----
+ * The draw is u(seed, pos) alone, so the token lnb_decode_sample_rules_until emits at position p is a pure function of (row_p, sampler, rules, the counted
+ * text up to p, p).  A verify pass of w columns at position pos carries the inputs d_0 .. d_{w-1}: d_0 = the current token, already in the occurrence
+ * table; d_1 .. = the draft.  Column i is the rules step at pos + i with the counts
+ *     c_j(i) = counts[j] + #{t in 1..i : d_t == j}
+ * -- the table as the rules loop would hold it after emitting d_1 .. d_i (the same token drafted twice adds two); bias, penalties, min-p, the sampler and
+ * the draw at pos + i are lnb_decode_sample_rules_until's.  Acceptance is the speculative rule: the longest prefix of columns whose token equals the next
+ * column's input.  Every EMITTED token -- an accepted draft or the bonus token -- is then added to the table (the run not finished, token >= 0; a stop
+ * token is counted before it freezes the run); a rejected draft never reaches it.  csrc/lnb_sample.h states the rule (lnb_sample_delta_count).
+ * lnb_decode_speculative_sample_rules_until: out_tokens[0 .. *n_generated), *n_generated, *finished and the KV rows [0, start_pos + *n_generated) of every
+ *   layer are bit-identical to lnb_decode_sample_rules_until with the same sampler, rules and counted text, whatever the draft settings, the corpus or
+ *   the chunking (the caller hands earlier chunks back in `counted` as there).  Rules that are all off give lnb_decode_speculative_sample_until's tokens
+ *   and stats bit for bit.  The context's two tables are rebuilt before the first pass of every call.  The rules verify passes have captured graphs of
+ *   their own per (width, attention form) beside the greedy and the sampling ones -- no family drops or recaptures another -- which point at the device
+ *   copies of the sampler and the rules: another rule set replays them.  A pass without a draft replays the context's rules one-token graph; max_draft 0
+ *   runs lnb_decode_sample_rules_until itself.
+ * lnb_decode_speculative_sample_rules_many: the contract of lnb_decode_speculative_sample_many with lnb_decode_sample_rules_until(ctxs[s], &samplers[s],
+ *   &rules[s], counted[s], n_counted[s], ...) as member s's reference; a column's delta is its member's own earlier columns of the pass, the emitted
+ *   tokens go into that member's table.  A skipped member's (start_pos[s] < 0) rules and counted text are not looked at beyond the checks.
+ * lnb_op_spec_sample_rules_accept (a test aid, as lnb_op_spec_sample_accept): the verify launch on host rows with the table `counts` [V] (NULL: all
+ *   zero) -> the tokens the pass emits and, in counts_out [V] (optional), the table after the commit.
+ * Refused, argument checks before any handle is dereferenced and everything before any cache is written: whatever lnb_decode_speculative_sample_until /
+ *   _many refuse and whatever lnb_decode_sample_rules_until refuses; the op also a column token outside [0, V).  Token-probability records and pipeline
+ *   ticks stay refused under rules. */
+int lnb_decode_speculative_sample_rules_until(lnb_ctx* c, const lnb_sampler* sampler, const lnb_logit_rules* rules, const int32_t* counted, int n_counted,
+                                              const int32_t* history, int n_history, int32_t token, int start_pos, int max_steps, int32_t* out_tokens,
+                                              int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out);
+int lnb_decode_speculative_sample_rules_many(lnb_ctx* const* ctxs, int n, const lnb_sampler* samplers /* [n] */, const lnb_logit_rules* rules /* [n] */,
+                                             const int32_t* const* counted /* [n] */, const int32_t* n_counted /* [n] */, const int32_t* const* history,
+                                             const int32_t* n_history, const int32_t* tokens, const int32_t* start_pos, int max_steps, int col_budget,
+                                             int32_t* out_tokens, int32_t* n_generated, int32_t* finished, lnb_spec_stats* stats, lnb_spec_many_info* info,
+                                             float* ms_out);
+int lnb_op_spec_sample_rules_accept(int device, const uint16_t* logits_bf16 /* [w][V] */, int w, int V, const lnb_sampler* sampler,
+                                    const lnb_logit_rules* rules, const uint32_t* counts /* [V] or NULL */, int pos0, const int32_t* col_tokens /* [w] */,
+                                    const int32_t* stop_ids, int n_stop, int32_t* emitted /* [w] */, int* n_emitted, int* finished,
+                                    uint32_t* counts_out /* [V] or NULL */);
+/* measurement aid: average HIP-event time of a verify pass's token launch alone on host rows (as the op above): spec_sample_rules_commit_kernel under
+ * `rules`, or spec_sample_commit_kernel (rules NULL); the repeats go on from the state the launch before left */
+int lnb_profile_spec_verify(int device, const uint16_t* logits_bf16 /* [w][V] */, int w, int V, const lnb_sampler* sampler, const lnb_logit_rules* rules,
+                            const uint32_t* counts /* [V] or NULL */, int pos0, const int32_t* col_tokens /* [w] */, int iters, float* avg_ms_out);
 /* measurement aid: average HIP-event time of a decode step's token launch alone -- sample_kernel with this sampler, or argmax_kernel (sampler
  * NULL) -- on the logits row the context's last step left; the launches advance the context's device state from `pos` as steps do.  Whole-model
  * contexts with no lnb_forward_stage_begin pending; a bad sampler is refused as above. */

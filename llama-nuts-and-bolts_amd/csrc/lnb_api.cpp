@@ -104,6 +104,8 @@ hipError_t lnbk_token_probs(const TokProbParams* p, hipStream_t st);
 hipError_t lnbk_spec_argmax(const uint16_t* logits, int V, int w, int32_t* g, hipStream_t st);
 hipError_t lnbk_spec_commit(const int32_t* g, int w, const BatchTab* tab, hipStream_t st);
 hipError_t lnbk_spec_sample_commit(const uint16_t* logits, int V, int w, const double* etab, const LnbSampler* smp, int32_t* g, const BatchTab* tab, unsigned* cnt, hipStream_t st);
+hipError_t lnbk_spec_sample_rules_commit(const uint16_t* logits, int V, int w, const double* etab, const LnbSampler* smp, const LnbRulesDev* rules, int32_t* g,
+                                         const BatchTab* tab, unsigned* cnt, hipStream_t st);
 hipError_t lnbk_ngram_draft(const DraftParams* p, hipStream_t st);
 hipError_t lnbk_kv_fork(const KvForkTab* tab, int nt, int split, hipStream_t st);
 hipError_t lnbk_append_many_setup(const AmPass* p, hipStream_t st);
@@ -112,6 +114,7 @@ hipError_t lnbk_spec_many_draft(const SmPass* p, hipStream_t st);
 hipError_t lnbk_spec_many_pack(const SmPass* p, hipStream_t st);
 hipError_t lnbk_spec_many_commit(const SmPass* p, hipStream_t st);
 hipError_t lnbk_spec_many_sample_commit(const SmPass* p, hipStream_t st);
+hipError_t lnbk_spec_many_sample_rules_commit(const SmPass* p, hipStream_t st);
 }
 
 // The HIP runtime spreads a process's streams over a fixed number of hardware queues (its default: 4) and streams that share a queue run one
@@ -3007,7 +3010,8 @@ static int spec_alloc(lnb_ctx* c, int text_len) {
 // the verify batch of width w, its graph captured on first use: embedding gather of the w column tokens, the blocks, the head, the
 // columns' argmax, the commit.  With the matrix-core copy the products are its column forms, without it rows of gemm_stream_kernel.
 // form 1: the pass runs the long-context pair, 2: the multi-row pair (one graph per form and width); their scratch is the context's, shared by all widths
-static int spec_verify_batch(lnb_ctx* c, int w, GraphForm form, bool sample, lnb_batch** out, hipGraphExec_t* graph_out) {
+// launch: the token launch of the pass -- greedy, sampling or sampling under rules -- each a graph family of its own per (width, form) in the batch's table
+static int spec_verify_batch(lnb_ctx* c, int w, GraphForm form, GraphLaunch launch, lnb_batch** out, hipGraphExec_t* graph_out) {
     lnb_model* m = c->m;
     const bool long_form = form != GF_SHORT;
     if (long_form && attn_long_scratch(LNB_MAX_DRAFT + 1, m->a.n_heads, c->seq_len, c->sp_e_buf, c->sp_z_part, "the verify passes")) return -1;   // (host side of the call, outside any capture)
@@ -3024,10 +3028,14 @@ static int spec_verify_batch(lnb_ctx* c, int w, GraphForm form, bool sample, lnb
     }
     b->e_buf = c->sp_e_buf; b->z_part = c->sp_z_part;
     b->attn_long = long_form; b->attn_rows = form == GF_ROWS; b->rows_zseq = c->rows_flags & 1;
-    GraphExec& gslot = b->graphs.slot(sample ? GL_SAMPLE : GL_GREEDY, form);
+    GraphExec& gslot = b->graphs.slot(launch, form);
     auto body = [&]() -> int {
         if (enqueue_batch_pass(b)) return -1;
-        if (sample) {                                        // the token launch is the one difference: every column's sampled token at its own position, then the same acceptance
+        if (launch == GL_SAMPLE_RULES) {                     // every column's token under the context's device rules, its counts the table's plus the drafts in front of it
+            HIPCHK(lnbk_spec_sample_rules_commit(b->logits, m->a.vocab_size, w, m->prob_etab, c->d_smp, c->rl.d_rules, c->sp_g, b->tab, c->sp_cnt + 1, b->stream));
+            return 0;
+        }
+        if (launch == GL_SAMPLE) {                           // the token launch is the one difference: every column's sampled token at its own position, then the same acceptance
             HIPCHK(lnbk_spec_sample_commit(b->logits, m->a.vocab_size, w, m->prob_etab, c->d_smp, c->sp_g, b->tab, c->sp_cnt + 1, b->stream));
             return 0;
         }
@@ -3048,14 +3056,16 @@ static DraftParams spec_draft_params(lnb_ctx* c, int n_text, int max_steps) {
     p.max_steps = max_steps; p.seq_len = c->seq_len; p.out = c->sp_tok; p.col_st = c->sp_st; p.word = c->sp_word_dev; p.best = c->sp_best; p.cnt = c->sp_cnt;
     return p;
 }
-// lnb_decode_speculative_until (smp null) and lnb_decode_speculative_sample_until: one loop; the sampler picks the token launch of a pass -- the sampling
-// one-token graph or the verify batch's sampling graph -- and nothing else
+// lnb_decode_speculative_until (smp null), lnb_decode_speculative_sample_until and lnb_decode_speculative_sample_rules_until (rc): one loop; the sampler
+// and the rules pick the token launch of a pass -- the one-token graph or the verify batch's graph of that launch -- and nothing else.  Under rules the
+// context's two tables are built before the first pass and every pass's token launch keeps them (the one-token graph: sample_rules_kernel).
 static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* history, int n_history, int32_t token, int start_pos, int max_steps,
-                            int32_t* out_tokens, int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out) {
+                            int32_t* out_tokens, int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out, const RulesCall* rc = nullptr) {
     if (n_history < 0) return fail("negative history length %d", n_history);
     if (max_steps <= 0) return fail("max_steps must be positive");
     if (!c || !out_tokens || !n_generated || (n_history > 0 && !history)) return fail("null argument");
     lnb_model* m = c->m;
+    if (rc && rules_check(rc->rules, rc->counted, rc->n_counted, m->a.vocab_size, "")) return -1;         // (the ids against the vocabulary, now that it is known)
     if (!m->first() || !m->last()) return fail("speculative decoding needs a whole-model handle");
     if (c->mode != LNB_MODE_EXACT) return fail("speculative decoding is exact-mode only: its verify pass is the batched exact step (the tolerance mode has none)");
     if (c->top_k > 0) return fail("speculative decoding does not record token probabilities: lnb_ctx_set_token_probs(ctx, 0) first");
@@ -3064,7 +3074,7 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
     if (smp && sample_vocab_check(m->a.vocab_size)) return -1;
     if (stats) *stats = lnb_spec_stats{};
     if (c->sp_max_draft == 0) {                              // drafting off: the greedy (the sampling) loop itself, one pass per token
-        if (decode_greedy_impl(c, token, start_pos, max_steps, out_tokens, n_generated, finished, ms_out, smp)) return -1;
+        if (decode_greedy_impl(c, token, start_pos, max_steps, out_tokens, n_generated, finished, ms_out, smp, rc)) return -1;
         if (stats) stats->passes = *n_generated;
         return 0;
     }
@@ -3076,10 +3086,16 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
     if (!m->batch_enabled) HIPCHK(lnbk_batch_prepare());
     const int n_text = n_history + 1;
     if (smp && !c->d_smp) HIPCHK(dev_alloc(c->d_smp, sizeof(LnbSampler)));
-    if (spec_alloc(c, n_text) || capture_decode_graphs(c, start_pos, max_steps, smp ? GL_SAMPLE : GL_GREEDY)) return -1;
+    if (rc && !c->rl.d_rules) HIPCHK(dev_alloc(c->rl.d_rules, sizeof(LnbRulesDev)));
+    const GraphLaunch launch = rc ? GL_SAMPLE_RULES : smp ? GL_SAMPLE : GL_GREEDY;
+    if (spec_alloc(c, n_text) || capture_decode_graphs(c, start_pos, max_steps, launch)) return -1;
     hipStream_t st = c->stream;
     c->tp_last_k = 0; c->tp_last_n = 0;
     if (smp) HIPCHK(hipMemcpyAsync(c->d_smp, smp, sizeof(LnbSampler), hipMemcpyHostToDevice, st));       // (the captured graphs hold the pointer: another sampler replays them)
+    if (rc) {                                                // the tables of the counted text; the device rules are what every rules graph points at
+        if (rules_tables(c, rc->rules, rc->counted, rc->n_counted, token, st, &c->rl.h_rules)) return -1;
+        HIPCHK(hipMemcpyAsync(c->rl.d_rules, &c->rl.h_rules, sizeof(LnbRulesDev), hipMemcpyHostToDevice, st));
+    }
     if (n_history > 0) HIPCHK(hipMemcpyAsync(c->sp_text, history, (size_t)n_history * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(c->sp_text + n_history, &token, 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(c->dtok, &token, 4, hipMemcpyHostToDevice, st));
@@ -3103,13 +3119,13 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
         s.passes++;
         if (k == 0) {
             const bool lg = want_long_attention(c, 1, start_pos + n_out);
-            HIPCHK(hipGraphLaunch(c->graphs.slot(smp ? GL_SAMPLE : GL_GREEDY, lg ? GF_LONG : GF_SHORT), st));
+            HIPCHK(hipGraphLaunch(c->graphs.slot(launch, lg ? GF_LONG : GF_SHORT), st));
         } else {
             lnb_batch* b = nullptr; hipGraphExec_t pass = nullptr;
             // the pass's last column sits at start_pos + n_out + k: the long form when the context is beyond the one-workgroup kernels' reach or past the threshold
             const bool lf = c->seq_len > c->attn_short_cap || start_pos + n_out + k + 1 > c->sp_attn_long_T;
             const GraphForm form = !lf ? GF_SHORT : (c->rows_flags & 2) ? GF_ROWS : GF_LONG;     // (rows: lnb_ctx_set_rows_attention's opt-in -- K and V read once for all columns)
-            if (spec_verify_batch(c, k + 1, form, smp != nullptr, &b, &pass)) return -1;
+            if (spec_verify_batch(c, k + 1, form, launch, &b, &pass)) return -1;
             HIPCHK(hipGraphLaunch(pass, st));
             c->sp_last_form = form; b->last_form = lf ? 1 : 0;
             s.verify_passes++; s.drafted += k;
@@ -3147,6 +3163,16 @@ extern "C" int lnb_decode_speculative_sample_until(lnb_ctx* c, const lnb_sampler
     if (!sampler) return fail("null argument (sampler)");
     if (sampler_check(sampler, "")) return -1;
     return spec_decode_impl(c, sampler, history, n_history, token, start_pos, max_steps, out_tokens, n_generated, finished, stats, ms_out);
+}
+// the same loop under logit rules (include/lnb.h): the tokens of lnb_decode_sample_rules_until, because the rules step at a position is a function of that
+// position's row, the sampler, the rules, the counted text up to it and the position -- and a verify column is given exactly that counted text
+extern "C" int lnb_decode_speculative_sample_rules_until(lnb_ctx* c, const lnb_sampler* sampler, const lnb_logit_rules* rules, const int32_t* counted, int n_counted,
+                                                         const int32_t* history, int n_history, int32_t token, int start_pos, int max_steps, int32_t* out_tokens,
+                                                         int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out) {
+    if (!sampler) return fail("null argument (sampler)");
+    if (sampler_check(sampler, "") || rules_check(rules, counted, n_counted, 0, "")) return -1;
+    const RulesCall rc{rules, counted, n_counted};
+    return spec_decode_impl(c, sampler, history, n_history, token, start_pos, max_steps, out_tokens, n_generated, finished, stats, ms_out, &rc);
 }
 // ngram_draft_kernel on host arrays (a test aid, as lnb_op_argmax): the draft that follows text, with no decode limits
 extern "C" int lnb_op_ngram_draft(int device, const int32_t* text, int n_text, const int32_t* corpus, int n_corpus,
@@ -3188,7 +3214,7 @@ static int spec_many_build(SpecMany* sm, hipStream_t st) {
     auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_mem = carve(N * sizeof(SmMember)), o_want = carve(N * 4), o_run = carve(N * 4), o_draft = carve(N * LNB_SPEC_MAX_DRAFT * 4),
                  o_best = carve(N * 2 * LNB_SPEC_MAX_NGRAM * 4), o_cnt = carve((N + 1) * 4), o_rows = carve(N * sizeof(AmRow)), o_seg = carve(N * sizeof(SmSeg)),
-                 o_stats = carve(N * sizeof(SmStats)), o_g = carve(N * 4), o_smp = carve(N * sizeof(LnbSampler));
+                 o_stats = carve(N * sizeof(SmStats)), o_g = carve(N * 4), o_smp = carve(N * sizeof(LnbSampler)), o_rules = carve(N * sizeof(LnbRulesDev));
     HIPCHK(dev_alloc(sm->dev, off));
     HIPCHK(hipMemsetAsync(sm->dev, 0, off, st));
     HIPCHK(pinned_alloc(sm->word, 16, hipHostMallocMapped));
@@ -3201,6 +3227,7 @@ static int spec_many_build(SpecMany* sm, hipStream_t st) {
     p.members = (const SmMember*)(d + o_mem); p.want = (int32_t*)(d + o_want); p.running = (int32_t*)(d + o_run); p.draft = (int32_t*)(d + o_draft);
     p.best = (int*)(d + o_best); p.cnt = (unsigned*)(d + o_cnt); p.rows = (AmRow*)(d + o_rows); p.seg = (SmSeg*)(d + o_seg);
     p.stats = (SmStats*)(d + o_stats); p.g = (int32_t*)(d + o_g); p.word = word_dev; p.smp = (const LnbSampler*)(d + o_smp);
+    p.rules = (const LnbRulesDev*)(d + o_rules);
     return 0;
 }
 // the object is published only when all of it exists: a failed allocation leaves the handle as it was, and the next call starts over
@@ -3211,13 +3238,16 @@ static int spec_many_alloc(AppendMany* am) {
     am->sm = sm;
     return 0;
 }
-// lnb_decode_speculative_many (sampling false) and lnb_decode_speculative_sample_many: one loop; the commit launch of a pass is the one difference
+struct RulesMany { const lnb_logit_rules* rules; const int32_t* const* counted; const int32_t* n_counted; };      // [n] each
+// lnb_decode_speculative_many (sampling false), lnb_decode_speculative_sample_many and lnb_decode_speculative_sample_rules_many (rl): one loop; the commit
+// launch of a pass is the one difference.  Under rules every running member's two tables are built before the first pass.
 static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_sampler* samplers, const int32_t* const* history, const int32_t* n_history,
                           const int32_t* tokens, const int32_t* start_pos, int max_steps, int col_budget,
                           int32_t* out_tokens, int32_t* n_generated, int32_t* finished,
-                          lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out) {
-    const char* const name = sampling ? "lnb_decode_speculative_sample_many" : "lnb_decode_speculative_many";
+                          lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out, const RulesMany* rl = nullptr) {
+    const char* const name = rl ? "lnb_decode_speculative_sample_rules_many" : sampling ? "lnb_decode_speculative_sample_many" : "lnb_decode_speculative_many";
     if (sampling && !samplers) return fail("%s: null argument (samplers)", name);
+    if (rl && (!rl->rules || !rl->counted || !rl->n_counted)) return fail("%s: null argument (%s)", name, !rl->rules ? "rules" : !rl->counted ? "counted" : "n_counted");
     // ---- the arguments alone: no handle is dereferenced
     if (!ctxs || !history || !n_history || !tokens || !start_pos || !out_tokens || !n_generated)
         return fail("%s: null argument (%s)", name, !ctxs ? "ctxs" : !history ? "history" : !n_history ? "n_history" : !tokens ? "tokens" : !start_pos ? "start_pos" :
@@ -3225,7 +3255,10 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
     if (n < 1 || n > LNB_BATCH_MAX) return fail("%s: a call takes 1..%d contexts (got %d)", name, LNB_BATCH_MAX, n);
     if (sampling) {
         char who[96];
-        for (int s = 0; s < n; s++) { snprintf(who, sizeof who, "%s: member %d: ", name, s); if (sampler_check(samplers + s, who)) return -1; }
+        for (int s = 0; s < n; s++) {
+            snprintf(who, sizeof who, "%s: member %d: ", name, s);
+            if (sampler_check(samplers + s, who) || (rl && rules_check(rl->rules + s, rl->counted[s], rl->n_counted[s], 0, who))) return -1;
+        }
     }
     if (max_steps <= 0) return fail("%s: max_steps must be positive (got %d)", name, max_steps);
     if (col_budget != 0 && (col_budget < n || col_budget > LNB_BATCH_MAX))
@@ -3243,6 +3276,10 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
     if (batch_shape_check(m, name)) return -1;
     if (sampling && sample_vocab_check(m->a.vocab_size)) return -1;
     const int V = m->a.vocab_size, cap = ctxs[0]->attn_short_cap;
+    if (rl) {                                                // (the ids against the vocabulary, now that it is known)
+        char who[96];
+        for (int s = 0; s < n; s++) { snprintf(who, sizeof who, "%s: member %d: ", name, s); if (rules_check(rl->rules + s, rl->counted[s], rl->n_counted[s], V, who)) return -1; }
+    }
     const int budget = col_budget ? col_budget : LNB_STREAM_COLS * ((n + LNB_STREAM_COLS - 1) / LNB_STREAM_COLS);
     int n_levels = 1, need_T = 0; bool any_long = false; size_t text_total = 0;
     for (int s = 0; s < n; s++) {
@@ -3306,6 +3343,12 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
     if (text_total) HIPCHK(hipMemcpyAsync(sm->text, text.data(), text_total * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(sm->p.stats, 0, LNB_BATCH_MAX * sizeof(SmStats), st));
     if (sampling) HIPCHK(hipMemcpyAsync((void*)sm->p.smp, samplers, (size_t)n * sizeof(LnbSampler), hipMemcpyHostToDevice, st));
+    std::vector<LnbRulesDev> hr(rl ? n : 0, LnbRulesDev{1.0f, 0.0f, 0.0f, 0.0f, nullptr, nullptr});     // (a skipped member has no column: its entry is never read)
+    if (rl) {                                                // every running member's tables, on the pass stream (member_drain above: its own stream is idle)
+        for (int s = 0; s < n; s++)
+            if (start_pos[s] >= 0 && rules_tables(ctxs[s], rl->rules + s, rl->counted[s], rl->n_counted[s], tokens[s], st, &hr[s])) return -1;
+        HIPCHK(hipMemcpyAsync((void*)sm->p.rules, hr.data(), (size_t)n * sizeof(LnbRulesDev), hipMemcpyHostToDevice, st));
+    }
     HIPCHK(hipMemsetAsync(b->derr, 0, 4, st));
     for (int s = 0; s < n; s++) if (start_pos[s] >= 0) {
         HIPCHK(hipMemcpyAsync(ctxs[s]->dtok, tokens + s, 4, hipMemcpyHostToDevice, st));
@@ -3314,6 +3357,7 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
     b->rows_form = !m->batch_enabled; b->force_zseq = 0; b->attn_rows = false;
     SmPass sp = sm->p; sp.n = n; sp.max_steps = max_steps; sp.budget = budget; sp.n_levels = n_levels; sp.logits = b->logits; sp.V = V;
     if (sampling) sp.etab = m->prob_etab; else sp.smp = nullptr;
+    if (!rl) sp.rules = nullptr;
     lnb_spec_many_info inf{};
     HIPCHK(hipEventRecord(sm->ev0, st));
     HIPCHK(lnbk_spec_many_draft(&sp, st));
@@ -3336,7 +3380,7 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
         HIPCHK(lnbk_append_many_setup(&ap, st));
         if (enqueue_batch_pass(b)) return -1;
         sp.width = width;
-        HIPCHK(sampling ? lnbk_spec_many_sample_commit(&sp, st) : lnbk_spec_many_commit(&sp, st));
+        HIPCHK(rl ? lnbk_spec_many_sample_rules_commit(&sp, st) : sampling ? lnbk_spec_many_sample_commit(&sp, st) : lnbk_spec_many_commit(&sp, st));
         HIPCHK(lnbk_spec_many_draft(&sp, st));
         HIPCHK(lnbk_spec_many_pack(&sp, st));
         HIPCHK(hipEventRecord(sm->ev, st));
@@ -3375,6 +3419,15 @@ extern "C" int lnb_decode_speculative_sample_many(lnb_ctx* const* ctxs, int n, c
                                                   int32_t* out_tokens, int32_t* n_generated, int32_t* finished,
                                                   lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out) {
     return spec_many_impl(true, ctxs, n, samplers, history, n_history, tokens, start_pos, max_steps, col_budget, out_tokens, n_generated, finished, stats, info, ms_out);
+}
+// the same call under one rule set per member (include/lnb.h): every member's tokens are those of its own lnb_decode_sample_rules_until
+extern "C" int lnb_decode_speculative_sample_rules_many(lnb_ctx* const* ctxs, int n, const lnb_sampler* samplers, const lnb_logit_rules* rules,
+                                                        const int32_t* const* counted, const int32_t* n_counted, const int32_t* const* history, const int32_t* n_history,
+                                                        const int32_t* tokens, const int32_t* start_pos, int max_steps, int col_budget,
+                                                        int32_t* out_tokens, int32_t* n_generated, int32_t* finished,
+                                                        lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out) {
+    const RulesMany rl{rules, counted, n_counted};
+    return spec_many_impl(true, ctxs, n, samplers, history, n_history, tokens, start_pos, max_steps, col_budget, out_tokens, n_generated, finished, stats, info, ms_out, &rl);
 }
 
 // ---- layer-sharded pipeline: the exchange behind the C ABI ---------------------------------------------------------------------
@@ -4033,6 +4086,92 @@ extern "C" int lnb_op_spec_sample_accept(int device, const uint16_t* logits_bf16
     *n_emitted = hst[0].n_out;
     if (finished) *finished = hst[0].finished;
     return 0;
+}
+// spec_sample_rules_commit_kernel on host rows (test aid): lnb_op_spec_sample_accept under `rules` with the occurrence table `counts` [V] (NULL: all zero;
+// col_tokens[0] is taken as counted in it already) -> what the pass emits and, in counts_out [V] (optional), the table after the commit.
+// iters > 0 (lnb_profile_spec_verify): the launch is then repeated iters times between two events on the same rows -> *avg_ms; plain: spec_sample_commit_kernel
+// in its place (the rules are then only checked).  The repeats go on from the state the launch before left: positions and counts move as in a run.
+static int spec_rules_accept_impl(int device, const uint16_t* logits_bf16, int w, int V, const lnb_sampler* sampler, const lnb_logit_rules* rules,
+                                  const uint32_t* counts, int pos0, const int32_t* col_tokens, const int32_t* stop_ids, int n_stop, int32_t* emitted,
+                                  int* n_emitted, int* finished, uint32_t* counts_out, bool plain, int iters, float* avg_ms) {
+    if (!logits_bf16 || !sampler || !rules || !col_tokens || !emitted || !n_emitted || (n_stop > 0 && !stop_ids)) return fail("null argument");
+    if (w < 1 || w > LNB_MAX_DRAFT + 1) return fail("a verify pass has 1..%d columns (got %d)", LNB_MAX_DRAFT + 1, w);
+    if (sample_vocab_check(V)) return -1;
+    if (sampler_check(sampler, "") || rules_check(rules, nullptr, 0, V, "")) return -1;
+    if (pos0 < 0 || n_stop < 0 || n_stop > LNB_MAX_STOP_IDS) return fail("bad arguments: pos0 %d, %d stop ids (at most %d)", pos0, n_stop, LNB_MAX_STOP_IDS);
+    for (int i = 0; i < w; i++) if (col_tokens[i] < 0 || col_tokens[i] >= V) return fail("column token %d at index %d is outside the vocabulary [0, %d)", col_tokens[i], i, V);
+    if (op_device(device)) return -1;
+    const size_t W = w;
+    std::vector<double> et; prob_exp_table(et);
+    const size_t o_x = align256(65536 * 8), o_s = o_x + align256(W * V * 2 + 16), o_st = o_s + align256(sizeof(LnbSampler)), o_tok = o_st + align256(W * sizeof(StepState)),
+                 o_g = o_tok + align256(W * 4), o_log = o_g + align256(W * 4), o_tab = o_log + align256(W * 4), o_cnt = o_tab + align256(sizeof(BatchTab)),
+                 o_r = o_cnt + 256, o_c = o_r + align256(sizeof(LnbRulesDev)), o_b = o_c + align256((size_t)V * 4), need = o_b + align256((size_t)V * 2);
+    Dev<char> buf;
+    HIPCHK(dev_alloc(buf, need));
+    char* const b = buf;
+    std::vector<StepState> hst(W, StepState{});
+    for (int i = 0; i < w; i++) hst[i].pos = pos0 + i;
+    hst[0].n_stop = n_stop; hst[0].honour_stop = 1;
+    for (int k = 0; k < n_stop; k++) hst[0].stop[k] = stop_ids[k];
+    std::vector<BatchTab> tab(1, BatchTab{});
+    for (int i = 0; i < w; i++) { tab[0].st[i] = (StepState*)(b + o_st) + i; tab[0].dtok[i] = (int32_t*)(b + o_tok) + i; }
+    tab[0].dout[0] = (int32_t*)(b + o_log); tab[0].dout_cap[0] = w; tab[0].n = w;
+    std::vector<uint16_t> hb((size_t)V, (uint16_t)0);
+    for (int k = 0; k < rules->n_bias; k++) hb[rules->bias_ids[k]] = bf_trunc_h(rules->bias_values[k]);
+    const LnbRulesDev hr{rules->repetition_penalty, rules->presence_penalty, rules->frequency_penalty, rules->min_p, (lnbs_u32*)(b + o_c),
+                         rules->n_bias > 0 ? (const lnbs_u16*)(b + o_b) : nullptr};
+    HIPCHK(hipMemset(b + o_g, 0, need - o_g));
+    HIPCHK(hipMemcpy(b, et.data(), 65536 * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_x, logits_bf16, W * V * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_s, sampler, sizeof(LnbSampler), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_st, hst.data(), W * sizeof(StepState), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_tok, col_tokens, W * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_tab, tab.data(), sizeof(BatchTab), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_r, &hr, sizeof hr, hipMemcpyHostToDevice));
+    if (counts) HIPCHK(hipMemcpy(b + o_c, counts, (size_t)V * 4, hipMemcpyHostToDevice));
+    if (rules->n_bias > 0) HIPCHK(hipMemcpy(b + o_b, hb.data(), (size_t)V * 2, hipMemcpyHostToDevice));
+    auto launch = [&]() {
+        return plain ? lnbk_spec_sample_commit((const uint16_t*)(b + o_x), V, w, (const double*)b, (const LnbSampler*)(b + o_s), (int32_t*)(b + o_g),
+                                               (const BatchTab*)(b + o_tab), (unsigned*)(b + o_cnt), nullptr)
+                     : lnbk_spec_sample_rules_commit((const uint16_t*)(b + o_x), V, w, (const double*)b, (const LnbSampler*)(b + o_s), (const LnbRulesDev*)(b + o_r),
+                                                     (int32_t*)(b + o_g), (const BatchTab*)(b + o_tab), (unsigned*)(b + o_cnt), nullptr);
+    };
+    HIPCHK(launch());
+    if (iters > 0) {
+        Event e0, e1;
+        HIPCHK(event_create(e0)); HIPCHK(event_create(e1));
+        for (int i = 0; i < 3; i++) HIPCHK(launch());
+        HIPCHK(hipEventRecord(e0, nullptr));
+        for (int i = 0; i < iters; i++) HIPCHK(launch());
+        HIPCHK(hipEventRecord(e1, nullptr));
+        HIPCHK(hipDeviceSynchronize());
+        float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        *avg_ms = ms / (float)iters;
+        return 0;
+    }
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(hst.data(), b + o_st, sizeof(StepState), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(emitted, b + o_log, W * 4, hipMemcpyDeviceToHost));
+    if (counts_out) HIPCHK(hipMemcpy(counts_out, b + o_c, (size_t)V * 4, hipMemcpyDeviceToHost));
+    if (hst[0].n_out < 1 || hst[0].n_out > w) return fail("internal error: a pass of %d columns emitted %d tokens", w, hst[0].n_out);
+    *n_emitted = hst[0].n_out;
+    if (finished) *finished = hst[0].finished;
+    return 0;
+}
+extern "C" int lnb_op_spec_sample_rules_accept(int device, const uint16_t* logits_bf16, int w, int V, const lnb_sampler* sampler, const lnb_logit_rules* rules,
+                                               const uint32_t* counts, int pos0, const int32_t* col_tokens, const int32_t* stop_ids, int n_stop, int32_t* emitted,
+                                               int* n_emitted, int* finished, uint32_t* counts_out) {
+    return spec_rules_accept_impl(device, logits_bf16, w, V, sampler, rules, counts, pos0, col_tokens, stop_ids, n_stop, emitted, n_emitted, finished, counts_out, false, 0, nullptr);
+}
+// measurement aid (tools/spec_sample_bench.py --rules): average HIP-event time of a verify pass's token launch ALONE on host rows -- spec_sample_rules_commit_kernel
+// under `rules`, or spec_sample_commit_kernel (rules NULL) -- w columns from position pos0, no stop ids
+extern "C" int lnb_profile_spec_verify(int device, const uint16_t* logits_bf16, int w, int V, const lnb_sampler* sampler, const lnb_logit_rules* rules,
+                                       const uint32_t* counts, int pos0, const int32_t* col_tokens, int iters, float* avg_ms_out) {
+    if (!avg_ms_out || iters <= 0) return fail("bad arguments");
+    const lnb_logit_rules off = {1.0f, 0.0f, 0.0f, 0.0f, 0, 0, nullptr, nullptr};
+    int32_t emitted[LNB_MAX_DRAFT + 1]; int n = 0;
+    return spec_rules_accept_impl(device, logits_bf16, w, V, sampler, rules ? rules : &off, counts, pos0, col_tokens, nullptr, 0, emitted, &n, nullptr, nullptr, !rules, iters,
+                                  avg_ms_out);
 }
 extern "C" int lnb_op_exp_table(int device, float divisor, double* out65536) {
     if (!out65536) return fail("null argument");

@@ -324,4 +324,5 @@ struct SmPass {                                            // the launches aroun
     int32_t* g;                                            // [LNB_BATCH_MAX] argmax per column
     const uint16_t* logits; int32_t V, width;              // commit: the pass's logits and width as the host launched it
     const struct LnbSampler* smp; const double* etab;      // spec_many_sample_commit_kernel: [LNB_BATCH_MAX] the members' samplers, the model's exp table (the greedy call: both null)
+    const struct LnbRulesDev* rules;                       // spec_many_sample_rules_commit_kernel: [LNB_BATCH_MAX] the members' rules, each with ITS context's two tables (else null)
 };

@@ -66,6 +66,8 @@
     X(SAMPLE_BATCH, "sample.batch", "batch_sample_kernel: one workgroup per member of a batched sampling step, each with its own sampler") \
     X(SAMPLE_SPEC, "sample.spec", "spec_sample_commit_kernel: one workgroup per column of a verify pass, each at its own position; the last one accepts and emits") \
     X(SAMPLE_SPEC_MANY, "sample.spec_many", "spec_many_sample_commit_kernel: the same per column of a many-context pass, each member with its own sampler") \
+    X(SAMPLE_SPEC_RULES, "sample.spec_rules", "spec_sample_rules_commit_kernel: one workgroup per column of a verify pass under logit rules, its counts the table's plus the drafts in front of it; the last one accepts, emits and counts") \
+    X(SAMPLE_SPEC_MANY_RULES, "sample.spec_many_rules", "spec_many_sample_rules_commit_kernel: the same per column of a many-context pass, each member with its own sampler, rules and tables") \
     /* the same token launches under logit rules (lnb_decode_sample_rules_until: step 0 in the row load, step 4b in the probe) */ \
     X(SAMPLE_RULES_ROW, "sample.rules_row", "sample_rules_kernel: one workgroup per logits row with its counts and bias tables -- the one-token rules step, rows of lnb_op_sample_rules") \
     X(SAMPLE_RULES_BATCH, "sample.rules_batch", "batch_sample_rules_kernel: one workgroup per member of a batched rules step, each with its own sampler, rules and tables") \

@@ -4145,7 +4145,14 @@ DEVINL void sample_rules_load8(const uint16_t* p, bool vec, int j0, int V, uint3
         w[t] = (j < V ? (uint32_t)p[j] : 0u) | ((j + 1 < V ? (uint32_t)p[j + 1] : 0u) << 16);
     }
 }
-DEVINL void sample_rules_group(const uint16_t* x, const LnbRulesDev& ru, bool alx, bool alc, bool alb, int j0, int V, uint32_t (&wd)[4]) {
+// DELTA (the verify pass under rules, spec_sample_rules_commit_kernel): the column's counts are the table's PLUS the drafts in front of it, which wait
+// in the LDS (SpecDelta).  dmask = the drafts that fall into this lane's entries -- zero for all but <= 15 lanes of the workgroup -- and only such a lane
+// walks them: a draft inside this group adds one to its count (the same token drafted twice adds two), BEFORE the "all eight zero" test below, because a
+// drafted token the table has never seen is exactly the entry that test would skip.  The table itself is only read.
+struct SpecDelta { int n; int32_t tok[LNB_SPEC_MAX_DRAFT]; };
+template <bool DELTA = false>
+DEVINL void sample_rules_group(const uint16_t* x, const LnbRulesDev& ru, bool alx, bool alc, bool alb, int j0, int V, uint32_t (&wd)[4], unsigned dmask = 0,
+                               const SpecDelta* dl = nullptr) {
     const bool full = j0 + 8 <= V;
     uint32_t cw[8];
     sample_rules_load8(x, full && alx, j0, V, wd);
@@ -4155,6 +4162,18 @@ DEVINL void sample_rules_group(const uint16_t* x, const LnbRulesDev& ru, bool al
     } else {
 #pragma unroll
         for (int i = 0; i < 8; i++) cw[i] = j0 + i < V ? ru.counts[j0 + i] : 0u;
+    }
+    if constexpr (DELTA) {
+        // (every index static: a loop of unknown length here took the packed keys out of the registers.  A lane with a draft pays 15 LDS reads and 15 x 8
+        // compare-adds in each of its groups and bounds its workgroup; the launch is timed as a whole in profiles/spec_rules.md)
+        if (dmask != 0u) {
+#pragma unroll
+            for (int t = 0; t < LNB_SPEC_MAX_DRAFT; t++) {   // (an entry at or beyond V may be counted: the caller gives it key 0 whatever its value)
+                const unsigned o = (dmask >> t) & 1u ? (unsigned)(dl->tok[t] - j0) : 8u;
+#pragma unroll
+                for (int i = 0; i < 8; i++) cw[i] += o == (unsigned)i ? 1u : 0u;
+            }
+        }
     }
     if ((cw[0] | cw[1] | cw[2] | cw[3] | cw[4] | cw[5] | cw[6] | cw[7]) != 0u &&      // (a counted token is rare: most groups skip 0a and 0b whole)
         (ru.repetition_penalty != 1.0f || ru.presence_penalty != 0.0f || ru.frequency_penalty != 0.0f)) {
@@ -4177,9 +4196,10 @@ DEVINL void sample_rules_group(const uint16_t* x, const LnbRulesDev& ru, bool al
 }
 // -> the token, valid in thread 0, and sh.z = the row's info.  has_u: pos_or_u is u of step 8 itself.  RULES: the row is adjusted by ru's step 0 as it
 // is loaded, S is step 4b's, and temperature 0 = the first maximum of the adjusted row (steps 1-3); without it the code is the plain sampler's, token for token.
-template <bool RULES = false>
+// DELTA (with RULES): the counts are the table's plus the drafts of *dl (LDS, written and fenced by a barrier before the call) -- see sample_rules_group.
+template <bool RULES = false, bool DELTA = false>
 DEVINL int sample_block(const uint16_t* x, int V, const double* etab, const LnbSampler& s, bool has_u, unsigned long long pos_or_u, SampleSh& sh,
-                        const LnbRulesDev* rules = nullptr) {
+                        const LnbRulesDev* rules = nullptr, const SpecDelta* dl = nullptr) {
     const int tid = threadIdx.x;
     int par = 0;
     if (tid == 0) { const LnbSampleInfo z0 = {0, 0, 0, 0, 0, 0, 0}; sh.z = z0; }      // (read back by thread 0 only)
@@ -4191,13 +4211,20 @@ DEVINL int sample_block(const uint16_t* x, int V, const double* etab, const LnbS
     auto key_of = [&](uint16_t b) -> uint32_t { return lnb_sample_key(T == 1.0f ? b : lnb_sample_scale(b, T)); };
     LnbRulesDev ru = {1.0f, 0.0f, 0.0f, 0.0f, nullptr, nullptr};
     if constexpr (RULES) ru = *rules;
+    unsigned dmask = 0;                                      // the drafts inside this lane's entries [tid * per, tid * per + per)
+    if constexpr (DELTA) {
+        const int nd = dl->n < LNB_SPEC_MAX_DRAFT ? dl->n : LNB_SPEC_MAX_DRAFT;
+#pragma unroll
+        for (int t = 0; t < LNB_SPEC_MAX_DRAFT; t++) dmask |= (t < nd && (unsigned)(dl->tok[t] - tid * per) < (unsigned)per ? 1u : 0u) << t;
+    }
 #pragma unroll
     for (int q = 0; q < 16; q++) {
         if (q * 8 < per) {
             const int j0 = tid * per + q * 8;
             if constexpr (RULES) {
                 uint32_t wd[4];
-                sample_rules_group(x, ru, al, (((uintptr_t)ru.counts) & 15) == 0, (((uintptr_t)ru.bias) & 15) == 0, j0, V, wd);
+                if constexpr (DELTA) sample_rules_group<true>(x, ru, al, (((uintptr_t)ru.counts) & 15) == 0, (((uintptr_t)ru.bias) & 15) == 0, j0, V, wd, dmask, dl);
+                else sample_rules_group(x, ru, al, (((uintptr_t)ru.counts) & 15) == 0, (((uintptr_t)ru.bias) & 15) == 0, j0, V, wd);
 #pragma unroll
                 for (int t = 0; t < 4; t++) {
                     const int j = j0 + 2 * t;
@@ -4475,7 +4502,9 @@ __global__ __launch_bounds__(1024) void spec_argmax_kernel(const uint16_t* logit
 // columns 0 .. a is emitted in order, exactly as a greedy step emits its token -- token log, position, the context's token word, and the stop
 // ids (the stop token is emitted and freezes the generation: nothing behind it).  Column 0 is the context's own state (tab->st[0]).
 // (spec_accept_emit: one thread; shared with spec_sample_commit_kernel, whose g holds the sampler's tokens -- the same loop for both)
-DEVINL void spec_accept_emit(const int32_t* g, int w, const BatchTab* tab) {
+// counts (optional): the context's occurrence table under logit rules -- every emitted token is counted as sample_rules_advance counts it (the run not
+// finished, tok >= 0; a stop token before it freezes the run), a rejected draft never.
+DEVINL void spec_accept_emit(const int32_t* g, int w, const BatchTab* tab, uint32_t* counts = nullptr) {
     StepState* st = tab->st[0];
     if (st->finished) return;
     int a = 0;
@@ -4487,6 +4516,7 @@ DEVINL void spec_accept_emit(const int32_t* g, int w, const BatchTab* tab) {
         st->n_out = n + 1;
         st->pos = st->pos + 1;
         *tab->dtok[0] = tok;
+        if (counts && tok >= 0) counts[tok] += 1u;           // (tok < V: an index of the row)
         bool stop = false;
         if (st->honour_stop) for (int k = 0; k < st->n_stop; k++) if (tok == st->stop[k]) stop = true;
         if (stop) { st->finished = 1; break; }
@@ -4523,6 +4553,37 @@ __global__ __launch_bounds__(1024) void spec_sample_commit_kernel(const uint16_t
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     *end.cnt = 0;                                            // (ready for the next launch: stream order)
     spec_accept_emit(end.g, end.w, end.tab);
+}
+// ---- the same under logit rules (lnb_decode_speculative_sample_rules_until) ----------------------------------------------------------------
+// Column i is the rules step at pos + i, so its occurrence counts are those the rules loop would hold after emitting d_1 .. d_i:
+// c_j(i) = counts[j] + #{t in 1..i : d_t == j} (lnb_sample.h: lnb_sample_delta_count).  The drafts in front of the column are read once into the LDS and
+// patched into the row load (sample_rules_group<true>); no column workgroup writes the table, because the other columns are reading it.  The last workgroup
+// through the ticket accepts, emits and only THEN adds the emitted tokens to the table: every column's table reads sit before its release fence, the last
+// workgroup's acquire fence follows them all -- the ticket use of spec_sample_commit_kernel.  The next launch of the stream sees the table as the rules
+// loop would hold it.  Temperature 0 is the argmax of the adjusted row inside sample_block<true>: no argmax LDS here.
+struct SpecSampleRulesEnd { SpecSampleEnd e; uint32_t* counts; };
+LNB_NO_PK_F32 __global__ __launch_bounds__(1024) void spec_sample_rules_commit_kernel(const uint16_t* logits, int V, const double* etab, const LnbSampler* smp,
+                                                                                      const LnbRulesDev* rules, int32_t* g, const BatchTab* tab, unsigned* cnt) {
+    __shared__ SampleSh sh;
+    __shared__ SpecSampleRulesEnd end;
+    __shared__ SpecDelta dl;
+    const int i = blockIdx.x;
+    const LnbSampler s = smp[0];
+    const uint16_t* x = logits + (size_t)i * V;
+    const unsigned long long pos = (unsigned long long)(long long)tab->st[i]->pos;
+    const int nd = i < LNB_SPEC_MAX_DRAFT ? i : LNB_SPEC_MAX_DRAFT;
+    if (threadIdx.x == 0) { end.e.g = g; end.e.cnt = cnt; end.e.tab = tab; end.e.w = (int)gridDim.x; end.e.last = 0; end.counts = rules->counts; dl.n = nd; }
+    if ((int)threadIdx.x < nd) dl.tok[threadIdx.x] = *tab->dtok[threadIdx.x + 1];      // d_1 .. d_i: the inputs of columns 1 .. i
+    __syncthreads();
+    const int tok = sample_block<true, true>(x, V, etab, s, false, pos, sh, rules, &dl);
+    if (threadIdx.x != 0) return;
+    end.e.g[i] = tok;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    const unsigned t = __hip_atomic_fetch_add(end.e.cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (t != (unsigned)end.e.w - 1u) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    *end.e.cnt = 0;                                          // (ready for the next launch: stream order)
+    spec_accept_emit(end.e.g, end.e.w, end.e.tab, end.counts);
 }
 DEVINL int32_t spec_text_at(const DraftParams& p, int j) { return j < p.n_text ? p.text[j] : p.gen[j - p.n_text]; }
 // N-gram (prompt lookup) draft of the next pass.  Workgroup b tries n = ngram_max - b: the latest start j in R = text ++ gen of an earlier
@@ -5441,6 +5502,14 @@ extern "C" hipError_t lnbk_spec_sample_commit(const uint16_t* logits, int V, int
     hipLaunchKernelGGL(spec_sample_commit_kernel, dim3((unsigned)w), dim3(1024), 0, st, logits, V, etab, smp, g, tab, cnt);
     return hipGetLastError();
 }
+// the same under logit rules: rules[0] with the context's two tables
+extern "C" hipError_t lnbk_spec_sample_rules_commit(const uint16_t* logits, int V, int w, const double* etab, const LnbSampler* smp, const LnbRulesDev* rules,
+                                                    int32_t* g, const BatchTab* tab, unsigned* cnt, hipStream_t st) {
+    if (V < 1 || V > LNB_SAMPLE_MAX_V || w < 1 || w > LNB_SPEC_MAX_DRAFT + 1 || !logits || !etab || !smp || !rules || !g || !tab || !cnt) return hipErrorInvalidValue;
+    form_ran(Form::SAMPLE_SPEC_RULES);
+    hipLaunchKernelGGL(spec_sample_rules_commit_kernel, dim3((unsigned)w), dim3(1024), 0, st, logits, V, etab, smp, rules, g, tab, cnt);
+    return hipGetLastError();
+}
 extern "C" hipError_t lnbk_set_state(StepState* state, int pos, int n_out, int honour_stop, hipStream_t st) {
     hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(1), 0, st, state, pos, n_out, honour_stop);
     return hipGetLastError();
@@ -5721,5 +5790,12 @@ extern "C" hipError_t lnbk_spec_many_sample_commit(const SmPass* p, hipStream_t 
     if (!spec_many_tables_ok(p) || !p->logits || p->V < 1 || p->V > LNB_SAMPLE_MAX_V || p->width < 1 || p->width > LNB_BATCH_MAX || !p->smp || !p->etab) return hipErrorInvalidValue;
     form_ran(Form::SAMPLE_SPEC_MANY);
     hipLaunchKernelGGL(spec_many_sample_commit_kernel, dim3((unsigned)p->width), dim3(1024), 0, st, *p);
+    return hipGetLastError();
+}
+extern "C" hipError_t lnbk_spec_many_sample_rules_commit(const SmPass* p, hipStream_t st) {
+    if (!spec_many_tables_ok(p) || !p->logits || p->V < 1 || p->V > LNB_SAMPLE_MAX_V || p->width < 1 || p->width > LNB_BATCH_MAX || !p->smp || !p->etab || !p->rules)
+        return hipErrorInvalidValue;
+    form_ran(Form::SAMPLE_SPEC_MANY_RULES);
+    hipLaunchKernelGGL(spec_many_sample_rules_commit_kernel, dim3((unsigned)p->width), dim3(1024), 0, st, *p);
     return hipGetLastError();
 }

@@ -96,6 +96,13 @@ LNB_SAMPLE_FN lnbs_u16 lnb_sample_adjust(lnbs_u16 x16, lnbs_u32 c, const lnbs_u1
     if (c > 0) x16 = lnb_sample_penalise(x16, c, rp, presence, frequency);
     return bias16 ? lnb_sample_add_bias(x16, *bias16) : x16;
 }
+// The counts a column of a VERIFY pass sees (lnb_decode_speculative_sample_rules_until): column i is the rules step at pos + i, whose table would hold
+// the drafts d_1 .. d_i in front of it on top of the base table -- c_j(i) = base_j + #{t < n_delta : delta[t] == j}, delta = d_1 .. d_i.  A token drafted
+// twice adds two.
+LNB_SAMPLE_FN lnbs_u32 lnb_sample_delta_count(lnbs_u32 base, int j, const int* delta, int n_delta) {
+    for (int t = 0; t < n_delta; t++) base += delta[t] == j ? 1u : 0u;
+    return base;
+}
 // step 4b: the smallest weight of S
 LNB_SAMPLE_FN lnbs_u64 lnb_sample_min_weight(float min_p, lnbs_u64 w_a) {
     const double p = (double)min_p * (double)w_a;

@@ -15,6 +15,8 @@
 //                             emit the argmax of its columns 0 .. a_s into the member's OWN state, token word and log, as spec_commit_kernel does.
 //   spec_many_sample_commit_kernel   the same with every member's own sampler (lnb_decode_speculative_sample_many): column c's token is the sampler's of
 //                             its member at the column's own position; acceptance and emission are the same function (spec_many_accept_emit).
+//   spec_many_sample_rules_commit_kernel   the same under every member's own logit rules (lnb_decode_speculative_sample_rules_many): column c's counts are its
+//                             member's table plus that member's own earlier draft columns of this pass; the emitted tokens are counted into that member's table.
 // Plain C++ and vector stores; no waits; every index is bounded by the tables' own sizes (members < p.n <= LNB_BATCH_MAX, columns < LNB_BATCH_MAX,
 // draft tokens < LNB_SPEC_MAX_DRAFT, n-gram results < LNB_SPEC_MAX_NGRAM).
 #pragma once
@@ -100,7 +102,8 @@ __global__ __launch_bounds__(LNB_BATCH_MAX) void spec_many_pack_kernel(SmPass p)
 
 // what the last workgroup's thread s does for member s (shared by spec_many_commit_kernel and spec_many_sample_commit_kernel: p.g holds the columns'
 // argmax or the samplers' tokens, the loop is the same)
-DEVINL void spec_many_accept_emit(const SmPass& p, int s) {
+// counts (optional): member s's occurrence table under logit rules -- every emitted token is counted, as spec_accept_emit does
+DEVINL void spec_many_accept_emit(const SmPass& p, int s, uint32_t* counts = nullptr) {
     if (s >= p.n || s >= LNB_BATCH_MAX) return;
     const SmSeg sg = p.seg[s];
     if (sg.cols <= 0 || sg.first < 0 || sg.first + sg.cols > p.width || p.width > LNB_BATCH_MAX) return;
@@ -116,6 +119,7 @@ DEVINL void spec_many_accept_emit(const SmPass& p, int s) {
         st->n_out = no + 1;
         st->pos = st->pos + 1;
         *m.tok = t;
+        if (counts && t >= 0) counts[t] += 1u;
         bool stop = false;
         if (st->honour_stop) for (int q = 0; q < st->n_stop; q++) if (t == st->stop[q]) stop = true;
         if (stop) { st->finished = 1; break; }
@@ -171,4 +175,42 @@ __global__ __launch_bounds__(1024) void spec_many_sample_commit_kernel(SmPass p)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     if (threadIdx.x == 0) end.cnt[LNB_BATCH_MAX] = 0;        // (ready for the next launch: stream order)
     spec_many_accept_emit(end, (int)threadIdx.x);
+}
+
+// spec_many_sample_commit_kernel under every member's own logit rules: column c of member mem takes samplers[mem], rules[mem] and member mem's two tables;
+// its delta is the tokens of the member's OWN earlier columns of this pass (rows[first + 1 .. c], first = the member's first column), read once into the
+// LDS (spec_sample_rules_commit_kernel, lnb_kernels.hip).  No column workgroup writes a table; thread s of the last workgroup through the ticket accepts,
+// emits and then counts member s's emitted tokens into member s's table -- every column's table reads sit before its release, the acquire follows them all.
+LNB_NO_PK_F32 __global__ __launch_bounds__(1024) void spec_many_sample_rules_commit_kernel(SmPass p) {
+    __shared__ SampleSh sh;
+    __shared__ SmPass end;
+    __shared__ SpecDelta dl;
+    __shared__ int s_last;
+    const int c = (int)blockIdx.x;
+    const AmRow row = p.rows[c];
+    const int mem = row.member >= 0 && row.member < LNB_BATCH_MAX ? row.member : 0;
+    const LnbSampler s = p.smp[mem];
+    const uint16_t* x = p.logits + (size_t)c * p.V;
+    const double* etab = p.etab;
+    const LnbRulesDev* rules = p.rules + mem;
+    const int V = p.V;
+    const unsigned long long pos = (unsigned long long)(long long)row.pos;
+    const int first = p.seg[mem].first;
+    const int nd = first < 0 || first > c ? 0 : min(c - first, LNB_SPEC_MAX_DRAFT);
+    if (threadIdx.x == 0) { end = p; s_last = 0; dl.n = nd; }
+    if ((int)threadIdx.x < nd) dl.tok[threadIdx.x] = p.rows[first + 1 + (int)threadIdx.x].token;      // (first + nd <= c < the pass's width)
+    __syncthreads();
+    const int tok = sample_block<true, true>(x, V, etab, s, false, pos, sh, rules, &dl);
+    if (threadIdx.x == 0) {
+        end.g[c] = tok;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        const unsigned t = __hip_atomic_fetch_add(end.cnt + LNB_BATCH_MAX, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = t == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (threadIdx.x == 0) end.cnt[LNB_BATCH_MAX] = 0;        // (ready for the next launch: stream order)
+    const int m = (int)threadIdx.x;
+    spec_many_accept_emit(end, m, m < end.n && m < LNB_BATCH_MAX ? end.rules[m].counts : nullptr);
 }

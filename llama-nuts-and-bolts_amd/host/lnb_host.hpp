@@ -298,6 +298,17 @@ public:
         r.Tokens.resize(n); r.Finished = fin != 0;
         return r;
     }
+    // lnb_decode_speculative_sample_rules_until: the tokens of DecodeSampleRulesUntil with the same sampler, rules and counted text, in fewer passes
+    Speculative DecodeSpeculativeSampleRulesUntil(const lnb_sampler& sampler, const lnb_logit_rules& rules, const std::vector<TokenId>& counted,
+                                                  const std::vector<TokenId>& history, TokenId token, int startPos, int maxSteps) {
+        Speculative r; r.Tokens.resize(maxSteps > 0 ? maxSteps : 1);
+        int n = 0, fin = 0;
+        check(lnb_decode_speculative_sample_rules_until(h_, &sampler, &rules, counted.empty() ? nullptr : counted.data(), (int)counted.size(),
+                                                        history.empty() ? nullptr : history.data(), (int)history.size(), token, startPos, maxSteps,
+                                                        r.Tokens.data(), &n, &fin, &r.Stats, nullptr));
+        r.Tokens.resize(n); r.Finished = fin != 0;
+        return r;
+    }
 private:
     static void layer_cb(int layer, int n, double secs, void* user) {      // infContext.Logf(...), llamatransformer.go:163
         auto* self = (InferenceContext*)user;
@@ -355,9 +366,11 @@ inline AppendManyInfo GetAppendManyInfo(const LlamaTransformer& t) {       // of
 struct SpeculativeMany {
     std::vector<std::vector<TokenId>> Tokens; std::vector<bool> Finished; std::vector<lnb_spec_stats> Stats; lnb_spec_many_info Info{}; float Ms = 0.f;
 };
-// samplers: nullptr = lnb_decode_speculative_many (greedy), else lnb_decode_speculative_sample_many with samplers[n]
+// samplers: nullptr = lnb_decode_speculative_many (greedy), else lnb_decode_speculative_sample_many with samplers[n]; rules and counted (both or neither):
+// lnb_decode_speculative_sample_rules_many with rules[n] and one counted text per context
 inline SpeculativeMany decodeSpeculativeMany(const lnb_sampler* samplers, const std::vector<InferenceContext*>& ctxs, const std::vector<std::vector<TokenId>>& histories,
-                                             const std::vector<TokenId>& tokens, const std::vector<int>& startPos, int maxSteps, int colBudget) {
+                                             const std::vector<TokenId>& tokens, const std::vector<int>& startPos, int maxSteps, int colBudget,
+                                             const lnb_logit_rules* rules = nullptr, const std::vector<std::vector<TokenId>>* counted = nullptr) {
     const size_t n = ctxs.size(), steps = maxSteps > 0 ? (size_t)maxSteps : 1;
     if (n == 0 || histories.size() != n || tokens.size() != n || startPos.size() != n) throw std::runtime_error("DecodeSpeculativeMany: the arrays differ in length");
     std::vector<lnb_ctx*> hs;
@@ -365,7 +378,12 @@ inline SpeculativeMany decodeSpeculativeMany(const lnb_sampler* samplers, const 
     for (auto* c : ctxs) hs.push_back(c ? c->handle() : nullptr);
     for (const auto& h : histories) { hp.push_back(h.empty() ? nullptr : h.data()); hn.push_back((int32_t)h.size()); }
     SpeculativeMany r; r.Stats.resize(n);
-    if (samplers)
+    if (rules) {
+        std::vector<const int32_t*> cp; std::vector<int32_t> cn;
+        for (const auto& t : *counted) { cp.push_back(t.empty() ? nullptr : t.data()); cn.push_back((int32_t)t.size()); }
+        check(lnb_decode_speculative_sample_rules_many(hs.data(), (int)n, samplers, rules, cp.data(), cn.data(), hp.data(), hn.data(), tokens.data(), pos.data(), maxSteps,
+                                                       colBudget, out.data(), ng.data(), fin.data(), r.Stats.data(), &r.Info, &r.Ms));
+    } else if (samplers)
         check(lnb_decode_speculative_sample_many(hs.data(), (int)n, samplers, hp.data(), hn.data(), tokens.data(), pos.data(), maxSteps, colBudget, out.data(), ng.data(),
                                                  fin.data(), r.Stats.data(), &r.Info, &r.Ms));
     else
@@ -385,6 +403,15 @@ inline SpeculativeMany DecodeSpeculativeSampleMany(const std::vector<InferenceCo
                                                    const std::vector<int>& startPos, int maxSteps, int colBudget = 0) {
     if (samplers.size() != ctxs.size() || samplers.empty()) throw std::runtime_error("DecodeSpeculativeSampleMany: one sampler per context");
     return decodeSpeculativeMany(samplers.data(), ctxs, histories, tokens, startPos, maxSteps, colBudget);
+}
+// lnb_decode_speculative_sample_rules_many: the same under one rule set and one counted text per context; every context's tokens are its own DecodeSampleRulesUntil's
+inline SpeculativeMany DecodeSpeculativeSampleRulesMany(const std::vector<InferenceContext*>& ctxs, const std::vector<lnb_sampler>& samplers,
+                                                        const std::vector<lnb_logit_rules>& rules, const std::vector<std::vector<TokenId>>& counted,
+                                                        const std::vector<std::vector<TokenId>>& histories, const std::vector<TokenId>& tokens,
+                                                        const std::vector<int>& startPos, int maxSteps, int colBudget = 0) {
+    if (samplers.size() != ctxs.size() || rules.size() != ctxs.size() || counted.size() != ctxs.size() || samplers.empty())
+        throw std::runtime_error("DecodeSpeculativeSampleRulesMany: one sampler, one rule set and one counted text per context");
+    return decodeSpeculativeMany(samplers.data(), ctxs, histories, tokens, startPos, maxSteps, colBudget, rules.data(), &counted);
 }
 
 enum GenerationState{ GSInProgress = 1, GSFinishedByReachingEOS = 2, GSFinishedByReachingSeqLen = 3 };   // inference.go:13-17

@@ -77,6 +77,8 @@ EXPORTS = [
     "lnb_forward_append_many", "lnb_model_append_many_info",
     "lnb_decode_speculative_many",
     "lnb_decode_speculative_sample_until", "lnb_decode_speculative_sample_many", "lnb_op_spec_sample_accept",
+    "lnb_decode_speculative_sample_rules_until", "lnb_decode_speculative_sample_rules_many", "lnb_op_spec_sample_rules_accept",
+    "lnb_profile_spec_verify",
     "lnb_form_count", "lnb_form_count_reset", "lnb_form_name",
     "lnb_op_rmsnorm_sum",
     "lnb_ctx_attention",
@@ -309,6 +311,13 @@ def lib():
     L.lnb_decode_speculative_sample_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Sampler), C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, vp, vp, vp,
                                                      C.POINTER(SpecStats), C.POINTER(SpecManyInfo), f32p]
     L.lnb_op_spec_sample_accept.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.c_int, vp, vp, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.lnb_decode_speculative_sample_rules_until.argtypes = [vp, C.POINTER(Sampler), C.POINTER(LogitRules), vp, C.c_int, vp, C.c_int, C.c_int32, C.c_int, C.c_int, vp,
+                                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(SpecStats), f32p]
+    L.lnb_decode_speculative_sample_rules_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Sampler), C.POINTER(LogitRules), vp, vp, C.POINTER(vp), vp, vp, vp,
+                                                           C.c_int, C.c_int, vp, vp, vp, C.POINTER(SpecStats), C.POINTER(SpecManyInfo), f32p]
+    L.lnb_op_spec_sample_rules_accept.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.POINTER(LogitRules), vp, C.c_int, vp, vp, C.c_int, vp,
+                                                  C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
+    L.lnb_profile_spec_verify.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.POINTER(LogitRules), vp, C.c_int, vp, C.c_int, f32p]
     L.lnb_model_num_tensors.argtypes = [vp]
     L.lnb_model_tensor_info.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.lnb_checkpoint_open.argtypes = [C.c_char_p, C.POINTER(vp)]
@@ -841,14 +850,21 @@ class InferenceContext:
                                                  C.byref(n), C.byref(fin), C.byref(st), C.byref(ms)))
         return out[:n.value].copy(), bool(fin.value), st.as_dict(), ms.value
 
-    def decode_speculative_sample_until(self, sampler, history, token, start_pos, max_steps):
+    def decode_speculative_sample_until(self, sampler, history, token, start_pos, max_steps, rules=None, counted=None):
         """decode_sample_until with drafts verified in batched passes (lnb_decode_speculative_sample_until): the same tokens and KV rows, because the
-        sampler's draw depends on (seed, position) only.  sampler = a Sampler or (temperature, top_k, top_p, seed); None reaches the library as NULL
+        sampler's draw depends on (seed, position) only.  sampler = a Sampler or (temperature, top_k, top_p, seed); None reaches the library as NULL.
+        rules or counted given: lnb_decode_speculative_sample_rules_until -- the tokens of decode_sample_until(..., rules=, counted=)
         -> (tokens, finished flag, stats dict, device ms)"""
         s = None if sampler is None else _samplers([sampler], 1)
         h = np.ascontiguousarray(history, dtype=np.int32)
         out = np.empty(max(int(max_steps), 0), dtype=np.int32)
         ms, n, fin, st = C.c_float(0), C.c_int(0), C.c_int(0), SpecStats()
+        if rules is not None or counted is not None:
+            rr, _keep = _rules([rules], 1)
+            cn = np.ascontiguousarray(counted if counted is not None else [], dtype=np.int32)
+            _chk(self.L.lnb_decode_speculative_sample_rules_until(self.h, s, rr, _p(cn) if cn.size else None, int(cn.size), _p(h) if h.size else None, int(h.size),
+                                                                  int(token), start_pos, max_steps, _p(out), C.byref(n), C.byref(fin), C.byref(st), C.byref(ms)))
+            return out[:n.value].copy(), bool(fin.value), st.as_dict(), ms.value
         _chk(self.L.lnb_decode_speculative_sample_until(self.h, s, _p(h) if h.size else None, int(h.size), int(token), start_pos, max_steps, _p(out),
                                                         C.byref(n), C.byref(fin), C.byref(st), C.byref(ms)))
         return out[:n.value].copy(), bool(fin.value), st.as_dict(), ms.value
@@ -952,12 +968,22 @@ def ForwardAppendMany(ctxs, token_lists, start_pos, want_logits=True):
     return [logits[e - r:e] for e, r in zip(ends, rows)], am
 
 
-def DecodeSpeculativeSampleMany(ctxs, samplers, histories, tokens, start_pos, max_steps, col_budget=0):
+def DecodeSpeculativeSampleMany(ctxs, samplers, histories, tokens, start_pos, max_steps, col_budget=0, rules=None, counted=None):
     """DecodeSpeculativeMany with one sampler per context (lnb_decode_speculative_sample_many): every context's tokens, finished flag and KV rows are the
-    bits of its own decode_sample_until; a temperature-0 member is greedy -> the same tuple"""
+    bits of its own decode_sample_until; a temperature-0 member is greedy.  rules (one LogitRules, argument tuple or None per member) or counted (one id
+    list per member) given: lnb_decode_speculative_sample_rules_many, every member its own decode_sample_until(..., rules=, counted=) -> the same tuple"""
     ctxs = list(ctxs)
-    ss = None if samplers is None else _samplers(samplers, len(ctxs))
-    return _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, True, ss)
+    n = len(ctxs)
+    ss = None if samplers is None else _samplers(samplers, n)
+    if rules is None and counted is None:
+        return _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, True, ss)
+    rr, _keep = _rules(rules if rules is not None else [None] * n, n)
+    texts = [np.ascontiguousarray(t if t is not None else [], dtype=np.int32) for t in (counted if counted is not None else [None] * n)]
+    if len(texts) != n:
+        raise LnbError("DecodeSpeculativeSampleMany: %d contexts, %d counted texts" % (n, len(texts)))
+    ptrs = (C.c_void_p * n)(*[t.ctypes.data if t.size else None for t in texts])
+    nc = np.array([t.size for t in texts], dtype=np.int32)
+    return _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, True, ss, (rr, ptrs, nc))
 
 
 def DecodeSpeculativeMany(ctxs, histories, tokens, start_pos, max_steps, col_budget=0):
@@ -969,7 +995,7 @@ def DecodeSpeculativeMany(ctxs, histories, tokens, start_pos, max_steps, col_bud
     return _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, False, None)
 
 
-def _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, sample, ss):
+def _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, sample, ss, rules=None):
     ctxs = list(ctxs)
     n = len(ctxs)
     hist = [np.ascontiguousarray(h, dtype=np.int32).reshape(-1) for h in histories]
@@ -984,7 +1010,11 @@ def _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_
     out = np.zeros((n, max(int(max_steps), 1)), dtype=np.int32)
     ng = np.zeros(n, dtype=np.int32); fin = np.zeros(n, dtype=np.int32)
     st = (SpecStats * n)(); info = SpecManyInfo(); ms = C.c_float(0)
-    if sample:
+    if rules is not None:
+        rr, ptrs, nc = rules
+        _chk(L.lnb_decode_speculative_sample_rules_many(arr, n, ss, rr, ptrs, _p(nc), harr, _p(nh), _p(tok), _p(pos), int(max_steps), int(col_budget), _p(out),
+                                                        _p(ng), _p(fin), st, C.byref(info), C.byref(ms)))
+    elif sample:
         _chk(L.lnb_decode_speculative_sample_many(arr, n, ss, harr, _p(nh), _p(tok), _p(pos), int(max_steps), int(col_budget), _p(out), _p(ng), _p(fin),
                                                   st, C.byref(info), C.byref(ms)))
     else:
@@ -1168,8 +1198,6 @@ class InferenceEngine:
         self.rules = rules
         if rules is not None and self.sampler is None:
             self.sampler = Sampler(0.0)
-        if rules is not None and draft is not None:
-            raise LnbError("logit rules in the speculative loops are out of scope (include/lnb.h): pass draft=None with rules")
         if draft is not None and len(tuple(draft)) != 3:
             raise LnbError("draft must be None or (max_draft, ngram_min, ngram_max)")
         self.draft = None if draft is None else tuple(int(v) for v in draft)      # None: one pass per token.  Else the speculative loop drafts from the running text: the same tokens
@@ -1208,7 +1236,8 @@ class InferenceEngine:
                     if self.sampler is None:
                         more, _, _, _ = ctx.decode_speculative_until(prompt, first, len(prompt), n_new - 1)
                     else:
-                        more, _, _, _ = ctx.decode_speculative_sample_until(self.sampler, prompt, first, len(prompt), n_new - 1)
+                        more, _, _, _ = ctx.decode_speculative_sample_until(self.sampler, prompt, first, len(prompt), n_new - 1, rules=self.rules,
+                                                                            counted=None if self.rules is None else prompt)
                 elif self.sampler is None:
                     more, _ = ctx.decode_greedy(first, len(prompt), n_new - 1)
                 else:
@@ -1347,6 +1376,40 @@ def op_spec_sample_accept(logits_u16, sampler, pos0, col_tokens, stop_ids=(), de
     _chk(lib().lnb_op_spec_sample_accept(device, _p(a), w, V, _samplers([sampler], 1), int(pos0), _p(ct), _p(stop) if stop.size else None, int(stop.size),
                                          _p(out), C.byref(n), C.byref(fin)))
     return out[:n.value].copy(), bool(fin.value)
+
+
+def op_spec_sample_rules_accept(logits_u16, sampler, rules, counts, pos0, col_tokens, stop_ids=(), device=0):
+    """spec_sample_rules_commit_kernel on host rows (lnb_op_spec_sample_rules_accept): op_spec_sample_accept under `rules` (a LogitRules, its argument tuple or
+    None) with the occurrence table counts [V] (None: all zero), which already holds col_tokens[0]; column i sees counts plus col_tokens[1 .. i]
+    -> (the tokens the pass emits, finished flag, the table after the commit as a uint32 array)"""
+    a = np.ascontiguousarray(logits_u16, dtype=np.uint16)
+    w, V = a.shape
+    ct = np.ascontiguousarray(col_tokens, dtype=np.int32)
+    if ct.size != w:
+        raise LnbError("%d column tokens for %d rows" % (ct.size, w))
+    c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+    if c is not None and c.size != V:
+        raise LnbError("%d counts for rows of %d entries" % (c.size, V))
+    rr, _keep = _rules([rules], 1)
+    stop = np.ascontiguousarray(stop_ids, dtype=np.int32)
+    out = np.zeros(w, dtype=np.int32)
+    after = np.zeros(V, dtype=np.uint32)
+    n, fin = C.c_int(0), C.c_int(0)
+    _chk(lib().lnb_op_spec_sample_rules_accept(device, _p(a), w, V, _samplers([sampler], 1), rr, None if c is None else _p(c), int(pos0), _p(ct),
+                                               _p(stop) if stop.size else None, int(stop.size), _p(out), C.byref(n), C.byref(fin), _p(after)))
+    return out[:n.value].copy(), bool(fin.value), after
+
+
+def profile_spec_verify(logits_u16, sampler, rules, counts, pos0, col_tokens, iters, device=0):
+    """average device ms of a verify pass's token launch alone on these rows (lnb_profile_spec_verify): under `rules`, or the plain sampling launch (None)"""
+    a = np.ascontiguousarray(logits_u16, dtype=np.uint16)
+    ct = np.ascontiguousarray(col_tokens, dtype=np.int32)
+    c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+    rr = None if rules is None else _rules([rules], 1)[0]
+    ms = C.c_float(0)
+    _chk(lib().lnb_profile_spec_verify(device, _p(a), a.shape[0], a.shape[1], _samplers([sampler], 1), rr, None if c is None else _p(c), int(pos0), _p(ct), int(iters),
+                                       C.byref(ms)))
+    return ms.value
 
 
 def op_exp_table(divisor=1.0, device=0):

@@ -187,8 +187,10 @@ def main(asm_path=None):
     # of one VGPR around it.  Their scratch size is 0 and their vgpr_spill_count is 0, which the line above still requires.)
     # (spec_sample_commit_kernel / spec_many_sample_commit_kernel: the same sample_block inlined, 17 / 15 scalars in VGPR lanes; what their epilogues need waits in the LDS)
     # (sample_rules_kernel / batch_sample_rules_kernel: the same sample_block with the rules' row load, 7 / 4 scalars in VGPR lanes; no argmax arrays in their LDS)
+    # (spec_sample_rules_commit_kernel / spec_many_sample_rules_commit_kernel: the rules' row load with the draft delta; figures in profiles/spec_rules.md)
     SGPR_SPILL_OK = ("attn_gqa_kernel", "attn_one_kernel", "_Z13sample_kernelP", "_Z19batch_sample_kernelP",      # (these two kernels and no other *sample_kernel)
-                     "_Z25spec_sample_commit_kernelP", "_Z30spec_many_sample_commit_kernel6SmPass", "_Z19sample_rules_kernelP", "_Z25batch_sample_rules_kernelP")
+                     "_Z25spec_sample_commit_kernelP", "_Z30spec_many_sample_commit_kernel6SmPass", "_Z19sample_rules_kernelP", "_Z25batch_sample_rules_kernelP",
+                     "_Z31spec_sample_rules_commit_kernelP", "_Z36spec_many_sample_rules_commit_kernel6SmPass")
     spills, cur = [], ""
     for l in txt:
         mname = re.search(r"\.name:\s+(\S+)", l)

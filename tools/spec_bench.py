@@ -14,7 +14,10 @@ the verify passes at a long context: a prompt of --prefix tokens, the corpus = t
 rows greedy and width 2 / 8 / 16 only.  --seq-len: the context's capacity (beyond ~7.8 K the passes run the long-context attention);
 --long-threshold N: lnb_ctx_set_batched_attention (0 = the long-context form in every verify pass).
 --rows-attention: every width twice -- the long-context pair with the columns as grid.z (verify_attention_form 1) and the multi-row pair that reads K and V
-once for all columns (lnb_ctx_set_rows_attention flags bit 1, form 2) -- median ms per pass of --reps runs with min..max, next to the one-token step."""
+once for all columns (lnb_ctx_set_rows_attention flags bit 1, form 2) -- median ms per pass of --reps runs with min..max, next to the one-token step.
+
+  python tools/spec_bench.py --rules [--steps 256] [--reps 5]
+the speculative sampling loops under logit rules against the rules loop, and the rules verify launch alone (rules_loop below)."""
 import argparse
 import json
 import os
@@ -76,6 +79,79 @@ def long_prefix(args):
             f.write("\n")
 
 
+def rules_loop(args):
+    """--rules: the speculative loops under logit rules (lnb_decode_speculative_sample_rules_until) at configs[1] with the matrix-core copy.  Per sampler: the rules loop
+    (the baseline), the plain speculative sampling loop on ITS continuation, the rules speculative loop with the true continuation and with every 8th token wrong as the
+    corpus -- runs alternated, medians [min .. max], tokens checked -- then the token launch ALONE on sixteen logits rows of the model: the rules verify launch and the
+    plain one at widths 2 / 8 / 16 (lnb_profile_spec_verify) beside sample_rules_kernel on one row (lnb_profile_sample_rules)."""
+    g = json.load(open(os.path.join(ROOT, "tests", "golden", "configs1_tokens.json")))
+    P, N, V, MD = 128, min(args.steps, 256), lnb.LLAMA_8B["vocab_size"], 7
+    model = lnb.LlamaTransformer(**dict(lnb.LLAMA_8B, n_layers=args.layers)).fill_synthetic(g["weights_seed"]).finalize()
+    model.enable_batch()
+    prompt = lnb.synth_tokens(g["prompt_seed"], P, V)
+    ctx = lnb.InferenceContext(model, P + N + 1)
+    _, first = ctx.Forward(prompt, 0, want_logits=False)
+    rows16, _ = ctx.ForwardAppend(prompt[-16:], P - 16, want_logits=True)     # (the same sixteen rows once more, for their logits)
+    rows16 = (np.ascontiguousarray(rows16, dtype=np.float32).view(np.uint32) >> 16).astype(np.uint16)
+    rules = lnb.LogitRules(1.2, 0.4, 0.1, 0.05, [(j, -0.5) for j in range(100, 164)] + [(7, float("-inf"))])
+    counts = np.bincount(prompt, minlength=V).astype(np.uint32)
+    stat = lambda xs: {"median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4)}
+    res = {"workload": "Llama-3.1-8B shape (%d layers), synthetic weights, %d-token prompt, %d steps, max_draft %d, n-grams 1..4, rules (1.2, 0.4, 0.1, min-p 0.05, 65 bias "
+                       "entries, one -inf), counted text = the prompt; medians of %d alternated runs" % (args.layers, P, N, MD, args.reps), "loop": {}, "launch_us": {}}
+
+    def timed(fn, want):
+        lnb._chk(lnb.lib().lnb_ctx_synchronize(ctx.h))
+        t0 = time.perf_counter()
+        r = fn()
+        ms = (time.perf_counter() - t0) * 1e3
+        assert (r[0] == want).all(), "tokens differ from the reference loop's"
+        return ms, r
+
+    for name, smp in (("(1, 0, 1)", (1.0, 0, 1.0, 777)), ("(0.7, 40, 0.9)", (0.7, 40, 0.9, 777))):
+        want_r = ctx.decode_sample_until(smp, first, P, N, rules=rules, counted=prompt)[0]
+        want_p = ctx.decode_sample_until(smp, first, P, N)[0]
+        wrong8 = np.concatenate([[first], want_r]).astype(np.int32)
+        wrong8[7::8] = (wrong8[7::8] + 1) % V
+        kinds = {"rules loop (baseline)": lambda: ctx.decode_sample_until(smp, first, P, N, rules=rules, counted=prompt),
+                 "plain speculative sampling, true corpus": lambda: (ctx.set_draft(MD, 1, 4, np.concatenate([[first], want_p])),
+                                                                     ctx.decode_speculative_sample_until(smp, prompt, first, P, N))[1],
+                 "rules speculative, true corpus": lambda: (ctx.set_draft(MD, 1, 4, np.concatenate([[first], want_r])),
+                                                            ctx.decode_speculative_sample_until(smp, prompt, first, P, N, rules=rules, counted=prompt))[1],
+                 "rules speculative, every 8th wrong": lambda: (ctx.set_draft(MD, 1, 4, wrong8),
+                                                                ctx.decode_speculative_sample_until(smp, prompt, first, P, N, rules=rules, counted=prompt))[1]}
+        runs = {k: [] for k in kinds}
+        for rep in range(args.reps + 1):                     # (the first round captures the graphs)
+            for k, fn in kinds.items():
+                runs[k].append(timed(fn, want_p if k.startswith("plain") else want_r))
+        cell = {}
+        for k, rs in runs.items():
+            ms = [r[0] for r in rs[1:]]
+            cell[k] = {"ms": stat(ms), "tokens_per_s": round(N / statistics.median(ms) * 1e3, 1)}
+            if len(rs[-1][1]) == 4:
+                st, dev = rs[-1][1][2], statistics.median(r[1][3] for r in rs[1:])
+                cell[k].update(st, device_ms_per_pass=round(dev / st["passes"], 4), accepted_per_pass=round(st["accepted"] / st["passes"], 3))
+        step = statistics.median(r[1][2] for r in runs["rules loop (baseline)"][1:]) / N
+        for k in ("rules speculative, true corpus", "rules speculative, every 8th wrong"):      # a pass of cost t emits 1 + accepted tokens: even with the loop at t / step - 1
+            cell[k]["break_even_accepted_per_pass"] = round(cell[k]["device_ms_per_pass"] / step - 1.0, 3)
+        cell["rules loop (baseline)"]["device_ms_per_step"] = round(step, 4)
+        res["loop"][name] = cell
+        launch = {}
+        for rep in range(args.reps):
+            for w in (2, 8, 16):
+                cols = [int(t) for t in prompt[-16:][:w]]
+                for k, r in (("rules verify, width %d" % w, rules), ("rules verify, all off, width %d" % w, lnb.LogitRules()), ("plain verify, width %d" % w, None)):
+                    launch.setdefault(k, []).append(1e3 * lnb.profile_spec_verify(rows16[:w], smp, r, counts, P - 16, cols, 200))
+            launch.setdefault("sample_rules_kernel, one row", []).append(1e3 * ctx.profile_sample(smp, P, 200, rules=rules))
+            launch.setdefault("sample_kernel, one row", []).append(1e3 * ctx.profile_sample(smp, P, 200))
+        res["launch_us"][name] = {k: stat(v) for k, v in launch.items()}
+    ctx.close(); model.close()
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=287)
@@ -86,7 +162,10 @@ def main():
     ap.add_argument("--long-threshold", type=int, default=None, help="lnb_ctx_set_batched_attention(N)")
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--rows-attention", action="store_true", help="with --prefix: each width on the long pair (form 1) and on the multi-row pair (form 2)")
+    ap.add_argument("--rules", action="store_true", help="the speculative sampling loops under logit rules, and their verify launch alone")
     args = ap.parse_args()
+    if args.rules:
+        return rules_loop(args)
     if args.prefix is not None:
         return long_prefix(args)
     g = json.load(open(os.path.join(ROOT, "tests", "golden", "configs1_tokens.json")))
