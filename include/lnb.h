@@ -682,7 +682,27 @@ int lnb_profile_sample(lnb_ctx* c, const lnb_sampler* sampler, int pos, int iter
 int lnb_batch_set_attention(lnb_batch* b, int long_threshold, int force_zseq);
 /* the same for the verify passes of lnb_decode_speculative_until on this context (chosen per pass; one scratch for all widths) */
 int lnb_ctx_set_batched_attention(lnb_ctx* c, int long_threshold, int force_zseq);
+/* Shared prefix of a batch: while set, every step of the batch (lnb_batch_decode, _decode_until, _decode_sample_until, _decode_sample_rules_until,
+ * lnb_batch_profile_kernel) reads positions [0, n_pos) of every live member's attention from src's caches, in every layer, once per 16 (member, head)
+ * rows instead of once per member.  A member's own rows [0, n_pos) are not read by the batch -- a context that only ever decodes in this batch needs
+ * no lnb_ctx_fork -- and its rows from n_pos on are read and written exactly as before.  Defined result: every member's tokens, logits, finished
+ * flag and KV rows [n_pos, ...) are those of the same batch run on members that hold src's rows, bit for bit (hence those of the member's own
+ * single-context run).  The one arithmetic difference is that of the prefill attention: below n_pos & ~15 a product p * v is fused into its add, which
+ * shows only when a single product is not a normal f32.  A set prefix always takes this form (lnb_batch_attention_form: 2), with no threshold; it is
+ * meant for many members on a long prefix: it re-reads K and V per 16 rows where the other forms re-read them per member, but its time hardly falls with
+ * the member count.  Measured (profiles/shared_prefix_attention.md, 8B head geometry): faster from about a hundred members on a prefix of a thousand
+ * positions or more, and wherever the batch would otherwise run the long-context pair; slower with 32 members or fewer at capacities the one-workgroup
+ * kernels reach -- there it saves the fork, not time.  Members and src may differ in capacity; src may be a member.
+ * src == NULL or n_pos == 0 clears.  Refused, with lnb_last_error naming the argument and nothing changed: n_pos < 0; n_pos beyond src's capacity;
+ * n_pos at or beyond a member's capacity; src of another model handle (model, device or stage range); a member or src with a
+ * lnb_forward_stage_begin pending; a member in the tolerance mode; head_dim other than 128 / 64.  While it is set, a decode call whose live member
+ * starts below n_pos is refused (a frozen member's negative position is exempt), so are lnb_batch_set_state / lnb_pipeline_tick_batch, and so are
+ * lnb_ctx_destroy and lnb_ctx_reset of src.  Setting or clearing drops the batch's captured steps of this form.  Scratch, allocated by this call:
+ * with tiles = ceil(n * (n_heads / n_kv_heads) / 16) and L = the largest member capacity,
+ * n_kv_heads * tiles * (ceil(L / 16) * 512 + 16 * ceil(L / 256) * 8) bytes (36.2 MB for 128 members of 4352 positions at 32 / 8 heads). */
+int lnb_batch_set_shared_prefix(lnb_batch* b, lnb_ctx* src, int n_pos);
 /* 0: the last batched call / verify pass ran the one-workgroup kernels, 1: the long-context pair (a test and a bench print it);
+ * lnb_batch_attention_form also 2: the shared-prefix pair (lnb_batch_set_shared_prefix);
  * lnb_ctx_verify_attention_form also 2: the multi-row long-context pair (lnb_ctx_set_rows_attention, flags bit 1) */
 int lnb_batch_attention_form(const lnb_batch* b, int* out);
 int lnb_ctx_verify_attention_form(const lnb_ctx* c, int* out);

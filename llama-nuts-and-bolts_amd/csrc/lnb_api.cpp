@@ -45,6 +45,7 @@ extern "C" {
 hipError_t lnbk_gemv(const GemvParams* p, int rw, int nch, int epi, int norm, hipStream_t st);
 hipError_t lnbk_attn(const AttnParams* p, hipStream_t st);
 hipError_t lnbk_attn_rows(const AttnParams* p, int pos0, hipStream_t st);
+hipError_t lnbk_attn_shared(const AttnSharedParams* sp, hipStream_t st);
 hipError_t lnbk_kv_scan_nonfinite(const uint16_t* ck, const uint16_t* cv, int seq_len, int kv_dim, int hd, const StepState* st, int pos0, int rows, int* word, hipStream_t s);
 hipError_t lnbk_nonfinite_or(int* dst, const int* src, hipStream_t s);
 hipError_t lnbk_attn_plain(const AttnParams* p, const int* word, hipStream_t st);
@@ -171,7 +172,7 @@ static hipError_t event_create(Event& e, unsigned flags = hipEventDefault) { ret
 static hipError_t stream_create(Stream& s, unsigned flags) { return s.fill([&](hipStream_t* q) { return hipStreamCreateWithFlags(q, flags); }); }
 // which captured step: the token launch that ends it, and the attention form its launches bake in
 enum GraphLaunch { GL_GREEDY = 0, GL_SAMPLE, GL_STAGE, GL_SAMPLE_RULES, GL_COUNT };
-enum GraphForm { GF_SHORT = 0, GF_LONG, GF_ROWS, GF_COUNT };         // (0, 1, 2: also what lnb_ctx_verify_attention_form reports)
+enum GraphForm { GF_SHORT = 0, GF_LONG, GF_ROWS, GF_SHARED, GF_COUNT };      // (0, 1, 2: also what lnb_ctx_verify_attention_form reports; GF_SHARED: a batch with a shared prefix)
 using Graphs = GraphTable<hipGraphExec_t, hipGraphExecDestroy, GL_COUNT, GF_COUNT>;
 
 static inline float bf_wide_h(uint16_t b) { uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; }
@@ -265,6 +266,7 @@ struct lnb_ctx {
     int mode = LNB_MODE_EXACT;             // LNB_MODE_FAST: split-K kernels of lnb_fast.hip (tolerance mode, opt-in)
     int sched = LNB_SCHED_LATENCY;         // LNB_SCHED_THROUGHPUT: the co-residency-friendly forms of the one-token kernels (lnb_ctx_set_schedule)
     int n_stop = 0;                        // host copy of StepState.n_stop (lnb_ctx_set_stop_ids): entry points that cannot honour stop ids refuse such a context
+    int prefix_users = 0;                  // live lnb_batch handles whose shared prefix this context is (lnb_batch_set_shared_prefix): their launches read its caches
     int batch_users = 0;                   // live lnb_batch handles this context is a member of: their device tables and captured graphs hold its raw pointers
     // long-context decode attention (attn_long_*_kernel): used for one-token calls whose context exceeds attn_long_T
     Dev<double> e_buf, z_part; Dev<int> zseq_count;
@@ -964,6 +966,7 @@ extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
     // a batch bakes its members' device pointers (state words, token words, caches) into its tables and captured graphs: freeing a member
     // under it would make the next lnb_batch_decode / lnb_pipeline_tick_batch read and write freed memory.  Destroy the batch first.
     if (c->batch_users > 0) return fail("context is a member of %d live batch(es): lnb_batch_destroy them first", c->batch_users);
+    if (c->prefix_users > 0) return fail("context is the shared prefix of %d live batch(es): clear it (lnb_batch_set_shared_prefix(b, NULL, 0)) or destroy them first", c->prefix_users);
     hipSetDevice(c->m->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     for (lnb_batch* b : c->sp_b) if (b) lnb_batch_destroy(b);      // the verify batches: their tables hold this context's pointers
@@ -973,6 +976,7 @@ extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
 
 extern "C" int lnb_ctx_reset(lnb_ctx* c) {
     if (!c) return fail("null argument");
+    if (c->prefix_users > 0) return fail("context is the shared prefix of %d live batch(es): clear it (lnb_batch_set_shared_prefix(b, NULL, 0)) or destroy them first", c->prefix_users);
     HIPCHK(hipSetDevice(c->m->device));
     const size_t kvn = (size_t)c->seq_len * c->m->kv_dim;
     for (size_t l = 0; l < c->ck.size(); l++) if (c->ck[l]) { HIPCHK(hipMemsetAsync(c->ck[l], 0, kvn * 2, c->stream)); HIPCHK(hipMemsetAsync(c->cv[l], 0, kvn * 2, c->stream)); }
@@ -2177,6 +2181,10 @@ struct lnb_batch {
     int attn_long_T = 0x7FFFFFFF, force_zseq = 0, last_form = 0;
     Dev<double> e_own, z_own;              // the batch's own scratch (scratch_owned)
     double* e_buf = nullptr; double* z_part = nullptr;     // what the launches take: e_own / z_own, or (a verify batch) its context's sp_e_buf / sp_z_part
+    // shared prefix (lnb_batch_set_shared_prefix): every step reads positions [0, sp_n) of every member from sp_src's caches (the shared form, one graph
+    // of its own per token launch: GF_SHARED); sp_idx / sp_z: its scratch (lnb_shared_idx_bytes / lnb_shared_z_bytes), allocated by the call that sets it
+    lnb_ctx* sp_src = nullptr; int sp_n = 0;
+    Dev<uint64_t> sp_idx; Dev<double> sp_z;
     Dev<LnbSampler> d_smp;                 // the device array of n samplers the sampling steps point at
     Dev<LnbRulesDev> d_rules; std::vector<LnbRulesDev> h_rules;      // the same for the rules steps: every member's rules and ITS CONTEXT's tables (BatchTab stays as it is)
     // a verify batch whose columns run the multi-row long-context pair (lnb_ctx_set_rows_attention, flags bit 1)
@@ -2266,6 +2274,7 @@ extern "C" int lnb_batch_destroy(lnb_batch* b) {
     hipSetDevice(b->m->device);
     if (b->stream) hipStreamSynchronize(b->stream);
     if (b->counted) for (lnb_ctx* c : b->ctxs) c->batch_users--;
+    if (b->sp_src) b->sp_src->prefix_users--;
     delete b;
     return 0;
 }
@@ -2385,8 +2394,23 @@ static int batch_select_form(lnb_batch* b, bool want_long) {
     b->attn_long = want_long;
     return 0;
 }
+// what a batch with a shared prefix asks of a call's start positions (a frozen sequence's negative position is exempt, as below) and of the source
+static int batch_prefix_check(const lnb_batch* b, const int32_t* start_pos) {
+    if (!b->sp_src) return 0;
+    for (int s = 0; s < b->n; s++)
+        if (start_pos[s] >= 0 && start_pos[s] < b->sp_n)
+            return fail("sequence %d: start_pos %d lies below the batch's shared prefix (n_pos %d): a live member starts at or beyond it", s, start_pos[s], b->sp_n);
+    if (b->sp_src->pending) return fail("the shared prefix's context (src): a lnb_forward_stage_begin has not been ended");
+    return 0;
+}
+static int batch_graph_form(const lnb_batch* b) { return b->sp_src ? GF_SHARED : b->attn_long ? GF_LONG : GF_SHORT; }
+static int batch_ran_form(const lnb_batch* b) { return b->sp_src ? 2 : b->attn_long ? 1 : 0; }      // what lnb_batch_attention_form reports
 // ... for a run that starts at these positions: the largest decides (a frozen sequence's negative position does not move the form)
 static int batch_select_form_at(lnb_batch* b, const int32_t* start_pos) {
+    if (b->sp_src) {                                         // a shared prefix: the shared form at every position (no threshold, no scratch of the long form)
+        if (hipStreamSynchronize(b->sp_src->stream) != hipSuccess) return fail("the shared prefix's context: its stream reports an error");
+        return 0;
+    }
     int max_pos = 0;
     for (int s = 0; s < b->n; s++) max_pos = std::max(max_pos, start_pos[s]);
     return batch_select_form(b, batch_want_long(b, max_pos));
@@ -2477,6 +2501,13 @@ static int enqueue_batch_kernel(lnb_batch* b, int l, int which) {
         ap.S = b->n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
         ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
         ap.zseq_count = b->zseq ? b->zseq : b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
+        if (b->sp_src) {                                     // a set prefix always takes the shared form: the members' rows below it may be unfilled
+            AttnSharedParams sp{}; sp.a = ap;
+            sp.a.seq_len = b->maxT; sp.a.force_zseq = b->force_zseq & 1; sp.a.z_part = b->sp_z; sp.idx = b->sp_idx;
+            sp.src_k = b->sp_src->ck[l - m->layer_begin]; sp.src_v = b->sp_src->cv[l - m->layer_begin]; sp.src_len = b->sp_src->seq_len; sp.n_pos = b->sp_n;
+            sp.n_tiles = lnb_shared_tiles(b->n, a.n_heads / a.n_kv_heads); sp.njt = (b->maxT + 15) / 16;
+            HIPCHK(lnbk_attn_shared(&sp, b->stream)); return 0;
+        }
         HIPCHK(batch_attn_launch(b, ap, b->stream)); return 0; }
     case K_WO: {
         BatchProd d{BP_WO, nullptr, b->att_xt, &L.wo, L.m_wo, m->q_dim, dim, 1, EPI_RESID}; d.out = b->h; d.res = b->x;
@@ -2572,6 +2603,7 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     }
     HIPCHK(hipSetDevice(m->device));
     if (n_steps <= 0) return fail("n_steps must be positive");
+    if (batch_prefix_check(b, start_pos)) return -1;
     for (int s = 0; s < b->n; s++) {
         lnb_ctx* c = b->ctxs[s];
         if (n_steps > c->dout_cap) return fail("sequence %d: n_steps %d exceeds the context length %d", s, n_steps, c->dout_cap);
@@ -2586,7 +2618,7 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     hipStream_t st = b->stream;
     if (batch_select_form_at(b, start_pos)) return -1;
     const bool use_graph = knob(Knob::NO_GRAPH) == 0;
-    GraphExec& gslot = b->graphs.slot(rules ? GL_SAMPLE_RULES : smp ? GL_SAMPLE : GL_GREEDY, b->attn_long ? GF_LONG : GF_SHORT);       // one captured step per form
+    GraphExec& gslot = b->graphs.slot(rules ? GL_SAMPLE_RULES : smp ? GL_SAMPLE : GL_GREEDY, batch_graph_form(b));       // one captured step per form
     if (smp && !b->d_smp) HIPCHK(dev_alloc(b->d_smp, (size_t)LNB_BATCH_MAX * sizeof(LnbSampler)));
     if (rules && !b->d_rules) { HIPCHK(dev_alloc(b->d_rules, (size_t)LNB_BATCH_MAX * sizeof(LnbRulesDev))); b->h_rules.assign(LNB_BATCH_MAX, LnbRulesDev{}); }
     if (use_graph && capture_once(gslot, st, [&] { return enqueue_batch_step(b, false, smp != nullptr, rules != nullptr); })) return -1;
@@ -2613,7 +2645,7 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
         else if (enqueue_batch_step(b, false, smp != nullptr, rules != nullptr)) return -1;
     }
     HIPCHK(hipEventRecord(b->ev1, st));
-    b->last_form = b->attn_long ? 1 : 0;
+    b->last_form = batch_ran_form(b);
     for (int s = 0; s < b->n; s++)
         HIPCHK(hipMemcpyAsync(out_tokens + (size_t)s * n_steps, b->ctxs[s]->dout, (size_t)n_steps * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(b->h_io + 2 * LNB_BATCH_MAX, b->derr, 4, hipMemcpyDeviceToHost, st));
@@ -2651,6 +2683,7 @@ extern "C" int lnb_batch_check_error(lnb_batch* b) {
 // single-sequence prefill ticks left there).
 extern "C" int lnb_batch_set_state(lnb_batch* b, const int32_t* tokens, const int32_t* start_pos) {
     if (!b || !start_pos) return fail("null argument");
+    if (b->sp_src) return fail("the batch has a shared prefix (lnb_batch_set_shared_prefix): pipeline ticks do not run the shared attention form; clear it first");
     HIPCHK(hipSetDevice(b->m->device));
     HIPCHK(hipMemsetAsync(b->derr, 0, 4, b->stream));        // a fresh run: forget what an earlier one latched
     const bool one_stage = b->m->first() && b->m->last();
@@ -2687,6 +2720,7 @@ extern "C" int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int it
     HIPCHK(hipSetDevice(m->device));
     if (iters <= 0 || which < 0 || which > K_LAYER) return fail("bad arguments");
     if (which == K_HEAD && !m->last()) return fail("this stage does not own output.weight");
+    if (b->sp_src && pos < b->sp_n) return fail("pos %d lies below the batch's shared prefix (n_pos %d)", pos, b->sp_n);
     for (int s = 0; s < b->n; s++) { if (check_call(b->ctxs[s], 1, pos)) return -1; b->h_io[s] = 0; b->h_io[LNB_BATCH_MAX + s] = pos; b->ctxs[s]->dev_pos = -1; }
     if (batch_select_form_at(b, b->h_io + LNB_BATCH_MAX)) return -1;
     hipStream_t st = b->stream;
@@ -2704,7 +2738,7 @@ extern "C" int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int it
     HIPCHK(hipEventRecord(b->ev0, st));
     for (int i = 0; i < iters; i++) if (run(i + 3)) return -1;
     HIPCHK(hipEventRecord(b->ev1, st));
-    b->last_form = b->attn_long ? 1 : 0;
+    b->last_form = batch_ran_form(b);
     HIPCHK(hipStreamSynchronize(st));
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
     *avg_ms_out = ms / (float)iters;
@@ -2913,6 +2947,45 @@ extern "C" int lnb_batch_set_attention(lnb_batch* b, int long_threshold, int for
         b->graphs.drop(GF_LONG);
         b->force_zseq = force_zseq;
     }
+    return 0;
+}
+// lnb_batch_set_shared_prefix (include/lnb.h).  The form bakes the source's cache pointers and n_pos into its launches: setting or clearing drops the
+// shared form's graphs; the scratch is allocated here, outside any capture.
+extern "C" int lnb_batch_set_shared_prefix(lnb_batch* b, lnb_ctx* src, int n_pos) {
+    if (n_pos < 0) return fail("n_pos must not be negative (got %d)", n_pos);
+    if (!b) return fail("null argument: b");
+    const bool clear = !src || n_pos == 0;
+    lnb_model* m = b->m;
+    if (!clear) {
+        if (src->m != m) return fail("src belongs to another model handle than the batch's members (the model, the device and the stage range must be theirs)");
+        if (n_pos > src->seq_len) return fail("n_pos %d is beyond src's capacity of %d positions", n_pos, src->seq_len);
+        for (int s = 0; s < b->n; s++)
+            if (n_pos >= b->ctxs[s]->seq_len) return fail("n_pos %d is at or beyond the capacity of member %d (%d positions): its own rows start at n_pos", n_pos, s, b->ctxs[s]->seq_len);
+        if (src->pending) return fail("src: a lnb_forward_stage_begin has not been ended");
+        for (int s = 0; s < b->n; s++) if (b->ctxs[s]->mode != LNB_MODE_EXACT) return fail("member %d is in the tolerance mode: the shared prefix is exact-order only", s);
+        if (m->head_dim != 128 && m->head_dim != 64) return fail("the shared-prefix attention has forms for head_dim 128 and 64 (this model: %d)", m->head_dim);
+        if (b->col_st || b->zseq) return fail("b is a pass batch of the library's own, not a caller's batch");
+    }
+    for (int s = 0; s < b->n; s++) if (b->ctxs[s]->pending) return fail("member %d: a lnb_forward_stage_begin has not been ended", s);
+    HIPCHK(hipSetDevice(m->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    Dev<uint64_t> idx; Dev<double> z;
+    if (!clear) {
+        const int G = m->a.n_heads / m->a.n_kv_heads;
+        const size_t ib = lnb_shared_idx_bytes(b->n, G, m->a.n_kv_heads, b->maxT), zb = lnb_shared_z_bytes(b->n, G, m->a.n_kv_heads, b->maxT);
+        hipError_t e = dev_alloc(idx, ib);
+        if (e == hipSuccess) e = dev_alloc(z, zb);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("the shared-prefix attention needs %.1f MB of scratch (%d sequences, %d KV heads, %d positions): %s", (double)(ib + zb) / 1e6, b->n, m->a.n_kv_heads, b->maxT, hipGetErrorString(e));
+        }
+        HIPCHK(hipStreamSynchronize(src->stream));           // whatever src's own stream still writes to its rows comes first
+    }
+    b->graphs.drop(GF_SHARED);
+    if (b->sp_src) b->sp_src->prefix_users--;
+    b->sp_idx = std::move(idx); b->sp_z = std::move(z);
+    b->sp_src = clear ? nullptr : src; b->sp_n = clear ? 0 : n_pos;
+    if (b->sp_src) b->sp_src->prefix_users++;
     return 0;
 }
 extern "C" int lnb_batch_attention_form(const lnb_batch* b, int* out) {
@@ -3692,6 +3765,7 @@ extern "C" int lnb_pipeline_tick_batch(lnb_pipe* p, lnb_batch* run, lnb_batch* s
     if (token_slot_out) *token_slot_out = -1;
     if (run) {
         if (run->top_k > 0) return fail("the batch's contexts record token probabilities, which pipeline ticks do not support (lnb_ctx_set_token_probs(ctx, 0))");
+        if (run->sp_src) return fail("the batch has a shared prefix (lnb_batch_set_shared_prefix): pipeline ticks do not run the shared attention form; clear it first");
         hipStream_t st = run->stream;
         if (run->link.await(st, "batch")) return -1;
         const bool ring_in = first && p->world > 1;

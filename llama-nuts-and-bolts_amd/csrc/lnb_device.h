@@ -178,6 +178,21 @@ struct AttnRowsParams {
                                 // (a verify pass: its columns alias one context, column 0 carries the context's own state) or a.st->pos -- so a captured graph serves every position
     int pos_off;                // ... + pos_off = the position of this launch's first row
 };
+// shared-prefix attention of a batched step (lnb_batch_set_shared_prefix; attn_shared_scores_kernel + attn_shared_pv_kernel, lnb_shared_prefix.h): positions
+// [0, n_pos) of every member are read from ONE source context's caches.  a carries what the batched long pair takes (q, out / out_xt, btab, bkv, S, H, KVH, hd,
+// exp_tab, force_zseq, zseq_count) with seq_len = the largest member's cache length and z_part [KVH][n_tiles * 16][ceil(seq_len / 256)].
+struct AttnSharedParams {
+    AttnParams a;
+    const uint16_t* src_k; const uint16_t* src_v;      // the source's caches of this layer
+    int src_len;                // the source's cache length (its K stride)
+    int n_pos;                  // shared positions
+    int n_tiles;                // row tiles of 16 per KV head: lnb_shared_tiles(S, H / KVH)
+    int njt;                    // 16-position tiles per strip: ceil(seq_len / 16)
+    uint64_t* idx;              // [KVH][n_tiles][njt][64 lanes] x 8 bytes: the sixteen-bit exp-table indices of the scores launch, in the PV launch's operand order
+};
+LNB_HD int lnb_shared_tiles(int n, int G) { return (n * G + 15) / 16; }
+LNB_HD size_t lnb_shared_idx_bytes(int n, int G, int KVH, int max_len) { return (size_t)KVH * lnb_shared_tiles(n, G) * (size_t)((max_len + 15) / 16) * 512; }
+LNB_HD size_t lnb_shared_z_bytes(int n, int G, int KVH, int max_len) { return (size_t)KVH * lnb_shared_tiles(n, G) * 16 * (size_t)((max_len + 255) / 256) * 8; }
 
 // ---- batched exact decode: up to 16 independent sequences per pass over the weights (lnb_batch_kernels.h) --------------------------
 // v_mfma_f32_16x16x4_f32 IS the reference's k-ordered chain (NOTES.md 5.6); its 16 batch columns carry 16 SEQUENCES' decode tokens,

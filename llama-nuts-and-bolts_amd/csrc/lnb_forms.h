@@ -56,6 +56,9 @@
     X(ATTN_BATCH_DENSE, "attn_batch.dense", "attn_exact_kernel<128, DENSE>: head_dim 128 and more than 256 (head, sequence) workgroups, dispatched tile-major") \
     X(ATTN_BATCH_DENSE_HM, "attn_batch.dense_headmajor", "the same kernel dispatched head-major (LNB_ATTN_BATCH_HEADMAJOR=1)") \
     X(ATTN_BATCH_GQA, "attn_batch.gqa", "attn_gqa_kernel<128, 4>: one workgroup per (KV head, sequence) for four query heads per KV head") \
+    /* shared-prefix attention of a batched step (lnbk_attn_shared: lnb_batch_set_shared_prefix) */ \
+    X(ATTN_BATCH_SHARED_SCORES, "attn_batch.shared_scores", "attn_shared_scores_kernel<HD>: 16 (member, head) rows per matrix-core tile against the source's K, sixteen-bit exp indices out") \
+    X(ATTN_BATCH_SHARED_PV, "attn_batch.shared_pv", "attn_shared_pv_kernel<HD>: one wave per (row tile, 32 output dims), the source's V read once per 16 rows") \
     /* prefix sharing (lnb_ctx_fork) */ \
     X(KV_FORK_PLAIN, "kv_fork.plain", "kv_fork_kernel<false>, one destination group") \
     X(KV_FORK_NT, "kv_fork.nt", "kv_fork_kernel<true>: non-temporal loads and stores (LNB_FORK_NT)") \

@@ -5752,6 +5752,24 @@ extern "C" hipError_t lnbk_kv_fork(const KvForkTab* tab, int nt, int split, hipS
     return hipGetLastError();
 }
 
+// shared-prefix attention of a batched step (lnb_shared_prefix.h): scores, then PV.  The grids cover the largest member capacity and every row tile: a captured
+// graph serves every position.  head_dim 128 / 64 (the matrix-core forms have none for 32); everything the kernels index is checked here.
+#include "lnb_shared_prefix.h"
+extern "C" hipError_t lnbk_attn_shared(const AttnSharedParams* sp, hipStream_t st) {
+    if (!sp) return hipErrorInvalidValue;
+    const AttnParams* p = &sp->a;
+    if (!p->btab || !p->bkv || !p->q || !p->exp_tab || !p->z_part || !sp->idx || !sp->src_k || !sp->src_v || (!p->out && !p->out_xt)) return hipErrorInvalidValue;
+    if (p->S < 1 || p->S > LNB_BATCH_MAX || p->KVH < 1 || p->H % p->KVH || p->seq_len < 1 || p->seq_len > LNB_SEQ_MAX) return hipErrorInvalidValue;
+    if (sp->n_pos < 1 || sp->n_pos > sp->src_len || sp->n_pos >= p->seq_len || sp->n_tiles != lnb_shared_tiles(p->S, p->H / p->KVH) || sp->njt != (p->seq_len + 15) / 16) return hipErrorInvalidValue;
+    return with_hd<64>(p, [&](auto HD) {
+        form_ran(Form::ATTN_BATCH_SHARED_SCORES);
+        hipLaunchKernelGGL(attn_shared_scores_kernel<HD>, dim3((p->seq_len + ASP_NT - 1) / ASP_NT, sp->n_tiles, p->KVH), dim3(ASP_NT), 0, st, *sp);
+        form_ran(Form::ATTN_BATCH_SHARED_PV);
+        hipLaunchKernelGGL(attn_shared_pv_kernel<HD>, dim3(sp->n_tiles, HD / 32, p->KVH), dim3(64), 0, st, *sp);
+        return hipGetLastError();
+    });
+}
+
 // lnb_forward_append_many: per pass, the columns' tables from the call's row and member tables, and the argmax of the members' last rows (lnb_append_many.h)
 #include "lnb_append_many.h"
 extern "C" hipError_t lnbk_append_many_setup(const AmPass* p, hipStream_t st) {

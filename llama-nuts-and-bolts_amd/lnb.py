@@ -70,7 +70,7 @@ EXPORTS = [
     "lnb_decode_sample_rules_until", "lnb_batch_decode_sample_rules_until", "lnb_op_sample_rules", "lnb_profile_sample_rules",
     "lnb_forward_append", "lnb_forward_score_append",
     "lnb_ctx_set_draft", "lnb_decode_speculative_until", "lnb_op_ngram_draft",
-    "lnb_batch_set_attention", "lnb_ctx_set_batched_attention", "lnb_batch_attention_form", "lnb_ctx_verify_attention_form",
+    "lnb_batch_set_attention", "lnb_ctx_set_batched_attention", "lnb_batch_attention_form", "lnb_ctx_verify_attention_form", "lnb_batch_set_shared_prefix",
     "lnb_ctx_create_long", "lnb_ctx_max_rows",
     "lnb_ctx_set_rows_attention", "lnb_ctx_append_attention_form",
     "lnb_ctx_fork", "lnb_ctx_prefix_bytes", "lnb_ctx_save_prefix", "lnb_ctx_load_prefix",
@@ -269,6 +269,7 @@ def lib():
     L.lnb_batch_set_attention.argtypes = [vp, C.c_int, C.c_int]
     L.lnb_ctx_set_batched_attention.argtypes = [vp, C.c_int, C.c_int]
     L.lnb_batch_attention_form.argtypes = [vp, C.POINTER(C.c_int)]
+    L.lnb_batch_set_shared_prefix.argtypes = [vp, vp, C.c_int]
     L.lnb_ctx_verify_attention_form.argtypes = [vp, C.POINTER(C.c_int)]
     L.lnb_ctx_set_rows_attention.argtypes = [vp, C.c_int, C.c_int]
     L.lnb_ctx_append_attention_form.argtypes = [vp, C.POINTER(C.c_int)]
@@ -1091,8 +1092,15 @@ class Batch:
         _chk(self.L.lnb_batch_set_attention(self.h, int(long_threshold), int(force_zseq)))
         return self
 
+    def set_shared_prefix(self, src, n_pos):
+        """every step reads positions [0, n_pos) of every member from the context src (lnb_batch_set_shared_prefix: same bits as members that hold src's
+        rows; the members' own rows below n_pos are not read); src None or n_pos 0 clears"""
+        _chk(self.L.lnb_batch_set_shared_prefix(self.h, None if src is None else src.h, int(n_pos)))
+        self._prefix_src = src                               # (kept alive: the batch's launches read its caches)
+        return self
+
     def attention_form(self):
-        """0: the last call of this batch ran the one-workgroup attention kernels, 1: the long-context pair"""
+        """0: the last call of this batch ran the one-workgroup attention kernels, 1: the long-context pair, 2: the shared-prefix pair (set_shared_prefix)"""
         n = C.c_int(0)
         _chk(self.L.lnb_batch_attention_form(self.h, C.byref(n)))
         return n.value
