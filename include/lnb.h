@@ -701,6 +701,36 @@ int lnb_ctx_set_batched_attention(lnb_ctx* c, int long_threshold, int force_zseq
  * with tiles = ceil(n * (n_heads / n_kv_heads) / 16) and L = the largest member capacity,
  * n_kv_heads * tiles * (ceil(L / 16) * 512 + 16 * ceil(L / 256) * 8) bytes (36.2 MB for 128 members of 4352 positions at 32 / 8 heads). */
 int lnb_batch_set_shared_prefix(lnb_batch* b, lnb_ctx* src, int n_pos);
+/* The same for the ragged passes of a model handle: while set, EVERY pass of lnb_forward_append_many, lnb_decode_speculative_many,
+ * lnb_decode_speculative_sample_many and lnb_decode_speculative_sample_rules_many on m reads positions [0, n_pos) of every column from src's caches,
+ * in every layer, once per 16 (column, head) rows, whatever the members' capacities (the long-context pair is not used).  A member's own rows below
+ * n_pos are never read (it needs no lnb_ctx_fork); its rows from n_pos on are read and written as before.  src may be a member; capacities may differ.
+ * The contract of each call is unchanged: every member's KV rows, logits, argmax, tokens and finished flag are the bits of the same call on members
+ * that hold src's rows, hence of the member's own single-context run.  Columns of ONE member also share that member's own rows: a tile of 16 rows that
+ * all point at one member cache takes the whole 16-position tiles of [n_pos, T) on the matrix cores as well (T: the tile's smallest position + 1).  The
+ * one arithmetic difference is the one stated above: in the matrix-core segments -- below n_pos & ~15, and in such a tile's own whole tiles -- a product
+ * p * v is fused into its add, which shows only when a single product is not a normal f32.
+ * flags bit 0: every row walks the serial sum (counted per (row, head) in lnb_model_many_zseq_count); bit 1: no tile takes the matrix-core segment over
+ * a member's own rows (experiment switch, same bits).  src == NULL or n_pos == 0 clears.  Setting or clearing waits for the pass object's stream.
+ * Refused, with lnb_last_error naming the argument and nothing changed: n_pos < 0; n_pos beyond src's capacity; src of another model handle; src with a
+ * lnb_forward_stage_begin pending; head_dim other than 128 / 64; unknown flag bits.  While it is set, one of those calls refuses -- before any cache is
+ * written -- a live member with start_pos[s] < n_pos and a live member of capacity <= n_pos (a skipped member's negative start_pos is exempt);
+ * lnb_ctx_destroy and lnb_ctx_reset of src are refused (src's user count changes under the model handle's pass mutex only, as a batch's does under
+ * its own calls: set, clear and destroy from one thread at a time); lnb_model_destroy clears it.  Scratch: the formula of lnb_batch_set_shared_prefix with n = the
+ * call's widest pass and L = its largest member capacity, allocated or grown by the call that first needs it (a failure carries the size).
+ * When to use it (profiles/many_shared_prefix.md, 8B shape): for appends of many rows behind a long prefix -- 32 or 127 members x 8 rows are 14 % faster
+ * behind 1024 positions and 27 % faster behind 4096 than the cleared form on forked members, and a second turn of 16 rows per member behind 4096 + 512 own
+ * positions takes 32.6 ms against 43.2 (61.4 with flags bit 1: the gain there IS the matrix-core segment over the member's own rows).  Not for narrow
+ * speculative passes: 8 requests at budget 32 behind 4096 positions are 17 % SLOWER than cleared (264 against 227 ms for 64 steps); the cause was not
+ * measured (supposed: a pass of at most 32 columns gives the two launches too few waves).  There the form saves the fork, not time.
+ * lnb_model_many_shared_info: of the last such call on m, the passes that ran the ragged form and the (row tile, KV head, layer) launches whose tile took
+ * the matrix-core segment over a member's own rows.  lnb_model_many_zseq_count: rows of the pass object's launches that walked the serial sum since
+ * the handle's first such call (a 32-bit device counter: it wraps like an int). */
+int lnb_model_set_many_shared_prefix(lnb_model* m, lnb_ctx* src, int n_pos, int flags);
+int lnb_model_many_shared_info(const lnb_model* m, int* shared_passes, int64_t* own_mfma_tiles);
+int lnb_model_many_zseq_count(const lnb_model* m, int64_t* out);
+/* the scratch bytes of that form for passes of up to `columns` columns and a largest member capacity of max_len positions (-1: a bad argument) */
+int64_t lnb_many_shared_scratch_bytes(int columns, int n_heads, int n_kv_heads, int max_len);
 /* 0: the last batched call / verify pass ran the one-workgroup kernels, 1: the long-context pair (a test and a bench print it);
  * lnb_batch_attention_form also 2: the shared-prefix pair (lnb_batch_set_shared_prefix);
  * lnb_ctx_verify_attention_form also 2: the multi-row long-context pair (lnb_ctx_set_rows_attention, flags bit 1) */

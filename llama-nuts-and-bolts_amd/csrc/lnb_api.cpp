@@ -46,6 +46,7 @@ hipError_t lnbk_gemv(const GemvParams* p, int rw, int nch, int epi, int norm, hi
 hipError_t lnbk_attn(const AttnParams* p, hipStream_t st);
 hipError_t lnbk_attn_rows(const AttnParams* p, int pos0, hipStream_t st);
 hipError_t lnbk_attn_shared(const AttnSharedParams* sp, hipStream_t st);
+hipError_t lnbk_attn_ragged(const AttnRaggedParams* rp, hipStream_t st);
 hipError_t lnbk_kv_scan_nonfinite(const uint16_t* ck, const uint16_t* cv, int seq_len, int kv_dim, int hd, const StepState* st, int pos0, int rows, int* word, hipStream_t s);
 hipError_t lnbk_nonfinite_or(int* dst, const int* src, hipStream_t s);
 hipError_t lnbk_attn_plain(const AttnParams* p, const int* word, hipStream_t st);
@@ -218,6 +219,12 @@ struct lnb_model {
     // the LM head's 13-bit copy (lnb_model_finalize, LNB_HEAD_PACKED; 128-row two-chain blocks: lnb_wpack.h), as LayerW's p_* fields are for gate|up
     Dev<void> p_out; unsigned p_out_base = 0; bool p_out_ok = false; int p_out_status = -1; int64_t wpack_head_bytes = 0;
     std::mutex am_mu; struct AppendMany* am = nullptr;     // lnb_forward_append_many: the call's buffers and tables, created on first use; the mutex is held for a whole call
+    // lnb_model_set_many_shared_prefix (under am_mu): the passes of the append-many and speculative-many calls read positions [0, msp_n) of every column from
+    // msp_src's caches (the ragged form, lnb_ragged_prefix.h).  msp_idx / msp_z: its scratch, grown by the call that first needs more (many_shared_begin);
+    // msp_tiles: the device counter of tiles that took the matrix-core segment over a member's own rows; msp_passes: passes of the last call that ran the form
+    lnb_ctx* msp_src = nullptr; int msp_n = 0, msp_flags = 0, msp_passes = 0;
+    Dev<uint64_t> msp_idx; Dev<double> msp_z; size_t msp_idx_bytes = 0, msp_z_bytes = 0;
+    Dev<unsigned long long> msp_tiles;
     bool first() const { return part_begin == 0; }
     bool last() const { return part_end == 3 * a.n_layers; }
     bool has_part(int l, int q) const { return 3 * l + q >= part_begin && 3 * l + q < part_end; }
@@ -588,6 +595,7 @@ extern "C" int lnb_model_destroy(lnb_model* m) {
     if (!m) return 0;
     hipSetDevice(m->device);
     append_many_free(m);
+    if (m->msp_src) { m->msp_src->prefix_users--; m->msp_src = nullptr; }      // (lnb_model_set_many_shared_prefix: the handle's end clears it)
     delete m;
     return 0;
 }
@@ -966,7 +974,7 @@ extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
     // a batch bakes its members' device pointers (state words, token words, caches) into its tables and captured graphs: freeing a member
     // under it would make the next lnb_batch_decode / lnb_pipeline_tick_batch read and write freed memory.  Destroy the batch first.
     if (c->batch_users > 0) return fail("context is a member of %d live batch(es): lnb_batch_destroy them first", c->batch_users);
-    if (c->prefix_users > 0) return fail("context is the shared prefix of %d live batch(es): clear it (lnb_batch_set_shared_prefix(b, NULL, 0)) or destroy them first", c->prefix_users);
+    if (c->prefix_users > 0) return fail("context is the shared prefix of %d live batch(es) or model handle(s): clear it (lnb_batch_set_shared_prefix(b, NULL, 0), lnb_model_set_many_shared_prefix(m, NULL, 0, 0)) or destroy them first", c->prefix_users);
     hipSetDevice(c->m->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     for (lnb_batch* b : c->sp_b) if (b) lnb_batch_destroy(b);      // the verify batches: their tables hold this context's pointers
@@ -976,7 +984,7 @@ extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
 
 extern "C" int lnb_ctx_reset(lnb_ctx* c) {
     if (!c) return fail("null argument");
-    if (c->prefix_users > 0) return fail("context is the shared prefix of %d live batch(es): clear it (lnb_batch_set_shared_prefix(b, NULL, 0)) or destroy them first", c->prefix_users);
+    if (c->prefix_users > 0) return fail("context is the shared prefix of %d live batch(es) or model handle(s): clear it (lnb_batch_set_shared_prefix(b, NULL, 0), lnb_model_set_many_shared_prefix(m, NULL, 0, 0)) or destroy them first", c->prefix_users);
     HIPCHK(hipSetDevice(c->m->device));
     const size_t kvn = (size_t)c->seq_len * c->m->kv_dim;
     for (size_t l = 0; l < c->ck.size(); l++) if (c->ck[l]) { HIPCHK(hipMemsetAsync(c->ck[l], 0, kvn * 2, c->stream)); HIPCHK(hipMemsetAsync(c->cv[l], 0, kvn * 2, c->stream)); }
@@ -2199,6 +2207,7 @@ struct lnb_batch {
     // speculative verify batch (lnb_decode_speculative_until): every column is ONE context (ctxs[s] = it, the same caches); columns s >= 1 take
     // their state and token word from col_st + s / col_tok + s instead of the context's own (the context's sp_st / sp_tok: it owns them)
     StepState* col_st = nullptr; int32_t* col_tok = nullptr;
+    bool many_shared = false;              // ... and its passes read a shared prefix from the model handle's msp_src (lnb_model_set_many_shared_prefix): the ragged form
     int* zseq = nullptr;                   // lnb_forward_append_many's pass batch has no member contexts: the serial-sum counter the attention launches get instead of ctxs[0]'s (AppendMany::zseq owns it)
 };
 // What every batched step asks of the model stage it runs on (who: the caller, as its message names it).  A whole-model handle is a stage of whole blocks.
@@ -2508,6 +2517,14 @@ static int enqueue_batch_kernel(lnb_batch* b, int l, int which) {
             sp.n_tiles = lnb_shared_tiles(b->n, a.n_heads / a.n_kv_heads); sp.njt = (b->maxT + 15) / 16;
             HIPCHK(lnbk_attn_shared(&sp, b->stream)); return 0;
         }
+        if (b->many_shared) {                                // a ragged pass under lnb_model_set_many_shared_prefix: the ragged form whatever the members' capacities
+            AttnRaggedParams rp{}; AttnSharedParams& sp = rp.s; sp.a = ap;
+            sp.a.seq_len = b->maxT; sp.a.force_zseq = m->msp_flags & 1; sp.a.z_part = m->msp_z; sp.idx = m->msp_idx;
+            sp.src_k = m->msp_src->ck[l - m->layer_begin]; sp.src_v = m->msp_src->cv[l - m->layer_begin]; sp.src_len = m->msp_src->seq_len; sp.n_pos = m->msp_n;
+            sp.n_tiles = lnb_shared_tiles(b->n, a.n_heads / a.n_kv_heads); sp.njt = (b->maxT + 15) / 16;
+            rp.no_own = (m->msp_flags >> 1) & 1; rp.own_tiles = m->msp_tiles;
+            HIPCHK(lnbk_attn_ragged(&rp, b->stream)); return 0;
+        }
         HIPCHK(batch_attn_launch(b, ap, b->stream)); return 0; }
     case K_WO: {
         BatchProd d{BP_WO, nullptr, b->att_xt, &L.wo, L.m_wo, m->q_dim, dim, 1, EPI_RESID}; d.out = b->h; d.res = b->x;
@@ -2807,6 +2824,36 @@ static int append_many_alloc(lnb_model* m) {
     }
     return 0;
 }
+// What a call on the pass object does first while lnb_model_set_many_shared_prefix is set (under am_mu, before any cache is written): its live members
+// (start_pos < 0: skipped) start at or beyond the prefix and reach beyond it, and the ragged form's scratch holds the call's widest pass of `width`
+// columns and its largest member capacity maxT.  Every call leaves the pass stream drained: nothing reads the scratch that is replaced.
+static int many_shared_begin(lnb_model* m, lnb_batch* b, const char* name, lnb_ctx* const* ctxs, int n, const int32_t* start_pos, int width, int maxT) {
+    m->msp_passes = 0; b->many_shared = false;
+    if (!m->msp_src) return 0;
+    for (int s = 0; s < n; s++) {
+        if (start_pos[s] < 0) continue;
+        if (ctxs[s]->seq_len <= m->msp_n) return fail("%s: member %d: its capacity of %d positions does not reach beyond the shared prefix (n_pos %d)", name, s, ctxs[s]->seq_len, m->msp_n);
+        if (start_pos[s] < m->msp_n) return fail("%s: member %d: start_pos %d lies below the shared prefix (n_pos %d): a live member starts at or beyond it", name, s, start_pos[s], m->msp_n);
+    }
+    if (m->msp_src->pending) return fail("%s: the shared prefix's context (src): a lnb_forward_stage_begin has not been ended", name);
+    const int G = m->a.n_heads / m->a.n_kv_heads, KVH = m->a.n_kv_heads;
+    const size_t ib = std::max(lnb_shared_idx_bytes(width, G, KVH, maxT), m->msp_idx_bytes), zb = std::max(lnb_shared_z_bytes(width, G, KVH, maxT), m->msp_z_bytes);
+    if (ib > m->msp_idx_bytes || zb > m->msp_z_bytes || !m->msp_tiles) {
+        m->msp_idx.reset(); m->msp_z.reset(); m->msp_idx_bytes = m->msp_z_bytes = 0;
+        hipError_t e = dev_alloc(m->msp_idx, ib);
+        if (e == hipSuccess) e = dev_alloc(m->msp_z, zb);
+        if (e == hipSuccess && !m->msp_tiles) e = dev_alloc(m->msp_tiles, 8);
+        if (e != hipSuccess) {
+            m->msp_idx.reset(); m->msp_z.reset(); (void)hipGetLastError();
+            return fail("%s: the shared-prefix attention of a ragged pass needs %.1f MB of scratch (%d columns, %d KV heads, %d positions): %s", name, (double)(ib + zb) / 1e6, width, KVH, maxT, hipGetErrorString(e));
+        }
+        m->msp_idx_bytes = ib; m->msp_z_bytes = zb;
+    }
+    HIPCHK(hipStreamSynchronize(m->msp_src->stream));       // whatever src's own stream still writes to its rows comes first
+    HIPCHK(hipMemsetAsync(m->msp_tiles, 0, 8, b->stream));
+    b->many_shared = true;
+    return 0;
+}
 extern "C" int lnb_model_append_many_info(const lnb_model* m, int* passes, int* max_columns, int* long_passes) {
     if (!m) return fail("lnb_model_append_many_info: null argument (model)");
     const AppendMany* am = m->am;
@@ -2863,8 +2910,11 @@ extern "C" int lnb_forward_append_many(lnb_ctx* const* ctxs, int n, const int32_
       } }
     RowPackWalk walk; RowSeg segs[ROWPACK_MAX_W]; int width = 0; int64_t row0 = 0;
     int need_n = 0, need_T = 0;                              // the long-context pair's scratch over every pass that runs it
+    int wide_n = 0, wide_T = 0;                              // the widest pass, the largest capacity: the ragged shared-prefix form's scratch
+    for (int s = 0; s < n; s++) wide_T = std::max(wide_T, ctxs[s]->seq_len);
     if (rowpack_begin(&walk, n, n_rows, W)) return fail("%s: internal error: the rows could not be packed", name);
     while (int ns = rowpack_next(&walk, segs, &width, &row0)) {
+        wide_n = std::max(wide_n, width);
         bool lng = false; int maxT = 0;
         for (int g = 0; g < ns; g++) { const lnb_ctx* c = ctxs[segs[g].member]; maxT = std::max(maxT, c->seq_len); lng = lng || c->seq_len > c->attn_short_cap; }
         if (lng) { need_n = std::max(need_n, width); need_T = std::max(need_T, maxT); }
@@ -2874,6 +2924,8 @@ extern "C" int lnb_forward_append_many(lnb_ctx* const* ctxs, int n, const int32_
     HIPCHK(lnbk_batch_prepare());
     if (append_many_alloc(m)) return -1;
     AppendMany* am = m->am; lnb_batch* b = am->b; hipStream_t st = b->stream;
+    if (many_shared_begin(m, b, name, ctxs, n, start_pos, wide_n, wide_T)) return -1;
+    if (b->many_shared) need_n = need_T = 0;                 // (the ragged form serves every capacity: the long-context pair does not run)
     if (need_n > am->scratch_n || need_T > am->scratch_T) {
         const int sn = std::max(need_n, am->scratch_n), sT = std::max(need_T, am->scratch_T);
         am->scratch_n = am->scratch_T = 0;
@@ -2906,6 +2958,7 @@ extern "C" int lnb_forward_append_many(lnb_ctx* const* ctxs, int n, const int32_
     while (int ns = rowpack_next(&walk, segs, &width, &row0)) {
         bool lng = false; int maxT = 0;
         for (int g = 0; g < ns; g++) { const lnb_ctx* c = ctxs[segs[g].member]; maxT = std::max(maxT, c->seq_len); lng = lng || c->seq_len > c->attn_short_cap; }
+        lng = lng && !b->many_shared;
         b->n = width; b->maxT = maxT; b->lds_T = std::min(maxT, ctxs[0]->attn_short_cap); b->must_long = lng; b->attn_long = lng;
         const int layout = batch_plan_layout(batch_plan_of(b));      // what the activation buffers of this pass hold: B-operand columns, column groups or rows
         if (am->last_layout >= 0 && (layout != am->last_layout || width < am->last_width) && batch_bufs_zero(b, LNB_BATCH_MAX)) return -1;       // dead columns are zero again
@@ -2921,12 +2974,66 @@ extern "C" int lnb_forward_append_many(lnb_ctx* const* ctxs, int n, const int32_
             if (pass > 0 && fetch((pass - 1) & 1, prev_r0, prev_w)) return -1;        // the pass before, while this one runs
         }
         prev_w = width; prev_r0 = row0; pass++;
-        am->passes = pass; am->max_columns = std::max(am->max_columns, width); am->long_passes += lng ? 1 : 0;
+        am->passes = pass; am->max_columns = std::max(am->max_columns, width); am->long_passes += lng ? 1 : 0; m->msp_passes += b->many_shared ? 1 : 0;
     }
     if (logits_out && fetch((pass - 1) & 1, prev_r0, prev_w)) return -1;
     HIPCHK(hipMemcpyAsync(am->h_arg, am->d_arg, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (argmax_out) memcpy(argmax_out, am->h_arg, (size_t)n * 4);
+    return 0;
+}
+
+// lnb_model_set_many_shared_prefix (include/lnb.h).  The passes are eager launches: nothing is baked in, the next call reads the model handle's fields under
+// the mutex every such call holds.  The scratch is the first call's business (many_shared_begin): only a call knows its widest pass.
+extern "C" int lnb_model_set_many_shared_prefix(lnb_model* m, lnb_ctx* src, int n_pos, int flags) {
+    if (n_pos < 0) return fail("n_pos must not be negative (got %d)", n_pos);
+    if (flags & ~3) return fail("flags: unknown bits 0x%x (bit 0: every row walks the serial sum, bit 1: no matrix-core segment over a member's own rows)", flags & ~3);
+    if (!m) return fail("null argument: m");
+    const bool clear = !src || n_pos == 0;
+    if (!clear) {
+        if (src->m != m) return fail("src belongs to another model handle than m (the model, the device and the stage range must be m's)");
+        if (n_pos > src->seq_len) return fail("n_pos %d is beyond src's capacity of %d positions", n_pos, src->seq_len);
+        if (src->pending) return fail("src: a lnb_forward_stage_begin has not been ended");
+        if (m->head_dim != 128 && m->head_dim != 64) return fail("head_dim: the shared-prefix attention has forms for 128 and 64 (this model: %d)", m->head_dim);
+    }
+    std::lock_guard<std::mutex> lock(m->am_mu);
+    HIPCHK(hipSetDevice(m->device));
+    if (m->am && m->am->b && m->am->b->stream) HIPCHK(hipStreamSynchronize(m->am->b->stream));
+    if (!clear) HIPCHK(hipStreamSynchronize(src->stream));   // whatever src's own stream still writes to its rows comes first
+    if (m->msp_src) m->msp_src->prefix_users--;
+    m->msp_src = clear ? nullptr : src; m->msp_n = clear ? 0 : n_pos; m->msp_flags = clear ? 0 : flags;
+    if (m->msp_src) m->msp_src->prefix_users++;
+    if (clear) { m->msp_idx.reset(); m->msp_z.reset(); m->msp_idx_bytes = m->msp_z_bytes = 0; }
+    return 0;
+}
+extern "C" int lnb_model_many_shared_info(const lnb_model* cm, int* shared_passes, int64_t* own_mfma_tiles) {
+    if (!cm) return fail("lnb_model_many_shared_info: null argument (m)");
+    lnb_model* m = const_cast<lnb_model*>(cm);
+    std::lock_guard<std::mutex> lock(m->am_mu);
+    if (shared_passes) *shared_passes = m->msp_passes;
+    if (own_mfma_tiles) {                                    // (every call on the pass object ends with its stream drained)
+        unsigned long long v = 0;
+        if (m->msp_tiles && m->msp_passes > 0) { HIPCHK(hipSetDevice(m->device)); HIPCHK(hipMemcpy(&v, m->msp_tiles, 8, hipMemcpyDeviceToHost)); }
+        *own_mfma_tiles = (int64_t)v;
+    }
+    return 0;
+}
+extern "C" int64_t lnb_many_shared_scratch_bytes(int columns, int n_heads, int n_kv_heads, int max_len) {
+    if (columns < 1 || columns > LNB_BATCH_MAX || n_kv_heads < 1 || n_heads < n_kv_heads || n_heads % n_kv_heads || max_len < 1 || max_len > LNB_SEQ_MAX) {
+        fail("lnb_many_shared_scratch_bytes: columns 1..%d, n_heads a multiple of n_kv_heads, max_len 1..%d", LNB_BATCH_MAX, LNB_SEQ_MAX);
+        return -1;
+    }
+    return (int64_t)(lnb_shared_idx_bytes(columns, n_heads / n_kv_heads, n_kv_heads, max_len) + lnb_shared_z_bytes(columns, n_heads / n_kv_heads, n_kv_heads, max_len));
+}
+// rows of the pass object's attention launches that walked the serial f64 sum (the ragged and the long-context forms count there: the passes have no member
+// context to count in), since the model handle's first such call.  The device word is a 32-bit int and wraps like one.
+extern "C" int lnb_model_many_zseq_count(const lnb_model* cm, int64_t* out) {
+    if (!cm || !out) return fail("lnb_model_many_zseq_count: null argument (%s)", !cm ? "m" : "out");
+    lnb_model* m = const_cast<lnb_model*>(cm);
+    std::lock_guard<std::mutex> lock(m->am_mu);
+    int v = 0;
+    if (m->am && m->am->zseq) { HIPCHK(hipSetDevice(m->device)); HIPCHK(hipMemcpy(&v, m->am->zseq, 4, hipMemcpyDeviceToHost)); }
+    *out = v;
     return 0;
 }
 
@@ -3379,6 +3486,8 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
     AppendMany* am = m->am; lnb_batch* b = am->b; hipStream_t st = b->stream;
     if (spec_many_alloc(am)) return -1;
     SpecMany* sm = am->sm;
+    if (many_shared_begin(m, b, name, ctxs, n, start_pos, budget, std::max(need_T, 1))) return -1;
+    if (b->many_shared) any_long = false;                    // (the ragged form serves every capacity: the long-context pair does not run)
     if (any_long && (budget > am->scratch_n || need_T > am->scratch_T)) {
         const int sn = std::max(budget, am->scratch_n), sT = std::max(need_T, am->scratch_T);
         am->scratch_n = am->scratch_T = 0;
@@ -3443,7 +3552,7 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
         const int width = wd[0], any = wd[1], running = wd[2], maxT = wd[3];
         if (width < 0 || running < 0 || running > n || width < running || width > budget || (running > 0 && inf.passes >= max_steps)) return fail("%s: internal error: a pass of %d columns for %d running members", name, width, running);
         if (running == 0) break;
-        const bool lng = maxT > cap;
+        const bool lng = maxT > cap && !b->many_shared;
         b->n = width; b->maxT = maxT; b->lds_T = std::min(maxT, cap); b->must_long = lng; b->attn_long = lng;
         const int layout = batch_plan_layout(batch_plan_of(b));
         if (am->last_layout >= 0 && (layout != am->last_layout || width < am->last_width) && batch_bufs_zero(b, LNB_BATCH_MAX)) return -1;       // dead columns are zero again
@@ -3457,7 +3566,7 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
         HIPCHK(lnbk_spec_many_draft(&sp, st));
         HIPCHK(lnbk_spec_many_pack(&sp, st));
         HIPCHK(hipEventRecord(sm->ev, st));
-        inf.passes++; inf.verify_passes += any ? 1 : 0; inf.columns += width; inf.max_columns = std::max<int64_t>(inf.max_columns, width); inf.long_passes += lng ? 1 : 0;
+        inf.passes++; inf.verify_passes += any ? 1 : 0; inf.columns += width; inf.max_columns = std::max<int64_t>(inf.max_columns, width); inf.long_passes += lng ? 1 : 0; m->msp_passes += b->many_shared ? 1 : 0;
     }
     HIPCHK(hipEventRecord(sm->ev1, st));
     std::vector<StepState> hs(n); std::vector<SmStats> hst(n);

@@ -193,6 +193,13 @@ struct AttnSharedParams {
 LNB_HD int lnb_shared_tiles(int n, int G) { return (n * G + 15) / 16; }
 LNB_HD size_t lnb_shared_idx_bytes(int n, int G, int KVH, int max_len) { return (size_t)KVH * lnb_shared_tiles(n, G) * (size_t)((max_len + 15) / 16) * 512; }
 LNB_HD size_t lnb_shared_z_bytes(int n, int G, int KVH, int max_len) { return (size_t)KVH * lnb_shared_tiles(n, G) * 16 * (size_t)((max_len + 255) / 256) * 8; }
+// the same for a ragged pass (lnb_model_set_many_shared_prefix; attn_ragged_scores_kernel + attn_ragged_pv_kernel, lnb_ragged_prefix.h): s is the shared form's
+// block with S = the pass's columns; the scratch formulas are the two above
+struct AttnRaggedParams {
+    AttnSharedParams s;
+    int no_own;                 // 1: no tile takes the matrix-core segment over the member's own rows (flags bit 1)
+    unsigned long long* own_tiles;      // counts (tile, KV head) pairs of a launch that took it; may be nullptr
+};
 
 // ---- batched exact decode: up to 16 independent sequences per pass over the weights (lnb_batch_kernels.h) --------------------------
 // v_mfma_f32_16x16x4_f32 IS the reference's k-ordered chain (NOTES.md 5.6); its 16 batch columns carry 16 SEQUENCES' decode tokens,

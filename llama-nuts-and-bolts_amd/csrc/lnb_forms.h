@@ -59,6 +59,9 @@
     /* shared-prefix attention of a batched step (lnbk_attn_shared: lnb_batch_set_shared_prefix) */ \
     X(ATTN_BATCH_SHARED_SCORES, "attn_batch.shared_scores", "attn_shared_scores_kernel<HD>: 16 (member, head) rows per matrix-core tile against the source's K, sixteen-bit exp indices out") \
     X(ATTN_BATCH_SHARED_PV, "attn_batch.shared_pv", "attn_shared_pv_kernel<HD>: one wave per (row tile, 32 output dims), the source's V read once per 16 rows") \
+    /* shared-prefix attention of a ragged pass (lnbk_attn_ragged: lnb_model_set_many_shared_prefix) */ \
+    X(ATTN_MANY_RAGGED_SCORES, "attn_many.ragged_scores", "attn_ragged_scores_kernel<HD>: the shared scores form for columns that share a member -- a uniform tile also takes the member's own K on the matrix cores") \
+    X(ATTN_MANY_RAGGED_PV, "attn_many.ragged_pv", "attn_ragged_pv_kernel<HD>: one wave per (row tile, 32 output dims), source V and a uniform tile's own V read once per 16 rows, operands two tiles ahead in registers") \
     /* prefix sharing (lnb_ctx_fork) */ \
     X(KV_FORK_PLAIN, "kv_fork.plain", "kv_fork_kernel<false>, one destination group") \
     X(KV_FORK_NT, "kv_fork.nt", "kv_fork_kernel<true>: non-temporal loads and stores (LNB_FORK_NT)") \

@@ -5769,6 +5769,22 @@ extern "C" hipError_t lnbk_attn_shared(const AttnSharedParams* sp, hipStream_t s
         return hipGetLastError();
     });
 }
+// the same for a ragged pass (lnb_ragged_prefix.h): the columns of lnb_forward_append_many and of the speculative-many calls, several per member
+#include "lnb_ragged_prefix.h"
+extern "C" hipError_t lnbk_attn_ragged(const AttnRaggedParams* rp, hipStream_t st) {
+    if (!rp) return hipErrorInvalidValue;
+    const AttnSharedParams* sp = &rp->s; const AttnParams* p = &sp->a;
+    if (!p->btab || !p->bkv || !p->q || !p->exp_tab || !p->z_part || !sp->idx || !sp->src_k || !sp->src_v || (!p->out && !p->out_xt)) return hipErrorInvalidValue;
+    if (p->S < 1 || p->S > LNB_BATCH_MAX || p->KVH < 1 || p->H % p->KVH || p->seq_len < 1 || p->seq_len > LNB_SEQ_MAX) return hipErrorInvalidValue;
+    if (sp->n_pos < 1 || sp->n_pos > sp->src_len || sp->n_pos >= p->seq_len || sp->n_tiles != lnb_shared_tiles(p->S, p->H / p->KVH) || sp->njt != (p->seq_len + 15) / 16) return hipErrorInvalidValue;
+    return with_hd<64>(p, [&](auto HD) {
+        form_ran(Form::ATTN_MANY_RAGGED_SCORES);
+        hipLaunchKernelGGL(attn_ragged_scores_kernel<HD>, dim3((p->seq_len + ASP_NT - 1) / ASP_NT, sp->n_tiles, p->KVH), dim3(ASP_NT), 0, st, *rp);
+        form_ran(Form::ATTN_MANY_RAGGED_PV);
+        hipLaunchKernelGGL(attn_ragged_pv_kernel<HD>, dim3(sp->n_tiles, HD / 32, p->KVH), dim3(64), 0, st, *rp);
+        return hipGetLastError();
+    });
+}
 
 // lnb_forward_append_many: per pass, the columns' tables from the call's row and member tables, and the argmax of the members' last rows (lnb_append_many.h)
 #include "lnb_append_many.h"

@@ -75,6 +75,7 @@ EXPORTS = [
     "lnb_ctx_set_rows_attention", "lnb_ctx_append_attention_form",
     "lnb_ctx_fork", "lnb_ctx_prefix_bytes", "lnb_ctx_save_prefix", "lnb_ctx_load_prefix",
     "lnb_forward_append_many", "lnb_model_append_many_info",
+    "lnb_model_set_many_shared_prefix", "lnb_model_many_shared_info", "lnb_model_many_zseq_count", "lnb_many_shared_scratch_bytes",
     "lnb_decode_speculative_many",
     "lnb_decode_speculative_sample_until", "lnb_decode_speculative_sample_many", "lnb_op_spec_sample_accept",
     "lnb_decode_speculative_sample_rules_until", "lnb_decode_speculative_sample_rules_many", "lnb_op_spec_sample_rules_accept",
@@ -280,6 +281,11 @@ def lib():
     L.lnb_ctx_load_prefix.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int)]
     L.lnb_forward_append_many.argtypes = [C.POINTER(vp), C.c_int, vp, vp, vp, vp, vp]
     L.lnb_model_append_many_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.lnb_model_set_many_shared_prefix.argtypes = [vp, vp, C.c_int, C.c_int]
+    L.lnb_model_many_shared_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.lnb_model_many_zseq_count.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.lnb_many_shared_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.lnb_many_shared_scratch_bytes.restype = C.c_int64
     L.lnb_decode_speculative_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, vp, vp, vp,
                                               C.POINTER(SpecStats), C.POINTER(SpecManyInfo), f32p]
     L.lnb_pipeline_tick_batch.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int)]
@@ -641,6 +647,20 @@ class LlamaTransformer:
         p, w, g = C.c_int(0), C.c_int(0), C.c_int(0)
         _chk(self.L.lnb_model_append_many_info(self.h, C.byref(p), C.byref(w), C.byref(g)))
         return {"passes": p.value, "max_columns": w.value, "long_passes": g.value}
+
+    def set_many_shared_prefix(self, src, n_pos, flags=0):
+        """every pass of ForwardAppendMany / decode_speculative_many (and its sampling forms) on this transformer reads positions [0, n_pos) of every
+        column from the context src (lnb_model_set_many_shared_prefix: same bits as members that hold src's rows); flags bit 0: every row walks the
+        serial sum, bit 1: no matrix-core segment over a member's own rows; (None, 0) clears.  -> self"""
+        _chk(self.L.lnb_model_set_many_shared_prefix(self.h, None if src is None else src.h, int(n_pos), int(flags)))
+        return self
+
+    def many_shared_info(self):
+        """of the last such call: {shared_passes, own_mfma_tiles} (lnb_model_many_shared_info) and zseq, the rows that walked the serial sum so far"""
+        p, t, z = C.c_int(0), C.c_int64(0), C.c_int64(0)
+        _chk(self.L.lnb_model_many_shared_info(self.h, C.byref(p), C.byref(t)))
+        _chk(self.L.lnb_model_many_zseq_count(self.h, C.byref(z)))
+        return {"shared_passes": p.value, "own_mfma_tiles": t.value, "zseq": z.value}
 
     def close(self):
         if self.h:

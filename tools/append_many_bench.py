@@ -23,6 +23,9 @@ ap.add_argument("--extra", default="4x128", help="further cells, members x rows,
 ap.add_argument("--logits-cells", default="32x8,4x128", help="cells that are also measured with the logits copied to the host")
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--step-timeout", type=int, default=120, help="seconds one measured step (warm-up + repeats of one form of one cell) may take")
+ap.add_argument("--share-prefix", action="store_true", help="measure lnb_model_set_many_shared_prefix instead: every cell with the prefix shared and cleared "
+                "(with --own also shared under flags bit 1), alternating in this process; prints one JSON line per cell (profiles/many_shared_prefix.md)")
+ap.add_argument("--own", type=int, default=0, help="--share-prefix: positions of own text every member holds in front of the measured rows (start_pos = prefix + own)")
 ap.add_argument("--out", default="")
 ap.add_argument("--md", default="")
 ap.add_argument("--from-json", default="", help="write --md from the --out file of an earlier run instead of measuring")
@@ -33,7 +36,7 @@ prefixes = [int(s) for s in a.prefixes.split(",")]
 cells = [(n, r) for n in (int(s) for s in a.members.split(",")) for r in (int(s) for s in a.rows.split(","))] + pairs(a.extra)
 logit_cells = set(pairs(a.logits_cells))
 NMAX, RMAX, PMAX = max(max(n for n, _ in cells), 128), max(r for _, r in cells), max(prefixes)
-CAP = PMAX + RMAX + 64
+CAP = PMAX + a.own + RMAX + 64
 
 
 def limited(fn):
@@ -117,6 +120,51 @@ def measure():
     return res
 
 
+def measure_shared():
+    """per cell the one call with the prefix shared, cleared (the members hold the forked rows) and -- with own text -- shared without the matrix-core own
+    segment, one after the other inside every repeat; the first round is the warm-up"""
+    NS = max(n for n, _ in cells)
+    m = lnb.LlamaTransformer(device=0, **cfg).fill_synthetic(1234).finalize(rope_rows=max(2048, CAP)).enable_batch()
+    src = lnb.InferenceContext(m, CAP, max_rows=PMAX, long_context=True)
+    ctxs = [lnb.InferenceContext(m, CAP, max_rows=max(RMAX, 16), long_context=True) for _ in range(NS)]
+    toks = lnb.synth_tokens(99, PMAX, V)
+    user = [lnb.synth_tokens(1000 + s, a.own + RMAX, V) for s in range(NS)]
+    forms = [("shared", 0), ("cleared", None)] + ([("shared_no_own_mfma", 2)] if a.own else [])
+    for P in prefixes:
+        limited(lambda: src.Forward(toks[:P], 0, want_logits=False))
+        for c0 in range(0, NS, 32):
+            limited(lambda: src.ForkPrefix(ctxs[c0:c0 + 32], P))
+        own_done = 0
+        for n, r in cells:
+            members, lists, pos = ctxs[:n], [user[s][a.own:a.own + r] for s in range(n)], [P + a.own] * n
+            if a.own and n > own_done:                       # the members' own text behind the prefix, once
+                limited(lambda: lnb.ForwardAppendMany(ctxs[own_done:n], [user[s][:a.own] for s in range(own_done, n)], [P] * (n - own_done), want_logits=False))
+                own_done = n
+            ms, cell = {f: [] for f, _ in forms}, {"prefix": P, "own": a.own, "members": n, "rows": r}
+
+            def rounds():
+                for i in range(a.reps + 1):
+                    for f, flags in forms:
+                        m.set_many_shared_prefix(None if flags is None else src, P, flags or 0)
+                        t0 = time.perf_counter()
+                        lnb.ForwardAppendMany(members, lists, pos, want_logits=False)
+                        if i:
+                            ms[f].append((time.perf_counter() - t0) * 1e3)
+                        if f == "shared":
+                            cell["passes"], cell["own_mfma_tiles"] = m.append_many_info()["passes"], m.many_shared_info()["own_mfma_tiles"]
+                m.set_many_shared_prefix(None, 0)
+            limited(rounds)
+            for f, v in ms.items():
+                cell[f + "_ms"] = {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+            print(json.dumps(cell), flush=True)
+    for c in ctxs:
+        c.close()
+    src.close(); m.close()
+
+
+if a.share_prefix:
+    measure_shared()
+    sys.exit(0)
 res = json.load(open(a.from_json)) if a.from_json else measure()
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

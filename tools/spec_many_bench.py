@@ -23,6 +23,8 @@ ap.add_argument("--corpora", default="0,8,4,2", help="every k-th corpus token wr
 ap.add_argument("--forms", default="rows,columns", help="rows = without the matrix-core copy, columns = with it (in this order: the copy cannot be dropped)")
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--step-timeout", type=int, default=120)
+ap.add_argument("--share-prefix", type=int, default=0, help="N > 0: measure lnb_model_set_many_shared_prefix instead -- the largest --members count behind one N-position "
+                "prefix at every budget, shared and cleared alternating in this process; one JSON line per budget (profiles/many_shared_prefix.md)")
 ap.add_argument("--out", default="")
 ap.add_argument("--md", default="")
 ap.add_argument("--from-json", default="", help="write --md from the --out file of an earlier run instead of measuring")
@@ -195,6 +197,49 @@ def write_md(res, path):
         f.write("Total run time of the measurement %.0f s.\n" % res["seconds"])
 
 
+def measure_shared():
+    """n members behind one prefix of N positions, each with 16 tokens of its own; the draft corpus is the member's own greedy continuation"""
+    N, n, steps, cfg = a.share_prefix, NMAX, 64, dict(lnb.LLAMA_8B, n_layers=a.layers)
+    V, cap = cfg["vocab_size"], a.share_prefix + 16 + 64 + 32
+    m = lnb.LlamaTransformer(device=0, **cfg).fill_synthetic(GOLD["weights_seed"]).finalize(rope_rows=max(2048, cap)).enable_batch()
+    src = lnb.InferenceContext(m, cap, max_rows=N, long_context=True)
+    ctxs = [lnb.InferenceContext(m, cap, max_rows=16, long_context=True) for _ in range(n)]
+    prefix = lnb.synth_tokens(99, N, V)
+    own = [lnb.synth_tokens(1000 + s, 16, V) for s in range(n)]
+    limited(lambda: src.Forward(prefix, 0, want_logits=False))
+    limited(lambda: src.ForkPrefix(ctxs, N))
+    firsts = [int(t) for t in limited(lambda: lnb.ForwardAppendMany(ctxs, own, [N] * n, want_logits=False))[1]]
+    hist, pos = [np.concatenate([prefix, o]) for o in own], [N + 16] * n
+    want = [[int(t) for t in limited(lambda s=s: ctxs[s].decode_greedy(firsts[s], N + 16, steps))[0]] for s in range(n)]
+    for s, c in enumerate(ctxs):
+        c.set_draft(MD, NGRAM[0], NGRAM[1], np.array([firsts[s]] + want[s], dtype=np.int32))
+    for B in BUDGETS:
+        ms, cell = {"shared": [], "cleared": []}, {"prefix": N, "members": n, "budget": B, "steps": steps}
+
+        def rounds():
+            for i in range(a.reps + 1):
+                for f in ("shared", "cleared"):
+                    m.set_many_shared_prefix(src if f == "shared" else None, N)
+                    t0 = time.perf_counter()
+                    r = lnb.DecodeSpeculativeMany(ctxs, hist, firsts, pos, steps, B)
+                    if i:
+                        ms[f].append((time.perf_counter() - t0) * 1e3)
+                    if [[int(t) for t in x] for x in r[0]] != want:
+                        raise SystemExit("%s, budget %d: the tokens differ from the members' greedy runs: this run is not timed" % (f, B))
+                    cell[f + "_passes"] = r[3]["passes"]
+            m.set_many_shared_prefix(None, 0)
+        limited(rounds)
+        for f, v in ms.items():
+            cell[f + "_ms"] = {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+        print(json.dumps(cell), flush=True)
+    for c in ctxs:
+        c.close()
+    src.close(); m.close()
+
+
+if a.share_prefix:
+    measure_shared()
+    sys.exit(0)
 res = json.load(open(a.from_json)) if a.from_json else measure()
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
