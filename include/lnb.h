@@ -356,7 +356,8 @@ int lnb_decode_greedy_until(lnb_ctx* c, int32_t token, int start_pos, int max_st
  *   e.g. the prompt); afterwards the cache rows [0, start_pos + *n_generated) hold that call's bits and lnb_decode_greedy / lnb_forward
  *   continue the context.  Requires a whole-model handle, the exact mode and dim, n_heads*head_dim, FFN hidden size multiples of 128 (any
  *   seq_len lnb_ctx_create accepts: a context beyond the one-workgroup attention's reach -- ~7.8 K positions at head_dim 128 -- verifies on
- *   the long-context kernels, lnb_ctx_set_batched_attention); refuses token probabilities, the tolerance mode and a
+ *   the long-context kernels, lnb_ctx_set_batched_attention); refuses token probabilities (lnb_ctx_set_token_probs; the emitted token's record
+ *   is lnb_ctx_set_emitted_probs's), the tolerance mode and a
  *   member of a live batch.  With or without lnb_model_enable_batch (its column forms, or rows of the streaming product; same bits).
  *   stats (optional): passes, verify_passes (passes with a draft), drafted (draft tokens verified), accepted (draft tokens emitted:
  *   *n_generated - passes).  ms_out (optional): HIP-event time of the whole loop.
@@ -546,9 +547,10 @@ int lnb_batch_profile_kernel(lnb_batch* b, int which, int pos, int iters, float*
  *   token lnb_decode_sample_until emits at position p is sample(row_p, sampler, p) and depends on nothing else; column i of a verify pass has
  *   row_{pos + i} exactly, so the greedy acceptance rule holds with "the sampler's token of column i at position pos + i" in place of the argmax.
  *   No distribution is compared and there is no tolerance: the output is the sampling loop's token sequence, the same bits, in fewer passes.
- * Out of scope: rejection sampling against a draft MODEL, pipeline ticks, recording the sampled token's probability.  Logit bias, repetition
+ * Out of scope: rejection sampling against a draft MODEL, pipeline ticks.  The sampled token's probability: lnb_ctx_set_emitted_probs, below (the
+ *   greedy loops' lnb_ctx_set_token_probs stays refused here).  Logit bias, repetition
  *   penalties and min-p: the rules calls below, the speculative loops included (lnb_decode_speculative_sample_rules_until / _many); under rules
- *   pipeline ticks, token-probability records and a draft model are out of scope. */
+ *   pipeline ticks, lnb_ctx_set_token_probs records and a draft model are out of scope. */
 #define LNB_SAMPLE_MAX_VOCAB 131072
 typedef struct lnb_sampler { float temperature; float top_p; int32_t top_k; int32_t reserved; uint64_t seed; } lnb_sampler;
 typedef struct lnb_sample_info { uint64_t w_all, w_topk, w_kept; int32_t n_candidates, n_kept, degenerate, pad; } lnb_sample_info;
@@ -602,6 +604,44 @@ int lnb_op_sample_rules(int device, const uint16_t* logits_bf16, int rows, int V
                         lnb_sample_info* info);
 /* lnb_profile_sample with the rules launch (sample_rules_kernel on the context's tables as the last rules call left them; rules NULL: all off) */
 int lnb_profile_sample_rules(lnb_ctx* c, const lnb_sampler* sampler, const lnb_logit_rules* rules, int pos, int iters, float* avg_ms_out);
+/* ---- the emitted token's record: the probability of the token a sampling or speculative loop actually produced ----
+ * lnb_ctx_set_emitted_probs: top_k -1 (the default: off -- the same graphs, launches and bits as without the feature) or 0..LNB_MAX_TOP_K.  Whole-model
+ *   contexts only; drops the context's captured graphs; refused while the context belongs to a live batch; refused while lnb_ctx_set_token_probs is on, as
+ *   that call is while this switch is on (the two records exclude each other).
+ * With the switch on, every token t that one of the loops below emits from the step's raw logits row x (what lnb_forward returns: before temperature and
+ *   before any logit rule) leaves one record; record i belongs to out_tokens[i]:
+ *     tok_logit = f32(x_t);  tok_prob = float32(exp(f64(x_t)) / Z), the bits lnb_forward_score reports for targets = t on that row (the certified estimate
+ *     first, the serial walk where it cannot settle this quotient; walks are counted in lnb_ctx_token_prob_walks);  log_z as lnb_ctx_read_token_probs;
+ *     ids / logits / probs [top_k] = the RAW row's top k exactly as lnb_ctx_read_token_probs defines them -- entry 0 is the row's argmax, which need not be t;
+ *     w_tok, w_kept = the sampler's own exact probability of t as the fraction w_tok / w_kept: w_t of step 4 (4b under rules) and W_K of step 8 of the
+ *     sampling rule above; both 0 for a greedy step (temperature 0), a degenerate row and a candidate-less row.
+ *   A token of -1 (an all-NaN or candidate-less row) records NaN for tok_logit and tok_prob and 0 for both weights.  A finished generation records nothing
+ *   behind its stop token; the stop token itself is recorded.
+ * Honoured by lnb_decode_sample_until, lnb_decode_sample_rules_until, lnb_batch_decode_sample_until, lnb_batch_decode_sample_rules_until (all members at
+ *   one value; read each member context), lnb_decode_speculative_until, lnb_decode_speculative_sample_until and lnb_decode_speculative_sample_rules_until.
+ *   The speculative calls record emitted tokens only -- accepted drafts and the bonus token, a rejected column leaves no trace -- and their records are
+ *   BIT-IDENTICAL to the sampling loop's (the greedy call: to the sampling loop's at temperature 0), whatever the draft settings, corpus or chunking --
+ *   with one reservation for log_z when the vocabulary is no multiple of 8: the estimate of Z is summed over sub-slices cut from the row's first 16-byte
+ *   boundary, and row c of a verify pass or of a batch starts c * V entries into the logits, so its cut -- hence the last bits of log_z, and whether the row
+ *   walks -- can differ from the one-token step's.  log_z then agrees within its (V + 8) 2^-52 bound; every other field is bit-identical at any V.
+ *   lnb_ctx_token_prob_walks counts the rows of emitted tokens only, as the sampling loop does: a rejected column is not counted.
+ *   These steps are graph families of their own beside the plain ones; neither drops or recaptures the other.
+ * Every other entry point refuses a context with the switch on, naming it: lnb_decode_greedy[_until] and lnb_batch_decode[_until] (which have
+ *   lnb_ctx_set_token_probs), the three *_many speculative calls, lnb_forward_append_many and pipeline ticks.  Out of scope, deliberately: records in the
+ *   _many forms and in pipeline ticks.
+ * lnb_ctx_read_emitted_probs: records [first, first + n) of the last honoured call that ran the context, with lnb_ctx_read_token_probs's bounds rule.
+ *   tok_logit / tok_prob / log_z / w_tok / w_kept: [n]; ids / logits / probs: [n * k], k = the top_k that call ran with.  Any output pointer may be NULL.
+ * lnb_ctx_emitted_probs_last: *top_k = the top_k the last honoured call of this context recorded with (-1: it recorded nothing), *n = its records.
+ * lnb_op_emitted_probs: the device path on host rows [rows][V] (a test aid, as lnb_op_token_probs and lnb_op_sample_rules): the row summary launch, then
+ *   the token launch with the emitted entry; rules NULL = the plain sampler, else rules [rows] with counts [rows][V] (NULL: all zero).  force_serial: every
+ *   row walks the serial sum (the same bits).  Any output but tokens_out may be NULL. */
+int lnb_ctx_set_emitted_probs(lnb_ctx* c, int top_k);
+int lnb_ctx_read_emitted_probs(lnb_ctx* c, int first, int n, float* tok_logit, float* tok_prob, double* log_z, uint64_t* w_tok, uint64_t* w_kept,
+                               int32_t* ids, float* logits, float* probs);
+int lnb_ctx_emitted_probs_last(lnb_ctx* c, int* top_k, int* n);
+int lnb_op_emitted_probs(int device, const uint16_t* logits_bf16, int rows, int V, int top_k, const lnb_sampler* samplers, const lnb_logit_rules* rules,
+                         const uint32_t* counts, const int32_t* pos, const uint64_t* draws, int force_serial, int32_t* tokens_out, float* tok_logit,
+                         float* tok_prob, double* log_z, uint64_t* w_tok, uint64_t* w_kept, int32_t* ids, float* logits, float* probs, int* serial_walks);
 /* ---- sampling in the speculative loops ----
  * lnb_decode_speculative_sample_until: out_tokens[0 .. *n_generated), *n_generated, *finished and the KV rows [0, start_pos + *n_generated) of every
  *   layer are bit-identical to lnb_decode_sample_until(c, sampler, token, start_pos, max_steps, ...) on a context holding the same rows below

@@ -117,6 +117,9 @@ hipError_t lnbk_spec_many_pack(const SmPass* p, hipStream_t st);
 hipError_t lnbk_spec_many_commit(const SmPass* p, hipStream_t st);
 hipError_t lnbk_spec_many_sample_commit(const SmPass* p, hipStream_t st);
 hipError_t lnbk_spec_many_sample_rules_commit(const SmPass* p, hipStream_t st);
+hipError_t lnbk_emit_summary(const TokProbParams* p, hipStream_t st);
+hipError_t lnbk_emit_sample(const EmitTokParams* p, int n, hipStream_t st);
+hipError_t lnbk_emit_spec_commit(const EmitSpecParams* p, int w, hipStream_t st);
 }
 
 // The HIP runtime spreads a process's streams over a fixed number of hardware queues (its default: 4) and streams that share a queue run one
@@ -172,7 +175,10 @@ template <class T> static hipError_t pinned_alloc(Pinned<T>& p, size_t bytes, un
 static hipError_t event_create(Event& e, unsigned flags = hipEventDefault) { return e.fill([&](hipEvent_t* q) { return hipEventCreateWithFlags(q, flags); }); }
 static hipError_t stream_create(Stream& s, unsigned flags) { return s.fill([&](hipStream_t* q) { return hipStreamCreateWithFlags(q, flags); }); }
 // which captured step: the token launch that ends it, and the attention form its launches bake in
-enum GraphLaunch { GL_GREEDY = 0, GL_SAMPLE, GL_STAGE, GL_SAMPLE_RULES, GL_COUNT };
+// (the _EMIT families: the same steps with the emitted token's record, lnb_ctx_set_emitted_probs -- families of their own, so neither drops or recaptures the other)
+enum GraphLaunch { GL_GREEDY = 0, GL_SAMPLE, GL_STAGE, GL_SAMPLE_RULES, GL_SAMPLE_EMIT, GL_SAMPLE_RULES_EMIT, GL_COUNT };
+static bool gl_rules(GraphLaunch l) { return l == GL_SAMPLE_RULES || l == GL_SAMPLE_RULES_EMIT; }
+static bool gl_emit(GraphLaunch l) { return l == GL_SAMPLE_EMIT || l == GL_SAMPLE_RULES_EMIT; }
 enum GraphForm { GF_SHORT = 0, GF_LONG, GF_ROWS, GF_SHARED, GF_COUNT };      // (0, 1, 2: also what lnb_ctx_verify_attention_form reports; GF_SHARED: a batch with a shared prefix)
 using Graphs = GraphTable<hipGraphExec_t, hipGraphExecDestroy, GL_COUNT, GF_COUNT>;
 
@@ -304,6 +310,20 @@ struct lnb_ctx {
         Dev<double> zpart; Dev<uint64_t> kpart; Dev<unsigned> cnt;   // one row's partials, arrival ticket
     } tp;
     int tp_last_k = 0, tp_last_n = 0;      // what the last decode call that ran this context recorded (k 0: nothing)
+    // the emitted token's record in the sampling and speculative loops (lnb_ctx_set_emitted_probs; lnb_emit_probs.h): -1 = off.  One allocation: the log
+    // (dout_cap records), the summary launch's partials and parked Z of one row, and the verify passes' scratch of 16 records; `log` and `out` / `s_out` are
+    // the device structs the launches read (the TokProbOut members alias the log / the pass scratch)
+    int emit_k = -1;
+    struct EmitBufs {
+        Dev<char> mem;
+        EmitLog* log = nullptr; TokProbOut* out = nullptr; TokProbOut* s_out = nullptr;
+        float* tok_logit = nullptr; float* tok_prob = nullptr; double* logz = nullptr; unsigned long long* w = nullptr;
+        int32_t* ids = nullptr; float* logit = nullptr; float* prob = nullptr;
+        double* zpart = nullptr; uint64_t* kpart = nullptr; unsigned* cnt = nullptr; EmitPark* park = nullptr;          // one row (the decode step)
+        double* s_zpart = nullptr; uint64_t* s_kpart = nullptr; unsigned* s_cnt = nullptr; EmitPark* s_park = nullptr;  // 16 columns (a verify pass)
+        int32_t* s_ids = nullptr; float* s_logit = nullptr; float* s_prob = nullptr; unsigned long long* gw = nullptr;
+    } em;
+    int em_last_k = -1, em_last_n = 0;     // what the last supported call recorded (k -1: nothing)
     DevGrown<char> sc_buf;                 // lnb_forward_score's scratch, grown on demand
     // speculative decoding (lnb_ctx_set_draft, lnb_decode_speculative_until): drafting settings, the corpus, the running text's head (history +
     // token), the verify columns' states and token words (index 0 unused: column 0 is this context's own), their argmax, the draft kernel's
@@ -1671,6 +1691,7 @@ extern "C" int lnb_forward_score_append(lnb_ctx* c, const int32_t* tokens, int s
 
 // one decode step = embed(token on device) -> layers -> head -> [token probabilities] -> argmax that feeds the next step; sample: the sampler's token
 // (the context's device sampler, lnb_decode_sample_until) in place of the argmax
+static int enqueue_emit_token(lnb_ctx* c, bool rules);
 static int enqueue_decode_step(lnb_ctx* c, GraphLaunch launch = GL_GREEDY) {
     lnb_model* m = c->m;
     // LNB_MEASURE_SKIP_TOKEN_KERNELS=1 (timing only, the tokens are garbage): the step without its embedding gather and argmax launches =
@@ -1683,7 +1704,8 @@ static int enqueue_decode_step(lnb_ctx* c, GraphLaunch launch = GL_GREEDY) {
         TokProbParams p = tp_params(m, c->logits, 1, c->top_k, c->tp.zpart, c->tp.kpart, c->tp.cnt, c->tp.out, 0);
         HIPCHK(lnbk_token_probs(&p, c->stream));
     }
-    if (launch == GL_SAMPLE_RULES)
+    if (gl_emit(launch)) { if (enqueue_emit_token(c, gl_rules(launch))) return -1; }
+    else if (launch == GL_SAMPLE_RULES)
         HIPCHK(lnbk_sample_rules(c->logits, m->a.vocab_size, 1, m->prob_etab, c->d_smp, c->rl.d_rules, c->dtok, c->st, c->dout, c->dout_cap, 1, nullptr, nullptr, nullptr, c->stream));
     else if (launch == GL_SAMPLE) HIPCHK(lnbk_sample(c->logits, m->a.vocab_size, 1, m->prob_etab, c->d_smp, c->dtok, c->st, c->dout, c->dout_cap, 1, nullptr, nullptr, nullptr, c->stream));
     else if (!skip) HIPCHK(lnbk_argmax(c->logits, m->a.vocab_size, c->dtok, c->st, c->dout, c->dout_cap, 1, c->stream));
@@ -1709,6 +1731,8 @@ extern "C" int lnb_ctx_set_token_probs(lnb_ctx* c, int top_k) {
     if (top_k < 0 || top_k > LNB_MAX_TOP_K) return fail("top_k must be 0..%d (got %d)", LNB_MAX_TOP_K, top_k);
     if (!c->m->first() || !c->m->last()) return fail("token probabilities need a whole-model handle (pipeline stages are not supported)");
     if (c->batch_users > 0) return fail("context is a member of %d live batch(es): its top-k is fixed until they are destroyed", c->batch_users);
+    if (top_k > 0 && c->emit_k >= 0)
+        return fail("lnb_ctx_set_token_probs: the context records emitted-token probabilities; the two records exclude each other (lnb_ctx_set_emitted_probs(ctx, -1) first)");
     HIPCHK(hipSetDevice(c->m->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->graphs.drop_all();
@@ -1749,6 +1773,92 @@ extern "C" int lnb_ctx_token_prob_walks(lnb_ctx* c, int* out) {
     HIPCHK(hipMemcpyAsync(c->h_io, c->zseq_count + 2, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     *out = c->h_io[0];
+    return 0;
+}
+// The emitted token's record (include/lnb.h): -1 (default) = off -- nothing is allocated, enqueued or captured for it.  The graph families with records
+// bake in the log's addresses and top_k: setting the switch drops them (drop_all, as lnb_ctx_set_token_probs does).
+static const char* const k_emit_advice = "records emitted-token probabilities (lnb_ctx_set_emitted_probs), which this entry point does not: lnb_ctx_set_emitted_probs(ctx, -1) first";
+extern "C" int lnb_ctx_set_emitted_probs(lnb_ctx* c, int top_k) {
+    if (!c) return fail("null argument");
+    if (top_k < -1 || top_k > LNB_MAX_TOP_K) return fail("lnb_ctx_set_emitted_probs: top_k must be -1 (off) or 0..%d (got %d)", LNB_MAX_TOP_K, top_k);
+    if (!c->m->first() || !c->m->last()) return fail("lnb_ctx_set_emitted_probs needs a whole-model handle (pipeline stages are not supported)");
+    if (c->batch_users > 0) return fail("context is a member of %d live batch(es): lnb_ctx_set_emitted_probs is fixed until they are destroyed", c->batch_users);
+    if (top_k >= 0 && c->top_k > 0)
+        return fail("lnb_ctx_set_emitted_probs: the context records the greedy loops' token probabilities; the two records exclude each other (lnb_ctx_set_token_probs(ctx, 0) first)");
+    HIPCHK(hipSetDevice(c->m->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->graphs.drop_all();
+    for (lnb_batch*& b : c->sp_b) if (b) { lnb_batch_destroy(b); b = nullptr; }       // (the verify batches' graphs of the record families hold the old log)
+    c->em = {};
+    c->emit_k = -1; c->em_last_k = -1; c->em_last_n = 0;
+    if (top_k < 0) return 0;
+    // the layout of the one allocation (every piece 256-byte aligned)
+    const size_t cap = (size_t)c->dout_cap, K = (size_t)std::max(top_k, 1), W = LNB_MAX_DRAFT + 1, G = LNB_TOKPROB_MAX_G;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    const size_t o_log = take(sizeof(EmitLog)), o_out = take(sizeof(TokProbOut)), o_sout = take(sizeof(TokProbOut)), o_tl = take(cap * 4), o_tp = take(cap * 4),
+                 o_lz = take(cap * 8), o_w = take(cap * 16), o_ids = take(cap * K * 4), o_lg = take(cap * K * 4), o_pr = take(cap * K * 4), o_zp = take(G * 8),
+                 o_kp = take(G * K * 8), o_cnt = take(4), o_pk = take(sizeof(EmitPark)), o_szp = take(W * G * 8), o_skp = take(W * G * K * 8), o_scnt = take(W * 4),
+                 o_spk = take(W * sizeof(EmitPark)), o_sids = take(W * K * 4), o_slg = take(W * K * 4), o_spr = take(W * K * 4), o_gw = take(W * 16);
+    HIPCHK(dev_alloc(c->em.mem, off));
+    char* const b = c->em.mem;
+    auto& e = c->em;
+    e.log = (EmitLog*)(b + o_log); e.out = (TokProbOut*)(b + o_out); e.s_out = (TokProbOut*)(b + o_sout);
+    e.tok_logit = (float*)(b + o_tl); e.tok_prob = (float*)(b + o_tp); e.logz = (double*)(b + o_lz); e.w = (unsigned long long*)(b + o_w);
+    e.ids = (int32_t*)(b + o_ids); e.logit = (float*)(b + o_lg); e.prob = (float*)(b + o_pr);
+    e.zpart = (double*)(b + o_zp); e.kpart = (uint64_t*)(b + o_kp); e.cnt = (unsigned*)(b + o_cnt); e.park = (EmitPark*)(b + o_pk);
+    e.s_zpart = (double*)(b + o_szp); e.s_kpart = (uint64_t*)(b + o_skp); e.s_cnt = (unsigned*)(b + o_scnt); e.s_park = (EmitPark*)(b + o_spk);
+    e.s_ids = (int32_t*)(b + o_sids); e.s_logit = (float*)(b + o_slg); e.s_prob = (float*)(b + o_spr); e.gw = (unsigned long long*)(b + o_gw);
+    HIPCHK(hipMemsetAsync(b, 0, off, c->stream));            // (the arrival tickets start at zero; never captured)
+    const EmitLog lg{e.tok_logit, e.tok_prob, e.logz, e.w, e.ids, e.logit, e.prob, c->zseq_count + 2, c->dout_cap, top_k};
+    TokProbOut o{}; o.st = c->st; o.ids = e.ids; o.logit = e.logit; o.prob = e.prob; o.log_z = e.logz; o.walks = c->zseq_count + 2; o.cap = c->dout_cap;
+    TokProbOut so{}; so.ids = e.s_ids; so.logit = e.s_logit; so.prob = e.s_prob; so.cap = (int)W;      // (slot = column; ln Z and the walk count are the commit's: emitted columns only)
+    HIPCHK(hipMemcpyAsync(e.log, &lg, sizeof lg, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(e.out, &o, sizeof o, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(e.s_out, &so, sizeof so, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                 // (stack memory)
+    c->emit_k = top_k;
+    return 0;
+}
+extern "C" int lnb_ctx_read_emitted_probs(lnb_ctx* c, int first, int n, float* tok_logit, float* tok_prob, double* log_z, uint64_t* w_tok, uint64_t* w_kept,
+                                          int32_t* ids, float* logits, float* probs) {
+    if (!c) return fail("null argument");
+    if (c->em_last_k < 0 || !c->em.mem) return fail("the last decode call of this context recorded no emitted-token probabilities (lnb_ctx_set_emitted_probs)");
+    if (first < 0 || n < 0 || first + n > c->em_last_n)
+        return fail("records [%d, %d) requested: the last decode call generated %d tokens", first, first + n, c->em_last_n);
+    if (n == 0) return 0;
+    const size_t k = c->em_last_k, off = (size_t)first * k, cnt = (size_t)n * k;
+    hipStream_t st = c->stream;
+    HIPCHK(hipSetDevice(c->m->device));
+    std::vector<uint64_t> w(w_tok || w_kept ? (size_t)n * 2 : 0);
+    if (tok_logit) HIPCHK(hipMemcpyAsync(tok_logit, c->em.tok_logit + first, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (tok_prob) HIPCHK(hipMemcpyAsync(tok_prob, c->em.tok_prob + first, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (log_z) HIPCHK(hipMemcpyAsync(log_z, c->em.logz + first, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    if (!w.empty()) HIPCHK(hipMemcpyAsync(w.data(), c->em.w + 2 * (size_t)first, (size_t)n * 16, hipMemcpyDeviceToHost, st));
+    if (ids && cnt) HIPCHK(hipMemcpyAsync(ids, c->em.ids + off, cnt * 4, hipMemcpyDeviceToHost, st));
+    if (logits && cnt) HIPCHK(hipMemcpyAsync(logits, c->em.logit + off, cnt * 4, hipMemcpyDeviceToHost, st));
+    if (probs && cnt) HIPCHK(hipMemcpyAsync(probs, c->em.prob + off, cnt * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < n && !w.empty(); i++) { if (w_tok) w_tok[i] = w[2 * i]; if (w_kept) w_kept[i] = w[2 * i + 1]; }
+    return 0;
+}
+// what the last honoured call recorded: its top_k (-1: nothing) and how many records -- so that a binding sizes its arrays by the call, not by its own copy of the switch
+extern "C" int lnb_ctx_emitted_probs_last(lnb_ctx* c, int* top_k, int* n) {
+    if (!c || !top_k || !n) return fail("null argument");
+    *top_k = c->em.mem ? c->em_last_k : -1; *n = *top_k < 0 ? 0 : c->em_last_n;
+    return 0;
+}
+// the row summary launch + the token launch with the emitted entry, for one row of this context (the decode step)
+static int enqueue_emit_token(lnb_ctx* c, bool rules) {
+    lnb_model* m = c->m;
+    TokProbParams p = tp_params(m, c->logits, 1, c->emit_k, c->em.zpart, c->em.kpart, c->em.cnt, c->em.out, 0);
+    p.park = c->em.park;
+    HIPCHK(lnbk_emit_summary(&p, c->stream));
+    EmitTokParams t{};
+    t.logits = c->logits; t.V = m->a.vocab_size; t.etab = m->prob_etab; t.smp = c->d_smp; t.rules = rules ? c->rl.d_rules.get() : nullptr;
+    t.next_token = c->dtok; t.st = c->st; t.out_tokens = c->dout; t.out_cap = c->dout_cap; t.advance = 1;
+    t.park = c->em.park; t.log = c->em.log;
+    HIPCHK(lnbk_emit_sample(&t, 1, c->stream));
     return 0;
 }
 // What `body` enqueues on `st`, captured into the graph slot -- once: a slot that holds a graph is left alone and the body does not run.
@@ -1932,7 +2042,7 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
         if (sample_vocab_check(m->a.vocab_size)) return -1;
         if (c->top_k > 0) return fail("the context %s", k_sample_probs_advice);
         if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
-    }
+    } else if (c->emit_k >= 0) return fail("lnb_decode_greedy: the context %s (the greedy loops have lnb_ctx_set_token_probs)", k_emit_advice);
     HIPCHK(hipSetDevice(m->device));
     if (n_steps <= 0) return fail("n_steps must be positive");
     if (n_steps > c->dout_cap) return fail("n_steps %d exceeds the context length %d", n_steps, c->dout_cap);
@@ -1942,9 +2052,10 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     const bool use_graph = knob(Knob::NO_GRAPH) == 0;
     if (smp && !c->d_smp) HIPCHK(dev_alloc(c->d_smp, sizeof(LnbSampler)));
     if (rc && !c->rl.d_rules) HIPCHK(dev_alloc(c->rl.d_rules, sizeof(LnbRulesDev)));
-    const GraphLaunch launch = rc ? GL_SAMPLE_RULES : smp ? GL_SAMPLE : GL_GREEDY;
+    const bool emit = smp && c->emit_k >= 0;
+    const GraphLaunch launch = rc ? (emit ? GL_SAMPLE_RULES_EMIT : GL_SAMPLE_RULES) : smp ? (emit ? GL_SAMPLE_EMIT : GL_SAMPLE) : GL_GREEDY;
     if (use_graph && capture_decode_graphs(c, start_pos, n_steps, launch)) return -1;
-    c->tp_last_k = 0; c->tp_last_n = 0;
+    c->tp_last_k = 0; c->tp_last_n = 0; c->em_last_k = -1; c->em_last_n = 0;
     if (smp) HIPCHK(hipMemcpyAsync(c->d_smp, smp, sizeof(LnbSampler), hipMemcpyHostToDevice, st));
     if (rc) {
         if (rules_tables(c, rc->rules, rc->counted, rc->n_counted, token, st, &c->rl.h_rules)) return -1;
@@ -1973,6 +2084,7 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     if (c->h_io[1]) return fail("generated token id is outside the vocabulary");
     if (n_generated) { *n_generated = hs.n_out; if (finished) *finished = hs.finished; c->dev_pos = -1; }     // (a stopped run leaves the device position short of start_pos + n_steps)
     c->tp_last_k = c->top_k; c->tp_last_n = n_generated ? hs.n_out : n_steps;
+    if (emit) { c->em_last_k = c->emit_k; c->em_last_n = c->tp_last_n; }
     return 0;
 }
 
@@ -2204,6 +2316,8 @@ struct lnb_batch {
     PipeLink link;
     // token probabilities (the members' lnb_ctx_set_token_probs, one top_k for all): one row per sequence into its context's log (the records' members alias the contexts' logs)
     int top_k = 0; Dev<TokProbOut> tp_out; Dev<double> tp_zpart; Dev<uint64_t> tp_kpart; Dev<unsigned> tp_cnt;
+    // the members' lnb_ctx_set_emitted_probs (one value for all, -1: off): per member its log's device structs, the summary launch's partials and the parked Z
+    int emit_k = -1; Dev<TokProbOut> em_out; Dev<EmitLog> em_log; Dev<EmitPark> em_park; Dev<double> em_zpart; Dev<uint64_t> em_kpart; Dev<unsigned> em_cnt;
     // speculative verify batch (lnb_decode_speculative_until): every column is ONE context (ctxs[s] = it, the same caches); columns s >= 1 take
     // their state and token word from col_st + s / col_tok + s instead of the context's own (the context's sp_st / sp_tok: it owns them)
     StepState* col_st = nullptr; int32_t* col_tok = nullptr;
@@ -2322,6 +2436,22 @@ static int batch_alloc(lnb_batch* b) {
         HIPCHK(dev_alloc(b->tp_zpart, n * LNB_TOKPROB_MAX_G * 8)); HIPCHK(dev_alloc(b->tp_kpart, n * G * b->top_k * 8));
         HIPCHK(dev_alloc(b->tp_cnt, n * 4)); HIPCHK(hipMemsetAsync(b->tp_cnt, 0, n * 4, b->stream));
     }
+    std::vector<TokProbOut> eo(b->emit_k >= 0 ? n : 0);
+    std::vector<EmitLog> el(eo.size());
+    if (b->emit_k >= 0) {
+        const size_t G = (size_t)lnb_tokprob_slices(n), K = (size_t)std::max(b->emit_k, 1);
+        for (int s = 0; s < n; s++) {
+            const lnb_ctx* c = b->ctxs[s];
+            const auto& e = c->em;
+            eo[s] = TokProbOut{}; eo[s].st = c->st; eo[s].ids = e.ids; eo[s].logit = e.logit; eo[s].prob = e.prob; eo[s].log_z = e.logz; eo[s].walks = c->zseq_count + 2; eo[s].cap = c->dout_cap;
+            el[s] = EmitLog{e.tok_logit, e.tok_prob, e.logz, e.w, e.ids, e.logit, e.prob, c->zseq_count + 2, c->dout_cap, b->emit_k};
+        }
+        HIPCHK(dev_alloc(b->em_out, n * sizeof(TokProbOut))); HIPCHK(dev_alloc(b->em_log, n * sizeof(EmitLog))); HIPCHK(dev_alloc(b->em_park, n * sizeof(EmitPark)));
+        HIPCHK(hipMemcpyAsync(b->em_out, eo.data(), n * sizeof(TokProbOut), hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipMemcpyAsync(b->em_log, el.data(), n * sizeof(EmitLog), hipMemcpyHostToDevice, b->stream));
+        HIPCHK(dev_alloc(b->em_zpart, n * LNB_TOKPROB_MAX_G * 8)); HIPCHK(dev_alloc(b->em_kpart, n * G * K * 8));
+        HIPCHK(dev_alloc(b->em_cnt, n * 4)); HIPCHK(hipMemsetAsync(b->em_cnt, 0, n * 4, b->stream));
+    }
     HIPCHK(hipStreamSynchronize(b->stream));
     return 0;
 }
@@ -2336,6 +2466,8 @@ extern "C" int lnb_batch_create(lnb_ctx* const* ctxs, int n, lnb_batch** out) {
         if (ctxs[s]->mode != LNB_MODE_EXACT) return fail("context %d is in the tolerance mode: batched decode is exact-order only", s);
         if (ctxs[s]->top_k != ctxs[0]->top_k)
             return fail("context %d records top-%d token probabilities, context 0 top-%d: a batch needs one setting", s, ctxs[s]->top_k, ctxs[0]->top_k);
+        if (ctxs[s]->emit_k != ctxs[0]->emit_k)
+            return fail("context %d has lnb_ctx_set_emitted_probs at %d, context 0 at %d: a batch needs one setting", s, ctxs[s]->emit_k, ctxs[0]->emit_k);
     }
     lnb_model* m = ctxs[0]->m;
     HIPCHK(hipSetDevice(m->device));
@@ -2347,7 +2479,7 @@ extern "C" int lnb_batch_create(lnb_ctx* const* ctxs, int n, lnb_batch** out) {
         HIPCHK(lnbk_batch_prepare());
     }
     lnb_batch* b = new lnb_batch();
-    b->m = m; b->n = n; b->ctxs.assign(ctxs, ctxs + n); b->rows_form = !m->batch_enabled; b->top_k = ctxs[0]->top_k;
+    b->m = m; b->n = n; b->ctxs.assign(ctxs, ctxs + n); b->rows_form = !m->batch_enabled; b->top_k = ctxs[0]->top_k; b->emit_k = ctxs[0]->emit_k;
     for (int s = 0; s < n; s++) {
         if (lnbk_attn_long_layout_lds(ctxs[s]->seq_len) > 160 * 1024) {       // (neither lnb_ctx_create nor lnb_ctx_create_long makes such a context: cannot happen)
             const int sl = ctxs[s]->seq_len; delete b;
@@ -2559,7 +2691,15 @@ static int enqueue_batch_step(lnb_batch* b, bool ring_in = false, bool sample = 
     lnb_model* m = b->m;
     if (ring_in && m->first()) HIPCHK(lnbk_batch_scatter_ring(b->tab, b->ring, b->stream));
     if (enqueue_batch_pass(b)) return -1;
-    if (m->last() && rules) {                                // every member's own sampler, rules and tables (lnb_batch_decode_sample_rules_until)
+    if (m->last() && sample && b->emit_k >= 0) {              // the same two token launches with every member's record into its own context's log
+        TokProbParams p = tp_params(m, b->logits, b->n, b->emit_k, b->em_zpart, b->em_kpart, b->em_cnt, b->em_out, 1);
+        p.park = b->em_park;
+        HIPCHK(lnbk_emit_summary(&p, b->stream));
+        EmitTokParams t{};
+        t.logits = b->logits; t.V = m->a.vocab_size; t.etab = m->prob_etab; t.smp = b->d_smp; t.rules = rules ? b->d_rules.get() : nullptr;
+        t.tab = b->tab; t.park = b->em_park; t.log = b->em_log; t.per_row_log = 1;
+        HIPCHK(lnbk_emit_sample(&t, b->n, b->stream));
+    } else if (m->last() && rules) {                         // every member's own sampler, rules and tables (lnb_batch_decode_sample_rules_until)
         HIPCHK(lnbk_batch_sample_rules(b->logits, m->a.vocab_size, m->prob_etab, b->d_smp, b->d_rules, b->tab, b->n, b->stream));
     } else if (m->last() && sample) {                               // every member's own sampler (lnb_batch_decode_sample_until: a whole model, no token probabilities)
         HIPCHK(lnbk_batch_sample(b->logits, m->a.vocab_size, m->prob_etab, b->d_smp, b->tab, b->n, b->stream));
@@ -2617,7 +2757,7 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     if (smp) {
         if (sample_vocab_check(m->a.vocab_size)) return -1;
         for (int s = 0; s < b->n; s++) if (b->ctxs[s]->top_k > 0) return fail("sequence %d: its context %s", s, k_sample_probs_advice);
-    }
+    } else if (b->emit_k >= 0) return fail("lnb_batch_decode: the batch's contexts record emitted-token probabilities (lnb_ctx_set_emitted_probs), which the greedy loops do not (they have lnb_ctx_set_token_probs)");
     HIPCHK(hipSetDevice(m->device));
     if (n_steps <= 0) return fail("n_steps must be positive");
     if (batch_prefix_check(b, start_pos)) return -1;
@@ -2631,11 +2771,12 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
         if (c->pending) return fail("sequence %d: a lnb_forward_stage_begin has not been ended", s);
         if (member_drain(c)) return -1;
     }
-    for (lnb_ctx* c : b->ctxs) { c->tp_last_k = 0; c->tp_last_n = 0; }
+    for (lnb_ctx* c : b->ctxs) { c->tp_last_k = 0; c->tp_last_n = 0; c->em_last_k = -1; c->em_last_n = 0; }
     hipStream_t st = b->stream;
     if (batch_select_form_at(b, start_pos)) return -1;
     const bool use_graph = knob(Knob::NO_GRAPH) == 0;
-    GraphExec& gslot = b->graphs.slot(rules ? GL_SAMPLE_RULES : smp ? GL_SAMPLE : GL_GREEDY, batch_graph_form(b));       // one captured step per form
+    const bool emit = smp && b->emit_k >= 0;
+    GraphExec& gslot = b->graphs.slot(rules ? (emit ? GL_SAMPLE_RULES_EMIT : GL_SAMPLE_RULES) : smp ? (emit ? GL_SAMPLE_EMIT : GL_SAMPLE) : GL_GREEDY, batch_graph_form(b));       // one captured step per form
     if (smp && !b->d_smp) HIPCHK(dev_alloc(b->d_smp, (size_t)LNB_BATCH_MAX * sizeof(LnbSampler)));
     if (rules && !b->d_rules) { HIPCHK(dev_alloc(b->d_rules, (size_t)LNB_BATCH_MAX * sizeof(LnbRulesDev))); b->h_rules.assign(LNB_BATCH_MAX, LnbRulesDev{}); }
     if (use_graph && capture_once(gslot, st, [&] { return enqueue_batch_step(b, false, smp != nullptr, rules != nullptr); })) return -1;
@@ -2673,6 +2814,7 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     if (b->h_io[2 * LNB_BATCH_MAX]) return fail("sequence %d: generated token id is outside the vocabulary", b->h_io[2 * LNB_BATCH_MAX] - 1);
     for (int s = 0; s < (int)hs.size(); s++) { n_generated[s] = hs[s].n_out; if (finished) finished[s] = hs[s].finished; }
     for (int s = 0; s < b->n; s++) { b->ctxs[s]->tp_last_k = b->top_k; b->ctxs[s]->tp_last_n = n_generated ? n_generated[s] : n_steps; }
+    if (emit) for (lnb_ctx* c : b->ctxs) { c->em_last_k = b->emit_k; c->em_last_n = c->tp_last_n; }
     return 0;
 }
 // what a batched tick exchanges, for a host layer that moves it itself (lnb_pipeline_init_host)
@@ -2712,6 +2854,7 @@ extern "C" int lnb_batch_set_state(lnb_batch* b, const int32_t* tokens, const in
         // and appending KV rows behind the stop.  Stop ids in a multi-stage batched pipeline belong to the host: it reads the tokens.
         if (c->top_k > 0 && !one_stage)
             return fail("sequence %d: its context records token probabilities, which pipeline stages do not support (lnb_ctx_set_token_probs(ctx, 0))", s);
+        if (c->emit_k >= 0) return fail("sequence %d: its context %s", s, k_emit_advice);
         if (c->n_stop > 0 && !one_stage)
             return fail("sequence %d: its context carries %d stop ids, which a batched tick of a multi-stage pipeline cannot honour (only the last stage sees the "
                         "token): clear them (lnb_ctx_set_stop_ids(ctx, NULL, 0)) and end the sequence on the host", s, c->n_stop);
@@ -2887,6 +3030,7 @@ extern "C" int lnb_forward_append_many(lnb_ctx* const* ctxs, int n, const int32_
         const lnb_ctx* c = ctxs[s];
         if (c->mode != LNB_MODE_EXACT) return fail("%s: context %d is in the tolerance mode: the call is exact-mode only", name, s);
         if (c->pending) return fail("%s: context %d: a lnb_forward_stage_begin has not been ended", name, s);
+        if (c->emit_k >= 0) return fail("%s: context %d %s", name, s, k_emit_advice);
         const int64_t T = (int64_t)start_pos[s] + n_rows[s];
         if (T > m->cis_rows) return fail("%s: member %d: position %lld is beyond the %d-row RoPE table", name, s, (long long)T, m->cis_rows);
         if (T > c->seq_len) return fail("%s: member %d: position %lld is beyond the KV cache of %d", name, s, (long long)T, c->seq_len);
@@ -3211,6 +3355,17 @@ static int spec_verify_batch(lnb_ctx* c, int w, GraphForm form, GraphLaunch laun
     GraphExec& gslot = b->graphs.slot(launch, form);
     auto body = [&]() -> int {
         if (enqueue_batch_pass(b)) return -1;
+        if (gl_emit(launch)) {                               // the summary of all w columns at once into the pass scratch, then the commit that records the emitted ones
+            TokProbParams p = tp_params(m, b->logits, w, c->emit_k, c->em.s_zpart, c->em.s_kpart, c->em.s_cnt, c->em.s_out, 0);
+            p.park = c->em.s_park;
+            HIPCHK(lnbk_emit_summary(&p, b->stream));
+            EmitSpecParams e{};
+            e.logits = b->logits; e.V = m->a.vocab_size; e.etab = m->prob_etab; e.smp = c->d_smp; e.rules = gl_rules(launch) ? c->rl.d_rules.get() : nullptr;
+            e.g = c->sp_g; e.gw = c->em.gw; e.tab = b->tab; e.cnt = c->sp_cnt + 1; e.park = c->em.s_park;
+            e.s_ids = c->em.s_ids; e.s_logit = c->em.s_logit; e.s_prob = c->em.s_prob; e.log = c->em.log;
+            HIPCHK(lnbk_emit_spec_commit(&e, w, b->stream));
+            return 0;
+        }
         if (launch == GL_SAMPLE_RULES) {                     // every column's token under the context's device rules, its counts the table's plus the drafts in front of it
             HIPCHK(lnbk_spec_sample_rules_commit(b->logits, m->a.vocab_size, w, m->prob_etab, c->d_smp, c->rl.d_rules, c->sp_g, b->tab, c->sp_cnt + 1, b->stream));
             return 0;
@@ -3251,6 +3406,11 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
     if (c->top_k > 0) return fail("speculative decoding does not record token probabilities: lnb_ctx_set_token_probs(ctx, 0) first");
     if (c->batch_users > 0) return fail("context is a member of %d live batch(es): speculative decoding runs it alone (lnb_batch_destroy first)", c->batch_users);
     if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
+    // with records the greedy call runs the record families of the sampling loop at temperature 0 (the raw row's argmax, both weights 0): the greedy
+    // step has no token launch with the emitted entry of its own
+    static const lnb_sampler k_greedy = {0.0f, 1.0f, 0, 0, 0};
+    const bool emit = c->emit_k >= 0;
+    if (emit && !smp) smp = &k_greedy;
     if (smp && sample_vocab_check(m->a.vocab_size)) return -1;
     if (stats) *stats = lnb_spec_stats{};
     if (c->sp_max_draft == 0) {                              // drafting off: the greedy (the sampling) loop itself, one pass per token
@@ -3267,10 +3427,10 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
     const int n_text = n_history + 1;
     if (smp && !c->d_smp) HIPCHK(dev_alloc(c->d_smp, sizeof(LnbSampler)));
     if (rc && !c->rl.d_rules) HIPCHK(dev_alloc(c->rl.d_rules, sizeof(LnbRulesDev)));
-    const GraphLaunch launch = rc ? GL_SAMPLE_RULES : smp ? GL_SAMPLE : GL_GREEDY;
+    const GraphLaunch launch = rc ? (emit ? GL_SAMPLE_RULES_EMIT : GL_SAMPLE_RULES) : smp ? (emit ? GL_SAMPLE_EMIT : GL_SAMPLE) : GL_GREEDY;
     if (spec_alloc(c, n_text) || capture_decode_graphs(c, start_pos, max_steps, launch)) return -1;
     hipStream_t st = c->stream;
-    c->tp_last_k = 0; c->tp_last_n = 0;
+    c->tp_last_k = 0; c->tp_last_n = 0; c->em_last_k = -1; c->em_last_n = 0;
     if (smp) HIPCHK(hipMemcpyAsync(c->d_smp, smp, sizeof(LnbSampler), hipMemcpyHostToDevice, st));       // (the captured graphs hold the pointer: another sampler replays them)
     if (rc) {                                                // the tables of the counted text; the device rules are what every rules graph points at
         if (rules_tables(c, rc->rules, rc->counted, rc->n_counted, token, st, &c->rl.h_rules)) return -1;
@@ -3329,6 +3489,7 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
     if (err) return fail("generated token id is outside the vocabulary");
     *n_generated = n_out;
     if (finished) *finished = fin;
+    if (emit) { c->em_last_k = c->emit_k; c->em_last_n = n_out; }
     s.accepted = (int64_t)n_out - s.passes;                  // every pass emits its column 0 token plus the drafts it accepted
     if (stats) *stats = s;
     return 0;
@@ -3466,6 +3627,7 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
         const lnb_ctx* c = ctxs[s];
         if (c->mode != LNB_MODE_EXACT) return fail("%s: context %d is in the tolerance mode: the call is exact-mode only", name, s);
         if (c->top_k > 0) return fail("%s: context %d records token probabilities, which the call does not: lnb_ctx_set_token_probs(ctx, 0) first", name, s);
+        if (c->emit_k >= 0) return fail("%s: context %d %s", name, s, k_emit_advice);
         if (c->pending) return fail("%s: context %d: a lnb_forward_stage_begin has not been ended", name, s);
         if (c->batch_users > 0) return fail("%s: context %d is a member of %d live batch(es): lnb_batch_destroy first", name, s, c->batch_users);
         if (max_steps > c->dout_cap) return fail("%s: member %d: max_steps %d exceeds its token log of %d", name, s, max_steps, c->dout_cap);
@@ -3840,6 +4002,7 @@ extern "C" int lnb_pipeline_tick(lnb_pipe* p, lnb_ctx* run, int run_rows, int ru
     if (recv && recv_rows > recv->max_rows) return fail("a hand-off of %d rows into a context whose activation buffers hold %d rows (lnb_ctx_create_long's max_rows)", recv_rows, recv->max_rows);
     if (run) {
         if (run->top_k > 0) return fail("the context records token probabilities, which pipeline ticks do not support (lnb_ctx_set_token_probs(ctx, 0))");
+        if (run->emit_k >= 0) return fail("lnb_pipeline_tick: the context %s", k_emit_advice);
         if (check_call(run, run_rows, run_pos)) return -1;
         if (run_tokens && !first) return fail("tokens given to a stage that does not own tok_embeddings");
         if (!run_tokens && first && run_rows != 1) return fail("the first stage needs host tokens for a multi-row step");
@@ -3874,6 +4037,7 @@ extern "C" int lnb_pipeline_tick_batch(lnb_pipe* p, lnb_batch* run, lnb_batch* s
     if (token_slot_out) *token_slot_out = -1;
     if (run) {
         if (run->top_k > 0) return fail("the batch's contexts record token probabilities, which pipeline ticks do not support (lnb_ctx_set_token_probs(ctx, 0))");
+        if (run->emit_k >= 0) return fail("lnb_pipeline_tick_batch: every context of the batch %s", k_emit_advice);
         if (run->sp_src) return fail("the batch has a shared prefix (lnb_batch_set_shared_prefix): pipeline ticks do not run the shared attention form; clear it first");
         hipStream_t st = run->stream;
         if (run->link.await(st, "batch")) return -1;
@@ -4227,6 +4391,82 @@ extern "C" int lnb_op_sample_rules(int device, const uint16_t* logits_bf16, int 
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(tokens_out, b + o_t, R * 4, hipMemcpyDeviceToHost));
     if (info) HIPCHK(hipMemcpy(info, b + o_i, R * sizeof(LnbSampleInfo), hipMemcpyDeviceToHost));
+    return 0;
+}
+// the emitted token's record on host rows (test aid): the row summary launch, then the token launch with the emitted entry -- row i with samplers[i] at
+// pos[i] (or u = draws[i]), under rules[i] and the counts row i when rules is given (counts NULL: all zero).  Any output but tokens_out may be NULL.
+extern "C" int lnb_op_emitted_probs(int device, const uint16_t* logits_bf16, int rows, int V, int top_k, const lnb_sampler* samplers, const lnb_logit_rules* rules,
+                                    const uint32_t* counts, const int32_t* pos, const uint64_t* draws, int force_serial, int32_t* tokens_out, float* tok_logit,
+                                    float* tok_prob, double* log_z, uint64_t* w_tok, uint64_t* w_kept, int32_t* ids, float* logits, float* probs, int* serial_walks) {
+    if (!logits_bf16 || !samplers || !pos || !tokens_out) return fail("null argument");
+    if (rows <= 0) return fail("empty operand");
+    if (top_k < 0 || top_k > LNB_MAX_TOP_K) return fail("top_k must be 0..%d (got %d)", LNB_MAX_TOP_K, top_k);
+    if (sample_vocab_check(V)) return -1;
+    char who[32];
+    bool any_bias = false;
+    for (int i = 0; i < rows; i++) {
+        snprintf(who, sizeof who, "row %d: ", i);
+        if (sampler_check(samplers + i, who) || (rules && rules_check(rules + i, nullptr, 0, V, who))) return -1;
+        any_bias = any_bias || (rules && rules[i].n_bias > 0);
+    }
+    if (op_device(device)) return -1;
+    const size_t R = rows, K = std::max(top_k, 1), G = lnb_tokprob_slices(rows);
+    std::vector<double> et; prob_exp_table(et);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    const size_t o_et = take(65536 * 8), o_x = take(R * V * 2 + 16), o_s = take(R * sizeof(LnbSampler)), o_p = take(R * 4), o_u = take(R * 8), o_t = take(R * 4),
+                 o_r = take(R * sizeof(LnbRulesDev)), o_c = take(rules ? R * V * 4 : 4), o_b = take(any_bias ? R * V * 2 : 2), o_out = take(sizeof(TokProbOut)),
+                 o_log = take(sizeof(EmitLog)), o_z = take(R * LNB_TOKPROB_MAX_G * 8), o_k = take(R * G * K * 8), o_cnt = take(R * 4), o_pk = take(R * sizeof(EmitPark)),
+                 o_tl = take(R * 4), o_tp = take(R * 4), o_lz = take(R * 8), o_w = take(R * 16), o_ids = take(R * K * 4), o_lg = take(R * K * 4), o_pr = take(R * K * 4),
+                 o_wk = take(4);
+    Dev<char> buf;
+    HIPCHK(dev_alloc(buf, off));
+    char* const b = buf;
+    std::vector<LnbRulesDev> hr(rules ? R : 0);
+    std::vector<uint16_t> hb(any_bias ? R * V : 0, (uint16_t)0);
+    for (size_t i = 0; i < hr.size(); i++) {
+        const lnb_logit_rules& r = rules[i];
+        for (int k = 0; k < r.n_bias; k++) hb[i * V + r.bias_ids[k]] = bf_trunc_h(r.bias_values[k]);
+        hr[i] = LnbRulesDev{r.repetition_penalty, r.presence_penalty, r.frequency_penalty, r.min_p, (lnbs_u32*)(b + o_c) + i * V,
+                            r.n_bias > 0 ? (const lnbs_u16*)(b + o_b) + i * V : nullptr};
+    }
+    TokProbOut o{}; o.ids = (int32_t*)(b + o_ids); o.logit = (float*)(b + o_lg); o.prob = (float*)(b + o_pr); o.log_z = (double*)(b + o_lz); o.walks = (int*)(b + o_wk); o.cap = rows;
+    const EmitLog lg{(float*)(b + o_tl), (float*)(b + o_tp), (double*)(b + o_lz), (unsigned long long*)(b + o_w), o.ids, o.logit, o.prob, (int*)(b + o_wk), rows, top_k};
+    HIPCHK(hipMemset(b, 0, off));                            // (tickets, the walk counter, the counts when none are given)
+    HIPCHK(hipMemcpy(b + o_et, et.data(), 65536 * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_x, logits_bf16, R * V * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_s, samplers, R * sizeof(LnbSampler), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_p, pos, R * 4, hipMemcpyHostToDevice));
+    if (draws) HIPCHK(hipMemcpy(b + o_u, draws, R * 8, hipMemcpyHostToDevice));
+    if (rules) HIPCHK(hipMemcpy(b + o_r, hr.data(), R * sizeof(LnbRulesDev), hipMemcpyHostToDevice));
+    if (rules && counts) HIPCHK(hipMemcpy(b + o_c, counts, R * V * 4, hipMemcpyHostToDevice));
+    if (any_bias) HIPCHK(hipMemcpy(b + o_b, hb.data(), R * V * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_out, &o, sizeof o, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_log, &lg, sizeof lg, hipMemcpyHostToDevice));
+    TokProbParams p{};
+    p.logits = (const uint16_t*)(b + o_x); p.V = V; p.rows = rows; p.k = top_k; p.G = (int)G; p.etab = (const double*)(b + o_et);
+    p.zpart = (double*)(b + o_z); p.kpart = (uint64_t*)(b + o_k); p.cnt = (unsigned*)(b + o_cnt); p.out = (const TokProbOut*)(b + o_out); p.per_row_out = 0;
+    p.force_serial = force_serial ? 1 : 0; p.park = (EmitPark*)(b + o_pk);
+    HIPCHK(lnbk_emit_summary(&p, nullptr));
+    EmitTokParams t{};
+    t.logits = p.logits; t.V = V; t.etab = p.etab; t.smp = (const LnbSampler*)(b + o_s); t.rules = rules ? (const LnbRulesDev*)(b + o_r) : nullptr;
+    t.next_token = (int32_t*)(b + o_t); t.op_pos = (const int32_t*)(b + o_p); t.op_draws = draws ? (const unsigned long long*)(b + o_u) : nullptr;
+    t.park = p.park; t.log = (const EmitLog*)(b + o_log);
+    HIPCHK(lnbk_emit_sample(&t, rows, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(tokens_out, b + o_t, R * 4, hipMemcpyDeviceToHost));
+    if (tok_logit) HIPCHK(hipMemcpy(tok_logit, b + o_tl, R * 4, hipMemcpyDeviceToHost));
+    if (tok_prob) HIPCHK(hipMemcpy(tok_prob, b + o_tp, R * 4, hipMemcpyDeviceToHost));
+    if (log_z) HIPCHK(hipMemcpy(log_z, b + o_lz, R * 8, hipMemcpyDeviceToHost));
+    if (w_tok || w_kept) {
+        std::vector<uint64_t> w(R * 2);
+        HIPCHK(hipMemcpy(w.data(), b + o_w, R * 16, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < R; i++) { if (w_tok) w_tok[i] = w[2 * i]; if (w_kept) w_kept[i] = w[2 * i + 1]; }
+    }
+    if (top_k > 0 && ids) HIPCHK(hipMemcpy(ids, b + o_ids, R * top_k * 4, hipMemcpyDeviceToHost));
+    if (top_k > 0 && logits) HIPCHK(hipMemcpy(logits, b + o_lg, R * top_k * 4, hipMemcpyDeviceToHost));
+    if (top_k > 0 && probs) HIPCHK(hipMemcpy(probs, b + o_pr, R * top_k * 4, hipMemcpyDeviceToHost));
+    if (serial_walks) HIPCHK(hipMemcpy(serial_walks, b + o_wk, 4, hipMemcpyDeviceToHost));
     return 0;
 }
 // spec_sample_commit_kernel on host rows (test aid): the w columns of a verify pass whose column i holds logits row i, takes col_tokens[i] and sits at

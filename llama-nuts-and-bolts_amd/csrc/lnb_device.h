@@ -301,9 +301,43 @@ struct TokProbParams {
     const TokProbOut* out; int per_row_out;    // out[row] (a batch: one context per row) or out[0] for every row
     const int32_t* targets; float* tlogit; float* tprob;   // scoring: [rows] (targets nullptr: no target)
     int force_serial;                          // every row walks the serial sum (tests)
+    struct EmitPark* park;                     // the PARK instantiations only (lnb_emit_probs.h): [rows] the row's certified Z state for the token launch; else nullptr
 };
 // slices per row: a power of two (it divides LNB_TOKPROB_MAX_G, the sub-slices of the sum), about 2048 workgroups in all
 LNB_HD int lnb_tokprob_slices(int rows) { int g = LNB_TOKPROB_MAX_G; while (g > 1 && (long)g * rows > 2048) g >>= 1; return g; }
+
+// ---- the emitted token's record (lnb_ctx_set_emitted_probs; lnb_emit_probs.h) ------------------------------------------------------------
+// The row summary launch (token_probs_kernel's PARK instantiations) runs BEFORE the token launch and cannot know the token: it writes the row's top k and
+// parks what the token launch needs to certify f32(e_t / Z) itself -- the estimate zt, whether the row already walked the serial sum, and the walked Z.
+struct EmitPark { double zt, z; int32_t walked, pad; };
+struct EmitLog {                               // one context's record log (or, cap = rows, the rows of lnb_op_emitted_probs)
+    float* tok_logit; float* tok_prob;         // [cap]
+    double* log_z;                             // [cap]
+    unsigned long long* w;                     // [cap][2] = {w_tok, w_kept}
+    int32_t* ids; float* logit; float* prob;   // [cap][k]: written by the summary launch (a verify pass: copied from the pass scratch by the commit)
+    int* walks;                                // rows that walked the serial sum (the context's counter; may be nullptr)
+    int32_t cap, k;
+};
+// the token launch with the emitted entry: one row / rows of lnb_op_emitted_probs (tab nullptr) or one workgroup per member of a batch (tab)
+struct EmitTokParams {
+    const uint16_t* logits; int V; const double* etab;
+    const struct LnbSampler* smp; const struct LnbRulesDev* rules;     // [rows] / [members]; rules: the RULES instantiations
+    int32_t* next_token; StepState* st; int32_t* out_tokens; int out_cap, advance;      // as sample_kernel's
+    const int32_t* op_pos; const unsigned long long* op_draws;
+    const BatchTab* tab;
+    const EmitPark* park;                      // [rows] / [members]
+    const EmitLog* log; int per_row_log;       // log[member] (a batch) or log[0]
+};
+// the verify pass's token launch with records: spec_sample_commit_kernel's arguments, the pass scratch the summary launch filled and the context's log
+struct EmitSpecParams {
+    const uint16_t* logits; int V; const double* etab;
+    const struct LnbSampler* smp; const struct LnbRulesDev* rules;
+    int32_t* g; unsigned long long* gw;        // [16] the columns' tokens, [16][2] their {w_tok, w_kept}
+    const BatchTab* tab; unsigned* cnt;
+    const EmitPark* park;                      // [16] per column
+    const int32_t* s_ids; const float* s_logit; const float* s_prob;   // [16][k] the columns' top k
+    const EmitLog* log;
+};
 
 // ---- speculative greedy decoding (lnb_decode_speculative_until; ngram_draft_kernel, spec_commit_kernel) ---------------------------------
 // A verify pass is a batched decode step of w = draft_len + 1 columns that all alias ONE context: column i takes d_i at position pos + i,

@@ -77,6 +77,11 @@
     /* the same token launches under logit rules (lnb_decode_sample_rules_until: step 0 in the row load, step 4b in the probe) */ \
     X(SAMPLE_RULES_ROW, "sample.rules_row", "sample_rules_kernel: one workgroup per logits row with its counts and bias tables -- the one-token rules step, rows of lnb_op_sample_rules") \
     X(SAMPLE_RULES_BATCH, "sample.rules_batch", "batch_sample_rules_kernel: one workgroup per member of a batched rules step, each with its own sampler, rules and tables") \
+    /* the emitted token's record (lnb_ctx_set_emitted_probs; lnb_emit_probs.h): never launched while the switch is off */ \
+    X(EMIT_SUMMARY, "emit.summary", "token_probs_kernel<KT, PARK>: the row summary launch -- the raw row's top k into the record slot (a verify pass: all columns at once into the pass scratch), the row's Z state parked for the token launch") \
+    X(EMIT_ROW, "emit.row", "emit_sample_kernel<RULES, false>: the one-token sampling (rules) step with the emitted entry, rows of lnb_op_emitted_probs") \
+    X(EMIT_BATCH, "emit.batch", "emit_sample_kernel<RULES, true>: one workgroup per member of a batched sampling (rules) step, each recording into its own context's log") \
+    X(EMIT_SPEC, "emit.spec", "emit_spec_commit_kernel<RULES>: one workgroup per column of a verify pass; the last one accepts, emits and records the emitted columns in order") \
     /* the tolerance mode (lnb_fast.hip: launch_a, launch_b, launch_gemm_fast, lnbk_fast_attn) */ \
     X(FAST_GEMV_A_RG8, "fast_gemv_a.rg8", "fast_gemv_a<*, *, *, 8>: split-K GEMV over a chain layout, 8 rows per work unit (few units, LNB_FAST_RG=8)") \
     X(FAST_GEMV_A_RG16, "fast_gemv_a.rg16", "the same, 16 rows per work unit") \

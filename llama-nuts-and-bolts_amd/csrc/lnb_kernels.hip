@@ -4057,6 +4057,7 @@ struct SampleSh {
     unsigned tie0;
     int owner, tok;
     LnbSampleInfo z;                                         // filled as the sums become known (thread 0), copied out at the end
+    unsigned long long w_tok;                                // EMIT: the token's own weight w_t (0: greedy, degenerate, no candidate)
 };
 // (a reduction's result is the same in every lane: saying so keeps everything the thresholds are computed from in scalar registers)
 DEVINL unsigned sample_uniform(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
@@ -4197,12 +4198,14 @@ DEVINL void sample_rules_group(const uint16_t* x, const LnbRulesDev& ru, bool al
 // -> the token, valid in thread 0, and sh.z = the row's info.  has_u: pos_or_u is u of step 8 itself.  RULES: the row is adjusted by ru's step 0 as it
 // is loaded, S is step 4b's, and temperature 0 = the first maximum of the adjusted row (steps 1-3); without it the code is the plain sampler's, token for token.
 // DELTA (with RULES): the counts are the table's plus the drafts of *dl (LDS, written and fenced by a barrier before the call) -- see sample_rules_group.
-template <bool RULES = false, bool DELTA = false>
+// EMIT (lnb_emit_probs.h): sh.w_tok = the token's weight w_t of step 4 (4b) beside sh.z.w_kept = W_K -- the sampler's own probability of the token.
+template <bool RULES = false, bool DELTA = false, bool EMIT = false>
 DEVINL int sample_block(const uint16_t* x, int V, const double* etab, const LnbSampler& s, bool has_u, unsigned long long pos_or_u, SampleSh& sh,
                         const LnbRulesDev* rules = nullptr, const SpecDelta* dl = nullptr) {
     const int tid = threadIdx.x;
     int par = 0;
     if (tid == 0) { const LnbSampleInfo z0 = {0, 0, 0, 0, 0, 0, 0}; sh.z = z0; }      // (read back by thread 0 only)
+    if constexpr (EMIT) { if (tid == 0) sh.w_tok = 0; }      // (every way out lies behind a barrier)
     const float T = RULES && s.temperature == 0.0f ? 1.0f : s.temperature;
     const int per = (((V + 1023) >> 10) + 7) & ~7;
     // the row, once: scaled (step 1), keyed (steps 2 and 5), packed
@@ -4375,7 +4378,7 @@ DEVINL int sample_block(const uint16_t* x, int V, const double* etab, const LnbS
         const bool member = tid < per && (k > t2 || (k == t2 && rank < m2));
         const unsigned long long wv = member ? sample_key_weight(etab, k, E) : 0;
         const unsigned long long exv = sh.ex + sample_wg_scan(sh, par, wv, tt);
-        if (member && exv <= r && r < exv + wv) sh.tok = sh.owner * per + tid;
+        if (member && exv <= r && r < exv + wv) { sh.tok = sh.owner * per + tid; if constexpr (EMIT) sh.w_tok = wv; }
     }
     __syncthreads();
     return sh.tok;
@@ -4747,7 +4750,8 @@ DEVINL double tp_zseq_wave(const uint16_t* x, int V, const double* etab) {
     }
     return z;
 }
-template <int KT> __global__ __launch_bounds__(256) void token_probs_kernel(TokProbParams p) {
+// PARK (the row summary launch of lnb_emit_probs.h): the row's Z state is also parked in p.park[row] for the token launch that follows
+template <int KT, bool PARK = false> __global__ __launch_bounds__(256) void token_probs_kernel(TokProbParams p) {
     constexpr int KA = KT > 0 ? KT : 1;                      // (KT = 0: scoring only, no top-k)
     __shared__ uint64_t sk[4 * KA];
     __shared__ double sz[4 * LNB_TOKPROB_MAX_G];
@@ -4859,11 +4863,13 @@ template <int KT> __global__ __launch_bounds__(256) void token_probs_kernel(TokP
     float pr = 0.0f;
     if (id >= 0) pr = cert_p32(e, cz, bad);
     double z = zt;
-    if (__any(bad)) {
+    const bool walk = __any(bad);
+    if (walk) {
         z = tp_zseq_wave(x, V, p.etab);
         if (id >= 0) pr = (float)(e / z);
         if (lane == 0 && o.walks) atomicAdd(o.walks, 1);
     }
+    if constexpr (PARK) { if (lane == 0) p.park[row] = EmitPark{zt, z, walk ? 1 : 0, 0}; }
     const float qnan = __uint_as_float(0x7FC00000u);
     if (lane < k) {
         const size_t at = (size_t)slot * k + lane;
@@ -4981,6 +4987,7 @@ __global__ void wpack_pack_head_kernel(const uint16_t* w, char* out, int N, int 
 #include "lnb_batch_kernels.h"
 #include "lnb_knobs.h"
 #include "lnb_forms.h"
+#include "lnb_emit_probs.h"
 
 // ------------------------------------------------------------------------------------------------
 // host-side launchers (called from lnb_api.cpp)

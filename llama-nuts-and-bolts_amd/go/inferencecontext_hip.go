@@ -575,6 +575,52 @@ func (ic *InferenceContext) SetTokenProbs(lt *LlamaTransformer, topK int) error 
 	return nil
 }
 
+// EmittedProbs is the record of the tokens a sampling or speculative loop emitted (include/lnb.h: lnb_ctx_set_emitted_probs): per token its own logit
+// and probability, ln Z and the sampler's probability of it as WTok / WKept; Ids, Logits and Probs [n*K] are the RAW row's top K.
+type EmittedProbs struct {
+	TokLogit, TokProb []float32
+	LogZ              []float64
+	WTok, WKept       []uint64
+	Ids               []TokenId
+	Logits, Probs     []float32
+	K                 int
+}
+
+// SetEmittedProbs switches the record on (topK 0..LNB_MAX_TOP_K) or off (-1, the default).  It excludes SetTokenProbs.
+func (ic *InferenceContext) SetEmittedProbs(lt *LlamaTransformer, topK int) error {
+	if err := ic.attach(lt); err != nil {
+		return err
+	}
+	return lnbCall(func() C.int { return C.lnb_ctx_set_emitted_probs(ic.handle, C.int(topK)) })
+}
+
+// ReadEmittedProbs returns records [first, first+n) of the last sampling or speculative call.
+func (ic *InferenceContext) ReadEmittedProbs(first int, n int) (*EmittedProbs, error) {
+	if ic.handle == nil {
+		return nil, fmt.Errorf("inference context is closed")
+	}
+	var lastK, lastN C.int // K is the recording call's
+	if err := lnbCall(func() C.int { return C.lnb_ctx_emitted_probs_last(ic.handle, &lastK, &lastN) }); err != nil {
+		return nil, err
+	}
+	k := int(lastK)
+	if k < 0 {
+		k = 0
+	}
+	r := &EmittedProbs{TokLogit: make([]float32, n+1), TokProb: make([]float32, n+1), LogZ: make([]float64, n+1), WTok: make([]uint64, n+1), WKept: make([]uint64, n+1),
+		Ids: make([]TokenId, n*k+1), Logits: make([]float32, n*k+1), Probs: make([]float32, n*k+1), K: k}
+	if err := lnbCall(func() C.int {
+		return C.lnb_ctx_read_emitted_probs(ic.handle, C.int(first), C.int(n), (*C.float)(unsafe.Pointer(&r.TokLogit[0])), (*C.float)(unsafe.Pointer(&r.TokProb[0])),
+			(*C.double)(unsafe.Pointer(&r.LogZ[0])), (*C.uint64_t)(unsafe.Pointer(&r.WTok[0])), (*C.uint64_t)(unsafe.Pointer(&r.WKept[0])),
+			(*C.int32_t)(unsafe.Pointer(&r.Ids[0])), (*C.float)(unsafe.Pointer(&r.Logits[0])), (*C.float)(unsafe.Pointer(&r.Probs[0])))
+	}); err != nil {
+		return nil, err
+	}
+	r.TokLogit, r.TokProb, r.LogZ, r.WTok, r.WKept = r.TokLogit[:n], r.TokProb[:n], r.LogZ[:n], r.WTok[:n], r.WKept[:n]
+	r.Ids, r.Logits, r.Probs = r.Ids[:n*k], r.Logits[:n*k], r.Probs[:n*k]
+	return r, nil
+}
+
 // TokenProbs returns records [first, first+n) of the last greedy call: ids, logits and probs [n*k] (entry i*k is the generated token) and
 // ln Z [n] of each row.
 func (ic *InferenceContext) TokenProbs(first int, n int) (ids []TokenId, logits []float32, probs []float32, logZ []float64, err error) {

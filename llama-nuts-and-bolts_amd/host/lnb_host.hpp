@@ -212,6 +212,25 @@ public:
         r.Ids.resize((size_t)n * topK_); r.Logits.resize(r.Ids.size()); r.Probs.resize(r.Ids.size()); r.LogZ.resize(n);
         return r;
     }
+    // lnb_ctx_set_emitted_probs / lnb_ctx_read_emitted_probs: the record of every token the sampling and speculative loops emit (topK -1: off)
+    void SetEmittedProbs(int topK) { check(lnb_ctx_set_emitted_probs(h_, topK)); }
+    struct EmittedProbs {                                    // [n]; Ids / Logits / Probs: [n * K], the RAW row's top K
+        std::vector<float> TokLogit, TokProb; std::vector<double> LogZ; std::vector<uint64_t> WTok, WKept;
+        std::vector<int32_t> Ids; std::vector<float> Logits, Probs; int K = 0;
+    };
+    EmittedProbs ReadEmittedProbs(int n, int first = 0) const {
+        EmittedProbs r;
+        int lastK = -1, lastN = 0;                           // K is the recording call's, not this object's memory of the switch
+        check(lnb_ctx_emitted_probs_last(h_, &lastK, &lastN));
+        r.K = lastK > 0 ? lastK : 0;
+        const size_t N = (size_t)n, NK = N * r.K;
+        r.TokLogit.resize(N + 1); r.TokProb.resize(N + 1); r.LogZ.resize(N + 1); r.WTok.resize(N + 1); r.WKept.resize(N + 1);
+        r.Ids.resize(NK + 1); r.Logits.resize(NK + 1); r.Probs.resize(NK + 1);
+        check(lnb_ctx_read_emitted_probs(h_, first, n, r.TokLogit.data(), r.TokProb.data(), r.LogZ.data(), r.WTok.data(), r.WKept.data(), r.Ids.data(),
+                                         r.Logits.data(), r.Probs.data()));
+        r.TokLogit.resize(N); r.TokProb.resize(N); r.LogZ.resize(N); r.WTok.resize(N); r.WKept.resize(N); r.Ids.resize(NK); r.Logits.resize(NK); r.Probs.resize(NK);
+        return r;
+    }
     // lnb_forward_score: Forward reporting each row's target logit / probability and ln Z instead of the logits (targets[i] < 0: NaN)
     struct Score { std::vector<float> TargetLogit, TargetProb; std::vector<double> LogZ; TokenId ArgmaxLast = -1; };
     Score ScoreTokens(const std::vector<TokenId>& tokens, int startPos, const std::vector<TokenId>& targets) {

@@ -83,6 +83,7 @@ EXPORTS = [
     "lnb_form_count", "lnb_form_count_reset", "lnb_form_name",
     "lnb_op_rmsnorm_sum",
     "lnb_ctx_attention",
+    "lnb_ctx_set_emitted_probs", "lnb_ctx_read_emitted_probs", "lnb_ctx_emitted_probs_last", "lnb_op_emitted_probs",
 ]
 EPILOGUES = {"store": 0, "qkv_rope": 1, "resid": 2, "silu_mul": 3}      # EPI_* of csrc/lnb_device.h: the second index of the launch tally
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
@@ -295,6 +296,10 @@ def lib():
     L.lnb_op_exp_table.argtypes = [C.c_int, C.c_float, vp]
     L.lnb_ctx_set_token_probs.argtypes = [vp, C.c_int]
     L.lnb_ctx_read_token_probs.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.lnb_ctx_set_emitted_probs.argtypes = [vp, C.c_int]
+    L.lnb_ctx_read_emitted_probs.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lnb_ctx_emitted_probs_last.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.lnb_op_emitted_probs.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.lnb_ctx_token_prob_walks.argtypes = [vp, C.POINTER(C.c_int)]
     L.lnb_forward_score.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, i32p]
     L.lnb_forward_append.argtypes = [vp, vp, C.c_int, C.c_int, vp, i32p]
@@ -828,6 +833,25 @@ class InferenceContext:
         _chk(self.L.lnb_ctx_read_token_probs(self.h, int(first), int(n), _p(ids), _p(lg), _p(pr), _p(lz)))
         return ids[:, :k], lg[:, :k], pr[:, :k], lz[:n]
 
+    def set_emitted_probs(self, k):
+        """record, for every token the sampling and speculative loops emit, the token's own logit and probability, ln Z, the raw row's top k (0..MAX_TOP_K)
+        and the sampler's probability of it as w_tok / w_kept (lnb_ctx_set_emitted_probs); -1 = off, the default"""
+        _chk(self.L.lnb_ctx_set_emitted_probs(self.h, int(k)))
+        return self
+
+    def read_emitted_probs(self, n=None, first=0):
+        """records [first, first + n) of the last sampling / speculative call (n None: all behind first) -> dict of tok_logit / tok_prob f32 [n], log_z f64 [n],
+        w_tok / w_kept uint64 [n], ids int32 / logits f32 / probs f32 [n, k] (the RAW row's top k: ids[:, 0] is the row's argmax, not necessarily the token);
+        k is the top_k that call recorded with (lnb_ctx_emitted_probs_last)"""
+        lk, ln = C.c_int(-1), C.c_int(0)
+        _chk(self.L.lnb_ctx_emitted_probs_last(self.h, C.byref(lk), C.byref(ln)))
+        k, n = max(lk.value, 0), max(ln.value - int(first), 0) if n is None else int(n)
+        r = dict(tok_logit=np.empty(n, np.float32), tok_prob=np.empty(n, np.float32), log_z=np.empty(n, np.float64), w_tok=np.empty(n, np.uint64),
+                 w_kept=np.empty(n, np.uint64), ids=np.empty((n, k), np.int32), logits=np.empty((n, k), np.float32), probs=np.empty((n, k), np.float32))
+        ptr = lambda a: _p(a) if a.size else None
+        _chk(self.L.lnb_ctx_read_emitted_probs(self.h, int(first), n, *[ptr(r[f]) for f in ("tok_logit", "tok_prob", "log_z", "w_tok", "w_kept", "ids", "logits", "probs")]))
+        return r
+
     def set_draft(self, max_draft, ngram_min=1, ngram_max=4, corpus=()):
         """n-gram drafts for decode_speculative_until: up to max_draft (0..MAX_DRAFT; 0 = off, the default) tokens per pass, looked up with
         n-grams of ngram_min..ngram_max tokens in the running text, then in corpus (copied to the device)"""
@@ -1215,7 +1239,7 @@ class InferenceEngine:
     long_context: the generation's context is a long one (lnb_ctx_create_long, up to MAX_SEQ_LEN positions) whose activation buffers hold
     prefill_chunk rows, or the prompt when the chunk is 0."""
 
-    def __init__(self, transformer, seq_len, stop_token_ids=(), prefill_chunk=0, long_context=False, sampler=None, draft=None, rules=None):
+    def __init__(self, transformer, seq_len, stop_token_ids=(), prefill_chunk=0, long_context=False, sampler=None, draft=None, rules=None, emitted_probs=None):
         if int(prefill_chunk) < 0:
             raise LnbError("prefill_chunk must be 0 (one Forward) or a positive row count")
         self.t, self.seq_len, self.stop, self.prefill_chunk = transformer, seq_len, set(stop_token_ids), int(prefill_chunk)
@@ -1224,7 +1248,10 @@ class InferenceEngine:
         # rules (a LogitRules or its argument tuple): logit bias, penalties and min-p on every generated token; the counted text is the prompt plus what has
         # been generated.  Without a sampler the rules run greedy (temperature 0 = the argmax of the adjusted row).
         self.rules = rules
-        if rules is not None and self.sampler is None:
+        # emitted_probs = k (0..MAX_TOP_K): GenerateTokens returns (tokens, records) -- record i = InferenceContext.read_emitted_probs's fields for tokens[i].
+        # The records belong to the sampling loops: without a sampler they run at temperature 0 (the greedy tokens).
+        self.emitted_probs = None if emitted_probs is None else int(emitted_probs)
+        if (rules is not None or self.emitted_probs is not None) and self.sampler is None:
             self.sampler = Sampler(0.0)
         if draft is not None and len(tuple(draft)) != 3:
             raise LnbError("draft must be None or (max_draft, ngram_min, ngram_max)")
@@ -1250,7 +1277,14 @@ class InferenceEngine:
                 # (the same bits into the same KV row) for its logits, then sample_kernel on that row
                 row, _ = ctx.ForwardAppend(prompt[-1:], len(prompt) - 1, want_logits=True)
                 row16 = (np.ascontiguousarray(row[0], dtype=np.float32).view(np.uint32) >> 16).astype(np.uint16)
-                if self.rules is None:
+                if self.emitted_probs is not None:           # the same token with its record, from the same row
+                    counts = None if self.rules is None else np.bincount(np.asarray(prompt, dtype=np.int64), minlength=row16.size).astype(np.uint32)
+                    recs = [op_emitted_probs(row16, self.emitted_probs, [self.sampler], [len(prompt) - 1], rules=None if self.rules is None else [self.rules],
+                                             counts=counts, device=self.t.device)]
+                    first = int(recs[0].pop("tokens")[0])
+                    recs[0].pop("serial_walks")
+                    ctx.set_emitted_probs(self.emitted_probs)
+                elif self.rules is None:
                     first = int(op_sample(row16, [self.sampler], [len(prompt) - 1], want_info=False, device=self.t.device)[0][0])
                 else:                                        # the counted text of that step is the prompt
                     counts = np.bincount(np.asarray(prompt, dtype=np.int64), minlength=row16.size).astype(np.uint32)
@@ -1274,6 +1308,10 @@ class InferenceEngine:
                     out.append(int(t))
                     if int(t) in self.stop:
                         break
+                if self.emitted_probs is not None:
+                    recs.append(ctx.read_emitted_probs(len(out) - 1))
+            if self.emitted_probs is not None:
+                return out, {f: np.concatenate([r[f] for r in recs]) for f in recs[0]}
             return out
         finally:
             ctx.close()
@@ -1354,6 +1392,33 @@ def op_sample_rules(logits_u16, samplers, rules, counts, pos, draws=None, want_i
     info = (SampleInfo * rows)() if want_info else None
     _chk(lib().lnb_op_sample_rules(device, _p(a), rows, V, ss, rr, None if c is None else _p(c), _p(p), None if u is None else _p(u), _p(tok), info))
     return tok, ([i.as_dict() for i in info] if want_info else None)
+
+
+def op_emitted_probs(logits_u16, top_k, samplers, pos, draws=None, rules=None, counts=None, force_serial=False, device=0):
+    """the emitted token's record on rows of bf16 logits [rows, V] (lnb_op_emitted_probs): the row summary launch, then the token launch with the emitted entry --
+    row i with samplers[i] at pos[i] (or u = draws[i]); rules (a list of LogitRules / tuples / None per row) with counts (uint32 [rows, V]; None: zero) picks the
+    rules form -> dict of tokens, tok_logit, tok_prob, log_z, w_tok, w_kept [rows], ids / logits / probs [rows, k], serial_walks"""
+    a = np.ascontiguousarray(logits_u16, dtype=np.uint16)
+    if a.ndim == 1:
+        a = a[None, :]
+    rows, V = a.shape
+    k = int(top_k)
+    ss = _samplers(samplers, rows)
+    rr, _keep = (None, None) if rules is None else _rules(rules, rows)
+    c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32).reshape(rows, V)
+    p = np.ascontiguousarray(pos, dtype=np.int32)
+    u = None if draws is None else np.array([int(d) & 0xFFFFFFFFFFFFFFFF for d in draws], dtype=np.uint64)
+    if p.size != rows or (u is not None and u.size != rows):
+        raise LnbError("%d rows, %d positions%s" % (rows, p.size, "" if u is None else ", %d draws" % u.size))
+    r = dict(tokens=np.full(rows, -2, np.int32), tok_logit=np.empty(rows, np.float32), tok_prob=np.empty(rows, np.float32), log_z=np.empty(rows, np.float64),
+             w_tok=np.empty(rows, np.uint64), w_kept=np.empty(rows, np.uint64), ids=np.empty((rows, k), np.int32), logits=np.empty((rows, k), np.float32),
+             probs=np.empty((rows, k), np.float32))
+    walks = C.c_int(0)
+    _chk(lib().lnb_op_emitted_probs(device, _p(a), rows, V, k, ss, rr, None if c is None else _p(c), _p(p), None if u is None else _p(u), 1 if force_serial else 0,
+                                    *[_p(r[f]) if r[f].size else None for f in ("tokens", "tok_logit", "tok_prob", "log_z", "w_tok", "w_kept", "ids", "logits", "probs")],
+                                    C.byref(walks)))
+    r["serial_walks"] = walks.value
+    return r
 
 
 def op_token_probs(logits_u16, top_k, targets=None, force_serial=False, device=0):

@@ -190,7 +190,12 @@ def main(asm_path=None):
     # (spec_sample_rules_commit_kernel / spec_many_sample_rules_commit_kernel: the rules' row load with the draft delta; figures in profiles/spec_rules.md)
     SGPR_SPILL_OK = ("attn_gqa_kernel", "attn_one_kernel", "_Z13sample_kernelP", "_Z19batch_sample_kernelP",      # (these two kernels and no other *sample_kernel)
                      "_Z25spec_sample_commit_kernelP", "_Z30spec_many_sample_commit_kernel6SmPass", "_Z19sample_rules_kernelP", "_Z25batch_sample_rules_kernelP",
-                     "_Z31spec_sample_rules_commit_kernelP", "_Z36spec_many_sample_rules_commit_kernel6SmPass")
+                     "_Z31spec_sample_rules_commit_kernelP", "_Z36spec_many_sample_rules_commit_kernel6SmPass",
+                     # (lnb_emit_probs.h: the same sample_block inlined into the token launches with the emitted entry -- emit_sample_kernel<RULES, BATCH> 17 / 12 / 12 / 7
+                     # and emit_spec_commit_kernel<RULES> 18 / 15 scalars in VGPR lanes; what their epilogues need waits in the LDS; scratch 0, vgpr_spill_count 0)
+                     # (the six instantiations by name: another one has to be looked at and added)
+                     "_Z18emit_sample_kernelILb0ELb0EEv13EmitTokParams", "_Z18emit_sample_kernelILb0ELb1EEv13EmitTokParams", "_Z18emit_sample_kernelILb1ELb0EEv13EmitTokParams",
+                     "_Z18emit_sample_kernelILb1ELb1EEv13EmitTokParams", "_Z23emit_spec_commit_kernelILb0EEv14EmitSpecParams", "_Z23emit_spec_commit_kernelILb1EEv14EmitSpecParams")
     spills, cur = [], ""
     for l in txt:
         mname = re.search(r"\.name:\s+(\S+)", l)
