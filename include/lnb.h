@@ -370,6 +370,34 @@ int lnb_decode_speculative_until(lnb_ctx* c, const int32_t* history, int n_histo
                                  lnb_spec_stats* stats, float* ms_out);
 int lnb_op_ngram_draft(int device, const int32_t* text, int n_text, const int32_t* corpus, int n_corpus,
                        int ngram_min, int ngram_max, int max_draft, int32_t* out, int* n_out);
+/* ---- a TREE of drafts per pass: several occurrences of the matched n-gram verified together, the same tokens and KV rows ------------------------
+ * The chain goes wrong where the latest occurrence of the n-gram continues differently from the text; an earlier occurrence often holds the right
+ * continuation, and up to 16 columns of a verify pass cost the same.  lnb_ctx_set_draft_branches(ctx, n_branches), n_branches 1..LNB_MAX_DRAFT_BRANCHES
+ * (default 1: the chain above, bit for bit and graph for graph -- nothing of the tree path is launched or captured).  With n_branches > 1:
+ *   Draft (tree_draft_kernel): the same match rule; of the first n with a match, the up to n_branches LATEST starts, R latest first, then C latest first;
+ *   each continuation cut exactly as the chain is; the continuations are merged in that order into a trie -- node 0 = the current token, nodes numbered
+ *   in insertion order, at most 16 nodes and pos + nodes <= seq_len, a candidate merged only while a column is left -- so candidate 0 is the whole chain.
+ *   Verify: node i is column i, the one-token step at pos + depth[i] (RoPE row, sampler draw) whose K / V row is parked in cache slot pos + i; a column
+ *   attends over [0, pos) and the slots of its ancestors and itself (attn_tree_scores_kernel + attn_tree_pv_kernel, K and V of [0, pos) read once per KV
+ *   head for all columns).  The reference's softmax subtracts no maximum, so a masked entry adds +0 to the f64 sum and to the PV chain: the argument of
+ *   lnb_forward_append -- column i IS the one-token step at pos + depth[i], bit for bit, for finite V rows.
+ *   Accept: from node 0, at node i with token g_i go to the child whose input token is g_i, else stop; g is emitted along the path as the chain's commit
+ *   emits.  Compact: the accepted node at depth d moves from slot pos + i_d to pos + d (tree_kv_compact_kernel, all layers in one launch), so afterwards
+ *   rows [0, pos + accepted + 1) are the greedy loop's bits; rows beyond may hold rejected nodes, as after a chain.
+ *   A trie without a branching node (one occurrence, or occurrences that agree) is a chain and runs the chain's pass.
+ *   Covered: lnb_decode_speculative_until and lnb_decode_speculative_sample_until (the draw is u(seed, position) and a node's position is pos + depth,
+ *   so the acceptance argument holds per node), head_dim 128 / 64, contexts the one-workgroup attention serves (seq_len up to ~7.8 K at head_dim 128).
+ *   Ignored -- the call drafts the chain and runs exactly what it runs with n_branches 1, same tokens: longer contexts, head_dim 32,
+ *   lnb_decode_speculative_sample_rules_until and any call with lnb_ctx_set_emitted_probs on (their counts "in front of a column" are defined for a chain),
+ *   and every lnb_decode_speculative*_many call.
+ *   stats: drafted counts the nodes beyond node 0; accepted keeps its definition.  lnb_ctx_verify_attention_form reports 3 after a tree pass.
+ *   Arguments are checked before the handle; refused while a lnb_forward_stage_begin is pending; drops no captured graph.
+ * lnb_op_tree_draft: the tree draft kernel on host arrays (a test aid): tokens16 / parent16 / depth16 have 16 entries, -1 behind node *n_nodes - 1
+ *   (tokens16[0] = -1: node 0 is the caller's current token; parent16[0] = -1). */
+#define LNB_MAX_DRAFT_BRANCHES 4
+int lnb_ctx_set_draft_branches(lnb_ctx* c, int n_branches);
+int lnb_op_tree_draft(int device, const int32_t* text, int n_text, const int32_t* corpus, int n_corpus, int ngram_min, int ngram_max, int max_draft,
+                      int n_branches, int32_t* tokens16, int32_t* parent16, int32_t* depth16, int* n_nodes);
 
 /* ---- speculative greedy decoding of MANY contexts: every member drafts for itself, one pass over the weights verifies them all --------------
  * lnb_decode_speculative_until reads the weights once per pass of ONE context; lnb_batch_decode_until serves many contexts per pass, one column

@@ -40,6 +40,7 @@ static_assert(sizeof(lnb_sampler) == sizeof(LnbSampler) && sizeof(lnb_sampler) =
               LNB_SAMPLE_MAX_VOCAB == LNB_SAMPLE_MAX_V, "lnb.h and lnb_sample.h disagree on the sampler");
 static_assert(sizeof(lnb_logit_rules) == 40 && offsetof(lnb_logit_rules, bias_ids) == 24 && sizeof(LnbRulesDev) == 32, "the layout of the logit rules");
 static_assert(LNB_MAX_DRAFT == LNB_SPEC_MAX_DRAFT && LNB_MAX_DRAFT + 1 <= LNB_STREAM_COLS, "a verify pass is one column group of at most 16 columns");
+static_assert(LNB_MAX_DRAFT_BRANCHES == LNB_TREE_MAX_BRANCHES && LNB_MAX_DRAFT + 1 == 16, "TreeCols holds 16 nodes, tree_draft_kernel up to four starts per array");
 
 extern "C" {
 hipError_t lnbk_gemv(const GemvParams* p, int rw, int nch, int epi, int norm, hipStream_t st);
@@ -109,6 +110,12 @@ hipError_t lnbk_spec_sample_commit(const uint16_t* logits, int V, int w, const d
 hipError_t lnbk_spec_sample_rules_commit(const uint16_t* logits, int V, int w, const double* etab, const LnbSampler* smp, const LnbRulesDev* rules, int32_t* g,
                                          const BatchTab* tab, unsigned* cnt, hipStream_t st);
 hipError_t lnbk_ngram_draft(const DraftParams* p, hipStream_t st);
+hipError_t lnbk_tree_draft(const TreeDraftParams* tp, hipStream_t st);
+hipError_t lnbk_attn_tree(const AttnTreeParams* tp, hipStream_t st);
+hipError_t lnbk_tree_commit(const int32_t* g, int w, const BatchTab* tab, TreeCols* tree, hipStream_t st);
+hipError_t lnbk_tree_sample_commit(const uint16_t* logits, int V, int w, const double* etab, const LnbSampler* smp, int32_t* g, const BatchTab* tab, unsigned* cnt,
+                                   TreeCols* tree, hipStream_t st);
+hipError_t lnbk_tree_kv_compact(const TreeCompactParams* cp, hipStream_t st);
 hipError_t lnbk_kv_fork(const KvForkTab* tab, int nt, int split, hipStream_t st);
 hipError_t lnbk_append_many_setup(const AmPass* p, hipStream_t st);
 hipError_t lnbk_append_many_finish(const uint16_t* logits, int V, const AmRow* rows, int width, int32_t* out, hipStream_t st);
@@ -179,7 +186,8 @@ static hipError_t stream_create(Stream& s, unsigned flags) { return s.fill([&](h
 enum GraphLaunch { GL_GREEDY = 0, GL_SAMPLE, GL_STAGE, GL_SAMPLE_RULES, GL_SAMPLE_EMIT, GL_SAMPLE_RULES_EMIT, GL_COUNT };
 static bool gl_rules(GraphLaunch l) { return l == GL_SAMPLE_RULES || l == GL_SAMPLE_RULES_EMIT; }
 static bool gl_emit(GraphLaunch l) { return l == GL_SAMPLE_EMIT || l == GL_SAMPLE_RULES_EMIT; }
-enum GraphForm { GF_SHORT = 0, GF_LONG, GF_ROWS, GF_SHARED, GF_COUNT };      // (0, 1, 2: also what lnb_ctx_verify_attention_form reports; GF_SHARED: a batch with a shared prefix)
+enum GraphForm { GF_SHORT = 0, GF_LONG, GF_ROWS, GF_SHARED, GF_TREE, GF_COUNT };     // (0, 1, 2: also what lnb_ctx_verify_attention_form reports; GF_SHARED: a batch with a shared prefix;
+                                                                                     // GF_TREE: a verify pass over a draft tree, reported as 3)
 using Graphs = GraphTable<hipGraphExec_t, hipGraphExecDestroy, GL_COUNT, GF_COUNT>;
 
 static inline float bf_wide_h(uint16_t b) { uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; }
@@ -339,6 +347,11 @@ struct lnb_ctx {
     // scratch all widths share (sized for 16 columns, allocated when a pass first needs the long form), the form of the last verify pass
     int sp_attn_long_T = 0x7FFFFFFF, sp_force_zseq = 0, sp_last_form = 0;
     Dev<double> sp_e_buf, sp_z_part;
+    // a tree of drafts per pass (lnb_ctx_set_draft_branches; lnb_tree_verify.h): the node tables the draft kernel writes and the pass reads, the draft
+    // kernel's per-n match starts, and the tree attention's scratch for 16 columns (allocated when a call first drafts trees)
+    int sp_branches = 1;
+    Dev<TreeCols> sp_tree; Dev<int> sp_tbest;
+    Dev<uint64_t> sp_tree_idx; Dev<double> sp_tree_z;
     // multi-row long-context attention (attn_rows_*_kernel, lnb_ctx_set_rows_attention): appends of 2..15 rows (any row count at head_dim 32) whose
     // start_pos + seq exceeds rows_T (default attn_short_cap: the calls the row-per-workgroup kernel cannot take) run it; rows_flags bit 0 = every row
     // walks the serial sum, bit 1 = the verify passes run it wherever they would run the long form.  Its scratch is sp_e_buf / sp_z_part.
@@ -2321,7 +2334,11 @@ struct lnb_batch {
     // speculative verify batch (lnb_decode_speculative_until): every column is ONE context (ctxs[s] = it, the same caches); columns s >= 1 take
     // their state and token word from col_st + s / col_tok + s instead of the context's own (the context's sp_st / sp_tok: it owns them)
     StepState* col_st = nullptr; int32_t* col_tok = nullptr;
-    bool many_shared = false;              // ... and its passes read a shared prefix from the model handle's msp_src (lnb_model_set_many_shared_prefix): the ragged form
+    // ... and, when the pass being enqueued verifies a draft TREE (tree; GF_TREE graphs), parks column s's K / V row in slot tree_cols->slot[s] and runs the
+    // tree attention pair on the context's scratch (lnb_tree_verify.h); tree_cols is set for every verify batch, read only by tree passes
+    TreeCols* tree_cols = nullptr; bool tree = false;
+    uint64_t* tree_idx = nullptr; double* tree_z = nullptr;
+    bool many_shared = false;             // ... and its passes read a shared prefix from the model handle's msp_src (lnb_model_set_many_shared_prefix): the ragged form
     int* zseq = nullptr;                   // lnb_forward_append_many's pass batch has no member contexts: the serial-sum counter the attention launches get instead of ctxs[0]'s (AppendMany::zseq owns it)
 };
 // What every batched step asks of the model stage it runs on (who: the caller, as its message names it).  A whole-model handle is a stage of whole blocks.
@@ -2407,6 +2424,7 @@ static int batch_alloc(lnb_batch* b) {
     HIPCHK(event_create(b->ev0)); HIPCHK(event_create(b->ev1));
     HIPCHK(pinned_alloc(b->h_io, (2 * LNB_BATCH_MAX + 8) * 4, hipHostMallocDefault));
     BatchTab t{}; t.n = n;
+    if (b->tree_cols) t.slot = b->tree_cols->slot;           // (a device address: computed, not read)
     std::vector<BatchKV> kv(m->layers.size());
     for (int s = 0; s < LNB_BATCH_MAX; s++) {
         lnb_ctx* c = b->ctxs[s < n ? s : 0];                // (unused columns point at sequence 0's words: never dereferenced, never null)
@@ -2584,6 +2602,7 @@ struct BatchProd {
     const TiledDesc* t; const uint16_t* m16; int K, n_rows, nch, epi;
     uint16_t* out = nullptr; uint16_t* out_xt = nullptr; const uint16_t* res = nullptr;
     const BatchKV* kv = nullptr;           // EPI_QKV_ROPE: the layer's caches
+    bool slot = false;                     // EPI_QKV_ROPE of a tree verify pass: the K / V rows go to the columns' slots (the kernels' EPI_QKV_ROPE_SLOT arm)
 };
 // The norm launch and the product launch of one product, through the feed the plan gives it.
 // COLUMN with plan.groups (17 .. 32 sequences, LNB_BATCH_GROUPS=0: off): the thin matrices -- one k-ordered chain per 16-row tile and 16 columns -- as
@@ -2610,14 +2629,14 @@ static int enqueue_batch_product(lnb_batch* b, const BatchPlan& plan, const Batc
         p.out = d.out; p.out_xt = d.out_xt; p.res = d.res;
         if (d.epi == EPI_SILU_MUL) p.silu = m->silu;
         if (d.epi == EPI_QKV_ROPE) { p.cis = m->cis; p.q_out = b->q; p.tab = b->tab; p.kv = d.kv; p.q_dim = m->q_dim; p.kv_dim = m->kv_dim; p.head_dim = m->head_dim; }
-        HIPCHK(lnbk_stream(&p, d.epi, G ? 0 : stream_acc2(p), g_num_cus, st));
+        HIPCHK(lnbk_stream(&p, d.slot ? EPI_QKV_ROPE_SLOT : d.epi, G ? 0 : stream_acc2(p), g_num_cus, st));
         return 0;
     }
     GemmParams g{}; g.w16 = d.m16; g.w = d.t->w; g.rw = d.t->rw; g.nch = d.nch; g.x = x; g.K = d.K; g.n_rows = d.n_rows; g.S = b->n;
     g.out = d.out; g.out_xt = d.out_xt; g.res = d.res;
     if (d.epi == EPI_SILU_MUL) g.silu = m->silu;
     if (d.epi == EPI_QKV_ROPE) { g.cis = m->cis; g.q_out = b->q; g.btab = b->tab; g.bkv = d.kv; g.q_dim = m->q_dim; g.kv_dim = m->kv_dim; g.head_dim = m->head_dim; }
-    HIPCHK(lnbk_gemm_stream(&g, d.epi, g_num_cus, st));
+    HIPCHK(lnbk_gemm_stream(&g, d.slot ? EPI_QKV_ROPE_SLOT : d.epi, g_num_cus, st));
     return 0;
 }
 // which: K_QKV (attention norm + wq|wk|wv + RoPE + KV append), K_ATTN, K_WO, K_W13 (ffn norm + w1|w3 + SiLU*up), K_W2, K_HEAD (norm + output)
@@ -2634,7 +2653,7 @@ static int enqueue_batch_kernel(lnb_batch* b, int l, int which) {
     const BatchKV* kv = b->kv + (l - m->layer_begin);
     switch (which) {
     case K_QKV: {
-        BatchProd d{BP_QKV, L.attn_norm, b->x, &L.wqkv, L.m_wqkv, dim, L.wqkv.n_rows, 1, EPI_QKV_ROPE}; d.kv = kv;
+        BatchProd d{BP_QKV, L.attn_norm, b->x, &L.wqkv, L.m_wqkv, dim, L.wqkv.n_rows, 1, EPI_QKV_ROPE}; d.kv = kv; d.slot = b->tree;
         return enqueue_batch_product(b, plan, d); }
     case K_ATTN: {
         const bool wo_column = plan.feed[BP_WO] == FEED_COLUMN;
@@ -2642,6 +2661,12 @@ static int enqueue_batch_kernel(lnb_batch* b, int l, int which) {
         ap.S = b->n; ap.H = a.n_heads; ap.KVH = a.n_kv_heads; ap.hd = m->head_dim; ap.host_T = 0;
         ap.divisor = bf_wide_h(bf_trunc_h((float)std::sqrt((double)m->head_dim)));
         ap.zseq_count = b->zseq ? b->zseq : b->ctxs[0]->zseq_count; ap.exp_tab = m->exp_tab;     // (attn_gqa_kernel looks exp up)
+        if (b->tree) {                                       // a verify pass over a draft tree: the columns' rows sit in their slots, each row sees its ancestors
+            AttnTreeParams tp{}; tp.a = ap;
+            tp.a.seq_len = b->maxT; tp.a.force_zseq = b->force_zseq & 1; tp.a.z_part = b->tree_z; tp.idx = b->tree_idx; tp.tree = b->tree_cols;
+            tp.n_tiles = lnb_shared_tiles(b->n, a.n_heads / a.n_kv_heads); tp.njt = (b->maxT + 15) / 16;
+            HIPCHK(lnbk_attn_tree(&tp, b->stream)); return 0;
+        }
         if (b->sp_src) {                                     // a set prefix always takes the shared form: the members' rows below it may be unfilled
             AttnSharedParams sp{}; sp.a = ap;
             sp.a.seq_len = b->maxT; sp.a.force_zseq = b->force_zseq & 1; sp.a.z_part = b->sp_z; sp.idx = b->sp_idx;
@@ -3252,7 +3277,7 @@ extern "C" int lnb_ctx_set_batched_attention(lnb_ctx* c, int long_threshold, int
     HIPCHK(hipStreamSynchronize(c->stream));
     if (long_threshold >= 0) c->sp_attn_long_T = long_threshold;
     if (force_zseq != c->sp_force_zseq) {
-        for (lnb_batch* b : c->sp_b) if (b) { b->force_zseq = force_zseq; b->graphs.drop(GF_LONG); }      // (the greedy pass and its sampling twin; a verify batch has no stage step)
+        for (lnb_batch* b : c->sp_b) if (b) { b->force_zseq = force_zseq; b->graphs.drop(GF_LONG); b->graphs.drop(GF_TREE); }      // (the greedy pass and its sampling twin; a verify batch has no stage step)
         c->sp_force_zseq = force_zseq;
     }
     return 0;
@@ -3312,6 +3337,15 @@ extern "C" int lnb_ctx_set_draft(lnb_ctx* c, int max_draft, int ngram_min, int n
     c->sp_n_corpus = n_corpus; c->sp_max_draft = max_draft; c->sp_ngram_min = ngram_min; c->sp_ngram_max = ngram_max;
     return 0;
 }
+// lnb_ctx_set_draft_branches (include/lnb.h): how many occurrences of the matched n-gram a pass drafts from.  A host-side setting read at the start of the next
+// speculative call; the tree passes have graph families of their own (GF_TREE), so nothing captured is dropped either way.
+extern "C" int lnb_ctx_set_draft_branches(lnb_ctx* c, int n_branches) {
+    if (n_branches < 1 || n_branches > LNB_MAX_DRAFT_BRANCHES) return fail("n_branches must be 1..%d (got %d)", LNB_MAX_DRAFT_BRANCHES, n_branches);
+    if (!c) return fail("null argument");
+    if (c->pending) return fail("a lnb_forward_stage_begin has not been ended");
+    c->sp_branches = n_branches;
+    return 0;
+}
 // the per-context buffers of the drafting loop (the text head grows with the history)
 static int spec_alloc(lnb_ctx* c, int text_len) {
     if (!c->sp_st) {
@@ -3324,6 +3358,9 @@ static int spec_alloc(lnb_ctx* c, int text_len) {
         HIPCHK(pinned_alloc(c->sp_word, 16, hipHostMallocMapped));
         HIPCHK(hipHostGetDevicePointer((void**)&c->sp_word_dev, c->sp_word, 0));
         HIPCHK(event_create(c->sp_ev));
+        // the node tables of a draft tree: every verify batch's column table points at their slot words, whether or not a tree pass ever runs
+        HIPCHK(dev_alloc(c->sp_tree, sizeof(TreeCols))); HIPCHK(hipMemsetAsync(c->sp_tree, 0, sizeof(TreeCols), c->stream));
+        HIPCHK(dev_alloc(c->sp_tbest, LNB_SPEC_MAX_NGRAM * 2 * LNB_TREE_MAX_BRANCHES * sizeof(int)));
     }
     if (!c->sp_text.fits((size_t)text_len * 4)) {
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -3337,7 +3374,13 @@ static int spec_alloc(lnb_ctx* c, int text_len) {
 // launch: the token launch of the pass -- greedy, sampling or sampling under rules -- each a graph family of its own per (width, form) in the batch's table
 static int spec_verify_batch(lnb_ctx* c, int w, GraphForm form, GraphLaunch launch, lnb_batch** out, hipGraphExec_t* graph_out) {
     lnb_model* m = c->m;
-    const bool long_form = form != GF_SHORT;
+    const bool long_form = form == GF_LONG || form == GF_ROWS, tree = form == GF_TREE;
+    if (tree && !c->sp_tree_idx) {                           // the tree pair's scratch for 16 columns, shared by all widths (host side of the call, outside any capture)
+        const int G = m->a.n_heads / m->a.n_kv_heads;
+        hipError_t e = dev_alloc(c->sp_tree_idx, lnb_shared_idx_bytes(LNB_MAX_DRAFT + 1, G, m->a.n_kv_heads, c->seq_len));
+        if (e == hipSuccess) e = dev_alloc(c->sp_tree_z, lnb_shared_z_bytes(LNB_MAX_DRAFT + 1, G, m->a.n_kv_heads, c->seq_len));
+        if (e != hipSuccess) { c->sp_tree_idx.reset(); c->sp_tree_z.reset(); (void)hipGetLastError(); return fail("the tree verify attention's scratch: %s", hipGetErrorString(e)); }
+    }
     if (long_form && attn_long_scratch(LNB_MAX_DRAFT + 1, m->a.n_heads, c->seq_len, c->sp_e_buf, c->sp_z_part, "the verify passes")) return -1;   // (host side of the call, outside any capture)
     lnb_batch* b = c->sp_b[w];
     const bool fresh = !b;
@@ -3346,15 +3389,26 @@ static int spec_verify_batch(lnb_ctx* c, int w, GraphForm form, GraphLaunch laun
         b->m = m; b->n = w; b->ctxs.assign(w, c); b->rows_form = !m->batch_enabled;
         b->maxT = c->seq_len; b->lds_T = std::min(c->seq_len, c->attn_short_cap); b->must_long = c->seq_len > c->attn_short_cap;
         b->scratch_owned = false; b->force_zseq = c->sp_force_zseq;
-        b->col_st = c->sp_st; b->col_tok = c->sp_tok;
+        b->col_st = c->sp_st; b->col_tok = c->sp_tok; b->tree_cols = c->sp_tree;
         if (batch_alloc(b)) { lnb_batch_destroy(b); return -1; }
         c->sp_b[w] = b;
     }
     b->e_buf = c->sp_e_buf; b->z_part = c->sp_z_part;
     b->attn_long = long_form; b->attn_rows = form == GF_ROWS; b->rows_zseq = c->rows_flags & 1;
+    b->tree = tree; b->tree_idx = c->sp_tree_idx; b->tree_z = c->sp_tree_z;
     GraphExec& gslot = b->graphs.slot(launch, form);
     auto body = [&]() -> int {
         if (enqueue_batch_pass(b)) return -1;
+        if (tree) {                                          // every column's token at its own position, the walk from node 0, then the accepted rows into place (all layers, one launch)
+            if (launch == GL_SAMPLE) HIPCHK(lnbk_tree_sample_commit(b->logits, m->a.vocab_size, w, m->prob_etab, c->d_smp, c->sp_g, b->tab, c->sp_cnt + 1, c->sp_tree, b->stream));
+            else if (launch == GL_GREEDY) {
+                HIPCHK(lnbk_spec_argmax(b->logits, m->a.vocab_size, w, c->sp_g, b->stream));
+                HIPCHK(lnbk_tree_commit(c->sp_g, w, b->tab, c->sp_tree, b->stream));
+            } else return fail("internal error: a tree verify pass under token launch %d", (int)launch);
+            TreeCompactParams cp{c->sp_tree, b->kv, (int)m->layers.size(), m->kv_dim, m->head_dim, c->seq_len};
+            HIPCHK(lnbk_tree_kv_compact(&cp, b->stream));
+            return 0;
+        }
         if (gl_emit(launch)) {                               // the summary of all w columns at once into the pass scratch, then the commit that records the emitted ones
             TokProbParams p = tp_params(m, b->logits, w, c->emit_k, c->em.s_zpart, c->em.s_kpart, c->em.s_cnt, c->em.s_out, 0);
             p.park = c->em.s_park;
@@ -3444,8 +3498,13 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
     HIPCHK(ctx_set_state(c, start_pos, 0, false, true));
     c->call_T = 0;
     const DraftParams dp = spec_draft_params(c, n_text, max_steps);
+    // A tree of drafts per pass (lnb_ctx_set_draft_branches): the greedy and the plain sampling call, on a context the one-workgroup kernels serve, head_dim 128 / 64.
+    // Everything else -- rules and records (their counts "in front of a column" are a chain's), longer contexts, head_dim 32 -- drafts the chain: today's launches.
+    const bool use_tree = c->sp_branches > 1 && !rc && !emit && c->seq_len <= c->attn_short_cap && (m->head_dim == 128 || m->head_dim == 64);
+    TreeDraftParams tdp{}; tdp.d = dp; tdp.n_branches = c->sp_branches; tdp.max_nodes = LNB_MAX_DRAFT + 1; tdp.tree = c->sp_tree; tdp.tbest = c->sp_tbest;
+    auto draft = [&]() { return use_tree ? lnbk_tree_draft(&tdp, st) : lnbk_ngram_draft(&dp, st); };
     HIPCHK(hipEventRecord(c->ev0, st));
-    HIPCHK(lnbk_ngram_draft(&dp, st));
+    HIPCHK(draft());
     HIPCHK(hipEventRecord(c->sp_ev, st));
     lnb_spec_stats s{};
     int n_out = 0, fin = 0;
@@ -3455,7 +3514,10 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
         const volatile int32_t* wd = c->sp_word;
         const int k = wd[0]; n_out = wd[1]; fin = wd[2];
         if (fin || n_out >= max_steps) break;
-        if (k < 0 || k > c->sp_max_draft) return fail("internal error: draft length %d", k);
+        // k + 1 = the pass's columns: the nodes of the tree (a chain: the draft length + 1); branching: some node has two children -- a trie that is
+        // a chain (one occurrence, or occurrences that agree) IS today's pass and runs today's graph
+        const bool branching = use_tree && wd[3] != 0;
+        if (k < 0 || k > (use_tree ? LNB_MAX_DRAFT : c->sp_max_draft)) return fail("internal error: draft length %d", k);
         s.passes++;
         if (k == 0) {
             const bool lg = want_long_attention(c, 1, start_pos + n_out);
@@ -3464,13 +3526,13 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
             lnb_batch* b = nullptr; hipGraphExec_t pass = nullptr;
             // the pass's last column sits at start_pos + n_out + k: the long form when the context is beyond the one-workgroup kernels' reach or past the threshold
             const bool lf = c->seq_len > c->attn_short_cap || start_pos + n_out + k + 1 > c->sp_attn_long_T;
-            const GraphForm form = !lf ? GF_SHORT : (c->rows_flags & 2) ? GF_ROWS : GF_LONG;     // (rows: lnb_ctx_set_rows_attention's opt-in -- K and V read once for all columns)
+            const GraphForm form = branching ? GF_TREE : !lf ? GF_SHORT : (c->rows_flags & 2) ? GF_ROWS : GF_LONG;     // (rows: lnb_ctx_set_rows_attention's opt-in -- K and V read once for all columns)
             if (spec_verify_batch(c, k + 1, form, launch, &b, &pass)) return -1;
             HIPCHK(hipGraphLaunch(pass, st));
-            c->sp_last_form = form; b->last_form = lf ? 1 : 0;
+            c->sp_last_form = branching ? 3 : form; b->last_form = !branching && lf ? 1 : 0;
             s.verify_passes++; s.drafted += k;
         }
-        HIPCHK(lnbk_ngram_draft(&dp, st));
+        HIPCHK(draft());
         HIPCHK(hipEventRecord(c->sp_ev, st));
     }
     HIPCHK(hipEventRecord(c->ev1, st));
@@ -3540,6 +3602,37 @@ extern "C" int lnb_op_ngram_draft(int device, const int32_t* text, int n_text, c
     if (word[0] < 0 || word[0] > max_draft) return fail("internal error: draft length %d", word[0]);
     for (int i = 0; i < word[0]; i++) out[i] = h[1 + i];
     *n_out = word[0];
+    return 0;
+}
+// tree_draft_kernel on host arrays (the same kind of test aid): the trie of the up to n_branches latest continuations of text, with no decode limits.
+// tokens16 / parent16 / depth16: 16 entries each, -1 behind the last node (tokens16[0] = -1: node 0 is the caller's current token)
+extern "C" int lnb_op_tree_draft(int device, const int32_t* text, int n_text, const int32_t* corpus, int n_corpus, int ngram_min, int ngram_max, int max_draft,
+                                 int n_branches, int32_t* tokens16, int32_t* parent16, int32_t* depth16, int* n_nodes) {
+    if (n_text < 0) return fail("negative text length %d", n_text);
+    if (spec_check_draft_args(max_draft, ngram_min, ngram_max, n_corpus)) return -1;
+    if (n_branches < 1 || n_branches > LNB_MAX_DRAFT_BRANCHES) return fail("n_branches must be 1..%d (got %d)", LNB_MAX_DRAFT_BRANCHES, n_branches);
+    if ((n_text > 0 && !text) || (n_corpus > 0 && !corpus) || !tokens16 || !parent16 || !depth16 || !n_nodes) return fail("null argument");
+    if (op_device(device)) return -1;
+    DevArena a;
+    int32_t* dt = a.alloc<int32_t>((size_t)std::max(n_text, 1)); int32_t* dc = a.alloc<int32_t>((size_t)std::max(n_corpus, 1));
+    int32_t* dout = a.alloc<int32_t>(3 * 16); int32_t* dword = a.alloc<int32_t>(4);
+    int* tbest = a.alloc<int>(LNB_SPEC_MAX_NGRAM * 2 * LNB_TREE_MAX_BRANCHES); unsigned* cnt = a.alloc<unsigned>(4);
+    HIPCHK(a.error());
+    HIPCHK(hipMemset(cnt, 0, 16)); HIPCHK(hipMemset(dout, 0, 3 * 16 * 4));
+    if (n_text > 0) HIPCHK(hipMemcpy(dt, text, (size_t)n_text * 4, hipMemcpyHostToDevice));
+    if (n_corpus > 0) HIPCHK(hipMemcpy(dc, corpus, (size_t)n_corpus * 4, hipMemcpyHostToDevice));
+    TreeDraftParams tp{}; DraftParams& p = tp.d;
+    p.text = dt; p.n_text = n_text; p.corpus = dc; p.n_corpus = n_corpus; p.ngram_min = ngram_min; p.ngram_max = ngram_max; p.max_draft = max_draft;
+    p.out = dout; p.word = dword; p.cnt = cnt;
+    tp.n_branches = n_branches; tp.max_nodes = LNB_MAX_DRAFT + 1; tp.tbest = tbest; tp.op_depth = dout + 16; tp.op_parent = dout + 32;
+    HIPCHK(lnbk_tree_draft(&tp, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    int32_t h[3 * 16] = {}, word[4] = {};
+    HIPCHK(hipMemcpy(word, dword, 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h, dout, sizeof h, hipMemcpyDeviceToHost));
+    if (word[0] < 0 || word[0] > LNB_MAX_DRAFT) return fail("internal error: %d tree nodes", word[0] + 1);
+    *n_nodes = word[0] + 1;
+    for (int i = 0; i < 16; i++) { tokens16[i] = i > 0 && i <= word[0] ? h[i] : -1; depth16[i] = i <= word[0] ? h[16 + i] : -1; parent16[i] = i <= word[0] ? h[32 + i] : -1; }
     return 0;
 }
 

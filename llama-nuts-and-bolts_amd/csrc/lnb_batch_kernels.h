@@ -60,8 +60,9 @@ template <int EPI> DEVINL void stream_epilogue(const StreamParams& p, const f32x
         else if (EPI == EPI_SILU_MUL) {                                                                                   // activations.go:36-39, :614
             const uint16_t gs = bf_trunc(p.silu[bf_trunc(g[r])]);
             p.out_xt[xt_index(s, n)] = bf_trunc(bf_wide(gs) * bf_wide(bf_trunc(u[r])));
-        } else if (EPI == EPI_QKV_ROPE) {                                                                                 // llamatransformer.go:297-403
+        } else if (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_ROPE_SLOT) {                                                     // llamatransformer.go:297-403
             const int pos = p.tab->st[s]->pos;                                                                            // this sequence's own position
+            const int slot = EPI == EPI_QKV_ROPE_SLOT ? p.tab->slot[s] : pos;                                             // (a tree verify pass parks the row in the column's slot)
             const uint16_t mine = bf_trunc(g[r]), other = bf_trunc(g[r ^ 1]);                                             // RoPE partner 2i <-> 2i+1: same lane
             if (n < p.q_dim + p.kv_dim) {
                 const int d = n % p.head_dim, i = d >> 1;
@@ -73,9 +74,9 @@ template <int EPI> DEVINL void stream_epilogue(const StreamParams& p, const f32x
                 if (n < p.q_dim) p.q_out[(size_t)s * p.q_dim + n] = r16;
                 else {                                                                                                    // :402, K cache [kv head][d/8][position][8]
                     const int kc = n - p.q_dim, kh = kc / p.head_dim;
-                    p.kv->ck[s][(((size_t)kh * (p.head_dim >> 3) + (d >> 3)) * p.tab->seq_len[s] + pos) * 8 + (d & 7)] = r16;
+                    p.kv->ck[s][(((size_t)kh * (p.head_dim >> 3) + (d >> 3)) * p.tab->seq_len[s] + slot) * 8 + (d & 7)] = r16;
                 }
-            } else p.kv->cv[s][(size_t)pos * p.kv_dim + (n - p.q_dim - p.kv_dim)] = mine;                                 // :403
+            } else p.kv->cv[s][(size_t)slot * p.kv_dim + (n - p.q_dim - p.kv_dim)] = mine;                                // :403
         }
     }
 }

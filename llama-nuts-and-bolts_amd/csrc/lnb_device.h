@@ -73,7 +73,9 @@ struct StepState {
 };
 
 enum { EPI_STORE = 0, EPI_QKV_ROPE = 1, EPI_RESID = 2, EPI_SILU_MUL = 3,
-       EPI_STORE2 = 4 };       // kernel-internal: EPI_STORE of a two-chain block of 2 RW rows (the packed LM head); the form tally counts it as EPI_STORE
+       EPI_STORE2 = 4,         // kernel-internal: EPI_STORE of a two-chain block of 2 RW rows (the packed LM head); the form tally counts it as EPI_STORE
+       EPI_QKV_ROPE_SLOT = 5 };// kernel-internal: EPI_QKV_ROPE of a tree verify pass (lnb_tree_verify.h) -- the K / V rows of column s go to the cache SLOT
+                               // BatchTab::slot[s] while the rotation stays at the column's position word; the form tally counts it as EPI_QKV_ROPE
 
 struct GemvParams {
     const uint16_t* w;          // tiled weights
@@ -231,6 +233,7 @@ struct BatchTab {                  // device-resident: the sequences of a batch 
     int32_t dout_cap[LNB_BATCH_MAX];
     int32_t seq_len[LNB_BATCH_MAX];   // ... KV-cache length (the K cache layout depends on it)
     int32_t n, pad[3];
+    const int32_t* slot;           // a tree verify pass (EPI_QKV_ROPE_SLOT, attn_tree_*_kernel): [n] the cache slot of every column's K / V row; nothing else reads it
 };
 struct BatchKV { uint16_t* ck[LNB_BATCH_MAX]; uint16_t* cv[LNB_BATCH_MAX]; };   // one per layer: every sequence's caches of that layer
 
@@ -356,6 +359,38 @@ struct DraftParams {
     int* best;                                 // [2 * LNB_SPEC_MAX_NGRAM]: per workgroup, the latest match start in R and in C (-1: none)
     unsigned* cnt;                             // arrival ticket, zero between launches (the last workgroup resets it)
 };
+
+// ---- a TREE of drafts in one verify pass (lnb_ctx_set_draft_branches; tree_draft_kernel, lnb_tree_verify.h) ------------------------------------
+// The up to n_branches latest continuations of the matched n-gram, merged into a trie of at most 16 nodes: node 0 is the current token, nodes are numbered
+// in insertion order (a parent's index lies below its children's), node i is column i of the pass.  Column i is the one-token step at pos + depth[i] (its
+// position word: RoPE row, sampler draw) whose K / V row is parked in cache SLOT pos + i and which attends over [0, pos) and the slots of its ancestors
+// and itself -- slots ascend with depth along a root path, so a row's order is the one-token step's.  TreeCols is per context, written by the draft
+// kernel (everything but path), the commit (path) and read by the pass's kernels: one captured graph serves every tree of its width.
+constexpr int LNB_TREE_MAX_BRANCHES = 4;       // = LNB_MAX_DRAFT_BRANCHES of lnb.h
+struct TreeCols {
+    int32_t n, pos;                            // nodes of the pass, the position of node 0 when it was drafted
+    int32_t slot[16];                          // pos + i
+    int32_t depth[16], parent[16];             // parent[0] = -1
+    uint32_t mask[16];                         // bit j: node j is an ancestor of node i or i itself
+    int32_t n_path, path[16];                  // the commit's accepted path: path[d] = its node at depth d (path[0] = 0); n_path 0 = a frozen run
+};
+struct TreeDraftParams {
+    DraftParams d;                             // word = {nodes - 1, n_out, finished, 1 if a node has two children (0: the trie is today's chain)}
+    int n_branches, max_nodes;                 // max_nodes: 16, less for tests; the kernel also keeps pos + nodes <= seq_len
+    TreeCols* tree;                            // nullptr: none kept (the host mirror below is filled all the same)
+    int* tbest;                                // [LNB_SPEC_MAX_NGRAM][2][LNB_TREE_MAX_BRANCHES] per n: the latest match starts in R and in C, latest first (-1: none)
+    int32_t* op_depth; int32_t* op_parent;     // lnb_op_tree_draft: the nodes' depths and parents (nullptr in the decode loop)
+};
+// tree verify attention (attn_tree_scores_kernel + attn_tree_pv_kernel): a carries what the shared form takes (q, out / out_xt, btab, bkv, S = the columns,
+// H, KVH, hd, seq_len = the context's capacity, exp_tab, force_zseq, zseq_count, z_part [KVH][n_tiles * 16][ceil(seq_len / 256)]); every column is ONE
+// context, so K and V come from bkv's column 0 and the position from btab->st[0]
+struct AttnTreeParams {
+    AttnParams a;
+    const TreeCols* tree;
+    int n_tiles, njt;                          // lnb_shared_tiles(S, H / KVH), ceil(seq_len / 16)
+    uint64_t* idx;                             // [KVH][n_tiles][njt][64 lanes] x 8 bytes, the shared form's scratch layout
+};
+struct TreeCompactParams { const TreeCols* tree; const BatchKV* kv; int n_layers, kv_dim, head_dim, seq_len; };
 
 // ---- speculative decoding of many contexts (lnb_decode_speculative_many; lnb_spec_many.h, lnb_specpack.h) ------------------------------------
 // A pass is a pass of lnb_forward_append_many whose row table is written ON THE DEVICE: per member, column 0 = its current token at its position

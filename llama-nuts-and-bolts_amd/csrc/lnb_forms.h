@@ -62,6 +62,9 @@
     /* shared-prefix attention of a ragged pass (lnbk_attn_ragged: lnb_model_set_many_shared_prefix) */ \
     X(ATTN_MANY_RAGGED_SCORES, "attn_many.ragged_scores", "attn_ragged_scores_kernel<HD>: the shared scores form for columns that share a member -- a uniform tile also takes the member's own K on the matrix cores") \
     X(ATTN_MANY_RAGGED_PV, "attn_many.ragged_pv", "attn_ragged_pv_kernel<HD>: one wave per (row tile, 32 output dims), source V and a uniform tile's own V read once per 16 rows, operands two tiles ahead in registers") \
+    /* attention over a draft tree (lnbk_attn_tree: lnb_ctx_set_draft_branches) */ \
+    X(ATTN_TREE_SCORES, "attn_tree.scores", "attn_tree_scores_kernel<HD>: 16 (column, head) rows of a tree verify pass per matrix-core tile against the context's K, the pass's own slots under each row's ancestor mask") \
+    X(ATTN_TREE_PV, "attn_tree.pv", "attn_tree_pv_kernel<HD>: one wave per (row tile, 32 output dims), the context's V read once per 16 rows, masked slots skipped") \
     /* prefix sharing (lnb_ctx_fork) */ \
     X(KV_FORK_PLAIN, "kv_fork.plain", "kv_fork_kernel<false>, one destination group") \
     X(KV_FORK_NT, "kv_fork.nt", "kv_fork_kernel<true>: non-temporal loads and stores (LNB_FORK_NT)") \

@@ -1527,9 +1527,10 @@ template <int EPI> DEVINL void gemm_epilogue4(const GemmParams& p, const f32x4& 
             const uint16_t y = bf_trunc(bf_wide(gs) * bf_wide(bf_trunc(u[r])));
             if (p.out_xt) p.out_xt[xt_group(m, p.n_rows) + xt_index(m & 15, n)] = y;       // the next product reads column groups (mfma_pair_kernel)
             else p.out[o] = y;
-        } else if (EPI == EPI_QKV_ROPE) {                                                                         // llamatransformer.go:297-403
+        } else if (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_ROPE_SLOT) {                                             // llamatransformer.go:297-403
             // rows of one sequence: consecutive positions of its cache; rows of a batch (btab): row m is sequence m's one new token
             const int pos = p.btab ? p.btab->st[m]->pos : p.st->pos + m;
+            const int slot = EPI == EPI_QKV_ROPE_SLOT ? p.btab->slot[m] : pos;                                    // (a tree verify pass, always with btab: the row is parked in the column's slot)
             const int seq_len = p.btab ? p.btab->seq_len[m] : p.seq_len;
             uint16_t* const cache_k = p.btab ? p.bkv->ck[m] : p.cache_k;
             uint16_t* const cache_v = p.btab ? p.bkv->cv[m] : p.cache_v;
@@ -1544,9 +1545,9 @@ template <int EPI> DEVINL void gemm_epilogue4(const GemmParams& p, const f32x4& 
                 if (n < p.q_dim) p.q_out[(size_t)m * p.q_dim + n] = r16;
                 else {
                     const int kc = n - p.q_dim, kh = kc / p.head_dim;
-                    cache_k[(((size_t)kh * (p.head_dim >> 3) + (d >> 3)) * seq_len + pos) * 8 + (d & 7)] = r16;
+                    cache_k[(((size_t)kh * (p.head_dim >> 3) + (d >> 3)) * seq_len + slot) * 8 + (d & 7)] = r16;
                 }
-            } else cache_v[(size_t)pos * p.kv_dim + (n - p.q_dim - p.kv_dim)] = mine;
+            } else cache_v[(size_t)slot * p.kv_dim + (n - p.q_dim - p.kv_dim)] = mine;
         }
     }
 }
@@ -4598,14 +4599,15 @@ DEVINL int32_t spec_text_at(const DraftParams& p, int j) { return j < p.n_text ?
 // the call sbest = {latest match start in R, in C} (-1: none).  ngram_pick: what the last workgroup makes of the `count` results in p.best
 // (result q belongs to n = ngram_max - q) -> the draft length after every cut, *src = 0 R / 1 C, *start = the draft's first token in that array.
 // Shared by ngram_draft_kernel and spec_many_draft_kernel (lnb_spec_many.h): one rule, one body.
-DEVINL void ngram_search_block(const DraftParams& p, int n, int L, int32_t* suf, int* sbest) {
+// BOUNDED (tree_draft_kernel's later rounds): only starts below hi_r in R and below hi_c in C -- the next latest match behind the one a round before found
+template <bool BOUNDED = false> DEVINL void ngram_search_block(const DraftParams& p, int n, int L, int32_t* suf, int* sbest, int hi_r = 0, int hi_c = 0) {
     const int tid = threadIdx.x;
     if (tid < 2) sbest[tid] = -1;
     if (tid < n && n <= L) suf[tid] = spec_text_at(p, L - n + tid);
     __syncthreads();
     if (n < L) {                                             // descending per thread: its first hit is its latest
         int mine = -1;
-        for (int j = L - n - 1 - tid; j >= 0; j -= (int)blockDim.x) {
+        for (int j = (BOUNDED ? hi_r : L - n) - 1 - tid; j >= 0; j -= (int)blockDim.x) {
             bool ok = true;
             for (int t = 0; t < n && ok; t++) ok = spec_text_at(p, j + t) == suf[t];
             if (ok) { mine = j; break; }
@@ -4614,7 +4616,7 @@ DEVINL void ngram_search_block(const DraftParams& p, int n, int L, int32_t* suf,
     }
     if (n <= L && p.n_corpus > n) {
         int mine = -1;
-        for (int j = p.n_corpus - n - 1 - tid; j >= 0; j -= (int)blockDim.x) {
+        for (int j = (BOUNDED ? hi_c : p.n_corpus - n) - 1 - tid; j >= 0; j -= (int)blockDim.x) {
             bool ok = true;
             for (int t = 0; t < n && ok; t++) ok = p.corpus[j + t] == suf[t];
             if (ok) { mine = j; break; }
@@ -4664,6 +4666,88 @@ __global__ __launch_bounds__(256) void ngram_draft_kernel(DraftParams p) {
     for (int i = 0; i < k; i++) p.out[1 + i] = src == 0 ? spec_text_at(p, start + i) : p.corpus[start + i];
     if (p.col_st) for (int i = 1; i <= k; i++) p.col_st[i].pos = pos + i;
     p.word[0] = k; p.word[1] = n_gen; p.word[2] = finished;
+}
+// The draft TREE of the next pass (lnb_ctx_set_draft_branches; TreeCols, lnb_device.h).  Same match rule and the same search body: workgroup b tries
+// n = ngram_max - b, now in up to n_branches rounds -- round r looks only below the start round r - 1 found, per array -- and leaves its starts, latest
+// first, in tbest.  The last workgroup to arrive takes the first n with a match and of its starts the first n_branches in the order R latest first, then
+// C latest first; each continuation is cut exactly as ngram_pick cuts the chain.  One thread merges them into the trie in that order, a candidate only
+// while a column is left (max_nodes, and pos + nodes <= seq_len: every node has a cache slot), so candidate 0 is today's whole chain.
+__global__ __launch_bounds__(256) void tree_draft_kernel(TreeDraftParams tp) {
+    __shared__ int32_t suf[LNB_SPEC_MAX_NGRAM];
+    __shared__ int sbest[2];
+    __shared__ int s_last;
+    const DraftParams& p = tp.d;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int n = p.ngram_max - b;
+    const int n_gen = p.st ? p.st->n_out : 0;
+    const int L = p.n_text + n_gen;
+    int* const mine = tp.tbest + b * 2 * LNB_TREE_MAX_BRANCHES;
+    int hi_r = L - n, hi_c = p.n_corpus - n;
+    for (int r = 0; r < LNB_TREE_MAX_BRANCHES; r++) {        // (uniform: every thread reads the same sbest behind the body's closing barrier)
+        int fr = -1, fc = -1;
+        if (r < tp.n_branches) {
+            ngram_search_block<true>(p, n, L, suf, sbest, hi_r, hi_c);
+            fr = sbest[0]; fc = sbest[1];
+            __syncthreads();                                 // (the next round resets sbest)
+        }
+        hi_r = fr < 0 ? 0 : fr; hi_c = fc < 0 ? 0 : fc;      // an exhausted array stays exhausted
+        if (tid == 0) { mine[r] = fr; mine[LNB_TREE_MAX_BRANCHES + r] = fc; }
+    }
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        const unsigned t = __hip_atomic_fetch_add(p.cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = t == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last || tid != 0) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    *p.cnt = 0;                                              // (ready for the next launch: stream order)
+    const int finished = p.st ? p.st->finished : 0, pos = p.st ? p.st->pos : 0;
+    int cap = tp.max_nodes, lim = p.max_draft;               // lim: the longest continuation after every cut
+    if (p.st) {
+        cap = min(cap, p.seq_len - pos);
+        lim = min(lim, min(p.max_steps - n_gen - 1, p.seq_len - pos - 1));
+        if (finished || lim < 0) lim = 0;
+    }
+    const int32_t* best = nullptr; int nq = 0;
+    for (int q = 0; q < (int)gridDim.x && !best; q++) {
+        const int* t = tp.tbest + q * 2 * LNB_TREE_MAX_BRANCHES;
+        if (t[0] >= 0 || t[LNB_TREE_MAX_BRANCHES] >= 0) { best = t; nq = p.ngram_max - q; }
+    }
+    __shared__ int32_t tok[16], depth[16], parent[16];      // (one thread's tables, indexed at run time: LDS, not scratch memory)
+    __shared__ uint32_t mask[16];
+    int nodes = 1, branching = 0, taken = 0;
+    depth[0] = 0; parent[0] = -1; mask[0] = 1u; tok[0] = 0;
+    for (int e = 0; best && e < 2 * LNB_TREE_MAX_BRANCHES && taken < tp.n_branches; e++) {       // e: R's starts, then C's
+        const int j = best[e];
+        if (j < 0) continue;
+        taken++;
+        const int src = e >= LNB_TREE_MAX_BRANCHES, start = j + nq;
+        const int k = min(src ? p.n_corpus - start : L - start, lim);
+        int cur = 0;
+        for (int t = 0; t < k; t++) {
+            const int32_t x = src ? p.corpus[start + t] : spec_text_at(p, start + t);
+            int child = -1, kids = 0;
+            for (int i = cur + 1; i < nodes; i++) if (parent[i] == cur) { kids++; if (tok[i] == x) child = i; }
+            if (child < 0) {
+                if (nodes >= cap) break;                     // no column left: this candidate ends here
+                child = nodes++;
+                tok[child] = x; parent[child] = cur; depth[child] = depth[cur] + 1; mask[child] = mask[cur] | (1u << child);
+                if (kids) branching = 1;
+            }
+            cur = child;
+        }
+    }
+    for (int i = 1; i < nodes; i++) {
+        p.out[i] = tok[i];
+        if (p.col_st) p.col_st[i].pos = pos + depth[i];
+    }
+    for (int i = 0; i < nodes; i++) {
+        if (tp.tree) { tp.tree->slot[i] = pos + i; tp.tree->depth[i] = depth[i]; tp.tree->parent[i] = parent[i]; tp.tree->mask[i] = mask[i]; }
+        if (tp.op_depth) { tp.op_depth[i] = depth[i]; tp.op_parent[i] = parent[i]; }
+    }
+    if (tp.tree) { tp.tree->n = nodes; tp.tree->pos = pos; tp.tree->n_path = 0; }
+    p.word[0] = nodes - 1; p.word[1] = n_gen; p.word[2] = finished; p.word[3] = branching;
 }
 
 // ---- token probabilities: what the reference's Softmax (operations_impl.go:478-511) gives for one logits row, and ml.Argmax's top k ----
@@ -5554,8 +5638,11 @@ extern "C" hipError_t lnbk_m16_from_tiled(const uint16_t* src, uint16_t* dst, in
 }
 // the epilogues mfma_pair_kernel exists for (nullptr: none)
 static auto pair_kernel(int epi) -> void (*)(StreamParams) {
-    return epi == EPI_STORE ? mfma_pair_kernel<EPI_STORE> : epi == EPI_RESID ? mfma_pair_kernel<EPI_RESID> : epi == EPI_QKV_ROPE ? mfma_pair_kernel<EPI_QKV_ROPE> : nullptr;
+    return epi == EPI_STORE ? mfma_pair_kernel<EPI_STORE> : epi == EPI_RESID ? mfma_pair_kernel<EPI_RESID> : epi == EPI_QKV_ROPE ? mfma_pair_kernel<EPI_QKV_ROPE>
+           : epi == EPI_QKV_ROPE_SLOT ? mfma_pair_kernel<EPI_QKV_ROPE_SLOT> : nullptr;
 }
+// the tally row of an epilogue: the slot arm of a tree verify pass is the same form and counts as EPI_QKV_ROPE (no form name of its own)
+static int tally_epi(int epi) { return epi == EPI_QKV_ROPE_SLOT ? EPI_QKV_ROPE : epi; }
 // acc2: two tile-chains per wave (fat matrices and the gate|up pairs); else one (thin matrices: every tile on its own SIMD)
 extern "C" hipError_t lnbk_stream(const StreamParams* p, int epi, int acc2, int num_cus, hipStream_t st) {
     const int G = p->n_groups > 1 ? p->n_groups : 1;
@@ -5568,16 +5655,17 @@ extern "C" hipError_t lnbk_stream(const StreamParams* p, int epi, int acc2, int 
     if (const auto pair = pair_kernel(epi); pair && !acc2 && (G > 1 || knob(Knob::STREAM_PAIR))) {
         const size_t lds = (size_t)2 * 2 * MP_BUF;
         unsigned gp = (unsigned)((q.n_jobs * G + 1) / 2); if (gp > (unsigned)num_cus) gp = (unsigned)num_cus;
-        form_ran(Form::MFMA_PAIR, epi);
+        form_ran(Form::MFMA_PAIR, tally_epi(epi));
         hipLaunchKernelGGL(pair, dim3(gp), dim3(256), lds, st, q);
         return hipGetLastError();
     }
 #define LNB_STREAM(E) (acc2 ? mfma_stream_kernel<2, E> : mfma_stream_kernel<1, E>)
     void (*const k)(StreamParams) = epi == EPI_STORE ? LNB_STREAM(EPI_STORE) : epi == EPI_RESID ? LNB_STREAM(EPI_RESID) : epi == EPI_QKV_ROPE ? LNB_STREAM(EPI_QKV_ROPE)
+                                    : epi == EPI_QKV_ROPE_SLOT ? LNB_STREAM(EPI_QKV_ROPE_SLOT)
                                     : (epi == EPI_SILU_MUL && acc2 && p->nch == 2) ? mfma_stream_kernel<2, EPI_SILU_MUL> : nullptr;
 #undef LNB_STREAM
     if (!k) return hipErrorInvalidValue;
-    form_ran(acc2 ? Form::MFMA_STREAM_C2 : Form::MFMA_STREAM_C1, epi);
+    form_ran(acc2 ? Form::MFMA_STREAM_C2 : Form::MFMA_STREAM_C1, tally_epi(epi));
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, q);
     return hipGetLastError();
 }
@@ -5599,6 +5687,8 @@ extern "C" hipError_t lnbk_batch_prepare(void) {             // raise the dynami
         if (pair_kernel(ep)) e = raise_lds(pair_kernel(ep));
         if (e == hipSuccess) e = lnbk_gemm_stream(nullptr, ep, 0, nullptr);
     }
+    if (e == hipSuccess) e = raise_lds(pair_kernel(EPI_QKV_ROPE_SLOT));
+    if (e == hipSuccess) e = lnbk_gemm_stream(nullptr, EPI_QKV_ROPE_SLOT, 0, nullptr);
     done = e == hipSuccess;
     return e;
 }
@@ -5684,7 +5774,7 @@ template <int EPI, int NCH> static hipError_t launch_gemm_stream(const GemmParam
         const int tpg = 4 / NCH, n_tg = (n_tiles + tpg - 1) / tpg;
         const dim3 g((unsigned)((n_tg + 3) / 4), (unsigned)ct);
         const size_t l = (size_t)2 * 16 * GS_PITCH * 4;             // (16 KiB + padding: within what every kernel gets)
-        form_ran(Form::GEMM_BLGP, EPI);
+        form_ran(Form::GEMM_BLGP, tally_epi(EPI));
         hipLaunchKernelGGL((gemm_blgp_kernel<EPI, NCH>), g, dim3(256), l, st, q);
         return hipGetLastError();
     }
@@ -5710,8 +5800,8 @@ template <int EPI, int NCH> static hipError_t launch_gemm_stream(const GemmParam
     const auto k = gs_kernel<EPI, NCH>(ntw, src, tt);
     if (!k) return hipErrorInvalidValue;
     // (the table's rows run source-major: copy 1 / 2 / 4 / 4.tt, row-broadcast the same four, chain 1 / 2 / 4)
-    form_ran((Form)((int)Form::GS_COPY_1 + 4 * src + (ntw == 1 ? 0 : ntw == 2 ? 1 : tt ? 3 : 2)), EPI);
-    form_ran(q.rows_fastest ? Form::GS_ORDER_ROWS : Form::GS_ORDER_TILES, EPI);
+    form_ran((Form)((int)Form::GS_COPY_1 + 4 * src + (ntw == 1 ? 0 : ntw == 2 ? 1 : tt ? 3 : 2)), tally_epi(EPI));
+    form_ran(q.rows_fastest ? Form::GS_ORDER_ROWS : Form::GS_ORDER_TILES, tally_epi(EPI));
     hipLaunchKernelGGL(k, grid, dim3(256), lds, st, q);
     return hipGetLastError();
 }
@@ -5720,6 +5810,7 @@ extern "C" hipError_t lnbk_gemm_stream(const GemmParams* p, int epi, int num_cus
         case EPI_STORE: return launch_gemm_stream<EPI_STORE, 1>(p, num_cus, st);
         case EPI_RESID: return launch_gemm_stream<EPI_RESID, 1>(p, num_cus, st);
         case EPI_QKV_ROPE: return launch_gemm_stream<EPI_QKV_ROPE, 1>(p, num_cus, st);
+        case EPI_QKV_ROPE_SLOT: return (p && !p->btab) ? hipErrorInvalidValue : launch_gemm_stream<EPI_QKV_ROPE_SLOT, 1>(p, num_cus, st);
         case EPI_SILU_MUL: return (p && p->nch != 2) ? hipErrorInvalidValue : launch_gemm_stream<EPI_SILU_MUL, 2>(p, num_cus, st);
         default: return hipErrorInvalidValue;
     }
@@ -5792,6 +5883,8 @@ extern "C" hipError_t lnbk_attn_ragged(const AttnRaggedParams* rp, hipStream_t s
         return hipGetLastError();
     });
 }
+// attention over a draft tree, the tree commit and the KV compaction of a tree verify pass (lnb_ctx_set_draft_branches)
+#include "lnb_tree_verify.h"
 
 // lnb_forward_append_many: per pass, the columns' tables from the call's row and member tables, and the argmax of the members' last rows (lnb_append_many.h)
 #include "lnb_append_many.h"

@@ -288,6 +288,15 @@ func (ic *InferenceContext) SetDraft(lt *LlamaTransformer, maxDraft int, ngramMi
 	return lnbCall(func() C.int { return C.lnb_ctx_set_draft(ic.handle, C.int(maxDraft), C.int(ngramMin), C.int(ngramMax), p, C.int(len(corpus))) })
 }
 
+// SetDraftBranches lets a pass draft a tree: up to nBranches (1..LNB_MAX_DRAFT_BRANCHES; 1 = the chain, the default) occurrences of the matched
+// n-gram are verified together (lnb_ctx_set_draft_branches).  The tokens and KV rows are the same.
+func (ic *InferenceContext) SetDraftBranches(lt *LlamaTransformer, nBranches int) error {
+	if err := ic.attach(lt); err != nil {
+		return err
+	}
+	return lnbCall(func() C.int { return C.lnb_ctx_set_draft_branches(ic.handle, C.int(nBranches)) })
+}
+
 // SetBatchedAttention picks the attention form of DecodeSpeculativeUntil's verify passes: past longThreshold positions (negative: keep;
 // default: never, unless the context is beyond the one-workgroup kernels' reach) the long-context kernels.  forceZseq 1: every column
 // walks the serial f64 sum.  The bits are the same either way.

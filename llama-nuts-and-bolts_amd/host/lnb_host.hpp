@@ -275,6 +275,9 @@ public:
     void SetDraft(int maxDraft, int ngramMin, int ngramMax, const std::vector<TokenId>& corpus = {}) {
         check(lnb_ctx_set_draft(h_, maxDraft, ngramMin, ngramMax, corpus.empty() ? nullptr : corpus.data(), (int)corpus.size()));
     }
+    // a tree of drafts per pass (lnb_ctx_set_draft_branches): up to nBranches (1..LNB_MAX_DRAFT_BRANCHES; 1 = the chain, the default) occurrences of the
+    // matched n-gram verified together; same tokens and KV rows
+    void SetDraftBranches(int nBranches) { check(lnb_ctx_set_draft_branches(h_, nBranches)); }
     // attention form of DecodeSpeculativeUntil's verify passes: past longThreshold positions (default: never, unless the context is beyond the
     // one-workgroup kernels' reach) the long-context kernels; forceZseq: always walk the serial f64 sum.  Same bits either way.
     void SetBatchedAttention(int longThreshold = -1, int forceZseq = 0) { check(lnb_ctx_set_batched_attention(h_, longThreshold, forceZseq)); }

@@ -69,7 +69,7 @@ EXPORTS = [
     "lnb_decode_sample_until", "lnb_batch_decode_sample_until", "lnb_op_sample", "lnb_profile_sample",
     "lnb_decode_sample_rules_until", "lnb_batch_decode_sample_rules_until", "lnb_op_sample_rules", "lnb_profile_sample_rules",
     "lnb_forward_append", "lnb_forward_score_append",
-    "lnb_ctx_set_draft", "lnb_decode_speculative_until", "lnb_op_ngram_draft",
+    "lnb_ctx_set_draft", "lnb_decode_speculative_until", "lnb_op_ngram_draft", "lnb_ctx_set_draft_branches", "lnb_op_tree_draft",
     "lnb_batch_set_attention", "lnb_ctx_set_batched_attention", "lnb_batch_attention_form", "lnb_ctx_verify_attention_form", "lnb_batch_set_shared_prefix",
     "lnb_ctx_create_long", "lnb_ctx_max_rows",
     "lnb_ctx_set_rows_attention", "lnb_ctx_append_attention_form",
@@ -88,6 +88,7 @@ EXPORTS = [
 EPILOGUES = {"store": 0, "qkv_rope": 1, "resid": 2, "silu_mul": 3}      # EPI_* of csrc/lnb_device.h: the second index of the launch tally
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
 MAX_DRAFT = 15           # LNB_MAX_DRAFT of include/lnb.h (tests/test_speculative_cpu.py compares them)
+MAX_DRAFT_BRANCHES = 4   # LNB_MAX_DRAFT_BRANCHES of include/lnb.h
 MAX_SEQ_LEN = 131072     # LNB_MAX_SEQ_LEN of include/lnb.h (tests/test_long_context_cpu.py compares them)
 MAX_FORK = 128           # LNB_MAX_FORK of include/lnb.h (tests/test_prefix_fork_cpu.py compares them)
 ABI_VERSION = 6          # LNB_ABI_VERSION of include/lnb.h this binding was written against (tests/test_cabi.py compares it with the header's)
@@ -318,6 +319,8 @@ def lib():
     L.lnb_decode_speculative_until.argtypes = [vp, vp, C.c_int, C.c_int32, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                C.POINTER(SpecStats), f32p]
     L.lnb_op_ngram_draft.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_int)]
+    L.lnb_ctx_set_draft_branches.argtypes = [vp, C.c_int]
+    L.lnb_op_tree_draft.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
     L.lnb_decode_speculative_sample_until.argtypes = [vp, C.POINTER(Sampler), vp, C.c_int, C.c_int32, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                       C.POINTER(SpecStats), f32p]
     L.lnb_decode_speculative_sample_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Sampler), C.POINTER(vp), vp, vp, vp, C.c_int, C.c_int, vp, vp, vp,
@@ -852,11 +855,13 @@ class InferenceContext:
         _chk(self.L.lnb_ctx_read_emitted_probs(self.h, int(first), n, *[ptr(r[f]) for f in ("tok_logit", "tok_prob", "log_z", "w_tok", "w_kept", "ids", "logits", "probs")]))
         return r
 
-    def set_draft(self, max_draft, ngram_min=1, ngram_max=4, corpus=()):
+    def set_draft(self, max_draft, ngram_min=1, ngram_max=4, corpus=(), branches=1):
         """n-gram drafts for decode_speculative_until: up to max_draft (0..MAX_DRAFT; 0 = off, the default) tokens per pass, looked up with
-        n-grams of ngram_min..ngram_max tokens in the running text, then in corpus (copied to the device)"""
+        n-grams of ngram_min..ngram_max tokens in the running text, then in corpus (copied to the device).  branches (1..MAX_DRAFT_BRANCHES,
+        lnb_ctx_set_draft_branches): that many occurrences of the matched n-gram are drafted as one tree per pass; 1 = the chain"""
         a = np.ascontiguousarray(corpus, dtype=np.int32)
         _chk(self.L.lnb_ctx_set_draft(self.h, int(max_draft), int(ngram_min), int(ngram_max), _p(a) if a.size else None, int(a.size)))
+        _chk(self.L.lnb_ctx_set_draft_branches(self.h, int(branches)))
         return self
 
     def set_batched_attention(self, long_threshold=-1, force_zseq=0):
@@ -1453,6 +1458,18 @@ def op_ngram_draft(text, corpus=(), ngram_min=1, ngram_max=4, max_draft=MAX_DRAF
     _chk(lib().lnb_op_ngram_draft(device, _p(t) if t.size else None, int(t.size), _p(c) if c.size else None, int(c.size),
                                   int(ngram_min), int(ngram_max), int(max_draft), _p(out), C.byref(n)))
     return out[:n.value].copy()
+
+
+def op_tree_draft(text, corpus=(), ngram_min=1, ngram_max=4, max_draft=MAX_DRAFT, branches=2, device=0):
+    """tree_draft_kernel on host arrays (lnb_op_tree_draft): the trie of the up to `branches` latest continuations of `text`
+    -> (tokens, parent, depth) int32 arrays of one entry per node; node 0 is the caller's token (tokens[0] = parent[0] = -1)"""
+    t = np.ascontiguousarray(text, dtype=np.int32)
+    c = np.ascontiguousarray(corpus, dtype=np.int32)
+    tok, par, dep = (np.empty(16, dtype=np.int32) for _ in range(3))
+    n = C.c_int(0)
+    _chk(lib().lnb_op_tree_draft(device, _p(t) if t.size else None, int(t.size), _p(c) if c.size else None, int(c.size),
+                                 int(ngram_min), int(ngram_max), int(max_draft), int(branches), _p(tok), _p(par), _p(dep), C.byref(n)))
+    return tok[:n.value].copy(), par[:n.value].copy(), dep[:n.value].copy()
 
 
 def op_spec_sample_accept(logits_u16, sampler, pos0, col_tokens, stop_ids=(), device=0):

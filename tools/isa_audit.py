@@ -191,6 +191,9 @@ def main(asm_path=None):
     SGPR_SPILL_OK = ("attn_gqa_kernel", "attn_one_kernel", "_Z13sample_kernelP", "_Z19batch_sample_kernelP",      # (these two kernels and no other *sample_kernel)
                      "_Z25spec_sample_commit_kernelP", "_Z30spec_many_sample_commit_kernel6SmPass", "_Z19sample_rules_kernelP", "_Z25batch_sample_rules_kernelP",
                      "_Z31spec_sample_rules_commit_kernelP", "_Z36spec_many_sample_rules_commit_kernel6SmPass",
+                     # (lnb_tree_verify.h: spec_sample_commit_kernel with the tree walk behind the ticket -- the same sample_block inlined, the same 17 scalars in VGPR
+                     # lanes; scratch 0, vgpr_spill_count 0)
+                     "_Z25tree_sample_commit_kernelP",
                      # (lnb_emit_probs.h: the same sample_block inlined into the token launches with the emitted entry -- emit_sample_kernel<RULES, BATCH> 17 / 12 / 12 / 7
                      # and emit_spec_commit_kernel<RULES> 18 / 15 scalars in VGPR lanes; what their epilogues need waits in the LDS; scratch 0, vgpr_spill_count 0)
                      # (the six instantiations by name: another one has to be looked at and added)
