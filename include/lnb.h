@@ -632,6 +632,45 @@ int lnb_op_sample_rules(int device, const uint16_t* logits_bf16, int rows, int V
                         lnb_sample_info* info);
 /* lnb_profile_sample with the rules launch (sample_rules_kernel on the context's tables as the last rules call left them; rules NULL: all off) */
 int lnb_profile_sample_rules(lnb_ctx* c, const lnb_sampler* sampler, const lnb_logit_rules* rules, int pos, int iters, float* avg_ms_out);
+/* ---- a token automaton in the sampling loops: keep a generation inside a grammar, on the device ----
+ * A grammar engine compiles to a deterministic automaton over token ids: in state s the tokens of row s are allowed, taking token t leads to next(s, t).
+ * The caller brings it as CSR over states (no grammar compiler lives here); a context that holds one runs its sampling loops under a step 0d behind
+ * 0a-0c of the rule above:
+ *   0d. for every j OUTSIDE the row of the context's state: f = -inf (bits 0xFF80); entries inside the row are untouched
+ * Steps 1-8 and 4b run on that row; temperature == 0 is ml.Argmax of it.  A forbidden entry is never a candidate of step 2, so the token is what the
+ * rule gives for the same row with those entries replaced by -inf BEFORE step 0a (0a-0c map -inf to -inf for every accepted rule set): that is
+ * tests/logit_rules_ref.py on a pre-masked row, and lnb_logit_rules with -inf biases wherever the forbidden set fits in LNB_MAX_LOGIT_BIAS ids.
+ * After a token t >= 0 is emitted by a generation that is not finished: state' = edge_next[row_ptr[state] + rank(t)], rank(t) = the number of allowed
+ * tokens below t in the state's row (the row is ascending, so that IS t's edge: no search).  A state with an empty row is FINAL: reaching it finishes
+ * the generation exactly as a stop id does (token emitted, finished = 1, everything frozen).  t == -1 (no candidate) and a frozen generation leave the
+ * state alone.  The token is a pure function of (logits row, sampler, rules, counted text, pos, state): a run gives the same tokens and end state
+ * whatever its chunking, and a batch member gives those of its own single run.
+ * On the device: a dense bitset mask[n_states][ceil(V / 32)], row_ptr and edge_next (lnb_automaton_info: device_bytes); edge_token is only read by the
+ *   build launch, which also checks ascending tokens inside a row, token < V and next < n_states and names the first offending edge.
+ * lnb_automaton_create: host checks first, each naming its argument (NULL; n_states < 1; row_ptr not starting at 0 or not monotone).  m gives V and the device.
+ * lnb_automaton_destroy: refused while a context holds the automaton.
+ * lnb_ctx_set_automaton(c, a, state): a == NULL detaches.  Arguments are checked before the handle; refused for stage handles, for an automaton of
+ *   another model handle or vocabulary, for state outside [0, n_states), and -- attaching or detaching -- while the context belongs to a live batch;
+ *   with the automaton the context already holds it only re-sets the state (a stream-ordered store) and is allowed there.
+ * lnb_ctx_automaton_state: a stream-ordered read of the state word; -1: none attached.
+ * Honoured by lnb_decode_sample_until, lnb_decode_sample_rules_until and their batch forms (members without an automaton are untouched in the same
+ *   launch), through token launches and captured graphs of their own: a context without an automaton launches and captures exactly what it did.
+ * Refused while attached, naming lnb_ctx_set_automaton, before any cache is written: the greedy loops (use temperature 0 through the sampling call),
+ *   every speculative call (the _many decode calls among them; lnb_forward_append_many samples nothing and stays open), pipeline ticks, a context with lnb_ctx_set_emitted_probs or lnb_ctx_set_token_probs on, and a call whose context
+ *   is already in a final state.  Those, and any grammar compiler, are out of scope.
+ * lnb_op_sample_automaton: the kernel on host rows, as lnb_op_sample_rules (rules NULL: all off), row i in state states[i]; next_states_out[i] = the
+ *   state behind tokens_out[i] (states[i] itself for token -1). */
+typedef struct lnb_automaton lnb_automaton;
+/* CSR over states: row s = edges [row_ptr[s], row_ptr[s+1]), edge_token strictly ascending inside a row, edge_next in [0, n_states) */
+int lnb_automaton_create(lnb_model* m, int n_states, const int64_t* row_ptr, const int32_t* edge_token, const int32_t* edge_next, lnb_automaton** out);
+int lnb_automaton_destroy(lnb_automaton* a);
+int lnb_automaton_info(const lnb_automaton* a, int* n_states, int64_t* n_edges, int64_t* device_bytes);
+int lnb_ctx_set_automaton(lnb_ctx* c, lnb_automaton* a, int state);
+int lnb_ctx_automaton_state(lnb_ctx* c, int* state);
+int lnb_op_sample_automaton(int device, const uint16_t* logits_bf16, int rows, int V, const lnb_sampler* samplers,
+                            const lnb_logit_rules* rules /* [rows] or NULL */, const uint32_t* counts /* or NULL */, const int32_t* pos, const uint64_t* draws,
+                            int n_states, const int64_t* row_ptr, const int32_t* edge_token, const int32_t* edge_next,
+                            const int32_t* states /* [rows] */, int32_t* tokens_out, int32_t* next_states_out, lnb_sample_info* info);
 /* ---- the emitted token's record: the probability of the token a sampling or speculative loop actually produced ----
  * lnb_ctx_set_emitted_probs: top_k -1 (the default: off -- the same graphs, launches and bits as without the feature) or 0..LNB_MAX_TOP_K.  Whole-model
  *   contexts only; drops the context's captured graphs; refused while the context belongs to a live batch; refused while lnb_ctx_set_token_probs is on, as

@@ -68,6 +68,9 @@ hipError_t lnbk_batch_sample(const uint16_t* logits, int V, const double* etab, 
 hipError_t lnbk_sample_rules(const uint16_t* logits, int V, int rows, const double* etab, const LnbSampler* smp, const LnbRulesDev* rules, int32_t* next_token,
                              StepState* state, int32_t* out_tokens, int out_cap, int advance, const int32_t* pos, const unsigned long long* draws, LnbSampleInfo* info,
                              hipStream_t st);
+hipError_t lnbk_automaton_build(const DfaBuildParams* p, hipStream_t st);
+hipError_t lnbk_sample_automaton(const DfaTokParams* p, int rows, hipStream_t st);
+hipError_t lnbk_batch_sample_automaton(const DfaTokParams* p, int nseq, hipStream_t st);
 hipError_t lnbk_batch_sample_rules(const uint16_t* logits, int V, const double* etab, const LnbSampler* smp, const LnbRulesDev* rules, const BatchTab* tab, int nseq,
                                    hipStream_t st);
 hipError_t lnbk_rules_tables(uint32_t* counts, int V, const int32_t* counted, int n_counted, int32_t token, uint16_t* bias, const int32_t* ids, const float* values,
@@ -183,7 +186,8 @@ static hipError_t event_create(Event& e, unsigned flags = hipEventDefault) { ret
 static hipError_t stream_create(Stream& s, unsigned flags) { return s.fill([&](hipStream_t* q) { return hipStreamCreateWithFlags(q, flags); }); }
 // which captured step: the token launch that ends it, and the attention form its launches bake in
 // (the _EMIT families: the same steps with the emitted token's record, lnb_ctx_set_emitted_probs -- families of their own, so neither drops or recaptures the other)
-enum GraphLaunch { GL_GREEDY = 0, GL_SAMPLE, GL_STAGE, GL_SAMPLE_RULES, GL_SAMPLE_EMIT, GL_SAMPLE_RULES_EMIT, GL_COUNT };
+// (GL_SAMPLE_DFA: the sampling / rules step of a context or batch that holds a token automaton, lnb_ctx_set_automaton -- again a family of its own)
+enum GraphLaunch { GL_GREEDY = 0, GL_SAMPLE, GL_STAGE, GL_SAMPLE_RULES, GL_SAMPLE_EMIT, GL_SAMPLE_RULES_EMIT, GL_SAMPLE_DFA, GL_COUNT };
 static bool gl_rules(GraphLaunch l) { return l == GL_SAMPLE_RULES || l == GL_SAMPLE_RULES_EMIT; }
 static bool gl_emit(GraphLaunch l) { return l == GL_SAMPLE_EMIT || l == GL_SAMPLE_RULES_EMIT; }
 enum GraphForm { GF_SHORT = 0, GF_LONG, GF_ROWS, GF_SHARED, GF_TREE, GF_COUNT };     // (0, 1, 2: also what lnb_ctx_verify_attention_form reports; GF_SHARED: a batch with a shared prefix;
@@ -304,6 +308,9 @@ struct lnb_ctx {
         Dev<uint32_t> counts; Dev<uint16_t> bias; DevGrown<char> stage; Dev<LnbRulesDev> d_rules;
         LnbRulesDev h_rules{};             // what the last call copied to d_rules (it must outlive the copy)
     } rl;
+    // the token automaton (lnb_ctx_set_automaton; lnb_automaton.h): the handle, the device struct its graphs point at (the state word lives there) and
+    // the state as the host last knew it -- set by lnb_ctx_set_automaton, read back by every call that ran under it (a final one refuses the next call)
+    struct lnb_automaton* dfa = nullptr; Dev<LnbDfaDev> d_dfa; LnbDfaDev h_dfa{}; int dfa_state = -1;
     PipeLink link;                         // pipeline stage (lnb_pipeline_tick): events towards / from the exchange stream
     int dev_pos = -1;                      // position the device-side StepState will hold when the stream reaches this point (-1: unknown)
     bool attn_causal = false;              // set by lnb_forward_append around its multi-row call: the attention launches take the true causal mask (AttnParams::causal)
@@ -364,6 +371,12 @@ struct lnb_ctx {
 // the set_state launch" shortcut (dev_pos) can never act on a position some OTHER entry point has since overwritten (lnb_forward,
 // lnb_decode_greedy and lnb_profile_kernel may be mixed with ticks on one context).  known = false: the caller is about to advance
 // the state on the device by itself (greedy loop) and the host stops tracking it.
+// what every entry point that does not run under a token automaton says to a context that holds one (include/lnb.h: lnb_ctx_set_automaton)
+static int dfa_refuse(const lnb_ctx* c, const char* who) {
+    if (!c->dfa) return 0;
+    return fail("%s: the context holds a token automaton (lnb_ctx_set_automaton), which this entry point does not run under: detach it first "
+                "(lnb_ctx_set_automaton(ctx, NULL, 0))", who);
+}
 static hipError_t ctx_set_state(lnb_ctx* c, int pos, int n_out, bool known, bool honour_stop = false) {
     c->dev_pos = known ? pos : -1;
     return lnbk_set_state(c->st, pos, n_out, honour_stop ? 1 : 0, c->stream);
@@ -1002,6 +1015,7 @@ static int ctx_alloc(lnb_ctx* c) {
     return 0;
 }
 
+static void ctx_drop_automaton(lnb_ctx* c);
 extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
     if (!c) return 0;
     // a batch bakes its members' device pointers (state words, token words, caches) into its tables and captured graphs: freeing a member
@@ -1011,6 +1025,7 @@ extern "C" int lnb_ctx_destroy(lnb_ctx* c) {
     hipSetDevice(c->m->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     for (lnb_batch* b : c->sp_b) if (b) lnb_batch_destroy(b);      // the verify batches: their tables hold this context's pointers
+    ctx_drop_automaton(c);
     delete c;
     return 0;
 }
@@ -1718,7 +1733,12 @@ static int enqueue_decode_step(lnb_ctx* c, GraphLaunch launch = GL_GREEDY) {
         HIPCHK(lnbk_token_probs(&p, c->stream));
     }
     if (gl_emit(launch)) { if (enqueue_emit_token(c, gl_rules(launch))) return -1; }
-    else if (launch == GL_SAMPLE_RULES)
+    else if (launch == GL_SAMPLE_DFA) {                      // the rules launch under the context's automaton (lnb_automaton.h)
+        DfaTokParams t{};
+        t.logits = c->logits; t.V = m->a.vocab_size; t.etab = m->prob_etab; t.smp = c->d_smp; t.rules = c->rl.d_rules;
+        t.next_token = c->dtok; t.st = c->st; t.out_tokens = c->dout; t.out_cap = c->dout_cap; t.advance = 1; t.dfa = c->d_dfa;
+        HIPCHK(lnbk_sample_automaton(&t, 1, c->stream));
+    } else if (launch == GL_SAMPLE_RULES)
         HIPCHK(lnbk_sample_rules(c->logits, m->a.vocab_size, 1, m->prob_etab, c->d_smp, c->rl.d_rules, c->dtok, c->st, c->dout, c->dout_cap, 1, nullptr, nullptr, nullptr, c->stream));
     else if (launch == GL_SAMPLE) HIPCHK(lnbk_sample(c->logits, m->a.vocab_size, 1, m->prob_etab, c->d_smp, c->dtok, c->st, c->dout, c->dout_cap, 1, nullptr, nullptr, nullptr, c->stream));
     else if (!skip) HIPCHK(lnbk_argmax(c->logits, m->a.vocab_size, c->dtok, c->st, c->dout, c->dout_cap, 1, c->stream));
@@ -1952,6 +1972,132 @@ static int rules_tables(lnb_ctx* c, const lnb_logit_rules* r, const int32_t* cou
     *out = LnbRulesDev{r->repetition_penalty, r->presence_penalty, r->frequency_penalty, r->min_p, c->rl.counts, r->n_bias > 0 ? (const lnbs_u16*)c->rl.bias.get() : nullptr};
     return 0;
 }
+// ---- the token automaton of the sampling loops (include/lnb.h: lnb_ctx_set_automaton; lnb_automaton.h) -------------------------------------
+// The handle owns the three device arrays; contexts that hold it count in `users` and point their LnbDfaDev at them.  row_ptr stays on the host too:
+// whether a state is final is asked before every call.
+struct lnb_automaton {
+    lnb_model* m = nullptr; int device = 0, V = 0, words = 0, n_states = 0, users = 0;
+    int64_t n_edges = 0; size_t bytes = 0;
+    std::vector<int64_t> row_ptr;
+    Dev<uint32_t> mask; Dev<long long> d_row_ptr; Dev<int32_t> edge_next;
+    bool final_state(int s) const { return row_ptr[s + 1] == row_ptr[s]; }
+};
+// what the host can check without reading an edge, each by its argument's name
+static int automaton_host_check(const char* who, int n_states, const int64_t* row_ptr, const int32_t* edge_token, const int32_t* edge_next) {
+    if (!row_ptr) return fail("%s: null argument (row_ptr)", who);
+    if (!edge_token) return fail("%s: null argument (edge_token)", who);
+    if (!edge_next) return fail("%s: null argument (edge_next)", who);
+    if (n_states < 1) return fail("%s: n_states must be >= 1 (got %d)", who, n_states);
+    if (row_ptr[0] != 0) return fail("%s: row_ptr[0] must be 0 (got %lld)", who, (long long)row_ptr[0]);
+    for (int s = 0; s < n_states; s++)
+        if (row_ptr[s + 1] < row_ptr[s]) return fail("%s: row_ptr must not decrease (row_ptr[%d] = %lld behind %lld)", who, s + 1, (long long)row_ptr[s + 1], (long long)row_ptr[s]);
+    return 0;
+}
+// the three device arrays of a checked CSR on the current device: upload, the build launch, its error word
+static int automaton_build(const char* who, lnb_automaton* a, int V, int n_states, const int64_t* row_ptr, const int32_t* edge_token, const int32_t* edge_next) {
+    a->V = V; a->words = (V + 31) / 32; a->n_states = n_states; a->n_edges = row_ptr[n_states];
+    a->row_ptr.assign(row_ptr, row_ptr + n_states + 1);
+    const size_t nm = (size_t)n_states * a->words * 4, nr = (size_t)(n_states + 1) * 8, ne = (size_t)std::max<int64_t>(a->n_edges, 1) * 4;
+    a->bytes = nm + nr + ne;
+    Dev<int32_t> d_tok; Dev<unsigned long long> d_err;
+    if (dev_alloc(a->mask, nm) != hipSuccess || dev_alloc(a->d_row_ptr, nr) != hipSuccess || dev_alloc(a->edge_next, ne) != hipSuccess ||
+        dev_alloc(d_tok, ne) != hipSuccess || dev_alloc(d_err, 8) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("%s: n_states = %d and %lld edges need %zu bytes of device memory (a mask row of %d bytes per state), which hipMalloc does not give", who, n_states,
+                    (long long)a->n_edges, a->bytes + ne, a->words * 4);
+    }
+    unsigned long long err = ~0ull;
+    HIPCHK(hipMemcpy(a->d_row_ptr, row_ptr, nr, hipMemcpyHostToDevice));
+    if (a->n_edges) { HIPCHK(hipMemcpy(a->edge_next, edge_next, (size_t)a->n_edges * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_tok, edge_token, (size_t)a->n_edges * 4, hipMemcpyHostToDevice)); }
+    HIPCHK(hipMemcpy(d_err, &err, 8, hipMemcpyHostToDevice));
+    const DfaBuildParams p{a->d_row_ptr, d_tok, a->edge_next, a->mask, d_err, n_states, V, a->words, 0};
+    HIPCHK(lnbk_automaton_build(&p, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(&err, d_err, 8, hipMemcpyDeviceToHost));
+    if (err != ~0ull) {                                      // the first offending edge, by what is wrong with it
+        const int64_t e = (int64_t)err;
+        const int s = (int)(std::upper_bound(a->row_ptr.begin(), a->row_ptr.end(), e) - a->row_ptr.begin()) - 1;
+        const int t = edge_token[e], nx = edge_next[e];
+        if (t < 0 || t >= V) return fail("%s: edge_token[%lld] = %d (state %d) is outside the vocabulary [0, %d)", who, (long long)e, t, s, V);
+        if (nx < 0 || nx >= n_states) return fail("%s: edge_next[%lld] = %d (state %d) is outside [0, %d)", who, (long long)e, nx, s, n_states);
+        return fail("%s: edge_token[%lld] = %d (state %d) does not ascend: the edge in front of it has token %d", who, (long long)e, t, s, edge_token[e - 1]);
+    }
+    return 0;
+}
+extern "C" int lnb_automaton_create(lnb_model* m, int n_states, const int64_t* row_ptr, const int32_t* edge_token, const int32_t* edge_next, lnb_automaton** out) {
+    if (!out) return fail("lnb_automaton_create: null argument (out)");
+    if (automaton_host_check("lnb_automaton_create", n_states, row_ptr, edge_token, edge_next)) return -1;
+    if (!m) return fail("lnb_automaton_create: null argument (m)");
+    if (!m->first() || !m->last()) return fail("lnb_automaton_create needs a whole-model handle (pipeline stages sample nothing)");
+    if (sample_vocab_check(m->a.vocab_size)) return -1;
+    HIPCHK(hipSetDevice(m->device));
+    lnb_automaton* a = new lnb_automaton;
+    a->m = m; a->device = m->device;
+    if (automaton_build("lnb_automaton_create", a, m->a.vocab_size, n_states, row_ptr, edge_token, edge_next)) { delete a; return -1; }
+    *out = a;
+    return 0;
+}
+extern "C" int lnb_automaton_destroy(lnb_automaton* a) {
+    if (!a) return 0;
+    if (a->users > 0) return fail("lnb_automaton_destroy: %d context(s) hold the automaton: detach it first (lnb_ctx_set_automaton(ctx, NULL, 0))", a->users);
+    hipSetDevice(a->device);
+    delete a;
+    return 0;
+}
+extern "C" int lnb_automaton_info(const lnb_automaton* a, int* n_states, int64_t* n_edges, int64_t* device_bytes) {
+    if (!a) return fail("lnb_automaton_info: null argument (a)");
+    if (n_states) *n_states = a->n_states;
+    if (n_edges) *n_edges = a->n_edges;
+    if (device_bytes) *device_bytes = (int64_t)a->bytes;
+    return 0;
+}
+static void ctx_drop_automaton(lnb_ctx* c) { if (c->dfa) { c->dfa->users--; c->dfa = nullptr; c->dfa_state = -1; } }
+extern "C" int lnb_ctx_set_automaton(lnb_ctx* c, lnb_automaton* a, int state) {
+    if (!c) return fail("lnb_ctx_set_automaton: null argument (c)");
+    if (state < 0) return fail("lnb_ctx_set_automaton: state must be >= 0 (got %d)", state);
+    lnb_model* m = c->m;
+    if (!m->first() || !m->last()) return fail("lnb_ctx_set_automaton needs a whole-model handle (pipeline stages sample nothing)");
+    if (a && (a->m != m || a->V != m->a.vocab_size)) return fail("lnb_ctx_set_automaton: the automaton was created for another lnb_model handle or vocabulary");
+    if (a && state >= a->n_states) return fail("lnb_ctx_set_automaton: state %d is outside [0, %d)", state, a->n_states);
+    HIPCHK(hipSetDevice(m->device));
+    if (a && a == c->dfa) {                                  // only the state moves: one stream-ordered store into the struct the graphs point at
+        c->dfa_state = state;
+        HIPCHK(hipMemcpyAsync(&c->d_dfa.get()->state, &c->dfa_state, 4, hipMemcpyHostToDevice, c->stream));
+        return 0;
+    }
+    if (c->batch_users > 0)
+        return fail("lnb_ctx_set_automaton: the context is a member of %d live batch(es): which members hold an automaton is fixed until they are destroyed", c->batch_users);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    ctx_drop_automaton(c);
+    if (!a) return 0;
+    if (!c->d_dfa) HIPCHK(dev_alloc(c->d_dfa, sizeof(LnbDfaDev)));
+    c->h_dfa = LnbDfaDev{state, a->words, a->n_states, 0, a->mask, a->d_row_ptr, a->edge_next};
+    HIPCHK(hipMemcpyAsync(c->d_dfa, &c->h_dfa, sizeof(LnbDfaDev), hipMemcpyHostToDevice, c->stream));
+    c->dfa = a; c->dfa_state = state; a->users++;
+    return 0;
+}
+extern "C" int lnb_ctx_automaton_state(lnb_ctx* c, int* state) {
+    if (!c || !state) return fail("lnb_ctx_automaton_state: null argument");
+    *state = -1;
+    if (!c->dfa) return 0;
+    HIPCHK(hipSetDevice(c->m->device));
+    HIPCHK(hipMemcpyAsync(&c->dfa_state, &c->d_dfa.get()->state, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *state = c->dfa_state;
+    return 0;
+}
+// what a sampling call asks of a context that holds an automaton, before any cache is written (frozen: a batch member that sits the call out)
+static int automaton_call_check(const lnb_ctx* c, const char* who, bool frozen = false) {
+    if (c->emit_k >= 0)
+        return fail("%sthe context holds a token automaton (lnb_ctx_set_automaton) and records emitted-token probabilities, which exclude each other: "
+                    "lnb_ctx_set_emitted_probs(ctx, -1) or lnb_ctx_set_automaton(ctx, NULL, 0) first", who);
+    if (c->top_k > 0)
+        return fail("%sthe context holds a token automaton (lnb_ctx_set_automaton) and records token probabilities, which exclude each other: "
+                    "lnb_ctx_set_token_probs(ctx, 0) or lnb_ctx_set_automaton(ctx, NULL, 0) first", who);
+    if (!frozen && c->dfa->final_state(c->dfa_state))
+        return fail("%sthe context's automaton is in the final state %d: nothing may follow (lnb_ctx_set_automaton(ctx, a, state) starts again)", who, c->dfa_state);
+    return 0;
+}
 struct RulesCall { const lnb_logit_rules* rules; const int32_t* counted; int n_counted; };      // one generation's rules and counted text
 static const char* const k_sample_probs_advice ="records token probabilities, whose records promise ids[i * k] == out_tokens[i] -- a sampled token does not keep that: "
                                                  "switch them off (lnb_ctx_set_token_probs(ctx, 0)) for a sampling call";
@@ -2051,6 +2197,13 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     lnb_model* m = c->m;
     if (rc && rules_check(rc->rules, rc->counted, rc->n_counted, m->a.vocab_size, "")) return -1;         // (the ids against the vocabulary, now that it is known)
     if (!m->first() || !m->last()) return fail("%s needs a whole-model handle", rc ? "lnb_decode_sample_rules_until" : smp ? "lnb_decode_sample_until" : "lnb_decode_greedy");
+    if (!smp && dfa_refuse(c, "lnb_decode_greedy (the greedy loops: use temperature 0 through lnb_decode_sample_until)")) return -1;
+    static const lnb_logit_rules rules_off = {1.0f, 0.0f, 0.0f, 0.0f, 0, 0, nullptr, nullptr};
+    const RulesCall rc_off{&rules_off, nullptr, 0};
+    if (c->dfa) {                                            // the automaton's token launch is the rules launch: all-off rules are the plain sampler, bit for bit
+        if (automaton_call_check(c, "")) return -1;
+        if (!rc) rc = &rc_off;
+    }
     if (smp) {
         if (sample_vocab_check(m->a.vocab_size)) return -1;
         if (c->top_k > 0) return fail("the context %s", k_sample_probs_advice);
@@ -2066,7 +2219,7 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     if (smp && !c->d_smp) HIPCHK(dev_alloc(c->d_smp, sizeof(LnbSampler)));
     if (rc && !c->rl.d_rules) HIPCHK(dev_alloc(c->rl.d_rules, sizeof(LnbRulesDev)));
     const bool emit = smp && c->emit_k >= 0;
-    const GraphLaunch launch = rc ? (emit ? GL_SAMPLE_RULES_EMIT : GL_SAMPLE_RULES) : smp ? (emit ? GL_SAMPLE_EMIT : GL_SAMPLE) : GL_GREEDY;
+    const GraphLaunch launch = c->dfa ? GL_SAMPLE_DFA : rc ? (emit ? GL_SAMPLE_RULES_EMIT : GL_SAMPLE_RULES) : smp ? (emit ? GL_SAMPLE_EMIT : GL_SAMPLE) : GL_GREEDY;
     if (use_graph && capture_decode_graphs(c, start_pos, n_steps, launch)) return -1;
     c->tp_last_k = 0; c->tp_last_n = 0; c->em_last_k = -1; c->em_last_n = 0;
     if (smp) HIPCHK(hipMemcpyAsync(c->d_smp, smp, sizeof(LnbSampler), hipMemcpyHostToDevice, st));
@@ -2092,6 +2245,7 @@ static int decode_greedy_impl(lnb_ctx* c, int32_t token, int start_pos, int n_st
     HIPCHK(hipMemcpyAsync(c->h_io + 1, c->derr, 4, hipMemcpyDeviceToHost, st));
     StepState hs{};
     if (n_generated) HIPCHK(hipMemcpyAsync(&hs, c->st, sizeof(StepState), hipMemcpyDeviceToHost, st));
+    if (c->dfa) HIPCHK(hipMemcpyAsync(&c->dfa_state, &c->d_dfa.get()->state, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (ms_out) HIPCHK(hipEventElapsedTime(ms_out, c->ev0, c->ev1));
     if (c->h_io[1]) return fail("generated token id is outside the vocabulary");
@@ -2319,6 +2473,7 @@ struct lnb_batch {
     lnb_ctx* sp_src = nullptr; int sp_n = 0;
     Dev<uint64_t> sp_idx; Dev<double> sp_z;
     Dev<LnbSampler> d_smp;                 // the device array of n samplers the sampling steps point at
+    Dev<LnbDfaDev*> d_dfa; std::vector<LnbDfaDev*> h_dfa;           // ... and for the automaton steps: every member's device struct, nullptr for a member without one
     Dev<LnbRulesDev> d_rules; std::vector<LnbRulesDev> h_rules;      // the same for the rules steps: every member's rules and ITS CONTEXT's tables (BatchTab stays as it is)
     // a verify batch whose columns run the multi-row long-context pair (lnb_ctx_set_rows_attention, flags bit 1)
     bool attn_rows = false; int rows_zseq = 0;
@@ -2712,11 +2867,15 @@ static int enqueue_batch_pass(lnb_batch* b) {
 // One batched step of this model STAGE: the pass, and on the last stage the argmax (which advances every sequence's position); a stage
 // without the head advances the positions itself.  ring_in: the first stage of a multi-stage pipeline takes the tokens from the contiguous
 // words the last stage sent (lnb_pipeline_tick_batch).
-static int enqueue_batch_step(lnb_batch* b, bool ring_in = false, bool sample = false, bool rules = false) {
+static int enqueue_batch_step(lnb_batch* b, bool ring_in = false, bool sample = false, bool rules = false, bool dfa = false) {
     lnb_model* m = b->m;
     if (ring_in && m->first()) HIPCHK(lnbk_batch_scatter_ring(b->tab, b->ring, b->stream));
     if (enqueue_batch_pass(b)) return -1;
-    if (m->last() && sample && b->emit_k >= 0) {              // the same two token launches with every member's record into its own context's log
+    if (m->last() && dfa) {                                  // the rules launch with every member's automaton or none (lnb_automaton.h)
+        DfaTokParams t{};
+        t.logits = b->logits; t.V = m->a.vocab_size; t.etab = m->prob_etab; t.smp = b->d_smp; t.rules = b->d_rules; t.tab = b->tab; t.member_dfa = b->d_dfa;
+        HIPCHK(lnbk_batch_sample_automaton(&t, b->n, b->stream));
+    } else if (m->last() && sample && b->emit_k >= 0) {       // the same two token launches with every member's record into its own context's log
         TokProbParams p = tp_params(m, b->logits, b->n, b->emit_k, b->em_zpart, b->em_kpart, b->em_cnt, b->em_out, 1);
         p.park = b->em_park;
         HIPCHK(lnbk_emit_summary(&p, b->stream));
@@ -2779,6 +2938,22 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     if (!m->first() || !m->last())
         return fail("%s needs a whole-model handle; pipeline stages run their batches through lnb_pipeline_tick_batch",
                     rules ? "lnb_batch_decode_sample_rules_until" : smp ? "lnb_batch_decode_sample_until" : "lnb_batch_decode");
+    bool dfa = false;
+    for (int s = 0; s < b->n; s++) {
+        lnb_ctx* c = b->ctxs[s];
+        if (!c->dfa) continue;
+        dfa = true;
+        char who[32];
+        snprintf(who, sizeof who, "sequence %d: ", s);
+        if (!smp) return dfa_refuse(c, "lnb_batch_decode (the greedy loops: use temperature 0 through lnb_batch_decode_sample_until)");
+        if (automaton_call_check(c, who, start_pos[s] < 0)) return -1;
+    }
+    static const lnb_logit_rules rules_off = {1.0f, 0.0f, 0.0f, 0.0f, 0, 0, nullptr, nullptr};
+    std::vector<lnb_logit_rules> off_rules; std::vector<const int32_t*> off_counted; std::vector<int32_t> off_n;
+    if (dfa && !rules) {                                     // the automaton's token launch is the rules launch: all-off rules are the plain sampler, bit for bit
+        off_rules.assign(b->n, rules_off); off_counted.assign(b->n, nullptr); off_n.assign(b->n, 0);
+        rules = off_rules.data(); counted = off_counted.data(); n_counted = off_n.data();
+    }
     if (smp) {
         if (sample_vocab_check(m->a.vocab_size)) return -1;
         for (int s = 0; s < b->n; s++) if (b->ctxs[s]->top_k > 0) return fail("sequence %d: its context %s", s, k_sample_probs_advice);
@@ -2801,10 +2976,15 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     if (batch_select_form_at(b, start_pos)) return -1;
     const bool use_graph = knob(Knob::NO_GRAPH) == 0;
     const bool emit = smp && b->emit_k >= 0;
-    GraphExec& gslot = b->graphs.slot(rules ? (emit ? GL_SAMPLE_RULES_EMIT : GL_SAMPLE_RULES) : smp ? (emit ? GL_SAMPLE_EMIT : GL_SAMPLE) : GL_GREEDY, batch_graph_form(b));       // one captured step per form
+    GraphExec& gslot = b->graphs.slot(dfa ? GL_SAMPLE_DFA : rules ? (emit ? GL_SAMPLE_RULES_EMIT : GL_SAMPLE_RULES) : smp ? (emit ? GL_SAMPLE_EMIT : GL_SAMPLE) : GL_GREEDY, batch_graph_form(b));       // one captured step per form
     if (smp && !b->d_smp) HIPCHK(dev_alloc(b->d_smp, (size_t)LNB_BATCH_MAX * sizeof(LnbSampler)));
     if (rules && !b->d_rules) { HIPCHK(dev_alloc(b->d_rules, (size_t)LNB_BATCH_MAX * sizeof(LnbRulesDev))); b->h_rules.assign(LNB_BATCH_MAX, LnbRulesDev{}); }
-    if (use_graph && capture_once(gslot, st, [&] { return enqueue_batch_step(b, false, smp != nullptr, rules != nullptr); })) return -1;
+    if (dfa && !b->d_dfa) { HIPCHK(dev_alloc(b->d_dfa, (size_t)LNB_BATCH_MAX * sizeof(LnbDfaDev*))); b->h_dfa.assign(LNB_BATCH_MAX, nullptr); }
+    if (use_graph && capture_once(gslot, st, [&] { return enqueue_batch_step(b, false, smp != nullptr, rules != nullptr, dfa); })) return -1;
+    if (dfa) {
+        for (int s = 0; s < b->n; s++) b->h_dfa[s] = b->ctxs[s]->dfa ? b->ctxs[s]->d_dfa.get() : nullptr;
+        HIPCHK(hipMemcpyAsync(b->d_dfa, b->h_dfa.data(), (size_t)b->n * sizeof(LnbDfaDev*), hipMemcpyHostToDevice, st));
+    }
     if (smp) HIPCHK(hipMemcpyAsync(b->d_smp, smp, (size_t)b->n * sizeof(LnbSampler), hipMemcpyHostToDevice, st));
     if (rules) {                                             // every running member's tables, on the batch's stream (member_drain above: its own stream is idle)
         for (int s = 0; s < b->n; s++) {
@@ -2825,7 +3005,7 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     HIPCHK(hipEventRecord(b->ev0, st));
     for (int i = 0; i < n_steps; i++) {
         if (use_graph) HIPCHK(hipGraphLaunch(gslot, st));
-        else if (enqueue_batch_step(b, false, smp != nullptr, rules != nullptr)) return -1;
+        else if (enqueue_batch_step(b, false, smp != nullptr, rules != nullptr, dfa)) return -1;
     }
     HIPCHK(hipEventRecord(b->ev1, st));
     b->last_form = batch_ran_form(b);
@@ -2834,6 +3014,7 @@ static int batch_decode_impl(lnb_batch* b, const int32_t* tokens, const int32_t*
     HIPCHK(hipMemcpyAsync(b->h_io + 2 * LNB_BATCH_MAX, b->derr, 4, hipMemcpyDeviceToHost, st));
     std::vector<StepState> hs(n_generated ? b->n : 0);
     for (int s = 0; s < (int)hs.size(); s++) HIPCHK(hipMemcpyAsync(&hs[s], b->ctxs[s]->st, sizeof(StepState), hipMemcpyDeviceToHost, st));
+    for (lnb_ctx* c : b->ctxs) if (c->dfa) HIPCHK(hipMemcpyAsync(&c->dfa_state, &c->d_dfa.get()->state, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (ms_out) HIPCHK(hipEventElapsedTime(ms_out, b->ev0, b->ev1));
     if (b->h_io[2 * LNB_BATCH_MAX]) return fail("sequence %d: generated token id is outside the vocabulary", b->h_io[2 * LNB_BATCH_MAX] - 1);
@@ -3456,6 +3637,7 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
     lnb_model* m = c->m;
     if (rc && rules_check(rc->rules, rc->counted, rc->n_counted, m->a.vocab_size, "")) return -1;         // (the ids against the vocabulary, now that it is known)
     if (!m->first() || !m->last()) return fail("speculative decoding needs a whole-model handle");
+    if (dfa_refuse(c, "speculative decoding")) return -1;
     if (c->mode != LNB_MODE_EXACT) return fail("speculative decoding is exact-mode only: its verify pass is the batched exact step (the tolerance mode has none)");
     if (c->top_k > 0) return fail("speculative decoding does not record token probabilities: lnb_ctx_set_token_probs(ctx, 0) first");
     if (c->batch_users > 0) return fail("context is a member of %d live batch(es): speculative decoding runs it alone (lnb_batch_destroy first)", c->batch_users);
@@ -3707,6 +3889,7 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
     lnb_model* m = ctxs[0]->m;
     for (int s = 0; s < n; s++) if (ctxs[s]->m != m) return fail("%s: context %d belongs to another lnb_model handle", name, s);
     if (!m->first() || !m->last()) return fail("%s needs a whole-model handle: pipeline stages have no speculative decoding", name);
+    for (int s = 0; s < n; s++) if (dfa_refuse(ctxs[s], name)) return -1;
     if (batch_shape_check(m, name)) return -1;
     if (sampling && sample_vocab_check(m->a.vocab_size)) return -1;
     const int V = m->a.vocab_size, cap = ctxs[0]->attn_short_cap;
@@ -4096,6 +4279,7 @@ extern "C" int lnb_pipeline_tick(lnb_pipe* p, lnb_ctx* run, int run_rows, int ru
     if (run) {
         if (run->top_k > 0) return fail("the context records token probabilities, which pipeline ticks do not support (lnb_ctx_set_token_probs(ctx, 0))");
         if (run->emit_k >= 0) return fail("lnb_pipeline_tick: the context %s", k_emit_advice);
+        if (dfa_refuse(run, "lnb_pipeline_tick")) return -1;
         if (check_call(run, run_rows, run_pos)) return -1;
         if (run_tokens && !first) return fail("tokens given to a stage that does not own tok_embeddings");
         if (!run_tokens && first && run_rows != 1) return fail("the first stage needs host tokens for a multi-row step");
@@ -4131,6 +4315,7 @@ extern "C" int lnb_pipeline_tick_batch(lnb_pipe* p, lnb_batch* run, lnb_batch* s
     if (run) {
         if (run->top_k > 0) return fail("the batch's contexts record token probabilities, which pipeline ticks do not support (lnb_ctx_set_token_probs(ctx, 0))");
         if (run->emit_k >= 0) return fail("lnb_pipeline_tick_batch: every context of the batch %s", k_emit_advice);
+        for (lnb_ctx* c : run->ctxs) if (dfa_refuse(c, "lnb_pipeline_tick_batch")) return -1;
         if (run->sp_src) return fail("the batch has a shared prefix (lnb_batch_set_shared_prefix): pipeline ticks do not run the shared attention form; clear it first");
         hipStream_t st = run->stream;
         if (run->link.await(st, "batch")) return -1;
@@ -4483,6 +4668,67 @@ extern "C" int lnb_op_sample_rules(int device, const uint16_t* logits_bf16, int 
                              nullptr));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(tokens_out, b + o_t, R * 4, hipMemcpyDeviceToHost));
+    if (info) HIPCHK(hipMemcpy(info, b + o_i, R * sizeof(LnbSampleInfo), hipMemcpyDeviceToHost));
+    return 0;
+}
+// sample_dfa_kernel on host rows (test aid): lnb_op_sample_rules (rules NULL: all off) with row i in state states[i] of the automaton given as CSR, which
+// goes through lnb_automaton_create's checks and build launch -> the tokens and the states behind them
+extern "C" int lnb_op_sample_automaton(int device, const uint16_t* logits_bf16, int rows, int V, const lnb_sampler* samplers, const lnb_logit_rules* rules,
+                                       const uint32_t* counts, const int32_t* pos, const uint64_t* draws, int n_states, const int64_t* row_ptr,
+                                       const int32_t* edge_token, const int32_t* edge_next, const int32_t* states, int32_t* tokens_out, int32_t* next_states_out,
+                                       lnb_sample_info* info) {
+    if (!logits_bf16 || !samplers || !pos || !states || !tokens_out || !next_states_out) return fail("lnb_op_sample_automaton: null argument");
+    if (rows <= 0) return fail("empty operand");
+    if (sample_vocab_check(V)) return -1;
+    if (automaton_host_check("lnb_op_sample_automaton", n_states, row_ptr, edge_token, edge_next)) return -1;
+    const lnb_logit_rules off = {1.0f, 0.0f, 0.0f, 0.0f, 0, 0, nullptr, nullptr};
+    char who[32];
+    bool any_bias = false;
+    for (int i = 0; i < rows; i++) {
+        snprintf(who, sizeof who, "row %d: ", i);
+        if (sampler_check(samplers + i, who) || (rules && rules_check(rules + i, nullptr, 0, V, who))) return -1;
+        if (states[i] < 0 || states[i] >= n_states) return fail("%sstate %d is outside [0, %d)", who, states[i], n_states);
+        any_bias = any_bias || (rules && rules[i].n_bias > 0);
+    }
+    if (op_device(device)) return -1;
+    lnb_automaton a;
+    if (automaton_build("lnb_op_sample_automaton", &a, V, n_states, row_ptr, edge_token, edge_next)) return -1;
+    const size_t R = rows;
+    std::vector<double> et; prob_exp_table(et);
+    const size_t o_x = align256(65536 * 8), o_s = o_x + align256(R * V * 2 + 16), o_p = o_s + align256(R * sizeof(LnbSampler)), o_u = o_p + align256(R * 4),
+                 o_t = o_u + align256(R * 8), o_i = o_t + align256(R * 4), o_r = o_i + align256(R * sizeof(LnbSampleInfo)), o_c = o_r + align256(R * sizeof(LnbRulesDev)),
+                 o_q = o_c + align256(R * V * 4), o_n = o_q + align256(R * 4), o_d = o_n + align256(R * 4), o_b = o_d + align256(sizeof(LnbDfaDev)),
+                 need = o_b + (any_bias ? align256(R * V * 2) : 0);
+    Dev<char> buf;
+    HIPCHK(dev_alloc(buf, need));
+    char* const b = buf;
+    std::vector<LnbRulesDev> hr(R);
+    std::vector<uint16_t> hb(any_bias ? R * V : 0, (uint16_t)0);
+    for (size_t i = 0; i < R; i++) {
+        const lnb_logit_rules& r = rules ? rules[i] : off;
+        for (int k = 0; k < r.n_bias; k++) hb[i * V + r.bias_ids[k]] = bf_trunc_h(r.bias_values[k]);
+        hr[i] = LnbRulesDev{r.repetition_penalty, r.presence_penalty, r.frequency_penalty, r.min_p, (lnbs_u32*)(b + o_c) + i * V,
+                            r.n_bias > 0 ? (const lnbs_u16*)(b + o_b) + i * V : nullptr};
+    }
+    const LnbDfaDev hd{0, a.words, a.n_states, 0, a.mask, a.d_row_ptr, a.edge_next};
+    HIPCHK(hipMemcpy(b, et.data(), 65536 * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_x, logits_bf16, R * V * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_s, samplers, R * sizeof(LnbSampler), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_p, pos, R * 4, hipMemcpyHostToDevice));
+    if (draws) HIPCHK(hipMemcpy(b + o_u, draws, R * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_r, hr.data(), R * sizeof(LnbRulesDev), hipMemcpyHostToDevice));
+    if (counts && rules) HIPCHK(hipMemcpy(b + o_c, counts, R * V * 4, hipMemcpyHostToDevice)); else HIPCHK(hipMemset(b + o_c, 0, R * V * 4));
+    if (any_bias) HIPCHK(hipMemcpy(b + o_b, hb.data(), R * V * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_q, states, R * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b + o_d, &hd, sizeof hd, hipMemcpyHostToDevice));
+    DfaTokParams t{};
+    t.logits = (const uint16_t*)(b + o_x); t.V = V; t.etab = (const double*)b; t.smp = (const LnbSampler*)(b + o_s); t.rules = (const LnbRulesDev*)(b + o_r);
+    t.next_token = (int32_t*)(b + o_t); t.op_pos = (const int32_t*)(b + o_p); t.op_draws = draws ? (const unsigned long long*)(b + o_u) : nullptr;
+    t.op_info = info ? (LnbSampleInfo*)(b + o_i) : nullptr; t.dfa = (LnbDfaDev*)(b + o_d); t.op_states = (const int32_t*)(b + o_q); t.op_next = (int32_t*)(b + o_n);
+    HIPCHK(lnbk_sample_automaton(&t, rows, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(tokens_out, b + o_t, R * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(next_states_out, b + o_n, R * 4, hipMemcpyDeviceToHost));
     if (info) HIPCHK(hipMemcpy(info, b + o_i, R * sizeof(LnbSampleInfo), hipMemcpyDeviceToHost));
     return 0;
 }

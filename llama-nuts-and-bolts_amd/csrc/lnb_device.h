@@ -342,6 +342,33 @@ struct EmitSpecParams {
     const EmitLog* log;
 };
 
+// ---- the token automaton of the sampling loops (lnb_ctx_set_automaton; lnb_automaton.h) -------------------------------------------------------
+// One context's view of its automaton: the state word the token launch reads and writes, and the three device arrays of the lnb_automaton it holds.
+// The captured graphs point at this struct, so another automaton or another start state replays the same graph.
+struct LnbDfaDev {
+    int32_t state, words, n_states, pad;       // words = ceil(V / 32): the length of a mask row
+    const uint32_t* mask;                      // [n_states][words] bit t of row s: token t is allowed in state s
+    const long long* row_ptr;                  // [n_states + 1]
+    const int32_t* edge_next;                  // [n_edges] in token order inside a row
+};
+// the token launch under an automaton: sample_rules_kernel's arguments (tab nullptr) or batch_sample_rules_kernel's (tab) and where the state lives
+struct DfaTokParams {
+    const uint16_t* logits; int V; const double* etab;
+    const struct LnbSampler* smp; const struct LnbRulesDev* rules;     // [rows] / [members]
+    int32_t* next_token; StepState* st; int32_t* out_tokens; int out_cap, advance;      // as sample_rules_kernel's
+    const int32_t* op_pos; const unsigned long long* op_draws; struct LnbSampleInfo* op_info;
+    const BatchTab* tab;
+    LnbDfaDev* dfa;                            // the context's (advance) / the tables of lnb_op_sample_automaton, whose rows have their states in op_states
+    LnbDfaDev* const* member_dfa;              // tab: [members], nullptr = a member without an automaton
+    const int32_t* op_states; int32_t* op_next;   // advance == 0: [rows]
+};
+// lnb_automaton_create's build launch: one workgroup per state.  err: the lowest offending edge index (all ones: none)
+struct DfaBuildParams {
+    const long long* row_ptr; const int32_t* edge_token; const int32_t* edge_next;
+    uint32_t* mask; unsigned long long* err;
+    int32_t n_states, V, words, pad;
+};
+
 // ---- speculative greedy decoding (lnb_decode_speculative_until; ngram_draft_kernel, spec_commit_kernel) ---------------------------------
 // A verify pass is a batched decode step of w = draft_len + 1 columns that all alias ONE context: column i takes d_i at position pos + i,
 // every column has the context's caches (BatchKV), column 0 its own StepState and token word, columns 1.. the context's column words.

@@ -80,6 +80,9 @@
     /* the same token launches under logit rules (lnb_decode_sample_rules_until: step 0 in the row load, step 4b in the probe) */ \
     X(SAMPLE_RULES_ROW, "sample.rules_row", "sample_rules_kernel: one workgroup per logits row with its counts and bias tables -- the one-token rules step, rows of lnb_op_sample_rules") \
     X(SAMPLE_RULES_BATCH, "sample.rules_batch", "batch_sample_rules_kernel: one workgroup per member of a batched rules step, each with its own sampler, rules and tables") \
+    /* ... and under a token automaton (lnb_ctx_set_automaton; lnb_automaton.h): never launched while no context holds one */ \
+    X(SAMPLE_DFA_ROW, "sample.dfa_row", "sample_dfa_kernel<false>: the one-token rules step with the state's mask row staged in the LDS and the transition by rank, rows of lnb_op_sample_automaton") \
+    X(SAMPLE_DFA_BATCH, "sample.dfa_batch", "sample_dfa_kernel<true>: one workgroup per member of a batched step, each with its own automaton and state or none") \
     /* the emitted token's record (lnb_ctx_set_emitted_probs; lnb_emit_probs.h): never launched while the switch is off */ \
     X(EMIT_SUMMARY, "emit.summary", "token_probs_kernel<KT, PARK>: the row summary launch -- the raw row's top k into the record slot (a verify pass: all columns at once into the pass scratch), the row's Z state parked for the token launch") \
     X(EMIT_ROW, "emit.row", "emit_sample_kernel<RULES, false>: the one-token sampling (rules) step with the emitted entry, rows of lnb_op_emitted_probs") \

@@ -4200,9 +4200,12 @@ DEVINL void sample_rules_group(const uint16_t* x, const LnbRulesDev& ru, bool al
 // is loaded, S is step 4b's, and temperature 0 = the first maximum of the adjusted row (steps 1-3); without it the code is the plain sampler's, token for token.
 // DELTA (with RULES): the counts are the table's plus the drafts of *dl (LDS, written and fenced by a barrier before the call) -- see sample_rules_group.
 // EMIT (lnb_emit_probs.h): sh.w_tok = the token's weight w_t of step 4 (4b) beside sh.z.w_kept = W_K -- the sampler's own probability of the token.
-template <bool RULES = false, bool DELTA = false, bool EMIT = false>
+// MASKED (with RULES; lnb_automaton.h): step 0d -- amask = the automaton state's mask row in the LDS (bit j: entry j is allowed); an entry outside it is
+// -inf, which is key 0 whatever the temperature, so the lane's byte of the row joins the group's keys and nothing behind the row load knows of it.
+template <bool RULES = false, bool DELTA = false, bool EMIT = false, bool MASKED = false>
 DEVINL int sample_block(const uint16_t* x, int V, const double* etab, const LnbSampler& s, bool has_u, unsigned long long pos_or_u, SampleSh& sh,
-                        const LnbRulesDev* rules = nullptr, const SpecDelta* dl = nullptr) {
+                        const LnbRulesDev* rules = nullptr, const SpecDelta* dl = nullptr, const uint32_t* amask = nullptr) {
+    static_assert(!MASKED || (RULES && !DELTA), "the masked row load is the rules form's");
     const int tid = threadIdx.x;
     int par = 0;
     if (tid == 0) { const LnbSampleInfo z0 = {0, 0, 0, 0, 0, 0, 0}; sh.z = z0; }      // (read back by thread 0 only)
@@ -4229,10 +4232,13 @@ DEVINL int sample_block(const uint16_t* x, int V, const double* etab, const LnbS
                 uint32_t wd[4];
                 if constexpr (DELTA) sample_rules_group<true>(x, ru, al, (((uintptr_t)ru.counts) & 15) == 0, (((uintptr_t)ru.bias) & 15) == 0, j0, V, wd, dmask, dl);
                 else sample_rules_group(x, ru, al, (((uintptr_t)ru.counts) & 15) == 0, (((uintptr_t)ru.bias) & 15) == 0, j0, V, wd);
+                uint32_t allow = 0xffu;                     // (j0 is a multiple of 8: the group's eight mask bits are one byte of one word)
+                if constexpr (MASKED) allow = amask[j0 >> 5] >> (j0 & 31);
 #pragma unroll
                 for (int t = 0; t < 4; t++) {
                     const int j = j0 + 2 * t;
-                    const uint32_t lo = j < V ? key_of((uint16_t)(wd[t] & 0xffffu)) : 0u, hi = j + 1 < V ? key_of((uint16_t)(wd[t] >> 16)) : 0u;
+                    const uint32_t lo = j < V && ((allow >> (2 * t)) & 1u) ? key_of((uint16_t)(wd[t] & 0xffffu)) : 0u;
+                    const uint32_t hi = j + 1 < V && ((allow >> (2 * t + 1)) & 1u) ? key_of((uint16_t)(wd[t] >> 16)) : 0u;
                     kr[q * 4 + t] = lo | (hi << 16);
                 }
             } else if (al && j0 + 8 <= V) {
@@ -5072,6 +5078,7 @@ __global__ void wpack_pack_head_kernel(const uint16_t* w, char* out, int N, int 
 #include "lnb_knobs.h"
 #include "lnb_forms.h"
 #include "lnb_emit_probs.h"
+#include "lnb_automaton.h"
 
 // ------------------------------------------------------------------------------------------------
 // host-side launchers (called from lnb_api.cpp)

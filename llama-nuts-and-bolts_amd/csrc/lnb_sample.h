@@ -21,6 +21,7 @@
 //   0b. c_j > 0 and (presence != 0 or frequency != 0):  t = frequency * f32(c_j); t = presence + t; f = trunc_bf16(f - t)
 //   0c. a bias table is present:  f = trunc_bf16(f + f32(bias_j)), for EVERY j
 //   4b. min-p: M = uint64(f64(min_p) * f64(w_a)), w_a = the weight of the maximum; S = {j: w_j >= max(M, 1)} (the weight grows with the key: only kmin moves)
+//   0d. a token automaton is attached (include/lnb.h: lnb_ctx_set_automaton; lnb_automaton.h):  f = -inf for every j outside the row of the context's state
 // Steps 1-8 run on the adjusted row; temperature 0 is ml.Argmax of the ADJUSTED row (steps 1-3 at temperature 1).
 // Steps 6 and 7 each come down to a pair (threshold key t, number m of entries kept among those whose key equals t, the lowest indices first).
 #pragma once

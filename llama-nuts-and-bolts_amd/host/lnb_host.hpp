@@ -177,6 +177,25 @@ private:
     ModelArgs args_; lnb_model* h_ = nullptr;
 };
 
+// lnb_automaton (include/lnb.h): a deterministic automaton over token ids as CSR over states -- rowPtr [n_states + 1], edgeToken strictly ascending inside a
+// row, edgeNext the state behind each edge, an empty row = a final state.  The caller's grammar engine builds the arrays; InferenceContext::SetAutomaton
+// attaches it.  Destroy the contexts that hold it (or detach it) first.
+class TokenAutomaton {
+public:
+    TokenAutomaton(const LlamaTransformer& t, const std::vector<int64_t>& rowPtr, const std::vector<int32_t>& edgeToken, const std::vector<int32_t>& edgeNext) {
+        if (rowPtr.empty() || edgeToken.size() != edgeNext.size() || (int64_t)edgeToken.size() < rowPtr.back())
+            throw std::runtime_error("a token automaton is rowPtr [n_states + 1], edgeToken and edgeNext [rowPtr.back()]");
+        check(lnb_automaton_create(t.handle(), (int)rowPtr.size() - 1, rowPtr.data(), edgeToken.data(), edgeNext.data(), &h_));
+    }
+    ~TokenAutomaton() { if (h_) lnb_automaton_destroy(h_); }
+    TokenAutomaton(const TokenAutomaton&) = delete;
+    TokenAutomaton& operator=(const TokenAutomaton&) = delete;
+    int64_t DeviceBytes() const { int64_t b = 0; check(lnb_automaton_info(h_, nullptr, nullptr, &b)); return b; }
+    lnb_automaton* handle() const { return h_; }
+private:
+    lnb_automaton* h_ = nullptr;
+};
+
 using LogFn = std::function<void(const std::string&)>;
 
 class InferenceContext {                 // inferencecontext.go:8-52
@@ -270,6 +289,11 @@ public:
         if (finished) *finished = fin != 0;
         return out;
     }
+    // lnb_ctx_set_automaton: DecodeSampleUntil / DecodeSampleRulesUntil (and the batch forms) stay inside the token automaton `a` from `state` on; nullptr
+    // detaches; with the automaton already held only the state is set.  A final state (an empty row) finishes the generation as a stop id does.
+    void SetAutomaton(lnb_automaton* a, int state = 0) { check(lnb_ctx_set_automaton(h_, a, state)); }
+    // lnb_ctx_automaton_state: the state the context's stream has reached; -1: none attached
+    int AutomatonState() { int s = -1; check(lnb_ctx_automaton_state(h_, &s)); return s; }
     // speculative greedy decoding (include/lnb.h): n-gram drafts (maxDraft 0..LNB_MAX_DRAFT, 0 = off) verified in batched passes -- the tokens
     // and KV rows of lnb_decode_greedy_until; history = the tokens before `token` (the prompt)
     void SetDraft(int maxDraft, int ngramMin, int ngramMax, const std::vector<TokenId>& corpus = {}) {

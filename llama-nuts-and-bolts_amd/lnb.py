@@ -84,6 +84,7 @@ EXPORTS = [
     "lnb_op_rmsnorm_sum",
     "lnb_ctx_attention",
     "lnb_ctx_set_emitted_probs", "lnb_ctx_read_emitted_probs", "lnb_ctx_emitted_probs_last", "lnb_op_emitted_probs",
+    "lnb_automaton_create", "lnb_automaton_destroy", "lnb_automaton_info", "lnb_ctx_set_automaton", "lnb_ctx_automaton_state", "lnb_op_sample_automaton",
 ]
 EPILOGUES = {"store": 0, "qkv_rope": 1, "resid": 2, "silu_mul": 3}      # EPI_* of csrc/lnb_device.h: the second index of the launch tally
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
@@ -314,6 +315,13 @@ def lib():
     L.lnb_batch_decode_sample_rules_until.argtypes = [vp, C.POINTER(Sampler), C.POINTER(LogitRules), vp, vp, i32p, i32p, C.c_int, vp, vp, vp, f32p]
     L.lnb_op_sample_rules.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.POINTER(LogitRules), vp, vp, vp, vp, C.POINTER(SampleInfo)]
     L.lnb_profile_sample_rules.argtypes = [vp, C.POINTER(Sampler), C.POINTER(LogitRules), C.c_int, C.c_int, f32p]
+    L.lnb_automaton_create.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(vp)]
+    L.lnb_automaton_destroy.argtypes = [vp]
+    L.lnb_automaton_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.lnb_ctx_set_automaton.argtypes = [vp, vp, C.c_int]
+    L.lnb_ctx_automaton_state.argtypes = [vp, C.POINTER(C.c_int)]
+    L.lnb_op_sample_automaton.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.POINTER(LogitRules), vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp,
+                                          C.POINTER(SampleInfo)]
     L.lnb_op_token_probs.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.lnb_ctx_set_draft.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int]
     L.lnb_decode_speculative_until.argtypes = [vp, vp, C.c_int, C.c_int32, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -676,6 +684,39 @@ class LlamaTransformer:
             self.h = C.c_void_p()
 
 
+def _csr(row_ptr, edge_token, edge_next):
+    """the three CSR arrays of a token automaton as the C ABI takes them"""
+    rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    et = np.ascontiguousarray(edge_token, dtype=np.int32)
+    en = np.ascontiguousarray(edge_next, dtype=np.int32)
+    if rp.ndim != 1 or rp.size < 1 or et.shape != en.shape or et.ndim != 1 or et.size < int(rp[-1]):
+        raise LnbError("a token automaton is row_ptr [n_states + 1], edge_token and edge_next [row_ptr[-1]]")
+    return rp, et, en
+
+
+class TokenAutomaton:
+    """lnb_automaton (include/lnb.h): a deterministic automaton over token ids as CSR over states -- row s = edges [row_ptr[s], row_ptr[s + 1]), edge_token
+    strictly ascending inside a row, edge_next the state behind each edge; a state with an empty row is final.  The caller's grammar engine builds it."""
+
+    def __init__(self, transformer, row_ptr, edge_token, edge_next):
+        self.L = lib()
+        rp, et, en = _csr(row_ptr, edge_token, edge_next)
+        h = C.c_void_p()
+        _chk(self.L.lnb_automaton_create(transformer.h, int(rp.size) - 1, _p(rp), _p(et), _p(en), C.byref(h)))
+        self.h, self.t = h, transformer
+
+    def info(self):
+        """-> (n_states, n_edges, device bytes)"""
+        n, e, b = C.c_int(0), C.c_int64(0), C.c_int64(0)
+        _chk(self.L.lnb_automaton_info(self.h, C.byref(n), C.byref(e), C.byref(b)))
+        return n.value, e.value, b.value
+
+    def close(self):
+        if self.h:
+            _chk(self.L.lnb_automaton_destroy(self.h))       # (refused while a context holds it)
+            self.h = None
+
+
 class InferenceContext:
     """model.NewInferenceContext (inferencecontext.go:17-46): device KV cache for one generation.
     max_rows / long_context select lnb_ctx_create_long: up to MAX_SEQ_LEN positions (the transformer finalized with that many rope_rows), the per-call
@@ -835,6 +876,19 @@ class InferenceContext:
         lz = np.empty(max(n, 1), dtype=np.float64)
         _chk(self.L.lnb_ctx_read_token_probs(self.h, int(first), int(n), _p(ids), _p(lg), _p(pr), _p(lz)))
         return ids[:, :k], lg[:, :k], pr[:, :k], lz[:n]
+
+    def set_automaton(self, automaton, state=0):
+        """run the sampling loops of this context inside a TokenAutomaton, from `state` (lnb_ctx_set_automaton); None detaches.  With the automaton the
+        context already holds, only the state is set."""
+        _chk(self.L.lnb_ctx_set_automaton(self.h, None if automaton is None else automaton.h, int(state)))
+        self.automaton = automaton                           # (kept alive while attached)
+        return self
+
+    def automaton_state(self):
+        """the automaton state the context's stream has reached (lnb_ctx_automaton_state); -1: none attached"""
+        v = C.c_int(-1)
+        _chk(self.L.lnb_ctx_automaton_state(self.h, C.byref(v)))
+        return v.value
 
     def set_emitted_probs(self, k):
         """record, for every token the sampling and speculative loops emit, the token's own logit and probability, ln Z, the raw row's top k (0..MAX_TOP_K)
@@ -1244,7 +1298,8 @@ class InferenceEngine:
     long_context: the generation's context is a long one (lnb_ctx_create_long, up to MAX_SEQ_LEN positions) whose activation buffers hold
     prefill_chunk rows, or the prompt when the chunk is 0."""
 
-    def __init__(self, transformer, seq_len, stop_token_ids=(), prefill_chunk=0, long_context=False, sampler=None, draft=None, rules=None, emitted_probs=None):
+    def __init__(self, transformer, seq_len, stop_token_ids=(), prefill_chunk=0, long_context=False, sampler=None, draft=None, rules=None, emitted_probs=None,
+                 automaton=None, automaton_state=0):
         if int(prefill_chunk) < 0:
             raise LnbError("prefill_chunk must be 0 (one Forward) or a positive row count")
         self.t, self.seq_len, self.stop, self.prefill_chunk = transformer, seq_len, set(stop_token_ids), int(prefill_chunk)
@@ -1256,7 +1311,13 @@ class InferenceEngine:
         # emitted_probs = k (0..MAX_TOP_K): GenerateTokens returns (tokens, records) -- record i = InferenceContext.read_emitted_probs's fields for tokens[i].
         # The records belong to the sampling loops: without a sampler they run at temperature 0 (the greedy tokens).
         self.emitted_probs = None if emitted_probs is None else int(emitted_probs)
-        if (rules is not None or self.emitted_probs is not None) and self.sampler is None:
+        # automaton = (row_ptr, edge_token, edge_next) numpy arrays (what a TokenAutomaton is built from): every generated token, the prompt's own next
+        # token included, stays inside it from automaton_state on; a final state ends the generation.  Without a sampler it runs at temperature 0.
+        self.automaton = None if automaton is None else _csr(*automaton)
+        self.automaton_state = int(automaton_state)
+        if self.automaton is not None and (draft is not None or self.emitted_probs is not None):
+            raise LnbError("a token automaton runs in the sampling loop only: neither a draft nor emitted_probs goes with it (lnb_ctx_set_automaton)")
+        if (rules is not None or self.emitted_probs is not None or self.automaton is not None) and self.sampler is None:
             self.sampler = Sampler(0.0)
         if draft is not None and len(tuple(draft)) != 3:
             raise LnbError("draft must be None or (max_draft, ngram_min, ngram_max)")
@@ -1289,6 +1350,16 @@ class InferenceEngine:
                     first = int(recs[0].pop("tokens")[0])
                     recs[0].pop("serial_walks")
                     ctx.set_emitted_probs(self.emitted_probs)
+                elif self.automaton is not None:             # the same row under the start state's mask; the loop goes on from the state behind the token
+                    counts = None if self.rules is None else np.bincount(np.asarray(prompt, dtype=np.int64), minlength=row16.size).astype(np.uint32)
+                    tk, ns, _ = op_sample_automaton(row16, [self.sampler], self.automaton, [self.automaton_state], [len(prompt) - 1],
+                                                    rules=None if self.rules is None else [self.rules], counts=counts, want_info=False, device=self.t.device)
+                    first, state = int(tk[0]), int(ns[0])
+                    rp = self.automaton[0]
+                    if first >= 0 and rp[state + 1] == rp[state]:
+                        return [first]                       # the first token already reached a final state
+                    dfa = TokenAutomaton(self.t, *self.automaton)
+                    ctx.set_automaton(dfa, state)
                 elif self.rules is None:
                     first = int(op_sample(row16, [self.sampler], [len(prompt) - 1], want_info=False, device=self.t.device)[0][0])
                 else:                                        # the counted text of that step is the prompt
@@ -1319,7 +1390,10 @@ class InferenceEngine:
                 return out, {f: np.concatenate([r[f] for r in recs]) for f in recs[0]}
             return out
         finally:
+            dfa = getattr(ctx, "automaton", None)
             ctx.close()
+            if dfa is not None:
+                dfa.close()
 
 
 def op_linear(x_u16, w_u16, rw=0, device=0):
@@ -1397,6 +1471,30 @@ def op_sample_rules(logits_u16, samplers, rules, counts, pos, draws=None, want_i
     info = (SampleInfo * rows)() if want_info else None
     _chk(lib().lnb_op_sample_rules(device, _p(a), rows, V, ss, rr, None if c is None else _p(c), _p(p), None if u is None else _p(u), _p(tok), info))
     return tok, ([i.as_dict() for i in info] if want_info else None)
+
+
+def op_sample_automaton(logits_u16, samplers, automaton, states, pos, draws=None, rules=None, counts=None, want_info=True, device=0):
+    """sample_dfa_kernel on rows of bf16 logits [rows, V] (lnb_op_sample_automaton): op_sample_rules (rules None: all off) with row i in state states[i] of
+    automaton = (row_ptr, edge_token, edge_next) -> (tokens int32 [rows], the states behind them int32 [rows], list of info dicts or None)"""
+    a = np.ascontiguousarray(logits_u16, dtype=np.uint16)
+    if a.ndim == 1:
+        a = a[None, :]
+    rows, V = a.shape
+    ss = _samplers(samplers, rows)
+    rr, _keep = (None, None) if rules is None else _rules(rules, rows)
+    c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32).reshape(rows, V)
+    p = np.ascontiguousarray(pos, dtype=np.int32)
+    q = np.ascontiguousarray(states, dtype=np.int32)
+    u = None if draws is None else np.array([int(d) & 0xFFFFFFFFFFFFFFFF for d in draws], dtype=np.uint64)
+    if p.size != rows or q.size != rows or (u is not None and u.size != rows):
+        raise LnbError("%d rows, %d positions, %d states%s" % (rows, p.size, q.size, "" if u is None else ", %d draws" % u.size))
+    rp, et, en = _csr(*automaton)
+    tok = np.full(rows, -2, dtype=np.int32)
+    nxt = np.full(rows, -2, dtype=np.int32)
+    info = (SampleInfo * rows)() if want_info else None
+    _chk(lib().lnb_op_sample_automaton(device, _p(a), rows, V, ss, rr, None if c is None else _p(c), _p(p), None if u is None else _p(u), int(rp.size) - 1, _p(rp),
+                                       _p(et), _p(en), _p(q), _p(tok), _p(nxt), info))
+    return tok, nxt, ([i.as_dict() for i in info] if want_info else None)
 
 
 def op_emitted_probs(logits_u16, top_k, samplers, pos, draws=None, rules=None, counts=None, force_serial=False, device=0):

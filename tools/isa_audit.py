@@ -198,7 +198,10 @@ def main(asm_path=None):
                      # and emit_spec_commit_kernel<RULES> 18 / 15 scalars in VGPR lanes; what their epilogues need waits in the LDS; scratch 0, vgpr_spill_count 0)
                      # (the six instantiations by name: another one has to be looked at and added)
                      "_Z18emit_sample_kernelILb0ELb0EEv13EmitTokParams", "_Z18emit_sample_kernelILb0ELb1EEv13EmitTokParams", "_Z18emit_sample_kernelILb1ELb0EEv13EmitTokParams",
-                     "_Z18emit_sample_kernelILb1ELb1EEv13EmitTokParams", "_Z23emit_spec_commit_kernelILb0EEv14EmitSpecParams", "_Z23emit_spec_commit_kernelILb1EEv14EmitSpecParams")
+                     "_Z18emit_sample_kernelILb1ELb1EEv13EmitTokParams", "_Z23emit_spec_commit_kernelILb0EEv14EmitSpecParams", "_Z23emit_spec_commit_kernelILb1EEv14EmitSpecParams",
+                     # (lnb_automaton.h: the rules form of sample_block with the masked row load -- sample_dfa_kernel<BATCH> 9 / 5 scalars in VGPR lanes, 128 VGPRs,
+                     # 17176 bytes of LDS; what the transition needs waits in the LDS; scratch 0, vgpr_spill_count 0)
+                     "_Z17sample_dfa_kernelILb0EEv12DfaTokParams", "_Z17sample_dfa_kernelILb1EEv12DfaTokParams")
     spills, cur = [], ""
     for l in txt:
         mname = re.search(r"\.name:\s+(\S+)", l)
