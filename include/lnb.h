@@ -656,8 +656,9 @@ int lnb_profile_sample_rules(lnb_ctx* c, const lnb_sampler* sampler, const lnb_l
  * Honoured by lnb_decode_sample_until, lnb_decode_sample_rules_until and their batch forms (members without an automaton are untouched in the same
  *   launch), through token launches and captured graphs of their own: a context without an automaton launches and captures exactly what it did.
  * Refused while attached, naming lnb_ctx_set_automaton, before any cache is written: the greedy loops (use temperature 0 through the sampling call),
- *   every speculative call (the _many decode calls among them; lnb_forward_append_many samples nothing and stays open), pipeline ticks, a context with lnb_ctx_set_emitted_probs or lnb_ctx_set_token_probs on, and a call whose context
- *   is already in a final state.  Those, and any grammar compiler, are out of scope.
+ *   every speculative call but lnb_decode_speculative_automaton_until below (the _many decode calls among them; lnb_forward_append_many samples nothing and
+ *   stays open), pipeline ticks, a context with lnb_ctx_set_emitted_probs or lnb_ctx_set_token_probs on, and a call whose context is already in a final
+ *   state.  Those, and any grammar compiler, are out of scope.
  * lnb_op_sample_automaton: the kernel on host rows, as lnb_op_sample_rules (rules NULL: all off), row i in state states[i]; next_states_out[i] = the
  *   state behind tokens_out[i] (states[i] itself for token -1). */
 typedef struct lnb_automaton lnb_automaton;
@@ -671,6 +672,48 @@ int lnb_op_sample_automaton(int device, const uint16_t* logits_bf16, int rows, i
                             const lnb_logit_rules* rules /* [rows] or NULL */, const uint32_t* counts /* or NULL */, const int32_t* pos, const uint64_t* draws,
                             int n_states, const int64_t* row_ptr, const int32_t* edge_token, const int32_t* edge_next,
                             const int32_t* states /* [rows] */, int32_t* tokens_out, int32_t* next_states_out, lnb_sample_info* info);
+/* ---- speculative decoding under a token automaton, with forced-token drafts ----
+ * The rule.  A verify pass at position pos carries the inputs d_0 .. d_{w-1}; d_0 is the current token and the context's state s_0 is already the state
+ * behind d_0, the one that governs the next token.
+ *   column state:  column i is the automaton step at pos + i in state s_i = next(s_{i-1}, d_i);
+ *   column counts: c_j(i), exactly as defined for lnb_decode_speculative_sample_rules_until;
+ *   column token:  g_i = what the automaton's one-token step gives for that row, state, counted text and position (steps 0a-0d, then 1-8);
+ *   next state:    n_i = next(s_i, g_i); g_i == -1: n_i = s_i;
+ *   acceptance:    unchanged -- the longest prefix with g_i == d_{i+1};
+ *   emission:      for i = 0 .. a: g_i is emitted as every speculative call emits, counted under rules, the context's state becomes n_i, and the run stops
+ *                  with finished = 1 at a stop id or when n_i is final (an empty row).  A rejected column leaves no trace in the state, the table or the output.
+ * The draft.  The n-gram chain of lnb_decode_speculative_until is passed through the automaton on the device before the host sees its length:
+ *   walk:   for i = 1 .. k, a d_i outside the row of s_{i-1} cuts the draft to i - 1 (a forbidden guess never takes a column); a final s_i cuts it to i;
+ *   extend: while the row of s_k holds exactly one token t, s_k is not final and k is below max_draft, max_steps - n_out - 1 and seq_len - pos - 1:
+ *           d_{k+1} = t.  A forced token is a certain draft and needs no n-gram match (k = 0 extends as well).
+ * lnb_decode_speculative_automaton_until: out_tokens[0 .. *n_generated), *n_generated, *finished, the automaton's end state (lnb_ctx_automaton_state) and the
+ *   KV rows [0, start_pos + *n_generated) of every layer are bit-identical to lnb_decode_sample_rules_until on a context holding the same rows, automaton and
+ *   start state -- with rules NULL, to lnb_decode_sample_until -- whatever the draft settings, the corpus or the chunking.  stats->drafted counts the columns
+ *   behind the filter, forced ones included.  The verify passes are a graph family of their own per (width, attention form) beside the others; no family
+ *   drops or recaptures another.  A pass whose filtered draft is empty replays the context's automaton one-token graph; max_draft 0 runs the sampling loop
+ *   itself.  lnb_ctx_set_draft_branches is ignored: the chain is drafted.
+ *   Refused, each with a message, before any cache is written: a context without an automaton; lnb_ctx_set_emitted_probs or lnb_ctx_set_token_probs on; a
+ *   context already in a final state; whatever lnb_decode_speculative_sample_rules_until refuses.  Every other speculative call still refuses a context that
+ *   holds an automaton.  Out of scope: the _many forms, the tree of drafts, emitted-token records and pipeline ticks under an automaton.
+ * lnb_op_automaton_draft (a test aid, as lnb_op_ngram_draft): the filter on host arrays -- draft [n_draft <= max_draft] walked from state0, no decode limits
+ *   -> out [max_draft], *n_out = the kept and extended tokens, col_state [max_draft + 1] = s_0 .. s_k.
+ * lnb_op_spec_automaton_accept (a test aid, as lnb_op_spec_sample_rules_accept; rules NULL: all off): the verify launch on host rows with column 0 in state0;
+ *   the column states are walked on the host from col_tokens, and a token that cannot be walked is an argument error -> also *end_state. */
+int lnb_decode_speculative_automaton_until(lnb_ctx* c, const lnb_sampler* sampler, const lnb_logit_rules* rules /* NULL: off */, const int32_t* counted,
+                                           int n_counted, const int32_t* history, int n_history, int32_t token, int start_pos, int max_steps,
+                                           int32_t* out_tokens, int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out);
+int lnb_op_automaton_draft(int device, int V, int n_states, const int64_t* row_ptr, const int32_t* edge_token, const int32_t* edge_next, int state0,
+                           const int32_t* draft, int n_draft, int max_draft, int32_t* out, int* n_out, int32_t* col_state);
+int lnb_op_spec_automaton_accept(int device, const uint16_t* logits_bf16 /* [w][V] */, int w, int V, const lnb_sampler* sampler,
+                                 const lnb_logit_rules* rules /* or NULL */, const uint32_t* counts /* [V] or NULL */, int pos0,
+                                 const int32_t* col_tokens /* [w] */, const int32_t* stop_ids, int n_stop, int n_states, const int64_t* row_ptr,
+                                 const int32_t* edge_token, const int32_t* edge_next, int state0, int32_t* emitted /* [w] */, int* n_emitted, int* finished,
+                                 int* end_state, uint32_t* counts_out /* [V] or NULL */);
+/* measurement aid, as lnb_profile_spec_verify: average HIP-event time of the verify launch under an automaton alone, on the same host rows */
+int lnb_profile_spec_automaton_verify(int device, const uint16_t* logits_bf16 /* [w][V] */, int w, int V, const lnb_sampler* sampler,
+                                      const lnb_logit_rules* rules /* or NULL */, const uint32_t* counts /* [V] or NULL */, int pos0,
+                                      const int32_t* col_tokens /* [w] */, int n_states, const int64_t* row_ptr, const int32_t* edge_token,
+                                      const int32_t* edge_next, int state0, int iters, float* avg_ms_out);
 /* ---- the emitted token's record: the probability of the token a sampling or speculative loop actually produced ----
  * lnb_ctx_set_emitted_probs: top_k -1 (the default: off -- the same graphs, launches and bits as without the feature) or 0..LNB_MAX_TOP_K.  Whole-model
  *   contexts only; drops the context's captured graphs; refused while the context belongs to a live batch; refused while lnb_ctx_set_token_probs is on, as

@@ -71,6 +71,8 @@ hipError_t lnbk_sample_rules(const uint16_t* logits, int V, int rows, const doub
 hipError_t lnbk_automaton_build(const DfaBuildParams* p, hipStream_t st);
 hipError_t lnbk_sample_automaton(const DfaTokParams* p, int rows, hipStream_t st);
 hipError_t lnbk_batch_sample_automaton(const DfaTokParams* p, int nseq, hipStream_t st);
+hipError_t lnbk_automaton_draft(const DfaDraftParams* p, hipStream_t st);
+hipError_t lnbk_spec_sample_automaton_commit(const SpecDfaParams* p, int w, hipStream_t st);
 hipError_t lnbk_batch_sample_rules(const uint16_t* logits, int V, const double* etab, const LnbSampler* smp, const LnbRulesDev* rules, const BatchTab* tab, int nseq,
                                    hipStream_t st);
 hipError_t lnbk_rules_tables(uint32_t* counts, int V, const int32_t* counted, int n_counted, int32_t token, uint16_t* bias, const int32_t* ids, const float* values,
@@ -186,7 +188,8 @@ static hipError_t event_create(Event& e, unsigned flags = hipEventDefault) { ret
 static hipError_t stream_create(Stream& s, unsigned flags) { return s.fill([&](hipStream_t* q) { return hipStreamCreateWithFlags(q, flags); }); }
 // which captured step: the token launch that ends it, and the attention form its launches bake in
 // (the _EMIT families: the same steps with the emitted token's record, lnb_ctx_set_emitted_probs -- families of their own, so neither drops or recaptures the other)
-// (GL_SAMPLE_DFA: the sampling / rules step of a context or batch that holds a token automaton, lnb_ctx_set_automaton -- again a family of its own)
+// (GL_SAMPLE_DFA: the sampling / rules step of a context or batch that holds a token automaton, lnb_ctx_set_automaton -- again a family of its own; in a
+// verify batch's table: the passes of lnb_decode_speculative_automaton_until, per width and attention form)
 enum GraphLaunch { GL_GREEDY = 0, GL_SAMPLE, GL_STAGE, GL_SAMPLE_RULES, GL_SAMPLE_EMIT, GL_SAMPLE_RULES_EMIT, GL_SAMPLE_DFA, GL_COUNT };
 static bool gl_rules(GraphLaunch l) { return l == GL_SAMPLE_RULES || l == GL_SAMPLE_RULES_EMIT; }
 static bool gl_emit(GraphLaunch l) { return l == GL_SAMPLE_EMIT || l == GL_SAMPLE_RULES_EMIT; }
@@ -311,6 +314,10 @@ struct lnb_ctx {
     // the token automaton (lnb_ctx_set_automaton; lnb_automaton.h): the handle, the device struct its graphs point at (the state word lives there) and
     // the state as the host last knew it -- set by lnb_ctx_set_automaton, read back by every call that ran under it (a final one refuses the next call)
     struct lnb_automaton* dfa = nullptr; Dev<LnbDfaDev> d_dfa; LnbDfaDev h_dfa{}; int dfa_state = -1;
+    // lnb_decode_speculative_automaton_until (lnb_spec_automaton.h): one column's worth of column states of the next pass, as many states behind the
+    // columns' tokens, and the four words ngram_draft_kernel leaves for the draft filter; allocated by the first such call
+    static constexpr int SP_DFA_NEXT = LNB_MAX_DRAFT + 1, SP_DFA_WORD = 2 * (LNB_MAX_DRAFT + 1), SP_DFA_INTS = SP_DFA_WORD + 4;
+    Dev<int32_t> sp_dfa;
     PipeLink link;                         // pipeline stage (lnb_pipeline_tick): events towards / from the exchange stream
     int dev_pos = -1;                      // position the device-side StepState will hold when the stream reaches this point (-1: unknown)
     bool attn_causal = false;              // set by lnb_forward_append around its multi-row call: the attention launches take the true causal mask (AttnParams::causal)
@@ -3601,6 +3608,13 @@ static int spec_verify_batch(lnb_ctx* c, int w, GraphForm form, GraphLaunch laun
             HIPCHK(lnbk_emit_spec_commit(&e, w, b->stream));
             return 0;
         }
+        if (launch == GL_SAMPLE_DFA) {                       // the rules launch with every column's own automaton state; the commit moves the context's state word
+            SpecDfaParams p{};
+            p.logits = b->logits; p.V = m->a.vocab_size; p.etab = m->prob_etab; p.smp = c->d_smp; p.rules = c->rl.d_rules; p.g = c->sp_g; p.nst = c->sp_dfa + lnb_ctx::SP_DFA_NEXT;
+            p.tab = b->tab; p.cnt = c->sp_cnt + 1; p.dfa = c->d_dfa; p.col_state = c->sp_dfa;
+            HIPCHK(lnbk_spec_sample_automaton_commit(&p, w, b->stream));
+            return 0;
+        }
         if (launch == GL_SAMPLE_RULES) {                     // every column's token under the context's device rules, its counts the table's plus the drafts in front of it
             HIPCHK(lnbk_spec_sample_rules_commit(b->logits, m->a.vocab_size, w, m->prob_etab, c->d_smp, c->rl.d_rules, c->sp_g, b->tab, c->sp_cnt + 1, b->stream));
             return 0;
@@ -3630,14 +3644,24 @@ static DraftParams spec_draft_params(lnb_ctx* c, int n_text, int max_steps) {
 // and the rules pick the token launch of a pass -- the one-token graph or the verify batch's graph of that launch -- and nothing else.  Under rules the
 // context's two tables are built before the first pass and every pass's token launch keeps them (the one-token graph: sample_rules_kernel).
 static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* history, int n_history, int32_t token, int start_pos, int max_steps,
-                            int32_t* out_tokens, int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out, const RulesCall* rc = nullptr) {
+                            int32_t* out_tokens, int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out, const RulesCall* rc = nullptr,
+                            bool automaton = false) {
     if (n_history < 0) return fail("negative history length %d", n_history);
     if (max_steps <= 0) return fail("max_steps must be positive");
     if (!c || !out_tokens || !n_generated || (n_history > 0 && !history)) return fail("null argument");
     lnb_model* m = c->m;
     if (rc && rules_check(rc->rules, rc->counted, rc->n_counted, m->a.vocab_size, "")) return -1;         // (the ids against the vocabulary, now that it is known)
     if (!m->first() || !m->last()) return fail("speculative decoding needs a whole-model handle");
-    if (dfa_refuse(c, "speculative decoding")) return -1;
+    // automaton (lnb_decode_speculative_automaton_until alone): the context's token automaton governs the call -- the token launch of every pass is the
+    // automaton's, the chain is filtered and extended by dfa_draft_kernel, all-off rules stand in for none (as in the sampling loop)
+    static const lnb_logit_rules rules_off = {1.0f, 0.0f, 0.0f, 0.0f, 0, 0, nullptr, nullptr};
+    const RulesCall rc_off{&rules_off, nullptr, 0};
+    if (!automaton) { if (dfa_refuse(c, "speculative decoding")) return -1; }
+    else {
+        if (!c->dfa) return fail("lnb_decode_speculative_automaton_until: the context holds no token automaton (lnb_ctx_set_automaton first)");
+        if (automaton_call_check(c, "lnb_decode_speculative_automaton_until: ")) return -1;
+        if (!rc) rc = &rc_off;
+    }
     if (c->mode != LNB_MODE_EXACT) return fail("speculative decoding is exact-mode only: its verify pass is the batched exact step (the tolerance mode has none)");
     if (c->top_k > 0) return fail("speculative decoding does not record token probabilities: lnb_ctx_set_token_probs(ctx, 0) first");
     if (c->batch_users > 0) return fail("context is a member of %d live batch(es): speculative decoding runs it alone (lnb_batch_destroy first)", c->batch_users);
@@ -3663,7 +3687,8 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
     const int n_text = n_history + 1;
     if (smp && !c->d_smp) HIPCHK(dev_alloc(c->d_smp, sizeof(LnbSampler)));
     if (rc && !c->rl.d_rules) HIPCHK(dev_alloc(c->rl.d_rules, sizeof(LnbRulesDev)));
-    const GraphLaunch launch = rc ? (emit ? GL_SAMPLE_RULES_EMIT : GL_SAMPLE_RULES) : smp ? (emit ? GL_SAMPLE_EMIT : GL_SAMPLE) : GL_GREEDY;
+    const GraphLaunch launch = automaton ? GL_SAMPLE_DFA : rc ? (emit ? GL_SAMPLE_RULES_EMIT : GL_SAMPLE_RULES) : smp ? (emit ? GL_SAMPLE_EMIT : GL_SAMPLE) : GL_GREEDY;
+    if (automaton && !c->sp_dfa) HIPCHK(dev_alloc(c->sp_dfa, lnb_ctx::SP_DFA_INTS * sizeof(int32_t)));
     if (spec_alloc(c, n_text) || capture_decode_graphs(c, start_pos, max_steps, launch)) return -1;
     hipStream_t st = c->stream;
     c->tp_last_k = 0; c->tp_last_n = 0; c->em_last_k = -1; c->em_last_n = 0;
@@ -3679,12 +3704,22 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
     for (lnb_batch* b : c->sp_b) if (b) HIPCHK(hipMemsetAsync(b->derr, 0, 4, st));
     HIPCHK(ctx_set_state(c, start_pos, 0, false, true));
     c->call_T = 0;
-    const DraftParams dp = spec_draft_params(c, n_text, max_steps);
+    DraftParams dp = spec_draft_params(c, n_text, max_steps);
+    DfaDraftParams fp{};                                     // under an automaton the n-gram kernel's word goes to the filter, whose word the host reads
+    if (automaton) {
+        dp.word = c->sp_dfa + lnb_ctx::SP_DFA_WORD;
+        fp.dfa = c->d_dfa; fp.tok = c->sp_tok; fp.col_st = c->sp_st; fp.st = c->st; fp.word_in = dp.word; fp.word = c->sp_word_dev; fp.col_state = c->sp_dfa;
+        fp.max_draft = c->sp_max_draft; fp.max_steps = max_steps; fp.seq_len = c->seq_len;
+    }
     // A tree of drafts per pass (lnb_ctx_set_draft_branches): the greedy and the plain sampling call, on a context the one-workgroup kernels serve, head_dim 128 / 64.
     // Everything else -- rules and records (their counts "in front of a column" are a chain's), longer contexts, head_dim 32 -- drafts the chain: today's launches.
     const bool use_tree = c->sp_branches > 1 && !rc && !emit && c->seq_len <= c->attn_short_cap && (m->head_dim == 128 || m->head_dim == 64);
     TreeDraftParams tdp{}; tdp.d = dp; tdp.n_branches = c->sp_branches; tdp.max_nodes = LNB_MAX_DRAFT + 1; tdp.tree = c->sp_tree; tdp.tbest = c->sp_tbest;
-    auto draft = [&]() { return use_tree ? lnbk_tree_draft(&tdp, st) : lnbk_ngram_draft(&dp, st); };
+    auto draft = [&]() {
+        if (use_tree) return lnbk_tree_draft(&tdp, st);
+        const hipError_t e = lnbk_ngram_draft(&dp, st);
+        return e != hipSuccess || !automaton ? e : lnbk_automaton_draft(&fp, st);
+    };
     HIPCHK(hipEventRecord(c->ev0, st));
     HIPCHK(draft());
     HIPCHK(hipEventRecord(c->sp_ev, st));
@@ -3721,6 +3756,7 @@ static int spec_decode_impl(lnb_ctx* c, const lnb_sampler* smp, const int32_t* h
     HIPCHK(hipMemcpyAsync(out_tokens, c->dout, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
     int err = 0;
     HIPCHK(hipMemcpyAsync(c->h_io + 1, c->derr, 4, hipMemcpyDeviceToHost, st));
+    if (automaton) HIPCHK(hipMemcpyAsync(&c->dfa_state, &c->d_dfa.get()->state, 4, hipMemcpyDeviceToHost, st));      // (the host mirror, as decode_greedy_impl reads it back)
     HIPCHK(hipStreamSynchronize(st));
     err |= c->h_io[1];
     for (lnb_batch* b : c->sp_b) if (b) {
@@ -3758,6 +3794,18 @@ extern "C" int lnb_decode_speculative_sample_rules_until(lnb_ctx* c, const lnb_s
     if (sampler_check(sampler, "") || rules_check(rules, counted, n_counted, 0, "")) return -1;
     const RulesCall rc{rules, counted, n_counted};
     return spec_decode_impl(c, sampler, history, n_history, token, start_pos, max_steps, out_tokens, n_generated, finished, stats, ms_out, &rc);
+}
+// the same loop under the context's token automaton (include/lnb.h): the tokens and the end state of lnb_decode_sample_rules_until (rules NULL: of
+// lnb_decode_sample_until) under that automaton, because a verify column is given the state, the counted text and the position the sampling loop would hold
+extern "C" int lnb_decode_speculative_automaton_until(lnb_ctx* c, const lnb_sampler* sampler, const lnb_logit_rules* rules, const int32_t* counted, int n_counted,
+                                                      const int32_t* history, int n_history, int32_t token, int start_pos, int max_steps, int32_t* out_tokens,
+                                                      int* n_generated, int* finished, lnb_spec_stats* stats, float* ms_out) {
+    if (!sampler) return fail("null argument (sampler)");
+    if (sampler_check(sampler, "")) return -1;
+    if (!rules) return spec_decode_impl(c, sampler, history, n_history, token, start_pos, max_steps, out_tokens, n_generated, finished, stats, ms_out, nullptr, true);
+    if (rules_check(rules, counted, n_counted, 0, "")) return -1;
+    const RulesCall rc{rules, counted, n_counted};
+    return spec_decode_impl(c, sampler, history, n_history, token, start_pos, max_steps, out_tokens, n_generated, finished, stats, ms_out, &rc, true);
 }
 // ngram_draft_kernel on host arrays (a test aid, as lnb_op_argmax): the draft that follows text, with no decode limits
 extern "C" int lnb_op_ngram_draft(int device, const int32_t* text, int n_text, const int32_t* corpus, int n_corpus,
@@ -4853,21 +4901,42 @@ extern "C" int lnb_op_spec_sample_accept(int device, const uint16_t* logits_bf16
 // col_tokens[0] is taken as counted in it already) -> what the pass emits and, in counts_out [V] (optional), the table after the commit.
 // iters > 0 (lnb_profile_spec_verify): the launch is then repeated iters times between two events on the same rows -> *avg_ms; plain: spec_sample_commit_kernel
 // in its place (the rules are then only checked).  The repeats go on from the state the launch before left: positions and counts move as in a run.
+// dfa (lnb_op_spec_automaton_accept): spec_sample_dfa_commit_kernel in its place, under the automaton given as CSR from state0 -- the column states are walked
+// on the host from col_tokens[1 ..] -> also *end_state, the state word after the commit
+struct DfaOp { int n_states; const int64_t* row_ptr; const int32_t* edge_token; const int32_t* edge_next; int state0; int* end_state; };
 static int spec_rules_accept_impl(int device, const uint16_t* logits_bf16, int w, int V, const lnb_sampler* sampler, const lnb_logit_rules* rules,
                                   const uint32_t* counts, int pos0, const int32_t* col_tokens, const int32_t* stop_ids, int n_stop, int32_t* emitted,
-                                  int* n_emitted, int* finished, uint32_t* counts_out, bool plain, int iters, float* avg_ms) {
+                                  int* n_emitted, int* finished, uint32_t* counts_out, bool plain, int iters, float* avg_ms, const DfaOp* dfa = nullptr) {
     if (!logits_bf16 || !sampler || !rules || !col_tokens || !emitted || !n_emitted || (n_stop > 0 && !stop_ids)) return fail("null argument");
     if (w < 1 || w > LNB_MAX_DRAFT + 1) return fail("a verify pass has 1..%d columns (got %d)", LNB_MAX_DRAFT + 1, w);
     if (sample_vocab_check(V)) return -1;
     if (sampler_check(sampler, "") || rules_check(rules, nullptr, 0, V, "")) return -1;
     if (pos0 < 0 || n_stop < 0 || n_stop > LNB_MAX_STOP_IDS) return fail("bad arguments: pos0 %d, %d stop ids (at most %d)", pos0, n_stop, LNB_MAX_STOP_IDS);
     for (int i = 0; i < w; i++) if (col_tokens[i] < 0 || col_tokens[i] >= V) return fail("column token %d at index %d is outside the vocabulary [0, %d)", col_tokens[i], i, V);
+    int32_t col_state[2 * (LNB_MAX_DRAFT + 1)] = {};
+    if (dfa) {
+        if (automaton_host_check("lnb_op_spec_automaton_accept", dfa->n_states, dfa->row_ptr, dfa->edge_token, dfa->edge_next)) return -1;
+        if (dfa->state0 < 0 || dfa->state0 >= dfa->n_states) return fail("lnb_op_spec_automaton_accept: state0 %d is outside [0, %d)", dfa->state0, dfa->n_states);
+        int s = dfa->state0;
+        for (int i = 0; i < w; i++) {                        // column i's state: the edge of col_tokens[i] out of column i - 1's
+            if (i > 0) {
+                const int32_t *e0 = dfa->edge_token + dfa->row_ptr[s], *e1 = dfa->edge_token + dfa->row_ptr[s + 1], *e = std::lower_bound(e0, e1, col_tokens[i]);
+                const int nx = e != e1 && *e == col_tokens[i] ? dfa->edge_next[e - dfa->edge_token] : -1;
+                if (nx < 0 || nx >= dfa->n_states) return fail("lnb_op_spec_automaton_accept: column token %d at index %d cannot be walked from state %d", col_tokens[i], i, s);
+                s = nx;
+            }
+            col_state[i] = s;                                // (a final state: the column has no candidate, and the commit stops in front of it)
+        }
+    }
     if (op_device(device)) return -1;
+    lnb_automaton a;
+    if (dfa && automaton_build("lnb_op_spec_automaton_accept", &a, V, dfa->n_states, dfa->row_ptr, dfa->edge_token, dfa->edge_next)) return -1;
     const size_t W = w;
     std::vector<double> et; prob_exp_table(et);
     const size_t o_x = align256(65536 * 8), o_s = o_x + align256(W * V * 2 + 16), o_st = o_s + align256(sizeof(LnbSampler)), o_tok = o_st + align256(W * sizeof(StepState)),
                  o_g = o_tok + align256(W * 4), o_log = o_g + align256(W * 4), o_tab = o_log + align256(W * 4), o_cnt = o_tab + align256(sizeof(BatchTab)),
-                 o_r = o_cnt + 256, o_c = o_r + align256(sizeof(LnbRulesDev)), o_b = o_c + align256((size_t)V * 4), need = o_b + align256((size_t)V * 2);
+                 o_r = o_cnt + 256, o_c = o_r + align256(sizeof(LnbRulesDev)), o_b = o_c + align256((size_t)V * 4), o_d = o_b + align256((size_t)V * 2),
+                 o_q = o_d + align256(sizeof(LnbDfaDev)), need = o_q + align256(sizeof col_state);
     Dev<char> buf;
     HIPCHK(dev_alloc(buf, need));
     char* const b = buf;
@@ -4892,7 +4961,17 @@ static int spec_rules_accept_impl(int device, const uint16_t* logits_bf16, int w
     HIPCHK(hipMemcpy(b + o_r, &hr, sizeof hr, hipMemcpyHostToDevice));
     if (counts) HIPCHK(hipMemcpy(b + o_c, counts, (size_t)V * 4, hipMemcpyHostToDevice));
     if (rules->n_bias > 0) HIPCHK(hipMemcpy(b + o_b, hb.data(), (size_t)V * 2, hipMemcpyHostToDevice));
+    SpecDfaParams dp{};
+    if (dfa) {
+        const LnbDfaDev hd{dfa->state0, a.words, a.n_states, 0, a.mask, a.d_row_ptr, a.edge_next};
+        HIPCHK(hipMemcpy(b + o_d, &hd, sizeof hd, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b + o_q, col_state, sizeof col_state, hipMemcpyHostToDevice));
+        dp.logits = (const uint16_t*)(b + o_x); dp.V = V; dp.etab = (const double*)b; dp.smp = (const LnbSampler*)(b + o_s); dp.rules = (const LnbRulesDev*)(b + o_r);
+        dp.g = (int32_t*)(b + o_g); dp.nst = (int32_t*)(b + o_q) + LNB_MAX_DRAFT + 1; dp.tab = (const BatchTab*)(b + o_tab); dp.cnt = (unsigned*)(b + o_cnt);
+        dp.dfa = (LnbDfaDev*)(b + o_d); dp.col_state = (const int32_t*)(b + o_q);
+    }
     auto launch = [&]() {
+        if (dfa) return lnbk_spec_sample_automaton_commit(&dp, w, nullptr);
         return plain ? lnbk_spec_sample_commit((const uint16_t*)(b + o_x), V, w, (const double*)b, (const LnbSampler*)(b + o_s), (int32_t*)(b + o_g),
                                                (const BatchTab*)(b + o_tab), (unsigned*)(b + o_cnt), nullptr)
                      : lnbk_spec_sample_rules_commit((const uint16_t*)(b + o_x), V, w, (const double*)b, (const LnbSampler*)(b + o_s), (const LnbRulesDev*)(b + o_r),
@@ -4915,9 +4994,60 @@ static int spec_rules_accept_impl(int device, const uint16_t* logits_bf16, int w
     HIPCHK(hipMemcpy(hst.data(), b + o_st, sizeof(StepState), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(emitted, b + o_log, W * 4, hipMemcpyDeviceToHost));
     if (counts_out) HIPCHK(hipMemcpy(counts_out, b + o_c, (size_t)V * 4, hipMemcpyDeviceToHost));
+    if (dfa) HIPCHK(hipMemcpy(dfa->end_state, b + o_d, 4, hipMemcpyDeviceToHost));       // (LnbDfaDev's first word)
     if (hst[0].n_out < 1 || hst[0].n_out > w) return fail("internal error: a pass of %d columns emitted %d tokens", w, hst[0].n_out);
     *n_emitted = hst[0].n_out;
     if (finished) *finished = hst[0].finished;
+    return 0;
+}
+// spec_sample_dfa_commit_kernel on host rows (test aid): lnb_op_spec_sample_rules_accept (rules NULL: all off) under the automaton given as CSR, column 0 in
+// state0 -> also *end_state.  A column token that state0's walk cannot take is an argument error.
+extern "C" int lnb_op_spec_automaton_accept(int device, const uint16_t* logits_bf16, int w, int V, const lnb_sampler* sampler, const lnb_logit_rules* rules,
+                                            const uint32_t* counts, int pos0, const int32_t* col_tokens, const int32_t* stop_ids, int n_stop, int n_states,
+                                            const int64_t* row_ptr, const int32_t* edge_token, const int32_t* edge_next, int state0, int32_t* emitted, int* n_emitted,
+                                            int* finished, int* end_state, uint32_t* counts_out) {
+    if (!end_state) return fail("lnb_op_spec_automaton_accept: null argument (end_state)");
+    const lnb_logit_rules off = {1.0f, 0.0f, 0.0f, 0.0f, 0, 0, nullptr, nullptr};
+    const DfaOp dfa{n_states, row_ptr, edge_token, edge_next, state0, end_state};
+    return spec_rules_accept_impl(device, logits_bf16, w, V, sampler, rules ? rules : &off, counts, pos0, col_tokens, stop_ids, n_stop, emitted, n_emitted,
+                                  finished, counts_out, false, 0, nullptr, &dfa);
+}
+// dfa_draft_kernel on host arrays (test aid, as lnb_op_ngram_draft): the draft `draft` [n_draft] walked from state0 of the automaton given as CSR, cut and
+// extended up to max_draft tokens, with no decode limits -> out [max_draft] / *n_out and col_state [max_draft + 1] (col_state[0] = state0)
+extern "C" int lnb_op_automaton_draft(int device, int V, int n_states, const int64_t* row_ptr, const int32_t* edge_token, const int32_t* edge_next, int state0,
+                                      const int32_t* draft, int n_draft, int max_draft, int32_t* out, int* n_out, int32_t* col_state) {
+    if (automaton_host_check("lnb_op_automaton_draft", n_states, row_ptr, edge_token, edge_next)) return -1;
+    if (max_draft < 0 || max_draft > LNB_MAX_DRAFT) return fail("max_draft must be 0..%d (got %d)", LNB_MAX_DRAFT, max_draft);
+    if (n_draft < 0 || n_draft > max_draft) return fail("lnb_op_automaton_draft: n_draft must be 0..max_draft (got %d, max_draft %d)", n_draft, max_draft);
+    if (state0 < 0 || state0 >= n_states) return fail("lnb_op_automaton_draft: state0 %d is outside [0, %d)", state0, n_states);
+    if ((n_draft > 0 && !draft) || !out || !n_out || !col_state) return fail("lnb_op_automaton_draft: null argument");
+    if (sample_vocab_check(V)) return -1;
+    if (op_device(device)) return -1;
+    lnb_automaton a;
+    if (automaton_build("lnb_op_automaton_draft", &a, V, n_states, row_ptr, edge_token, edge_next)) return -1;
+    constexpr int W = LNB_MAX_DRAFT + 1;
+    DevArena ar;
+    LnbDfaDev* dd = ar.alloc<LnbDfaDev>(1); int32_t* dtok = ar.alloc<int32_t>(W); int32_t* dcs = ar.alloc<int32_t>(W); int32_t* dword = ar.alloc<int32_t>(8);
+    HIPCHK(ar.error());
+    const LnbDfaDev hd{state0, a.words, a.n_states, 0, a.mask, a.d_row_ptr, a.edge_next};
+    int32_t htok[W] = {}, hcs[W] = {}, word[8] = {n_draft, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < n_draft; i++) htok[1 + i] = draft[i];
+    HIPCHK(hipMemcpy(dd, &hd, sizeof hd, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dtok, htok, sizeof htok, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dcs, hcs, sizeof hcs, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dword, word, sizeof word, hipMemcpyHostToDevice));
+    DfaDraftParams p{};
+    p.dfa = dd; p.tok = dtok; p.word_in = dword; p.word = dword + 4; p.col_state = dcs; p.max_draft = max_draft;
+    HIPCHK(lnbk_automaton_draft(&p, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(word, dword, sizeof word, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(htok, dtok, sizeof htok, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hcs, dcs, sizeof hcs, hipMemcpyDeviceToHost));
+    const int k = word[4];
+    if (k < 0 || k > max_draft) return fail("internal error: draft length %d", k);
+    for (int i = 0; i < k; i++) out[i] = htok[1 + i];
+    for (int i = 0; i <= k; i++) col_state[i] = hcs[i];
+    *n_out = k;
     return 0;
 }
 extern "C" int lnb_op_spec_sample_rules_accept(int device, const uint16_t* logits_bf16, int w, int V, const lnb_sampler* sampler, const lnb_logit_rules* rules,
@@ -4934,6 +5064,17 @@ extern "C" int lnb_profile_spec_verify(int device, const uint16_t* logits_bf16, 
     int32_t emitted[LNB_MAX_DRAFT + 1]; int n = 0;
     return spec_rules_accept_impl(device, logits_bf16, w, V, sampler, rules ? rules : &off, counts, pos0, col_tokens, nullptr, 0, emitted, &n, nullptr, nullptr, !rules, iters,
                                   avg_ms_out);
+}
+// the same for the verify launch under an automaton (tools/spec_automaton_bench.py): spec_sample_dfa_commit_kernel on the same rows, column 0 in state0
+extern "C" int lnb_profile_spec_automaton_verify(int device, const uint16_t* logits_bf16, int w, int V, const lnb_sampler* sampler, const lnb_logit_rules* rules,
+                                                 const uint32_t* counts, int pos0, const int32_t* col_tokens, int n_states, const int64_t* row_ptr,
+                                                 const int32_t* edge_token, const int32_t* edge_next, int state0, int iters, float* avg_ms_out) {
+    if (!avg_ms_out || iters <= 0) return fail("bad arguments");
+    const lnb_logit_rules off = {1.0f, 0.0f, 0.0f, 0.0f, 0, 0, nullptr, nullptr};
+    int32_t emitted[LNB_MAX_DRAFT + 1]; int n = 0, end = 0;
+    const DfaOp dfa{n_states, row_ptr, edge_token, edge_next, state0, &end};
+    return spec_rules_accept_impl(device, logits_bf16, w, V, sampler, rules ? rules : &off, counts, pos0, col_tokens, nullptr, 0, emitted, &n, nullptr, nullptr, false, iters,
+                                  avg_ms_out, &dfa);
 }
 extern "C" int lnb_op_exp_table(int device, float divisor, double* out65536) {
     if (!out65536) return fail("null argument");

@@ -387,6 +387,27 @@ struct DraftParams {
     unsigned* cnt;                             // arrival ticket, zero between launches (the last workgroup resets it)
 };
 
+// ---- speculative decoding under a token automaton (lnb_decode_speculative_automaton_until; lnb_spec_automaton.h) ------------------------------
+// The draft filter, one workgroup behind ngram_draft_kernel on the same stream: the chain's tokens tok[1 .. k] walked from the automaton's state word, cut
+// and extended by forced tokens; col_state[i] = the state that governs column i's token.
+struct DfaDraftParams {
+    const LnbDfaDev* dfa;                      // the context's struct (its state word = s_0) / the tables and start state of lnb_op_automaton_draft
+    int32_t* tok;                              // the column token words: d_i = tok[i], i = 1 .. k (in and out)
+    StepState* col_st; const StepState* st;    // decode: col_st[i].pos = pos + i for an extended column, the cuts of DraftParams; st nullptr: neither
+    const int32_t* word_in;                    // {k, n_out, finished} as ngram_draft_kernel left them
+    int32_t* word;                             // {k behind the filter, n_out, finished} (decode: the host's pinned word)
+    int32_t* col_state;                        // [LNB_SPEC_MAX_DRAFT + 1]
+    int max_draft, max_steps, seq_len;
+};
+// the verify pass's token launch under the automaton: spec_sample_rules_commit_kernel's arguments, the column states and where (g_i, n_i) are published
+struct SpecDfaParams {
+    const uint16_t* logits; int V; const double* etab;
+    const struct LnbSampler* smp; const struct LnbRulesDev* rules;
+    int32_t* g; int32_t* nst;                  // [LNB_SPEC_MAX_DRAFT + 1] each: column i's token and the state behind it
+    const BatchTab* tab; unsigned* cnt;
+    LnbDfaDev* dfa; const int32_t* col_state;
+};
+
 // ---- a TREE of drafts in one verify pass (lnb_ctx_set_draft_branches; tree_draft_kernel, lnb_tree_verify.h) ------------------------------------
 // The up to n_branches latest continuations of the matched n-gram, merged into a trie of at most 16 nodes: node 0 is the current token, nodes are numbered
 // in insertion order (a parent's index lies below its children's), node i is column i of the pass.  Column i is the one-token step at pos + depth[i] (its

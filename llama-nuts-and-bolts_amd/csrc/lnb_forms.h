@@ -83,6 +83,9 @@
     /* ... and under a token automaton (lnb_ctx_set_automaton; lnb_automaton.h): never launched while no context holds one */ \
     X(SAMPLE_DFA_ROW, "sample.dfa_row", "sample_dfa_kernel<false>: the one-token rules step with the state's mask row staged in the LDS and the transition by rank, rows of lnb_op_sample_automaton") \
     X(SAMPLE_DFA_BATCH, "sample.dfa_batch", "sample_dfa_kernel<true>: one workgroup per member of a batched step, each with its own automaton and state or none") \
+    /* ... and in the speculative loop under one (lnb_decode_speculative_automaton_until; lnb_spec_automaton.h) */ \
+    X(SAMPLE_SPEC_DFA, "sample.spec_dfa", "spec_sample_dfa_commit_kernel: one workgroup per column of a verify pass under an automaton, its column state's mask row in the LDS beside the draft delta; the last one accepts, emits, counts and moves the state") \
+    X(DRAFT_DFA, "draft.dfa", "dfa_draft_kernel: one workgroup walks the n-gram draft through the automaton, cuts it at a forbidden token or a final state and extends it by forced tokens") \
     /* the emitted token's record (lnb_ctx_set_emitted_probs; lnb_emit_probs.h): never launched while the switch is off */ \
     X(EMIT_SUMMARY, "emit.summary", "token_probs_kernel<KT, PARK>: the row summary launch -- the raw row's top k into the record slot (a verify pass: all columns at once into the pass scratch), the row's Z state parked for the token launch") \
     X(EMIT_ROW, "emit.row", "emit_sample_kernel<RULES, false>: the one-token sampling (rules) step with the emitted entry, rows of lnb_op_emitted_probs") \

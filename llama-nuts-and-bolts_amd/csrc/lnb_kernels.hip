@@ -4202,10 +4202,11 @@ DEVINL void sample_rules_group(const uint16_t* x, const LnbRulesDev& ru, bool al
 // EMIT (lnb_emit_probs.h): sh.w_tok = the token's weight w_t of step 4 (4b) beside sh.z.w_kept = W_K -- the sampler's own probability of the token.
 // MASKED (with RULES; lnb_automaton.h): step 0d -- amask = the automaton state's mask row in the LDS (bit j: entry j is allowed); an entry outside it is
 // -inf, which is key 0 whatever the temperature, so the lane's byte of the row joins the group's keys and nothing behind the row load knows of it.
+// MASKED and DELTA combine (lnb_spec_automaton.h: a verify column under an automaton): the delta patches the counts, the mask the keys -- one row load.
 template <bool RULES = false, bool DELTA = false, bool EMIT = false, bool MASKED = false>
 DEVINL int sample_block(const uint16_t* x, int V, const double* etab, const LnbSampler& s, bool has_u, unsigned long long pos_or_u, SampleSh& sh,
                         const LnbRulesDev* rules = nullptr, const SpecDelta* dl = nullptr, const uint32_t* amask = nullptr) {
-    static_assert(!MASKED || (RULES && !DELTA), "the masked row load is the rules form's");
+    static_assert(!MASKED || RULES, "the masked row load is the rules form's");
     const int tid = threadIdx.x;
     int par = 0;
     if (tid == 0) { const LnbSampleInfo z0 = {0, 0, 0, 0, 0, 0, 0}; sh.z = z0; }      // (read back by thread 0 only)
@@ -4514,7 +4515,9 @@ __global__ __launch_bounds__(1024) void spec_argmax_kernel(const uint16_t* logit
 // (spec_accept_emit: one thread; shared with spec_sample_commit_kernel, whose g holds the sampler's tokens -- the same loop for both)
 // counts (optional): the context's occurrence table under logit rules -- every emitted token is counted as sample_rules_advance counts it (the run not
 // finished, tok >= 0; a stop token before it freezes the run), a rejected draft never.
-DEVINL void spec_accept_emit(const int32_t* g, int w, const BatchTab* tab, uint32_t* counts = nullptr) {
+// nst, dfa (optional; lnb_spec_automaton.h): the context's automaton and the state n_i behind every column's token -- an emitted token >= 0 moves the state
+// word to its n_i, and a final n_i (an empty row) finishes the run as a stop id does; a rejected column's n_i is never read.
+DEVINL void spec_accept_emit(const int32_t* g, int w, const BatchTab* tab, uint32_t* counts = nullptr, const int32_t* nst = nullptr, LnbDfaDev* dfa = nullptr) {
     StepState* st = tab->st[0];
     if (st->finished) return;
     int a = 0;
@@ -4529,6 +4532,11 @@ DEVINL void spec_accept_emit(const int32_t* g, int w, const BatchTab* tab, uint3
         if (counts && tok >= 0) counts[tok] += 1u;           // (tok < V: an index of the row)
         bool stop = false;
         if (st->honour_stop) for (int k = 0; k < st->n_stop; k++) if (tok == st->stop[k]) stop = true;
+        if (dfa && tok >= 0) {
+            const int ns = nst[i];
+            dfa->state = ns;
+            if (dfa->row_ptr[ns + 1] == dfa->row_ptr[ns]) stop = true;
+        }
         if (stop) { st->finished = 1; break; }
     }
 }
@@ -5079,6 +5087,7 @@ __global__ void wpack_pack_head_kernel(const uint16_t* w, char* out, int N, int 
 #include "lnb_forms.h"
 #include "lnb_emit_probs.h"
 #include "lnb_automaton.h"
+#include "lnb_spec_automaton.h"
 
 // ------------------------------------------------------------------------------------------------
 // host-side launchers (called from lnb_api.cpp)

@@ -85,6 +85,7 @@ EXPORTS = [
     "lnb_ctx_attention",
     "lnb_ctx_set_emitted_probs", "lnb_ctx_read_emitted_probs", "lnb_ctx_emitted_probs_last", "lnb_op_emitted_probs",
     "lnb_automaton_create", "lnb_automaton_destroy", "lnb_automaton_info", "lnb_ctx_set_automaton", "lnb_ctx_automaton_state", "lnb_op_sample_automaton",
+    "lnb_decode_speculative_automaton_until", "lnb_op_automaton_draft", "lnb_op_spec_automaton_accept", "lnb_profile_spec_automaton_verify",
 ]
 EPILOGUES = {"store": 0, "qkv_rope": 1, "resid": 2, "silu_mul": 3}      # EPI_* of csrc/lnb_device.h: the second index of the launch tally
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
@@ -340,6 +341,12 @@ def lib():
                                                            C.c_int, C.c_int, vp, vp, vp, C.POINTER(SpecStats), C.POINTER(SpecManyInfo), f32p]
     L.lnb_op_spec_sample_rules_accept.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.POINTER(LogitRules), vp, C.c_int, vp, vp, C.c_int, vp,
                                                   C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
+    L.lnb_decode_speculative_automaton_until.argtypes = L.lnb_decode_speculative_sample_rules_until.argtypes
+    L.lnb_op_automaton_draft.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.POINTER(C.c_int), vp]
+    L.lnb_op_spec_automaton_accept.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.POINTER(LogitRules), vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp,
+                                               vp, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
+    L.lnb_profile_spec_automaton_verify.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.POINTER(LogitRules), vp, C.c_int, vp, C.c_int, vp, vp, vp,
+                                                    C.c_int, C.c_int, f32p]
     L.lnb_profile_spec_verify.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.POINTER(LogitRules), vp, C.c_int, vp, C.c_int, f32p]
     L.lnb_model_num_tensors.argtypes = [vp]
     L.lnb_model_tensor_info.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
@@ -973,6 +980,20 @@ class InferenceContext:
                                                         C.byref(n), C.byref(fin), C.byref(st), C.byref(ms)))
         return out[:n.value].copy(), bool(fin.value), st.as_dict(), ms.value
 
+    def decode_speculative_automaton_until(self, sampler, history, token, start_pos, max_steps, rules=None, counted=None):
+        """decode_sample_until under this context's automaton (set_automaton) with drafts verified in batched passes (lnb_decode_speculative_automaton_until):
+        the n-gram chain is walked through the automaton, cut where it leaves it and extended by forced tokens; the same tokens, end state and KV rows as
+        decode_sample_until(..., rules=, counted=) under the same automaton and start state -> (tokens, finished flag, stats dict, device ms)"""
+        s = None if sampler is None else _samplers([sampler], 1)
+        h = np.ascontiguousarray(history, dtype=np.int32)
+        out = np.empty(max(int(max_steps), 0), dtype=np.int32)
+        ms, n, fin, st = C.c_float(0), C.c_int(0), C.c_int(0), SpecStats()
+        rr, _keep = (None, None) if rules is None and counted is None else _rules([rules], 1)
+        cn = np.ascontiguousarray(counted if counted is not None else [], dtype=np.int32)
+        _chk(self.L.lnb_decode_speculative_automaton_until(self.h, s, rr, _p(cn) if cn.size else None, int(cn.size), _p(h) if h.size else None, int(h.size),
+                                                           int(token), start_pos, max_steps, _p(out), C.byref(n), C.byref(fin), C.byref(st), C.byref(ms)))
+        return out[:n.value].copy(), bool(fin.value), st.as_dict(), ms.value
+
     def token_prob_walks(self):
         """rows of this context (decode steps, scored rows) whose probabilities walked the reference's serial sum"""
         n = C.c_int(0)
@@ -1315,8 +1336,9 @@ class InferenceEngine:
         # token included, stays inside it from automaton_state on; a final state ends the generation.  Without a sampler it runs at temperature 0.
         self.automaton = None if automaton is None else _csr(*automaton)
         self.automaton_state = int(automaton_state)
-        if self.automaton is not None and (draft is not None or self.emitted_probs is not None):
-            raise LnbError("a token automaton runs in the sampling loop only: neither a draft nor emitted_probs goes with it (lnb_ctx_set_automaton)")
+        # With draft= the generation runs decode_speculative_automaton_until: the same tokens, forced tokens drafted by the automaton itself.
+        if self.automaton is not None and self.emitted_probs is not None:
+            raise LnbError("a token automaton does not go with emitted_probs: the records are not kept under an automaton (lnb_ctx_set_automaton)")
         if (rules is not None or self.emitted_probs is not None or self.automaton is not None) and self.sampler is None:
             self.sampler = Sampler(0.0)
         if draft is not None and len(tuple(draft)) != 3:
@@ -1373,6 +1395,9 @@ class InferenceEngine:
                     ctx.set_draft(*self.draft)
                     if self.sampler is None:
                         more, _, _, _ = ctx.decode_speculative_until(prompt, first, len(prompt), n_new - 1)
+                    elif self.automaton is not None:
+                        more, _, _, _ = ctx.decode_speculative_automaton_until(self.sampler, prompt, first, len(prompt), n_new - 1, rules=self.rules,
+                                                                               counted=None if self.rules is None else prompt)
                     else:
                         more, _, _, _ = ctx.decode_speculative_sample_until(self.sampler, prompt, first, len(prompt), n_new - 1, rules=self.rules,
                                                                             counted=None if self.rules is None else prompt)
@@ -1608,6 +1633,45 @@ def op_spec_sample_rules_accept(logits_u16, sampler, rules, counts, pos0, col_to
     return out[:n.value].copy(), bool(fin.value), after
 
 
+def op_automaton_draft(automaton, state0, draft, max_draft=MAX_DRAFT, V=None, device=0):
+    """dfa_draft_kernel on host arrays (lnb_op_automaton_draft): `draft` walked from state0 of automaton = (row_ptr, edge_token, edge_next) over a vocabulary of
+    V ids (default: the largest edge token + 1), cut at a forbidden token or a final state and extended by forced tokens up to max_draft
+    -> (the kept and extended tokens int32 [k], the column states int32 [k + 1])"""
+    rp, et, en = _csr(*automaton)
+    d = np.ascontiguousarray(draft, dtype=np.int32)
+    out = np.empty(max(int(max_draft), 1), dtype=np.int32)
+    cs = np.empty(int(max_draft) + 1, dtype=np.int32)
+    n = C.c_int(0)
+    V = (int(et.max()) + 1 if et.size else 1) if V is None else int(V)
+    _chk(lib().lnb_op_automaton_draft(device, V, int(rp.size) - 1, _p(rp), _p(et), _p(en), int(state0), _p(d) if d.size else None, int(d.size), int(max_draft),
+                                      _p(out), C.byref(n), _p(cs)))
+    return out[:n.value].copy(), cs[:n.value + 1].copy()
+
+
+def op_spec_automaton_accept(logits_u16, sampler, rules, counts, pos0, col_tokens, automaton, state0, stop_ids=(), device=0):
+    """spec_sample_dfa_commit_kernel on host rows (lnb_op_spec_automaton_accept): op_spec_sample_rules_accept (rules None: all off) under automaton =
+    (row_ptr, edge_token, edge_next) with column 0 in state0 and column i in the state col_tokens[1 .. i] lead to
+    -> (the tokens the pass emits, finished flag, the state after the commit, the table after the commit as a uint32 array)"""
+    a = np.ascontiguousarray(logits_u16, dtype=np.uint16)
+    w, V = a.shape
+    ct = np.ascontiguousarray(col_tokens, dtype=np.int32)
+    if ct.size != w:
+        raise LnbError("%d column tokens for %d rows" % (ct.size, w))
+    c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+    if c is not None and c.size != V:
+        raise LnbError("%d counts for rows of %d entries" % (c.size, V))
+    rr, _keep = (None, None) if rules is None else _rules([rules], 1)
+    rp, et, en = _csr(*automaton)
+    stop = np.ascontiguousarray(stop_ids, dtype=np.int32)
+    out = np.zeros(w, dtype=np.int32)
+    after = np.zeros(V, dtype=np.uint32)
+    n, fin, end = C.c_int(0), C.c_int(0), C.c_int(0)
+    _chk(lib().lnb_op_spec_automaton_accept(device, _p(a), w, V, _samplers([sampler], 1), rr, None if c is None else _p(c), int(pos0), _p(ct),
+                                            _p(stop) if stop.size else None, int(stop.size), int(rp.size) - 1, _p(rp), _p(et), _p(en), int(state0), _p(out),
+                                            C.byref(n), C.byref(fin), C.byref(end), _p(after)))
+    return out[:n.value].copy(), bool(fin.value), end.value, after
+
+
 def profile_spec_verify(logits_u16, sampler, rules, counts, pos0, col_tokens, iters, device=0):
     """average device ms of a verify pass's token launch alone on these rows (lnb_profile_spec_verify): under `rules`, or the plain sampling launch (None)"""
     a = np.ascontiguousarray(logits_u16, dtype=np.uint16)
@@ -1617,6 +1681,19 @@ def profile_spec_verify(logits_u16, sampler, rules, counts, pos0, col_tokens, it
     ms = C.c_float(0)
     _chk(lib().lnb_profile_spec_verify(device, _p(a), a.shape[0], a.shape[1], _samplers([sampler], 1), rr, None if c is None else _p(c), int(pos0), _p(ct), int(iters),
                                        C.byref(ms)))
+    return ms.value
+
+
+def profile_spec_automaton_verify(logits_u16, sampler, rules, counts, pos0, col_tokens, automaton, state0, iters, device=0):
+    """the same for the verify launch under automaton = (row_ptr, edge_token, edge_next), column 0 in state0 (lnb_profile_spec_automaton_verify)"""
+    a = np.ascontiguousarray(logits_u16, dtype=np.uint16)
+    ct = np.ascontiguousarray(col_tokens, dtype=np.int32)
+    c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+    rr = None if rules is None else _rules([rules], 1)[0]
+    rp, et, en = _csr(*automaton)
+    ms = C.c_float(0)
+    _chk(lib().lnb_profile_spec_automaton_verify(device, _p(a), a.shape[0], a.shape[1], _samplers([sampler], 1), rr, None if c is None else _p(c), int(pos0), _p(ct),
+                                                 int(rp.size) - 1, _p(rp), _p(et), _p(en), int(state0), int(iters), C.byref(ms)))
     return ms.value
 
 

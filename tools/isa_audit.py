@@ -201,7 +201,10 @@ def main(asm_path=None):
                      "_Z18emit_sample_kernelILb1ELb1EEv13EmitTokParams", "_Z23emit_spec_commit_kernelILb0EEv14EmitSpecParams", "_Z23emit_spec_commit_kernelILb1EEv14EmitSpecParams",
                      # (lnb_automaton.h: the rules form of sample_block with the masked row load -- sample_dfa_kernel<BATCH> 9 / 5 scalars in VGPR lanes, 128 VGPRs,
                      # 17176 bytes of LDS; what the transition needs waits in the LDS; scratch 0, vgpr_spill_count 0)
-                     "_Z17sample_dfa_kernelILb0EEv12DfaTokParams", "_Z17sample_dfa_kernelILb1EEv12DfaTokParams")
+                     "_Z17sample_dfa_kernelILb0EEv12DfaTokParams", "_Z17sample_dfa_kernelILb1EEv12DfaTokParams",
+                     # (lnb_spec_automaton.h: the same row load with the draft delta beside the mask -- spec_sample_dfa_commit_kernel 17 scalars in VGPR lanes, 128 VGPRs,
+                     # 17224 bytes of LDS; scratch 0, vgpr_spill_count 0)
+                     "_Z29spec_sample_dfa_commit_kernel13SpecDfaParams")
     spills, cur = [], ""
     for l in txt:
         mname = re.search(r"\.name:\s+(\S+)", l)
