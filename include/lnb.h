@@ -656,8 +656,8 @@ int lnb_profile_sample_rules(lnb_ctx* c, const lnb_sampler* sampler, const lnb_l
  * Honoured by lnb_decode_sample_until, lnb_decode_sample_rules_until and their batch forms (members without an automaton are untouched in the same
  *   launch), through token launches and captured graphs of their own: a context without an automaton launches and captures exactly what it did.
  * Refused while attached, naming lnb_ctx_set_automaton, before any cache is written: the greedy loops (use temperature 0 through the sampling call),
- *   every speculative call but lnb_decode_speculative_automaton_until below (the _many decode calls among them; lnb_forward_append_many samples nothing and
- *   stays open), pipeline ticks, a context with lnb_ctx_set_emitted_probs or lnb_ctx_set_token_probs on, and a call whose context is already in a final
+ *   every speculative call but lnb_decode_speculative_automaton_until and lnb_decode_speculative_automaton_many below (the three other _many decode calls
+ *   among them; lnb_forward_append_many samples nothing and stays open), pipeline ticks, a context with lnb_ctx_set_emitted_probs or lnb_ctx_set_token_probs on, and a call whose context is already in a final
  *   state.  Those, and any grammar compiler, are out of scope.
  * lnb_op_sample_automaton: the kernel on host rows, as lnb_op_sample_rules (rules NULL: all off), row i in state states[i]; next_states_out[i] = the
  *   state behind tokens_out[i] (states[i] itself for token -1). */
@@ -693,8 +693,9 @@ int lnb_op_sample_automaton(int device, const uint16_t* logits_bf16, int rows, i
  *   drops or recaptures another.  A pass whose filtered draft is empty replays the context's automaton one-token graph; max_draft 0 runs the sampling loop
  *   itself.  lnb_ctx_set_draft_branches is ignored: the chain is drafted.
  *   Refused, each with a message, before any cache is written: a context without an automaton; lnb_ctx_set_emitted_probs or lnb_ctx_set_token_probs on; a
- *   context already in a final state; whatever lnb_decode_speculative_sample_rules_until refuses.  Every other speculative call still refuses a context that
- *   holds an automaton.  Out of scope: the _many forms, the tree of drafts, emitted-token records and pipeline ticks under an automaton.
+ *   context already in a final state; whatever lnb_decode_speculative_sample_rules_until refuses.  Every other speculative call but
+ *   lnb_decode_speculative_automaton_many (below, behind the rules _many call) still refuses a context that holds an automaton.  Out of scope: the tree of
+ *   drafts, emitted-token records and pipeline ticks under an automaton.
  * lnb_op_automaton_draft (a test aid, as lnb_op_ngram_draft): the filter on host arrays -- draft [n_draft <= max_draft] walked from state0, no decode limits
  *   -> out [max_draft], *n_out = the kept and extended tokens, col_state [max_draft + 1] = s_0 .. s_k.
  * lnb_op_spec_automaton_accept (a test aid, as lnb_op_spec_sample_rules_accept; rules NULL: all off): the verify launch on host rows with column 0 in state0;
@@ -814,7 +815,40 @@ int lnb_op_spec_sample_rules_accept(int device, const uint16_t* logits_bf16 /* [
                                     const lnb_logit_rules* rules, const uint32_t* counts /* [V] or NULL */, int pos0, const int32_t* col_tokens /* [w] */,
                                     const int32_t* stop_ids, int n_stop, int32_t* emitted /* [w] */, int* n_emitted, int* finished,
                                     uint32_t* counts_out /* [V] or NULL */);
-/* measurement aid: average HIP-event time of a verify pass's token launch alone on host rows (as the op above): spec_sample_rules_commit_kernel under
+/* ---- speculative decoding of many contexts under token automata ----
+ * lnb_decode_speculative_automaton_many: lnb_decode_speculative_sample_rules_many for members that hold a token automaton (lnb_ctx_set_automaton: the
+ *   automaton and the start state are the ones on the context) or none -- a member without one runs the rules column unmasked, as in
+ *   lnb_batch_decode_sample_rules_until.  Per pass and member the rule is lnb_decode_speculative_automaton_until's: the member's n-gram chain is walked
+ *   through its automaton on the device (a forbidden token cuts in front of it, a final state behind it, forced tokens are appended up to max_draft,
+ *   max_steps - n_out - 1 and seq_len - pos - 1, with or without an n-gram match), the grant rule runs on the extended lengths (a grant may cut a forced
+ *   run), column i of the member samples under the state s_i and the counts c_j(i) of its own earlier columns, and every emitted token moves the member's
+ *   state; a stop id or a final state finishes the member, which leaves later passes.
+ *   Per member s, out_tokens, n_generated[s], finished[s], the end state (lnb_ctx_automaton_state), the occurrence table and the KV rows
+ *   [0, start_pos[s] + n_generated[s]) of every layer are bit-identical to lnb_decode_sample_rules_until on a context with the same rows, automaton, start
+ *   state, sampler, rules and counted text -- with rules NULL (all off; counted and n_counted are then not read), to lnb_decode_sample_until -- whatever the
+ *   draft settings, the corpora, col_budget, the other members or the chunking.  stats[s].drafted counts the columns behind the filter and the grant.
+ *   lnb_ctx_set_draft_branches is ignored: the chain is drafted.  lnb_model_set_many_shared_prefix works as in the other _many calls.
+ *   Refused, each with a message, before any cache is written: a member already in a final state (a skipped one, start_pos[s] < 0, is not asked);
+ *   lnb_ctx_set_emitted_probs or lnb_ctx_set_token_probs on; whatever lnb_decode_speculative_sample_rules_many refuses.  The three other _many calls keep
+ *   refusing a context that holds an automaton.
+ * lnb_op_spec_automaton_many_accept (a test aid, in the style of lnb_op_spec_automaton_accept): the verify launch on w <= 128 host rows.  Member s holds the
+ *   columns seg[2 s] .. seg[2 s] + seg[2 s + 1] (members in order, 1..16 columns each, together the pass) with samplers[s], rules[s] (rules NULL: all off),
+ *   the table counts[s] (counts or counts[s] NULL: zero), pos0[s] and its stop ids; ONE automaton given as CSR is shared by the members, member s's
+ *   column 0 in state0[s] (-1: the member holds none).  The column states are walked on the host from the column tokens; a token that cannot be walked is
+ *   an argument error -> emitted + seg[2 s] / n_emitted[s], finished[s], end_state[s] (-1: none) and counts_out + s * V (optional): the table after the commit. */
+int lnb_decode_speculative_automaton_many(lnb_ctx* const* ctxs, int n, const lnb_sampler* samplers /* [n] */,
+                                          const lnb_logit_rules* rules /* [n], or NULL: all off */, const int32_t* const* counted, const int32_t* n_counted,
+                                          const int32_t* const* history, const int32_t* n_history, const int32_t* tokens, const int32_t* start_pos,
+                                          int max_steps, int col_budget, int32_t* out_tokens, int32_t* n_generated, int32_t* finished,
+                                          lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out);
+int lnb_op_spec_automaton_many_accept(int device, const uint16_t* logits_bf16 /* [w][V] */, int w, int V, int n, const int32_t* seg /* [n][2] = {first, cols} */,
+                                      const lnb_sampler* samplers /* [n] */, const lnb_logit_rules* rules /* [n] or NULL */,
+                                      const uint32_t* const* counts /* [n] of [V], or NULL */, const int32_t* pos0 /* [n] */, const int32_t* col_tokens /* [w] */,
+                                      const int32_t* const* stop_ids /* [n] */, const int32_t* n_stop /* [n] or NULL */, int n_states, const int64_t* row_ptr,
+                                      const int32_t* edge_token, const int32_t* edge_next, const int32_t* state0 /* [n] */, int32_t* emitted /* [w] */,
+                                      int32_t* n_emitted /* [n] */, int32_t* finished /* [n] */, int32_t* end_state /* [n] */,
+                                      uint32_t* counts_out /* [n][V] or NULL */);
+/* measurement aid: average HIP-event time of a verify pass's token launch alone on host rows (as lnb_op_spec_sample_rules_accept): spec_sample_rules_commit_kernel under
  * `rules`, or spec_sample_commit_kernel (rules NULL); the repeats go on from the state the launch before left */
 int lnb_profile_spec_verify(int device, const uint16_t* logits_bf16 /* [w][V] */, int w, int V, const lnb_sampler* sampler, const lnb_logit_rules* rules,
                             const uint32_t* counts /* [V] or NULL */, int pos0, const int32_t* col_tokens /* [w] */, int iters, float* avg_ms_out);

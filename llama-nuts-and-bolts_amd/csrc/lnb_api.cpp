@@ -129,6 +129,8 @@ hipError_t lnbk_spec_many_pack(const SmPass* p, hipStream_t st);
 hipError_t lnbk_spec_many_commit(const SmPass* p, hipStream_t st);
 hipError_t lnbk_spec_many_sample_commit(const SmPass* p, hipStream_t st);
 hipError_t lnbk_spec_many_sample_rules_commit(const SmPass* p, hipStream_t st);
+hipError_t lnbk_spec_many_dfa_draft(const SmPass* p, hipStream_t st);
+hipError_t lnbk_spec_many_sample_dfa_commit(const SmPass* p, hipStream_t st);
 hipError_t lnbk_emit_summary(const TokProbParams* p, hipStream_t st);
 hipError_t lnbk_emit_sample(const EmitTokParams* p, int n, hipStream_t st);
 hipError_t lnbk_emit_spec_commit(const EmitSpecParams* p, int w, hipStream_t st);
@@ -3133,6 +3135,7 @@ struct SpecMany {
     Dev<char> dev; SmPass p{};              // (p's device arrays are carved out of dev; p.word is the device address of `word`)
     DevGrown<int32_t> text;
     Pinned<int32_t> word; Event ev, ev0, ev1;
+    Dev<int32_t> dfa;                       // lnb_decode_speculative_automaton_many (created on its first call): SmPass's col_state rows, then its nst words
 };
 struct AppendMany {
     lnb_batch* b = nullptr;                 // stream, activation buffers and logits for LNB_BATCH_MAX columns, tab / kv filled per pass (append_many_free destroys it)
@@ -3908,8 +3911,10 @@ struct RulesMany { const lnb_logit_rules* rules; const int32_t* const* counted; 
 static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_sampler* samplers, const int32_t* const* history, const int32_t* n_history,
                           const int32_t* tokens, const int32_t* start_pos, int max_steps, int col_budget,
                           int32_t* out_tokens, int32_t* n_generated, int32_t* finished,
-                          lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out, const RulesMany* rl = nullptr) {
-    const char* const name = rl ? "lnb_decode_speculative_sample_rules_many" : sampling ? "lnb_decode_speculative_sample_many" : "lnb_decode_speculative_many";
+                          lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out, const RulesMany* rl = nullptr, bool automaton = false) {
+    // automaton (lnb_decode_speculative_automaton_many alone, always with rl): a member may hold a token automaton -- every member's chain goes through
+    // spec_many_dfa_draft_kernel before the grant, and the commit launch is the one under the column states (lnb_spec_automaton_many.h)
+    const char* const name = automaton ? "lnb_decode_speculative_automaton_many" : rl ? "lnb_decode_speculative_sample_rules_many" : sampling ? "lnb_decode_speculative_sample_many" : "lnb_decode_speculative_many";
     if (sampling && !samplers) return fail("%s: null argument (samplers)", name);
     if (rl && (!rl->rules || !rl->counted || !rl->n_counted)) return fail("%s: null argument (%s)", name, !rl->rules ? "rules" : !rl->counted ? "counted" : "n_counted");
     // ---- the arguments alone: no handle is dereferenced
@@ -3937,7 +3942,13 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
     lnb_model* m = ctxs[0]->m;
     for (int s = 0; s < n; s++) if (ctxs[s]->m != m) return fail("%s: context %d belongs to another lnb_model handle", name, s);
     if (!m->first() || !m->last()) return fail("%s needs a whole-model handle: pipeline stages have no speculative decoding", name);
-    for (int s = 0; s < n; s++) if (dfa_refuse(ctxs[s], name)) return -1;
+    for (int s = 0; s < n; s++) {
+        if (!automaton) { if (dfa_refuse(ctxs[s], name)) return -1; continue; }
+        if (!ctxs[s]->dfa) continue;                         // (legal, as in lnb_batch_decode_sample_rules_until: it runs the rules column unmasked)
+        char who[96];
+        snprintf(who, sizeof who, "%s: member %d: ", name, s);
+        if (automaton_call_check(ctxs[s], who, start_pos[s] < 0)) return -1;
+    }
     if (batch_shape_check(m, name)) return -1;
     if (sampling && sample_vocab_check(m->a.vocab_size)) return -1;
     const int V = m->a.vocab_size, cap = ctxs[0]->attn_short_cap;
@@ -3972,6 +3983,8 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
     AppendMany* am = m->am; lnb_batch* b = am->b; hipStream_t st = b->stream;
     if (spec_many_alloc(am)) return -1;
     SpecMany* sm = am->sm;
+    constexpr size_t dfa_words = (size_t)LNB_BATCH_MAX * (LNB_SPEC_MAX_DRAFT + 1) + LNB_BATCH_MAX;
+    if (automaton && !sm->dfa) { HIPCHK(dev_alloc(sm->dfa, dfa_words * 4)); HIPCHK(hipMemsetAsync(sm->dfa, 0, dfa_words * 4, st)); }
     if (many_shared_begin(m, b, name, ctxs, n, start_pos, budget, std::max(need_T, 1))) return -1;
     if (b->many_shared) any_long = false;                    // (the ragged form serves every capacity: the long-context pair does not run)
     if (any_long && (budget > am->scratch_n || need_T > am->scratch_T)) {
@@ -3996,6 +4009,7 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
           if (s >= n || start_pos[s] < 0) continue;
           SmMember& e = smm[s];
           e.st = c->st; e.tok = c->dtok; e.log = c->dout; e.log_cap = c->dout_cap; e.seq_len = c->seq_len; e.active = 1;
+          e.dfa = automaton && c->dfa ? c->d_dfa.get() : nullptr;
           e.text = sm->text + t0; e.n_text = n_history[s] + 1;
           if (n_history[s] > 0) memcpy(text.data() + t0, history[s], (size_t)n_history[s] * 4);
           text[t0 + n_history[s]] = tokens[s];
@@ -4026,10 +4040,15 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
     SmPass sp = sm->p; sp.n = n; sp.max_steps = max_steps; sp.budget = budget; sp.n_levels = n_levels; sp.logits = b->logits; sp.V = V;
     if (sampling) sp.etab = m->prob_etab; else sp.smp = nullptr;
     if (!rl) sp.rules = nullptr;
+    if (automaton) { sp.col_state = sm->dfa; sp.nst = sm->dfa + (size_t)LNB_BATCH_MAX * (LNB_SPEC_MAX_DRAFT + 1); }
+    auto draft_and_pack = [&]() {                            // every member's chain, under an automaton filtered and extended, then the grant rule: no host round trip between them
+        hipError_t e = lnbk_spec_many_draft(&sp, st);
+        if (e == hipSuccess && automaton) e = lnbk_spec_many_dfa_draft(&sp, st);
+        return e != hipSuccess ? e : lnbk_spec_many_pack(&sp, st);
+    };
     lnb_spec_many_info inf{};
     HIPCHK(hipEventRecord(sm->ev0, st));
-    HIPCHK(lnbk_spec_many_draft(&sp, st));
-    HIPCHK(lnbk_spec_many_pack(&sp, st));
+    HIPCHK(draft_and_pack());
     HIPCHK(hipEventRecord(sm->ev, st));
     for (;;) {
         // the one host round trip of a pass: the pack kernel's block {width, any_draft, running members, largest seq_len of a running member}
@@ -4048,9 +4067,8 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
         HIPCHK(lnbk_append_many_setup(&ap, st));
         if (enqueue_batch_pass(b)) return -1;
         sp.width = width;
-        HIPCHK(rl ? lnbk_spec_many_sample_rules_commit(&sp, st) : sampling ? lnbk_spec_many_sample_commit(&sp, st) : lnbk_spec_many_commit(&sp, st));
-        HIPCHK(lnbk_spec_many_draft(&sp, st));
-        HIPCHK(lnbk_spec_many_pack(&sp, st));
+        HIPCHK(automaton ? lnbk_spec_many_sample_dfa_commit(&sp, st) : rl ? lnbk_spec_many_sample_rules_commit(&sp, st) : sampling ? lnbk_spec_many_sample_commit(&sp, st) : lnbk_spec_many_commit(&sp, st));
+        HIPCHK(draft_and_pack());
         HIPCHK(hipEventRecord(sm->ev, st));
         inf.passes++; inf.verify_passes += any ? 1 : 0; inf.columns += width; inf.max_columns = std::max<int64_t>(inf.max_columns, width); inf.long_passes += lng ? 1 : 0; m->msp_passes += b->many_shared ? 1 : 0;
     }
@@ -4061,6 +4079,8 @@ static int spec_many_impl(bool sampling, lnb_ctx* const* ctxs, int n, const lnb_
         HIPCHK(hipMemcpyAsync(&hs[s], ctxs[s]->st, sizeof(StepState), hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipMemcpyAsync(hst.data(), sm->p.stats, (size_t)n * sizeof(SmStats), hipMemcpyDeviceToHost, st));
+    if (automaton) for (int s = 0; s < n; s++) if (start_pos[s] >= 0 && ctxs[s]->dfa)                // (the host mirror, as decode_greedy_impl reads it back)
+        HIPCHK(hipMemcpyAsync(&ctxs[s]->dfa_state, &ctxs[s]->d_dfa.get()->state, 4, hipMemcpyDeviceToHost, st));
     int32_t err = 0;
     HIPCHK(hipMemcpyAsync(&err, b->derr, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -4096,6 +4116,19 @@ extern "C" int lnb_decode_speculative_sample_rules_many(lnb_ctx* const* ctxs, in
                                                         lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out) {
     const RulesMany rl{rules, counted, n_counted};
     return spec_many_impl(true, ctxs, n, samplers, history, n_history, tokens, start_pos, max_steps, col_budget, out_tokens, n_generated, finished, stats, info, ms_out, &rl);
+}
+// the same call for members that hold a token automaton or none (include/lnb.h): every member's tokens and end state are those of its own
+// lnb_decode_sample_rules_until (rules NULL: of lnb_decode_sample_until) under its automaton; all-off rules stand in for none, as in the sampling loops
+extern "C" int lnb_decode_speculative_automaton_many(lnb_ctx* const* ctxs, int n, const lnb_sampler* samplers, const lnb_logit_rules* rules,
+                                                     const int32_t* const* counted, const int32_t* n_counted, const int32_t* const* history, const int32_t* n_history,
+                                                     const int32_t* tokens, const int32_t* start_pos, int max_steps, int col_budget,
+                                                     int32_t* out_tokens, int32_t* n_generated, int32_t* finished,
+                                                     lnb_spec_stats* stats, lnb_spec_many_info* info, float* ms_out) {
+    static const lnb_logit_rules rules_off = {1.0f, 0.0f, 0.0f, 0.0f, 0, 0, nullptr, nullptr};
+    const size_t N = n >= 1 && n <= LNB_BATCH_MAX ? (size_t)n : 1;       // (n itself is refused below, by name)
+    const std::vector<lnb_logit_rules> off_rules(N, rules_off); const std::vector<const int32_t*> off_counted(N, nullptr); const std::vector<int32_t> off_n(N, 0);
+    const RulesMany rl = rules ? RulesMany{rules, counted, n_counted} : RulesMany{off_rules.data(), off_counted.data(), off_n.data()};
+    return spec_many_impl(true, ctxs, n, samplers, history, n_history, tokens, start_pos, max_steps, col_budget, out_tokens, n_generated, finished, stats, info, ms_out, &rl, true);
 }
 
 // ---- layer-sharded pipeline: the exchange behind the C ABI ---------------------------------------------------------------------
@@ -5011,6 +5044,109 @@ extern "C" int lnb_op_spec_automaton_accept(int device, const uint16_t* logits_b
     const DfaOp dfa{n_states, row_ptr, edge_token, edge_next, state0, end_state};
     return spec_rules_accept_impl(device, logits_bf16, w, V, sampler, rules ? rules : &off, counts, pos0, col_tokens, stop_ids, n_stop, emitted, n_emitted,
                                   finished, counts_out, false, 0, nullptr, &dfa);
+}
+// spec_many_sample_dfa_commit_kernel on host rows (test aid, in the style of lnb_op_spec_automaton_accept): one pass of w columns, member s holding columns
+// seg[2 s] .. + seg[2 s + 1] with its own sampler, rules (NULL: all off), table counts[s] (NULL: zero), pos0[s] and stop ids, under ONE automaton given as
+// CSR and shared by the members, member s's column 0 in state0[s] (-1: the member holds none) -- the column states are walked on the host from the column
+// tokens -> per member: emitted + seg[2 s] .. / n_emitted[s], finished[s], end_state[s] (-1: none) and, in counts_out + s * V (optional), its table after the commit
+extern "C" int lnb_op_spec_automaton_many_accept(int device, const uint16_t* logits_bf16, int w, int V, int n, const int32_t* seg, const lnb_sampler* samplers,
+                                                 const lnb_logit_rules* rules, const uint32_t* const* counts, const int32_t* pos0, const int32_t* col_tokens,
+                                                 const int32_t* const* stop_ids, const int32_t* n_stop, int n_states, const int64_t* row_ptr, const int32_t* edge_token,
+                                                 const int32_t* edge_next, const int32_t* state0, int32_t* emitted, int32_t* n_emitted, int32_t* finished,
+                                                 int32_t* end_state, uint32_t* counts_out) {
+    const char* const name = "lnb_op_spec_automaton_many_accept";
+    if (!logits_bf16 || !seg || !samplers || !pos0 || !col_tokens || !state0 || !emitted || !n_emitted || !finished || !end_state) return fail("%s: null argument", name);
+    if (w < 1 || w > LNB_BATCH_MAX || n < 1 || n > w) return fail("%s: a pass has 1..%d columns and 1..w members (got w %d, n %d)", name, LNB_BATCH_MAX, w, n);
+    if (sample_vocab_check(V)) return -1;
+    if (automaton_host_check(name, n_states, row_ptr, edge_token, edge_next)) return -1;
+    const lnb_logit_rules off = {1.0f, 0.0f, 0.0f, 0.0f, 0, 0, nullptr, nullptr};
+    constexpr int CS = LNB_MAX_DRAFT + 1;
+    std::vector<int32_t> col_state((size_t)LNB_BATCH_MAX * CS, 0);
+    std::vector<AmRow> rows(w);
+    for (int i = 0; i < w; i++) if (col_tokens[i] < 0 || col_tokens[i] >= V) return fail("%s: column token %d at index %d is outside the vocabulary [0, %d)", name, col_tokens[i], i, V);
+    int next = 0;
+    for (int s = 0; s < n; s++) {
+        char who[96];
+        snprintf(who, sizeof who, "%s: member %d: ", name, s);
+        const int first = seg[2 * s], cols = seg[2 * s + 1];
+        if (first != next || cols < 1 || cols > CS || first + cols > w) return fail("%sits columns {%d, %d} must follow the member before it, 1..%d of them inside the pass", who, first, cols, CS);
+        next = first + cols;
+        if (sampler_check(samplers + s, who) || rules_check(rules ? rules + s : &off, nullptr, 0, V, who)) return -1;
+        const int ns = n_stop ? n_stop[s] : 0;
+        if (pos0[s] < 0 || ns < 0 || ns > LNB_MAX_STOP_IDS || (ns > 0 && (!stop_ids || !stop_ids[s]))) return fail("%sbad arguments: pos0 %d, %d stop ids (at most %d)", who, pos0[s], ns, LNB_MAX_STOP_IDS);
+        if (state0[s] < -1 || state0[s] >= n_states) return fail("%sstate0 %d is outside [0, %d) (-1: no automaton)", who, state0[s], n_states);
+        int q = state0[s];
+        for (int i = 0; i < cols; i++) {                     // column i's state: the edge of its token out of column i - 1's
+            const int t = col_tokens[first + i];
+            if (i > 0 && q >= 0) {
+                const int32_t *e0 = edge_token + row_ptr[q], *e1 = edge_token + row_ptr[q + 1], *e = std::lower_bound(e0, e1, t);
+                const int nx = e != e1 && *e == t ? edge_next[e - edge_token] : -1;
+                if (nx < 0 || nx >= n_states) return fail("%scolumn token %d at index %d cannot be walked from state %d", who, t, first + i, q);
+                q = nx;
+            }
+            col_state[(size_t)s * CS + i] = q < 0 ? 0 : q;
+            rows[first + i] = AmRow{s, pos0[s] + i, t, i == cols - 1 ? 1 : 0};
+        }
+    }
+    if (next != w) return fail("%s: the members' columns end at %d, the pass at %d", name, next, w);
+    if (op_device(device)) return -1;
+    lnb_automaton a;
+    if (automaton_build(name, &a, V, n_states, row_ptr, edge_token, edge_next)) return -1;
+    const size_t N = n, W = w, NB = LNB_BATCH_MAX;
+    DevArena ar;
+    double* d_et = ar.alloc<double>(65536); uint16_t* d_x = ar.alloc<uint16_t>(W * V + 8); LnbSampler* d_smp = ar.alloc<LnbSampler>(N); LnbRulesDev* d_rules = ar.alloc<LnbRulesDev>(N);
+    uint32_t* d_counts = ar.alloc<uint32_t>(N * V); uint16_t* d_bias = ar.alloc<uint16_t>(N * V); LnbDfaDev* d_dfa = ar.alloc<LnbDfaDev>(N); SmMember* d_mem = ar.alloc<SmMember>(N);
+    StepState* d_st = ar.alloc<StepState>(N); AmRow* d_rows = ar.alloc<AmRow>(W); SmSeg* d_seg = ar.alloc<SmSeg>(N); int32_t* d_cs = ar.alloc<int32_t>(NB * CS);
+    int32_t* d_words = ar.alloc<int32_t>(4 * NB + 2 * NB + 1);      // token words [NB], logs [w], g [NB], nst [NB], then what spec_many_tables_ok asks for and the tickets [NB + 1]
+    HIPCHK(ar.error());
+    int32_t *d_tok = d_words, *d_log = d_words + NB, *d_g = d_words + 2 * NB, *d_nst = d_words + 3 * NB; unsigned* d_cnt = (unsigned*)(d_words + 4 * NB);
+    std::vector<double> et; prob_exp_table(et);
+    std::vector<LnbRulesDev> hr(N); std::vector<LnbDfaDev> hd(N); std::vector<SmMember> hm(N, SmMember{}); std::vector<StepState> hst(N, StepState{}); std::vector<SmSeg> hseg(N);
+    std::vector<int32_t> htok(NB, 0);
+    HIPCHK(hipMemset(d_counts, 0, N * V * 4)); HIPCHK(hipMemset(d_bias, 0, N * V * 2)); HIPCHK(hipMemset(d_words, 0, (6 * NB + 1) * 4));
+    for (int s = 0; s < n; s++) {
+        const lnb_logit_rules* r = rules ? rules + s : &off;
+        hr[s] = LnbRulesDev{r->repetition_penalty, r->presence_penalty, r->frequency_penalty, r->min_p, d_counts + (size_t)s * V, r->n_bias > 0 ? d_bias + (size_t)s * V : nullptr};
+        if (counts && counts[s]) HIPCHK(hipMemcpy(d_counts + (size_t)s * V, counts[s], (size_t)V * 4, hipMemcpyHostToDevice));
+        if (r->n_bias > 0) {
+            std::vector<uint16_t> hb((size_t)V, (uint16_t)0);
+            for (int k = 0; k < r->n_bias; k++) hb[r->bias_ids[k]] = bf_trunc_h(r->bias_values[k]);
+            HIPCHK(hipMemcpy(d_bias + (size_t)s * V, hb.data(), (size_t)V * 2, hipMemcpyHostToDevice));
+        }
+        hd[s] = LnbDfaDev{std::max(state0[s], 0), a.words, a.n_states, 0, a.mask, a.d_row_ptr, a.edge_next};
+        hseg[s] = SmSeg{seg[2 * s], seg[2 * s + 1]};
+        hst[s].pos = pos0[s]; hst[s].honour_stop = 1; hst[s].n_stop = n_stop ? n_stop[s] : 0;
+        for (int k = 0; k < hst[s].n_stop; k++) hst[s].stop[k] = stop_ids[s][k];
+        htok[s] = col_tokens[seg[2 * s]];
+        SmMember& e = hm[s];
+        e.st = d_st + s; e.tok = d_tok + s; e.log = d_log + seg[2 * s]; e.log_cap = seg[2 * s + 1]; e.active = 1; e.dfa = state0[s] >= 0 ? d_dfa + s : nullptr;
+    }
+    HIPCHK(hipMemcpy(d_et, et.data(), 65536 * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_x, logits_bf16, W * V * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_smp, samplers, N * sizeof(LnbSampler), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_rules, hr.data(), N * sizeof(LnbRulesDev), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_dfa, hd.data(), N * sizeof(LnbDfaDev), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_mem, hm.data(), N * sizeof(SmMember), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_st, hst.data(), N * sizeof(StepState), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_rows, rows.data(), W * sizeof(AmRow), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_seg, hseg.data(), N * sizeof(SmSeg), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_cs, col_state.data(), NB * CS * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_tok, htok.data(), NB * 4, hipMemcpyHostToDevice));
+    SmPass p{};
+    p.members = d_mem; p.n = n; p.max_steps = CS; p.budget = LNB_BATCH_MAX; p.n_levels = 1; p.rows = d_rows; p.seg = d_seg; p.g = d_g; p.cnt = d_cnt;
+    p.want = p.running = p.draft = d_g; p.best = (int*)d_g; p.stats = (SmStats*)d_g; p.word = d_g;       // (the draft and pack kernels' tables: the commit reads none of them)
+    p.logits = d_x; p.V = V; p.width = w; p.smp = d_smp; p.etab = d_et; p.rules = d_rules; p.col_state = d_cs; p.nst = d_nst;
+    HIPCHK(lnbk_spec_many_sample_dfa_commit(&p, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(hst.data(), d_st, N * sizeof(StepState), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hd.data(), d_dfa, N * sizeof(LnbDfaDev), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(emitted, d_log, W * 4, hipMemcpyDeviceToHost));
+    if (counts_out) HIPCHK(hipMemcpy(counts_out, d_counts, N * V * 4, hipMemcpyDeviceToHost));
+    for (int s = 0; s < n; s++) {
+        if (hst[s].n_out < 1 || hst[s].n_out > seg[2 * s + 1]) return fail("%s: internal error: member %d's %d columns emitted %d tokens", name, s, seg[2 * s + 1], hst[s].n_out);
+        n_emitted[s] = hst[s].n_out; finished[s] = hst[s].finished; end_state[s] = state0[s] >= 0 ? hd[s].state : -1;
+    }
+    return 0;
 }
 // dfa_draft_kernel on host arrays (test aid, as lnb_op_ngram_draft): the draft `draft` [n_draft] walked from state0 of the automaton given as CSR, cut and
 // extended up to max_draft tokens, with no decode limits -> out [max_draft] / *n_out and col_state [max_draft + 1] (col_state[0] = state0)

@@ -14,9 +14,9 @@
 // LDS: the mask row is a static array of LNB_SAMPLE_MAX_V / 8 = 16384 bytes BESIDE sample_block's own SampleSh (712 bytes, untouched) and the end struct
 // (80 bytes): 17176 bytes per workgroup at V = 131072 and at every smaller V.  tools/isa_audit.py: 128 VGPRs, no scratch, no VGPR spill, 9 / 5 scalars
 // parked in lanes (the other sample_block kernels park 4 .. 18).
-// The speculative loop under an automaton (lnb_decode_speculative_automaton_until: the draft filter and the verify launch) is lnb_spec_automaton.h.
-// Out of scope: the other speculative calls (the _many forms, the tree of drafts), the emitted-token records and pipeline ticks under an automaton, and any
-// grammar compiler.
+// The speculative loop under an automaton (lnb_decode_speculative_automaton_until: the draft filter and the verify launch) is lnb_spec_automaton.h, its
+// many-context form (lnb_decode_speculative_automaton_many) lnb_spec_automaton_many.h.
+// Out of scope: the other speculative calls (the tree of drafts), the emitted-token records and pipeline ticks under an automaton, and any grammar compiler.
 #pragma once
 
 constexpr int LNB_DFA_MASK_WORDS = LNB_SAMPLE_MAX_V / 32;

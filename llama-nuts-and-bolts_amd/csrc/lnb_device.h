@@ -448,6 +448,7 @@ struct SmMember {
     const int32_t* text; const int32_t* corpus;            // its running text's head (history ++ token) and its corpus (lnb_ctx_set_draft)
     int32_t log_cap, n_text, n_corpus, ngram_min, ngram_max, max_draft, seq_len;
     int32_t active;                                        // 0: skipped by the caller (start_pos < 0): nothing of it is read or written
+    LnbDfaDev* dfa;                                        // lnb_decode_speculative_automaton_many: the member's automaton view (its state word), nullptr = it holds none
 };
 struct SmSeg { int32_t first, cols; };                     // a member's columns of the pass: [first, first + cols); cols 0 = it has none
 struct SmStats { int32_t passes, verify_passes, drafted, pad; };
@@ -464,4 +465,8 @@ struct SmPass {                                            // the launches aroun
     const uint16_t* logits; int32_t V, width;              // commit: the pass's logits and width as the host launched it
     const struct LnbSampler* smp; const double* etab;      // spec_many_sample_commit_kernel: [LNB_BATCH_MAX] the members' samplers, the model's exp table (the greedy call: both null)
     const struct LnbRulesDev* rules;                       // spec_many_sample_rules_commit_kernel: [LNB_BATCH_MAX] the members' rules, each with ITS context's two tables (else null)
+    // lnb_decode_speculative_automaton_many (lnb_spec_automaton_many.h; else both null): member s's row of column states, [LNB_SPEC_MAX_DRAFT + 1] words indexed by
+    // the member's OWN column, and the state behind every column's token, indexed by the pass's column
+    int32_t* col_state;                                    // [LNB_BATCH_MAX][LNB_SPEC_MAX_DRAFT + 1]
+    int32_t* nst;                                          // [LNB_BATCH_MAX]
 };

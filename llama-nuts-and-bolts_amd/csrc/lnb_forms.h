@@ -86,6 +86,9 @@
     /* ... and in the speculative loop under one (lnb_decode_speculative_automaton_until; lnb_spec_automaton.h) */ \
     X(SAMPLE_SPEC_DFA, "sample.spec_dfa", "spec_sample_dfa_commit_kernel: one workgroup per column of a verify pass under an automaton, its column state's mask row in the LDS beside the draft delta; the last one accepts, emits, counts and moves the state") \
     X(DRAFT_DFA, "draft.dfa", "dfa_draft_kernel: one workgroup walks the n-gram draft through the automaton, cuts it at a forbidden token or a final state and extends it by forced tokens") \
+    /* ... and for many contexts per pass (lnb_decode_speculative_automaton_many; lnb_spec_automaton_many.h) */ \
+    X(SAMPLE_SPEC_MANY_DFA, "sample.spec_many_dfa", "spec_many_sample_dfa_commit_kernel: the same per column of a many-context pass, each member with its own automaton and column states or none; the last one accepts, emits, counts and moves every member's state") \
+    X(DRAFT_DFA_MANY, "draft.dfa_many", "spec_many_dfa_draft_kernel: one workgroup per member walks that member's n-gram draft through its automaton, cuts it and extends it by forced tokens, in front of the grant rule") \
     /* the emitted token's record (lnb_ctx_set_emitted_probs; lnb_emit_probs.h): never launched while the switch is off */ \
     X(EMIT_SUMMARY, "emit.summary", "token_probs_kernel<KT, PARK>: the row summary launch -- the raw row's top k into the record slot (a verify pass: all columns at once into the pass scratch), the row's Z state parked for the token launch") \
     X(EMIT_ROW, "emit.row", "emit_sample_kernel<RULES, false>: the one-token sampling (rules) step with the emitted entry, rows of lnb_op_emitted_probs") \

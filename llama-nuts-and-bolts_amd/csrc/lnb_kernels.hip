@@ -5949,3 +5949,5 @@ extern "C" hipError_t lnbk_spec_many_sample_rules_commit(const SmPass* p, hipStr
     hipLaunchKernelGGL(spec_many_sample_rules_commit_kernel, dim3((unsigned)p->width), dim3(1024), 0, st, *p);
     return hipGetLastError();
 }
+// lnb_decode_speculative_automaton_many: the same pass with every member's draft filtered by its automaton and the commit under the column states
+#include "lnb_spec_automaton_many.h"

@@ -47,40 +47,47 @@ DEVINL unsigned dfa_row_count(const uint32_t* row, int words, int lim, DfaDraftS
     *one = tt;
     return c;
 }
+DEVINL bool dfa_final(const LnbDfaDev& d, int q) { return d.row_ptr[q + 1] == d.row_ptr[q]; }
+// Walk and extend, one rule for dfa_draft_kernel and spec_many_dfa_draft_kernel (lnb_spec_automaton_many.h): the chain d_1 .. d_k (d_i = tok1[i - 1]) from
+// the non-final state s, extended up to lim tokens -> the k behind the filter; thread 0 writes the forced tokens, col_state[1 .. k] and, with col_st, the
+// extended columns' positions pos + i.  Uniform: every lane reads the same words.
+DEVINL int dfa_filter_chain(const LnbDfaDev& d, int s, int32_t* tok1, int k, int lim, int32_t* col_state, StepState* col_st, int pos, DfaDraftSh& sh) {
+    const bool t0 = threadIdx.x == 0;
+    int par = 0, one = -1, kept = 0;
+    for (int i = 1; i <= k; i++) {
+        const int t = tok1[i - 1];
+        const uint32_t* row = d.mask + (size_t)s * d.words;
+        if ((unsigned)t >= (unsigned)d.words * 32u || !((row[t >> 5] >> (t & 31)) & 1u)) break;      // (the bits behind V are zero: dfa_build_kernel)
+        const unsigned rank = dfa_row_count(row, d.words, t, sh, par, &one);
+        s = d.edge_next[d.row_ptr[s] + (long long)rank];
+        kept = i;
+        if (t0) col_state[i] = s;
+        if (dfa_final(d, s)) break;
+    }
+    k = kept;
+    while (k < lim && !dfa_final(d, s)) {
+        if (dfa_row_count(d.mask + (size_t)s * d.words, d.words, d.words * 32, sh, par, &one) != 1u) break;
+        s = d.edge_next[d.row_ptr[s]];
+        k++;
+        if (t0) {
+            tok1[k - 1] = one; col_state[k] = s;
+            if (col_st) col_st[k].pos = pos + k;
+        }
+    }
+    return k;
+}
 __global__ __launch_bounds__(1024) void dfa_draft_kernel(DfaDraftParams p) {
     __shared__ DfaDraftSh sh;
     const LnbDfaDev d = *p.dfa;
     const bool t0 = threadIdx.x == 0;
-    int par = 0, one = -1;
-    int s = d.state, k = p.word_in[0];
+    int k = p.word_in[0];
     const int n_out = p.word_in[1], fin = p.word_in[2];
-    auto final_state = [&](int q) { return d.row_ptr[q + 1] == d.row_ptr[q]; };
-    if (t0) p.col_state[0] = s;
-    if (!fin && !final_state(s)) {                           // (everything below is uniform: every lane reads the same words)
-        int kept = 0;
-        for (int i = 1; i <= k; i++) {
-            const int t = p.tok[i];
-            const uint32_t* row = d.mask + (size_t)s * d.words;
-            if ((unsigned)t >= (unsigned)d.words * 32u || !((row[t >> 5] >> (t & 31)) & 1u)) break;      // (the bits behind V are zero: dfa_build_kernel)
-            const unsigned rank = dfa_row_count(row, d.words, t, sh, par, &one);
-            s = d.edge_next[d.row_ptr[s] + (long long)rank];
-            kept = i;
-            if (t0) p.col_state[i] = s;
-            if (final_state(s)) break;
-        }
-        k = kept;
+    if (t0) p.col_state[0] = d.state;
+    if (!fin && !dfa_final(d, d.state)) {
         const int pos = p.st ? p.st->pos : 0;
         int lim = p.max_draft < LNB_SPEC_MAX_DRAFT ? p.max_draft : LNB_SPEC_MAX_DRAFT;
         if (p.st) lim = min(lim, min(p.max_steps - n_out - 1, p.seq_len - pos - 1));
-        while (k < lim && !final_state(s)) {
-            if (dfa_row_count(d.mask + (size_t)s * d.words, d.words, d.words * 32, sh, par, &one) != 1u) break;
-            s = d.edge_next[d.row_ptr[s]];
-            k++;
-            if (t0) {
-                p.tok[k] = one; p.col_state[k] = s;
-                if (p.col_st) p.col_st[k].pos = pos + k;
-            }
-        }
+        k = dfa_filter_chain(d, d.state, p.tok + 1, k, lim, p.col_state, p.col_st, pos, sh);
     }
     if (t0) { p.word[0] = k; p.word[1] = n_out; p.word[2] = fin; }
 }

@@ -103,7 +103,9 @@ __global__ __launch_bounds__(LNB_BATCH_MAX) void spec_many_pack_kernel(SmPass p)
 // what the last workgroup's thread s does for member s (shared by spec_many_commit_kernel and spec_many_sample_commit_kernel: p.g holds the columns'
 // argmax or the samplers' tokens, the loop is the same)
 // counts (optional): member s's occurrence table under logit rules -- every emitted token is counted, as spec_accept_emit does
-DEVINL void spec_many_accept_emit(const SmPass& p, int s, uint32_t* counts = nullptr) {
+// nst (optional; lnb_spec_automaton_many.h): the state n_c behind every column's token -- an emitted token >= 0 of a member that holds an automaton moves its
+// state word to that column's n_c, and a final n_c (an empty row) finishes the member as a stop id does; a rejected column's n_c is never read
+DEVINL void spec_many_accept_emit(const SmPass& p, int s, uint32_t* counts = nullptr, const int32_t* nst = nullptr) {
     if (s >= p.n || s >= LNB_BATCH_MAX) return;
     const SmSeg sg = p.seg[s];
     if (sg.cols <= 0 || sg.first < 0 || sg.first + sg.cols > p.width || p.width > LNB_BATCH_MAX) return;
@@ -122,6 +124,11 @@ DEVINL void spec_many_accept_emit(const SmPass& p, int s, uint32_t* counts = nul
         if (counts && t >= 0) counts[t] += 1u;
         bool stop = false;
         if (st->honour_stop) for (int q = 0; q < st->n_stop; q++) if (t == st->stop[q]) stop = true;
+        if (nst && m.dfa && t >= 0) {
+            const int ns = nst[sg.first + i];
+            m.dfa->state = ns;
+            if (m.dfa->row_ptr[ns + 1] == m.dfa->row_ptr[ns]) stop = true;
+        }
         if (stop) { st->finished = 1; break; }
     }
 }

@@ -416,7 +416,7 @@ struct SpeculativeMany {
 // lnb_decode_speculative_sample_rules_many with rules[n] and one counted text per context
 inline SpeculativeMany decodeSpeculativeMany(const lnb_sampler* samplers, const std::vector<InferenceContext*>& ctxs, const std::vector<std::vector<TokenId>>& histories,
                                              const std::vector<TokenId>& tokens, const std::vector<int>& startPos, int maxSteps, int colBudget,
-                                             const lnb_logit_rules* rules = nullptr, const std::vector<std::vector<TokenId>>* counted = nullptr) {
+                                             const lnb_logit_rules* rules = nullptr, const std::vector<std::vector<TokenId>>* counted = nullptr, bool automaton = false) {
     const size_t n = ctxs.size(), steps = maxSteps > 0 ? (size_t)maxSteps : 1;
     if (n == 0 || histories.size() != n || tokens.size() != n || startPos.size() != n) throw std::runtime_error("DecodeSpeculativeMany: the arrays differ in length");
     std::vector<lnb_ctx*> hs;
@@ -427,7 +427,7 @@ inline SpeculativeMany decodeSpeculativeMany(const lnb_sampler* samplers, const 
     if (rules) {
         std::vector<const int32_t*> cp; std::vector<int32_t> cn;
         for (const auto& t : *counted) { cp.push_back(t.empty() ? nullptr : t.data()); cn.push_back((int32_t)t.size()); }
-        check(lnb_decode_speculative_sample_rules_many(hs.data(), (int)n, samplers, rules, cp.data(), cn.data(), hp.data(), hn.data(), tokens.data(), pos.data(), maxSteps,
+        check((automaton ? lnb_decode_speculative_automaton_many : lnb_decode_speculative_sample_rules_many)(hs.data(), (int)n, samplers, rules, cp.data(), cn.data(), hp.data(), hn.data(), tokens.data(), pos.data(), maxSteps,
                                                        colBudget, out.data(), ng.data(), fin.data(), r.Stats.data(), &r.Info, &r.Ms));
     } else if (samplers)
         check(lnb_decode_speculative_sample_many(hs.data(), (int)n, samplers, hp.data(), hn.data(), tokens.data(), pos.data(), maxSteps, colBudget, out.data(), ng.data(),
@@ -458,6 +458,15 @@ inline SpeculativeMany DecodeSpeculativeSampleRulesMany(const std::vector<Infere
     if (samplers.size() != ctxs.size() || rules.size() != ctxs.size() || counted.size() != ctxs.size() || samplers.empty())
         throw std::runtime_error("DecodeSpeculativeSampleRulesMany: one sampler, one rule set and one counted text per context");
     return decodeSpeculativeMany(samplers.data(), ctxs, histories, tokens, startPos, maxSteps, colBudget, rules.data(), &counted);
+}
+// lnb_decode_speculative_automaton_many: the same for contexts that hold a token automaton or none; every context's tokens and end state are its own sampling loop's under its automaton
+inline SpeculativeMany DecodeSpeculativeAutomatonMany(const std::vector<InferenceContext*>& ctxs, const std::vector<lnb_sampler>& samplers,
+                                                      const std::vector<lnb_logit_rules>& rules, const std::vector<std::vector<TokenId>>& counted,
+                                                      const std::vector<std::vector<TokenId>>& histories, const std::vector<TokenId>& tokens,
+                                                      const std::vector<int>& startPos, int maxSteps, int colBudget = 0) {
+    if (samplers.size() != ctxs.size() || rules.size() != ctxs.size() || counted.size() != ctxs.size() || samplers.empty())
+        throw std::runtime_error("DecodeSpeculativeAutomatonMany: one sampler, one rule set and one counted text per context");
+    return decodeSpeculativeMany(samplers.data(), ctxs, histories, tokens, startPos, maxSteps, colBudget, rules.data(), &counted, true);
 }
 
 enum GenerationState{ GSInProgress = 1, GSFinishedByReachingEOS = 2, GSFinishedByReachingSeqLen = 3 };   // inference.go:13-17

@@ -86,6 +86,7 @@ EXPORTS = [
     "lnb_ctx_set_emitted_probs", "lnb_ctx_read_emitted_probs", "lnb_ctx_emitted_probs_last", "lnb_op_emitted_probs",
     "lnb_automaton_create", "lnb_automaton_destroy", "lnb_automaton_info", "lnb_ctx_set_automaton", "lnb_ctx_automaton_state", "lnb_op_sample_automaton",
     "lnb_decode_speculative_automaton_until", "lnb_op_automaton_draft", "lnb_op_spec_automaton_accept", "lnb_profile_spec_automaton_verify",
+    "lnb_decode_speculative_automaton_many", "lnb_op_spec_automaton_many_accept",
 ]
 EPILOGUES = {"store": 0, "qkv_rope": 1, "resid": 2, "silu_mul": 3}      # EPI_* of csrc/lnb_device.h: the second index of the launch tally
 MAX_TOP_K = 16           # LNB_MAX_TOP_K of include/lnb.h (tests/test_token_probs_cpu.py compares them)
@@ -345,6 +346,9 @@ def lib():
     L.lnb_op_automaton_draft.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.POINTER(C.c_int), vp]
     L.lnb_op_spec_automaton_accept.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.POINTER(LogitRules), vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp,
                                                vp, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
+    L.lnb_decode_speculative_automaton_many.argtypes = L.lnb_decode_speculative_sample_rules_many.argtypes
+    L.lnb_op_spec_automaton_many_accept.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(Sampler), C.POINTER(LogitRules), C.POINTER(vp), vp, vp,
+                                                    C.POINTER(vp), vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lnb_profile_spec_automaton_verify.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.POINTER(LogitRules), vp, C.c_int, vp, C.c_int, vp, vp, vp,
                                                     C.c_int, C.c_int, f32p]
     L.lnb_profile_spec_verify.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(Sampler), C.POINTER(LogitRules), vp, C.c_int, vp, C.c_int, f32p]
@@ -1093,7 +1097,7 @@ def ForwardAppendMany(ctxs, token_lists, start_pos, want_logits=True):
     return [logits[e - r:e] for e, r in zip(ends, rows)], am
 
 
-def DecodeSpeculativeSampleMany(ctxs, samplers, histories, tokens, start_pos, max_steps, col_budget=0, rules=None, counted=None):
+def DecodeSpeculativeSampleMany(ctxs, samplers, histories, tokens, start_pos, max_steps, col_budget=0, rules=None, counted=None, automaton=False):
     """DecodeSpeculativeMany with one sampler per context (lnb_decode_speculative_sample_many): every context's tokens, finished flag and KV rows are the
     bits of its own decode_sample_until; a temperature-0 member is greedy.  rules (one LogitRules, argument tuple or None per member) or counted (one id
     list per member) given: lnb_decode_speculative_sample_rules_many, every member its own decode_sample_until(..., rules=, counted=) -> the same tuple"""
@@ -1101,14 +1105,21 @@ def DecodeSpeculativeSampleMany(ctxs, samplers, histories, tokens, start_pos, ma
     n = len(ctxs)
     ss = None if samplers is None else _samplers(samplers, n)
     if rules is None and counted is None:
-        return _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, True, ss)
+        return _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, True, ss, (None, None, None) if automaton else None, automaton)
     rr, _keep = _rules(rules if rules is not None else [None] * n, n)
     texts = [np.ascontiguousarray(t if t is not None else [], dtype=np.int32) for t in (counted if counted is not None else [None] * n)]
     if len(texts) != n:
         raise LnbError("DecodeSpeculativeSampleMany: %d contexts, %d counted texts" % (n, len(texts)))
     ptrs = (C.c_void_p * n)(*[t.ctypes.data if t.size else None for t in texts])
     nc = np.array([t.size for t in texts], dtype=np.int32)
-    return _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, True, ss, (rr, ptrs, nc))
+    return _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, True, ss, (rr, ptrs, nc), automaton)
+
+
+def DecodeSpeculativeAutomatonMany(ctxs, samplers, histories, tokens, start_pos, max_steps, rules=None, counted=None, col_budget=0):
+    """DecodeSpeculativeSampleMany for contexts that hold a token automaton (set_automaton) or none (lnb_decode_speculative_automaton_many): every member's
+    chain is cut and extended by its automaton's forced tokens on the device, and its tokens, finished flag, end state and KV rows are the bits of its own
+    decode_sample_until(..., rules=, counted=) under that automaton and start state -> the same tuple"""
+    return DecodeSpeculativeSampleMany(ctxs, samplers, histories, tokens, start_pos, max_steps, col_budget, rules, counted, automaton=True)
 
 
 def DecodeSpeculativeMany(ctxs, histories, tokens, start_pos, max_steps, col_budget=0):
@@ -1120,7 +1131,7 @@ def DecodeSpeculativeMany(ctxs, histories, tokens, start_pos, max_steps, col_bud
     return _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, False, None)
 
 
-def _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, sample, ss, rules=None):
+def _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_budget, sample, ss, rules=None, automaton=False):
     ctxs = list(ctxs)
     n = len(ctxs)
     hist = [np.ascontiguousarray(h, dtype=np.int32).reshape(-1) for h in histories]
@@ -1137,8 +1148,9 @@ def _decode_speculative_many(ctxs, histories, tokens, start_pos, max_steps, col_
     st = (SpecStats * n)(); info = SpecManyInfo(); ms = C.c_float(0)
     if rules is not None:
         rr, ptrs, nc = rules
-        _chk(L.lnb_decode_speculative_sample_rules_many(arr, n, ss, rr, ptrs, _p(nc), harr, _p(nh), _p(tok), _p(pos), int(max_steps), int(col_budget), _p(out),
-                                                        _p(ng), _p(fin), st, C.byref(info), C.byref(ms)))
+        call = L.lnb_decode_speculative_automaton_many if automaton else L.lnb_decode_speculative_sample_rules_many
+        _chk(call(arr, n, ss, rr, ptrs, None if nc is None else _p(nc), harr, _p(nh), _p(tok), _p(pos), int(max_steps), int(col_budget), _p(out),
+                  _p(ng), _p(fin), st, C.byref(info), C.byref(ms)))
     elif sample:
         _chk(L.lnb_decode_speculative_sample_many(arr, n, ss, harr, _p(nh), _p(tok), _p(pos), int(max_steps), int(col_budget), _p(out), _p(ng), _p(fin),
                                                   st, C.byref(info), C.byref(ms)))
@@ -1670,6 +1682,37 @@ def op_spec_automaton_accept(logits_u16, sampler, rules, counts, pos0, col_token
                                             _p(stop) if stop.size else None, int(stop.size), int(rp.size) - 1, _p(rp), _p(et), _p(en), int(state0), _p(out),
                                             C.byref(n), C.byref(fin), C.byref(end), _p(after)))
     return out[:n.value].copy(), bool(fin.value), end.value, after
+
+
+def op_spec_automaton_many_accept(logits_u16, segs, samplers, rules, counts, pos0, col_tokens, automaton, state0, stop_ids=None, device=0):
+    """spec_many_sample_dfa_commit_kernel on host rows (lnb_op_spec_automaton_many_accept): one pass of w <= 128 columns whose member s holds the columns
+    segs[s] = (first, cols) with samplers[s], rules[s] (rules None: all off), the table counts[s] (counts or counts[s] None: zero), pos0[s] and stop_ids[s],
+    under automaton = (row_ptr, edge_token, edge_next) with the member's column 0 in state0[s] (-1: it holds none)
+    -> per member a tuple (the tokens it emits, finished flag, the state after the commit or -1, its table after the commit as a uint32 array)"""
+    a = np.ascontiguousarray(logits_u16, dtype=np.uint16)
+    w, V = a.shape
+    sg = np.ascontiguousarray(segs, dtype=np.int32).reshape(-1, 2)
+    n = sg.shape[0]
+    ct = np.ascontiguousarray(col_tokens, dtype=np.int32)
+    if ct.size != w:
+        raise LnbError("%d column tokens for %d rows" % (ct.size, w))
+    cs = [None if counts is None or c is None else np.ascontiguousarray(c, dtype=np.uint32) for c in (counts if counts is not None else [None] * n)]
+    if len(cs) != n or any(c is not None and c.size != V for c in cs):
+        raise LnbError("one table of %d counts (or None) per member" % V)
+    rr, _keep = (None, None) if rules is None else _rules(rules, n)
+    rp, et, en = _csr(*automaton)
+    stops = [np.ascontiguousarray(s, dtype=np.int32) for s in (stop_ids if stop_ids is not None else [()] * n)]
+    p0, s0, ns = (np.ascontiguousarray(v, dtype=np.int32) for v in (pos0, state0, [s.size for s in stops]))
+    if len(stops) != n or p0.size != n or s0.size != n:
+        raise LnbError("one pos0, state0 and stop id list per member (%d members)" % n)
+    cptr = (C.c_void_p * n)(*[None if c is None else c.ctypes.data for c in cs])
+    sptr = (C.c_void_p * n)(*[s.ctypes.data if s.size else None for s in stops])
+    out = np.zeros(w, dtype=np.int32)
+    after = np.zeros((n, V), dtype=np.uint32)
+    ne, fin, end = (np.zeros(n, dtype=np.int32) for _ in range(3))
+    _chk(lib().lnb_op_spec_automaton_many_accept(device, _p(a), w, V, n, _p(sg), _samplers(samplers, n), rr, cptr, _p(p0), _p(ct), sptr, _p(ns), int(rp.size) - 1,
+                                                 _p(rp), _p(et), _p(en), _p(s0), _p(out), _p(ne), _p(fin), _p(end), _p(after)))
+    return [(out[f:f + ne[s]].copy(), bool(fin[s]), int(end[s]), after[s]) for s, (f, _) in enumerate(sg)]
 
 
 def profile_spec_verify(logits_u16, sampler, rules, counts, pos0, col_tokens, iters, device=0):

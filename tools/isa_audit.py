@@ -204,7 +204,10 @@ def main(asm_path=None):
                      "_Z17sample_dfa_kernelILb0EEv12DfaTokParams", "_Z17sample_dfa_kernelILb1EEv12DfaTokParams",
                      # (lnb_spec_automaton.h: the same row load with the draft delta beside the mask -- spec_sample_dfa_commit_kernel 17 scalars in VGPR lanes, 128 VGPRs,
                      # 17224 bytes of LDS; scratch 0, vgpr_spill_count 0)
-                     "_Z29spec_sample_dfa_commit_kernel13SpecDfaParams")
+                     "_Z29spec_sample_dfa_commit_kernel13SpecDfaParams",
+                     # (lnb_spec_automaton_many.h: the same two row loads, masked and unmasked, per column of a many-context pass -- spec_many_sample_dfa_commit_kernel
+                     # 35 scalars in VGPR lanes (each of the two inlined sample_block bodies parks its own), 121 VGPRs, 17344 bytes of LDS; scratch 0, vgpr_spill_count 0)
+                     "_Z34spec_many_sample_dfa_commit_kernel6SmPass")
     spills, cur = [], ""
     for l in txt:
         mname = re.search(r"\.name:\s+(\S+)", l)
